@@ -2,7 +2,7 @@
 """Throughput benchmark of the encode_images() hot path (BASELINE.json metric: images/sec FastViTHD
 encode @1024x1024 bf16).
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -12,13 +12,20 @@ With N > 1 every rank encodes its own 32 images (weak scaling, no data-path coll
 encoder) and the step ends with the single RCCL all-gather of visual tokens at the projector
 boundary.  Rank 0 prints ONE JSON line.
 
-Extra objects on that line:
+A plain run sets up, warms up, times --steps steps and prints the line; nothing else runs.
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy (float32; a fixed,
+seeded sample of the elements when the whole would exceed 60 MiB); inputs and weights are seeded,
+so two builds can be compared output for output.
+
+Extra objects on the line with --full (each --no-* switch drops one):
+  power         - package power / joules per step over the timed steps (sysfs hwmon).
   roofline      - for the dominant kernel class: algorithmic FLOPs (or bytes) per launch divided by
                   the average launch duration measured live with HIP events on the launch stream
                   (fvhd_profile_*), against the dense bf16 MFMA peak / HBM3E peak.
+  kernels       - per-class table from the same profiled pass (ms per step, launches, TF/s or GB/s).
+  ttft, c4_1gpu, c5 - the other BASELINE.json configs, a few seconds each.
   cpu_baseline  - the CPU oracle (a port of the reference's PyTorch path; the reference itself is
                   not present on the GPU box) timed on this host's cores on a bounded sample.
-  kernels       - per-class table from the same profiled pass (ms per step, launches, TF/s or GB/s).
 """
 from __future__ import annotations
 
@@ -37,6 +44,22 @@ if ROOT not in sys.path:
 
 MFMA_PEAK_TFLOPS = 2500.0     # dense bf16, MI355X_MICROARCH.md "Chip-level parameters"
 HBM_PEAK_GBS = 8000.0         # HBM3E spec, same table
+DUMP_LIMIT_BYTES = 60 << 20   # --dump-outputs: all files together stay under 64 MB
+
+
+def dump_outputs(dirname: str, arrays) -> None:
+    """Writes each tensor of `arrays` ({name: tensor}) as dirname/<name>.npy in float32.  When the whole would exceed
+    DUMP_LIMIT_BYTES, every tensor keeps the same share of its flattened elements, chosen by a fixed seed (ascending order)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total = 4 * sum(t.numel() for t in arrays.values())
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().contiguous()
+        if total > DUMP_LIMIT_BYTES:
+            keep = a.numel() * DUMP_LIMIT_BYTES // total
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, f"{name}.npy"), a.numpy())
 
 
 def algorithmic_work(B: int, R: int, hidden: int, fused: bool = True, dw_mix=None):
@@ -284,6 +307,10 @@ def main():
     ap.add_argument("--hidden", type=int, default=896, help="LLM hidden size of the projector (896 = Qwen2-0.5B)")
     ap.add_argument("--graph", action="store_true", help="hipGraph replay of the tower's interior launches (fvhd_set_graph)")
     ap.add_argument("--attn-fp8", action="store_true", help="e4m3 MFMA operands in the attention cores (BASELINE.json configs[4] as named; opt-in)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: power over the timed steps, a profiled pass (roofline, kernels), the ttft / c4_1gpu / c5 legs and the "
+                         "CPU baseline (the --no-* switches drop single ones)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--tower-only", action="store_true", help="time the vision tower without the projector")
@@ -293,14 +320,18 @@ def main():
                          "several ranks on ONE GPU (tests: RCCL refuses two ranks on one device) - never a performance number")
     ap.add_argument("--same-device", action="store_true", help="with --backend gloo: every rank uses cuda:0 (several ranks on a one-GPU box)")
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="default run: skip the `c4_1gpu` and `c5` objects (BASELINE configs[3] single-GPU leg, configs[4]) appended to the throughput line")
+                    help="--full: skip the `c4_1gpu` and `c5` objects (BASELINE configs[3] single-GPU leg, configs[4]) appended to the throughput line")
     ap.add_argument("--ttft-llm", default="kernels", choices=["kernels", "kernels-graph", "hf-graph", "hf-eager"],
                     help="--ttft: prefill on the hand-written kernels (fvhd_llm_prefill; default), the same as one hipGraph, or the stock transformers module (graph / eager)")
     ap.add_argument("--ttft", action="store_true", help="report time-to-first-token of FastVLM prefill instead (tools/ttft.py, BASELINE configs[2]; with --gpus N / "
                                                         "--hidden 3584: configs[3] - encode sharded over the ranks, RCCL all-gather at the projector boundary, data-parallel prefill)")
-    ap.add_argument("--no-ttft", action="store_true", help="default run: skip the `ttft` object (BASELINE configs[2], B = 8, Qwen2-0.5B widths) appended to the throughput line")
+    ap.add_argument("--no-ttft", action="store_true", help="--full: skip the `ttft` object (BASELINE configs[2], B = 8, Qwen2-0.5B widths) appended to the throughput line")
     ap.add_argument("--llm-layers", type=int, default=0, help="--ttft: truncate the decoder stack to this many layers (tests; 0 = the published depth)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.ttft and args.dump_outputs:
+        ap.error("--dump-outputs writes the throughput path's outputs; it does not apply to --ttft")
     args.batch_given = any(a == "--batch" or a.startswith("--batch=") for a in sys.argv[1:])
 
     t_start = time.perf_counter()
@@ -396,7 +427,7 @@ def main():
     if multi:
         dist.barrier()
     torch.cuda.synchronize()
-    power = PowerSampler(local_rank) if rank == 0 else None
+    power = PowerSampler(local_rank) if rank == 0 and args.full else None
     if power:
         power.start()
     t0 = time.perf_counter()
@@ -410,6 +441,9 @@ def main():
     power_obj = power.finish(dt, args.steps) if power else None
     trace("timed region done")
     assert torch.isfinite(out.float()).all()
+    if rank == 0 and args.dump_outputs:          # every rank holds the same gathered tokens at N > 1
+        dump_outputs(args.dump_outputs, {"tower_features" if args.tower_only else "image_features": out})
+        trace("outputs written")
     if multi:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -432,9 +466,10 @@ def main():
                    **({"collective": f"all_gather_into_tensor over {'nccl (RCCL)' if args.backend == 'nccl' else 'gloo (host-staged; test only)'}, world {world}",
                        "gather_side": side} if multi else {})},
     }
-    result["power"] = power_obj      # package power / joules per step over the timed region (None without hwmon access)
+    if args.full:
+        result["power"] = power_obj      # package power / joules per step over the timed region (None without hwmon access)
 
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         ctx = tower._context()
         ctx.profile_enable(True)
         ctx.profile_reset()
@@ -499,7 +534,7 @@ def main():
         tot_fl = sum(v[0] for v in work.values())
         result["whole_step_tflops"] = round(tot_fl / (dt / args.steps) / 1e12, 1)
 
-    if rank == 0 and world == 1 and not args.no_ttft and R == 1024 and not args.tower_only:
+    if rank == 0 and world == 1 and args.full and not args.no_ttft and R == 1024 and not args.tower_only:
         # the second half of the BASELINE metric on the same line (configs[2]: FastVLM-0.5B prefill TTFT, B = 8): encode_images ->
         # embedding splice -> Qwen2-0.5B prefill on fvhd_llm_prefill (KV cache written) -> first token on the host.  ~3 s of the run.
         try:
@@ -511,7 +546,7 @@ def main():
             result["ttft"] = {"value": None, "error": f"{type(e).__name__}: {e}"}
         trace("ttft leg done")
 
-    if rank == 0 and world == 1 and not args.no_extra_configs and not args.no_ttft and R == 1024 and not args.tower_only and B == 32 and Hd == 896:
+    if rank == 0 and world == 1 and args.full and not args.no_extra_configs and not args.no_ttft and R == 1024 and not args.tower_only and B == 32 and Hd == 896:
         # the remaining BASELINE.json configs on the driver's clock, a few seconds each:
         # c4_1gpu - the single-GPU leg of configs[3]: 8 images, FastVLM-7B widths (Qwen2-7B, 28 layers, 7.6 B random bf16 parameters), TTFT
         #           with the gather side of the 7B model's projector; the 8-GPU all-gather leg is `bench.py --ttft --hidden 3584 --gpus 8`
@@ -552,7 +587,7 @@ def main():
         torch.cuda.empty_cache()
         trace("c5 leg done")
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(R, Hd)
 
     if rank == 0:

@@ -11,7 +11,7 @@ O=gpurun_out/${TAG}
 case "$STAGE" in
 suite)      # the whole GPU suite + the driver's bench line
     timeout 1200 python -m pytest tests -m gpu -x -q --durations=12 > ${O}_pytest.log 2>&1; echo "pytest rc=$?"; tail -4 ${O}_pytest.log
-    timeout 600 python bench.py > ${O}_bench.json 2> ${O}_bench.err; echo "bench rc=$?"; cut -c1-600 ${O}_bench.json
+    timeout 600 python bench.py --full > ${O}_bench.json 2> ${O}_bench.err; echo "bench rc=$?"; cut -c1-600 ${O}_bench.json
     ;;
 ffn)        # fused ConvFFN variants: correctness of the variant library, sustained time / power / energy per launch, whole step
     for lib in ${FFN_LIBS:-"" old}; do
@@ -20,7 +20,7 @@ ffn)        # fused ConvFFN variants: correctness of the variant library, sustai
         [ -f $L ] || { echo "missing $L"; continue; }
         FVHD_LIB=$L timeout 600 python -m pytest tests/test_gpu_ops.py -m gpu -x -q -k "ffn" > ${O}_ffn_${lib:-base}_pytest.log 2>&1; tail -1 ${O}_ffn_${lib:-base}_pytest.log
         FVHD_LIB=$L timeout 300 python tools/power_probe.py ffn384 ffn192 ffn96 2>/dev/null | tee -a ${O}_ffn_power.log
-        FVHD_LIB=$L timeout 300 python bench.py --no-cpu-baseline --no-ttft > ${O}_bench_${lib:-base}.json 2>/dev/null; python - <<PY
+        FVHD_LIB=$L timeout 300 python bench.py --full --no-cpu-baseline --no-ttft > ${O}_bench_${lib:-base}.json 2>/dev/null; python - <<PY
 import json
 d=json.load(open("${O}_bench_${lib:-base}.json")); print("${lib:-base}", d["ms_per_step"], d["value"], {k:v["ms_per_step"] for k,v in d["kernels"].items()})
 PY
@@ -28,13 +28,13 @@ PY
     ;;
 extra)      # the other BASELINE configs: TTFT at the 7B width, 1536^2 with bf16 / e4m3 attention operands
     timeout 600 python bench.py --ttft --hidden 3584 --steps 10 --warmup 2 > ${O}_ttft_h3584.json 2> ${O}_ttft_h3584.err; echo "ttft3584 rc=$?"; cut -c1-400 ${O}_ttft_h3584.json
-    timeout 400 python bench.py --res 1536 --batch 16 --no-cpu-baseline --no-ttft > ${O}_bench_1536.json 2>/dev/null; echo "1536 rc=$?"; cut -c1-300 ${O}_bench_1536.json
-    timeout 400 python bench.py --res 1536 --batch 16 --attn-fp8 --no-cpu-baseline --no-ttft > ${O}_bench_1536_fp8.json 2>/dev/null; echo "1536 fp8 rc=$?"; cut -c1-300 ${O}_bench_1536_fp8.json
+    timeout 400 python bench.py --full --res 1536 --batch 16 --no-cpu-baseline --no-ttft > ${O}_bench_1536.json 2>/dev/null; echo "1536 rc=$?"; cut -c1-300 ${O}_bench_1536.json
+    timeout 400 python bench.py --full --res 1536 --batch 16 --attn-fp8 --no-cpu-baseline --no-ttft > ${O}_bench_1536_fp8.json 2>/dev/null; echo "1536 fp8 rc=$?"; cut -c1-300 ${O}_bench_1536_fp8.json
     ;;
 stem)       # the fully fused stem: op + step tests, A/B against the round-3 path (FVHD_FUSED_STEM=1) in the whole step
     timeout 900 python -m pytest tests/test_gpu_ops.py tests/test_gpu_steps.py -m gpu -x -q -k "stem or steps" > ${O}_stem_pytest.log 2>&1; echo "pytest rc=$?"; tail -2 ${O}_stem_pytest.log
     for v in 1 2; do
-        FVHD_FUSED_STEM=$v timeout 300 python bench.py --no-cpu-baseline --no-ttft > ${O}_bench_stem$v.json 2>/dev/null; python - <<PY
+        FVHD_FUSED_STEM=$v timeout 300 python bench.py --full --no-cpu-baseline --no-ttft > ${O}_bench_stem$v.json 2>/dev/null; python - <<PY
 import json
 d=json.load(open("${O}_bench_stem$v.json")); print("FVHD_FUSED_STEM=$v", d["ms_per_step"], d["value"], d["kernels"]["stem"], d["conv_stage"]["frac"])
 PY
@@ -82,7 +82,7 @@ gemmlib)    # GEMM source variants as whole libraries (production dispatch): op 
     for lib in ${GEMM_LIBS:-base fp0}; do
         [ "$lib" = base ] && L=ml_fastvlm_amd/libfvhd.so || L=ml_fastvlm_amd/libfvhd_$lib.so
         FVHD_LIB=$L timeout 300 python -m pytest tests/test_gpu_ops.py -m gpu -x -q -k "gemm" > ${O}_gemm_${lib}_pytest.log 2>&1; tail -1 ${O}_gemm_${lib}_pytest.log
-        FVHD_LIB=$L timeout 300 python bench.py --no-cpu-baseline --no-ttft > ${O}_bench_gemm_${lib}.json 2>/dev/null; python - <<PY
+        FVHD_LIB=$L timeout 300 python bench.py --full --no-cpu-baseline --no-ttft > ${O}_bench_gemm_${lib}.json 2>/dev/null; python - <<PY
 import json
 d=json.load(open("${O}_bench_gemm_${lib}.json")); print("$lib", d["ms_per_step"], d["value"], {k:v["ms_per_step"] for k,v in d["kernels"].items() if k.startswith("gemm") or k=="projector"})
 PY
@@ -92,9 +92,9 @@ rest)       # the GPU tests a -x run did not reach + one named file
     timeout 900 python -m pytest ${REST_TESTS:-tests/test_qwen2_prefill.py tests/test_splice.py tests/test_preprocess.py} -m gpu -x -q > ${O}_pytest_rest.log 2>&1; echo "pytest rest rc=$?"; tail -3 ${O}_pytest_rest.log
     ;;
 final)      # evidence of the final binary: bench line, small batches, PMC passes + kernel trace
-    timeout 600 python bench.py > ${O}_final_bench.json 2> ${O}_final_bench.err; echo "bench rc=$?"; cut -c1-300 ${O}_final_bench.json
-    timeout 300 python bench.py --batch 8 --no-cpu-baseline --no-ttft > ${O}_bench_b8.json 2>/dev/null; cut -c1-200 ${O}_bench_b8.json
-    timeout 300 python bench.py --batch 1 --no-cpu-baseline --no-ttft > ${O}_bench_b1.json 2>/dev/null; cut -c1-200 ${O}_bench_b1.json
+    timeout 600 python bench.py --full > ${O}_final_bench.json 2> ${O}_final_bench.err; echo "bench rc=$?"; cut -c1-300 ${O}_final_bench.json
+    timeout 300 python bench.py --full --batch 8 --no-cpu-baseline --no-ttft > ${O}_bench_b8.json 2>/dev/null; cut -c1-200 ${O}_bench_b8.json
+    timeout 300 python bench.py --full --batch 1 --no-cpu-baseline --no-ttft > ${O}_bench_b1.json 2>/dev/null; cut -c1-200 ${O}_bench_b1.json
     timeout 300 python tools/power_probe.py ffn384 ffn192 ffn96 dwmix192 dwmix384 stem attn 2>/dev/null | tee ${O}_final_power.log
     bash tools/run_pmc.sh ${TAG}
     # kernel trace of the TTFT path (encode B = 8 -> splice -> Qwen2-0.5B prefill): per-layer launch times of the prefill
@@ -108,7 +108,7 @@ r6d)        # round 6: PatchEmbed's stride-2 depthwise conv on the matrix cores:
     [ -f ml_fastvlm_amd/libfvhd_ablate.so ] && FVHD_LIB=ml_fastvlm_amd/libfvhd_ablate.so timeout 300 python tools/bench_ops.py dwdown 2>&1 | grep -v Warning | tee -a ${O}_dwdown.log
     timeout 900 python -m pytest tests/test_gpu_steps.py tests/test_gpu_tower.py -m gpu -q --maxfail=15 > ${O}_pytest_steps.log 2>&1; echo "pytest steps rc=$?"; tail -15 ${O}_pytest_steps.log | cut -c1-300
     for v in 0 1 0 1; do
-        FVHD_DWDOWN_MFMA=$v timeout 300 python bench.py --no-cpu-baseline --no-ttft --no-extra-configs > ${O}_bench_dd$v.json 2>/dev/null; python - <<PY | tee -a ${O}_ab.log
+        FVHD_DWDOWN_MFMA=$v timeout 300 python bench.py --full --no-cpu-baseline --no-ttft --no-extra-configs > ${O}_bench_dd$v.json 2>/dev/null; python - <<PY | tee -a ${O}_ab.log
 import json
 d=json.load(open("${O}_bench_dd$v.json")); print("FVHD_DWDOWN_MFMA=$v", d["ms_per_step"], d["value"], {k:v["ms_per_step"] for k,v in d["kernels"].items() if k.startswith("dw") or k in ("gemm_1x1", "stem")}, d["conv_stage"]["frac"])
 PY
@@ -130,7 +130,7 @@ r6e)        # round 6: dw_down ablations (variant libraries libfvhd_dd<bits>.so 
     timeout 900 python -m pytest tests/test_gpu_steps.py tests/test_gpu_tower.py -m gpu -q --maxfail=15 > ${O}_pytest_steps.log 2>&1; echo "pytest steps rc=$?"; tail -5 ${O}_pytest_steps.log | cut -c1-300
     for lib in base vtr0 base vtr0; do
         [ "$lib" = base ] && L=ml_fastvlm_amd/libfvhd.so || L=ml_fastvlm_amd/libfvhd_$lib.so
-        FVHD_LIB=$L timeout 300 python bench.py --no-cpu-baseline --no-ttft --no-extra-configs > ${O}_bench_$lib.json 2>/dev/null; python - <<PY | tee -a ${O}_ab.log
+        FVHD_LIB=$L timeout 300 python bench.py --full --no-cpu-baseline --no-ttft --no-extra-configs > ${O}_bench_$lib.json 2>/dev/null; python - <<PY | tee -a ${O}_ab.log
 import json
 d=json.load(open("${O}_bench_$lib.json")); print("$lib", d["ms_per_step"], d["value"], {k:v["ms_per_step"] for k,v in d["kernels"].items() if k.startswith("dw") or k in ("attention", "stem")}, d["conv_stage"]["frac"], d["attention_block"]["frac"])
 PY
@@ -152,7 +152,7 @@ r6f)        # round 6: dw_down skeleton ablations, dw7x7 with 32-px strips (stag
     done
     for lib in base vtr0 base vtr0; do
         [ "$lib" = base ] && L=ml_fastvlm_amd/libfvhd.so || L=ml_fastvlm_amd/libfvhd_$lib.so
-        FVHD_LIB=$L timeout 300 python bench.py --no-cpu-baseline --no-ttft --no-extra-configs > ${O}_bench_$lib.json 2>/dev/null; python - <<PY | tee -a ${O}_ab.log
+        FVHD_LIB=$L timeout 300 python bench.py --full --no-cpu-baseline --no-ttft --no-extra-configs > ${O}_bench_$lib.json 2>/dev/null; python - <<PY | tee -a ${O}_ab.log
 import json
 d=json.load(open("${O}_bench_$lib.json")); print("$lib", d["ms_per_step"], d["value"], {k:v["ms_per_step"] for k,v in d["kernels"].items() if k.startswith("dw") or k in ("attention", "stem")}, d["conv_stage"]["frac"], d["attention_block"]["frac"])
 PY
@@ -170,7 +170,7 @@ r6g)        # round 6: dw_down with DMA / store wave roles and per-row operand r
     FVHD_LIB=ml_fastvlm_amd/libfvhd_ablate.so timeout 300 python tools/bench_ops.py dwdown 2>&1 | grep "dw_down" | tee ${O}_dwdown_rc.log
     for lib in base ddold base ddold; do
         [ "$lib" = base ] && L=ml_fastvlm_amd/libfvhd.so || L=ml_fastvlm_amd/libfvhd_$lib.so
-        FVHD_LIB=$L timeout 300 python bench.py --no-cpu-baseline --no-ttft --no-extra-configs > ${O}_bench_$lib.json 2>/dev/null; python - <<PY | tee -a ${O}_ab.log
+        FVHD_LIB=$L timeout 300 python bench.py --full --no-cpu-baseline --no-ttft --no-extra-configs > ${O}_bench_$lib.json 2>/dev/null; python - <<PY | tee -a ${O}_ab.log
 import json
 d=json.load(open("${O}_bench_$lib.json")); print("$lib", d["ms_per_step"], d["value"], {k:v["ms_per_step"] for k,v in d["kernels"].items() if k.startswith("dw") or k in ("attention", "stem")}, d["conv_stage"]["frac"], d["attention_block"]["frac"])
 PY
@@ -187,7 +187,7 @@ r6h)        # round 6: XCD-aware block order where channel blocks share 128-B li
     done
     for lib in base x0 base x0; do
         [ "$lib" = base ] && L=ml_fastvlm_amd/libfvhd.so || L=ml_fastvlm_amd/libfvhd_$lib.so
-        FVHD_LIB=$L timeout 300 python bench.py --no-cpu-baseline --no-ttft --no-extra-configs > ${O}_bench_$lib.json 2>/dev/null; python - <<PY | tee -a ${O}_ab.log
+        FVHD_LIB=$L timeout 300 python bench.py --full --no-cpu-baseline --no-ttft --no-extra-configs > ${O}_bench_$lib.json 2>/dev/null; python - <<PY | tee -a ${O}_ab.log
 import json
 d=json.load(open("${O}_bench_$lib.json")); print("$lib", d["ms_per_step"], d["value"], {k:v["ms_per_step"] for k,v in d["kernels"].items() if k.startswith("dw") or k in ("stem",)}, d["conv_stage"]["frac"])
 PY
@@ -200,7 +200,7 @@ r6i)        # round 6: 128 x 192 tiles for the N = 192 1x1 + GELU of PatchEmbed 
         FVHD_LIB=ml_fastvlm_amd/libfvhd_ablate.so FVHD_GEMM_NF6=$v BENCH_GEMM_VARIANTS=1 timeout 200 python tools/bench_ops.py gemm 2>&1 | grep "1x1" | tee -a ${O}_nf6.log
     done
     for v in 1 0 1 0; do
-        FVHD_GEMM_NF6=$v timeout 300 python bench.py --no-cpu-baseline --no-ttft --no-extra-configs > ${O}_bench_nf6_$v.json 2>/dev/null; python - <<PY | tee -a ${O}_ab.log
+        FVHD_GEMM_NF6=$v timeout 300 python bench.py --full --no-cpu-baseline --no-ttft --no-extra-configs > ${O}_bench_nf6_$v.json 2>/dev/null; python - <<PY | tee -a ${O}_ab.log
 import json
 d=json.load(open("${O}_bench_nf6_$v.json")); print("FVHD_GEMM_NF6=$v", d["ms_per_step"], d["value"], {k:v["ms_per_step"] for k,v in d["kernels"].items() if k.startswith("gemm")})
 PY
@@ -212,7 +212,7 @@ r6j)        # round 6: XCD-remapped block order in the depthwise pair for EVERY 
         [ "$lib" = base ] && L=ml_fastvlm_amd/libfvhd.so || L=ml_fastvlm_amd/libfvhd_$lib.so
         echo "--- $lib" | tee -a ${O}_fzx2.log
         FVHD_LIB=$L timeout 200 python tools/bench_ops.py dw37 2>&1 | grep "dw3+dw7" | cut -c1-140 | tee -a ${O}_fzx2.log
-        FVHD_LIB=$L timeout 300 python bench.py --no-cpu-baseline --no-ttft --no-extra-configs > ${O}_bench_$lib.json 2>/dev/null; python - <<PY | tee -a ${O}_fzx2.log
+        FVHD_LIB=$L timeout 300 python bench.py --full --no-cpu-baseline --no-ttft --no-extra-configs > ${O}_bench_$lib.json 2>/dev/null; python - <<PY | tee -a ${O}_fzx2.log
 import json
 d=json.load(open("${O}_bench_$lib.json")); print("$lib", d["ms_per_step"], d["value"], {k:v["ms_per_step"] for k,v in d["kernels"].items() if k.startswith("dw")}, d["conv_stage"]["frac"])
 PY
@@ -224,7 +224,7 @@ r6k)        # round 6: the 32-channel block of the depthwise pair on pairs of st
         [ "$lib" = base ] && L=ml_fastvlm_amd/libfvhd.so || L=ml_fastvlm_amd/libfvhd_$lib.so
         echo "--- $lib" | tee -a ${O}_half2.log
         FVHD_LIB=$L timeout 200 python tools/bench_ops.py dw37 2>&1 | grep "dw3+dw7" | cut -c1-140 | tee -a ${O}_half2.log
-        FVHD_LIB=$L timeout 300 python bench.py --no-cpu-baseline --no-ttft --no-extra-configs > ${O}_bench_$lib.json 2>/dev/null; python - <<PY | tee -a ${O}_half2.log
+        FVHD_LIB=$L timeout 300 python bench.py --full --no-cpu-baseline --no-ttft --no-extra-configs > ${O}_bench_$lib.json 2>/dev/null; python - <<PY | tee -a ${O}_half2.log
 import json
 d=json.load(open("${O}_bench_$lib.json")); print("$lib", d["ms_per_step"], d["value"], {k:v["ms_per_step"] for k,v in d["kernels"].items() if k.startswith("dw")}, d["conv_stage"]["frac"])
 PY
@@ -239,7 +239,7 @@ r6a)        # round 6: the fused dw3x3 -> dw7x7 kernel: op tests, then fused vs 
 r6b)        # round 6: the fused depthwise launch inside the tower: step / tower / precision tests, then FVHD_FUSED_DW=0 / 1 on one box
     timeout 1200 python -m pytest tests/test_gpu_steps.py tests/test_gpu_tower.py tests/test_gpu_ffn_precision.py tests/test_gpu_ops.py -m gpu -q --maxfail=15 --durations=5 > ${O}_pytest.log 2>&1; echo "pytest rc=$?"; tail -25 ${O}_pytest.log | cut -c1-300
     for v in 0 1 0 1; do
-        FVHD_FUSED_DW=$v timeout 300 python bench.py --no-cpu-baseline --no-ttft --no-extra-configs > ${O}_bench_dw$v.json 2>/dev/null; python - <<PY | tee -a ${O}_ab.log
+        FVHD_FUSED_DW=$v timeout 300 python bench.py --full --no-cpu-baseline --no-ttft --no-extra-configs > ${O}_bench_dw$v.json 2>/dev/null; python - <<PY | tee -a ${O}_ab.log
 import json
 d=json.load(open("${O}_bench_dw$v.json")); print("FVHD_FUSED_DW=$v", d["ms_per_step"], d["value"], {k:v["ms_per_step"] for k,v in d["kernels"].items() if k.startswith("dw") or k in ("ffn_fused", "stem")}, d["conv_stage"]["frac"])
 PY
@@ -247,12 +247,12 @@ PY
     ;;
 r5a)        # round 5, first call: whole GPU suite (all failures, not -x), the driver's line, GEMM layout A/B (bits + time), WRITE_SIZE of the GEMM classes
     timeout 1500 python -m pytest tests -m gpu -q --maxfail=25 --durations=8 > ${O}_pytest.log 2>&1; echo "pytest rc=$?"; tail -30 ${O}_pytest.log | cut -c1-300
-    timeout 900 python bench.py > ${O}_bench.json 2> ${O}_bench.err; echo "bench rc=$?"; cut -c1-400 ${O}_bench.json; tail -3 ${O}_bench.err
+    timeout 900 python bench.py --full > ${O}_bench.json 2> ${O}_bench.err; echo "bench rc=$?"; cut -c1-400 ${O}_bench.json; tail -3 ${O}_bench.err
     python tools/gemm_bits.py > ${O}_gemm_bits_base.json 2>${O}_gemm_bits.err; FVHD_LIB=ml_fastvlm_amd/libfvhd_g1.so python tools/gemm_bits.py > ${O}_gemm_bits_g1.json 2>>${O}_gemm_bits.err
     python tools/gemm_bits.py --diff ${O}_gemm_bits_base.json ${O}_gemm_bits_g1.json | tee ${O}_gemm_bits_diff.log
     for lib in base g1; do
         [ "$lib" = base ] && L=ml_fastvlm_amd/libfvhd.so || L=ml_fastvlm_amd/libfvhd_$lib.so
-        FVHD_LIB=$L timeout 300 python bench.py --no-cpu-baseline --no-ttft > ${O}_bench_gemm_${lib}.json 2>/dev/null; python - <<PY | tee -a ${O}_gemm_ab.log
+        FVHD_LIB=$L timeout 300 python bench.py --full --no-cpu-baseline --no-ttft > ${O}_bench_gemm_${lib}.json 2>/dev/null; python - <<PY | tee -a ${O}_gemm_ab.log
 import json
 d=json.load(open("${O}_bench_gemm_${lib}.json")); print("$lib", d["ms_per_step"], d["value"], {k:v["ms_per_step"] for k,v in d["kernels"].items() if k.startswith("gemm") or k in ("projector", "dw7", "dw3", "ffn_fused")})
 PY
@@ -274,7 +274,7 @@ r5b)        # round 5, second call: the tests the first call failed / the kernel
     timeout 900 python -m pytest tests/test_gpu_ffn_precision.py tests/test_gpu_ops.py tests/test_qwen2_prefill.py tests/test_gpu_steps.py "tests/test_gpu_reference.py::test_drop_in_defaults_are_range_safe_on_a_saturating_checkpoint" -m gpu -q --maxfail=20 --durations=5 > ${O}_pytest.log 2>&1; echo "pytest rc=$?"; tail -25 ${O}_pytest.log | cut -c1-300
     run_bench() { # label, env...
         local label=$1; shift
-        env "$@" timeout 300 python bench.py --no-cpu-baseline --no-ttft > ${O}_bench_${label}.json 2>/dev/null; python - <<PY | tee -a ${O}_ab.log
+        env "$@" timeout 300 python bench.py --full --no-cpu-baseline --no-ttft > ${O}_bench_${label}.json 2>/dev/null; python - <<PY | tee -a ${O}_ab.log
 import json
 d=json.load(open("${O}_bench_${label}.json")); print("${label}", d["ms_per_step"], d["value"], {k:v["ms_per_step"] for k,v in d["kernels"].items() if k.startswith("gemm") or k in ("projector", "dw7", "dw3", "ffn_fused")})
 PY
@@ -304,7 +304,7 @@ r5c)        # round 5, third call: the two range tests again, epilogue walk A/B 
     timeout 600 python -m pytest tests/test_gpu_ffn_precision.py "tests/test_gpu_reference.py::test_drop_in_defaults_are_range_safe_on_a_saturating_checkpoint" tests/test_gpu_ops.py -k "not gemm and not attention and not ffn_fused" -m gpu -q --maxfail=20 > ${O}_pytest.log 2>&1; echo "pytest rc=$?"; tail -12 ${O}_pytest.log | cut -c1-300
     run_bench() { # label, env...
         local label=$1; shift
-        env "$@" timeout 300 python bench.py --no-cpu-baseline --no-ttft > ${O}_bench_${label}.json 2>/dev/null; python - <<PY | tee -a ${O}_ab.log
+        env "$@" timeout 300 python bench.py --full --no-cpu-baseline --no-ttft > ${O}_bench_${label}.json 2>/dev/null; python - <<PY | tee -a ${O}_ab.log
 import json
 d=json.load(open("${O}_bench_${label}.json")); print("${label}", d["ms_per_step"], d["value"], {k:v["ms_per_step"] for k,v in d["kernels"].items() if k.startswith("gemm") or k in ("projector", "dw7", "dw3", "ffn_fused")})
 PY
@@ -327,7 +327,7 @@ r5d)        # round 5, fourth call: amax through 64 slots + one atomic per workg
     timeout 600 python -m pytest tests/test_gpu_ffn_precision.py tests/test_gpu_ops.py -k "not attention and not ffn_fused and not stem" -m gpu -q --maxfail=20 > ${O}_pytest.log 2>&1; echo "pytest rc=$?"; tail -6 ${O}_pytest.log | cut -c1-300
     run_bench() { # label, env...
         local label=$1; shift
-        env "$@" timeout 300 python bench.py --no-cpu-baseline --no-ttft > ${O}_bench_${label}.json 2>/dev/null; python - <<PY | tee -a ${O}_ab.log
+        env "$@" timeout 300 python bench.py --full --no-cpu-baseline --no-ttft > ${O}_bench_${label}.json 2>/dev/null; python - <<PY | tee -a ${O}_ab.log
 import json
 d=json.load(open("${O}_bench_${label}.json")); print("${label}", d["ms_per_step"], d["value"], {k:v["ms_per_step"] for k,v in d["kernels"].items() if k.startswith("gemm") or k in ("projector", "dw7", "dw3", "ffn_fused")})
 PY
@@ -363,7 +363,7 @@ r5f)        # round 5: skewed channel halves of the dw7 kernel's transposed imag
     timeout 600 python -m pytest tests/test_gpu_ops.py tests/test_gpu_steps.py -k "dw or steps" -m gpu -q --maxfail=20 > ${O}_pytest.log 2>&1; echo "pytest rc=$?"; tail -4 ${O}_pytest.log | cut -c1-300
     run_bench() { # label, env...
         local label=$1; shift
-        env "$@" timeout 300 python bench.py --no-cpu-baseline --no-ttft > ${O}_bench_${label}.json 2>/dev/null; python - <<PY | tee -a ${O}_ab.log
+        env "$@" timeout 300 python bench.py --full --no-cpu-baseline --no-ttft > ${O}_bench_${label}.json 2>/dev/null; python - <<PY | tee -a ${O}_ab.log
 import json
 d=json.load(open("${O}_bench_${label}.json")); print("${label}", d["ms_per_step"], d["value"], {k:v["ms_per_step"] for k,v in d["kernels"].items() if k in ("dw7", "dw3", "ffn_fused", "stem", "dw_down")})
 PY
