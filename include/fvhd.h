@@ -46,8 +46,10 @@ typedef void* fvhd_stream_t; /* hipStream_t */
  * (ml_fastvlm_amd/_lib.py does): the major part changes whenever an exported signature or the meaning of an argument changes.
  * 100 = rounds 1-3; round 4 changed signatures under the same number (fvhd_op_stem_fused + w2 / b2, fvhd_op_ffn_fused / fvhd_ffn_pack +
  * precision, fvhd_op_rope + rope_theta) - a mistake this number corrects; 500 = round 5 (adds the range guard, fvhd_op_dw7_amax,
- * fvhd_op_gemm_qkv_rope / fvhd_gemm_qkv_rope_supported, the fvhd_llm_* stream contract; no signature of round 4 changed). */
-#define FVHD_VERSION 500
+ * fvhd_op_gemm_qkv_rope / fvhd_gemm_qkv_rope_supported, the fvhd_llm_* stream contract; no signature of round 4 changed); 501 adds the
+ * LLM decode (fvhd_llm_cache_reserve / start / decode / cache_state / set_tied_embeddings, the optional model.embed_tokens.weight key,
+ * fvhd_op_dec_*); nothing earlier changed. */
+#define FVHD_VERSION 501
 int fvhd_version(void);
 const char* fvhd_last_error(void);
 
@@ -338,7 +340,8 @@ void fvhd_llm_destroy(fvhd_llm* ctx);
 /* One tensor of the state dict: key = "model.layers.<l>.{input_layernorm,post_attention_layernorm}.weight",
  * "model.layers.<l>.self_attn.{q,k,v}_proj.{weight,bias}", "model.layers.<l>.self_attn.o_proj.weight",
  * "model.layers.<l>.mlp.{gate,up,down}_proj.weight", "model.norm.weight", "lm_head.weight" (the embedding table when the
- * model ties them; the leading "model." may be absent).  host_data: contiguous HOST memory of `dtype` (FVHD_F32 / F16 / BF16) in the
+ * model ties them; the leading "model." may be absent), and - optional, for the decode of a model that does not tie them -
+ * "model.embed_tokens.weight".  host_data: contiguous HOST memory of `dtype` (FVHD_F32 / F16 / BF16) in the
  * reference's [out, in] layout; converted (matrices to bf16, vectors to fp32), packed (q|k|v rows concatenated, gate / up rows
  * interleaved) and uploaded before the call returns.  Any other key is an error. */
 int fvhd_llm_set_tensor(fvhd_llm* ctx, const char* key, const void* host_data, int dtype, const int64_t* shape, int ndim);
@@ -413,6 +416,60 @@ int fvhd_op_qkv_splitk_rope(fvhd_stream_t stream, const void* A, const void* Wt,
  * out [B*T, n_heads * head_dim] bf16; key_valid uint8 [B, T] or NULL; head_dim in {64, 128} */
 int fvhd_op_attention_causal(fvhd_stream_t stream, const void* qkv, void* out, const uint8_t* key_valid, int B, int T, int n_heads,
                              int n_kv_heads, int head_dim);
+
+/* ---- LLM decode: generation on the library's own KV cache --------------------------------------------------------------------------
+ * After a prefill, one new token per sequence per call, with greedy selection on the device - what transformers' greedy generate loop
+ * does after its first forward, on the same packed weights as the prefill (no further weight copy).  Per decoder layer 5 launches:
+ * [RMSNorm + q|k|v GEMM + bias + rotary + cache append] [attention over the cache] [o_proj + residual] [RMSNorm + gate|up + silu * up]
+ * [down_proj + residual], then [final RMSNorm + lm_head + per-workgroup argmax] [argmax reduce + advance]; the GEMMs stream the weights
+ * once (B <= 16 rows), fp32 accumulation, deterministic split-K reductions (identical bits run to run).
+ * Everything that changes from step to step - the cache slot, the positions, the mask column - lives in device memory and is advanced by
+ * the step itself: the host arguments of fvhd_llm_decode are the same for every token, so ONE captured graph replays a whole generation. */
+/* The decode's input embedding.  model.embed_tokens.weight [vocab, hidden] (fvhd_llm_set_tensor(_device); optional for the prefill and
+ * fvhd_llm_finalize) is used whenever it was set.  Without it, tied != 0 declares that the model ties its embeddings
+ * (tie_word_embeddings: Qwen2-0.5B / 1.5B) and the decode embeds through the packed lm_head rows.  Nothing is assumed: until one of the
+ * two is done - or after tied == 0 without the embedding table - fvhd_llm_start / fvhd_llm_decode fail with an error. */
+int fvhd_llm_set_tied_embeddings(fvhd_llm* ctx, int tied);
+/* Allocates the cache: K and V bf16 [n_layers][batch][n_kv_heads][capacity][head_dim] (transformers' per-layer layout with a capacity
+ * stride), the key-valid mask [batch][capacity], the next position of every sequence (int64 [batch]), the current length, the last chosen
+ * ids, the error word and the decode workspace.  1 <= batch <= 16; hidden, n_heads * head_dim and intermediate multiples of 128.
+ * Synchronises (refused while a stream is being captured); replaces an earlier cache (a graph captured on it is then invalid). */
+int fvhd_llm_cache_reserve(fvhd_llm* ctx, int batch, int capacity);
+/* fvhd_llm_prefill's arithmetic on embeds [batch, seq_len, hidden] (batch <= the reserved batch, seq_len <= capacity), then: its rotated
+ * K / V in cache slots [0, seq_len), key_valid (NULL = all valid) as the mask, length = seq_len, next position of sequence b =
+ * position_ids[b, seq_len - 1] + 1 (NULL: seq_len), the error word cleared.  logits_out: NULL or fp32 [batch, vocab] of the last
+ * position; next_ids_out: NULL or int64 [batch] = their argmax (ties: the lowest index, as torch.argmax). */
+int fvhd_llm_start(fvhd_llm* ctx, const void* embeds, int dtype, const uint8_t* key_valid, const int64_t* position_ids, int batch, int seq_len,
+                   float* logits_out, int64_t* next_ids_out, fvhd_stream_t stream);
+/* One step: token_ids int64 [batch] on the device, or NULL = the ids the previous start / decode chose; appends their k / v at slot
+ * `length` with mask 1, advances length and positions by one, and writes logits_out (NULL or fp32 [batch, vocab]) and next_ids_out
+ * (NULL or int64 [batch]).  A step past `capacity` (or given an id outside [0, vocab)) writes nothing and sets a sticky error word that the
+ * next fvhd_llm_decode reports as an error (fvhd_llm_cache_state reads it at once).  Capture-safe after fvhd_llm_start. */
+int fvhd_llm_decode(fvhd_llm* ctx, const int64_t* token_ids, float* logits_out, int64_t* next_ids_out, fvhd_stream_t stream);
+/* synchronises the device, then: the cache length and the error word (0 = fine, 1 = past capacity, 2 = token id out of range) */
+int fvhd_llm_cache_state(fvhd_llm* ctx, int* length, int* status);
+
+/* single ops of the decode step (unit-test entry points); B in [1, 16]; K % 128 == 0; `splits` = workgroups per output tile along K
+ * (partial: fp32 scratch [splits][N * 16], counters: int [ceil(N / 64)] ZEROED before the first call - each launch leaves them zero)
+ * out = epilogue(rmsnorm?(x) . Wt^T): x [B, K] bf16, norm_w fp32 [K] or NULL (no norm), Wt [N, K] bf16; FVHD_EPI_RESID: out [B, N] =
+ * resid + acc (resid may alias out); FVHD_EPI_SWIGLU: out [B, N / 2] = silu(acc[2j]) * acc[2j + 1] (gate / up rows interleaved). */
+int fvhd_op_dec_gemm(fvhd_stream_t stream, int epi, const void* x, int B, const float* norm_w, float eps, const void* Wt, int N, int K, const void* resid,
+                     void* out, float* partial, int* counters, int splits);
+/* the q|k|v projection of one decode step: bf16(rmsnorm?(x) . Wt^T + bias), rotary embedding (fvhd_op_rope's) of the q and k heads at
+ * position pos[b] (int64 [B]), q -> q_out [B, n_heads * head_dim], k / v -> k_cache / v_cache [>= B][n_kv_heads][capacity][head_dim] at slot
+ * *length (a device int) */
+int fvhd_op_dec_qkv(fvhd_stream_t stream, const void* x, int B, int K, const float* norm_w, float eps, const void* Wt, const float* bias, void* q_out,
+                    const int64_t* pos, const float* table, int table_positions, float rope_theta, void* k_cache, void* v_cache, int capacity,
+                    const int* length, int n_heads, int n_kv_heads, int head_dim, float* partial, int* counters, int splits);
+/* single-query grouped-query attention over cache keys [0, *length) of every sequence: q [B, n_heads * head_dim] bf16, caches as above,
+ * key_valid uint8 [>= B][capacity] -> out [B, n_heads * head_dim] bf16; head_dim 64 / 128.  partial: fp32 [B * n_heads * splits * (head_dim + 2)],
+ * counters: int [B * n_heads] zeroed */
+int fvhd_op_dec_attention(fvhd_stream_t stream, const void* q, const void* k_cache, const void* v_cache, const uint8_t* key_valid, void* out, int B,
+                          int n_heads, int n_kv_heads, int head_dim, int capacity, const int* length, float* partial, int* counters, int splits);
+/* final norm + lm_head + argmax: logits (NULL or fp32 [B, V]) = rmsnorm?(x) . Wt^T, ids_out int64 [B] = argmax (lowest index on ties);
+ * scratch_v / scratch_i: [ceil(V / 64) * 16] each */
+int fvhd_op_dec_lm_argmax(fvhd_stream_t stream, const void* x, int B, const float* norm_w, float eps, const void* Wt, int V, int K, float* logits,
+                          int64_t* ids_out, float* scratch_v, int* scratch_i);
 
 #ifdef __cplusplus
 }

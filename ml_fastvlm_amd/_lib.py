@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # FVHD_LIB: another build of the same ABI (the ablation library of `python -m ml_fastvlm_amd.build` with FVHD_FFN_ABLATE=1)
 LIB_PATH = os.environ.get("FVHD_LIB") or os.path.join(_HERE, "libfvhd.so")
 
-ABI_VERSION = 500               # FVHD_VERSION of the include/fvhd.h this stub was written against (major = ABI_VERSION // 100)
+ABI_VERSION = 501               # FVHD_VERSION of the include/fvhd.h this stub was written against (major = ABI_VERSION // 100)
 F32, F16, BF16 = 0, 1, 2
 FFN_HALF, FFN_BF16 = 0, 1        # precision of the fused ConvFFN's hidden activation (include/fvhd.h)
 EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_LS_RESID, EPI_RESID, EPI_SWIGLU = 0, 1, 2, 3, 4, 5
@@ -94,6 +94,15 @@ def _declare(lib) -> None:
         "fvhd_op_gemm_splitk": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci]),
         "fvhd_op_qkv_splitk_rope": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, ci]),
         "fvhd_op_gemm_splitk_norm": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, C.c_float]),
+        "fvhd_llm_set_tied_embeddings": (ci, [vp, ci]),
+        "fvhd_llm_cache_reserve": (ci, [vp, ci, ci]),
+        "fvhd_llm_start": (ci, [vp, vp, ci, vp, vp, ci, ci, vp, vp, vp]),
+        "fvhd_llm_decode": (ci, [vp, vp, vp, vp, vp]),
+        "fvhd_llm_cache_state": (ci, [vp, C.POINTER(ci), C.POINTER(ci)]),
+        "fvhd_op_dec_gemm": (ci, [vp, ci, vp, ci, vp, cf, vp, ci, ci, vp, vp, vp, vp, ci]),
+        "fvhd_op_dec_qkv": (ci, [vp, vp, ci, ci, vp, cf, vp, vp, vp, vp, vp, ci, cf, vp, vp, ci, vp, ci, ci, ci, vp, vp, ci]),
+        "fvhd_op_dec_attention": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, ci]),
+        "fvhd_op_dec_lm_argmax": (ci, [vp, vp, ci, vp, cf, vp, ci, ci, vp, vp, vp, vp]),
     }
     del fp, cl
     for name, (res, args) in sig.items():
@@ -112,11 +121,13 @@ def load():
                 f"{LIB_PATH} not found: the HIP extension is not built. Run `python -m ml_fastvlm_amd.build` "
                 "(hipcc, gfx950). There is no CPU fallback for this path.")
         lib = C.CDLL(LIB_PATH)
-        _declare(lib)
+        # the version first: a stale library (built before symbols this binding declares) fails with the ABI message, not an AttributeError
+        lib.fvhd_version.restype, lib.fvhd_version.argtypes = C.c_int, []
         got = lib.fvhd_version()
         if got // 100 != ABI_VERSION // 100 or got < ABI_VERSION:
             raise FvhdError(f"{LIB_PATH} reports ABI version {got}, this binding was written for {ABI_VERSION} (include/fvhd.h FVHD_VERSION): "
                             "rebuild the library (`python -m ml_fastvlm_amd.build`) - argument lists differ between major versions")
+        _declare(lib)
         _lib = lib
     return _lib
 

@@ -227,3 +227,59 @@ def prepare_inputs_labels_for_multimodal(self, input_ids, position_ids, attentio
     out = S.multimodal_splice(input_ids, position_ids, attention_mask, labels, image_features, self.get_model().embed_tokens.weight,
                               getattr(cfg, "tokenizer_padding_side", "right"), getattr(cfg, "tokenizer_model_max_length", None))
     return out[0], out[1], out[2], past_key_values, out[4], out[5]
+
+
+_GENERATE_IGNORED = ("temperature", "top_p", "top_k")     # sampling knobs transformers itself ignores under do_sample=False
+
+
+def generator_context(model, batch: int, capacity: int):
+    """The `Qwen2Generator` of a (Llava)Qwen2ForCausalLM, on the model's `prefill_context` (same packed weights - no further copy), cached
+    on the model and rebuilt when the weights change or a larger (batch, capacity) is asked for."""
+    from .qwen2_decode import Qwen2Generator
+    pre = prefill_context(model)
+    gen = getattr(model, "_fvhd_generator", None)
+    if gen is None or gen.pre is not pre or gen.batch < batch or gen.capacity < capacity:
+        if gen is not None and gen.pre is pre:
+            batch, capacity = max(batch, gen.batch), max(capacity, gen.capacity)
+        gen = Qwen2Generator.from_hf(model, batch, capacity, prefill=pre)
+        object.__setattr__(model, "_fvhd_generator", gen)
+    return gen
+
+
+@torch.no_grad()
+def generate(model, input_ids, images=None, image_sizes=None, attention_mask=None, max_new_tokens: int = 256, eos_token_id=None,
+             pad_token_id=None, do_sample: bool = False, num_beams: int = 1, **kwargs):
+    """`LlavaQwen2ForCausalLM.generate` (`llava_qwen.py:106-143`) with greedy decoding on the library: the multimodal splice
+    (`model.prepare_inputs_labels_for_multimodal`) or the token embedding, then the prefill and every decode step on the hand-written
+    Qwen2 kernels (`Qwen2Generator.greedy`).  Returns the new tokens [B, n] as transformers' generate(inputs_embeds=...) does.  Greedy only:
+    sampling, beam search and other decoding strategies raise NotImplementedError.  The model must be bf16 on a HIP device."""
+    if do_sample:
+        raise NotImplementedError("ml_fastvlm_amd.generate: do_sample=True (sampling) is not implemented - greedy decoding only; "
+                                  "Qwen2Generator.step exposes the logits for sampling in torch")
+    if num_beams != 1:
+        raise NotImplementedError(f"ml_fastvlm_amd.generate: num_beams={num_beams} (beam search) is not implemented - greedy decoding only")
+    if "inputs_embeds" in kwargs:                            # as the reference's generate (llava_qwen.py:120)
+        raise NotImplementedError("`inputs_embeds` is not supported")
+    for k, v in kwargs.items():
+        if k in _GENERATE_IGNORED or (k == "use_cache" and v):
+            continue
+        raise NotImplementedError(f"ml_fastvlm_amd.generate: the generation setting {k}={v!r} is not implemented - greedy decoding only")
+    lm_w = model.lm_head.weight
+    if lm_w.device.type != "cuda" or lm_w.dtype != torch.bfloat16:
+        raise ValueError(f"ml_fastvlm_amd.generate: needs a bf16 model on a HIP device (got {lm_w.dtype} on {lm_w.device}); "
+                         "the decode kernels compute in bf16")
+    position_ids = None
+    if images is not None:
+        (input_ids, position_ids, attention_mask, _, inputs_embeds, _) = model.prepare_inputs_labels_for_multimodal(
+            input_ids, position_ids, attention_mask, None, None, images, image_sizes=image_sizes)
+    else:
+        inputs_embeds = model.get_input_embeddings()(input_ids)
+    gc = getattr(model, "generation_config", None)
+    if eos_token_id is None:
+        eos_token_id = getattr(gc, "eos_token_id", None)
+    if pad_token_id is None:
+        pad_token_id = getattr(gc, "pad_token_id", None)
+    B, T = inputs_embeds.shape[:2]
+    gen = generator_context(model, B, T + max_new_tokens)
+    return gen.greedy(inputs_embeds, attention_mask, position_ids, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id,
+                      pad_token_id=pad_token_id)

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/fvhd.h"
+#include "llm_decode.h"
 
 extern "C" {
 int fvhd_launch_gemm(hipStream_t, const void*, const void*, const float*, const float*, const void*, void*, int, int, int, int, int);
@@ -26,6 +27,14 @@ int fvhd_launch_llm_attention(hipStream_t, const void*, void*, const unsigned ch
 int fvhd_launch_cast_rows(hipStream_t, const void*, int, void*, long);
 int fvhd_launch_gather_rows(hipStream_t, const void*, void*, int, int, int, int);
 int fvhd_set_error(const char* msg);     // fvhd_api.hip: the library's one thread-local error string
+// llm_decode.hip
+int fvhd_launch_dec_gemm(hipStream_t, const DecGemmArgs*);
+int fvhd_launch_dec_attention(hipStream_t, const void*, const void*, const void*, const unsigned char*, void*, int, int, int, int, int, const int*, int, int, int,
+                              float*, int*, const int*);
+int fvhd_launch_dec_embed(hipStream_t, const int64_t*, const int64_t*, const void*, int, int, void*, unsigned char*, int, int, const int*, int*, int*);
+int fvhd_launch_dec_argmax_finish(hipStream_t, const float*, const int*, int, int, int64_t*, int64_t*, int64_t*, int*, const int*);
+int fvhd_launch_dec_argmax_blocks(hipStream_t, const float*, int, int, float*, int*);
+int fvhd_launch_dec_start_state(hipStream_t, int64_t*, const int64_t*, int, int, int*, int*);
 }
 
 namespace {
@@ -108,6 +117,26 @@ struct fvhd_llm {
     hipEvent_t load_ev = nullptr;
     hipStream_t load_stream = nullptr;
     bool load_pending = false;
+    // ---- decode (fvhd_llm_cache_reserve / start / decode) ----
+    char* emb = nullptr;                   // model.embed_tokens.weight, bf16 [V][H]: optional, the decode's input table of an untied model
+    int tied = -1;                         // fvhd_llm_set_tied_embeddings: 1 = the decode embeds through the packed lm_head rows, 0 = through
+                                           // `emb`; -1 = not said - the decode then needs `emb` (it never guesses the lm_head rows)
+    char* dc = nullptr;                    // one allocation: caches, mask, device words, decode workspace, rotary table
+    size_t dc_bytes = 0;
+    int dc_batch = 0, dc_cap = 0, dc_pos = 0;
+    int run_batch = 0;                     // batch of the last fvhd_llm_start (the decode steps run on it)
+    char *kcache = nullptr, *vcache = nullptr, *dh = nullptr, *dq = nullptr, *datt = nullptr, *dact = nullptr;
+    unsigned char* mask = nullptr;
+    int64_t *posv = nullptr, *last_ids = nullptr;
+    int *len = nullptr, *status = nullptr, *cnt = nullptr, *amax_i = nullptr;
+    float *dpart = nullptr, *apart = nullptr, *amax_v = nullptr, *dlogits = nullptr, *drope = nullptr;
+    int* status_host = nullptr;            // host-mapped copy of the error word: read by every host call without a synchronisation
+    int* status_host_dev = nullptr;
+    int cnt_att = 0;                       // counters [0, cnt_att) of the GEMMs, then B * nh of the attention
+    struct Plan { int S = 1, cpw = 1; } p_qkv, p_o, p_gu, p_d, p_lm;
+    int att_S = 1, att_chunk = 0;
+    char* pre_kv = nullptr;                // the prefill's own [n_layers][batch][nkv][seq_len][hd] caches, copied into the strided ones
+    size_t pre_kv_bytes = 0;
 };
 
 namespace {
@@ -131,6 +160,19 @@ int tensor_index(const fvhd_llm* c, const std::string& key, int* layer, int* whi
     for (int i = 0; i < 12; ++i)
         if (rest == kNames[i]) { *layer = l; *which = i; return l * 12 + i; }
     return -1;
+}
+
+bool is_embed_key(const char* key)
+{
+    const std::string k(key);
+    return k == "model.embed_tokens.weight" || k == "embed_tokens.weight";
+}
+
+int ensure_emb(fvhd_llm* c)
+{
+    if (c->emb) return 0;
+    const hipError_t e = hipMalloc((void**)&c->emb, (size_t)c->V * c->H * 2);
+    return e == hipSuccess ? 0 : lhip("hipMalloc(embed_tokens)", e);
 }
 
 // host rows [rows][cols] of `dtype` -> device bf16 rows at dst, dst row pitch `pitch_elems` (interleaving = pitch 2 * cols)
@@ -270,6 +312,10 @@ void fvhd_llm_destroy(fvhd_llm* c)
     if (c->ws) (void)hipFree(c->ws);
     for (char* p : c->retired) (void)hipFree(p);
     if (c->load_ev) (void)hipEventDestroy(c->load_ev);
+    if (c->emb) (void)hipFree(c->emb);
+    if (c->dc) (void)hipFree(c->dc);
+    if (c->pre_kv) (void)hipFree(c->pre_kv);
+    if (c->status_host) (void)hipHostFree(c->status_host);
     delete c;
 }
 
@@ -277,6 +323,13 @@ int fvhd_llm_set_tensor(fvhd_llm* c, const char* key, const void* host_data, int
 {
     if (!c || !key || !host_data || !shape) return lfail("fvhd_llm_set_tensor: NULL argument");
     if (dtype < 0 || dtype > 2) return lfail("fvhd_llm_set_tensor: bad dtype");
+    if (is_embed_key(key)) {
+        if (!(ndim == 2 && shape[0] == c->V && shape[1] == c->H)) return lfail(std::string("fvhd_llm_set_tensor: bad shape for ") + key);
+        DevGuard g(c->device);
+        if (g.err != hipSuccess) return lhip("hipSetDevice", g.err);
+        int e = ensure_emb(c);
+        return e ? e : upload_matrix(host_data, dtype, c->V, c->H, c->emb, c->H);
+    }
     int layer = -1, which = -1;
     const int idx = tensor_index(c, key, &layer, &which);
     if (idx < 0) return lfail(std::string("fvhd_llm_set_tensor: not a tensor of the Qwen2 decoder stack: ") + key);
@@ -320,6 +373,18 @@ int fvhd_llm_set_tensor(fvhd_llm* c, const char* key, const void* host_data, int
 int fvhd_llm_set_tensor_device(fvhd_llm* c, const char* key, const void* dev_data, int dtype, const int64_t* shape, int ndim, fvhd_stream_t stream)
 {
     if (!c || !key || !dev_data || !shape) return lfail("fvhd_llm_set_tensor_device: NULL argument");
+    if (is_embed_key(key)) {
+        if (!(ndim == 2 && shape[0] == c->V && shape[1] == c->H)) return lfail(std::string("fvhd_llm_set_tensor_device: bad shape for ") + key);
+        if (dtype != FVHD_BF16) return lfail("fvhd_llm_set_tensor_device: matrices must be bf16 on the device (model.embed_tokens.weight)");
+        DevGuard g(c->device);
+        if (g.err != hipSuccess) return lhip("hipSetDevice", g.err);
+        int e = ensure_emb(c);
+        if (e) return e;
+        const hipError_t he = hipMemcpyAsync(c->emb, dev_data, (size_t)c->V * c->H * 2, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+        if (he != hipSuccess) return lhip("hipMemcpyAsync(embed_tokens)", he);
+        const hipError_t se = hipStreamSynchronize((hipStream_t)stream);     // an optional tensor: no event bookkeeping, the copy is done here
+        return se == hipSuccess ? 0 : lhip("hipStreamSynchronize(embed_tokens)", se);
+    }
     int layer = -1, which = -1;
     const int idx = tensor_index(c, key, &layer, &which);
     if (idx < 0) return lfail(std::string("fvhd_llm_set_tensor_device: not a tensor of the Qwen2 decoder stack: ") + key);
@@ -527,6 +592,238 @@ int fvhd_llm_debug_hidden(fvhd_llm* c, void* out, int rows, fvhd_stream_t stream
     return e == hipSuccess ? 0 : lhip("hipMemcpyAsync", e);
 }
 
+// ---- decode: the library's own KV cache, one token per sequence per step (include/fvhd.h "LLM decode") ----
+}  // extern "C"
+
+namespace {
+
+fvhd_llm::Plan dec_plan(int N, int K, int ncu)
+{
+    // split K until the grid holds about two workgroups per CU (at most 16 slices: the last arriver reads them all)
+    const int ntiles = N / 16, ncol = (ntiles + 3) / 4, KC = K / 128;
+    const int want = (2 * ncu + ncol - 1) / ncol;
+    fvhd_llm::Plan p;
+    p.S = std::max(1, std::min(std::min(want, KC), 16));
+    p.cpw = (KC + p.S - 1) / p.S;
+    p.S = (KC + p.cpw - 1) / p.cpw;
+    return p;
+}
+
+void att_plan(int cap, int heads, int ncu, int* S, int* chunk)
+{
+    // key slices until the grid (batch * n_heads * slices) holds ~2 workgroups per CU - at B = 1 the 14 heads of Qwen2-0.5B alone fill
+    // 14 of 256 CUs - with at least 64 keys (one block per lane) per slice and at most 32 slices
+    const int want = (2 * ncu + heads - 1) / heads;
+    const int s = std::max(1, std::min(std::min(want, (cap + 63) / 64), 32));
+    *chunk = ((cap + s - 1) / s + 63) / 64 * 64;
+    *S = (cap + *chunk - 1) / *chunk;
+}
+
+int dec_status_error(const fvhd_llm* c, const char* who)
+{
+    const int st = *(volatile int*)c->status_host;
+    if (st == 1)
+        return lfail(std::string(who) + ": the KV cache is full (capacity " + std::to_string(c->dc_cap) +
+                     " positions): a decode step past it wrote nothing - reserve a larger cache (fvhd_llm_cache_reserve) and start again");
+    if (st == 2) return lfail(std::string(who) + ": a decode step was given a token id outside [0, vocab); it wrote nothing - start again");
+    return 0;
+}
+
+// the decode's input embedding: model.embed_tokens.weight when it was set, the packed lm_head rows only when the caller said the model ties them
+int dec_embedding_error(const fvhd_llm* c, const char* who)
+{
+    if (c->emb || c->tied == 1) return 0;
+    if (c->tied == 0)
+        return lfail(std::string(who) + ": this model does not tie its embeddings - set model.embed_tokens.weight (fvhd_llm_set_tensor) before decoding");
+    return lfail(std::string(who) + ": the decode's input embedding is unknown - set model.embed_tokens.weight (fvhd_llm_set_tensor), or call "
+                 "fvhd_llm_set_tied_embeddings(ctx, 1) for a model whose lm_head IS its embedding table (tie_word_embeddings)");
+}
+
+}  // namespace
+
+extern "C" {
+
+int fvhd_llm_set_tied_embeddings(fvhd_llm* c, int tied)
+{
+    if (!c) return lfail("fvhd_llm_set_tied_embeddings: ctx is NULL");
+    c->tied = tied != 0 ? 1 : 0;
+    return 0;
+}
+
+int fvhd_llm_cache_reserve(fvhd_llm* c, int batch, int capacity)
+{
+    if (!c || batch < 1 || batch > 16 || capacity < 1) return lfail("fvhd_llm_cache_reserve: needs a context, 1 <= batch <= 16 and capacity >= 1");
+    for (char g : c->got)
+        if (!g) return lfail("fvhd_llm_cache_reserve: weights incomplete (fvhd_llm_finalize reports the missing tensor)");
+    if (c->H % 128 || (c->nh * c->hd) % 128 || c->I % 128)
+        return lfail("fvhd_llm_cache_reserve: the decode needs hidden, n_heads * head_dim and intermediate to be multiples of 128");
+    DevGuard g(c->device);
+    if (g.err != hipSuccess) return lhip("hipSetDevice", g.err);
+    int e = ensure_ws(c, batch, 1, nullptr, false);              // the rotary table
+    if (e) return e;
+    int ncu = 0;
+    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || ncu <= 0) ncu = 256;
+    const int H = c->H, I = c->I, nh = c->nh, nkv = c->nkv, hd = c->hd, V = c->V, L = c->L;
+    c->p_qkv = dec_plan(c->qkvw, H, ncu);
+    c->p_o = dec_plan(H, nh * hd, ncu);
+    c->p_gu = dec_plan(2 * I, H, ncu);
+    c->p_d = dec_plan(H, I, ncu);
+    c->p_lm = fvhd_llm::Plan{1, H / 128};
+    att_plan(capacity, batch * nh, ncu, &c->att_S, &c->att_chunk);
+    size_t part = 0;
+    int ncol = 1;
+    for (auto pr : {std::make_pair(c->p_qkv, c->qkvw), std::make_pair(c->p_o, H), std::make_pair(c->p_gu, 2 * I), std::make_pair(c->p_d, H)}) {
+        if (pr.first.S > 1) part = std::max(part, (size_t)pr.first.S * pr.second * 64);
+        ncol = std::max(ncol, (pr.second / 16 + 3) / 4);
+    }
+    const int lm_ncol = (V / 16 + 3) / 4;
+    c->cnt_att = ncol;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += al256(bytes); return o; };
+    const size_t kvb = (size_t)L * batch * nkv * capacity * hd * 2;
+    const size_t o_k = take(kvb), o_v = take(kvb), o_mask = take((size_t)batch * capacity), o_pos = take(8 * batch), o_last = take(8 * batch),
+                 o_len = take(4), o_status = take(4), o_h = take((size_t)batch * H * 2), o_q = take((size_t)batch * nh * hd * 2),
+                 o_att = take((size_t)batch * nh * hd * 2), o_act = take((size_t)batch * I * 2), o_part = take(std::max(part, (size_t)16)),
+                 o_apart = take((size_t)batch * nh * c->att_S * (hd + 2) * 4), o_cnt = take((size_t)(ncol + batch * nh) * 4),
+                 o_av = take((size_t)lm_ncol * 16 * 4), o_ai = take((size_t)lm_ncol * 16 * 4), o_logits = take((size_t)batch * V * 4),
+                 o_rope = take((size_t)c->ws_pos * hd * 4);
+    hipError_t he = hipDeviceSynchronize();                      // refused while a stream is being captured (like fvhd_llm_reserve)
+    if (he != hipSuccess) return lhip("fvhd_llm_cache_reserve: hipDeviceSynchronize", he);
+    if (c->dc) (void)hipFree(c->dc);
+    c->dc = nullptr;
+    c->dc_batch = c->dc_cap = c->run_batch = 0;
+    if ((he = hipMalloc((void**)&c->dc, off)) != hipSuccess) return lhip("hipMalloc(llm KV cache)", he);
+    if ((he = hipMemset(c->dc, 0, off)) != hipSuccess) return lhip("hipMemset(llm KV cache)", he);      // counters start at zero
+    if (!c->status_host) {
+        if ((he = hipHostMalloc((void**)&c->status_host, 4, hipHostMallocMapped)) != hipSuccess) return lhip("hipHostMalloc(status word)", he);
+        if ((he = hipHostGetDevicePointer((void**)&c->status_host_dev, c->status_host, 0)) != hipSuccess) return lhip("hipHostGetDevicePointer", he);
+    }
+    *(volatile int*)c->status_host = 0;
+    char* d = c->dc;
+    c->kcache = d + o_k; c->vcache = d + o_v; c->mask = (unsigned char*)(d + o_mask); c->posv = (int64_t*)(d + o_pos); c->last_ids = (int64_t*)(d + o_last);
+    c->len = (int*)(d + o_len); c->status = (int*)(d + o_status); c->dh = d + o_h; c->dq = d + o_q; c->datt = d + o_att; c->dact = d + o_act;
+    c->dpart = (float*)(d + o_part); c->apart = (float*)(d + o_apart); c->cnt = (int*)(d + o_cnt); c->amax_v = (float*)(d + o_av);
+    c->amax_i = (int*)(d + o_ai); c->dlogits = (float*)(d + o_logits); c->drope = (float*)(d + o_rope);
+    c->dc_bytes = off; c->dc_batch = batch; c->dc_cap = capacity; c->dc_pos = c->ws_pos;
+    // the decode's own copy of the rotary table: a later, larger prefill may replace the prefill workspace under a captured decode graph
+    if ((he = hipMemcpy(c->drope, c->rope, (size_t)c->ws_pos * hd * 4, hipMemcpyDeviceToDevice)) != hipSuccess) return lhip("hipMemcpy(rope table)", he);
+    return 0;
+}
+
+int fvhd_llm_start(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* key_valid, const int64_t* position_ids, int batch, int seq_len,
+                   float* logits_out, int64_t* next_ids_out, fvhd_stream_t stream)
+{
+    if (!c || !embeds) return lfail("fvhd_llm_start: NULL argument");
+    if (!c->dc) return lfail("fvhd_llm_start: no KV cache - call fvhd_llm_cache_reserve first");
+    if (batch < 1 || batch > c->dc_batch) return lfail("fvhd_llm_start: batch must be in [1, the batch of fvhd_llm_cache_reserve]");
+    if (seq_len < 1 || seq_len > c->dc_cap) return lfail("fvhd_llm_start: seq_len must be in [1, the capacity of fvhd_llm_cache_reserve]");
+    if (int e = dec_embedding_error(c, "fvhd_llm_start")) return e;
+    DevGuard g(c->device);
+    if (g.err != hipSuccess) return lhip("hipSetDevice", g.err);
+    hipStream_t st = (hipStream_t)stream;
+    const int L = c->L, nkv = c->nkv, hd = c->hd, T = seq_len, B = batch, cap = c->dc_cap;
+    const size_t layer_src = (size_t)B * nkv * T * hd * 2, need = 2 * (size_t)L * layer_src;
+    if (need > c->pre_kv_bytes) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+            return lfail("fvhd_llm_start: its staging buffer must grow but the stream is being captured");
+        hipError_t he = hipDeviceSynchronize();
+        if (he != hipSuccess) return lhip("hipDeviceSynchronize", he);
+        if (c->pre_kv) (void)hipFree(c->pre_kv);
+        c->pre_kv = nullptr;
+        c->pre_kv_bytes = 0;
+        if ((he = hipMalloc((void**)&c->pre_kv, need)) != hipSuccess) return lhip("hipMalloc(prefill KV staging)", he);
+        c->pre_kv_bytes = need;
+    }
+    *(volatile int*)c->status_host = 0;
+    float* logits = logits_out ? logits_out : c->dlogits;
+    char* pk = c->pre_kv;
+    char* pv = c->pre_kv + (size_t)L * layer_src;
+    int e = fvhd_llm_prefill(c, embeds, dtype, key_valid, position_ids, B, T, logits, pk, pv, stream);
+    if (e) return e;
+    const size_t layer_dst = (size_t)c->dc_batch * nkv * cap * hd * 2;
+    for (int l = 0; l < L; ++l) {
+        hipError_t he = hipMemcpy2DAsync(c->kcache + l * layer_dst, (size_t)cap * hd * 2, pk + l * layer_src, (size_t)T * hd * 2, (size_t)T * hd * 2,
+                                         (size_t)B * nkv, hipMemcpyDeviceToDevice, st);
+        if (he == hipSuccess)
+            he = hipMemcpy2DAsync(c->vcache + l * layer_dst, (size_t)cap * hd * 2, pv + l * layer_src, (size_t)T * hd * 2, (size_t)T * hd * 2,
+                                  (size_t)B * nkv, hipMemcpyDeviceToDevice, st);
+        if (he != hipSuccess) return lhip("hipMemcpy2DAsync(KV cache)", he);
+    }
+    hipError_t he = hipMemsetAsync(c->mask, 0, (size_t)c->dc_batch * cap, st);
+    if (he == hipSuccess)
+        he = key_valid ? hipMemcpy2DAsync(c->mask, cap, key_valid, T, T, B, hipMemcpyDeviceToDevice, st) : hipMemset2DAsync(c->mask, cap, 1, T, B, st);
+    if (he != hipSuccess) return lhip("key mask copy", he);
+    // the first token: the same (max, index) pairs + reduce as the decode's lm_head (lowest index on ties), then the cache state
+    LCHECK(fvhd_launch_dec_argmax_blocks(st, logits, c->V, B, c->amax_v, c->amax_i), "first-token argmax (blocks)");
+    LCHECK(fvhd_launch_dec_argmax_finish(st, c->amax_v, c->amax_i, (c->V + 63) / 64, B, c->last_ids, next_ids_out, nullptr, nullptr, nullptr),
+           "first-token argmax (reduce)");
+    LCHECK(fvhd_launch_dec_start_state(st, c->posv, position_ids, B, T, c->len, c->status), "decode state");
+    c->run_batch = B;
+    return 0;
+}
+
+int fvhd_llm_decode(fvhd_llm* c, const int64_t* token_ids, float* logits_out, int64_t* next_ids_out, fvhd_stream_t stream)
+{
+    if (!c) return lfail("fvhd_llm_decode: ctx is NULL");
+    if (!c->dc || !c->run_batch) return lfail("fvhd_llm_decode: no started sequence - call fvhd_llm_cache_reserve and fvhd_llm_start first");
+    if (int e = dec_status_error(c, "fvhd_llm_decode")) return e;
+    if (int e = dec_embedding_error(c, "fvhd_llm_decode")) return e;
+    DevGuard g(c->device);
+    if (g.err != hipSuccess) return lhip("hipSetDevice", g.err);
+    hipStream_t st = (hipStream_t)stream;
+    const int B = c->run_batch, H = c->H, I = c->I, nh = c->nh, nkv = c->nkv, hd = c->hd, cap = c->dc_cap;
+    const char* w = c->wdev;
+    LCHECK(fvhd_launch_dec_embed(st, token_ids, c->last_ids, c->emb ? c->emb : w + c->lm_off, c->V, H, c->dh, c->mask, B, cap, c->len, c->status,
+                                 c->status_host_dev), "decode embed");
+    const size_t layer_kv = (size_t)c->dc_batch * nkv * cap * hd * 2;
+    auto gemm = [&](int epi, const void* x, int K, const float* norm_w, const void* W, int N, const fvhd_llm::Plan& p) {
+        DecGemmArgs a;
+        a.x = x; a.ldx = K; a.norm_w = norm_w; a.eps = c->eps; a.W = W; a.N = N; a.K = K; a.B = B; a.S = p.S; a.cpw = p.cpw;
+        a.part = c->dpart; a.cnt = c->cnt; a.epi = epi; a.status = c->status;
+        return a;
+    };
+    for (int l = 0; l < c->L; ++l) {
+        const LayerOff& o = c->lo[l];
+        DecGemmArgs a = gemm(DEC_EPI_QKV, c->dh, H, (const float*)(w + o.ln1), w + o.wqkv, c->qkvw, c->p_qkv);
+        a.bias = (const float*)(w + o.bqkv); a.out = c->dq; a.ldo = nh * hd; a.pos = c->posv; a.rope = c->drope; a.P = c->dc_pos; a.theta = c->theta;
+        a.nh = nh; a.nkv = nkv; a.hd = hd; a.kc = c->kcache + l * layer_kv; a.vc = c->vcache + l * layer_kv; a.cap = cap; a.len = c->len;
+        LCHECK(fvhd_launch_dec_gemm(st, &a), "decode q|k|v + rope + cache append");
+        LCHECK(fvhd_launch_dec_attention(st, c->dq, c->kcache + l * layer_kv, c->vcache + l * layer_kv, c->mask, c->datt, B, nh, nkv, hd, cap, c->len, 1,
+                                         c->att_S, c->att_chunk, c->apart, c->cnt + c->cnt_att, c->status), "decode attention");
+        a = gemm(DEC_EPI_RESID, c->datt, nh * hd, nullptr, w + o.wo, H, c->p_o);
+        a.resid = c->dh; a.out = c->dh; a.ldo = H;
+        LCHECK(fvhd_launch_dec_gemm(st, &a), "decode o_proj + residual");
+        a = gemm(DEC_EPI_SWIGLU, c->dh, H, (const float*)(w + o.ln2), w + o.wgu, 2 * I, c->p_gu);
+        a.out = c->dact; a.ldo = I;
+        LCHECK(fvhd_launch_dec_gemm(st, &a), "decode rmsnorm + gate|up + silu");
+        a = gemm(DEC_EPI_RESID, c->dact, I, nullptr, w + o.wd, H, c->p_d);
+        a.resid = c->dh; a.out = c->dh; a.ldo = H;
+        LCHECK(fvhd_launch_dec_gemm(st, &a), "decode down_proj + residual");
+    }
+    DecGemmArgs a = gemm(DEC_EPI_ARGMAX, c->dh, H, (const float*)(w + c->norm_off), w + c->lm_off, c->V, c->p_lm);
+    a.logits = logits_out; a.amax_v = c->amax_v; a.amax_i = c->amax_i;
+    LCHECK(fvhd_launch_dec_gemm(st, &a), "decode final norm + lm_head + argmax");
+    LCHECK(fvhd_launch_dec_argmax_finish(st, c->amax_v, c->amax_i, (c->V / 16 + 3) / 4, B, c->last_ids, next_ids_out, c->posv, c->len, c->status),
+           "decode argmax reduce");
+    return 0;
+}
+
+int fvhd_llm_cache_state(fvhd_llm* c, int* length, int* status)
+{
+    if (!c || !c->dc) return lfail("fvhd_llm_cache_state: no KV cache");
+    DevGuard g(c->device);
+    if (g.err != hipSuccess) return lhip("hipSetDevice", g.err);
+    int v[2] = {0, 0};
+    hipError_t he = hipDeviceSynchronize();
+    if (he == hipSuccess) he = hipMemcpy(&v[0], c->len, 4, hipMemcpyDeviceToHost);
+    if (he == hipSuccess) he = hipMemcpy(&v[1], c->status, 4, hipMemcpyDeviceToHost);
+    if (he != hipSuccess) return lhip("fvhd_llm_cache_state", he);
+    if (length) *length = v[0];
+    if (status) *status = v[1];
+    return 0;
+}
+
 // ---- single ops (unit tests) ----
 int fvhd_op_rmsnorm(fvhd_stream_t st, const void* x, void* y, const float* w, int M, int H, float eps)
 {
@@ -593,6 +890,70 @@ int fvhd_op_attention_causal(fvhd_stream_t st, const void* qkv, void* out, const
     if (!qkv || !out) return lfail("fvhd_op_attention_causal: NULL pointer");
     int e = fvhd_launch_llm_attention((hipStream_t)st, qkv, out, key_valid, B, T, n_heads, n_kv_heads, head_dim);
     return e ? lhip("fvhd_op_attention_causal", (hipError_t)e) : 0;
+}
+
+// ---- single ops of the decode step (unit tests) ----
+static void dec_split(DecGemmArgs& a, int splits)
+{
+    a.cpw = (a.K / 128 + splits - 1) / splits;
+    a.S = (a.K / 128 + a.cpw - 1) / a.cpw;
+}
+
+int fvhd_op_dec_gemm(fvhd_stream_t st, int epi, const void* x, int B, const float* norm_w, float eps, const void* Wt, int N, int K, const void* resid,
+                     void* out, float* partial, int* counters, int splits)
+{
+    if (!x || !Wt || !out || (epi == FVHD_EPI_RESID && !resid)) return lfail("fvhd_op_dec_gemm: NULL pointer");
+    if (epi != FVHD_EPI_RESID && epi != FVHD_EPI_SWIGLU) return lfail("fvhd_op_dec_gemm: epi must be FVHD_EPI_RESID or FVHD_EPI_SWIGLU");
+    if (B < 1 || B > 16 || N % 16 || K % 128 || splits < 1 || (splits > 1 && (!partial || !counters)))
+        return lfail("fvhd_op_dec_gemm: needs 1 <= B <= 16, N % 16 == 0, K % 128 == 0, splits >= 1 (and scratch when splits > 1)");
+    DecGemmArgs a;
+    a.x = x; a.ldx = K; a.norm_w = norm_w; a.eps = eps; a.W = Wt; a.N = N; a.K = K; a.B = B; a.part = partial; a.cnt = counters;
+    a.epi = epi; a.resid = resid; a.out = out; a.ldo = epi == FVHD_EPI_SWIGLU ? N / 2 : N;
+    dec_split(a, splits);
+    int e = fvhd_launch_dec_gemm((hipStream_t)st, &a);
+    return e ? lhip("fvhd_op_dec_gemm", (hipError_t)e) : 0;
+}
+
+int fvhd_op_dec_qkv(fvhd_stream_t st, const void* x, int B, int K, const float* norm_w, float eps, const void* Wt, const float* bias, void* q_out,
+                    const int64_t* pos, const float* table, int table_positions, float rope_theta, void* k_cache, void* v_cache, int capacity,
+                    const int* length, int n_heads, int n_kv_heads, int head_dim, float* partial, int* counters, int splits)
+{
+    if (!x || !Wt || !bias || !q_out || !pos || !table || !k_cache || !v_cache || !length) return lfail("fvhd_op_dec_qkv: NULL pointer");
+    if (B < 1 || B > 16 || K % 128 || splits < 1 || head_dim % 16 || n_heads < 1 || n_kv_heads < 1 || capacity < 1 || table_positions < 1 ||
+        (splits > 1 && (!partial || !counters)))
+        return lfail("fvhd_op_dec_qkv: needs 1 <= B <= 16, K % 128 == 0, head_dim % 16 == 0, splits >= 1 (and scratch when splits > 1)");
+    DecGemmArgs a;
+    a.x = x; a.ldx = K; a.norm_w = norm_w; a.eps = eps; a.W = Wt; a.N = (n_heads + 2 * n_kv_heads) * head_dim; a.K = K; a.B = B;
+    a.part = partial; a.cnt = counters; a.epi = DEC_EPI_QKV; a.bias = bias; a.out = q_out; a.ldo = n_heads * head_dim; a.pos = pos; a.rope = table;
+    a.P = table_positions; a.theta = rope_theta; a.nh = n_heads; a.nkv = n_kv_heads; a.hd = head_dim; a.kc = k_cache; a.vc = v_cache; a.cap = capacity;
+    a.len = length;
+    dec_split(a, splits);
+    int e = fvhd_launch_dec_gemm((hipStream_t)st, &a);
+    return e ? lhip("fvhd_op_dec_qkv", (hipError_t)e) : 0;
+}
+
+int fvhd_op_dec_attention(fvhd_stream_t st, const void* q, const void* k_cache, const void* v_cache, const uint8_t* key_valid, void* out, int B, int n_heads,
+                          int n_kv_heads, int head_dim, int capacity, const int* length, float* partial, int* counters, int splits)
+{
+    if (!q || !k_cache || !v_cache || !key_valid || !out || !length) return lfail("fvhd_op_dec_attention: NULL pointer");
+    if (splits < 1 || capacity < 1 || (splits > 1 && (!partial || !counters))) return lfail("fvhd_op_dec_attention: splits >= 1 (and scratch when splits > 1)");
+    const int chunk = ((capacity + splits - 1) / splits + 63) / 64 * 64, S = (capacity + chunk - 1) / chunk;
+    int e = fvhd_launch_dec_attention((hipStream_t)st, q, k_cache, v_cache, key_valid, out, B, n_heads, n_kv_heads, head_dim, capacity, length, 0, S, chunk,
+                                      partial, counters, nullptr);
+    return e ? lhip("fvhd_op_dec_attention", (hipError_t)e) : 0;
+}
+
+int fvhd_op_dec_lm_argmax(fvhd_stream_t st, const void* x, int B, const float* norm_w, float eps, const void* Wt, int V, int K, float* logits, int64_t* ids_out,
+                          float* scratch_v, int* scratch_i)
+{
+    if (!x || !Wt || !ids_out || !scratch_v || !scratch_i) return lfail("fvhd_op_dec_lm_argmax: NULL pointer");
+    if (B < 1 || B > 16 || V % 16 || K % 128) return lfail("fvhd_op_dec_lm_argmax: needs 1 <= B <= 16, V % 16 == 0, K % 128 == 0");
+    DecGemmArgs a;
+    a.x = x; a.ldx = K; a.norm_w = norm_w; a.eps = eps; a.W = Wt; a.N = V; a.K = K; a.B = B; a.S = 1; a.cpw = K / 128; a.epi = DEC_EPI_ARGMAX;
+    a.logits = logits; a.amax_v = scratch_v; a.amax_i = scratch_i;
+    int e = fvhd_launch_dec_gemm((hipStream_t)st, &a);
+    if (!e) e = fvhd_launch_dec_argmax_finish((hipStream_t)st, scratch_v, scratch_i, (V / 16 + 3) / 4, B, nullptr, ids_out, nullptr, nullptr, nullptr);
+    return e ? lhip("fvhd_op_dec_lm_argmax", (hipError_t)e) : 0;
 }
 
 }  // extern "C"

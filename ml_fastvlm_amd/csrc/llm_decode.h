@@ -1,0 +1,38 @@
+// Arguments of the decode-step weight-streaming GEMM (llm_decode.hip), shared with the launch sequence in llm_api.hip.
+#pragma once
+#include <stdint.h>
+
+#define DEC_EPI_RESID 4      // out[b][n] = bf16(resid[b][n] + acc)                        (o_proj / down_proj + the skip)
+#define DEC_EPI_SWIGLU 5     // out[b][j] = bf16(silu(acc[2j]) * acc[2j + 1])             (gate|up rows interleaved)
+#define DEC_EPI_QKV 6        // bias, ONE bf16 rounding, rotary embedding of q / k, q -> out, k / v -> cache slot *len
+#define DEC_EPI_ARGMAX 7     // fp32 logits (optional) + per-workgroup (max, index) of every row
+
+struct DecGemmArgs {
+    const void* x = nullptr;       // bf16 rows [B][ldx]; the first K columns are the operand
+    int ldx = 0;
+    const float* norm_w = nullptr; // non-NULL: Qwen2RMSNorm of the x rows (statistics over K) folded into the operand load
+    float eps = 1e-6f;
+    const void* W = nullptr;       // bf16 [N][K] (the packed layouts of the prefill)
+    int N = 0, K = 0, B = 0;
+    int S = 1, cpw = 0;            // K split over S workgroups of cpw 128-deep chunks (the last one may hold fewer)
+    float* part = nullptr;         // S > 1: fp32 slabs [S][N / 16][64][4]
+    int* cnt = nullptr;            // S > 1: one arrival counter per workgroup column, zero between launches (the last arriver resets it)
+    int epi = 0;
+    const void* resid = nullptr;   // RESID: bf16 [B][ldo] (may alias out)
+    void* out = nullptr;           // RESID / SWIGLU: bf16 [B][ldo]; QKV: q rows bf16 [B][ldo = n_heads * head_dim]
+    int ldo = 0;
+    const float* bias = nullptr;   // QKV: fp32 [N]
+    const int64_t* pos = nullptr;  // QKV: position of every row's token, int64 [B]
+    const float* rope = nullptr;   // QKV: (cos, sin) table [P][hd / 2][2]
+    int P = 0;
+    float theta = 1e6f;
+    int nh = 0, nkv = 0, hd = 0;
+    void* kc = nullptr;            // QKV: this layer's caches, bf16 [cache_batch][nkv][cap][hd]
+    void* vc = nullptr;
+    int cap = 0;
+    const int* len = nullptr;      // QKV: the slot the new token's k / v go to (device word)
+    float* logits = nullptr;       // ARGMAX: fp32 [B][N] or NULL
+    float* amax_v = nullptr;       // ARGMAX: [gridDim][16] best value / index of every row within the workgroup's columns
+    int* amax_i = nullptr;
+    const int* status = nullptr;   // non-NULL: the launch does nothing while *status != 0 (a step past the cache's capacity)
+};

@@ -35,6 +35,7 @@ class Qwen2Prefill:
         self.device = torch.device("cuda", device_index)
         self.hidden, self.n_layers, self.n_heads, self.n_kv_heads, self.head_dim = hidden, n_layers, n_heads, n_kv_heads, head_dim
         self.intermediate, self.vocab = intermediate, vocab
+        self.tie_word_embeddings = None           # from_hf records the config's flag (the decode's input embedding depends on it)
 
     # ---- construction from the reference's module -------------------------------------------------------------------------------
     @classmethod
@@ -60,6 +61,7 @@ class Qwen2Prefill:
         mpe = getattr(cfg, "max_position_embeddings", None)
         if mpe:                                   # rows of the rotary table; positions beyond it are computed in the kernel, never clamped
             _lib.check(_lib.load().fvhd_llm_set_max_positions(self._h, int(mpe)), "fvhd_llm_set_max_positions")
+        self.tie_word_embeddings = bool(getattr(cfg, "tie_word_embeddings", False))
         self.load_state_dict(model.state_dict())
         return self
 

@@ -1,0 +1,97 @@
+"""Decode-step time of the Qwen2 LLM on one MI355X: the library's steps (`ml_fastvlm_amd.qwen2_decode.Qwen2Generator`) replayed as one
+captured graph and called eagerly, against the stock `transformers` decode loop continuing from the same prefill cache.
+
+    python tools/decode_bench.py [--hidden 896 1536 3584] [--batch 1 8] [--prompt 285] [--new 128]
+
+Full layer counts, random bf16 weights (`tools/ttft.py: build_llm`).  Prints ONE JSON line: per (width, batch) the ms per token of each
+path, the bytes a step must read (packed weights + the KV cache at the mean length) and their fraction of 8 TB/s."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def _ms_per(fn, n, dev):
+    torch.cuda.synchronize(dev)
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(n):
+        fn()
+    b.record()
+    torch.cuda.synchronize(dev)
+    return a.elapsed_time(b) / n
+
+
+@torch.no_grad()
+def measure(hidden: int, batch: int, prompt: int, new: int, dev) -> dict:
+    from tools.ttft import build_llm
+    from ml_fastvlm_amd.qwen2_decode import Qwen2Generator
+    from ml_fastvlm_amd.qwen2_prefill import kv_to_dynamic_cache
+    llm = build_llm(hidden, dev)
+    cfg = llm.config
+    gen = Qwen2Generator.from_hf(llm, batch, prompt + new + 4)
+    g = torch.Generator(device=dev).manual_seed(0)
+    emb = (0.5 * torch.randn(batch, prompt, hidden, device=dev, generator=g)).to(torch.bfloat16)
+    mask = torch.ones(batch, prompt, device=dev, dtype=torch.long)
+    res = {"hidden": hidden, "layers": cfg.num_hidden_layers, "batch": batch, "prompt": prompt, "new_tokens": new}
+    # graph replay of one captured step
+    gen.start(emb, mask, logits=False)
+    graph = torch.cuda.CUDAGraph()
+    side = torch.cuda.Stream(dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        with torch.cuda.graph(graph, stream=side):
+            gen.step(logits=False)
+    torch.cuda.current_stream(dev).wait_stream(side)
+    graph.replay()
+    gen.start(emb, mask, logits=False)
+    res["graph_ms_per_token"] = round(_ms_per(graph.replay, new, dev), 4)
+    gen.start(emb, mask, logits=False)
+    res["eager_ms_per_token"] = round(_ms_per(lambda: gen.step(logits=False), new, dev), 4)
+    # the stock transformers loop (eager module calls, DynamicCache) continuing from the same prefill's cache
+    pre = gen.pre
+    logits, k, v = pre(emb, mask, None, return_kv=True)
+    cache = kv_to_dynamic_cache(k, v)
+    state = {"tok": logits.argmax(-1), "mask": mask, "pos": torch.full((batch, 1), prompt - 1, device=dev, dtype=torch.long)}
+
+    def hf_step():
+        state["mask"] = torch.cat([state["mask"], torch.ones(batch, 1, device=dev, dtype=torch.long)], 1)
+        state["pos"] = state["pos"] + 1
+        out = llm(input_ids=state["tok"][:, None], attention_mask=state["mask"], position_ids=state["pos"], past_key_values=cache, use_cache=True)
+        state["tok"] = out.logits[:, -1].argmax(-1)
+
+    for _ in range(3):                                      # lazy initialisation of the stock path stays out of the timing
+        hf_step()
+    res["stock_transformers_ms_per_token"] = round(_ms_per(hf_step, new, dev), 4)
+    I, H, nh, nkv, hd, V = cfg.intermediate_size, hidden, cfg.num_attention_heads, cfg.num_key_value_heads, hidden // cfg.num_attention_heads, cfg.vocab_size
+    wbytes = cfg.num_hidden_layers * ((nh + 2 * nkv) * hd * H + H * nh * hd + 3 * I * H) * 2 + V * H * 2
+    kvbytes = cfg.num_hidden_layers * batch * nkv * (prompt + new / 2) * hd * 2 * 2
+    res["weight_bytes_per_token"] = int(wbytes)
+    res["kv_bytes_per_token"] = int(kvbytes)
+    res["fraction_of_8TBps_graph"] = round((wbytes + kvbytes) / (res["graph_ms_per_token"] * 1e-3) / 8e12, 3)
+    res["speedup_graph_vs_stock"] = round(res["stock_transformers_ms_per_token"] / res["graph_ms_per_token"], 2)
+    del gen, pre, llm, cache, k, v
+    torch.cuda.empty_cache()
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--hidden", type=int, nargs="+", default=[896, 1536, 3584])
+    ap.add_argument("--batch", type=int, nargs="+", default=[1, 8])
+    ap.add_argument("--prompt", type=int, default=285)
+    ap.add_argument("--new", type=int, default=128)
+    a = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    rows = [measure(h, b, a.prompt, a.new, dev) for h in a.hidden for b in a.batch]
+    print(json.dumps({"tool": "decode_bench", "device": torch.cuda.get_device_name(dev), "results": rows}))
+
+
+if __name__ == "__main__":
+    main()
