@@ -48,8 +48,9 @@ typedef void* fvhd_stream_t; /* hipStream_t */
  * precision, fvhd_op_rope + rope_theta) - a mistake this number corrects; 500 = round 5 (adds the range guard, fvhd_op_dw7_amax,
  * fvhd_op_gemm_qkv_rope / fvhd_gemm_qkv_rope_supported, the fvhd_llm_* stream contract; no signature of round 4 changed); 501 adds the
  * LLM decode (fvhd_llm_cache_reserve / start / decode / cache_state / set_tied_embeddings, the optional model.embed_tokens.weight key,
- * fvhd_op_dec_*); nothing earlier changed. */
-#define FVHD_VERSION 501
+ * fvhd_op_dec_*); nothing earlier changed.  502 adds LLM sampling (fvhd_llm_set_sampling, fvhd_op_dec_sample): greedy stays the
+ * default and computes what 501 did; no earlier signature changed. */
+#define FVHD_VERSION 502
 int fvhd_version(void);
 const char* fvhd_last_error(void);
 
@@ -448,6 +449,27 @@ int fvhd_llm_start(fvhd_llm* ctx, const void* embeds, int dtype, const uint8_t* 
 int fvhd_llm_decode(fvhd_llm* ctx, const int64_t* token_ids, float* logits_out, int64_t* next_ids_out, fvhd_stream_t stream);
 /* synchronises the device, then: the cache length and the error word (0 = fine, 1 = past capacity, 2 = token id out of range) */
 int fvhd_llm_cache_state(fvhd_llm* ctx, int* length, int* status);
+
+/* ---- LLM sampling: temperature / top-k / top-p on the device ------------------------------------------------------------------------
+ * transformers' multinomial sampling for num_beams = 1 (TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper in that order,
+ * min_tokens_to_keep = 1): s = logits / temperature (IEEE fp32 division); top_k >= 1 keeps s >= the min(top_k, V)-th largest value, ties
+ * included (0 = off); top_p in [0, 1) keeps a token when the normalised mass of the tokens before it in descending s is < top_p, the top
+ * token always (1 = off); then one draw from the softmax over the kept set.  The kept set is {s >= theta}: tokens tied exactly at the
+ * top-p boundary are kept as a group, where transformers' unstable sort may split them.  The draw is the inverse CDF in token-index order:
+ * the smallest kept index whose prefix mass exceeds u * Z, Z = sum of exp(s - s_max) over the kept set.  u = (x0 >> 8) * 2^-24 of
+ * Philox4x32-10 with key (seed low word, seed high word) and counter (row, n, 0, 0), n = the cache length when the token is chosen (the
+ * prompt length for the token fvhd_llm_start chooses, + 1 per decode step).  Only the distribution equals torch.multinomial's, not its
+ * draws.  Deterministic: the same logits, settings, seed and n give the same id, eager or replayed from a graph.
+ * do_sample = 0 (the default) is greedy, what fvhd_llm_start / fvhd_llm_decode did before: the argmax, bit for bit.  The settings are read
+ * when fvhd_llm_start / fvhd_llm_decode enqueue, so a captured graph keeps those it was captured with.  Refused: a temperature that is
+ * not finite or not > 0, top_k < 0, top_p outside [0, 1].  With sampling, the step writes its logits to the caller's logits_out or to the
+ * context's own buffer, and replaces the argmax reduce by the sampler's launches (llm_sample.hip). */
+int fvhd_llm_set_sampling(fvhd_llm* ctx, int do_sample, float temperature, int top_k, float top_p, unsigned long long seed);
+/* the sampler on its own (tests): logits fp32 [B, V] (1 <= B <= 16, V >= 1) -> ids int64 [B]; n = the Philox counter's second word;
+ * u_override: NULL (Philox) or fp32 [B]; info: NULL or fp32 [B, 4] = (theta, kept count, Z, u).  Allocates a process-wide workspace on
+ * first use: eager calls only, not during stream capture. */
+int fvhd_op_dec_sample(fvhd_stream_t stream, const float* logits, int B, int V, float temperature, int top_k, float top_p, unsigned long long seed,
+                       int n, const float* u_override, int64_t* ids, float* info);
 
 /* single ops of the decode step (unit-test entry points); B in [1, 16]; K % 128 == 0; `splits` = workgroups per output tile along K
  * (partial: fp32 scratch [splits][N * 16], counters: int [ceil(N / 64)] ZEROED before the first call - each launch leaves them zero)

@@ -11,7 +11,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # FVHD_LIB: another build of the same ABI (the ablation library of `python -m ml_fastvlm_amd.build` with FVHD_FFN_ABLATE=1)
 LIB_PATH = os.environ.get("FVHD_LIB") or os.path.join(_HERE, "libfvhd.so")
 
-ABI_VERSION = 501               # FVHD_VERSION of the include/fvhd.h this stub was written against (major = ABI_VERSION // 100)
+ABI_VERSION = 501               # the oldest FVHD_VERSION (include/fvhd.h) this stub loads (major = ABI_VERSION // 100)
+SAMPLING_VERSION = 502          # the first with fvhd_llm_set_sampling / fvhd_op_dec_sample (declared only when the library has them)
 F32, F16, BF16 = 0, 1, 2
 FFN_HALF, FFN_BF16 = 0, 1        # precision of the fused ConvFFN's hidden activation (include/fvhd.h)
 EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_LS_RESID, EPI_RESID, EPI_SWIGLU = 0, 1, 2, 3, 4, 5
@@ -104,6 +105,11 @@ def _declare(lib) -> None:
         "fvhd_op_dec_attention": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, ci]),
         "fvhd_op_dec_lm_argmax": (ci, [vp, vp, ci, vp, cf, vp, ci, ci, vp, vp, vp, vp]),
     }
+    if lib.fvhd_version() >= SAMPLING_VERSION:     # an older library loads without them; sampling_lib() then names the rebuild
+        sig.update({
+            "fvhd_llm_set_sampling": (ci, [vp, ci, cf, ci, cf, C.c_ulonglong]),
+            "fvhd_op_dec_sample": (ci, [vp, vp, ci, ci, cf, ci, cf, C.c_ulonglong, ci, vp, vp, vp]),
+        })
     del fp, cl
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)     # AttributeError here = the .so does not export what fvhd.h declares
@@ -130,6 +136,17 @@ def load():
         _declare(lib)
         _lib = lib
     return _lib
+
+
+def sampling_lib():
+    """load(), for the sampling entry points: a library older than SAMPLING_VERSION loads (greedy decoding works on it) but has none of
+    them, and this says so instead of an AttributeError."""
+    lib = load()
+    got = lib.fvhd_version()
+    if got < SAMPLING_VERSION:
+        raise FvhdError(f"{LIB_PATH} reports ABI version {got}: sampling (fvhd_llm_set_sampling, fvhd_op_dec_sample) needs {SAMPLING_VERSION} - "
+                        "rebuild the library (`python -m ml_fastvlm_amd.build`)")
+    return lib
 
 
 def check(code: int, what: str = "") -> None:

@@ -11,6 +11,7 @@ the MI355X tower into an unmodified checkout of apple/ml-fastvlm.
 """
 from __future__ import annotations
 
+import math
 import re
 
 import torch
@@ -91,13 +92,16 @@ def encode_images(vision_tower, mm_projector, images):
     return project(vision_tower, mm_projector, image_features)
 
 
-def install_into_llava(splice: bool = False, prefill: bool = False, prefill_any_dtype: bool = False) -> None:
+def install_into_llava(splice: bool = False, prefill: bool = False, prefill_any_dtype: bool = False, generate: bool = False) -> None:
     """Make an unmodified `llava` package (the reference) build and call the MI355X tower; splice=True also routes
     `prepare_inputs_labels_for_multimodal` through the GPU splice (needs the embeddings on a HIP device); prefill=True also runs the
     PREFILL step of `LlavaQwen2ForCausalLM.forward` (`llava_qwen.py:92-103`: the first forward of `generate`, on `inputs_embeds`
     with an empty cache) on the hand-written Qwen2 kernels (`ml_fastvlm_amd.qwen2_prefill`), handing the KV cache to the stock
     decode loop.  The kernels compute in bf16: by default only a bf16 model takes them (an fp32 / fp16 model keeps the reference's forward
-    and its precision); prefill_any_dtype=True opts such a model in knowingly (its prefill then runs in bf16, the cache is cast back)."""
+    and its precision); prefill_any_dtype=True opts such a model in knowingly (its prefill then runs in bf16, the cache is cast back).
+    generate=True replaces `LlavaQwen2ForCausalLM.generate` (`llava_qwen.py:106-143`) by `_make_library_generate`: the unchanged call of
+    predict.py (sampling included) then runs its prefill and every decode step on the library, and any setting the library does not
+    implement falls back to the reference's generate with a one-time warning."""
     import llava.model.llava_arch as arch
     import llava.model.multimodal_encoder.builder as enc_builder
 
@@ -122,6 +126,10 @@ def install_into_llava(splice: bool = False, prefill: bool = False, prefill_any_
         import llava.model.language_model.llava_qwen as lq
         cur = lq.LlavaQwen2ForCausalLM.forward
         lq.LlavaQwen2ForCausalLM.forward = _make_prefill_forward(getattr(cur, "_fvhd_orig", cur), any_dtype=prefill_any_dtype)
+    if generate:
+        import llava.model.language_model.llava_qwen as lq
+        cur = lq.LlavaQwen2ForCausalLM.generate
+        lq.LlavaQwen2ForCausalLM.generate = _make_library_generate(getattr(cur, "_fvhd_orig", cur))
 
 
 def _is_fresh_dynamic_cache(pkv) -> bool:
@@ -268,18 +276,109 @@ def generate(model, input_ids, images=None, image_sizes=None, attention_mask=Non
     if lm_w.device.type != "cuda" or lm_w.dtype != torch.bfloat16:
         raise ValueError(f"ml_fastvlm_amd.generate: needs a bf16 model on a HIP device (got {lm_w.dtype} on {lm_w.device}); "
                          "the decode kernels compute in bf16")
-    position_ids = None
-    if images is not None:
-        (input_ids, position_ids, attention_mask, _, inputs_embeds, _) = model.prepare_inputs_labels_for_multimodal(
-            input_ids, position_ids, attention_mask, None, None, images, image_sizes=image_sizes)
-    else:
-        inputs_embeds = model.get_input_embeddings()(input_ids)
     gc = getattr(model, "generation_config", None)
     if eos_token_id is None:
         eos_token_id = getattr(gc, "eos_token_id", None)
     if pad_token_id is None:
         pad_token_id = getattr(gc, "pad_token_id", None)
+    return _generate_on_library(model, input_ids, images, image_sizes, attention_mask, None, max_new_tokens, eos_token_id, pad_token_id)
+
+
+def _generate_on_library(model, input_ids, images, image_sizes, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id,
+                         sampling=None):
+    """the body shared by `generate` and `_make_library_generate`: the multimodal splice (or the token embedding), then the prefill and every
+    decode step on the library - `Qwen2Generator.greedy`, or `.sample(**sampling)`"""
+    if images is not None:
+        (input_ids, position_ids, attention_mask, _, inputs_embeds, _) = model.prepare_inputs_labels_for_multimodal(
+            input_ids, position_ids, attention_mask, None, None, images, image_sizes=image_sizes)
+    else:
+        inputs_embeds = model.get_input_embeddings()(input_ids)
     B, T = inputs_embeds.shape[:2]
     gen = generator_context(model, B, T + max_new_tokens)
-    return gen.greedy(inputs_embeds, attention_mask, position_ids, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id,
-                      pad_token_id=pad_token_id)
+    if sampling is None:
+        return gen.greedy(inputs_embeds, attention_mask, position_ids, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id,
+                          pad_token_id=pad_token_id)
+    return gen.sample(inputs_embeds, attention_mask, position_ids, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id,
+                      pad_token_id=pad_token_id, **sampling)
+
+
+# GenerationConfig fields whose value (beside None) means "this processor / mode is off"; any other value is a setting the library does
+# not implement, and `_make_library_generate` leaves the call to the reference's generate
+_OFF = {
+    "num_beams": (1,), "num_return_sequences": (1,), "num_beam_groups": (1,), "diversity_penalty": (0.0,), "penalty_alpha": (),
+    "repetition_penalty": (1.0,), "encoder_repetition_penalty": (1.0,), "min_p": (), "top_h": (), "typical_p": (1.0,),
+    "epsilon_cutoff": (0.0,), "eta_cutoff": (0.0,), "no_repeat_ngram_size": (0,), "encoder_no_repeat_ngram_size": (0,), "bad_words_ids": (),
+    "suppress_tokens": (), "begin_suppress_tokens": (), "sequence_bias": (), "forced_bos_token_id": (), "forced_eos_token_id": (),
+    "exponential_decay_length_penalty": (), "renormalize_logits": (False,), "remove_invalid_values": (False,), "guidance_scale": (1.0,),
+    "watermarking_config": (), "min_length": (0,), "min_new_tokens": (0,), "max_time": (), "stop_strings": (), "dola_layers": (),
+    "constraints": (), "force_words_ids": (), "token_healing": (False,), "low_memory": (False,), "prompt_lookup_num_tokens": (),
+    "cache_implementation": (), "use_mtp": (False,), "output_scores": (False,), "output_logits": (False,), "return_dict_in_generate": (False,),
+    "output_attentions": (False,), "output_hidden_states": (False,),
+}
+# generate()'s own arguments beside **kwargs: any of them given asks for something the library does not do
+_GENERATE_ARGS = ("generation_config", "logits_processor", "stopping_criteria", "prefix_allowed_tokens_fn", "synced_gpus", "assistant_model",
+                  "streamer", "negative_prompt_ids", "negative_prompt_attention_mask", "custom_generate", "assistant_tokenizer", "tokenizer")
+
+
+def _library_generate_settings(model, kwargs):
+    """transformers' own resolution of a generate(**kwargs) call (`_prepare_generation_config`, which generate itself calls: its global
+    defaults such as top_k = 50, the model's generation_config, then the call's arguments) -> (settings, None) when the library can run
+    it, (None, reason) when it cannot.  settings: max_new_tokens, eos_token_id, pad_token_id and `sampling` (None = greedy, else the
+    keyword arguments of Qwen2Generator.sample)."""
+    for k in _GENERATE_ARGS:
+        if kwargs.get(k) is not None:
+            return None, f"{k} is given"
+    try:
+        gc, model_kwargs = model._prepare_generation_config(None, **kwargs)
+    except Exception as e:                                       # a setting transformers itself rejects: its generate reports it
+        return None, f"the settings do not resolve ({type(e).__name__}: {e})"
+    extra = sorted(k for k, v in model_kwargs.items() if v is not None)
+    if extra:
+        return None, f"model arguments {extra}"
+    for k, off in _OFF.items():
+        v = getattr(gc, k, None)
+        if v is not None and v not in off:
+            return None, f"{k}={v!r}"
+    if gc.max_new_tokens is None:
+        return None, "max_new_tokens is not given"
+    if not gc.use_cache:
+        return None, "use_cache=False"
+    sampling = None
+    if gc.do_sample:
+        sampling = dict(temperature=1.0 if gc.temperature is None else float(gc.temperature), top_k=int(gc.top_k or 0),
+                        top_p=1.0 if gc.top_p is None else float(gc.top_p))
+        if not (0.0 < sampling["temperature"] < math.inf) or not 0.0 <= sampling["top_p"] <= 1.0 or sampling["top_k"] < 0:
+            return None, f"temperature={gc.temperature!r}, top_k={gc.top_k!r}, top_p={gc.top_p!r}"
+    return dict(max_new_tokens=int(gc.max_new_tokens), eos_token_id=gc.eos_token_id, pad_token_id=gc.pad_token_id, sampling=sampling), None
+
+
+def _make_library_generate(orig_generate):
+    """`LlavaQwen2ForCausalLM.generate` (`llava_qwen.py:106-143`) on the library: the same argument handling (position_ids / attention_mask
+    popped, inputs_embeds refused), the settings resolved as transformers resolves them (`_library_generate_settings`), then the
+    multimodal splice and `Qwen2Generator.greedy` / `.sample` on `generator_context(model, ...)`.  It takes the library only for greedy or
+    temperature / top-k / top-p sampling with num_beams = 1, one sequence per prompt, no other logits processor, stopping criterion or
+    streamer, max_new_tokens given, use_cache, no scores / dict output, a bf16 model on a HIP device and a batch of at most 16; anything
+    else is the original generate, with a one-time warning that names the reason.  Returns the new tokens [B, n], as the reference's
+    generate(inputs_embeds=...) does."""
+    def generate(self, inputs=None, images=None, image_sizes=None, **kwargs):
+        if "inputs_embeds" in kwargs:                            # as the reference (llava_qwen.py:120-121)
+            raise NotImplementedError("`inputs_embeds` is not supported")
+        settings, reason = _library_generate_settings(self, {k: v for k, v in kwargs.items() if k not in ("position_ids", "attention_mask")})
+        lm_w = self.lm_head.weight
+        if settings is not None and (lm_w.device.type != "cuda" or lm_w.dtype != torch.bfloat16):
+            settings, reason = None, f"the model is {lm_w.dtype} on {lm_w.device} (the library decodes a bf16 model on a HIP device)"
+        if settings is not None and inputs is not None and inputs.shape[0] > 16:
+            settings, reason = None, f"batch {inputs.shape[0]} > 16"
+        if settings is None:
+            warned = getattr(self, "_fvhd_generate_warned", frozenset())
+            if reason not in warned:
+                import warnings
+                warnings.warn(f"ml_fastvlm_amd: generate stays on the reference ({reason})")
+                object.__setattr__(self, "_fvhd_generate_warned", warned | {reason})
+            return orig_generate(self, inputs, images, image_sizes, **kwargs)
+        with torch.no_grad():
+            return _generate_on_library(self, inputs, images, image_sizes, kwargs.get("attention_mask"), kwargs.get("position_ids"),
+                                        settings["max_new_tokens"], settings["eos_token_id"], settings["pad_token_id"], settings["sampling"])
+    generate._fvhd_generate = True
+    generate._fvhd_orig = orig_generate
+    return generate

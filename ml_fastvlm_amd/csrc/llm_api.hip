@@ -35,6 +35,9 @@ int fvhd_launch_dec_embed(hipStream_t, const int64_t*, const int64_t*, const voi
 int fvhd_launch_dec_argmax_finish(hipStream_t, const float*, const int*, int, int, int64_t*, int64_t*, int64_t*, int*, const int*);
 int fvhd_launch_dec_argmax_blocks(hipStream_t, const float*, int, int, float*, int*);
 int fvhd_launch_dec_start_state(hipStream_t, int64_t*, const int64_t*, int, int, int*, int*);
+// llm_sample.hip
+size_t fvhd_dec_sample_ws_bytes(void);
+int fvhd_launch_dec_sample(hipStream_t, const DecSampleArgs*, void*);
 }
 
 namespace {
@@ -137,6 +140,12 @@ struct fvhd_llm {
     int att_S = 1, att_chunk = 0;
     char* pre_kv = nullptr;                // the prefill's own [n_layers][batch][nkv][seq_len][hd] caches, copied into the strided ones
     size_t pre_kv_bytes = 0;
+    // fvhd_llm_set_sampling: read when fvhd_llm_start / fvhd_llm_decode enqueue (a captured graph keeps what it was captured with)
+    int do_sample = 0;
+    float temperature = 1.f, top_p = 1.f;
+    int top_k = 0;
+    unsigned long long seed = 0;
+    char* sws = nullptr;                   // the sampler's workspace (inside `dc`)
 };
 
 namespace {
@@ -629,6 +638,21 @@ int dec_status_error(const fvhd_llm* c, const char* who)
     return 0;
 }
 
+DecSampleArgs dec_sample_args(const fvhd_llm* c, const float* logits, int B)
+{
+    DecSampleArgs a;
+    a.logits = logits; a.B = B; a.V = c->V; a.temperature = c->temperature; a.top_k = c->top_k; a.top_p = c->top_p; a.seed = c->seed;
+    return a;
+}
+
+const char* sampling_error(float temperature, int top_k, float top_p)
+{
+    if (!(temperature > 0.f) || !std::isfinite(temperature)) return "temperature must be finite and > 0";
+    if (top_k < 0) return "top_k must be >= 0 (0 = off)";
+    if (!(top_p >= 0.f && top_p <= 1.f)) return "top_p must be in [0, 1] (1 = off)";
+    return nullptr;
+}
+
 // the decode's input embedding: model.embed_tokens.weight when it was set, the packed lm_head rows only when the caller said the model ties them
 int dec_embedding_error(const fvhd_llm* c, const char* who)
 {
@@ -686,7 +710,7 @@ int fvhd_llm_cache_reserve(fvhd_llm* c, int batch, int capacity)
                  o_att = take((size_t)batch * nh * hd * 2), o_act = take((size_t)batch * I * 2), o_part = take(std::max(part, (size_t)16)),
                  o_apart = take((size_t)batch * nh * c->att_S * (hd + 2) * 4), o_cnt = take((size_t)(ncol + batch * nh) * 4),
                  o_av = take((size_t)lm_ncol * 16 * 4), o_ai = take((size_t)lm_ncol * 16 * 4), o_logits = take((size_t)batch * V * 4),
-                 o_rope = take((size_t)c->ws_pos * hd * 4);
+                 o_rope = take((size_t)c->ws_pos * hd * 4), o_sws = take(fvhd_dec_sample_ws_bytes());
     hipError_t he = hipDeviceSynchronize();                      // refused while a stream is being captured (like fvhd_llm_reserve)
     if (he != hipSuccess) return lhip("fvhd_llm_cache_reserve: hipDeviceSynchronize", he);
     if (c->dc) (void)hipFree(c->dc);
@@ -703,7 +727,7 @@ int fvhd_llm_cache_reserve(fvhd_llm* c, int batch, int capacity)
     c->kcache = d + o_k; c->vcache = d + o_v; c->mask = (unsigned char*)(d + o_mask); c->posv = (int64_t*)(d + o_pos); c->last_ids = (int64_t*)(d + o_last);
     c->len = (int*)(d + o_len); c->status = (int*)(d + o_status); c->dh = d + o_h; c->dq = d + o_q; c->datt = d + o_att; c->dact = d + o_act;
     c->dpart = (float*)(d + o_part); c->apart = (float*)(d + o_apart); c->cnt = (int*)(d + o_cnt); c->amax_v = (float*)(d + o_av);
-    c->amax_i = (int*)(d + o_ai); c->dlogits = (float*)(d + o_logits); c->drope = (float*)(d + o_rope);
+    c->amax_i = (int*)(d + o_ai); c->dlogits = (float*)(d + o_logits); c->drope = (float*)(d + o_rope); c->sws = d + o_sws;
     c->dc_bytes = off; c->dc_batch = batch; c->dc_cap = capacity; c->dc_pos = c->ws_pos;
     // the decode's own copy of the rotary table: a later, larger prefill may replace the prefill workspace under a captured decode graph
     if ((he = hipMemcpy(c->drope, c->rope, (size_t)c->ws_pos * hd * 4, hipMemcpyDeviceToDevice)) != hipSuccess) return lhip("hipMemcpy(rope table)", he);
@@ -754,6 +778,17 @@ int fvhd_llm_start(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* ke
     if (he == hipSuccess)
         he = key_valid ? hipMemcpy2DAsync(c->mask, cap, key_valid, T, T, B, hipMemcpyDeviceToDevice, st) : hipMemset2DAsync(c->mask, cap, 1, T, B, st);
     if (he != hipSuccess) return lhip("key mask copy", he);
+    if (c->do_sample) {
+        // sampling: the cache state first, so that the draw reads n = the prompt length from the device
+        LCHECK(fvhd_launch_dec_start_state(st, c->posv, position_ids, B, T, c->len, c->status), "decode state");
+        DecSampleArgs a = dec_sample_args(c, logits, B);
+        a.len = c->len;
+        a.last = c->last_ids;
+        a.ids_out = next_ids_out;
+        LCHECK(fvhd_launch_dec_sample(st, &a, c->sws), "first-token sampling");
+        c->run_batch = B;
+        return 0;
+    }
     // the first token: the same (max, index) pairs + reduce as the decode's lm_head (lowest index on ties), then the cache state
     LCHECK(fvhd_launch_dec_argmax_blocks(st, logits, c->V, B, c->amax_v, c->amax_i), "first-token argmax (blocks)");
     LCHECK(fvhd_launch_dec_argmax_finish(st, c->amax_v, c->amax_i, (c->V + 63) / 64, B, c->last_ids, next_ids_out, nullptr, nullptr, nullptr),
@@ -803,9 +838,32 @@ int fvhd_llm_decode(fvhd_llm* c, const int64_t* token_ids, float* logits_out, in
     }
     DecGemmArgs a = gemm(DEC_EPI_ARGMAX, c->dh, H, (const float*)(w + c->norm_off), w + c->lm_off, c->V, c->p_lm);
     a.logits = logits_out; a.amax_v = c->amax_v; a.amax_i = c->amax_i;
+    if (c->do_sample) {
+        // sampling replaces the argmax reduce: it reads the logits (the caller's, else the context's buffer), chooses with n = length + 1
+        // (the cache holds this step's token), and advances positions and length
+        if (!a.logits) a.logits = c->dlogits;
+        LCHECK(fvhd_launch_dec_gemm(st, &a), "decode final norm + lm_head");
+        DecSampleArgs sa = dec_sample_args(c, a.logits, B);
+        sa.len = c->len; sa.n_add = 1; sa.last = c->last_ids; sa.ids_out = next_ids_out; sa.posv = c->posv; sa.len_advance = c->len;
+        sa.status = c->status;
+        LCHECK(fvhd_launch_dec_sample(st, &sa, c->sws), "decode sampling");
+        return 0;
+    }
     LCHECK(fvhd_launch_dec_gemm(st, &a), "decode final norm + lm_head + argmax");
     LCHECK(fvhd_launch_dec_argmax_finish(st, c->amax_v, c->amax_i, (c->V / 16 + 3) / 4, B, c->last_ids, next_ids_out, c->posv, c->len, c->status),
            "decode argmax reduce");
+    return 0;
+}
+
+int fvhd_llm_set_sampling(fvhd_llm* c, int do_sample, float temperature, int top_k, float top_p, unsigned long long seed)
+{
+    if (!c) return lfail("fvhd_llm_set_sampling: ctx is NULL");
+    if (const char* e = sampling_error(temperature, top_k, top_p)) return lfail(std::string("fvhd_llm_set_sampling: ") + e);
+    c->do_sample = do_sample != 0;
+    c->temperature = temperature;
+    c->top_k = top_k;
+    c->top_p = top_p;
+    c->seed = seed;
     return 0;
 }
 
@@ -954,6 +1012,30 @@ int fvhd_op_dec_lm_argmax(fvhd_stream_t st, const void* x, int B, const float* n
     int e = fvhd_launch_dec_gemm((hipStream_t)st, &a);
     if (!e) e = fvhd_launch_dec_argmax_finish((hipStream_t)st, scratch_v, scratch_i, (V / 16 + 3) / 4, B, nullptr, ids_out, nullptr, nullptr, nullptr);
     return e ? lhip("fvhd_op_dec_lm_argmax", (hipError_t)e) : 0;
+}
+
+// the sampler on its own: a process-wide workspace, allocated (and its counters zeroed) on first use - eager calls only
+int fvhd_op_dec_sample(fvhd_stream_t st, const float* logits, int B, int V, float temperature, int top_k, float top_p, unsigned long long seed, int n,
+                       const float* u_override, int64_t* ids, float* info)
+{
+    if (!logits || !ids) return lfail("fvhd_op_dec_sample: NULL pointer");
+    if (B < 1 || B > 16 || V < 1) return lfail("fvhd_op_dec_sample: needs 1 <= B <= 16 and V >= 1");
+    if (const char* e = sampling_error(temperature, top_k, top_p)) return lfail(std::string("fvhd_op_dec_sample: ") + e);
+    static char* ws[64] = {};
+    int dev = 0;
+    hipError_t he = hipGetDevice(&dev);
+    if (he != hipSuccess) return lhip("hipGetDevice", he);
+    if (dev < 0 || dev >= 64) return lfail("fvhd_op_dec_sample: device index out of range");
+    if (!ws[dev]) {
+        const size_t bytes = fvhd_dec_sample_ws_bytes();
+        if ((he = hipMalloc((void**)&ws[dev], bytes)) != hipSuccess) { ws[dev] = nullptr; return lhip("hipMalloc(sampler workspace)", he); }
+        if ((he = hipMemset(ws[dev], 0, bytes)) != hipSuccess) return lhip("hipMemset(sampler workspace)", he);
+    }
+    DecSampleArgs a;
+    a.logits = logits; a.B = B; a.V = V; a.temperature = temperature; a.top_k = top_k; a.top_p = top_p; a.seed = seed; a.n_add = n;
+    a.u_override = u_override; a.ids_out = ids; a.info = info;
+    int e = fvhd_launch_dec_sample((hipStream_t)st, &a, ws[dev]);
+    return e ? lhip("fvhd_op_dec_sample", (hipError_t)e) : 0;
 }
 
 }  // extern "C"

@@ -36,3 +36,22 @@ struct DecGemmArgs {
     int* amax_i = nullptr;
     const int* status = nullptr;   // non-NULL: the launch does nothing while *status != 0 (a step past the cache's capacity)
 };
+
+// Arguments of the sampler (llm_sample.hip): temperature / top-k / top-p over fp32 logits [B][V], one draw per row.
+struct DecSampleArgs {
+    const float* logits = nullptr;
+    int B = 0, V = 0;
+    float temperature = 1.f;       // > 0
+    int top_k = 0;                 // 0 = off
+    float top_p = 1.f;             // 1 = off
+    unsigned long long seed = 0;   // Philox key: low word, high word
+    const int* len = nullptr;      // Philox counter (row, n = (len ? *len : 0) + n_add, 0, 0)
+    int n_add = 0;
+    const float* u_override = nullptr;   // non-NULL: u [B] instead of Philox
+    int64_t* last = nullptr;       // chosen ids [B] (each optional)
+    int64_t* ids_out = nullptr;
+    float* info = nullptr;         // [B][4]: theta, kept count, Z, u
+    int64_t* posv = nullptr;       // non-NULL: positions += 1
+    int* len_advance = nullptr;    // non-NULL: *len_advance += 1 once every row has read n
+    const int* status = nullptr;
+};

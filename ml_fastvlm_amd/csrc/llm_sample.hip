@@ -1,0 +1,430 @@
+// Token sampling on the device: temperature / top-k / top-p over the fp32 logits [B][V] of the lm_head (include/fvhd.h "LLM sampling").
+//
+// transformers' multinomial sampling for num_beams = 1 (min_tokens_to_keep = 1), in the order of its logits processors:
+//   s = logits / T (IEEE division), top-k keeps s >= the min(k, V)-th largest value (ties kept), top-p keeps a token when the
+//   normalised mass of the tokens before it (descending s) is < top_p, then one draw from the softmax over the kept set.
+// Both filters keep a prefix by value, so the kept set is {i : s_i >= theta} for one threshold per row; tokens tied at the top-p
+// boundary are kept as a group (transformers' unstable sort may split them).
+//
+// Launches (grid = S slices x B rows, 256 threads; each pass reads the whole row, the slices meet in the last-arriving workgroup of the
+// row as in the decode GEMM's split-K):
+//   dec_sample_max      the row maximum -> s_max, and the row's search state
+//   dec_sample_level    one 8-bit digit of the threshold's order-preserving 32-bit key per launch (MSB first): a 256-bin histogram of
+//                       counts and exp(s - s_max) masses of the keys that match the digits found so far; 4 launches find the top-k
+//                       threshold (by count), 4 more the top-p threshold among its kept set (by mass).  The histograms sum integers
+//                       (counts, and masses in 2^-40 fixed point) so their totals do not depend on the order of the LDS adds; there
+//                       are no floating-point atomics.
+//   dec_sample_draw     Z = sum of exp(s - s_max) over the kept set (per-thread contiguous chunks in index order, chunk sums scanned in a
+//                       fixed order), u from Philox4x32-10, and the inverse CDF in TOKEN-INDEX order: the smallest kept index whose
+//                       prefix mass is > u * Z (the last kept token if rounding finds none).  Same distribution as a draw in sorted
+//                       order, no sort.  Then the ids, the optional info row, and - behind every row - the advance of positions / length.
+// Everything is deterministic: the same logits, settings, seed and n give the same id, eager or replayed.
+#include "fvhd_common.h"
+#include "llm_decode.h"
+
+namespace {
+
+constexpr int SMAX = 32;                         // slices per row
+constexpr int BMAX = 16;                         // rows
+enum { SM_TOPK = 1, SM_TOPP = 2, SM_DRAW = 3 };
+
+struct SampleRow {                               // per-row search state, written by the row's last-arriving workgroup
+    float smax;
+    unsigned prefix;                             // the threshold key's digits found so far
+    int shift;                                   // bit position of the next digit (24 .. 0)
+    int mode;
+    unsigned cnt_above;                          // keys above the prefix (and >= lo_key)
+    unsigned lo_key;                             // top-p after top-k: only keys >= the top-k threshold take part
+    unsigned theta_key;                          // SM_DRAW: the kept set is {key >= theta_key}
+    int target_set;
+    unsigned long long mass_above;               // fixed-point mass of those keys
+    unsigned long long target;                   // top-p: top_p * Z_k, fixed point
+};
+
+struct SampleWs {
+    SampleRow* rows;                             // [BMAX]
+    float* pmax;                                 // [BMAX][SMAX]
+    unsigned* hc;                                // [BMAX][SMAX][256]
+    unsigned long long* hm;                      // [BMAX][SMAX][256]
+    float* dpre;                                 // [BMAX][SMAX][256] exclusive prefix of the chunk masses within the slice
+    float* dchunk;                               // [BMAX][SMAX][256] chunk masses
+    float* dsum;                                 // [BMAX][SMAX] slice mass
+    int* dlast;                                  // [BMAX][SMAX] last kept index of the slice (-1: none)
+    unsigned* dcnt;                              // [BMAX][SMAX] kept count of the slice
+    int* cnt;                                    // [BMAX + 1] arrival counters (zero between launches)
+};
+
+size_t al256s(size_t x) { return (x + 255) & ~(size_t)255; }
+
+SampleWs carve(void* base)
+{
+    char* p = (char*)base;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char* q = p + off; off += al256s(bytes); return q; };
+    SampleWs w;
+    w.rows = (SampleRow*)take(sizeof(SampleRow) * BMAX);
+    w.pmax = (float*)take(4 * BMAX * SMAX);
+    w.hc = (unsigned*)take(4 * BMAX * SMAX * 256);
+    w.hm = (unsigned long long*)take(8 * BMAX * SMAX * 256);
+    w.dpre = (float*)take(4 * BMAX * SMAX * 256);
+    w.dchunk = (float*)take(4 * BMAX * SMAX * 256);
+    w.dsum = (float*)take(4 * BMAX * SMAX);
+    w.dlast = (int*)take(4 * BMAX * SMAX);
+    w.dcnt = (unsigned*)take(4 * BMAX * SMAX);
+    w.cnt = (int*)take(4 * (BMAX + 1));
+    return w;
+}
+
+size_t ws_bytes()
+{
+    return al256s(sizeof(SampleRow) * BMAX) + 2 * al256s(4 * BMAX * SMAX) + al256s(4 * BMAX * SMAX * 256) + al256s(8 * BMAX * SMAX * 256) +
+           2 * al256s(4 * BMAX * SMAX * 256) + 2 * al256s(4 * BMAX * SMAX) + al256s(4 * (BMAX + 1));
+}
+
+// the in-launch hand-off of llm_decode.hip: every thread's stores are done; true (in every thread) in the workgroup that arrived last for
+// counter `c`, which it resets for the next launch
+__device__ bool arrive_last(int* c, int n, int* flag)
+{
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const int t = __hip_atomic_fetch_add(c, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int last = t == n - 1;
+        if (last) {
+            __hip_atomic_store(c, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        *flag = last;
+    }
+    __syncthreads();
+    return *flag != 0;
+}
+
+// order-preserving key of an fp32 value: a > b <=> key(a) > key(b); -0 and +0 share one key
+FVHD_DEV unsigned okey(float s)
+{
+    unsigned u = __float_as_uint(s);
+    if (u == 0x80000000u) u = 0;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+FVHD_DEV float key_value(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+FVHD_DEV float scaled(float x, float T) { return __fdiv_rn(x, T); }     // TemperatureLogitsWarper: scores / temperature, IEEE
+
+FVHD_DEV unsigned long long fixed_mass(float e) { return (unsigned long long)(e * 0x1p40f); }
+
+// Philox4x32-10 (Salmon et al., SC'11): counter (c0..c3), key (k0, k1) -> the first output word
+FVHD_DEV unsigned philox_x0(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1)
+{
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0;
+        c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1;
+        c3 = lo0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return c0;
+}
+
+// slice s of S over a row of V: [i0, i1)
+FVHD_DEV void slice_of(int V, int S, int s, int& i0, int& i1)
+{
+    const int L = (V + S - 1) / S;
+    i0 = min(s * L, V);
+    i1 = min(i0 + L, V);
+}
+
+// inclusive scan over 256 threads in LDS (Hillis-Steele; a fixed order of additions)
+template <typename T>
+FVHD_DEV T block_scan_incl(T v, T* buf)
+{
+    const int tid = threadIdx.x;
+    buf[tid] = v;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {
+        const T add = tid >= o ? buf[tid - o] : (T)0;
+        __syncthreads();
+        v += add;
+        buf[tid] = v;
+        __syncthreads();
+    }
+    return v;
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------
+// the row maximum (s_max = max(logits) / T: IEEE division is monotonic) and the initial search state
+__global__ __launch_bounds__(256) void dec_sample_max_kernel(const DecSampleArgs a, const SampleWs w)
+{
+    if (a.status && *a.status) return;
+    __shared__ float red[4];
+    __shared__ int flag;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.y, s = blockIdx.x, S = gridDim.x;
+    const float* x = a.logits + (size_t)b * a.V;
+    int i0, i1;
+    slice_of(a.V, S, s, i0, i1);
+    float m = -INFINITY;
+    for (int i = i0 + tid; i < i1; i += 256) m = fmaxf(m, x[i]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    if (lane == 0) red[wave] = m;
+    __syncthreads();
+    if (tid == 0) w.pmax[b * SMAX + s] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    if (!arrive_last(w.cnt + b, S, &flag)) return;
+    if (tid == 0) {
+        float M = -INFINITY;
+        for (int t = 0; t < S; ++t) M = fmaxf(M, w.pmax[b * SMAX + t]);
+        const bool topk = a.top_k > 0 && a.top_k < a.V, topp = a.top_p < 1.0f;
+        SampleRow r;
+        r.smax = scaled(M, a.temperature);
+        r.prefix = 0;
+        r.shift = 24;
+        r.mode = topk ? SM_TOPK : topp ? SM_TOPP : SM_DRAW;
+        r.cnt_above = 0;
+        r.lo_key = 0;
+        r.theta_key = 0;
+        r.target_set = 0;
+        r.mass_above = 0;
+        r.target = 0;
+        w.rows[b] = r;
+    }
+}
+
+// one 8-bit digit of the threshold key (see the file comment)
+__global__ __launch_bounds__(256) void dec_sample_level_kernel(const DecSampleArgs a, const SampleWs w)
+{
+    if (a.status && *a.status) return;
+    __shared__ unsigned hc[256];
+    __shared__ unsigned long long hm[256];
+    __shared__ unsigned long long scan64[256];
+    __shared__ unsigned scan32[256];
+    __shared__ int flag, pick;
+    const int tid = threadIdx.x, b = blockIdx.y, s = blockIdx.x, S = gridDim.x;
+    const SampleRow r = w.rows[b];
+    if (r.mode != SM_TOPK && r.mode != SM_TOPP) return;                        // row resolved: every workgroup of it leaves
+    hc[tid] = 0;
+    hm[tid] = 0;
+    __syncthreads();
+    const float* x = a.logits + (size_t)b * a.V;
+    int i0, i1;
+    slice_of(a.V, S, s, i0, i1);
+    const float T = a.temperature, M = r.smax;
+    const int shift = r.shift;
+    const unsigned pre = r.prefix, lo = r.lo_key;
+    const bool top = shift == 24;
+    for (int i = i0 + tid; i < i1; i += 256) {
+        const float v = scaled(x[i], T);
+        const unsigned k = okey(v);
+        if (k >= lo && (top || (k >> (shift + 8)) == pre)) {
+            const int d = (k >> shift) & 255;
+            atomicAdd(&hc[d], 1u);
+            atomicAdd(&hm[d], fixed_mass(expf(v - M)));
+        }
+    }
+    __syncthreads();
+    const size_t slab = ((size_t)b * SMAX + s) * 256 + tid;
+    w.hc[slab] = hc[tid];
+    w.hm[slab] = hm[tid];
+    if (!arrive_last(w.cnt + b, S, &flag)) return;
+    // the row's histogram: thread j = bin j; j' = 255 - j orders the bins by descending key, so an inclusive scan over j' gives the keys at
+    // or above bin j
+    const int j = 255 - tid;
+    unsigned c = 0;
+    unsigned long long m = 0;
+    for (int t = 0; t < S; ++t) {
+        c += w.hc[((size_t)b * SMAX + t) * 256 + j];
+        m += w.hm[((size_t)b * SMAX + t) * 256 + j];
+    }
+    const unsigned c_incl = block_scan_incl<unsigned>(c, scan32);
+    const unsigned long long m_incl = block_scan_incl<unsigned long long>(m, scan64);
+    const unsigned above_c = r.cnt_above + c_incl - c;
+    const unsigned long long above_m = r.mass_above + m_incl - m;
+    unsigned long long target = r.target;
+    if (r.mode == SM_TOPP && !r.target_set)                                     // top-p alone: Z over the whole row (the level-0 total)
+        target = (unsigned long long)((double)a.top_p * (double)scan64[255]);
+    if (tid == 0) pick = -1;
+    __syncthreads();
+    bool chosen;
+    if (r.mode == SM_TOPK) {
+        const unsigned need = (unsigned)a.top_k;
+        chosen = c > 0 && above_c < need && above_c + c >= need;                // the bin holding the k-th largest key
+    } else {
+        // kept: nothing (or less than top_p of the mass) lies above; the top token always.  above_m grows with j', so the kept bins are
+        // the j' up to the largest eligible one - the lowest kept key
+        if (c > 0 && (above_m < target || above_m == 0)) atomicMax(&pick, tid);
+        __syncthreads();
+        chosen = tid == pick;
+    }
+    if (!chosen) return;
+    SampleRow n = r;
+    n.prefix = (top ? 0u : (pre << 8)) | (unsigned)j;
+    n.cnt_above = above_c;
+    n.mass_above = above_m;
+    n.target = target;
+    n.target_set = r.mode == SM_TOPP ? 1 : r.target_set;
+    if (shift > 0) {
+        n.shift = shift - 8;
+    } else if (r.mode == SM_TOPK && a.top_p < 1.0f) {                           // top-k resolved: top-p over its kept set next
+        n.mode = SM_TOPP;
+        n.prefix = 0;
+        n.shift = 24;
+        n.lo_key = (pre << 8) | (unsigned)j;
+        n.cnt_above = 0;
+        n.mass_above = 0;
+        n.target = (unsigned long long)((double)a.top_p * (double)(above_m + m));
+        n.target_set = 1;
+    } else {
+        n.mode = SM_DRAW;
+        n.theta_key = (pre << 8) | (unsigned)j;
+    }
+    w.rows[b] = n;
+}
+
+// Z, the draw in token-index order, the ids and the advance (see the file comment)
+__global__ __launch_bounds__(256) void dec_sample_draw_kernel(const DecSampleArgs a, const SampleWs w)
+{
+    if (a.status && *a.status) return;
+    __shared__ float scan[256];
+    __shared__ float ssum[SMAX];
+    __shared__ int slast[SMAX];
+    __shared__ unsigned scnt[SMAX];
+    __shared__ int flag, pick_t, pick_s, pick_id;
+    __shared__ float base_s, target_s, z_s, u_s;
+    __shared__ unsigned kept_s;
+    __shared__ int ilast[4];
+    __shared__ unsigned icnt[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.y, s = blockIdx.x, S = gridDim.x;
+    const SampleRow r = w.rows[b];
+    const float* x = a.logits + (size_t)b * a.V;
+    const float T = a.temperature, M = r.smax;
+    const unsigned theta = r.mode == SM_DRAW ? r.theta_key : 0u;
+    int i0, i1;
+    slice_of(a.V, S, s, i0, i1);
+    const int C = (i1 - i0 + 255) / 256;
+    const int c0 = min(i0 + tid * C, i1), c1 = min(c0 + C, i1);
+    float local = 0.f;
+    int last = -1;
+    unsigned cnt = 0;
+    for (int i = c0; i < c1; ++i) {
+        const float v = scaled(x[i], T);
+        if (okey(v) >= theta) { local += expf(v - M); last = i; ++cnt; }
+    }
+    const float incl = block_scan_incl<float>(local, scan);
+    const size_t slab = ((size_t)b * SMAX + s) * 256 + tid;
+    w.dpre[slab] = incl - local;
+    w.dchunk[slab] = local;
+    int lm = last;
+    unsigned cs = cnt;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { lm = max(lm, __shfl_xor(lm, o, 64)); cs += __shfl_xor(cs, o, 64); }
+    if (lane == 0) { ilast[wave] = lm; icnt[wave] = cs; }
+    __syncthreads();
+    if (tid == 0) {
+        w.dlast[b * SMAX + s] = max(max(ilast[0], ilast[1]), max(ilast[2], ilast[3]));
+        w.dcnt[b * SMAX + s] = icnt[0] + icnt[1] + icnt[2] + icnt[3];
+    }
+    if (tid == 255) w.dsum[b * SMAX + s] = incl;                                // the slice total: the scan's last element
+    if (!arrive_last(w.cnt + b, S, &flag)) return;
+    if (tid < S) {
+        ssum[tid] = w.dsum[b * SMAX + tid];
+        slast[tid] = w.dlast[b * SMAX + tid];
+        scnt[tid] = w.dcnt[b * SMAX + tid];
+    }
+    if (tid == 0) pick_t = 256;
+    __syncthreads();
+    if (tid == 0) {
+        float Z = 0.f;
+        unsigned kept = 0;
+        int lastk = -1;
+        for (int t = 0; t < S; ++t) { Z += ssum[t]; kept += scnt[t]; lastk = max(lastk, slast[t]); }
+        float u;
+        if (a.u_override) {
+            u = a.u_override[b];
+        } else {
+            const int n = (a.len ? *a.len : 0) + a.n_add;
+            u = (float)(philox_x0((unsigned)b, (unsigned)n, 0u, 0u, (unsigned)a.seed, (unsigned)(a.seed >> 32)) >> 8) * 0x1p-24f;
+        }
+        const float target = u * Z;
+        float cum = 0.f;
+        int ps = -1;
+        for (int t = 0; t < S; ++t) {
+            if (scnt[t] > 0 && cum + ssum[t] > target) { ps = t; break; }
+            cum += ssum[t];
+        }
+        pick_s = ps;
+        pick_id = ps < 0 ? lastk : -1;
+        base_s = cum;
+        target_s = target;
+        z_s = Z;
+        u_s = u;
+        kept_s = kept;
+    }
+    __syncthreads();
+    const int ps = pick_s;
+    if (ps >= 0) {
+        const size_t sl = ((size_t)b * SMAX + ps) * 256 + tid;
+        const float base = base_s + w.dpre[sl], ch = w.dchunk[sl];
+        if (ch > 0.f && base + ch > target_s) atomicMin(&pick_t, tid);
+        __syncthreads();
+        if (tid == pick_t) {                                                     // walk the chunk with the sum order of the first pass
+            int p0, p1;
+            slice_of(a.V, S, ps, p0, p1);
+            const int Cp = (p1 - p0 + 255) / 256;
+            const int q0 = min(p0 + tid * Cp, p1), q1 = min(q0 + Cp, p1);
+            float acc = 0.f;
+            int id = -1;
+            for (int i = q0; i < q1; ++i) {
+                const float v = scaled(x[i], T);
+                if (okey(v) >= theta) {
+                    acc += expf(v - M);
+                    id = i;
+                    if (base + acc > target_s) break;
+                }
+            }
+            pick_id = id;
+        }
+        __syncthreads();
+        if (tid == 0 && pick_id < 0) pick_id = slast[ps];                       // rounding: the slice's last kept token
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const int64_t id = pick_id < 0 ? 0 : pick_id;
+        if (a.last) a.last[b] = id;
+        if (a.ids_out) a.ids_out[b] = id;
+        if (a.posv) a.posv[b] += 1;
+        if (a.info) {
+            a.info[b * 4 + 0] = theta == 0u ? -INFINITY : key_value(theta);
+            a.info[b * 4 + 1] = (float)kept_s;
+            a.info[b * 4 + 2] = z_s;
+            a.info[b * 4 + 3] = u_s;
+        }
+    }
+    // every row has read n: the last row to get here advances the length
+    if (a.len_advance && arrive_last(w.cnt + BMAX, gridDim.y, &flag) && tid == 0) *a.len_advance += 1;
+}
+
+// ---------------------------------------------------------------------------------------------------
+extern "C" size_t fvhd_dec_sample_ws_bytes(void) { return ws_bytes(); }
+
+extern "C" int fvhd_launch_dec_sample(hipStream_t st, const DecSampleArgs* a, void* ws)
+{
+    if (!a->logits || !ws || a->B < 1 || a->B > BMAX || a->V < 1 || !(a->temperature > 0.f) || a->top_k < 0 || !(a->top_p >= 0.f && a->top_p <= 1.f))
+        return (int)hipErrorInvalidValue;
+    const SampleWs w = carve(ws);
+    const int S = a->V >= SMAX * 2048 ? SMAX : (a->V + 2047) / 2048;
+    const dim3 grid((unsigned)S, (unsigned)a->B), block(256);
+    hipLaunchKernelGGL(dec_sample_max_kernel, grid, block, 0, st, *a, w);
+    const int levels = 4 * ((a->top_k > 0 && a->top_k < a->V) + (a->top_p < 1.f));
+    for (int l = 0; l < levels; ++l) hipLaunchKernelGGL(dec_sample_level_kernel, grid, block, 0, st, *a, w);
+    hipLaunchKernelGGL(dec_sample_draw_kernel, grid, block, 0, st, *a, w);
+    return (int)hipGetLastError();
+}

@@ -10,7 +10,9 @@ replays for the whole generation.
     tokens = gen.greedy(inputs_embeds, attention_mask, None, max_new_tokens=256, eos_token_id=eos, pad_token_id=pad)
 
 `greedy` returns what transformers' greedy `generate(inputs_embeds=...)` returns: the new tokens only, [B, n], stopped at the step
-where every sequence has finished, finished sequences padded with `pad_token_id`.
+where every sequence has finished, finished sequences padded with `pad_token_id`.  `sample` does the same with transformers' multinomial
+sampling (temperature / top-k / top-p, include/fvhd.h "LLM sampling") chosen on the device inside the captured step: the same
+distribution as transformers', not the same draws (the random numbers are Philox4x32-10 keyed by the seed, `philox_uniform`).
 """
 from __future__ import annotations
 
@@ -21,6 +23,28 @@ import torch
 
 from . import _lib
 from .qwen2_prefill import Qwen2Prefill
+
+
+_PHILOX_M = (0xD2511F53, 0xCD9E8D57)
+_PHILOX_W = (0x9E3779B9, 0xBB67AE85)
+
+
+def philox4x32_10(counter: Sequence[int], key: Sequence[int]) -> list:
+    """Philox4x32-10 (Salmon et al., SC'11): 4 counter words, 2 key words -> 4 output words (the device's generator, restated)"""
+    c0, c1, c2, c3 = (int(x) & 0xFFFFFFFF for x in counter)
+    k0, k1 = (int(x) & 0xFFFFFFFF for x in key)
+    for _ in range(10):
+        p0, p1 = _PHILOX_M[0] * c0, _PHILOX_M[1] * c2
+        c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & 0xFFFFFFFF, (p0 >> 32) ^ c3 ^ k1, p0 & 0xFFFFFFFF
+        k0, k1 = (k0 + _PHILOX_W[0]) & 0xFFFFFFFF, (k1 + _PHILOX_W[1]) & 0xFFFFFFFF
+    return [c0, c1, c2, c3]
+
+
+def philox_uniform(seed: int, row: int, n: int) -> float:
+    """the sampler's u for batch row `row` when the cache holds n tokens: (x0 >> 8) * 2^-24 of Philox4x32-10 with counter (row, n, 0, 0)
+    and key (seed low word, seed high word) - exact in fp32"""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return (philox4x32_10((row, n, 0, 0), (seed, seed >> 32))[0] >> 8) * 2.0 ** -24
 
 
 def generation_position_ids(attention_mask: Optional[torch.Tensor], batch: int, seq_len: int, device=None) -> torch.Tensor:
@@ -106,7 +130,19 @@ class Qwen2Generator:
         _lib.check(_lib.load().fvhd_llm_cache_state(self.pre._h, C.byref(n), C.byref(st)), "fvhd_llm_cache_state")
         return n.value, st.value
 
-    # ---- greedy generation ---------------------------------------------------------------------------------------------------------------
+    # ---- sampling settings ---------------------------------------------------------------------------------------------------------------
+    def set_sampling(self, do_sample: bool = False, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0) -> None:
+        """the selection of start() / step() from now on (`fvhd_llm_set_sampling`): greedy (the default) or sampling; a captured step keeps the
+        settings it was captured with.  top_k 0 and top_p 1 are off; the seed is the Philox key (64 bits)."""
+        lib = _lib.sampling_lib()
+        _lib.check(lib.fvhd_llm_set_sampling(self.pre._h, int(bool(do_sample)), float(temperature), int(top_k), float(top_p),
+                                             int(seed) & 0xFFFFFFFFFFFFFFFF), "fvhd_llm_set_sampling")
+
+    def _set_greedy(self) -> None:
+        if _lib.load().fvhd_version() >= _lib.SAMPLING_VERSION:      # a library without sampling is greedy anyway
+            self.set_sampling(False)
+
+    # ---- generation --------------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def greedy(self, inputs_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None,
                max_new_tokens: int = 256, eos_token_id: Union[None, int, Sequence[int]] = None, pad_token_id: Optional[int] = None,
@@ -114,6 +150,27 @@ class Qwen2Generator:
         """transformers' greedy search (`GenerationMixin._sample` with do_sample=False) on the library's steps -> new tokens [B, n].
         graph=True captures one step (decode + the finished-sequence bookkeeping) into a CUDA graph and replays it; "all finished" is
         polled every `poll_every` steps (no host synchronisation per token) and the output trimmed to the step where it happened."""
+        self._set_greedy()
+        return self._run(inputs_embeds, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id, graph, poll_every)
+
+    @torch.no_grad()
+    def sample(self, inputs_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None,
+               max_new_tokens: int = 256, temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, seed: Optional[int] = None,
+               eos_token_id: Union[None, int, Sequence[int]] = None, pad_token_id: Optional[int] = None, graph: bool = True,
+               poll_every: int = 16) -> torch.Tensor:
+        """transformers' multinomial sampling (`GenerationMixin._sample` with do_sample=True, num_beams=1: temperature, then top-k, then
+        top-p) on the library's steps -> new tokens [B, n], with greedy's return contract, EOS / pad bookkeeping and graph replay.
+        seed None: 63 bits from torch's default CPU generator, so `torch.manual_seed` makes a run repeat.  The same seed gives the same
+        tokens, eager or graph; the draws are not torch.multinomial's (only the distribution is the same)."""
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.long).item())
+        self.set_sampling(True, temperature, top_k, top_p, seed)
+        try:
+            return self._run(inputs_embeds, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id, graph, poll_every)
+        finally:
+            self.set_sampling(False)
+
+    def _run(self, inputs_embeds, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id, graph, poll_every) -> torch.Tensor:
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be >= 1")
         B, T = inputs_embeds.shape[:2]

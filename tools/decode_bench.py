@@ -2,6 +2,11 @@
 captured graph and called eagerly, against the stock `transformers` decode loop continuing from the same prefill cache.
 
     python tools/decode_bench.py [--hidden 896 1536 3584] [--batch 1 8] [--prompt 285] [--new 128]
+    python tools/decode_bench.py --sample [--hidden 896] [--batch 1 8]
+
+--sample times the sampled step (`Qwen2Generator.set_sampling`, csrc/llm_sample.hip) next to the greedy one, both by graph replay at
+vocab 151936, with predict.py's settings (temperature 0.2, top_k 50: transformers' default) and a flat one (temperature 1.0, top_k 0,
+top_p 0.95); greedy is timed before and after the sampled settings and averaged.
 
 Full layer counts, random bf16 weights (`tools/ttft.py: build_llm`).  Prints ONE JSON line: per (width, batch) the ms per token of each
 path, the bytes a step must read (packed weights + the KV cache at the mean length) and their fraction of 8 TB/s."""
@@ -81,14 +86,69 @@ def measure(hidden: int, batch: int, prompt: int, new: int, dev) -> dict:
     return res
 
 
+SAMPLE_SETTINGS = {"predict_py": dict(temperature=0.2, top_k=50, top_p=1.0), "flat": dict(temperature=1.0, top_k=0, top_p=0.95)}
+
+
+@torch.no_grad()
+def measure_sample(hidden: int, batch: int, prompt: int, new: int, dev) -> dict:
+    from tools.ttft import build_llm
+    from ml_fastvlm_amd.qwen2_decode import Qwen2Generator
+    llm = build_llm(hidden, dev)
+    gen = Qwen2Generator.from_hf(llm, batch, prompt + new + 4)
+    g = torch.Generator(device=dev).manual_seed(0)
+    emb = (0.5 * torch.randn(batch, prompt, hidden, device=dev, generator=g)).to(torch.bfloat16)
+    mask = torch.ones(batch, prompt, device=dev, dtype=torch.long)
+    res = {"hidden": hidden, "layers": llm.config.num_hidden_layers, "batch": batch, "vocab": llm.config.vocab_size, "prompt": prompt,
+           "new_tokens": new}
+
+    def graph_ms(settings):
+        if settings is None:
+            gen.set_sampling(False)
+        else:
+            gen.set_sampling(True, seed=1, **settings)
+        gen.start(emb, mask, logits=False)
+        graph = torch.cuda.CUDAGraph()
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            with torch.cuda.graph(graph, stream=side):
+                gen.step(logits=False)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        graph.replay()
+        gen.start(emb, mask, logits=False)
+        ms = _ms_per(graph.replay, new, dev)
+        assert gen.cache_state() == (prompt + new, 0)
+        return ms
+
+    greedy = [graph_ms(None)]
+    for name, st in SAMPLE_SETTINGS.items():
+        res[f"{name}_settings"] = st
+        res[f"{name}_graph_ms_per_token"] = round(graph_ms(st), 4)
+    greedy.append(graph_ms(None))
+    gen.set_sampling(False)
+    res["greedy_graph_ms_per_token"] = round(sum(greedy) / 2, 4)
+    res["greedy_graph_ms_per_token_runs"] = [round(x, 4) for x in greedy]
+    for name in SAMPLE_SETTINGS:
+        res[f"{name}_added_us_per_token"] = round(1000 * (res[f"{name}_graph_ms_per_token"] - res["greedy_graph_ms_per_token"]), 1)
+    del gen, llm
+    torch.cuda.empty_cache()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--hidden", type=int, nargs="+", default=[896, 1536, 3584])
     ap.add_argument("--batch", type=int, nargs="+", default=[1, 8])
     ap.add_argument("--prompt", type=int, default=285)
     ap.add_argument("--new", type=int, default=128)
+    ap.add_argument("--sample", action="store_true", help="the sampled step against the greedy one (default widths: 896 only)")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
+    if a.sample:
+        hidden = a.hidden if "--hidden" in sys.argv else [896]
+        rows = [measure_sample(h, b, a.prompt, a.new, dev) for h in hidden for b in a.batch]
+        print(json.dumps({"tool": "decode_bench", "mode": "sample", "device": torch.cuda.get_device_name(dev), "results": rows}))
+        return
     rows = [measure(h, b, a.prompt, a.new, dev) for h in a.hidden for b in a.batch]
     print(json.dumps({"tool": "decode_bench", "device": torch.cuda.get_device_name(dev), "results": rows}))
 
