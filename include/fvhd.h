@@ -454,8 +454,10 @@ int fvhd_llm_cache_state(fvhd_llm* ctx, int* length, int* status);
  * transformers' multinomial sampling for num_beams = 1 (TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper in that order,
  * min_tokens_to_keep = 1): s = logits / temperature (IEEE fp32 division); top_k >= 1 keeps s >= the min(top_k, V)-th largest value, ties
  * included (0 = off); top_p in [0, 1) keeps a token when the normalised mass of the tokens before it in descending s is < top_p, the top
- * token always (1 = off); then one draw from the softmax over the kept set.  The kept set is {s >= theta}: tokens tied exactly at the
- * top-p boundary are kept as a group, where transformers' unstable sort may split them.  The draw is the inverse CDF in token-index order:
+ * token always (1 = off); then one draw from the softmax over the kept set.  The kept set is {s >= theta, s > -inf}: a -inf logit is
+ * never kept, counted or drawn, and tokens tied exactly at the top-p boundary are kept as a group, where transformers' unstable sort may
+ * split them.  A row needs at least one finite logit: the result for a row of -inf only (or with a NaN) is undefined, as it is in
+ * transformers (softmax of such a row is NaN).  The draw is the inverse CDF in token-index order:
  * the smallest kept index whose prefix mass exceeds u * Z, Z = sum of exp(s - s_max) over the kept set.  u = (x0 >> 8) * 2^-24 of
  * Philox4x32-10 with key (seed low word, seed high word) and counter (row, n, 0, 0), n = the cache length when the token is chosen (the
  * prompt length for the token fvhd_llm_start chooses, + 1 per decode step).  Only the distribution equals torch.multinomial's, not its

@@ -4,7 +4,9 @@
 //   s = logits / T (IEEE division), top-k keeps s >= the min(k, V)-th largest value (ties kept), top-p keeps a token when the
 //   normalised mass of the tokens before it (descending s) is < top_p, then one draw from the softmax over the kept set.
 // Both filters keep a prefix by value, so the kept set is {i : s_i >= theta} for one threshold per row; tokens tied at the top-p
-// boundary are kept as a group (transformers' unstable sort may split them).
+// boundary are kept as a group (transformers' unstable sort may split them).  A -inf logit (a suppressed token) is never kept, never
+// counted and never drawn, also when no filter is on or the top-k threshold itself is -inf.  A row needs one finite logit: a row of
+// -inf only has s_max = -inf and NaN masses, its result is undefined (include/fvhd.h).
 //
 // Launches (grid = S slices x B rows, 256 threads; each pass reads the whole row, the slices meet in the last-arriving workgroup of the
 // row as in the decode GEMM's split-K):
@@ -316,7 +318,7 @@ __global__ __launch_bounds__(256) void dec_sample_draw_kernel(const DecSampleArg
     unsigned cnt = 0;
     for (int i = c0; i < c1; ++i) {
         const float v = scaled(x[i], T);
-        if (okey(v) >= theta) { local += expf(v - M); last = i; ++cnt; }
+        if (okey(v) >= theta && v > -INFINITY) { local += expf(v - M); last = i; ++cnt; }      // a -inf logit is never kept
     }
     const float incl = block_scan_incl<float>(local, scan);
     const size_t slab = ((size_t)b * SMAX + s) * 256 + tid;
@@ -384,7 +386,7 @@ __global__ __launch_bounds__(256) void dec_sample_draw_kernel(const DecSampleArg
             int id = -1;
             for (int i = q0; i < q1; ++i) {
                 const float v = scaled(x[i], T);
-                if (okey(v) >= theta) {
+                if (okey(v) >= theta && v > -INFINITY) {
                     acc += expf(v - M);
                     id = i;
                     if (base + acc > target_s) break;
