@@ -49,8 +49,10 @@ typedef void* fvhd_stream_t; /* hipStream_t */
  * fvhd_op_gemm_qkv_rope / fvhd_gemm_qkv_rope_supported, the fvhd_llm_* stream contract; no signature of round 4 changed); 501 adds the
  * LLM decode (fvhd_llm_cache_reserve / start / decode / cache_state / set_tied_embeddings, the optional model.embed_tokens.weight key,
  * fvhd_op_dec_*); nothing earlier changed.  502 adds LLM sampling (fvhd_llm_set_sampling, fvhd_op_dec_sample): greedy stays the
- * default and computes what 501 did; no earlier signature changed. */
-#define FVHD_VERSION 502
+ * default and computes what 501 did; no earlier signature changed.  503 widens the LLM decode from 16 to 64 sequences per step
+ * (fvhd_llm_cache_reserve, fvhd_op_dec_gemm / _qkv / _attention / _lm_argmax: B in [1, 64]; the scratch of the single ops grows with
+ * ceil(B / 16)); no signature changed and B <= 16 computes what 502 did, bit for bit. */
+#define FVHD_VERSION 503
 int fvhd_version(void);
 const char* fvhd_last_error(void);
 
@@ -423,7 +425,7 @@ int fvhd_op_attention_causal(fvhd_stream_t stream, const void* qkv, void* out, c
  * does after its first forward, on the same packed weights as the prefill (no further weight copy).  Per decoder layer 5 launches:
  * [RMSNorm + q|k|v GEMM + bias + rotary + cache append] [attention over the cache] [o_proj + residual] [RMSNorm + gate|up + silu * up]
  * [down_proj + residual], then [final RMSNorm + lm_head + per-workgroup argmax] [argmax reduce + advance]; the GEMMs stream the weights
- * once (B <= 16 rows), fp32 accumulation, deterministic split-K reductions (identical bits run to run).
+ * once (B <= 64 rows: a weight fragment multiplies ceil(B / 16) tiles of 16 rows), fp32 accumulation, deterministic split-K reductions (identical bits run to run).
  * Everything that changes from step to step - the cache slot, the positions, the mask column - lives in device memory and is advanced by
  * the step itself: the host arguments of fvhd_llm_decode are the same for every token, so ONE captured graph replays a whole generation. */
 /* The decode's input embedding.  model.embed_tokens.weight [vocab, hidden] (fvhd_llm_set_tensor(_device); optional for the prefill and
@@ -433,7 +435,7 @@ int fvhd_op_attention_causal(fvhd_stream_t stream, const void* qkv, void* out, c
 int fvhd_llm_set_tied_embeddings(fvhd_llm* ctx, int tied);
 /* Allocates the cache: K and V bf16 [n_layers][batch][n_kv_heads][capacity][head_dim] (transformers' per-layer layout with a capacity
  * stride), the key-valid mask [batch][capacity], the next position of every sequence (int64 [batch]), the current length, the last chosen
- * ids, the error word and the decode workspace.  1 <= batch <= 16; hidden, n_heads * head_dim and intermediate multiples of 128.
+ * ids, the error word and the decode workspace.  1 <= batch <= 64; hidden, n_heads * head_dim and intermediate multiples of 128.
  * Synchronises (refused while a stream is being captured); replaces an earlier cache (a graph captured on it is then invalid). */
 int fvhd_llm_cache_reserve(fvhd_llm* ctx, int batch, int capacity);
 /* fvhd_llm_prefill's arithmetic on embeds [batch, seq_len, hidden] (batch <= the reserved batch, seq_len <= capacity), then: its rotated
@@ -459,7 +461,7 @@ int fvhd_llm_cache_state(fvhd_llm* ctx, int* length, int* status);
  * split them.  A row needs at least one finite logit: the result for a row of -inf only (or with a NaN) is undefined, as it is in
  * transformers (softmax of such a row is NaN).  The draw is the inverse CDF in token-index order:
  * the smallest kept index whose prefix mass exceeds u * Z, Z = sum of exp(s - s_max) over the kept set.  u = (x0 >> 8) * 2^-24 of
- * Philox4x32-10 with key (seed low word, seed high word) and counter (row, n, 0, 0), n = the cache length when the token is chosen (the
+ * Philox4x32-10 with key (seed low word, seed high word) and counter (row, n, 0, 0), row = the sequence's row in the batch, n = the cache length when the token is chosen (the
  * prompt length for the token fvhd_llm_start chooses, + 1 per decode step).  Only the distribution equals torch.multinomial's, not its
  * draws.  Deterministic: the same logits, settings, seed and n give the same id, eager or replayed from a graph.
  * do_sample = 0 (the default) is greedy, what fvhd_llm_start / fvhd_llm_decode did before: the argmax, bit for bit.  The settings are read
@@ -473,8 +475,8 @@ int fvhd_llm_set_sampling(fvhd_llm* ctx, int do_sample, float temperature, int t
 int fvhd_op_dec_sample(fvhd_stream_t stream, const float* logits, int B, int V, float temperature, int top_k, float top_p, unsigned long long seed,
                        int n, const float* u_override, int64_t* ids, float* info);
 
-/* single ops of the decode step (unit-test entry points); B in [1, 16]; K % 128 == 0; `splits` = workgroups per output tile along K
- * (partial: fp32 scratch [splits][N * 16], counters: int [ceil(N / 64)] ZEROED before the first call - each launch leaves them zero)
+/* single ops of the decode step (unit-test entry points); B in [1, 64]; K % 128 == 0; `splits` = workgroups per output tile along K
+ * (partial: fp32 scratch [splits][N * 16 * ceil(B / 16)], counters: int [ceil(N / 64)] ZEROED before the first call - each launch leaves them zero)
  * out = epilogue(rmsnorm?(x) . Wt^T): x [B, K] bf16, norm_w fp32 [K] or NULL (no norm), Wt [N, K] bf16; FVHD_EPI_RESID: out [B, N] =
  * resid + acc (resid may alias out); FVHD_EPI_SWIGLU: out [B, N / 2] = silu(acc[2j]) * acc[2j + 1] (gate / up rows interleaved). */
 int fvhd_op_dec_gemm(fvhd_stream_t stream, int epi, const void* x, int B, const float* norm_w, float eps, const void* Wt, int N, int K, const void* resid,
@@ -491,7 +493,7 @@ int fvhd_op_dec_qkv(fvhd_stream_t stream, const void* x, int B, int K, const flo
 int fvhd_op_dec_attention(fvhd_stream_t stream, const void* q, const void* k_cache, const void* v_cache, const uint8_t* key_valid, void* out, int B,
                           int n_heads, int n_kv_heads, int head_dim, int capacity, const int* length, float* partial, int* counters, int splits);
 /* final norm + lm_head + argmax: logits (NULL or fp32 [B, V]) = rmsnorm?(x) . Wt^T, ids_out int64 [B] = argmax (lowest index on ties);
- * scratch_v / scratch_i: [ceil(V / 64) * 16] each */
+ * scratch_v / scratch_i: [ceil(V / 64) * 16 * ceil(B / 16)] each */
 int fvhd_op_dec_lm_argmax(fvhd_stream_t stream, const void* x, int B, const float* norm_w, float eps, const void* Wt, int V, int K, float* logits,
                           int64_t* ids_out, float* scratch_v, int* scratch_i);
 

@@ -13,6 +13,8 @@ LIB_PATH = os.environ.get("FVHD_LIB") or os.path.join(_HERE, "libfvhd.so")
 
 ABI_VERSION = 501               # the oldest FVHD_VERSION (include/fvhd.h) this stub loads (major = ABI_VERSION // 100)
 SAMPLING_VERSION = 502          # the first with fvhd_llm_set_sampling / fvhd_op_dec_sample (declared only when the library has them)
+WIDE_BATCH_VERSION = 503       # the first whose decode takes more than 16 sequences per step (up to MAX_DECODE_BATCH)
+MAX_DECODE_BATCH = 64
 F32, F16, BF16 = 0, 1, 2
 FFN_HALF, FFN_BF16 = 0, 1        # precision of the fused ConvFFN's hidden activation (include/fvhd.h)
 EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_LS_RESID, EPI_RESID, EPI_SWIGLU = 0, 1, 2, 3, 4, 5
@@ -146,6 +148,19 @@ def sampling_lib():
     if got < SAMPLING_VERSION:
         raise FvhdError(f"{LIB_PATH} reports ABI version {got}: sampling (fvhd_llm_set_sampling, fvhd_op_dec_sample) needs {SAMPLING_VERSION} - "
                         "rebuild the library (`python -m ml_fastvlm_amd.build`)")
+    return lib
+
+
+def decode_lib(batch: int):
+    """load(), for a decode of `batch` sequences: a library older than WIDE_BATCH_VERSION loads and decodes up to 16 sequences per step;
+    a wider batch on it names the rebuild instead of the library's own "batch <= 16" refusal."""
+    lib = load()
+    got = lib.fvhd_version()
+    if batch > MAX_DECODE_BATCH:
+        raise FvhdError(f"the decode takes at most {MAX_DECODE_BATCH} sequences per step (asked for {batch})")
+    if batch > 16 and got < WIDE_BATCH_VERSION:
+        raise FvhdError(f"{LIB_PATH} reports ABI version {got}: a decode batch of {batch} (more than 16 sequences per step) needs "
+                        f"{WIDE_BATCH_VERSION} - rebuild the library (`python -m ml_fastvlm_amd.build`)")
     return lib
 
 

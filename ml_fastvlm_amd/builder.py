@@ -352,12 +352,18 @@ def _library_generate_settings(model, kwargs):
     return dict(max_new_tokens=int(gc.max_new_tokens), eos_token_id=gc.eos_token_id, pad_token_id=gc.pad_token_id, sampling=sampling), None
 
 
+def _batch_reason(batch: int):
+    """None when the library decodes `batch` sequences in one step, else the reason it cannot"""
+    from ._lib import MAX_DECODE_BATCH
+    return f"batch {batch} > {MAX_DECODE_BATCH}" if batch > MAX_DECODE_BATCH else None
+
+
 def _make_library_generate(orig_generate):
     """`LlavaQwen2ForCausalLM.generate` (`llava_qwen.py:106-143`) on the library: the same argument handling (position_ids / attention_mask
     popped, inputs_embeds refused), the settings resolved as transformers resolves them (`_library_generate_settings`), then the
     multimodal splice and `Qwen2Generator.greedy` / `.sample` on `generator_context(model, ...)`.  It takes the library only for greedy or
     temperature / top-k / top-p sampling with num_beams = 1, one sequence per prompt, no other logits processor, stopping criterion or
-    streamer, max_new_tokens given, use_cache, no scores / dict output, a bf16 model on a HIP device and a batch of at most 16; anything
+    streamer, max_new_tokens given, use_cache, no scores / dict output, a bf16 model on a HIP device and a batch of at most 64; anything
     else is the original generate, with a one-time warning that names the reason.  Returns the new tokens [B, n], as the reference's
     generate(inputs_embeds=...) does."""
     def generate(self, inputs=None, images=None, image_sizes=None, **kwargs):
@@ -365,10 +371,10 @@ def _make_library_generate(orig_generate):
             raise NotImplementedError("`inputs_embeds` is not supported")
         settings, reason = _library_generate_settings(self, {k: v for k, v in kwargs.items() if k not in ("position_ids", "attention_mask")})
         lm_w = self.lm_head.weight
+        if settings is not None and inputs is not None and _batch_reason(inputs.shape[0]) is not None:
+            settings, reason = None, _batch_reason(inputs.shape[0])
         if settings is not None and (lm_w.device.type != "cuda" or lm_w.dtype != torch.bfloat16):
             settings, reason = None, f"the model is {lm_w.dtype} on {lm_w.device} (the library decodes a bf16 model on a HIP device)"
-        if settings is not None and inputs is not None and inputs.shape[0] > 16:
-            settings, reason = None, f"batch {inputs.shape[0]} > 16"
         if settings is None:
             warned = getattr(self, "_fvhd_generate_warned", frozenset())
             if reason not in warned:

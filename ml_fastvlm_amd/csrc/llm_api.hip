@@ -132,7 +132,9 @@ struct fvhd_llm {
     unsigned char* mask = nullptr;
     int64_t *posv = nullptr, *last_ids = nullptr;
     int *len = nullptr, *status = nullptr, *cnt = nullptr, *amax_i = nullptr;
-    float *dpart = nullptr, *apart = nullptr, *amax_v = nullptr, *dlogits = nullptr, *drope = nullptr;
+    float *dpart = nullptr, *apart = nullptr, *amax_v = nullptr, *dlogits = nullptr, *drope = nullptr, *drstd = nullptr;
+    int dec_rstd_once = 1;                 // a decode GEMM with a folded norm above 16 rows: the row statistics from one small launch (dec_rstd_kernel)
+                                           // instead of every workgroup; FVHD_DEC_RSTD_ONCE=0 for the A/B (identical bits)
     int* status_host = nullptr;            // host-mapped copy of the error word: read by every host call without a synchronisation
     int* status_host_dev = nullptr;
     int cnt_att = 0;                       // counters [0, cnt_att) of the GEMMs, then B * nh of the attention
@@ -287,6 +289,7 @@ int fvhd_llm_create(fvhd_llm** out, int device, int hidden, int n_layers, int n_
     if (const char* ev = getenv("FVHD_LLM_QKVSPLIT")) c->qkv_splits = atoi(ev);
     if (const char* ev = getenv("FVHD_LLM_FUSENORM")) c->fuse_norm = atoi(ev);
     if (const char* ev = getenv("FVHD_LLM_FUSEROPE")) c->fuse_rope = atoi(ev);
+    if (const char* ev = getenv("FVHD_DEC_RSTD_ONCE")) c->dec_rstd_once = atoi(ev);
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off += al256(bytes); return o; };
     c->lo.resize(n_layers);
@@ -676,7 +679,7 @@ int fvhd_llm_set_tied_embeddings(fvhd_llm* c, int tied)
 
 int fvhd_llm_cache_reserve(fvhd_llm* c, int batch, int capacity)
 {
-    if (!c || batch < 1 || batch > 16 || capacity < 1) return lfail("fvhd_llm_cache_reserve: needs a context, 1 <= batch <= 16 and capacity >= 1");
+    if (!c || batch < 1 || batch > 64 || capacity < 1) return lfail("fvhd_llm_cache_reserve: needs a context, 1 <= batch <= 64 and capacity >= 1");
     for (char g : c->got)
         if (!g) return lfail("fvhd_llm_cache_reserve: weights incomplete (fvhd_llm_finalize reports the missing tensor)");
     if (c->H % 128 || (c->nh * c->hd) % 128 || c->I % 128)
@@ -694,10 +697,11 @@ int fvhd_llm_cache_reserve(fvhd_llm* c, int batch, int capacity)
     c->p_d = dec_plan(H, I, ncu);
     c->p_lm = fvhd_llm::Plan{1, H / 128};
     att_plan(capacity, batch * nh, ncu, &c->att_S, &c->att_chunk);
+    const int NB = (batch + 15) / 16;                            // batch tiles of the decode GEMM: slabs and (max, index) pairs per tile
     size_t part = 0;
     int ncol = 1;
     for (auto pr : {std::make_pair(c->p_qkv, c->qkvw), std::make_pair(c->p_o, H), std::make_pair(c->p_gu, 2 * I), std::make_pair(c->p_d, H)}) {
-        if (pr.first.S > 1) part = std::max(part, (size_t)pr.first.S * pr.second * 64);
+        if (pr.first.S > 1) part = std::max(part, (size_t)pr.first.S * pr.second * 64 * NB);
         ncol = std::max(ncol, (pr.second / 16 + 3) / 4);
     }
     const int lm_ncol = (V / 16 + 3) / 4;
@@ -709,8 +713,8 @@ int fvhd_llm_cache_reserve(fvhd_llm* c, int batch, int capacity)
                  o_len = take(4), o_status = take(4), o_h = take((size_t)batch * H * 2), o_q = take((size_t)batch * nh * hd * 2),
                  o_att = take((size_t)batch * nh * hd * 2), o_act = take((size_t)batch * I * 2), o_part = take(std::max(part, (size_t)16)),
                  o_apart = take((size_t)batch * nh * c->att_S * (hd + 2) * 4), o_cnt = take((size_t)(ncol + batch * nh) * 4),
-                 o_av = take((size_t)lm_ncol * 16 * 4), o_ai = take((size_t)lm_ncol * 16 * 4), o_logits = take((size_t)batch * V * 4),
-                 o_rope = take((size_t)c->ws_pos * hd * 4), o_sws = take(fvhd_dec_sample_ws_bytes());
+                 o_av = take((size_t)lm_ncol * 16 * NB * 4), o_ai = take((size_t)lm_ncol * 16 * NB * 4), o_logits = take((size_t)batch * V * 4),
+                 o_rope = take((size_t)c->ws_pos * hd * 4), o_sws = take(fvhd_dec_sample_ws_bytes()), o_rstd = take(4 * 64);
     hipError_t he = hipDeviceSynchronize();                      // refused while a stream is being captured (like fvhd_llm_reserve)
     if (he != hipSuccess) return lhip("fvhd_llm_cache_reserve: hipDeviceSynchronize", he);
     if (c->dc) (void)hipFree(c->dc);
@@ -727,7 +731,7 @@ int fvhd_llm_cache_reserve(fvhd_llm* c, int batch, int capacity)
     c->kcache = d + o_k; c->vcache = d + o_v; c->mask = (unsigned char*)(d + o_mask); c->posv = (int64_t*)(d + o_pos); c->last_ids = (int64_t*)(d + o_last);
     c->len = (int*)(d + o_len); c->status = (int*)(d + o_status); c->dh = d + o_h; c->dq = d + o_q; c->datt = d + o_att; c->dact = d + o_act;
     c->dpart = (float*)(d + o_part); c->apart = (float*)(d + o_apart); c->cnt = (int*)(d + o_cnt); c->amax_v = (float*)(d + o_av);
-    c->amax_i = (int*)(d + o_ai); c->dlogits = (float*)(d + o_logits); c->drope = (float*)(d + o_rope); c->sws = d + o_sws;
+    c->amax_i = (int*)(d + o_ai); c->dlogits = (float*)(d + o_logits); c->drope = (float*)(d + o_rope); c->sws = d + o_sws; c->drstd = (float*)(d + o_rstd);
     c->dc_bytes = off; c->dc_batch = batch; c->dc_cap = capacity; c->dc_pos = c->ws_pos;
     // the decode's own copy of the rotary table: a later, larger prefill may replace the prefill workspace under a captured decode graph
     if ((he = hipMemcpy(c->drope, c->rope, (size_t)c->ws_pos * hd * 4, hipMemcpyDeviceToDevice)) != hipSuccess) return lhip("hipMemcpy(rope table)", he);
@@ -815,7 +819,7 @@ int fvhd_llm_decode(fvhd_llm* c, const int64_t* token_ids, float* logits_out, in
     auto gemm = [&](int epi, const void* x, int K, const float* norm_w, const void* W, int N, const fvhd_llm::Plan& p) {
         DecGemmArgs a;
         a.x = x; a.ldx = K; a.norm_w = norm_w; a.eps = c->eps; a.W = W; a.N = N; a.K = K; a.B = B; a.S = p.S; a.cpw = p.cpw;
-        a.part = c->dpart; a.cnt = c->cnt; a.epi = epi; a.status = c->status;
+        a.part = c->dpart; a.cnt = c->cnt; a.epi = epi; a.status = c->status; a.rstd = c->dec_rstd_once ? c->drstd : nullptr;
         return a;
     };
     for (int l = 0; l < c->L; ++l) {
@@ -962,8 +966,8 @@ int fvhd_op_dec_gemm(fvhd_stream_t st, int epi, const void* x, int B, const floa
 {
     if (!x || !Wt || !out || (epi == FVHD_EPI_RESID && !resid)) return lfail("fvhd_op_dec_gemm: NULL pointer");
     if (epi != FVHD_EPI_RESID && epi != FVHD_EPI_SWIGLU) return lfail("fvhd_op_dec_gemm: epi must be FVHD_EPI_RESID or FVHD_EPI_SWIGLU");
-    if (B < 1 || B > 16 || N % 16 || K % 128 || splits < 1 || (splits > 1 && (!partial || !counters)))
-        return lfail("fvhd_op_dec_gemm: needs 1 <= B <= 16, N % 16 == 0, K % 128 == 0, splits >= 1 (and scratch when splits > 1)");
+    if (B < 1 || B > 64 || N % 16 || K % 128 || splits < 1 || (splits > 1 && (!partial || !counters)))
+        return lfail("fvhd_op_dec_gemm: needs 1 <= B <= 64, N % 16 == 0, K % 128 == 0, splits >= 1 (and scratch when splits > 1)");
     DecGemmArgs a;
     a.x = x; a.ldx = K; a.norm_w = norm_w; a.eps = eps; a.W = Wt; a.N = N; a.K = K; a.B = B; a.part = partial; a.cnt = counters;
     a.epi = epi; a.resid = resid; a.out = out; a.ldo = epi == FVHD_EPI_SWIGLU ? N / 2 : N;
@@ -977,9 +981,9 @@ int fvhd_op_dec_qkv(fvhd_stream_t st, const void* x, int B, int K, const float* 
                     const int* length, int n_heads, int n_kv_heads, int head_dim, float* partial, int* counters, int splits)
 {
     if (!x || !Wt || !bias || !q_out || !pos || !table || !k_cache || !v_cache || !length) return lfail("fvhd_op_dec_qkv: NULL pointer");
-    if (B < 1 || B > 16 || K % 128 || splits < 1 || head_dim % 16 || n_heads < 1 || n_kv_heads < 1 || capacity < 1 || table_positions < 1 ||
+    if (B < 1 || B > 64 || K % 128 || splits < 1 || head_dim % 16 || n_heads < 1 || n_kv_heads < 1 || capacity < 1 || table_positions < 1 ||
         (splits > 1 && (!partial || !counters)))
-        return lfail("fvhd_op_dec_qkv: needs 1 <= B <= 16, K % 128 == 0, head_dim % 16 == 0, splits >= 1 (and scratch when splits > 1)");
+        return lfail("fvhd_op_dec_qkv: needs 1 <= B <= 64, K % 128 == 0, head_dim % 16 == 0, splits >= 1 (and scratch when splits > 1)");
     DecGemmArgs a;
     a.x = x; a.ldx = K; a.norm_w = norm_w; a.eps = eps; a.W = Wt; a.N = (n_heads + 2 * n_kv_heads) * head_dim; a.K = K; a.B = B;
     a.part = partial; a.cnt = counters; a.epi = DEC_EPI_QKV; a.bias = bias; a.out = q_out; a.ldo = n_heads * head_dim; a.pos = pos; a.rope = table;
@@ -994,6 +998,7 @@ int fvhd_op_dec_attention(fvhd_stream_t st, const void* q, const void* k_cache, 
                           int n_kv_heads, int head_dim, int capacity, const int* length, float* partial, int* counters, int splits)
 {
     if (!q || !k_cache || !v_cache || !key_valid || !out || !length) return lfail("fvhd_op_dec_attention: NULL pointer");
+    if (B < 1 || B > 64) return lfail("fvhd_op_dec_attention: needs 1 <= B <= 64");
     if (splits < 1 || capacity < 1 || (splits > 1 && (!partial || !counters))) return lfail("fvhd_op_dec_attention: splits >= 1 (and scratch when splits > 1)");
     const int chunk = ((capacity + splits - 1) / splits + 63) / 64 * 64, S = (capacity + chunk - 1) / chunk;
     int e = fvhd_launch_dec_attention((hipStream_t)st, q, k_cache, v_cache, key_valid, out, B, n_heads, n_kv_heads, head_dim, capacity, length, 0, S, chunk,
@@ -1005,7 +1010,7 @@ int fvhd_op_dec_lm_argmax(fvhd_stream_t st, const void* x, int B, const float* n
                           float* scratch_v, int* scratch_i)
 {
     if (!x || !Wt || !ids_out || !scratch_v || !scratch_i) return lfail("fvhd_op_dec_lm_argmax: NULL pointer");
-    if (B < 1 || B > 16 || V % 16 || K % 128) return lfail("fvhd_op_dec_lm_argmax: needs 1 <= B <= 16, V % 16 == 0, K % 128 == 0");
+    if (B < 1 || B > 64 || V % 16 || K % 128) return lfail("fvhd_op_dec_lm_argmax: needs 1 <= B <= 64, V % 16 == 0, K % 128 == 0");
     DecGemmArgs a;
     a.x = x; a.ldx = K; a.norm_w = norm_w; a.eps = eps; a.W = Wt; a.N = V; a.K = K; a.B = B; a.S = 1; a.cpw = K / 128; a.epi = DEC_EPI_ARGMAX;
     a.logits = logits; a.amax_v = scratch_v; a.amax_i = scratch_i;

@@ -15,7 +15,7 @@ struct DecGemmArgs {
     const void* W = nullptr;       // bf16 [N][K] (the packed layouts of the prefill)
     int N = 0, K = 0, B = 0;
     int S = 1, cpw = 0;            // K split over S workgroups of cpw 128-deep chunks (the last one may hold fewer)
-    float* part = nullptr;         // S > 1: fp32 slabs [S][N / 16][64][4]
+    float* part = nullptr;         // S > 1: fp32 slabs [S][N / 16][NB][64][4], NB = ceil(B / 16) batch tiles
     int* cnt = nullptr;            // S > 1: one arrival counter per workgroup column, zero between launches (the last arriver resets it)
     int epi = 0;
     const void* resid = nullptr;   // RESID: bf16 [B][ldo] (may alias out)
@@ -32,15 +32,19 @@ struct DecGemmArgs {
     int cap = 0;
     const int* len = nullptr;      // QKV: the slot the new token's k / v go to (device word)
     float* logits = nullptr;       // ARGMAX: fp32 [B][N] or NULL
-    float* amax_v = nullptr;       // ARGMAX: [gridDim][16] best value / index of every row within the workgroup's columns
+    float* amax_v = nullptr;       // ARGMAX: [gridDim][16 * NB] best value / index of every row within the workgroup's columns
     int* amax_i = nullptr;
     const int* status = nullptr;   // non-NULL: the launch does nothing while *status != 0 (a step past the cache's capacity)
+    float* rstd = nullptr;         // B > 16 with norm_w: scratch [B]; the row statistics are computed once, by a launch of their own, instead of
+                                   // in every workgroup (NULL: every workgroup recomputes them, as at B <= 16; the bits are the same)
 };
 
 // Arguments of the sampler (llm_sample.hip): temperature / top-k / top-p over fp32 logits [B][V], one draw per row.
 struct DecSampleArgs {
     const float* logits = nullptr;
-    int B = 0, V = 0;
+    int B = 0, V = 0;              // B in [1, 64]: launched in blocks of 16 rows
+    int row0 = 0;                  // set per block by the launcher: first row of the block (logits, ids, positions, u and the Philox
+                                   // counter are indexed by the global row row0 + r, the workspace by r)
     float temperature = 1.f;       // > 0
     int top_k = 0;                 // 0 = off
     float top_p = 1.f;             // 1 = off
@@ -52,6 +56,6 @@ struct DecSampleArgs {
     int64_t* ids_out = nullptr;
     float* info = nullptr;         // [B][4]: theta, kept count, Z, u
     int64_t* posv = nullptr;       // non-NULL: positions += 1
-    int* len_advance = nullptr;    // non-NULL: *len_advance += 1 once every row has read n
+    int* len_advance = nullptr;    // non-NULL: *len_advance += 1 once every row (of the last block) has read n
     const int* status = nullptr;
 };

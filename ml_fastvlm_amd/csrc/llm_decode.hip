@@ -1,6 +1,6 @@
 // Qwen2 decode step kernels: one new token per sequence against the library's own KV cache (include/fvhd.h "LLM decode").
 //
-// A decode step is a weight stream: B <= 16 rows against every weight of the model.  The prefill's GEMMs (gemm.hip) pad M to 128 / 256
+// A decode step is a weight stream: B <= 64 rows against every weight of the model.  The prefill's GEMMs (gemm.hip) pad M to 128 / 256
 // rows and launch a handful of workgroups at N = 896, so the step has kernels of its own:
 //   dec_gemm_kernel     M = B in [1, 16]: every wave owns 16 weight rows (one 16 x 16 x 32 MFMA tile: A = weights, B = the activation
 //                       rows), streams them once from HBM straight to VGPRs (non-temporal), and K is split over workgroups where N alone
@@ -8,6 +8,8 @@
 //                       summed in slice order: deterministic, no float atomics).  RMSNorm is folded into the operand load (every workgroup
 //                       recomputes the B row statistics), the epilogue is one of: residual add, silu(gate) * up, bias + rotary embedding +
 //                       KV-cache append, or fp32 logits + per-workgroup argmax.
+//   dec_gemm_wide_kernel   the same for B in [17, 64]: ceil(B / 16) batch tiles of 16 rows per weight fragment, the arithmetic of
+//                       dec_gemm_kernel per tile; the row statistics come from dec_rstd_kernel, once per launch.
 //   dec_attention       single-query grouped-query attention over the cache, split over the key axis (flash-decoding) with the same
 //                       in-launch combine.
 //   dec_embed / dec_argmax_finish (+ dec_argmax_blocks / dec_start_state at fvhd_llm_start)     the step's first and last launches: token embedding + the capacity check, the
@@ -195,6 +197,214 @@ __global__ __launch_bounds__(256) void dec_gemm_kernel(const DecGemmArgs a)
     }
 }
 
+// The same GEMM for 17 .. 64 rows: NB = ceil(B / 16) batch tiles of 16 rows in 2 .. 4.  A weight fragment is still read once (ld_nt) and
+// multiplies the NB activation fragments into NB accumulators; lane (lr, g) loads activation row min(t * 16 + lr, B - 1) for tile t and
+// accumulator t holds out[row = g * 4 + r][batch = t * 16 + lr].  Batch tile t does the arithmetic of dec_gemm_kernel on rows
+// [16 t, 16 t + 16) in its order, so a row's bits do not depend on the batch it is decoded in; the split-K slab is [S][N / 16][NB][64][4],
+// the (max, index) pairs [gridDim][16 * NB].  dec_gemm_kernel stays what it was, instruction for instruction: written as the NB = 1 case of
+// this template the compiler scheduled its prologue differently, which cost 0.2-0.5 % of the 0.5B step at B = 1 / 8.
+template <int EPI, int NB>
+__global__ __launch_bounds__(256) void dec_gemm_wide_kernel(const DecGemmArgs a)
+{
+    static_assert(NB >= 2 && NB <= 4, "batch tiles of the wide decode GEMM");
+    if (a.status && *a.status) return;
+    __shared__ float sh[16 * NB + 4 + 4 * 16 * NB * 2];
+    float* rstd = sh;
+    int* flag = (int*)(sh + 16 * NB);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 15, g = lane >> 4;
+    const int ntiles = a.N / 16, S = a.S;
+    const int column = blockIdx.x / S, s = blockIdx.x % S;
+    const int tile = column * 4 + wave;
+    const bool active = tile < ntiles;                           // wave-uniform
+    const int B = a.B, K = a.K;
+    const bf16* x = (const bf16*)a.x;
+    if (a.norm_w) {
+        if (a.rstd) {                                            // dec_rstd_kernel wrote them once for the launch
+            if (tid < B) rstd[tid] = a.rstd[tid];
+        } else {                                                 // rmsnorm_kernel's statistics, in its order (identical bits)
+            for (int b = wave; b < B; b += 4) {
+                const bf16* xr = x + (size_t)b * a.ldx;
+                float ss = 0.f;
+                for (int c = lane * 8; c < K; c += 512) {
+                    const f32x8 v = bf8_to_f32(*(const bf16x8*)(xr + c));
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) ss = __builtin_fmaf(v[k], v[k], ss);
+                }
+                ss = wave_sum(ss);
+                if (lane == 0) rstd[b] = 1.0f / sqrtf(ss / (float)K + a.eps);
+            }
+        }
+        __syncthreads();
+    }
+    int wrow = tile * 16 + lr;
+    if constexpr (EPI == DEC_EPI_QKV) {
+        const int tph = a.hd / 16, head = tile / tph, pb = tile % tph;
+        wrow = head * a.hd + (lr < 8 ? pb * 8 + lr : a.hd / 2 + pb * 8 + lr - 8);
+    }
+    int xb[NB];
+    f32x4 acc[NB];
+#pragma unroll
+    for (int t = 0; t < NB; ++t) { xb[t] = min(t * 16 + lr, B - 1); acc[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    if (active) {
+        const bf16* wr = (const bf16*)a.W + (size_t)min(wrow, a.N - 1) * K + g * 8;
+        const bf16* xr[NB];
+        float rs[NB];
+#pragma unroll
+        for (int t = 0; t < NB; ++t) {
+            xr[t] = x + (size_t)xb[t] * a.ldx + g * 8;
+            rs[t] = a.norm_w ? rstd[xb[t]] : 1.f;
+        }
+        const int KC = K / 128, c0 = s * a.cpw, c1 = min(c0 + a.cpw, KC);
+        for (int c = c0; c < c1; ++c) {
+            bf16x8 wf[4], xf[NB][4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) wf[j] = ld_nt(wr + c * 128 + j * 32);
+#pragma unroll
+            for (int t = 0; t < NB; ++t)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) xf[t][j] = *(const bf16x8*)(xr[t] + c * 128 + j * 32);
+            if (a.norm_w) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float* w = a.norm_w + c * 128 + j * 32 + g * 8;
+                    const f32x4 w0 = *(const f32x4*)w, w1 = *(const f32x4*)(w + 4);
+#pragma unroll
+                    for (int t = 0; t < NB; ++t) {
+                        const f32x8 v = bf8_to_f32(xf[t][j]);
+                        f32x8 o;
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) { o[k] = v[k] * rs[t] * w0[k]; o[4 + k] = v[4 + k] * rs[t] * w1[k]; }
+                        xf[t][j] = f32_to_bf8(o);
+                    }
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < NB; ++t)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], xf[t][j], acc[t], 0, 0, 0);
+        }
+    }
+    if (S > 1) {
+        if (active) {
+#pragma unroll
+            for (int t = 0; t < NB; ++t) *(f32x4*)(a.part + ((((size_t)s * ntiles + tile) * NB + t) * 64 + lane) * 4) = acc[t];
+        }
+        if (!arrive_last(a.cnt + column, S, flag)) return;
+        if (active) {
+#pragma unroll
+            for (int t = 0; t < NB; ++t) {
+                acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+                for (int u = 0; u < S; ++u) acc[t] += *(const f32x4*)(a.part + ((((size_t)u * ntiles + tile) * NB + t) * 64 + lane) * 4);
+            }
+        }
+    }
+    const int n0 = tile * 16 + g * 4;                            // this lane's 4 outputs of batch tile t: rows n0 .. n0 + 3 of batch row t * 16 + lr
+    if constexpr (EPI == DEC_EPI_RESID) {
+#pragma unroll
+        for (int t = 0; t < NB; ++t) {
+            const int b = t * 16 + lr;
+            if (active && b < B) {
+                const f32x4 r = bf4_to_f32(*(const bf16x4*)((const bf16*)a.resid + (size_t)b * a.ldo + n0));
+                *(bf16x4*)((bf16*)a.out + (size_t)b * a.ldo + n0) = f32_to_bf4(r + acc[t]);
+            }
+        }
+    } else if constexpr (EPI == DEC_EPI_SWIGLU) {
+#pragma unroll
+        for (int t = 0; t < NB; ++t) {
+            const int b = t * 16 + lr;
+            if (active && b < B) {
+                bf16x2 o;
+                o[0] = (bf16)(acc[t][0] * sigmoidf_fast(acc[t][0]) * acc[t][1]);
+                o[1] = (bf16)(acc[t][2] * sigmoidf_fast(acc[t][2]) * acc[t][3]);
+                *(bf16x2*)((bf16*)a.out + (size_t)b * a.ldo + n0 / 2) = o;
+            }
+        }
+    } else if constexpr (EPI == DEC_EPI_QKV) {
+        if (active) {
+            const int hd = a.hd, tph = hd / 16, head = tile / tph, pb = tile % tph;
+            const bool first = g < 2;
+            const int i4 = pb * 8 + (g & 1) * 4, d = first ? i4 : hd / 2 + i4;
+            const f32x4 bias = *(const f32x4*)(a.bias + head * hd + d);
+#pragma unroll
+            for (int t = 0; t < NB; ++t) {
+                const int b = t * 16 + lr;
+                const f32x4 v = bf4_to_f32(f32_to_bf4(acc[t] + bias));  // the projection's output as the reference holds it (bf16)
+                f32x4 other;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) other[r] = __shfl_xor(v[r], 32, 64);
+                bf16x4 res = f32_to_bf4(v);
+                if (b < B) {
+                    if (head < a.nh + a.nkv) {
+                        bf16x4 ra, rb;
+                        rope_rotate(first ? v : other, first ? other : v, (long)a.pos[b], i4, a.rope, hd, a.P, a.theta, ra, rb);
+                        res = first ? ra : rb;
+                    }
+                    if (head < a.nh) {
+                        *(bf16x4*)((bf16*)a.out + (size_t)b * a.ldo + head * hd + d) = res;
+                    } else {
+                        const int kvh = head < a.nh + a.nkv ? head - a.nh : head - a.nh - a.nkv;
+                        bf16* cache = (bf16*)(head < a.nh + a.nkv ? a.kc : a.vc);
+                        const int slot = *a.len;
+                        if (slot >= 0 && slot < a.cap)
+                            *(bf16x4*)(cache + (((size_t)b * a.nkv + kvh) * a.cap + slot) * hd + d) = res;
+                    }
+                }
+            }
+        }
+    } else if constexpr (EPI == DEC_EPI_ARGMAX) {
+        float* rv = sh + 16 * NB + 4;                            // [wave][batch tile][16] best value / index of the wave's 16 weight rows
+        int* ri = (int*)(rv + 64 * NB);
+#pragma unroll
+        for (int t = 0; t < NB; ++t) {
+            const int b = t * 16 + lr;
+            float bv = -INFINITY;
+            int bi = 0x7fffffff;
+            if (active && b < B) {
+                if (a.logits) *(f32x4*)(a.logits + (size_t)b * a.N + n0) = acc[t];
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (better(acc[t][r], n0 + r, bv, bi)) { bv = acc[t][r]; bi = n0 + r; }
+            }
+#pragma unroll
+            for (int o = 16; o <= 32; o <<= 1) {
+                const float ov = __shfl_xor(bv, o, 64);
+                const int oi = __shfl_xor(bi, o, 64);
+                if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+            }
+            if (lane < 16) { rv[(wave * NB + t) * 16 + lane] = bv; ri[(wave * NB + t) * 16 + lane] = bi; }
+        }
+        __syncthreads();
+        if (tid < 16 * NB && tid < B) {
+            const int t = tid >> 4, r = tid & 15;
+            float v = rv[t * 16 + r];
+            int i = ri[t * 16 + r];
+            for (int w = 1; w < 4; ++w)
+                if (better(rv[(w * NB + t) * 16 + r], ri[(w * NB + t) * 16 + r], v, i)) { v = rv[(w * NB + t) * 16 + r]; i = ri[(w * NB + t) * 16 + r]; }
+            a.amax_v[(size_t)blockIdx.x * (16 * NB) + tid] = v;
+            a.amax_i[(size_t)blockIdx.x * (16 * NB) + tid] = i;
+        }
+    }
+}
+
+// The RMSNorm row statistics of a wide launch (B > 16), once per launch site instead of once per workgroup of dec_gemm_kernel: wave = row,
+// the same loop, the same bits.
+__global__ __launch_bounds__(256) void dec_rstd_kernel(const bf16* __restrict__ x, int ldx, int K, int B, float eps, float* __restrict__ rstd,
+                                                       const int* status)
+{
+    if (status && *status) return;
+    const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const bf16* xr = x + (size_t)b * ldx;
+    float ss = 0.f;
+    for (int c = lane * 8; c < K; c += 512) {
+        const f32x8 v = bf8_to_f32(*(const bf16x8*)(xr + c));
+#pragma unroll
+        for (int k = 0; k < 8; ++k) ss = __builtin_fmaf(v[k], v[k], ss);
+    }
+    ss = wave_sum(ss);
+    if (lane == 0) rstd[b] = 1.0f / sqrtf(ss / (float)K + eps);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // Single-query attention of q [B][nh * HD] over the cache keys [0, *len + len_add) of sequence b (kv head h / (nh / nkv)), key_valid
 // [cache_batch][cap]: out = softmax(q . k * HD^-0.5 over valid keys) . v, fp32 softmax.  Workgroup = (b, h, key slice of `chunk` keys);
@@ -338,20 +548,20 @@ __global__ __launch_bounds__(256) void dec_embed_kernel(const int64_t* __restric
     if (threadIdx.x == 0) key_valid[(size_t)b * cap + L] = 1;
 }
 
-// The lm_head's per-workgroup (max, index) pairs [nblk][16] -> ids of the B rows (ties: lowest index), then - when `len` is given - the
-// advance of the step: positions + 1, length + 1.
+// The lm_head's per-workgroup (max, index) pairs [nblk][16 * ceil(B / 16)] -> ids of the B rows (ties: lowest index), then - when `len` is
+// given - the advance of the step: positions + 1, length + 1.  Workgroup t takes the 16 rows of batch tile t.
 __global__ __launch_bounds__(256) void dec_argmax_finish_kernel(const float* __restrict__ av, const int* __restrict__ ai, int nblk, int B, int64_t* last,
                                                                 int64_t* ids_out, int64_t* posv, int* len, const int* status)
 {
     if (status && *status) return;
     __shared__ float sv[256];
     __shared__ int si[256];
-    const int tid = threadIdx.x;
-    for (int b = 0; b < B; ++b) {
+    const int tid = threadIdx.x, ld = 16 * gridDim.x;
+    for (int b = blockIdx.x * 16; b < min(B, blockIdx.x * 16 + 16); ++b) {
         float v = -INFINITY;
         int i = 0x7fffffff;
         for (int k = tid; k < nblk; k += 256)
-            if (better(av[(size_t)k * 16 + b], ai[(size_t)k * 16 + b], v, i)) { v = av[(size_t)k * 16 + b]; i = ai[(size_t)k * 16 + b]; }
+            if (better(av[(size_t)k * ld + b], ai[(size_t)k * ld + b], v, i)) { v = av[(size_t)k * ld + b]; i = ai[(size_t)k * ld + b]; }
         sv[tid] = v;
         si[tid] = i;
         __syncthreads();
@@ -367,7 +577,7 @@ __global__ __launch_bounds__(256) void dec_argmax_finish_kernel(const float* __r
         }
         __syncthreads();
     }
-    if (tid == 0 && len) *len += 1;
+    if (tid == 0 && blockIdx.x == 0 && len) *len += 1;          // nothing in this launch reads it
 }
 
 // fvhd_llm_start's first-token argmax over the prefill's fp32 logits [B][V], in the lm_head's shape: workgroup k takes columns
@@ -376,7 +586,7 @@ __global__ __launch_bounds__(256) void dec_argmax_finish_kernel(const float* __r
 __global__ __launch_bounds__(256) void dec_argmax_blocks_kernel(const float* __restrict__ logits, int V, int B, float* __restrict__ av, int* __restrict__ ai)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int col = blockIdx.x * 64 + lane;
+    const int col = blockIdx.x * 64 + lane, ld = (B + 15) / 16 * 16;
     for (int b = wave; b < B; b += 4) {
         float v = -INFINITY;
         int i = 0x7fffffff;
@@ -387,7 +597,7 @@ __global__ __launch_bounds__(256) void dec_argmax_blocks_kernel(const float* __r
             const int oi = __shfl_xor(i, o, 64);
             if (better(ov, oi, v, i)) { v = ov; i = oi; }
         }
-        if (lane == 0) { av[(size_t)blockIdx.x * 16 + b] = v; ai[(size_t)blockIdx.x * 16 + b] = i; }
+        if (lane == 0) { av[(size_t)blockIdx.x * ld + b] = v; ai[(size_t)blockIdx.x * ld + b] = i; }
     }
 }
 
@@ -400,25 +610,35 @@ __global__ __launch_bounds__(64) void dec_start_state_kernel(int64_t* posv, cons
 }
 
 // ---------------------------------------------------------------------------------------------------
+template <int EPI>
+static void launch_dec_gemm(hipStream_t st, const dim3 grid, const DecGemmArgs& a)
+{
+    const dim3 block(256);
+    switch ((a.B + 15) / 16) {
+    case 1: hipLaunchKernelGGL(dec_gemm_kernel<EPI>, grid, block, 0, st, a); break;
+    case 2: hipLaunchKernelGGL((dec_gemm_wide_kernel<EPI, 2>), grid, block, 0, st, a); break;
+    case 3: hipLaunchKernelGGL((dec_gemm_wide_kernel<EPI, 3>), grid, block, 0, st, a); break;
+    default: hipLaunchKernelGGL((dec_gemm_wide_kernel<EPI, 4>), grid, block, 0, st, a); break;
+    }
+}
+
 extern "C" int fvhd_launch_dec_gemm(hipStream_t st, const DecGemmArgs* a)
 {
-    if (a->B < 1 || a->B > 16 || a->N % 16 || a->K % 128 || a->S < 1 || a->cpw < 1 || (long)a->S * a->cpw < a->K / 128 ||
+    if (a->B < 1 || a->B > 64 || a->N % 16 || a->K % 128 || a->S < 1 || a->cpw < 1 || (long)a->S * a->cpw < a->K / 128 ||
         (long)(a->S - 1) * a->cpw >= a->K / 128 || (a->S > 1 && (!a->part || !a->cnt)))
         return (int)hipErrorInvalidValue;
+    if (a->epi < DEC_EPI_RESID || a->epi > DEC_EPI_ARGMAX) return (int)hipErrorInvalidValue;
+    if (a->epi == DEC_EPI_QKV && (a->hd % 16 || a->N != (a->nh + 2 * a->nkv) * a->hd)) return (int)hipErrorInvalidValue;
+    if (a->epi == DEC_EPI_ARGMAX && a->S != 1) return (int)hipErrorInvalidValue;
+    if (a->norm_w && a->rstd && a->B > 16)
+        hipLaunchKernelGGL(dec_rstd_kernel, dim3((a->B + 3) / 4), dim3(256), 0, st, (const bf16*)a->x, a->ldx, a->K, a->B, a->eps, a->rstd, a->status);
     const int ncol = (a->N / 16 + 3) / 4;
-    const dim3 grid((unsigned)((long)ncol * a->S)), block(256);
+    const dim3 grid((unsigned)((long)ncol * a->S));
     switch (a->epi) {
-    case DEC_EPI_RESID: hipLaunchKernelGGL(dec_gemm_kernel<DEC_EPI_RESID>, grid, block, 0, st, *a); break;
-    case DEC_EPI_SWIGLU: hipLaunchKernelGGL(dec_gemm_kernel<DEC_EPI_SWIGLU>, grid, block, 0, st, *a); break;
-    case DEC_EPI_QKV:
-        if (a->hd % 16 || a->N != (a->nh + 2 * a->nkv) * a->hd) return (int)hipErrorInvalidValue;
-        hipLaunchKernelGGL(dec_gemm_kernel<DEC_EPI_QKV>, grid, block, 0, st, *a);
-        break;
-    case DEC_EPI_ARGMAX:
-        if (a->S != 1) return (int)hipErrorInvalidValue;
-        hipLaunchKernelGGL(dec_gemm_kernel<DEC_EPI_ARGMAX>, grid, block, 0, st, *a);
-        break;
-    default: return (int)hipErrorInvalidValue;
+    case DEC_EPI_RESID: launch_dec_gemm<DEC_EPI_RESID>(st, grid, *a); break;
+    case DEC_EPI_SWIGLU: launch_dec_gemm<DEC_EPI_SWIGLU>(st, grid, *a); break;
+    case DEC_EPI_QKV: launch_dec_gemm<DEC_EPI_QKV>(st, grid, *a); break;
+    default: launch_dec_gemm<DEC_EPI_ARGMAX>(st, grid, *a); break;
     }
     return (int)hipGetLastError();
 }
@@ -452,14 +672,14 @@ extern "C" int fvhd_launch_dec_embed(hipStream_t st, const int64_t* tok, const i
 extern "C" int fvhd_launch_dec_argmax_finish(hipStream_t st, const float* av, const int* ai, int nblk, int B, int64_t* last, int64_t* ids_out, int64_t* posv,
                                              int* len, const int* status)
 {
-    if (B < 1 || B > 16 || nblk < 1) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(dec_argmax_finish_kernel, dim3(1), dim3(256), 0, st, av, ai, nblk, B, last, ids_out, posv, len, status);
+    if (B < 1 || B > 64 || nblk < 1) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(dec_argmax_finish_kernel, dim3((B + 15) / 16), dim3(256), 0, st, av, ai, nblk, B, last, ids_out, posv, len, status);
     return (int)hipGetLastError();
 }
 
 extern "C" int fvhd_launch_dec_argmax_blocks(hipStream_t st, const float* logits, int V, int B, float* av, int* ai)
 {
-    if (B < 1 || B > 16 || V < 1) return (int)hipErrorInvalidValue;
+    if (B < 1 || B > 64 || V < 1) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(dec_argmax_blocks_kernel, dim3((V + 63) / 64), dim3(256), 0, st, logits, V, B, av, ai);
     return (int)hipGetLastError();
 }

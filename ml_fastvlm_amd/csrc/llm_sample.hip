@@ -27,7 +27,7 @@
 namespace {
 
 constexpr int SMAX = 32;                         // slices per row
-constexpr int BMAX = 16;                         // rows
+constexpr int BMAX = 16;                         // rows per launch (a wider batch runs in blocks of BMAX rows, fvhd_launch_dec_sample)
 enum { SM_TOPK = 1, SM_TOPP = 2, SM_DRAW = 3 };
 
 struct SampleRow {                               // per-row search state, written by the row's last-arriving workgroup
@@ -171,7 +171,7 @@ __global__ __launch_bounds__(256) void dec_sample_max_kernel(const DecSampleArgs
     __shared__ float red[4];
     __shared__ int flag;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.y, s = blockIdx.x, S = gridDim.x;
-    const float* x = a.logits + (size_t)b * a.V;
+    const float* x = a.logits + (size_t)(a.row0 + b) * a.V;
     int i0, i1;
     slice_of(a.V, S, s, i0, i1);
     float m = -INFINITY;
@@ -216,7 +216,7 @@ __global__ __launch_bounds__(256) void dec_sample_level_kernel(const DecSampleAr
     hc[tid] = 0;
     hm[tid] = 0;
     __syncthreads();
-    const float* x = a.logits + (size_t)b * a.V;
+    const float* x = a.logits + (size_t)(a.row0 + b) * a.V;
     int i0, i1;
     slice_of(a.V, S, s, i0, i1);
     const float T = a.temperature, M = r.smax;
@@ -305,8 +305,9 @@ __global__ __launch_bounds__(256) void dec_sample_draw_kernel(const DecSampleArg
     __shared__ int ilast[4];
     __shared__ unsigned icnt[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.y, s = blockIdx.x, S = gridDim.x;
+    const int row = a.row0 + b;                                                 // the batch row: b indexes the workspace only
     const SampleRow r = w.rows[b];
-    const float* x = a.logits + (size_t)b * a.V;
+    const float* x = a.logits + (size_t)(a.row0 + b) * a.V;
     const float T = a.temperature, M = r.smax;
     const unsigned theta = r.mode == SM_DRAW ? r.theta_key : 0u;
     int i0, i1;
@@ -350,10 +351,10 @@ __global__ __launch_bounds__(256) void dec_sample_draw_kernel(const DecSampleArg
         for (int t = 0; t < S; ++t) { Z += ssum[t]; kept += scnt[t]; lastk = max(lastk, slast[t]); }
         float u;
         if (a.u_override) {
-            u = a.u_override[b];
+            u = a.u_override[row];
         } else {
             const int n = (a.len ? *a.len : 0) + a.n_add;
-            u = (float)(philox_x0((unsigned)b, (unsigned)n, 0u, 0u, (unsigned)a.seed, (unsigned)(a.seed >> 32)) >> 8) * 0x1p-24f;
+            u = (float)(philox_x0((unsigned)row, (unsigned)n, 0u, 0u, (unsigned)a.seed, (unsigned)(a.seed >> 32)) >> 8) * 0x1p-24f;
         }
         const float target = u * Z;
         float cum = 0.f;
@@ -400,17 +401,17 @@ __global__ __launch_bounds__(256) void dec_sample_draw_kernel(const DecSampleArg
     __syncthreads();
     if (tid == 0) {
         const int64_t id = pick_id < 0 ? 0 : pick_id;
-        if (a.last) a.last[b] = id;
-        if (a.ids_out) a.ids_out[b] = id;
-        if (a.posv) a.posv[b] += 1;
+        if (a.last) a.last[row] = id;
+        if (a.ids_out) a.ids_out[row] = id;
+        if (a.posv) a.posv[row] += 1;
         if (a.info) {
-            a.info[b * 4 + 0] = theta == 0u ? -INFINITY : key_value(theta);
-            a.info[b * 4 + 1] = (float)kept_s;
-            a.info[b * 4 + 2] = z_s;
-            a.info[b * 4 + 3] = u_s;
+            a.info[row * 4 + 0] = theta == 0u ? -INFINITY : key_value(theta);
+            a.info[row * 4 + 1] = (float)kept_s;
+            a.info[row * 4 + 2] = z_s;
+            a.info[row * 4 + 3] = u_s;
         }
     }
-    // every row has read n: the last row to get here advances the length
+    // every row has read n (the earlier blocks of a wide batch ran before this launch): the last row to get here advances the length
     if (a.len_advance && arrive_last(w.cnt + BMAX, gridDim.y, &flag) && tid == 0) *a.len_advance += 1;
 }
 
@@ -419,14 +420,22 @@ extern "C" size_t fvhd_dec_sample_ws_bytes(void) { return ws_bytes(); }
 
 extern "C" int fvhd_launch_dec_sample(hipStream_t st, const DecSampleArgs* a, void* ws)
 {
-    if (!a->logits || !ws || a->B < 1 || a->B > BMAX || a->V < 1 || !(a->temperature > 0.f) || a->top_k < 0 || !(a->top_p >= 0.f && a->top_p <= 1.f))
+    if (!a->logits || !ws || a->B < 1 || a->B > 4 * BMAX || a->V < 1 || !(a->temperature > 0.f) || a->top_k < 0 || !(a->top_p >= 0.f && a->top_p <= 1.f))
         return (int)hipErrorInvalidValue;
     const SampleWs w = carve(ws);
     const int S = a->V >= SMAX * 2048 ? SMAX : (a->V + 2047) / 2048;
-    const dim3 grid((unsigned)S, (unsigned)a->B), block(256);
-    hipLaunchKernelGGL(dec_sample_max_kernel, grid, block, 0, st, *a, w);
     const int levels = 4 * ((a->top_k > 0 && a->top_k < a->V) + (a->top_p < 1.f));
-    for (int l = 0; l < levels; ++l) hipLaunchKernelGGL(dec_sample_level_kernel, grid, block, 0, st, *a, w);
-    hipLaunchKernelGGL(dec_sample_draw_kernel, grid, block, 0, st, *a, w);
+    // blocks of BMAX rows, one after the other on the stream (they share the workspace): every block reads the same n, the last one
+    // advances the length
+    for (int row0 = 0; row0 < a->B; row0 += BMAX) {
+        DecSampleArgs blk = *a;
+        blk.row0 = row0;
+        blk.B = a->B - row0 < BMAX ? a->B - row0 : BMAX;
+        if (row0 + BMAX < a->B) blk.len_advance = nullptr;
+        const dim3 grid((unsigned)S, (unsigned)blk.B), block(256);
+        hipLaunchKernelGGL(dec_sample_max_kernel, grid, block, 0, st, blk, w);
+        for (int l = 0; l < levels; ++l) hipLaunchKernelGGL(dec_sample_level_kernel, grid, block, 0, st, blk, w);
+        hipLaunchKernelGGL(dec_sample_draw_kernel, grid, block, 0, st, blk, w);
+    }
     return (int)hipGetLastError();
 }

@@ -2,7 +2,8 @@
 
 After the prefill (`Qwen2Prefill`), `transformers`' generate loop runs one eager forward per new token.  `Qwen2Generator` runs those
 steps on the library's own KV cache instead (`fvhd_llm_cache_reserve` / `fvhd_llm_start` / `fvhd_llm_decode`, include/fvhd.h "LLM
-decode"): 5 launches per decoder layer on the prefill context's packed weights (no further weight copy), greedy selection on the device,
+decode"): 5 launches per decoder layer on the prefill context's packed weights (no further weight copy), up to 64 sequences per step (the
+weights are streamed once for all of them), greedy selection on the device,
 and every step-dependent value (cache slot, positions, mask column) in device memory, so ONE captured `torch.cuda.graph` of a step
 replays for the whole generation.
 
@@ -61,14 +62,15 @@ def generation_position_ids(attention_mask: Optional[torch.Tensor], batch: int, 
 class Qwen2Generator:
     def __init__(self, prefill: Qwen2Prefill, batch: int, capacity: int, embed_tokens: Optional[torch.Tensor] = None,
                  tie_word_embeddings: Optional[bool] = None):
-        """prefill: the context whose packed weights the steps use; batch <= 16 sequences, capacity = prompt + new tokens.
+        """prefill: the context whose packed weights the steps use; batch <= 64 sequences (`_lib.MAX_DECODE_BATCH`; more than 16 need a
+        library of `_lib.WIDE_BATCH_VERSION`), capacity = prompt + new tokens.
         embed_tokens: the input embedding table of a model that does not tie it to lm_head (Qwen2-7B) - required for such a model.
         tie_word_embeddings: None = what `Qwen2Prefill.from_hf` recorded from the config; when that is unknown too (a context built by hand)
         and no embed_tokens is given, start() / step() fail instead of guessing that lm_head is the embedding table."""
         self.pre = prefill
         self.batch, self.capacity = int(batch), int(capacity)
         self.device = prefill.device
-        lib = _lib.load()
+        lib = _lib.decode_lib(self.batch)
         tied = tie_word_embeddings if tie_word_embeddings is not None else getattr(prefill, "tie_word_embeddings", None)
         if tied is not None:
             _lib.check(lib.fvhd_llm_set_tied_embeddings(prefill._h, int(bool(tied))), "fvhd_llm_set_tied_embeddings")

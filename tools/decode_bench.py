@@ -1,8 +1,13 @@
 """Decode-step time of the Qwen2 LLM on one MI355X: the library's steps (`ml_fastvlm_amd.qwen2_decode.Qwen2Generator`) replayed as one
 captured graph and called eagerly, against the stock `transformers` decode loop continuing from the same prefill cache.
 
-    python tools/decode_bench.py [--hidden 896 1536 3584] [--batch 1 8] [--prompt 285] [--new 128]
+    python tools/decode_bench.py [--hidden 896 1536 3584] [--batch 1 8 16 32 64] [--prompt 285] [--new 128] [--repeats 3] [--no-stock]
     python tools/decode_bench.py --sample [--hidden 896] [--batch 1 8]
+    python tools/decode_bench.py --trace-steps 16 --hidden 3584 --batch 64      (eager steps only: the program of a kernel trace)
+
+--batch takes up to 64 sequences per step (more than 16 need a library of version 503).  --repeats times the graph replay that many
+times (`graph_ms_per_token` is their median, `graph_ms_per_token_runs` all of them); --no-stock leaves the stock transformers loop (and
+the eager library step) out - above 16 sequences it only measures transformers.  A width's model is built and packed once for all batches.
 
 --sample times the sampled step (`Qwen2Generator.set_sampling`, csrc/llm_sample.hip) next to the greedy one, both by graph replay at
 vocab 151936, with predict.py's settings (temperature 0.2, top_k 50: transformers' default) and a flat one (temperature 1.0, top_k 0,
@@ -34,17 +39,23 @@ def _ms_per(fn, n, dev):
 
 
 @torch.no_grad()
-def measure(hidden: int, batch: int, prompt: int, new: int, dev) -> dict:
-    from tools.ttft import build_llm
+def measure(llm, pre, batch: int, prompt: int, new: int, dev, repeats: int = 1, stock: bool = True, trace_steps: int = 0) -> dict:
     from ml_fastvlm_amd.qwen2_decode import Qwen2Generator
     from ml_fastvlm_amd.qwen2_prefill import kv_to_dynamic_cache
-    llm = build_llm(hidden, dev)
     cfg = llm.config
-    gen = Qwen2Generator.from_hf(llm, batch, prompt + new + 4)
+    hidden = cfg.hidden_size
+    gen = Qwen2Generator.from_hf(llm, batch, prompt + new + 4, prefill=pre)
     g = torch.Generator(device=dev).manual_seed(0)
     emb = (0.5 * torch.randn(batch, prompt, hidden, device=dev, generator=g)).to(torch.bfloat16)
     mask = torch.ones(batch, prompt, device=dev, dtype=torch.long)
     res = {"hidden": hidden, "layers": cfg.num_hidden_layers, "batch": batch, "prompt": prompt, "new_tokens": new}
+    if trace_steps:                                         # a kernel trace's program: the prefill and `trace_steps` eager steps, nothing else
+        gen.start(emb, mask, logits=False)
+        for _ in range(trace_steps):
+            gen.step(logits=False)
+        torch.cuda.synchronize(dev)
+        res["trace_steps"] = trace_steps
+        return res
     # graph replay of one captured step
     gen.start(emb, mask, logits=False)
     graph = torch.cuda.CUDAGraph()
@@ -55,12 +66,24 @@ def measure(hidden: int, batch: int, prompt: int, new: int, dev) -> dict:
             gen.step(logits=False)
     torch.cuda.current_stream(dev).wait_stream(side)
     graph.replay()
-    gen.start(emb, mask, logits=False)
-    res["graph_ms_per_token"] = round(_ms_per(graph.replay, new, dev), 4)
+    runs = []
+    for _ in range(max(1, repeats)):
+        gen.start(emb, mask, logits=False)
+        runs.append(round(_ms_per(graph.replay, new, dev), 4))
+        assert gen.cache_state() == (prompt + new, 0)
+    res["graph_ms_per_token"] = sorted(runs)[len(runs) // 2]
+    res["graph_ms_per_token_runs"] = runs
+    I, H, nh, nkv, hd, V = cfg.intermediate_size, hidden, cfg.num_attention_heads, cfg.num_key_value_heads, hidden // cfg.num_attention_heads, cfg.vocab_size
+    wbytes = cfg.num_hidden_layers * ((nh + 2 * nkv) * hd * H + H * nh * hd + 3 * I * H) * 2 + V * H * 2
+    kvbytes = cfg.num_hidden_layers * batch * nkv * (prompt + new / 2) * hd * 2 * 2
+    res["weight_bytes_per_token"] = int(wbytes)
+    res["kv_bytes_per_token"] = int(kvbytes)
+    res["fraction_of_8TBps_graph"] = round((wbytes + kvbytes) / (res["graph_ms_per_token"] * 1e-3) / 8e12, 3)
+    if not stock:
+        return res
     gen.start(emb, mask, logits=False)
     res["eager_ms_per_token"] = round(_ms_per(lambda: gen.step(logits=False), new, dev), 4)
     # the stock transformers loop (eager module calls, DynamicCache) continuing from the same prefill's cache
-    pre = gen.pre
     logits, k, v = pre(emb, mask, None, return_kv=True)
     cache = kv_to_dynamic_cache(k, v)
     state = {"tok": logits.argmax(-1), "mask": mask, "pos": torch.full((batch, 1), prompt - 1, device=dev, dtype=torch.long)}
@@ -74,16 +97,23 @@ def measure(hidden: int, batch: int, prompt: int, new: int, dev) -> dict:
     for _ in range(3):                                      # lazy initialisation of the stock path stays out of the timing
         hf_step()
     res["stock_transformers_ms_per_token"] = round(_ms_per(hf_step, new, dev), 4)
-    I, H, nh, nkv, hd, V = cfg.intermediate_size, hidden, cfg.num_attention_heads, cfg.num_key_value_heads, hidden // cfg.num_attention_heads, cfg.vocab_size
-    wbytes = cfg.num_hidden_layers * ((nh + 2 * nkv) * hd * H + H * nh * hd + 3 * I * H) * 2 + V * H * 2
-    kvbytes = cfg.num_hidden_layers * batch * nkv * (prompt + new / 2) * hd * 2 * 2
-    res["weight_bytes_per_token"] = int(wbytes)
-    res["kv_bytes_per_token"] = int(kvbytes)
-    res["fraction_of_8TBps_graph"] = round((wbytes + kvbytes) / (res["graph_ms_per_token"] * 1e-3) / 8e12, 3)
     res["speedup_graph_vs_stock"] = round(res["stock_transformers_ms_per_token"] / res["graph_ms_per_token"], 2)
-    del gen, pre, llm, cache, k, v
-    torch.cuda.empty_cache()
     return res
+
+
+def measure_width(hidden: int, batches, prompt: int, new: int, dev, **kw) -> list:
+    """every batch of one width on ONE model and ONE packed copy of its weights"""
+    from tools.ttft import build_llm
+    from ml_fastvlm_amd.qwen2_prefill import Qwen2Prefill
+    llm = build_llm(hidden, dev)
+    pre = Qwen2Prefill.from_hf(llm)
+    rows = []
+    for b in batches:
+        rows.append(measure(llm, pre, b, prompt, new, dev, **kw))
+        torch.cuda.empty_cache()
+    del pre, llm
+    torch.cuda.empty_cache()
+    return rows
 
 
 SAMPLE_SETTINGS = {"predict_py": dict(temperature=0.2, top_k=50, top_p=1.0), "flat": dict(temperature=1.0, top_k=0, top_p=0.95)}
@@ -142,6 +172,9 @@ def main():
     ap.add_argument("--prompt", type=int, default=285)
     ap.add_argument("--new", type=int, default=128)
     ap.add_argument("--sample", action="store_true", help="the sampled step against the greedy one (default widths: 896 only)")
+    ap.add_argument("--repeats", type=int, default=1, help="time the graph replay this many times")
+    ap.add_argument("--no-stock", action="store_true", help="leave out the stock transformers loop and the eager library step")
+    ap.add_argument("--trace-steps", type=int, default=0, help="run only the prefill and this many eager steps (for a kernel trace)")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     if a.sample:
@@ -149,8 +182,11 @@ def main():
         rows = [measure_sample(h, b, a.prompt, a.new, dev) for h in hidden for b in a.batch]
         print(json.dumps({"tool": "decode_bench", "mode": "sample", "device": torch.cuda.get_device_name(dev), "results": rows}))
         return
-    rows = [measure(h, b, a.prompt, a.new, dev) for h in a.hidden for b in a.batch]
-    print(json.dumps({"tool": "decode_bench", "device": torch.cuda.get_device_name(dev), "results": rows}))
+    from ml_fastvlm_amd import _lib
+    rows = [r for h in a.hidden for r in measure_width(h, a.batch, a.prompt, a.new, dev, repeats=a.repeats, stock=not a.no_stock,
+                                                       trace_steps=a.trace_steps)]
+    print(json.dumps({"tool": "decode_bench", "device": torch.cuda.get_device_name(dev), "library_version": _lib.load().fvhd_version(),
+                      "results": rows}))
 
 
 if __name__ == "__main__":

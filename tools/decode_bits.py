@@ -1,0 +1,95 @@
+"""Are the decode's bits those of another build of the library?  Dumps teacher-forced step logits and sampled ids of small Qwen2
+stand-ins, then compares two dumps with torch.equal.
+
+    FVHD_LIB=/path/to/other/libfvhd.so python tools/decode_bits.py dump other.pt
+    python tools/decode_bits.py dump this.pt
+    python tools/decode_bits.py compare other.pt this.pt  > profiles/<round>_decode_batch_bits.log
+
+Per width (the 0.5B and 7B shapes, 2 / 1 layers, vocab 4096) and batch (1, 8, 16 - what every library version decodes): the fp32 logits
+of the prefill and of 16 steps fed fixed token ids, the greedy ids of every step, and the ids of a sampled generation (temperature 0.7,
+top_k 50, top_p 0.9, seed 3).  Everything is seeded; the two dumps must come from the same GPU model."""
+from __future__ import annotations
+
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+CONFIGS = {
+    "0.5B": dict(hidden_size=896, num_hidden_layers=2, num_attention_heads=14, num_key_value_heads=2, intermediate_size=4864, tie_word_embeddings=True),
+    "7B": dict(hidden_size=3584, num_hidden_layers=1, num_attention_heads=28, num_key_value_heads=4, intermediate_size=18944, tie_word_embeddings=False),
+}
+BATCHES = (1, 8, 16)
+T, STEPS, VOCAB = 24, 16, 4096
+
+
+def _model(name):
+    from transformers import Qwen2Config, Qwen2ForCausalLM
+    torch.manual_seed(0)
+    cfg = Qwen2Config(vocab_size=VOCAB, max_position_embeddings=4096, rope_theta=1e6, rms_norm_eps=1e-6, **CONFIGS[name])
+    m = Qwen2ForCausalLM(cfg).eval()
+    with torch.no_grad():
+        for p in m.parameters():
+            if p.dim() == 1:
+                p.add_(0.05 * torch.randn_like(p))
+    return m.to("cuda", torch.bfloat16)
+
+
+@torch.no_grad()
+def dump(path):
+    from ml_fastvlm_amd import _lib
+    from ml_fastvlm_amd.qwen2_decode import Qwen2Generator
+    from ml_fastvlm_amd.qwen2_prefill import Qwen2Prefill
+    out = {"version": _lib.load().fvhd_version(), "device": torch.cuda.get_device_name(0)}
+    for name in CONFIGS:
+        m = _model(name)
+        pre = Qwen2Prefill.from_hf(m)
+        for B in BATCHES:
+            g = torch.Generator().manual_seed(100 + B)
+            e = (0.5 * torch.randn(B, T, m.config.hidden_size, generator=g)).to("cuda", torch.bfloat16)
+            mask = torch.ones(B, T, dtype=torch.long)
+            for b in range(B):
+                mask[b, :(5 * b) % 13] = 0
+            mask = mask.cuda()
+            fed = torch.randint(0, VOCAB, (STEPS, B), generator=g).cuda()
+            gen = Qwen2Generator.from_hf(m, B, T + STEPS + 4, prefill=pre)
+            lg, ids = gen.start(e, mask)
+            logits, chosen = [lg.clone().cpu()], [ids.clone().cpu()]
+            for i in range(STEPS):
+                lg, ids = gen.step(fed[i].contiguous())
+                logits.append(lg.clone().cpu())
+                chosen.append(ids.clone().cpu())
+            key = f"{name} B={B}"
+            out[key + " logits"] = torch.stack(logits)
+            out[key + " greedy ids"] = torch.stack(chosen)
+            out[key + " sampled ids"] = gen.sample(e, mask, None, max_new_tokens=STEPS, temperature=0.7, top_k=50, top_p=0.9, seed=3).cpu()
+            out[key + " greedy generation"] = gen.greedy(e, mask, None, max_new_tokens=STEPS, pad_token_id=0).cpu()
+            del gen
+    torch.save(out, path)
+    print(f"decode_bits: library version {out['version']} on {out['device']}: {len(out) - 2} tensors -> {path}")
+
+
+def compare(pa, pb):
+    a, b = torch.load(pa), torch.load(pb)
+    print(f"decode_bits compare: library version {a['version']} ({a['device']}) against {b['version']} ({b['device']})")
+    keys = [k for k in a if k not in ("version", "device")]
+    assert keys == [k for k in b if k not in ("version", "device")]
+    bad = 0
+    for k in keys:
+        same = a[k].shape == b[k].shape and torch.equal(a[k], b[k])
+        finite = bool(torch.isfinite(a[k].float()).all())
+        bad += not (same and finite)
+        print(f"{k:28s} {str(tuple(a[k].shape)):18s} {'torch.equal: True' if same else 'DIFFERENT'}{'' if finite else '  (non-finite values)'}")
+    print(f"{len(keys) - bad} of {len(keys)} tensors identical")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    if len(sys.argv) == 3 and sys.argv[1] == "dump":
+        dump(sys.argv[2])
+    elif len(sys.argv) == 4 and sys.argv[1] == "compare":
+        sys.exit(compare(sys.argv[2], sys.argv[3]))
+    else:
+        sys.exit(__doc__)
