@@ -22,6 +22,7 @@
 #ifndef FVHD_H
 #define FVHD_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -51,8 +52,10 @@ typedef void* fvhd_stream_t; /* hipStream_t */
  * fvhd_op_dec_*); nothing earlier changed.  502 adds LLM sampling (fvhd_llm_set_sampling, fvhd_op_dec_sample): greedy stays the
  * default and computes what 501 did; no earlier signature changed.  503 widens the LLM decode from 16 to 64 sequences per step
  * (fvhd_llm_cache_reserve, fvhd_op_dec_gemm / _qkv / _attention / _lm_argmax: B in [1, 64]; the scratch of the single ops grows with
- * ceil(B / 16)); no signature changed and B <= 16 computes what 502 did, bit for bit. */
-#define FVHD_VERSION 503
+ * ceil(B / 16)); no signature changed and B <= 16 computes what 502 did, bit for bit.  504 adds 8-bit LLM weights
+ * (fvhd_llm_set_weight_format, fvhd_llm_weight_bytes, fvhd_llm_debug_packed_e4m3, fvhd_op_quantize_e4m3, fvhd_op_dec_gemm_w8 / _qkv_w8 /
+ * _lm_argmax_w8): bf16 stays the default and computes what 503 did, bit for bit; nothing earlier changed. */
+#define FVHD_VERSION 504
 int fvhd_version(void);
 const char* fvhd_last_error(void);
 
@@ -496,6 +499,53 @@ int fvhd_op_dec_attention(fvhd_stream_t stream, const void* q, const void* k_cac
  * scratch_v / scratch_i: [ceil(V / 64) * 16 * ceil(B / 16)] each */
 int fvhd_op_dec_lm_argmax(fvhd_stream_t stream, const void* x, int B, const float* norm_w, float eps, const void* Wt, int V, int K, float* logits,
                           int64_t* ids_out, float* scratch_v, int* scratch_i);
+
+/* ---- LLM 8-bit weights: the packed matrices as OCP e4m3 codes with one scale per output row (version 504) ---------------------------------
+ * Weight-only storage: a matrix W [N, K] (the reference's [out, in] layout) is held as K e4m3 codes (gfx950's e4m3fn: no infinity,
+ * maximum 448) per row plus scale[n] (fp32); row n stands for code * scale[n].  The arithmetic does not change: the decode GEMMs convert the
+ * codes to bf16 in registers (exact), multiply the same bf16 activation fragments on the same 16 x 16 x 32 MFMA with fp32 accumulation and
+ * apply the row scale to the finished accumulator (after the split-K sum, before bias / residual / SwiGLU / logits); the prefill dequantises
+ * each matrix into a bf16 scratch (the size of the largest matrix, lm_head included) right before its bf16 GEMM.  The step streams half the
+ * bytes and the packed copy occupies half the bytes; no bf16 copy of the matrices is kept.  Vectors (norm weights, biases), the KV cache,
+ * the activations and model.embed_tokens.weight (a row gather) stay as they are; a tied model's decode embeds through the dequantised
+ * lm_head rows.
+ * The library's quantiser uses POWER-OF-TWO scales: scale = 2^ceil(log2(amax_row / 448)) (kept >= 2^-126; an all-zero row: scale 1, codes 0),
+ * codes = w / scale rounded to nearest even; amax / scale lies in (224, 448], nothing saturates.  code * scale is then exactly a bf16
+ * value, so the prefill (bf16 code * scale) and the decode (scale applied in fp32 to the accumulator) work on identical weight values, and a
+ * stock bf16 / fp32 model holding the dequantised weights is an exact-weight oracle.  The single ops below accept any positive finite fp32
+ * scale; only powers of two keep that identity. */
+#define FVHD_W_BF16 0
+#define FVHD_W_E4M3 1
+/* The storage format of the packed matrices (lm_head.weight included).  Call it right after fvhd_llm_create: once a tensor was set it fails
+ * with an error (both fvhd_llm_set_tensor paths quantise matrices as they arrive).  FVHD_W_E4M3 needs hidden, n_heads * head_dim and
+ * intermediate to be multiples of 128.  Re-allocates the weight buffer (and the dequantisation scratch). */
+int fvhd_llm_set_weight_format(fvhd_llm* ctx, int format);
+/* device bytes held by the packed weights: matrices, row scales, norm weights and biases (not the workspace, the caches, the optional
+ * embedding table or the e4m3 dequantisation scratch) */
+int fvhd_llm_weight_bytes(const fvhd_llm* ctx, size_t* bytes);
+/* tests: one packed matrix of an FVHD_W_E4M3 context in plain [N, K] order (the K order inside the weight buffer is private):
+ * codes_out u8 [N][K], scale_out fp32 [N], device pointers.  FVHD_MAT_QKV: q | k | v rows [(n_heads + 2 n_kv_heads) * head_dim, hidden];
+ * FVHD_MAT_GATE_UP: gate / up rows interleaved [2 * intermediate, hidden]; FVHD_MAT_LM_HEAD ignores `layer`. */
+#define FVHD_MAT_QKV 0
+#define FVHD_MAT_O 1
+#define FVHD_MAT_GATE_UP 2
+#define FVHD_MAT_DOWN 3
+#define FVHD_MAT_LM_HEAD 4
+int fvhd_llm_debug_packed_e4m3(fvhd_llm* ctx, int layer, int matrix, void* codes_out, float* scale_out, fvhd_stream_t stream);
+/* the quantiser on its own: W bf16 [N, K] (K % 8 == 0) -> codes u8 [N, K] (row-major, k order), scale fp32 [N]; codes equal torch's
+ * (w / scale).to(torch.float8_e4m3fn) bit for bit */
+int fvhd_op_quantize_e4m3(fvhd_stream_t stream, const void* W, int N, int K, void* codes, float* scale);
+/* fvhd_op_dec_gemm / _qkv / _lm_argmax on e4m3 weights: the same arguments plus `scale` (fp32 [N]), Wt = plain row-major codes u8 [N, K].
+ * With every scale = 1 the output has the bits of the bf16 op on bf16(codes).  The codes are first repacked into a process-wide scratch
+ * (allocated on demand): eager calls only, not during stream capture. */
+int fvhd_op_dec_gemm_w8(fvhd_stream_t stream, int epi, const void* x, int B, const float* norm_w, float eps, const void* Wt, const float* scale, int N,
+                        int K, const void* resid, void* out, float* partial, int* counters, int splits);
+int fvhd_op_dec_qkv_w8(fvhd_stream_t stream, const void* x, int B, int K, const float* norm_w, float eps, const void* Wt, const float* scale,
+                       const float* bias, void* q_out, const int64_t* pos, const float* table, int table_positions, float rope_theta, void* k_cache,
+                       void* v_cache, int capacity, const int* length, int n_heads, int n_kv_heads, int head_dim, float* partial, int* counters,
+                       int splits);
+int fvhd_op_dec_lm_argmax_w8(fvhd_stream_t stream, const void* x, int B, const float* norm_w, float eps, const void* Wt, const float* scale, int V,
+                             int K, float* logits, int64_t* ids_out, float* scratch_v, int* scratch_i);
 
 #ifdef __cplusplus
 }

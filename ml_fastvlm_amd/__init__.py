@@ -8,6 +8,7 @@ Public surface (mirrors `llava.model.multimodal_encoder` / `multimodal_projector
 """
 from .builder import build_vision_projector, build_vision_tower, encode_images, generate, install_into_llava, library_projector, project  # noqa: F401
 from .mobileclip_encoder import MobileCLIPVisionTower, load_model_config  # noqa: F401
+from .qwen2_prefill import quantize_rows_e4m3  # noqa: F401
 
 __all__ = ["MobileCLIPVisionTower", "build_vision_tower", "build_vision_projector", "encode_images", "project",
-           "library_projector", "install_into_llava", "load_model_config", "generate"]
+           "library_projector", "install_into_llava", "load_model_config", "generate", "quantize_rows_e4m3"]

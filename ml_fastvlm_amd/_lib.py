@@ -14,7 +14,11 @@ LIB_PATH = os.environ.get("FVHD_LIB") or os.path.join(_HERE, "libfvhd.so")
 ABI_VERSION = 501               # the oldest FVHD_VERSION (include/fvhd.h) this stub loads (major = ABI_VERSION // 100)
 SAMPLING_VERSION = 502          # the first with fvhd_llm_set_sampling / fvhd_op_dec_sample (declared only when the library has them)
 WIDE_BATCH_VERSION = 503       # the first whose decode takes more than 16 sequences per step (up to MAX_DECODE_BATCH)
+W8_VERSION = 504               # the first with 8-bit (e4m3) LLM weights: fvhd_llm_set_weight_format, fvhd_op_*_w8 (declared only when the library has them)
 MAX_DECODE_BATCH = 64
+W_BF16, W_E4M3 = 0, 1           # fvhd_llm_set_weight_format (include/fvhd.h)
+WEIGHT_FORMATS = {"bf16": W_BF16, "fp8_e4m3": W_E4M3}
+MAT_QKV, MAT_O, MAT_GATE_UP, MAT_DOWN, MAT_LM_HEAD = 0, 1, 2, 3, 4     # fvhd_llm_debug_packed_e4m3
 F32, F16, BF16 = 0, 1, 2
 FFN_HALF, FFN_BF16 = 0, 1        # precision of the fused ConvFFN's hidden activation (include/fvhd.h)
 EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_LS_RESID, EPI_RESID, EPI_SWIGLU = 0, 1, 2, 3, 4, 5
@@ -112,6 +116,16 @@ def _declare(lib) -> None:
             "fvhd_llm_set_sampling": (ci, [vp, ci, cf, ci, cf, C.c_ulonglong]),
             "fvhd_op_dec_sample": (ci, [vp, vp, ci, ci, cf, ci, cf, C.c_ulonglong, ci, vp, vp, vp]),
         })
+    if lib.fvhd_version() >= W8_VERSION:           # an older library loads without them; w8_lib() then names the rebuild
+        sig.update({
+            "fvhd_llm_set_weight_format": (ci, [vp, ci]),
+            "fvhd_llm_weight_bytes": (ci, [vp, C.POINTER(C.c_size_t)]),
+            "fvhd_llm_debug_packed_e4m3": (ci, [vp, ci, ci, vp, vp, vp]),
+            "fvhd_op_quantize_e4m3": (ci, [vp, vp, ci, ci, vp, vp]),
+            "fvhd_op_dec_gemm_w8": (ci, [vp, ci, vp, ci, vp, cf, vp, vp, ci, ci, vp, vp, vp, vp, ci]),
+            "fvhd_op_dec_qkv_w8": (ci, [vp, vp, ci, ci, vp, cf, vp, vp, vp, vp, vp, vp, ci, cf, vp, vp, ci, vp, ci, ci, ci, vp, vp, ci]),
+            "fvhd_op_dec_lm_argmax_w8": (ci, [vp, vp, ci, vp, cf, vp, vp, ci, ci, vp, vp, vp, vp]),
+        })
     del fp, cl
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)     # AttributeError here = the .so does not export what fvhd.h declares
@@ -149,6 +163,25 @@ def sampling_lib():
         raise FvhdError(f"{LIB_PATH} reports ABI version {got}: sampling (fvhd_llm_set_sampling, fvhd_op_dec_sample) needs {SAMPLING_VERSION} - "
                         "rebuild the library (`python -m ml_fastvlm_amd.build`)")
     return lib
+
+
+def w8_lib():
+    """load(), for the 8-bit weight entry points: a library older than W8_VERSION loads (bf16 weights work on it) but has none of them, and
+    this says so instead of an AttributeError."""
+    lib = load()
+    got = lib.fvhd_version()
+    if got < W8_VERSION:
+        raise FvhdError(f"{LIB_PATH} reports ABI version {got}: 8-bit weights (fvhd_llm_set_weight_format, fvhd_op_dec_gemm_w8, ...) need "
+                        f"{W8_VERSION} - rebuild the library (`python -m ml_fastvlm_amd.build`)")
+    return lib
+
+
+def weight_format_code(weights: str) -> int:
+    """"bf16" / "fp8_e4m3" -> FVHD_W_BF16 / FVHD_W_E4M3; anything else is a ValueError"""
+    try:
+        return WEIGHT_FORMATS[weights]
+    except (KeyError, TypeError):
+        raise ValueError(f"weights must be one of {sorted(WEIGHT_FORMATS)}, got {weights!r}") from None
 
 
 def decode_lib(batch: int):

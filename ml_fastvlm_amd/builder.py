@@ -92,7 +92,8 @@ def encode_images(vision_tower, mm_projector, images):
     return project(vision_tower, mm_projector, image_features)
 
 
-def install_into_llava(splice: bool = False, prefill: bool = False, prefill_any_dtype: bool = False, generate: bool = False) -> None:
+def install_into_llava(splice: bool = False, prefill: bool = False, prefill_any_dtype: bool = False, generate: bool = False,
+                       llm_weights: str = "bf16") -> None:
     """Make an unmodified `llava` package (the reference) build and call the MI355X tower; splice=True also routes
     `prepare_inputs_labels_for_multimodal` through the GPU splice (needs the embeddings on a HIP device); prefill=True also runs the
     PREFILL step of `LlavaQwen2ForCausalLM.forward` (`llava_qwen.py:92-103`: the first forward of `generate`, on `inputs_embeds`
@@ -101,7 +102,11 @@ def install_into_llava(splice: bool = False, prefill: bool = False, prefill_any_
     and its precision); prefill_any_dtype=True opts such a model in knowingly (its prefill then runs in bf16, the cache is cast back).
     generate=True replaces `LlavaQwen2ForCausalLM.generate` (`llava_qwen.py:106-143`) by `_make_library_generate`: the unchanged call of
     predict.py (sampling included) then runs its prefill and every decode step on the library, and any setting the library does not
-    implement falls back to the reference's generate with a one-time warning."""
+    implement falls back to the reference's generate with a one-time warning.
+    llm_weights: "bf16" (the default) or "fp8_e4m3" - the storage of the LLM's packed matrices in the library's prefill / decode contexts
+    (`Qwen2Prefill.from_hf(weights=...)`), recorded on `LlavaQwen2ForCausalLM` for `prefill_context` to read."""
+    from ._lib import weight_format_code
+    weight_format_code(llm_weights)
     import llava.model.llava_arch as arch
     import llava.model.multimodal_encoder.builder as enc_builder
 
@@ -122,6 +127,9 @@ def install_into_llava(splice: bool = False, prefill: bool = False, prefill_any_
     arch.LlavaMetaForCausalLM.encode_images = _encode_images
     if splice:
         arch.LlavaMetaForCausalLM.prepare_inputs_labels_for_multimodal = prepare_inputs_labels_for_multimodal
+    if prefill or generate:
+        import llava.model.language_model.llava_qwen as lq
+        lq.LlavaQwen2ForCausalLM._fvhd_llm_weights = llm_weights
     if prefill:
         import llava.model.language_model.llava_qwen as lq
         cur = lq.LlavaQwen2ForCausalLM.forward
@@ -192,16 +200,24 @@ def _make_prefill_forward(orig_forward, any_dtype: bool = False):
     return forward
 
 
-def prefill_context(model):
+def prefill_context(model, weights=None):
     """The `Qwen2Prefill` context of a (Llava)Qwen2ForCausalLM, built on first use and rebuilt when its weights change (in place or by
     re-assignment).  `install_into_llava(prefill=True)` users call this once after loading the model so that the packing (device-to-device
-    copies, ~0.1 s for 0.5B) is not part of the first request's TTFT."""
+    copies, ~0.1 s for 0.5B) is not part of the first request's TTFT.
+    weights: "bf16" / "fp8_e4m3" - recorded on the model (`_fvhd_llm_weights`); None = what was recorded (by an earlier call or by
+    `install_into_llava(llm_weights=...)`), else "bf16".  A context in the other format is rebuilt, not reused."""
+    from ._lib import weight_format_code
     from .qwen2_prefill import Qwen2Prefill
+    if weights is None:
+        weights = getattr(model, "_fvhd_llm_weights", "bf16")
+    else:
+        weight_format_code(weights)
+        object.__setattr__(model, "_fvhd_llm_weights", weights)
     key = tuple((p.data_ptr(), p._version) for p in (model.lm_head.weight, model.model.layers[0].self_attn.q_proj.weight,
                                                       model.model.layers[-1].mlp.down_proj.weight, model.model.norm.weight))
     pre = getattr(model, "_fvhd_prefill_ctx", None)
-    if pre is None or pre[0] != key:
-        pre = (key, Qwen2Prefill.from_hf(model))
+    if pre is None or pre[0] != key or pre[1].weight_format != weights:
+        pre = (key, Qwen2Prefill.from_hf(model, weights=weights))
         object.__setattr__(model, "_fvhd_prefill_ctx", pre)
     return pre[1]
 
@@ -240,16 +256,17 @@ def prepare_inputs_labels_for_multimodal(self, input_ids, position_ids, attentio
 _GENERATE_IGNORED = ("temperature", "top_p", "top_k")     # sampling knobs transformers itself ignores under do_sample=False
 
 
-def generator_context(model, batch: int, capacity: int):
+def generator_context(model, batch: int, capacity: int, weights=None):
     """The `Qwen2Generator` of a (Llava)Qwen2ForCausalLM, on the model's `prefill_context` (same packed weights - no further copy), cached
-    on the model and rebuilt when the weights change or a larger (batch, capacity) is asked for."""
+    on the model and rebuilt when the weights change, their format (`weights`, as in `prefill_context`) changes or a larger (batch, capacity)
+    is asked for."""
     from .qwen2_decode import Qwen2Generator
-    pre = prefill_context(model)
+    pre = prefill_context(model, weights)
     gen = getattr(model, "_fvhd_generator", None)
     if gen is None or gen.pre is not pre or gen.batch < batch or gen.capacity < capacity:
         if gen is not None and gen.pre is pre:
             batch, capacity = max(batch, gen.batch), max(capacity, gen.capacity)
-        gen = Qwen2Generator.from_hf(model, batch, capacity, prefill=pre)
+        gen = Qwen2Generator.from_hf(model, batch, capacity, prefill=pre, weights=pre.weight_format)
         object.__setattr__(model, "_fvhd_generator", gen)
     return gen
 

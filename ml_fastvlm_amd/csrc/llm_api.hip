@@ -35,6 +35,10 @@ int fvhd_launch_dec_embed(hipStream_t, const int64_t*, const int64_t*, const voi
 int fvhd_launch_dec_argmax_finish(hipStream_t, const float*, const int*, int, int, int64_t*, int64_t*, int64_t*, int*, const int*);
 int fvhd_launch_dec_argmax_blocks(hipStream_t, const float*, int, int, float*, int*);
 int fvhd_launch_dec_start_state(hipStream_t, int64_t*, const int64_t*, int, int, int*, int*);
+// llm_w8.hip
+int fvhd_launch_quantize_e4m3(hipStream_t, const void*, int, int, void*, long, float*, int, int);
+int fvhd_launch_w8_unpack(hipStream_t, const void*, const float*, void*, long, int, int);
+int fvhd_launch_dec_embed_w8(hipStream_t, const int64_t*, const int64_t*, const void*, const float*, int, int, void*, unsigned char*, int, int, const int*, int*, int*);
 // llm_sample.hip
 size_t fvhd_dec_sample_ws_bytes(void);
 int fvhd_launch_dec_sample(hipStream_t, const DecSampleArgs*, void*);
@@ -80,7 +84,7 @@ float load_as_float(const void* p, int dtype, size_t i)
     return half_to_float(((const uint16_t*)p)[i]);
 }
 
-struct LayerOff { size_t ln1, wqkv, bqkv, wo, ln2, wgu, wd; };
+struct LayerOff { size_t ln1, wqkv, bqkv, wo, ln2, wgu, wd, sqkv, so, sgu, sd; };     // s*: the fp32 row scales of an e4m3 matrix
 
 struct DevGuard {
     int prev = -1; bool sw = false; hipError_t err = hipSuccess;
@@ -97,7 +101,12 @@ struct fvhd_llm {
     char* wdev = nullptr;
     size_t wbytes = 0;
     std::vector<LayerOff> lo;
-    size_t norm_off = 0, lm_off = 0;
+    size_t norm_off = 0, lm_off = 0, lm_soff = 0;
+    int wfmt = FVHD_W_BF16;                // fvhd_llm_set_weight_format: FVHD_W_E4M3 = every matrix as e4m3 codes (1 byte, the K order of llm_w8.hip) + one
+                                           // fp32 scale per row; vectors and model.embed_tokens.weight are not affected
+    bool any_set = false;                  // a tensor was set: the format is fixed
+    char* wscratch = nullptr;              // e4m3: bf16 scratch of the largest matrix - the prefill dequantises each matrix into it right before its GEMM
+    size_t wscratch_bytes = 0;
     std::vector<char> got;                 // per expected tensor: received?
     std::vector<std::string> names;
     // workspace
@@ -179,6 +188,73 @@ bool is_embed_key(const char* key)
     return k == "model.embed_tokens.weight" || k == "embed_tokens.weight";
 }
 
+// offsets of the packed weights in `wdev` for the context's weight format -> c->lo, norm_off, lm_off, lm_soff, wbytes
+void weight_layout(fvhd_llm* c)
+{
+    const size_t H = c->H, I = c->I, qkvw = c->qkvw, ao = (size_t)c->nh * c->hd, V = c->V;
+    const bool q8 = c->wfmt == FVHD_W_E4M3;
+    const size_t eb = q8 ? 1 : 2;          // bytes per matrix element
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += al256(bytes); return o; };
+    c->lo.assign(c->L, LayerOff{});
+    for (int l = 0; l < c->L; ++l) {
+        LayerOff& o = c->lo[l];
+        o.ln1 = take(H * 4);
+        o.wqkv = take(qkvw * H * eb);
+        o.bqkv = take(qkvw * 4);
+        o.wo = take(H * ao * eb);
+        o.ln2 = take(H * 4);
+        o.wgu = take(2 * I * H * eb);
+        o.wd = take(H * I * eb);
+        if (q8) { o.sqkv = take(qkvw * 4); o.so = take(H * 4); o.sgu = take(2 * I * 4); o.sd = take(H * 4); }
+    }
+    c->norm_off = take(H * 4);
+    c->lm_off = take(V * H * eb);
+    c->lm_soff = q8 ? take(V * 4) : 0;
+    c->wbytes = off;
+}
+
+// where a tensor of the state dict goes: cols == 0: `rows` floats at base + 4 eoff; else a [rows][cols] matrix whose element (0, 0) is
+// element eoff of the packed matrix at `base`, rows `pitch` elements apart (gate / up: interleaved rows), and - e4m3 - whose row scales
+// start at float seoff of `sbase`, one every `sstride` floats
+struct Slot { size_t base = 0, eoff = 0, rows = 0, cols = 0, pitch = 0, sbase = 0, seoff = 0; int sstride = 1; };
+
+Slot slot_of(const fvhd_llm* c, int layer, int which)
+{
+    const size_t H = c->H, hd = c->hd, nh = c->nh, nkv = c->nkv, I = c->I;
+    Slot s;
+    if (layer < 0) {
+        if (which == 0) { s.base = c->norm_off; s.rows = H; }
+        else { s.base = c->lm_off; s.rows = c->V; s.cols = H; s.pitch = H; s.sbase = c->lm_soff; }
+        return s;
+    }
+    const LayerOff& o = c->lo[layer];
+    switch (which) {
+    case 0: s.base = o.ln1; s.rows = H; break;
+    case 1: s.base = o.wqkv; s.rows = nh * hd; s.cols = H; s.pitch = H; s.sbase = o.sqkv; break;
+    case 2: s.base = o.bqkv; s.rows = nh * hd; break;
+    case 3: s.base = o.wqkv; s.eoff = nh * hd * H; s.rows = nkv * hd; s.cols = H; s.pitch = H; s.sbase = o.sqkv; s.seoff = nh * hd; break;
+    case 4: s.base = o.bqkv; s.eoff = nh * hd; s.rows = nkv * hd; break;
+    case 5: s.base = o.wqkv; s.eoff = (nh + nkv) * hd * H; s.rows = nkv * hd; s.cols = H; s.pitch = H; s.sbase = o.sqkv; s.seoff = (nh + nkv) * hd; break;
+    case 6: s.base = o.bqkv; s.eoff = (nh + nkv) * hd; s.rows = nkv * hd; break;
+    case 7: s.base = o.wo; s.rows = H; s.cols = nh * hd; s.pitch = nh * hd; s.sbase = o.so; break;
+    case 8: s.base = o.ln2; s.rows = H; break;
+    // gate / up rows interleaved (row 2j = gate_j, row 2j + 1 = up_j): the SwiGLU epilogue of the GEMM pairs adjacent columns
+    case 9: s.base = o.wgu; s.rows = I; s.cols = H; s.pitch = 2 * H; s.sbase = o.sgu; s.sstride = 2; break;
+    case 10: s.base = o.wgu; s.eoff = H; s.rows = I; s.cols = H; s.pitch = 2 * H; s.sbase = o.sgu; s.seoff = 1; s.sstride = 2; break;
+    case 11: s.base = o.wd; s.rows = H; s.cols = I; s.pitch = I; s.sbase = o.sd; break;
+    }
+    return s;
+}
+
+// e4m3: bf16 rows [rows][cols] on the device -> codes + scales at the slot (rows are whole, so every source tensor quantises on its own)
+int quantize_into(fvhd_llm* c, const Slot& s, const void* dev_bf16, hipStream_t st)
+{
+    const int e = fvhd_launch_quantize_e4m3(st, dev_bf16, (int)s.rows, (int)s.cols, c->wdev + s.base + s.eoff, (long)s.pitch,
+                                            (float*)(c->wdev + s.sbase) + s.seoff, s.sstride, 1);
+    return e ? lhip("quantise to e4m3", (hipError_t)e) : 0;
+}
+
 int ensure_emb(fvhd_llm* c)
 {
     if (c->emb) return 0;
@@ -195,6 +271,19 @@ int upload_matrix(const void* host, int dtype, size_t rows, size_t cols, char* d
         for (size_t i = 0; i < rows * cols; ++i) tmp[i] = bf16_rne(load_as_float(host, dtype, i));
     hipError_t e = hipMemcpy2D(dst, pitch_elems * 2, tmp.data(), cols * 2, cols * 2, rows, hipMemcpyHostToDevice);
     return e == hipSuccess ? 0 : lhip("hipMemcpy2D(llm weights)", e);
+}
+
+// e4m3: the same host rows through a bf16 staging buffer on the device and the quantise kernel
+int upload_matrix_q(fvhd_llm* c, const void* host, int dtype, const Slot& s)
+{
+    char* stage = nullptr;
+    hipError_t e = hipMalloc((void**)&stage, s.rows * s.cols * 2);
+    if (e != hipSuccess) return lhip("hipMalloc(quantise staging)", e);
+    int r = upload_matrix(host, dtype, s.rows, s.cols, stage, s.cols);
+    if (!r) r = quantize_into(c, s, stage, nullptr);
+    if (!r && (e = hipStreamSynchronize(nullptr)) != hipSuccess) r = lhip("hipStreamSynchronize(quantise)", e);
+    (void)hipFree(stage);
+    return r;
 }
 
 int upload_vector_f32(const void* host, int dtype, size_t n, char* dst)
@@ -290,26 +379,11 @@ int fvhd_llm_create(fvhd_llm** out, int device, int hidden, int n_layers, int n_
     if (const char* ev = getenv("FVHD_LLM_FUSENORM")) c->fuse_norm = atoi(ev);
     if (const char* ev = getenv("FVHD_LLM_FUSEROPE")) c->fuse_rope = atoi(ev);
     if (const char* ev = getenv("FVHD_DEC_RSTD_ONCE")) c->dec_rstd_once = atoi(ev);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += al256(bytes); return o; };
-    c->lo.resize(n_layers);
-    for (int l = 0; l < n_layers; ++l) {
-        LayerOff& o = c->lo[l];
-        o.ln1 = take((size_t)hidden * 4);
-        o.wqkv = take((size_t)qkvw * hidden * 2);
-        o.bqkv = take((size_t)qkvw * 4);
-        o.wo = take((size_t)hidden * n_heads * head_dim * 2);
-        o.ln2 = take((size_t)hidden * 4);
-        o.wgu = take((size_t)2 * intermediate * hidden * 2);
-        o.wd = take((size_t)hidden * intermediate * 2);
-    }
-    c->norm_off = take((size_t)hidden * 4);
-    c->lm_off = take((size_t)vocab * hidden * 2);
-    c->wbytes = off;
+    weight_layout(c);
     c->got.assign((size_t)n_layers * 12 + 2, 0);
     DevGuard g(device);
     if (g.err != hipSuccess) { delete c; return lhip("hipSetDevice", g.err); }
-    hipError_t e = hipMalloc((void**)&c->wdev, off);
+    hipError_t e = hipMalloc((void**)&c->wdev, c->wbytes);
     if (e != hipSuccess) { delete c; return lhip("hipMalloc(llm weights)", e); }
     *out = c;
     return 0;
@@ -321,6 +395,7 @@ void fvhd_llm_destroy(fvhd_llm* c)
     DevGuard g(c->device);
     (void)hipDeviceSynchronize();
     if (c->wdev) (void)hipFree(c->wdev);
+    if (c->wscratch) (void)hipFree(c->wscratch);
     if (c->ws) (void)hipFree(c->ws);
     for (char* p : c->retired) (void)hipFree(p);
     if (c->load_ev) (void)hipEventDestroy(c->load_ev);
@@ -329,6 +404,41 @@ void fvhd_llm_destroy(fvhd_llm* c)
     if (c->pre_kv) (void)hipFree(c->pre_kv);
     if (c->status_host) (void)hipHostFree(c->status_host);
     delete c;
+}
+
+int fvhd_llm_set_weight_format(fvhd_llm* c, int format)
+{
+    if (!c) return lfail("fvhd_llm_set_weight_format: ctx is NULL");
+    if (format != FVHD_W_BF16 && format != FVHD_W_E4M3) return lfail("fvhd_llm_set_weight_format: format must be FVHD_W_BF16 or FVHD_W_E4M3");
+    if (c->any_set)
+        return lfail("fvhd_llm_set_weight_format: a tensor was already set - choose the format right after fvhd_llm_create, before the first "
+                     "fvhd_llm_set_tensor / fvhd_llm_set_tensor_device (the matrices are quantised as they arrive)");
+    if (format == c->wfmt) return 0;
+    if (format == FVHD_W_E4M3 && (c->H % 128 || (c->nh * c->hd) % 128 || c->I % 128))
+        return lfail("fvhd_llm_set_weight_format: FVHD_W_E4M3 needs hidden, n_heads * head_dim and intermediate to be multiples of 128");
+    DevGuard g(c->device);
+    if (g.err != hipSuccess) return lhip("hipSetDevice", g.err);
+    if (c->wdev) (void)hipFree(c->wdev);
+    if (c->wscratch) (void)hipFree(c->wscratch);
+    c->wdev = c->wscratch = nullptr;
+    c->wscratch_bytes = 0;
+    c->wfmt = format;
+    weight_layout(c);
+    hipError_t e = hipMalloc((void**)&c->wdev, c->wbytes);
+    if (e != hipSuccess) return lhip("hipMalloc(llm weights)", e);
+    if (format == FVHD_W_E4M3) {
+        const size_t H = c->H, big = std::max(std::max((size_t)c->qkvw, (size_t)2 * c->I), (size_t)c->V) * H;
+        c->wscratch_bytes = std::max(big, H * std::max((size_t)c->I, (size_t)c->nh * c->hd)) * 2;
+        if ((e = hipMalloc((void**)&c->wscratch, c->wscratch_bytes)) != hipSuccess) return lhip("hipMalloc(dequantisation scratch)", e);
+    }
+    return 0;
+}
+
+int fvhd_llm_weight_bytes(const fvhd_llm* c, size_t* bytes)
+{
+    if (!c || !bytes) return lfail("fvhd_llm_weight_bytes: NULL argument");
+    *bytes = c->wbytes;
+    return 0;
 }
 
 int fvhd_llm_set_tensor(fvhd_llm* c, const char* key, const void* host_data, int dtype, const int64_t* shape, int ndim)
@@ -340,42 +450,28 @@ int fvhd_llm_set_tensor(fvhd_llm* c, const char* key, const void* host_data, int
         DevGuard g(c->device);
         if (g.err != hipSuccess) return lhip("hipSetDevice", g.err);
         int e = ensure_emb(c);
-        return e ? e : upload_matrix(host_data, dtype, c->V, c->H, c->emb, c->H);
+        if (!e) e = upload_matrix(host_data, dtype, c->V, c->H, c->emb, c->H);
+        if (!e) c->any_set = true;
+        return e;
     }
     int layer = -1, which = -1;
     const int idx = tensor_index(c, key, &layer, &which);
     if (idx < 0) return lfail(std::string("fvhd_llm_set_tensor: not a tensor of the Qwen2 decoder stack: ") + key);
-    const int H = c->H, hd = c->hd, nh = c->nh, nkv = c->nkv, I = c->I;
-    auto want = [&](int64_t r, int64_t cc) -> bool { return cc < 0 ? (ndim == 1 && shape[0] == r) : (ndim == 2 && shape[0] == r && shape[1] == cc); };
+    const Slot sl = slot_of(c, layer, which);
+    const bool vec = sl.cols == 0;
+    const bool ok = vec ? (ndim == 1 && (size_t)shape[0] == sl.rows) : (ndim == 2 && (size_t)shape[0] == sl.rows && (size_t)shape[1] == sl.cols);
     DevGuard g(c->device);
     if (g.err != hipSuccess) return lhip("hipSetDevice", g.err);
     int e = 0;
-    bool ok = true;
-    if (layer < 0) {
-        if (which == 0) { ok = want(H, -1); if (ok) e = upload_vector_f32(host_data, dtype, H, c->wdev + c->norm_off); }
-        else { ok = want(c->V, H); if (ok) e = upload_matrix(host_data, dtype, c->V, H, c->wdev + c->lm_off, H); }
-    } else {
-        const LayerOff& o = c->lo[layer];
-        char* w = c->wdev;
-        switch (which) {
-        case 0: ok = want(H, -1); if (ok) e = upload_vector_f32(host_data, dtype, H, w + o.ln1); break;
-        case 1: ok = want((int64_t)nh * hd, H); if (ok) e = upload_matrix(host_data, dtype, (size_t)nh * hd, H, w + o.wqkv, H); break;
-        case 2: ok = want((int64_t)nh * hd, -1); if (ok) e = upload_vector_f32(host_data, dtype, (size_t)nh * hd, w + o.bqkv); break;
-        case 3: ok = want((int64_t)nkv * hd, H); if (ok) e = upload_matrix(host_data, dtype, (size_t)nkv * hd, H, w + o.wqkv + (size_t)nh * hd * H * 2, H); break;
-        case 4: ok = want((int64_t)nkv * hd, -1); if (ok) e = upload_vector_f32(host_data, dtype, (size_t)nkv * hd, w + o.bqkv + (size_t)nh * hd * 4); break;
-        case 5: ok = want((int64_t)nkv * hd, H); if (ok) e = upload_matrix(host_data, dtype, (size_t)nkv * hd, H, w + o.wqkv + (size_t)(nh + nkv) * hd * H * 2, H); break;
-        case 6: ok = want((int64_t)nkv * hd, -1); if (ok) e = upload_vector_f32(host_data, dtype, (size_t)nkv * hd, w + o.bqkv + (size_t)(nh + nkv) * hd * 4); break;
-        case 7: ok = want(H, (int64_t)nh * hd); if (ok) e = upload_matrix(host_data, dtype, H, (size_t)nh * hd, w + o.wo, (size_t)nh * hd); break;
-        case 8: ok = want(H, -1); if (ok) e = upload_vector_f32(host_data, dtype, H, w + o.ln2); break;
-        // gate / up rows interleaved (row 2j = gate_j, row 2j + 1 = up_j): the SwiGLU epilogue of the GEMM pairs adjacent columns
-        case 9: ok = want(I, H); if (ok) e = upload_matrix(host_data, dtype, I, H, w + o.wgu, (size_t)2 * H); break;
-        case 10: ok = want(I, H); if (ok) e = upload_matrix(host_data, dtype, I, H, w + o.wgu + (size_t)H * 2, (size_t)2 * H); break;
-        case 11: ok = want(H, I); if (ok) e = upload_matrix(host_data, dtype, H, I, w + o.wd, I); break;
-        }
+    if (ok) {
+        if (vec) e = upload_vector_f32(host_data, dtype, sl.rows, c->wdev + sl.base + sl.eoff * 4);
+        else if (c->wfmt == FVHD_W_E4M3) e = upload_matrix_q(c, host_data, dtype, sl);
+        else e = upload_matrix(host_data, dtype, sl.rows, sl.cols, c->wdev + sl.base + sl.eoff * 2, sl.pitch);
     }
     if (!ok) return lfail(std::string("fvhd_llm_set_tensor: bad shape for ") + key);
     if (e) return e;
     c->got[idx] = 1;
+    c->any_set = true;
     return 0;
 }
 
@@ -395,34 +491,15 @@ int fvhd_llm_set_tensor_device(fvhd_llm* c, const char* key, const void* dev_dat
         const hipError_t he = hipMemcpyAsync(c->emb, dev_data, (size_t)c->V * c->H * 2, hipMemcpyDeviceToDevice, (hipStream_t)stream);
         if (he != hipSuccess) return lhip("hipMemcpyAsync(embed_tokens)", he);
         const hipError_t se = hipStreamSynchronize((hipStream_t)stream);     // an optional tensor: no event bookkeeping, the copy is done here
-        return se == hipSuccess ? 0 : lhip("hipStreamSynchronize(embed_tokens)", se);
+        if (se != hipSuccess) return lhip("hipStreamSynchronize(embed_tokens)", se);
+        c->any_set = true;
+        return 0;
     }
     int layer = -1, which = -1;
     const int idx = tensor_index(c, key, &layer, &which);
     if (idx < 0) return lfail(std::string("fvhd_llm_set_tensor_device: not a tensor of the Qwen2 decoder stack: ") + key);
-    const size_t H = c->H, hd = c->hd, nh = c->nh, nkv = c->nkv, I = c->I;
-    // destination (offset, rows, cols, row pitch in elements) of every slot; vectors: cols = 0
-    size_t off = 0, rows = 0, cols = 0, pitch = 0;
-    if (layer < 0) {
-        if (which == 0) { off = c->norm_off; rows = H; }
-        else { off = c->lm_off; rows = c->V; cols = H; pitch = H; }
-    } else {
-        const LayerOff& o = c->lo[layer];
-        switch (which) {
-        case 0: off = o.ln1; rows = H; break;
-        case 1: off = o.wqkv; rows = nh * hd; cols = H; pitch = H; break;
-        case 2: off = o.bqkv; rows = nh * hd; break;
-        case 3: off = o.wqkv + nh * hd * H * 2; rows = nkv * hd; cols = H; pitch = H; break;
-        case 4: off = o.bqkv + nh * hd * 4; rows = nkv * hd; break;
-        case 5: off = o.wqkv + (nh + nkv) * hd * H * 2; rows = nkv * hd; cols = H; pitch = H; break;
-        case 6: off = o.bqkv + (nh + nkv) * hd * 4; rows = nkv * hd; break;
-        case 7: off = o.wo; rows = H; cols = nh * hd; pitch = nh * hd; break;
-        case 8: off = o.ln2; rows = H; break;
-        case 9: off = o.wgu; rows = I; cols = H; pitch = 2 * H; break;              // gate rows at even, up rows at odd positions
-        case 10: off = o.wgu + H * 2; rows = I; cols = H; pitch = 2 * H; break;
-        case 11: off = o.wd; rows = H; cols = I; pitch = I; break;
-        }
-    }
+    const Slot sl = slot_of(c, layer, which);
+    const size_t rows = sl.rows, cols = sl.cols;
     const bool vec = cols == 0;
     if (vec ? !(ndim == 1 && (size_t)shape[0] == rows) : !(ndim == 2 && (size_t)shape[0] == rows && (size_t)shape[1] == cols))
         return lfail(std::string("fvhd_llm_set_tensor_device: bad shape for ") + key);
@@ -430,8 +507,12 @@ int fvhd_llm_set_tensor_device(fvhd_llm* c, const char* key, const void* dev_dat
         return lfail(std::string("fvhd_llm_set_tensor_device: matrices must be bf16 and vectors fp32 on the device (") + key + ")");
     DevGuard g(c->device);
     if (g.err != hipSuccess) return lhip("hipSetDevice", g.err);
-    hipError_t e = vec ? hipMemcpyAsync(c->wdev + off, dev_data, rows * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream)
-                       : hipMemcpy2DAsync(c->wdev + off, pitch * 2, dev_data, cols * 2, cols * 2, rows, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    hipError_t e = hipSuccess;
+    if (vec) e = hipMemcpyAsync(c->wdev + sl.base + sl.eoff * 4, dev_data, rows * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    else if (c->wfmt == FVHD_W_E4M3) {                          // quantised on `stream` straight from the caller's tensor
+        if (int qe = quantize_into(c, sl, dev_data, (hipStream_t)stream)) return qe;
+    } else
+        e = hipMemcpy2DAsync(c->wdev + sl.base + sl.eoff * 2, sl.pitch * 2, dev_data, cols * 2, cols * 2, rows, hipMemcpyDeviceToDevice, (hipStream_t)stream);
     if (e != hipSuccess) return lhip("hipMemcpyAsync(llm weights, device to device)", e);
     // order later work after this copy (advisor, round 4: a prefill on ANOTHER stream could read half-packed weights)
     if (!c->load_ev && (e = hipEventCreateWithFlags(&c->load_ev, hipEventDisableTiming)) != hipSuccess) return lhip("hipEventCreate", e);
@@ -440,6 +521,7 @@ int fvhd_llm_set_tensor_device(fvhd_llm* c, const char* key, const void* dev_dat
     c->load_stream = (hipStream_t)stream;
     c->load_pending = true;
     c->got[idx] = 1;
+    c->any_set = true;
     return 0;
 }
 
@@ -549,49 +631,62 @@ int fvhd_llm_prefill(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* 
     const int down_sp = pick_splits(H, I, c->down_splits), o_sp = pick_splits(H, nh * hd, c->o_splits);
     // q|k|v projection: split in two, the reduce applies bias + rotary embedding + the KV-cache copies (splitk_bias_rope_kernel)
     const int qkv_sp = pick_splits(c->qkvw, H, std::min(c->qkv_splits, 2));
+    // the matrix a GEMM reads: the packed bf16 weights, or - e4m3 - the bf16 scratch the codes are dequantised into right before it
+    // (1 byte in, 2 bytes out per element; the GEMMs run one after the other on `st`, so one scratch of the largest matrix serves them all)
+    auto weights = [&](size_t off, size_t soff, long N, int K, const void** p) -> int {
+        if (c->wfmt != FVHD_W_E4M3) { *p = w + off; return 0; }
+        *p = c->wscratch;
+        return fvhd_launch_w8_unpack(st, w + off, (const float*)(w + soff), c->wscratch, N, K, 0);
+    };
+    const void *wqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wd = nullptr, *wlm = nullptr;
     bool xn_ready = false;                      // c->xn already holds input_layernorm(c->h) of the coming layer
     for (int l = 0; l < c->L; ++l) {
         const LayerOff& o = c->lo[l];
         if (!xn_ready) LCHECK(fvhd_launch_rmsnorm(st, c->h, c->xn, (const float*)(w + o.ln1), Mp, H, c->eps), "rmsnorm 1");
         void* kc = k_cache ? (char*)k_cache + l * cache_layer : nullptr;
         void* vc = v_cache ? (char*)v_cache + l * cache_layer : nullptr;
+        LCHECK(weights(o.wqkv, o.sqkv, c->qkvw, H, &wqkv), "dequantise q|k|v");
         if (qkv_sp > 1) {
-            LCHECK(fvhd_launch_gemm_splitk_partials(st, c->xn, w + o.wqkv, c->part, Mp, c->qkvw, H, qkv_sp), "qkv gemm (split-K)");
+            LCHECK(fvhd_launch_gemm_splitk_partials(st, c->xn, wqkv, c->part, Mp, c->qkvw, H, qkv_sp), "qkv gemm (split-K)");
             LCHECK(fvhd_launch_splitk_bias_rope(st, c->part, qkv_sp, Mp, (const float*)(w + o.bqkv), c->qkv, (const long*)position_ids, c->rope, kc, vc,
                                                 M, T, nh, nkv, hd, c->ws_pos, c->theta), "qkv reduce + bias + rope");
         } else if (c->fuse_rope && fvhd_gemm_qkv_rope_supported(Mp, c->qkvw, H, hd, nh, nkv)) {
             // round 5: bias + rotary embedding + the KV-cache copies in the projection's own epilogue (head_dim 64; bit-identical to the two launches)
-            LCHECK(fvhd_launch_gemm_qkv_rope(st, c->xn, w + o.wqkv, (const float*)(w + o.bqkv), c->qkv, Mp, c->qkvw, H, (const long*)position_ids, c->rope, kc, vc,
+            LCHECK(fvhd_launch_gemm_qkv_rope(st, c->xn, wqkv, (const float*)(w + o.bqkv), c->qkv, Mp, c->qkvw, H, (const long*)position_ids, c->rope, kc, vc,
                                              M, T, nh, nkv, hd, c->ws_pos, c->theta), "qkv gemm + rope");
         } else {
-            LCHECK(fvhd_launch_gemm(st, c->xn, w + o.wqkv, (const float*)(w + o.bqkv), nullptr, nullptr, c->qkv, Mp, c->qkvw, H, EPI_BIAS, FVHD_BF16), "qkv gemm");
+            LCHECK(fvhd_launch_gemm(st, c->xn, wqkv, (const float*)(w + o.bqkv), nullptr, nullptr, c->qkv, Mp, c->qkvw, H, EPI_BIAS, FVHD_BF16), "qkv gemm");
             LCHECK(fvhd_launch_rope(st, c->qkv, (const long*)position_ids, c->rope, kc, vc, M, T, nh, nkv, hd, c->ws_pos, c->theta), "rope");
         }
         LCHECK(fvhd_launch_llm_attention(st, c->qkv, c->att, key_valid, B, T, nh, nkv, hd), "attention");
+        LCHECK(weights(o.wo, o.so, H, nh * hd, &wo), "dequantise o_proj");
         if (o_sp > 1 && c->fuse_norm) {
-            LCHECK(fvhd_launch_gemm_splitk_norm(st, c->att, w + o.wo, c->h, c->h, c->part, Mp, H, nh * hd, o_sp, (const float*)(w + o.ln2), c->xn, c->eps),
+            LCHECK(fvhd_launch_gemm_splitk_norm(st, c->att, wo, c->h, c->h, c->part, Mp, H, nh * hd, o_sp, (const float*)(w + o.ln2), c->xn, c->eps),
                    "o_proj gemm (split-K + rmsnorm 2)");
         } else {
-            if (o_sp > 1) LCHECK(fvhd_launch_gemm_splitk(st, c->att, w + o.wo, c->h, c->h, c->part, Mp, H, nh * hd, o_sp), "o_proj gemm (split-K)");
-            else LCHECK(fvhd_launch_gemm(st, c->att, w + o.wo, nullptr, nullptr, c->h, c->h, Mp, H, nh * hd, EPI_RESID, FVHD_BF16), "o_proj gemm");
+            if (o_sp > 1) LCHECK(fvhd_launch_gemm_splitk(st, c->att, wo, c->h, c->h, c->part, Mp, H, nh * hd, o_sp), "o_proj gemm (split-K)");
+            else LCHECK(fvhd_launch_gemm(st, c->att, wo, nullptr, nullptr, c->h, c->h, Mp, H, nh * hd, EPI_RESID, FVHD_BF16), "o_proj gemm");
             LCHECK(fvhd_launch_rmsnorm(st, c->h, c->xn, (const float*)(w + o.ln2), Mp, H, c->eps), "rmsnorm 2");
         }
-        LCHECK(fvhd_launch_gemm(st, c->xn, w + o.wgu, nullptr, nullptr, nullptr, c->act, Mp, 2 * I, H, EPI_SWIGLU, FVHD_BF16), "gate_up gemm");
+        LCHECK(weights(o.wgu, o.sgu, 2 * (long)I, H, &wgu), "dequantise gate|up");
+        LCHECK(fvhd_launch_gemm(st, c->xn, wgu, nullptr, nullptr, nullptr, c->act, Mp, 2 * I, H, EPI_SWIGLU, FVHD_BF16), "gate_up gemm");
         xn_ready = false;
+        LCHECK(weights(o.wd, o.sd, H, I, &wd), "dequantise down_proj");
         if (down_sp > 1 && c->fuse_norm && l + 1 < c->L) {
-            LCHECK(fvhd_launch_gemm_splitk_norm(st, c->act, w + o.wd, c->h, c->h, c->part, Mp, H, I, down_sp, (const float*)(w + c->lo[l + 1].ln1), c->xn, c->eps),
+            LCHECK(fvhd_launch_gemm_splitk_norm(st, c->act, wd, c->h, c->h, c->part, Mp, H, I, down_sp, (const float*)(w + c->lo[l + 1].ln1), c->xn, c->eps),
                    "down gemm (split-K + rmsnorm 1 of the next layer)");
             xn_ready = true;
         } else if (down_sp > 1) {
-            LCHECK(fvhd_launch_gemm_splitk(st, c->act, w + o.wd, c->h, c->h, c->part, Mp, H, I, down_sp), "down gemm (split-K)");
+            LCHECK(fvhd_launch_gemm_splitk(st, c->act, wd, c->h, c->h, c->part, Mp, H, I, down_sp), "down gemm (split-K)");
         } else {
-            LCHECK(fvhd_launch_gemm(st, c->act, w + o.wd, nullptr, nullptr, c->h, c->h, Mp, H, I, EPI_RESID, FVHD_BF16), "down gemm");
+            LCHECK(fvhd_launch_gemm(st, c->act, wd, nullptr, nullptr, c->h, c->h, Mp, H, I, EPI_RESID, FVHD_BF16), "down gemm");
         }
     }
     // logits of the LAST position of every sequence (what generate() reads: outputs.logits[:, -1, :])
     LCHECK(fvhd_launch_gather_rows(st, c->h, c->last, B, T, T - 1, H), "gather last rows");
     LCHECK(fvhd_launch_rmsnorm(st, c->last, c->lastn, (const float*)(w + c->norm_off), B, H, c->eps), "final norm");
-    LCHECK(fvhd_launch_gemm(st, c->lastn, w + c->lm_off, nullptr, nullptr, nullptr, logits_out, B, c->V, H, EPI_NONE, FVHD_F32), "lm_head gemm");
+    LCHECK(weights(c->lm_off, c->lm_soff, c->V, H, &wlm), "dequantise lm_head");
+    LCHECK(fvhd_launch_gemm(st, c->lastn, wlm, nullptr, nullptr, nullptr, logits_out, B, c->V, H, EPI_NONE, FVHD_F32), "lm_head gemm");
     return 0;
 }
 
@@ -602,6 +697,33 @@ int fvhd_llm_debug_hidden(fvhd_llm* c, void* out, int rows, fvhd_stream_t stream
     DevGuard g(c->device);
     hipError_t e = hipMemcpyAsync(out, c->h, (size_t)rows * c->H * 2, hipMemcpyDeviceToDevice, (hipStream_t)stream);
     return e == hipSuccess ? 0 : lhip("hipMemcpyAsync", e);
+}
+
+// one packed matrix of an e4m3 context in plain [N, K] order (the packing test): codes u8 [N][K], scales fp32 [N], device pointers
+int fvhd_llm_debug_packed_e4m3(fvhd_llm* c, int layer, int matrix, void* codes_out, float* scale_out, fvhd_stream_t stream)
+{
+    if (!c || !codes_out || !scale_out) return lfail("fvhd_llm_debug_packed_e4m3: NULL argument");
+    if (c->wfmt != FVHD_W_E4M3) return lfail("fvhd_llm_debug_packed_e4m3: the context holds bf16 weights (fvhd_llm_set_weight_format)");
+    if (matrix < FVHD_MAT_QKV || matrix > FVHD_MAT_LM_HEAD || (matrix != FVHD_MAT_LM_HEAD && (layer < 0 || layer >= c->L)))
+        return lfail("fvhd_llm_debug_packed_e4m3: matrix must be FVHD_MAT_QKV .. FVHD_MAT_LM_HEAD and layer in [0, n_layers)");
+    size_t off = c->lm_off, soff = c->lm_soff;
+    long N = c->V;
+    int K = c->H;
+    if (matrix != FVHD_MAT_LM_HEAD) {
+        const LayerOff& o = c->lo[layer];
+        switch (matrix) {
+        case FVHD_MAT_QKV: off = o.wqkv; soff = o.sqkv; N = c->qkvw; break;
+        case FVHD_MAT_O: off = o.wo; soff = o.so; N = c->H; K = c->nh * c->hd; break;
+        case FVHD_MAT_GATE_UP: off = o.wgu; soff = o.sgu; N = 2 * (long)c->I; break;
+        default: off = o.wd; soff = o.sd; N = c->H; K = c->I; break;
+        }
+    }
+    DevGuard g(c->device);
+    if (g.err != hipSuccess) return lhip("hipSetDevice", g.err);
+    if (int e = wait_for_loads(c)) return e;
+    LCHECK(fvhd_launch_w8_unpack((hipStream_t)stream, c->wdev + off, nullptr, codes_out, N, K, 1), "fvhd_llm_debug_packed_e4m3");
+    const hipError_t he = hipMemcpyAsync(scale_out, c->wdev + soff, (size_t)N * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    return he == hipSuccess ? 0 : lhip("hipMemcpyAsync", he);
 }
 
 // ---- decode: the library's own KV cache, one token per sequence per step (include/fvhd.h "LLM decode") ----
@@ -813,34 +935,41 @@ int fvhd_llm_decode(fvhd_llm* c, const int64_t* token_ids, float* logits_out, in
     hipStream_t st = (hipStream_t)stream;
     const int B = c->run_batch, H = c->H, I = c->I, nh = c->nh, nkv = c->nkv, hd = c->hd, cap = c->dc_cap;
     const char* w = c->wdev;
-    LCHECK(fvhd_launch_dec_embed(st, token_ids, c->last_ids, c->emb ? c->emb : w + c->lm_off, c->V, H, c->dh, c->mask, B, cap, c->len, c->status,
-                                 c->status_host_dev), "decode embed");
+    const bool q8 = c->wfmt == FVHD_W_E4M3;
+    if (q8 && !c->emb) {                                         // a tied model: the token row dequantised from the lm_head codes
+        LCHECK(fvhd_launch_dec_embed_w8(st, token_ids, c->last_ids, w + c->lm_off, (const float*)(w + c->lm_soff), c->V, H, c->dh, c->mask, B, cap, c->len,
+                                        c->status, c->status_host_dev), "decode embed (e4m3 lm_head rows)");
+    } else {
+        LCHECK(fvhd_launch_dec_embed(st, token_ids, c->last_ids, c->emb ? c->emb : w + c->lm_off, c->V, H, c->dh, c->mask, B, cap, c->len, c->status,
+                                     c->status_host_dev), "decode embed");
+    }
     const size_t layer_kv = (size_t)c->dc_batch * nkv * cap * hd * 2;
-    auto gemm = [&](int epi, const void* x, int K, const float* norm_w, const void* W, int N, const fvhd_llm::Plan& p) {
+    auto gemm = [&](int epi, const void* x, int K, const float* norm_w, const void* W, size_t soff, int N, const fvhd_llm::Plan& p) {
         DecGemmArgs a;
+        a.wscale = q8 ? (const float*)(w + soff) : nullptr;
         a.x = x; a.ldx = K; a.norm_w = norm_w; a.eps = c->eps; a.W = W; a.N = N; a.K = K; a.B = B; a.S = p.S; a.cpw = p.cpw;
         a.part = c->dpart; a.cnt = c->cnt; a.epi = epi; a.status = c->status; a.rstd = c->dec_rstd_once ? c->drstd : nullptr;
         return a;
     };
     for (int l = 0; l < c->L; ++l) {
         const LayerOff& o = c->lo[l];
-        DecGemmArgs a = gemm(DEC_EPI_QKV, c->dh, H, (const float*)(w + o.ln1), w + o.wqkv, c->qkvw, c->p_qkv);
+        DecGemmArgs a = gemm(DEC_EPI_QKV, c->dh, H, (const float*)(w + o.ln1), w + o.wqkv, o.sqkv, c->qkvw, c->p_qkv);
         a.bias = (const float*)(w + o.bqkv); a.out = c->dq; a.ldo = nh * hd; a.pos = c->posv; a.rope = c->drope; a.P = c->dc_pos; a.theta = c->theta;
         a.nh = nh; a.nkv = nkv; a.hd = hd; a.kc = c->kcache + l * layer_kv; a.vc = c->vcache + l * layer_kv; a.cap = cap; a.len = c->len;
         LCHECK(fvhd_launch_dec_gemm(st, &a), "decode q|k|v + rope + cache append");
         LCHECK(fvhd_launch_dec_attention(st, c->dq, c->kcache + l * layer_kv, c->vcache + l * layer_kv, c->mask, c->datt, B, nh, nkv, hd, cap, c->len, 1,
                                          c->att_S, c->att_chunk, c->apart, c->cnt + c->cnt_att, c->status), "decode attention");
-        a = gemm(DEC_EPI_RESID, c->datt, nh * hd, nullptr, w + o.wo, H, c->p_o);
+        a = gemm(DEC_EPI_RESID, c->datt, nh * hd, nullptr, w + o.wo, o.so, H, c->p_o);
         a.resid = c->dh; a.out = c->dh; a.ldo = H;
         LCHECK(fvhd_launch_dec_gemm(st, &a), "decode o_proj + residual");
-        a = gemm(DEC_EPI_SWIGLU, c->dh, H, (const float*)(w + o.ln2), w + o.wgu, 2 * I, c->p_gu);
+        a = gemm(DEC_EPI_SWIGLU, c->dh, H, (const float*)(w + o.ln2), w + o.wgu, o.sgu, 2 * I, c->p_gu);
         a.out = c->dact; a.ldo = I;
         LCHECK(fvhd_launch_dec_gemm(st, &a), "decode rmsnorm + gate|up + silu");
-        a = gemm(DEC_EPI_RESID, c->dact, I, nullptr, w + o.wd, H, c->p_d);
+        a = gemm(DEC_EPI_RESID, c->dact, I, nullptr, w + o.wd, o.sd, H, c->p_d);
         a.resid = c->dh; a.out = c->dh; a.ldo = H;
         LCHECK(fvhd_launch_dec_gemm(st, &a), "decode down_proj + residual");
     }
-    DecGemmArgs a = gemm(DEC_EPI_ARGMAX, c->dh, H, (const float*)(w + c->norm_off), w + c->lm_off, c->V, c->p_lm);
+    DecGemmArgs a = gemm(DEC_EPI_ARGMAX, c->dh, H, (const float*)(w + c->norm_off), w + c->lm_off, c->lm_soff, c->V, c->p_lm);
     a.logits = logits_out; a.amax_v = c->amax_v; a.amax_i = c->amax_i;
     if (c->do_sample) {
         // sampling replaces the argmax reduce: it reads the logits (the caller's, else the context's buffer), chooses with n = length + 1
@@ -1017,6 +1146,89 @@ int fvhd_op_dec_lm_argmax(fvhd_stream_t st, const void* x, int B, const float* n
     int e = fvhd_launch_dec_gemm((hipStream_t)st, &a);
     if (!e) e = fvhd_launch_dec_argmax_finish((hipStream_t)st, scratch_v, scratch_i, (V / 16 + 3) / 4, B, nullptr, ids_out, nullptr, nullptr, nullptr);
     return e ? lhip("fvhd_op_dec_lm_argmax", (hipError_t)e) : 0;
+}
+
+// ---- the same single ops on e4m3 weights: Wt = plain row-major codes u8 [N][K], scale fp32 [N] ----
+// The kernels read the packed K order (llm_w8.hip): the codes are repacked into a process-wide scratch first, grown on demand - eager
+// calls only, like fvhd_op_dec_sample's workspace.
+static int w8_op_repack(hipStream_t st, const char* who, const void* Wt, long N, int K, const void** packed)
+{
+    static char* buf[64] = {};
+    static size_t cap[64] = {};
+    int dev = 0;
+    hipError_t he = hipGetDevice(&dev);
+    if (he != hipSuccess) return lhip("hipGetDevice", he);
+    if (dev < 0 || dev >= 64) return lfail(std::string(who) + ": device index out of range");
+    const size_t need = (size_t)N * K;
+    if (need > cap[dev]) {
+        if (buf[dev]) (void)hipFree(buf[dev]);                  // (synchronises: no earlier launch still reads it)
+        buf[dev] = nullptr;
+        cap[dev] = 0;
+        if ((he = hipMalloc((void**)&buf[dev], need)) != hipSuccess) { buf[dev] = nullptr; return lhip("hipMalloc(e4m3 repack scratch)", he); }
+        cap[dev] = need;
+    }
+    const int e = fvhd_launch_w8_unpack(st, Wt, nullptr, buf[dev], N, K, 2);
+    if (e) return lhip(who, (hipError_t)e);
+    *packed = buf[dev];
+    return 0;
+}
+
+int fvhd_op_quantize_e4m3(fvhd_stream_t st, const void* W, int N, int K, void* codes, float* scale)
+{
+    if (!W || !codes || !scale) return lfail("fvhd_op_quantize_e4m3: NULL pointer");
+    if (N < 1 || K < 8 || K % 8) return lfail("fvhd_op_quantize_e4m3: needs N >= 1, K >= 8 and K % 8 == 0");
+    int e = fvhd_launch_quantize_e4m3((hipStream_t)st, W, N, K, codes, K, scale, 1, 0);
+    return e ? lhip("fvhd_op_quantize_e4m3", (hipError_t)e) : 0;
+}
+
+int fvhd_op_dec_gemm_w8(fvhd_stream_t st, int epi, const void* x, int B, const float* norm_w, float eps, const void* Wt, const float* scale, int N, int K,
+                        const void* resid, void* out, float* partial, int* counters, int splits)
+{
+    if (!x || !Wt || !scale || !out || (epi == FVHD_EPI_RESID && !resid)) return lfail("fvhd_op_dec_gemm_w8: NULL pointer");
+    if (epi != FVHD_EPI_RESID && epi != FVHD_EPI_SWIGLU) return lfail("fvhd_op_dec_gemm_w8: epi must be FVHD_EPI_RESID or FVHD_EPI_SWIGLU");
+    if (B < 1 || B > 64 || N < 16 || N % 16 || K < 128 || K % 128 || splits < 1 || (splits > 1 && (!partial || !counters)))
+        return lfail("fvhd_op_dec_gemm_w8: needs 1 <= B <= 64, N % 16 == 0, K % 128 == 0, splits >= 1 (and scratch when splits > 1)");
+    DecGemmArgs a;
+    if (int e = w8_op_repack((hipStream_t)st, "fvhd_op_dec_gemm_w8", Wt, N, K, &a.W)) return e;
+    a.x = x; a.ldx = K; a.norm_w = norm_w; a.eps = eps; a.wscale = scale; a.N = N; a.K = K; a.B = B; a.part = partial; a.cnt = counters;
+    a.epi = epi; a.resid = resid; a.out = out; a.ldo = epi == FVHD_EPI_SWIGLU ? N / 2 : N;
+    dec_split(a, splits);
+    int e = fvhd_launch_dec_gemm((hipStream_t)st, &a);
+    return e ? lhip("fvhd_op_dec_gemm_w8", (hipError_t)e) : 0;
+}
+
+int fvhd_op_dec_qkv_w8(fvhd_stream_t st, const void* x, int B, int K, const float* norm_w, float eps, const void* Wt, const float* scale, const float* bias,
+                       void* q_out, const int64_t* pos, const float* table, int table_positions, float rope_theta, void* k_cache, void* v_cache, int capacity,
+                       const int* length, int n_heads, int n_kv_heads, int head_dim, float* partial, int* counters, int splits)
+{
+    if (!x || !Wt || !scale || !bias || !q_out || !pos || !table || !k_cache || !v_cache || !length) return lfail("fvhd_op_dec_qkv_w8: NULL pointer");
+    if (B < 1 || B > 64 || K < 128 || K % 128 || splits < 1 || head_dim < 16 || head_dim % 16 || n_heads < 1 || n_kv_heads < 1 || capacity < 1 ||
+        table_positions < 1 || (splits > 1 && (!partial || !counters)))
+        return lfail("fvhd_op_dec_qkv_w8: needs 1 <= B <= 64, K % 128 == 0, head_dim % 16 == 0, splits >= 1 (and scratch when splits > 1)");
+    DecGemmArgs a;
+    a.N = (n_heads + 2 * n_kv_heads) * head_dim;
+    if (int e = w8_op_repack((hipStream_t)st, "fvhd_op_dec_qkv_w8", Wt, a.N, K, &a.W)) return e;
+    a.x = x; a.ldx = K; a.norm_w = norm_w; a.eps = eps; a.wscale = scale; a.K = K; a.B = B;
+    a.part = partial; a.cnt = counters; a.epi = DEC_EPI_QKV; a.bias = bias; a.out = q_out; a.ldo = n_heads * head_dim; a.pos = pos; a.rope = table;
+    a.P = table_positions; a.theta = rope_theta; a.nh = n_heads; a.nkv = n_kv_heads; a.hd = head_dim; a.kc = k_cache; a.vc = v_cache; a.cap = capacity;
+    a.len = length;
+    dec_split(a, splits);
+    int e = fvhd_launch_dec_gemm((hipStream_t)st, &a);
+    return e ? lhip("fvhd_op_dec_qkv_w8", (hipError_t)e) : 0;
+}
+
+int fvhd_op_dec_lm_argmax_w8(fvhd_stream_t st, const void* x, int B, const float* norm_w, float eps, const void* Wt, const float* scale, int V, int K,
+                             float* logits, int64_t* ids_out, float* scratch_v, int* scratch_i)
+{
+    if (!x || !Wt || !scale || !ids_out || !scratch_v || !scratch_i) return lfail("fvhd_op_dec_lm_argmax_w8: NULL pointer");
+    if (B < 1 || B > 64 || V < 16 || V % 16 || K < 128 || K % 128) return lfail("fvhd_op_dec_lm_argmax_w8: needs 1 <= B <= 64, V % 16 == 0, K % 128 == 0");
+    DecGemmArgs a;
+    if (int e = w8_op_repack((hipStream_t)st, "fvhd_op_dec_lm_argmax_w8", Wt, V, K, &a.W)) return e;
+    a.x = x; a.ldx = K; a.norm_w = norm_w; a.eps = eps; a.wscale = scale; a.N = V; a.K = K; a.B = B; a.S = 1; a.cpw = K / 128; a.epi = DEC_EPI_ARGMAX;
+    a.logits = logits; a.amax_v = scratch_v; a.amax_i = scratch_i;
+    int e = fvhd_launch_dec_gemm((hipStream_t)st, &a);
+    if (!e) e = fvhd_launch_dec_argmax_finish((hipStream_t)st, scratch_v, scratch_i, (V / 16 + 3) / 4, B, nullptr, ids_out, nullptr, nullptr, nullptr);
+    return e ? lhip("fvhd_op_dec_lm_argmax_w8", (hipError_t)e) : 0;
 }
 
 // the sampler on its own: a process-wide workspace, allocated (and its counters zeroed) on first use - eager calls only

@@ -37,6 +37,8 @@ struct DecGemmArgs {
     const int* status = nullptr;   // non-NULL: the launch does nothing while *status != 0 (a step past the cache's capacity)
     float* rstd = nullptr;         // B > 16 with norm_w: scratch [B]; the row statistics are computed once, by a launch of their own, instead of
                                    // in every workgroup (NULL: every workgroup recomputes them, as at B <= 16; the bits are the same)
+    const float* wscale = nullptr; // non-NULL: W holds OCP e4m3 codes [N][K], one byte each, in the packed K order of llm_w8.hip, and row n
+                                   // stands for code * wscale[n] (fp32 [N]); the launch goes to dec_gemm_w8_kernel
 };
 
 // Arguments of the sampler (llm_sample.hip): temperature / top-k / top-p over fp32 logits [B][V], one draw per row.

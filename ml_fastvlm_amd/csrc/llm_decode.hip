@@ -622,6 +622,8 @@ static void launch_dec_gemm(hipStream_t st, const dim3 grid, const DecGemmArgs& 
     }
 }
 
+extern "C" int fvhd_launch_dec_gemm_w8(hipStream_t st, const DecGemmArgs* a);     // llm_w8.hip
+
 extern "C" int fvhd_launch_dec_gemm(hipStream_t st, const DecGemmArgs* a)
 {
     if (a->B < 1 || a->B > 64 || a->N % 16 || a->K % 128 || a->S < 1 || a->cpw < 1 || (long)a->S * a->cpw < a->K / 128 ||
@@ -632,6 +634,7 @@ extern "C" int fvhd_launch_dec_gemm(hipStream_t st, const DecGemmArgs* a)
     if (a->epi == DEC_EPI_ARGMAX && a->S != 1) return (int)hipErrorInvalidValue;
     if (a->norm_w && a->rstd && a->B > 16)
         hipLaunchKernelGGL(dec_rstd_kernel, dim3((a->B + 3) / 4), dim3(256), 0, st, (const bf16*)a->x, a->ldx, a->K, a->B, a->eps, a->rstd, a->status);
+    if (a->wscale) return fvhd_launch_dec_gemm_w8(st, a);         // e4m3 weights: the sibling kernels
     const int ncol = (a->N / 16 + 3) / 4;
     const dim3 grid((unsigned)((long)ncol * a->S));
     switch (a->epi) {

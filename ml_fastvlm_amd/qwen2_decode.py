@@ -83,10 +83,15 @@ class Qwen2Generator:
         self._run_batch = 0
 
     @classmethod
-    def from_hf(cls, model, batch: int, capacity: int, prefill: Optional[Qwen2Prefill] = None) -> "Qwen2Generator":
+    def from_hf(cls, model, batch: int, capacity: int, prefill: Optional[Qwen2Prefill] = None, weights: str = "bf16") -> "Qwen2Generator":
         """model: a `transformers` Qwen2ForCausalLM / the reference's LlavaQwen2ForCausalLM on a HIP device; `prefill` reuses an existing
-        context of that model (e.g. `ml_fastvlm_amd.builder.prefill_context(model)`) instead of packing the weights again."""
-        pre = prefill if prefill is not None else Qwen2Prefill.from_hf(model)
+        context of that model (e.g. `ml_fastvlm_amd.builder.prefill_context(model)`) instead of packing the weights again.
+        weights: "bf16" or "fp8_e4m3" (`Qwen2Prefill.from_hf`); a `prefill` context in the other format is an error, never a silent repack."""
+        _lib.weight_format_code(weights)
+        if prefill is not None and getattr(prefill, "weight_format", "bf16") != weights:
+            raise ValueError(f"Qwen2Generator.from_hf(weights={weights!r}): the prefill context passed holds {prefill.weight_format} weights - "
+                             f"build it with Qwen2Prefill.from_hf(model, weights={weights!r}) or pass the matching `weights`")
+        pre = prefill if prefill is not None else Qwen2Prefill.from_hf(model, weights=weights)
         tied = bool(getattr(model.config, "tie_word_embeddings", False))
         emb = None if tied else model.get_input_embeddings().weight
         return cls(pre, batch, capacity, embed_tokens=emb, tie_word_embeddings=tied)

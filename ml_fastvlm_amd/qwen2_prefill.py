@@ -36,11 +36,17 @@ class Qwen2Prefill:
         self.hidden, self.n_layers, self.n_heads, self.n_kv_heads, self.head_dim = hidden, n_layers, n_heads, n_kv_heads, head_dim
         self.intermediate, self.vocab = intermediate, vocab
         self.tie_word_embeddings = None           # from_hf records the config's flag (the decode's input embedding depends on it)
+        self.weight_format = "bf16"               # set_weight_format: "fp8_e4m3" = the packed matrices as e4m3 codes + one scale per row
+        self._tensors_set = 0
 
     # ---- construction from the reference's module -------------------------------------------------------------------------------
     @classmethod
-    def from_hf(cls, model, device: Optional[torch.device] = None) -> "Qwen2Prefill":
-        """model: a `transformers` Qwen2ForCausalLM (or the reference's LlavaQwen2ForCausalLM, whose decoder stack it is)."""
+    def from_hf(cls, model, device: Optional[torch.device] = None, weights: str = "bf16") -> "Qwen2Prefill":
+        """model: a `transformers` Qwen2ForCausalLM (or the reference's LlavaQwen2ForCausalLM, whose decoder stack it is).
+        weights: "bf16" (the default), or "fp8_e4m3" - every matrix of the decoder stack and lm_head stored as OCP e4m3 codes with one
+        power-of-two scale per output row (`quantize_rows_e4m3`), quantised on the device as it is packed: half the bytes held and half the
+        bytes a decode step streams; activations, the KV cache and the arithmetic (bf16 MFMA, fp32 accumulation) stay what they are."""
+        _lib.weight_format_code(weights)
         cfg = model.config
         dev = torch.device(device) if device is not None else next(model.parameters()).device
         if dev.type != "cuda":
@@ -62,8 +68,41 @@ class Qwen2Prefill:
         if mpe:                                   # rows of the rotary table; positions beyond it are computed in the kernel, never clamped
             _lib.check(_lib.load().fvhd_llm_set_max_positions(self._h, int(mpe)), "fvhd_llm_set_max_positions")
         self.tie_word_embeddings = bool(getattr(cfg, "tie_word_embeddings", False))
+        self.set_weight_format(weights)
         self.load_state_dict(model.state_dict())
         return self
+
+    def set_weight_format(self, weights: str) -> None:
+        """"bf16" or "fp8_e4m3" (`fvhd_llm_set_weight_format`): before the first tensor is set - the matrices are quantised as they arrive"""
+        code = _lib.weight_format_code(weights)
+        if weights == self.weight_format:
+            return
+        if self._tensors_set:
+            raise _lib.FvhdError(f"Qwen2Prefill.set_weight_format({weights!r}): {self._tensors_set} tensors were already set as "
+                                 f"{self.weight_format} - choose the format before the first tensor (from_hf(model, weights=...))")
+        _lib.check(_lib.w8_lib().fvhd_llm_set_weight_format(self._h, code), "fvhd_llm_set_weight_format")
+        self.weight_format = weights
+
+    @property
+    def weight_bytes(self) -> int:
+        """device bytes of the packed weights (matrices, row scales, norm weights, biases)"""
+        n = C.c_size_t(0)
+        _lib.check(_lib.w8_lib().fvhd_llm_weight_bytes(self._h, C.byref(n)), "fvhd_llm_weight_bytes")
+        return int(n.value)
+
+    def packed_e4m3(self, layer: int, matrix: int):
+        """tests: one packed matrix of an "fp8_e4m3" context in plain [N, K] order -> (codes float8_e4m3fn [N, K], scale fp32 [N]);
+        matrix: `_lib.MAT_QKV` (q | k | v rows), `MAT_O`, `MAT_GATE_UP` (gate / up rows interleaved), `MAT_DOWN`, `MAT_LM_HEAD`"""
+        qkvw = (self.n_heads + 2 * self.n_kv_heads) * self.head_dim
+        N, K = {_lib.MAT_QKV: (qkvw, self.hidden), _lib.MAT_O: (self.hidden, self.n_heads * self.head_dim),
+                _lib.MAT_GATE_UP: (2 * self.intermediate, self.hidden), _lib.MAT_DOWN: (self.hidden, self.intermediate),
+                _lib.MAT_LM_HEAD: (self.vocab, self.hidden)}[matrix]
+        codes = torch.empty((N, K), device=self.device, dtype=torch.uint8)
+        scale = torch.empty((N,), device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.w8_lib().fvhd_llm_debug_packed_e4m3(self._h, int(layer), int(matrix), _lib.ptr(codes), _lib.ptr(scale),
+                                                                _lib.stream_ptr(self.device)), "fvhd_llm_debug_packed_e4m3")
+        return codes.view(torch.float8_e4m3fn), scale
 
     def load_state_dict(self, sd) -> None:
         """The decoder-stack tensors of a (Llava)Qwen2ForCausalLM state dict; `lm_head.weight` falls back to the embedding table
@@ -96,6 +135,7 @@ class Qwen2Prefill:
         footprint: the packed copy (q|k|v concatenated, gate / up interleaved, bf16) lives NEXT to the module's own weights, which the
         stock decode loop keeps using - 2x the LLM's weight bytes on the device (0.99 GB / 15.2 GB more for Qwen2-0.5B / 7B)."""
         t = t.detach()
+        self._tensors_set += 1
         shape = (C.c_int64 * max(1, t.dim()))(*t.shape)
         if t.device.type == "cuda" and t.device == self.device:
             want = torch.bfloat16 if t.dim() == 2 else torch.float32
@@ -179,6 +219,28 @@ class Qwen2Prefill:
         out = torch.empty((rows, self.hidden), device=self.device, dtype=torch.bfloat16)
         _lib.check(_lib.load().fvhd_llm_debug_hidden(self._h, _lib.ptr(out), rows, _lib.stream_ptr(self.device)), "fvhd_llm_debug_hidden")
         return out
+
+
+def quantize_rows_e4m3(w: torch.Tensor):
+    """The library's 8-bit weight recipe in plain torch (any device): w [N, K] -> (codes torch.float8_e4m3fn [N, K], scale fp32 [N]), row n
+    standing for codes[n] * scale[n].  scale = 2^ceil(log2(amax_row / 448)), evaluated exactly from amax's exponent and mantissa (amax =
+    m 2^e, m in [0.5, 1): the exponent is e - 9, + 1 when m > 7/8) and kept >= 2^-126; an all-zero row gets scale 1.  codes = w / scale
+    (exact: a power of two) rounded to nearest even by torch's conversion; amax / scale lies in (224, 448], so nothing saturates, and
+    codes * scale is exactly representable in bf16."""
+    if w.dim() != 2:
+        raise ValueError(f"quantize_rows_e4m3 takes a matrix [N, K], got {tuple(w.shape)}")
+    wf = w.detach().float()
+    amax = wf.abs().amax(1)
+    mant, exp = torch.frexp(amax)
+    se = (exp - 9 + (mant > 0.875).to(exp.dtype)).clamp(min=-126)
+    pow2 = ((se.to(torch.int32) + 127) << 23).view(torch.float32)         # 2^se from its bit pattern (torch.ldexp is inexact on some devices)
+    scale = torch.where(amax > 0, pow2, torch.ones_like(amax))
+    return (wf / scale[:, None]).to(torch.float8_e4m3fn), scale
+
+
+def dequantize_rows_e4m3(codes: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """codes * scale as fp32 [N, K] (exact; for power-of-two scales every value is a bf16 value)"""
+    return codes.float() * scale.float()[:, None]
 
 
 def kv_to_dynamic_cache(k: torch.Tensor, v: torch.Tensor):

@@ -1,0 +1,228 @@
+"""8-bit LLM weights (include/fvhd.h version 504), the parts that need no GPU: the quantisation recipe restated in torch
+(`ml_fastvlm_amd.quantize_rows_e4m3`), the version constants, the refusals of the new entry points and of the Python arguments."""
+import ctypes as C
+
+import pytest
+import torch
+
+
+def _matrices():
+    """random rows; rows whose values span 30 binades; amax exactly on both sides of the 1.75 mantissa boundary; a zero row; a tiny row"""
+    g = torch.Generator().manual_seed(0)
+    w = torch.randn(12, 256, generator=g)
+    w[1] *= torch.exp2(torch.randint(-20, 10, (256,), generator=g).float())
+    w[2] = 0
+    w[3] *= 1e-30
+    w[4] = w[4].clamp(-1, 1)
+    w[4, 7] = 1.75                    # amax = 1.75 * 2^0: amax / scale = 448 exactly
+    w[5] = w[5].clamp(-1, 1)
+    w[5, 9] = -1.7578125              # the next bf16 above 1.75: the scale doubles
+    w[6] = w[6].clamp(-0.5, 0.5)
+    w[6, 0] = 1.0                     # a power of two
+    w[7] *= 3e4
+    return w.to(torch.bfloat16)
+
+
+def test_quantize_rows_recipe():
+    from ml_fastvlm_amd import quantize_rows_e4m3
+    w = _matrices()
+    codes, scale = quantize_rows_e4m3(w)
+    assert codes.dtype == torch.float8_e4m3fn and codes.shape == w.shape and scale.dtype == torch.float32 and scale.shape == (w.shape[0],)
+    mant, _ = torch.frexp(scale)
+    assert bool((mant == 0.5).all()), "scales are powers of two"
+    amax = w.float().abs().amax(1)
+    nz = amax > 0
+    ratio = amax[nz] / scale[nz]
+    assert bool(((ratio > 224) & (ratio <= 448)).all()), ratio
+    assert float(amax[4] / scale[4]) == 448.0 and float(scale[5]) == 2 * float(scale[4])
+    assert torch.equal(codes.view(torch.uint8), (w.float() / scale[:, None]).to(torch.float8_e4m3fn).view(torch.uint8))
+    assert float(scale[2]) == 1.0 and int(codes[2].view(torch.uint8).abs().sum()) == 0
+    assert bool(torch.isfinite(codes.float()).all()) and float(codes.float().abs().max()) <= 448
+    deq = codes.float() * scale[:, None]
+    assert torch.equal(deq.to(torch.bfloat16).float(), deq), "codes * scale is exactly representable in bf16"
+    # quantising the dequantised matrix again reproduces its values exactly (the scale may drop by binades when a row's amax rounded down)
+    codes2, scale2 = quantize_rows_e4m3(deq.to(torch.bfloat16))
+    assert torch.equal(codes2.float() * scale2[:, None], deq)
+    # the relative error of a value against its row's amax is bounded by half an e4m3 ulp at the top binade: 2^-4 * 256 / 224 of amax
+    err = (deq - w.float()).abs().amax(1)
+    assert bool((err[nz] <= amax[nz] * 2.0 ** -4).all())
+
+
+def test_quantize_rows_takes_matrices_only():
+    from ml_fastvlm_amd import quantize_rows_e4m3
+    with pytest.raises(ValueError, match="matrix"):
+        quantize_rows_e4m3(torch.zeros(8))
+
+
+def test_version_constant():
+    from ml_fastvlm_amd import _lib
+    lib = _lib.load()
+    assert _lib.W8_VERSION == 504 <= lib.fvhd_version()
+    assert _lib.w8_lib() is lib
+    assert _lib.WEIGHT_FORMATS == {"bf16": 0, "fp8_e4m3": 1}
+
+
+def test_new_entry_points_refuse_null_and_bad_arguments_with_a_message():
+    """host pointers and a NULL stream: a launch would fault, the refusal comes first"""
+    from ml_fastvlm_amd import _lib
+    lib = _lib.w8_lib()
+    host = torch.zeros(256)
+    idb = torch.zeros(65, dtype=torch.long)
+    p, q = C.c_void_p(host.data_ptr()), C.c_void_p(idb.data_ptr())
+    n = C.c_size_t(0)
+
+    def refused(code, *words):
+        assert code != 0
+        msg = lib.fvhd_last_error()
+        for w in words:
+            assert w in msg, (w, msg)
+
+    refused(lib.fvhd_llm_set_weight_format(None, _lib.W_E4M3), b"fvhd_llm_set_weight_format", b"NULL")
+    refused(lib.fvhd_llm_weight_bytes(None, C.byref(n)), b"fvhd_llm_weight_bytes", b"NULL")
+    refused(lib.fvhd_llm_debug_packed_e4m3(None, 0, _lib.MAT_QKV, p, p, None), b"fvhd_llm_debug_packed_e4m3", b"NULL")
+    refused(lib.fvhd_op_quantize_e4m3(None, None, 16, 128, p, p), b"fvhd_op_quantize_e4m3", b"NULL")
+    refused(lib.fvhd_op_quantize_e4m3(None, p, 16, 128, None, p), b"fvhd_op_quantize_e4m3", b"NULL")
+    refused(lib.fvhd_op_quantize_e4m3(None, p, 16, 12, p, p), b"K % 8")
+    for epi in (_lib.EPI_RESID, _lib.EPI_SWIGLU):
+        refused(lib.fvhd_op_dec_gemm_w8(None, epi, p, 1, None, 1e-6, p, None, 16, 128, p, p, None, None, 1), b"fvhd_op_dec_gemm_w8", b"NULL")
+        refused(lib.fvhd_op_dec_gemm_w8(None, epi, p, 1, None, 1e-6, None, p, 16, 128, p, p, None, None, 1), b"fvhd_op_dec_gemm_w8", b"NULL")
+        refused(lib.fvhd_op_dec_gemm_w8(None, epi, p, 65, None, 1e-6, p, p, 16, 128, p, p, None, None, 1), b"B <= 64")
+        refused(lib.fvhd_op_dec_gemm_w8(None, epi, p, 1, None, 1e-6, p, p, 16, 64, p, p, None, None, 1), b"K % 128")
+        refused(lib.fvhd_op_dec_gemm_w8(None, epi, p, 1, None, 1e-6, p, p, 16, 128, p, p, None, None, 2), b"scratch")
+    refused(lib.fvhd_op_dec_gemm_w8(None, _lib.EPI_BIAS, p, 1, None, 1e-6, p, p, 16, 128, p, p, None, None, 1), b"epi")
+    refused(lib.fvhd_op_dec_qkv_w8(None, p, 1, 128, None, 1e-6, p, None, p, p, q, p, 16, 1e6, p, p, 8, p, 1, 1, 64, None, None, 1),
+            b"fvhd_op_dec_qkv_w8", b"NULL")
+    refused(lib.fvhd_op_dec_qkv_w8(None, p, 65, 128, None, 1e-6, p, p, p, p, q, p, 16, 1e6, p, p, 8, p, 1, 1, 64, None, None, 1), b"B <= 64")
+    refused(lib.fvhd_op_dec_lm_argmax_w8(None, p, 1, None, 1e-6, p, None, 16, 128, None, q, p, p), b"fvhd_op_dec_lm_argmax_w8", b"NULL")
+    refused(lib.fvhd_op_dec_lm_argmax_w8(None, p, 65, None, 1e-6, p, p, 16, 128, None, q, p, p), b"B <= 64")
+
+
+def _tiny():
+    from transformers import Qwen2Config, Qwen2ForCausalLM
+    cfg = Qwen2Config(vocab_size=64, hidden_size=64, num_hidden_layers=1, num_attention_heads=2, num_key_value_heads=1, intermediate_size=128)
+    return Qwen2ForCausalLM(cfg)
+
+
+def test_an_unknown_weight_format_is_a_value_error():
+    """before the device, the library or the model's tensors are looked at"""
+    from ml_fastvlm_amd import _lib
+    from ml_fastvlm_amd.builder import generator_context, prefill_context
+    from ml_fastvlm_amd.qwen2_decode import Qwen2Generator
+    from ml_fastvlm_amd.qwen2_prefill import Qwen2Prefill
+    m = _tiny()
+    for bad in ("int3", "fp8", None, 8):
+        with pytest.raises(ValueError, match="weights must be one of"):
+            Qwen2Prefill.from_hf(m, weights=bad)
+        with pytest.raises(ValueError, match="weights must be one of"):
+            Qwen2Generator.from_hf(m, 1, 8, weights=bad)
+        with pytest.raises(ValueError, match="weights must be one of"):
+            _lib.weight_format_code(bad)
+    with pytest.raises(ValueError, match="int3"):
+        prefill_context(m, weights="int3")
+    with pytest.raises(ValueError, match="int3"):
+        generator_context(m, 1, 8, weights="int3")
+    assert not hasattr(m, "_fvhd_llm_weights")                    # a refused format is not recorded
+    assert _lib.weight_format_code("bf16") == _lib.W_BF16 and _lib.weight_format_code("fp8_e4m3") == _lib.W_E4M3
+
+
+def test_a_prefill_context_in_another_format_is_an_error_not_a_repack():
+    from types import SimpleNamespace
+    from ml_fastvlm_amd.qwen2_decode import Qwen2Generator
+    m = _tiny()
+    for have, want in (("bf16", "fp8_e4m3"), ("fp8_e4m3", "bf16")):
+        pre = SimpleNamespace(weight_format=have)
+        with pytest.raises(ValueError, match=have):
+            Qwen2Generator.from_hf(m, 1, 8, prefill=pre, weights=want)
+
+
+class _Fn:
+    def __init__(self, f):
+        self.f = f
+
+    def __call__(self, *a):
+        return self.f(*a)
+
+
+def _stub_library(monkeypatch, version, calls):
+    """the pattern of tests/test_decode_batch.py: a stand-in library that reports `version` and records the calls named in `calls`"""
+    from ml_fastvlm_amd import _lib
+
+    class Lib:
+        fvhd_version = _Fn(lambda: version)
+
+        def __getattr__(self, name):
+            fn = _Fn(lambda *a: calls.append(name) or 0)
+            object.__setattr__(self, name, fn)
+            return fn
+
+    monkeypatch.setattr(_lib, "_lib", None)
+    monkeypatch.setattr(_lib.os.path, "exists", lambda p: True)
+    monkeypatch.setattr(_lib.C, "CDLL", lambda path: Lib())
+    return _lib.load()
+
+
+def test_a_503_library_loads_and_8bit_weights_name_the_rebuild(monkeypatch):
+    from ml_fastvlm_amd import _lib
+    from ml_fastvlm_amd.qwen2_prefill import Qwen2Prefill
+    calls = []
+    lib = _stub_library(monkeypatch, 503, calls)
+    assert lib.fvhd_version() == 503 and _lib.decode_lib(64) is lib and _lib.sampling_lib() is lib
+    with pytest.raises(_lib.FvhdError, match="504"):
+        _lib.w8_lib()
+    pre = Qwen2Prefill(0, 128, 1, 2, 1, 64, 128, 64)              # bf16 contexts work on the old library
+    pre.set_weight_format("bf16")                                 # the default again: nothing to ask the library
+    with pytest.raises(_lib.FvhdError, match="504"):
+        pre.set_weight_format("fp8_e4m3")
+    assert pre.weight_format == "bf16" and "fvhd_llm_set_weight_format" not in calls
+    pre._h = None
+
+
+def test_the_weight_format_is_refused_once_a_tensor_was_set(monkeypatch):
+    """the library's rule (fvhd_llm_set_weight_format after the first fvhd_llm_set_tensor fails; tests/test_gpu_decode_w8.py checks it on
+    the library itself) stated by the Python object before the call: the matrices are quantised as they arrive"""
+    from ml_fastvlm_amd import _lib
+    from ml_fastvlm_amd.qwen2_prefill import Qwen2Prefill
+    calls = []
+    _stub_library(monkeypatch, 504, calls)
+    pre = Qwen2Prefill(0, 128, 1, 2, 1, 64, 128, 64)
+    pre.set_weight_format("fp8_e4m3")
+    assert calls.count("fvhd_llm_set_weight_format") == 1 and pre.weight_format == "fp8_e4m3"
+    pre._set(_lib.load(), "model.norm.weight", torch.ones(128))
+    with pytest.raises(_lib.FvhdError, match="already set"):
+        pre.set_weight_format("bf16")
+    assert calls.count("fvhd_llm_set_weight_format") == 1 and pre.weight_format == "fp8_e4m3"
+    pre.set_weight_format("fp8_e4m3")                             # the format it has: fine
+    pre._h = None
+
+
+def test_prefill_context_records_the_format_and_rebuilds_for_another(monkeypatch):
+    from ml_fastvlm_amd import builder
+    from ml_fastvlm_amd import qwen2_prefill as qp
+    built = []
+
+    class Pre:
+        def __init__(self, weights):
+            self.weight_format = weights
+
+    monkeypatch.setattr(qp.Qwen2Prefill, "from_hf", classmethod(lambda cls, model, device=None, weights="bf16": built.append(weights) or Pre(weights)))
+    m = _tiny()
+    a = builder.prefill_context(m)
+    assert built == ["bf16"] and builder.prefill_context(m) is a and built == ["bf16"]
+    b = builder.prefill_context(m, weights="fp8_e4m3")
+    assert built == ["bf16", "fp8_e4m3"] and b is not a and m._fvhd_llm_weights == "fp8_e4m3"
+    assert builder.prefill_context(m) is b and built == ["bf16", "fp8_e4m3"]       # None = the recorded format
+    c = builder.prefill_context(m, weights="bf16")
+    assert built == ["bf16", "fp8_e4m3", "bf16"] and c.weight_format == "bf16" and m._fvhd_llm_weights == "bf16"
+
+
+def test_decode_bench_has_the_weights_option():
+    import importlib
+    import sys
+    tool = importlib.import_module("tools.decode_bench")
+    old = sys.argv
+    try:
+        sys.argv = ["decode_bench.py", "--weights", "int3"]
+        with pytest.raises(SystemExit):
+            tool.main()
+    finally:
+        sys.argv = old

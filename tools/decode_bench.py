@@ -4,6 +4,7 @@ captured graph and called eagerly, against the stock `transformers` decode loop 
     python tools/decode_bench.py [--hidden 896 1536 3584] [--batch 1 8 16 32 64] [--prompt 285] [--new 128] [--repeats 3] [--no-stock]
     python tools/decode_bench.py --sample [--hidden 896] [--batch 1 8]
     python tools/decode_bench.py --trace-steps 16 --hidden 3584 --batch 64      (eager steps only: the program of a kernel trace)
+    python tools/decode_bench.py --weights fp8_e4m3 ...                         (the packed matrices as e4m3 codes + row scales)
 
 --batch takes up to 64 sequences per step (more than 16 need a library of version 503).  --repeats times the graph replay that many
 times (`graph_ms_per_token` is their median, `graph_ms_per_token_runs` all of them); --no-stock leaves the stock transformers loop (and
@@ -39,16 +40,16 @@ def _ms_per(fn, n, dev):
 
 
 @torch.no_grad()
-def measure(llm, pre, batch: int, prompt: int, new: int, dev, repeats: int = 1, stock: bool = True, trace_steps: int = 0) -> dict:
+def measure(llm, pre, batch: int, prompt: int, new: int, dev, repeats: int = 1, stock: bool = True, trace_steps: int = 0, weights: str = "bf16") -> dict:
     from ml_fastvlm_amd.qwen2_decode import Qwen2Generator
     from ml_fastvlm_amd.qwen2_prefill import kv_to_dynamic_cache
     cfg = llm.config
     hidden = cfg.hidden_size
-    gen = Qwen2Generator.from_hf(llm, batch, prompt + new + 4, prefill=pre)
+    gen = Qwen2Generator.from_hf(llm, batch, prompt + new + 4, prefill=pre, weights=weights)
     g = torch.Generator(device=dev).manual_seed(0)
     emb = (0.5 * torch.randn(batch, prompt, hidden, device=dev, generator=g)).to(torch.bfloat16)
     mask = torch.ones(batch, prompt, device=dev, dtype=torch.long)
-    res = {"hidden": hidden, "layers": cfg.num_hidden_layers, "batch": batch, "prompt": prompt, "new_tokens": new}
+    res = {"hidden": hidden, "layers": cfg.num_hidden_layers, "batch": batch, "prompt": prompt, "new_tokens": new, "weights": weights}
     if trace_steps:                                         # a kernel trace's program: the prefill and `trace_steps` eager steps, nothing else
         gen.start(emb, mask, logits=False)
         for _ in range(trace_steps):
@@ -75,6 +76,8 @@ def measure(llm, pre, batch: int, prompt: int, new: int, dev, repeats: int = 1, 
     res["graph_ms_per_token_runs"] = runs
     I, H, nh, nkv, hd, V = cfg.intermediate_size, hidden, cfg.num_attention_heads, cfg.num_key_value_heads, hidden // cfg.num_attention_heads, cfg.vocab_size
     wbytes = cfg.num_hidden_layers * ((nh + 2 * nkv) * hd * H + H * nh * hd + 3 * I * H) * 2 + V * H * 2
+    if weights == "fp8_e4m3":                               # one byte per element + one fp32 scale per output row
+        wbytes = wbytes // 2 + 4 * (cfg.num_hidden_layers * ((nh + 2 * nkv) * hd + 2 * H + 2 * I) + V)
     kvbytes = cfg.num_hidden_layers * batch * nkv * (prompt + new / 2) * hd * 2 * 2
     res["weight_bytes_per_token"] = int(wbytes)
     res["kv_bytes_per_token"] = int(kvbytes)
@@ -101,15 +104,15 @@ def measure(llm, pre, batch: int, prompt: int, new: int, dev, repeats: int = 1, 
     return res
 
 
-def measure_width(hidden: int, batches, prompt: int, new: int, dev, **kw) -> list:
+def measure_width(hidden: int, batches, prompt: int, new: int, dev, weights: str = "bf16", **kw) -> list:
     """every batch of one width on ONE model and ONE packed copy of its weights"""
     from tools.ttft import build_llm
     from ml_fastvlm_amd.qwen2_prefill import Qwen2Prefill
     llm = build_llm(hidden, dev)
-    pre = Qwen2Prefill.from_hf(llm)
+    pre = Qwen2Prefill.from_hf(llm, weights=weights)        # ("bf16" asks nothing new of the library: a build before 504 still measures)
     rows = []
     for b in batches:
-        rows.append(measure(llm, pre, b, prompt, new, dev, **kw))
+        rows.append(measure(llm, pre, b, prompt, new, dev, weights=weights, **kw))
         torch.cuda.empty_cache()
     del pre, llm
     torch.cuda.empty_cache()
@@ -174,6 +177,7 @@ def main():
     ap.add_argument("--sample", action="store_true", help="the sampled step against the greedy one (default widths: 896 only)")
     ap.add_argument("--repeats", type=int, default=1, help="time the graph replay this many times")
     ap.add_argument("--no-stock", action="store_true", help="leave out the stock transformers loop and the eager library step")
+    ap.add_argument("--weights", choices=["bf16", "fp8_e4m3"], default="bf16", help="storage of the packed LLM matrices (fp8_e4m3 needs a library of version 504)")
     ap.add_argument("--trace-steps", type=int, default=0, help="run only the prefill and this many eager steps (for a kernel trace)")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -184,7 +188,7 @@ def main():
         return
     from ml_fastvlm_amd import _lib
     rows = [r for h in a.hidden for r in measure_width(h, a.batch, a.prompt, a.new, dev, repeats=a.repeats, stock=not a.no_stock,
-                                                       trace_steps=a.trace_steps)]
+                                                       trace_steps=a.trace_steps, weights=a.weights)]
     print(json.dumps({"tool": "decode_bench", "device": torch.cuda.get_device_name(dev), "library_version": _lib.load().fvhd_version(),
                       "results": rows}))
 

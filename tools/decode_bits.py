@@ -1,11 +1,12 @@
 """Are the decode's bits those of another build of the library?  Dumps teacher-forced step logits and sampled ids of small Qwen2
 stand-ins, then compares two dumps with torch.equal.
 
-    FVHD_LIB=/path/to/other/libfvhd.so python tools/decode_bits.py dump other.pt
-    python tools/decode_bits.py dump this.pt
+    FVHD_LIB=/path/to/other/libfvhd.so python tools/decode_bits.py dump other.pt [batch ...]
+    python tools/decode_bits.py dump this.pt [batch ...]
     python tools/decode_bits.py compare other.pt this.pt  > profiles/<round>_decode_batch_bits.log
 
-Per width (the 0.5B and 7B shapes, 2 / 1 layers, vocab 4096) and batch (1, 8, 16 - what every library version decodes): the fp32 logits
+Per width (the 0.5B and 7B shapes, 2 / 1 layers, vocab 4096) and batch (1, 8, 16 - what every library version decodes - unless batches
+are named: `dump x.pt 1 8 16 64` for two libraries of version 503 or later): the fp32 logits
 of the prefill and of 16 steps fed fixed token ids, the greedy ids of every step, and the ids of a sampled generation (temperature 0.7,
 top_k 50, top_p 0.9, seed 3).  Everything is seeded; the two dumps must come from the same GPU model."""
 from __future__ import annotations
@@ -38,7 +39,7 @@ def _model(name):
 
 
 @torch.no_grad()
-def dump(path):
+def dump(path, batches=BATCHES):
     from ml_fastvlm_amd import _lib
     from ml_fastvlm_amd.qwen2_decode import Qwen2Generator
     from ml_fastvlm_amd.qwen2_prefill import Qwen2Prefill
@@ -46,7 +47,7 @@ def dump(path):
     for name in CONFIGS:
         m = _model(name)
         pre = Qwen2Prefill.from_hf(m)
-        for B in BATCHES:
+        for B in batches:
             g = torch.Generator().manual_seed(100 + B)
             e = (0.5 * torch.randn(B, T, m.config.hidden_size, generator=g)).to("cuda", torch.bfloat16)
             mask = torch.ones(B, T, dtype=torch.long)
@@ -87,8 +88,8 @@ def compare(pa, pb):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) == 3 and sys.argv[1] == "dump":
-        dump(sys.argv[2])
+    if len(sys.argv) >= 3 and sys.argv[1] == "dump":
+        dump(sys.argv[2], tuple(int(b) for b in sys.argv[3:]) or BATCHES)
     elif len(sys.argv) == 4 and sys.argv[1] == "compare":
         sys.exit(compare(sys.argv[2], sys.argv[3]))
     else:

@@ -398,6 +398,26 @@ for rows in zip(*tm):
     print(rows[0][:24], " | ".join(r.split(":")[1].strip() for r in rows), " (new, pre, new, pre)")
 PY
     ;;
+w8)         # 8-bit LLM weights: the new ops and model tests, then the bf16 decode / prefill tests they must leave alone; a step that crashes or runs out of time ends the stage
+    timeout -k 10 600 python -m pytest tests/test_gpu_w8_ops.py tests/test_gpu_decode_w8.py -m gpu -q -s --maxfail=10 --durations=5 > ${O}_w8_pytest.log 2>&1; rc=$?; echo "pytest w8 rc=$rc"; tail -6 ${O}_w8_pytest.log | cut -c1-300
+    [ $rc -le 1 ] || exit $rc
+    timeout -k 10 1500 python -m pytest tests/test_gpu_decode.py tests/test_gpu_decode_ops.py tests/test_gpu_decode_batch.py tests/test_gpu_decode_long.py tests/test_gpu_sample.py tests/test_gpu_sample_edges.py tests/test_qwen2_prefill.py tests/test_gpu_ttft.py -m gpu -q --maxfail=10 --durations=5 > ${O}_w8_llm_pytest.log 2>&1; rc=$?; echo "pytest llm rc=$rc"; tail -6 ${O}_w8_llm_pytest.log | cut -c1-300
+    [ $rc -le 1 ] || exit $rc
+    ;;
+w8bits)     # 8-bit LLM weights: the bf16 path's bits against another build (W8_PARENT=path/to/libfvhd.so of the parent commit), tools/decode_bits.py at B = 1 / 8 / 16 / 64
+    FVHD_LIB=${W8_PARENT:?the parent build} timeout -k 10 300 python tools/decode_bits.py dump /tmp/${TAG}_bits_parent.pt 1 8 16 64 > ${O}_bits_dump.log 2>&1 \
+        && timeout -k 10 300 python tools/decode_bits.py dump /tmp/${TAG}_bits_this.pt 1 8 16 64 >> ${O}_bits_dump.log 2>&1 \
+        && timeout -k 10 120 python tools/decode_bits.py compare /tmp/${TAG}_bits_parent.pt /tmp/${TAG}_bits_this.pt > ${O}_decode_w8_bits.log 2>&1
+    echo "bits rc=$?"; tail -2 ${O}_decode_w8_bits.log
+    ;;
+w8bench)    # 8-bit LLM weights: step time of the parent's bf16 (W8_PARENT), this build's bf16 and this build's e4m3 in three alternating fresh processes each
+    ARGS="--hidden 896 3584 --batch 1 8 16 64 --prompt 285 --new 128 --repeats 3 --no-stock"
+    for rep in 1 2 3; do
+        FVHD_LIB=${W8_PARENT:?the parent build} timeout -k 10 400 python tools/decode_bench.py $ARGS > ${O}_bench_parent_$rep.json 2> ${O}_bench_parent_$rep.err || { echo "parent $rep failed"; exit 1; }
+        timeout -k 10 400 python tools/decode_bench.py $ARGS > ${O}_bench_bf16_$rep.json 2> ${O}_bench_bf16_$rep.err || { echo "bf16 $rep failed"; exit 1; }
+        timeout -k 10 400 python tools/decode_bench.py $ARGS --weights fp8_e4m3 > ${O}_bench_e4m3_$rep.json 2> ${O}_bench_e4m3_$rep.err || { echo "e4m3 $rep failed"; exit 1; }
+    done
+    ;;
 pmc)        # rocprofv3 kernel trace + the PMC passes of the final binary
     bash tools/run_pmc.sh ${TAG}
     ;;
