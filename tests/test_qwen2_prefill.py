@@ -6,7 +6,8 @@ STATED TOLERANCES (bf16 storage, fp32 accumulation against fp32 references):
   single ops: |err| <= 1e-2 |want| + 1e-2 rms(want);
   decoder stack: rel-L2 of the residual stream <= 5e-3 per layer (it is re-rounded to bf16 four times per layer), <= 1.5e-2 after the
   2-layer stacks tested here; logits rel-L2 <= 2e-2, cosine >= 0.9995; greedy token equal wherever the reference's top-2 margin
-  exceeds twice the logit error."""
+  exceeds twice the logit error.
+  The same kernels element by element against fp64 with the rms PER ROW, at the tile edges, under masks and in exact cases: tests/test_gpu_prefill_ops.py."""
 import ctypes as C
 
 import pytest
