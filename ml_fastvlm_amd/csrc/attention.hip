@@ -24,6 +24,7 @@
 //     row sums of those bf16 values accumulated in fp32 by the matrix cores (a ones fragment), O^T accumulators fp32; out-of-range keys are
 //     masked to -1e30, out-of-range queries are not stored (any N works, e.g. 16 or 576).
 #include "fvhd_common.h"
+#include "launchers.h"
 
 // ---------------------------------------------------------------------------------------------------
 // LayerNorm over the channel axis: x [M, C] bf16 -> y [M, C] bf16.  One wave per row, C % 4 == 0.

@@ -16,6 +16,7 @@
 //   * dw7_mfma_kernel (dwconv_mfma.hip): the 7x7 stride-1 case on the 16-block 4x4x4 MFMA, taken by fvhd_launch_dwconv
 //     wherever the map is at least 24 px wide and the channels come in whole 128-B / 192-B pixels (and the launch fills the chip).
 #include "fvhd_common.h"
+#include "launchers.h"
 
 // ---------------------------------------------------------------------------------------------------
 // LDS-tiled depthwise conv - the hot variant (38 dw3x3 + 46 dw7x7 + 4 dw7x7/s2 + the stem's dw3x3/s2 per forward).
@@ -318,11 +319,6 @@ static hipError_t launch_dw_tiled(hipStream_t st, const bf16* x, bf16* y, const 
 }
 
 // x [B,H,W,Cin] bf16 -> y [B,OH,OW,Cin*mult] bf16; w fp32 [K*K][Cout]; bias fp32 [Cout] or null.
-extern "C" int fvhd_dw7_mfma_supported(int B, int H, int W, int C, int force);
-extern "C" int fvhd_launch_dw7_mfma(hipStream_t st, const void* x, void* y, const float* w, const float* bias, int B, int H, int W, int C, unsigned* amax);
-extern "C" int fvhd_dw7s2_mfma_supported(int B, int H, int W, int Cin, int force);
-extern "C" int fvhd_launch_dw7s2_mfma(hipStream_t st, const void* x, void* y, const float* w, const float* bias, int B, int H, int W, int Cin, int gelu);
-
 // batch_invariant != 0: the kernel choice may depend on the SHAPE of one image only, never on B (bit-identical rows whatever the
 // batch they travel in); 0: the fastest kernel for this B (the VALU dw7x7 below the matrix-core kernel's fill threshold)
 // amax (may be null; honoured by the stride-1 7x7 kernels - the ConvFFN's depthwise conv - and by the RepMixer 3x3): see dwconv_tiled_kernel

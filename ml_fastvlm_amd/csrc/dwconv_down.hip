@@ -24,6 +24,7 @@
 // dwconv_mfma.hip), accumulation is fp32, bias rides in as the C operand of a row's first MFMA, GELU (fvhd_common.h: degree 7) in fp32.
 // LDS: 3 x 9 KB raw pairs + 4 x 2.5 KB images + 4 x 2 x 1.6 KB output rows + 1.3 KB zeros = 52 KB: three workgroups per CU.
 #include "fvhd_common.h"
+#include "launchers.h"
 
 namespace {
 

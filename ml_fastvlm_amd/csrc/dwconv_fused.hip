@@ -30,6 +30,7 @@
 // LDS: 4 raw rows 36 KB + y / A staging 2 x 18 KB + transposed x / y images 2 x 20.5 KB = 113 KB -> one workgroup (two waves
 // per SIMD) per CU.
 #include "fvhd_common.h"
+#include "launchers.h"
 
 namespace {
 

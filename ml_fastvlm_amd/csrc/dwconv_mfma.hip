@@ -33,6 +33,7 @@
 //     outside are never read; rows per chunk shrink with the batch (dwm_rows_per_chunk) so small launches still fill the chip.
 // Hand-pinned hazards (the compiler does not know the asm statements are MFMAs): see the comments at the asm statements.
 #include "fvhd_common.h"
+#include "launchers.h"
 
 namespace {
 

@@ -29,6 +29,7 @@
 // traffic by LDS-DMA from a dedicated wave with counted vmcnt); they ended at parity with the one-tile kernels below (630 / 474 /
 // 389 vs 602 / 464 / 387 us at C = 96 / 192 / 384: profiles/r02_ffn_persist_notes.md) and were removed in round 3 (git: 815bb98).
 #include "fvhd_common.h"
+#include "launchers.h"
 #include <stdlib.h>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));

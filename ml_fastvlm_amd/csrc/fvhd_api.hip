@@ -12,34 +12,8 @@
 #include <string>
 #include <vector>
 
-#include "../../include/fvhd.h"
-
-// ---- kernel launchers (dwconv.hip, gemm.hip, attention.hip, stem_head.hip) -------------------------
-extern "C" {
-int fvhd_launch_dwconv(hipStream_t, const void*, void*, const float*, const float*, int, int, int, int, int, int, int, int, int, unsigned*);
-int fvhd_launch_dw7_mfma(hipStream_t, const void*, void*, const float*, const float*, int, int, int, int, unsigned*);
-int fvhd_launch_preprocess(hipStream_t, const void*, int, int, long, int, int, unsigned, const int*, const int*, int, const int*, const int*, int, int, int,
-                           void*, const float*, int, void*, int);
-int fvhd_dw7_mfma_supported(int, int, int, int, int);
-int fvhd_launch_dw7s2_mfma(hipStream_t, const void*, void*, const float*, const float*, int, int, int, int, int);
-int fvhd_launch_dw3_dw7(hipStream_t, const void*, void*, void*, const float*, const float*, const float*, const float*, int, int, int, int, unsigned*);
-int fvhd_launch_gemm(hipStream_t, const void*, const void*, const float*, const float*, const void*, void*, int, int, int, int, int);
-int fvhd_gemm_splitk_plan(int, int, int);
-int fvhd_launch_gemm_splitk_ls(hipStream_t, const void*, const void*, const float*, const float*, const void*, void*, float*, int, int, int, int);
-int fvhd_launch_layernorm(hipStream_t, const void*, void*, const float*, const float*, int, int, float);
-int fvhd_launch_stem_fused(hipStream_t, const void*, int, void*, const float*, const float*, const float*, const float*, const void*, const float*, int, int);
-int fvhd_launch_attention(hipStream_t, const void*, void*, int, int, int, int);
-int fvhd_launch_stem_conv(hipStream_t, const void*, int, void*, const float*, const float*, int, int);
-int fvhd_launch_se_head(hipStream_t, const void*, float*, float*, const float*, const float*, const float*, const float*,
-                        void*, int, int, int, int, int);
-int fvhd_launch_cast_to_bf16(hipStream_t, const void*, int, void*, long);
-int fvhd_launch_ffn_fused(hipStream_t, const void*, const void*, const float*, const void*, const float*, const float*, void*, int, int, int);
-float fvhd_ffn_half_w2_limit(void);
-int fvhd_ffn_fused_supported(int);
-int fvhd_launch_splice(hipStream_t, const long*, const int*, const int*, const long*, const long*, const void*, const void*, void*,
-                       unsigned char*, long*, long*, int, int, int, int, long, long, int, int);
-int fvhd_ffn_pack_host(int, const float*, const float*, uint16_t*, uint16_t*, int);
-}
+#include "api_host.h"
+#include "launchers.h"
 
 namespace {
 
@@ -63,15 +37,6 @@ constexpr int kDims[kStages] = {96, 192, 384, 768, 1536};
 constexpr int kOutDim = 3072;   // cls_ratio 2.0 * 1536 (mci.py:1403)
 constexpr int kSeRd = 192;      // 3072 * 0.0625 (mci.py:49)
 constexpr float kBnEps = 1e-5f, kLnEps = 1e-5f;
-
-uint16_t f32_to_bf16_rne(float f)
-{
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);   // NaN
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
 
 struct HostTensor {
     std::vector<float> data;
@@ -352,26 +317,9 @@ bool pack_ffn(fvhd_ctx* c, Packer& pk, const std::string& p, const std::string& 
     return pack_vec(c, pk, ls_key, {C, 1, 1}, &out->ls);
 }
 
-// Every entry point that takes a context runs with the CONTEXT's device current and restores the caller's on exit: a tower on
-// cuda:1 must neither allocate its arena on cuda:0 nor leave cuda:1 current for the caller's next torch allocation.
-struct DeviceGuard {
-    int prev = -1;
-    bool switched = false;
-    hipError_t err = hipSuccess;
-    explicit DeviceGuard(int dev)
-    {
-        err = hipGetDevice(&prev);
-        if (err == hipSuccess && prev != dev) { err = hipSetDevice(dev); switched = err == hipSuccess; }
-    }
-    ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
-    DeviceGuard(const DeviceGuard&) = delete;
-    DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
 #define FVHD_ON_DEVICE(c)                                              \
     DeviceGuard _guard((c)->device);                                   \
     if (_guard.err != hipSuccess) return hip_fail("hipSetDevice", _guard.err)
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 constexpr size_t kSplitKPartialBytes = (size_t)512 * 128 * 128 * 4;   // fvhd_gemm_splitk_plan: at most 512 (tile, slice) pairs of 128 x 128 fp32
 
@@ -386,8 +334,8 @@ Ws carve(const fvhd_ctx* c, char* base, int B, int hidden)
     const size_t unit = (size_t)(c->R / 4) * (c->R / 4) * 96 * 2 * B;   // bytes of one stage-0 activation (bf16)
     const size_t Tn = (size_t)(c->R / 64) * (c->R / 64);
     Ws w;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align256(bytes); return p; };
+    Arena a;
+    auto take = [&](size_t bytes) { const size_t o = a.take(bytes); return base ? base + o : nullptr; };
     w.X = take(unit);
     w.T = take(unit);
     w.A = take(unit);
@@ -398,7 +346,7 @@ Ws carve(const fvhd_ctx* c, char* base, int B, int hidden)
     w.pooled = (float*)take((size_t)B * (kOutDim + kSeRd) * 4);
     w.scale = (float*)take((size_t)B * kOutDim * 4);
     w.part = (float*)take(kSplitKPartialBytes);
-    w.total = off;
+    w.total = a.off;
     return w;
 }
 
@@ -414,11 +362,8 @@ void clear_graphs(fvhd_ctx* c)
 int ensure_ws(fvhd_ctx* c, int B, hipStream_t st = nullptr, bool check_capture = false)
 {
     if (c->ws && B <= c->ws_batch && c->hidden <= c->ws_hidden) return 0;
-    if (check_capture) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-            return fail("fvhd: the workspace must grow for this batch size but the stream is being captured - call fvhd_reserve(ctx, batch) before capturing");
-    }
+    if (check_capture && is_capturing(st))
+        return fail("fvhd: the workspace must grow for this batch size but the stream is being captured - call fvhd_reserve(ctx, batch) before capturing");
     clear_graphs(c);                         // cached graphs point into the old arena
     const int nb = B > c->ws_batch ? B : c->ws_batch;
     const size_t need = carve(c, nullptr, nb, c->hidden).total;
@@ -760,10 +705,7 @@ int encode_body(fvhd_ctx* c, const void* images, int img_dtype, int B, void* out
     char *X = w.X, *T = w.T;
 
     bool use_graph = c->graph && !c->prof && n >= 3;
-    if (use_graph) {                       // a caller that is itself capturing gets plain launches (they land in its graph)
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) use_graph = false;
-    }
+    if (use_graph && is_capturing(st, true)) use_graph = false;     // a caller that is itself capturing gets plain launches (they land in its graph)
     if (!use_graph) return run_range(c, st, 0, n - 1, w, B, X, T, images, img_dtype, out, out_dtype);
 
     // ---- stem | graph of the interior steps | head ----
@@ -812,8 +754,7 @@ int encode_impl(fvhd_ctx* c, const void* images, int img_dtype, int B, void* out
     if (e) return e;
     // ---- range guard: poll the earlier calls' read-backs, zero this call's slots; after the launches, read them back asynchronously.
     // Not while the caller captures the stream (an event recorded into a graph cannot be polled) - such callers calibrate up front.
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    const bool capturing = hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+    const bool capturing = is_capturing(st, true);
     if (capturing) c->ws_captured = true;                     // the caller's graph now holds pointers into this arena: retire it, never free it
     c->guard_active = c->guard_on && c->guard_dev && c->guard_n == (int)c->m.steps.size() && !capturing && !c->audit_dev;
     if (c->guard_active) {
@@ -861,7 +802,7 @@ int fvhd_version(void) { return FVHD_VERSION; }
 
 const char* fvhd_last_error(void) { return g_err.c_str(); }
 
-// the other translation units of the library (llm_api.hip) report through the same thread-local message; returns 1
+// the other translation units of the library (the llm_*.hip C-ABI files) report through the same thread-local message; returns 1
 int fvhd_set_error(const char* msg) { return fail(msg ? msg : "unknown error"); }
 
 int fvhd_create(fvhd_ctx** out, int device, int image_size, int max_batch)
@@ -1044,10 +985,7 @@ int fvhd_project(fvhd_ctx* c, const void* tokens, int in_dtype, int rows, void* 
     const int Tn = fvhd_num_tokens(c);
     int e = ensure_ws(c, (rows + Tn - 1) / Tn, (hipStream_t)stream, true);
     if (e) return e;
-    {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) c->ws_captured = true;
-    }
+    if (is_capturing((hipStream_t)stream, true)) c->ws_captured = true;
     const Ws w = carve(c, c->ws, c->ws_batch, c->ws_hidden);
     return project_impl(c, tokens, in_dtype, rows, out, out_dtype, (hipStream_t)stream, w);
 }
@@ -1208,9 +1146,7 @@ int fvhd_audit_ranges(fvhd_ctx* c, const void* images, int img_dtype, int batch,
     if (img_dtype < 0 || img_dtype > 2) return fail("fvhd_audit_ranges: bad dtype");
     FVHD_ON_DEVICE(c);
     hipStream_t st = (hipStream_t)stream;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-        return fail("fvhd_audit_ranges: not during stream capture (it reads its result back)");
+    if (is_capturing(st)) return fail("fvhd_audit_ranges: not during stream capture (it reads its result back)");
     int e = prepare(c, batch, st);
     if (e) return e;
     const int n = (int)c->m.steps.size();

@@ -24,6 +24,7 @@
 //   * block ids are remapped so each XCD's private L2 sees a contiguous range of the tile order, and the order walks
 //     8 x 8 super-tiles (see the kernel): every A / W panel fetched from HBM feeds 8 resident tiles.
 #include "fvhd_common.h"
+#include "launchers.h"
 #include "gemm_layout.h"
 #include "rope.h"
 #include <stdlib.h>

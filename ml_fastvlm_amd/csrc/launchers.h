@@ -1,0 +1,83 @@
+// Every internal extern "C" symbol of the library that crosses a translation unit, declared ONCE: the file that defines a launcher and
+// every file that calls it include this header, so a prototype that drifts from its definition is a compile error (the symbols are
+// unmangled - a mismatch would still link and pass garbage).  Launchers return a hipError_t as int.  The public functions that kernel files
+// define (fvhd_gemm_splitk_plan, fvhd_gemm_qkv_rope_supported, fvhd_dw3_dw7_supported, ...) get the same check from include/fvhd.h, included here.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "../../include/fvhd.h"
+#include "llm_decode.h"
+
+extern "C" {
+int fvhd_set_error(const char* msg);     // fvhd_api.hip: the library's one thread-local error string; returns 1
+// dwconv.hip
+int fvhd_launch_dwconv(hipStream_t st, const void* x, void* y, const float* w, const float* bias, int B, int H, int W, int Cin, int K, int stride, int mult, int gelu,
+                       int flags, unsigned* amax);
+// dwconv_mfma.hip
+int fvhd_dw7_mfma_supported(int B, int H, int W, int C, int force);
+int fvhd_launch_dw7_mfma(hipStream_t st, const void* x, void* y, const float* w, const float* bias, int B, int H, int W, int C, unsigned* amax);
+// dwconv_down.hip
+int fvhd_launch_dw7s2_mfma(hipStream_t st, const void* x, void* y, const float* w, const float* bias, int B, int H, int W, int Cin, int gelu);
+// dwconv_fused.hip
+int fvhd_launch_dw3_dw7(hipStream_t st, const void* x, void* y, void* a, const float* w3, const float* b3, const float* w7, const float* b7, int B, int H, int W, int C,
+                        unsigned* amax);
+// gemm.hip
+int fvhd_launch_gemm(hipStream_t st, const void* A, const void* Wt, const float* bias, const float* ls, const void* resid, void* out, int M, int N, int K, int epi,
+                     int out_dtype);
+int fvhd_launch_gemm_splitk(hipStream_t st, const void* A, const void* Wt, const void* resid, void* out, float* partial, int M, int N, int K, int splits);
+int fvhd_launch_gemm_splitk_ls(hipStream_t st, const void* A, const void* Wt, const float* bias, const float* ls, const void* resid, void* out, float* partial, int M,
+                               int N, int K, int splits);
+int fvhd_launch_gemm_splitk_partials(hipStream_t st, const void* A, const void* Wt, float* partial, int M, int N, int K, int splits);
+int fvhd_launch_gemm_splitk_norm(hipStream_t st, const void* A, const void* Wt, const void* resid, void* out, float* partial, int M, int N, int K, int splits,
+                                 const float* norm_w, void* norm_out, float eps);
+int fvhd_launch_gemm_qkv_rope(hipStream_t st, const void* A, const void* Wt, const float* bias, void* out, int Mp, int N, int K, const long* pos, const float* table,
+                              void* kcache, void* vcache, int M, int T, int nh, int nkv, int HD, int P, float theta);
+// attention.hip
+int fvhd_launch_layernorm(hipStream_t st, const void* x, void* y, const float* w, const float* b, int M, int C, float eps);
+int fvhd_launch_attention(hipStream_t st, const void* qkv, void* out, int B, int N, int C, int fp8);
+// stem_head.hip
+int fvhd_launch_stem_conv(hipStream_t st, const void* img, int dtype, void* out, const float* w, const float* bias, int B, int R);
+int fvhd_launch_stem_fused(hipStream_t st, const void* img, int dtype, void* out, const float* w0, const float* b0, const float* w1, const float* b1, const void* w2,
+                           const float* b2, int B, int R);
+int fvhd_launch_se_head(hipStream_t st, const void* y, float* pooled, float* scale, const float* wr, const float* br, const float* we, const float* be, void* out,
+                        int out_dtype, int B, int T, int C, int RD);
+int fvhd_launch_cast_to_bf16(hipStream_t st, const void* x, int dtype, void* y, long n);
+// ffn_fused.hip
+int fvhd_ffn_pack_host(int C, const float* fc1, const float* fc2, uint16_t* w1img, uint16_t* w2img, int precision);
+float fvhd_ffn_half_w2_limit(void);
+int fvhd_launch_ffn_fused(hipStream_t st, const void* A, const void* w1img, const float* b1, const void* w2img, const float* b2, const float* ls, void* X, int M, int C,
+                          int precision);
+// splice.hip
+int fvhd_launch_splice(hipStream_t st, const long* ids, const int* start, const int* seqlen, const long* feat_row0, const long* labels_in, const void* table,
+                       const void* feats, void* out, unsigned char* mask_out, long* pos_out, long* labels_out, int B, int L, int H, int max_len, long vocab,
+                       long n_feat_rows, int left_pad, int dtype);
+// preprocess.hip
+int fvhd_launch_preprocess(hipStream_t st, const void* src, int src_h, int src_w, long src_pitch, int pad_top, int pad_left, unsigned bg, const int* hb, const int* hc,
+                           int hk, const int* vb, const int* vc, int vk, int row0, int nrows, void* tmp, const float* lut, int R, void* out, int out_dtype);
+// llm.hip
+int fvhd_launch_rmsnorm(hipStream_t st, const void* x, void* y, const float* w, int M, int H, float eps);
+int fvhd_launch_rope(hipStream_t st, void* qkv, const long* pos, const float* table, void* kcache, void* vcache, int M, int T, int nh, int nkv, int HD, int P, float theta);
+int fvhd_launch_splitk_bias_rope(hipStream_t st, const float* partial, int splits, int Mp, const float* bias, void* qkv, const long* pos, const float* table, void* kcache,
+                                 void* vcache, int M, int T, int nh, int nkv, int HD, int P, float theta);
+int fvhd_launch_llm_attention(hipStream_t st, const void* qkv, void* out, const unsigned char* key_valid, int B, int T, int nh, int nkv, int HD);
+int fvhd_launch_cast_rows(hipStream_t st, const void* src, int dtype, void* dst, long n);
+int fvhd_launch_gather_rows(hipStream_t st, const void* src, void* dst, int B, int T, int t_sel, int H);
+// llm_decode.hip
+int fvhd_launch_dec_gemm(hipStream_t st, const DecGemmArgs* a);
+int fvhd_launch_dec_attention(hipStream_t st, const void* q, const void* kc, const void* vc, const unsigned char* key_valid, void* out, int B, int nh, int nkv, int hd,
+                              int cap, const int* len, int len_add, int S, int chunk, float* part, int* cnt, const int* status);
+int fvhd_launch_dec_embed(hipStream_t st, const int64_t* tok, const int64_t* last, const void* table, int V, int H, void* h, unsigned char* key_valid, int B, int cap,
+                          const int* len, int* status, int* status_host);
+int fvhd_launch_dec_argmax_finish(hipStream_t st, const float* av, const int* ai, int nblk, int B, int64_t* last, int64_t* ids_out, int64_t* posv, int* len,
+                                  const int* status);
+int fvhd_launch_dec_argmax_blocks(hipStream_t st, const float* logits, int V, int B, float* av, int* ai);
+int fvhd_launch_dec_start_state(hipStream_t st, int64_t* posv, const int64_t* position_ids, int B, int T, int* len, int* status);
+// llm_w8.hip
+int fvhd_launch_dec_gemm_w8(hipStream_t st, const DecGemmArgs* a);
+int fvhd_launch_quantize_e4m3(hipStream_t st, const void* w, int rows, int K, void* codes, long pitch, float* scale, int sstride, int packed);
+int fvhd_launch_w8_unpack(hipStream_t st, const void* src, const float* scale, void* dst, long N, int K, int mode);
+int fvhd_launch_dec_embed_w8(hipStream_t st, const int64_t* tok, const int64_t* last, const void* table, const float* scale, int V, int H, void* h,
+                             unsigned char* key_valid, int B, int cap, const int* len, int* status, int* status_host);
+// llm_sample.hip
+size_t fvhd_dec_sample_ws_bytes(void);
+int fvhd_launch_dec_sample(hipStream_t st, const DecSampleArgs* a, void* ws);
+}

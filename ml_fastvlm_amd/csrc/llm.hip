@@ -13,6 +13,7 @@
 // q|k|v rows, optionally filling the KV cache), and a causal grouped-query flash attention for head_dim 64 / 128.
 // Activations are bf16 rows [B*T (padded to 256), width], statistics and accumulation fp32 - the same arithmetic contract as the tower.
 #include "fvhd_common.h"
+#include "launchers.h"
 #include "rope.h"
 
 // ---------------------------------------------------------------------------------------------------

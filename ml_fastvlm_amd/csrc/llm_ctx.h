@@ -1,0 +1,104 @@
+// Private header of the Qwen2 C-ABI sources (llm_weights.hip, llm_prefill.hip, llm_step.hip, llm_ops.hip): the context, the descriptor of
+// a packed matrix, error reporting and the few helpers one file defines and another calls.
+#pragma once
+#include <string>
+#include <vector>
+
+#include "api_host.h"
+#include "launchers.h"
+
+#pragma GCC visibility push(hidden)      // the helpers shared between the four sources are not exported symbols
+
+constexpr int kMaxSplits = 4;
+
+struct LayerOff { size_t ln1, bqkv, ln2, w[4], s[4]; };     // w, s: by FVHD_MAT_QKV .. FVHD_MAT_DOWN; s: the fp32 row scales of an e4m3 matrix
+
+struct __attribute__((visibility("default"))) fvhd_llm {     // (its inline constructor and destructor have always been weak exported symbols)
+    int device = 0, H = 0, L = 0, nh = 0, nkv = 0, hd = 0, I = 0, V = 0;
+    float eps = 1e-6f, theta = 1e6f;
+    int qkvw = 0;
+    char* wdev = nullptr;
+    size_t wbytes = 0;
+    std::vector<LayerOff> lo;
+    size_t norm_off = 0, lm_off = 0, lm_soff = 0;
+    int wfmt = FVHD_W_BF16;                // fvhd_llm_set_weight_format: FVHD_W_E4M3 = every matrix as e4m3 codes (1 byte, the K order of llm_w8.hip) + one
+                                           // fp32 scale per row; vectors and model.embed_tokens.weight are not affected
+    bool any_set = false;                  // a tensor was set: the format is fixed
+    char* wscratch = nullptr;              // e4m3: bf16 scratch of the largest matrix - the prefill dequantises each matrix into it right before its GEMM
+    size_t wscratch_bytes = 0;
+    std::vector<char> got;                 // per expected tensor: received?
+    std::vector<std::string> names;
+    // workspace
+    char* ws = nullptr;
+    size_t ws_bytes = 0;
+    int ws_rows = 0, ws_batch = 0, ws_pos = 0;
+    char *h = nullptr, *xn = nullptr, *qkv = nullptr, *att = nullptr, *act = nullptr, *last = nullptr, *lastn = nullptr;
+    float *rope = nullptr, *part = nullptr;
+    int fuse_rope = 0;                     // FVHD_LLM_FUSEROPE=1: rotary embedding + KV-cache copies inside the q|k|v projection's epilogue instead of their own launch (identical bits; measured neutral - prefill 3.421 / 3.410 -> 3.404 / 3.407 ms at B = 8, 2.316 -> 2.342 at B = 1, profiles/r05_ttft_fuserope_ab.log: the 5.4-us launch saved comes back as epilogue time - so off by default)
+    int down_splits = kMaxSplits, o_splits = 2, qkv_splits = 0, fuse_norm = 1;     // FVHD_LLM_SPLITK / FVHD_LLM_OSPLIT (largest split of down_proj / o_proj, 0 = never) / FVHD_LLM_QKVSPLIT / FVHD_LLM_FUSENORM
+    int max_pos = 0;                       // fvhd_llm_set_max_positions (config.max_position_embeddings): rows of the rotary table
+    // A prefill that ran while its stream was being captured put this workspace's pointers into the CALLER's graph.  Such a workspace is
+    // never freed when a later call needs a bigger one: it is retired (kept until fvhd_llm_destroy), so the captured graph keeps
+    // replaying on valid memory.  `generation` counts workspace replacements (fvhd_llm_workspace_generation).
+    bool ws_captured = false;
+    std::vector<char*> retired;
+    int generation = 0;
+    // fvhd_llm_set_tensor_device enqueues its copies on the CALLER's stream: `load_ev` is recorded behind the latest one so that
+    // fvhd_llm_finalize (host wait) and fvhd_llm_prefill (stream wait, whatever stream it runs on) are ordered after the packing
+    hipEvent_t load_ev = nullptr;
+    hipStream_t load_stream = nullptr;
+    bool load_pending = false;
+    // ---- decode (fvhd_llm_cache_reserve / start / decode) ----
+    char* emb = nullptr;                   // model.embed_tokens.weight, bf16 [V][H]: optional, the decode's input table of an untied model
+    int tied = -1;                         // fvhd_llm_set_tied_embeddings: 1 = the decode embeds through the packed lm_head rows, 0 = through
+                                           // `emb`; -1 = not said - the decode then needs `emb` (it never guesses the lm_head rows)
+    char* dc = nullptr;                    // one allocation: caches, mask, device words, decode workspace, rotary table
+    size_t dc_bytes = 0;
+    int dc_batch = 0, dc_cap = 0, dc_pos = 0;
+    int run_batch = 0;                     // batch of the last fvhd_llm_start (the decode steps run on it)
+    char *kcache = nullptr, *vcache = nullptr, *dh = nullptr, *dq = nullptr, *datt = nullptr, *dact = nullptr;
+    unsigned char* mask = nullptr;
+    int64_t *posv = nullptr, *last_ids = nullptr;
+    int *len = nullptr, *status = nullptr, *cnt = nullptr, *amax_i = nullptr;
+    float *dpart = nullptr, *apart = nullptr, *amax_v = nullptr, *dlogits = nullptr, *drope = nullptr, *drstd = nullptr;
+    int dec_rstd_once = 1;                 // a decode GEMM with a folded norm above 16 rows: the row statistics from one small launch (dec_rstd_kernel)
+                                           // instead of every workgroup; FVHD_DEC_RSTD_ONCE=0 for the A/B (identical bits)
+    int* status_host = nullptr;            // host-mapped copy of the error word: read by every host call without a synchronisation
+    int* status_host_dev = nullptr;
+    int cnt_att = 0;                       // counters [0, cnt_att) of the GEMMs, then B * nh of the attention
+    struct Plan { int S = 1, cpw = 1; } plan[5];      // K split of the decode GEMM of every matrix, by FVHD_MAT_*
+    int att_S = 1, att_chunk = 0;
+    char* pre_kv = nullptr;                // the prefill's own [n_layers][batch][nkv][seq_len][hd] caches, copied into the strided ones
+    size_t pre_kv_bytes = 0;
+    // fvhd_llm_set_sampling: read when fvhd_llm_start / fvhd_llm_decode enqueue (a captured graph keeps what it was captured with)
+    int do_sample = 0;
+    float temperature = 1.f, top_p = 1.f;
+    int top_k = 0;
+    unsigned long long seed = 0;
+    char* sws = nullptr;                   // the sampler's workspace (inside `dc`)
+};
+
+inline int lfail(const std::string& m) { return fvhd_set_error(m.c_str()); }
+inline int lhip(const char* what, hipError_t e) { return lfail(std::string(what) + ": " + hipGetErrorString(e)); }
+inline int lret(const char* what, int e) { return e ? lhip(what, (hipError_t)e) : 0; }      // e: what a launcher returned
+
+#define LCHECK(expr, what) do { if (int _e = (expr)) return lhip(what, (hipError_t)_e); } while (0)
+// the CONTEXT's device is current for the rest of the function; two statements and a local `_guard`, like FVHD_ON_DEVICE: top level of a function body only
+#define LLM_ON_DEVICE(c) DeviceGuard _guard((c)->device); if (_guard.err != hipSuccess) return lhip("hipSetDevice", _guard.err)
+
+inline int cu_count(const fvhd_llm* c)      // compute units of the context's device (256 if the query fails)
+{
+    int n = 0;
+    return hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess && n > 0 ? n : 256;
+}
+
+// one packed matrix: [N][K] elements (bf16, or e4m3 codes) at wdev + off; e4m3: its N fp32 row scales at wdev + soff
+struct Mat { size_t off, soff; long N; int K; };
+Mat mat_of(const fvhd_llm* c, int layer, int matrix);             // llm_weights.hip; matrix: FVHD_MAT_* (layer is ignored for FVHD_MAT_LM_HEAD)
+
+int first_missing_tensor(const fvhd_llm* c);                      // llm_weights.hip: index into c->got, -1 when every tensor has arrived
+int wait_for_loads(fvhd_llm* c);                                  // llm_weights.hip
+int ensure_ws(fvhd_llm* c, int B, int T, hipStream_t st, bool check_capture);     // llm_prefill.hip
+const char* sampling_error(float temperature, int top_k, float top_p);            // llm_step.hip: NULL when the parameters are valid
+
+#pragma GCC visibility pop

@@ -1,4 +1,4 @@
-// Arguments of the decode-step weight-streaming GEMM (llm_decode.hip), shared with the launch sequence in llm_api.hip.
+// Arguments of the decode-step weight-streaming GEMM (llm_decode.hip), shared with the launch sequences in llm_step.hip and llm_ops.hip.
 #pragma once
 #include <stdint.h>
 

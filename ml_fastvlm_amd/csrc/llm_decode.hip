@@ -17,7 +17,7 @@
 // Everything that changes from token to token (the cache slot, the positions, the mask column) is read from device memory, so one
 // captured graph replays the step for a whole generation.
 #include "fvhd_common.h"
-#include "llm_decode.h"
+#include "launchers.h"      // (with llm_decode.h: the argument structs)
 #include "rope.h"
 
 namespace {
@@ -621,8 +621,6 @@ static void launch_dec_gemm(hipStream_t st, const dim3 grid, const DecGemmArgs& 
     default: hipLaunchKernelGGL((dec_gemm_wide_kernel<EPI, 4>), grid, block, 0, st, a); break;
     }
 }
-
-extern "C" int fvhd_launch_dec_gemm_w8(hipStream_t st, const DecGemmArgs* a);     // llm_w8.hip
 
 extern "C" int fvhd_launch_dec_gemm(hipStream_t st, const DecGemmArgs* a)
 {

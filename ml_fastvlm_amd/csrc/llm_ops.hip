@@ -1,0 +1,235 @@
+// C ABI of the Qwen2 kernels one at a time (include/fvhd.h fvhd_op_*): the unit tests' entry points.  None of them takes a context.
+#include "llm_ctx.h"
+
+extern "C" {
+
+int fvhd_op_rmsnorm(fvhd_stream_t st, const void* x, void* y, const float* w, int M, int H, float eps)
+{
+    if (!x || !y || !w) return lfail("fvhd_op_rmsnorm: NULL pointer");
+    return lret("fvhd_op_rmsnorm", fvhd_launch_rmsnorm((hipStream_t)st, x, y, w, M, H, eps));
+}
+
+int fvhd_op_rope(fvhd_stream_t st, void* qkv, const int64_t* pos, const float* table, void* k_cache, void* v_cache, int M, int T, int n_heads,
+                 int n_kv_heads, int head_dim, int table_positions, float rope_theta)
+{
+    if (!qkv || !table) return lfail("fvhd_op_rope: NULL pointer");
+    return lret("fvhd_op_rope", fvhd_launch_rope((hipStream_t)st, qkv, (const long*)pos, table, k_cache, v_cache, M, T, n_heads, n_kv_heads, head_dim,
+                                                 table_positions, rope_theta));
+}
+
+int fvhd_op_gemm_qkv_rope(fvhd_stream_t st, const void* A, const void* Wt, const float* bias, void* out, int Mp, int N, int K, const int64_t* pos,
+                          const float* table, void* k_cache, void* v_cache, int M, int T, int n_heads, int n_kv_heads, int head_dim, int table_positions,
+                          float rope_theta)
+{
+    if (!A || !Wt || !bias || !out || !table) return lfail("fvhd_op_gemm_qkv_rope: NULL pointer");
+    if (!fvhd_gemm_qkv_rope_supported(Mp, N, K, head_dim, n_heads, n_kv_heads))
+        return lfail("fvhd_op_gemm_qkv_rope: needs head_dim 64, N = (n_heads + 2 n_kv_heads) * 64, Mp % 128 == 0, N % 128 == 0, K % 64 == 0 and at most one "
+                     "128 x 128 tile per CU (fvhd_gemm_qkv_rope_supported); other shapes run fvhd_op_gemm + fvhd_op_rope");
+    int e = fvhd_launch_gemm_qkv_rope((hipStream_t)st, A, Wt, bias, out, Mp, N, K, (const long*)pos, table, k_cache, v_cache, M, T, n_heads, n_kv_heads,
+                                      head_dim, table_positions, rope_theta);
+    return e ? lhip("fvhd_op_gemm_qkv_rope", (hipError_t)e) : 0;
+}
+
+int fvhd_op_gemm_splitk(fvhd_stream_t st, const void* A, const void* Wt, const void* resid, void* out, float* partial, int M, int N, int K, int splits)
+{
+    if (!A || !Wt || !out || !partial) return lfail("fvhd_op_gemm_splitk: NULL pointer");
+    if (splits < 1 || N % 128 || K % (64 * splits)) return lfail("fvhd_op_gemm_splitk: needs N % 128 == 0 and K % (64 * splits) == 0");
+    return lret("fvhd_op_gemm_splitk", fvhd_launch_gemm_splitk((hipStream_t)st, A, Wt, resid, out, partial, M, N, K, splits));
+}
+
+int fvhd_op_gemm_splitk_norm(fvhd_stream_t st, const void* A, const void* Wt, const void* resid, void* out, float* partial, int M, int N, int K, int splits,
+                             const float* norm_w, void* norm_out, float eps)
+{
+    if (!A || !Wt || !out || !partial || !norm_w || !norm_out) return lfail("fvhd_op_gemm_splitk_norm: NULL pointer");
+    if (norm_out == out) return lfail("fvhd_op_gemm_splitk_norm: norm_out must not alias out");
+    if (splits < 1 || N % 128 || K % (64 * splits)) return lfail("fvhd_op_gemm_splitk_norm: needs N % 128 == 0 and K % (64 * splits) == 0");
+    return lret("fvhd_op_gemm_splitk_norm", fvhd_launch_gemm_splitk_norm((hipStream_t)st, A, Wt, resid, out, partial, M, N, K, splits, norm_w, norm_out, eps));
+}
+
+int fvhd_op_qkv_splitk_rope(fvhd_stream_t st, const void* A, const void* Wt, const float* bias, float* partial, void* qkv, const int64_t* pos,
+                            const float* table, void* k_cache, void* v_cache, int M, int Mp, int K, int T, int n_heads, int n_kv_heads, int head_dim,
+                            int table_positions, float rope_theta, int splits)
+{
+    if (!A || !Wt || !partial || !qkv || !table) return lfail("fvhd_op_qkv_splitk_rope: NULL pointer");
+    const int width = (n_heads + 2 * n_kv_heads) * head_dim;
+    if (splits < 1 || width % 128 || K % (64 * splits) || Mp < M) return lfail("fvhd_op_qkv_splitk_rope: needs width % 128 == 0, K % (64 * splits) == 0, Mp >= M");
+    int e = fvhd_launch_gemm_splitk_partials((hipStream_t)st, A, Wt, partial, Mp, width, K, splits);
+    if (e) return lhip("fvhd_op_qkv_splitk_rope (gemm)", (hipError_t)e);
+    e = fvhd_launch_splitk_bias_rope((hipStream_t)st, partial, splits, Mp, bias, qkv, (const long*)pos, table, k_cache, v_cache, M, T, n_heads, n_kv_heads,
+                                     head_dim, table_positions, rope_theta);
+    return e ? lhip("fvhd_op_qkv_splitk_rope (reduce)", (hipError_t)e) : 0;
+}
+
+int fvhd_op_attention_causal(fvhd_stream_t st, const void* qkv, void* out, const uint8_t* key_valid, int B, int T, int n_heads, int n_kv_heads, int head_dim)
+{
+    if (!qkv || !out) return lfail("fvhd_op_attention_causal: NULL pointer");
+    return lret("fvhd_op_attention_causal", fvhd_launch_llm_attention((hipStream_t)st, qkv, out, key_valid, B, T, n_heads, n_kv_heads, head_dim));
+}
+
+// ---- single ops of the decode step (unit tests) ----
+// One builder per epilogue family fills DecGemmArgs; `scale` is NULL for a bf16 matrix, the fp32 row scales of an e4m3 one (the *_w8 entry points)
+static DecGemmArgs dec_args(int epi, const void* x, int B, const float* norm_w, float eps, const void* W, const float* scale, int N, int K, int splits)
+{
+    DecGemmArgs a;
+    a.x = x; a.ldx = K; a.norm_w = norm_w; a.eps = eps; a.W = W; a.wscale = scale; a.N = N; a.K = K; a.B = B; a.epi = epi;
+    a.cpw = (K / 128 + splits - 1) / splits;
+    if (a.cpw) a.S = (K / 128 + a.cpw - 1) / a.cpw;      // (K < 128: the launcher refuses cpw = 0)
+    return a;
+}
+
+static DecGemmArgs dec_gemm_args(int epi, const void* x, int B, const float* norm_w, float eps, const void* W, const float* scale, int N, int K,
+                                 const void* resid, void* out, float* partial, int* counters, int splits)
+{
+    DecGemmArgs a = dec_args(epi, x, B, norm_w, eps, W, scale, N, K, splits);
+    a.part = partial; a.cnt = counters; a.resid = resid; a.out = out; a.ldo = epi == FVHD_EPI_SWIGLU ? N / 2 : N;
+    return a;
+}
+
+static DecGemmArgs dec_qkv_args(const void* x, int B, int K, const float* norm_w, float eps, const void* W, const float* scale, const float* bias, void* q_out,
+                                const int64_t* pos, const float* table, int table_positions, float rope_theta, void* k_cache, void* v_cache, int capacity,
+                                const int* length, int n_heads, int n_kv_heads, int head_dim, float* partial, int* counters, int splits)
+{
+    DecGemmArgs a = dec_args(DEC_EPI_QKV, x, B, norm_w, eps, W, scale, (n_heads + 2 * n_kv_heads) * head_dim, K, splits);
+    a.part = partial; a.cnt = counters; a.bias = bias; a.out = q_out; a.ldo = n_heads * head_dim; a.pos = pos; a.rope = table; a.P = table_positions;
+    a.theta = rope_theta; a.nh = n_heads; a.nkv = n_kv_heads; a.hd = head_dim; a.kc = k_cache; a.vc = v_cache; a.cap = capacity; a.len = length;
+    return a;
+}
+
+static DecGemmArgs dec_argmax_args(const void* x, int B, const float* norm_w, float eps, const void* W, const float* scale, int V, int K, float* logits,
+                                   float* scratch_v, int* scratch_i)
+{
+    DecGemmArgs a = dec_args(DEC_EPI_ARGMAX, x, B, norm_w, eps, W, scale, V, K, 1);
+    a.logits = logits; a.amax_v = scratch_v; a.amax_i = scratch_i;
+    return a;
+}
+
+// e4m3 = a.wscale set: only the *_w8 entry points pass a scale (and refuse a NULL one), the bf16 ones pass nullptr and skip this.  a.W arrives as
+// plain row-major codes u8 [N][K]; the kernels read the packed K order of llm_w8.hip, so the codes are repacked into a process-wide scratch first,
+// grown on demand (eager calls only, like fvhd_op_dec_sample's workspace).  Then the launch; ARGMAX also reduces the (max, index) pairs to ids.
+static int dec_run(hipStream_t st, const char* who, DecGemmArgs a, int64_t* ids_out = nullptr)
+{
+    if (a.wscale) {
+        static char* buf[64] = {};
+        static size_t cap[64] = {};
+        int dev = 0;
+        hipError_t he = hipGetDevice(&dev);
+        if (he != hipSuccess) return lhip("hipGetDevice", he);
+        if (dev < 0 || dev >= 64) return lfail(std::string(who) + ": device index out of range");
+        const size_t need = (size_t)a.N * a.K;
+        if (need > cap[dev]) {
+            if (buf[dev]) (void)hipFree(buf[dev]);                  // (synchronises: no earlier launch still reads it)
+            buf[dev] = nullptr;
+            cap[dev] = 0;
+            if ((he = hipMalloc((void**)&buf[dev], need)) != hipSuccess) { buf[dev] = nullptr; return lhip("hipMalloc(e4m3 repack scratch)", he); }
+            cap[dev] = need;
+        }
+        if (int e = fvhd_launch_w8_unpack(st, a.W, nullptr, buf[dev], a.N, a.K, 2)) return lhip(who, (hipError_t)e);
+        a.W = buf[dev];
+    }
+    int e = fvhd_launch_dec_gemm(st, &a);
+    if (!e && a.epi == DEC_EPI_ARGMAX) e = fvhd_launch_dec_argmax_finish(st, a.amax_v, a.amax_i, (a.N / 16 + 3) / 4, a.B, nullptr, ids_out, nullptr, nullptr, nullptr);
+    return lret(who, e);
+}
+
+int fvhd_op_dec_gemm(fvhd_stream_t st, int epi, const void* x, int B, const float* norm_w, float eps, const void* Wt, int N, int K, const void* resid,
+                     void* out, float* partial, int* counters, int splits)
+{
+    if (!x || !Wt || !out || (epi == FVHD_EPI_RESID && !resid)) return lfail("fvhd_op_dec_gemm: NULL pointer");
+    if (epi != FVHD_EPI_RESID && epi != FVHD_EPI_SWIGLU) return lfail("fvhd_op_dec_gemm: epi must be FVHD_EPI_RESID or FVHD_EPI_SWIGLU");
+    if (B < 1 || B > 64 || N % 16 || K % 128 || splits < 1 || (splits > 1 && (!partial || !counters)))
+        return lfail("fvhd_op_dec_gemm: needs 1 <= B <= 64, N % 16 == 0, K % 128 == 0, splits >= 1 (and scratch when splits > 1)");
+    return dec_run((hipStream_t)st, "fvhd_op_dec_gemm", dec_gemm_args(epi, x, B, norm_w, eps, Wt, nullptr, N, K, resid, out, partial, counters, splits));
+}
+
+int fvhd_op_dec_gemm_w8(fvhd_stream_t st, int epi, const void* x, int B, const float* norm_w, float eps, const void* Wt, const float* scale, int N, int K,
+                        const void* resid, void* out, float* partial, int* counters, int splits)
+{
+    if (!x || !Wt || !scale || !out || (epi == FVHD_EPI_RESID && !resid)) return lfail("fvhd_op_dec_gemm_w8: NULL pointer");
+    if (epi != FVHD_EPI_RESID && epi != FVHD_EPI_SWIGLU) return lfail("fvhd_op_dec_gemm_w8: epi must be FVHD_EPI_RESID or FVHD_EPI_SWIGLU");
+    if (B < 1 || B > 64 || N < 16 || N % 16 || K < 128 || K % 128 || splits < 1 || (splits > 1 && (!partial || !counters)))
+        return lfail("fvhd_op_dec_gemm_w8: needs 1 <= B <= 64, N % 16 == 0, K % 128 == 0, splits >= 1 (and scratch when splits > 1)");
+    return dec_run((hipStream_t)st, "fvhd_op_dec_gemm_w8", dec_gemm_args(epi, x, B, norm_w, eps, Wt, scale, N, K, resid, out, partial, counters, splits));
+}
+
+int fvhd_op_dec_qkv(fvhd_stream_t st, const void* x, int B, int K, const float* norm_w, float eps, const void* Wt, const float* bias, void* q_out,
+                    const int64_t* pos, const float* table, int table_positions, float rope_theta, void* k_cache, void* v_cache, int capacity,
+                    const int* length, int n_heads, int n_kv_heads, int head_dim, float* partial, int* counters, int splits)
+{
+    if (!x || !Wt || !bias || !q_out || !pos || !table || !k_cache || !v_cache || !length) return lfail("fvhd_op_dec_qkv: NULL pointer");
+    if (B < 1 || B > 64 || K % 128 || splits < 1 || head_dim % 16 || n_heads < 1 || n_kv_heads < 1 || capacity < 1 || table_positions < 1 ||
+        (splits > 1 && (!partial || !counters)))
+        return lfail("fvhd_op_dec_qkv: needs 1 <= B <= 64, K % 128 == 0, head_dim % 16 == 0, splits >= 1 (and scratch when splits > 1)");
+    return dec_run((hipStream_t)st, "fvhd_op_dec_qkv", dec_qkv_args(x, B, K, norm_w, eps, Wt, nullptr, bias, q_out, pos, table, table_positions, rope_theta, k_cache,
+                                                                    v_cache, capacity, length, n_heads, n_kv_heads, head_dim, partial, counters, splits));
+}
+
+int fvhd_op_dec_qkv_w8(fvhd_stream_t st, const void* x, int B, int K, const float* norm_w, float eps, const void* Wt, const float* scale, const float* bias,
+                       void* q_out, const int64_t* pos, const float* table, int table_positions, float rope_theta, void* k_cache, void* v_cache, int capacity,
+                       const int* length, int n_heads, int n_kv_heads, int head_dim, float* partial, int* counters, int splits)
+{
+    if (!x || !Wt || !scale || !bias || !q_out || !pos || !table || !k_cache || !v_cache || !length) return lfail("fvhd_op_dec_qkv_w8: NULL pointer");
+    if (B < 1 || B > 64 || K < 128 || K % 128 || splits < 1 || head_dim < 16 || head_dim % 16 || n_heads < 1 || n_kv_heads < 1 || capacity < 1 ||
+        table_positions < 1 || (splits > 1 && (!partial || !counters)))
+        return lfail("fvhd_op_dec_qkv_w8: needs 1 <= B <= 64, K % 128 == 0, head_dim % 16 == 0, splits >= 1 (and scratch when splits > 1)");
+    return dec_run((hipStream_t)st, "fvhd_op_dec_qkv_w8", dec_qkv_args(x, B, K, norm_w, eps, Wt, scale, bias, q_out, pos, table, table_positions, rope_theta, k_cache,
+                                                                       v_cache, capacity, length, n_heads, n_kv_heads, head_dim, partial, counters, splits));
+}
+
+int fvhd_op_dec_attention(fvhd_stream_t st, const void* q, const void* k_cache, const void* v_cache, const uint8_t* key_valid, void* out, int B, int n_heads,
+                          int n_kv_heads, int head_dim, int capacity, const int* length, float* partial, int* counters, int splits)
+{
+    if (!q || !k_cache || !v_cache || !key_valid || !out || !length) return lfail("fvhd_op_dec_attention: NULL pointer");
+    if (B < 1 || B > 64) return lfail("fvhd_op_dec_attention: needs 1 <= B <= 64");
+    if (splits < 1 || capacity < 1 || (splits > 1 && (!partial || !counters))) return lfail("fvhd_op_dec_attention: splits >= 1 (and scratch when splits > 1)");
+    const int chunk = ((capacity + splits - 1) / splits + 63) / 64 * 64, S = (capacity + chunk - 1) / chunk;
+    return lret("fvhd_op_dec_attention", fvhd_launch_dec_attention((hipStream_t)st, q, k_cache, v_cache, key_valid, out, B, n_heads, n_kv_heads, head_dim, capacity,
+                                                                   length, 0, S, chunk, partial, counters, nullptr));
+}
+
+int fvhd_op_dec_lm_argmax(fvhd_stream_t st, const void* x, int B, const float* norm_w, float eps, const void* Wt, int V, int K, float* logits, int64_t* ids_out,
+                          float* scratch_v, int* scratch_i)
+{
+    if (!x || !Wt || !ids_out || !scratch_v || !scratch_i) return lfail("fvhd_op_dec_lm_argmax: NULL pointer");
+    if (B < 1 || B > 64 || V % 16 || K % 128) return lfail("fvhd_op_dec_lm_argmax: needs 1 <= B <= 64, V % 16 == 0, K % 128 == 0");
+    return dec_run((hipStream_t)st, "fvhd_op_dec_lm_argmax", dec_argmax_args(x, B, norm_w, eps, Wt, nullptr, V, K, logits, scratch_v, scratch_i), ids_out);
+}
+
+int fvhd_op_dec_lm_argmax_w8(fvhd_stream_t st, const void* x, int B, const float* norm_w, float eps, const void* Wt, const float* scale, int V, int K,
+                             float* logits, int64_t* ids_out, float* scratch_v, int* scratch_i)
+{
+    if (!x || !Wt || !scale || !ids_out || !scratch_v || !scratch_i) return lfail("fvhd_op_dec_lm_argmax_w8: NULL pointer");
+    if (B < 1 || B > 64 || V < 16 || V % 16 || K < 128 || K % 128) return lfail("fvhd_op_dec_lm_argmax_w8: needs 1 <= B <= 64, V % 16 == 0, K % 128 == 0");
+    return dec_run((hipStream_t)st, "fvhd_op_dec_lm_argmax_w8", dec_argmax_args(x, B, norm_w, eps, Wt, scale, V, K, logits, scratch_v, scratch_i), ids_out);
+}
+
+int fvhd_op_quantize_e4m3(fvhd_stream_t st, const void* W, int N, int K, void* codes, float* scale)
+{
+    if (!W || !codes || !scale) return lfail("fvhd_op_quantize_e4m3: NULL pointer");
+    if (N < 1 || K < 8 || K % 8) return lfail("fvhd_op_quantize_e4m3: needs N >= 1, K >= 8 and K % 8 == 0");
+    return lret("fvhd_op_quantize_e4m3", fvhd_launch_quantize_e4m3((hipStream_t)st, W, N, K, codes, K, scale, 1, 0));
+}
+
+// the sampler on its own: a process-wide workspace, allocated (and its counters zeroed) on first use - eager calls only
+int fvhd_op_dec_sample(fvhd_stream_t st, const float* logits, int B, int V, float temperature, int top_k, float top_p, unsigned long long seed, int n,
+                       const float* u_override, int64_t* ids, float* info)
+{
+    if (!logits || !ids) return lfail("fvhd_op_dec_sample: NULL pointer");
+    if (B < 1 || B > 16 || V < 1) return lfail("fvhd_op_dec_sample: needs 1 <= B <= 16 and V >= 1");
+    if (const char* e = sampling_error(temperature, top_k, top_p)) return lfail(std::string("fvhd_op_dec_sample: ") + e);
+    static char* ws[64] = {};
+    int dev = 0;
+    hipError_t he = hipGetDevice(&dev);
+    if (he != hipSuccess) return lhip("hipGetDevice", he);
+    if (dev < 0 || dev >= 64) return lfail("fvhd_op_dec_sample: device index out of range");
+    if (!ws[dev]) {
+        const size_t bytes = fvhd_dec_sample_ws_bytes();
+        if ((he = hipMalloc((void**)&ws[dev], bytes)) != hipSuccess) { ws[dev] = nullptr; return lhip("hipMalloc(sampler workspace)", he); }
+        if ((he = hipMemset(ws[dev], 0, bytes)) != hipSuccess) return lhip("hipMemset(sampler workspace)", he);
+    }
+    DecSampleArgs a;
+    a.logits = logits; a.B = B; a.V = V; a.temperature = temperature; a.top_k = top_k; a.top_p = top_p; a.seed = seed; a.n_add = n;
+    a.u_override = u_override; a.ids_out = ids; a.info = info;
+    return lret("fvhd_op_dec_sample", fvhd_launch_dec_sample((hipStream_t)st, &a, ws[dev]));
+}
+
+}  // extern "C"

@@ -22,7 +22,7 @@
 //                       order, no sort.  Then the ids, the optional info row, and - behind every row - the advance of positions / length.
 // Everything is deterministic: the same logits, settings, seed and n give the same id, eager or replayed.
 #include "fvhd_common.h"
-#include "llm_decode.h"
+#include "launchers.h"      // (with llm_decode.h: the argument structs)
 
 namespace {
 

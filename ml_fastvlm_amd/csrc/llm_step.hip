@@ -1,0 +1,281 @@
+// C ABI of the Qwen2 decode (include/fvhd.h "LLM decode"): the library's own KV cache, one token per sequence per step.
+// Kernels: llm_decode.hip, llm_w8.hip, llm_sample.hip.
+#include <cmath>
+
+#include "llm_ctx.h"
+
+namespace {
+
+fvhd_llm::Plan dec_plan(int N, int K, int ncu)
+{
+    // split K until the grid holds about two workgroups per CU (at most 16 slices: the last arriver reads them all)
+    const int ntiles = N / 16, ncol = (ntiles + 3) / 4, KC = K / 128;
+    const int want = (2 * ncu + ncol - 1) / ncol;
+    fvhd_llm::Plan p;
+    p.S = std::max(1, std::min(std::min(want, KC), 16));
+    p.cpw = (KC + p.S - 1) / p.S;
+    p.S = (KC + p.cpw - 1) / p.cpw;
+    return p;
+}
+
+void att_plan(int cap, int heads, int ncu, int* S, int* chunk)
+{
+    // key slices until the grid (batch * n_heads * slices) holds ~2 workgroups per CU - at B = 1 the 14 heads of Qwen2-0.5B alone fill
+    // 14 of 256 CUs - with at least 64 keys (one block per lane) per slice and at most 32 slices
+    const int want = (2 * ncu + heads - 1) / heads;
+    const int s = std::max(1, std::min(std::min(want, (cap + 63) / 64), 32));
+    *chunk = ((cap + s - 1) / s + 63) / 64 * 64;
+    *S = (cap + *chunk - 1) / *chunk;
+}
+
+int dec_status_error(const fvhd_llm* c, const char* who)
+{
+    const int st = *(volatile int*)c->status_host;
+    if (st == 1)
+        return lfail(std::string(who) + ": the KV cache is full (capacity " + std::to_string(c->dc_cap) +
+                     " positions): a decode step past it wrote nothing - reserve a larger cache (fvhd_llm_cache_reserve) and start again");
+    if (st == 2) return lfail(std::string(who) + ": a decode step was given a token id outside [0, vocab); it wrote nothing - start again");
+    return 0;
+}
+
+DecSampleArgs dec_sample_args(const fvhd_llm* c, const float* logits, int B)
+{
+    DecSampleArgs a;
+    a.logits = logits; a.B = B; a.V = c->V; a.temperature = c->temperature; a.top_k = c->top_k; a.top_p = c->top_p; a.seed = c->seed;
+    return a;
+}
+
+// the decode's input embedding: model.embed_tokens.weight when it was set, the packed lm_head rows only when the caller said the model ties them
+int dec_embedding_error(const fvhd_llm* c, const char* who)
+{
+    if (c->emb || c->tied == 1) return 0;
+    if (c->tied == 0)
+        return lfail(std::string(who) + ": this model does not tie its embeddings - set model.embed_tokens.weight (fvhd_llm_set_tensor) before decoding");
+    return lfail(std::string(who) + ": the decode's input embedding is unknown - set model.embed_tokens.weight (fvhd_llm_set_tensor), or call "
+                 "fvhd_llm_set_tied_embeddings(ctx, 1) for a model whose lm_head IS its embedding table (tie_word_embeddings)");
+}
+
+}  // namespace
+
+const char* sampling_error(float temperature, int top_k, float top_p)
+{
+    if (!(temperature > 0.f) || !std::isfinite(temperature)) return "temperature must be finite and > 0";
+    if (top_k < 0) return "top_k must be >= 0 (0 = off)";
+    if (!(top_p >= 0.f && top_p <= 1.f)) return "top_p must be in [0, 1] (1 = off)";
+    return nullptr;
+}
+
+extern "C" {
+
+int fvhd_llm_set_tied_embeddings(fvhd_llm* c, int tied)
+{
+    if (!c) return lfail("fvhd_llm_set_tied_embeddings: ctx is NULL");
+    c->tied = tied != 0 ? 1 : 0;
+    return 0;
+}
+
+int fvhd_llm_cache_reserve(fvhd_llm* c, int batch, int capacity)
+{
+    if (!c || batch < 1 || batch > 64 || capacity < 1) return lfail("fvhd_llm_cache_reserve: needs a context, 1 <= batch <= 64 and capacity >= 1");
+    if (first_missing_tensor(c) >= 0) return lfail("fvhd_llm_cache_reserve: weights incomplete (fvhd_llm_finalize reports the missing tensor)");
+    if (c->H % 128 || (c->nh * c->hd) % 128 || c->I % 128)
+        return lfail("fvhd_llm_cache_reserve: the decode needs hidden, n_heads * head_dim and intermediate to be multiples of 128");
+    LLM_ON_DEVICE(c);
+    int e = ensure_ws(c, batch, 1, nullptr, false);              // the rotary table
+    if (e) return e;
+    const int ncu = cu_count(c);
+    const int H = c->H, I = c->I, nh = c->nh, nkv = c->nkv, hd = c->hd, V = c->V, L = c->L;
+    att_plan(capacity, batch * nh, ncu, &c->att_S, &c->att_chunk);
+    const int NB = (batch + 15) / 16;                            // batch tiles of the decode GEMM: slabs and (max, index) pairs per tile
+    size_t part = 0;
+    int ncol = 1;
+    for (int m = FVHD_MAT_QKV; m <= FVHD_MAT_DOWN; ++m) {
+        const Mat d = mat_of(c, 0, m);
+        const fvhd_llm::Plan p = c->plan[m] = dec_plan((int)d.N, d.K, ncu);
+        if (p.S > 1) part = std::max(part, (size_t)p.S * d.N * 64 * NB);
+        ncol = std::max(ncol, ((int)d.N / 16 + 3) / 4);
+    }
+    c->plan[FVHD_MAT_LM_HEAD] = fvhd_llm::Plan{1, H / 128};
+    const int lm_ncol = (V / 16 + 3) / 4;
+    c->cnt_att = ncol;
+    Arena a;
+    const size_t kvb = (size_t)L * batch * nkv * capacity * hd * 2;
+    const size_t o_k = a.take(kvb), o_v = a.take(kvb), o_mask = a.take((size_t)batch * capacity), o_pos = a.take(8 * batch), o_last = a.take(8 * batch),
+                 o_len = a.take(4), o_status = a.take(4), o_h = a.take((size_t)batch * H * 2), o_q = a.take((size_t)batch * nh * hd * 2),
+                 o_att = a.take((size_t)batch * nh * hd * 2), o_act = a.take((size_t)batch * I * 2), o_part = a.take(std::max(part, (size_t)16)),
+                 o_apart = a.take((size_t)batch * nh * c->att_S * (hd + 2) * 4), o_cnt = a.take((size_t)(ncol + batch * nh) * 4),
+                 o_av = a.take((size_t)lm_ncol * 16 * NB * 4), o_ai = a.take((size_t)lm_ncol * 16 * NB * 4), o_logits = a.take((size_t)batch * V * 4),
+                 o_rope = a.take((size_t)c->ws_pos * hd * 4), o_sws = a.take(fvhd_dec_sample_ws_bytes()), o_rstd = a.take(4 * 64);
+    hipError_t he = hipDeviceSynchronize();                      // refused while a stream is being captured (like fvhd_llm_reserve)
+    if (he != hipSuccess) return lhip("fvhd_llm_cache_reserve: hipDeviceSynchronize", he);
+    if (c->dc) (void)hipFree(c->dc);
+    c->dc = nullptr;
+    c->dc_batch = c->dc_cap = c->run_batch = 0;
+    if ((he = hipMalloc((void**)&c->dc, a.off)) != hipSuccess) return lhip("hipMalloc(llm KV cache)", he);
+    if ((he = hipMemset(c->dc, 0, a.off)) != hipSuccess) return lhip("hipMemset(llm KV cache)", he);      // counters start at zero
+    if (!c->status_host) {
+        if ((he = hipHostMalloc((void**)&c->status_host, 4, hipHostMallocMapped)) != hipSuccess) return lhip("hipHostMalloc(status word)", he);
+        if ((he = hipHostGetDevicePointer((void**)&c->status_host_dev, c->status_host, 0)) != hipSuccess) return lhip("hipHostGetDevicePointer", he);
+    }
+    *(volatile int*)c->status_host = 0;
+    char* d = c->dc;
+    c->kcache = d + o_k; c->vcache = d + o_v; c->mask = (unsigned char*)(d + o_mask); c->posv = (int64_t*)(d + o_pos); c->last_ids = (int64_t*)(d + o_last);
+    c->len = (int*)(d + o_len); c->status = (int*)(d + o_status); c->dh = d + o_h; c->dq = d + o_q; c->datt = d + o_att; c->dact = d + o_act;
+    c->dpart = (float*)(d + o_part); c->apart = (float*)(d + o_apart); c->cnt = (int*)(d + o_cnt); c->amax_v = (float*)(d + o_av);
+    c->amax_i = (int*)(d + o_ai); c->dlogits = (float*)(d + o_logits); c->drope = (float*)(d + o_rope); c->sws = d + o_sws; c->drstd = (float*)(d + o_rstd);
+    c->dc_bytes = a.off; c->dc_batch = batch; c->dc_cap = capacity; c->dc_pos = c->ws_pos;
+    // the decode's own copy of the rotary table: a later, larger prefill may replace the prefill workspace under a captured decode graph
+    if ((he = hipMemcpy(c->drope, c->rope, (size_t)c->ws_pos * hd * 4, hipMemcpyDeviceToDevice)) != hipSuccess) return lhip("hipMemcpy(rope table)", he);
+    return 0;
+}
+
+int fvhd_llm_start(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* key_valid, const int64_t* position_ids, int batch, int seq_len,
+                   float* logits_out, int64_t* next_ids_out, fvhd_stream_t stream)
+{
+    if (!c || !embeds) return lfail("fvhd_llm_start: NULL argument");
+    if (!c->dc) return lfail("fvhd_llm_start: no KV cache - call fvhd_llm_cache_reserve first");
+    if (batch < 1 || batch > c->dc_batch) return lfail("fvhd_llm_start: batch must be in [1, the batch of fvhd_llm_cache_reserve]");
+    if (seq_len < 1 || seq_len > c->dc_cap) return lfail("fvhd_llm_start: seq_len must be in [1, the capacity of fvhd_llm_cache_reserve]");
+    if (int e = dec_embedding_error(c, "fvhd_llm_start")) return e;
+    LLM_ON_DEVICE(c);
+    hipStream_t st = (hipStream_t)stream;
+    const int L = c->L, nkv = c->nkv, hd = c->hd, T = seq_len, B = batch, cap = c->dc_cap;
+    const size_t layer_src = (size_t)B * nkv * T * hd * 2, need = 2 * (size_t)L * layer_src;
+    if (need > c->pre_kv_bytes) {
+        if (is_capturing(st)) return lfail("fvhd_llm_start: its staging buffer must grow but the stream is being captured");
+        hipError_t he = hipDeviceSynchronize();
+        if (he != hipSuccess) return lhip("hipDeviceSynchronize", he);
+        if (c->pre_kv) (void)hipFree(c->pre_kv);
+        c->pre_kv = nullptr;
+        c->pre_kv_bytes = 0;
+        if ((he = hipMalloc((void**)&c->pre_kv, need)) != hipSuccess) return lhip("hipMalloc(prefill KV staging)", he);
+        c->pre_kv_bytes = need;
+    }
+    *(volatile int*)c->status_host = 0;
+    float* logits = logits_out ? logits_out : c->dlogits;
+    char* pk = c->pre_kv;
+    char* pv = c->pre_kv + (size_t)L * layer_src;
+    int e = fvhd_llm_prefill(c, embeds, dtype, key_valid, position_ids, B, T, logits, pk, pv, stream);
+    if (e) return e;
+    const size_t layer_dst = (size_t)c->dc_batch * nkv * cap * hd * 2;
+    for (int l = 0; l < L; ++l) {
+        hipError_t he = hipMemcpy2DAsync(c->kcache + l * layer_dst, (size_t)cap * hd * 2, pk + l * layer_src, (size_t)T * hd * 2, (size_t)T * hd * 2,
+                                         (size_t)B * nkv, hipMemcpyDeviceToDevice, st);
+        if (he == hipSuccess)
+            he = hipMemcpy2DAsync(c->vcache + l * layer_dst, (size_t)cap * hd * 2, pv + l * layer_src, (size_t)T * hd * 2, (size_t)T * hd * 2,
+                                  (size_t)B * nkv, hipMemcpyDeviceToDevice, st);
+        if (he != hipSuccess) return lhip("hipMemcpy2DAsync(KV cache)", he);
+    }
+    hipError_t he = hipMemsetAsync(c->mask, 0, (size_t)c->dc_batch * cap, st);
+    if (he == hipSuccess)
+        he = key_valid ? hipMemcpy2DAsync(c->mask, cap, key_valid, T, T, B, hipMemcpyDeviceToDevice, st) : hipMemset2DAsync(c->mask, cap, 1, T, B, st);
+    if (he != hipSuccess) return lhip("key mask copy", he);
+    if (c->do_sample) {
+        // sampling: the cache state first, so that the draw reads n = the prompt length from the device
+        LCHECK(fvhd_launch_dec_start_state(st, c->posv, position_ids, B, T, c->len, c->status), "decode state");
+        DecSampleArgs a = dec_sample_args(c, logits, B);
+        a.len = c->len; a.last = c->last_ids; a.ids_out = next_ids_out;
+        LCHECK(fvhd_launch_dec_sample(st, &a, c->sws), "first-token sampling");
+    } else {
+        // the first token: the same (max, index) pairs + reduce as the decode's lm_head (lowest index on ties), then the cache state
+        LCHECK(fvhd_launch_dec_argmax_blocks(st, logits, c->V, B, c->amax_v, c->amax_i), "first-token argmax (blocks)");
+        LCHECK(fvhd_launch_dec_argmax_finish(st, c->amax_v, c->amax_i, (c->V + 63) / 64, B, c->last_ids, next_ids_out, nullptr, nullptr, nullptr),
+               "first-token argmax (reduce)");
+        LCHECK(fvhd_launch_dec_start_state(st, c->posv, position_ids, B, T, c->len, c->status), "decode state");
+    }
+    c->run_batch = B;
+    return 0;
+}
+
+int fvhd_llm_decode(fvhd_llm* c, const int64_t* token_ids, float* logits_out, int64_t* next_ids_out, fvhd_stream_t stream)
+{
+    if (!c) return lfail("fvhd_llm_decode: ctx is NULL");
+    if (!c->dc || !c->run_batch) return lfail("fvhd_llm_decode: no started sequence - call fvhd_llm_cache_reserve and fvhd_llm_start first");
+    if (int e = dec_status_error(c, "fvhd_llm_decode")) return e;
+    if (int e = dec_embedding_error(c, "fvhd_llm_decode")) return e;
+    LLM_ON_DEVICE(c);
+    hipStream_t st = (hipStream_t)stream;
+    const int B = c->run_batch, H = c->H, I = c->I, nh = c->nh, nkv = c->nkv, hd = c->hd, cap = c->dc_cap;
+    const char* w = c->wdev;
+    const bool q8 = c->wfmt == FVHD_W_E4M3;
+    if (q8 && !c->emb) {                                         // a tied model: the token row dequantised from the lm_head codes
+        LCHECK(fvhd_launch_dec_embed_w8(st, token_ids, c->last_ids, w + c->lm_off, (const float*)(w + c->lm_soff), c->V, H, c->dh, c->mask, B, cap, c->len,
+                                        c->status, c->status_host_dev), "decode embed (e4m3 lm_head rows)");
+    } else {
+        LCHECK(fvhd_launch_dec_embed(st, token_ids, c->last_ids, c->emb ? c->emb : w + c->lm_off, c->V, H, c->dh, c->mask, B, cap, c->len, c->status,
+                                     c->status_host_dev), "decode embed");
+    }
+    const size_t layer_kv = (size_t)c->dc_batch * nkv * cap * hd * 2;
+    auto gemm = [&](int epi, const void* x, const float* norm_w, int layer, int matrix) {
+        const Mat m = mat_of(c, layer, matrix);
+        const fvhd_llm::Plan& p = c->plan[matrix];
+        DecGemmArgs a;
+        a.wscale = q8 ? (const float*)(w + m.soff) : nullptr;
+        a.x = x; a.ldx = m.K; a.norm_w = norm_w; a.eps = c->eps; a.W = w + m.off; a.N = (int)m.N; a.K = m.K; a.B = B; a.S = p.S; a.cpw = p.cpw;
+        a.part = c->dpart; a.cnt = c->cnt; a.epi = epi; a.status = c->status; a.rstd = c->dec_rstd_once ? c->drstd : nullptr;
+        return a;
+    };
+    for (int l = 0; l < c->L; ++l) {
+        const LayerOff& o = c->lo[l];
+        DecGemmArgs a = gemm(DEC_EPI_QKV, c->dh, (const float*)(w + o.ln1), l, FVHD_MAT_QKV);
+        a.bias = (const float*)(w + o.bqkv); a.out = c->dq; a.ldo = nh * hd; a.pos = c->posv; a.rope = c->drope; a.P = c->dc_pos; a.theta = c->theta;
+        a.nh = nh; a.nkv = nkv; a.hd = hd; a.kc = c->kcache + l * layer_kv; a.vc = c->vcache + l * layer_kv; a.cap = cap; a.len = c->len;
+        LCHECK(fvhd_launch_dec_gemm(st, &a), "decode q|k|v + rope + cache append");
+        LCHECK(fvhd_launch_dec_attention(st, c->dq, c->kcache + l * layer_kv, c->vcache + l * layer_kv, c->mask, c->datt, B, nh, nkv, hd, cap, c->len, 1,
+                                         c->att_S, c->att_chunk, c->apart, c->cnt + c->cnt_att, c->status), "decode attention");
+        a = gemm(DEC_EPI_RESID, c->datt, nullptr, l, FVHD_MAT_O);
+        a.resid = c->dh; a.out = c->dh; a.ldo = H;
+        LCHECK(fvhd_launch_dec_gemm(st, &a), "decode o_proj + residual");
+        a = gemm(DEC_EPI_SWIGLU, c->dh, (const float*)(w + o.ln2), l, FVHD_MAT_GATE_UP);
+        a.out = c->dact; a.ldo = I;
+        LCHECK(fvhd_launch_dec_gemm(st, &a), "decode rmsnorm + gate|up + silu");
+        a = gemm(DEC_EPI_RESID, c->dact, nullptr, l, FVHD_MAT_DOWN);
+        a.resid = c->dh; a.out = c->dh; a.ldo = H;
+        LCHECK(fvhd_launch_dec_gemm(st, &a), "decode down_proj + residual");
+    }
+    DecGemmArgs a = gemm(DEC_EPI_ARGMAX, c->dh, (const float*)(w + c->norm_off), -1, FVHD_MAT_LM_HEAD);
+    a.logits = logits_out; a.amax_v = c->amax_v; a.amax_i = c->amax_i;
+    if (c->do_sample) {
+        // sampling replaces the argmax reduce: it reads the logits (the caller's, else the context's buffer), chooses with n = length + 1
+        // (the cache holds this step's token), and advances positions and length
+        if (!a.logits) a.logits = c->dlogits;
+        LCHECK(fvhd_launch_dec_gemm(st, &a), "decode final norm + lm_head");
+        DecSampleArgs sa = dec_sample_args(c, a.logits, B);
+        sa.len = c->len; sa.n_add = 1; sa.last = c->last_ids; sa.ids_out = next_ids_out; sa.posv = c->posv; sa.len_advance = c->len;
+        sa.status = c->status;
+        LCHECK(fvhd_launch_dec_sample(st, &sa, c->sws), "decode sampling");
+        return 0;
+    }
+    LCHECK(fvhd_launch_dec_gemm(st, &a), "decode final norm + lm_head + argmax");
+    LCHECK(fvhd_launch_dec_argmax_finish(st, c->amax_v, c->amax_i, (c->V / 16 + 3) / 4, B, c->last_ids, next_ids_out, c->posv, c->len, c->status),
+           "decode argmax reduce");
+    return 0;
+}
+
+int fvhd_llm_set_sampling(fvhd_llm* c, int do_sample, float temperature, int top_k, float top_p, unsigned long long seed)
+{
+    if (!c) return lfail("fvhd_llm_set_sampling: ctx is NULL");
+    if (const char* e = sampling_error(temperature, top_k, top_p)) return lfail(std::string("fvhd_llm_set_sampling: ") + e);
+    c->do_sample = do_sample != 0;
+    c->temperature = temperature;
+    c->top_k = top_k;
+    c->top_p = top_p;
+    c->seed = seed;
+    return 0;
+}
+
+int fvhd_llm_cache_state(fvhd_llm* c, int* length, int* status)
+{
+    if (!c || !c->dc) return lfail("fvhd_llm_cache_state: no KV cache");
+    LLM_ON_DEVICE(c);
+    int v[2] = {0, 0};
+    hipError_t he = hipDeviceSynchronize();
+    if (he == hipSuccess) he = hipMemcpy(&v[0], c->len, 4, hipMemcpyDeviceToHost);
+    if (he == hipSuccess) he = hipMemcpy(&v[1], c->status, 4, hipMemcpyDeviceToHost);
+    if (he != hipSuccess) return lhip("fvhd_llm_cache_state", he);
+    if (length) *length = v[0];
+    if (status) *status = v[1];
+    return 0;
+}
+
+}  // extern "C"

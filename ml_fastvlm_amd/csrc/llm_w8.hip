@@ -15,7 +15,7 @@
 // - sit at byte 64 (j / 2) + 16 g + 8 (j % 2), so that lane (lr, g) reads its operands of two MFMA steps with ONE 16-byte load and a
 // wave's load covers 64 contiguous bytes of 16 rows - the access shape of the bf16 kernel at half the bytes.
 #include "fvhd_common.h"
-#include "llm_decode.h"
+#include "launchers.h"      // (with llm_decode.h: the argument structs)
 #include "rope.h"
 
 namespace {

@@ -13,6 +13,7 @@
 //           float table (the reference multiplies in float64 and rounds to float32: the table holds exactly those floats)
 //           -> three planes [3][R][R] of the caller's dtype, x fastest (coalesced stores)
 #include "fvhd_common.h"
+#include "launchers.h"
 
 namespace {
 

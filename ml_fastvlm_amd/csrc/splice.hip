@@ -12,6 +12,7 @@
 //                padding     -> zeros (llava_arch.py:306-322);   plus attention_mask / position_ids / labels of that row.
 // One 256-thread workgroup copies 4 rows, 64 lanes x 16 B per step: HBM-bound, B x max_len x H x 2 bytes in and out.
 #include "fvhd_common.h"
+#include "launchers.h"
 
 #define SPLICE_IGNORE (-100L)        /* IGNORE_INDEX, llava/constants.py:7 */
 

@@ -8,6 +8,7 @@
 //             written straight in the tower's output dtype/layout (feature_select is free:
 //             mobileclip_encoder.py:60-68).
 #include "fvhd_common.h"
+#include "launchers.h"
 
 template <typename T> FVHD_DEV float ld_as_f32(const T* p, size_t i);
 template <> FVHD_DEV float ld_as_f32<float>(const float* p, size_t i) { return p[i]; }

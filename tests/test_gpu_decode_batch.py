@@ -85,7 +85,7 @@ def _nb(B):
 
 
 def _plan_splits(N, K):
-    """the step's own choice (dec_plan in csrc/llm_api.hip): K split until the grid holds about two workgroups per CU, at most 16"""
+    """the step's own choice (dec_plan in csrc/llm_step.hip): K split until the grid holds about two workgroups per CU, at most 16"""
     ncu = torch.cuda.get_device_properties(0).multi_processor_count
     ncol, KC = (N // 16 + 3) // 4, K // 128
     S = max(1, min((2 * ncu + ncol - 1) // ncol, KC, 16))

@@ -1,4 +1,4 @@
-"""Qwen2 decode steps at cache sizes where the attention splits its key axis (csrc/llm_api.hip att_plan: capacity > 64 and a grid that
+"""Qwen2 decode steps at cache sizes where the attention splits its key axis (csrc/llm_step.hip att_plan: capacity > 64 and a grid that
 does not fill the chip): prompts of 285 and 600 tokens in a cache of 2304 positions, left padding longer than a key slice.  Every case
 first asserts, from att_plan's rule restated here, that it runs with more than one key slice - so the in-launch combine across slices,
 the len_add = 1 call form, the attention's counter offset and the scratch sizing of fvhd_llm_cache_reserve are what is measured.
@@ -26,7 +26,7 @@ CAP = 2304
 
 
 def _att_slices(cap, heads):
-    """att_plan (csrc/llm_api.hip), restated: -> (slices, keys per slice)"""
+    """att_plan (csrc/llm_step.hip), restated: -> (slices, keys per slice)"""
     ncu = torch.cuda.get_device_properties(0).multi_processor_count
     want = (2 * ncu + heads - 1) // heads
     s = max(1, min(want, (cap + 63) // 64, 32))
