@@ -1,7 +1,7 @@
 """TEST INFRASTRUCTURE ONLY - plain torch fp64 restatements of the prefill's single operations (csrc/llm.hip: RMSNorm, rotary embedding,
 causal grouped-query attention) on the bf16-rounded operands, written from oracle/qwen2_oracle.py (itself pinned to `transformers`), not
 from the kernels; a CPU model of the attention kernel's arithmetic (`flash_model`) that only serves to show that the inputs the GPU tests
-use leave room under their bound; the input families of those tests; and the shared comparison / sentinel-guard helpers.
+use leave room under their bound; the input families of those tests; and the comparison / sentinel-guard helpers of tests/llm_testlib.py.
 
 PINNING: tests/test_prefill_reference.py checks every *_ref here against oracle.qwen2_oracle in fp32 (<= 1e-5) and the headroom of every
 input family under the GPU tests' bound (flash_model's err / bound <= 0.5, census <= 2^-7)."""
@@ -13,47 +13,10 @@ import torch
 
 from oracle import qwen2_oracle as Q
 
-SENT = 0x7B3D                  # bf16 bit pattern of the guard fill (1.23e36), as tests/test_gpu_decode_ops.py
+# the comparison (rms PER ROW) and sentinel-guard helpers, shared with the decode tests: re-exported for this module's two users
+from llm_testlib import SENT, close as _close, guard_intact, guarded, same_bits, violations as _violations  # noqa: F401
+
 KT = 64                        # key tile of llm_attention_kernel
-
-
-# ---- comparison: the rms PER ROW --------------------------------------------------------------------------------------------------------
-def _violations(got, want, rtol, atol_rms, rows=None):
-    """-> (elements outside |err| <= rtol |want| + atol_rms rms(want row), the largest err / bound).  A row is the LAST dimension (one
-    (b, t, head) vector of hd values, one row of rmsnorm / rope); rows: bool mask over the leading dimensions of the rows to compare"""
-    assert got.shape == want.shape, (got.shape, want.shape)
-    got, want = got.double(), want.double()
-    assert bool(torch.isfinite(got).all()), "non-finite output"
-    if rows is not None:
-        got, want = got[rows], want[rows]
-    if want.numel() == 0:
-        return 0, 0.0
-    rms = want.pow(2).mean(-1, keepdim=True).sqrt()
-    err, bound = (got - want).abs(), rtol * want.abs() + atol_rms * rms
-    ratio = torch.where(err > 0, err / bound.clamp_min(1e-300), torch.zeros_like(err))
-    return int((err > bound).sum()), float(ratio.max())
-
-
-def _close(got, want, what, rtol, atol_rms, rows=None):
-    bad, worst = _violations(got, want, rtol, atol_rms, rows)
-    assert bad == 0, f"{what}: {bad} of {want.numel()} elements out of tolerance, worst err / bound {worst:.3g}"
-    return worst
-
-
-# ---- sentinel guards ---------------------------------------------------------------------------------------------------------------------
-def guarded(rows, width, device, guard_rows=64):
-    """a [rows + guard_rows, width] bf16 buffer filled with the sentinel -> (the whole buffer as int16 [rows + guard_rows, width],
-    the bf16 view of its first `rows` rows)"""
-    buf = torch.full((rows + guard_rows, width), SENT, device=device, dtype=torch.int16)
-    return buf, buf.view(torch.bfloat16)[:rows]
-
-
-def guard_intact(buf, rows):
-    return bool((buf[rows:] == SENT).all())
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and bool((a.contiguous().view(torch.int16) == b.contiguous().view(torch.int16)).all())
 
 
 # ---- the operations in fp64 --------------------------------------------------------------------------------------------------------------

@@ -1,10 +1,15 @@
 """The decode's batch limit (64 sequences per step, include/fvhd.h version 503): constants, refusals before any pointer is read, the
 502-library path and the generate fallback's reason.  No GPU."""
 import ctypes as C
+import os
+import sys
 import warnings
 
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import llm_testlib as L  # noqa: E402
 
 
 def test_constants_and_versions():
@@ -93,12 +98,6 @@ def test_more_than_64_sequences_is_refused_in_python_too():
         _lib.decode_lib(65)
 
 
-def _tiny():
-    from transformers import Qwen2Config, Qwen2ForCausalLM
-    cfg = Qwen2Config(vocab_size=64, hidden_size=64, num_hidden_layers=1, num_attention_heads=2, num_key_value_heads=1, intermediate_size=128)
-    return Qwen2ForCausalLM(cfg)
-
-
 def test_batch_reason():
     from ml_fastvlm_amd.builder import _batch_reason
     assert _batch_reason(1) is None and _batch_reason(17) is None and _batch_reason(64) is None
@@ -113,7 +112,7 @@ def test_library_generate_falls_back_above_64_rows_with_the_batch_as_the_reason(
         calls.append(inputs.shape[0])
         return "reference"
 
-    m = _tiny()                                                   # a CPU model: the batch is checked before the device
+    m = L.tiny_qwen2()                                                   # a CPU model: the batch is checked before the device
     gen = _make_library_generate(orig)
     kw = dict(do_sample=False, num_beams=1, max_new_tokens=4, use_cache=True)
     with warnings.catch_warnings(record=True) as w:

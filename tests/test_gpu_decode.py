@@ -3,33 +3,17 @@
 Oracle: transformers' Qwen2ForCausalLM in fp32 on the same bf16-rounded weights, continuing with its own cache.  Budgets: the single ops
 within the prefill tests' rel-L2 1e-2; teacher-forced step logits within rel-L2 2e-2 (bf16 activations through the stack); greedy token
 streams equal wherever the oracle's top-2 margin exceeds DELTA."""
-import ctypes as C
+import os
+import sys
 
 import pytest
 import torch
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from llm_testlib import (DELTA, GREEDY_SEEDS, lib, rel,  # noqa: E402,F401
+                         agree as _agree, models as _models, prompt as _prompt, ptr as _p, stream as _st)
+
 pytestmark = pytest.mark.gpu
-
-DELTA = 0.02          # fp32 logit margin above which our bf16 step must pick the oracle's token (the steps' logit error is ~10x smaller)
-
-
-def rel(a, b):
-    a, b = a.float(), b.float()
-    return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from ml_fastvlm_amd import _lib
-    return _lib.load()
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _st():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _norm_ref(x, w, eps=1e-6):
@@ -173,44 +157,6 @@ def test_dec_lm_argmax_full_vocab_ties(lib, B):
 
 
 # ---- model-level tests ---------------------------------------------------------------------------------------------------------------
-CONFIGS = {
-    "0.5B": dict(hidden_size=896, num_hidden_layers=2, num_attention_heads=14, num_key_value_heads=2, intermediate_size=4864, tie_word_embeddings=True),
-    "1.5B": dict(hidden_size=1536, num_hidden_layers=1, num_attention_heads=12, num_key_value_heads=2, intermediate_size=8960, tie_word_embeddings=True),
-    "7B": dict(hidden_size=3584, num_hidden_layers=1, num_attention_heads=28, num_key_value_heads=4, intermediate_size=18944, tie_word_embeddings=False),
-}
-
-
-def _models(name, seed=0, vocab=4096):
-    """(bf16 model on the GPU, fp32 oracle on the same bf16-rounded weights)"""
-    from transformers import Qwen2Config, Qwen2ForCausalLM
-    torch.manual_seed(seed)
-    cfg = Qwen2Config(vocab_size=vocab, max_position_embeddings=4096, rope_theta=1e6, rms_norm_eps=1e-6, **CONFIGS[name])
-    m = Qwen2ForCausalLM(cfg).eval()
-    with torch.no_grad():
-        for p in m.parameters():                                  # biases and norm weights away from their trivial init
-            if p.dim() == 1:
-                p.add_(0.05 * torch.randn_like(p))
-    m16 = m.to("cuda", torch.bfloat16)
-    ref = Qwen2ForCausalLM(cfg).eval().to("cuda")
-    ref.load_state_dict({k: v.float() for k, v in m16.state_dict().items()})
-    return m16, ref
-
-
-def _prompt(ref, B, T, side, seed=0):
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    e = 0.5 * torch.randn(B, T, ref.config.hidden_size, device="cuda", generator=g)
-    e = e.to(torch.bfloat16).float()
-    mask = torch.ones(B, T, device="cuda", dtype=torch.long)
-    for b in range(B):
-        npad = 3 * b
-        if npad:
-            if side == "left":
-                mask[b, :npad] = 0
-            else:
-                mask[b, T - npad:] = 0
-    return e, mask
-
-
 @pytest.mark.parametrize("name", ["0.5B", "1.5B", "7B"])
 def test_teacher_forced_steps(name):
     from transformers import DynamicCache
@@ -255,26 +201,6 @@ def test_teacher_forced_steps(name):
         pre = gen.pre(long, torch.ones(B, T + k, device="cuda", dtype=torch.long))
     assert rel(lg, pre) <= 1e-2, rel(lg, pre)
     assert isinstance(gen.pre, Qwen2Prefill)
-
-
-def _agree(ours, ref_seq, scores, delta=DELTA):
-    """token-for-token equality of every row up to the oracle's first step with a top-2 margin <= delta; -> steps compared per row"""
-    n = []
-    for b in range(ref_seq.shape[0]):
-        i = 0
-        while i < ref_seq.shape[1]:
-            top = scores[i][b].float().topk(2).values
-            if (top[0] - top[1]).item() <= delta:
-                break
-            assert i < ours.shape[1] and int(ours[b, i]) == int(ref_seq[b, i]), (b, i, ours[b].tolist(), ref_seq[b].tolist())
-            i += 1
-        n.append(i)
-    return n
-
-
-# prompt seeds (of `_prompt`, model seed 1) where the fp32 oracle's top-2 margin exceeds 2 * DELTA at EVERY step of every row for 12 new
-# tokens: there bf16 rounding cannot legitimately pick another token, so the outputs must be equal token for token
-GREEDY_SEEDS = {"left": [14, 83], "right": [64, 187]}
 
 
 @pytest.mark.parametrize("side", ["left", "right"])

@@ -1,6 +1,6 @@
 """Decode steps of 17 .. 64 sequences (csrc/llm_decode.hip batch tiles, include/fvhd.h version 503) against tests/decode_reference.py,
-the fp32 oracle and transformers' generate - with the helpers, shapes and tolerances of test_gpu_decode.py / test_gpu_decode_ops.py /
-test_gpu_sample*.py for the same operations (copied here: the arithmetic per row is the 16-row kernel's, so no new tolerance):
+the fp32 oracle and transformers' generate - with the helpers of tests/llm_testlib.py and the shapes and tolerances of test_gpu_decode.py /
+test_gpu_decode_ops.py / test_gpu_sample*.py for the same operations (the arithmetic per row is the 16-row kernel's, so no new tolerance):
 
   single ops       |got - want| <= 1e-2 |want| + 1e-2 rms(want_row), rms per batch row (fp32 logits: 2e-3)
   step logits      rel-L2 <= 2e-2 against the fp32 oracle
@@ -8,8 +8,6 @@ test_gpu_sample*.py for the same operations (copied here: the arithmetic per row
 
 and bit for bit: a B-row launch equals the same op on rows [0, 16), [16, 32), .. with the same `splits` - a batch tile IS the 16-row
 kernel's arithmetic - and copies of a prompt in different batch tiles give identical step logits."""
-import ctypes as C
-import math
 import os
 import sys
 import warnings
@@ -19,102 +17,19 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import decode_reference as R  # noqa: E402
+from llm_testlib import (DELTA, GREEDY_SEEDS, SENT, lib, rel,  # noqa: E402,F401
+                         agree as _agree, blocks as _blocks, close_by_batch_row as _close, dec_attention as _attention, dec_gemm as _gemm,
+                         dec_lm_argmax as _lm, guard_intact as _guard_intact, guarded_rows as _guarded, models as _models, nb as _nb,
+                         padded_mask, plan_splits as _plan_splits, prompt as _prompt, ptr as _p, row_scales as _row_scales, stream as _st,
+                         wide_prompt as _wide_prompt)
 
 pytestmark = pytest.mark.gpu
 
-DELTA = 0.02          # fp32 logit margin above which our bf16 step must pick the oracle's token (test_gpu_decode.py)
-SENT = 0x7B3D         # bf16 bit pattern of the guard fill (1.23e36)
 GAP = 1e-5            # a draw closer than this to a CDF / group boundary is not pinned by the reference (test_gpu_sample_edges.py)
 WIDE = [17, 24, 32, 33, 48, 63, 64]
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from ml_fastvlm_amd import _lib
-    return _lib.load()
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _st():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def rel(a, b):
-    a, b = a.float(), b.float()
-    return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
-
-
-def _violations(got, want, rtol=1e-2, atol_rms=1e-2):
-    got, want = got.double().reshape(got.shape[0], -1), want.double().reshape(want.shape[0], -1)
-    assert got.shape == want.shape, (got.shape, want.shape)
-    assert bool(torch.isfinite(got).all()), "non-finite output"
-    rms = want.pow(2).mean(-1, keepdim=True).sqrt()
-    err, bound = (got - want).abs(), rtol * want.abs() + atol_rms * rms
-    ratio = torch.where(err > 0, err / bound.clamp_min(1e-300), torch.zeros_like(err))
-    return int((err > bound).sum()), float(ratio.max())
-
-
-def _close(got, want, what, rtol=1e-2, atol_rms=1e-2):
-    bad, worst = _violations(got, want, rtol, atol_rms)
-    assert bad == 0, f"{what}: {bad} of {want.numel()} elements out of tolerance, worst err / bound {worst:.3g}"
-    return worst
-
-
-def _row_scales(B, g):
-    """factors spanning 0.05 .. 20, shuffled, a fresh permutation for every block of 16 rows"""
-    base = torch.logspace(math.log10(0.05), math.log10(20.0), 16, device="cuda", dtype=torch.float32)
-    s = torch.cat([base[torch.randperm(16, device="cuda", generator=g)] for _ in range((B + 15) // 16)])
-    return s[:B]
-
-
-def _guarded(width, B):
-    """[B, width] bf16 + 2 guard rows + 64 guard elements, sentinel-filled -> (buffer as int16, the [B, width] view of its head)"""
-    buf = torch.full(((B + 2) * width + 64,), SENT, device="cuda", dtype=torch.int16)
-    return buf, buf.view(torch.bfloat16)[:B * width].view(B, width)
-
-
-def _guard_intact(buf, used):
-    return bool((buf[used:] == SENT).all())
-
-
-def _nb(B):
-    return (B + 15) // 16
-
-
-def _plan_splits(N, K):
-    """the step's own choice (dec_plan in csrc/llm_step.hip): K split until the grid holds about two workgroups per CU, at most 16"""
-    ncu = torch.cuda.get_device_properties(0).multi_processor_count
-    ncol, KC = (N // 16 + 3) // 4, K // 128
-    S = max(1, min((2 * ncu + ncol - 1) // ncol, KC, 16))
-    cpw = (KC + S - 1) // S
-    return (KC + cpw - 1) // cpw
-
-
-def _blocks(B):
-    return [(i, min(i + 16, B)) for i in range(0, B, 16)]
-
-
 # ---- 1. the weight-streaming GEMM ---------------------------------------------------------------------------------------------------
-def _gemm(lib, epi, x, nw, W, resid, splits):
-    from ml_fastvlm_amd import _lib
-    B, K = x.shape
-    N = W.shape[0]
-    swiglu = epi == "swiglu"
-    width = N // 2 if swiglu else N
-    buf, out = _guarded(width, B)
-    part = torch.empty(splits * N * 16 * _nb(B), device="cuda") if splits > 1 else None
-    cnt = torch.zeros((N // 16 + 3) // 4, device="cuda", dtype=torch.int32) if splits > 1 else None
-    _lib.check(lib.fvhd_op_dec_gemm(_st(), _lib.EPI_SWIGLU if swiglu else _lib.EPI_RESID, _p(x), B, _p(nw), 1e-6, _p(W), N, K, _p(resid), _p(out),
-                                    _p(part), _p(cnt), splits), "dec_gemm")
-    torch.cuda.synchronize()
-    assert _guard_intact(buf, B * width), "rows >= B or the guard tail were written"
-    assert cnt is None or int(cnt.abs().sum()) == 0, "counters not back at zero"
-    return out.clone()
-
-
 GEMM_SHAPES = [(80, 256), (896, 4864), (9728, 896), (3584, 18944), (37888, 3584)]
 
 
@@ -195,35 +110,6 @@ def test_dec_qkv_wide(lib, nh, nkv, hd, H, B):
 
 
 # ---- 3. single-query attention over the cache ------------------------------------------------------------------------------------------
-def _attention(lib, q, kc, vc, mask, length, splits):
-    from ml_fastvlm_amd import _lib
-    B, nkv, cap, hd = kc.shape
-    nh = q.shape[1] // hd
-    buf, out = _guarded(nh * hd, B)
-    ln = torch.tensor([length], device="cuda", dtype=torch.int32)
-    part = torch.empty(B * nh * splits * (hd + 2), device="cuda") if splits > 1 else None
-    cnt = torch.zeros(B * nh, device="cuda", dtype=torch.int32) if splits > 1 else None
-    _lib.check(lib.fvhd_op_dec_attention(_st(), _p(q), _p(kc), _p(vc), _p(mask), _p(out), B, nh, nkv, hd, cap, _p(ln), _p(part), _p(cnt), splits),
-               "dec_attention")
-    torch.cuda.synchronize()
-    assert _guard_intact(buf, B * nh * hd), "rows >= B or the guard tail were written"
-    assert cnt is None or int(cnt.abs().sum()) == 0, "counters not back at zero"
-    return out.clone()
-
-
-def _padded_mask(B, cap, length, side):
-    """row b: a different number of padded keys (capped below the length): up to whole 64-key blocks for a long cache"""
-    step = 150 if length > 600 else max(length // 5, 1)
-    mask = torch.zeros(B, cap, device="cuda", dtype=torch.uint8)
-    for b in range(B):
-        npad = min(step * (b % 13 + 1), length - 1)
-        if side == "left":
-            mask[b, npad:length] = 1
-        else:
-            mask[b, :length - npad] = 1
-    return mask
-
-
 @pytest.mark.parametrize("hd,nh,nkv", [(64, 14, 2), (128, 28, 4)])
 @pytest.mark.parametrize("length,cap", [(1, 64), (285, 300), (2049, 2050)])
 @pytest.mark.parametrize("B", [40, 64])
@@ -234,7 +120,7 @@ def test_dec_attention_wide(lib, hd, nh, nkv, length, cap, B):
     vc = (torch.randn(B, nkv, cap, hd, device="cuda", generator=g) * _row_scales(B, g)[:, None, None, None]).to(torch.bfloat16)
     worst = 0.0
     for side in ("left", "right"):
-        mask = _padded_mask(B, cap, length, side)
+        mask = padded_mask(B, cap, length, side, wrap=13)          # row b: b % 13 + 1 steps of padded keys
         want = R.dec_attention_ref(q, kc, vc, mask, length)
         for splits in (1, 9):
             got = _attention(lib, q, kc, vc, mask, length, splits)
@@ -244,24 +130,6 @@ def test_dec_attention_wide(lib, hd, nh, nkv, length, cap, B):
 
 
 # ---- 4. lm_head + argmax -------------------------------------------------------------------------------------------------------------
-def _lm(lib, x, nw, W, logits=True):
-    from ml_fastvlm_amd import _lib
-    B, H = x.shape
-    V = W.shape[0]
-    lbuf = torch.full((B * V + 64,), float("nan"), device="cuda") if logits else None
-    lg = lbuf[:B * V].view(B, V) if logits else None
-    ids = torch.full((B + 4,), -7, device="cuda", dtype=torch.long)
-    nblk = (V // 16 + 3) // 4
-    sv = torch.empty(nblk * 16 * _nb(B), device="cuda")
-    si = torch.empty(nblk * 16 * _nb(B), device="cuda", dtype=torch.int32)
-    _lib.check(lib.fvhd_op_dec_lm_argmax(_st(), _p(x), B, _p(nw), 1e-6, _p(W), V, H, _p(lg), _p(ids), _p(sv), _p(si)), "lm_argmax")
-    torch.cuda.synchronize()
-    assert bool((ids[B:] == -7).all())
-    if logits:
-        assert bool(torch.isnan(lbuf[B * V:]).all()), "the logits' guard tail was written"
-    return lg, ids[:B].clone()
-
-
 @pytest.mark.parametrize("V,H", [(151936, 896), (4112, 896), (152064, 3584)])
 @pytest.mark.parametrize("B", [17, 64])
 def test_dec_lm_argmax_wide_and_ties(lib, V, H, B):
@@ -297,56 +165,6 @@ def test_dec_lm_argmax_wide_and_ties(lib, V, H, B):
 
 
 # ---- model-level tests ---------------------------------------------------------------------------------------------------------------
-CONFIGS = {
-    "0.5B": dict(hidden_size=896, num_hidden_layers=2, num_attention_heads=14, num_key_value_heads=2, intermediate_size=4864, tie_word_embeddings=True),
-    "7B": dict(hidden_size=3584, num_hidden_layers=1, num_attention_heads=28, num_key_value_heads=4, intermediate_size=18944, tie_word_embeddings=False),
-}
-
-
-def _models(name, seed=0, vocab=4096):
-    """(bf16 model on the GPU, fp32 oracle on the same bf16-rounded weights) - test_gpu_decode.py's"""
-    from transformers import Qwen2Config, Qwen2ForCausalLM
-    torch.manual_seed(seed)
-    cfg = Qwen2Config(vocab_size=vocab, max_position_embeddings=4096, rope_theta=1e6, rms_norm_eps=1e-6, **CONFIGS[name])
-    m = Qwen2ForCausalLM(cfg).eval()
-    with torch.no_grad():
-        for p in m.parameters():
-            if p.dim() == 1:
-                p.add_(0.05 * torch.randn_like(p))
-    m16 = m.to("cuda", torch.bfloat16)
-    ref = Qwen2ForCausalLM(cfg).eval().to("cuda")
-    ref.load_state_dict({k: v.float() for k, v in m16.state_dict().items()})
-    return m16, ref
-
-
-def _prompt(ref, B, T, side, seed=0):
-    """test_gpu_decode.py's: row b has 3 b padded positions"""
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    e = 0.5 * torch.randn(B, T, ref.config.hidden_size, device="cuda", generator=g)
-    e = e.to(torch.bfloat16).float()
-    mask = torch.ones(B, T, device="cuda", dtype=torch.long)
-    for b in range(B):
-        npad = 3 * b
-        if npad:
-            if side == "left":
-                mask[b, :npad] = 0
-            else:
-                mask[b, T - npad:] = 0
-    return e, mask
-
-
-def _wide_prompt(ref, B, T, seed=0, distinct=None):
-    """B rows with mixed left padding ((5 b) % 13 positions); distinct = n: rows are copies of the first n (row b = row b % n)"""
-    n = B if distinct is None else distinct
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    e = (0.5 * torch.randn(n, T, ref.config.hidden_size, device="cuda", generator=g)).to(torch.bfloat16).float()
-    mask = torch.ones(n, T, device="cuda", dtype=torch.long)
-    for b in range(n):
-        mask[b, :(5 * b) % 13] = 0
-    idx = torch.arange(B, device="cuda") % n
-    return e[idx].contiguous(), mask[idx].contiguous()
-
-
 @pytest.mark.parametrize("name", ["0.5B", "7B"])
 def test_teacher_forced_steps_wide(name):
     from transformers import DynamicCache
@@ -384,26 +202,6 @@ def test_teacher_forced_steps_wide(name):
             lg, ids = gen.step(ids.clone())
             assert torch.equal(lg[:16], lg[16:32]) and torch.equal(lg[:16], lg[32:48]), f"step {i}: the copies differ between batch tiles"
             assert len({tuple(r) for r in lg[:16, :8].tolist()}) == 16                   # the 16 prompts themselves are distinct
-
-
-def _agree(ours, ref_seq, scores, delta=DELTA):
-    """token-for-token equality of every row up to the oracle's first step with a top-2 margin <= delta; -> steps compared per row"""
-    n = []
-    for b in range(ref_seq.shape[0]):
-        i = 0
-        while i < ref_seq.shape[1]:
-            top = scores[i][b].float().topk(2).values
-            if (top[0] - top[1]).item() <= delta:
-                break
-            assert i < ours.shape[1] and int(ours[b, i]) == int(ref_seq[b, i]), (b, i, ours[b].tolist(), ref_seq[b].tolist())
-            i += 1
-        n.append(i)
-    return n
-
-
-# test_gpu_decode.py's: prompt seeds (of `_prompt`, model seed 1) where the fp32 oracle's top-2 margin exceeds 2 * DELTA at every step of
-# every row for 12 new tokens
-GREEDY_SEEDS = {"left": [14, 83], "right": [64, 187]}
 
 
 @pytest.mark.parametrize("B", [48, 33])

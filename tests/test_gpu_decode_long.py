@@ -3,7 +3,7 @@ does not fill the chip): prompts of 285 and 600 tokens in a cache of 2304 positi
 first asserts, from att_plan's rule restated here, that it runs with more than one key slice - so the in-launch combine across slices,
 the len_add = 1 call form, the attention's counter offset and the scratch sizing of fvhd_llm_cache_reserve are what is measured.
 
-Oracle: transformers' Qwen2ForCausalLM in fp32 on the same bf16-rounded weights (tests/test_gpu_decode.py::_models).  Budget: the step
+Oracle: transformers' Qwen2ForCausalLM in fp32 on the same bf16-rounded weights (tests/llm_testlib.py::models).  Budget: the step
 budget of test_teacher_forced_steps, rel-L2 <= 2e-2 of the step logits, applied PER ROW.  The stock bf16 transformers model is measured
 against the same oracle on the same inputs and printed beside ours.
 
@@ -18,7 +18,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_gpu_decode import DELTA, _agree, _models, _prompt  # noqa: E402
+import llm_testlib as L  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -41,8 +41,8 @@ def _assert_split(m16, reserved_batch, cap=CAP):
 
 
 def _long_prompt(ref, B, T, seed=0):
-    """_prompt's embeddings with row b left-padded by 97 * b positions (capped below T): more than one key slice from row 2 on"""
-    e, mask = _prompt(ref, B, T, "left", seed=seed)
+    """prompt's embeddings with row b left-padded by 97 * b positions (capped below T): more than one key slice from row 2 on"""
+    e, mask = L.prompt(ref, B, T, "left", seed=seed)
     mask[:] = 1
     for b in range(B):
         mask[b, :min(97 * b, T - 1)] = 0
@@ -86,7 +86,7 @@ def _forced_steps(gen, m16, ref, e, mask, steps):
                                       ("7B", 1, 285), ("7B", 1, 600)])
 def test_teacher_forced_steps_in_the_split_regime(name, B, T):
     from ml_fastvlm_amd.qwen2_decode import Qwen2Generator
-    m16, ref = _models(name)
+    m16, ref = L.models(name)
     S, chunk = _assert_split(m16, B)
     e, mask = _long_prompt(ref, B, T)
     gen = Qwen2Generator.from_hf(m16, B, CAP)
@@ -97,10 +97,10 @@ def test_teacher_forced_steps_in_the_split_regime(name, B, T):
 
 def test_start_plus_steps_equals_one_long_prefill():
     from ml_fastvlm_amd.qwen2_decode import Qwen2Generator
-    m16, ref = _models("0.5B")
+    m16, ref = L.models("0.5B")
     B, T, k = 2, 285, 6
     _assert_split(m16, B)
-    e, _ = _prompt(ref, B, T, "left")
+    e, _ = L.prompt(ref, B, T, "left")
     ones = torch.ones(B, T, device="cuda", dtype=torch.long)
     gen = Qwen2Generator.from_hf(m16, B, CAP)
     _, _, fed = _forced_steps(gen, m16, ref, e, ones, k)
@@ -119,7 +119,7 @@ def test_started_batch_smaller_than_the_reserved_one_after_a_full_generation():
     on a freshly reserved batch-8 generator - the unused rows' stale keys, mask bytes and positions must not matter.  (Not compared with a
     batch-3 reservation: att_plan sizes its slices by the reserved batch.)"""
     from ml_fastvlm_amd.qwen2_decode import Qwen2Generator
-    m16, ref = _models("0.5B", seed=2)
+    m16, ref = L.models("0.5B", seed=2)
     _assert_split(m16, 8)
     e8, mask8 = _long_prompt(ref, 8, 600, seed=1)
     e3, mask3 = _long_prompt(ref, 3, 285, seed=2)
@@ -147,7 +147,7 @@ def test_restart_with_a_shorter_prompt():
     """start(600 tokens) + 8 steps, then start(285 tokens) on the same generator: the following steps are bit-identical to a fresh
     generator's - stale cache rows and mask bytes beyond the new length are not read"""
     from ml_fastvlm_amd.qwen2_decode import Qwen2Generator
-    m16, ref = _models("0.5B", seed=3)
+    m16, ref = L.models("0.5B", seed=3)
     B = 4
     _assert_split(m16, B)
     e6, mask6 = _long_prompt(ref, B, 600, seed=3)
@@ -173,7 +173,7 @@ def test_restart_with_a_shorter_prompt():
 
 def test_graph_replay_bit_identical_in_the_split_regime():
     from ml_fastvlm_amd.qwen2_decode import Qwen2Generator
-    m16, ref = _models("0.5B", seed=3)
+    m16, ref = L.models("0.5B", seed=3)
     B, T, N = 3, 285, 16
     _assert_split(m16, B)
     e, mask = _long_prompt(ref, B, T, seed=4)
@@ -203,10 +203,10 @@ LONG_GREEDY_SEED = 13      # the first prompt seed of 0, 1, 2, .. (model seed 1)
 
 
 def test_greedy_equals_transformers_generate_on_a_long_prompt():
-    """T = 285, B = 3, 12 new tokens under test_gpu_decode's _agree rule.  The prompt seed is one for which the fp32 oracle keeps a top-2
-    margin > 2 * DELTA for the first 8 steps of every row (asserted from the oracle's scores alone), so at least 24 tokens are compared"""
+    """T = 285, B = 3, 12 new tokens under the agree rule of tests/llm_testlib.py.  The prompt seed is one for which the fp32 oracle keeps a top-2
+    margin > 2 * L.DELTA for the first 8 steps of every row (asserted from the oracle's scores alone), so at least 24 tokens are compared"""
     from ml_fastvlm_amd.qwen2_decode import Qwen2Generator
-    m16, ref = _models("0.5B", seed=1)
+    m16, ref = L.models("0.5B", seed=1)
     B, T, new = 3, 285, 12
     _assert_split(m16, B)
     e, mask = _long_prompt(ref, B, T, seed=LONG_GREEDY_SEED)
@@ -214,10 +214,10 @@ def test_greedy_equals_transformers_generate_on_a_long_prompt():
         r = ref.generate(inputs_embeds=e, attention_mask=mask, max_new_tokens=new, do_sample=False, eos_token_id=None, pad_token_id=0,
                          output_scores=True, return_dict_in_generate=True)
     top = torch.stack(r.scores, 1).float().topk(2, -1).values
-    assert (top[:, :8, 0] - top[:, :8, 1]).min().item() > 2 * DELTA          # the seed's precondition (oracle only)
+    assert (top[:, :8, 0] - top[:, :8, 1]).min().item() > 2 * L.DELTA          # the seed's precondition (oracle only)
     gen = Qwen2Generator.from_hf(m16, B, CAP)
     with torch.no_grad():
         got = gen.greedy(e.to(torch.bfloat16), mask, None, max_new_tokens=new, eos_token_id=None, pad_token_id=0)
-    n = _agree(got, r.sequences, r.scores)
+    n = L.agree(got, r.sequences, r.scores)
     print(f"long-prompt greedy: steps compared per row {n}")
     assert min(n) >= 8 and sum(n) >= 24, n

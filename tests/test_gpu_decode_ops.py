@@ -5,8 +5,6 @@ Bound: the project's single-op budget  |got - want| <= 1e-2 |want| + 1e-2 rms(wa
 given scales from 0.05 to 20, a pooled rms would hide the small ones.  (The decode attention keeps P in fp32, so it takes the same 1e-2;
 the fp32 logits of the lm_head take the prefill tests' 2e-3.)  Exact cases (one-hot operands, single keys, planted ties) are compared bit
 for bit or to one bf16 ulp.  Every output is allocated with a sentinel-filled guard: rows >= B and the tail must stay untouched."""
-import ctypes as C
-import math
 import os
 import sys
 
@@ -15,79 +13,15 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import decode_reference as R  # noqa: E402
+from llm_testlib import (GEMM_SHAPES, SENT, lib,  # noqa: E402,F401
+                         close_by_batch_row as _close, dec_attention as _attention, dec_gemm as _gemm, dec_lm_argmax as _lm,
+                         guard_intact as _guard_intact, guarded_rows as _guarded, lowest_argmax as _lowest_argmax,
+                         padded_mask as _padded_mask, ptr as _p, row_scales as _row_scales, stream as _st)
 
 pytestmark = pytest.mark.gpu
 
-SENT = 0x7B3D                  # bf16 bit pattern of the guard fill (1.23e36): no kernel output takes it by chance
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from ml_fastvlm_amd import _lib
-    return _lib.load()
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _st():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _violations(got, want, rtol=1e-2, atol_rms=1e-2):
-    """-> (elements outside |err| <= rtol |want| + atol_rms rms(want_row), the largest err / bound); rms over everything but dim 0"""
-    got, want = got.double().reshape(got.shape[0], -1), want.double().reshape(want.shape[0], -1)
-    assert got.shape == want.shape, (got.shape, want.shape)
-    assert bool(torch.isfinite(got).all()), "non-finite output"
-    rms = want.pow(2).mean(-1, keepdim=True).sqrt()
-    err, bound = (got - want).abs(), rtol * want.abs() + atol_rms * rms
-    ratio = torch.where(err > 0, err / bound.clamp_min(1e-300), torch.zeros_like(err))
-    return int((err > bound).sum()), float(ratio.max())
-
-
-def _close(got, want, what, rtol=1e-2, atol_rms=1e-2):
-    bad, worst = _violations(got, want, rtol, atol_rms)
-    assert bad == 0, f"{what}: {bad} of {want.numel()} elements out of tolerance, worst err / bound {worst:.3g}"
-    return worst
-
-
-def _row_scales(B, g):
-    """distinct factors spanning 0.05 .. 20, shuffled"""
-    s = torch.logspace(math.log10(0.05), math.log10(20.0), 16, device="cuda", dtype=torch.float32)[torch.randperm(16, device="cuda", generator=g)]
-    return s[:B] if B > 1 else s.new_tensor([20.0])
-
-
-def _guarded(width, B):
-    """a [16, width] bf16 buffer + 64 guard elements, filled with the sentinel -> (buffer as int16, the [B, width] view of its head)"""
-    buf = torch.full((16 * width + 64,), SENT, device="cuda", dtype=torch.int16)
-    return buf, buf.view(torch.bfloat16)[:B * width].view(B, width)
-
-
-def _guard_intact(buf, used):
-    return bool((buf[used:] == SENT).all())
-
 
 # ---- 1. the weight-streaming GEMM ---------------------------------------------------------------------------------------------------
-def _gemm(lib, epi, x, nw, W, resid, splits, alias=False):
-    """one fvhd_op_dec_gemm launch -> (out [B, width] clone, guard intact, counters zero).  splits == 1: NULL scratch."""
-    from ml_fastvlm_amd import _lib
-    B, K = x.shape
-    N = W.shape[0]
-    swiglu = epi == "swiglu"
-    width = N // 2 if swiglu else N
-    buf, out = _guarded(width, B)
-    part = torch.empty(splits * N * 16, device="cuda") if splits > 1 else None
-    cnt = torch.zeros((N // 16 + 3) // 4, device="cuda", dtype=torch.int32) if splits > 1 else None
-    if alias:
-        out.copy_(resid)
-        resid = out
-    _lib.check(lib.fvhd_op_dec_gemm(_st(), _lib.EPI_SWIGLU if swiglu else _lib.EPI_RESID, _p(x), B, _p(nw), 1e-6, _p(W), N, K, _p(resid), _p(out),
-                                    _p(part), _p(cnt), splits), "dec_gemm")
-    torch.cuda.synchronize()
-    return out.clone(), _guard_intact(buf, B * width), cnt is None or int(cnt.abs().sum()) == 0
-
-
 def _gemm_inputs(B, N, K, seed):
     g = torch.Generator(device="cuda").manual_seed(seed)
     x = (torch.randn(B, K, device="cuda", generator=g) * _row_scales(B, g)[:, None]).to(torch.bfloat16)
@@ -106,15 +40,10 @@ def test_dec_gemm_every_batch_size(lib, B, epi):
     for norm in (nw, None):
         want = R.dec_gemm_ref(x, norm, 1e-6, W, resid, epi)
         for splits in (1, 2):
-            got, guard, zero = _gemm(lib, epi, x, norm, W, resid, splits)
+            got = _gemm(lib, epi, x, norm, W, resid, splits)          # (asserts the guard and the counters)
             _close(got, want, f"B={B} {epi} norm={norm is not None} splits={splits}")
-            assert guard and zero
 
 
-# the ragged last workgroup, N / 16 % 4 = 1 (N = 16, 80, 912, 4880), 2 (32, 928, 4896) and 3 (48, 4912), beside the model widths
-# (remainder 0); K in {128, 256, 896, 4864} beside the model depths
-GEMM_SHAPES = [(16, 128), (32, 128), (48, 256), (80, 896), (912, 4864), (928, 896), (4880, 896), (4896, 256), (4912, 4864), (896, 896), (896, 4864), (9728, 896), (1536, 8960), (17920, 1536),
-               (3584, 18944), (37888, 3584)]
 ALL_SPLITS = (1, 2, 3, 4, 7, 16, 64)
 
 
@@ -130,18 +59,16 @@ def test_dec_gemm_elementwise(lib, N, K, epi):
         for norm in (nw, None):
             want = R.dec_gemm_ref(x, norm, 1e-6, W, resid, epi)
             for splits in ((1, 7, 16) if big else ALL_SPLITS):
-                got, guard, zero = _gemm(lib, epi, x, norm, W, resid, splits)
+                got = _gemm(lib, epi, x, norm, W, resid, splits)
                 worst = max(worst, _close(got, want, f"N={N} K={K} B={B} {epi} norm={norm is not None} splits={splits}"))
-                assert guard, "rows >= B or the guard tail were written"
-                assert zero, "counters not back at zero"
-            again, _, _ = _gemm(lib, epi, x, norm, W, resid, 7)
-            first, _, _ = _gemm(lib, epi, x, norm, W, resid, 7)
+            again = _gemm(lib, epi, x, norm, W, resid, 7)
+            first = _gemm(lib, epi, x, norm, W, resid, 7)
             assert torch.equal(again, first)                      # deterministic split-K
             if epi == "resid":                                    # the model's form: resid IS out
                 for splits in (1, 4):
-                    plain, _, _ = _gemm(lib, epi, x, norm, W, resid, splits)
-                    alias, guard, _ = _gemm(lib, epi, x, norm, W, resid, splits, alias=True)
-                    assert torch.equal(plain, alias) and guard
+                    plain = _gemm(lib, epi, x, norm, W, resid, splits)
+                    alias = _gemm(lib, epi, x, norm, W, resid, splits, alias=True)
+                    assert torch.equal(plain, alias)
     print(f"dec_gemm N={N} K={K} {epi}: worst err / bound {worst:.3f}")
 
 
@@ -162,19 +89,17 @@ def test_dec_gemm_one_hot_exact(lib, N, K):
         zero = torch.zeros(B, N, device="cuda", dtype=torch.bfloat16)
         want = W[:, ks].t().contiguous()
         for splits in ALL_SPLITS:
-            got, guard, z = _gemm(lib, "resid", x, None, W, zero, splits)
+            got = _gemm(lib, "resid", x, None, W, zero, splits)
             assert torch.equal(got, want), (B, splits, int((got != want).sum()))
-            assert guard and z
         Wg = W.clone()
         Wg[0::2] = torch.randint(-60, 61, (N // 2, K), device="cuda", generator=g).to(torch.bfloat16)
         col = Wg[:, ks].t().double()
         wb = (torch.nn.functional.silu(col[:, 0::2]) * col[:, 1::2]).to(torch.bfloat16)
         for splits in ALL_SPLITS:
-            got, guard, z = _gemm(lib, "swiglu", x, None, Wg, None, splits)
+            got = _gemm(lib, "swiglu", x, None, Wg, None, splits)
             gi, wi = got.view(torch.int16).int(), wb.view(torch.int16).int()
             ok = ((gi - wi).abs() <= 1) | ((got == 0) & (wb == 0))
             assert bool(ok.all()), (B, splits, int((~ok).sum()))
-            assert guard and z
 
 
 # ---- 2. q|k|v + rope + cache append ---------------------------------------------------------------------------------------------------
@@ -223,37 +148,6 @@ def test_dec_qkv_elementwise_and_cache_untouched(lib, nh, nkv, hd, H, B):
 
 
 # ---- 3. single-query attention over the cache ------------------------------------------------------------------------------------------
-def _attention(lib, q, kc, vc, mask, length, splits):
-    from ml_fastvlm_amd import _lib
-    B, nkv, cap, hd = kc.shape
-    nh = q.shape[1] // hd
-    buf, out = _guarded(nh * hd, B)
-    ln = torch.tensor([length], device="cuda", dtype=torch.int32)
-    part = torch.empty(B * nh * splits * (hd + 2), device="cuda") if splits > 1 else None
-    cnt = torch.zeros(B * nh, device="cuda", dtype=torch.int32) if splits > 1 else None
-    _lib.check(lib.fvhd_op_dec_attention(_st(), _p(q), _p(kc), _p(vc), _p(mask), _p(out), B, nh, nkv, hd, cap, _p(ln), _p(part), _p(cnt), splits),
-               "dec_attention")
-    torch.cuda.synchronize()
-    assert _guard_intact(buf, B * nh * hd), "rows >= B or the guard tail were written"
-    assert cnt is None or int(cnt.abs().sum()) == 0, "counters not back at zero"
-    return out.clone()
-
-
-def _padded_mask(B, cap, length, side, step=None):
-    """row b: step * (b + 1) padded keys (capped below the length), step 150 for a long cache (whole 64-key blocks and whole 128-key
-    slices masked, from row 0 on) and a fifth of a short one"""
-    if step is None:
-        step = 150 if length > 600 else max(length // 5, 1)
-    mask = torch.zeros(B, cap, device="cuda", dtype=torch.uint8)
-    for b in range(B):
-        npad = min(step * (b + 1), length - 1)
-        if side == "left":
-            mask[b, npad:length] = 1
-        else:
-            mask[b, :length - npad] = 1
-    return mask
-
-
 ATT_LENGTHS = [(1, 64), (63, 64), (64, 64), (65, 200), (285, 2304), (2304, 2304)]
 ATT_SPLITS = (1, 2, 9, 32)
 
@@ -334,30 +228,6 @@ def test_dec_attention_large_score_spread(lib, hd, nh, nkv, where):
 
 
 # ---- 4. lm_head + argmax -------------------------------------------------------------------------------------------------------------
-def _lm(lib, x, nw, W, logits=True):
-    from ml_fastvlm_amd import _lib
-    B, H = x.shape
-    V = W.shape[0]
-    lbuf = torch.full((B * V + 64,), float("nan"), device="cuda") if logits else None
-    lg = lbuf[:B * V].view(B, V) if logits else None
-    ids = torch.full((B + 4,), -7, device="cuda", dtype=torch.long)
-    nblk = (V // 16 + 3) // 4
-    sv = torch.empty(nblk * 16, device="cuda")
-    si = torch.empty(nblk * 16, device="cuda", dtype=torch.int32)
-    _lib.check(lib.fvhd_op_dec_lm_argmax(_st(), _p(x), B, _p(nw), 1e-6, _p(W), V, H, _p(lg), _p(ids), _p(sv), _p(si)), "lm_argmax")
-    torch.cuda.synchronize()
-    assert bool((ids[B:] == -7).all())
-    if logits:
-        assert bool(torch.isnan(lbuf[B * V:]).all()), "the logits' guard tail was written"
-    return lg, ids[:B].clone()
-
-
-def _lowest_argmax(lg):
-    V = lg.shape[1]
-    idx = torch.arange(V, device=lg.device)[None].expand_as(lg)
-    return torch.where(lg == lg.max(-1, keepdim=True).values, idx, torch.full_like(idx, V)).min(-1).values
-
-
 @pytest.mark.parametrize("V,H", [(151936, 896), (151936, 1536), (152064, 3584), (16, 896), (4112, 896), (4128, 896), (65552, 1536)])
 @pytest.mark.parametrize("B", [1, 16])
 def test_dec_lm_argmax_elementwise_and_ties(lib, V, H, B):

@@ -1,73 +1,33 @@
 """Qwen2 prefill and decode steps on e4m3 weights (`weights="fp8_e4m3"`, include/fvhd.h version 504) against torch fp32 / transformers.
 
-Oracle: the pattern of tests/test_gpu_decode.py with ONE change - every 2-D weight of the decoder stack and lm_head (for a tied model that
-is the embedding table too) is replaced by its dequantised value, `quantize_rows_e4m3` codes * scale, before the bf16 and fp32 copies are
+Oracle: the models of tests/test_gpu_decode.py (tests/llm_testlib.py::models) with ONE change, quantised=True - every 2-D weight of the
+decoder stack and lm_head (for a tied model that is the embedding table too) is replaced by its dequantised value,
+`quantize_rows_e4m3` codes * scale, before the bf16 and fp32 copies are
 made.  Those values are exact in bf16 and quantise to themselves, so the fp32 oracle holds exactly the weights the library computes with:
 what is left is the bf16 arithmetic of the steps, and the budgets are those of the bf16 tests (teacher-forced logits rel-L2 2e-2, greedy
 tokens equal where the oracle's top-2 margin exceeds DELTA)."""
 import ctypes as C
+import os
+import sys
 
 import pytest
 import torch
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import llm_testlib as L  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
-DELTA = 0.02          # as tests/test_gpu_decode.py
 W8 = "fp8_e4m3"
 
-CONFIGS = {
-    "0.5B": dict(hidden_size=896, num_hidden_layers=2, num_attention_heads=14, num_key_value_heads=2, intermediate_size=4864, tie_word_embeddings=True),
-    "1.5B": dict(hidden_size=1536, num_hidden_layers=1, num_attention_heads=12, num_key_value_heads=2, intermediate_size=8960, tie_word_embeddings=True),
-    "7B": dict(hidden_size=3584, num_hidden_layers=1, num_attention_heads=28, num_key_value_heads=4, intermediate_size=18944, tie_word_embeddings=False),
-}
 
-
-def rel(a, b):
-    a, b = a.float(), b.float()
-    return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
-
-
-def _models(name, seed=0, vocab=4096, device="cuda", quantised=True, layers=None):
-    """(bf16 model, fp32 oracle on the same weights); quantised: the matrices hold dequantised e4m3 values (an exact-weight oracle)"""
-    from transformers import Qwen2Config, Qwen2ForCausalLM
-    from ml_fastvlm_amd import quantize_rows_e4m3
-    torch.manual_seed(seed)
-    kw = dict(CONFIGS[name])
-    if layers:
-        kw["num_hidden_layers"] = layers
-    cfg = Qwen2Config(vocab_size=vocab, max_position_embeddings=4096, rope_theta=1e6, rms_norm_eps=1e-6, **kw)
-    m = Qwen2ForCausalLM(cfg).eval()
-    with torch.no_grad():
-        for p in m.parameters():                                  # biases and norm weights away from their trivial init
-            if p.dim() == 1:
-                p.add_(0.05 * torch.randn_like(p))
-    m16 = m.to(device, torch.bfloat16)
-    if quantised:
-        emb = m16.get_input_embeddings().weight
-        with torch.no_grad():
-            for p in m16.parameters():
-                if p.dim() == 2 and (p is not emb or cfg.tie_word_embeddings):
-                    codes, scale = quantize_rows_e4m3(p)
-                    p.copy_((codes.float() * scale[:, None]).to(torch.bfloat16))
-    ref = Qwen2ForCausalLM(cfg).eval().to(device)
-    ref.load_state_dict({k: v.float() for k, v in m16.state_dict().items()})
-    return m16, ref
+def _models(name, seed=0, quantised=True, layers=None):
+    return L.models(name, seed=seed, quantised=quantised, layers=layers)
 
 
 def _prompt(ref, B, T, side, seed=0):
-    """as tests/test_gpu_decode.py, drawn on the CPU (the seeds below were chosen there)"""
-    g = torch.Generator().manual_seed(seed)
-    e = 0.5 * torch.randn(B, T, ref.config.hidden_size, generator=g)
-    e = e.to(torch.bfloat16).float().to(ref.device)
-    mask = torch.ones(B, T, device=ref.device, dtype=torch.long)
-    for b in range(B):
-        npad = 3 * b
-        if npad:
-            if side == "left":
-                mask[b, :npad] = 0
-            else:
-                mask[b, T - npad:] = 0
-    return e, mask
+    """drawn on the CPU (the seeds below were chosen there)"""
+    return L.prompt(ref, B, T, side, seed=seed, draw_on="cpu")
 
 
 def _teacher_forced(gen, ref, e, mask, steps):
@@ -80,7 +40,7 @@ def _teacher_forced(gen, ref, e, mask, steps):
         lg, _ = gen.start(e.to(torch.bfloat16), mask, pos)
         out = ref(inputs_embeds=e, attention_mask=mask, position_ids=pos, past_key_values=DynamicCache(), use_cache=True)
         want = out.logits[:, -1]
-        errs = [rel(lg, want)]
+        errs = [L.rel(lg, want)]
         am, p = mask, pos
         emb_ref = ref.get_input_embeddings()
         for _ in range(steps):
@@ -90,7 +50,7 @@ def _teacher_forced(gen, ref, e, mask, steps):
             p = p[:, -1:] + 1
             out = ref(inputs_embeds=emb_ref(tok)[:, None], attention_mask=am, position_ids=p, past_key_values=out.past_key_values, use_cache=True)
             want = out.logits[:, -1]
-            errs.append(rel(lg, want))
+            errs.append(L.rel(lg, want))
     return errs
 
 
@@ -111,7 +71,7 @@ def test_teacher_forced_steps_e4m3(name, B):
 
 # prompt seeds (of `_prompt`, model seed 1, quantised) where the fp32 oracle's top-2 margin exceeds 2 * DELTA at EVERY step of every row for
 # 12 new tokens (the first two of seeds 0, 1, 2, ... each) - chosen from the oracle alone (on the CPU), as GREEDY_SEEDS of
-# tests/test_gpu_decode.py was
+# tests/llm_testlib.py was
 GREEDY_SEEDS = {"left": [198, 271], "right": [158, 440]}
 
 
@@ -130,7 +90,7 @@ def test_greedy_equals_transformers_generate_e4m3(side):
             got = gen.greedy(e.to(torch.bfloat16), mask, None, max_new_tokens=new, eos_token_id=None, pad_token_id=0)
             eager = gen.greedy(e.to(torch.bfloat16), mask, None, max_new_tokens=new, eos_token_id=None, pad_token_id=0, graph=False)
         top = torch.stack(r.scores, 1).float().topk(2, -1).values
-        assert (top[..., 0] - top[..., 1]).min().item() > DELTA          # the seed's precondition (oracle only)
+        assert (top[..., 0] - top[..., 1]).min().item() > L.DELTA          # the seed's precondition (oracle only)
         assert torch.equal(got.cpu(), r.sequences.cpu()), (got.tolist(), r.sequences.tolist())
         assert torch.equal(got, eager)
 

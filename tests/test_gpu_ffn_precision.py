@@ -15,6 +15,8 @@ dw7x7 kernels reduce max |A| per block and call so that a block whose PROVEN bou
 bf16-operand form - asynchronously (one batch late, with a warning) or, in "strict" mode, before the call returns.  The second
 checkpoint below (`_hot_weights_state_dict`) saturates through its fc1 WEIGHTS, i.e. only on real activations, which is what the guard
 and the audit have to find at run time."""
+import os
+import sys
 import warnings
 from types import SimpleNamespace
 
@@ -24,6 +26,9 @@ import torch
 import ml_fastvlm_amd as fv
 from ml_fastvlm_amd import _lib, synth
 from oracle import fastvithd_oracle as O
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import llm_testlib as L  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -61,11 +66,6 @@ def _hot_step(tower):
     return [i for i, (kind, stage, block, *_r) in enumerate(ctx.steps()) if kind == "repmixer_block" and (stage, block) == (1, 3)][0]
 
 
-def _metrics(got, want):
-    a, b = got.double().cpu().flatten(), want.double().cpu().flatten()
-    return ((a - b).norm() / b.norm()).item(), torch.nn.functional.cosine_similarity(a, b, dim=0).item()
-
-
 def test_audit_finds_the_saturating_block_and_the_switch_restores_parity():
     sd = _hot_state_dict()
     x = synth.synthetic_images(2, 256, seed=5)
@@ -82,7 +82,7 @@ def test_audit_finds_the_saturating_block_and_the_switch_restores_parity():
     # ... so the failure this test is about has to be forced
     ctx.set_ffn_precision(hot_step, _lib.FFN_HALF)
     before = tower(xd).float().cpu()
-    rel0, cos0 = _metrics(before, want)
+    rel0, cos0, _ = L.metrics(before, want)
 
     with warnings.catch_warnings(record=True) as caught:
         warnings.simplefilter("always")
@@ -96,7 +96,7 @@ def test_audit_finds_the_saturating_block_and_the_switch_restores_parity():
     assert any("ConvFFN block" in str(w.message) for w in caught), "a switch is reported as a warning"
 
     after = tower(xd).float().cpu()
-    rel1, cos1 = _metrics(after, want)
+    rel1, cos1, _ = L.metrics(after, want)
     print(f"fc1 output up to {hot[0]['max_abs_fc1']:.0f} in {HOT_BLOCK}: half-precision hidden rel-L2 {rel0:.3e} cos {cos0:.6f}  ->  "
           f"after the audit (that block on the bf16-operand form) rel-L2 {rel1:.3e} cos {cos1:.6f}")
     assert rel1 <= 1.5e-2 and cos1 >= 0.9998, (rel1, cos1)
@@ -139,7 +139,7 @@ def test_every_block_on_the_bf16_form_by_configuration():
         ctx = t._context()
         n_bf16 = sum(ctx.ffn_precision(i) == _lib.FFN_BF16 for i in range(len(ctx.steps())))
         assert n_bf16 == (38 if prec == "bf16" else 0)
-        rel, cos = _metrics(outs[prec], want)
+        rel, cos, _ = L.metrics(outs[prec], want)
         print(f"mm_vision_ffn_precision={prec}: vs fp32 oracle rel-L2 {rel:.3e} cos {cos:.6f}")
         assert rel <= 1e-2 and cos >= 0.9999, (prec, rel, cos)
     with pytest.raises(ValueError):
@@ -168,7 +168,7 @@ def test_the_default_configuration_is_range_safe_on_the_first_call():
     with warnings.catch_warnings(record=True) as caught:
         warnings.simplefilter("always")
         first = tower(x.to(DEV)).float().cpu()
-    rel, cos = _metrics(first, want)
+    rel, cos, _ = L.metrics(first, want)
     print(f"default configuration, fc1 output up to {peak:.3g}: first call rel-L2 {rel:.3e} cos {cos:.6f}")
     assert rel <= 1.5e-2 and cos >= 0.9998, (rel, cos)
     assert any("ConvFFN block" in str(w.message) for w in caught), "the audit of the first batch reports the switch"
@@ -183,7 +183,7 @@ def test_the_default_configuration_is_range_safe_on_the_first_call():
     assert torch.equal(again, first)
     # the forced half form is visibly wrong on this checkpoint
     bad = _tower(sd, mm_vision_ffn_precision="half", mm_vision_range_guard="off")(x.to(DEV)).float().cpu()
-    rel_bad, _ = _metrics(bad, want)
+    rel_bad, _, _ = L.metrics(bad, want)
     assert rel_bad >= 3.0 * rel, (rel_bad, rel)
 
 
@@ -209,8 +209,8 @@ def test_range_guard_catches_an_image_hotter_than_the_calibration_batch():
     msgs = [str(w.message) for w in caught if "range guard" in str(w.message)]
     assert len(msgs) == 1 and f"({hot}," in msgs[0], msgs
     assert ctx.ffn_precision(hot) == _lib.FFN_BF16
-    rel1, _ = _metrics(first, want)
-    rel2, cos2 = _metrics(second, want)
+    rel1, _, _ = L.metrics(first, want)
+    rel2, cos2, _ = L.metrics(second, want)
     print(f"asynchronous guard: hot batch on the half form rel-L2 {rel1:.3e}; next call rel-L2 {rel2:.3e} cos {cos2:.6f}")
     assert rel2 <= 1.5e-2 and cos2 >= 0.9998 and rel1 >= 3.0 * rel2
     assert torch.equal(second, third)
@@ -253,7 +253,7 @@ def test_auto_precision_audits_the_first_batches():
         warnings.simplefilter("always")
         first = tower(x.to(DEV)).float().cpu()
     assert any("ConvFFN block" in str(w.message) for w in caught)
-    rel, cos = _metrics(first, want)
+    rel, cos, _ = L.metrics(first, want)
     assert rel <= 1.5e-2 and cos >= 0.9998, (rel, cos)
     assert tower._ffn_audits_left == 1
     with warnings.catch_warnings(record=True) as caught:

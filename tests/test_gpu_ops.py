@@ -6,8 +6,6 @@ operands; the kernels accumulate in fp32 and round once on store, so the budget 
 rounding of the result (2^-9 relative) plus fp32 accumulation-order noise:
     |got - want| <= 1.0e-2 * |want| + 1.0e-2 * rms(want)
 """
-import ctypes as C
-
 import os
 import sys
 
@@ -18,20 +16,12 @@ import torch.nn.functional as F
 from ml_fastvlm_amd import _lib
 from oracle import fastvithd_oracle as O
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from llm_testlib import close_pooled as _close, ptr as _p, stream  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-
-
-def _close(got, want, rtol=1e-2, atol_rms=1e-2, what=""):
-    got, want = got.float().cpu(), want.float().cpu()
-    assert got.shape == want.shape, (got.shape, want.shape)
-    assert torch.isfinite(got).all(), f"{what}: non-finite output"
-    rms = want.pow(2).mean().sqrt().item()
-    err = (got - want).abs()
-    bound = rtol * want.abs() + atol_rms * rms
-    bad = (err > bound).sum().item()
-    assert bad == 0, f"{what}: {bad}/{err.numel()} elements out of tolerance, max err {err.max():.4g}, rms {rms:.4g}"
 
 
 def _bf(x):
@@ -39,11 +29,7 @@ def _bf(x):
 
 
 def _stream():
-    return C.c_void_p(torch.cuda.current_stream(torch.device(DEV)).cuda_stream)
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+    return stream(DEV)
 
 
 def _rand(*shape, seed=0, scale=1.0):

@@ -26,7 +26,6 @@ flat rows (q scale 0.05, hundreds of keys of equal weight, every P rounded to 8 
 deviation of ~0.08 of the bound and the maximum grows with the number of elements compared.  No measured attention ratio exceeds 0.5; one
 that did would be worth a look before anything else.
 """
-import ctypes as C
 import math
 import os
 import sys
@@ -36,30 +35,14 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import prefill_reference as R  # noqa: E402
+from llm_testlib import (CONFIGS, lib,  # noqa: E402,F401
+                         check as _check, compare_prefill, ptr as _p, qwen2_cfg, qwen2_model, stream as _st)
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
 THETA = 1e6
 
-
-@pytest.fixture(scope="module")
-def lib():
-    from ml_fastvlm_amd import _lib
-    return _lib.load()
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _st():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _check(code, what):
-    from ml_fastvlm_amd import _lib
-    _lib.check(code, what)
 
 
 # ---- attention ---------------------------------------------------------------------------------------------------------------------------
@@ -351,9 +334,8 @@ def test_qkv_splitk_rope_equals_reduce_then_rope(lib, splits):
 
 # ---- the whole prefill -------------------------------------------------------------------------------------------------------------------
 def _tiny():
-    import test_qwen2_prefill as TP
-    cfg = TP._cfg(hidden=128, layers=2, heads=2, kv=1, inter=256, vocab=512)
-    m = TP._model(cfg, seed=4)
+    cfg = qwen2_cfg(hidden=128, layers=2, heads=2, kv=1, inter=256, vocab=512)
+    m = qwen2_model(cfg, seed=4)
     m.load_state_dict({k: (v.to(torch.bfloat16).float() if v.dim() == 2 else v) for k, v in m.state_dict().items()})
     return cfg, m.to(DEV)
 
@@ -441,8 +423,7 @@ def test_prefill_workspace_history_does_not_leak():
 @pytest.mark.parametrize("B,T", [(2, 128), (1, 257)])
 def test_prefill_row_count_at_the_256_row_padding_edge(B, T):
     """B*T = 256 (no padding row) and 257 (255 of them) against transformers at the budgets of tests/test_qwen2_prefill.py"""
-    import test_qwen2_prefill as TP
-    TP._compare_prefill(TP._cfg(hidden=128, layers=2, heads=2, kv=1, inter=256, vocab=512), B, T, "left", seed=6, layers_tol=1.5e-2)
+    compare_prefill(qwen2_cfg(hidden=128, layers=2, heads=2, kv=1, inter=256, vocab=512), B, T, "left", seed=6, layers_tol=1.5e-2)
 
 
 @pytest.mark.parametrize("name", ["0.5B", "7B"])
@@ -451,10 +432,9 @@ def test_prefill_e4m3_weights_give_the_bits_of_bf16_on_dequantised_values(name):
     themselves): the "fp8_e4m3" context unpacks exactly the bf16 context's matrices and runs the same GEMMs on them - identical bits for
     logits, hidden states and the KV cache.  The only test that separates w8_unpack_kernel mode 0 from a nearly right one."""
     from transformers import Qwen2Config, Qwen2ForCausalLM
-    import test_gpu_decode_w8 as W8
     from ml_fastvlm_amd import quantize_rows_e4m3
     from ml_fastvlm_amd.qwen2_prefill import Qwen2Prefill
-    kw = dict(W8.CONFIGS[name], num_hidden_layers=2)
+    kw = dict(CONFIGS[name], num_hidden_layers=2)
     cfg = Qwen2Config(vocab_size=4096, max_position_embeddings=4096, rope_theta=1e6, rms_norm_eps=1e-6, **kw)
     torch.manual_seed(5)
     with torch.device(DEV):
@@ -473,9 +453,9 @@ def test_prefill_e4m3_weights_give_the_bits_of_bf16_on_dequantised_values(name):
     mask = torch.ones(B, T, device=DEV, dtype=torch.long)
     mask[1, :3] = 0
     pos = torch.clamp(torch.cumsum(mask, 1) - 1, min=0)
-    p8 = Qwen2Prefill.from_hf(m, weights=W8.W8)
+    p8 = Qwen2Prefill.from_hf(m, weights="fp8_e4m3")
     p16 = Qwen2Prefill.from_hf(m)
-    assert p8.weight_format == W8.W8 and p16.weight_format == "bf16"
+    assert p8.weight_format == "fp8_e4m3" and p16.weight_format == "bf16"
     a, b = _run(p8, x, mask, pos), _run(p16, x, mask, pos)
     assert bool(torch.isfinite(b[0]).all()) and float(b[0].abs().max()) > 0
     assert torch.equal(a[0], b[0]), f"logits: {int((a[0] != b[0]).sum())} of {a[0].numel()} differ"

@@ -16,6 +16,7 @@ as `oracle/_ref/reference_llava.zip` (git-ignored, shipped with the tree like li
 MIOpen is switched off for the reference runs (`torch.backends.cudnn.flags(enabled=False)`: ATen's native HIP convolutions) so a
 fresh box does not spend minutes compiling MIOpen kernels; the arithmetic is fp32 either way.
 """
+import os
 import sys
 from types import SimpleNamespace
 
@@ -26,19 +27,14 @@ import ml_fastvlm_amd as fv
 from ml_fastvlm_amd import synth
 from oracle import ref_import
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import llm_testlib as L  # noqa: E402
+
 pytestmark = [pytest.mark.gpu,
               pytest.mark.skipif(not ref_import.reference_available(),
                                  reason="reference not staged (run __graft_entry__.build() where /root/reference is mounted)")]
 DEV = "cuda:0"
 ARGS = SimpleNamespace(unfreeze_mm_vision_tower=False)
-
-
-def _metrics(got, want):
-    got, want = got.double().cpu().flatten(), want.double().cpu().flatten()
-    rel = ((got - want).norm() / want.norm()).item()
-    cos = torch.nn.functional.cosine_similarity(got, want, dim=0).item()
-    mx = ((got - want).abs().max() / want.abs().max()).item()
-    return rel, cos, mx
 
 
 @pytest.mark.parametrize("res,batch", [(256, 2), (1024, 4)])
@@ -55,7 +51,7 @@ def test_our_tower_vs_the_reference_tower_on_pytorch_rocm(res, batch):
     ours = ours.to(DEV, torch.bfloat16)
     got = ours(x)                                                # fp32 images in -> fp32 tokens out, bf16 arithmetic inside
     assert got.shape == want.shape == (batch, (res // 64) ** 2, 3072) and got.dtype == want.dtype == torch.float32
-    rel, cos, mx = _metrics(got, want)
+    rel, cos, mx = L.metrics(got, want)
     print(f"ours vs reference-on-GPU (fp32) r{res} B={batch}: rel-L2 {rel:.3e} cos {cos:.6f} max-abs/absmax {mx:.3e}")
     assert rel <= 1e-2 and cos >= 0.9999 and mx <= 3e-2, (rel, cos, mx)
     # the reference's own properties our tower mirrors
@@ -165,7 +161,7 @@ def test_reference_generate_with_our_tower_underneath():
             lq.LlavaQwen2ForCausalLM.forward = lq.LlavaQwen2ForCausalLM.forward._fvhd_orig
             seq_s, sc_s = gen(bf, ids, m_)                                           # same bf16 model, stock prefill
             fv.install_into_llava(splice=True, prefill=True)
-            rel, cos, _ = _metrics(sc_k[0], sc_s[0])
+            rel, cos, _ = L.metrics(sc_k[0], sc_s[0])
             print(f"bf16 model, {which}: first-token logits kernels vs stock bf16 prefill rel-L2 {rel:.3e} cos {cos:.6f}; tokens {seq_k.tolist()} vs {seq_s.tolist()}")
             assert rel <= 4e-2 and cos >= 0.999, (which, rel, cos)
             for b in range(3):                                                       # greedy tokens agree while every margin exceeds the error
@@ -179,11 +175,11 @@ def test_reference_generate_with_our_tower_underneath():
         (enc_builder.build_vision_tower, arch.build_vision_tower, arch.LlavaMetaForCausalLM.encode_images,
          arch.LlavaMetaForCausalLM.prepare_inputs_labels_for_multimodal, lq.LlavaQwen2ForCausalLM.forward) = saved
     for name, a, b in (("first token, prefill kernels", logits_p, logits_ref), ("second token (stock decode on our KV cache)", logits2_p, logits2_ref)):
-        rel, cos, mx = _metrics(a, b)
+        rel, cos, mx = L.metrics(a, b)
         print(f"{name}: logits vs the un-patched reference model rel-L2 {rel:.3e} cos {cos:.6f}")
         if name.startswith("first") or torch.equal(seq_p[:, 0], seq_ref[:, 0]):      # the second step is comparable only after the same first token
             assert rel <= 4e-2 and cos >= 0.999, (name, rel, cos)
-    rel, cos, mx = _metrics(logits, logits_ref)
+    rel, cos, mx = L.metrics(logits, logits_ref)
     print(f"first-token logits, patched vs un-patched reference model: rel-L2 {rel:.3e} cos {cos:.6f} max-abs/absmax {mx:.3e}")
     assert logits.shape == logits_ref.shape == (3, 1024)
     assert rel <= 3e-2 and cos >= 0.999, (rel, cos, mx)
@@ -238,7 +234,7 @@ def test_drop_in_defaults_are_range_safe_on_a_saturating_checkpoint():
         with torch.inference_mode(), warnings.catch_warnings(record=True) as caught:
             warnings.simplefilter("always")
             got = model.encode_images(images).float().cpu()                          # FIRST call
-        rel, cos, mx = _metrics(got, want)
+        rel, cos, mx = L.metrics(got, want)
         print(f"saturating checkpoint through install_into_llava() defaults: first encode_images rel-L2 {rel:.3e} cos {cos:.6f}")
         assert rel <= 1.5e-2 and cos >= 0.9998, (rel, cos, mx)
         tower = model.get_vision_tower()

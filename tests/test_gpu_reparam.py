@@ -8,6 +8,8 @@ built from the reference's own classes out of the archive `oracle/stage_referenc
      STATED TOLERANCE for (b): rel-L2 <= 5.5e-2, cosine >= 0.998 - the whole-tower budget of tests/test_gpu_tower.py for weights that are
      not the well-conditioned "mild" profile (the reference's own bf16 execution sits at 4.4e-2 on such weights: DESIGN.md section 2).
 """
+import os
+import sys
 from types import SimpleNamespace
 
 import pytest
@@ -16,6 +18,9 @@ import torch
 import ml_fastvlm_amd as fv
 from ml_fastvlm_amd import reparam, synth
 from oracle import ref_import
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from reparam_reference import reference_reparameterize, training_model  # noqa: E402
 
 pytestmark = [pytest.mark.gpu,
               pytest.mark.skipif(not ref_import.reference_available(),
@@ -29,8 +34,7 @@ def _tower():
 
 
 def test_training_checkpoint_through_load_training_checkpoint_matches_the_references_reparameterize_bit_for_bit():
-    from test_reparam import _reference_reparameterize, _training_model
-    train = _training_model()                                    # the reference's FastViT(inference_mode=False), fastvithd() hyper-parameters
+    train = training_model()                                     # the reference's FastViT(inference_mode=False), fastvithd() hyper-parameters
     sd_train = {k: v.clone() for k, v in train.state_dict().items()}
     assert reparam.is_training_state_dict(sd_train) and any(".rbr_conv." in k for k in sd_train) and any(".lkb_origin." in k for k in sd_train)
 
@@ -39,7 +43,7 @@ def test_training_checkpoint_through_load_training_checkpoint_matches_the_refere
     assert not missing and not unexpected
     ours = ours.to(DEV, torch.bfloat16)
 
-    want_sd = {k: v for k, v in _reference_reparameterize(train).state_dict().items() if not k.startswith("head.")}
+    want_sd = {k: v for k, v in reference_reparameterize(train).state_dict().items() if not k.startswith("head.")}
     theirs = _tower()
     want_sd["head.proj"] = ours.vision_tower.model.state_dict()["head.proj"].float().cpu()
     theirs.vision_tower.model.load_state_dict(want_sd, strict=True)

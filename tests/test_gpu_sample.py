@@ -3,54 +3,23 @@
 Oracle: transformers' own TemperatureLogitsWarper / TopKLogitsWarper / TopPLogitsWarper on the same fp32 logits for the kept set, an fp64
 inverse CDF in token-index order for the draw, the Python Philox of qwen2_decode for the random numbers, and the fp32 transformers model
 for the teacher-forced steps."""
-import ctypes as C
 import math
+import os
+import sys
 
 import pytest
 import torch
 
-pytestmark = pytest.mark.gpu
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from llm_testlib import DELTA, models as _models, oracle_scores as _oracle_scores, prompt as _prompt, sample as _sample  # noqa: E402
 
-DELTA = 0.02          # fp32 logit error budget of our bf16 steps (tests/test_gpu_decode.py)
+pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def lib():
     from ml_fastvlm_amd import _lib
     return _lib.sampling_lib()
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _st():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _sample(lib, logits, T, k, p, seed=0, n=0, u=None):
-    from ml_fastvlm_amd import _lib
-    B, V = logits.shape
-    ids = torch.full((B,), -1, device="cuda", dtype=torch.long)
-    info = torch.zeros(B, 4, device="cuda")
-    _lib.check(lib.fvhd_op_dec_sample(_st(), _p(logits), B, V, float(T), int(k), float(p), int(seed), int(n), _p(u), _p(ids), _p(info)),
-               "fvhd_op_dec_sample")
-    torch.cuda.synchronize()
-    return ids, info
-
-
-def _oracle_scores(logits, T, k, p):
-    """transformers' warpers, in _get_logits_processor's order -> processed scores (-inf = removed), on the host: there `scores / T` is
-    the IEEE division (torch on the GPU divides by a host scalar as a multiply by its reciprocal, which can differ by one ulp)"""
-    from transformers.generation.logits_process import TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper
-    s = logits.detach().float().cpu().clone()
-    if T != 1.0:
-        s = TemperatureLogitsWarper(T)(None, s)
-    if k > 0:
-        s = TopKLogitsWarper(k)(None, s)
-    if p < 1.0:
-        s = TopPLogitsWarper(p)(None, s)
-    return s
 
 
 def _near_top_p(logits, T, k, p, tol=1e-5):
@@ -180,40 +149,7 @@ def test_distribution_chi_square(lib):
     assert pval >= 1e-4
 
 
-# ---- model-level tests (the test_gpu_decode.py helpers, written again) ------------------------------------------------------------------
-CONFIGS = {"0.5B": dict(hidden_size=896, num_hidden_layers=2, num_attention_heads=14, num_key_value_heads=2, intermediate_size=4864,
-                        tie_word_embeddings=True)}
-
-
-def _models(name, seed=0, vocab=4096):
-    from transformers import Qwen2Config, Qwen2ForCausalLM
-    torch.manual_seed(seed)
-    cfg = Qwen2Config(vocab_size=vocab, max_position_embeddings=4096, rope_theta=1e6, rms_norm_eps=1e-6, **CONFIGS[name])
-    m = Qwen2ForCausalLM(cfg).eval()
-    with torch.no_grad():
-        for p in m.parameters():
-            if p.dim() == 1:
-                p.add_(0.05 * torch.randn_like(p))
-    m16 = m.to("cuda", torch.bfloat16)
-    ref = Qwen2ForCausalLM(cfg).eval().to("cuda")
-    ref.load_state_dict({k: v.float() for k, v in m16.state_dict().items()})
-    return m16, ref
-
-
-def _prompt(ref, B, T, side, seed=0):
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    e = (0.5 * torch.randn(B, T, ref.config.hidden_size, device="cuda", generator=g)).to(torch.bfloat16).float()
-    mask = torch.ones(B, T, device="cuda", dtype=torch.long)
-    for b in range(B):
-        npad = 3 * b
-        if npad:
-            if side == "left":
-                mask[b, :npad] = 0
-            else:
-                mask[b, T - npad:] = 0
-    return e, mask
-
-
+# ---- model-level tests ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("side", ["left", "right"])
 def test_top_k_1_equals_greedy(side):
     from ml_fastvlm_amd.qwen2_decode import Qwen2Generator

@@ -21,7 +21,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import decode_reference as R  # noqa: E402
-from test_gpu_sample import _oracle_scores, _sample  # noqa: E402
+import llm_testlib as L  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -106,14 +106,14 @@ def _run_case(lib, x, T, k, p, what, exempt=None, seed=0):
     B, V = x.shape
     refs, us, adm, frac = _plan_case(x, T, k, p, what, exempt, seed)
     xd = x.cuda().contiguous()
-    hf = _oracle_scores(x, T, k, p) > -math.inf                    # transformers' warpers on the rows actually launched
+    hf = L.oracle_scores(x, T, k, p) > -math.inf                    # transformers' warpers on the rows actually launched
     all_ids = []
     for i in range(us.shape[0]):
         ut = us[i].cuda().contiguous()
-        ids, info = _sample(lib, xd, T, k, p, u=ut)
+        ids, info = L.sample(lib, xd, T, k, p, u=ut)
         ids, info = ids.cpu(), info.cpu()
         if i == 0:
-            ids2, info2 = _sample(lib, xd, T, k, p, u=ut)
+            ids2, info2 = L.sample(lib, xd, T, k, p, u=ut)
             assert torch.equal(ids, ids2.cpu()) and torch.equal(info.view(torch.int32), info2.cpu().view(torch.int32)), what + ": two launches differ"
         all_ids.append(ids)
         for b, r in enumerate(refs):

@@ -5,7 +5,6 @@
                 the arithmetic is the bf16 kernel's; with power-of-two scales and a zero residual the output is that output times the scale
   tolerance     the three ops against tests/decode_reference.py on W = codes.double() * scale: the weights are exact and the arithmetic is
                 the bf16 ops', so the bounds are theirs (tests/test_gpu_decode.py: rel-L2 1e-2)"""
-import ctypes as C
 import os
 import sys
 
@@ -14,7 +13,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import decode_reference as R  # noqa: E402
-from test_gpu_decode_ops import GEMM_SHAPES  # noqa: E402
+from llm_testlib import (GEMM_SHAPES, rel,  # noqa: E402
+                         dec_gemm as _gemm_bf16, gemm_scratch as _scratch, lowest_argmax as _lowest_argmax, nb as _nb, ptr as _p, stream as _st)
 
 pytestmark = pytest.mark.gpu
 
@@ -25,19 +25,6 @@ BATCHES = (1, 3, 8, 16, 17, 33, 64)
 def lib():
     from ml_fastvlm_amd import _lib
     return _lib.w8_lib()
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _st():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def rel(a, b):
-    a, b = a.double(), b.double()
-    return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
 
 
 # ---- 1. the quantiser ---------------------------------------------------------------------------------------------------------------------
@@ -70,24 +57,6 @@ def test_quantize_op_equals_the_torch_recipe(lib, N, K):
 def _random_codes(N, K, g):
     """e4m3 codes of N(0, 1) values: every binade of the format, both signs, denormals and zeros"""
     return torch.randn(N, K, device="cuda", generator=g).to(torch.float8_e4m3fn)
-
-
-def _scratch(N, B, splits):
-    nb = (B + 15) // 16
-    part = torch.empty(splits * N * 16 * nb, device="cuda") if splits > 1 else None
-    cnt = torch.zeros((N // 16 + 3) // 4, device="cuda", dtype=torch.int32) if splits > 1 else None
-    return part, cnt
-
-
-def _gemm_bf16(lib, epi, x, nw, W, resid, splits):
-    from ml_fastvlm_amd import _lib
-    B, K = x.shape
-    N = W.shape[0]
-    out = torch.empty(B, N // 2 if epi == "swiglu" else N, device="cuda", dtype=torch.bfloat16)
-    part, cnt = _scratch(N, B, splits)
-    _lib.check(lib.fvhd_op_dec_gemm(_st(), _lib.EPI_SWIGLU if epi == "swiglu" else _lib.EPI_RESID, _p(x), B, _p(nw), 1e-6, _p(W), N, K, _p(resid), _p(out),
-                                    _p(part), _p(cnt), splits), "dec_gemm")
-    return out
 
 
 def _gemm_w8(lib, epi, x, nw, codes, scale, resid, splits):
@@ -200,7 +169,7 @@ def _lm_w8(lib, x, nw, codes, scale, logits=True):
     from ml_fastvlm_amd import _lib
     B, H = x.shape
     V = codes.shape[0]
-    nb = (B + 15) // 16
+    nb = _nb(B)
     lg = torch.empty(B, V, device="cuda") if logits else None
     ids = torch.full((B,), -7, device="cuda", dtype=torch.long)
     nblk = (V // 16 + 3) // 4
@@ -209,12 +178,6 @@ def _lm_w8(lib, x, nw, codes, scale, logits=True):
     _lib.check(lib.fvhd_op_dec_lm_argmax_w8(_st(), _p(x), B, _p(nw), 1e-6, _p(codes), _p(scale), V, H, _p(lg), _p(ids), _p(sv), _p(si)), "lm_argmax_w8")
     torch.cuda.synchronize()
     return lg, ids
-
-
-def _lowest_argmax(lg):
-    V = lg.shape[1]
-    idx = torch.arange(V, device=lg.device)[None].expand_as(lg)
-    return torch.where(lg == lg.max(-1, keepdim=True).values, idx, torch.full_like(idx, V)).min(-1).values
 
 
 @pytest.mark.parametrize("V,H", [(151936, 896), (152064, 3584), (4112, 896)])

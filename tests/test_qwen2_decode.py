@@ -1,8 +1,13 @@
 """CPU-side contract of the Qwen2 decode (ml_fastvlm_amd/qwen2_decode.py, builder.generate, _lib): no GPU needed."""
 import ctypes as C
+import os
+import sys
 
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import llm_testlib as L  # noqa: E402
 
 
 def test_stale_library_fails_with_the_abi_message(monkeypatch):
@@ -59,10 +64,8 @@ def test_generate_refuses_other_decoding_strategies(kw, name):
 
 def test_generate_refuses_non_bf16_models():
     import ml_fastvlm_amd as fv
-    from transformers import Qwen2Config, Qwen2ForCausalLM
-    cfg = Qwen2Config(vocab_size=64, hidden_size=64, num_hidden_layers=1, num_attention_heads=2, num_key_value_heads=1, intermediate_size=128)
     with pytest.raises(ValueError, match="bf16 model on a HIP device"):
-        fv.generate(Qwen2ForCausalLM(cfg), torch.zeros(1, 4, dtype=torch.long), max_new_tokens=2)
+        fv.generate(L.tiny_qwen2(), torch.zeros(1, 4, dtype=torch.long), max_new_tokens=2)
 
 
 @pytest.mark.parametrize("kind", ["left", "right", "none", "nomask"])

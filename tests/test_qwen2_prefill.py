@@ -8,7 +8,8 @@ STATED TOLERANCES (bf16 storage, fp32 accumulation against fp32 references):
   2-layer stacks tested here; logits rel-L2 <= 2e-2, cosine >= 0.9995; greedy token equal wherever the reference's top-2 margin
   exceeds twice the logit error.
   The same kernels element by element against fp64 with the rms PER ROW, at the tile edges, under masks and in exact cases: tests/test_gpu_prefill_ops.py."""
-import ctypes as C
+import os
+import sys
 
 import pytest
 import torch
@@ -16,63 +17,11 @@ import torch
 from ml_fastvlm_amd import _lib
 from oracle import qwen2_oracle as QO
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from llm_testlib import (bf as _bf, close_pooled as _close, compare_prefill as _compare_prefill, metrics as _metrics,  # noqa: E402
+                         prefill_inputs as _inputs, ptr as _p, qwen2_cfg as _cfg, qwen2_model as _model, stream)
+
 DEV = "cuda:0"
-
-
-def _cfg(hidden=128, layers=2, heads=2, kv=1, inter=256, vocab=512, theta=1e6, head_dim=None):
-    from transformers import Qwen2Config
-    cfg = Qwen2Config(vocab_size=vocab, hidden_size=hidden, intermediate_size=inter, num_hidden_layers=layers, num_attention_heads=heads,
-                      num_key_value_heads=kv, max_position_embeddings=4096, rms_norm_eps=1e-6, tie_word_embeddings=False)
-    for holder in ("rope_parameters", "rope_scaling"):
-        d = getattr(cfg, holder, None)
-        if isinstance(d, dict):
-            d["rope_theta"] = theta
-    if hasattr(cfg, "rope_theta") and getattr(cfg, "rope_theta", None) is not None:
-        cfg.rope_theta = theta
-    cfg._attn_implementation = "eager"
-    return cfg
-
-
-def _model(cfg, seed=0):
-    from transformers import Qwen2ForCausalLM
-    torch.manual_seed(seed)
-    m = Qwen2ForCausalLM(cfg).eval()
-    g = torch.Generator().manual_seed(seed + 1)
-    with torch.no_grad():                      # HF's init is N(0, 0.02) with zero biases and unit norms: give every tensor some life
-        for n, p in m.named_parameters():
-            if n.endswith("bias"):
-                p.copy_(torch.randn(p.shape, generator=g) * 0.1)
-            elif "norm" in n:
-                p.copy_(1.0 + 0.2 * torch.randn(p.shape, generator=g))
-            else:
-                p.copy_(torch.randn(p.shape, generator=g) * (1.5 / p.shape[-1] ** 0.5))
-    return m
-
-
-def _inputs(B, T, H, seed=0, pad="none"):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(B, T, H, generator=g)
-    mask = torch.ones(B, T, dtype=torch.long)
-    pos = torch.arange(T)[None].repeat(B, 1)
-    if pad != "none":
-        for b in range(B):
-            n = (3 * b + 1) % max(2, T // 3)
-            if n == 0:
-                continue
-            if pad == "left":
-                mask[b, :n] = 0
-                pos[b] = torch.clamp(torch.arange(T) - n, min=0)         # as prepare_inputs_labels_for_multimodal builds them (0 on padding)
-            else:
-                mask[b, T - n:] = 0
-                pos[b, T - n:] = 0
-    return x, mask, pos
-
-
-def _metrics(got, want):
-    got, want = got.double().cpu().flatten(), want.double().cpu().flatten()
-    rel = ((got - want).norm() / want.norm()).item()
-    cos = torch.nn.functional.cosine_similarity(got, want, dim=0).item()
-    return rel, cos
 
 
 # ------------------------------------------------------------------------------------------------- CPU: pin the oracle
@@ -117,24 +66,8 @@ def test_host_refuses_cpu_and_bad_shapes():
 
 
 # ------------------------------------------------------------------------------------------------- GPU: single ops
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
 def _stream():
-    return C.c_void_p(torch.cuda.current_stream(torch.device(DEV)).cuda_stream)
-
-
-def _bf(t):
-    return t.to(torch.bfloat16).float()
-
-
-def _close(got, want, what, rtol=1e-2, atol_rms=1e-2):
-    got, want = got.float().cpu(), want.float().cpu()
-    assert torch.isfinite(got).all(), what
-    tol = rtol * want.abs() + atol_rms * want.pow(2).mean().sqrt()
-    bad = (got - want).abs() > tol
-    assert not bad.any(), f"{what}: {int(bad.sum())} of {bad.numel()} out of tolerance, max err {(got - want).abs().max():.4g}"
+    return stream(DEV)
 
 
 @pytest.mark.gpu
@@ -351,43 +284,6 @@ def test_gemm_swiglu_and_residual_epilogues():
 
 
 # ------------------------------------------------------------------------------------------------- GPU: the whole prefill
-def _compare_prefill(cfg, B, T, pad, seed, layers_tol):
-    from ml_fastvlm_amd.qwen2_prefill import Qwen2Prefill, kv_to_dynamic_cache
-    m = _model(cfg, seed)
-    x, mask, pos = _inputs(B, T, cfg.hidden_size, seed=seed + 10, pad=pad)
-    x = _bf(x)
-    sd = {k: (_bf(v) if v.dim() == 2 else v) for k, v in m.state_dict().items()}     # the matrices the library holds are bf16
-    m.load_state_dict(sd)
-    with torch.no_grad():
-        want = m(inputs_embeds=x, attention_mask=mask, position_ids=pos).logits[:, -1]
-    _, hidden, kvs = QO.prefill(x, sd, cfg, mask, pos)
-    pre = Qwen2Prefill.from_hf(m.to(DEV))
-    logits, kc, vc = pre(x.to(DEV, torch.bfloat16), mask.to(DEV), pos.to(DEV), return_kv=True)
-    torch.cuda.synchronize()
-    assert logits.shape == (B, cfg.vocab_size) and logits.dtype == torch.float32 and torch.isfinite(logits).all()
-    valid = mask.bool()
-    got_h = pre.hidden_states(B * T).float().cpu().view(B, T, -1)
-    rel_h, cos_h = _metrics(got_h[valid], hidden[valid])
-    rel, cos = _metrics(logits, want)
-    print(f"prefill H={cfg.hidden_size} L={cfg.num_hidden_layers} B={B} T={T} pad={pad}: residual stream rel-L2 {rel_h:.3e} cos {cos_h:.6f}; "
-          f"last-position logits rel-L2 {rel:.3e} cos {cos:.6f}")
-    assert rel_h <= layers_tol and cos_h >= 0.9998, (rel_h, cos_h)
-    if pad != "right":                               # with right padding position -1 is a padding row: meaningless in the reference too
-        assert rel <= 2e-2 and cos >= 0.9995, (rel, cos)
-        top2 = want.topk(2, -1).values
-        err = (logits.cpu() - want).abs().max(-1).values
-        for b in range(B):
-            if top2[b, 0] - top2[b, 1] > 2 * err[b]:
-                assert int(logits[b].argmax()) == int(want[b].argmax())
-    # KV cache: rotated keys and values of the valid positions, in transformers' [B, nkv, T, hd] layer layout
-    for l in range(cfg.num_hidden_layers):
-        vm = valid[:, None, :, None].expand_as(kvs[l][0])
-        rk, _ = _metrics(kc[l].float().cpu()[vm], kvs[l][0][vm])
-        rv, _ = _metrics(vc[l].float().cpu()[vm], kvs[l][1][vm])
-        assert rk <= layers_tol and rv <= layers_tol, (l, rk, rv)
-    return m, pre, x, mask, pos, logits, kc, vc
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("pad", ["none", "left", "right"])
 def test_prefill_tiny_model_vs_transformers(pad):
@@ -435,7 +331,7 @@ def test_prefill_hands_its_kv_cache_to_the_transformers_decode_loop():
         cache = kv_to_dynamic_cache(kc.float(), vc.float())
         step_ours = m(input_ids=tok[:, None], past_key_values=cache, use_cache=True,
                       attention_mask=torch.ones(2, 41, device=DEV, dtype=torch.long), position_ids=torch.full((2, 1), 40, device=DEV)).logits[:, -1]
-    rel, cos = _metrics(step_ours, step_ref)
+    rel, cos, _ = _metrics(step_ours, step_ref)
     print(f"decode step from our KV cache vs from transformers' own: logits rel-L2 {rel:.3e} cos {cos:.6f}")
     assert rel <= 2e-2 and cos >= 0.9995
 

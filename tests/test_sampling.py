@@ -1,9 +1,14 @@
 """CPU-side contract of the token sampler (qwen2_decode.philox_uniform, _lib's 502 symbols, builder's generate settings): no GPU needed."""
 import ctypes as C
 import math
+import os
+import sys
 
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import llm_testlib as L  # noqa: E402
 
 
 @pytest.mark.parametrize("counter,key,want", [
@@ -86,27 +91,21 @@ def test_a_501_library_loads_and_sampling_names_the_rebuild(monkeypatch):
     gen._set_greedy()                                           # greedy on a 501 library: nothing to set
 
 
-def _tiny():
-    from transformers import Qwen2Config, Qwen2ForCausalLM
-    cfg = Qwen2Config(vocab_size=64, hidden_size=64, num_hidden_layers=1, num_attention_heads=2, num_key_value_heads=1, intermediate_size=128)
-    return Qwen2ForCausalLM(cfg)
-
-
 PREDICT = dict(do_sample=True, temperature=0.2, top_p=None, num_beams=1, max_new_tokens=256, use_cache=True)   # predict.py's generate()
 
 
 def test_settings_of_predict_py_run_on_the_library():
     from ml_fastvlm_amd.builder import _library_generate_settings
-    got, reason = _library_generate_settings(_tiny(), dict(PREDICT))
+    got, reason = _library_generate_settings(L.tiny_qwen2(), dict(PREDICT))
     assert reason is None
     assert got["max_new_tokens"] == 256 and got["sampling"] == dict(temperature=pytest.approx(0.2), top_k=50, top_p=1.0)
 
 
 def test_settings_greedy_and_the_model_generation_config():
     from ml_fastvlm_amd.builder import _library_generate_settings
-    got, reason = _library_generate_settings(_tiny(), dict(PREDICT, do_sample=False))
+    got, reason = _library_generate_settings(L.tiny_qwen2(), dict(PREDICT, do_sample=False))
     assert reason is None and got["sampling"] is None
-    m = _tiny()
+    m = L.tiny_qwen2()
     m.generation_config.top_k = 20
     got, reason = _library_generate_settings(m, dict(PREDICT))
     assert reason is None and got["sampling"]["top_k"] == 20
@@ -119,7 +118,7 @@ def test_settings_greedy_and_the_model_generation_config():
                                      (dict(min_new_tokens=3), "min_new_tokens"), (dict(num_return_sequences=2), "num_return_sequences")])
 def test_settings_outside_the_library_fall_back_with_the_reason(kw, name):
     from ml_fastvlm_amd.builder import _library_generate_settings
-    got, reason = _library_generate_settings(_tiny(), dict(PREDICT, **kw))
+    got, reason = _library_generate_settings(L.tiny_qwen2(), dict(PREDICT, **kw))
     assert got is None and name in reason
 
 
@@ -132,7 +131,7 @@ def test_library_generate_falls_back_on_a_cpu_model_with_one_warning():
         calls.append(kwargs)
         return "reference"
 
-    m = _tiny()
+    m = L.tiny_qwen2()
     gen = _make_library_generate(orig)
     with warnings.catch_warnings(record=True) as w:
         warnings.simplefilter("always")

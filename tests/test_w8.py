@@ -1,9 +1,14 @@
 """8-bit LLM weights (include/fvhd.h version 504), the parts that need no GPU: the quantisation recipe restated in torch
 (`ml_fastvlm_amd.quantize_rows_e4m3`), the version constants, the refusals of the new entry points and of the Python arguments."""
 import ctypes as C
+import os
+import sys
 
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import llm_testlib as L  # noqa: E402
 
 
 def _matrices():
@@ -97,19 +102,13 @@ def test_new_entry_points_refuse_null_and_bad_arguments_with_a_message():
     refused(lib.fvhd_op_dec_lm_argmax_w8(None, p, 65, None, 1e-6, p, p, 16, 128, None, q, p, p), b"B <= 64")
 
 
-def _tiny():
-    from transformers import Qwen2Config, Qwen2ForCausalLM
-    cfg = Qwen2Config(vocab_size=64, hidden_size=64, num_hidden_layers=1, num_attention_heads=2, num_key_value_heads=1, intermediate_size=128)
-    return Qwen2ForCausalLM(cfg)
-
-
 def test_an_unknown_weight_format_is_a_value_error():
     """before the device, the library or the model's tensors are looked at"""
     from ml_fastvlm_amd import _lib
     from ml_fastvlm_amd.builder import generator_context, prefill_context
     from ml_fastvlm_amd.qwen2_decode import Qwen2Generator
     from ml_fastvlm_amd.qwen2_prefill import Qwen2Prefill
-    m = _tiny()
+    m = L.tiny_qwen2()
     for bad in ("int3", "fp8", None, 8):
         with pytest.raises(ValueError, match="weights must be one of"):
             Qwen2Prefill.from_hf(m, weights=bad)
@@ -128,7 +127,7 @@ def test_an_unknown_weight_format_is_a_value_error():
 def test_a_prefill_context_in_another_format_is_an_error_not_a_repack():
     from types import SimpleNamespace
     from ml_fastvlm_amd.qwen2_decode import Qwen2Generator
-    m = _tiny()
+    m = L.tiny_qwen2()
     for have, want in (("bf16", "fp8_e4m3"), ("fp8_e4m3", "bf16")):
         pre = SimpleNamespace(weight_format=have)
         with pytest.raises(ValueError, match=have):
@@ -205,7 +204,7 @@ def test_prefill_context_records_the_format_and_rebuilds_for_another(monkeypatch
             self.weight_format = weights
 
     monkeypatch.setattr(qp.Qwen2Prefill, "from_hf", classmethod(lambda cls, model, device=None, weights="bf16": built.append(weights) or Pre(weights)))
-    m = _tiny()
+    m = L.tiny_qwen2()
     a = builder.prefill_context(m)
     assert built == ["bf16"] and builder.prefill_context(m) is a and built == ["bf16"]
     b = builder.prefill_context(m, weights="fp8_e4m3")
