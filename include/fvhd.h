@@ -54,8 +54,10 @@ typedef void* fvhd_stream_t; /* hipStream_t */
  * (fvhd_llm_cache_reserve, fvhd_op_dec_gemm / _qkv / _attention / _lm_argmax: B in [1, 64]; the scratch of the single ops grows with
  * ceil(B / 16)); no signature changed and B <= 16 computes what 502 did, bit for bit.  504 adds 8-bit LLM weights
  * (fvhd_llm_set_weight_format, fvhd_llm_weight_bytes, fvhd_llm_debug_packed_e4m3, fvhd_op_quantize_e4m3, fvhd_op_dec_gemm_w8 / _qkv_w8 /
- * _lm_argmax_w8): bf16 stays the default and computes what 503 did, bit for bit; nothing earlier changed. */
-#define FVHD_VERSION 504
+ * _lm_argmax_w8): bf16 stays the default and computes what 503 did, bit for bit; nothing earlier changed.  505 adds beam search
+ * (fvhd_llm_beam_reserve, fvhd_llm_cache_gather, fvhd_llm_beam_topk, fvhd_op_dec_beam_topk, fvhd_op_dec_cache_gather; error word 3):
+ * greedy and sampled steps compute what 504 did, bit for bit, and fvhd_llm_cache_reserve allocates what it did; nothing earlier changed. */
+#define FVHD_VERSION 505
 int fvhd_version(void);
 const char* fvhd_last_error(void);
 
@@ -452,7 +454,8 @@ int fvhd_llm_start(fvhd_llm* ctx, const void* embeds, int dtype, const uint8_t* 
  * (NULL or int64 [batch]).  A step past `capacity` (or given an id outside [0, vocab)) writes nothing and sets a sticky error word that the
  * next fvhd_llm_decode reports as an error (fvhd_llm_cache_state reads it at once).  Capture-safe after fvhd_llm_start. */
 int fvhd_llm_decode(fvhd_llm* ctx, const int64_t* token_ids, float* logits_out, int64_t* next_ids_out, fvhd_stream_t stream);
-/* synchronises the device, then: the cache length and the error word (0 = fine, 1 = past capacity, 2 = token id out of range) */
+/* synchronises the device, then: the cache length and the error word (0 = fine, 1 = past capacity, 2 = token id out of range, 3 = a
+ * cache reorder's row index out of range) */
 int fvhd_llm_cache_state(fvhd_llm* ctx, int* length, int* status);
 
 /* ---- LLM sampling: temperature / top-k / top-p on the device ------------------------------------------------------------------------
@@ -546,6 +549,43 @@ int fvhd_op_dec_qkv_w8(fvhd_stream_t stream, const void* x, int B, int K, const 
                        int splits);
 int fvhd_op_dec_lm_argmax_w8(fvhd_stream_t stream, const void* x, int B, const float* norm_w, float eps, const void* Wt, const float* scale, int V,
                              int K, float* logits, int64_t* ids_out, float* scratch_v, int* scratch_i);
+
+/* ---- LLM beam search: the top continuations and the KV-cache reorder on the device (version 505) -------------------------------------------
+ * transformers' `GenerationMixin._beam_search` keeps, per prompt, K = num_beams running hypotheses: K beams of G prompts are G * K rows of
+ * the decode step (row g * K + k = beam k of prompt g).  Per step it needs two operations on [rows, vocab] / cache-sized data; the rest is
+ * [G, 2 K] bookkeeping that the caller does (ml_fastvlm_amd/beam.py).
+ * Top continuations (step b + `_get_top_k_continuations`): acc[k * V + v] = ((logit[g K + k][v] - max_row) - log sum_v exp(logit - max_row))
+ * + score[g][k] in fp32, and per prompt its `keep` largest values in descending order with their flat indices k * V + v; equal values: the
+ * lower flat index first.  (A row's candidates are pre-selected by their raw logit, ties to the lower index: two logits of one row that
+ * differ but round to one accumulated value keep the order of the logits.)  2 <= num_beams <= 16, keep <= 64, keep <= vocab,
+ * groups * num_beams <= 64, vocab % 16 == 0, vocab <= 262144.  A row may hold -inf logits; a prompt with fewer than `keep` finite candidates
+ * and a row with a NaN are undefined.  A score of -1e9 (a dead beam) is an ordinary input.  Deterministic: fixed summation orders, the same
+ * bits eager or replayed.
+ * Cache reorder (`Cache.reorder_cache` / index_select of every layer): new row r of K and V of every layer, of the key-valid mask and of
+ * the next positions = old row src_rows[r] (int64 [rows_out] on the device, entries in [0, rows_in)), over cache slots [0, length).  Any
+ * map is correct (it goes through a scratch, never in place); slots >= length and rows >= rows_out keep their bytes; rows with
+ * src_rows[r] == r are not touched.  An index out of range writes nothing and sets the sticky error word to 3. */
+/* Allocates the reorder's scratch (two layers' K | V of the reserved cache) and the top-K workspace (about 2 MiB), apart from
+ * fvhd_llm_cache_reserve's allocation.  Synchronises (refused while a stream is being captured).  fvhd_llm_cache_reserve frees it with
+ * the cache it was sized for. */
+int fvhd_llm_beam_reserve(fvhd_llm* ctx);
+/* The reorder on the context's cache; the later steps run on rows_out sequences (<= the reserved batch; rows_in <= it too).  src_rows =
+ * r / num_beams turns G prefilled rows into G * num_beams.  The host arguments are the same every step: capture-safe after
+ * fvhd_llm_beam_reserve and fvhd_llm_start.  n_layers + 1 launches. */
+int fvhd_llm_cache_gather(fvhd_llm* ctx, const int64_t* src_rows, int rows_in, int rows_out, fvhd_stream_t stream);
+/* The top continuations of logits fp32 [groups * num_beams, vocab] (16-byte aligned) and beam_scores fp32 [groups, num_beams] ->
+ * cand_scores fp32 [groups, keep], cand_index int64 [groups, keep].  Capture-safe after fvhd_llm_beam_reserve.  3 launches. */
+int fvhd_llm_beam_topk(fvhd_llm* ctx, const float* logits, const float* beam_scores, int groups, int num_beams, int keep, float* cand_scores,
+                       int64_t* cand_index, fvhd_stream_t stream);
+/* the two operations on their own (tests), on plain device pointers; a process-wide scratch, allocated / grown on demand: eager calls
+ * only, not during stream capture.  fvhd_op_dec_cache_gather: k_cache / v_cache bf16 [n_layers][batch][n_kv_heads][capacity][head_dim],
+ * key_valid uint8 [batch][capacity], positions int64 [batch], length and status device ints (status: as the error word above; nothing
+ * happens while *status != 0). */
+int fvhd_op_dec_beam_topk(fvhd_stream_t stream, const float* logits, const float* beam_scores, int groups, int num_beams, int keep, int V,
+                          float* cand_scores, int64_t* cand_index);
+int fvhd_op_dec_cache_gather(fvhd_stream_t stream, void* k_cache, void* v_cache, uint8_t* key_valid, int64_t* positions, const int64_t* src_rows,
+                             int n_layers, int batch, int rows_in, int rows_out, int n_kv_heads, int head_dim, int capacity, const int* length,
+                             int* status);
 
 #ifdef __cplusplus
 }

@@ -15,6 +15,7 @@ ABI_VERSION = 501               # the oldest FVHD_VERSION (include/fvhd.h) this 
 SAMPLING_VERSION = 502          # the first with fvhd_llm_set_sampling / fvhd_op_dec_sample (declared only when the library has them)
 WIDE_BATCH_VERSION = 503       # the first whose decode takes more than 16 sequences per step (up to MAX_DECODE_BATCH)
 W8_VERSION = 504               # the first with 8-bit (e4m3) LLM weights: fvhd_llm_set_weight_format, fvhd_op_*_w8 (declared only when the library has them)
+BEAM_VERSION = 505             # the first with beam search: fvhd_llm_beam_reserve / _cache_gather / _beam_topk, fvhd_op_dec_beam_topk / _cache_gather (declared only when the library has them)
 MAX_DECODE_BATCH = 64
 W_BF16, W_E4M3 = 0, 1           # fvhd_llm_set_weight_format (include/fvhd.h)
 WEIGHT_FORMATS = {"bf16": W_BF16, "fp8_e4m3": W_E4M3}
@@ -126,6 +127,14 @@ def _declare(lib) -> None:
             "fvhd_op_dec_qkv_w8": (ci, [vp, vp, ci, ci, vp, cf, vp, vp, vp, vp, vp, vp, ci, cf, vp, vp, ci, vp, ci, ci, ci, vp, vp, ci]),
             "fvhd_op_dec_lm_argmax_w8": (ci, [vp, vp, ci, vp, cf, vp, vp, ci, ci, vp, vp, vp, vp]),
         })
+    if lib.fvhd_version() >= BEAM_VERSION:         # an older library loads without them; beam_lib() then names the rebuild
+        sig.update({
+            "fvhd_llm_beam_reserve": (ci, [vp]),
+            "fvhd_llm_cache_gather": (ci, [vp, vp, ci, ci, vp]),
+            "fvhd_llm_beam_topk": (ci, [vp, vp, vp, ci, ci, ci, vp, vp, vp]),
+            "fvhd_op_dec_beam_topk": (ci, [vp, vp, vp, ci, ci, ci, ci, vp, vp]),
+            "fvhd_op_dec_cache_gather": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp]),
+        })
     del fp, cl
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)     # AttributeError here = the .so does not export what fvhd.h declares
@@ -173,6 +182,17 @@ def w8_lib():
     if got < W8_VERSION:
         raise FvhdError(f"{LIB_PATH} reports ABI version {got}: 8-bit weights (fvhd_llm_set_weight_format, fvhd_op_dec_gemm_w8, ...) need "
                         f"{W8_VERSION} - rebuild the library (`python -m ml_fastvlm_amd.build`)")
+    return lib
+
+
+def beam_lib():
+    """load(), for the beam-search entry points: a library older than BEAM_VERSION loads (greedy and sampled decoding work on it) but has
+    none of them, and this says so instead of an AttributeError."""
+    lib = load()
+    got = lib.fvhd_version()
+    if got < BEAM_VERSION:
+        raise FvhdError(f"{LIB_PATH} reports ABI version {got}: beam search (fvhd_llm_beam_reserve, fvhd_llm_cache_gather, fvhd_llm_beam_topk, ...) "
+                        f"needs {BEAM_VERSION} - rebuild the library (`python -m ml_fastvlm_amd.build`)")
     return lib
 
 

@@ -93,7 +93,7 @@ def encode_images(vision_tower, mm_projector, images):
 
 
 def install_into_llava(splice: bool = False, prefill: bool = False, prefill_any_dtype: bool = False, generate: bool = False,
-                       llm_weights: str = "bf16") -> None:
+                       llm_weights: str = "bf16", beam_search: bool = False) -> None:
     """Make an unmodified `llava` package (the reference) build and call the MI355X tower; splice=True also routes
     `prepare_inputs_labels_for_multimodal` through the GPU splice (needs the embeddings on a HIP device); prefill=True also runs the
     PREFILL step of `LlavaQwen2ForCausalLM.forward` (`llava_qwen.py:92-103`: the first forward of `generate`, on `inputs_embeds`
@@ -103,6 +103,9 @@ def install_into_llava(splice: bool = False, prefill: bool = False, prefill_any_
     generate=True replaces `LlavaQwen2ForCausalLM.generate` (`llava_qwen.py:106-143`) by `_make_library_generate`: the unchanged call of
     predict.py (sampling included) then runs its prefill and every decode step on the library, and any setting the library does not
     implement falls back to the reference's generate with a one-time warning.
+    beam_search=True (with generate=True) lets that patched generate take the library for `num_beams` > 1 as well
+    (`Qwen2Generator.beam_search`): do_sample=False, one beam group, no other processor, batch * num_beams <= 64; without it num_beams > 1
+    keeps falling back, as before.
     llm_weights: "bf16" (the default) or "fp8_e4m3" - the storage of the LLM's packed matrices in the library's prefill / decode contexts
     (`Qwen2Prefill.from_hf(weights=...)`), recorded on `LlavaQwen2ForCausalLM` for `prefill_context` to read."""
     from ._lib import weight_format_code
@@ -137,7 +140,7 @@ def install_into_llava(splice: bool = False, prefill: bool = False, prefill_any_
     if generate:
         import llava.model.language_model.llava_qwen as lq
         cur = lq.LlavaQwen2ForCausalLM.generate
-        lq.LlavaQwen2ForCausalLM.generate = _make_library_generate(getattr(cur, "_fvhd_orig", cur))
+        lq.LlavaQwen2ForCausalLM.generate = _make_library_generate(getattr(cur, "_fvhd_orig", cur), beam_search=beam_search)
 
 
 def _is_fresh_dynamic_cache(pkv) -> bool:
@@ -282,7 +285,8 @@ def generate(model, input_ids, images=None, image_sizes=None, attention_mask=Non
         raise NotImplementedError("ml_fastvlm_amd.generate: do_sample=True (sampling) is not implemented - greedy decoding only; "
                                   "Qwen2Generator.step exposes the logits for sampling in torch")
     if num_beams != 1:
-        raise NotImplementedError(f"ml_fastvlm_amd.generate: num_beams={num_beams} (beam search) is not implemented - greedy decoding only")
+        raise NotImplementedError(f"ml_fastvlm_amd.generate: num_beams={num_beams} (beam search) is not implemented here - greedy decoding only; "
+                                  "ml_fastvlm_amd.beam_generate runs beam search")
     if "inputs_embeds" in kwargs:                            # as the reference's generate (llava_qwen.py:120)
         raise NotImplementedError("`inputs_embeds` is not supported")
     for k, v in kwargs.items():
@@ -301,16 +305,42 @@ def generate(model, input_ids, images=None, image_sizes=None, attention_mask=Non
     return _generate_on_library(model, input_ids, images, image_sizes, attention_mask, None, max_new_tokens, eos_token_id, pad_token_id)
 
 
+@torch.no_grad()
+def beam_generate(model, input_ids, images=None, image_sizes=None, attention_mask=None, max_new_tokens: int = 256, num_beams: int = 4,
+                  length_penalty: float = 1.0, early_stopping=False, num_return_sequences: int = 1, eos_token_id=None, pad_token_id=None,
+                  return_scores: bool = False):
+    """`generate`'s counterpart for `num_beams` > 1: `LlavaQwen2ForCausalLM.generate(..., num_beams=K)` (predict.py's --num_beams) with the
+    splice, the prefill, every decode step, the top continuations and the cache reorder on the library (`Qwen2Generator.beam_search`).
+    Returns the new tokens [B * num_return_sequences, n] as transformers' generate(inputs_embeds=..., num_beams=K) does, with return_scores
+    also its `sequences_scores`.  The model must be bf16 on a HIP device and B * num_beams <= 64."""
+    lm_w = model.lm_head.weight
+    if lm_w.device.type != "cuda" or lm_w.dtype != torch.bfloat16:
+        raise ValueError(f"ml_fastvlm_amd.beam_generate: needs a bf16 model on a HIP device (got {lm_w.dtype} on {lm_w.device}); "
+                         "the decode kernels compute in bf16")
+    gc = getattr(model, "generation_config", None)
+    if eos_token_id is None:
+        eos_token_id = getattr(gc, "eos_token_id", None)
+    if pad_token_id is None:
+        pad_token_id = getattr(gc, "pad_token_id", None)
+    beam = dict(num_beams=int(num_beams), length_penalty=float(length_penalty), early_stopping=early_stopping,
+                num_return_sequences=int(num_return_sequences), return_scores=return_scores)
+    return _generate_on_library(model, input_ids, images, image_sizes, attention_mask, None, max_new_tokens, eos_token_id, pad_token_id, beam=beam)
+
+
 def _generate_on_library(model, input_ids, images, image_sizes, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id,
-                         sampling=None):
-    """the body shared by `generate` and `_make_library_generate`: the multimodal splice (or the token embedding), then the prefill and every
-    decode step on the library - `Qwen2Generator.greedy`, or `.sample(**sampling)`"""
+                         sampling=None, beam=None):
+    """the body shared by `generate`, `beam_generate` and `_make_library_generate`: the multimodal splice (or the token embedding), then the
+    prefill and every decode step on the library - `Qwen2Generator.greedy`, `.sample(**sampling)` or `.beam_search(**beam)`"""
     if images is not None:
         (input_ids, position_ids, attention_mask, _, inputs_embeds, _) = model.prepare_inputs_labels_for_multimodal(
             input_ids, position_ids, attention_mask, None, None, images, image_sizes=image_sizes)
     else:
         inputs_embeds = model.get_input_embeddings()(input_ids)
     B, T = inputs_embeds.shape[:2]
+    if beam is not None:
+        gen = generator_context(model, B * beam["num_beams"], T + max_new_tokens)
+        return gen.beam_search(inputs_embeds, attention_mask, position_ids, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id,
+                               pad_token_id=pad_token_id, **beam)
     gen = generator_context(model, B, T + max_new_tokens)
     if sampling is None:
         return gen.greedy(inputs_embeds, attention_mask, position_ids, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id,
@@ -337,11 +367,12 @@ _GENERATE_ARGS = ("generation_config", "logits_processor", "stopping_criteria", 
                   "streamer", "negative_prompt_ids", "negative_prompt_attention_mask", "custom_generate", "assistant_tokenizer", "tokenizer")
 
 
-def _library_generate_settings(model, kwargs):
+def _library_generate_settings(model, kwargs, beam_search: bool = False):
     """transformers' own resolution of a generate(**kwargs) call (`_prepare_generation_config`, which generate itself calls: its global
     defaults such as top_k = 50, the model's generation_config, then the call's arguments) -> (settings, None) when the library can run
-    it, (None, reason) when it cannot.  settings: max_new_tokens, eos_token_id, pad_token_id and `sampling` (None = greedy, else the
-    keyword arguments of Qwen2Generator.sample)."""
+    it, (None, reason) when it cannot.  settings: max_new_tokens, eos_token_id, pad_token_id, `sampling` (None = greedy, else the
+    keyword arguments of Qwen2Generator.sample) and `beam` (None, or with beam_search=True and num_beams > 1 the keyword arguments of
+    Qwen2Generator.beam_search: num_beams, length_penalty, early_stopping, num_return_sequences)."""
     for k in _GENERATE_ARGS:
         if kwargs.get(k) is not None:
             return None, f"{k} is given"
@@ -352,10 +383,23 @@ def _library_generate_settings(model, kwargs):
     extra = sorted(k for k, v in model_kwargs.items() if v is not None)
     if extra:
         return None, f"model arguments {extra}"
+    beams = gc.num_beams if beam_search and isinstance(gc.num_beams, int) and gc.num_beams > 1 else None
     for k, off in _OFF.items():
         v = getattr(gc, k, None)
+        if beams is not None and k in ("num_beams", "num_return_sequences"):
+            continue
         if v is not None and v not in off:
             return None, f"{k}={v!r}"
+    beam = None
+    if beams is not None:
+        if gc.do_sample:
+            return None, f"do_sample=True with num_beams={beams} (beam sampling)"
+        n_ret = 1 if gc.num_return_sequences is None else int(gc.num_return_sequences)
+        early = False if gc.early_stopping is None else gc.early_stopping
+        if not 1 <= n_ret <= beams or beams > 16 or early not in (False, True, "never"):
+            return None, f"num_beams={beams}, num_return_sequences={gc.num_return_sequences!r}, early_stopping={gc.early_stopping!r}"
+        beam = dict(num_beams=beams, length_penalty=1.0 if gc.length_penalty is None else float(gc.length_penalty), early_stopping=early,
+                    num_return_sequences=n_ret)
     if gc.max_new_tokens is None:
         return None, "max_new_tokens is not given"
     if not gc.use_cache:
@@ -366,7 +410,7 @@ def _library_generate_settings(model, kwargs):
                         top_p=1.0 if gc.top_p is None else float(gc.top_p))
         if not (0.0 < sampling["temperature"] < math.inf) or not 0.0 <= sampling["top_p"] <= 1.0 or sampling["top_k"] < 0:
             return None, f"temperature={gc.temperature!r}, top_k={gc.top_k!r}, top_p={gc.top_p!r}"
-    return dict(max_new_tokens=int(gc.max_new_tokens), eos_token_id=gc.eos_token_id, pad_token_id=gc.pad_token_id, sampling=sampling), None
+    return dict(max_new_tokens=int(gc.max_new_tokens), eos_token_id=gc.eos_token_id, pad_token_id=gc.pad_token_id, sampling=sampling, beam=beam), None
 
 
 def _batch_reason(batch: int):
@@ -375,21 +419,25 @@ def _batch_reason(batch: int):
     return f"batch {batch} > {MAX_DECODE_BATCH}" if batch > MAX_DECODE_BATCH else None
 
 
-def _make_library_generate(orig_generate):
+def _make_library_generate(orig_generate, beam_search: bool = False):
     """`LlavaQwen2ForCausalLM.generate` (`llava_qwen.py:106-143`) on the library: the same argument handling (position_ids / attention_mask
     popped, inputs_embeds refused), the settings resolved as transformers resolves them (`_library_generate_settings`), then the
     multimodal splice and `Qwen2Generator.greedy` / `.sample` on `generator_context(model, ...)`.  It takes the library only for greedy or
     temperature / top-k / top-p sampling with num_beams = 1, one sequence per prompt, no other logits processor, stopping criterion or
     streamer, max_new_tokens given, use_cache, no scores / dict output, a bf16 model on a HIP device and a batch of at most 64; anything
     else is the original generate, with a one-time warning that names the reason.  Returns the new tokens [B, n], as the reference's
-    generate(inputs_embeds=...) does."""
+    generate(inputs_embeds=...) does.  beam_search=True: num_beams > 1 (do_sample=False, one beam group, num_return_sequences <= num_beams,
+    batch * num_beams <= 64) takes `Qwen2Generator.beam_search` and returns [B * num_return_sequences, n]; beam sampling, group / constrained
+    beam search and dict output stay on the original generate."""
     def generate(self, inputs=None, images=None, image_sizes=None, **kwargs):
         if "inputs_embeds" in kwargs:                            # as the reference (llava_qwen.py:120-121)
             raise NotImplementedError("`inputs_embeds` is not supported")
-        settings, reason = _library_generate_settings(self, {k: v for k, v in kwargs.items() if k not in ("position_ids", "attention_mask")})
+        settings, reason = _library_generate_settings(self, {k: v for k, v in kwargs.items() if k not in ("position_ids", "attention_mask")},
+                                                      beam_search=beam_search)
         lm_w = self.lm_head.weight
-        if settings is not None and inputs is not None and _batch_reason(inputs.shape[0]) is not None:
-            settings, reason = None, _batch_reason(inputs.shape[0])
+        rows = 0 if inputs is None else inputs.shape[0] * (settings["beam"]["num_beams"] if settings is not None and settings["beam"] else 1)
+        if settings is not None and inputs is not None and _batch_reason(rows) is not None:
+            settings, reason = None, _batch_reason(rows)
         if settings is not None and (lm_w.device.type != "cuda" or lm_w.dtype != torch.bfloat16):
             settings, reason = None, f"the model is {lm_w.dtype} on {lm_w.device} (the library decodes a bf16 model on a HIP device)"
         if settings is None:
@@ -401,7 +449,8 @@ def _make_library_generate(orig_generate):
             return orig_generate(self, inputs, images, image_sizes, **kwargs)
         with torch.no_grad():
             return _generate_on_library(self, inputs, images, image_sizes, kwargs.get("attention_mask"), kwargs.get("position_ids"),
-                                        settings["max_new_tokens"], settings["eos_token_id"], settings["pad_token_id"], settings["sampling"])
+                                        settings["max_new_tokens"], settings["eos_token_id"], settings["pad_token_id"], settings["sampling"],
+                                        settings["beam"])
     generate._fvhd_generate = True
     generate._fvhd_orig = orig_generate
     return generate

@@ -80,4 +80,10 @@ int fvhd_launch_dec_embed_w8(hipStream_t st, const int64_t* tok, const int64_t* 
 // llm_sample.hip
 size_t fvhd_dec_sample_ws_bytes(void);
 int fvhd_launch_dec_sample(hipStream_t st, const DecSampleArgs* a, void* ws);
+// llm_beam.hip
+size_t fvhd_dec_beam_topk_ws_bytes(void);
+int fvhd_dec_beam_topk_supported(int G, int K, int C, int V);
+int fvhd_launch_dec_beam_topk(hipStream_t st, const float* logits, const float* scores, int G, int K, int C, int V, float* out_v, int64_t* out_i, void* ws);
+size_t fvhd_dec_cache_gather_ws_bytes(int rows, int nkv, int hd, int cap);
+int fvhd_launch_dec_cache_gather(hipStream_t st, const DecCacheGatherArgs* a);
 }

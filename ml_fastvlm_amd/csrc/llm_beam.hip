@@ -1,0 +1,330 @@
+// Beam search on the device (include/fvhd.h "LLM beam search"): the top continuations of every prompt and the KV-cache reorder.
+//
+// dec_beam_topk: per prompt g the C largest of acc[k * V + v] = ((logit[g K + k][v] - max_row) - log sum_v exp(logit - max_row)) + score[g][k]
+// over its K beams (transformers' `_beam_search` step b + `_get_top_k_continuations`: log_softmax, + running_beam_scores, topk), without
+// sorting or even writing the K * V values: the term added to a row's logits is one constant, so a prompt's top C lie inside the per-row
+// top C of the RAW logits.  Three launches, 256 threads each:
+//   beam_slice   grid (S, rows): a slice of 4096 logits in registers (16 per thread) -> the slice's (max, sum exp(x - max)) and its top C
+//   beam_row     grid (rows):    the S * C survivors of a row -> the row's top C, and (max, log sum exp) from the slices in slice order
+//   beam_group   grid (G):       the K * C survivors of a prompt with their accumulated values -> the C best (value, flat index)
+// A candidate is ONE 64-bit key: the order-preserving image of its fp32 value in the high word, ~index in the low word - the larger key
+// is the larger value, and among equal values the lower index.  The top C of a workgroup's keys are C rounds of a block maximum (a
+// shuffle tree per wave, four partial maxima through LDS, one barrier per round); the winner is cleared in whichever thread holds it.
+// Every sum has a fixed order (per thread in index order, the shuffle tree, the waves and the slices in order): the same inputs give the
+// same bits, eager or replayed.  Candidates enter a row's top C by their raw logit (ties: the lower index), and the prompt's top C by
+// their accumulated value (ties: the lower flat index).
+//
+// dec_cache_gather: new row r of every layer's K and V (slots [0, *len)), of the key-valid mask and of the next positions = old row
+// src[r].  Never in place (a swap would read what it has just overwritten): a layer is gathered into a scratch and copied back by the
+// NEXT launch, which at the same time gathers the next layer into the scratch's other half - L + 1 launches for L layers, the mask and the
+// positions riding on the first two.  Rows with src[r] == r leave at once, in both directions.  Every workgroup checks all of src first:
+// one index outside [0, rows_in) and no launch writes anything but the error word (3).
+#include <algorithm>
+
+#include "fvhd_common.h"
+#include "launchers.h"      // (with llm_decode.h: DecCacheGatherArgs)
+
+namespace {
+
+typedef unsigned long long u64;
+
+constexpr int SLICE = 4096;                      // logits per beam_slice workgroup: 16 per thread
+constexpr int SMAXB = 64;                        // slices per row at most (V <= SLICE * SMAXB)
+constexpr int CMAX = 64;
+constexpr int RMAX = 64;                         // rows = G * K
+
+// order-preserving key of an fp32 value (llm_sample.hip's): a > b <=> key(a) > key(b); -0 and +0 share one key
+FVHD_DEV unsigned okey(float s)
+{
+    unsigned u = __float_as_uint(s);
+    if (u == 0x80000000u) u = 0;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+FVHD_DEV float key_value(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+// 0 = no candidate: below every real key (the key of -inf is 0x007fffff........)
+FVHD_DEV u64 make_key(float v, unsigned idx) { return ((u64)okey(v) << 32) | (0xffffffffu - idx); }
+FVHD_DEV float cand_value(u64 k) { return key_value((unsigned)(k >> 32)); }
+FVHD_DEV unsigned cand_index(u64 k) { return 0xffffffffu - (unsigned)k; }
+
+FVHD_DEV u64 wave_max(u64 v)
+{
+#pragma unroll
+    for (int o = 32; o; o >>= 1) {
+        const unsigned hi = (unsigned)__shfl_xor((int)(v >> 32), o), lo = (unsigned)__shfl_xor((int)(unsigned)v, o);
+        const u64 w = ((u64)hi << 32) | lo;
+        v = w > v ? w : v;
+    }
+    return v;
+}
+
+FVHD_DEV float wave_sum(float v)
+{
+#pragma unroll
+    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);      // a fixed tree: every lane ends with the same bits
+    return v;
+}
+
+// the block maximum of one key per thread; `red`: 4 LDS words of the caller, free again after the next barrier
+FVHD_DEV u64 block_max(u64 v, u64* red)
+{
+    v = wave_max(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const u64 a = red[0] > red[1] ? red[0] : red[1], b = red[2] > red[3] ? red[2] : red[3];
+    return a > b ? a : b;
+}
+
+// the C largest of the workgroup's keys (EPT per thread, real keys are distinct) -> out[0 .. C) in descending order (LDS or global;
+// exhausted: 0).  `red`: 8 LDS words, used alternately, so that one barrier per round is enough.
+template <int EPT>
+FVHD_DEV void block_top(u64 (&key)[EPT], int C, u64* out, u64* red)
+{
+    for (int c = 0; c < C; ++c) {
+        u64 best = 0;
+#pragma unroll
+        for (int j = 0; j < EPT; ++j) best = key[j] > best ? key[j] : best;
+        best = block_max(best, red + 4 * (c & 1));
+#pragma unroll
+        for (int j = 0; j < EPT; ++j) key[j] = key[j] == best ? 0 : key[j];
+        if (threadIdx.x == 0) out[c] = best;
+    }
+}
+
+__global__ __launch_bounds__(256) void beam_slice_kernel(const float* __restrict__ logits, int V, int S, int C, u64* __restrict__ keys,
+                                                         float* __restrict__ pmax, float* __restrict__ psum)
+{
+    __shared__ u64 red[8];
+    __shared__ float fred[4];
+    const int s = blockIdx.x, row = blockIdx.y, t = threadIdx.x;
+    const float* x = logits + (size_t)row * V;
+    u64 key[16];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int e = s * SLICE + (j * 256 + t) * 4;
+        if (e < V) {                                             // V % 16 == 0: a float4 lies inside the row or outside it
+            const f32x4 v = *(const f32x4*)(x + e);
+            key[4 * j + 0] = make_key(v[0], e); key[4 * j + 1] = make_key(v[1], e + 1);
+            key[4 * j + 2] = make_key(v[2], e + 2); key[4 * j + 3] = make_key(v[3], e + 3);
+        } else {
+            key[4 * j + 0] = key[4 * j + 1] = key[4 * j + 2] = key[4 * j + 3] = 0;
+        }
+    }
+    u64 best = 0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) best = key[j] > best ? key[j] : best;
+    const float m = cand_value(block_max(best, red));            // (every slice holds at least 16 logits)
+    float acc = 0.f;
+    if (m > -INFINITY) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+            if (key[j]) acc += expf(cand_value(key[j]) - m);
+    }
+    acc = wave_sum(acc);
+    if ((t & 63) == 0) fred[t >> 6] = acc;
+    __syncthreads();                                             // (also: `red` is free for block_top)
+    if (t == 0) {
+        pmax[row * S + s] = m;
+        psum[row * S + s] = ((fred[0] + fred[1]) + fred[2]) + fred[3];
+    }
+    block_top<16>(key, C, keys + ((size_t)row * S + s) * C, red);
+}
+
+__global__ __launch_bounds__(256) void beam_row_kernel(const u64* __restrict__ keys, const float* __restrict__ pmax, const float* __restrict__ psum,
+                                                       int S, int C, u64* __restrict__ rowtop, float* __restrict__ rowmax, float* __restrict__ rowlog)
+{
+    __shared__ u64 red[8];
+    const int row = blockIdx.x, t = threadIdx.x, n = S * C;      // n <= 4096
+    u64 key[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const int i = j * 256 + t;
+        key[j] = i < n ? keys[(size_t)row * n + i] : 0;
+    }
+    if (t == 0) {
+        float M = -INFINITY;
+        for (int s = 0; s < S; ++s) M = fmaxf(M, pmax[row * S + s]);
+        float sum = 0.f;
+        for (int s = 0; s < S; ++s) {
+            const float ms = pmax[row * S + s];
+            if (ms > -INFINITY) sum += psum[row * S + s] * expf(ms - M);
+        }
+        rowmax[row] = M;
+        rowlog[row] = logf(sum);
+    }
+    block_top<16>(key, C, rowtop + (size_t)row * C, red);
+}
+
+__global__ __launch_bounds__(256) void beam_group_kernel(const u64* __restrict__ rowtop, const float* __restrict__ rowmax, const float* __restrict__ rowlog,
+                                                         const float* __restrict__ scores, int K, int C, int V, float* __restrict__ out_v,
+                                                         int64_t* __restrict__ out_i)
+{
+    __shared__ u64 red[8];
+    __shared__ u64 top[CMAX];
+    const int g = blockIdx.x, t = threadIdx.x, n = K * C;        // n <= 1024
+    u64 key[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int i = j * 256 + t;
+        key[j] = 0;
+        if (i < n) {
+            const int k = i / C, row = g * K + k;
+            const u64 c = rowtop[(size_t)row * C + i % C];
+            if (c) {
+                const float acc = ((cand_value(c) - rowmax[row]) - rowlog[row]) + scores[row];
+                key[j] = make_key(acc, (unsigned)k * (unsigned)V + cand_index(c));
+            }
+        }
+    }
+    block_top<4>(key, C, top, red);
+    __syncthreads();
+    if (t < C) {
+        const u64 c = top[t];
+        out_v[(size_t)g * C + t] = c ? cand_value(c) : -INFINITY;
+        out_i[(size_t)g * C + t] = c ? (int64_t)cand_index(c) : 0;
+    }
+}
+
+struct TopkWs { u64* keys; float* pmax; float* psum; u64* rowtop; float* rowmax; float* rowlog; };
+
+size_t al256b(size_t x) { return (x + 255) & ~(size_t)255; }
+
+TopkWs carve_topk(void* base)
+{
+    char* p = (char*)base;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char* q = p + off; off += al256b(bytes); return q; };
+    TopkWs w;
+    w.keys = (u64*)take((size_t)8 * RMAX * SMAXB * CMAX);
+    w.pmax = (float*)take(4 * RMAX * SMAXB);
+    w.psum = (float*)take(4 * RMAX * SMAXB);
+    w.rowtop = (u64*)take(8 * RMAX * CMAX);
+    w.rowmax = (float*)take(4 * RMAX);
+    w.rowlog = (float*)take(4 * RMAX);
+    return w;
+}
+
+// one direction of the reorder: row r of `dst` = row (indirect ? src[r] : r) of `from`, for the rows with src[r] != r
+struct CacheMove {
+    const char* from_k = nullptr;      // K and V of one layer, rows of nkv * cap * hd bf16 (NULL: this launch moves no layer in this direction)
+    const char* from_v = nullptr;
+    char* to_k = nullptr;
+    char* to_v = nullptr;
+    const unsigned char* from_m = nullptr;     // the key-valid mask rows [cap] and the next positions (NULL: not in this launch)
+    unsigned char* to_m = nullptr;
+    const int64_t* from_p = nullptr;
+    int64_t* to_p = nullptr;
+    int indirect = 0;
+};
+
+struct CacheMoveArgs {
+    CacheMove job[2];                  // blockIdx.z: 0 = gather a layer into the scratch, 1 = copy the previous layer back from it
+    const int64_t* src;
+    int rows_in, rows_out, nkv, hd, cap;
+    const int* len;
+    int* status;
+    int* status_host;
+};
+
+__global__ __launch_bounds__(256) void dec_cache_move_kernel(CacheMoveArgs a)
+{
+    __shared__ int bad;
+    const CacheMove& j = a.job[blockIdx.z];
+    const int t = threadIdx.x;
+    if (t == 0) bad = 0;
+    __syncthreads();
+    if (t < a.rows_out) {
+        const int64_t s = a.src[t];
+        if (s < 0 || s >= a.rows_in) bad = 1;
+    }
+    __syncthreads();
+    const int st = *(volatile const int*)a.status;
+    if (bad) {                                                   // every workgroup of every launch finds the same: nothing is written
+        if (!st && t == 0 && blockIdx.x == 0 && blockIdx.y == 0) {
+            *a.status = 3;
+            if (a.status_host) *a.status_host = 3;
+        }
+        return;
+    }
+    if (st) return;
+    const int per_row = 2 * a.nkv + 1, r = blockIdx.y / per_row, w = blockIdx.y % per_row;
+    const int64_t s = a.src[r];
+    if (s == r) return;
+    const int64_t from = j.indirect ? s : r;
+    const int len = min(*a.len, a.cap);
+    if (w < 2 * a.nkv) {
+        if (!j.to_k) return;
+        const size_t head = (size_t)a.cap * a.hd * 2, off = (size_t)(w >> 1) * head, rowb = (size_t)a.nkv * head;
+        const u32x4* sp = (const u32x4*)(((w & 1) ? j.from_v : j.from_k) + from * rowb + off);
+        u32x4* dp = (u32x4*)(((w & 1) ? j.to_v : j.to_k) + r * rowb + off);
+        const int n16 = len * a.hd / 8;                          // hd % 8 == 0: whole 16-byte words
+        for (int i = blockIdx.x * 256 + t; i < n16; i += gridDim.x * 256) dp[i] = sp[i];
+    } else {
+        if (!j.to_m) return;
+        for (int i = blockIdx.x * 256 + t; i < len; i += gridDim.x * 256) j.to_m[(size_t)r * a.cap + i] = j.from_m[from * a.cap + i];
+        if (blockIdx.x == 0 && t == 0) j.to_p[r] = j.from_p[from];
+    }
+}
+
+}  // namespace
+
+extern "C" size_t fvhd_dec_beam_topk_ws_bytes(void)
+{
+    return al256b((size_t)8 * RMAX * SMAXB * CMAX) + 2 * al256b(4 * RMAX * SMAXB) + al256b(8 * RMAX * CMAX) + 2 * al256b(4 * RMAX);
+}
+
+extern "C" int fvhd_dec_beam_topk_supported(int G, int K, int C, int V)
+{
+    return G >= 1 && K >= 2 && K <= 16 && C >= 1 && C <= CMAX && C <= V && G * K <= RMAX && V >= 16 && V % 16 == 0 && V <= SLICE * SMAXB;
+}
+
+extern "C" int fvhd_launch_dec_beam_topk(hipStream_t st, const float* logits, const float* scores, int G, int K, int C, int V, float* out_v, int64_t* out_i,
+                                         void* ws)
+{
+    if (!fvhd_dec_beam_topk_supported(G, K, C, V) || ((uintptr_t)logits & 15)) return (int)hipErrorInvalidValue;
+    const TopkWs w = carve_topk(ws);
+    const int rows = G * K, S = (V + SLICE - 1) / SLICE;
+    hipLaunchKernelGGL(beam_slice_kernel, dim3(S, rows), dim3(256), 0, st, logits, V, S, C, w.keys, w.pmax, w.psum);
+    hipLaunchKernelGGL(beam_row_kernel, dim3(rows), dim3(256), 0, st, w.keys, w.pmax, w.psum, S, C, w.rowtop, w.rowmax, w.rowlog);
+    hipLaunchKernelGGL(beam_group_kernel, dim3(G), dim3(256), 0, st, w.rowtop, w.rowmax, w.rowlog, scores, K, C, V, out_v, out_i);
+    return (int)hipGetLastError();
+}
+
+// scratch: two halves of (K | V of `rows` rows), then `rows` mask rows, then `rows` positions
+extern "C" size_t fvhd_dec_cache_gather_ws_bytes(int rows, int nkv, int hd, int cap)
+{
+    const size_t rowb = (size_t)nkv * cap * hd * 2;
+    return 4 * al256b((size_t)rows * rowb) + al256b((size_t)rows * cap) + al256b((size_t)rows * 8);
+}
+
+extern "C" int fvhd_launch_dec_cache_gather(hipStream_t st, const DecCacheGatherArgs* g)
+{
+    if (g->layers < 1 || g->rows_in < 1 || g->rows_out < 1 || g->rows_in > g->batch || g->rows_out > g->batch || g->batch > RMAX || g->nkv < 1 ||
+        g->hd < 8 || g->hd % 8 || g->cap < 1 || ((uintptr_t)g->kc & 15) || ((uintptr_t)g->vc & 15) || ((uintptr_t)g->ws & 15))
+        return (int)hipErrorInvalidValue;
+    const size_t rowb = (size_t)g->nkv * g->cap * g->hd * 2, layer = (size_t)g->batch * rowb, half = al256b((size_t)g->batch * rowb);
+    char* sm = g->ws + 4 * half;
+    char* sp = sm + al256b((size_t)g->batch * g->cap);
+    CacheMoveArgs a;
+    a.src = g->src; a.rows_in = g->rows_in; a.rows_out = g->rows_out; a.nkv = g->nkv; a.hd = g->hd; a.cap = g->cap; a.len = g->len;
+    a.status = g->status; a.status_host = g->status_host;
+    const int gx = (int)std::min<size_t>(8, ((size_t)g->cap * g->hd / 8 + 255) / 256);
+    for (int i = 0; i <= g->layers; ++i) {
+        a.job[0] = CacheMove();
+        a.job[1] = CacheMove();
+        if (i < g->layers) {
+            CacheMove& m = a.job[0];
+            char* h = g->ws + 2 * half * (i & 1);
+            m.from_k = g->kc + i * layer; m.from_v = g->vc + i * layer; m.to_k = h; m.to_v = h + half; m.indirect = 1;
+            if (i == 0) { m.from_m = g->mask; m.to_m = (unsigned char*)sm; m.from_p = g->posv; m.to_p = (int64_t*)sp; }
+        }
+        if (i > 0) {
+            CacheMove& m = a.job[1];
+            char* h = g->ws + 2 * half * ((i - 1) & 1);
+            m.from_k = h; m.from_v = h + half; m.to_k = g->kc + (i - 1) * layer; m.to_v = g->vc + (i - 1) * layer;
+            if (i == 1) { m.from_m = (const unsigned char*)sm; m.to_m = g->mask; m.from_p = (const int64_t*)sp; m.to_p = g->posv; }
+        }
+        hipLaunchKernelGGL(dec_cache_move_kernel, dim3(gx, g->rows_out * (2 * g->nkv + 1), 2), dim3(256), 0, st, a);
+    }
+    return (int)hipGetLastError();
+}

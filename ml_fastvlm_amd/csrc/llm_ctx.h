@@ -76,6 +76,9 @@ struct __attribute__((visibility("default"))) fvhd_llm {     // (its inline cons
     int top_k = 0;
     unsigned long long seed = 0;
     char* sws = nullptr;                   // the sampler's workspace (inside `dc`)
+    // fvhd_llm_beam_reserve: one allocation of its own (fvhd_llm_cache_reserve's footprint is what it was), sized for the reserved cache
+    char* beam = nullptr;                  // the reorder's scratch (llm_beam.hip: two layers' K | V, the mask, the positions), then the top-K workspace
+    char* beam_topk = nullptr;
 };
 
 inline int lfail(const std::string& m) { return fvhd_set_error(m.c_str()); }

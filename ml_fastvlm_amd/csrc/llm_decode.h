@@ -61,3 +61,19 @@ struct DecSampleArgs {
     int* len_advance = nullptr;    // non-NULL: *len_advance += 1 once every row (of the last block) has read n
     const int* status = nullptr;
 };
+
+// Arguments of the KV-cache reorder (llm_beam.hip): row r of every layer's K / V (slots [0, *len)), of the mask and of the positions = row src[r].
+struct DecCacheGatherArgs {
+    char* kc = nullptr;            // K and V of all layers, bf16 [layers][batch][nkv][cap][hd]
+    char* vc = nullptr;
+    int layers = 0, batch = 0;     // batch: rows of the allocation (the layer stride)
+    unsigned char* mask = nullptr; // key-valid [batch][cap]
+    int64_t* posv = nullptr;       // next positions [batch]
+    const int64_t* src = nullptr;  // int64 [rows_out] on the device, every entry in [0, rows_in)
+    int rows_in = 0, rows_out = 0; // both <= batch
+    int nkv = 0, hd = 0, cap = 0;
+    const int* len = nullptr;      // device word: slots [0, *len) move
+    int* status = nullptr;         // the launches do nothing while *status != 0; an index out of range sets it (and *status_host, optional) to 3
+    int* status_host = nullptr;
+    char* ws = nullptr;            // fvhd_dec_cache_gather_ws_bytes(batch, nkv, hd, cap) bytes
+};

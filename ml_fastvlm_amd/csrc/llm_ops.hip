@@ -232,4 +232,54 @@ int fvhd_op_dec_sample(fvhd_stream_t st, const float* logits, int B, int V, floa
     return lret("fvhd_op_dec_sample", fvhd_launch_dec_sample((hipStream_t)st, &a, ws[dev]));
 }
 
+// the beam search's two operations on their own: process-wide scratch, allocated / grown on demand - eager calls only
+static int op_scratch(const char* who, char* (&buf)[64], size_t (&cap)[64], size_t need, char** out)
+{
+    int dev = 0;
+    hipError_t he = hipGetDevice(&dev);
+    if (he != hipSuccess) return lhip("hipGetDevice", he);
+    if (dev < 0 || dev >= 64) return lfail(std::string(who) + ": device index out of range");
+    if (need > cap[dev]) {
+        if (buf[dev]) (void)hipFree(buf[dev]);                      // (synchronises: no earlier launch still uses it)
+        buf[dev] = nullptr;
+        cap[dev] = 0;
+        if ((he = hipMalloc((void**)&buf[dev], need)) != hipSuccess) { buf[dev] = nullptr; return lhip("hipMalloc(beam search scratch)", he); }
+        cap[dev] = need;
+    }
+    *out = buf[dev];
+    return 0;
+}
+
+int fvhd_op_dec_beam_topk(fvhd_stream_t st, const float* logits, const float* beam_scores, int groups, int num_beams, int keep, int V, float* cand_scores,
+                          int64_t* cand_index)
+{
+    if (!logits || !beam_scores || !cand_scores || !cand_index) return lfail("fvhd_op_dec_beam_topk: NULL pointer");
+    if (!fvhd_dec_beam_topk_supported(groups, num_beams, keep, V) || ((uintptr_t)logits & 15))
+        return lfail("fvhd_op_dec_beam_topk: needs groups >= 1, 2 <= num_beams <= 16, 1 <= keep <= 64, keep <= V, groups * num_beams <= 64, V % 16 == 0, "
+                     "V <= 262144 and logits aligned to 16 bytes");
+    static char* buf[64] = {};
+    static size_t cap[64] = {};
+    char* ws = nullptr;
+    if (int e = op_scratch("fvhd_op_dec_beam_topk", buf, cap, fvhd_dec_beam_topk_ws_bytes(), &ws)) return e;
+    return lret("fvhd_op_dec_beam_topk", fvhd_launch_dec_beam_topk((hipStream_t)st, logits, beam_scores, groups, num_beams, keep, V, cand_scores, cand_index, ws));
+}
+
+int fvhd_op_dec_cache_gather(fvhd_stream_t st, void* k_cache, void* v_cache, uint8_t* key_valid, int64_t* positions, const int64_t* src_rows, int n_layers,
+                             int batch, int rows_in, int rows_out, int n_kv_heads, int head_dim, int capacity, const int* length, int* status)
+{
+    if (!k_cache || !v_cache || !key_valid || !positions || !src_rows || !length || !status) return lfail("fvhd_op_dec_cache_gather: NULL pointer");
+    if (n_layers < 1 || batch < 1 || batch > 64 || rows_in < 1 || rows_in > batch || rows_out < 1 || rows_out > batch || n_kv_heads < 1 || head_dim < 8 ||
+        head_dim % 8 || capacity < 1 || ((uintptr_t)k_cache & 15) || ((uintptr_t)v_cache & 15))
+        return lfail("fvhd_op_dec_cache_gather: needs n_layers >= 1, 1 <= rows_in, rows_out <= batch <= 64, head_dim % 8 == 0, capacity >= 1 and caches "
+                     "aligned to 16 bytes");
+    static char* buf[64] = {};
+    static size_t cap[64] = {};
+    char* ws = nullptr;
+    if (int e = op_scratch("fvhd_op_dec_cache_gather", buf, cap, fvhd_dec_cache_gather_ws_bytes(batch, n_kv_heads, head_dim, capacity), &ws)) return e;
+    DecCacheGatherArgs a;
+    a.kc = (char*)k_cache; a.vc = (char*)v_cache; a.layers = n_layers; a.batch = batch; a.mask = key_valid; a.posv = positions; a.src = src_rows;
+    a.rows_in = rows_in; a.rows_out = rows_out; a.nkv = n_kv_heads; a.hd = head_dim; a.cap = capacity; a.len = length; a.status = status; a.ws = ws;
+    return lret("fvhd_op_dec_cache_gather", fvhd_launch_dec_cache_gather((hipStream_t)st, &a));
+}
+
 }  // extern "C"

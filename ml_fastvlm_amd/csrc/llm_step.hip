@@ -1,5 +1,5 @@
 // C ABI of the Qwen2 decode (include/fvhd.h "LLM decode"): the library's own KV cache, one token per sequence per step.
-// Kernels: llm_decode.hip, llm_w8.hip, llm_sample.hip.
+// Kernels: llm_decode.hip, llm_w8.hip, llm_sample.hip, llm_beam.hip.
 #include <cmath>
 
 #include "llm_ctx.h"
@@ -35,6 +35,7 @@ int dec_status_error(const fvhd_llm* c, const char* who)
         return lfail(std::string(who) + ": the KV cache is full (capacity " + std::to_string(c->dc_cap) +
                      " positions): a decode step past it wrote nothing - reserve a larger cache (fvhd_llm_cache_reserve) and start again");
     if (st == 2) return lfail(std::string(who) + ": a decode step was given a token id outside [0, vocab); it wrote nothing - start again");
+    if (st == 3) return lfail(std::string(who) + ": a cache reorder was given a row index outside [0, rows_in); it wrote nothing - start again");
     return 0;
 }
 
@@ -109,7 +110,8 @@ int fvhd_llm_cache_reserve(fvhd_llm* c, int batch, int capacity)
     hipError_t he = hipDeviceSynchronize();                      // refused while a stream is being captured (like fvhd_llm_reserve)
     if (he != hipSuccess) return lhip("fvhd_llm_cache_reserve: hipDeviceSynchronize", he);
     if (c->dc) (void)hipFree(c->dc);
-    c->dc = nullptr;
+    if (c->beam) (void)hipFree(c->beam);                         // sized for the cache it was reserved for: fvhd_llm_beam_reserve again
+    c->dc = c->beam = c->beam_topk = nullptr;
     c->dc_batch = c->dc_cap = c->run_batch = 0;
     if ((he = hipMalloc((void**)&c->dc, a.off)) != hipSuccess) return lhip("hipMalloc(llm KV cache)", he);
     if ((he = hipMemset(c->dc, 0, a.off)) != hipSuccess) return lhip("hipMemset(llm KV cache)", he);      // counters start at zero
@@ -249,6 +251,53 @@ int fvhd_llm_decode(fvhd_llm* c, const int64_t* token_ids, float* logits_out, in
     LCHECK(fvhd_launch_dec_gemm(st, &a), "decode final norm + lm_head + argmax");
     LCHECK(fvhd_launch_dec_argmax_finish(st, c->amax_v, c->amax_i, (c->V / 16 + 3) / 4, B, c->last_ids, next_ids_out, c->posv, c->len, c->status),
            "decode argmax reduce");
+    return 0;
+}
+
+int fvhd_llm_beam_reserve(fvhd_llm* c)
+{
+    if (!c || !c->dc) return lfail("fvhd_llm_beam_reserve: no KV cache - call fvhd_llm_cache_reserve first");
+    LLM_ON_DEVICE(c);
+    hipError_t he = hipDeviceSynchronize();                      // refused while a stream is being captured (like fvhd_llm_cache_reserve)
+    if (he != hipSuccess) return lhip("fvhd_llm_beam_reserve: hipDeviceSynchronize", he);
+    if (c->beam) return 0;                                       // (fvhd_llm_cache_reserve frees it with the cache it was sized for)
+    Arena a;
+    const size_t o_gather = a.take(fvhd_dec_cache_gather_ws_bytes(c->dc_batch, c->nkv, c->hd, c->dc_cap)), o_topk = a.take(fvhd_dec_beam_topk_ws_bytes());
+    if ((he = hipMalloc((void**)&c->beam, a.off)) != hipSuccess) { c->beam = nullptr; return lhip("hipMalloc(beam search scratch)", he); }
+    c->beam_topk = c->beam + o_topk;
+    (void)o_gather;
+    return 0;
+}
+
+int fvhd_llm_cache_gather(fvhd_llm* c, const int64_t* src_rows, int rows_in, int rows_out, fvhd_stream_t stream)
+{
+    if (!c || !src_rows) return lfail("fvhd_llm_cache_gather: NULL argument");
+    if (!c->dc || !c->run_batch) return lfail("fvhd_llm_cache_gather: no started sequence - call fvhd_llm_cache_reserve and fvhd_llm_start first");
+    if (!c->beam) return lfail("fvhd_llm_cache_gather: no scratch - call fvhd_llm_beam_reserve first");
+    if (rows_in < 1 || rows_in > c->dc_batch || rows_out < 1 || rows_out > c->dc_batch)
+        return lfail("fvhd_llm_cache_gather: rows_in and rows_out must be in [1, the batch of fvhd_llm_cache_reserve]");
+    if (int e = dec_status_error(c, "fvhd_llm_cache_gather")) return e;
+    LLM_ON_DEVICE(c);
+    DecCacheGatherArgs a;
+    a.kc = c->kcache; a.vc = c->vcache; a.layers = c->L; a.batch = c->dc_batch; a.mask = c->mask; a.posv = c->posv; a.src = src_rows;
+    a.rows_in = rows_in; a.rows_out = rows_out; a.nkv = c->nkv; a.hd = c->hd; a.cap = c->dc_cap; a.len = c->len; a.status = c->status;
+    a.status_host = c->status_host_dev; a.ws = c->beam;
+    LCHECK(fvhd_launch_dec_cache_gather((hipStream_t)stream, &a), "cache reorder");
+    c->run_batch = rows_out;
+    return 0;
+}
+
+int fvhd_llm_beam_topk(fvhd_llm* c, const float* logits, const float* beam_scores, int groups, int num_beams, int keep, float* cand_scores,
+                       int64_t* cand_index, fvhd_stream_t stream)
+{
+    if (!c || !logits || !beam_scores || !cand_scores || !cand_index) return lfail("fvhd_llm_beam_topk: NULL argument");
+    if (!c->beam) return lfail("fvhd_llm_beam_topk: no workspace - call fvhd_llm_beam_reserve first");
+    if (!fvhd_dec_beam_topk_supported(groups, num_beams, keep, c->V) || ((uintptr_t)logits & 15))
+        return lfail("fvhd_llm_beam_topk: needs groups >= 1, 2 <= num_beams <= 16, 1 <= keep <= 64, keep <= vocab, groups * num_beams <= 64, "
+                     "vocab % 16 == 0, vocab <= 262144 and logits aligned to 16 bytes");
+    LLM_ON_DEVICE(c);
+    LCHECK(fvhd_launch_dec_beam_topk((hipStream_t)stream, logits, beam_scores, groups, num_beams, keep, c->V, cand_scores, cand_index, c->beam_topk),
+           "beam top-K");
     return 0;
 }
 

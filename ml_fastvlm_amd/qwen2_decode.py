@@ -14,6 +14,9 @@ replays for the whole generation.
 where every sequence has finished, finished sequences padded with `pad_token_id`.  `sample` does the same with transformers' multinomial
 sampling (temperature / top-k / top-p, include/fvhd.h "LLM sampling") chosen on the device inside the captured step: the same
 distribution as transformers', not the same draws (the random numbers are Philox4x32-10 keyed by the seed, `philox_uniform`).
+`beam_search` runs transformers' beam search (`num_beams` = K > 1): the K beams of G prompts are G * K rows of the same step, the top
+continuations and the KV-cache reorder are two more device operations (include/fvhd.h "LLM beam search"), and the [G, 2 K]-sized
+bookkeeping is `ml_fastvlm_amd.beam.BeamSearchState` - all of it inside the one captured graph per step.
 """
 from __future__ import annotations
 
@@ -131,8 +134,44 @@ class Qwen2Generator:
                        "fvhd_llm_decode")
         return lg, self._ids[:B]
 
+    # ---- beam search: the two device operations -----------------------------------------------------------------------------------------
+    def beam_reserve(self) -> None:
+        """the reorder's scratch and the top-K workspace for this cache (`fvhd_llm_beam_reserve`; once per generator, synchronises)"""
+        if not getattr(self, "_beam_reserved", False):
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.beam_lib().fvhd_llm_beam_reserve(self.pre._h), "fvhd_llm_beam_reserve")
+            self._beam_reserved = True
+
+    @torch.no_grad()
+    def cache_gather(self, src_rows: torch.Tensor, rows_in: int) -> None:
+        """cache row r (K / V of every layer, mask, next position) = old row src_rows[r] (`fvhd_llm_cache_gather`); the following steps run
+        on len(src_rows) rows.  src_rows: int64 on the device, entries in [0, rows_in).  Capture-safe after `beam_reserve`."""
+        if src_rows.dtype != torch.long or src_rows.device != self.device or src_rows.dim() != 1 or not src_rows.is_contiguous():
+            raise ValueError(f"src_rows must be a contiguous 1-D int64 tensor on {self.device}")
+        rows_out = src_rows.shape[0]
+        if not (1 <= rows_in <= self.batch and 1 <= rows_out <= self.batch):
+            raise ValueError(f"rows_in {rows_in} / rows_out {rows_out} exceed the reserved batch {self.batch}")
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.beam_lib().fvhd_llm_cache_gather(self.pre._h, _lib.ptr(src_rows), int(rows_in), rows_out, _lib.stream_ptr(self.device)),
+                       "fvhd_llm_cache_gather")
+        self._run_batch = rows_out
+
+    @torch.no_grad()
+    def beam_topk(self, logits: torch.Tensor, beam_scores: torch.Tensor, keep: int, out_scores: torch.Tensor, out_index: torch.Tensor) -> None:
+        """per prompt the `keep` best of log_softmax(logits [G * K, vocab]) + beam_scores [G, K] -> out_scores fp32 [G, keep], out_index
+        int64 [G, keep] = beam * vocab + token (`fvhd_llm_beam_topk`).  Capture-safe after `beam_reserve`."""
+        G, K = beam_scores.shape
+        for t, dt, shape in ((logits, torch.float32, (G * K, self.pre.vocab)), (beam_scores, torch.float32, (G, K)),
+                             (out_scores, torch.float32, (G, keep)), (out_index, torch.long, (G, keep))):
+            if t.dtype != dt or t.device != self.device or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"beam_topk: expected a contiguous {dt} tensor {shape} on {self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.beam_lib().fvhd_llm_beam_topk(self.pre._h, _lib.ptr(logits), _lib.ptr(beam_scores), G, K, int(keep), _lib.ptr(out_scores),
+                                                          _lib.ptr(out_index), _lib.stream_ptr(self.device)), "fvhd_llm_beam_topk")
+
     def cache_state(self):
-        """(length, error word) after a device synchronisation; error 1 = a step ran past the capacity"""
+        """(length, error word) after a device synchronisation; error 1 = a step ran past the capacity, 2 = a token id out of range, 3 = a
+        cache reorder's row index out of range"""
         n, st = C.c_int(0), C.c_int(0)
         _lib.check(_lib.load().fvhd_llm_cache_state(self.pre._h, C.byref(n), C.byref(st)), "fvhd_llm_cache_state")
         return n.value, st.value
@@ -235,3 +274,74 @@ class Qwen2Generator:
             if dead.numel():
                 n = int(dead[0, 0]) + 1
         return out[:, :n].clone()
+
+    @torch.no_grad()
+    def beam_search(self, inputs_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None,
+                    num_beams: int = 4, max_new_tokens: int = 256, length_penalty: float = 1.0, early_stopping: Union[bool, str] = False,
+                    num_return_sequences: int = 1, eos_token_id: Union[None, int, Sequence[int]] = None, pad_token_id: Optional[int] = None,
+                    graph: bool = True, poll_every: int = 16, return_scores: bool = False):
+        """transformers' beam search (`GenerationMixin._beam_search`, do_sample=False) on the library's steps -> new tokens
+        [G * num_return_sequences, n], with return_scores also the `sequences_scores` [G * num_return_sequences]: what
+        generate(inputs_embeds=..., num_beams=K) returns - per prompt its best finished hypotheses in descending score order, finished rows
+        padded with `pad_token_id`, cropped to the longest one.
+        The prompt is prefilled ONCE per prompt (`start` on G rows); one cache reorder with src = r // K makes the G * K rows.  Then one
+        step = reorder by the previous step's parent rows -> `step(fed_ids)` under greedy settings, for its logits -> `beam_topk` ->
+        `BeamSearchState.update`, which writes the next fed_ids and parent rows; graph=True captures that step once (one linear stream) and
+        replays it, and "search finished" is polled every `poll_every` steps - a finished search ignores the steps that ran past it."""
+        from .beam import BeamSearchState
+        if num_beams < 2:
+            raise ValueError(f"beam_search needs num_beams >= 2 (got {num_beams}): one beam is `greedy`")
+        if max_new_tokens < 1:
+            raise ValueError("max_new_tokens must be >= 1")
+        G, T = inputs_embeds.shape[:2]
+        K = int(num_beams)
+        rows = G * K
+        if rows > _lib.MAX_DECODE_BATCH:
+            raise ValueError(f"beam_search: {G} prompts x {K} beams = {rows} rows, the decode takes at most {_lib.MAX_DECODE_BATCH} per step")
+        if rows > self.batch:
+            raise ValueError(f"beam_search: {G} prompts x {K} beams = {rows} rows exceed the reserved batch {self.batch}")
+        if T + max_new_tokens - 1 > self.capacity:
+            raise ValueError(f"prompt {T} + {max_new_tokens} new tokens need a cache of {T + max_new_tokens - 1} positions, reserved {self.capacity}")
+        dev = self.device
+        state = BeamSearchState(G, K, self.pre.vocab, max_new_tokens, length_penalty, early_stopping, num_return_sequences, eos_token_id,
+                                pad_token_id, device=dev)
+        self.beam_reserve()
+        self._set_greedy()
+        cand_scores = torch.zeros((G, state.keep), device=dev, dtype=torch.float32)
+        cand_index = torch.zeros((G, state.keep), device=dev, dtype=torch.long)
+        lg, _ = self.start(inputs_embeds, attention_mask, position_ids, logits=True)
+        # the first step: the K rows of a prompt are equal (transformers forwards K copies of the prompt; only beam 0 has score 0)
+        logits = self._logits[:rows]
+        logits.copy_(lg.repeat_interleave(K, dim=0))
+        self.cache_gather(torch.arange(rows, device=dev, dtype=torch.long) // K, G)
+        self.beam_topk(logits, state.running_beam_scores, state.keep, cand_scores, cand_index)
+        state.update(cand_scores, cand_index)
+
+        def one_step():
+            self.cache_gather(state.parent, rows)
+            step_logits, _ = self.step(state.fed_ids, logits=True)
+            self.beam_topk(step_logits, state.running_beam_scores, state.keep, cand_scores, cand_index)
+            state.update(cand_scores, cand_index)
+
+        steps = max_new_tokens - 1
+        g = None
+        if graph and steps > 0:
+            g = torch.cuda.CUDAGraph()
+            s = torch.cuda.Stream(dev)
+            s.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(s):
+                with torch.cuda.graph(g, stream=s):
+                    one_step()
+            torch.cuda.current_stream(dev).wait_stream(s)
+        done = 0
+        while done < steps:
+            if state.finished():                                 # host sync once per poll_every steps
+                break
+            for _ in range(min(poll_every, steps - done)):
+                if g is not None:
+                    g.replay()
+                else:
+                    one_step()
+            done += min(poll_every, steps - done)
+        tokens, scores = state.result()
+        return (tokens, scores) if return_scores else tokens

@@ -5,6 +5,7 @@ captured graph and called eagerly, against the stock `transformers` decode loop 
     python tools/decode_bench.py --sample [--hidden 896] [--batch 1 8]
     python tools/decode_bench.py --trace-steps 16 --hidden 3584 --batch 64      (eager steps only: the program of a kernel trace)
     python tools/decode_bench.py --weights fp8_e4m3 ...                         (the packed matrices as e4m3 codes + row scales)
+    python tools/decode_bench.py --num-beams 4 --hidden 896 3584 --batch 1 16   (beam search: --batch prompts x K beams per step)
 
 --batch takes up to 64 sequences per step (more than 16 need a library of version 503).  --repeats times the graph replay that many
 times (`graph_ms_per_token` is their median, `graph_ms_per_token_runs` all of them); --no-stock leaves the stock transformers loop (and
@@ -13,6 +14,11 @@ the eager library step) out - above 16 sequences it only measures transformers. 
 --sample times the sampled step (`Qwen2Generator.set_sampling`, csrc/llm_sample.hip) next to the greedy one, both by graph replay at
 vocab 151936, with predict.py's settings (temperature 0.2, top_k 50: transformers' default) and a flat one (temperature 1.0, top_k 0,
 top_p 0.95); greedy is timed before and after the sampled settings and averaged.
+
+--num-beams K times one beam-search step (`Qwen2Generator.beam_search`'s: cache reorder, decode step with logits, top continuations,
+bookkeeping) by graph replay over a whole search of --new tokens, and - each captured and replayed on its own, on the state the search
+left - its parts: the plain step on the same rows, the reorder (with the search's last parent map, and with the worst one: every row
+moves), the top-K launches and the torch bookkeeping; then the stock `transformers` beam search on the same prompts.
 
 Full layer counts, random bf16 weights (`tools/ttft.py: build_llm`).  Prints ONE JSON line: per (width, batch) the ms per token of each
 path, the bytes a step must read (packed weights + the KV cache at the mean length) and their fraction of 8 TB/s."""
@@ -168,6 +174,115 @@ def measure_sample(hidden: int, batch: int, prompt: int, new: int, dev) -> dict:
     return res
 
 
+def _graph_of(fn, dev):
+    graph = torch.cuda.CUDAGraph()
+    side = torch.cuda.Stream(dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        with torch.cuda.graph(graph, stream=side):
+            fn()
+    torch.cuda.current_stream(dev).wait_stream(side)
+    return graph
+
+
+@torch.no_grad()
+def measure_beam(llm, pre, groups: int, K: int, prompt: int, new: int, dev, repeats: int = 1, stock: bool = True, weights: str = "bf16") -> dict:
+    from ml_fastvlm_amd.beam import BeamSearchState
+    from ml_fastvlm_amd.qwen2_decode import Qwen2Generator
+    cfg = llm.config
+    hidden, rows, V = cfg.hidden_size, groups * K, cfg.vocab_size
+    gen = Qwen2Generator.from_hf(llm, rows, prompt + new + 4, prefill=pre, weights=weights)
+    g = torch.Generator(device=dev).manual_seed(0)
+    emb = (0.5 * torch.randn(groups, prompt, hidden, device=dev, generator=g)).to(torch.bfloat16)
+    mask = torch.ones(groups, prompt, device=dev, dtype=torch.long)
+    res = {"hidden": hidden, "layers": cfg.num_hidden_layers, "prompts": groups, "num_beams": K, "rows": rows, "vocab": V, "prompt": prompt,
+           "new_tokens": new, "weights": weights}
+    gen.beam_reserve()
+    gen._set_greedy()
+    keep = 2 * K
+    cand_s = torch.zeros((groups, keep), device=dev)
+    cand_i = torch.zeros((groups, keep), device=dev, dtype=torch.long)
+    expand = torch.arange(rows, device=dev) // K
+    box = {}
+
+    def begin():                                            # Qwen2Generator.beam_search up to its first update; the state tensors keep their addresses
+        st = box.get("state")
+        fresh = BeamSearchState(groups, K, V, new, device=dev)
+        if st is None:
+            st = box["state"] = fresh
+        else:
+            for name, t in vars(fresh).items():
+                if isinstance(t, torch.Tensor):
+                    getattr(st, name).copy_(t)
+        lg, _ = gen.start(emb, mask, logits=True)
+        gen._logits[:rows].copy_(lg.repeat_interleave(K, dim=0))
+        gen.cache_gather(expand, groups)
+        gen.beam_topk(gen._logits[:rows], st.running_beam_scores, keep, cand_s, cand_i)
+        st.update(cand_s, cand_i)
+        return st
+
+    st = begin()
+
+    def one_step():
+        gen.cache_gather(st.parent, rows)
+        lg, _ = gen.step(st.fed_ids, logits=True)
+        gen.beam_topk(lg, st.running_beam_scores, keep, cand_s, cand_i)
+        st.update(cand_s, cand_i)
+
+    full = _graph_of(one_step, dev)
+    runs, moved = [], []
+    for _ in range(max(1, repeats)):
+        begin()
+        runs.append(round(_ms_per(full.replay, new - 1, dev), 4))
+        assert gen.cache_state() == (prompt + new - 1, 0) and st.finished()
+    res["beam_step_ms"] = sorted(runs)[len(runs) // 2]
+    res["beam_step_ms_runs"] = runs
+    # the parts, each replayed on its own (the cache length is reset first: a step past the capacity would do nothing)
+    begin()
+    for _ in range(new // 2):
+        full.replay()
+    torch.cuda.synchronize(dev)
+    parent = st.parent.clone()
+    res["rows_moved_at_mid_search"] = int((parent != torch.arange(rows, device=dev)).sum())
+    worst = torch.roll(torch.arange(rows, device=dev), 1)
+    src = parent.clone()
+    parts = {"plain_step_with_logits": lambda: gen.step(st.fed_ids, logits=True), "plain_step": lambda: gen.step(st.fed_ids, logits=False),
+             "topk": lambda: gen.beam_topk(gen._logits[:rows], st.running_beam_scores, keep, cand_s, cand_i),
+             "bookkeeping": lambda: st.update(cand_s, cand_i), "gather": lambda: gen.cache_gather(src, rows)}
+    for name, fn in parts.items():
+        graph = _graph_of(fn, dev)
+        for tag, m in ((("_mid_search_map", parent), ("_every_row_moves", worst), ("_identity", torch.arange(rows, device=dev))) if name == "gather" else (("", None),)):
+            begin()
+            if name == "gather":
+                for _ in range(new // 2):                   # the cache at its mean length
+                    full.replay()
+                src.copy_(m)
+            res[f"{name}{tag}_ms"] = round(_ms_per(graph.replay, new - 1 if name.startswith("plain") else new // 2, dev), 4)
+    res["added_ms_over_plain_step"] = round(res["beam_step_ms"] - res["plain_step_ms"], 4)
+    nkv, hd = cfg.num_key_value_heads, hidden // cfg.num_attention_heads
+    res["logits_bytes"] = rows * V * 4
+    res["kv_bytes_moved_twice_if_every_row_moves"] = int(2 * 2 * cfg.num_hidden_layers * rows * nkv * (prompt + new / 2) * hd * 2)
+    if stock:
+        ref_kw = dict(inputs_embeds=emb, attention_mask=mask, num_beams=K, max_new_tokens=new, do_sample=False, eos_token_id=None, pad_token_id=0)
+        llm.generation_config.eos_token_id = None           # (random weights: no early end)
+        llm.generate(**dict(ref_kw, max_new_tokens=4))      # lazy initialisation stays out of the timing
+        torch.cuda.synchronize(dev)
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        llm.generate(**dict(ref_kw, max_new_tokens=1))
+        b.record()
+        torch.cuda.synchronize(dev)
+        first = a.elapsed_time(b)
+        a.record()
+        llm.generate(**ref_kw)
+        b.record()
+        torch.cuda.synchronize(dev)
+        res["stock_transformers_beam_ms_per_step"] = round((a.elapsed_time(b) - first) / (new - 1), 4)
+        res["speedup_beam_step_vs_stock"] = round(res["stock_transformers_beam_ms_per_step"] / res["beam_step_ms"], 2)
+    del gen
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--hidden", type=int, nargs="+", default=[896, 1536, 3584])
@@ -179,8 +294,25 @@ def main():
     ap.add_argument("--no-stock", action="store_true", help="leave out the stock transformers loop and the eager library step")
     ap.add_argument("--weights", choices=["bf16", "fp8_e4m3"], default="bf16", help="storage of the packed LLM matrices (fp8_e4m3 needs a library of version 504)")
     ap.add_argument("--trace-steps", type=int, default=0, help="run only the prefill and this many eager steps (for a kernel trace)")
+    ap.add_argument("--num-beams", type=int, default=0, help="time beam search with this many beams per prompt (--batch = prompts; needs a library of version 505)")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
+    if a.num_beams:
+        from tools.ttft import build_llm
+        from ml_fastvlm_amd import _lib
+        from ml_fastvlm_amd.qwen2_prefill import Qwen2Prefill
+        rows = []
+        for h in a.hidden:
+            llm = build_llm(h, dev)
+            pre = Qwen2Prefill.from_hf(llm, weights=a.weights)
+            for b in a.batch:
+                rows.append(measure_beam(llm, pre, b, a.num_beams, a.prompt, a.new, dev, repeats=a.repeats, stock=not a.no_stock, weights=a.weights))
+                torch.cuda.empty_cache()
+            del pre, llm
+            torch.cuda.empty_cache()
+        print(json.dumps({"tool": "decode_bench", "mode": "beam", "device": torch.cuda.get_device_name(dev), "library_version": _lib.beam_lib().fvhd_version(),
+                          "results": rows}))
+        return
     if a.sample:
         hidden = a.hidden if "--hidden" in sys.argv else [896]
         rows = [measure_sample(h, b, a.prompt, a.new, dev) for h in hidden for b in a.batch]
