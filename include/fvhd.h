@@ -56,8 +56,11 @@ typedef void* fvhd_stream_t; /* hipStream_t */
  * (fvhd_llm_set_weight_format, fvhd_llm_weight_bytes, fvhd_llm_debug_packed_e4m3, fvhd_op_quantize_e4m3, fvhd_op_dec_gemm_w8 / _qkv_w8 /
  * _lm_argmax_w8): bf16 stays the default and computes what 503 did, bit for bit; nothing earlier changed.  505 adds beam search
  * (fvhd_llm_beam_reserve, fvhd_llm_cache_gather, fvhd_llm_beam_topk, fvhd_op_dec_beam_topk, fvhd_op_dec_cache_gather; error word 3):
- * greedy and sampled steps compute what 504 did, bit for bit, and fvhd_llm_cache_reserve allocates what it did; nothing earlier changed. */
-#define FVHD_VERSION 505
+ * greedy and sampled steps compute what 504 did, bit for bit, and fvhd_llm_cache_reserve allocates what it did; nothing earlier changed.
+ * 506 adds logits processors in the decode step (fvhd_llm_set_logits_processors, fvhd_op_dec_logits_process): off by default, and then
+ * every launch of fvhd_llm_start / fvhd_llm_decode is what 505 enqueued, bit for bit; fvhd_llm_cache_reserve also allocates the token
+ * history (4 * batch * capacity + batch * vocab / 8 bytes); nothing earlier changed. */
+#define FVHD_VERSION 506
 int fvhd_version(void);
 const char* fvhd_last_error(void);
 
@@ -586,6 +589,44 @@ int fvhd_op_dec_beam_topk(fvhd_stream_t stream, const float* logits, const float
 int fvhd_op_dec_cache_gather(fvhd_stream_t stream, void* k_cache, void* v_cache, uint8_t* key_valid, int64_t* positions, const int64_t* src_rows,
                              int n_layers, int batch, int rows_in, int rows_out, int n_kv_heads, int head_dim, int capacity, const int* length,
                              int* status);
+
+/* ---- LLM logits processors: repetition penalty, no-repeat n-grams, min_new_tokens and token bans inside the step (version 506) ----------
+ * transformers' processors for num_beams = 1 (generation/logits_process.py), applied in its order and before temperature / top-k / top-p, to
+ * the fp32 logits of fvhd_llm_start / fvhd_llm_decode between the lm_head and the choice.  The HISTORY of a sequence is what transformers'
+ * processors see as input_ids when generate() is given inputs_embeds: the tokens fed to the decode steps since fvhd_llm_start (token_ids, or
+ * the ids the previous call chose) - not the prompt.  It is empty (g = 0) when fvhd_llm_start chooses the first token and holds g tokens
+ * when the g-th decode step chooses.
+ *   repetition_penalty p (finite, > 0; 1 = off): for every DISTINCT token t of the history s[t] = s[t] < 0 ? s[t] * p : s[t] / p, an IEEE
+ *     fp32 division; a token that occurs many times is penalised once (RepetitionPenaltyLogitsProcessor's gather / scatter).
+ *   no_repeat_ngram_size n (0 = off): when g >= n, every window h[i .. i+n-1] whose first n - 1 tokens equal the last n - 1 of the history
+ *     sets s[h[i+n-1]] = -inf (NoRepeatNGramLogitsProcessor); n = 1 bans every token of the history.
+ *   min_new_tokens m (0 = off) with eos_ids: while g < m every EOS id is -inf (MinNewTokensLengthLogitsProcessor(0, m, eos)) - the first
+ *     token included.  Without EOS ids it does nothing.
+ *   suppress_ids: always -inf (SuppressTokensLogitsProcessor).
+ * Bans are written after the penalty.  Limits: n_eos <= 16, n_suppress <= 256, every id in [0, vocab), the history holds `capacity` tokens per
+ * sequence (the cache's own limit); anything else is refused with a message that names the limit.  eos_ids / suppress_ids are HOST int32
+ * arrays (NULL with a count of 0), copied into device memory the context owns.  All-off values (1, 0, 0, no lists) switch the feature off.
+ * Synchronises (refused while a stream is being captured).  Like the sampling settings, these are read when fvhd_llm_start /
+ * fvhd_llm_decode enqueue: a captured graph keeps the ones it was captured with (when other lists are set later, the 1 KiB block
+ * its launches read is kept alive until fvhd_llm_destroy; setting the same lists again changes nothing).  Set them BEFORE fvhd_llm_start: a decode step with processors on after a start without them is an error (it has no
+ * history), and a step enqueued with processors off appends nothing to the history.
+ * With any processor on, the call writes its fp32 logits to logits_out or the context's own buffer, edits them in place with one launch of
+ * one workgroup per sequence (it appends the step's fed token to the history and touches at most g + 272 logits per sequence, never the
+ * whole row; every logit is edited by exactly one lane, so the bits are the same eager or replayed), then chooses: greedy = the argmax of
+ * the processed logits (lowest index on ties, two launches as for the first token), sampling = the sampler on them.  logits_out then
+ * holds the PROCESSED scores (transformers' `scores`, not its raw `logits`).  A step that hits the sticky error word appends nothing.
+ * Beam search is not covered: transformers applies the processors to log-softmaxed scores there, and fvhd_llm_cache_gather does not
+ * reorder the history - keep the processors off around fvhd_llm_beam_topk / fvhd_llm_cache_gather.
+ * With every processor off (the default) nothing changes: no launch, no buffer traffic and no kernel branch is added. */
+int fvhd_llm_set_logits_processors(fvhd_llm* ctx, float repetition_penalty, int no_repeat_ngram_size, int min_new_tokens, const int32_t* host_eos_ids,
+                                   int n_eos, const int32_t* host_suppress_ids, int n_suppress);
+/* the processors on their own (tests): logits fp32 [B, V] edited in place (1 <= B <= 64), history int32 [B, capacity] on the device of which
+ * the first g tokens of every row count (0 <= g <= capacity; entries outside [0, V) are ignored), the settings as above (lists on the
+ * host).  Builds the first-occurrence records the kernel needs from the history on the device, then runs the step's kernel.  A process-wide
+ * scratch, allocated / grown on demand: eager calls only, not during stream capture. */
+int fvhd_op_dec_logits_process(fvhd_stream_t stream, float* logits, int B, int V, const int32_t* history, int capacity, int g, float repetition_penalty,
+                               int no_repeat_ngram_size, int min_new_tokens, const int32_t* host_eos_ids, int n_eos, const int32_t* host_suppress_ids,
+                               int n_suppress);
 
 #ifdef __cplusplus
 }

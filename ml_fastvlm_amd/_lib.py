@@ -16,7 +16,9 @@ SAMPLING_VERSION = 502          # the first with fvhd_llm_set_sampling / fvhd_op
 WIDE_BATCH_VERSION = 503       # the first whose decode takes more than 16 sequences per step (up to MAX_DECODE_BATCH)
 W8_VERSION = 504               # the first with 8-bit (e4m3) LLM weights: fvhd_llm_set_weight_format, fvhd_op_*_w8 (declared only when the library has them)
 BEAM_VERSION = 505             # the first with beam search: fvhd_llm_beam_reserve / _cache_gather / _beam_topk, fvhd_op_dec_beam_topk / _cache_gather (declared only when the library has them)
+PROCESSORS_VERSION = 506      # the first with logits processors in the step: fvhd_llm_set_logits_processors, fvhd_op_dec_logits_process (declared only when the library has them)
 MAX_DECODE_BATCH = 64
+MAX_EOS_IDS, MAX_SUPPRESS_IDS = 16, 256      # list limits of fvhd_llm_set_logits_processors (include/fvhd.h)
 W_BF16, W_E4M3 = 0, 1           # fvhd_llm_set_weight_format (include/fvhd.h)
 WEIGHT_FORMATS = {"bf16": W_BF16, "fp8_e4m3": W_E4M3}
 MAT_QKV, MAT_O, MAT_GATE_UP, MAT_DOWN, MAT_LM_HEAD = 0, 1, 2, 3, 4     # fvhd_llm_debug_packed_e4m3
@@ -135,6 +137,11 @@ def _declare(lib) -> None:
             "fvhd_op_dec_beam_topk": (ci, [vp, vp, vp, ci, ci, ci, ci, vp, vp]),
             "fvhd_op_dec_cache_gather": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp]),
         })
+    if lib.fvhd_version() >= PROCESSORS_VERSION:   # an older library loads without them; processors_lib() then names the rebuild
+        sig.update({
+            "fvhd_llm_set_logits_processors": (ci, [vp, cf, ci, ci, vp, ci, vp, ci]),
+            "fvhd_op_dec_logits_process": (ci, [vp, vp, ci, ci, vp, ci, ci, cf, ci, ci, vp, ci, vp, ci]),
+        })
     del fp, cl
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)     # AttributeError here = the .so does not export what fvhd.h declares
@@ -193,6 +200,17 @@ def beam_lib():
     if got < BEAM_VERSION:
         raise FvhdError(f"{LIB_PATH} reports ABI version {got}: beam search (fvhd_llm_beam_reserve, fvhd_llm_cache_gather, fvhd_llm_beam_topk, ...) "
                         f"needs {BEAM_VERSION} - rebuild the library (`python -m ml_fastvlm_amd.build`)")
+    return lib
+
+
+def processors_lib():
+    """load(), for the logits-processor entry points: a library older than PROCESSORS_VERSION loads (greedy, sampled and beam decoding work
+    on it) but has none of them, and this says so instead of an AttributeError."""
+    lib = load()
+    got = lib.fvhd_version()
+    if got < PROCESSORS_VERSION:
+        raise FvhdError(f"{LIB_PATH} reports ABI version {got}: logits processors (fvhd_llm_set_logits_processors, "
+                        f"fvhd_op_dec_logits_process) need {PROCESSORS_VERSION} - rebuild the library (`python -m ml_fastvlm_amd.build`)")
     return lib
 
 

@@ -93,7 +93,7 @@ def encode_images(vision_tower, mm_projector, images):
 
 
 def install_into_llava(splice: bool = False, prefill: bool = False, prefill_any_dtype: bool = False, generate: bool = False,
-                       llm_weights: str = "bf16", beam_search: bool = False) -> None:
+                       llm_weights: str = "bf16", beam_search: bool = False, logits_processors: bool = False) -> None:
     """Make an unmodified `llava` package (the reference) build and call the MI355X tower; splice=True also routes
     `prepare_inputs_labels_for_multimodal` through the GPU splice (needs the embeddings on a HIP device); prefill=True also runs the
     PREFILL step of `LlavaQwen2ForCausalLM.forward` (`llava_qwen.py:92-103`: the first forward of `generate`, on `inputs_embeds`
@@ -106,6 +106,8 @@ def install_into_llava(splice: bool = False, prefill: bool = False, prefill_any_
     beam_search=True (with generate=True) lets that patched generate take the library for `num_beams` > 1 as well
     (`Qwen2Generator.beam_search`): do_sample=False, one beam group, no other processor, batch * num_beams <= 64; without it num_beams > 1
     keeps falling back, as before.
+    logits_processors=True (with generate=True) lets it take the library for `repetition_penalty`, `no_repeat_ngram_size`, `min_new_tokens`
+    and `suppress_tokens` too (num_beams = 1; `Qwen2Generator.set_logits_processors`); without it those settings keep falling back.
     llm_weights: "bf16" (the default) or "fp8_e4m3" - the storage of the LLM's packed matrices in the library's prefill / decode contexts
     (`Qwen2Prefill.from_hf(weights=...)`), recorded on `LlavaQwen2ForCausalLM` for `prefill_context` to read."""
     from ._lib import weight_format_code
@@ -140,7 +142,8 @@ def install_into_llava(splice: bool = False, prefill: bool = False, prefill_any_
     if generate:
         import llava.model.language_model.llava_qwen as lq
         cur = lq.LlavaQwen2ForCausalLM.generate
-        lq.LlavaQwen2ForCausalLM.generate = _make_library_generate(getattr(cur, "_fvhd_orig", cur), beam_search=beam_search)
+        extra = dict(logits_processors=True) if logits_processors else {}
+        lq.LlavaQwen2ForCausalLM.generate = _make_library_generate(getattr(cur, "_fvhd_orig", cur), beam_search=beam_search, **extra)
 
 
 def _is_fresh_dynamic_cache(pkv) -> bool:
@@ -328,9 +331,10 @@ def beam_generate(model, input_ids, images=None, image_sizes=None, attention_mas
 
 
 def _generate_on_library(model, input_ids, images, image_sizes, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id,
-                         sampling=None, beam=None):
+                         sampling=None, beam=None, processors=None):
     """the body shared by `generate`, `beam_generate` and `_make_library_generate`: the multimodal splice (or the token embedding), then the
-    prefill and every decode step on the library - `Qwen2Generator.greedy`, `.sample(**sampling)` or `.beam_search(**beam)`"""
+    prefill and every decode step on the library - `Qwen2Generator.greedy`, `.sample(**sampling)` or `.beam_search(**beam)`; processors:
+    None or the logits-processor keywords of greedy / sample (repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens)"""
     if images is not None:
         (input_ids, position_ids, attention_mask, _, inputs_embeds, _) = model.prepare_inputs_labels_for_multimodal(
             input_ids, position_ids, attention_mask, None, None, images, image_sizes=image_sizes)
@@ -342,11 +346,12 @@ def _generate_on_library(model, input_ids, images, image_sizes, attention_mask, 
         return gen.beam_search(inputs_embeds, attention_mask, position_ids, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id,
                                pad_token_id=pad_token_id, **beam)
     gen = generator_context(model, B, T + max_new_tokens)
+    processors = processors or {}
     if sampling is None:
         return gen.greedy(inputs_embeds, attention_mask, position_ids, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id,
-                          pad_token_id=pad_token_id)
+                          pad_token_id=pad_token_id, **processors)
     return gen.sample(inputs_embeds, attention_mask, position_ids, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id,
-                      pad_token_id=pad_token_id, **sampling)
+                      pad_token_id=pad_token_id, **sampling, **processors)
 
 
 # GenerationConfig fields whose value (beside None) means "this processor / mode is off"; any other value is a setting the library does
@@ -365,14 +370,19 @@ _OFF = {
 # generate()'s own arguments beside **kwargs: any of them given asks for something the library does not do
 _GENERATE_ARGS = ("generation_config", "logits_processor", "stopping_criteria", "prefix_allowed_tokens_fn", "synced_gpus", "assistant_model",
                   "streamer", "negative_prompt_ids", "negative_prompt_attention_mask", "custom_generate", "assistant_tokenizer", "tokenizer")
+# the settings of _OFF that `Qwen2Generator.set_logits_processors` implements (num_beams = 1)
+_PROCESSORS = ("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens", "suppress_tokens")
 
 
-def _library_generate_settings(model, kwargs, beam_search: bool = False):
+def _library_generate_settings(model, kwargs, beam_search: bool = False, processors: bool = False):
     """transformers' own resolution of a generate(**kwargs) call (`_prepare_generation_config`, which generate itself calls: its global
     defaults such as top_k = 50, the model's generation_config, then the call's arguments) -> (settings, None) when the library can run
     it, (None, reason) when it cannot.  settings: max_new_tokens, eos_token_id, pad_token_id, `sampling` (None = greedy, else the
     keyword arguments of Qwen2Generator.sample) and `beam` (None, or with beam_search=True and num_beams > 1 the keyword arguments of
-    Qwen2Generator.beam_search: num_beams, length_penalty, early_stopping, num_return_sequences)."""
+    Qwen2Generator.beam_search: num_beams, length_penalty, early_stopping, num_return_sequences).  processors=True: with num_beams = 1,
+    repetition_penalty, no_repeat_ngram_size, min_new_tokens and suppress_tokens within the library's limits (16 EOS ids, 256 suppressed
+    ids, ids inside the vocabulary) no longer disqualify the call, and settings gains `processors`: None when all are off, else those four
+    keywords of Qwen2Generator.greedy / .sample."""
     for k in _GENERATE_ARGS:
         if kwargs.get(k) is not None:
             return None, f"{k} is given"
@@ -384,12 +394,25 @@ def _library_generate_settings(model, kwargs, beam_search: bool = False):
     if extra:
         return None, f"model arguments {extra}"
     beams = gc.num_beams if beam_search and isinstance(gc.num_beams, int) and gc.num_beams > 1 else None
+    single = isinstance(gc.num_beams, int) and gc.num_beams == 1 or gc.num_beams is None
     for k, off in _OFF.items():
         v = getattr(gc, k, None)
         if beams is not None and k in ("num_beams", "num_return_sequences"):
             continue
+        if processors and single and k in _PROCESSORS:
+            continue
         if v is not None and v not in off:
             return None, f"{k}={v!r}"
+    proc = None
+    if processors and single:
+        from .logits_processors import normalize
+        vocab = getattr(getattr(model, "config", None), "vocab_size", None)
+        try:
+            proc = normalize(gc.repetition_penalty, gc.no_repeat_ngram_size, gc.min_new_tokens, gc.eos_token_id, gc.suppress_tokens, vocab=vocab)
+        except (TypeError, ValueError) as e:                         # beyond the library's limits: the reference's generate runs it
+            return None, f"logits processors: {e}"
+        if proc is not None:
+            proc.pop("eos_token_id")                                 # greedy / sample take the run's own eos_token_id
     beam = None
     if beams is not None:
         if gc.do_sample:
@@ -410,7 +433,10 @@ def _library_generate_settings(model, kwargs, beam_search: bool = False):
                         top_p=1.0 if gc.top_p is None else float(gc.top_p))
         if not (0.0 < sampling["temperature"] < math.inf) or not 0.0 <= sampling["top_p"] <= 1.0 or sampling["top_k"] < 0:
             return None, f"temperature={gc.temperature!r}, top_k={gc.top_k!r}, top_p={gc.top_p!r}"
-    return dict(max_new_tokens=int(gc.max_new_tokens), eos_token_id=gc.eos_token_id, pad_token_id=gc.pad_token_id, sampling=sampling, beam=beam), None
+    settings = dict(max_new_tokens=int(gc.max_new_tokens), eos_token_id=gc.eos_token_id, pad_token_id=gc.pad_token_id, sampling=sampling, beam=beam)
+    if processors:
+        settings["processors"] = proc
+    return settings, None
 
 
 def _batch_reason(batch: int):
@@ -419,7 +445,7 @@ def _batch_reason(batch: int):
     return f"batch {batch} > {MAX_DECODE_BATCH}" if batch > MAX_DECODE_BATCH else None
 
 
-def _make_library_generate(orig_generate, beam_search: bool = False):
+def _make_library_generate(orig_generate, beam_search: bool = False, logits_processors: bool = False):
     """`LlavaQwen2ForCausalLM.generate` (`llava_qwen.py:106-143`) on the library: the same argument handling (position_ids / attention_mask
     popped, inputs_embeds refused), the settings resolved as transformers resolves them (`_library_generate_settings`), then the
     multimodal splice and `Qwen2Generator.greedy` / `.sample` on `generator_context(model, ...)`.  It takes the library only for greedy or
@@ -428,12 +454,15 @@ def _make_library_generate(orig_generate, beam_search: bool = False):
     else is the original generate, with a one-time warning that names the reason.  Returns the new tokens [B, n], as the reference's
     generate(inputs_embeds=...) does.  beam_search=True: num_beams > 1 (do_sample=False, one beam group, num_return_sequences <= num_beams,
     batch * num_beams <= 64) takes `Qwen2Generator.beam_search` and returns [B * num_return_sequences, n]; beam sampling, group / constrained
-    beam search and dict output stay on the original generate."""
+    beam search and dict output stay on the original generate.  logits_processors=True: repetition_penalty, no_repeat_ngram_size,
+    min_new_tokens and suppress_tokens (num_beams = 1, within the library's limits) run on the library as well
+    (`Qwen2Generator.set_logits_processors`); min_length, bad_words_ids, begin_suppress_tokens, sequence_bias and every other processor
+    keep falling back."""
     def generate(self, inputs=None, images=None, image_sizes=None, **kwargs):
         if "inputs_embeds" in kwargs:                            # as the reference (llava_qwen.py:120-121)
             raise NotImplementedError("`inputs_embeds` is not supported")
         settings, reason = _library_generate_settings(self, {k: v for k, v in kwargs.items() if k not in ("position_ids", "attention_mask")},
-                                                      beam_search=beam_search)
+                                                      beam_search=beam_search, **(dict(processors=True) if logits_processors else {}))
         lm_w = self.lm_head.weight
         rows = 0 if inputs is None else inputs.shape[0] * (settings["beam"]["num_beams"] if settings is not None and settings["beam"] else 1)
         if settings is not None and inputs is not None and _batch_reason(rows) is not None:
@@ -450,7 +479,7 @@ def _make_library_generate(orig_generate, beam_search: bool = False):
         with torch.no_grad():
             return _generate_on_library(self, inputs, images, image_sizes, kwargs.get("attention_mask"), kwargs.get("position_ids"),
                                         settings["max_new_tokens"], settings["eos_token_id"], settings["pad_token_id"], settings["sampling"],
-                                        settings["beam"])
+                                        settings["beam"], **(dict(processors=settings["processors"]) if settings.get("processors") else {}))
     generate._fvhd_generate = True
     generate._fvhd_orig = orig_generate
     return generate

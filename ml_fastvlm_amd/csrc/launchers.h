@@ -86,4 +86,7 @@ int fvhd_dec_beam_topk_supported(int G, int K, int C, int V);
 int fvhd_launch_dec_beam_topk(hipStream_t st, const float* logits, const float* scores, int G, int K, int C, int V, float* out_v, int64_t* out_i, void* ws);
 size_t fvhd_dec_cache_gather_ws_bytes(int rows, int nkv, int hd, int cap);
 int fvhd_launch_dec_cache_gather(hipStream_t st, const DecCacheGatherArgs* a);
+// llm_logits.hip
+int fvhd_launch_dec_logits_process(hipStream_t st, const DecLogitsArgs* a);
+int fvhd_launch_dec_logits_history(hipStream_t st, const int* tokens, int* hist, unsigned* seen, int B, int V, int cap, int g);
 }

@@ -10,6 +10,7 @@
 #pragma GCC visibility push(hidden)      // the helpers shared between the four sources are not exported symbols
 
 constexpr int kMaxSplits = 4;
+constexpr int kMaxEos = 16, kMaxSuppress = 256;     // list limits of the logits processors (include/fvhd.h)
 
 struct LayerOff { size_t ln1, bqkv, ln2, w[4], s[4]; };     // w, s: by FVHD_MAT_QKV .. FVHD_MAT_DOWN; s: the fp32 row scales of an e4m3 matrix
 
@@ -79,7 +80,22 @@ struct __attribute__((visibility("default"))) fvhd_llm {     // (its inline cons
     // fvhd_llm_beam_reserve: one allocation of its own (fvhd_llm_cache_reserve's footprint is what it was), sized for the reserved cache
     char* beam = nullptr;                  // the reorder's scratch (llm_beam.hip: two layers' K | V, the mask, the positions), then the top-K workspace
     char* beam_topk = nullptr;
+    // fvhd_llm_set_logits_processors (llm_logits.hip): read when fvhd_llm_start / fvhd_llm_decode enqueue, like the sampling settings
+    float proc_penalty = 1.f;
+    int proc_ngram = 0, proc_min_new = 0, proc_n_eos = 0, proc_n_sup = 0;
+    int* proc_lists = nullptr;             // device: EOS ids [16] | suppressed ids [256]; an allocation of its own.  One that a captured step
+    bool proc_lists_captured = false;      // has recorded is retired (kept until fvhd_llm_destroy) when OTHER lists are set, not overwritten
+    std::vector<int32_t> proc_lists_host;  // what proc_lists holds (setting the same lists again uploads and retires nothing)
+    int* hist = nullptr;                   // inside `dc`: per-row token history [dc_batch][dc_cap], the bitmap of its tokens
+    unsigned* hist_seen = nullptr;         // [dc_batch][ceil(V / 32)] and the prompt length recorded by the last fvhd_llm_start that ran
+    int* hist_base = nullptr;              // with processors on (history length = cache length - it)
+    bool hist_started = false;             // that start has happened: a decode step with processors on has a history to append to
 };
+
+inline bool processors_on(const fvhd_llm* c)
+{
+    return c->proc_penalty != 1.f || c->proc_ngram > 0 || (c->proc_min_new > 0 && c->proc_n_eos > 0) || c->proc_n_sup > 0;
+}
 
 inline int lfail(const std::string& m) { return fvhd_set_error(m.c_str()); }
 inline int lhip(const char* what, hipError_t e) { return lfail(std::string(what) + ": " + hipGetErrorString(e)); }
@@ -103,5 +119,8 @@ int first_missing_tensor(const fvhd_llm* c);                      // llm_weights
 int wait_for_loads(fvhd_llm* c);                                  // llm_weights.hip
 int ensure_ws(fvhd_llm* c, int B, int T, hipStream_t st, bool check_capture);     // llm_prefill.hip
 const char* sampling_error(float temperature, int top_k, float top_p);            // llm_step.hip: NULL when the parameters are valid
+// llm_step.hip: "" when the processor settings are valid for a vocabulary of V ids (V <= 0: the id range is not checked); lists: host memory
+std::string processors_error(float repetition_penalty, int no_repeat_ngram_size, int min_new_tokens, const int32_t* eos_ids, int n_eos,
+                             const int32_t* suppress_ids, int n_suppress, int V);
 
 #pragma GCC visibility pop

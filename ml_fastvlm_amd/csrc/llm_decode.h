@@ -77,3 +77,25 @@ struct DecCacheGatherArgs {
     int* status_host = nullptr;
     char* ws = nullptr;            // fvhd_dec_cache_gather_ws_bytes(batch, nkv, hd, cap) bytes
 };
+
+// Arguments of the logits processors (llm_logits.hip): sparse in-place edits of fp32 logits [B][V] from a per-row token history, one
+// workgroup per row (include/fvhd.h "LLM logits processors").
+struct DecLogitsArgs {
+    float* logits = nullptr;
+    int B = 0, V = 0;
+    int* hist = nullptr;           // [B][cap]: entry = token | 0x80000000 when an earlier entry of the row holds the same token
+    int cap = 0;
+    unsigned* seen = nullptr;      // [B][ceil(V / 32)] bits: token occurs in the row's history (tested and set by the append)
+    const int64_t* tok = nullptr;  // the step's fed ids: tok, else last; both NULL = nothing to append (the first token, the single op)
+    const int64_t* last = nullptr;
+    const int* len = nullptr;      // device words: history length before the append = *len - *base
+    int* base = nullptr;
+    int start_T = 0;               // > 0: fvhd_llm_start's launch - the history is empty and *base = start_T is recorded
+    int g_fixed = -1;              // >= 0: the history length itself (the single op)
+    float penalty = 1.f;           // repetition_penalty (1 = off)
+    int ngram = 0, min_new = 0;    // no_repeat_ngram_size, min_new_tokens (0 = off)
+    const int* eos = nullptr;      // int32 [n_eos] / [n_sup] on the device, every id in [0, V)
+    const int* sup = nullptr;
+    int n_eos = 0, n_sup = 0;
+    const int* status = nullptr;   // non-NULL: the launch does nothing (appends nothing) while *status != 0
+};

@@ -232,7 +232,7 @@ int fvhd_op_dec_sample(fvhd_stream_t st, const float* logits, int B, int V, floa
     return lret("fvhd_op_dec_sample", fvhd_launch_dec_sample((hipStream_t)st, &a, ws[dev]));
 }
 
-// the beam search's two operations on their own: process-wide scratch, allocated / grown on demand - eager calls only
+// process-wide scratch of a single op, allocated / grown on demand - eager calls only
 static int op_scratch(const char* who, char* (&buf)[64], size_t (&cap)[64], size_t need, char** out)
 {
     int dev = 0;
@@ -243,7 +243,7 @@ static int op_scratch(const char* who, char* (&buf)[64], size_t (&cap)[64], size
         if (buf[dev]) (void)hipFree(buf[dev]);                      // (synchronises: no earlier launch still uses it)
         buf[dev] = nullptr;
         cap[dev] = 0;
-        if ((he = hipMalloc((void**)&buf[dev], need)) != hipSuccess) { buf[dev] = nullptr; return lhip("hipMalloc(beam search scratch)", he); }
+        if ((he = hipMalloc((void**)&buf[dev], need)) != hipSuccess) { buf[dev] = nullptr; return lhip((std::string(who) + ": hipMalloc(scratch)").c_str(), he); }
         cap[dev] = need;
     }
     *out = buf[dev];
@@ -280,6 +280,37 @@ int fvhd_op_dec_cache_gather(fvhd_stream_t st, void* k_cache, void* v_cache, uin
     a.kc = (char*)k_cache; a.vc = (char*)v_cache; a.layers = n_layers; a.batch = batch; a.mask = key_valid; a.posv = positions; a.src = src_rows;
     a.rows_in = rows_in; a.rows_out = rows_out; a.nkv = n_kv_heads; a.hd = head_dim; a.cap = capacity; a.len = length; a.status = status; a.ws = ws;
     return lret("fvhd_op_dec_cache_gather", fvhd_launch_dec_cache_gather((hipStream_t)st, &a));
+}
+
+// the logits processors on their own: the history's first-occurrence records and bitmap are built on the device from the plain tokens
+// (process-wide scratch, grown on demand - eager calls only), then the step's kernel runs on them
+int fvhd_op_dec_logits_process(fvhd_stream_t st, float* logits, int B, int V, const int32_t* history, int capacity, int g, float repetition_penalty,
+                               int no_repeat_ngram_size, int min_new_tokens, const int32_t* host_eos_ids, int n_eos, const int32_t* host_suppress_ids,
+                               int n_suppress)
+{
+    if (!logits || !history) return lfail("fvhd_op_dec_logits_process: NULL pointer");
+    if (B < 1 || B > 64 || V < 1 || capacity < 1 || g < 0 || g > capacity)
+        return lfail("fvhd_op_dec_logits_process: needs 1 <= B <= 64, V >= 1, capacity >= 1 and 0 <= g <= capacity");
+    const std::string err = processors_error(repetition_penalty, no_repeat_ngram_size, min_new_tokens, host_eos_ids, n_eos, host_suppress_ids, n_suppress, V);
+    if (!err.empty()) return lfail("fvhd_op_dec_logits_process: " + err);
+    static char* buf[64] = {};
+    static size_t cap[64] = {};
+    const size_t hist_bytes = ((size_t)B * capacity * 4 + 255) & ~(size_t)255, seen_bytes = ((size_t)B * ((V + 31) / 32) * 4 + 255) & ~(size_t)255;
+    char* ws = nullptr;
+    if (int e = op_scratch("fvhd_op_dec_logits_process", buf, cap, hist_bytes + seen_bytes + (kMaxEos + kMaxSuppress) * 4, &ws)) return e;
+    hipStream_t s = (hipStream_t)st;
+    DecLogitsArgs a;
+    a.logits = logits; a.B = B; a.V = V; a.hist = (int*)ws; a.cap = capacity; a.seen = (unsigned*)(ws + hist_bytes); a.g_fixed = g;
+    a.penalty = repetition_penalty; a.ngram = no_repeat_ngram_size; a.min_new = n_eos ? min_new_tokens : 0;
+    int* lists = (int*)(ws + hist_bytes + seen_bytes);
+    a.eos = lists; a.n_eos = n_eos; a.sup = lists + kMaxEos; a.n_sup = n_suppress;
+    hipError_t he = hipMemsetAsync(a.seen, 0, seen_bytes, s);
+    if (he == hipSuccess && n_eos) he = hipMemcpyAsync(lists, host_eos_ids, (size_t)n_eos * 4, hipMemcpyHostToDevice, s);
+    if (he == hipSuccess && n_suppress) he = hipMemcpyAsync(lists + kMaxEos, host_suppress_ids, (size_t)n_suppress * 4, hipMemcpyHostToDevice, s);
+    if (he == hipSuccess) he = hipStreamSynchronize(s);          // the host lists are the caller's again
+    if (he != hipSuccess) return lhip("fvhd_op_dec_logits_process: list copy", he);
+    if (int e = fvhd_launch_dec_logits_history(s, history, a.hist, a.seen, B, V, capacity, g)) return lhip("fvhd_op_dec_logits_process (history)", (hipError_t)e);
+    return lret("fvhd_op_dec_logits_process", fvhd_launch_dec_logits_process(s, &a));
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 // C ABI of the Qwen2 decode (include/fvhd.h "LLM decode"): the library's own KV cache, one token per sequence per step.
-// Kernels: llm_decode.hip, llm_w8.hip, llm_sample.hip, llm_beam.hip.
+// Kernels: llm_decode.hip, llm_w8.hip, llm_sample.hip, llm_beam.hip, llm_logits.hip.
+#include <algorithm>
 #include <cmath>
 
 #include "llm_ctx.h"
@@ -56,7 +57,37 @@ int dec_embedding_error(const fvhd_llm* c, const char* who)
                  "fvhd_llm_set_tied_embeddings(ctx, 1) for a model whose lm_head IS its embedding table (tie_word_embeddings)");
 }
 
+// the processors' settings of this enqueue; the history fields of the step (fed ids, length, start) are the caller's to fill
+DecLogitsArgs dec_logits_args(fvhd_llm* c, float* logits, int B, hipStream_t st)
+{
+    DecLogitsArgs a;
+    a.logits = logits; a.B = B; a.V = c->V; a.hist = c->hist; a.cap = c->dc_cap; a.seen = c->hist_seen; a.len = c->len; a.base = c->hist_base;
+    a.penalty = c->proc_penalty; a.ngram = c->proc_ngram; a.min_new = c->proc_n_eos ? c->proc_min_new : 0;
+    a.eos = c->proc_lists; a.n_eos = c->proc_n_eos; a.sup = c->proc_lists ? c->proc_lists + kMaxEos : nullptr; a.n_sup = c->proc_n_sup;
+    if (c->proc_lists && is_capturing(st)) c->proc_lists_captured = true;     // the caller's graph now reads the lists: retired, never overwritten
+    return a;
+}
+
 }  // namespace
+
+std::string processors_error(float repetition_penalty, int no_repeat_ngram_size, int min_new_tokens, const int32_t* eos_ids, int n_eos,
+                             const int32_t* suppress_ids, int n_suppress, int V)
+{
+    if (!(repetition_penalty > 0.f) || !std::isfinite(repetition_penalty)) return "repetition_penalty must be finite and > 0 (1 = off)";
+    if (no_repeat_ngram_size < 0) return "no_repeat_ngram_size must be >= 0 (0 = off)";
+    if (min_new_tokens < 0) return "min_new_tokens must be >= 0 (0 = off)";
+    if (n_eos < 0 || n_eos > kMaxEos) return "at most " + std::to_string(kMaxEos) + " EOS ids (got " + std::to_string(n_eos) + ")";
+    if (n_suppress < 0 || n_suppress > kMaxSuppress)
+        return "at most " + std::to_string(kMaxSuppress) + " suppressed ids (got " + std::to_string(n_suppress) + ")";
+    if ((n_eos && !eos_ids) || (n_suppress && !suppress_ids)) return "a list with a count > 0 is NULL";
+    for (int k = 0; k < 2 && V > 0; ++k) {
+        const int32_t* ids = k ? suppress_ids : eos_ids;
+        for (int i = 0; i < (k ? n_suppress : n_eos); ++i)
+            if (ids[i] < 0 || ids[i] >= V)
+                return std::string(k ? "suppressed" : "EOS") + " id " + std::to_string(ids[i]) + " is outside [0, vocab = " + std::to_string(V) + ")";
+    }
+    return "";
+}
 
 const char* sampling_error(float temperature, int top_k, float top_p)
 {
@@ -106,13 +137,15 @@ int fvhd_llm_cache_reserve(fvhd_llm* c, int batch, int capacity)
                  o_att = a.take((size_t)batch * nh * hd * 2), o_act = a.take((size_t)batch * I * 2), o_part = a.take(std::max(part, (size_t)16)),
                  o_apart = a.take((size_t)batch * nh * c->att_S * (hd + 2) * 4), o_cnt = a.take((size_t)(ncol + batch * nh) * 4),
                  o_av = a.take((size_t)lm_ncol * 16 * NB * 4), o_ai = a.take((size_t)lm_ncol * 16 * NB * 4), o_logits = a.take((size_t)batch * V * 4),
-                 o_rope = a.take((size_t)c->ws_pos * hd * 4), o_sws = a.take(fvhd_dec_sample_ws_bytes()), o_rstd = a.take(4 * 64);
+                 o_rope = a.take((size_t)c->ws_pos * hd * 4), o_sws = a.take(fvhd_dec_sample_ws_bytes()), o_rstd = a.take(4 * 64),
+                 o_hist = a.take((size_t)batch * capacity * 4), o_seen = a.take((size_t)batch * ((V + 31) / 32) * 4), o_hbase = a.take(4);
     hipError_t he = hipDeviceSynchronize();                      // refused while a stream is being captured (like fvhd_llm_reserve)
     if (he != hipSuccess) return lhip("fvhd_llm_cache_reserve: hipDeviceSynchronize", he);
     if (c->dc) (void)hipFree(c->dc);
     if (c->beam) (void)hipFree(c->beam);                         // sized for the cache it was reserved for: fvhd_llm_beam_reserve again
     c->dc = c->beam = c->beam_topk = nullptr;
     c->dc_batch = c->dc_cap = c->run_batch = 0;
+    c->hist_started = false;
     if ((he = hipMalloc((void**)&c->dc, a.off)) != hipSuccess) return lhip("hipMalloc(llm KV cache)", he);
     if ((he = hipMemset(c->dc, 0, a.off)) != hipSuccess) return lhip("hipMemset(llm KV cache)", he);      // counters start at zero
     if (!c->status_host) {
@@ -125,6 +158,7 @@ int fvhd_llm_cache_reserve(fvhd_llm* c, int batch, int capacity)
     c->len = (int*)(d + o_len); c->status = (int*)(d + o_status); c->dh = d + o_h; c->dq = d + o_q; c->datt = d + o_att; c->dact = d + o_act;
     c->dpart = (float*)(d + o_part); c->apart = (float*)(d + o_apart); c->cnt = (int*)(d + o_cnt); c->amax_v = (float*)(d + o_av);
     c->amax_i = (int*)(d + o_ai); c->dlogits = (float*)(d + o_logits); c->drope = (float*)(d + o_rope); c->sws = d + o_sws; c->drstd = (float*)(d + o_rstd);
+    c->hist = (int*)(d + o_hist); c->hist_seen = (unsigned*)(d + o_seen); c->hist_base = (int*)(d + o_hbase);
     c->dc_bytes = a.off; c->dc_batch = batch; c->dc_cap = capacity; c->dc_pos = c->ws_pos;
     // the decode's own copy of the rotary table: a later, larger prefill may replace the prefill workspace under a captured decode graph
     if ((he = hipMemcpy(c->drope, c->rope, (size_t)c->ws_pos * hd * 4, hipMemcpyDeviceToDevice)) != hipSuccess) return lhip("hipMemcpy(rope table)", he);
@@ -172,6 +206,16 @@ int fvhd_llm_start(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* ke
     if (he == hipSuccess)
         he = key_valid ? hipMemcpy2DAsync(c->mask, cap, key_valid, T, T, B, hipMemcpyDeviceToDevice, st) : hipMemset2DAsync(c->mask, cap, 1, T, B, st);
     if (he != hipSuccess) return lhip("key mask copy", he);
+    const bool proc = processors_on(c);
+    c->hist_started = proc;
+    if (proc) {
+        // an empty history: no token is in the bitmap, and the launch records the prompt length the later steps count from; then the
+        // processors on the prefill's logits, before either choice reads them
+        if ((he = hipMemsetAsync(c->hist_seen, 0, (size_t)B * ((c->V + 31) / 32) * 4, st)) != hipSuccess) return lhip("history bitmap reset", he);
+        DecLogitsArgs pa = dec_logits_args(c, logits, B, st);
+        pa.start_T = T;
+        LCHECK(fvhd_launch_dec_logits_process(st, &pa), "first-token logits processors");
+    }
     if (c->do_sample) {
         // sampling: the cache state first, so that the draw reads n = the prompt length from the device
         LCHECK(fvhd_launch_dec_start_state(st, c->posv, position_ids, B, T, c->len, c->status), "decode state");
@@ -195,6 +239,10 @@ int fvhd_llm_decode(fvhd_llm* c, const int64_t* token_ids, float* logits_out, in
     if (!c->dc || !c->run_batch) return lfail("fvhd_llm_decode: no started sequence - call fvhd_llm_cache_reserve and fvhd_llm_start first");
     if (int e = dec_status_error(c, "fvhd_llm_decode")) return e;
     if (int e = dec_embedding_error(c, "fvhd_llm_decode")) return e;
+    const bool proc = processors_on(c);
+    if (proc && !c->hist_started)
+        return lfail("fvhd_llm_decode: logits processors are on but the sequence was started without them (no token history) - set them "
+                     "before fvhd_llm_start");
     LLM_ON_DEVICE(c);
     hipStream_t st = (hipStream_t)stream;
     const int B = c->run_batch, H = c->H, I = c->I, nh = c->nh, nkv = c->nkv, hd = c->hd, cap = c->dc_cap;
@@ -237,11 +285,18 @@ int fvhd_llm_decode(fvhd_llm* c, const int64_t* token_ids, float* logits_out, in
     }
     DecGemmArgs a = gemm(DEC_EPI_ARGMAX, c->dh, (const float*)(w + c->norm_off), -1, FVHD_MAT_LM_HEAD);
     a.logits = logits_out; a.amax_v = c->amax_v; a.amax_i = c->amax_i;
+    if (proc && !a.logits) a.logits = c->dlogits;
+    DecLogitsArgs pa;
+    if (proc) {
+        pa = dec_logits_args(c, a.logits, B, st);
+        pa.tok = token_ids; pa.last = c->last_ids; pa.status = c->status;
+    }
     if (c->do_sample) {
         // sampling replaces the argmax reduce: it reads the logits (the caller's, else the context's buffer), chooses with n = length + 1
         // (the cache holds this step's token), and advances positions and length
         if (!a.logits) a.logits = c->dlogits;
         LCHECK(fvhd_launch_dec_gemm(st, &a), "decode final norm + lm_head");
+        if (proc) LCHECK(fvhd_launch_dec_logits_process(st, &pa), "decode logits processors");      // one launch over all rows, then the sampler's blocks
         DecSampleArgs sa = dec_sample_args(c, a.logits, B);
         sa.len = c->len; sa.n_add = 1; sa.last = c->last_ids; sa.ids_out = next_ids_out; sa.posv = c->posv; sa.len_advance = c->len;
         sa.status = c->status;
@@ -249,6 +304,11 @@ int fvhd_llm_decode(fvhd_llm* c, const int64_t* token_ids, float* logits_out, in
         return 0;
     }
     LCHECK(fvhd_launch_dec_gemm(st, &a), "decode final norm + lm_head + argmax");
+    if (proc) {
+        // the lm_head's fused (max, index) pairs saw the raw logits: the pairs again, from the processed ones (the first token's launch)
+        LCHECK(fvhd_launch_dec_logits_process(st, &pa), "decode logits processors");
+        LCHECK(fvhd_launch_dec_argmax_blocks(st, a.logits, c->V, B, c->amax_v, c->amax_i), "decode argmax (blocks)");
+    }
     LCHECK(fvhd_launch_dec_argmax_finish(st, c->amax_v, c->amax_i, (c->V / 16 + 3) / 4, B, c->last_ids, next_ids_out, c->posv, c->len, c->status),
            "decode argmax reduce");
     return 0;
@@ -310,6 +370,41 @@ int fvhd_llm_set_sampling(fvhd_llm* c, int do_sample, float temperature, int top
     c->top_k = top_k;
     c->top_p = top_p;
     c->seed = seed;
+    return 0;
+}
+
+int fvhd_llm_set_logits_processors(fvhd_llm* c, float repetition_penalty, int no_repeat_ngram_size, int min_new_tokens, const int32_t* eos_ids, int n_eos,
+                                   const int32_t* suppress_ids, int n_suppress)
+{
+    if (!c) return lfail("fvhd_llm_set_logits_processors: ctx is NULL");
+    const std::string err = processors_error(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_ids, n_eos, suppress_ids, n_suppress, c->V);
+    if (!err.empty()) return lfail("fvhd_llm_set_logits_processors: " + err);
+    LLM_ON_DEVICE(c);
+    hipError_t he = hipDeviceSynchronize();                      // refused while a stream is being captured; no enqueued step still reads the lists
+    if (he != hipSuccess) return lhip("fvhd_llm_set_logits_processors: hipDeviceSynchronize", he);
+    std::vector<int32_t> lists(kMaxEos + kMaxSuppress, 0);
+    std::copy(eos_ids, eos_ids + n_eos, lists.begin());
+    std::copy(suppress_ids, suppress_ids + n_suppress, lists.begin() + kMaxEos);
+    if ((n_eos || n_suppress) && !(c->proc_lists && lists == c->proc_lists_host)) {      // (the same lists again: nothing to upload)
+        if (c->proc_lists && c->proc_lists_captured) {           // a captured step replays on the old lists
+            c->retired.push_back((char*)c->proc_lists);
+            c->proc_lists = nullptr;
+        }
+        c->proc_lists_captured = false;
+        if (!c->proc_lists && (he = hipMalloc((void**)&c->proc_lists, lists.size() * 4)) != hipSuccess) {
+            c->proc_lists = nullptr;
+            return lhip("hipMalloc(logits processor lists)", he);
+        }
+        c->proc_lists_host.clear();
+        if ((he = hipMemcpy(c->proc_lists, lists.data(), lists.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return lhip("hipMemcpy(id lists)", he);
+        if ((he = hipDeviceSynchronize()) != hipSuccess) return lhip("fvhd_llm_set_logits_processors: hipDeviceSynchronize", he);
+        c->proc_lists_host = lists;
+    }
+    c->proc_penalty = repetition_penalty;
+    c->proc_ngram = no_repeat_ngram_size;
+    c->proc_min_new = min_new_tokens;
+    c->proc_n_eos = n_eos;
+    c->proc_n_sup = n_suppress;
     return 0;
 }
 

@@ -219,6 +219,7 @@ void fvhd_llm_destroy(fvhd_llm* c)
     if (c->wscratch) (void)hipFree(c->wscratch);
     if (c->ws) (void)hipFree(c->ws);
     for (char* p : c->retired) (void)hipFree(p);
+    if (c->proc_lists) (void)hipFree(c->proc_lists);
     if (c->load_ev) (void)hipEventDestroy(c->load_ev);
     if (c->emb) (void)hipFree(c->emb);
     if (c->dc) (void)hipFree(c->dc);

@@ -17,9 +17,13 @@ distribution as transformers', not the same draws (the random numbers are Philox
 `beam_search` runs transformers' beam search (`num_beams` = K > 1): the K beams of G prompts are G * K rows of the same step, the top
 continuations and the KV-cache reorder are two more device operations (include/fvhd.h "LLM beam search"), and the [G, 2 K]-sized
 bookkeeping is `ml_fastvlm_amd.beam.BeamSearchState` - all of it inside the one captured graph per step.
+`greedy` and `sample` also take transformers' `repetition_penalty`, `no_repeat_ngram_size`, `min_new_tokens` and `suppress_tokens`
+(`set_logits_processors`, include/fvhd.h "LLM logits processors"): one more launch inside the captured step edits the logits before the
+choice, from a token history the step keeps on the device.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Optional, Sequence, Union
 
@@ -84,6 +88,7 @@ class Qwen2Generator:
         self._logits = torch.empty((self.batch, prefill.vocab), device=self.device, dtype=torch.float32)
         self._ids = torch.zeros((self.batch,), device=self.device, dtype=torch.long)
         self._run_batch = 0
+        self._processors = None                                  # what set_logits_processors last set (None = all off)
 
     @classmethod
     def from_hf(cls, model, batch: int, capacity: int, prefill: Optional[Qwen2Prefill] = None, weights: str = "bf16") -> "Qwen2Generator":
@@ -184,6 +189,29 @@ class Qwen2Generator:
         _lib.check(lib.fvhd_llm_set_sampling(self.pre._h, int(bool(do_sample)), float(temperature), int(top_k), float(top_p),
                                              int(seed) & 0xFFFFFFFFFFFFFFFF), "fvhd_llm_set_sampling")
 
+    # ---- logits processors ---------------------------------------------------------------------------------------------------------------
+    def set_logits_processors(self, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0,
+                              eos_token_id: Union[None, int, Sequence[int]] = None, suppress_tokens: Optional[Sequence[int]] = None) -> None:
+        """transformers' processors on the logits of start() / step() from now on, before the choice (`fvhd_llm_set_logits_processors`,
+        `ml_fastvlm_amd.logits_processors`): repetition_penalty != 1, no_repeat_ngram_size >= 1, min_new_tokens >= 1 with eos_token_id (at
+        most 16 ids), suppress_tokens (at most 256 ids); the defaults switch them off.  The history they read is the tokens fed to the
+        steps since start() - set them before start().  With any of them on, the logits that start() / step() return are the processed
+        scores.  Synchronises; a captured step keeps the settings it was captured with.  Not for beam_search."""
+        from .logits_processors import normalize
+        cfg = normalize(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, suppress_tokens, vocab=self.pre.vocab)
+        if cfg is None and self._processors is None and _lib.load().fvhd_version() < _lib.PROCESSORS_VERSION:
+            return                                               # off on a library that has none: nothing to say
+        lib = _lib.processors_lib()
+        off = dict(repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, eos_token_id=[], suppress_tokens=[])
+        c = cfg or off
+        eos = (C.c_int32 * max(1, len(c["eos_token_id"])))(*c["eos_token_id"])
+        sup = (C.c_int32 * max(1, len(c["suppress_tokens"])))(*c["suppress_tokens"])
+        with torch.cuda.device(self.device):
+            _lib.check(lib.fvhd_llm_set_logits_processors(self.pre._h, c["repetition_penalty"], c["no_repeat_ngram_size"], c["min_new_tokens"],
+                                                          C.cast(eos, C.c_void_p), len(c["eos_token_id"]), C.cast(sup, C.c_void_p),
+                                                          len(c["suppress_tokens"])), "fvhd_llm_set_logits_processors")
+        self._processors = cfg
+
     def _set_greedy(self) -> None:
         if _lib.load().fvhd_version() >= _lib.SAMPLING_VERSION:      # a library without sampling is greedy anyway
             self.set_sampling(False)
@@ -192,29 +220,50 @@ class Qwen2Generator:
     @torch.no_grad()
     def greedy(self, inputs_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None,
                max_new_tokens: int = 256, eos_token_id: Union[None, int, Sequence[int]] = None, pad_token_id: Optional[int] = None,
-               graph: bool = True, poll_every: int = 16) -> torch.Tensor:
+               graph: bool = True, poll_every: int = 16, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0,
+               suppress_tokens: Optional[Sequence[int]] = None) -> torch.Tensor:
         """transformers' greedy search (`GenerationMixin._sample` with do_sample=False) on the library's steps -> new tokens [B, n].
         graph=True captures one step (decode + the finished-sequence bookkeeping) into a CUDA graph and replays it; "all finished" is
-        polled every `poll_every` steps (no host synchronisation per token) and the output trimmed to the step where it happened."""
+        polled every `poll_every` steps (no host synchronisation per token) and the output trimmed to the step where it happened.
+        repetition_penalty / no_repeat_ngram_size / min_new_tokens (with eos_token_id) / suppress_tokens: transformers' logits processors
+        (`set_logits_processors`), set for this run and cleared after it."""
         self._set_greedy()
-        return self._run(inputs_embeds, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id, graph, poll_every)
+        with self._processors_for_run(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, suppress_tokens):
+            return self._run(inputs_embeds, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id, graph, poll_every)
 
     @torch.no_grad()
     def sample(self, inputs_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None,
                max_new_tokens: int = 256, temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, seed: Optional[int] = None,
                eos_token_id: Union[None, int, Sequence[int]] = None, pad_token_id: Optional[int] = None, graph: bool = True,
-               poll_every: int = 16) -> torch.Tensor:
+               poll_every: int = 16, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0,
+               suppress_tokens: Optional[Sequence[int]] = None) -> torch.Tensor:
         """transformers' multinomial sampling (`GenerationMixin._sample` with do_sample=True, num_beams=1: temperature, then top-k, then
         top-p) on the library's steps -> new tokens [B, n], with greedy's return contract, EOS / pad bookkeeping and graph replay.
         seed None: 63 bits from torch's default CPU generator, so `torch.manual_seed` makes a run repeat.  The same seed gives the same
-        tokens, eager or graph; the draws are not torch.multinomial's (only the distribution is the same)."""
+        tokens, eager or graph; the draws are not torch.multinomial's (only the distribution is the same).  The logits processors of
+        `greedy` apply before the temperature, as in transformers."""
         if seed is None:
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.long).item())
         self.set_sampling(True, temperature, top_k, top_p, seed)
         try:
-            return self._run(inputs_embeds, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id, graph, poll_every)
+            with self._processors_for_run(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, suppress_tokens):
+                return self._run(inputs_embeds, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id, graph, poll_every)
         finally:
             self.set_sampling(False)
+
+    @contextlib.contextmanager
+    def _processors_for_run(self, repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, suppress_tokens):
+        """the keyword processors of greedy() / sample(): set for the run, cleared in a finally.  With none given, whatever
+        set_logits_processors set stays as it is."""
+        from .logits_processors import normalize
+        if normalize(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, suppress_tokens, vocab=self.pre.vocab) is None:
+            yield
+            return
+        self.set_logits_processors(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, suppress_tokens)
+        try:
+            yield
+        finally:
+            self.set_logits_processors()
 
     def _run(self, inputs_embeds, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id, graph, poll_every) -> torch.Tensor:
         if max_new_tokens < 1:
@@ -291,6 +340,9 @@ class Qwen2Generator:
         from .beam import BeamSearchState
         if num_beams < 2:
             raise ValueError(f"beam_search needs num_beams >= 2 (got {num_beams}): one beam is `greedy`")
+        if self._processors is not None:
+            raise ValueError("beam_search: logits processors are set (set_logits_processors) - they are not implemented under beam search; "
+                             "clear them with set_logits_processors()")
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be >= 1")
         G, T = inputs_embeds.shape[:2]

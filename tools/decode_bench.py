@@ -6,6 +6,7 @@ captured graph and called eagerly, against the stock `transformers` decode loop 
     python tools/decode_bench.py --trace-steps 16 --hidden 3584 --batch 64      (eager steps only: the program of a kernel trace)
     python tools/decode_bench.py --weights fp8_e4m3 ...                         (the packed matrices as e4m3 codes + row scales)
     python tools/decode_bench.py --num-beams 4 --hidden 896 3584 --batch 1 16   (beam search: --batch prompts x K beams per step)
+    python tools/decode_bench.py --processors --hidden 896 --batch 1 64         (logits processors on against off, greedy and sampled)
 
 --batch takes up to 64 sequences per step (more than 16 need a library of version 503).  --repeats times the graph replay that many
 times (`graph_ms_per_token` is their median, `graph_ms_per_token_runs` all of them); --no-stock leaves the stock transformers loop (and
@@ -19,6 +20,13 @@ top_p 0.95); greedy is timed before and after the sampled settings and averaged.
 bookkeeping) by graph replay over a whole search of --new tokens, and - each captured and replayed on its own, on the state the search
 left - its parts: the plain step on the same rows, the reorder (with the search's last parent map, and with the worst one: every row
 moves), the top-K launches and the torch bookkeeping; then the stock `transformers` beam search on the same prompts.
+
+--processors times the step with all four logits processors on (`Qwen2Generator.set_logits_processors`, csrc/llm_logits.hip:
+repetition_penalty 1.2, no_repeat_ngram_size 3, min_new_tokens 8 with two EOS ids, three suppressed ids) against the same build's step
+with none, greedy and sampled (predict.py's settings), each by graph replay over --new tokens, measured twice in alternation and averaged.
+The addition is split by differences of whole steps: logits store = greedy with logits_out - greedy; process launch = sampled on - sampled
+off (the sampler stores its logits and chooses the same way either way); argmax from the logits = greedy on - greedy with logits_out -
+process launch.
 
 Full layer counts, random bf16 weights (`tools/ttft.py: build_llm`).  Prints ONE JSON line: per (width, batch) the ms per token of each
 path, the bytes a step must read (packed weights + the KV cache at the mean length) and their fraction of 8 TB/s."""
@@ -174,6 +182,53 @@ def measure_sample(hidden: int, batch: int, prompt: int, new: int, dev) -> dict:
     return res
 
 
+PROCESSORS = dict(repetition_penalty=1.2, no_repeat_ngram_size=3, min_new_tokens=8, eos_token_id=[151645, 151643], suppress_tokens=[0, 1, 2])
+
+
+@torch.no_grad()
+def measure_processors(llm, pre, batch: int, prompt: int, new: int, dev) -> dict:
+    from ml_fastvlm_amd.qwen2_decode import Qwen2Generator
+    cfg = llm.config
+    hidden = cfg.hidden_size
+    gen = Qwen2Generator.from_hf(llm, batch, prompt + new + 4, prefill=pre)
+    g = torch.Generator(device=dev).manual_seed(0)
+    emb = (0.5 * torch.randn(batch, prompt, hidden, device=dev, generator=g)).to(torch.bfloat16)
+    mask = torch.ones(batch, prompt, device=dev, dtype=torch.long)
+    res = {"hidden": hidden, "layers": cfg.num_hidden_layers, "batch": batch, "vocab": cfg.vocab_size, "prompt": prompt, "new_tokens": new,
+           "processors": PROCESSORS, "sampling": SAMPLE_SETTINGS["predict_py"]}
+
+    def graph_ms(sample, proc, logits):
+        gen.set_sampling(bool(sample), seed=1, **(SAMPLE_SETTINGS["predict_py"] if sample else {}))
+        gen.set_logits_processors(**(PROCESSORS if proc else {}))
+        gen.start(emb, mask, logits=False)
+        graph = _graph_of(lambda: gen.step(logits=logits), dev)
+        graph.replay()
+        gen.start(emb, mask, logits=False)
+        ms = _ms_per(graph.replay, new, dev)
+        assert gen.cache_state() == (prompt + new, 0)
+        return ms
+
+    cases = {"greedy_off": (False, False, False), "greedy_off_logits_out": (False, False, True), "greedy_on": (False, True, False),
+             "sample_off": (True, False, False), "sample_on": (True, True, False)}
+    runs = {k: [] for k in cases}
+    for order in (list(cases), list(cases)[::-1]):              # twice, the second time in reverse order
+        for k in order:
+            runs[k].append(graph_ms(*cases[k]))
+    gen.set_sampling(False)
+    gen.set_logits_processors()
+    for k, v in runs.items():
+        res[f"{k}_ms_per_token"] = round(sum(v) / len(v), 4)
+        res[f"{k}_ms_per_token_runs"] = [round(x, 4) for x in v]
+    us = lambda a, b: round(1000 * (res[f"{a}_ms_per_token"] - res[f"{b}_ms_per_token"]), 1)      # noqa: E731
+    res["greedy_added_us_per_token"] = us("greedy_on", "greedy_off")
+    res["sample_added_us_per_token"] = us("sample_on", "sample_off")
+    res["logits_store_us"] = us("greedy_off_logits_out", "greedy_off")
+    res["process_launch_us"] = res["sample_added_us_per_token"]
+    res["argmax_from_logits_us"] = round(us("greedy_on", "greedy_off_logits_out") - res["process_launch_us"], 1)
+    del gen
+    return res
+
+
 def _graph_of(fn, dev):
     graph = torch.cuda.CUDAGraph()
     side = torch.cuda.Stream(dev)
@@ -294,6 +349,7 @@ def main():
     ap.add_argument("--no-stock", action="store_true", help="leave out the stock transformers loop and the eager library step")
     ap.add_argument("--weights", choices=["bf16", "fp8_e4m3"], default="bf16", help="storage of the packed LLM matrices (fp8_e4m3 needs a library of version 504)")
     ap.add_argument("--trace-steps", type=int, default=0, help="run only the prefill and this many eager steps (for a kernel trace)")
+    ap.add_argument("--processors", action="store_true", help="the step with all four logits processors on against off (needs a library of version 506)")
     ap.add_argument("--num-beams", type=int, default=0, help="time beam search with this many beams per prompt (--batch = prompts; needs a library of version 505)")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -312,6 +368,22 @@ def main():
             torch.cuda.empty_cache()
         print(json.dumps({"tool": "decode_bench", "mode": "beam", "device": torch.cuda.get_device_name(dev), "library_version": _lib.beam_lib().fvhd_version(),
                           "results": rows}))
+        return
+    if a.processors:
+        from tools.ttft import build_llm
+        from ml_fastvlm_amd import _lib
+        from ml_fastvlm_amd.qwen2_prefill import Qwen2Prefill
+        rows = []
+        for h in (a.hidden if "--hidden" in sys.argv else [896]):
+            llm = build_llm(h, dev)
+            pre = Qwen2Prefill.from_hf(llm)
+            for b in a.batch:
+                rows.append(measure_processors(llm, pre, b, a.prompt, a.new, dev))
+                torch.cuda.empty_cache()
+            del pre, llm
+            torch.cuda.empty_cache()
+        print(json.dumps({"tool": "decode_bench", "mode": "processors", "device": torch.cuda.get_device_name(dev),
+                          "library_version": _lib.processors_lib().fvhd_version(), "results": rows}))
         return
     if a.sample:
         hidden = a.hidden if "--hidden" in sys.argv else [896]
