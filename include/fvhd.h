@@ -60,7 +60,7 @@ typedef void* fvhd_stream_t; /* hipStream_t */
  * 506 adds logits processors in the decode step (fvhd_llm_set_logits_processors, fvhd_op_dec_logits_process): off by default, and then
  * every launch of fvhd_llm_start / fvhd_llm_decode is what 505 enqueued, bit for bit; fvhd_llm_cache_reserve also allocates the token
  * history (4 * batch * capacity + batch * vocab / 8 bytes); nothing earlier changed. */
-#define FVHD_VERSION 506
+#define FVHD_VERSION 507
 int fvhd_version(void);
 const char* fvhd_last_error(void);
 
@@ -627,6 +627,69 @@ int fvhd_llm_set_logits_processors(fvhd_llm* ctx, float repetition_penalty, int 
 int fvhd_op_dec_logits_process(fvhd_stream_t stream, float* logits, int B, int V, const int32_t* history, int capacity, int g, float repetition_penalty,
                                int no_repeat_ngram_size, int min_new_tokens, const int32_t* host_eos_ids, int n_eos, const int32_t* host_suppress_ids,
                                int n_suppress);
+
+/* ---- LLM speculative verification: up to 16 tokens of ONE sequence per step, drafts by prompt lookup (version 507) ----------------------
+ * A decode step at one sequence uses one of the MFMA tile's 16 columns.  A VERIFY step feeds the last chosen token and T - 1 drafted tokens
+ * as the T rows of one step (2 <= T <= 16), takes the argmax of every row, and keeps the longest prefix of drafts the model itself would have
+ * chosen: n = the largest value with draft[i] == ids[i] for all i < n, and ids[0 .. n] are emitted - between 1 and T tokens, by construction
+ * the greedy output.  Launches: one embed (the capacity check for T slots: error word 1 and nothing written when length + T > capacity; the T
+ * token rows; positions position + t; mask bytes [length, length + T) set), then per layer the decode's own q|k|v, o_proj, gate|up and
+ * down_proj launches at B = T and ONE attention launch for the T queries on the one cache row, the decode's lm_head + argmax at B = T, and one
+ * accept launch (last id, position and length advance by the emitted count, the mask bytes above the new length are cleared again; the k / v
+ * of rejected drafts stay in slots above the length, where no later step reads them before it overwrites them).  Nothing depends on the host
+ * between steps: a step is capture-safe and replays as one graph.
+ * Order contract: row t of a verify step has the BITS of the plain step at length + t + 1.  The GEMM rows are independent MFMA columns; the
+ * q|k|v launch writes row t's rotated k and its v into a staging row; the attention kernel reads the keys >= length from staging, lets one
+ * workgroup per kv head move them into cache slots [length, length + T), loads every key block once per wave for the wave's queries, and keeps,
+ * per query, the key slices, the 64-key blocks per wave, the online-softmax updates, the j order of P.V and the wave and slice combines of
+ * the single-query kernel.
+ * Scope: the batch of fvhd_llm_start is 1; greedy only.  Refused with an error that names the reason: sampling on, logits processors on (the
+ * verify step does not maintain their token history), a started batch above 1, rows outside [2, max_rows].  bf16 and e4m3 weights.
+ * Prompt lookup (what transformers offers as prompt_lookup_num_tokens; no draft model): the token buffer holds the optional lookup ids
+ * (e.g. the prompt's input_ids; negative placeholders such as an image token are allowed, they never match and never become a draft) and
+ * then every generated token.  For n = max_ngram .. 1 (n < buffer length) the suffix is the last n tokens; the LARGEST i with
+ * buffer[i .. i + n) == suffix and i + n < length wins; the drafts are buffer[i + n ..], at most K, cut at the buffer's end and at the first
+ * negative id; missing drafts (no match at any n included) are the buffer's last token.  ml_fastvlm_amd/prompt_lookup.py restates the rule.
+ * The choice of drafts never changes the output, only how many steps it takes. */
+/* Allocates the step's scratch in one allocation the context owns: T-row activations, the k / v staging rows, per-row positions, the
+ * attention partials (max_rows times the single-query size), the token buffer (lookup_capacity + capacity + 16 ids) and the device words.
+ * Needs fvhd_llm_cache_reserve first (which also frees this allocation: reserve again), head_dim 64 or 128, 2 <= max_rows <= 16.
+ * An allocation that already covers max_rows and lookup_capacity is kept and the call returns at once; otherwise it grows to the larger
+ * of the old and the new sizes and synchronises (refused while a stream is being captured). */
+int fvhd_llm_spec_reserve(fvhd_llm* ctx, int max_rows, int lookup_capacity);
+/* One verify step on draft_ids (device int64 [rows - 1]) after fvhd_llm_start / a decode or verify step: logits_out NULL or fp32
+ * [rows, vocab] (row t = the logits after token t of the step), ids_out NULL or int64 [rows] = their argmax, emitted_out NULL or a device
+ * int32 = the number of tokens emitted (ids_out[0 .. emitted)).  Capture-safe. */
+int fvhd_llm_verify(fvhd_llm* ctx, const int64_t* draft_ids, int rows, float* logits_out, int64_t* ids_out, int32_t* emitted_out, fvhd_stream_t stream);
+/* A lookup generation, after fvhd_llm_start: seeds the token buffer with lookup_ids (device int64 [n_lookup], n_lookup <= lookup_capacity;
+ * NULL with 0) and the token fvhd_llm_start chose, which is also tokens_out[0].  tokens_out: device int64 [max_new_tokens], written by the
+ * later steps; host_eos_ids: host int32 [n_eos <= 16].  One small launch; fvhd_llm_start ends the generation. */
+int fvhd_llm_lookup_begin(fvhd_llm* ctx, const int64_t* lookup_ids, int n_lookup, const int32_t* host_eos_ids, int n_eos, int max_new_tokens,
+                          int64_t* tokens_out, fvhd_stream_t stream);
+/* draft (rows - 1 drafts, 1 <= max_ngram <= 16) + verify + accept: the emitted run is cut after its first EOS id and at max_new_tokens, appended
+ * to the token buffer and to tokens_out; after an EOS or at the limit the generation is finished and further steps do nothing.  The host
+ * arguments are the same every step: capture-safe, 2 + 5 n_layers + 3 launches (draft, embed; lm_head, argmax reduce, accept). */
+int fvhd_llm_lookup_step(fvhd_llm* ctx, int rows, int max_ngram, fvhd_stream_t stream);
+/* synchronises the device, then (each optional): tokens written to tokens_out, the finished flag, verify steps run and tokens they emitted */
+int fvhd_llm_lookup_state(fvhd_llm* ctx, int* written, int* finished, int* steps, int* tokens);
+/* the three new operations on their own (tests), on plain device pointers.
+ * fvhd_op_dec_attention_multi: q [T, n_heads * head_dim] bf16, k_cache / v_cache [n_kv_heads][capacity][head_dim] of the one sequence,
+ * k_staged / v_staged [T][n_kv_heads][head_dim] = the keys / values of slots *length .. *length + T - 1, key_valid uint8 [capacity] (bytes
+ * [*length, *length + T) set by the caller) -> out [T, n_heads * head_dim]; row t = fvhd_op_dec_attention at length *length + t + 1, bit for
+ * bit, with the same `splits`; the staged rows are copied into their cache slots.  *length + T > capacity: nothing happens.  partial: fp32
+ * [T * n_heads * splits * (head_dim + 2)], counters: int [n_heads] zeroed.
+ * fvhd_op_dec_lookup_draft: tokens int32 [*length] on the device -> draft_out int64 [K], 1 <= K <= 15.
+ * fvhd_op_dec_lookup_accept: draft int64 [T - 1], ids int64 [T]; words NULL (a bare verify step) or the int32 [24] device words of a
+ * generation: [0] token-buffer length, [1] tokens written, [2] finished, [3] steps, [4] tokens emitted, [5] max_new_tokens, [6] n_eos,
+ * [8 .. 23] EOS ids; tokens / out: the token buffer and the output (NULL allowed); emitted: NULL or a device int32; then the state of the
+ * sequence: last id, next position, length (device words) and its key-valid bytes [capacity]. */
+int fvhd_op_dec_attention_multi(fvhd_stream_t stream, const void* q, void* k_cache, void* v_cache, const void* k_staged, const void* v_staged,
+                                const uint8_t* key_valid, void* out, int T, int n_heads, int n_kv_heads, int head_dim, int capacity, const int* length,
+                                float* partial, int* counters, int splits);
+int fvhd_op_dec_lookup_draft(fvhd_stream_t stream, const int32_t* tokens, const int* length, int max_ngram, int K, int64_t* draft_out);
+int fvhd_op_dec_lookup_accept(fvhd_stream_t stream, const int64_t* draft, const int64_t* ids, int T, int32_t* words, int32_t* tokens, int tokens_capacity,
+                              int64_t* out, int out_capacity, int32_t* emitted, int64_t* last_id, int64_t* position, int* length, uint8_t* key_valid,
+                              int capacity);
 
 #ifdef __cplusplus
 }

@@ -17,7 +17,9 @@ WIDE_BATCH_VERSION = 503       # the first whose decode takes more than 16 seque
 W8_VERSION = 504               # the first with 8-bit (e4m3) LLM weights: fvhd_llm_set_weight_format, fvhd_op_*_w8 (declared only when the library has them)
 BEAM_VERSION = 505             # the first with beam search: fvhd_llm_beam_reserve / _cache_gather / _beam_topk, fvhd_op_dec_beam_topk / _cache_gather (declared only when the library has them)
 PROCESSORS_VERSION = 506      # the first with logits processors in the step: fvhd_llm_set_logits_processors, fvhd_op_dec_logits_process (declared only when the library has them)
+LOOKUP_VERSION = 507          # the first with speculative verification / prompt-lookup decoding: fvhd_llm_spec_reserve / _verify / _lookup_*, fvhd_op_dec_attention_multi / _lookup_draft / _lookup_accept (declared only when the library has them)
 MAX_DECODE_BATCH = 64
+MAX_VERIFY_ROWS = 16           # rows of one verify step (include/fvhd.h)
 MAX_EOS_IDS, MAX_SUPPRESS_IDS = 16, 256      # list limits of fvhd_llm_set_logits_processors (include/fvhd.h)
 W_BF16, W_E4M3 = 0, 1           # fvhd_llm_set_weight_format (include/fvhd.h)
 WEIGHT_FORMATS = {"bf16": W_BF16, "fp8_e4m3": W_E4M3}
@@ -142,6 +144,17 @@ def _declare(lib) -> None:
             "fvhd_llm_set_logits_processors": (ci, [vp, cf, ci, ci, vp, ci, vp, ci]),
             "fvhd_op_dec_logits_process": (ci, [vp, vp, ci, ci, vp, ci, ci, cf, ci, ci, vp, ci, vp, ci]),
         })
+    if lib.fvhd_version() >= LOOKUP_VERSION:       # an older library loads without them; lookup_lib() then names the rebuild
+        sig.update({
+            "fvhd_llm_spec_reserve": (ci, [vp, ci, ci]),
+            "fvhd_llm_verify": (ci, [vp, vp, ci, vp, vp, vp, vp]),
+            "fvhd_llm_lookup_begin": (ci, [vp, vp, ci, vp, ci, ci, vp, vp]),
+            "fvhd_llm_lookup_step": (ci, [vp, ci, ci, vp]),
+            "fvhd_llm_lookup_state": (ci, [vp] + [C.POINTER(ci)] * 4),
+            "fvhd_op_dec_attention_multi": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, ci]),
+            "fvhd_op_dec_lookup_draft": (ci, [vp, vp, vp, ci, ci, vp]),
+            "fvhd_op_dec_lookup_accept": (ci, [vp, vp, vp, ci, vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, ci]),
+        })
     del fp, cl
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)     # AttributeError here = the .so does not export what fvhd.h declares
@@ -211,6 +224,17 @@ def processors_lib():
     if got < PROCESSORS_VERSION:
         raise FvhdError(f"{LIB_PATH} reports ABI version {got}: logits processors (fvhd_llm_set_logits_processors, "
                         f"fvhd_op_dec_logits_process) need {PROCESSORS_VERSION} - rebuild the library (`python -m ml_fastvlm_amd.build`)")
+    return lib
+
+
+def lookup_lib():
+    """load(), for speculative verification and prompt-lookup decoding: a library older than LOOKUP_VERSION loads (every other way of
+    decoding works on it) but has none of the entry points, and this says so instead of an AttributeError."""
+    lib = load()
+    got = lib.fvhd_version()
+    if got < LOOKUP_VERSION:
+        raise FvhdError(f"{LIB_PATH} reports ABI version {got}: prompt-lookup decoding (fvhd_llm_spec_reserve, fvhd_llm_verify, "
+                        f"fvhd_llm_lookup_step, ...) needs {LOOKUP_VERSION} - rebuild the library (`python -m ml_fastvlm_amd.build`)")
     return lib
 
 

@@ -279,11 +279,14 @@ def generator_context(model, batch: int, capacity: int, weights=None):
 
 @torch.no_grad()
 def generate(model, input_ids, images=None, image_sizes=None, attention_mask=None, max_new_tokens: int = 256, eos_token_id=None,
-             pad_token_id=None, do_sample: bool = False, num_beams: int = 1, **kwargs):
+             pad_token_id=None, do_sample: bool = False, num_beams: int = 1, prompt_lookup_num_tokens=None,
+             max_matching_ngram_size: int = 2, **kwargs):
     """`LlavaQwen2ForCausalLM.generate` (`llava_qwen.py:106-143`) with greedy decoding on the library: the multimodal splice
     (`model.prepare_inputs_labels_for_multimodal`) or the token embedding, then the prefill and every decode step on the hand-written
     Qwen2 kernels (`Qwen2Generator.greedy`).  Returns the new tokens [B, n] as transformers' generate(inputs_embeds=...) does.  Greedy only:
-    sampling, beam search and other decoding strategies raise NotImplementedError.  The model must be bf16 on a HIP device."""
+    sampling, beam search and other decoding strategies raise NotImplementedError.  The model must be bf16 on a HIP device.
+    prompt_lookup_num_tokens=K (1 .. 15, one prompt per call): prompt-lookup decoding (`Qwen2Generator.lookup_greedy`) - the same tokens, K
+    drafts from n-gram matches (n <= max_matching_ngram_size) in `input_ids` and the generated tokens verified per step."""
     if do_sample:
         raise NotImplementedError("ml_fastvlm_amd.generate: do_sample=True (sampling) is not implemented - greedy decoding only; "
                                   "Qwen2Generator.step exposes the logits for sampling in torch")
@@ -296,6 +299,11 @@ def generate(model, input_ids, images=None, image_sizes=None, attention_mask=Non
         if k in _GENERATE_IGNORED or (k == "use_cache" and v):
             continue
         raise NotImplementedError(f"ml_fastvlm_amd.generate: the generation setting {k}={v!r} is not implemented - greedy decoding only")
+    lookup = None
+    if prompt_lookup_num_tokens is not None:
+        if input_ids.shape[0] != 1:
+            raise ValueError(f"ml_fastvlm_amd.generate: prompt_lookup_num_tokens takes ONE prompt per call (got a batch of {input_ids.shape[0]})")
+        lookup = dict(prompt_lookup_num_tokens=int(prompt_lookup_num_tokens), max_matching_ngram_size=int(max_matching_ngram_size), lookup_ids=input_ids)
     lm_w = model.lm_head.weight
     if lm_w.device.type != "cuda" or lm_w.dtype != torch.bfloat16:
         raise ValueError(f"ml_fastvlm_amd.generate: needs a bf16 model on a HIP device (got {lm_w.dtype} on {lm_w.device}); "
@@ -305,7 +313,7 @@ def generate(model, input_ids, images=None, image_sizes=None, attention_mask=Non
         eos_token_id = getattr(gc, "eos_token_id", None)
     if pad_token_id is None:
         pad_token_id = getattr(gc, "pad_token_id", None)
-    return _generate_on_library(model, input_ids, images, image_sizes, attention_mask, None, max_new_tokens, eos_token_id, pad_token_id)
+    return _generate_on_library(model, input_ids, images, image_sizes, attention_mask, None, max_new_tokens, eos_token_id, pad_token_id, lookup=lookup)
 
 
 @torch.no_grad()
@@ -331,7 +339,7 @@ def beam_generate(model, input_ids, images=None, image_sizes=None, attention_mas
 
 
 def _generate_on_library(model, input_ids, images, image_sizes, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id,
-                         sampling=None, beam=None, processors=None):
+                         sampling=None, beam=None, processors=None, lookup=None):
     """the body shared by `generate`, `beam_generate` and `_make_library_generate`: the multimodal splice (or the token embedding), then the
     prefill and every decode step on the library - `Qwen2Generator.greedy`, `.sample(**sampling)` or `.beam_search(**beam)`; processors:
     None or the logits-processor keywords of greedy / sample (repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens)"""
@@ -345,6 +353,10 @@ def _generate_on_library(model, input_ids, images, image_sizes, attention_mask, 
         gen = generator_context(model, B * beam["num_beams"], T + max_new_tokens)
         return gen.beam_search(inputs_embeds, attention_mask, position_ids, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id,
                                pad_token_id=pad_token_id, **beam)
+    if lookup is not None:                                    # greedy, one prompt: the cache also holds the drafts of the last step
+        gen = generator_context(model, B, T + max_new_tokens + lookup["prompt_lookup_num_tokens"])
+        return gen.lookup_greedy(inputs_embeds, attention_mask, position_ids, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id,
+                                 pad_token_id=pad_token_id, **lookup)
     gen = generator_context(model, B, T + max_new_tokens)
     processors = processors or {}
     if sampling is None:

@@ -86,6 +86,17 @@ int fvhd_dec_beam_topk_supported(int G, int K, int C, int V);
 int fvhd_launch_dec_beam_topk(hipStream_t st, const float* logits, const float* scores, int G, int K, int C, int V, float* out_v, int64_t* out_i, void* ws);
 size_t fvhd_dec_cache_gather_ws_bytes(int rows, int nkv, int hd, int cap);
 int fvhd_launch_dec_cache_gather(hipStream_t st, const DecCacheGatherArgs* a);
+// llm_spec.hip
+int fvhd_launch_spec_draft(hipStream_t st, const int* seq, const int* seq_len, int max_ngram, int K, int64_t* draft, const int* status, const int* words,
+                           int* gate);
+int fvhd_launch_spec_embed(hipStream_t st, const int64_t* draft, const int64_t* last, const void* table, const float* scale, int V, int H, void* h,
+                           unsigned char* key_valid, int T, int cap, const int* len, const int64_t* posv, int64_t* pos, int* status, int* status_host,
+                           int* gate);
+int fvhd_launch_spec_attention(hipStream_t st, const void* q, void* kc, void* vc, const void* ks, const void* vs, const unsigned char* key_valid, void* out,
+                               int T, int nh, int nkv, int hd, int cap, const int* len, int S, int chunk, float* part, int* cnt, const int* status);
+int fvhd_launch_spec_accept(hipStream_t st, const SpecAcceptArgs* a);
+int fvhd_launch_spec_begin(hipStream_t st, const int64_t* lookup, int n, const int64_t* last, int* seq, int64_t* out, int* words, int limit,
+                           const SpecEosList* eos);
 // llm_logits.hip
 int fvhd_launch_dec_logits_process(hipStream_t st, const DecLogitsArgs* a);
 int fvhd_launch_dec_logits_history(hipStream_t st, const int* tokens, int* hist, unsigned* seen, int B, int V, int cap, int g);

@@ -90,6 +90,18 @@ struct __attribute__((visibility("default"))) fvhd_llm {     // (its inline cons
     unsigned* hist_seen = nullptr;         // [dc_batch][ceil(V / 32)] and the prompt length recorded by the last fvhd_llm_start that ran
     int* hist_base = nullptr;              // with processors on (history length = cache length - it)
     bool hist_started = false;             // that start has happened: a decode step with processors on has a history to append to
+    // fvhd_llm_spec_reserve (llm_spec.hip): one allocation of its own, sized for the reserved cache - the T-row activations, the k / v
+    // staging rows [T][nkv][hd], the per-row positions, the attention partials [T][nh][att_S][hd + 2] and counters [nh], the drafts and
+    // ids of a step, the token buffer and the device words of a lookup generation (llm_decode.h SPEC_W_*)
+    char* spec = nullptr;
+    int spec_rows = 0, spec_seq_cap = 0;
+    char *sp_h = nullptr, *sp_q = nullptr, *sp_att = nullptr, *sp_act = nullptr, *sp_ks = nullptr, *sp_vs = nullptr;
+    int64_t *sp_pos = nullptr, *sp_draft = nullptr, *sp_ids = nullptr;
+    float* sp_apart = nullptr;
+    int *sp_cnt = nullptr, *sp_zero = nullptr, *sp_gate = nullptr, *sp_words = nullptr, *sp_seq = nullptr;
+    int64_t* sp_out = nullptr;             // fvhd_llm_lookup_begin: the caller's output tokens [sp_out_cap]
+    int sp_out_cap = 0;
+    bool sp_begun = false;
 };
 
 inline bool processors_on(const fvhd_llm* c)

@@ -99,3 +99,35 @@ struct DecLogitsArgs {
     int n_eos = 0, n_sup = 0;
     const int* status = nullptr;   // non-NULL: the launch does nothing (appends nothing) while *status != 0
 };
+
+// Speculative verification (llm_spec.hip).  The device words of a lookup generation, int32 [SPEC_WORDS]:
+#define SPEC_W_SEQ_LEN 0     // tokens in the token buffer (lookup ids, then every generated token)
+#define SPEC_W_WRITTEN 1     // tokens written to the output buffer
+#define SPEC_W_FINISHED 2    // an EOS id was emitted, or the token limit was reached: later steps do nothing
+#define SPEC_W_STEPS 3       // verify steps that ran
+#define SPEC_W_TOKENS 4      // tokens those steps emitted
+#define SPEC_W_LIMIT 5       // max_new_tokens
+#define SPEC_W_N_EOS 6
+#define SPEC_W_EOS 8         // .. 23: the EOS ids
+#define SPEC_WORDS 24
+
+struct SpecEosList { int n = 0; int ids[16] = {}; };
+
+// Arguments of the accept launch: drafts int64 [T - 1] against the step's argmax ids int64 [T]
+struct SpecAcceptArgs {
+    const int64_t* draft = nullptr;
+    const int64_t* ids = nullptr;
+    int T = 0;
+    int* words = nullptr;          // NULL: a bare verify step - no EOS cut, no limit, nothing appended
+    int* seq = nullptr;            // the token buffer int32 [seq_cap]
+    int seq_cap = 0;
+    int64_t* out = nullptr;        // the output tokens int64 [out_cap]
+    int out_cap = 0;
+    int* emitted = nullptr;        // optional: the number of tokens this step emitted (1 .. T)
+    int64_t* last = nullptr;       // the cache state of sequence 0: last id, next position, length, key-valid mask [cap]
+    int64_t* posv = nullptr;
+    int* len = nullptr;
+    unsigned char* key_valid = nullptr;
+    int cap = 0;
+    const int* gate = nullptr;     // non-NULL: the launch does nothing while *gate != 0
+};

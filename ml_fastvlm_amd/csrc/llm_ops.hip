@@ -313,4 +313,39 @@ int fvhd_op_dec_logits_process(fvhd_stream_t st, float* logits, int B, int V, co
     return lret("fvhd_op_dec_logits_process", fvhd_launch_dec_logits_process(s, &a));
 }
 
+// ---- single ops of the verify step (llm_spec.hip) ----
+int fvhd_op_dec_attention_multi(fvhd_stream_t st, const void* q, void* k_cache, void* v_cache, const void* k_staged, const void* v_staged,
+                                const uint8_t* key_valid, void* out, int T, int n_heads, int n_kv_heads, int head_dim, int capacity, const int* length,
+                                float* partial, int* counters, int splits)
+{
+    if (!q || !k_cache || !v_cache || !k_staged || !v_staged || !key_valid || !out || !length) return lfail("fvhd_op_dec_attention_multi: NULL pointer");
+    if (T < 2 || T > 16) return lfail("fvhd_op_dec_attention_multi: needs 2 <= T <= 16");
+    if (head_dim != 64 && head_dim != 128) return lfail("fvhd_op_dec_attention_multi: head_dim must be 64 or 128");
+    if (n_heads < 1 || n_kv_heads < 1 || n_heads % n_kv_heads) return lfail("fvhd_op_dec_attention_multi: n_heads must be a multiple of n_kv_heads");
+    if (splits < 1 || capacity < 1 || (splits > 1 && (!partial || !counters)))
+        return lfail("fvhd_op_dec_attention_multi: splits >= 1 (and scratch when splits > 1)");
+    const int chunk = ((capacity + splits - 1) / splits + 63) / 64 * 64, S = (capacity + chunk - 1) / chunk;
+    return lret("fvhd_op_dec_attention_multi", fvhd_launch_spec_attention((hipStream_t)st, q, k_cache, v_cache, k_staged, v_staged, key_valid, out, T, n_heads,
+                                                                          n_kv_heads, head_dim, capacity, length, S, chunk, partial, counters, nullptr));
+}
+
+int fvhd_op_dec_lookup_draft(fvhd_stream_t st, const int32_t* tokens, const int* length, int max_ngram, int K, int64_t* draft_out)
+{
+    if (!tokens || !length || !draft_out) return lfail("fvhd_op_dec_lookup_draft: NULL pointer");
+    if (max_ngram < 1 || max_ngram > 16 || K < 1 || K > 15) return lfail("fvhd_op_dec_lookup_draft: needs 1 <= max_ngram <= 16 and 1 <= K <= 15");
+    return lret("fvhd_op_dec_lookup_draft", fvhd_launch_spec_draft((hipStream_t)st, tokens, length, max_ngram, K, draft_out, nullptr, nullptr, nullptr));
+}
+
+int fvhd_op_dec_lookup_accept(fvhd_stream_t st, const int64_t* draft, const int64_t* ids, int T, int32_t* words, int32_t* tokens, int tokens_capacity,
+                              int64_t* out, int out_capacity, int32_t* emitted, int64_t* last_id, int64_t* position, int* length, uint8_t* key_valid,
+                              int capacity)
+{
+    if (!draft || !ids || !last_id || !position || !length || !key_valid) return lfail("fvhd_op_dec_lookup_accept: NULL pointer");
+    if (T < 2 || T > 16 || capacity < 1 || tokens_capacity < 0 || out_capacity < 0) return lfail("fvhd_op_dec_lookup_accept: needs 2 <= T <= 16 and capacity >= 1");
+    SpecAcceptArgs a;
+    a.draft = draft; a.ids = ids; a.T = T; a.words = words; a.seq = tokens; a.seq_cap = tokens_capacity; a.out = out; a.out_cap = out_capacity;
+    a.emitted = emitted; a.last = last_id; a.posv = position; a.len = length; a.key_valid = key_valid; a.cap = capacity;
+    return lret("fvhd_op_dec_lookup_accept", fvhd_launch_spec_accept((hipStream_t)st, &a));
+}
+
 }  // extern "C"

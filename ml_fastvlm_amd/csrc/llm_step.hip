@@ -1,5 +1,5 @@
 // C ABI of the Qwen2 decode (include/fvhd.h "LLM decode"): the library's own KV cache, one token per sequence per step.
-// Kernels: llm_decode.hip, llm_w8.hip, llm_sample.hip, llm_beam.hip, llm_logits.hip.
+// Kernels: llm_decode.hip, llm_w8.hip, llm_sample.hip, llm_beam.hip, llm_logits.hip, llm_spec.hip.
 #include <algorithm>
 #include <cmath>
 
@@ -143,7 +143,10 @@ int fvhd_llm_cache_reserve(fvhd_llm* c, int batch, int capacity)
     if (he != hipSuccess) return lhip("fvhd_llm_cache_reserve: hipDeviceSynchronize", he);
     if (c->dc) (void)hipFree(c->dc);
     if (c->beam) (void)hipFree(c->beam);                         // sized for the cache it was reserved for: fvhd_llm_beam_reserve again
-    c->dc = c->beam = c->beam_topk = nullptr;
+    if (c->spec) (void)hipFree(c->spec);                         // likewise: fvhd_llm_spec_reserve again
+    c->dc = c->beam = c->beam_topk = c->spec = nullptr;
+    c->spec_rows = 0;
+    c->sp_begun = false;
     c->dc_batch = c->dc_cap = c->run_batch = 0;
     c->hist_started = false;
     if ((he = hipMalloc((void**)&c->dc, a.off)) != hipSuccess) return lhip("hipMalloc(llm KV cache)", he);
@@ -230,6 +233,7 @@ int fvhd_llm_start(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* ke
         LCHECK(fvhd_launch_dec_start_state(st, c->posv, position_ids, B, T, c->len, c->status), "decode state");
     }
     c->run_batch = B;
+    c->sp_begun = false;                                         // a lookup generation belongs to the sequence it was begun on
     return 0;
 }
 
@@ -358,6 +362,181 @@ int fvhd_llm_beam_topk(fvhd_llm* c, const float* logits, const float* beam_score
     LLM_ON_DEVICE(c);
     LCHECK(fvhd_launch_dec_beam_topk((hipStream_t)stream, logits, beam_scores, groups, num_beams, keep, c->V, cand_scores, cand_index, c->beam_topk),
            "beam top-K");
+    return 0;
+}
+
+// ---- speculative verification (include/fvhd.h "LLM speculative verification"; kernels: llm_spec.hip) ----
+int fvhd_llm_spec_reserve(fvhd_llm* c, int max_rows, int lookup_capacity)
+{
+    if (!c || !c->dc) return lfail("fvhd_llm_spec_reserve: no KV cache - call fvhd_llm_cache_reserve first");
+    if (max_rows < 2 || max_rows > 16 || lookup_capacity < 0)
+        return lfail("fvhd_llm_spec_reserve: needs 2 <= max_rows <= 16 (the rows of one verify step) and lookup_capacity >= 0");
+    if (c->hd != 64 && c->hd != 128) return lfail("fvhd_llm_spec_reserve: the verify step's attention needs head_dim 64 or 128");
+    if (c->spec && c->spec_rows >= max_rows && c->spec_seq_cap >= lookup_capacity + c->dc_cap + 16) return 0;      // covered: kept as it is
+    LLM_ON_DEVICE(c);
+    hipError_t he = hipDeviceSynchronize();                      // refused while a stream is being captured (like fvhd_llm_cache_reserve)
+    if (he != hipSuccess) return lhip("fvhd_llm_spec_reserve: hipDeviceSynchronize", he);
+    const int T = std::max(max_rows, c->spec ? c->spec_rows : 0), H = c->H, I = c->I, nh = c->nh, nkv = c->nkv, hd = c->hd;
+    const int seq_cap = std::max(lookup_capacity + c->dc_cap + 16, c->spec ? c->spec_seq_cap : 0);
+    if (c->spec) (void)hipFree(c->spec);
+    c->spec = nullptr;
+    c->spec_rows = 0;
+    c->sp_begun = false;
+    Arena a;
+    const size_t o_h = a.take((size_t)T * H * 2), o_q = a.take((size_t)T * nh * hd * 2), o_att = a.take((size_t)T * nh * hd * 2),
+                 o_act = a.take((size_t)T * I * 2), o_ks = a.take((size_t)T * nkv * hd * 2), o_vs = a.take((size_t)T * nkv * hd * 2),
+                 o_pos = a.take(8 * T), o_draft = a.take(8 * 16), o_ids = a.take(8 * 16),
+                 o_apart = a.take((size_t)T * nh * c->att_S * (hd + 2) * 4), o_cnt = a.take((size_t)nh * 4), o_zero = a.take(4), o_gate = a.take(4),
+                 o_words = a.take(SPEC_WORDS * 4), o_seq = a.take((size_t)seq_cap * 4);
+    if ((he = hipMalloc((void**)&c->spec, a.off)) != hipSuccess) { c->spec = nullptr; return lhip("hipMalloc(verify step scratch)", he); }
+    if ((he = hipMemset(c->spec, 0, a.off)) != hipSuccess) return lhip("hipMemset(verify step scratch)", he);      // counters and the zero word
+    char* d = c->spec;
+    c->sp_h = d + o_h; c->sp_q = d + o_q; c->sp_att = d + o_att; c->sp_act = d + o_act; c->sp_ks = d + o_ks; c->sp_vs = d + o_vs;
+    c->sp_pos = (int64_t*)(d + o_pos); c->sp_draft = (int64_t*)(d + o_draft); c->sp_ids = (int64_t*)(d + o_ids); c->sp_apart = (float*)(d + o_apart);
+    c->sp_cnt = (int*)(d + o_cnt); c->sp_zero = (int*)(d + o_zero); c->sp_gate = (int*)(d + o_gate); c->sp_words = (int*)(d + o_words);
+    c->sp_seq = (int*)(d + o_seq);
+    c->spec_rows = T; c->spec_seq_cap = seq_cap;
+    return 0;
+}
+
+namespace {
+
+int spec_refusal(const fvhd_llm* c, const char* who, int rows)
+{
+    const std::string w(who);
+    if (!c->dc || !c->run_batch) return lfail(w + ": no started sequence - call fvhd_llm_cache_reserve and fvhd_llm_start first");
+    if (!c->spec) return lfail(w + ": no scratch - call fvhd_llm_spec_reserve first");
+    if (c->run_batch != 1) return lfail(w + ": the verify step takes ONE sequence (the batch of fvhd_llm_start is " + std::to_string(c->run_batch) + ")");
+    if (rows < 2 || rows > c->spec_rows)
+        return lfail(w + ": rows must be in [2, the max_rows of fvhd_llm_spec_reserve = " + std::to_string(c->spec_rows) + "]");
+    if (c->do_sample) return lfail(w + ": sampling is on (fvhd_llm_set_sampling) - the verify step is greedy only: it keeps the drafts the argmax confirms");
+    if (processors_on(c))
+        return lfail(w + ": logits processors are on (fvhd_llm_set_logits_processors) - the verify step does not maintain their token history");
+    return 0;
+}
+
+// one verify step on the drafts at `draft` (device int64 [T - 1]): embed, the decode's launches at B = T, the ids of the T rows
+int spec_enqueue(fvhd_llm* c, const int64_t* draft, int T, float* logits_out, int64_t* ids, int* gate, hipStream_t st)
+{
+    const int H = c->H, I = c->I, nh = c->nh, nkv = c->nkv, hd = c->hd, cap = c->dc_cap;
+    const char* w = c->wdev;
+    const bool q8 = c->wfmt == FVHD_W_E4M3;
+    const bool packed = q8 && !c->emb;                           // a tied model: the token rows dequantised from the lm_head codes
+    LCHECK(fvhd_launch_spec_embed(st, draft, c->last_ids, c->emb ? c->emb : w + c->lm_off, packed ? (const float*)(w + c->lm_soff) : nullptr, c->V, H, c->sp_h,
+                                  c->mask, T, cap, c->len, c->posv, c->sp_pos, c->status, c->status_host_dev, gate), "verify embed");
+    const size_t layer_kv = (size_t)c->dc_batch * nkv * cap * hd * 2;
+    auto gemm = [&](int epi, const void* x, const float* norm_w, int layer, int matrix) {
+        const Mat m = mat_of(c, layer, matrix);
+        const fvhd_llm::Plan& p = c->plan[matrix];
+        DecGemmArgs a;
+        a.wscale = q8 ? (const float*)(w + m.soff) : nullptr;
+        a.x = x; a.ldx = m.K; a.norm_w = norm_w; a.eps = c->eps; a.W = w + m.off; a.N = (int)m.N; a.K = m.K; a.B = T; a.S = p.S; a.cpw = p.cpw;
+        a.part = c->dpart; a.cnt = c->cnt; a.epi = epi; a.status = gate;
+        return a;
+    };
+    for (int l = 0; l < c->L; ++l) {
+        const LayerOff& o = c->lo[l];
+        // q|k|v on the decode's launch: per-row positions, k / v into staging row t (a "cache" of capacity 1 whose length word is 0)
+        DecGemmArgs a = gemm(DEC_EPI_QKV, c->sp_h, (const float*)(w + o.ln1), l, FVHD_MAT_QKV);
+        a.bias = (const float*)(w + o.bqkv); a.out = c->sp_q; a.ldo = nh * hd; a.pos = c->sp_pos; a.rope = c->drope; a.P = c->dc_pos; a.theta = c->theta;
+        a.nh = nh; a.nkv = nkv; a.hd = hd; a.kc = c->sp_ks; a.vc = c->sp_vs; a.cap = 1; a.len = c->sp_zero;
+        LCHECK(fvhd_launch_dec_gemm(st, &a), "verify q|k|v + rope + staging");
+        LCHECK(fvhd_launch_spec_attention(st, c->sp_q, c->kcache + l * layer_kv, c->vcache + l * layer_kv, c->sp_ks, c->sp_vs, c->mask, c->sp_att, T, nh, nkv,
+                                          hd, cap, c->len, c->att_S, c->att_chunk, c->sp_apart, c->sp_cnt, gate), "verify attention + cache append");
+        a = gemm(DEC_EPI_RESID, c->sp_att, nullptr, l, FVHD_MAT_O);
+        a.resid = c->sp_h; a.out = c->sp_h; a.ldo = H;
+        LCHECK(fvhd_launch_dec_gemm(st, &a), "verify o_proj + residual");
+        a = gemm(DEC_EPI_SWIGLU, c->sp_h, (const float*)(w + o.ln2), l, FVHD_MAT_GATE_UP);
+        a.out = c->sp_act; a.ldo = I;
+        LCHECK(fvhd_launch_dec_gemm(st, &a), "verify rmsnorm + gate|up + silu");
+        a = gemm(DEC_EPI_RESID, c->sp_act, nullptr, l, FVHD_MAT_DOWN);
+        a.resid = c->sp_h; a.out = c->sp_h; a.ldo = H;
+        LCHECK(fvhd_launch_dec_gemm(st, &a), "verify down_proj + residual");
+    }
+    DecGemmArgs a = gemm(DEC_EPI_ARGMAX, c->sp_h, (const float*)(w + c->norm_off), -1, FVHD_MAT_LM_HEAD);
+    a.logits = logits_out; a.amax_v = c->amax_v; a.amax_i = c->amax_i;
+    LCHECK(fvhd_launch_dec_gemm(st, &a), "verify final norm + lm_head + argmax");
+    LCHECK(fvhd_launch_dec_argmax_finish(st, c->amax_v, c->amax_i, (c->V / 16 + 3) / 4, T, nullptr, ids, nullptr, nullptr, gate), "verify argmax reduce");
+    return 0;
+}
+
+void spec_accept_args(fvhd_llm* c, const int64_t* draft, int T, int* gate, SpecAcceptArgs& a)
+{
+    a.draft = draft; a.ids = c->sp_ids; a.T = T; a.last = c->last_ids; a.posv = c->posv; a.len = c->len; a.key_valid = c->mask; a.cap = c->dc_cap;
+    a.gate = gate;
+}
+
+}  // namespace
+
+int fvhd_llm_verify(fvhd_llm* c, const int64_t* draft_ids, int rows, float* logits_out, int64_t* ids_out, int32_t* emitted_out, fvhd_stream_t stream)
+{
+    if (!c || !draft_ids) return lfail("fvhd_llm_verify: NULL argument");
+    if (int e = spec_refusal(c, "fvhd_llm_verify", rows)) return e;
+    if (int e = dec_status_error(c, "fvhd_llm_verify")) return e;
+    if (int e = dec_embedding_error(c, "fvhd_llm_verify")) return e;
+    LLM_ON_DEVICE(c);
+    hipStream_t st = (hipStream_t)stream;
+    int64_t* ids = ids_out ? ids_out : c->sp_ids;                // the argmax reduce writes them, the accept reads them
+    if (int e = spec_enqueue(c, draft_ids, rows, logits_out, ids, c->status, st)) return e;
+    SpecAcceptArgs a;
+    spec_accept_args(c, draft_ids, rows, c->status, a);
+    a.ids = ids;
+    a.emitted = emitted_out;
+    LCHECK(fvhd_launch_spec_accept(st, &a), "verify accept");
+    return 0;
+}
+
+int fvhd_llm_lookup_begin(fvhd_llm* c, const int64_t* lookup_ids, int n_lookup, const int32_t* host_eos_ids, int n_eos, int max_new_tokens,
+                          int64_t* tokens_out, fvhd_stream_t stream)
+{
+    if (!c || !tokens_out) return lfail("fvhd_llm_lookup_begin: NULL argument");
+    if (int e = spec_refusal(c, "fvhd_llm_lookup_begin", 2)) return e;
+    if (n_lookup < 0 || (n_lookup && !lookup_ids) || n_lookup + c->dc_cap + 16 > c->spec_seq_cap)
+        return lfail("fvhd_llm_lookup_begin: n_lookup must be in [0, the lookup_capacity of fvhd_llm_spec_reserve]");
+    if (n_eos < 0 || n_eos > kMaxEos || (n_eos && !host_eos_ids)) return lfail("fvhd_llm_lookup_begin: at most " + std::to_string(kMaxEos) + " EOS ids");
+    if (max_new_tokens < 1) return lfail("fvhd_llm_lookup_begin: max_new_tokens must be >= 1");
+    LLM_ON_DEVICE(c);
+    SpecEosList eos;
+    eos.n = n_eos;
+    for (int i = 0; i < n_eos; ++i) eos.ids[i] = host_eos_ids[i];
+    LCHECK(fvhd_launch_spec_begin((hipStream_t)stream, lookup_ids, n_lookup, c->last_ids, c->sp_seq, tokens_out, c->sp_words, max_new_tokens, &eos),
+           "lookup begin");
+    c->sp_out = tokens_out; c->sp_out_cap = max_new_tokens; c->sp_begun = true;
+    return 0;
+}
+
+int fvhd_llm_lookup_step(fvhd_llm* c, int rows, int max_ngram, fvhd_stream_t stream)
+{
+    if (!c) return lfail("fvhd_llm_lookup_step: ctx is NULL");
+    if (int e = spec_refusal(c, "fvhd_llm_lookup_step", rows)) return e;
+    if (!c->sp_begun) return lfail("fvhd_llm_lookup_step: no token buffer - call fvhd_llm_lookup_begin after fvhd_llm_start");
+    if (max_ngram < 1 || max_ngram > 16) return lfail("fvhd_llm_lookup_step: max_ngram must be in [1, 16]");
+    if (int e = dec_status_error(c, "fvhd_llm_lookup_step")) return e;
+    if (int e = dec_embedding_error(c, "fvhd_llm_lookup_step")) return e;
+    LLM_ON_DEVICE(c);
+    hipStream_t st = (hipStream_t)stream;
+    LCHECK(fvhd_launch_spec_draft(st, c->sp_seq, c->sp_words + SPEC_W_SEQ_LEN, max_ngram, rows - 1, c->sp_draft, c->status, c->sp_words, c->sp_gate),
+           "lookup draft");
+    if (int e = spec_enqueue(c, c->sp_draft, rows, nullptr, c->sp_ids, c->sp_gate, st)) return e;
+    SpecAcceptArgs a;
+    spec_accept_args(c, c->sp_draft, rows, c->sp_gate, a);
+    a.words = c->sp_words; a.seq = c->sp_seq; a.seq_cap = c->spec_seq_cap; a.out = c->sp_out; a.out_cap = c->sp_out_cap;
+    LCHECK(fvhd_launch_spec_accept(st, &a), "lookup accept");
+    return 0;
+}
+
+int fvhd_llm_lookup_state(fvhd_llm* c, int* written, int* finished, int* steps, int* tokens)
+{
+    if (!c || !c->spec) return lfail("fvhd_llm_lookup_state: no scratch - call fvhd_llm_spec_reserve first");
+    LLM_ON_DEVICE(c);
+    int v[SPEC_WORDS] = {};
+    hipError_t he = hipDeviceSynchronize();
+    if (he == hipSuccess) he = hipMemcpy(v, c->sp_words, sizeof(v), hipMemcpyDeviceToHost);
+    if (he != hipSuccess) return lhip("fvhd_llm_lookup_state", he);
+    if (written) *written = v[SPEC_W_WRITTEN];
+    if (finished) *finished = v[SPEC_W_FINISHED];
+    if (steps) *steps = v[SPEC_W_STEPS];
+    if (tokens) *tokens = v[SPEC_W_TOKENS];
     return 0;
 }
 

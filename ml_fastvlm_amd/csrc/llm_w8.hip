@@ -17,24 +17,12 @@
 #include "fvhd_common.h"
 #include "launchers.h"      // (with llm_decode.h: the argument structs)
 #include "rope.h"
+#include "w8_layout.h"  // w8_pos, e4m3x8_to_f32
 
 namespace {
 
 typedef unsigned char u8;
 
-// byte offset, in a packed row, of the 8 codes k0 .. k0 + 7 (k0 % 8 == 0)
-FVHD_DEV int w8_pos(int k0)
-{
-    const int j = (k0 >> 5) & 3, g = (k0 >> 3) & 3;
-    return (k0 & ~127) + ((j >> 1) << 6) + (g << 4) + ((j & 1) << 3);
-}
-
-FVHD_DEV f32x8 e4m3x8_to_f32(uint32_t lo, uint32_t hi)
-{
-    const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8(lo, false), b = __builtin_amdgcn_cvt_pk_f32_fp8(lo, true);
-    const f32x2 c = __builtin_amdgcn_cvt_pk_f32_fp8(hi, false), d = __builtin_amdgcn_cvt_pk_f32_fp8(hi, true);
-    return f32x8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
-}
 // 8 codes -> the bf16 MFMA fragment: every e4m3 value is a bf16 value (4 significant bits, a narrower exponent range)
 FVHD_DEV bf16x8 e4m3x8_to_bf8(uint32_t lo, uint32_t hi) { return f32_to_bf8(e4m3x8_to_f32(lo, hi)); }
 

@@ -224,6 +224,7 @@ void fvhd_llm_destroy(fvhd_llm* c)
     if (c->emb) (void)hipFree(c->emb);
     if (c->dc) (void)hipFree(c->dc);
     if (c->beam) (void)hipFree(c->beam);
+    if (c->spec) (void)hipFree(c->spec);
     if (c->pre_kv) (void)hipFree(c->pre_kv);
     if (c->status_host) (void)hipHostFree(c->status_host);
     delete c;

@@ -20,6 +20,9 @@ bookkeeping is `ml_fastvlm_amd.beam.BeamSearchState` - all of it inside the one 
 `greedy` and `sample` also take transformers' `repetition_penalty`, `no_repeat_ngram_size`, `min_new_tokens` and `suppress_tokens`
 (`set_logits_processors`, include/fvhd.h "LLM logits processors"): one more launch inside the captured step edits the logits before the
 choice, from a token history the step keeps on the device.
+`lookup_greedy` is `greedy` for one sequence with prompt-lookup decoding (include/fvhd.h "LLM speculative verification"): a step drafts up
+to 15 tokens by n-gram matching in the prompt's ids and the generated tokens, verifies them as the rows of ONE step (`verify`) and keeps
+what the model's own argmax confirms - the same tokens in fewer steps.
 """
 from __future__ import annotations
 
@@ -89,6 +92,8 @@ class Qwen2Generator:
         self._ids = torch.zeros((self.batch,), device=self.device, dtype=torch.long)
         self._run_batch = 0
         self._processors = None                                  # what set_logits_processors last set (None = all off)
+        self._spec_rows = 0                                      # the largest row count this generator asked of spec_reserve
+        self._spec_logits = self._spec_ids = self._spec_emitted = None      # verify()'s output buffers, made on first use
 
     @classmethod
     def from_hf(cls, model, batch: int, capacity: int, prefill: Optional[Qwen2Prefill] = None, weights: str = "bf16") -> "Qwen2Generator":
@@ -173,6 +178,134 @@ class Qwen2Generator:
         with torch.cuda.device(self.device):
             _lib.check(_lib.beam_lib().fvhd_llm_beam_topk(self.pre._h, _lib.ptr(logits), _lib.ptr(beam_scores), G, K, int(keep), _lib.ptr(out_scores),
                                                           _lib.ptr(out_index), _lib.stream_ptr(self.device)), "fvhd_llm_beam_topk")
+
+    # ---- speculative verification -------------------------------------------------------------------------------------------------------
+    def _verify_refusal(self, who: str, rows: int) -> None:
+        """the Python-side refusals of a verify step, each naming its reason (the library refuses the same)"""
+        if not 2 <= int(rows) <= _lib.MAX_VERIFY_ROWS:
+            raise ValueError(f"{who}: a verify step takes 2 .. {_lib.MAX_VERIFY_ROWS} rows (the last token + 1 .. {_lib.MAX_VERIFY_ROWS - 1} drafts), got {rows}")
+        if self._processors is not None:
+            raise ValueError(f"{who}: logits processors are set (set_logits_processors) - the verify step does not maintain their token history; "
+                             "clear them with set_logits_processors()")
+
+    def spec_reserve(self, T: int, lookup_capacity: int = 0) -> None:
+        """the scratch of verify steps of up to T rows and a token buffer for `lookup_capacity` lookup ids (`fvhd_llm_spec_reserve`).  The
+        library keeps an allocation that already covers the request (the call then returns at once) and grows it otherwise, which
+        synchronises; it is the library that knows whether the scratch still exists - another generator built on the same prefill
+        context reserves the cache again and frees it - so this asks every time."""
+        self._verify_refusal("spec_reserve", T)
+        lib = _lib.lookup_lib()
+        with torch.cuda.device(self.device):
+            _lib.check(lib.fvhd_llm_spec_reserve(self.pre._h, int(T), int(lookup_capacity)), "fvhd_llm_spec_reserve")
+        self._spec_rows = max(self._spec_rows, int(T))
+        if self._spec_ids is None:                               # verify()'s small outputs, made here so that a captured verify allocates nothing
+            self._spec_ids = torch.zeros((_lib.MAX_VERIFY_ROWS,), device=self.device, dtype=torch.long)
+            self._spec_emitted = torch.zeros((1,), device=self.device, dtype=torch.int32)
+
+    @torch.no_grad()
+    def verify(self, drafts: torch.Tensor, logits: bool = True):
+        """one verify step of the ONE started sequence on `drafts` (int64 [T - 1] on the device, T <= the rows of spec_reserve): the last
+        chosen token and the drafts are the T rows of one step -> (fp32 logits [T, vocab] or None, argmax ids [T], emitted: int32 [1] on the
+        device).  ids[:emitted] are the tokens the step produced: the drafts its own argmax confirmed, then the model's next token.
+        Row t's logits have the bits of the plain step() that feeds the same token.  Greedy only.  The returned tensors are the
+        generator's buffers; host arguments are the same every step (capture-safe; the logits buffer is made by the first call with logits=True,
+        so make that call before capturing one)."""
+        if self._run_batch != 1:
+            raise ValueError(f"verify: the verify step takes ONE sequence - the started batch is {self._run_batch}" if self._run_batch else
+                             "verify: call start() first")
+        if drafts.dtype != torch.long or drafts.device != self.device or drafts.dim() != 1 or not drafts.is_contiguous():
+            raise ValueError(f"drafts must be a contiguous 1-D int64 tensor on {self.device}")
+        T = drafts.shape[0] + 1
+        self._verify_refusal("verify", T)
+        if self._spec_rows < T:
+            raise ValueError(f"verify: {T} rows exceed the rows this generator reserved with spec_reserve ({self._spec_rows or 'none'})")
+        if logits and self._spec_logits is None:
+            self._spec_logits = torch.empty((_lib.MAX_VERIFY_ROWS, self.pre.vocab), device=self.device, dtype=torch.float32)
+        lg = self._spec_logits[:T] if logits else None
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lookup_lib().fvhd_llm_verify(self.pre._h, _lib.ptr(drafts), T, _lib.ptr(lg), _lib.ptr(self._spec_ids), _lib.ptr(self._spec_emitted),
+                                                         _lib.stream_ptr(self.device)), "fvhd_llm_verify")
+        return lg, self._spec_ids[:T], self._spec_emitted
+
+    def lookup_state(self):
+        """(tokens written, finished, verify steps, tokens they emitted) of the lookup generation, after a device synchronisation"""
+        v = [C.c_int(0) for _ in range(4)]
+        _lib.check(_lib.lookup_lib().fvhd_llm_lookup_state(self.pre._h, *[C.byref(x) for x in v]), "fvhd_llm_lookup_state")
+        return v[0].value, bool(v[1].value), v[2].value, v[3].value
+
+    @torch.no_grad()
+    def lookup_greedy(self, inputs_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None,
+                      max_new_tokens: int = 256, prompt_lookup_num_tokens: int = 7, max_matching_ngram_size: int = 2,
+                      lookup_ids: Optional[torch.Tensor] = None, eos_token_id: Union[None, int, Sequence[int]] = None,
+                      pad_token_id: Optional[int] = None, graph: bool = True, poll_every: int = 16, return_stats: bool = False):
+        """`greedy` for ONE sequence with prompt-lookup decoding: every step drafts `prompt_lookup_num_tokens` tokens by n-gram matching
+        (`ml_fastvlm_amd.prompt_lookup.propose`, n <= max_matching_ngram_size) in `lookup_ids` (int64 [n] or [1, n], e.g. the prompt's
+        input_ids; negative placeholders allowed) and the tokens generated so far, verifies them in one step of
+        prompt_lookup_num_tokens + 1 rows and keeps what the model's own argmax confirms.  The tokens are `greedy`'s - [1, n], stopped
+        after the first EOS id or at max_new_tokens - in fewer steps wherever the output repeats the prompt or itself.  The draft, the
+        verify step and the accept are one captured graph (graph=True); the finished flag is polled every `poll_every` replays.
+        return_stats: also {"steps": verify steps run, "tokens": new tokens written} - the first token is the prefill's, so plain greedy
+        decoding is steps == tokens - 1 and every accepted draft is one step fewer."""
+        T = int(prompt_lookup_num_tokens) + 1
+        self._verify_refusal("lookup_greedy", T)
+        if max_new_tokens < 1:
+            raise ValueError("max_new_tokens must be >= 1")
+        if not 1 <= int(max_matching_ngram_size) <= 16:
+            raise ValueError(f"lookup_greedy: max_matching_ngram_size must be in [1, 16], got {max_matching_ngram_size}")
+        B, P = inputs_embeds.shape[:2]
+        if B != 1:
+            raise ValueError(f"lookup_greedy: prompt-lookup decoding takes ONE sequence per call (got a batch of {B})")
+        if P + max_new_tokens + T - 1 > self.capacity:
+            raise ValueError(f"prompt {P} + {max_new_tokens} new tokens + {T - 1} drafts need a cache of {P + max_new_tokens + T - 1} positions, "
+                             f"reserved {self.capacity}")
+        eos = [] if eos_token_id is None else ([int(eos_token_id)] if isinstance(eos_token_id, int) else [int(e) for e in eos_token_id])
+        if len(eos) > _lib.MAX_EOS_IDS:
+            raise ValueError(f"lookup_greedy: at most {_lib.MAX_EOS_IDS} EOS ids (got {len(eos)})")
+        look = None
+        if lookup_ids is not None:
+            look = lookup_ids.reshape(-1).to(device=self.device, dtype=torch.long).contiguous()
+        n_look = 0 if look is None else look.shape[0]
+        lib = _lib.lookup_lib()
+        self._set_greedy()
+        self.spec_reserve(T, n_look)
+        dev = self.device
+        out = torch.zeros((max_new_tokens,), device=dev, dtype=torch.long)
+        self.start(inputs_embeds, attention_mask, position_ids, logits=False)
+        eos_c = (C.c_int32 * max(1, len(eos)))(*eos)
+        with torch.cuda.device(dev):
+            _lib.check(lib.fvhd_llm_lookup_begin(self.pre._h, _lib.ptr(look), n_look, C.cast(eos_c, C.c_void_p), len(eos), int(max_new_tokens), _lib.ptr(out),
+                                                 _lib.stream_ptr(dev)), "fvhd_llm_lookup_begin")
+
+        def one_step():
+            with torch.cuda.device(dev):
+                _lib.check(lib.fvhd_llm_lookup_step(self.pre._h, T, int(max_matching_ngram_size), _lib.stream_ptr(dev)), "fvhd_llm_lookup_step")
+
+        g = None
+        if graph and max_new_tokens > 1:
+            g = torch.cuda.CUDAGraph()
+            s = torch.cuda.Stream(dev)
+            s.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(s):
+                with torch.cuda.graph(g, stream=s):
+                    one_step()
+            torch.cuda.current_stream(dev).wait_stream(s)
+            # (capturing enqueues nothing: the generation's state is what lookup_begin left)
+        written, finished, steps, tokens = self.lookup_state()
+        while not finished and written < max_new_tokens:
+            for _ in range(max(1, int(poll_every))):             # at least one token per step: at most max_new_tokens - 1 steps in all
+                if g is not None:
+                    g.replay()
+                else:
+                    one_step()
+            before = written
+            written, finished, steps, tokens = self.lookup_state()      # host sync once per poll_every steps
+            if written == before:                                # a live step emits at least one token: the error word stopped them
+                break
+        n, st = self.cache_state()
+        if st:
+            raise _lib.FvhdError(f"lookup_greedy: the steps left error word {st} (1 = past the cache's capacity, 2 = a token id out of range)")
+        res = out[:written].clone()[None]
+        return (res, {"steps": steps, "tokens": written}) if return_stats else res
 
     def cache_state(self):
         """(length, error word) after a device synchronisation; error 1 = a step ran past the capacity, 2 = a token id out of range, 3 = a

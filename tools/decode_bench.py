@@ -7,6 +7,8 @@ captured graph and called eagerly, against the stock `transformers` decode loop 
     python tools/decode_bench.py --weights fp8_e4m3 ...                         (the packed matrices as e4m3 codes + row scales)
     python tools/decode_bench.py --num-beams 4 --hidden 896 3584 --batch 1 16   (beam search: --batch prompts x K beams per step)
     python tools/decode_bench.py --processors --hidden 896 --batch 1 64         (logits processors on against off, greedy and sampled)
+    python tools/decode_bench.py --lookup --hidden 896 3584 --rows 4 8 16       (prompt-lookup decoding: the verify step at one sequence)
+    python tools/decode_bench.py --lookup --trace-steps 16 --hidden 896 --rows 8    (eager verify steps only: the program of a kernel trace)
 
 --batch takes up to 64 sequences per step (more than 16 need a library of version 503).  --repeats times the graph replay that many
 times (`graph_ms_per_token` is their median, `graph_ms_per_token_runs` all of them); --no-stock leaves the stock transformers loop (and
@@ -28,11 +30,21 @@ The addition is split by differences of whole steps: logits store = greedy with 
 off (the sampler stores its logits and chooses the same way either way); argmax from the logits = greedy on - greedy with logits_out -
 process launch.
 
+--lookup times the verify step of prompt-lookup decoding (`Qwen2Generator.verify / lookup_greedy`, csrc/llm_spec.hip) at one sequence, by
+graph replay, for --rows 4 8 16 rows per step: the plain step at B = 1 and at B = rows (the yardstick: the same GEMMs, attention over
+`rows` caches instead of one), the verify step with every draft WRONG (a fixed draft id the recorded greedy run never emits: one token
+per step) and with every draft RIGHT (drafts from the recorded greedy run: `rows` tokens per step), the whole lookup step (draft +
+verify + accept) with the recorded run as lookup ids (drafts right wherever the run's 2-grams are unique: `accepted_per_step` says how
+many were), and the draft and accept launches replayed alone.  Derived: tokens per second at full acceptance and the break-even
+acceptance per draft (t_verify / t_plain(1) - 1) / (rows - 1), t_verify = the slower of the two verify runs.  Random weights
+emit noise-like tokens: no acceptance rate on real text is claimed here.
+
 Full layer counts, random bf16 weights (`tools/ttft.py: build_llm`).  Prints ONE JSON line: per (width, batch) the ms per token of each
 path, the bytes a step must read (packed weights + the KV cache at the mean length) and their fraction of 8 TB/s."""
 from __future__ import annotations
 
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -229,6 +241,139 @@ def measure_processors(llm, pre, batch: int, prompt: int, new: int, dev) -> dict
     return res
 
 
+@torch.no_grad()
+def measure_lookup(llm, pre, rows_list, prompt: int, new: int, dev, repeats: int = 1, weights: str = "bf16", trace_steps: int = 0) -> dict:
+    from ml_fastvlm_amd import _lib
+    from ml_fastvlm_amd.qwen2_decode import Qwen2Generator
+    cfg = llm.config
+    hidden, V = cfg.hidden_size, cfg.vocab_size
+    res = {"hidden": hidden, "layers": cfg.num_hidden_layers, "vocab": V, "prompt": prompt, "new_tokens": new, "weights": weights, "rows": {}}
+    g0 = torch.Generator(device=dev).manual_seed(0)
+    emb = (0.5 * torch.randn(1, prompt, hidden, device=dev, generator=g0)).to(torch.bfloat16)
+    mask = torch.ones(1, prompt, device=dev, dtype=torch.long)
+    med = lambda v: sorted(v)[len(v) // 2]      # noqa: E731
+
+    def plain(batch):                                       # the plain step at `batch` rows, as `measure` times it
+        gen = Qwen2Generator.from_hf(llm, batch, prompt + new + 20, prefill=pre, weights=weights)
+        e, m = emb.expand(batch, -1, -1).contiguous(), mask.expand(batch, -1).contiguous()
+        gen.start(e, m, logits=False)
+        graph = _graph_of(lambda: gen.step(logits=False), dev)
+        graph.replay()
+        runs = []
+        for _ in range(max(1, repeats)):
+            gen.start(e, m, logits=False)
+            runs.append(round(_ms_per(graph.replay, new, dev), 4))
+            assert gen.cache_state() == (prompt + new, 0)
+        del gen
+        return runs
+
+    if trace_steps:                                         # a kernel trace's program: the prefill and eager verify steps (every draft wrong) at rows_list[0]
+        gen = Qwen2Generator.from_hf(llm, 1, prompt + new + 20, prefill=pre, weights=weights)
+        gen.spec_reserve(rows_list[0])
+        drafts = torch.zeros((rows_list[0] - 1,), device=dev, dtype=torch.long)
+        gen.start(emb, mask, logits=False)
+        for _ in range(trace_steps):
+            gen.verify(drafts, logits=False)
+        torch.cuda.synchronize(dev)
+        res["trace_steps"], res["trace_rows"] = trace_steps, rows_list[0]
+        return res
+    yard = {T: plain(T) for T in rows_list}
+    res["plain_ms_runs"] = plain(1)
+    res["plain_ms"] = med(res["plain_ms_runs"])
+    gen = Qwen2Generator.from_hf(llm, 1, prompt + new + 20, prefill=pre, weights=weights)      # the cache the verify steps run on: made last
+    rec = gen.greedy(emb, mask, None, max_new_tokens=new, pad_token_id=0)[0]                   # the recorded greedy run
+    wrong = next(t for t in range(V) if t not in set(rec.tolist()))
+    lib = _lib.lookup_lib()
+    for T in rows_list:
+        r = {"plain_at_B_rows_ms_runs": yard[T], "plain_at_B_rows_ms": med(yard[T])}
+        gen.spec_reserve(16, new)
+        # every draft wrong: one token per step, `new - 1` steps
+        drafts = torch.full((T - 1,), wrong, device=dev, dtype=torch.long)
+        gen.start(emb, mask, logits=False)
+        graph = _graph_of(lambda: gen.verify(drafts, logits=False), dev)
+        runs = []
+        for _ in range(max(1, repeats)):
+            gen.start(emb, mask, logits=False)
+            runs.append(round(_ms_per(graph.replay, new - 1, dev), 4))
+            assert gen.cache_state() == (prompt + new - 1, 0)
+        r["verify_all_wrong_ms_runs"], r["verify_all_wrong_ms"] = runs, med(runs)
+        # every draft right: drafts taken from the recorded run, T tokens per step.  The drafts of step k are row k of a table, copied
+        # into the fixed draft buffer by two small torch kernels inside the graph (index_select + counter); those two are replayed alone
+        # and their time is subtracted
+        nst = (new - 1) // T
+        table = torch.stack([rec[k * T + 1:(k + 1) * T] for k in range(nst)]).contiguous()
+        idx = torch.zeros(1, device=dev, dtype=torch.long)
+
+        def feed():
+            torch.index_select(table, 0, idx, out=drafts.view(1, T - 1))
+            idx.add_(1)
+
+        def right_step():
+            feed()
+            gen.verify(drafts, logits=False)
+
+        gen.start(emb, mask, logits=False)
+        graph, feed_graph = _graph_of(right_step, dev), _graph_of(feed, dev)
+        runs, feeds = [], []
+        for _ in range(max(1, repeats)):
+            idx.zero_()
+            feeds.append(_ms_per(feed_graph.replay, nst, dev))
+            gen.start(emb, mask, logits=False)
+            idx.zero_()
+            runs.append(round(_ms_per(graph.replay, nst, dev) - feeds[-1], 4))
+            assert gen.cache_state() == (prompt + nst * T, 0), "a draft from the recorded run was rejected"
+        r["verify_all_right_ms_runs"], r["verify_all_right_ms"], r["draft_feed_us"] = runs, med(runs), round(1000 * med(feeds), 1)
+        # the whole lookup step (draft + verify + accept) with the recorded run as lookup ids: drafts right wherever its 2-grams are
+        # unique.  An untimed run counts the steps; the timed run replays exactly that many, with no host poll inside the interval
+        def begin():
+            gen.start(emb, mask, logits=False)
+            _lib.check(lib.fvhd_llm_lookup_begin(gen.pre._h, _lib.ptr(rec), new, C.cast(eos, C.c_void_p), 0, new, _lib.ptr(out), _lib.stream_ptr(dev)), "begin")
+
+        out = torch.zeros((new,), device=dev, dtype=torch.long)
+        eos = (C.c_int32 * 1)()
+        begin()
+        graph = _graph_of(lambda: _lib.check(lib.fvhd_llm_lookup_step(gen.pre._h, T, 2, _lib.stream_ptr(dev)), "step"), dev)
+        while True:
+            graph.replay()
+            written, finished, steps, _tok = gen.lookup_state()
+            if finished or written >= new:
+                break
+        assert torch.equal(out, rec), "the lookup run's tokens differ from the greedy run's"
+        runs = []
+        for _ in range(max(1, repeats)):
+            begin()
+            runs.append(round(_ms_per(graph.replay, steps, dev), 4))
+            assert gen.lookup_state()[:3] == (new, True, steps) and torch.equal(out, rec)
+        r["lookup_steps"], r["accepted_per_step"] = steps, round((new - 1) / max(steps, 1) - 1, 3)
+        r["lookup_step_ms_runs"], r["lookup_step_ms"] = runs, med(runs)
+        r["tokens_per_s_at_measured_acceptance"] = round((new - 1) / (r["lookup_steps"] * r["lookup_step_ms"] * 1e-3), 1)
+        r["tokens_per_s_at_full_acceptance"] = round(T / (r["verify_all_right_ms"] * 1e-3), 1)
+        t_verify = max(r["verify_all_wrong_ms"], r["verify_all_right_ms"])
+        r["break_even_acceptance_per_draft"] = round((t_verify / res["plain_ms"] - 1) / (T - 1), 4)
+        r["verify_over_plain_at_B_rows_ms"] = round(t_verify - r["plain_at_B_rows_ms"], 4)
+        res["rows"][str(T)] = r
+    # the draft and accept launches replayed alone (the single ops on buffers of the run's sizes)
+    seq = torch.cat([rec, rec]).to(torch.int32).contiguous()
+    ln = torch.tensor([seq.numel()], device=dev, dtype=torch.int32)
+    dr = torch.zeros(16, device=dev, dtype=torch.long)
+    ids = torch.arange(16, device=dev, dtype=torch.long)
+    last, pos = torch.zeros(1, device=dev, dtype=torch.long), torch.zeros(1, device=dev, dtype=torch.long)
+    length = torch.zeros(1, device=dev, dtype=torch.int32)
+    kvalid = torch.zeros(64, device=dev, dtype=torch.uint8)
+    def alone():
+        length.zero_()
+        _lib.check(lib.fvhd_op_dec_lookup_draft(_lib.stream_ptr(dev), _lib.ptr(seq), _lib.ptr(ln), 2, 15, _lib.ptr(dr)), "draft")
+        _lib.check(lib.fvhd_op_dec_lookup_accept(_lib.stream_ptr(dev), _lib.ptr(dr), _lib.ptr(ids), 16, None, None, 0, None, 0, None, _lib.ptr(last), _lib.ptr(pos),
+                                                 _lib.ptr(length), _lib.ptr(kvalid), 64), "accept")
+
+    graph = _graph_of(alone, dev)
+    graph.replay()
+    zero = _graph_of(lambda: length.zero_(), dev)
+    res["draft_and_accept_alone_us"] = round(1000 * (_ms_per(graph.replay, 200, dev) - _ms_per(zero.replay, 200, dev)), 1)
+    del gen
+    return res
+
+
 def _graph_of(fn, dev):
     graph = torch.cuda.CUDAGraph()
     side = torch.cuda.Stream(dev)
@@ -351,8 +496,24 @@ def main():
     ap.add_argument("--trace-steps", type=int, default=0, help="run only the prefill and this many eager steps (for a kernel trace)")
     ap.add_argument("--processors", action="store_true", help="the step with all four logits processors on against off (needs a library of version 506)")
     ap.add_argument("--num-beams", type=int, default=0, help="time beam search with this many beams per prompt (--batch = prompts; needs a library of version 505)")
+    ap.add_argument("--lookup", action="store_true", help="the verify step of prompt-lookup decoding at one sequence (needs a library of version 507)")
+    ap.add_argument("--rows", type=int, nargs="+", default=[4, 8, 16], help="--lookup: rows per verify step")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
+    if a.lookup:
+        from tools.ttft import build_llm
+        from ml_fastvlm_amd import _lib
+        from ml_fastvlm_amd.qwen2_prefill import Qwen2Prefill
+        rows = []
+        for h in (a.hidden if "--hidden" in sys.argv else [896, 3584]):
+            llm = build_llm(h, dev)
+            pre = Qwen2Prefill.from_hf(llm, weights=a.weights)
+            rows.append(measure_lookup(llm, pre, a.rows, a.prompt, a.new, dev, repeats=a.repeats, weights=a.weights, trace_steps=a.trace_steps))
+            del pre, llm
+            torch.cuda.empty_cache()
+        print(json.dumps({"tool": "decode_bench", "mode": "lookup", "device": torch.cuda.get_device_name(dev),
+                          "library_version": _lib.lookup_lib().fvhd_version(), "results": rows}))
+        return
     if a.num_beams:
         from tools.ttft import build_llm
         from ml_fastvlm_amd import _lib
