@@ -59,8 +59,10 @@ typedef void* fvhd_stream_t; /* hipStream_t */
  * greedy and sampled steps compute what 504 did, bit for bit, and fvhd_llm_cache_reserve allocates what it did; nothing earlier changed.
  * 506 adds logits processors in the decode step (fvhd_llm_set_logits_processors, fvhd_op_dec_logits_process): off by default, and then
  * every launch of fvhd_llm_start / fvhd_llm_decode is what 505 enqueued, bit for bit; fvhd_llm_cache_reserve also allocates the token
- * history (4 * batch * capacity + batch * vocab / 8 bytes); nothing earlier changed. */
-#define FVHD_VERSION 507
+ * history (4 * batch * capacity + batch * vocab / 8 bytes); nothing earlier changed.  508 adds fvhd_gemm_kernel_plan, a read-only query of
+ * fvhd_op_gemm's kernel choice (the FVHD_GEMM_PLAN_* codes): the launcher switches on the same function's value, every launch and its
+ * bits are what 507 ran; nothing earlier changed. */
+#define FVHD_VERSION 508
 int fvhd_version(void);
 const char* fvhd_last_error(void);
 
@@ -273,6 +275,20 @@ int fvhd_op_gemm(fvhd_stream_t stream, const void* A, const void* Wt, const floa
 int fvhd_op_gemm_splitk_ls(fvhd_stream_t stream, const void* A, const void* Wt, const float* bias, const float* ls, const void* resid, void* out,
                            float* partial, int M, int N, int K, int splits);
 int fvhd_gemm_splitk_plan(int M, int N, int K);
+/* Which kernel fvhd_op_gemm launches for this call on the CURRENT device (version 508; pure host code, the device supplies its CU count: the
+ * thresholds between the classes are rounds of tiles per CU) - one of the codes below, or a negative value for a call fvhd_op_gemm refuses.
+ * The launcher switches on the value of the same function, so the answer cannot drift from the launch.  Every class adds the K tiles of an
+ * output element in the same order: the classes give identical bits.  For tests that have to know which kernel they compare. */
+#define FVHD_GEMM_PLAN_V1_NF4_BK64 0 /* v1: 128 x 128 tiles (ragged M and N), K tiles of 64 */
+#define FVHD_GEMM_PLAN_V1_NF4_BK32 1 /* v1: 128 x 128, K tiles of 32 (K % 64 != 0) */
+#define FVHD_GEMM_PLAN_V1_NF3_BK64 2 /* v1: 128 x 96 tiles (N % 96 == 0, N % 128 != 0), K tiles of 64 */
+#define FVHD_GEMM_PLAN_V1_NF3_BK32 3 /* v1: 128 x 96, K tiles of 32 */
+#define FVHD_GEMM_PLAN_V1S 4         /* v1s: the streaming 128 x 128 kernel, at most one tile per CU */
+#define FVHD_GEMM_PLAN_256X128 5     /* streaming 256 x 128 */
+#define FVHD_GEMM_PLAN_256X256 6     /* streaming 256 x 256 */
+#define FVHD_GEMM_PLAN_PINGPONG 7    /* ping-pong 256 x 256 (K >= 3072) */
+#define FVHD_GEMM_PLAN_128X192 8     /* v1 with ONE 128 x 192 tile per row block (N = 192, FVHD_EPI_BIAS_GELU, many rows) */
+int fvhd_gemm_kernel_plan(int M, int N, int K, int epilogue, int out_dtype);
 /* LayerNormChannel (mci.py:617-623) on NHWC rows: x,y [M,C] bf16; w,b fp32 [C]. */
 int fvhd_op_layernorm(fvhd_stream_t stream, const void* x, void* y, const float* w, const float* b, int M, int C, float eps);
 /* MHSA core (mci.py:670-679): qkv [B*N,3C] bf16 -> out [B*N,C] bf16, head_dim 32. */

@@ -18,6 +18,9 @@ W8_VERSION = 504               # the first with 8-bit (e4m3) LLM weights: fvhd_l
 BEAM_VERSION = 505             # the first with beam search: fvhd_llm_beam_reserve / _cache_gather / _beam_topk, fvhd_op_dec_beam_topk / _cache_gather (declared only when the library has them)
 PROCESSORS_VERSION = 506      # the first with logits processors in the step: fvhd_llm_set_logits_processors, fvhd_op_dec_logits_process (declared only when the library has them)
 LOOKUP_VERSION = 507          # the first with speculative verification / prompt-lookup decoding: fvhd_llm_spec_reserve / _verify / _lookup_*, fvhd_op_dec_attention_multi / _lookup_draft / _lookup_accept (declared only when the library has them)
+GEMM_PLAN_VERSION = 508       # the first with fvhd_gemm_kernel_plan, the read-only query of fvhd_op_gemm's kernel choice (declared only when the library has it)
+(GEMM_PLAN_V1_NF4_BK64, GEMM_PLAN_V1_NF4_BK32, GEMM_PLAN_V1_NF3_BK64, GEMM_PLAN_V1_NF3_BK32, GEMM_PLAN_V1S, GEMM_PLAN_256X128, GEMM_PLAN_256X256,
+ GEMM_PLAN_PINGPONG, GEMM_PLAN_128X192) = range(9)      # FVHD_GEMM_PLAN_* (include/fvhd.h)
 MAX_DECODE_BATCH = 64
 MAX_VERIFY_ROWS = 16           # rows of one verify step (include/fvhd.h)
 MAX_EOS_IDS, MAX_SUPPRESS_IDS = 16, 256      # list limits of fvhd_llm_set_logits_processors (include/fvhd.h)
@@ -155,6 +158,8 @@ def _declare(lib) -> None:
             "fvhd_op_dec_lookup_draft": (ci, [vp, vp, vp, ci, ci, vp]),
             "fvhd_op_dec_lookup_accept": (ci, [vp, vp, vp, ci, vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, ci]),
         })
+    if lib.fvhd_version() >= GEMM_PLAN_VERSION:    # an older library loads without it; gemm_plan_lib() then names the rebuild
+        sig.update({"fvhd_gemm_kernel_plan": (ci, [ci, ci, ci, ci, ci])})
     del fp, cl
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)     # AttributeError here = the .so does not export what fvhd.h declares
@@ -235,6 +240,17 @@ def lookup_lib():
     if got < LOOKUP_VERSION:
         raise FvhdError(f"{LIB_PATH} reports ABI version {got}: prompt-lookup decoding (fvhd_llm_spec_reserve, fvhd_llm_verify, "
                         f"fvhd_llm_lookup_step, ...) needs {LOOKUP_VERSION} - rebuild the library (`python -m ml_fastvlm_amd.build`)")
+    return lib
+
+
+def gemm_plan_lib():
+    """load(), for fvhd_gemm_kernel_plan: a library older than GEMM_PLAN_VERSION loads (everything else works on it) but has no such query,
+    and this says so instead of an AttributeError."""
+    lib = load()
+    got = lib.fvhd_version()
+    if got < GEMM_PLAN_VERSION:
+        raise FvhdError(f"{LIB_PATH} reports ABI version {got}: the GEMM dispatch query (fvhd_gemm_kernel_plan) needs {GEMM_PLAN_VERSION} - "
+                        "rebuild the library (`python -m ml_fastvlm_amd.build`)")
     return lib
 
 

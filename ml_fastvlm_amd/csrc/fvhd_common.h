@@ -32,7 +32,7 @@ FVHD_DEV bf16x4 f32_to_bf4(f32x4 v) { return __builtin_convertvector(v, bf16x4);
 //   of [0, 4]) under the constraint Phi(4) = 1, with C0 nudged by 3e-7 so that the fp32 Horner chain gives Q(16) = 0.125
 //   EXACTLY: Phi(+-4) = 1 / 0 bit-exactly, i.e. gelu(x) = x for x >= 4 and 0 for x <= -4 whatever the magnitude of the
 //   pre-activation (the round-1 degree-9 fit saturated at Phi(-4) = 3.2e-5: gelu(-60) = -1.9e-3).
-//   |Phi error| <= 3.3e-5 on [-4, 4] (= 1 - Phi(4): the price of the exact tails), |gelu error| <= 1.3e-4 absolute,
+//   |Phi error| <= 3.31e-5 on [-4, 4] (1 - Phi(4) = 3.2e-5: the price of the exact tails), |gelu error| <= 1.33e-4 absolute,
 //   <= 5e-5 relative for x > 0: 1/40 of the bf16 half-ulp every activation is rounded with right after.
 // 11 full-rate VALU per value (v_med3, v_mul, 7 v_fma, v_fma, v_mul); no v_rcp / v_exp (quarter rate).  The ConvFFN
 // kernels spend 14-47 % of their chunk loop on it (tools/ubench/ffn_mix.hip), hence the low degree.

@@ -1046,16 +1046,17 @@ static hipError_t dispatch_epi(hipStream_t st, const bf16* A, const bf16* Wt, co
     return hipErrorInvalidValue;
 }
 
-// A [M,K] bf16, Wt [N,K] bf16, bias/ls fp32 [N], resid bf16 [M,N] (may alias out), out [M,N] of out_dtype.
-// Requirements: K % 32 == 0, N % 16 == 0.  Non-bf16 outputs only with epi == EPI_BIAS (f16 / f32) and EPI_NONE (f32).
-// EPI_SWIGLU: out is [M, N/2].
-extern "C" int fvhd_launch_gemm(hipStream_t st, const void* A, const void* Wt, const float* bias, const float* ls,
-                                const void* resid, void* out, int M, int N, int K, int epi, int out_dtype)
+// Which kernel fvhd_launch_gemm runs for a call, as the FVHD_GEMM_PLAN_* codes of include/fvhd.h (negative: the call is refused).  The ONE place
+// the choice is made: the launcher below switches on this value and fvhd_gemm_kernel_plan returns it, so a test that names a kernel class cannot
+// drift from the dispatch.  Pure host code; the current device only supplies its CU count.  (Debug builds: the internal code kPlanAblate.)
+constexpr int kPlanAblate = 100;
+static int gemm_plan(int M, int N, int K, int epi, int out_dtype)
 {
-    if (M <= 0 || N <= 0 || K <= 0 || (K % 32) || (N % 16)) return (int)hipErrorInvalidValue;
-    const bf16* a = (const bf16*)A;
-    const bf16* w = (const bf16*)Wt;
-    const bf16* r = (const bf16*)resid;
+    if (M <= 0 || N <= 0 || K <= 0 || (K % 32) || (N % 16)) return -1;
+    // non-bf16 outputs only with EPI_BIAS (f16 / f32) and EPI_NONE (f32: the lm_head's logits)
+    if (out_dtype == FVHD_BF16 ? (epi < EPI_NONE || epi > EPI_SWIGLU)
+                               : !((epi == EPI_BIAS && (out_dtype == FVHD_F16 || out_dtype == FVHD_F32)) || (epi == EPI_NONE && out_dtype == FVHD_F32)))
+        return -1;
     // streaming kernel where it has at least two full rounds of tiles (one 8-wave workgroup per CU): measured against v1 at B = 32
     // (tools/bench_ops.py gemm, profiles/r02_gemm_v1_v2.log) fc1 272 -> 264 us, fc2 (K = 3072) 215 -> 196, stage-5 qkv 177 -> 155,
     // projector fc 68 -> 56; with 384 tiles (stage-5 proj / fc2, 1.5 rounds) v1 stays ahead.  A 4-wave variant with 128 x 64 per
@@ -1063,17 +1064,11 @@ extern "C" int fvhd_launch_gemm(hipStream_t st, const void* A, const void* Wt, c
     // g_gemm_v2 (debug build; 10 = the 128 x 128 streaming kernel v1s wherever legal, split-K partials included): 0 = v1 only, 1 = the rule below, 2 = the 256 x 128 tile wherever it is legal, 3 = the 256 x 256 tile wherever legal,
     // 4 = the ping-pong 256 x 256 kernel wherever legal, 5 = 256 x 128 / 4 waves / BK 32 / two workgroups per CU wherever legal
     // v1s: launches of at most ~one 128 x 128 tile per CU (the prefill's q|k|v projection, the tower's GEMMs at B = 1): three K tiles in flight
-    if (out_dtype == FVHD_BF16 && epi >= EPI_NONE && epi <= EPI_SWIGLU && take_gemm128s(M, N, K, (long)(M / 128) * (N / 128)))
-        return (int)dispatch_gemm128s(st, a, w, bias, ls, r, out, M, N, K, epi);
+    if (out_dtype == FVHD_BF16 && take_gemm128s(M, N, K, (long)(M / 128) * (N / 128))) return FVHD_GEMM_PLAN_V1S;
     if (g_gemm_v2 && out_dtype == FVHD_BF16 && M % 256 == 0 && N % 128 == 0 && K % 64 == 0 && K >= 128) {
         const long long t128 = (long long)(M / 256) * (N / 128), t256 = N % 256 == 0 ? (long long)(M / 256) * (N / 256) : 0;
 #ifdef FVHD_DEBUG_KNOBS
-        if ((g_gemm_v2 == 8 || g_gemm_v2 == 9) && t256 > 0 && (epi == EPI_NONE || epi == EPI_BIAS_GELU)) {     // ablations of the 256 x 256 kernel
-            if (g_gemm_v2 == 8) return (int)(epi == EPI_NONE ? launch_gemm256<EPI_NONE, FVHD_BF16, 8, 256, 64, 1>(st, a, w, bias, ls, r, out, M, N, K)
-                                                              : launch_gemm256<EPI_BIAS_GELU, FVHD_BF16, 8, 256, 64, 1>(st, a, w, bias, ls, r, out, M, N, K));
-            return (int)(epi == EPI_NONE ? launch_gemm256<EPI_NONE, FVHD_BF16, 8, 256, 64, 2>(st, a, w, bias, ls, r, out, M, N, K)
-                                         : launch_gemm256<EPI_BIAS_GELU, FVHD_BF16, 8, 256, 64, 2>(st, a, w, bias, ls, r, out, M, N, K));
-        }
+        if ((g_gemm_v2 == 8 || g_gemm_v2 == 9) && t256 > 0 && (epi == EPI_NONE || epi == EPI_BIAS_GELU)) return kPlanAblate;     // ablations of the 256 x 256 kernel
 #endif
         // measured (tools/bench_ops.py gemm, profiles/r03_gemm_tiles.log, B = 32): the 256 x 256 tile wins from N = 2304 on when it has
         // ~2 rounds of tiles - stage-3 qkv 186 -> 165 us, fc1 268 -> 242, stage-4 fc1 224 -> 204, 7B projector 239 / 267 -> 211 / 239 -
@@ -1089,21 +1084,52 @@ extern "C" int fvhd_launch_gemm(hipStream_t st, const void* A, const void* Wt, c
         const bool use128 = g_gemm_v2 == 2 || (g_gemm_v2 == 1 && ((t128 >= 2 * ncu && full_enough) || (t128 * 2 >= ncu && K >= 3072)));
         // ping-pong kernel: same tile, +0-6 % over the plain 256 x 256 kernel, the more the longer K (profiles/r03_gemm_tiles.log: stage-4 fc2
         // K = 6144 185 -> 177 us, 7B projector K = 3584 243 -> 228 us = 0.92 PF/s; K = 768 shapes tie) - taken for K >= 3072
-        if ((g_gemm_v2 == 4 && t256 > 0) || (g_gemm_v2 == 1 && K >= 3072 && t256 * 2 >= ncu))
-            return (int)dispatch_gemm_pp(st, a, w, bias, ls, r, out, M, N, K, epi);
-        if (use256) return (int)dispatch_gemm256<256>(st, a, w, bias, ls, r, out, M, N, K, epi);
-        if (use128) return (int)dispatch_gemm256<128>(st, a, w, bias, ls, r, out, M, N, K, epi);
+        if ((g_gemm_v2 == 4 && t256 > 0) || (g_gemm_v2 == 1 && K >= 3072 && t256 * 2 >= ncu)) return FVHD_GEMM_PLAN_PINGPONG;
+        if (use256) return FVHD_GEMM_PLAN_256X256;
+        if (use128) return FVHD_GEMM_PLAN_256X128;
     }
     const bool nf3 = (N % 128 != 0) && (N % 96 == 0);
     const bool bk64 = (K % 64 == 0);
-    hipError_t e;
     // N = 192 with many row tiles (PatchEmbed's 1x1 + GELU after stage 0: M = B * 16384): ONE 128 x 192 tile per row block instead of two
     // 128 x 96 tiles - A is read once and the tile count halves; same K order per output element (identical bits).  Round 6, FVHD_GEMM_NF6=0: off.
     if (g_gemm_nf6 && nf3 && bk64 && N % 192 == 0 && epi == EPI_BIAS_GELU && out_dtype == FVHD_BF16 && (long long)((M + 127) / 128) * (N / 192) >= 4ll * cu_count())
-        return (int)launch_gemm<6, 64, EPI_BIAS_GELU, FVHD_BF16>(st, a, w, bias, ls, r, out, M, N, K);
-    if (nf3) e = bk64 ? dispatch_epi<3, 64>(st, a, w, bias, ls, r, out, M, N, K, epi, out_dtype)
-                      : dispatch_epi<3, 32>(st, a, w, bias, ls, r, out, M, N, K, epi, out_dtype);
-    else     e = bk64 ? dispatch_epi<4, 64>(st, a, w, bias, ls, r, out, M, N, K, epi, out_dtype)
-                      : dispatch_epi<4, 32>(st, a, w, bias, ls, r, out, M, N, K, epi, out_dtype);
-    return (int)e;
+        return FVHD_GEMM_PLAN_128X192;
+    if (nf3) return bk64 ? FVHD_GEMM_PLAN_V1_NF3_BK64 : FVHD_GEMM_PLAN_V1_NF3_BK32;
+    return bk64 ? FVHD_GEMM_PLAN_V1_NF4_BK64 : FVHD_GEMM_PLAN_V1_NF4_BK32;
+}
+
+extern "C" int fvhd_gemm_kernel_plan(int M, int N, int K, int epilogue, int out_dtype)
+{
+    const int p = gemm_plan(M, N, K, epilogue, out_dtype);
+    return p == kPlanAblate ? -1 : p;
+}
+
+// A [M,K] bf16, Wt [N,K] bf16, bias/ls fp32 [N], resid bf16 [M,N] (may alias out), out [M,N] of out_dtype.
+// Requirements: K % 32 == 0, N % 16 == 0.  Non-bf16 outputs only with epi == EPI_BIAS (f16 / f32) and EPI_NONE (f32).
+// EPI_SWIGLU: out is [M, N/2].  The kernel is gemm_plan's choice.
+extern "C" int fvhd_launch_gemm(hipStream_t st, const void* A, const void* Wt, const float* bias, const float* ls,
+                                const void* resid, void* out, int M, int N, int K, int epi, int out_dtype)
+{
+    const bf16* a = (const bf16*)A;
+    const bf16* w = (const bf16*)Wt;
+    const bf16* r = (const bf16*)resid;
+    switch (gemm_plan(M, N, K, epi, out_dtype)) {
+    case FVHD_GEMM_PLAN_V1S: return (int)dispatch_gemm128s(st, a, w, bias, ls, r, out, M, N, K, epi);
+    case FVHD_GEMM_PLAN_PINGPONG: return (int)dispatch_gemm_pp(st, a, w, bias, ls, r, out, M, N, K, epi);
+    case FVHD_GEMM_PLAN_256X256: return (int)dispatch_gemm256<256>(st, a, w, bias, ls, r, out, M, N, K, epi);
+    case FVHD_GEMM_PLAN_256X128: return (int)dispatch_gemm256<128>(st, a, w, bias, ls, r, out, M, N, K, epi);
+    case FVHD_GEMM_PLAN_128X192: return (int)launch_gemm<6, 64, EPI_BIAS_GELU, FVHD_BF16>(st, a, w, bias, ls, r, out, M, N, K);
+    case FVHD_GEMM_PLAN_V1_NF3_BK64: return (int)dispatch_epi<3, 64>(st, a, w, bias, ls, r, out, M, N, K, epi, out_dtype);
+    case FVHD_GEMM_PLAN_V1_NF3_BK32: return (int)dispatch_epi<3, 32>(st, a, w, bias, ls, r, out, M, N, K, epi, out_dtype);
+    case FVHD_GEMM_PLAN_V1_NF4_BK64: return (int)dispatch_epi<4, 64>(st, a, w, bias, ls, r, out, M, N, K, epi, out_dtype);
+    case FVHD_GEMM_PLAN_V1_NF4_BK32: return (int)dispatch_epi<4, 32>(st, a, w, bias, ls, r, out, M, N, K, epi, out_dtype);
+#ifdef FVHD_DEBUG_KNOBS
+    case kPlanAblate:
+        if (g_gemm_v2 == 8) return (int)(epi == EPI_NONE ? launch_gemm256<EPI_NONE, FVHD_BF16, 8, 256, 64, 1>(st, a, w, bias, ls, r, out, M, N, K)
+                                                          : launch_gemm256<EPI_BIAS_GELU, FVHD_BF16, 8, 256, 64, 1>(st, a, w, bias, ls, r, out, M, N, K));
+        return (int)(epi == EPI_NONE ? launch_gemm256<EPI_NONE, FVHD_BF16, 8, 256, 64, 2>(st, a, w, bias, ls, r, out, M, N, K)
+                                     : launch_gemm256<EPI_BIAS_GELU, FVHD_BF16, 8, 256, 64, 2>(st, a, w, bias, ls, r, out, M, N, K));
+#endif
+    }
+    return (int)hipErrorInvalidValue;
 }

@@ -122,3 +122,29 @@ def test_split_k_plan_is_host_logic(lib):
         assert got == sp, ((M, N, K), got, sp)
         if got > 1:
             assert -(-M // 128) * (N // 128) * got <= 512 and K % (64 * got) == 0 and K // got >= 384
+
+
+def test_gemm_kernel_plan_is_host_logic(lib):
+    """fvhd_gemm_kernel_plan (version 508, pure host code): the FVHD_GEMM_PLAN_* codes of the header are the stub's, and the query names
+    the kernel class of the shapes the dispatch comments name - on a machine without a device the rules are those of 256 CUs."""
+    from ml_fastvlm_amd import _lib
+    src = open(os.path.join(ROOT, "include", "fvhd.h")).read()
+    codes = {n: int(v) for n, v in re.findall(r"#define\s+FVHD_(GEMM_PLAN_[A-Z0-9_]+)\s+(\d+)", src)}
+    assert len(codes) == 9 and sorted(codes.values()) == list(range(9))
+    assert all(getattr(_lib, n) == v for n, v in codes.items())
+    assert _lib.GEMM_PLAN_VERSION == 508 <= lib.fvhd_version() and _lib.gemm_plan_lib() is lib
+    if torch.cuda.is_available() and torch.cuda.get_device_properties(0).multi_processor_count != 256:
+        return
+    want = {(1, 96, 96, 1, 2): _lib.GEMM_PLAN_V1_NF3_BK32, (256, 384, 96, 2, 2): _lib.GEMM_PLAN_V1_NF4_BK32, (513, 192, 384, 3, 2): _lib.GEMM_PLAN_V1_NF3_BK64,
+            (257, 1152, 64, 0, 2): _lib.GEMM_PLAN_V1_NF4_BK64, (131112, 192, 192, 2, 2): _lib.GEMM_PLAN_128X192, (131112, 192, 192, 1, 2): _lib.GEMM_PLAN_V1_NF3_BK64,
+            (128, 128, 128, 2, 2): _lib.GEMM_PLAN_V1S, (32768, 128, 128, 0, 2): _lib.GEMM_PLAN_V1S, (32896, 128, 128, 0, 2): _lib.GEMM_PLAN_V1_NF4_BK64,
+            (8192, 2048, 128, 2, 2): _lib.GEMM_PLAN_256X128, (7936, 2048, 128, 2, 2): _lib.GEMM_PLAN_V1_NF4_BK64, (11008, 384, 3072, 0, 2): _lib.GEMM_PLAN_256X128,
+            (12800, 2304, 128, 0, 2): _lib.GEMM_PLAN_256X256, (12544, 2304, 128, 0, 2): _lib.GEMM_PLAN_256X128,
+            (8192, 1024, 3072, 3, 2): _lib.GEMM_PLAN_PINGPONG, (8192, 1024, 3136, 0, 2): _lib.GEMM_PLAN_PINGPONG, (8192, 1024, 3008, 0, 2): _lib.GEMM_PLAN_V1_NF4_BK64,
+            (200, 384, 1536, 1, 0): _lib.GEMM_PLAN_V1_NF4_BK64, (200, 384, 1536, 1, 1): _lib.GEMM_PLAN_V1_NF4_BK64, (8, 1024, 896, 0, 0): _lib.GEMM_PLAN_V1_NF4_BK64,
+            # refused: K % 32, N % 16, empty, an epilogue that does not exist, output types an epilogue does not have
+            (8, 8, 40, 0, 2): -1, (8, 16, 40, 0, 2): -1, (0, 16, 32, 0, 2): -1, (8, 16, 32, 6, 2): -1, (8, 16, 32, -1, 2): -1, (200, 384, 1536, 3, 0): -1,
+            (200, 384, 1536, 0, 1): -1, (200, 384, 1536, 1, 3): -1}
+    for args, plan in want.items():
+        got = lib.fvhd_gemm_kernel_plan(*args)
+        assert (got < 0) if plan < 0 else got == plan, (args, got, plan)
