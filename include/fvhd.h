@@ -61,8 +61,11 @@ typedef void* fvhd_stream_t; /* hipStream_t */
  * every launch of fvhd_llm_start / fvhd_llm_decode is what 505 enqueued, bit for bit; fvhd_llm_cache_reserve also allocates the token
  * history (4 * batch * capacity + batch * vocab / 8 bytes); nothing earlier changed.  508 adds fvhd_gemm_kernel_plan, a read-only query of
  * fvhd_op_gemm's kernel choice (the FVHD_GEMM_PLAN_* codes): the launcher switches on the same function's value, every launch and its
- * bits are what 507 ran; nothing earlier changed. */
-#define FVHD_VERSION 508
+ * bits are what 507 ran; nothing earlier changed.  509 adds the extension of a started KV cache by a chunk of tokens and its rewind
+ * (fvhd_llm_extend, fvhd_llm_cache_rewind, fvhd_op_attention_extend / _cache_append / _extend_positions / _cache_rewind; error word 4):
+ * fvhd_llm_prefill, fvhd_llm_start, fvhd_llm_decode, fvhd_llm_verify and the lookup step enqueue what 508 did, launch for launch and bit for
+ * bit; the prefill workspace grows by 8 bytes per row (the positions of a chunk); nothing earlier changed. */
+#define FVHD_VERSION 509
 int fvhd_version(void);
 const char* fvhd_last_error(void);
 
@@ -474,7 +477,7 @@ int fvhd_llm_start(fvhd_llm* ctx, const void* embeds, int dtype, const uint8_t* 
  * next fvhd_llm_decode reports as an error (fvhd_llm_cache_state reads it at once).  Capture-safe after fvhd_llm_start. */
 int fvhd_llm_decode(fvhd_llm* ctx, const int64_t* token_ids, float* logits_out, int64_t* next_ids_out, fvhd_stream_t stream);
 /* synchronises the device, then: the cache length and the error word (0 = fine, 1 = past capacity, 2 = token id out of range, 3 = a
- * cache reorder's row index out of range) */
+ * cache reorder's row index out of range, 4 = a cache rewind's keep length out of range) */
 int fvhd_llm_cache_state(fvhd_llm* ctx, int* length, int* status);
 
 /* ---- LLM sampling: temperature / top-k / top-p on the device ------------------------------------------------------------------------
@@ -706,6 +709,57 @@ int fvhd_op_dec_lookup_draft(fvhd_stream_t stream, const int32_t* tokens, const 
 int fvhd_op_dec_lookup_accept(fvhd_stream_t stream, const int64_t* draft, const int64_t* ids, int T, int32_t* words, int32_t* tokens, int tokens_capacity,
                               int64_t* out, int out_capacity, int32_t* emitted, int64_t* last_id, int64_t* position, int* length, uint8_t* key_valid,
                               int capacity);
+
+/* ---- LLM extend: a chunk of T tokens per row onto a started KV cache, and the rewind (version 509) -------------------------------------------
+ * fvhd_llm_start prefills an EMPTY cache and fvhd_llm_decode adds one token per row.  fvhd_llm_extend adds a chunk of T >= 1 embedded tokens
+ * to every row of a cache that already holds `length` slots: the next turn of a dialogue, one question per row behind a shared prefix
+ * (fvhd_llm_cache_gather copies row 0 into N rows first), or the next piece of a prompt longer than one prefill.  What transformers does when
+ * forward() is called with past_key_values and T new positions.
+ * The decoder stack IS the prefill's (one internal function serves both entry points): the same GEMM launches, split-K choices, fused norms and
+ * e4m3 dequantise-into-scratch path on the B * T chunk rows.  Three things differ: the rotary embedding runs without cache pointers; where the
+ * prefill launches its attention, one launch per layer copies the chunk's rotated k heads and v heads into slots [length, length + T) of the
+ * layer's strided cache (16-byte vector copies; the first layer's launch also writes the mask bytes) and one launch computes causal
+ * grouped-query attention of the T chunk queries over slots [0, length + T) - key j is visible to chunk query t of row b iff j <= length + t
+ * and the cache's key_valid[b][j]; and without position ids a small launch writes pos[b][t] = next_position[b] + (valid chunk tokens of row b
+ * before t), transformers' cumsum(mask) - 1 continued from the row's next position.  `length` is read from the device word by every kernel:
+ * the host arguments do not depend on it, and the call composes with replayed decode graphs without a synchronisation.
+ * The attention kernel is the prefill's with its keys in the cache: S^T = K . Q^T on the 16x16x32 bf16 MFMA, P in registers, the denominator
+ * from a ones fragment, 64-key tiles ALIGNED TO SLOT 0 double-buffered in LDS, 128 queries per workgroup; a query row with no visible key is
+ * written as zeros.  With length = 0 it performs the prefill kernel's operations in the same order: fvhd_op_attention_extend(P = 0) has the
+ * bits of fvhd_op_attention_causal.  A tiny chunk on a long past runs on ceil(T / 128) * n_heads * batch workgroups that each walk the whole
+ * past: the keys are not split across workgroups.
+ * length + T > capacity: the first append writes nothing and sets the sticky error word to 1 (the host does not know `length`); every later
+ * launch of the call that writes cache state, the chosen ids included, then does nothing, and the next call reports the error. */
+/* chunk embeds [batch == the started batch][T][hidden], key_valid uint8 [batch][T] or NULL, position_ids int64 [batch][T] or NULL (continue
+ * every row from its next position over the valid chunk tokens) -> K / V of the chunk in slots [len, len + T), mask, len += T, next
+ * positions (position of the chunk's last token + 1); logits_out (NULL or fp32 [batch, vocab]) of the chunk's LAST position and next_ids_out
+ * through the same argmax / sampler launches as fvhd_llm_start (Philox n = the new length).
+ * Capture-safe under fvhd_llm_prefill's rule (the workspace reserved for (batch, T): fvhd_llm_reserve).  Refused, each with a message: no
+ * started sequence, T < 1, T > capacity, head_dim other than 64 / 128, a pending error word, logits processors on (their token history has
+ * no ids for embedded chunks - the stance of the verify step).  Ends a lookup generation (fvhd_llm_lookup_begin again). */
+int fvhd_llm_extend(fvhd_llm* ctx, const void* embeds, int dtype, const uint8_t* key_valid, const int64_t* position_ids, int T, float* logits_out,
+                    int64_t* next_ids_out, fvhd_stream_t stream);
+/* keep_dev: int32 [started batch] on the device.  For every row the slots [keep[b], length) leave the sequence: the row's next position
+ * drops by the number of VALID slots among them and their mask bytes are cleared; then length = max_b keep[b].  K / V bytes are not touched
+ * (later appends overwrite them).  A keep[b] outside [0, length] changes nothing and sets the sticky error word to 4.  One launch,
+ * capture-safe.  Refused with logits processors on (their history is not rewound).  After a rewind the ids "the previous step chose" are
+ * stale: the next call must be fvhd_llm_extend, or fvhd_llm_decode with explicit token_ids. */
+int fvhd_llm_cache_rewind(fvhd_llm* ctx, const int32_t* keep_dev, fvhd_stream_t stream);
+/* the kernels on their own (tests), on plain device pointers.
+ * fvhd_op_attention_extend: qkv [B*T, (n_heads + 2 n_kv_heads) * head_dim] bf16 (the chunk's packed rows, rope applied; the q heads are
+ * read), k_cache / v_cache bf16 [>= B][n_kv_heads][capacity][head_dim] with the chunk already in slots [*past_len, *past_len + T), key_valid
+ * uint8 [>= B][capacity] or NULL -> out [B*T, n_heads * head_dim] bf16; head_dim 64 / 128; *past_len + T > capacity: nothing is written.
+ * fvhd_op_cache_append: one layer - the k and v heads of the rows -> slots *past_len + t; key_valid (NULL: not written) [>= B][capacity] gets
+ * chunk_valid [B][T] (NULL: 1) at the same slots; *past_len + T > capacity: nothing is written and *status = 1; nothing while *status != 0.
+ * fvhd_op_extend_positions: pos_out int64 [B][T] from next_positions int64 [B] and chunk_valid [B][T] or NULL.
+ * fvhd_op_cache_rewind: fvhd_llm_cache_rewind on key_valid [rows][capacity], positions int64 [rows], *length, *status. */
+int fvhd_op_attention_extend(fvhd_stream_t stream, const void* qkv, const void* k_cache, const void* v_cache, const uint8_t* key_valid, void* out, int B,
+                             int T, int n_heads, int n_kv_heads, int head_dim, int capacity, const int* past_len);
+int fvhd_op_cache_append(fvhd_stream_t stream, const void* qkv, void* k_cache, void* v_cache, uint8_t* key_valid, const uint8_t* chunk_valid, int B, int T,
+                         int n_heads, int n_kv_heads, int head_dim, int capacity, const int* past_len, int* status);
+int fvhd_op_extend_positions(fvhd_stream_t stream, const int64_t* next_positions, const uint8_t* chunk_valid, int64_t* pos_out, int B, int T);
+int fvhd_op_cache_rewind(fvhd_stream_t stream, const int32_t* keep, int rows, uint8_t* key_valid, int64_t* positions, int capacity, int* length,
+                         int* status);
 
 #ifdef __cplusplus
 }

@@ -19,6 +19,7 @@ BEAM_VERSION = 505             # the first with beam search: fvhd_llm_beam_reser
 PROCESSORS_VERSION = 506      # the first with logits processors in the step: fvhd_llm_set_logits_processors, fvhd_op_dec_logits_process (declared only when the library has them)
 LOOKUP_VERSION = 507          # the first with speculative verification / prompt-lookup decoding: fvhd_llm_spec_reserve / _verify / _lookup_*, fvhd_op_dec_attention_multi / _lookup_draft / _lookup_accept (declared only when the library has them)
 GEMM_PLAN_VERSION = 508       # the first with fvhd_gemm_kernel_plan, the read-only query of fvhd_op_gemm's kernel choice (declared only when the library has it)
+EXTEND_VERSION = 509          # the first with fvhd_llm_extend / fvhd_llm_cache_rewind, fvhd_op_attention_extend / _cache_append / _extend_positions / _cache_rewind (declared only when the library has them)
 (GEMM_PLAN_V1_NF4_BK64, GEMM_PLAN_V1_NF4_BK32, GEMM_PLAN_V1_NF3_BK64, GEMM_PLAN_V1_NF3_BK32, GEMM_PLAN_V1S, GEMM_PLAN_256X128, GEMM_PLAN_256X256,
  GEMM_PLAN_PINGPONG, GEMM_PLAN_128X192) = range(9)      # FVHD_GEMM_PLAN_* (include/fvhd.h)
 MAX_DECODE_BATCH = 64
@@ -160,6 +161,15 @@ def _declare(lib) -> None:
         })
     if lib.fvhd_version() >= GEMM_PLAN_VERSION:    # an older library loads without it; gemm_plan_lib() then names the rebuild
         sig.update({"fvhd_gemm_kernel_plan": (ci, [ci, ci, ci, ci, ci])})
+    if lib.fvhd_version() >= EXTEND_VERSION:       # an older library loads without them; extend_lib() then names the rebuild
+        sig.update({
+            "fvhd_llm_extend": (ci, [vp, vp, ci, vp, vp, ci, vp, vp, vp]),
+            "fvhd_llm_cache_rewind": (ci, [vp, vp, vp]),
+            "fvhd_op_attention_extend": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]),
+            "fvhd_op_cache_append": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]),
+            "fvhd_op_extend_positions": (ci, [vp, vp, vp, vp, ci, ci]),
+            "fvhd_op_cache_rewind": (ci, [vp, vp, ci, vp, vp, ci, vp, vp]),
+        })
     del fp, cl
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)     # AttributeError here = the .so does not export what fvhd.h declares
@@ -251,6 +261,17 @@ def gemm_plan_lib():
     if got < GEMM_PLAN_VERSION:
         raise FvhdError(f"{LIB_PATH} reports ABI version {got}: the GEMM dispatch query (fvhd_gemm_kernel_plan) needs {GEMM_PLAN_VERSION} - "
                         "rebuild the library (`python -m ml_fastvlm_amd.build`)")
+    return lib
+
+
+def extend_lib():
+    """load(), for extending / rewinding a started KV cache: a library older than EXTEND_VERSION loads (every generation that begins at an
+    empty cache works on it) but has none of the entry points, and this says so instead of an AttributeError."""
+    lib = load()
+    got = lib.fvhd_version()
+    if got < EXTEND_VERSION:
+        raise FvhdError(f"{LIB_PATH} reports ABI version {got}: extending a started cache (fvhd_llm_extend, fvhd_llm_cache_rewind, "
+                        f"fvhd_op_attention_extend, ...) needs {EXTEND_VERSION} - rebuild the library (`python -m ml_fastvlm_amd.build`)")
     return lib
 
 

@@ -16,7 +16,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 BUILD = os.path.join(CSRC, "build")
 LIB = os.path.join(PKG, "libfvhd.so")
-SOURCES = ["dwconv.hip", "dwconv_mfma.hip", "dwconv_fused.hip", "dwconv_down.hip", "gemm.hip", "attention.hip", "stem_head.hip", "ffn_fused.hip", "splice.hip", "preprocess.hip", "llm.hip", "llm_decode.hip", "llm_w8.hip", "llm_sample.hip", "llm_beam.hip", "llm_logits.hip", "llm_spec.hip", "llm_weights.hip", "llm_prefill.hip", "llm_step.hip", "llm_ops.hip", "fvhd_api.hip"]
+SOURCES = ["dwconv.hip", "dwconv_mfma.hip", "dwconv_fused.hip", "dwconv_down.hip", "gemm.hip", "attention.hip", "stem_head.hip", "ffn_fused.hip", "splice.hip", "preprocess.hip", "llm.hip", "llm_extend.hip", "llm_decode.hip", "llm_w8.hip", "llm_sample.hip", "llm_beam.hip", "llm_logits.hip", "llm_spec.hip", "llm_weights.hip", "llm_prefill.hip", "llm_step.hip", "llm_ops.hip", "fvhd_api.hip"]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
          "-ffp-contract=fast", "-fno-gpu-rdc"]
@@ -38,7 +38,7 @@ NOPK = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 # (profiles/r03_vgpr_form_ab.log).  Not for ffn_fused.hip (C = 384 needs all 512 registers) nor gemm.hip (neutral).
 VGPR_FORM = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
 EXTRA_FLAGS = {"ffn_fused.hip": ["-fno-slp-vectorize", "-mllvm", "-pragma-unroll-threshold=200000"] + NOPK,
-               "attention.hip": NOPK + VGPR_FORM, "llm.hip": NOPK + VGPR_FORM, "stem_head.hip": VGPR_FORM,
+               "attention.hip": NOPK + VGPR_FORM, "llm.hip": NOPK + VGPR_FORM, "llm_extend.hip": NOPK + VGPR_FORM, "stem_head.hip": VGPR_FORM,
                # dwconv_mfma.hip: 7 x 84 hand-placed MFMA slots, every register-array index compile-time (768 B/lane of scratch otherwise)
                "dwconv_mfma.hip": ["-mllvm", "-pragma-unroll-threshold=200000"],
                # dwconv_fused.hip: the same row loops (3 x 60 producer slots, 7 x 84 consumer slots)

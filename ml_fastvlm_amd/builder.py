@@ -366,6 +366,149 @@ def _generate_on_library(model, input_ids, images, image_sizes, attention_mask, 
                       pad_token_id=pad_token_id, **sampling, **processors)
 
 
+# ---- multi-turn generation on one KV cache ------------------------------------------------------------------------------------------------
+def session_chunk(pending, input_ids, attention_mask=None, pad_token_id: int = 0):
+    """The chunk of a later turn: row b = [left padding | pending_b | the row's new ids] -> (ids int64 [B, L], mask int64 [B, L]), L = 1 + the
+    longest row.  pending: int64 [B], the token every row chose last and never fed (it is not in the cache yet); input_ids [B, n] with
+    attention_mask [B, n] or None (1 = a real token; a row's real tokens may sit anywhere, their order is kept)."""
+    B, n = input_ids.shape
+    if tuple(pending.shape) != (B,):
+        raise ValueError(f"this turn has {B} rows, the session holds {pending.shape[0]} (one row of new ids per started sequence)")
+    keep = torch.ones_like(input_ids, dtype=torch.bool) if attention_mask is None else attention_mask.to(input_ids.device) != 0
+    if tuple(keep.shape) != (B, n):
+        raise ValueError(f"attention_mask must be [B, n] = {(B, n)}, got {tuple(keep.shape)}")
+    counts = keep.sum(1)
+    L = int(counts.max()) + 1
+    ids = torch.full((B, L), int(pad_token_id), dtype=torch.long, device=input_ids.device)
+    mask = torch.zeros((B, L), dtype=torch.long, device=input_ids.device)
+    for b in range(B):
+        c = int(counts[b])
+        ids[b, L - c - 1] = pending[b]
+        ids[b, L - c:] = input_ids[b][keep[b]]
+        mask[b, L - c - 1:] = 1
+    return ids, mask
+
+
+def session_keep(length_before_decode: int, tokens, eos_token_id=None):
+    """After a turn that returned `tokens` [B, n]: row b produced n_b tokens, up to and including its first EOS (n when it has none).  Its
+    first n_b - 1 were fed to decode steps and belong in the cache; the last one is PENDING - chosen, never fed.  -> (keep: the cache slots
+    every row keeps, length_before_decode + n_b - 1, as a list; pending int64 [B]).  Rewinding to `keep` drops the pad tokens that the
+    run fed to finished rows and the steps that ran past the end between two polls."""
+    eos = [] if eos_token_id is None else ([int(eos_token_id)] if isinstance(eos_token_id, int) else [int(e) for e in eos_token_id])
+    tokens = tokens.cpu()
+    B, n = tokens.shape
+    keep, pending = [], []
+    for b in range(B):
+        row = tokens[b].tolist()
+        n_b = next((i + 1 for i, t in enumerate(row) if t in eos), n)
+        keep.append(int(length_before_decode) + n_b - 1)
+        pending.append(row[n_b - 1])
+    return keep, torch.tensor(pending, dtype=torch.long)
+
+
+class GenerationSession:
+    """Multi-turn generation of a (Llava)Qwen2ForCausalLM on ONE KV cache: the first `generate` is `ml_fastvlm_amd.generate` (splice or
+    embedding, prefill, decode); every later one embeds only the turn's own tokens, EXTENDS the cache by them (`Qwen2Generator.extend`) and
+    decodes on - the system prompt, the visual tokens and the earlier turns are not prefilled again.  No tokenizer and no conversation
+    template: the caller passes the ids of each turn (everything the template puts between the previous answer and the next one).
+
+        s = GenerationSession(model, batch=1, capacity=4096)
+        a1 = s.generate(ids_turn1, images=img, image_sizes=sizes, max_new_tokens=256, eos_token_id=eos)
+        a2 = s.generate(ids_turn2, max_new_tokens=256, eos_token_id=eos)          # ids_turn2: the new tokens only
+
+    Bookkeeping per row: the last token a turn produced (its EOS, or its last token at max_new_tokens) was chosen but never fed - it is
+    `pending` and opens the row's next chunk; after every turn the cache is rewound (`Qwen2Generator.rewind`) to the tokens each row
+    really holds (`session_keep`).  `fork(n)` copies the one started row into n rows (one image, n questions).  The session uses the
+    model's `generator_context`: a `generate` / `beam_generate` call on the same model in between replaces the cache, and the session's next
+    turn raises."""
+
+    def __init__(self, model, batch: int = 1, capacity: int = 2048, weights=None):
+        self.model, self.batch, self.capacity, self.weights = model, int(batch), int(capacity), weights
+        self.gen = None
+        self._pending = None                                     # int64 [rows] on the host
+        self.reset()
+
+    def reset(self) -> None:
+        """forget the dialogue: the next generate() starts at an empty cache"""
+        self._pending = None
+
+    @property
+    def rows(self) -> int:
+        return 0 if self._pending is None else int(self._pending.shape[0])
+
+    @property
+    def length(self) -> int:
+        """cache slots in use (the longest row; shorter rows have masked slots below it)"""
+        return 0 if self._pending is None else self.gen.length()
+
+    def _generator(self):
+        gen = generator_context(self.model, self.batch, self.capacity, self.weights)
+        if self._pending is not None and (gen is not self.gen or getattr(gen, "_session", None) is not self):
+            raise RuntimeError("GenerationSession: the model's cache was started again or rebuilt since this session's last turn (another generate "
+                               "call or session, new weights or a larger cache) - the cached dialogue is gone; reset() and start again")
+        self.gen = gen
+        return gen
+
+    def fork(self, n: int) -> None:
+        """the ONE started row -> n rows with the same cache content, next position and pending token (`Qwen2Generator.cache_gather`):
+        one image, n questions - give every row its own ids in the next generate()"""
+        if self.rows != 1:
+            raise ValueError(f"fork: needs a session with ONE started row (it has {self.rows})")
+        if not 1 <= int(n) <= self.batch:
+            raise ValueError(f"fork: {n} rows exceed the session's batch {self.batch}")
+        gen = self._generator()
+        gen.beam_reserve()
+        gen.cache_gather(torch.zeros((int(n),), device=gen.device, dtype=torch.long), 1)
+        self._pending = self._pending.repeat(int(n))
+
+    @torch.no_grad()
+    def generate(self, input_ids, images=None, image_sizes=None, attention_mask=None, max_new_tokens: int = 256, eos_token_id=None,
+                 pad_token_id=None, do_sample: bool = False, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0):
+        """-> the new tokens of this turn [B, n] (`Qwen2Generator.greedy` / `.sample`'s return contract).  First call: `input_ids` is the
+        whole prompt (with image placeholders when `images` is given).  Later calls: the turn's NEW ids [B, n] only, B = the session's
+        rows; attention_mask marks the real tokens of rows of different lengths.  Images in a later turn need B = 1 or rows whose
+        spliced lengths are equal (the splice pads to the right, the cache extends to the left)."""
+        model = self.model
+        lm_w = model.lm_head.weight
+        if lm_w.device.type != "cuda" or lm_w.dtype != torch.bfloat16:
+            raise ValueError(f"GenerationSession.generate: needs a bf16 model on a HIP device (got {lm_w.dtype} on {lm_w.device}); "
+                             "the decode kernels compute in bf16")
+        gc = getattr(model, "generation_config", None)
+        if eos_token_id is None:
+            eos_token_id = getattr(gc, "eos_token_id", None)
+        if pad_token_id is None:
+            pad_token_id = getattr(gc, "pad_token_id", None)
+        first = self._pending is None
+        position_ids = None
+        if first:
+            if input_ids.shape[0] > self.batch:
+                raise ValueError(f"GenerationSession.generate: {input_ids.shape[0]} rows exceed the session's batch {self.batch}")
+            ids, mask = input_ids, attention_mask
+        else:
+            ids, mask = session_chunk(self._pending.to(input_ids.device), input_ids, attention_mask, 0 if pad_token_id is None else int(pad_token_id))
+        if images is not None:
+            (_, position_ids, mask, _, embeds, _) = model.prepare_inputs_labels_for_multimodal(ids, None, mask, None, None, images, image_sizes=image_sizes)
+            if not first:
+                if embeds.shape[0] > 1 and mask is not None and not bool((mask != 0).all()):
+                    raise ValueError("GenerationSession.generate: the spliced chunk of this turn came back padded - images in a later turn need "
+                                     "B = 1 or rows of equal spliced length")
+                position_ids, mask = None, None                  # the chunk continues every row's own positions
+        else:
+            embeds = model.get_input_embeddings()(ids.to(lm_w.device))
+        gen = self._generator()
+        T = embeds.shape[1]
+        before = 0 if first else gen.length()
+        kw = dict(max_new_tokens=max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id, continue_cache=not first)
+        if do_sample:
+            tokens = gen.sample(embeds, mask, position_ids, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, **kw)
+        else:
+            tokens = gen.greedy(embeds, mask, position_ids, **kw)
+        keep, self._pending = session_keep(before + T, tokens, eos_token_id)
+        gen.rewind(keep)
+        gen._session = self                                      # start() clears it: whoever starts the cache again ends this dialogue
+        return tokens
+
+
 # GenerationConfig fields whose value (beside None) means "this processor / mode is off"; any other value is a setting the library does
 # not implement, and `_make_library_generate` leaves the call to the reference's generate
 _OFF = {

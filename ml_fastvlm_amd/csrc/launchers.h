@@ -61,6 +61,14 @@ int fvhd_launch_splitk_bias_rope(hipStream_t st, const float* partial, int split
 int fvhd_launch_llm_attention(hipStream_t st, const void* qkv, void* out, const unsigned char* key_valid, int B, int T, int nh, int nkv, int HD);
 int fvhd_launch_cast_rows(hipStream_t st, const void* src, int dtype, void* dst, long n);
 int fvhd_launch_gather_rows(hipStream_t st, const void* src, void* dst, int B, int T, int t_sel, int H);
+// llm_extend.hip
+int fvhd_launch_llm_attention_past(hipStream_t st, const void* qkv, const void* kc, const void* vc, const unsigned char* key_valid, void* out, int B, int T, int nh,
+                                   int nkv, int HD, int cap, const int* past_len, const int* status);
+int fvhd_launch_llm_cache_append(hipStream_t st, const void* qkv, void* kc, void* vc, unsigned char* key_valid, const unsigned char* chunk_valid, int B, int T, int nh,
+                                 int nkv, int HD, int cap, const int* past_len, int* status, int* status_host);
+int fvhd_launch_llm_extend_positions(hipStream_t st, const int64_t* next, const unsigned char* chunk_valid, int64_t* pos, int B, int T, const int* status);
+int fvhd_launch_llm_extend_state(hipStream_t st, int64_t* next, const int64_t* pos, int B, int T, int* len, const int* status);
+int fvhd_launch_llm_cache_rewind(hipStream_t st, const int* keep, int rows, unsigned char* key_valid, int64_t* next, int cap, int* len, int* status, int* status_host);
 // llm_decode.hip
 int fvhd_launch_dec_gemm(hipStream_t st, const DecGemmArgs* a);
 int fvhd_launch_dec_attention(hipStream_t st, const void* q, const void* kc, const void* vc, const unsigned char* key_valid, void* out, int B, int nh, int nkv, int hd,

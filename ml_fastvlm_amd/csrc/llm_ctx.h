@@ -35,6 +35,8 @@ struct __attribute__((visibility("default"))) fvhd_llm {     // (its inline cons
     int ws_rows = 0, ws_batch = 0, ws_pos = 0;
     char *h = nullptr, *xn = nullptr, *qkv = nullptr, *att = nullptr, *act = nullptr, *last = nullptr, *lastn = nullptr;
     float *rope = nullptr, *part = nullptr;
+    int64_t* epos = nullptr;               // inside `ws`: the positions [batch][T] of a chunk that fvhd_llm_extend was given without position ids
+    const int64_t* epos_used = nullptr;    // the positions the last decoder_stack() call used: the caller's, or `epos`
     int fuse_rope = 0;                     // FVHD_LLM_FUSEROPE=1: rotary embedding + KV-cache copies inside the q|k|v projection's epilogue instead of their own launch (identical bits; measured neutral - prefill 3.421 / 3.410 -> 3.404 / 3.407 ms at B = 8, 2.316 -> 2.342 at B = 1, profiles/r05_ttft_fuserope_ab.log: the 5.4-us launch saved comes back as epilogue time - so off by default)
     int down_splits = kMaxSplits, o_splits = 2, qkv_splits = 0, fuse_norm = 1;     // FVHD_LLM_SPLITK / FVHD_LLM_OSPLIT (largest split of down_proj / o_proj, 0 = never) / FVHD_LLM_QKVSPLIT / FVHD_LLM_FUSENORM
     int max_pos = 0;                       // fvhd_llm_set_max_positions (config.max_position_embeddings): rows of the rotary table
@@ -130,6 +132,9 @@ Mat mat_of(const fvhd_llm* c, int layer, int matrix);             // llm_weights
 int first_missing_tensor(const fvhd_llm* c);                      // llm_weights.hip: index into c->got, -1 when every tensor has arrived
 int wait_for_loads(fvhd_llm* c);                                  // llm_weights.hip
 int ensure_ws(fvhd_llm* c, int B, int T, hipStream_t st, bool check_capture);     // llm_prefill.hip
+// llm_prefill.hip: the launch sequence of fvhd_llm_prefill (extend = false) and of fvhd_llm_extend (extend = true: on the context's started cache)
+int decoder_stack(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* key_valid, const int64_t* position_ids, int batch, int seq_len,
+                  float* logits_out, void* k_cache, void* v_cache, hipStream_t st, bool extend);
 const char* sampling_error(float temperature, int top_k, float top_p);            // llm_step.hip: NULL when the parameters are valid
 // llm_step.hip: "" when the processor settings are valid for a vocabulary of V ids (V <= 0: the id range is not checked); lists: host memory
 std::string processors_error(float repetition_penalty, int no_repeat_ngram_size, int min_new_tokens, const int32_t* eos_ids, int n_eos,

@@ -66,6 +66,43 @@ int fvhd_op_attention_causal(fvhd_stream_t st, const void* qkv, void* out, const
     return lret("fvhd_op_attention_causal", fvhd_launch_llm_attention((hipStream_t)st, qkv, out, key_valid, B, T, n_heads, n_kv_heads, head_dim));
 }
 
+// ---- single ops of fvhd_llm_extend / fvhd_llm_cache_rewind (llm_extend.hip) ----
+int fvhd_op_attention_extend(fvhd_stream_t st, const void* qkv, const void* k_cache, const void* v_cache, const uint8_t* key_valid, void* out, int B, int T,
+                             int n_heads, int n_kv_heads, int head_dim, int capacity, const int* past_len)
+{
+    if (!qkv || !k_cache || !v_cache || !out || !past_len) return lfail("fvhd_op_attention_extend: NULL pointer");
+    if (head_dim != 64 && head_dim != 128) return lfail("fvhd_op_attention_extend: head_dim must be 64 or 128");
+    if (B < 1 || T < 1 || capacity < 1 || T > capacity || n_heads < 1 || n_kv_heads < 1 || n_heads % n_kv_heads)
+        return lfail("fvhd_op_attention_extend: needs B >= 1, 1 <= T <= capacity and n_heads a multiple of n_kv_heads");
+    return lret("fvhd_op_attention_extend", fvhd_launch_llm_attention_past((hipStream_t)st, qkv, k_cache, v_cache, key_valid, out, B, T, n_heads, n_kv_heads, head_dim,
+                                                                           capacity, past_len, nullptr));
+}
+
+int fvhd_op_cache_append(fvhd_stream_t st, const void* qkv, void* k_cache, void* v_cache, uint8_t* key_valid, const uint8_t* chunk_valid, int B, int T, int n_heads,
+                         int n_kv_heads, int head_dim, int capacity, const int* past_len, int* status)
+{
+    if (!qkv || !k_cache || !v_cache || !past_len || !status) return lfail("fvhd_op_cache_append: NULL pointer");
+    if (B < 1 || T < 1 || capacity < 1 || T > capacity || n_heads < 1 || n_kv_heads < 1 || head_dim < 8 || head_dim % 8 || ((uintptr_t)qkv & 15) ||
+        ((uintptr_t)k_cache & 15) || ((uintptr_t)v_cache & 15))
+        return lfail("fvhd_op_cache_append: needs B >= 1, 1 <= T <= capacity, head_dim % 8 == 0 and rows and caches aligned to 16 bytes");
+    return lret("fvhd_op_cache_append", fvhd_launch_llm_cache_append((hipStream_t)st, qkv, k_cache, v_cache, key_valid, chunk_valid, B, T, n_heads, n_kv_heads,
+                                                                     head_dim, capacity, past_len, status, nullptr));
+}
+
+int fvhd_op_extend_positions(fvhd_stream_t st, const int64_t* next_positions, const uint8_t* chunk_valid, int64_t* pos_out, int B, int T)
+{
+    if (!next_positions || !pos_out) return lfail("fvhd_op_extend_positions: NULL pointer");
+    if (B < 1 || T < 1) return lfail("fvhd_op_extend_positions: needs B >= 1 and T >= 1");
+    return lret("fvhd_op_extend_positions", fvhd_launch_llm_extend_positions((hipStream_t)st, next_positions, chunk_valid, pos_out, B, T, nullptr));
+}
+
+int fvhd_op_cache_rewind(fvhd_stream_t st, const int32_t* keep, int rows, uint8_t* key_valid, int64_t* positions, int capacity, int* length, int* status)
+{
+    if (!keep || !key_valid || !positions || !length || !status) return lfail("fvhd_op_cache_rewind: NULL pointer");
+    if (rows < 1 || rows > 64 || capacity < 1) return lfail("fvhd_op_cache_rewind: needs 1 <= rows <= 64 and capacity >= 1");
+    return lret("fvhd_op_cache_rewind", fvhd_launch_llm_cache_rewind((hipStream_t)st, keep, rows, key_valid, positions, capacity, length, status, nullptr));
+}
+
 // ---- single ops of the decode step (unit tests) ----
 // One builder per epilogue family fills DecGemmArgs; `scale` is NULL for a bf16 matrix, the fp32 row scales of an e4m3 one (the *_w8 entry points)
 static DecGemmArgs dec_args(int epi, const void* x, int B, const float* norm_w, float eps, const void* W, const float* scale, int N, int K, int splits)

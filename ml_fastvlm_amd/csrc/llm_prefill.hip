@@ -22,7 +22,7 @@ int ensure_ws(fvhd_llm* c, int B, int T, hipStream_t st, bool check_capture)
     const size_t o_h = a.take((size_t)nrows * c->H * 2), o_xn = a.take((size_t)nrows * c->H * 2), o_qkv = a.take((size_t)nrows * c->qkvw * 2),
                  o_att = a.take((size_t)nrows * c->nh * c->hd * 2), o_act = a.take((size_t)nrows * c->I * 2), o_last = a.take((size_t)lb * c->H * 2),
                  o_lastn = a.take((size_t)lb * c->H * 2), o_rope = a.take((size_t)np * c->hd * 4),
-                 o_part = a.take((size_t)nrows * std::max(kMaxSplits * c->H, 2 * c->qkvw) * 4);
+                 o_part = a.take((size_t)nrows * std::max(kMaxSplits * c->H, 2 * c->qkvw) * 4), o_epos = a.take((size_t)nrows * 8);
     hipError_t e = hipDeviceSynchronize();
     if (e != hipSuccess) return lhip("hipDeviceSynchronize", e);
     if (c->ws) {
@@ -39,6 +39,7 @@ int ensure_ws(fvhd_llm* c, int B, int T, hipStream_t st, bool check_capture)
     c->ws_bytes = a.off; c->ws_rows = nrows; c->ws_batch = nb; c->ws_pos = np;
     c->h = c->ws + o_h; c->xn = c->ws + o_xn; c->qkv = c->ws + o_qkv; c->att = c->ws + o_att; c->act = c->ws + o_act;
     c->last = c->ws + o_last; c->lastn = c->ws + o_lastn; c->rope = (float*)(c->ws + o_rope); c->part = (float*)(c->ws + o_part);
+    c->epos = (int64_t*)(c->ws + o_epos);
     // rotary table, fp32 like Qwen2RotaryEmbedding.forward: inv_freq_i = theta^(-2i/hd), angle = pos * inv_freq_i, (cos, sin)
     std::vector<float> tab((size_t)np * c->hd);
     for (int p = 0; p < np; ++p)
@@ -52,34 +53,17 @@ int ensure_ws(fvhd_llm* c, int B, int T, hipStream_t st, bool check_capture)
     return e == hipSuccess ? 0 : lhip("hipMemcpy(rope table)", e);
 }
 
-extern "C" {
-
-int fvhd_llm_set_max_positions(fvhd_llm* c, int max_position_embeddings)
+// The decoder stack of fvhd_llm_prefill and of fvhd_llm_extend (llm_step.hip) - ONE launch sequence: the GEMMs, their split-K choices, the
+// fused norms and the e4m3 dequantise-into-scratch path are the same in both.  extend = false is the prefill, launch for launch what it
+// always ran.  extend = true continues the context's started cache: key_valid is the CHUNK's mask [batch][seq_len], the rotary embedding
+// runs without cache pointers, and where the prefill launches llm_attention the chunk's k / v are appended to the layer's strided cache at
+// slot *len (the first layer's launch writes the mask column) and llm_attention_past reads keys [0, *len + seq_len) under the cache's mask;
+// without position ids the chunk's positions are computed on the device into the workspace.  c->epos_used is left pointing at the
+// positions the stack used (the caller's, or the workspace's).
+int decoder_stack(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* key_valid, const int64_t* position_ids, int batch, int seq_len,
+                  float* logits_out, void* k_cache, void* v_cache, hipStream_t st, bool extend)
 {
-    if (!c || max_position_embeddings <= 0) return lfail("fvhd_llm_set_max_positions: bad argument");
-    c->max_pos = max_position_embeddings;      // takes effect at the next workspace (re)allocation: call it before fvhd_llm_reserve
-    return 0;
-}
-
-int fvhd_llm_workspace_generation(const fvhd_llm* c) { return c ? c->generation : -1; }
-
-int fvhd_llm_reserve(fvhd_llm* c, int batch, int seq_len)
-{
-    if (!c || batch <= 0 || seq_len <= 0) return lfail("fvhd_llm_reserve: bad argument");
     LLM_ON_DEVICE(c);
-    return ensure_ws(c, batch, seq_len, nullptr, false);
-}
-
-int fvhd_llm_prefill(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* key_valid, const int64_t* position_ids, int batch, int seq_len,
-                     float* logits_out, void* k_cache, void* v_cache, fvhd_stream_t stream)
-{
-    if (!c || !embeds || !logits_out) return lfail("fvhd_llm_prefill: NULL argument");
-    if (dtype < 0 || dtype > 2) return lfail("fvhd_llm_prefill: bad dtype");
-    if (batch <= 0 || seq_len <= 0) return lfail("fvhd_llm_prefill: batch and seq_len must be positive");
-    if ((k_cache == nullptr) != (v_cache == nullptr)) return lfail("fvhd_llm_prefill: k_cache and v_cache come together");
-    if (first_missing_tensor(c) >= 0) return lfail("fvhd_llm_prefill: weights incomplete (fvhd_llm_finalize reports the missing tensor)");
-    LLM_ON_DEVICE(c);
-    hipStream_t st = (hipStream_t)stream;
     int e = ensure_ws(c, batch, seq_len, st, true);
     if (e) return e;
     {
@@ -107,8 +91,14 @@ int fvhd_llm_prefill(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* 
     const int B = batch, T = seq_len, M = B * T, Mp = (M + 255) / 256 * 256;
     const int H = c->H, I = c->I, nh = c->nh, nkv = c->nkv, hd = c->hd;
     const char* w = c->wdev;
-    if ((size_t)M * H % 4) return lfail("fvhd_llm_prefill: batch * seq_len * hidden must be a multiple of 4");
+    if ((size_t)M * H % 4) return lfail("fvhd_llm_prefill / fvhd_llm_extend: batch * seq_len * hidden must be a multiple of 4");
     LCHECK(fvhd_launch_cast_rows(st, embeds, dtype, c->h, (long)M * H), "cast embeds");
+    const size_t ext_layer = (size_t)c->dc_batch * nkv * c->dc_cap * hd * 2;      // extend: one layer of the context's strided caches
+    if (extend && !position_ids) {
+        LCHECK(fvhd_launch_llm_extend_positions(st, c->posv, key_valid, c->epos, B, T, c->status), "chunk positions");
+        position_ids = c->epos;
+    }
+    c->epos_used = position_ids;
     const size_t cache_layer = (size_t)B * nkv * T * hd * 2;
     // split-K factor of a GEMM with few output tiles (Mp / 128 x H / 128) - while the tiles of one slice do not fill the chip twice over, K is
     // split across workgroups (fp32 partials + a deterministic reduce that also adds the residual): down_proj 70 -> ~25 us per layer at the
@@ -158,7 +148,14 @@ int fvhd_llm_prefill(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* 
             LCHECK(fvhd_launch_gemm(st, c->xn, wqkv, (const float*)(w + o.bqkv), nullptr, nullptr, c->qkv, Mp, c->qkvw, H, FVHD_EPI_BIAS, FVHD_BF16), "qkv gemm");
             LCHECK(fvhd_launch_rope(st, c->qkv, (const long*)position_ids, c->rope, kc, vc, M, T, nh, nkv, hd, c->ws_pos, c->theta), "rope");
         }
-        LCHECK(fvhd_launch_llm_attention(st, c->qkv, c->att, key_valid, B, T, nh, nkv, hd), "attention");
+        if (extend) {
+            LCHECK(fvhd_launch_llm_cache_append(st, c->qkv, c->kcache + l * ext_layer, c->vcache + l * ext_layer, l == 0 ? c->mask : nullptr, key_valid, B, T, nh,
+                                                nkv, hd, c->dc_cap, c->len, c->status, c->status_host_dev), "cache append");
+            LCHECK(fvhd_launch_llm_attention_past(st, c->qkv, c->kcache + l * ext_layer, c->vcache + l * ext_layer, c->mask, c->att, B, T, nh, nkv, hd, c->dc_cap,
+                                                  c->len, c->status), "attention over the cache");
+        } else {
+            LCHECK(fvhd_launch_llm_attention(st, c->qkv, c->att, key_valid, B, T, nh, nkv, hd), "attention");
+        }
         LCHECK(weights(l, FVHD_MAT_O, &wo), "dequantise o_proj");
         if (o_sp > 1 && c->fuse_norm) {
             LCHECK(fvhd_launch_gemm_splitk_norm(st, c->att, wo, c->h, c->h, c->part, Mp, H, nh * hd, o_sp, (const float*)(w + o.ln2), c->xn, c->eps),
@@ -188,6 +185,35 @@ int fvhd_llm_prefill(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* 
     LCHECK(weights(-1, FVHD_MAT_LM_HEAD, &wlm), "dequantise lm_head");
     LCHECK(fvhd_launch_gemm(st, c->lastn, wlm, nullptr, nullptr, nullptr, logits_out, B, c->V, H, FVHD_EPI_NONE, FVHD_F32), "lm_head gemm");
     return 0;
+}
+
+extern "C" {
+
+int fvhd_llm_set_max_positions(fvhd_llm* c, int max_position_embeddings)
+{
+    if (!c || max_position_embeddings <= 0) return lfail("fvhd_llm_set_max_positions: bad argument");
+    c->max_pos = max_position_embeddings;      // takes effect at the next workspace (re)allocation: call it before fvhd_llm_reserve
+    return 0;
+}
+
+int fvhd_llm_workspace_generation(const fvhd_llm* c) { return c ? c->generation : -1; }
+
+int fvhd_llm_reserve(fvhd_llm* c, int batch, int seq_len)
+{
+    if (!c || batch <= 0 || seq_len <= 0) return lfail("fvhd_llm_reserve: bad argument");
+    LLM_ON_DEVICE(c);
+    return ensure_ws(c, batch, seq_len, nullptr, false);
+}
+
+int fvhd_llm_prefill(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* key_valid, const int64_t* position_ids, int batch, int seq_len,
+                     float* logits_out, void* k_cache, void* v_cache, fvhd_stream_t stream)
+{
+    if (!c || !embeds || !logits_out) return lfail("fvhd_llm_prefill: NULL argument");
+    if (dtype < 0 || dtype > 2) return lfail("fvhd_llm_prefill: bad dtype");
+    if (batch <= 0 || seq_len <= 0) return lfail("fvhd_llm_prefill: batch and seq_len must be positive");
+    if ((k_cache == nullptr) != (v_cache == nullptr)) return lfail("fvhd_llm_prefill: k_cache and v_cache come together");
+    if (first_missing_tensor(c) >= 0) return lfail("fvhd_llm_prefill: weights incomplete (fvhd_llm_finalize reports the missing tensor)");
+    return decoder_stack(c, embeds, dtype, key_valid, position_ids, batch, seq_len, logits_out, k_cache, v_cache, (hipStream_t)stream, false);
 }
 
 // hidden states after the decoder stack (before the final norm) of the last prefill: [batch * seq_len, hidden] bf16, for tests

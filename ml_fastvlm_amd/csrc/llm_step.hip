@@ -1,5 +1,5 @@
 // C ABI of the Qwen2 decode (include/fvhd.h "LLM decode"): the library's own KV cache, one token per sequence per step.
-// Kernels: llm_decode.hip, llm_w8.hip, llm_sample.hip, llm_beam.hip, llm_logits.hip, llm_spec.hip.
+// Kernels: llm_decode.hip, llm_w8.hip, llm_sample.hip, llm_beam.hip, llm_logits.hip, llm_spec.hip, llm_extend.hip.
 #include <algorithm>
 #include <cmath>
 
@@ -37,6 +37,7 @@ int dec_status_error(const fvhd_llm* c, const char* who)
                      " positions): a decode step past it wrote nothing - reserve a larger cache (fvhd_llm_cache_reserve) and start again");
     if (st == 2) return lfail(std::string(who) + ": a decode step was given a token id outside [0, vocab); it wrote nothing - start again");
     if (st == 3) return lfail(std::string(who) + ": a cache reorder was given a row index outside [0, rows_in); it wrote nothing - start again");
+    if (st == 4) return lfail(std::string(who) + ": a cache rewind was given a keep length outside [0, length]; it changed nothing - start again");
     return 0;
 }
 
@@ -315,6 +316,60 @@ int fvhd_llm_decode(fvhd_llm* c, const int64_t* token_ids, float* logits_out, in
     }
     LCHECK(fvhd_launch_dec_argmax_finish(st, c->amax_v, c->amax_i, (c->V / 16 + 3) / 4, B, c->last_ids, next_ids_out, c->posv, c->len, c->status),
            "decode argmax reduce");
+    return 0;
+}
+
+// ---- extend: a chunk of T tokens per row onto the started cache (include/fvhd.h "LLM extend"; kernels: llm_extend.hip) ----
+int fvhd_llm_extend(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* key_valid, const int64_t* position_ids, int T, float* logits_out,
+                    int64_t* next_ids_out, fvhd_stream_t stream)
+{
+    if (!c || !embeds) return lfail("fvhd_llm_extend: NULL argument");
+    if (dtype < 0 || dtype > 2) return lfail("fvhd_llm_extend: bad dtype");
+    if (!c->dc || !c->run_batch) return lfail("fvhd_llm_extend: no started sequence - call fvhd_llm_cache_reserve and fvhd_llm_start first");
+    if (T < 1) return lfail("fvhd_llm_extend: the chunk length T must be >= 1");
+    if (T > c->dc_cap)
+        return lfail("fvhd_llm_extend: the chunk length T = " + std::to_string(T) + " exceeds the capacity of fvhd_llm_cache_reserve (" +
+                     std::to_string(c->dc_cap) + ")");
+    if (c->hd != 64 && c->hd != 128) return lfail("fvhd_llm_extend: the attention over the cache needs head_dim 64 or 128");
+    if (int e = dec_status_error(c, "fvhd_llm_extend")) return e;
+    if (processors_on(c))
+        return lfail("fvhd_llm_extend: logits processors are on (fvhd_llm_set_logits_processors) - their token history has no ids for an embedded "
+                     "chunk; switch them off around fvhd_llm_extend");
+    if (first_missing_tensor(c) >= 0) return lfail("fvhd_llm_extend: weights incomplete (fvhd_llm_finalize reports the missing tensor)");
+    hipStream_t st = (hipStream_t)stream;
+    const int B = c->run_batch;
+    float* logits = logits_out ? logits_out : c->dlogits;
+    // the prefill's decoder stack on the chunk rows; per layer the append + the attention over slots [0, length + T) (llm_prefill.hip)
+    if (int e = decoder_stack(c, embeds, dtype, key_valid, position_ids, B, T, logits, nullptr, nullptr, st, true)) return e;
+    LLM_ON_DEVICE(c);
+    // the token: the launches of fvhd_llm_start (the sampler's n = the new length = length + T), then the state; all of them gated by
+    // the error word the first append sets when length + T > capacity
+    if (c->do_sample) {
+        DecSampleArgs a = dec_sample_args(c, logits, B);
+        a.len = c->len; a.n_add = T; a.last = c->last_ids; a.ids_out = next_ids_out; a.status = c->status;
+        LCHECK(fvhd_launch_dec_sample(st, &a, c->sws), "extend sampling");
+    } else {
+        LCHECK(fvhd_launch_dec_argmax_blocks(st, logits, c->V, B, c->amax_v, c->amax_i), "extend argmax (blocks)");
+        LCHECK(fvhd_launch_dec_argmax_finish(st, c->amax_v, c->amax_i, (c->V + 63) / 64, B, c->last_ids, next_ids_out, nullptr, nullptr, c->status),
+               "extend argmax (reduce)");
+    }
+    LCHECK(fvhd_launch_llm_extend_state(st, c->posv, c->epos_used, B, T, c->len, c->status), "extend state");
+    c->sp_begun = false;                                         // a lookup generation belongs to the sequence it was begun on
+    return 0;
+}
+
+int fvhd_llm_cache_rewind(fvhd_llm* c, const int32_t* keep_dev, fvhd_stream_t stream)
+{
+    if (!c || !keep_dev) return lfail("fvhd_llm_cache_rewind: NULL argument");
+    if (!c->dc || !c->run_batch) return lfail("fvhd_llm_cache_rewind: no started sequence - call fvhd_llm_cache_reserve and fvhd_llm_start first");
+    if (int e = dec_status_error(c, "fvhd_llm_cache_rewind")) return e;
+    if (processors_on(c))
+        return lfail("fvhd_llm_cache_rewind: logits processors are on (fvhd_llm_set_logits_processors) - their token history is not rewound; "
+                     "switch them off around fvhd_llm_cache_rewind");
+    LLM_ON_DEVICE(c);
+    LCHECK(fvhd_launch_llm_cache_rewind((hipStream_t)stream, keep_dev, c->run_batch, c->mask, c->posv, c->dc_cap, c->len, c->status, c->status_host_dev),
+           "cache rewind");
+    c->sp_begun = false;
     return 0;
 }
 

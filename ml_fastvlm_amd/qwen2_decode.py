@@ -23,6 +23,10 @@ choice, from a token history the step keeps on the device.
 `lookup_greedy` is `greedy` for one sequence with prompt-lookup decoding (include/fvhd.h "LLM speculative verification"): a step drafts up
 to 15 tokens by n-gram matching in the prompt's ids and the generated tokens, verifies them as the rows of ONE step (`verify`) and keeps
 what the model's own argmax confirms - the same tokens in fewer steps.
+`extend` appends a chunk of embedded tokens per row to the STARTED cache (include/fvhd.h "LLM extend": the prefill's decoder stack with an
+attention over the cached keys) and `rewind` drops the tail of every row; `greedy` / `sample` with `continue_cache=True` begin with
+`extend` where they otherwise begin with `start` - the next turn of a dialogue costs its own tokens, not the whole history again
+(`ml_fastvlm_amd.GenerationSession` keeps the turns' bookkeeping).
 """
 from __future__ import annotations
 
@@ -91,6 +95,7 @@ class Qwen2Generator:
         self._logits = torch.empty((self.batch, prefill.vocab), device=self.device, dtype=torch.float32)
         self._ids = torch.zeros((self.batch,), device=self.device, dtype=torch.long)
         self._run_batch = 0
+        self._length = None                                      # the cache length as the host knows it (None: unknown - `length()` asks the device)
         self._processors = None                                  # what set_logits_processors last set (None = all off)
         self._spec_rows = 0                                      # the largest row count this generator asked of spec_reserve
         self._spec_logits = self._spec_ids = self._spec_emitted = None      # verify()'s output buffers, made on first use
@@ -127,7 +132,78 @@ class Qwen2Generator:
             _lib.check(_lib.load().fvhd_llm_start(self.pre._h, _lib.ptr(x), _lib.dtype_code(x.dtype), _lib.ptr(am), _lib.ptr(pos), B, T, _lib.ptr(lg),
                                                   _lib.ptr(ids), _lib.stream_ptr(self.device)), "fvhd_llm_start")
         self._run_batch = B
+        self._length = T
+        self._session = None                                     # a GenerationSession's dialogue ends where the cache is started again
         return lg, ids
+
+    # ---- extend / rewind ---------------------------------------------------------------------------------------------------------------
+    def length(self) -> int:
+        """the cache length: what the host tracked through start / extend / step / rewind / greedy / sample, else (after a verify or lookup
+        step, whose emitted count lives on the device) one `cache_state` synchronisation"""
+        if getattr(self, "_length", None) is None:
+            self._length = self.cache_state()[0]
+        return self._length
+
+    def _length_add(self, n: int) -> None:
+        if getattr(self, "_length", None) is not None:
+            self._length += int(n)
+
+    @torch.no_grad()
+    def extend(self, inputs_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None,
+               logits: bool = True):
+        """a chunk of T embedded tokens per row onto the started cache (`fvhd_llm_extend`) -> (fp32 logits [B, vocab] of the chunk's last
+        position or None, the chosen ids [B]).  inputs_embeds [B, T, hidden] with B = the started batch; attention_mask [B, T]: the
+        CHUNK's mask (left padding for rows with fewer new tokens); position_ids None: every row continues from its next position over
+        its valid chunk tokens (computed on the device).  The cache length is read on the device: capture-safe once the workspace covers
+        (B, T).  Past the capacity nothing is written and the error word is set (`cache_state`).  Not with logits processors: their token
+        history has no ids for an embedded chunk.  The returned tensors are the generator's buffers, overwritten by the next step."""
+        B = self._run_batch
+        if B == 0:
+            raise RuntimeError("Qwen2Generator.extend: no started sequence - call start() first")
+        if self._processors is not None:
+            raise ValueError("extend: logits processors are set (set_logits_processors) - their token history has no ids for an embedded chunk; "
+                             "clear them with set_logits_processors()")
+        if not isinstance(inputs_embeds, torch.Tensor) or inputs_embeds.dim() != 3:
+            raise ValueError(f"extend: expected inputs_embeds of shape [B, T, hidden], got "
+                             f"{tuple(inputs_embeds.shape) if isinstance(inputs_embeds, torch.Tensor) else type(inputs_embeds)}")
+        if inputs_embeds.shape[0] != B:
+            raise ValueError(f"extend: the chunk has {inputs_embeds.shape[0]} rows, the started batch is {B} (one chunk row per started sequence)")
+        T = inputs_embeds.shape[1]
+        if T < 1 or T > self.capacity:
+            raise ValueError(f"extend: the chunk length {T} must be in [1, the reserved capacity {self.capacity}]")
+        x, am, pos = self.pre._check(inputs_embeds, attention_mask, position_ids)
+        lg = self._logits[:B] if logits else None
+        ids = self._ids[:B]
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.extend_lib().fvhd_llm_extend(self.pre._h, _lib.ptr(x), _lib.dtype_code(x.dtype), _lib.ptr(am), _lib.ptr(pos), T, _lib.ptr(lg),
+                                                         _lib.ptr(ids), _lib.stream_ptr(self.device)), "fvhd_llm_extend")
+        self._length_add(T)
+        return lg, ids
+
+    @torch.no_grad()
+    def rewind(self, keep) -> None:
+        """row b keeps its first keep[b] cache slots (`fvhd_llm_cache_rewind`): the slots behind them leave the sequence (mask cleared, the
+        row's next position lowered by the valid ones among them) and the length becomes max(keep).  keep: an int32 / int64 tensor or a
+        list, one entry per started row, each in [0, length] (anything else sets error word 4 on the device).  The ids the previous step
+        chose are stale afterwards: continue with extend(), or step() with explicit ids.  A tensor on the device is used as it is (int32) -
+        the host's length is then unknown until `length()` asks."""
+        B = self._run_batch
+        if B == 0:
+            raise RuntimeError("Qwen2Generator.rewind: no started sequence - call start() first")
+        if self._processors is not None:
+            raise ValueError("rewind: logits processors are set (set_logits_processors) - their token history is not rewound; "
+                             "clear them with set_logits_processors()")
+        on_device = isinstance(keep, torch.Tensor) and keep.device.type != "cpu"
+        k = keep if isinstance(keep, torch.Tensor) else torch.tensor([int(v) for v in keep], dtype=torch.int32)
+        if k.dim() != 1 or k.shape[0] != B or k.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"rewind: keep must hold one int32 / int64 entry per started row ({B}), got {k.dtype} {tuple(k.shape)}")
+        if not on_device and (int(k.min()) < 0 or (getattr(self, "_length", None) is not None and int(k.max()) > self._length)):
+            raise ValueError(f"rewind: keep {k.tolist()} must lie in [0, the cache length{'' if self._length is None else ' ' + str(self._length)}]")
+        new_len = None if on_device else int(k.max())
+        k = k.to(device=self.device, dtype=torch.int32).contiguous()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.extend_lib().fvhd_llm_cache_rewind(self.pre._h, _lib.ptr(k), _lib.stream_ptr(self.device)), "fvhd_llm_cache_rewind")
+        self._length = new_len
 
     @torch.no_grad()
     def step(self, ids: Optional[torch.Tensor] = None, logits: bool = True):
@@ -142,6 +218,7 @@ class Qwen2Generator:
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().fvhd_llm_decode(self.pre._h, _lib.ptr(ids), _lib.ptr(lg), _lib.ptr(self._ids[:B]), _lib.stream_ptr(self.device)),
                        "fvhd_llm_decode")
+        self._length_add(1)
         return lg, self._ids[:B]
 
     # ---- beam search: the two device operations -----------------------------------------------------------------------------------------
@@ -225,6 +302,7 @@ class Qwen2Generator:
         with torch.cuda.device(self.device):
             _lib.check(_lib.lookup_lib().fvhd_llm_verify(self.pre._h, _lib.ptr(drafts), T, _lib.ptr(lg), _lib.ptr(self._spec_ids), _lib.ptr(self._spec_emitted),
                                                          _lib.stream_ptr(self.device)), "fvhd_llm_verify")
+        self._length = None                                      # the emitted count lives on the device
         return lg, self._spec_ids[:T], self._spec_emitted
 
     def lookup_state(self):
@@ -302,14 +380,16 @@ class Qwen2Generator:
             if written == before:                                # a live step emits at least one token: the error word stopped them
                 break
         n, st = self.cache_state()
+        self._length = n
         if st:
-            raise _lib.FvhdError(f"lookup_greedy: the steps left error word {st} (1 = past the cache's capacity, 2 = a token id out of range)")
+            raise _lib.FvhdError(f"lookup_greedy: the steps left error word {st} (1 = past the cache's capacity, 2 = a token id out of range, "
+                                 "3 = a cache reorder's row index out of range, 4 = a cache rewind's keep length out of range)")
         res = out[:written].clone()[None]
         return (res, {"steps": steps, "tokens": written}) if return_stats else res
 
     def cache_state(self):
         """(length, error word) after a device synchronisation; error 1 = a step ran past the capacity, 2 = a token id out of range, 3 = a
-        cache reorder's row index out of range"""
+        cache reorder's row index out of range, 4 = a cache rewind's keep length out of range"""
         n, st = C.c_int(0), C.c_int(0)
         _lib.check(_lib.load().fvhd_llm_cache_state(self.pre._h, C.byref(n), C.byref(st)), "fvhd_llm_cache_state")
         return n.value, st.value
@@ -354,33 +434,35 @@ class Qwen2Generator:
     def greedy(self, inputs_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None,
                max_new_tokens: int = 256, eos_token_id: Union[None, int, Sequence[int]] = None, pad_token_id: Optional[int] = None,
                graph: bool = True, poll_every: int = 16, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0,
-               suppress_tokens: Optional[Sequence[int]] = None) -> torch.Tensor:
+               suppress_tokens: Optional[Sequence[int]] = None, continue_cache: bool = False) -> torch.Tensor:
         """transformers' greedy search (`GenerationMixin._sample` with do_sample=False) on the library's steps -> new tokens [B, n].
         graph=True captures one step (decode + the finished-sequence bookkeeping) into a CUDA graph and replays it; "all finished" is
         polled every `poll_every` steps (no host synchronisation per token) and the output trimmed to the step where it happened.
         repetition_penalty / no_repeat_ngram_size / min_new_tokens (with eos_token_id) / suppress_tokens: transformers' logits processors
-        (`set_logits_processors`), set for this run and cleared after it."""
+        (`set_logits_processors`), set for this run and cleared after it.
+        continue_cache=True: `inputs_embeds` is a chunk for the STARTED cache - the run begins with `extend` where it otherwise begins with
+        `start` (not with logits processors); everything after the first token is the same code."""
         self._set_greedy()
         with self._processors_for_run(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, suppress_tokens):
-            return self._run(inputs_embeds, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id, graph, poll_every)
+            return self._run(inputs_embeds, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id, graph, poll_every, continue_cache)
 
     @torch.no_grad()
     def sample(self, inputs_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None,
                max_new_tokens: int = 256, temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, seed: Optional[int] = None,
                eos_token_id: Union[None, int, Sequence[int]] = None, pad_token_id: Optional[int] = None, graph: bool = True,
                poll_every: int = 16, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0,
-               suppress_tokens: Optional[Sequence[int]] = None) -> torch.Tensor:
+               suppress_tokens: Optional[Sequence[int]] = None, continue_cache: bool = False) -> torch.Tensor:
         """transformers' multinomial sampling (`GenerationMixin._sample` with do_sample=True, num_beams=1: temperature, then top-k, then
         top-p) on the library's steps -> new tokens [B, n], with greedy's return contract, EOS / pad bookkeeping and graph replay.
         seed None: 63 bits from torch's default CPU generator, so `torch.manual_seed` makes a run repeat.  The same seed gives the same
         tokens, eager or graph; the draws are not torch.multinomial's (only the distribution is the same).  The logits processors of
-        `greedy` apply before the temperature, as in transformers."""
+        `greedy` apply before the temperature, as in transformers.  continue_cache: as in `greedy`."""
         if seed is None:
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.long).item())
         self.set_sampling(True, temperature, top_k, top_p, seed)
         try:
             with self._processors_for_run(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, suppress_tokens):
-                return self._run(inputs_embeds, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id, graph, poll_every)
+                return self._run(inputs_embeds, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id, graph, poll_every, continue_cache)
         finally:
             self.set_sampling(False)
 
@@ -398,12 +480,19 @@ class Qwen2Generator:
         finally:
             self.set_logits_processors()
 
-    def _run(self, inputs_embeds, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id, graph, poll_every) -> torch.Tensor:
+    def _run(self, inputs_embeds, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id, graph, poll_every,
+             continue_cache=False) -> torch.Tensor:
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be >= 1")
         B, T = inputs_embeds.shape[:2]
-        if T + max_new_tokens - 1 > self.capacity:
-            raise ValueError(f"prompt {T} + {max_new_tokens} new tokens need a cache of {T + max_new_tokens - 1} positions, reserved {self.capacity}")
+        past = 0
+        if continue_cache:
+            if self._run_batch == 0:
+                raise RuntimeError("continue_cache=True: no started sequence - call start() (or a run without continue_cache) first")
+            past = self.length()                                 # the host's own count; one synchronisation only when it is unknown
+        if past + T + max_new_tokens - 1 > self.capacity:
+            raise ValueError(f"{'the cached ' + str(past) + ' + chunk' if continue_cache else 'prompt'} {T} + {max_new_tokens} new tokens need a cache of "
+                             f"{past + T + max_new_tokens - 1} positions, reserved {self.capacity}")
         eos = [] if eos_token_id is None else ([int(eos_token_id)] if isinstance(eos_token_id, int) else [int(e) for e in eos_token_id])
         if eos and pad_token_id is None:
             pad_token_id = eos[0]                                # what transformers does (with a warning) when no pad token is set
@@ -425,7 +514,7 @@ class Qwen2Generator:
             alive.index_copy_(0, col, unfinished.any()[None])
             col.add_(1)
 
-        _, ids = self.start(inputs_embeds, attention_mask, position_ids, logits=False)
+        _, ids = (self.extend if continue_cache else self.start)(inputs_embeds, attention_mask, position_ids, logits=False)
         post(ids)
         steps = max_new_tokens - 1
         g = None
@@ -451,6 +540,7 @@ class Qwen2Generator:
                     _, raw = self.step(fed, logits=False)
                     post(raw)
             done += k
+        self._length = past + T + done                           # replayed steps included: the host counted them
         if eos:
             dead = (~alive[:done + 1]).nonzero()
             if dead.numel():
@@ -528,5 +618,6 @@ class Qwen2Generator:
                 else:
                     one_step()
             done += min(poll_every, steps - done)
+        self._length = T + done
         tokens, scores = state.result()
         return (tokens, scores) if return_scores else tokens
