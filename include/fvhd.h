@@ -64,8 +64,12 @@ typedef void* fvhd_stream_t; /* hipStream_t */
  * bits are what 507 ran; nothing earlier changed.  509 adds the extension of a started KV cache by a chunk of tokens and its rewind
  * (fvhd_llm_extend, fvhd_llm_cache_rewind, fvhd_op_attention_extend / _cache_append / _extend_positions / _cache_rewind; error word 4):
  * fvhd_llm_prefill, fvhd_llm_start, fvhd_llm_decode, fvhd_llm_verify and the lookup step enqueue what 508 did, launch for launch and bit for
- * bit; the prefill workspace grows by 8 bytes per row (the positions of a chunk); nothing earlier changed. */
-#define FVHD_VERSION 509
+ * bit; the prefill workspace grows by 8 bytes per row (the positions of a chunk); nothing earlier changed.  510 changes behaviour without a new
+ * symbol: behind fvhd_llm_cache_rewind / fvhd_llm_cache_gather the calls that would feed the ids "the previous step chose"
+ * (fvhd_llm_decode(token_ids = NULL), fvhd_llm_verify, fvhd_llm_lookup_begin / _step) are refused until fvhd_llm_start, fvhd_llm_extend or a
+ * fvhd_llm_decode on explicit token_ids, and fvhd_llm_decode, fvhd_llm_verify and fvhd_llm_cache_gather end a lookup generation; every call
+ * that is accepted enqueues what 509 did, launch for launch and bit for bit. */
+#define FVHD_VERSION 510
 int fvhd_version(void);
 const char* fvhd_last_error(void);
 
@@ -474,7 +478,8 @@ int fvhd_llm_start(fvhd_llm* ctx, const void* embeds, int dtype, const uint8_t* 
 /* One step: token_ids int64 [batch] on the device, or NULL = the ids the previous start / decode chose; appends their k / v at slot
  * `length` with mask 1, advances length and positions by one, and writes logits_out (NULL or fp32 [batch, vocab]) and next_ids_out
  * (NULL or int64 [batch]).  A step past `capacity` (or given an id outside [0, vocab)) writes nothing and sets a sticky error word that the
- * next fvhd_llm_decode reports as an error (fvhd_llm_cache_state reads it at once).  Capture-safe after fvhd_llm_start. */
+ * next fvhd_llm_decode reports as an error (fvhd_llm_cache_state reads it at once).  Capture-safe after fvhd_llm_start.
+ * token_ids = NULL is refused behind fvhd_llm_cache_rewind / fvhd_llm_cache_gather (see there).  Ends a lookup generation. */
 int fvhd_llm_decode(fvhd_llm* ctx, const int64_t* token_ids, float* logits_out, int64_t* next_ids_out, fvhd_stream_t stream);
 /* synchronises the device, then: the cache length and the error word (0 = fine, 1 = past capacity, 2 = token id out of range, 3 = a
  * cache reorder's row index out of range, 4 = a cache rewind's keep length out of range) */
@@ -586,7 +591,12 @@ int fvhd_op_dec_lm_argmax_w8(fvhd_stream_t stream, const void* x, int B, const f
  * Cache reorder (`Cache.reorder_cache` / index_select of every layer): new row r of K and V of every layer, of the key-valid mask and of
  * the next positions = old row src_rows[r] (int64 [rows_out] on the device, entries in [0, rows_in)), over cache slots [0, length).  Any
  * map is correct (it goes through a scratch, never in place); slots >= length and rows >= rows_out keep their bytes; rows with
- * src_rows[r] == r are not touched.  An index out of range writes nothing and sets the sticky error word to 3. */
+ * src_rows[r] == r are not touched.  An index out of range writes nothing and sets the sticky error word to 3.
+ * The ids "the previous step chose" are NOT reordered: after the call they belong to the rows as they were before it, so the next call must be
+ * fvhd_llm_extend, or fvhd_llm_decode with explicit token_ids; fvhd_llm_decode(token_ids = NULL), fvhd_llm_verify, fvhd_llm_lookup_begin and
+ * fvhd_llm_lookup_step are refused, with a message that says so and names the two ways on, until one of those two (or fvhd_llm_start) has
+ * been enqueued.  It is an enqueue-time rule of the host, like the settings of the logits processors: a captured step replays as it was
+ * captured, whatever was enqueued since.  Ends a lookup generation. */
 /* Allocates the reorder's scratch (two layers' K | V of the reserved cache) and the top-K workspace (about 2 MiB), apart from
  * fvhd_llm_cache_reserve's allocation.  Synchronises (refused while a stream is being captured).  fvhd_llm_cache_reserve frees it with
  * the cache it was sized for. */
@@ -682,7 +692,10 @@ int fvhd_llm_spec_reserve(fvhd_llm* ctx, int max_rows, int lookup_capacity);
 int fvhd_llm_verify(fvhd_llm* ctx, const int64_t* draft_ids, int rows, float* logits_out, int64_t* ids_out, int32_t* emitted_out, fvhd_stream_t stream);
 /* A lookup generation, after fvhd_llm_start: seeds the token buffer with lookup_ids (device int64 [n_lookup], n_lookup <= lookup_capacity;
  * NULL with 0) and the token fvhd_llm_start chose, which is also tokens_out[0].  tokens_out: device int64 [max_new_tokens], written by the
- * later steps; host_eos_ids: host int32 [n_eos <= 16].  One small launch; fvhd_llm_start ends the generation. */
+ * later steps; host_eos_ids: host int32 [n_eos <= 16].  One small launch.  The generation belongs to the sequence as the lookup steps left
+ * it: fvhd_llm_start, fvhd_llm_extend, fvhd_llm_decode, fvhd_llm_verify, fvhd_llm_cache_rewind, fvhd_llm_cache_gather, fvhd_llm_cache_reserve
+ * and a fvhd_llm_spec_reserve that grows the scratch end it when they enqueue (a later fvhd_llm_lookup_step is refused: "no token buffer");
+ * fvhd_llm_lookup_begin begins the next one. */
 int fvhd_llm_lookup_begin(fvhd_llm* ctx, const int64_t* lookup_ids, int n_lookup, const int32_t* host_eos_ids, int n_eos, int max_new_tokens,
                           int64_t* tokens_out, fvhd_stream_t stream);
 /* draft (rows - 1 drafts, 1 <= max_ngram <= 16) + verify + accept: the emitted run is cut after its first EOS id and at max_new_tokens, appended
@@ -743,7 +756,9 @@ int fvhd_llm_extend(fvhd_llm* ctx, const void* embeds, int dtype, const uint8_t*
  * drops by the number of VALID slots among them and their mask bytes are cleared; then length = max_b keep[b].  K / V bytes are not touched
  * (later appends overwrite them).  A keep[b] outside [0, length] changes nothing and sets the sticky error word to 4.  One launch,
  * capture-safe.  Refused with logits processors on (their history is not rewound).  After a rewind the ids "the previous step chose" are
- * stale: the next call must be fvhd_llm_extend, or fvhd_llm_decode with explicit token_ids. */
+ * stale: the next call must be fvhd_llm_extend, or fvhd_llm_decode with explicit token_ids - anything that would feed the stale ids
+ * (fvhd_llm_decode(token_ids = NULL), fvhd_llm_verify, fvhd_llm_lookup_begin / _step) is refused, under fvhd_llm_cache_gather's enqueue-time
+ * rule (a captured step replays as captured).  Ends a lookup generation. */
 int fvhd_llm_cache_rewind(fvhd_llm* ctx, const int32_t* keep_dev, fvhd_stream_t stream);
 /* the kernels on their own (tests), on plain device pointers.
  * fvhd_op_attention_extend: qkv [B*T, (n_heads + 2 n_kv_heads) * head_dim] bf16 (the chunk's packed rows, rope applied; the q heads are

@@ -104,6 +104,10 @@ struct __attribute__((visibility("default"))) fvhd_llm {     // (its inline cons
     int64_t* sp_out = nullptr;             // fvhd_llm_lookup_begin: the caller's output tokens [sp_out_cap]
     int sp_out_cap = 0;
     bool sp_begun = false;
+    // fvhd_llm_cache_rewind / fvhd_llm_cache_gather set it: last_ids (the ids "the previous step chose") then belong to the rows as they were
+    // before the call.  Cleared by fvhd_llm_start, fvhd_llm_extend and fvhd_llm_decode with explicit token_ids; while it is set every call
+    // that would feed last_ids is refused when it enqueues (a captured step replays as captured)
+    bool ids_stale = false;
 };
 
 inline bool processors_on(const fvhd_llm* c)

@@ -41,6 +41,14 @@ int dec_status_error(const fvhd_llm* c, const char* who)
     return 0;
 }
 
+// the enqueue-time rule behind a cache reorder / rewind: nothing may feed the ids the previous step chose
+int stale_ids_error(const fvhd_llm* c, const char* who)
+{
+    if (!c->ids_stale) return 0;
+    return lfail(std::string(who) + ": the ids the previous step chose belong to the rows as they were before the cache reorder / rewind "
+                 "(fvhd_llm_cache_gather / fvhd_llm_cache_rewind) - continue with fvhd_llm_extend, or with fvhd_llm_decode on explicit token_ids");
+}
+
 DecSampleArgs dec_sample_args(const fvhd_llm* c, const float* logits, int B)
 {
     DecSampleArgs a;
@@ -150,6 +158,7 @@ int fvhd_llm_cache_reserve(fvhd_llm* c, int batch, int capacity)
     c->sp_begun = false;
     c->dc_batch = c->dc_cap = c->run_batch = 0;
     c->hist_started = false;
+    c->ids_stale = false;
     if ((he = hipMalloc((void**)&c->dc, a.off)) != hipSuccess) return lhip("hipMalloc(llm KV cache)", he);
     if ((he = hipMemset(c->dc, 0, a.off)) != hipSuccess) return lhip("hipMemset(llm KV cache)", he);      // counters start at zero
     if (!c->status_host) {
@@ -235,6 +244,7 @@ int fvhd_llm_start(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* ke
     }
     c->run_batch = B;
     c->sp_begun = false;                                         // a lookup generation belongs to the sequence it was begun on
+    c->ids_stale = false;                                        // the ids chosen here are these rows'
     return 0;
 }
 
@@ -244,6 +254,8 @@ int fvhd_llm_decode(fvhd_llm* c, const int64_t* token_ids, float* logits_out, in
     if (!c->dc || !c->run_batch) return lfail("fvhd_llm_decode: no started sequence - call fvhd_llm_cache_reserve and fvhd_llm_start first");
     if (int e = dec_status_error(c, "fvhd_llm_decode")) return e;
     if (int e = dec_embedding_error(c, "fvhd_llm_decode")) return e;
+    if (!token_ids)
+        if (int e = stale_ids_error(c, "fvhd_llm_decode(token_ids = NULL)")) return e;
     const bool proc = processors_on(c);
     if (proc && !c->hist_started)
         return lfail("fvhd_llm_decode: logits processors are on but the sequence was started without them (no token history) - set them "
@@ -306,6 +318,8 @@ int fvhd_llm_decode(fvhd_llm* c, const int64_t* token_ids, float* logits_out, in
         sa.len = c->len; sa.n_add = 1; sa.last = c->last_ids; sa.ids_out = next_ids_out; sa.posv = c->posv; sa.len_advance = c->len;
         sa.status = c->status;
         LCHECK(fvhd_launch_dec_sample(st, &sa, c->sws), "decode sampling");
+        c->sp_begun = false;
+        if (token_ids) c->ids_stale = false;
         return 0;
     }
     LCHECK(fvhd_launch_dec_gemm(st, &a), "decode final norm + lm_head + argmax");
@@ -316,6 +330,8 @@ int fvhd_llm_decode(fvhd_llm* c, const int64_t* token_ids, float* logits_out, in
     }
     LCHECK(fvhd_launch_dec_argmax_finish(st, c->amax_v, c->amax_i, (c->V / 16 + 3) / 4, B, c->last_ids, next_ids_out, c->posv, c->len, c->status),
            "decode argmax reduce");
+    c->sp_begun = false;                                         // a plain step: the token buffer of a lookup generation no longer describes the sequence
+    if (token_ids) c->ids_stale = false;                         // the ids chosen on fed ids are these rows'
     return 0;
 }
 
@@ -355,6 +371,7 @@ int fvhd_llm_extend(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* k
     }
     LCHECK(fvhd_launch_llm_extend_state(st, c->posv, c->epos_used, B, T, c->len, c->status), "extend state");
     c->sp_begun = false;                                         // a lookup generation belongs to the sequence it was begun on
+    c->ids_stale = false;
     return 0;
 }
 
@@ -370,6 +387,7 @@ int fvhd_llm_cache_rewind(fvhd_llm* c, const int32_t* keep_dev, fvhd_stream_t st
     LCHECK(fvhd_launch_llm_cache_rewind((hipStream_t)stream, keep_dev, c->run_batch, c->mask, c->posv, c->dc_cap, c->len, c->status, c->status_host_dev),
            "cache rewind");
     c->sp_begun = false;
+    c->ids_stale = true;                                         // last_ids were chosen behind the slots that just left
     return 0;
 }
 
@@ -403,6 +421,8 @@ int fvhd_llm_cache_gather(fvhd_llm* c, const int64_t* src_rows, int rows_in, int
     a.status_host = c->status_host_dev; a.ws = c->beam;
     LCHECK(fvhd_launch_dec_cache_gather((hipStream_t)stream, &a), "cache reorder");
     c->run_batch = rows_out;
+    c->sp_begun = false;                                         // a lookup generation belongs to the row it was begun on
+    c->ids_stale = true;                                         // the reorder moves K, V, mask and positions, not last_ids
     return 0;
 }
 
@@ -527,6 +547,7 @@ int fvhd_llm_verify(fvhd_llm* c, const int64_t* draft_ids, int rows, float* logi
 {
     if (!c || !draft_ids) return lfail("fvhd_llm_verify: NULL argument");
     if (int e = spec_refusal(c, "fvhd_llm_verify", rows)) return e;
+    if (int e = stale_ids_error(c, "fvhd_llm_verify")) return e;
     if (int e = dec_status_error(c, "fvhd_llm_verify")) return e;
     if (int e = dec_embedding_error(c, "fvhd_llm_verify")) return e;
     LLM_ON_DEVICE(c);
@@ -538,6 +559,7 @@ int fvhd_llm_verify(fvhd_llm* c, const int64_t* draft_ids, int rows, float* logi
     a.ids = ids;
     a.emitted = emitted_out;
     LCHECK(fvhd_launch_spec_accept(st, &a), "verify accept");
+    c->sp_begun = false;                                         // a bare verify step appends nothing to a lookup generation's token buffer
     return 0;
 }
 
@@ -546,6 +568,7 @@ int fvhd_llm_lookup_begin(fvhd_llm* c, const int64_t* lookup_ids, int n_lookup, 
 {
     if (!c || !tokens_out) return lfail("fvhd_llm_lookup_begin: NULL argument");
     if (int e = spec_refusal(c, "fvhd_llm_lookup_begin", 2)) return e;
+    if (int e = stale_ids_error(c, "fvhd_llm_lookup_begin")) return e;
     if (n_lookup < 0 || (n_lookup && !lookup_ids) || n_lookup + c->dc_cap + 16 > c->spec_seq_cap)
         return lfail("fvhd_llm_lookup_begin: n_lookup must be in [0, the lookup_capacity of fvhd_llm_spec_reserve]");
     if (n_eos < 0 || n_eos > kMaxEos || (n_eos && !host_eos_ids)) return lfail("fvhd_llm_lookup_begin: at most " + std::to_string(kMaxEos) + " EOS ids");
@@ -564,6 +587,7 @@ int fvhd_llm_lookup_step(fvhd_llm* c, int rows, int max_ngram, fvhd_stream_t str
 {
     if (!c) return lfail("fvhd_llm_lookup_step: ctx is NULL");
     if (int e = spec_refusal(c, "fvhd_llm_lookup_step", rows)) return e;
+    if (int e = stale_ids_error(c, "fvhd_llm_lookup_step")) return e;
     if (!c->sp_begun) return lfail("fvhd_llm_lookup_step: no token buffer - call fvhd_llm_lookup_begin after fvhd_llm_start");
     if (max_ngram < 1 || max_ngram > 16) return lfail("fvhd_llm_lookup_step: max_ngram must be in [1, 16]");
     if (int e = dec_status_error(c, "fvhd_llm_lookup_step")) return e;

@@ -97,6 +97,7 @@ class Qwen2Generator:
         self._run_batch = 0
         self._length = None                                      # the cache length as the host knows it (None: unknown - `length()` asks the device)
         self._processors = None                                  # what set_logits_processors last set (None = all off)
+        self._ids_stale = False                                  # a rewind / cache_gather since the ids were chosen (`_stale_ids_refusal`)
         self._spec_rows = 0                                      # the largest row count this generator asked of spec_reserve
         self._spec_logits = self._spec_ids = self._spec_emitted = None      # verify()'s output buffers, made on first use
 
@@ -133,6 +134,7 @@ class Qwen2Generator:
                                                   _lib.ptr(ids), _lib.stream_ptr(self.device)), "fvhd_llm_start")
         self._run_batch = B
         self._length = T
+        self._ids_stale = False
         self._session = None                                     # a GenerationSession's dialogue ends where the cache is started again
         return lg, ids
 
@@ -143,6 +145,12 @@ class Qwen2Generator:
         if getattr(self, "_length", None) is None:
             self._length = self.cache_state()[0]
         return self._length
+
+    def _stale_ids_refusal(self, who: str) -> None:
+        """the library's enqueue-time rule (include/fvhd.h, fvhd_llm_cache_rewind / fvhd_llm_cache_gather), raised before calling in"""
+        if getattr(self, "_ids_stale", False):
+            raise ValueError(f"{who}: the ids the previous step chose belong to the rows as they were before the cache reorder / rewind "
+                             "(cache_gather / rewind) - continue with extend(), or with step() on explicit ids")
 
     def _length_add(self, n: int) -> None:
         if getattr(self, "_length", None) is not None:
@@ -178,6 +186,7 @@ class Qwen2Generator:
             _lib.check(_lib.extend_lib().fvhd_llm_extend(self.pre._h, _lib.ptr(x), _lib.dtype_code(x.dtype), _lib.ptr(am), _lib.ptr(pos), T, _lib.ptr(lg),
                                                          _lib.ptr(ids), _lib.stream_ptr(self.device)), "fvhd_llm_extend")
         self._length_add(T)
+        self._ids_stale = False
         return lg, ids
 
     @torch.no_grad()
@@ -185,7 +194,7 @@ class Qwen2Generator:
         """row b keeps its first keep[b] cache slots (`fvhd_llm_cache_rewind`): the slots behind them leave the sequence (mask cleared, the
         row's next position lowered by the valid ones among them) and the length becomes max(keep).  keep: an int32 / int64 tensor or a
         list, one entry per started row, each in [0, length] (anything else sets error word 4 on the device).  The ids the previous step
-        chose are stale afterwards: continue with extend(), or step() with explicit ids.  A tensor on the device is used as it is (int32) -
+        chose are stale afterwards: continue with extend(), or step() with explicit ids - step(None) and verify() are refused.  A tensor on the device is used as it is (int32) -
         the host's length is then unknown until `length()` asks."""
         B = self._run_batch
         if B == 0:
@@ -204,14 +213,18 @@ class Qwen2Generator:
         with torch.cuda.device(self.device):
             _lib.check(_lib.extend_lib().fvhd_llm_cache_rewind(self.pre._h, _lib.ptr(k), _lib.stream_ptr(self.device)), "fvhd_llm_cache_rewind")
         self._length = new_len
+        self._ids_stale = True
 
     @torch.no_grad()
     def step(self, ids: Optional[torch.Tensor] = None, logits: bool = True):
         """one decode step on `ids` (int64 [B] on the device; None = the ids the previous step chose) -> (logits [B, vocab] or None, ids [B]).
-        Host arguments are the same for every step: the call can be captured into a graph and replayed."""
+        Host arguments are the same for every step: the call can be captured into a graph and replayed.  After rewind() / cache_gather()
+        the chosen ids are the old rows': ids=None is refused until an extend() or a step on explicit ids."""
         B = self._run_batch
         if B == 0:
             raise RuntimeError("Qwen2Generator.step: call start() first")
+        if ids is None:
+            self._stale_ids_refusal("step(ids=None)")
         if ids is not None and (ids.dtype != torch.long or ids.device != self.device or tuple(ids.shape) != (B,) or not ids.is_contiguous()):
             raise ValueError(f"ids must be a contiguous int64 tensor [{B}] on {self.device}")
         lg = self._logits[:B] if logits else None
@@ -219,6 +232,8 @@ class Qwen2Generator:
             _lib.check(_lib.load().fvhd_llm_decode(self.pre._h, _lib.ptr(ids), _lib.ptr(lg), _lib.ptr(self._ids[:B]), _lib.stream_ptr(self.device)),
                        "fvhd_llm_decode")
         self._length_add(1)
+        if ids is not None:
+            self._ids_stale = False
         return lg, self._ids[:B]
 
     # ---- beam search: the two device operations -----------------------------------------------------------------------------------------
@@ -232,7 +247,8 @@ class Qwen2Generator:
     @torch.no_grad()
     def cache_gather(self, src_rows: torch.Tensor, rows_in: int) -> None:
         """cache row r (K / V of every layer, mask, next position) = old row src_rows[r] (`fvhd_llm_cache_gather`); the following steps run
-        on len(src_rows) rows.  src_rows: int64 on the device, entries in [0, rows_in).  Capture-safe after `beam_reserve`."""
+        on len(src_rows) rows.  src_rows: int64 on the device, entries in [0, rows_in).  Capture-safe after `beam_reserve`.  The chosen ids are
+        not reordered: continue with extend(), or step() with explicit ids - step(None) and verify() are refused."""
         if src_rows.dtype != torch.long or src_rows.device != self.device or src_rows.dim() != 1 or not src_rows.is_contiguous():
             raise ValueError(f"src_rows must be a contiguous 1-D int64 tensor on {self.device}")
         rows_out = src_rows.shape[0]
@@ -242,6 +258,7 @@ class Qwen2Generator:
             _lib.check(_lib.beam_lib().fvhd_llm_cache_gather(self.pre._h, _lib.ptr(src_rows), int(rows_in), rows_out, _lib.stream_ptr(self.device)),
                        "fvhd_llm_cache_gather")
         self._run_batch = rows_out
+        self._ids_stale = True
 
     @torch.no_grad()
     def beam_topk(self, logits: torch.Tensor, beam_scores: torch.Tensor, keep: int, out_scores: torch.Tensor, out_index: torch.Tensor) -> None:
@@ -294,6 +311,7 @@ class Qwen2Generator:
             raise ValueError(f"drafts must be a contiguous 1-D int64 tensor on {self.device}")
         T = drafts.shape[0] + 1
         self._verify_refusal("verify", T)
+        self._stale_ids_refusal("verify")
         if self._spec_rows < T:
             raise ValueError(f"verify: {T} rows exceed the rows this generator reserved with spec_reserve ({self._spec_rows or 'none'})")
         if logits and self._spec_logits is None:

@@ -1,0 +1,276 @@
+"""TEST INFRASTRUCTURE ONLY - a host model of the state the Qwen2 cache calls share (include/fvhd.h "LLM decode", "LLM beam search",
+"LLM speculative verification", "LLM extend"; DESIGN.md "orders of cache calls").  It restates what the header promises about the state
+and holds nothing about kernels: a slot is the embedding row that was fed into it plus a valid bit, and the logits of an op are whatever a
+from-scratch forward of `flat(row)` gives.  The ids an op chooses are an INPUT of every method (`ids_returned`: what the library, or any
+other implementation under test, returned) - the model never computes a logit.
+
+State per row: slots [0, length) (embedding row + valid bit), the next position, the last chosen id.
+State per context: the run batch, `length`, the sticky error word (0 fine, 1 past capacity, 2 token id out of range, 3 reorder index out of
+range, 4 rewind keep out of range), "ids stale" (a reorder / rewind since the ids were chosen), and the open lookup generation (token
+buffer, tokens written, finished, steps, tokens).
+
+Every method mirrors one call.  It raises `Refused` where the HOST refuses (the message names the reason as the library's does), returns
+False where the device word is already set or gets set (nothing changes: everything is frozen until `start`), True where the op ran.
+
+PINNING: tests/test_cache_model.py checks `flat()` against transformers' own incremental forward with past_key_values, op by op, and the
+accept / draft / error-word bookkeeping against hand-made cases."""
+from __future__ import annotations
+
+import torch
+
+from extend_reference import rewind_model
+from ml_fastvlm_amd.prompt_lookup import propose
+
+MAX_VERIFY_ROWS = 16
+STALE = "the ids the previous step chose belong to the rows as they were before the cache reorder / rewind"
+
+
+class Refused(Exception):
+    """the host refuses the call: nothing is enqueued, no state and no flag changes"""
+
+
+class CacheModel:
+    def __init__(self, batch: int, capacity: int, table: torch.Tensor):
+        """table: the embedding table [vocab, hidden] through which fed ids become slots (the oracle's own, fp32)"""
+        self.batch, self.capacity = int(batch), int(capacity)
+        self.table = table.detach().float().cpu()
+        self.vocab, self.hidden = self.table.shape
+        self.emb = torch.zeros(self.batch, self.capacity, self.hidden)
+        self.mask = torch.zeros(self.batch, self.capacity, dtype=torch.uint8)
+        self.pos = torch.zeros(self.batch, dtype=torch.long)
+        self.last = [None] * self.batch
+        self.run_batch = self.length = self.error = 0
+        self.ids_stale = False
+        self.lookup = None                     # dict(buffer, out, written, finished, steps, tokens, limit, eos) while a generation is open
+
+    # ---- helpers -----------------------------------------------------------------------------------------------------------------------
+    def state(self):
+        """what fvhd_llm_cache_state reports"""
+        return self.length, self.error
+
+    def _started(self, who):
+        if not self.run_batch:
+            raise Refused(f"{who}: no started sequence")
+
+    def _pending(self, who):
+        """the sticky word in front of a call: either the host refuses or the launches do nothing - the state is the same"""
+        return self.error != 0
+
+    def _stale(self, who):
+        if self.ids_stale:
+            raise Refused(f"{who}: {STALE} - continue with extend, or with a step on explicit ids")
+
+    def _ids(self, ids, n):
+        ids = [int(i) for i in (ids.tolist() if isinstance(ids, torch.Tensor) else ids)]
+        assert len(ids) == n, (len(ids), n)
+        return ids
+
+    # ---- start / step / extend ---------------------------------------------------------------------------------------------------------
+    def start(self, embeds, mask, ids_returned):
+        """fvhd_llm_start with generate's own position ids (cumsum(mask) - 1, 0 on padding): slots [0, T), length = T, next position =
+        the last column's position + 1, the error word cleared, every host flag reset"""
+        B, T = embeds.shape[:2]
+        if not (1 <= B <= self.batch and 1 <= T <= self.capacity):
+            raise Refused("start: batch / length exceed the reserved cache")
+        m = torch.ones(B, T, dtype=torch.uint8) if mask is None else (mask != 0).to(torch.uint8).cpu()
+        self.mask.zero_()
+        self.mask[:B, :T] = m
+        self.emb[:B, :T] = embeds.detach().float().cpu()
+        pos = (m.long().cumsum(-1) - 1).masked_fill(m == 0, 0)
+        self.pos[:B] = pos[:, -1] + 1
+        self.last[:B] = self._ids(ids_returned, B)
+        self.run_batch, self.length, self.error = B, T, 0
+        self.ids_stale, self.lookup = False, None
+        return True
+
+    def step(self, ids, ids_returned):
+        """fvhd_llm_decode: ids None = the last chosen ids (refused while they are stale)"""
+        self._started("step")
+        if ids is None:
+            self._stale("step(ids = None)")
+        if self._pending("step"):
+            return False
+        B = self.run_batch
+        fed = self.last[:B] if ids is None else self._ids(ids, B)
+        self.lookup = None
+        if ids is not None:
+            self.ids_stale = False
+        if self.length >= self.capacity:
+            self.error = 1
+            return False
+        if any(i is None or i < 0 or i >= self.vocab for i in fed):
+            self.error = 2
+            return False
+        L = self.length
+        self.emb[:B, L] = self.table[torch.tensor(fed)]
+        self.mask[:B, L] = 1
+        self.pos[:B] += 1
+        self.length = L + 1
+        self.last[:B] = self._ids(ids_returned, B)
+        return True
+
+    def extend(self, chunk, chunk_mask, ids_returned):
+        """fvhd_llm_extend without position ids: every row continues from its next position over its valid chunk tokens"""
+        self._started("extend")
+        B, T = self.run_batch, chunk.shape[1]
+        if chunk.shape[0] != B:
+            raise Refused(f"extend: the chunk has {chunk.shape[0]} rows, the started batch is {B}")
+        if T < 1 or T > self.capacity:
+            raise Refused(f"extend: the chunk length {T} must be in [1, capacity]")
+        if self._pending("extend"):
+            return False
+        self.lookup, self.ids_stale = None, False
+        if self.length + T > self.capacity:
+            self.error = 1
+            return False
+        m = torch.ones(B, T, dtype=torch.uint8) if chunk_mask is None else (chunk_mask != 0).to(torch.uint8).cpu()
+        L = self.length
+        self.emb[:B, L:L + T] = chunk.detach().float().cpu()
+        self.mask[:B, L:L + T] = m
+        self.pos[:B] += m[:, :T - 1].long().sum(-1) + 1           # the position of the chunk's last token + 1
+        self.length = L + T
+        self.last[:B] = self._ids(ids_returned, B)
+        return True
+
+    # ---- rewind / gather ---------------------------------------------------------------------------------------------------------------
+    def rewind(self, keep):
+        """fvhd_llm_cache_rewind (extend_reference.rewind_model): the embeddings behind keep[b] stay where they are, invisible"""
+        self._started("rewind")
+        B = self.run_batch
+        keep = self._ids(keep, B)
+        if self._pending("rewind"):
+            return False
+        self.lookup, self.ids_stale = None, True
+        mask, pos, length, err = rewind_model(self.mask[:B], self.pos[:B], self.length, keep)
+        if err:
+            self.error = err
+            return False
+        self.mask[:B], self.pos[:B], self.length = mask, pos, length
+        return True
+
+    def gather(self, src, rows_in):
+        """fvhd_llm_cache_gather: new row r = old row src[r] over slots [0, length) - embeddings, mask, next position; NOT the last ids"""
+        self._started("gather")
+        src = [int(s) for s in (src.tolist() if isinstance(src, torch.Tensor) else src)]
+        rows_out = len(src)
+        if not (1 <= rows_in <= self.batch and 1 <= rows_out <= self.batch):
+            raise Refused("gather: rows_in and rows_out must be in [1, the reserved batch]")
+        if self._pending("gather"):
+            return False
+        self.run_batch = rows_out
+        self.lookup, self.ids_stale = None, True
+        if any(s < 0 or s >= rows_in for s in src):
+            self.error = 3
+            return False
+        L, idx = self.length, torch.tensor(src)
+        self.emb[:rows_out, :L] = self.emb[idx, :L]
+        self.mask[:rows_out, :L] = self.mask[idx, :L]
+        self.pos[:rows_out] = self.pos[idx]
+        return True
+
+    # ---- verify / lookup ---------------------------------------------------------------------------------------------------------------
+    def _spec_refusal(self, who, rows):
+        self._started(who)
+        if self.run_batch != 1:
+            raise Refused(f"{who}: the verify step takes ONE sequence")
+        if not 2 <= rows <= MAX_VERIFY_ROWS:
+            raise Refused(f"{who}: rows must be in [2, {MAX_VERIFY_ROWS}]")
+        self._stale(who)
+
+    def _accept(self, drafts, ids, cut=None):
+        """the T rows of one verify step on the one sequence -> emitted count, or 0 when the error word stopped it.  ids[i] needs to be
+        right only up to the first rejected draft (the rows behind it are never read).  cut(e, ids) -> e: the lookup's EOS / limit cut"""
+        T, L = len(drafts) + 1, self.length
+        if L + T > self.capacity:
+            self.error = 1
+            return 0
+        fed = [self.last[0]] + list(drafts)
+        if any(i is None or i < 0 or i >= self.vocab for i in fed):
+            self.error = 2
+            return 0
+        n = 0
+        while n < T - 1 and drafts[n] == ids[n]:
+            n += 1
+        e = n + 1
+        if cut is not None:
+            e = cut(e, ids)
+        self.emb[0, L:L + T] = self.table[torch.tensor(fed)]      # the k / v of rejected drafts stay above the length, invisible
+        self.mask[0, L:L + e] = 1
+        self.mask[0, L + e:L + T] = 0
+        self.pos[0] += e
+        self.length = L + e
+        self.last[0] = int(ids[e - 1])
+        return e
+
+    def verify(self, drafts, ids_returned):
+        """fvhd_llm_verify -> the emitted count (0: the error word stopped the step)"""
+        drafts = self._ids(drafts, len(drafts))
+        self._spec_refusal("verify", len(drafts) + 1)
+        if self._pending("verify"):
+            return 0
+        self.lookup = None
+        return self._accept(drafts, self._ids(ids_returned, len(ids_returned)))
+
+    def lookup_begin(self, lookup_ids, eos_ids, max_new_tokens):
+        self._spec_refusal("lookup_begin", 2)
+        if max_new_tokens < 1:
+            raise Refused("lookup_begin: max_new_tokens must be >= 1")
+        look = [] if lookup_ids is None else self._ids(lookup_ids, len(lookup_ids))
+        eos = [int(e) for e in (eos_ids or [])]
+        first = self.last[0]
+        self.lookup = dict(buffer=look + [first], out=[first], written=1, finished=max_new_tokens <= 1 or first in eos, steps=0, tokens=0,
+                           limit=int(max_new_tokens), eos=eos)
+        return True
+
+    def lookup_drafts(self, rows, max_ngram):
+        """the drafts the next lookup step will verify (prompt_lookup.propose on the token buffer)"""
+        return propose(self.lookup["buffer"], max_ngram, rows - 1)
+
+    def lookup_step(self, rows, max_ngram, ids_returned):
+        """fvhd_llm_lookup_step -> the emitted count (0: finished, or the error word stopped it)"""
+        self._spec_refusal("lookup_step", rows)
+        if self.lookup is None:
+            raise Refused("lookup_step: no token buffer - lookup_begin after start")
+        g = self.lookup
+        if self._pending("lookup_step") or g["finished"]:
+            return 0
+        drafts = self.lookup_drafts(rows, max_ngram)
+
+        def cut(e, ids):
+            for i in range(e):
+                if int(ids[i]) in g["eos"]:
+                    e, g["finished"] = i + 1, True
+                    break
+            room = max(g["limit"] - g["written"], 1)
+            if e >= room:
+                e, g["finished"] = room, True
+            return e
+
+        ids = self._ids(ids_returned, len(ids_returned))
+        e = self._accept(drafts, ids, cut)
+        if e:
+            g["buffer"] += ids[:e]
+            g["out"] += ids[:e]
+            g["written"] += e
+            g["steps"] += 1
+            g["tokens"] += e
+        return e
+
+    def lookup_state(self):
+        g = self.lookup
+        return g["written"], g["finished"], g["steps"], g["tokens"]
+
+    # ---- what a from-scratch forward needs ---------------------------------------------------------------------------------------------
+    def defined(self, row):
+        """the logits of the op that just ran are those of the LAST slot's query: a row whose last slot is invalid has none"""
+        return self.length > 0 and bool(self.mask[row, self.length - 1])
+
+    def flat(self, row):
+        """-> dict(inputs_embeds [1, length, hidden], attention_mask [1, length] (holes included), position_ids [1, length] = cumsum(mask) - 1
+        (0 on invalid slots), defined).  The last-position logits of a forward on these are the expected logits of the op that just ran.
+        Asserts the row's next position is the number of its valid slots: that is what makes cumsum(mask) - 1 the row's positions."""
+        L = self.length
+        m = self.mask[row, :L].long()
+        assert int(self.pos[row]) == int(m.sum()), f"row {row}: next position {int(self.pos[row])}, {int(m.sum())} valid slots"
+        pos = (m.cumsum(-1) - 1).masked_fill(m == 0, 0)
+        return dict(inputs_embeds=self.emb[row, :L][None].clone(), attention_mask=m[None], position_ids=pos[None], defined=self.defined(row))
