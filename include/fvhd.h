@@ -68,7 +68,9 @@ typedef void* fvhd_stream_t; /* hipStream_t */
  * symbol: behind fvhd_llm_cache_rewind / fvhd_llm_cache_gather the calls that would feed the ids "the previous step chose"
  * (fvhd_llm_decode(token_ids = NULL), fvhd_llm_verify, fvhd_llm_lookup_begin / _step) are refused until fvhd_llm_start, fvhd_llm_extend or a
  * fvhd_llm_decode on explicit token_ids, and fvhd_llm_decode, fvhd_llm_verify and fvhd_llm_cache_gather end a lookup generation; every call
- * that is accepted enqueues what 509 did, launch for launch and bit for bit. */
+ * that is accepted enqueues what 509 did, launch for launch and bit for bit.  Added under 510 (new symbols only, the number stays): scoring
+ * given tokens - fvhd_lm_score_scratch_bytes, fvhd_lm_score_plan, fvhd_op_lm_score, fvhd_llm_score_reserve, fvhd_llm_score; every existing
+ * call enqueues what it did and fvhd_llm_reserve allocates what it did. */
 #define FVHD_VERSION 510
 int fvhd_version(void);
 const char* fvhd_last_error(void);
@@ -775,6 +777,38 @@ int fvhd_op_cache_append(fvhd_stream_t stream, const void* qkv, void* k_cache, v
 int fvhd_op_extend_positions(fvhd_stream_t stream, const int64_t* next_positions, const uint8_t* chunk_valid, int64_t* pos_out, int B, int T);
 int fvhd_op_cache_rewind(fvhd_stream_t stream, const int32_t* keep, int rows, uint8_t* key_valid, int64_t* positions, int capacity, int* length,
                          int* status);
+
+/* ---- LLM scoring: the log-probability of GIVEN tokens at every position (added under 510) -------------------------------------------------------
+ * fvhd_llm_prefill / _start / _extend project only the last position of every row through lm_head.  Scoring - transformers'
+ * forward(labels=...), multiple-choice answers by likelihood, perplexity of a caption - needs log p(target | prefix) at EVERY position:
+ *     z = xn . W^T (16x16x32 bf16 MFMA, fp32 accumulation)     lse[m] = log sum_v exp(z[m][v])     logprob[m] = z[m][target[m]] - lse[m]
+ * in one kernel that never materialises [rows, vocab] (llm_score.hip): a workgroup owns 128 rows and walks one of S segments of the vocabulary
+ * with an online softmax per row (running max: logits of magnitude 1e4 give finite results), a small second launch combines the S segment
+ * states of a row in segment order.  Scratch: 16 bytes per (row, segment), not initialised by the caller.
+ * Shapes: M >= 1 (rows past M are neither read as valid nor written), V % 8 == 0 (V need not be a multiple of the 128-column tile: columns
+ * >= V enter neither the max nor the sum), K % 32 == 0; anything else is refused with a message.
+ * target < 0 (transformers' ignore label is -100): logprob = 0.0 exactly, lse is still written.  target >= V: logprob = NaN (no status word).
+ * Otherwise the target logit is the very fp32 value that entered the sum, so logprob <= 0 up to the rounding of the log.
+ * Bits: the same launch gives the same bits; a row's lse and logprob depend neither on the other rows' contents nor on any target but its
+ * own (lse on none); they may depend on (M, V, K) through the plan: fvhd_lm_score_plan returns S (0: the shape is refused). */
+size_t fvhd_lm_score_scratch_bytes(int M, int V, int K);
+int fvhd_lm_score_plan(int M, int V, int K);
+/* xn [M][K] bf16 (rows after the final RMSNorm), Wt [V][K] bf16 (lm_head as stored), targets int64 [M] -> logprob_out fp32 [M], lse_out fp32
+ * [M] or NULL.  All pointers on the device, xn / Wt / scratch aligned to 16 bytes; scratch_bytes >= fvhd_lm_score_scratch_bytes(M, V, K). */
+int fvhd_op_lm_score(fvhd_stream_t stream, const void* xn, const void* Wt, const int64_t* targets, int M, int V, int K, float* logprob_out,
+                     float* lse_out, void* scratch, size_t scratch_bytes);
+/* On a context: scores the rows of the LAST fvhd_llm_prefill / fvhd_llm_start / fvhd_llm_extend of this context, whose final hidden states
+ * are still in its workspace: the final RMSNorm of all batch * T rows, lm_head (an e4m3 context dequantises it into its scratch first, as
+ * the stack does), the score launches.  target_ids int64 [batch][T] on the device: target_ids[b][t] is the id whose probability under the
+ * distribution predicted at position t is wanted - the caller shifts.  logprob_out fp32 [batch][T], lse_out NULL or fp32 [batch][T].
+ * The score scratch is an allocation of its own that grows on demand; fvhd_llm_score_reserve(rows) sizes it for rows = batch * T ahead
+ * (growing it synchronises the device: like fvhd_llm_reserve it then fails with a message while a stream is being captured, and the
+ * failed synchronise invalidates that capture - reserve before capturing; a reserve that finds the scratch large enough does nothing
+ * and is allowed at any time), after which fvhd_llm_score enqueues without a host synchronisation and is
+ * capture-safe; a scratch that a capturing stream used is retired, not freed, when it must grow.  Refused, each with a message: no stack
+ * call yet on the current workspace (a stack call that failed part-way leaves none), capture without a sufficient reserve, NULL targets or output. */
+int fvhd_llm_score_reserve(fvhd_llm* ctx, int rows);
+int fvhd_llm_score(fvhd_llm* ctx, const int64_t* target_ids, float* logprob_out, float* lse_out, fvhd_stream_t stream);
 
 #ifdef __cplusplus
 }

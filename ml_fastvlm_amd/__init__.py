@@ -6,15 +6,16 @@ Public surface (mirrors `llava.model.multimodal_encoder` / `multimodal_projector
     install_into_llava, `generate` (greedy generation with the Qwen2 prefill and decode steps on the library's kernels),
     `beam_generate` (the same with beam search; `BeamSearchState` is its bookkeeping), `GenerationSession` (multi-turn generation that extends the
     KV cache by each turn's tokens instead of prefilling the dialogue again), `process_reference` (the decode step's logits
-    processors restated in plain torch), and
+    processors restated in plain torch), `score` (the log-likelihood of given tokens, `forward(labels=...)` per sequence, with lm_head and the
+    log-softmax fused in one kernel; `GenerationSession.score` ranks candidate answers behind one prefilled image), and
     `distributed` for the one-process-per-GPU data-parallel path.
 """
 from .beam import BeamSearchState  # noqa: F401
-from .builder import GenerationSession, beam_generate, build_vision_projector, build_vision_tower, encode_images, generate, install_into_llava, library_projector, project  # noqa: F401
+from .builder import GenerationSession, beam_generate, build_vision_projector, build_vision_tower, encode_images, generate, install_into_llava, library_projector, project, score  # noqa: F401
 from .logits_processors import process_reference  # noqa: F401
 from .mobileclip_encoder import MobileCLIPVisionTower, load_model_config  # noqa: F401
 from .qwen2_prefill import quantize_rows_e4m3  # noqa: F401
 
 __all__ = ["MobileCLIPVisionTower", "build_vision_tower", "build_vision_projector", "encode_images", "project",
            "library_projector", "install_into_llava", "load_model_config", "generate", "quantize_rows_e4m3", "beam_generate", "BeamSearchState",
-           "process_reference", "GenerationSession"]
+           "process_reference", "GenerationSession", "score"]

@@ -170,6 +170,14 @@ def _declare(lib) -> None:
             "fvhd_op_extend_positions": (ci, [vp, vp, vp, vp, ci, ci]),
             "fvhd_op_cache_rewind": (ci, [vp, vp, ci, vp, vp, ci, vp, vp]),
         })
+    if hasattr(lib, "fvhd_op_lm_score"):           # added under 510: a 510 library built before them loads without; score_lib() then names the rebuild
+        sig.update({
+            "fvhd_lm_score_scratch_bytes": (C.c_size_t, [ci, ci, ci]),
+            "fvhd_lm_score_plan": (ci, [ci, ci, ci]),
+            "fvhd_op_lm_score": (ci, [vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, C.c_size_t]),
+            "fvhd_llm_score_reserve": (ci, [vp, ci]),
+            "fvhd_llm_score": (ci, [vp, vp, vp, vp, vp]),
+        })
     del fp, cl
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)     # AttributeError here = the .so does not export what fvhd.h declares
@@ -272,6 +280,16 @@ def extend_lib():
     if got < EXTEND_VERSION:
         raise FvhdError(f"{LIB_PATH} reports ABI version {got}: extending a started cache (fvhd_llm_extend, fvhd_llm_cache_rewind, "
                         f"fvhd_op_attention_extend, ...) needs {EXTEND_VERSION} - rebuild the library (`python -m ml_fastvlm_amd.build`)")
+    return lib
+
+
+def score_lib():
+    """load(), for scoring given tokens (fvhd_llm_score, fvhd_op_lm_score, ...): the entry points were added under FVHD_VERSION 510, so a
+    library built before them reports the same number and loads; this says so instead of an AttributeError."""
+    lib = load()
+    if not hasattr(lib, "fvhd_op_lm_score"):
+        raise FvhdError(f"{LIB_PATH} (ABI version {lib.fvhd_version()}) was built before scoring (fvhd_llm_score, fvhd_llm_score_reserve, "
+                        "fvhd_op_lm_score, ...) - rebuild the library (`python -m ml_fastvlm_amd.build`)")
     return lib
 
 

@@ -406,6 +406,74 @@ def session_keep(length_before_decode: int, tokens, eos_token_id=None):
     return keep, torch.tensor(pending, dtype=torch.long)
 
 
+def session_score_chunk(pending, input_ids, continuation_ids, continuation_mask=None, pad_token_id: int = 0):
+    """The chunk `GenerationSession.score` extends the cache by: row b = [left padding | pending_b | input_ids_b | its
+    continuation] -> (ids int64 [B, L], mask int64 [B, L], labels int64 [B, L], where int64 [B, c]), L = 1 + n + the longest continuation.
+    The padding is on the LEFT, as in `session_chunk`: an extend takes every row's next position from the chunk's last column, so a chunk
+    that ended in padding would leave the row one position too far.  labels is
+    -100 except at a row's continuation tokens, where it is the token itself (transformers' `labels` convention: `score_targets` shifts
+    it); where[b][j] = the chunk column of continuation token j of row b, -1 where continuation_mask is 0.  input_ids: [B, n] real
+    tokens (n may be 0) or None; continuation_ids [B, c] with continuation_mask [B, c] or None (1 = a real token, order kept)."""
+    B, c = continuation_ids.shape
+    if tuple(pending.shape) != (B,):
+        raise ValueError(f"this call has {B} rows, the session holds {pending.shape[0]} (one continuation per started sequence)")
+    if input_ids is None:
+        input_ids = continuation_ids.new_zeros((B, 0))
+    if input_ids.dim() != 2 or input_ids.shape[0] != B:
+        raise ValueError(f"input_ids must be [B, n] with B = {B}, got {tuple(input_ids.shape)}")
+    keep = torch.ones_like(continuation_ids, dtype=torch.bool) if continuation_mask is None else continuation_mask.to(continuation_ids.device) != 0
+    if tuple(keep.shape) != (B, c):
+        raise ValueError(f"continuation_mask must be [B, c] = {(B, c)}, got {tuple(keep.shape)}")
+    n = input_ids.shape[1]
+    counts = keep.sum(1)
+    if int(counts.min()) < 1:
+        raise ValueError("every row needs at least one continuation token")
+    L = 1 + n + int(counts.max())
+    dev = continuation_ids.device
+    ids = torch.full((B, L), int(pad_token_id), dtype=torch.long, device=dev)
+    mask = torch.zeros((B, L), dtype=torch.long, device=dev)
+    labels = torch.full((B, L), -100, dtype=torch.long, device=dev)
+    where = torch.full((B, c), -1, dtype=torch.long, device=dev)
+    for b in range(B):
+        k = int(counts[b])
+        o = L - (1 + n + k)
+        ids[b, o] = pending[b]
+        ids[b, o + 1:o + 1 + n] = input_ids[b]
+        ids[b, L - k:] = continuation_ids[b][keep[b]]
+        labels[b, L - k:] = continuation_ids[b][keep[b]]
+        mask[b, o:] = 1
+        where[b][keep[b]] = torch.arange(L - k, L, device=dev)
+    return ids, mask, labels, where
+
+
+@torch.no_grad()
+def score(model, input_ids, labels, images=None, image_sizes=None, attention_mask=None, weights=None):
+    """The log-likelihood of GIVEN tokens - `LlavaQwen2ForCausalLM.forward(labels=...)` per sequence, on the library: the multimodal splice
+    (with images, `prepare_inputs_labels_for_multimodal` returns the labels aligned with the spliced embeds) or the token embedding, the
+    prefill, then lm_head with the log-softmax and the pick of the label fused in one kernel on every position (`Qwen2Prefill.score`; no
+    [B * T, vocab] logits).  labels [B, T]: aligned with input_ids, -100 = not scored, shifted inside as transformers does ->
+    {"sum_logprob": fp32 [B], "tokens": int64 [B] (scored tokens), "token_logprobs": fp32 [B, T'] (T' = the spliced length)}.
+    -sum_logprob / tokens is the reference's `.loss` of each sequence.  The model must be bf16 on a HIP device."""
+    from .qwen2_prefill import label_aligned, score_targets
+    lm_w = model.lm_head.weight
+    if lm_w.device.type != "cuda" or lm_w.dtype != torch.bfloat16:
+        raise ValueError(f"ml_fastvlm_amd.score: needs a bf16 model on a HIP device (got {lm_w.dtype} on {lm_w.device}); the kernels compute in bf16")
+    if labels is None or tuple(labels.shape) != tuple(input_ids.shape):
+        raise ValueError(f"ml_fastvlm_amd.score: labels must be aligned with input_ids {tuple(input_ids.shape)}")
+    position_ids = None
+    if images is not None:
+        (_, position_ids, attention_mask, _, embeds, labels) = model.prepare_inputs_labels_for_multimodal(
+            input_ids, None, attention_mask, None, labels, images, image_sizes=image_sizes)
+    else:
+        embeds = model.get_input_embeddings()(input_ids.to(lm_w.device))
+    pre = prefill_context(model, weights)
+    labels = labels.to(lm_w.device)
+    mask = None if attention_mask is None else attention_mask.to(lm_w.device)
+    token_logprobs, _ = pre.score(embeds, labels, mask, position_ids)
+    scored = label_aligned(score_targets(labels, mask) >= 0)
+    return {"sum_logprob": token_logprobs.sum(1), "tokens": scored.sum(1), "token_logprobs": token_logprobs}
+
+
 class GenerationSession:
     """Multi-turn generation of a (Llava)Qwen2ForCausalLM on ONE KV cache: the first `generate` is `ml_fastvlm_amd.generate` (splice or
     embedding, prefill, decode); every later one embeds only the turn's own tokens, EXTENDS the cache by them (`Qwen2Generator.extend`) and
@@ -507,6 +575,33 @@ class GenerationSession:
         gen.rewind(keep)
         gen._session = self                                      # start() clears it: whoever starts the cache again ends this dialogue
         return tokens
+
+    @torch.no_grad()
+    def score(self, input_ids, continuation_ids, continuation_mask=None):
+        """How likely is each row's continuation?  Per row the cache is extended by [pending | input_ids | continuation] (shorter rows
+        padded on the left through the chunk mask; `session_score_chunk`), the continuation positions are scored (`Qwen2Generator.score_last`) and the
+        cache is rewound to the length it had: the dialogue, the pending tokens and what the next generate() produces are untouched.
+        input_ids [rows, n] (the same number of real tokens in every row; None = nothing between the dialogue and the continuation),
+        continuation_ids [rows, c] with continuation_mask [rows, c] or None -> (sum_logprob fp32 [rows], token_logprobs fp32 [rows, c],
+        0 where the mask is 0).  After `fork(n)`: one image, n candidate answers, which is likeliest - in ONE extend."""
+        if self._pending is None:
+            raise ValueError("GenerationSession.score: the session has no started rows - generate() a first turn (the prompt) before scoring")
+        model = self.model
+        dev = model.lm_head.weight.device
+        ids, mask, labels, where = session_score_chunk(self._pending.to(continuation_ids.device), input_ids, continuation_ids, continuation_mask)
+        gen = self._generator()
+        before = gen.length()
+        if before + ids.shape[1] > gen.capacity:
+            raise ValueError(f"GenerationSession.score: {before} cached slots + a chunk of {ids.shape[1]} exceed the capacity {gen.capacity}")
+        embeds = model.get_input_embeddings()(ids.to(dev))
+        gen.extend(embeds, mask.to(dev), None, logits=False)
+        token_logprobs, _ = gen.score_last(labels.to(dev))
+        gen.rewind([before] * self.rows)
+        gen._session = self
+        where = where.to(dev)
+        picked = torch.gather(token_logprobs, 1, where.clamp_min(0))
+        picked = torch.where(where >= 0, picked, torch.zeros_like(picked))
+        return picked.sum(1), picked
 
 
 # GenerationConfig fields whose value (beside None) means "this processor / mode is off"; any other value is a setting the library does

@@ -105,6 +105,8 @@ int fvhd_launch_spec_attention(hipStream_t st, const void* q, void* kc, void* vc
 int fvhd_launch_spec_accept(hipStream_t st, const SpecAcceptArgs* a);
 int fvhd_launch_spec_begin(hipStream_t st, const int64_t* lookup, int n, const int64_t* last, int* seq, int64_t* out, int* words, int limit,
                            const SpecEosList* eos);
+// llm_score.hip (the shape is valid when fvhd_lm_score_plan(M, V, K) != 0; scratch: fvhd_lm_score_scratch_bytes, 16-byte aligned)
+int fvhd_launch_lm_score(hipStream_t st, const void* xn, const void* Wt, const int64_t* target, int M, int V, int K, float* logprob, float* lse, void* scratch);
 // llm_logits.hip
 int fvhd_launch_dec_logits_process(hipStream_t st, const DecLogitsArgs* a);
 int fvhd_launch_dec_logits_history(hipStream_t st, const int* tokens, int* hist, unsigned* seen, int B, int V, int cap, int g);

@@ -108,6 +108,13 @@ struct __attribute__((visibility("default"))) fvhd_llm {     // (its inline cons
     // before the call.  Cleared by fvhd_llm_start, fvhd_llm_extend and fvhd_llm_decode with explicit token_ids; while it is set every call
     // that would feed last_ids is refused when it enqueues (a captured step replays as captured)
     bool ids_stale = false;
+    // fvhd_llm_score (llm_prefill.hip): what the last decoder_stack() call left in `h` - its (batch, T) and the workspace generation it ran
+    // on (a workspace replaced since holds no rows) - and the score launch's scratch: an allocation of its own that grows on demand
+    // (fvhd_llm_score_reserve); one that a capturing stream used is retired when it must grow, like the workspace
+    int last_batch = 0, last_T = 0, last_gen = -1;
+    char* score_ws = nullptr;
+    size_t score_bytes = 0;
+    bool score_captured = false;
 };
 
 inline bool processors_on(const fvhd_llm* c)

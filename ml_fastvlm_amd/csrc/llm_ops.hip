@@ -103,6 +103,21 @@ int fvhd_op_cache_rewind(fvhd_stream_t st, const int32_t* keep, int rows, uint8_
     return lret("fvhd_op_cache_rewind", fvhd_launch_llm_cache_rewind((hipStream_t)st, keep, rows, key_valid, positions, capacity, length, status, nullptr));
 }
 
+// ---- scoring given tokens (llm_score.hip) ----
+int fvhd_op_lm_score(fvhd_stream_t st, const void* xn, const void* Wt, const int64_t* targets, int M, int V, int K, float* logprob_out, float* lse_out,
+                     void* scratch, size_t scratch_bytes)
+{
+    if (!xn || !Wt || !targets || !logprob_out || !scratch) return lfail("fvhd_op_lm_score: NULL pointer");
+    if (M < 1) return lfail("fvhd_op_lm_score: needs M >= 1");
+    if (V < 8 || V % 8) return lfail("fvhd_op_lm_score: the vocabulary V = " + std::to_string(V) + " must be a positive multiple of 8 (V % 8 == 0)");
+    if (K < 32 || K % 32) return lfail("fvhd_op_lm_score: the hidden size K = " + std::to_string(K) + " must be a positive multiple of 32 (K % 32 == 0)");
+    if (((uintptr_t)xn & 15) || ((uintptr_t)Wt & 15) || ((uintptr_t)scratch & 15)) return lfail("fvhd_op_lm_score: xn, Wt and scratch must be aligned to 16 bytes");
+    const size_t need = fvhd_lm_score_scratch_bytes(M, V, K);
+    if (scratch_bytes < need)
+        return lfail("fvhd_op_lm_score: scratch too small: " + std::to_string(scratch_bytes) + " bytes, fvhd_lm_score_scratch_bytes(M, V, K) = " + std::to_string(need));
+    return lret("fvhd_op_lm_score", fvhd_launch_lm_score((hipStream_t)st, xn, Wt, targets, M, V, K, logprob_out, lse_out, scratch));
+}
+
 // ---- single ops of the decode step (unit tests) ----
 // One builder per epilogue family fills DecGemmArgs; `scale` is NULL for a bf16 matrix, the fp32 row scales of an e4m3 one (the *_w8 entry points)
 static DecGemmArgs dec_args(int epi, const void* x, int B, const float* norm_w, float eps, const void* W, const float* scale, int N, int K, int splits)

@@ -53,6 +53,17 @@ int ensure_ws(fvhd_llm* c, int B, int T, hipStream_t st, bool check_capture)
     return e == hipSuccess ? 0 : lhip("hipMemcpy(rope table)", e);
 }
 
+// The matrix a GEMM reads: the packed bf16 weights, or - e4m3 - the bf16 scratch the codes are dequantised into right before it (1 byte in,
+// 2 bytes out per element; the GEMMs run one after the other on `st`, so one scratch of the largest matrix serves them all).  One function
+// for the decoder stack and for fvhd_llm_score.
+static int stack_weights(fvhd_llm* c, hipStream_t st, int layer, int matrix, const void** p)
+{
+    const Mat m = mat_of(c, layer, matrix);
+    if (c->wfmt != FVHD_W_E4M3) { *p = c->wdev + m.off; return 0; }
+    *p = c->wscratch;
+    return fvhd_launch_w8_unpack(st, c->wdev + m.off, (const float*)(c->wdev + m.soff), c->wscratch, m.N, m.K, 0);
+}
+
 // The decoder stack of fvhd_llm_prefill and of fvhd_llm_extend (llm_step.hip) - ONE launch sequence: the GEMMs, their split-K choices, the
 // fused norms and the e4m3 dequantise-into-scratch path are the same in both.  extend = false is the prefill, launch for launch what it
 // always ran.  extend = true continues the context's started cache: key_valid is the CHUNK's mask [batch][seq_len], the rotary embedding
@@ -64,6 +75,7 @@ int decoder_stack(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* key
                   float* logits_out, void* k_cache, void* v_cache, hipStream_t st, bool extend)
 {
     LLM_ON_DEVICE(c);
+    c->last_batch = 0;                          // fvhd_llm_score: from here on c->h is being rewritten; set again when every launch is enqueued
     int e = ensure_ws(c, batch, seq_len, st, true);
     if (e) return e;
     {
@@ -120,14 +132,7 @@ int decoder_stack(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* key
     const int down_sp = pick_splits(H, I, c->down_splits), o_sp = pick_splits(H, nh * hd, c->o_splits);
     // q|k|v projection: split in two, the reduce applies bias + rotary embedding + the KV-cache copies (splitk_bias_rope_kernel)
     const int qkv_sp = pick_splits(c->qkvw, H, std::min(c->qkv_splits, 2));
-    // the matrix a GEMM reads: the packed bf16 weights, or - e4m3 - the bf16 scratch the codes are dequantised into right before it
-    // (1 byte in, 2 bytes out per element; the GEMMs run one after the other on `st`, so one scratch of the largest matrix serves them all)
-    auto weights = [&](int layer, int matrix, const void** p) -> int {
-        const Mat m = mat_of(c, layer, matrix);
-        if (c->wfmt != FVHD_W_E4M3) { *p = w + m.off; return 0; }
-        *p = c->wscratch;
-        return fvhd_launch_w8_unpack(st, w + m.off, (const float*)(w + m.soff), c->wscratch, m.N, m.K, 0);
-    };
+    auto weights = [&](int layer, int matrix, const void** p) -> int { return stack_weights(c, st, layer, matrix, p); };
     const void *wqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wd = nullptr, *wlm = nullptr;
     bool xn_ready = false;                      // c->xn already holds input_layernorm(c->h) of the coming layer
     for (int l = 0; l < c->L; ++l) {
@@ -184,6 +189,40 @@ int decoder_stack(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* key
     LCHECK(fvhd_launch_rmsnorm(st, c->last, c->lastn, (const float*)(w + c->norm_off), B, H, c->eps), "final norm");
     LCHECK(weights(-1, FVHD_MAT_LM_HEAD, &wlm), "dequantise lm_head");
     LCHECK(fvhd_launch_gemm(st, c->lastn, wlm, nullptr, nullptr, nullptr, logits_out, B, c->V, H, FVHD_EPI_NONE, FVHD_F32), "lm_head gemm");
+    c->last_batch = B; c->last_T = T; c->last_gen = c->generation;      // fvhd_llm_score: c->h holds these rows
+    return 0;
+}
+
+// The score scratch for up to `rows` rows: 16 bytes per (row, segment).  S * M is not monotone in M (S falls as the row blocks grow), so the
+// allocation covers every M <= rows: S <= 64, and S <= max(1, 512 / blocks) with M <= 128 blocks.
+static size_t score_bytes_for(int rows)
+{
+    const size_t blocks = ((size_t)rows + 127) / 128;
+    return 16 * std::min((size_t)64 * rows, (size_t)65536 + 128 * blocks);
+}
+
+static int ensure_score_ws(fvhd_llm* c, int rows, hipStream_t st, bool check_capture)
+{
+    const size_t need = score_bytes_for(rows);
+    if (c->score_ws && need <= c->score_bytes) return 0;
+    if (check_capture && is_capturing(st))
+        return lfail("fvhd_llm_score: the score scratch must grow for " + std::to_string(rows) + " rows but the stream is being captured - call "
+                     "fvhd_llm_score_reserve first");
+    hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess)
+        return lfail(std::string(check_capture ? "fvhd_llm_score" : "fvhd_llm_score_reserve") + ": the score scratch must grow, which synchronises the device, "
+                     "and that failed - not allowed while a stream is being captured, reserve before the capture begins (hipDeviceSynchronize: " +
+                     hipGetErrorString(e) + ")");
+    if (c->score_ws) {
+        if (c->score_captured) c->retired.push_back(c->score_ws);      // a caller's graph may still replay on it
+        else (void)hipFree(c->score_ws);
+    }
+    c->score_ws = nullptr;
+    c->score_bytes = 0;
+    c->score_captured = false;
+    e = hipMalloc((void**)&c->score_ws, need);
+    if (e != hipSuccess) return lhip("hipMalloc(llm score scratch)", e);
+    c->score_bytes = need;
     return 0;
 }
 
@@ -214,6 +253,38 @@ int fvhd_llm_prefill(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* 
     if ((k_cache == nullptr) != (v_cache == nullptr)) return lfail("fvhd_llm_prefill: k_cache and v_cache come together");
     if (first_missing_tensor(c) >= 0) return lfail("fvhd_llm_prefill: weights incomplete (fvhd_llm_finalize reports the missing tensor)");
     return decoder_stack(c, embeds, dtype, key_valid, position_ids, batch, seq_len, logits_out, k_cache, v_cache, (hipStream_t)stream, false);
+}
+
+int fvhd_llm_score_reserve(fvhd_llm* c, int rows)
+{
+    if (!c || rows <= 0) return lfail("fvhd_llm_score_reserve: bad argument");
+    LLM_ON_DEVICE(c);
+    if (c->score_ws && score_bytes_for(rows) <= c->score_bytes) return 0;      // nothing to do: allowed at any time
+    // Growing synchronises the device.  The call has no stream to ask about a capture (asking the legacy stream invalidates a capture in
+    // progress on this runtime: tried), so - like fvhd_llm_reserve - it learns of one from the failed synchronise and says so.
+    return ensure_score_ws(c, rows, nullptr, false);
+}
+
+// final norm of ALL rows of the last stack call, lm_head, log-softmax and the pick of the target in one kernel (llm_score.hip)
+int fvhd_llm_score(fvhd_llm* c, const int64_t* target_ids, float* logprob_out, float* lse_out, fvhd_stream_t stream)
+{
+    if (!c) return lfail("fvhd_llm_score: NULL context");
+    if (!target_ids || !logprob_out) return lfail("fvhd_llm_score: NULL targets or output");
+    if (!c->ws || c->last_gen != c->generation || c->last_batch <= 0)
+        return lfail("fvhd_llm_score: no fvhd_llm_prefill / fvhd_llm_start / fvhd_llm_extend has run on the current workspace - there are no rows to score");
+    LLM_ON_DEVICE(c);
+    hipStream_t st = (hipStream_t)stream;
+    const int M = c->last_batch * c->last_T, H = c->H;
+    if (!fvhd_lm_score_plan(M, c->V, H))
+        return lfail("fvhd_llm_score: needs vocab % 8 == 0 and hidden % 32 == 0 (vocab " + std::to_string(c->V) + ", hidden " + std::to_string(H) + ")");
+    if (int e = ensure_score_ws(c, M, st, true)) return e;
+    if (is_capturing(st)) { c->score_captured = true; c->ws_captured = true; }
+    const char* w = c->wdev;
+    LCHECK(fvhd_launch_rmsnorm(st, c->h, c->xn, (const float*)(w + c->norm_off), M, H, c->eps), "final norm (all rows)");
+    const void* wlm = nullptr;
+    LCHECK(stack_weights(c, st, -1, FVHD_MAT_LM_HEAD, &wlm), "dequantise lm_head");
+    LCHECK(fvhd_launch_lm_score(st, c->xn, wlm, target_ids, M, c->V, H, logprob_out, lse_out, c->score_ws), "lm_head score");
+    return 0;
 }
 
 // hidden states after the decoder stack (before the final norm) of the last prefill: [batch * seq_len, hidden] bf16, for tests

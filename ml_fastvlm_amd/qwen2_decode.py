@@ -135,6 +135,9 @@ class Qwen2Generator:
         self._run_batch = B
         self._length = T
         self._ids_stale = False
+        self._last_chunk = self.pre._last_rows = (B, T)          # what score_last may score ...
+        self._last_mask = am                                     # ... under this mask ...
+        self._last_call = self.pre._last_call = object()         # ... while this call is still the context's last stack call
         self._session = None                                     # a GenerationSession's dialogue ends where the cache is started again
         return lg, ids
 
@@ -187,7 +190,27 @@ class Qwen2Generator:
                                                          _lib.ptr(ids), _lib.stream_ptr(self.device)), "fvhd_llm_extend")
         self._length_add(T)
         self._ids_stale = False
+        self._last_chunk = self.pre._last_rows = (B, T)
+        self._last_mask = am
+        self._last_call = self.pre._last_call = object()
         return lg, ids
+
+    @torch.no_grad()
+    def score_last(self, labels: torch.Tensor):
+        """`Qwen2Prefill.score` on the rows of the last start() / extend(), which are still in the context's workspace: labels [B, T]
+        aligned with that call's inputs (-100 = not scored), shifted inside under that call's attention mask -> (token_logprobs fp32
+        [B, T], lse fp32 [B, T]); entry [b][t] = log p(labels[b][t] | the cache before the chunk, chunk tokens < t), 0 at [b][0]: the
+        first token of a chunk is predicted by the call BEFORE it (its logits were that call's return value)."""
+        from .qwen2_prefill import label_aligned, score_targets
+        chunk = getattr(self, "_last_chunk", None)
+        if chunk is None or getattr(self.pre, "_last_call", None) is not self._last_call:
+            raise RuntimeError("Qwen2Generator.score_last: no start() / extend() of this generator is the context's last stack call "
+                               "(a prefill or another generator's call on the same context ran since): its rows and mask are gone")
+        if not isinstance(labels, torch.Tensor) or tuple(labels.shape) != chunk:
+            raise ValueError(f"score_last: labels must be [B, T] = {chunk} (the last start / extend), got "
+                             f"{tuple(labels.shape) if isinstance(labels, torch.Tensor) else type(labels)}")
+        targets = score_targets(labels.to(self.device), self._last_mask)
+        return tuple(label_aligned(t) for t in self.pre.score_rows(targets))
 
     @torch.no_grad()
     def rewind(self, keep) -> None:

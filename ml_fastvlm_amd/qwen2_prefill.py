@@ -206,6 +206,8 @@ class Qwen2Prefill:
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().fvhd_llm_prefill(self._h, _lib.ptr(x), _lib.dtype_code(x.dtype), _lib.ptr(am), _lib.ptr(pos), B, T,
                                                     _lib.ptr(logits), _lib.ptr(kc), _lib.ptr(vc), _lib.stream_ptr(self.device)), "fvhd_llm_prefill")
+        self._last_rows = (B, T)                                 # what score_rows may score ...
+        self._last_call = object()                               # ... and which call left them (a token: `Qwen2Generator.score_last` compares it)
         return (logits, kc, vc) if return_kv else logits
 
     @property
@@ -214,11 +216,79 @@ class Qwen2Prefill:
         kept alive - but only a re-capture uses the new one)"""
         return int(_lib.load().fvhd_llm_workspace_generation(self._h))
 
+    # ---- scoring given tokens -----------------------------------------------------------------------------------------------------
+    def score_reserve(self, rows: int) -> None:
+        """size the score scratch for batch * T = `rows` rows now (growth synchronises the device and is refused during stream capture)"""
+        _lib.check(_lib.score_lib().fvhd_llm_score_reserve(self._h, int(rows)), "fvhd_llm_score_reserve")
+
+    @torch.no_grad()
+    def score_rows(self, targets: torch.Tensor, out: Optional[torch.Tensor] = None, lse_out: Optional[torch.Tensor] = None):
+        """The rows of the LAST prefill / start / extend of this context, still in its workspace (`fvhd_llm_score`): targets int64 [B, T]
+        on the device, targets[b][t] = the id whose probability under the distribution PREDICTED AT position t is wanted (the caller
+        shifts: `score_targets`), negative = ignore -> (logprob fp32 [B, T], lse fp32 [B, T]), both indexed by the predicting position.
+        logprob is 0.0 at an ignored target and NaN at a target >= vocab.  Final norm of all rows, lm_head and the log-softmax in one
+        kernel: no [B * T, vocab] tensor.  out / lse_out: contiguous fp32 [B, T] buffers to write into (a captured call)."""
+        if not isinstance(targets, torch.Tensor) or targets.dim() != 2 or targets.dtype != torch.long:
+            raise ValueError(f"score_rows: targets must be an int64 tensor [B, T], got "
+                             f"{(targets.dtype, tuple(targets.shape)) if isinstance(targets, torch.Tensor) else type(targets)}")
+        want = getattr(self, "_last_rows", None)
+        if want is not None and tuple(targets.shape) != want:
+            raise ValueError(f"score_rows: targets are {tuple(targets.shape)}, the last prefill / start / extend of this context ran [B, T] = {want}")
+        t = targets.to(self.device).contiguous()
+        for name, buf in (("out", out), ("lse_out", lse_out)):
+            if buf is not None and (buf.dtype != torch.float32 or buf.device != self.device or buf.shape != t.shape or not buf.is_contiguous()):
+                raise ValueError(f"score_rows: {name} must be a contiguous fp32 tensor {tuple(t.shape)} on {self.device}")
+        lp = out if out is not None else torch.empty(t.shape, device=self.device, dtype=torch.float32)
+        lse = lse_out if lse_out is not None else torch.empty(t.shape, device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.score_lib().fvhd_llm_score(self._h, _lib.ptr(t), _lib.ptr(lp), _lib.ptr(lse), _lib.stream_ptr(self.device)), "fvhd_llm_score")
+        return lp, lse
+
+    @torch.no_grad()
+    def score(self, inputs_embeds: torch.Tensor, labels: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
+              position_ids: Optional[torch.Tensor] = None):
+        """transformers' `forward(labels=...)` per token: `labels` [B, T] is aligned with the inputs and shifted inside ->
+        (token_logprobs fp32 [B, T], lse fp32 [B, T]); entry [b][t] = log p(labels[b][t] | tokens < t) and the log-sum-exp of the logits
+        it was read from.  token_logprobs is 0 at [b][0], wherever the label is -100 (any negative id) and wherever attention_mask (of the
+        token or of the position before it) is 0; lse[b][0] = 0.  -token_logprobs.sum() / (scored tokens) is the reference's loss."""
+        if not isinstance(labels, torch.Tensor) or labels.dim() != 2 or tuple(labels.shape) != tuple(inputs_embeds.shape[:2]):
+            raise ValueError(f"score: labels must be [B, T] = {tuple(inputs_embeds.shape[:2])}, got "
+                             f"{tuple(labels.shape) if isinstance(labels, torch.Tensor) else type(labels)}")
+        targets = score_targets(labels.to(self.device), None if attention_mask is None else attention_mask.to(self.device))
+        self(inputs_embeds, attention_mask, position_ids)
+        return tuple(label_aligned(t) for t in self.score_rows(targets))
+
     def hidden_states(self, rows: int) -> torch.Tensor:
         """tests: the residual stream after the last decoder layer of the previous prefill, [rows, hidden] bf16"""
         out = torch.empty((rows, self.hidden), device=self.device, dtype=torch.bfloat16)
         _lib.check(_lib.load().fvhd_llm_debug_hidden(self._h, _lib.ptr(out), rows, _lib.stream_ptr(self.device)), "fvhd_llm_debug_hidden")
         return out
+
+
+def score_targets(labels: torch.Tensor, attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """transformers' label shift as the targets of `score_rows` (pure torch, any device): labels [B, T] aligned with the inputs ->
+    targets int64 [B, T], targets[b][t] = labels[b][t + 1] - the token position t predicts - and -100 (ignore) at t = T - 1, where the
+    label is negative, and where attention_mask is 0 at t + 1 (a padding token is not scored) or at t (a padding position predicts
+    nothing: the first real token of a left-padded row has no prefix, like token 0 of an unpadded one)."""
+    if labels.dim() != 2:
+        raise ValueError(f"score_targets: labels must be [B, T], got {tuple(labels.shape)}")
+    if attention_mask is not None and tuple(attention_mask.shape) != tuple(labels.shape):
+        raise ValueError(f"score_targets: attention_mask must be [B, T] = {tuple(labels.shape)}, got {tuple(attention_mask.shape)}")
+    lab = labels.long()
+    tgt = torch.full_like(lab, -100)
+    tgt[:, :-1] = lab[:, 1:]
+    tgt[tgt < 0] = -100
+    if attention_mask is not None:
+        keep = attention_mask != 0
+        ok = keep.clone()
+        ok[:, :-1] &= keep[:, 1:]
+        tgt[~ok] = -100
+    return tgt.contiguous()
+
+
+def label_aligned(per_position: torch.Tensor) -> torch.Tensor:
+    """a [B, T] result indexed by the PREDICTING position -> indexed by the predicted token: entry [b][t] = input [b][t - 1], 0 at t = 0"""
+    return torch.cat([torch.zeros_like(per_position[:, :1]), per_position[:, :-1]], 1)
 
 
 def quantize_rows_e4m3(w: torch.Tensor):
