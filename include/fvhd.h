@@ -70,7 +70,10 @@ typedef void* fvhd_stream_t; /* hipStream_t */
  * fvhd_llm_decode on explicit token_ids, and fvhd_llm_decode, fvhd_llm_verify and fvhd_llm_cache_gather end a lookup generation; every call
  * that is accepted enqueues what 509 did, launch for launch and bit for bit.  Added under 510 (new symbols only, the number stays): scoring
  * given tokens - fvhd_lm_score_scratch_bytes, fvhd_lm_score_plan, fvhd_op_lm_score, fvhd_llm_score_reserve, fvhd_llm_score; every existing
- * call enqueues what it did and fvhd_llm_reserve allocates what it did. */
+ * call enqueues what it did and fvhd_llm_reserve allocates what it did.  Also added under 510 (new symbols only, the number stays): 4-bit
+ * LLM weights - FVHD_W_MXFP4 for fvhd_llm_set_weight_format, fvhd_llm_debug_packed_mxfp4, fvhd_op_quantize_mxfp4, fvhd_op_dec_gemm_w4 /
+ * _qkv_w4 / _lm_argmax_w4, fvhd_op_w4_unpack; bf16 and e4m3 contexts enqueue what they did, bit for bit (a caller detects the symbols, as
+ * ml_fastvlm_amd/_lib.py w4_lib() does). */
 #define FVHD_VERSION 510
 int fvhd_version(void);
 const char* fvhd_last_error(void);
@@ -550,7 +553,8 @@ int fvhd_op_dec_lm_argmax(fvhd_stream_t stream, const void* x, int B, const floa
 #define FVHD_W_E4M3 1
 /* The storage format of the packed matrices (lm_head.weight included).  Call it right after fvhd_llm_create: once a tensor was set it fails
  * with an error (both fvhd_llm_set_tensor paths quantise matrices as they arrive).  FVHD_W_E4M3 needs hidden, n_heads * head_dim and
- * intermediate to be multiples of 128.  Re-allocates the weight buffer (and the dequantisation scratch). */
+ * intermediate to be multiples of 128; so does FVHD_W_MXFP4 ("LLM 4-bit weights" below).  Re-allocates the weight buffer (and the
+ * dequantisation scratch). */
 int fvhd_llm_set_weight_format(fvhd_llm* ctx, int format);
 /* device bytes held by the packed weights: matrices, row scales, norm weights and biases (not the workspace, the caches, the optional
  * embedding table or the e4m3 dequantisation scratch) */
@@ -578,6 +582,44 @@ int fvhd_op_dec_qkv_w8(fvhd_stream_t stream, const void* x, int B, int K, const 
                        int splits);
 int fvhd_op_dec_lm_argmax_w8(fvhd_stream_t stream, const void* x, int B, const float* norm_w, float eps, const void* Wt, const float* scale, int V,
                              int K, float* logits, int64_t* ids_out, float* scratch_v, int* scratch_i);
+
+/* ---- LLM 4-bit weights: the packed matrices as OCP MXFP4 - e2m1 codes with one power-of-two scale per 32 elements (added under 510) ---------
+ * Weight-only storage, 4.25 bits per weight.  A matrix W [N, K] (K % 128 == 0, the e4m3 rule), in plain order for the single ops and the
+ * read-back:
+ *   codes  u8 [N, K / 2]   element k is in byte k / 2, even k in the low nibble; a code is sign (bit 3) + an index (bits 2..0) into
+ *                          {0, 0.5, 1, 1.5, 2, 3, 4, 6}
+ *   scales u8 [N, K / 32]  byte E stands for 2^(E - 127) (e8m0), one per block of 32 consecutive k of a row
+ * and element (n, k) stands for code * 2^(E - 127), which is exactly a bf16 value.  The arithmetic does not change: the decode GEMMs turn a
+ * dword of codes and its block scale into the bf16 MFMA fragment in registers (v_cvt_scalef32_pk_bf16_fp4, exact) - the very operand the
+ * bf16 kernels load from the dequantised matrix - and run the same MFMAs in the same order; nothing scales the accumulator.  So every op
+ * below, and every call on an FVHD_W_MXFP4 context, has the BITS of its bf16 counterpart on the dequantised matrices.  The prefill / extend /
+ * score path dequantises each matrix into the bf16 scratch of the e4m3 format (same size rule) right before its GEMM; a tied model's decode
+ * embeds through the dequantised lm_head rows.  The K order inside the weight buffer is private.
+ * The library's quantiser (both fvhd_llm_set_tensor paths, each source tensor on its own; fvhd_op_quantize_mxfp4), per block:
+ * se = ceil(log2(amax / 6)) evaluated exactly from amax's bf16 exponent and mantissa (amax = m 2^e, m in [1, 2): e - 2 + (m > 1.5)), clamped
+ * to [-125, 125], 0 for an all-zero block, E = se + 127 in [2, 252]; codes = w / 2^se rounded to the nearest grid value, ties to the even
+ * index, saturating at 6 (only at the upper clamp); the sign bit is w's (a small negative becomes -0).  amax / 2^se lies in (3, 6].  This is
+ * a COARSE format: the relative L2 error of a Gaussian matrix is about 0.12 (e4m3 with row scales: 0.036). */
+#define FVHD_W_MXFP4 2      /* fvhd_llm_set_weight_format: the e4m3 rules (before the first tensor; hidden, n_heads * head_dim, intermediate % 128) */
+/* tests: one packed matrix of an FVHD_W_MXFP4 context in plain order: codes_out u8 [N][K / 2], scales_out u8 [N][K / 32], device pointers;
+ * layer / matrix as for fvhd_llm_debug_packed_e4m3 */
+int fvhd_llm_debug_packed_mxfp4(fvhd_llm* ctx, int layer, int matrix, void* codes_out, void* scales_out, fvhd_stream_t stream);
+/* the quantiser on its own: W bf16 [N, K] (K % 32 == 0, 16-byte aligned) -> codes u8 [N, K / 2], scales u8 [N, K / 32] */
+int fvhd_op_quantize_mxfp4(fvhd_stream_t stream, const void* W, int N, int K, void* codes, void* scales);
+/* fvhd_op_dec_gemm / _qkv / _lm_argmax on MXFP4 weights: the _w8 signatures with `codes, scales` (plain order, 4-byte aligned) in place of
+ * `codes, scale`.  Any scale byte whose products stay finite and normal is accepted.  The codes are first repacked into a process-wide scratch
+ * (allocated on demand): eager calls only, not during stream capture. */
+int fvhd_op_dec_gemm_w4(fvhd_stream_t stream, int epi, const void* x, int B, const float* norm_w, float eps, const void* Wt, const void* scales, int N,
+                        int K, const void* resid, void* out, float* partial, int* counters, int splits);
+int fvhd_op_dec_qkv_w4(fvhd_stream_t stream, const void* x, int B, int K, const float* norm_w, float eps, const void* Wt, const void* scales,
+                       const float* bias, void* q_out, const int64_t* pos, const float* table, int table_positions, float rope_theta, void* k_cache,
+                       void* v_cache, int capacity, const int* length, int n_heads, int n_kv_heads, int head_dim, float* partial, int* counters,
+                       int splits);
+int fvhd_op_dec_lm_argmax_w4(fvhd_stream_t stream, const void* x, int B, const float* norm_w, float eps, const void* Wt, const void* scales, int V,
+                             int K, float* logits, int64_t* ids_out, float* scratch_v, int* scratch_i);
+/* the layout kernel on its own (tests; K % 128 == 0): mode 0: codes in the private K order + scales -> bf16 [N, K] (dst 16-byte aligned);
+ * 1: private order -> plain codes; 2: plain -> private order (scales are in k order either way and may be NULL for modes 1, 2) */
+int fvhd_op_w4_unpack(fvhd_stream_t stream, const void* src, const void* scales, void* dst, int N, int K, int mode);
 
 /* ---- LLM beam search: the top continuations and the KV-cache reorder on the device (version 505) -------------------------------------------
  * transformers' `GenerationMixin._beam_search` keeps, per prompt, K = num_beams running hypotheses: K beams of G prompts are G * K rows of

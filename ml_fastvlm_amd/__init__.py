@@ -15,7 +15,8 @@ from .builder import GenerationSession, beam_generate, build_vision_projector, b
 from .logits_processors import process_reference  # noqa: F401
 from .mobileclip_encoder import MobileCLIPVisionTower, load_model_config  # noqa: F401
 from .qwen2_prefill import quantize_rows_e4m3  # noqa: F401
+from .qwen2_prefill import dequantize_blocks_mxfp4, quantize_blocks_mxfp4  # noqa: F401
 
 __all__ = ["MobileCLIPVisionTower", "build_vision_tower", "build_vision_projector", "encode_images", "project",
-           "library_projector", "install_into_llava", "load_model_config", "generate", "quantize_rows_e4m3", "beam_generate", "BeamSearchState",
+           "library_projector", "install_into_llava", "load_model_config", "generate", "quantize_rows_e4m3", "quantize_blocks_mxfp4", "dequantize_blocks_mxfp4", "beam_generate", "BeamSearchState",
            "process_reference", "GenerationSession", "score"]

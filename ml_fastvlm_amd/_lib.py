@@ -27,6 +27,8 @@ MAX_VERIFY_ROWS = 16           # rows of one verify step (include/fvhd.h)
 MAX_EOS_IDS, MAX_SUPPRESS_IDS = 16, 256      # list limits of fvhd_llm_set_logits_processors (include/fvhd.h)
 W_BF16, W_E4M3 = 0, 1           # fvhd_llm_set_weight_format (include/fvhd.h)
 WEIGHT_FORMATS = {"bf16": W_BF16, "fp8_e4m3": W_E4M3}
+W_MXFP4 = 2                     # added under 510 (w4_lib()): OCP MXFP4, e2m1 codes + one e8m0 scale per 32 elements of a row
+MX_WEIGHT_FORMATS = {"mxfp4": W_MXFP4}
 MAT_QKV, MAT_O, MAT_GATE_UP, MAT_DOWN, MAT_LM_HEAD = 0, 1, 2, 3, 4     # fvhd_llm_debug_packed_e4m3
 F32, F16, BF16 = 0, 1, 2
 FFN_HALF, FFN_BF16 = 0, 1        # precision of the fused ConvFFN's hidden activation (include/fvhd.h)
@@ -178,6 +180,15 @@ def _declare(lib) -> None:
             "fvhd_llm_score_reserve": (ci, [vp, ci]),
             "fvhd_llm_score": (ci, [vp, vp, vp, vp, vp]),
         })
+    if hasattr(lib, "fvhd_op_dec_gemm_w4"):        # added under 510: a 510 library built before them loads without; w4_lib() then names the rebuild
+        sig.update({
+            "fvhd_llm_debug_packed_mxfp4": (ci, [vp, ci, ci, vp, vp, vp]),
+            "fvhd_op_quantize_mxfp4": (ci, [vp, vp, ci, ci, vp, vp]),
+            "fvhd_op_dec_gemm_w4": (ci, [vp, ci, vp, ci, vp, cf, vp, vp, ci, ci, vp, vp, vp, vp, ci]),
+            "fvhd_op_dec_qkv_w4": (ci, [vp, vp, ci, ci, vp, cf, vp, vp, vp, vp, vp, vp, ci, cf, vp, vp, ci, vp, ci, ci, ci, vp, vp, ci]),
+            "fvhd_op_dec_lm_argmax_w4": (ci, [vp, vp, ci, vp, cf, vp, vp, ci, ci, vp, vp, vp, vp]),
+            "fvhd_op_w4_unpack": (ci, [vp, vp, vp, vp, ci, ci, ci]),
+        })
     del fp, cl
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)     # AttributeError here = the .so does not export what fvhd.h declares
@@ -293,12 +304,22 @@ def score_lib():
     return lib
 
 
+def w4_lib():
+    """load(), for the 4-bit (MXFP4) weight entry points: they were added under FVHD_VERSION 510, so a library built before them reports
+    the same number and loads; this says so instead of an AttributeError."""
+    lib = load()
+    if not hasattr(lib, "fvhd_op_dec_gemm_w4"):
+        raise FvhdError(f"{LIB_PATH} (ABI version {lib.fvhd_version()}) was built before 4-bit weights (FVHD_W_MXFP4, fvhd_op_quantize_mxfp4, "
+                        "fvhd_op_dec_gemm_w4, ...) - rebuild the library (`python -m ml_fastvlm_amd.build`)")
+    return lib
+
+
 def weight_format_code(weights: str) -> int:
-    """"bf16" / "fp8_e4m3" -> FVHD_W_BF16 / FVHD_W_E4M3; anything else is a ValueError"""
+    """"bf16" / "fp8_e4m3" / "mxfp4" -> FVHD_W_BF16 / FVHD_W_E4M3 / FVHD_W_MXFP4; anything else is a ValueError"""
     try:
-        return WEIGHT_FORMATS[weights]
+        return {**WEIGHT_FORMATS, **MX_WEIGHT_FORMATS}[weights]
     except (KeyError, TypeError):
-        raise ValueError(f"weights must be one of {sorted(WEIGHT_FORMATS)}, got {weights!r}") from None
+        raise ValueError(f"weights must be one of {sorted({**WEIGHT_FORMATS, **MX_WEIGHT_FORMATS})}, got {weights!r}") from None
 
 
 def decode_lib(batch: int):

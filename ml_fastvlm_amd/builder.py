@@ -108,7 +108,7 @@ def install_into_llava(splice: bool = False, prefill: bool = False, prefill_any_
     keeps falling back, as before.
     logits_processors=True (with generate=True) lets it take the library for `repetition_penalty`, `no_repeat_ngram_size`, `min_new_tokens`
     and `suppress_tokens` too (num_beams = 1; `Qwen2Generator.set_logits_processors`); without it those settings keep falling back.
-    llm_weights: "bf16" (the default) or "fp8_e4m3" - the storage of the LLM's packed matrices in the library's prefill / decode contexts
+    llm_weights: "bf16" (the default), "fp8_e4m3" or "mxfp4" - the storage of the LLM's packed matrices in the library's prefill / decode contexts
     (`Qwen2Prefill.from_hf(weights=...)`), recorded on `LlavaQwen2ForCausalLM` for `prefill_context` to read."""
     from ._lib import weight_format_code
     weight_format_code(llm_weights)
@@ -210,7 +210,7 @@ def prefill_context(model, weights=None):
     """The `Qwen2Prefill` context of a (Llava)Qwen2ForCausalLM, built on first use and rebuilt when its weights change (in place or by
     re-assignment).  `install_into_llava(prefill=True)` users call this once after loading the model so that the packing (device-to-device
     copies, ~0.1 s for 0.5B) is not part of the first request's TTFT.
-    weights: "bf16" / "fp8_e4m3" - recorded on the model (`_fvhd_llm_weights`); None = what was recorded (by an earlier call or by
+    weights: "bf16" / "fp8_e4m3" / "mxfp4" - recorded on the model (`_fvhd_llm_weights`); None = what was recorded (by an earlier call or by
     `install_into_llava(llm_weights=...)`), else "bf16".  A context in the other format is rebuilt, not reused."""
     from ._lib import weight_format_code
     from .qwen2_prefill import Qwen2Prefill

@@ -85,6 +85,12 @@ int fvhd_launch_quantize_e4m3(hipStream_t st, const void* w, int rows, int K, vo
 int fvhd_launch_w8_unpack(hipStream_t st, const void* src, const float* scale, void* dst, long N, int K, int mode);
 int fvhd_launch_dec_embed_w8(hipStream_t st, const int64_t* tok, const int64_t* last, const void* table, const float* scale, int V, int H, void* h,
                              unsigned char* key_valid, int B, int cap, const int* len, int* status, int* status_host);
+// llm_w4.hip
+int fvhd_launch_dec_gemm_w4(hipStream_t st, const DecGemmArgs* a);
+int fvhd_launch_quantize_mxfp4(hipStream_t st, const void* w, int rows, int K, void* codes, long pitch, void* scales, long spitch, int packed);
+int fvhd_launch_w4_unpack(hipStream_t st, const void* src, const void* scales, void* dst, long N, int K, int mode);
+int fvhd_launch_dec_embed_w4(hipStream_t st, const int64_t* tok, const int64_t* last, const void* table, const void* scales, int V, int H, void* h,
+                             unsigned char* key_valid, int B, int cap, const int* len, int* status, int* status_host);
 // llm_sample.hip
 size_t fvhd_dec_sample_ws_bytes(void);
 int fvhd_launch_dec_sample(hipStream_t st, const DecSampleArgs* a, void* ws);
@@ -97,9 +103,9 @@ int fvhd_launch_dec_cache_gather(hipStream_t st, const DecCacheGatherArgs* a);
 // llm_spec.hip
 int fvhd_launch_spec_draft(hipStream_t st, const int* seq, const int* seq_len, int max_ngram, int K, int64_t* draft, const int* status, const int* words,
                            int* gate);
-int fvhd_launch_spec_embed(hipStream_t st, const int64_t* draft, const int64_t* last, const void* table, const float* scale, int V, int H, void* h,
-                           unsigned char* key_valid, int T, int cap, const int* len, const int64_t* posv, int64_t* pos, int* status, int* status_host,
-                           int* gate);
+int fvhd_launch_spec_embed(hipStream_t st, const int64_t* draft, const int64_t* last, const void* table, const float* scale, const void* wblk, int V, int H,
+                           void* h, unsigned char* key_valid, int T, int cap, const int* len, const int64_t* posv, int64_t* pos, int* status,
+                           int* status_host, int* gate);
 int fvhd_launch_spec_attention(hipStream_t st, const void* q, void* kc, void* vc, const void* ks, const void* vs, const unsigned char* key_valid, void* out,
                                int T, int nh, int nkv, int hd, int cap, const int* len, int S, int chunk, float* part, int* cnt, const int* status);
 int fvhd_launch_spec_accept(hipStream_t st, const SpecAcceptArgs* a);

@@ -12,7 +12,8 @@
 constexpr int kMaxSplits = 4;
 constexpr int kMaxEos = 16, kMaxSuppress = 256;     // list limits of the logits processors (include/fvhd.h)
 
-struct LayerOff { size_t ln1, bqkv, ln2, w[4], s[4]; };     // w, s: by FVHD_MAT_QKV .. FVHD_MAT_DOWN; s: the fp32 row scales of an e4m3 matrix
+struct LayerOff { size_t ln1, bqkv, ln2, w[4], s[4]; };     // w, s: by FVHD_MAT_QKV .. FVHD_MAT_DOWN; s: the fp32 row scales of an e4m3 matrix,
+                                                            // the block scale bytes of an MXFP4 one
 
 struct __attribute__((visibility("default"))) fvhd_llm {     // (its inline constructor and destructor have always been weak exported symbols)
     int device = 0, H = 0, L = 0, nh = 0, nkv = 0, hd = 0, I = 0, V = 0;
@@ -24,8 +25,10 @@ struct __attribute__((visibility("default"))) fvhd_llm {     // (its inline cons
     size_t norm_off = 0, lm_off = 0, lm_soff = 0;
     int wfmt = FVHD_W_BF16;                // fvhd_llm_set_weight_format: FVHD_W_E4M3 = every matrix as e4m3 codes (1 byte, the K order of llm_w8.hip) + one
                                            // fp32 scale per row; vectors and model.embed_tokens.weight are not affected
+                                           // FVHD_W_MXFP4 = every matrix as e2m1 codes (two per byte, the K order of w4_layout.h) + one e8m0 scale
+                                           // byte per 32 elements of a row
     bool any_set = false;                  // a tensor was set: the format is fixed
-    char* wscratch = nullptr;              // e4m3: bf16 scratch of the largest matrix - the prefill dequantises each matrix into it right before its GEMM
+    char* wscratch = nullptr;              // e4m3 / MXFP4: bf16 scratch of the largest matrix - the prefill dequantises each matrix into it right before its GEMM
     size_t wscratch_bytes = 0;
     std::vector<char> got;                 // per expected tensor: received?
     std::vector<std::string> names;
@@ -136,7 +139,8 @@ inline int cu_count(const fvhd_llm* c)      // compute units of the context's de
     return hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess && n > 0 ? n : 256;
 }
 
-// one packed matrix: [N][K] elements (bf16, or e4m3 codes) at wdev + off; e4m3: its N fp32 row scales at wdev + soff
+// one packed matrix: [N][K] elements (bf16, e4m3 codes or MXFP4 codes) at wdev + off; its scales at wdev + soff: e4m3 N fp32 row scales,
+// MXFP4 u8 [N][K / 32]
 struct Mat { size_t off, soff; long N; int K; };
 Mat mat_of(const fvhd_llm* c, int layer, int matrix);             // llm_weights.hip; matrix: FVHD_MAT_* (layer is ignored for FVHD_MAT_LM_HEAD)
 

@@ -39,6 +39,8 @@ struct DecGemmArgs {
                                    // in every workgroup (NULL: every workgroup recomputes them, as at B <= 16; the bits are the same)
     const float* wscale = nullptr; // non-NULL: W holds OCP e4m3 codes [N][K], one byte each, in the packed K order of llm_w8.hip, and row n
                                    // stands for code * wscale[n] (fp32 [N]); the launch goes to dec_gemm_w8_kernel
+    const unsigned char* wblk = nullptr;   // non-NULL (wscale is NULL then): W holds MXFP4 codes [N][K / 2] in the packed K order of w4_layout.h and
+                                   // wblk the e8m0 block scales u8 [N][K / 32]; the launch goes to dec_gemm_w4_kernel (llm_w4.hip)
 };
 
 // Arguments of the sampler (llm_sample.hip): temperature / top-k / top-p over fp32 logits [B][V], one draw per row.

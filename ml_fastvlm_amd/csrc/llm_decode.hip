@@ -633,6 +633,7 @@ extern "C" int fvhd_launch_dec_gemm(hipStream_t st, const DecGemmArgs* a)
     if (a->norm_w && a->rstd && a->B > 16)
         hipLaunchKernelGGL(dec_rstd_kernel, dim3((a->B + 3) / 4), dim3(256), 0, st, (const bf16*)a->x, a->ldx, a->K, a->B, a->eps, a->rstd, a->status);
     if (a->wscale) return fvhd_launch_dec_gemm_w8(st, a);         // e4m3 weights: the sibling kernels
+    if (a->wblk) return fvhd_launch_dec_gemm_w4(st, a);           // MXFP4 weights: theirs
     const int ncol = (a->N / 16 + 3) / 4;
     const dim3 grid((unsigned)((long)ncol * a->S));
     switch (a->epi) {

@@ -157,25 +157,28 @@ static DecGemmArgs dec_argmax_args(const void* x, int B, const float* norm_w, fl
 
 // e4m3 = a.wscale set: only the *_w8 entry points pass a scale (and refuse a NULL one), the bf16 ones pass nullptr and skip this.  a.W arrives as
 // plain row-major codes u8 [N][K]; the kernels read the packed K order of llm_w8.hip, so the codes are repacked into a process-wide scratch first,
-// grown on demand (eager calls only, like fvhd_op_dec_sample's workspace).  Then the launch; ARGMAX also reduces the (max, index) pairs to ids.
+// grown on demand (eager calls only, like fvhd_op_dec_sample's workspace).  MXFP4 = a.wblk set (the *_w4 entry points): plain codes u8
+// [N][K / 2] repacked into the same scratch, the block scales read where they are.  Then the launch; ARGMAX also reduces the (max, index)
+// pairs to ids.
 static int dec_run(hipStream_t st, const char* who, DecGemmArgs a, int64_t* ids_out = nullptr)
 {
-    if (a.wscale) {
+    if (a.wscale || a.wblk) {
         static char* buf[64] = {};
         static size_t cap[64] = {};
         int dev = 0;
         hipError_t he = hipGetDevice(&dev);
         if (he != hipSuccess) return lhip("hipGetDevice", he);
         if (dev < 0 || dev >= 64) return lfail(std::string(who) + ": device index out of range");
-        const size_t need = (size_t)a.N * a.K;
+        const size_t need = a.wblk ? (size_t)a.N * a.K / 2 : (size_t)a.N * a.K;
         if (need > cap[dev]) {
             if (buf[dev]) (void)hipFree(buf[dev]);                  // (synchronises: no earlier launch still reads it)
             buf[dev] = nullptr;
             cap[dev] = 0;
-            if ((he = hipMalloc((void**)&buf[dev], need)) != hipSuccess) { buf[dev] = nullptr; return lhip("hipMalloc(e4m3 repack scratch)", he); }
+            if ((he = hipMalloc((void**)&buf[dev], need)) != hipSuccess) { buf[dev] = nullptr; return lhip("hipMalloc(repack scratch)", he); }
             cap[dev] = need;
         }
-        if (int e = fvhd_launch_w8_unpack(st, a.W, nullptr, buf[dev], a.N, a.K, 2)) return lhip(who, (hipError_t)e);
+        if (int e = a.wblk ? fvhd_launch_w4_unpack(st, a.W, nullptr, buf[dev], a.N, a.K, 2) : fvhd_launch_w8_unpack(st, a.W, nullptr, buf[dev], a.N, a.K, 2))
+            return lhip(who, (hipError_t)e);
         a.W = buf[dev];
     }
     int e = fvhd_launch_dec_gemm(st, &a);
@@ -252,6 +255,66 @@ int fvhd_op_dec_lm_argmax_w8(fvhd_stream_t st, const void* x, int B, const float
     if (!x || !Wt || !scale || !ids_out || !scratch_v || !scratch_i) return lfail("fvhd_op_dec_lm_argmax_w8: NULL pointer");
     if (B < 1 || B > 64 || V < 16 || V % 16 || K < 128 || K % 128) return lfail("fvhd_op_dec_lm_argmax_w8: needs 1 <= B <= 64, V % 16 == 0, K % 128 == 0");
     return dec_run((hipStream_t)st, "fvhd_op_dec_lm_argmax_w8", dec_argmax_args(x, B, norm_w, eps, Wt, scale, V, K, logits, scratch_v, scratch_i), ids_out);
+}
+
+// ---- the same single ops on MXFP4 weights (llm_w4.hip): Wt = plain codes u8 [N][K / 2], scales = block scales u8 [N][K / 32] ----
+static bool misaligned4(const void* codes, const void* scales) { return ((uintptr_t)codes & 3) || ((uintptr_t)scales & 3); }
+
+int fvhd_op_dec_gemm_w4(fvhd_stream_t st, int epi, const void* x, int B, const float* norm_w, float eps, const void* Wt, const void* scales, int N, int K,
+                        const void* resid, void* out, float* partial, int* counters, int splits)
+{
+    if (!x || !Wt || !scales || !out || (epi == FVHD_EPI_RESID && !resid)) return lfail("fvhd_op_dec_gemm_w4: NULL pointer");
+    if (epi != FVHD_EPI_RESID && epi != FVHD_EPI_SWIGLU) return lfail("fvhd_op_dec_gemm_w4: epi must be FVHD_EPI_RESID or FVHD_EPI_SWIGLU");
+    if (B < 1 || B > 64 || N < 16 || N % 16 || K < 128 || K % 128 || splits < 1 || (splits > 1 && (!partial || !counters)))
+        return lfail("fvhd_op_dec_gemm_w4: needs 1 <= B <= 64, N % 16 == 0, K % 128 == 0, splits >= 1 (and scratch when splits > 1)");
+    if (misaligned4(Wt, scales)) return lfail("fvhd_op_dec_gemm_w4: codes and scales must be aligned to 4 bytes");
+    DecGemmArgs a = dec_gemm_args(epi, x, B, norm_w, eps, Wt, nullptr, N, K, resid, out, partial, counters, splits);
+    a.wblk = (const unsigned char*)scales;
+    return dec_run((hipStream_t)st, "fvhd_op_dec_gemm_w4", a);
+}
+
+int fvhd_op_dec_qkv_w4(fvhd_stream_t st, const void* x, int B, int K, const float* norm_w, float eps, const void* Wt, const void* scales, const float* bias,
+                       void* q_out, const int64_t* pos, const float* table, int table_positions, float rope_theta, void* k_cache, void* v_cache, int capacity,
+                       const int* length, int n_heads, int n_kv_heads, int head_dim, float* partial, int* counters, int splits)
+{
+    if (!x || !Wt || !scales || !bias || !q_out || !pos || !table || !k_cache || !v_cache || !length) return lfail("fvhd_op_dec_qkv_w4: NULL pointer");
+    if (B < 1 || B > 64 || K < 128 || K % 128 || splits < 1 || head_dim < 16 || head_dim % 16 || n_heads < 1 || n_kv_heads < 1 || capacity < 1 ||
+        table_positions < 1 || (splits > 1 && (!partial || !counters)))
+        return lfail("fvhd_op_dec_qkv_w4: needs 1 <= B <= 64, K % 128 == 0, head_dim % 16 == 0, splits >= 1 (and scratch when splits > 1)");
+    if (misaligned4(Wt, scales)) return lfail("fvhd_op_dec_qkv_w4: codes and scales must be aligned to 4 bytes");
+    DecGemmArgs a = dec_qkv_args(x, B, K, norm_w, eps, Wt, nullptr, bias, q_out, pos, table, table_positions, rope_theta, k_cache, v_cache, capacity, length,
+                                 n_heads, n_kv_heads, head_dim, partial, counters, splits);
+    a.wblk = (const unsigned char*)scales;
+    return dec_run((hipStream_t)st, "fvhd_op_dec_qkv_w4", a);
+}
+
+int fvhd_op_dec_lm_argmax_w4(fvhd_stream_t st, const void* x, int B, const float* norm_w, float eps, const void* Wt, const void* scales, int V, int K,
+                             float* logits, int64_t* ids_out, float* scratch_v, int* scratch_i)
+{
+    if (!x || !Wt || !scales || !ids_out || !scratch_v || !scratch_i) return lfail("fvhd_op_dec_lm_argmax_w4: NULL pointer");
+    if (B < 1 || B > 64 || V < 16 || V % 16 || K < 128 || K % 128) return lfail("fvhd_op_dec_lm_argmax_w4: needs 1 <= B <= 64, V % 16 == 0, K % 128 == 0");
+    if (misaligned4(Wt, scales)) return lfail("fvhd_op_dec_lm_argmax_w4: codes and scales must be aligned to 4 bytes");
+    DecGemmArgs a = dec_argmax_args(x, B, norm_w, eps, Wt, nullptr, V, K, logits, scratch_v, scratch_i);
+    a.wblk = (const unsigned char*)scales;
+    return dec_run((hipStream_t)st, "fvhd_op_dec_lm_argmax_w4", a, ids_out);
+}
+
+int fvhd_op_quantize_mxfp4(fvhd_stream_t st, const void* W, int N, int K, void* codes, void* scales)
+{
+    if (!W || !codes || !scales) return lfail("fvhd_op_quantize_mxfp4: NULL pointer");
+    if (N < 1 || K < 32 || K % 32) return lfail("fvhd_op_quantize_mxfp4: needs N >= 1, K >= 32 and K % 32 == 0");
+    if (((uintptr_t)W & 15) || ((uintptr_t)codes & 3)) return lfail("fvhd_op_quantize_mxfp4: W must be aligned to 16 bytes, codes to 4");
+    return lret("fvhd_op_quantize_mxfp4", fvhd_launch_quantize_mxfp4((hipStream_t)st, W, N, K, codes, K / 2, scales, K / 32, 0));
+}
+
+// the layout kernel on its own (tests): mode 0: packed codes + scales -> bf16 [N][K] (the prefill's dequantise); 1: packed -> plain codes;
+// 2: plain -> packed codes.  K % 128 == 0.
+int fvhd_op_w4_unpack(fvhd_stream_t st, const void* src, const void* scales, void* dst, int N, int K, int mode)
+{
+    if (!src || !dst || (mode == 0 && !scales)) return lfail("fvhd_op_w4_unpack: NULL pointer");
+    if (N < 1 || K < 128 || K % 128 || mode < 0 || mode > 2) return lfail("fvhd_op_w4_unpack: needs N >= 1, K % 128 == 0 and mode in 0 .. 2");
+    if (((uintptr_t)src & 3) || ((uintptr_t)dst & 15)) return lfail("fvhd_op_w4_unpack: src must be aligned to 4 bytes, dst to 16");
+    return lret("fvhd_op_w4_unpack", fvhd_launch_w4_unpack((hipStream_t)st, src, scales, dst, N, K, mode));
 }
 
 int fvhd_op_quantize_e4m3(fvhd_stream_t st, const void* W, int N, int K, void* codes, float* scale)

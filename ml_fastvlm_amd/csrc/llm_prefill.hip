@@ -53,14 +53,15 @@ int ensure_ws(fvhd_llm* c, int B, int T, hipStream_t st, bool check_capture)
     return e == hipSuccess ? 0 : lhip("hipMemcpy(rope table)", e);
 }
 
-// The matrix a GEMM reads: the packed bf16 weights, or - e4m3 - the bf16 scratch the codes are dequantised into right before it (1 byte in,
-// 2 bytes out per element; the GEMMs run one after the other on `st`, so one scratch of the largest matrix serves them all).  One function
+// The matrix a GEMM reads: the packed bf16 weights, or - e4m3 / MXFP4 - the bf16 scratch the codes are dequantised into right before it
+// (1 byte or 17 / 32 of one in, 2 bytes out per element; the GEMMs run one after the other on `st`, so one scratch of the largest matrix serves them all).  One function
 // for the decoder stack and for fvhd_llm_score.
 static int stack_weights(fvhd_llm* c, hipStream_t st, int layer, int matrix, const void** p)
 {
     const Mat m = mat_of(c, layer, matrix);
-    if (c->wfmt != FVHD_W_E4M3) { *p = c->wdev + m.off; return 0; }
+    if (c->wfmt == FVHD_W_BF16) { *p = c->wdev + m.off; return 0; }
     *p = c->wscratch;
+    if (c->wfmt == FVHD_W_MXFP4) return fvhd_launch_w4_unpack(st, c->wdev + m.off, c->wdev + m.soff, c->wscratch, m.N, m.K, 0);
     return fvhd_launch_w8_unpack(st, c->wdev + m.off, (const float*)(c->wdev + m.soff), c->wscratch, m.N, m.K, 0);
 }
 

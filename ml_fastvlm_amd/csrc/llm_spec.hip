@@ -12,6 +12,7 @@
 // bits of the plain step at length *len + t + 1.
 #include "fvhd_common.h"
 #include "launchers.h"
+#include "w4_layout.h"  // w4_pos, w4_scale, fp4x8_to_bf8
 #include "w8_layout.h"  // w8_pos, e4m3x8_to_f32
 
 namespace {
@@ -96,10 +97,11 @@ __global__ __launch_bounds__(256) void spec_draft_kernel(const int* __restrict__
 
 // ---------------------------------------------------------------------------------------------------
 // The step's token rows.  Workgroup = row t: row 0 = the token the previous step chose, row t = draft[t - 1].  Nothing is written when the
-// T slots do not fit (error 1, sticky); an id outside [0, V) is error 2.  scale != NULL: the table holds packed e4m3 lm_head rows.
+// T slots do not fit (error 1, sticky); an id outside [0, V) is error 2.  scale != NULL: the table holds packed e4m3 lm_head rows;
+// wblk != NULL: packed MXFP4 lm_head rows and these block scales (w4_layout.h).
 __global__ __launch_bounds__(256) void spec_embed_kernel(const int64_t* __restrict__ draft, const int64_t* __restrict__ last, const void* __restrict__ table,
-                                                         const float* __restrict__ scale, int V, int H, bf16* __restrict__ h, unsigned char* __restrict__ key_valid,
-                                                         int T, int cap, const int* len, const int64_t* posv, int64_t* __restrict__ pos, int* status,
+                                                         const float* __restrict__ scale, const u8* __restrict__ wblk, int V, int H, bf16* __restrict__ h,
+                                                         unsigned char* __restrict__ key_valid, int T, int cap, const int* len, const int64_t* posv, int64_t* __restrict__ pos, int* status,
                                                          int* status_host, int* gate)
 {
     if (*gate) return;
@@ -124,6 +126,11 @@ __global__ __launch_bounds__(256) void spec_embed_kernel(const int64_t* __restri
             for (int i = 0; i < 8; ++i) v[i] *= s;
             *(bf16x8*)(h + (size_t)t * H + c) = f32_to_bf8(v);
         }
+    } else if (wblk) {
+        const u8* src = (const u8*)table + (size_t)id * (H / 2);
+        const u8* sr = wblk + (size_t)id * (H / 32);
+        for (int c = threadIdx.x * 8; c < H; c += 256 * 8)
+            *(bf16x8*)(h + (size_t)t * H + c) = fp4x8_to_bf8(*(const uint32_t*)(src + w4_pos(c)), w4_scale(sr[c >> 5]));
     } else {
         const bf16* src = (const bf16*)table + (size_t)id * H;
         for (int c = threadIdx.x * 8; c < H; c += 256 * 8) *(u32x4*)(h + (size_t)t * H + c) = *(const u32x4*)(src + c);
@@ -379,12 +386,12 @@ extern "C" int fvhd_launch_spec_draft(hipStream_t st, const int* seq, const int*
     return (int)hipGetLastError();
 }
 
-extern "C" int fvhd_launch_spec_embed(hipStream_t st, const int64_t* draft, const int64_t* last, const void* table, const float* scale, int V, int H, void* h,
-                                      unsigned char* key_valid, int T, int cap, const int* len, const int64_t* posv, int64_t* pos, int* status,
+extern "C" int fvhd_launch_spec_embed(hipStream_t st, const int64_t* draft, const int64_t* last, const void* table, const float* scale, const void* wblk, int V, int H,
+                                      void* h, unsigned char* key_valid, int T, int cap, const int* len, const int64_t* posv, int64_t* pos, int* status,
                                       int* status_host, int* gate)
 {
-    if (T < 2 || T > 16 || H % 8) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(spec_embed_kernel, dim3(T), dim3(256), 0, st, draft, last, table, scale, V, H, (bf16*)h, key_valid, T, cap, len, posv, pos, status,
+    if (T < 2 || T > 16 || H % 8 || (wblk && (scale || H % 128))) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(spec_embed_kernel, dim3(T), dim3(256), 0, st, draft, last, table, scale, (const u8*)wblk, V, H, (bf16*)h, key_valid, T, cap, len, posv, pos, status,
                        status_host, gate);
     return (int)hipGetLastError();
 }

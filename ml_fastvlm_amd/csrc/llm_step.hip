@@ -264,8 +264,11 @@ int fvhd_llm_decode(fvhd_llm* c, const int64_t* token_ids, float* logits_out, in
     hipStream_t st = (hipStream_t)stream;
     const int B = c->run_batch, H = c->H, I = c->I, nh = c->nh, nkv = c->nkv, hd = c->hd, cap = c->dc_cap;
     const char* w = c->wdev;
-    const bool q8 = c->wfmt == FVHD_W_E4M3;
-    if (q8 && !c->emb) {                                         // a tied model: the token row dequantised from the lm_head codes
+    const bool q8 = c->wfmt == FVHD_W_E4M3, q4 = c->wfmt == FVHD_W_MXFP4;
+    if (q4 && !c->emb) {
+        LCHECK(fvhd_launch_dec_embed_w4(st, token_ids, c->last_ids, w + c->lm_off, w + c->lm_soff, c->V, H, c->dh, c->mask, B, cap, c->len, c->status,
+                                        c->status_host_dev), "decode embed (MXFP4 lm_head rows)");
+    } else if (q8 && !c->emb) {                                         // a tied model: the token row dequantised from the lm_head codes
         LCHECK(fvhd_launch_dec_embed_w8(st, token_ids, c->last_ids, w + c->lm_off, (const float*)(w + c->lm_soff), c->V, H, c->dh, c->mask, B, cap, c->len,
                                         c->status, c->status_host_dev), "decode embed (e4m3 lm_head rows)");
     } else {
@@ -278,6 +281,7 @@ int fvhd_llm_decode(fvhd_llm* c, const int64_t* token_ids, float* logits_out, in
         const fvhd_llm::Plan& p = c->plan[matrix];
         DecGemmArgs a;
         a.wscale = q8 ? (const float*)(w + m.soff) : nullptr;
+        a.wblk = q4 ? (const unsigned char*)(w + m.soff) : nullptr;
         a.x = x; a.ldx = m.K; a.norm_w = norm_w; a.eps = c->eps; a.W = w + m.off; a.N = (int)m.N; a.K = m.K; a.B = B; a.S = p.S; a.cpw = p.cpw;
         a.part = c->dpart; a.cnt = c->cnt; a.epi = epi; a.status = c->status; a.rstd = c->dec_rstd_once ? c->drstd : nullptr;
         return a;
@@ -495,16 +499,17 @@ int spec_enqueue(fvhd_llm* c, const int64_t* draft, int T, float* logits_out, in
 {
     const int H = c->H, I = c->I, nh = c->nh, nkv = c->nkv, hd = c->hd, cap = c->dc_cap;
     const char* w = c->wdev;
-    const bool q8 = c->wfmt == FVHD_W_E4M3;
-    const bool packed = q8 && !c->emb;                           // a tied model: the token rows dequantised from the lm_head codes
-    LCHECK(fvhd_launch_spec_embed(st, draft, c->last_ids, c->emb ? c->emb : w + c->lm_off, packed ? (const float*)(w + c->lm_soff) : nullptr, c->V, H, c->sp_h,
-                                  c->mask, T, cap, c->len, c->posv, c->sp_pos, c->status, c->status_host_dev, gate), "verify embed");
+    const bool q8 = c->wfmt == FVHD_W_E4M3, q4 = c->wfmt == FVHD_W_MXFP4;
+    const bool packed = !c->emb;                                 // a tied model: the token rows dequantised from the lm_head codes
+    LCHECK(fvhd_launch_spec_embed(st, draft, c->last_ids, c->emb ? c->emb : w + c->lm_off, packed && q8 ? (const float*)(w + c->lm_soff) : nullptr,
+                                  packed && q4 ? w + c->lm_soff : nullptr, c->V, H, c->sp_h, c->mask, T, cap, c->len, c->posv, c->sp_pos, c->status, c->status_host_dev, gate), "verify embed");
     const size_t layer_kv = (size_t)c->dc_batch * nkv * cap * hd * 2;
     auto gemm = [&](int epi, const void* x, const float* norm_w, int layer, int matrix) {
         const Mat m = mat_of(c, layer, matrix);
         const fvhd_llm::Plan& p = c->plan[matrix];
         DecGemmArgs a;
         a.wscale = q8 ? (const float*)(w + m.soff) : nullptr;
+        a.wblk = q4 ? (const unsigned char*)(w + m.soff) : nullptr;
         a.x = x; a.ldx = m.K; a.norm_w = norm_w; a.eps = c->eps; a.W = w + m.off; a.N = (int)m.N; a.K = m.K; a.B = T; a.S = p.S; a.cpw = p.cpw;
         a.part = c->dpart; a.cnt = c->cnt; a.epi = epi; a.status = gate;
         return a;

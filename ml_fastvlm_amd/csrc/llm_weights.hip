@@ -47,30 +47,36 @@ bool is_embed_key(const char* key)
 void weight_layout(fvhd_llm* c)
 {
     const size_t H = c->H, I = c->I, qkvw = c->qkvw, ao = (size_t)c->nh * c->hd, V = c->V;
-    const bool q8 = c->wfmt == FVHD_W_E4M3;
-    const size_t eb = q8 ? 1 : 2;          // bytes per matrix element
+    const bool q8 = c->wfmt == FVHD_W_E4M3, q4 = c->wfmt == FVHD_W_MXFP4;
+    // bytes of N * K matrix elements, and of their scales: e4m3 one fp32 per row, MXFP4 one byte per 32 elements (K % 128 == 0)
+    auto mb = [&](size_t N, size_t K) { return q4 ? N * K / 2 : q8 ? N * K : N * K * 2; };
+    auto sb = [&](size_t N, size_t K) { return q4 ? N * K / 32 : N * 4; };
     Arena a;
     c->lo.assign(c->L, LayerOff{});
     for (int l = 0; l < c->L; ++l) {
         LayerOff& o = c->lo[l];
         o.ln1 = a.take(H * 4);
-        o.w[FVHD_MAT_QKV] = a.take(qkvw * H * eb);
+        o.w[FVHD_MAT_QKV] = a.take(mb(qkvw, H));
         o.bqkv = a.take(qkvw * 4);
-        o.w[FVHD_MAT_O] = a.take(H * ao * eb);
+        o.w[FVHD_MAT_O] = a.take(mb(H, ao));
         o.ln2 = a.take(H * 4);
-        o.w[FVHD_MAT_GATE_UP] = a.take(2 * I * H * eb);
-        o.w[FVHD_MAT_DOWN] = a.take(H * I * eb);
-        if (q8) { o.s[FVHD_MAT_QKV] = a.take(qkvw * 4); o.s[FVHD_MAT_O] = a.take(H * 4); o.s[FVHD_MAT_GATE_UP] = a.take(2 * I * 4); o.s[FVHD_MAT_DOWN] = a.take(H * 4); }
+        o.w[FVHD_MAT_GATE_UP] = a.take(mb(2 * I, H));
+        o.w[FVHD_MAT_DOWN] = a.take(mb(H, I));
+        if (q8 || q4) {
+            o.s[FVHD_MAT_QKV] = a.take(sb(qkvw, H)); o.s[FVHD_MAT_O] = a.take(sb(H, ao));
+            o.s[FVHD_MAT_GATE_UP] = a.take(sb(2 * I, H)); o.s[FVHD_MAT_DOWN] = a.take(sb(H, I));
+        }
     }
     c->norm_off = a.take(H * 4);
-    c->lm_off = a.take(V * H * eb);
-    c->lm_soff = q8 ? a.take(V * 4) : 0;
+    c->lm_off = a.take(mb(V, H));
+    c->lm_soff = q8 || q4 ? a.take(sb(V, H)) : 0;
     c->wbytes = a.off;
 }
 
 // where a tensor of the state dict goes: cols == 0: `rows` floats at base + 4 eoff; else a [rows][cols] matrix whose element (0, 0) is
 // element eoff of the packed matrix at `base`, rows `pitch` elements apart (gate / up: interleaved rows), and - e4m3 - whose row scales
-// start at float seoff of `sbase`, one every `sstride` floats
+// start at float seoff of `sbase`, one every `sstride` floats (MXFP4: the scale bytes of row r are the cols / 32 bytes at
+// sbase + (seoff + r * sstride) * cols / 32, the codes of element (0, 0) at base + eoff / 2)
 struct Slot { size_t base = 0, eoff = 0, rows = 0, cols = 0, pitch = 0, sbase = 0, seoff = 0; int sstride = 1; };
 
 Slot slot_of(const fvhd_llm* c, int layer, int which)
@@ -108,6 +114,14 @@ int quantize_into(fvhd_llm* c, const Slot& s, const void* dev_bf16, hipStream_t 
                                                               (float*)(c->wdev + s.sbase) + s.seoff, s.sstride, 1));
 }
 
+// MXFP4: the same rows -> codes + block scales at the slot
+int quantize_into_w4(fvhd_llm* c, const Slot& s, const void* dev_bf16, hipStream_t st)
+{
+    const size_t spr = s.cols / 32;       // scale bytes per row
+    return lret("quantise to MXFP4", fvhd_launch_quantize_mxfp4(st, dev_bf16, (int)s.rows, (int)s.cols, c->wdev + s.base + s.eoff / 2, (long)(s.pitch / 2),
+                                                                c->wdev + s.sbase + s.seoff * spr, (long)(s.sstride * spr), 1));
+}
+
 int ensure_emb(fvhd_llm* c)
 {
     if (c->emb) return 0;
@@ -126,14 +140,14 @@ int upload_matrix(const void* host, int dtype, size_t rows, size_t cols, char* d
     return e == hipSuccess ? 0 : lhip("hipMemcpy2D(llm weights)", e);
 }
 
-// e4m3: the same host rows through a bf16 staging buffer on the device and the quantise kernel
+// e4m3 / MXFP4: the same host rows through a bf16 staging buffer on the device and the quantise kernel
 int upload_matrix_q(fvhd_llm* c, const void* host, int dtype, const Slot& s)
 {
     char* stage = nullptr;
     hipError_t e = hipMalloc((void**)&stage, s.rows * s.cols * 2);
     if (e != hipSuccess) return lhip("hipMalloc(quantise staging)", e);
     int r = upload_matrix(host, dtype, s.rows, s.cols, stage, s.cols);
-    if (!r) r = quantize_into(c, s, stage, nullptr);
+    if (!r) r = c->wfmt == FVHD_W_MXFP4 ? quantize_into_w4(c, s, stage, nullptr) : quantize_into(c, s, stage, nullptr);
     if (!r && (e = hipStreamSynchronize(nullptr)) != hipSuccess) r = lhip("hipStreamSynchronize(quantise)", e);
     (void)hipFree(stage);
     return r;
@@ -234,13 +248,16 @@ void fvhd_llm_destroy(fvhd_llm* c)
 int fvhd_llm_set_weight_format(fvhd_llm* c, int format)
 {
     if (!c) return lfail("fvhd_llm_set_weight_format: ctx is NULL");
-    if (format != FVHD_W_BF16 && format != FVHD_W_E4M3) return lfail("fvhd_llm_set_weight_format: format must be FVHD_W_BF16 or FVHD_W_E4M3");
+    if (format != FVHD_W_BF16 && format != FVHD_W_E4M3 && format != FVHD_W_MXFP4)
+        return lfail("fvhd_llm_set_weight_format: format must be FVHD_W_BF16, FVHD_W_E4M3 or FVHD_W_MXFP4");
     if (c->any_set)
         return lfail("fvhd_llm_set_weight_format: a tensor was already set - choose the format right after fvhd_llm_create, before the first "
                      "fvhd_llm_set_tensor / fvhd_llm_set_tensor_device (the matrices are quantised as they arrive)");
     if (format == c->wfmt) return 0;
     if (format == FVHD_W_E4M3 && (c->H % 128 || (c->nh * c->hd) % 128 || c->I % 128))
         return lfail("fvhd_llm_set_weight_format: FVHD_W_E4M3 needs hidden, n_heads * head_dim and intermediate to be multiples of 128");
+    if (format == FVHD_W_MXFP4 && (c->H % 128 || (c->nh * c->hd) % 128 || c->I % 128))
+        return lfail("fvhd_llm_set_weight_format: FVHD_W_MXFP4 needs hidden, n_heads * head_dim and intermediate to be multiples of 128");
     LLM_ON_DEVICE(c);
     if (c->wdev) (void)hipFree(c->wdev);
     if (c->wscratch) (void)hipFree(c->wscratch);
@@ -250,7 +267,7 @@ int fvhd_llm_set_weight_format(fvhd_llm* c, int format)
     weight_layout(c);
     hipError_t e = hipMalloc((void**)&c->wdev, c->wbytes);
     if (e != hipSuccess) return lhip("hipMalloc(llm weights)", e);
-    if (format == FVHD_W_E4M3) {
+    if (format != FVHD_W_BF16) {
         for (int m = FVHD_MAT_QKV; m <= FVHD_MAT_LM_HEAD; ++m) {          // the largest matrix as bf16 (every layer has the same sizes)
             const Mat d = mat_of(c, 0, m);
             c->wscratch_bytes = std::max(c->wscratch_bytes, (size_t)d.N * d.K * 2);
@@ -289,7 +306,7 @@ int fvhd_llm_set_tensor(fvhd_llm* c, const char* key, const void* host_data, int
     if (!ok) return lfail(std::string("fvhd_llm_set_tensor: bad shape for ") + key);
     int e = 0;
     if (vec) e = upload_vector_f32(host_data, dtype, sl.rows, c->wdev + sl.base + sl.eoff * 4);
-    else if (c->wfmt == FVHD_W_E4M3) e = upload_matrix_q(c, host_data, dtype, sl);
+    else if (c->wfmt != FVHD_W_BF16) e = upload_matrix_q(c, host_data, dtype, sl);
     else e = upload_matrix(host_data, dtype, sl.rows, sl.cols, c->wdev + sl.base + sl.eoff * 2, sl.pitch);
     if (e) return e;
     c->got[idx] = 1;
@@ -331,6 +348,8 @@ int fvhd_llm_set_tensor_device(fvhd_llm* c, const char* key, const void* dev_dat
     if (vec) e = hipMemcpyAsync(c->wdev + sl.base + sl.eoff * 4, dev_data, rows * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream);
     else if (c->wfmt == FVHD_W_E4M3) {                          // quantised on `stream` straight from the caller's tensor
         if (int qe = quantize_into(c, sl, dev_data, (hipStream_t)stream)) return qe;
+    } else if (c->wfmt == FVHD_W_MXFP4) {
+        if (int qe = quantize_into_w4(c, sl, dev_data, (hipStream_t)stream)) return qe;
     } else
         e = hipMemcpy2DAsync(c->wdev + sl.base + sl.eoff * 2, sl.pitch * 2, dev_data, cols * 2, cols * 2, rows, hipMemcpyDeviceToDevice, (hipStream_t)stream);
     if (e != hipSuccess) return lhip("hipMemcpyAsync(llm weights, device to device)", e);
@@ -359,6 +378,7 @@ int fvhd_llm_finalize(fvhd_llm* c)
 int fvhd_llm_debug_packed_e4m3(fvhd_llm* c, int layer, int matrix, void* codes_out, float* scale_out, fvhd_stream_t stream)
 {
     if (!c || !codes_out || !scale_out) return lfail("fvhd_llm_debug_packed_e4m3: NULL argument");
+    if (c->wfmt == FVHD_W_MXFP4) return lfail("fvhd_llm_debug_packed_e4m3: the context holds MXFP4 weights, not e4m3 (fvhd_llm_debug_packed_mxfp4)");
     if (c->wfmt != FVHD_W_E4M3) return lfail("fvhd_llm_debug_packed_e4m3: the context holds bf16 weights (fvhd_llm_set_weight_format)");
     if (matrix < FVHD_MAT_QKV || matrix > FVHD_MAT_LM_HEAD || (matrix != FVHD_MAT_LM_HEAD && (layer < 0 || layer >= c->L)))
         return lfail("fvhd_llm_debug_packed_e4m3: matrix must be FVHD_MAT_QKV .. FVHD_MAT_LM_HEAD and layer in [0, n_layers)");
@@ -367,6 +387,21 @@ int fvhd_llm_debug_packed_e4m3(fvhd_llm* c, int layer, int matrix, void* codes_o
     if (int e = wait_for_loads(c)) return e;
     LCHECK(fvhd_launch_w8_unpack((hipStream_t)stream, c->wdev + m.off, nullptr, codes_out, m.N, m.K, 1), "fvhd_llm_debug_packed_e4m3");
     const hipError_t he = hipMemcpyAsync(scale_out, c->wdev + m.soff, (size_t)m.N * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    return he == hipSuccess ? 0 : lhip("hipMemcpyAsync", he);
+}
+
+// one packed matrix of an MXFP4 context in plain [N, K] order: codes u8 [N][K / 2], block scales u8 [N][K / 32], device pointers
+int fvhd_llm_debug_packed_mxfp4(fvhd_llm* c, int layer, int matrix, void* codes_out, void* scales_out, fvhd_stream_t stream)
+{
+    if (!c || !codes_out || !scales_out) return lfail("fvhd_llm_debug_packed_mxfp4: NULL argument");
+    if (c->wfmt != FVHD_W_MXFP4) return lfail("fvhd_llm_debug_packed_mxfp4: the context does not hold MXFP4 weights (fvhd_llm_set_weight_format)");
+    if (matrix < FVHD_MAT_QKV || matrix > FVHD_MAT_LM_HEAD || (matrix != FVHD_MAT_LM_HEAD && (layer < 0 || layer >= c->L)))
+        return lfail("fvhd_llm_debug_packed_mxfp4: matrix must be FVHD_MAT_QKV .. FVHD_MAT_LM_HEAD and layer in [0, n_layers)");
+    const Mat m = mat_of(c, layer, matrix);
+    LLM_ON_DEVICE(c);
+    if (int e = wait_for_loads(c)) return e;
+    LCHECK(fvhd_launch_w4_unpack((hipStream_t)stream, c->wdev + m.off, nullptr, codes_out, m.N, m.K, 1), "fvhd_llm_debug_packed_mxfp4");
+    const hipError_t he = hipMemcpyAsync(scales_out, c->wdev + m.soff, (size_t)m.N * (m.K / 32), hipMemcpyDeviceToDevice, (hipStream_t)stream);
     return he == hipSuccess ? 0 : lhip("hipMemcpyAsync", he);
 }
 

@@ -105,7 +105,7 @@ class Qwen2Generator:
     def from_hf(cls, model, batch: int, capacity: int, prefill: Optional[Qwen2Prefill] = None, weights: str = "bf16") -> "Qwen2Generator":
         """model: a `transformers` Qwen2ForCausalLM / the reference's LlavaQwen2ForCausalLM on a HIP device; `prefill` reuses an existing
         context of that model (e.g. `ml_fastvlm_amd.builder.prefill_context(model)`) instead of packing the weights again.
-        weights: "bf16" or "fp8_e4m3" (`Qwen2Prefill.from_hf`); a `prefill` context in the other format is an error, never a silent repack."""
+        weights: "bf16", "fp8_e4m3" or "mxfp4" (`Qwen2Prefill.from_hf`); a `prefill` context in the other format is an error, never a silent repack."""
         _lib.weight_format_code(weights)
         if prefill is not None and getattr(prefill, "weight_format", "bf16") != weights:
             raise ValueError(f"Qwen2Generator.from_hf(weights={weights!r}): the prefill context passed holds {prefill.weight_format} weights - "

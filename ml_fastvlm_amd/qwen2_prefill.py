@@ -36,7 +36,8 @@ class Qwen2Prefill:
         self.hidden, self.n_layers, self.n_heads, self.n_kv_heads, self.head_dim = hidden, n_layers, n_heads, n_kv_heads, head_dim
         self.intermediate, self.vocab = intermediate, vocab
         self.tie_word_embeddings = None           # from_hf records the config's flag (the decode's input embedding depends on it)
-        self.weight_format = "bf16"               # set_weight_format: "fp8_e4m3" = the packed matrices as e4m3 codes + one scale per row
+        self.weight_format = "bf16"               # set_weight_format: "fp8_e4m3" = the packed matrices as e4m3 codes + one scale per row,
+                                                  # "mxfp4" = as e2m1 codes + one power-of-two scale per 32 elements of a row
         self._tensors_set = 0
 
     # ---- construction from the reference's module -------------------------------------------------------------------------------
@@ -45,7 +46,9 @@ class Qwen2Prefill:
         """model: a `transformers` Qwen2ForCausalLM (or the reference's LlavaQwen2ForCausalLM, whose decoder stack it is).
         weights: "bf16" (the default), or "fp8_e4m3" - every matrix of the decoder stack and lm_head stored as OCP e4m3 codes with one
         power-of-two scale per output row (`quantize_rows_e4m3`), quantised on the device as it is packed: half the bytes held and half the
-        bytes a decode step streams; activations, the KV cache and the arithmetic (bf16 MFMA, fp32 accumulation) stay what they are."""
+        bytes a decode step streams; or "mxfp4" - the same matrices as OCP MXFP4 (`quantize_blocks_mxfp4`: e2m1 codes, one power-of-two
+        scale per 32 elements of a row, 4.25 bits per weight; a coarse format).  Activations, the KV cache and the arithmetic (bf16 MFMA,
+        fp32 accumulation) stay what they are."""
         _lib.weight_format_code(weights)
         cfg = model.config
         dev = torch.device(device) if device is not None else next(model.parameters()).device
@@ -73,14 +76,15 @@ class Qwen2Prefill:
         return self
 
     def set_weight_format(self, weights: str) -> None:
-        """"bf16" or "fp8_e4m3" (`fvhd_llm_set_weight_format`): before the first tensor is set - the matrices are quantised as they arrive"""
+        """"bf16", "fp8_e4m3" or "mxfp4" (`fvhd_llm_set_weight_format`): before the first tensor is set - the matrices are quantised as they arrive"""
         code = _lib.weight_format_code(weights)
         if weights == self.weight_format:
             return
         if self._tensors_set:
             raise _lib.FvhdError(f"Qwen2Prefill.set_weight_format({weights!r}): {self._tensors_set} tensors were already set as "
                                  f"{self.weight_format} - choose the format before the first tensor (from_hf(model, weights=...))")
-        _lib.check(_lib.w8_lib().fvhd_llm_set_weight_format(self._h, code), "fvhd_llm_set_weight_format")
+        lib = _lib.w4_lib() if weights in _lib.MX_WEIGHT_FORMATS else _lib.w8_lib()
+        _lib.check(lib.fvhd_llm_set_weight_format(self._h, code), "fvhd_llm_set_weight_format")
         self.weight_format = weights
 
     @property
@@ -90,13 +94,27 @@ class Qwen2Prefill:
         _lib.check(_lib.w8_lib().fvhd_llm_weight_bytes(self._h, C.byref(n)), "fvhd_llm_weight_bytes")
         return int(n.value)
 
+    def _matrix_shape(self, matrix: int):
+        qkvw = (self.n_heads + 2 * self.n_kv_heads) * self.head_dim
+        return {_lib.MAT_QKV: (qkvw, self.hidden), _lib.MAT_O: (self.hidden, self.n_heads * self.head_dim),
+                _lib.MAT_GATE_UP: (2 * self.intermediate, self.hidden), _lib.MAT_DOWN: (self.hidden, self.intermediate),
+                _lib.MAT_LM_HEAD: (self.vocab, self.hidden)}[matrix]
+
+    def packed_mxfp4(self, layer: int, matrix: int):
+        """tests: one packed matrix of an "mxfp4" context in plain order -> (codes u8 [N, K / 2], scales u8 [N, K / 32]), the layout of
+        `quantize_blocks_mxfp4`; matrix as for `packed_e4m3`"""
+        N, K = self._matrix_shape(matrix)
+        codes = torch.empty((N, K // 2), device=self.device, dtype=torch.uint8)
+        scales = torch.empty((N, K // 32), device=self.device, dtype=torch.uint8)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.w4_lib().fvhd_llm_debug_packed_mxfp4(self._h, int(layer), int(matrix), _lib.ptr(codes), _lib.ptr(scales),
+                                                                 _lib.stream_ptr(self.device)), "fvhd_llm_debug_packed_mxfp4")
+        return codes, scales
+
     def packed_e4m3(self, layer: int, matrix: int):
         """tests: one packed matrix of an "fp8_e4m3" context in plain [N, K] order -> (codes float8_e4m3fn [N, K], scale fp32 [N]);
         matrix: `_lib.MAT_QKV` (q | k | v rows), `MAT_O`, `MAT_GATE_UP` (gate / up rows interleaved), `MAT_DOWN`, `MAT_LM_HEAD`"""
-        qkvw = (self.n_heads + 2 * self.n_kv_heads) * self.head_dim
-        N, K = {_lib.MAT_QKV: (qkvw, self.hidden), _lib.MAT_O: (self.hidden, self.n_heads * self.head_dim),
-                _lib.MAT_GATE_UP: (2 * self.intermediate, self.hidden), _lib.MAT_DOWN: (self.hidden, self.intermediate),
-                _lib.MAT_LM_HEAD: (self.vocab, self.hidden)}[matrix]
+        N, K = self._matrix_shape(matrix)
         codes = torch.empty((N, K), device=self.device, dtype=torch.uint8)
         scale = torch.empty((N,), device=self.device, dtype=torch.float32)
         with torch.cuda.device(self.device):
@@ -311,6 +329,45 @@ def quantize_rows_e4m3(w: torch.Tensor):
 def dequantize_rows_e4m3(codes: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     """codes * scale as fp32 [N, K] (exact; for power-of-two scales every value is a bf16 value)"""
     return codes.float() * scale.float()[:, None]
+
+
+E2M1_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)      # the magnitudes of the OCP e2m1 codes, by index (bits 2..0; bit 3 = sign)
+
+
+def quantize_blocks_mxfp4(w: torch.Tensor):
+    """The library's 4-bit weight recipe in plain torch (any device): w [N, K], K % 32 == 0, rounded to bf16 first (the library's matrices
+    are bf16) -> (codes u8 [N, K / 2], scales u8 [N, K / 32]).  Element k of a row is in byte k / 2, even k in the low nibble; a code is
+    sign (bit 3) + an index into E2M1_GRID; scale byte E of a block of 32 consecutive k stands for 2^(E - 127).
+    Per block: se = ceil(log2(amax / 6)) evaluated exactly from amax's bf16 bit pattern (amax = m 2^e, m in [1, 2): e - 2 + (m > 1.5)),
+    clamped to [-125, 125], 0 for an all-zero block, E = se + 127.  codes = |w| / 2^se (exact) to the nearest grid value, a tie to the even
+    index, above 6 saturating (possible only at the upper clamp); the sign bit is w's own, so a small negative becomes -0.  amax / 2^se lies
+    in (3, 6] and code * scale is exactly a bf16 value.  A coarse format: about 0.12 relative L2 error on a Gaussian matrix."""
+    if w.dim() != 2 or w.shape[1] % 32:
+        raise ValueError(f"quantize_blocks_mxfp4 takes a matrix [N, K] with K % 32 == 0, got {tuple(w.shape)}")
+    N, K = w.shape
+    bits = w.detach().to(torch.bfloat16).contiguous().view(torch.int16).to(torch.int32) & 0xffff
+    mag = (bits & 0x7fff).view(N, K // 32, 32)
+    am = mag.amax(-1)
+    se = ((am >> 7) - 127 - 2 + ((am & 0x7f) > 0x40).to(torch.int32)).clamp(-125, 125)
+    se = torch.where(am > 0, se, torch.zeros_like(se))
+    inv = ((127 - se) << 23).view(torch.float32)                          # 2^-se from its bit pattern
+    a = (mag << 16).view(torch.float32) * inv[..., None]
+    idx = ((a > 0.25).to(torch.int32) + (a >= 0.75) + (a > 1.25) + (a >= 1.75) + (a > 2.5) + (a >= 3.5) + (a > 5.0)).view(N, K)
+    code = ((bits >> 15) << 3) | idx
+    codes = (code[:, 0::2] | (code[:, 1::2] << 4)).to(torch.uint8)
+    return codes, (se + 127).to(torch.uint8)
+
+
+def dequantize_blocks_mxfp4(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """code * 2^(E - 127) as bf16 [N, K] (exact; a code with the sign bit and index 0 gives -0); scale bytes 1 .. 254"""
+    N, K = codes.shape[0], codes.shape[1] * 2
+    c = codes.to(torch.int32)
+    code = torch.stack([c & 0xf, c >> 4], -1).view(N, K)
+    grid = torch.tensor(E2M1_GRID, device=codes.device, dtype=torch.float32)
+    val = grid[code & 7]
+    val = torch.where((code & 8) != 0, -val, val)
+    scale = (scales.to(torch.int32) << 23).view(torch.float32)
+    return (val.view(N, K // 32, 32) * scale[..., None]).view(N, K).to(torch.bfloat16)
 
 
 def kv_to_dynamic_cache(k: torch.Tensor, v: torch.Tensor):

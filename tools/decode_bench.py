@@ -5,6 +5,7 @@ captured graph and called eagerly, against the stock `transformers` decode loop 
     python tools/decode_bench.py --sample [--hidden 896] [--batch 1 8]
     python tools/decode_bench.py --trace-steps 16 --hidden 3584 --batch 64      (eager steps only: the program of a kernel trace)
     python tools/decode_bench.py --weights fp8_e4m3 ...                         (the packed matrices as e4m3 codes + row scales)
+    python tools/decode_bench.py --weights mxfp4 ...                            (as MXFP4: e2m1 codes + one scale byte per 32 elements)
     python tools/decode_bench.py --num-beams 4 --hidden 896 3584 --batch 1 16   (beam search: --batch prompts x K beams per step)
     python tools/decode_bench.py --processors --hidden 896 --batch 1 64         (logits processors on against off, greedy and sampled)
     python tools/decode_bench.py --lookup --hidden 896 3584 --rows 4 8 16       (prompt-lookup decoding: the verify step at one sequence)
@@ -100,10 +101,8 @@ def measure(llm, pre, batch: int, prompt: int, new: int, dev, repeats: int = 1, 
         assert gen.cache_state() == (prompt + new, 0)
     res["graph_ms_per_token"] = sorted(runs)[len(runs) // 2]
     res["graph_ms_per_token_runs"] = runs
-    I, H, nh, nkv, hd, V = cfg.intermediate_size, hidden, cfg.num_attention_heads, cfg.num_key_value_heads, hidden // cfg.num_attention_heads, cfg.vocab_size
-    wbytes = cfg.num_hidden_layers * ((nh + 2 * nkv) * hd * H + H * nh * hd + 3 * I * H) * 2 + V * H * 2
-    if weights == "fp8_e4m3":                               # one byte per element + one fp32 scale per output row
-        wbytes = wbytes // 2 + 4 * (cfg.num_hidden_layers * ((nh + 2 * nkv) * hd + 2 * H + 2 * I) + V)
+    nkv, hd = cfg.num_key_value_heads, hidden // cfg.num_attention_heads
+    wbytes = step_weight_bytes(cfg, weights)
     kvbytes = cfg.num_hidden_layers * batch * nkv * (prompt + new / 2) * hd * 2 * 2
     res["weight_bytes_per_token"] = int(wbytes)
     res["kv_bytes_per_token"] = int(kvbytes)
@@ -483,6 +482,18 @@ def measure_beam(llm, pre, groups: int, K: int, prompt: int, new: int, dev, repe
     return res
 
 
+def step_weight_bytes(cfg, weights: str) -> int:
+    """bytes of the packed matrices one decode step streams (every layer's q|k|v, o, gate|up, down and lm_head)"""
+    I, H, nh, nkv, V = cfg.intermediate_size, cfg.hidden_size, cfg.num_attention_heads, cfg.num_key_value_heads, cfg.vocab_size
+    hd = H // nh
+    elems = cfg.num_hidden_layers * ((nh + 2 * nkv) * hd * H + H * nh * hd + 3 * I * H) + V * H
+    if weights == "fp8_e4m3":                               # one byte per element + one fp32 scale per output row
+        return elems + 4 * (cfg.num_hidden_layers * ((nh + 2 * nkv) * hd + 2 * H + 2 * I) + V)
+    if weights == "mxfp4":                                  # half a byte per element + one scale byte per 32 elements
+        return elems // 2 + elems // 32
+    return elems * 2
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--hidden", type=int, nargs="+", default=[896, 1536, 3584])
@@ -492,7 +503,8 @@ def main():
     ap.add_argument("--sample", action="store_true", help="the sampled step against the greedy one (default widths: 896 only)")
     ap.add_argument("--repeats", type=int, default=1, help="time the graph replay this many times")
     ap.add_argument("--no-stock", action="store_true", help="leave out the stock transformers loop and the eager library step")
-    ap.add_argument("--weights", choices=["bf16", "fp8_e4m3"], default="bf16", help="storage of the packed LLM matrices (fp8_e4m3 needs a library of version 504)")
+    ap.add_argument("--weights", choices=["bf16", "fp8_e4m3", "mxfp4"], default="bf16",
+                    help="storage of the packed LLM matrices (fp8_e4m3 needs a library of version 504, mxfp4 one built with the 4-bit entry points)")
     ap.add_argument("--trace-steps", type=int, default=0, help="run only the prefill and this many eager steps (for a kernel trace)")
     ap.add_argument("--processors", action="store_true", help="the step with all four logits processors on against off (needs a library of version 506)")
     ap.add_argument("--num-beams", type=int, default=0, help="time beam search with this many beams per prompt (--batch = prompts; needs a library of version 505)")
