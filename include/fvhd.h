@@ -277,7 +277,9 @@ int fvhd_op_dw7s2_mfma(fvhd_stream_t stream, const void* x, void* y, const float
 int fvhd_op_dw7_amax(fvhd_stream_t stream, const void* x, void* y, const float* w, const float* bias, int B, int H, int W, int C, int mfma,
                      void* amax_bits);
 /* out[M,N] = epi(A[M,K] . Wt[N,K]^T): A, Wt, resid bf16; bias, ls fp32 [N]; K % 32 == 0, N % 16 == 0.  out_dtype other than bf16 only with
- * FVHD_EPI_BIAS (f16 / f32) and FVHD_EPI_NONE (f32: lm_head logits); FVHD_EPI_SWIGLU writes [M, N/2]. */
+ * FVHD_EPI_BIAS (f16 / f32) and FVHD_EPI_NONE (f32: lm_head logits); FVHD_EPI_SWIGLU writes [M, N/2].  A NULL A, Wt or out, and a NULL bias /
+ * ls / resid under an epilogue that reads it (bias: BIAS, BIAS_GELU, BIAS_LS_RESID; ls: BIAS_LS_RESID; resid: BIAS_LS_RESID, RESID), is refused
+ * with an error and nothing is launched; the vectors an epilogue does not read may be NULL. */
 int fvhd_op_gemm(fvhd_stream_t stream, const void* A, const void* Wt, const float* bias, const float* ls,
                  const void* resid, void* out, int M, int N, int K, int epilogue, int out_dtype);
 /* the residual GEMM of ConvFFN.fc2 / MHSA.proj (out = resid + ls * (A . Wt^T + bias); mci.py:926 + 1106-1109, :681 + 1185-1187) with K split over

@@ -1262,6 +1262,10 @@ int fvhd_op_dw7_amax(fvhd_stream_t st, const void* x, void* y, const float* w, c
 int fvhd_op_gemm(fvhd_stream_t st, const void* A, const void* Wt, const float* bias, const float* ls, const void* resid,
                  void* out, int M, int N, int K, int epilogue, int out_dtype)
 {
+    if (!A || !Wt || !out) return fail("fvhd_op_gemm: NULL pointer");
+    if ((epilogue == FVHD_EPI_BIAS || epilogue == FVHD_EPI_BIAS_GELU || epilogue == FVHD_EPI_BIAS_LS_RESID) && !bias) return fail("fvhd_op_gemm: this epilogue needs bias");
+    if (epilogue == FVHD_EPI_BIAS_LS_RESID && !ls) return fail("fvhd_op_gemm: FVHD_EPI_BIAS_LS_RESID needs ls");
+    if ((epilogue == FVHD_EPI_BIAS_LS_RESID || epilogue == FVHD_EPI_RESID) && !resid) return fail("fvhd_op_gemm: this epilogue needs resid");
     int e = fvhd_launch_gemm((hipStream_t)st, A, Wt, bias, ls, resid, out, M, N, K, epilogue, out_dtype);
     return e ? hip_fail("fvhd_op_gemm", (hipError_t)e) : 0;
 }

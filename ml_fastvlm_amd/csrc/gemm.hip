@@ -1113,6 +1113,9 @@ extern "C" int fvhd_launch_gemm(hipStream_t st, const void* A, const void* Wt, c
     const bf16* a = (const bf16*)A;
     const bf16* w = (const bf16*)Wt;
     const bf16* r = (const bf16*)resid;
+    // a vector the epilogue reads must be there: the kernels dereference it without a look
+    const bool reads_bias = epi == EPI_BIAS || epi == EPI_BIAS_GELU || epi == EPI_BIAS_LS_RESID, reads_resid = epi == EPI_BIAS_LS_RESID || epi == EPI_RESID;
+    if (!A || !Wt || !out || (reads_bias && !bias) || (epi == EPI_BIAS_LS_RESID && !ls) || (reads_resid && !resid)) return (int)hipErrorInvalidValue;
     switch (gemm_plan(M, N, K, epi, out_dtype)) {
     case FVHD_GEMM_PLAN_V1S: return (int)dispatch_gemm128s(st, a, w, bias, ls, r, out, M, N, K, epi);
     case FVHD_GEMM_PLAN_PINGPONG: return (int)dispatch_gemm_pp(st, a, w, bias, ls, r, out, M, N, K, epi);

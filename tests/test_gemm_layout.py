@@ -47,6 +47,7 @@ int main()
     for (int BN : {64, 128, 256}) bad += check<1>(BN) + check<2>(BN) + check<4>(BN);
     static_assert(EpiGrp<4, 0, 2>::value == 2 && EpiGrp<4, 3, 2>::value == 2 && EpiGrp<4, 5, 2>::value == 4, "bf16 rows: pairs; SwiGLU: quads");
     static_assert(EpiGrp<3, 0, 2>::value == 1 && EpiGrp<4, 0, 0>::value == 1 && EpiGrp<4, 1, 1>::value == 1, "96-wide tile, fp32 / f16 outputs: identity");
+    static_assert(EpiGrp<3, 5, 2>::value == 1 && EpiGrp<8, 5, 2>::value == 4, "SwiGLU on the 96-wide tile: identity and 4-byte stores (tests/test_gpu_prefill_gemm_ops.py)");
     std::printf(bad ? "FAILED %d\n" : "ok\n", bad);
     return bad != 0;
 }

@@ -53,48 +53,20 @@ P = _lib
 V1 = (P.GEMM_PLAN_V1_NF4_BK64, P.GEMM_PLAN_V1_NF4_BK32, P.GEMM_PLAN_V1_NF3_BK64, P.GEMM_PLAN_V1_NF3_BK32)
 
 
-def _bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(a.view(torch.int16 if a.dtype.itemsize == 2 else torch.int32),
-                                                                     b.view(torch.int16 if b.dtype.itemsize == 2 else torch.int32))
+_bits = T.bits
 
 
 def _plan(lib, M, N, K, epi, dtype=BF16):
-    return _lib.gemm_plan_lib().fvhd_gemm_kernel_plan(M, N, K, epi, _lib.dtype_code(dtype))
+    return T.plan(M, N, K, epi, dtype)
 
 
 # ---- GEMM ---------------------------------------------------------------------------------------------------------------------------------
 def _gemm_case(lib, plan, M, N, K, epi, family, dtype=BF16, seed=0, other_rows=()):
-    """one (shape, epilogue, family) of one kernel class: plan asserted, guarded launch, inputs unchanged, second launch (in place for
-    the residual epilogue, as the tower calls it) bit-identical, then the family's contract.  other_rows: row counts M' whose launch on
-    the first M' rows takes ANOTHER class and must give the same bits."""
-    assert _plan(lib, M, N, K, epi, dtype) == plan, (M, N, K, epi, _plan(lib, M, N, K, epi, dtype), plan)
-    A, W, b, ls, r = R.gemm_family(family, M, N, K, epi, seed + 1000 * epi, device=DEV)
-    out = T.gemm(lib, A, W, b, ls, r, epi, dtype)
-    assert _bits(out, T.gemm(lib, A, W, b, ls, r, epi, dtype, inplace=epi == LSR)), "a second launch gave other bits"
-    want, S = R.gemm_ref(A, W, b, ls, r, epi)
-    what = f"gemm plan {plan} {M}x{N}x{K} epi {epi} {str(dtype)[6:]} {family}"
-    if family == "exact":
-        assert torch.equal(out, want.to(dtype)), f"{what}: not the bits of the exact result"
-        print(f"{what}: exact")
-    else:
-        line = f"{what}: worst err / bound {R.inside(out, want, R.gemm_bound(want, S, epi, dtype, ls), what):.3f}"
-        if epi == GELU:      # GELU7_ABS is the polynomial's own error: against the polynomial of the fp64 pre-activation nothing of it is needed
-            line += f", against the documented polynomial {R.inside(out, *R.poly_contract(R.gemm_ref(A, W, b, epi=BIAS)[0], R.C_ACC * S, dtype), what + ' (polynomial)'):.3f}"
-        print(line)
-    for Mp in other_rows:
-        p2 = _plan(lib, Mp, N, K, epi, dtype)
-        assert p2 >= 0 and p2 != plan, (Mp, p2)
-        sub = T.gemm(lib, A[:Mp].contiguous(), W, b, ls, r[:Mp].contiguous() if r is not None else None, epi, dtype)
-        assert _bits(sub, out[:Mp]), f"{what}: class {p2} on the first {Mp} rows gives other bits"
-    return out
+    """tower_testlib.gemm_case (shared with tests/test_gpu_prefill_gemm_ops.py) -> out"""
+    return T.gemm_case(lib, plan, M, N, K, epi, family, dtype, seed, other_rows)[0]
 
 
-V1_SHAPES = [   # (plan, M, N, K): ragged N at 16-column granularity, one K tile (32: BK 32, 64: BK 64), three (96), M around the 128-row tile
-    (P.GEMM_PLAN_V1_NF4_BK32, 1, 16, 32), (P.GEMM_PLAN_V1_NF4_BK64, 127, 48, 64), (P.GEMM_PLAN_V1_NF4_BK32, 128, 80, 96), (P.GEMM_PLAN_V1_NF4_BK32, 129, 144, 32),
-    (P.GEMM_PLAN_V1_NF4_BK64, 257, 208, 64), (P.GEMM_PLAN_V1_NF4_BK32, 257, 272, 96),
-    (P.GEMM_PLAN_V1_NF4_BK64, 257, 1152, 64),      # tiles_n = 9: the last super-tile group is narrower
-    (P.GEMM_PLAN_V1_NF3_BK32, 129, 96, 96), (P.GEMM_PLAN_V1_NF3_BK64, 257, 288, 64), (P.GEMM_PLAN_V1_NF3_BK32, 1, 96, 32), (P.GEMM_PLAN_V1_NF3_BK64, 128, 192, 128),
-]
+V1_SHAPES = T.V1_SHAPES
 
 
 @pytest.mark.parametrize("plan,M,N,K", V1_SHAPES)
@@ -125,9 +97,8 @@ def test_gemm_v1s(lib, M, N, K):
 
 def _streaming(lib, plan, M, N, K, full, other_rows=(256, 200)):
     """a class with 256-row tiles: the first 256 rows alone take v1s and the first 200 v1 - both must give the bits of the large launch"""
-    for epi, family in ([(NONE, "exact"), (BIAS, "exact"), (LSR, "exact"), (NONE, "rc"), (BIAS, "rc"), (GELU, "rc"), (LSR, "rc")] if full else
-                        [(LSR, "exact"), (GELU, "rc"), (LSR, "rc")]):
-        _gemm_case(lib, plan, M, N, K, epi, family, other_rows=other_rows if family == "rc" else ())
+    T.streaming(lib, plan, M, N, K, [(NONE, "exact"), (BIAS, "exact"), (LSR, "exact"), (NONE, "rc"), (BIAS, "rc"), (GELU, "rc"), (LSR, "rc")] if full else
+                [(LSR, "exact"), (GELU, "rc"), (LSR, "rc")], other_rows)
 
 
 @pytest.mark.parametrize("M,N,K,full", [(8192, 2048, 128, True), (8192, 2048, 192, False), (11008, 384, 3072, False)])     # 512 tiles; the long-K rule with N % 256 != 0

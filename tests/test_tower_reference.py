@@ -41,6 +41,7 @@ def test_refs_agree_with_the_oracle():
     A, W, b, ls, r = rn(9, 64), rn(48, 64) / 8, rn(48), torch.rand(48, generator=g), rn(9, 48)
     _fp32_close(R.gemm_ref(A, W, b, None, None, R.EPI_BIAS_GELU)[0], O.gelu(F.linear(A, W, b)))
     _fp32_close(R.gemm_ref(A, W, b, ls, r, R.EPI_BIAS_LS_RESID)[0], r + ls * F.linear(A, W, b))
+    _fp32_close(R.gemm_ref(A, W, None, None, r, R.EPI_RESID)[0], r + F.linear(A, W))
     # layernorm_channel on NCHW
     M, C = 7, 96
     xx, w, bb = 2 * rn(M, C) + 0.5, torch.rand(C, generator=g) + 0.5, 0.1 * rn(C)
@@ -121,6 +122,58 @@ def test_gemm_model_under_half_the_bound():
     assert worst_acc <= 0.5 * R.C_ACC
     # the exact family's premise: partial sums below 2^24 up to K = 6144
     assert 9 * 6144 + 3 < 2 ** 24
+
+
+def test_swiglu_ref_is_the_qwen2_mlp_front():
+    """gemm_ref(EPI_SWIGLU) on W = rows interleaved gate_j, up_j is F.silu(gate_proj(x)) * up_proj(x) of transformers' Qwen2MLP in fp64"""
+    from transformers import Qwen2Config
+    from transformers.models.qwen2.modeling_qwen2 import Qwen2MLP
+    torch.manual_seed(0)
+    H, I, M = 64, 48, 9
+    mlp = Qwen2MLP(Qwen2Config(hidden_size=H, intermediate_size=I)).double()
+    x = torch.randn(M, H, dtype=torch.float64)
+    W = torch.stack([mlp.gate_proj.weight, mlp.up_proj.weight], 1).reshape(2 * I, H).detach()      # row 2j = gate_j, row 2j + 1 = up_j
+    assert torch.equal(W[0::2], mlp.gate_proj.weight) and torch.equal(W[1::2], mlp.up_proj.weight)       # de-interleaved: the module's own
+    want, S = R.gemm_ref(x, W, epi=R.EPI_SWIGLU)
+    with torch.no_grad():
+        front = mlp.act_fn(mlp.gate_proj(x)) * mlp.up_proj(x)
+        assert isinstance(mlp.act_fn, torch.nn.SiLU) or float((mlp.act_fn(x) - F.silu(x)).abs().max()) == 0.0
+        assert want.shape == (M, I) and S.shape == (M, 2 * I)
+        assert float((want - front).abs().max()) <= 1e-14 * float(front.abs().max())
+        assert float((mlp.down_proj(want) - mlp(x)).abs().max()) <= 1e-13 * float(mlp(x).abs().max())
+
+
+PREFILL_EPIS = (R.EPI_RESID, R.EPI_SWIGLU)
+
+
+def _bound(A, W, ls, r, epi):
+    want, S = R.gemm_ref(A, W, None, ls, r, epi)
+    pre = A.double() @ W.double().t() if epi == R.EPI_SWIGLU else None
+    return want, R.gemm_bound(want, S, epi, torch.bfloat16, ls, pre=pre), pre
+
+
+def test_prefill_epilogue_models_under_half_the_bound():
+    """EPI_RESID / EPI_SWIGLU: the fault-free model on "rc" at or below half its bound; on "exact" the bits of bf16(fp64) (RESID) and
+    one bf16 ulp with the gate sums inside +-GATE_MAX (SwiGLU's pairing family) - and inside the rc bound there as well"""
+    worst = {}
+    for N, K in GEMM_NK:
+        for epi in PREFILL_EPIS:
+            for fam in ("rc", "exact"):
+                A, W, b, ls, r = R.gemm_family(fam, 48, N, K, epi, seed=N + K + epi)
+                assert b is None and ls is None and (r is None) == (epi == R.EPI_SWIGLU)
+                want, bound, pre = _bound(A, W, ls, r, epi)
+                assert want.shape == (48, N // 2 if epi == R.EPI_SWIGLU else N)
+                got = R.gemm_model(A, W, b, ls, r, epi)
+                bad, ratio = R.within(got, want, bound)
+                worst[(epi, fam)] = max(worst.get((epi, fam), 0.0), ratio)
+                assert bad == 0 and ratio <= 0.5, (N, K, epi, fam, ratio)
+                if fam == "exact" and epi == R.EPI_RESID:
+                    assert torch.equal(got, want.to(torch.bfloat16)), (N, K)
+                elif fam == "exact":
+                    assert float(pre[:, 0::2].abs().max()) <= R.GATE_MAX < 60 and R.one_ulp(got, want.to(torch.bfloat16)) == 0, (N, K)
+                    assert float((R.acc32(A, W).double() - pre).abs().max()) == 0.0            # both sums exact in fp32
+    print("prefill epilogues, model: worst err / bound " + ", ".join(f"epi {e} {f} {v:.3f}" for (e, f), v in worst.items()))
+    assert float(R.sig_rel(torch.tensor(60.0))) < 1e-3 * R.U[torch.bfloat16]      # the fast sigmoid's allowance never carries a comparison
 
 
 @pytest.mark.parametrize("precision", [_lib.FFN_HALF, _lib.FFN_BF16])
@@ -238,6 +291,44 @@ def test_gemm_faults_are_rejected_and_the_pooled_bound_lets_the_small_ones_pass(
     assert 1 <= int(small.sum()) <= M // 4
     faulty = torch.where(small, R.gemm_model(A, W, fault="skip_last_k"), R.gemm_model(A, W))
     assert _rejected(faulty, want, R.gemm_bound(want, S, R.EPI_NONE)) and _passes_pooled(faulty, want)
+
+
+PREFILL_FAULTS = ((R.EPI_SWIGLU, "swap_gate_up"), (R.EPI_SWIGLU, "pair_shift"), (R.EPI_RESID, "resid_neighbour8"), (R.EPI_RESID, "resid_dropped"))
+
+
+@pytest.mark.parametrize("epi,fault", PREFILL_FAULTS)
+def test_prefill_epilogue_faults_are_rejected(epi, fault):
+    """each fault of the prefill's epilogues fails the per-element bound on "rc" AND the exact family's check (bits for RESID, one ulp
+    for SwiGLU's pairing family); the violation counts are asserted > 0 and printed.  ("resid_dropped" hits the 16-column group of the
+    smallest columns: the next test shows that the pooled bound of the first op tests lets it pass.)"""
+    M, N, K = 32, 48, 64
+    A, W, b, ls, r = R.gemm_family("rc", M, N, K, epi, seed=3)
+    want, bound, _ = _bound(A, W, ls, r, epi)
+    group = int(W.float().abs().amax(1).view(N // 16, 16).amax(1).argmin())
+    assert R.within(R.gemm_model(A, W, b, ls, r, epi), want, bound)[0] == 0
+    faulty = R.gemm_model(A, W, b, ls, r, epi, fault=fault, group=group)
+    n_rc = R.within(faulty, want, bound)[0]
+    A, W, b, ls, r = R.gemm_family("exact", M, N, K, epi, seed=3)
+    want16 = R.gemm_ref(A, W, b, ls, r, epi)[0].to(torch.bfloat16)
+    good, faulty = R.gemm_model(A, W, b, ls, r, epi), R.gemm_model(A, W, b, ls, r, epi, fault=fault, group=group)
+    if epi == R.EPI_RESID:
+        assert torch.equal(good, want16)
+        n_exact = int((faulty != want16).sum())
+    else:
+        assert R.one_ulp(good, want16) == 0
+        n_exact = R.one_ulp(faulty, want16)
+    print(f"epi {epi} fault {fault}: {n_rc} of {want.numel()} elements outside the rc bound, {n_exact} of {want16.numel()} fail the exact family")
+    assert n_rc > 0 and n_exact > 0, (epi, fault, n_rc, n_exact)
+
+
+def test_dropped_residual_of_small_columns_passes_the_pooled_bound():
+    M, N, K = 32, 48, 64
+    A, W, _, _, r = R.gemm_family("rc", M, N, K, R.EPI_RESID, seed=3)
+    order = W.float().abs().amax(1).argsort()
+    W, r = W[order], r[:, order].contiguous()                     # columns in ascending scale: group 0 is the smallest
+    want, bound, _ = _bound(A, W, None, r, R.EPI_RESID)
+    faulty = R.gemm_model(A, W, None, None, r, R.EPI_RESID, fault="resid_dropped", group=0)
+    assert _rejected(faulty, want, bound) and _passes_pooled(faulty, want)
 
 
 def test_ffn_fault_is_rejected():

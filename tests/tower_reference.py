@@ -1,5 +1,5 @@
-"""TEST INFRASTRUCTURE ONLY - plain torch fp64 restatements of the vision tower's single operations (csrc/gemm.hip, ffn_fused.hip,
-attention.hip, stem_head.hip, dwconv*.hip) on the bf16-rounded operands, written from oracle/fastvithd_oracle.py and the arithmetic
+"""TEST INFRASTRUCTURE ONLY - plain torch fp64 restatements of the vision tower's single operations (csrc/gemm.hip - with the two
+epilogues the Qwen2 prefill adds to the same kernel family -, ffn_fused.hip, attention.hip, stem_head.hip, dwconv*.hip) on the bf16-rounded operands, written from oracle/fastvithd_oracle.py and the arithmetic
 include/fvhd.h documents, not from the kernels; the per-element bounds of tests/test_gpu_tower_ops.py; the seeded input families of
 those tests; and CPU models of the arithmetic a kernel is ALLOWED (bf16 operands, fp32 accumulation over the K tiles in order, the
 polynomial GELUs, bf16 P over 64-key tiles with the online rescale, ONE rounding to the output type) that only serve to show that the
@@ -10,6 +10,10 @@ BOUNDS (per element; every rms is per row; nothing is pooled and no element is e
 to T - 2^-7 bf16, 2^-10 f16 (+ 2^-24 absolute: its subnormal step), 2^-22 f32 - as the prefill tests state it:
   GEMM             |err| <= u(T) |want| + C_ACC f S (+ GELU7_ABS),  S = |A| @ |W|^T;  f = 1, |ls_n| (EPI_BIAS_LS_RESID) or GELU_SLOPE = 1.13
                    (EPI_BIAS_GELU: the accumulation error passes through the GELU, max |gelu'| = 1.129)
+                   EPI_RESID (Qwen2 prefill: o_proj, down_proj): the form of EPI_BIAS_LS_RESID with ls = 1 and no bias
+  GEMM, SwiGLU     |err| <= u(bf16) |want| + C_ACC (SILU_SLOPE S_gate |up| + |silu(gate)| S_up) + sig_rel(gate) |want|, want = silu(gate) up
+                   [M, N / 2]; S_gate, S_up the |A| @ |W|^T sums of the two columns; SILU_SLOPE = 1.1 (max |silu'| = 1.0998); sig_rel(g) =
+                   2^-20 + 2^-24 |g|, the fast sigmoid's fp32 chain (derived at sig_rel; four orders of magnitude below u)
   fused FFN        2^-7 |want| + |ls_n| sum_h ((e_phi |pre_mh| + u_hid |hid_mh|) + C_ACC (1.13 S1_mh + |hid_mh|)) |W2_nh|,  S1 = |A| @ |W1|^T
                    e_phi: 1.4e-3 (FFN_HALF, include/fvhd.h) / 2.33e-4 (FFN_BF16, csrc/fvhd_common.h);  u_hid: 2^-11 (f16) / 2^-8 (bf16)
   attention        2e-2 |want| + 2e-2 rms(row), a row = one (image, query, head) vector of 32 values: the project's budget
@@ -20,7 +24,8 @@ to T - 2^-7 bf16, 2^-10 f16 (+ 2^-24 absolute: its subnormal step), 2^-22 f32 - 
 MEASURED (tests/test_tower_reference.py prints them; `python -m pytest tests/test_tower_reference.py -s`), over every family and every
 (N, K) class the GPU tests use:
   GEMM, K = 32 .. 3136, fp32 sums of 32-wide K slabs in order: worst |acc32 - acc64| / S = 8.8e-8 -> C_ACC = 2^-22 = 2.4e-7 (2.7 times
-        that); the whole model, rounded once, sits at 0.498 (bf16), 0.496 (f16), 0.26 (f32) of the bound
+        that); the whole model, rounded once, sits at 0.498 (bf16), 0.496 (f16), 0.26 (f32) of the bound; EPI_RESID 0.498, EPI_SWIGLU
+        0.497 ("rc") and 0.494 (the integer pairing family, where it is also within one bf16 ulp element by element)
   layernorm, C = 4 .. 2048, two-pass fp32 statistics: worst error before the rounding / ((|x| + |mean|) rstd |w|) = 3.7e-7 (the
         large-mean family) -> C_LN = 2^-20 = 9.5e-7; the model sits at 0.498 of the bound
   fused FFN model 0.26 (FFN_HALF) / 0.19 (FFN_BF16); attention model 0.41 (qscale) and below; depthwise 0.497; SE head <= 0.5
@@ -30,7 +35,10 @@ MEASURED (tests/test_tower_reference.py prints them; `python -m pytest tests/tes
         attained near x = -3: a model that evaluates the polynomial reaches 0.94 of a bound with a GELU term, by definition.  The margin
         of two is therefore shown with the exact GELU in the model (0.49), and the polynomial model only has to stay inside.
 PINNING: tests/test_tower_reference.py checks every *_ref against oracle.fastvithd_oracle in fp32, every model against half its bound on
-every family, and that the bound rejects ten planted faults (nine of them; the tenth provably cannot be seen in a bf16 output)."""
+every family, and that the bound rejects ten planted faults (nine of them; the tenth provably cannot be seen in a bf16 output); for the
+prefill's two epilogues (tests/test_gpu_prefill_gemm_ops.py) gemm_ref against transformers' Qwen2MLP in fp64, the model on both families,
+and four more faults (gate / up swapped, gate j with up j + 1, the residual of the neighbouring 8 columns, a residual dropped on 16
+columns), each rejected by the "rc" bound AND by the exact family."""
 from __future__ import annotations
 
 import math
@@ -48,12 +56,14 @@ from llm_testlib import SENT, check, close, close_pooled, guard_intact, guarded,
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_LS_RESID = _lib.EPI_NONE, _lib.EPI_BIAS, _lib.EPI_BIAS_GELU, _lib.EPI_BIAS_LS_RESID
+EPI_RESID, EPI_SWIGLU = _lib.EPI_RESID, _lib.EPI_SWIGLU          # the Qwen2 prefill's epilogues of the same kernel family
 
 U = {torch.bfloat16: 2.0 ** -7, torch.float16: 2.0 ** -10, torch.float32: 2.0 ** -22}     # twice the worst case of one rounding
 U_ABS = {torch.bfloat16: 0.0, torch.float16: 2.0 ** -24, torch.float32: 0.0}                # ... of a SUBNORMAL result (f16 below 6.1e-5: steps of 2^-24)
 C_ACC = 2.0 ** -22             # fp32 accumulation, as a fraction of S (measured: see the docstring)
 C_LN = 2.0 ** -20              # layernorm's fp32 statistics, as a fraction of (|x| + |mean|) rstd |w|
 GELU_SLOPE = 1.13              # max |gelu'(x)| = 1.129 (at x = 1.41)
+SILU_SLOPE = 1.1               # max |silu'(x)| = 1.0998 (at x = 2.4)
 GELU7_ABS, PHI7 = 1.33e-4, 3.31e-5     # csrc/fvhd_common.h: the degree-7 fit every kernel but the fused FFN evaluates
 GELU5_ABS, PHI5 = 8.2e-4, 2.33e-4     # csrc/fvhd_common.h: the degree-5 fit of the fused FFN's FFN_BF16 form
 PHI_HALF = 1.4e-3                      # include/fvhd.h: |Phi error| of the FFN_HALF form
@@ -163,9 +173,14 @@ def gelu_half16(x_over_4):
 
 # ---- GEMM ---------------------------------------------------------------------------------------------------------------------------------
 def gemm_ref(A, W, bias=None, ls=None, resid=None, epi=EPI_NONE):
-    """fvhd_op_gemm in fp64 on the operands as given (bf16 A, W, resid; fp32 bias, ls) -> (want [M, N], S = |A| @ |W|^T)"""
+    """fvhd_op_gemm in fp64 on the operands as given (bf16 A, W, resid; fp32 bias, ls) -> (want, S = |A| @ |W|^T [M, N]); want is
+    [M, N], for EPI_SWIGLU [M, N / 2]: silu(A.W^T[:, 2j]) * A.W^T[:, 2j + 1], the rows of W interleaved gate_j, up_j"""
     a, w = A.double(), W.double()
     y, S = a @ w.t(), a.abs() @ w.abs().t()
+    if epi == EPI_SWIGLU:
+        return F.silu(y[:, 0::2]) * y[:, 1::2], S
+    if epi == EPI_RESID:
+        return resid.double() + y, S
     if epi != EPI_NONE:
         y = y + bias.double()
     if epi == EPI_BIAS_GELU:
@@ -175,9 +190,35 @@ def gemm_ref(A, W, bias=None, ls=None, resid=None, epi=EPI_NONE):
     return y, S
 
 
-def gemm_bound(want, S, epi, dtype=torch.bfloat16, ls=None):
+def sig_rel(gate):
+    """relative error allowed to x * sigmoidf_fast(x) * up of csrc/fvhd_common.h, rcp(1 + exp2(x * -log2(e))) in fp32, as a function of
+    the gate pre-activation: 2^-20 + 2^-24 |g|.  Derivation: the argument t = x * c is one fp32 product, |dt| <= 2^-24 |t| (c itself is
+    off by 0.22 * 2^-24), and an absolute dt on exp2's argument is a relative ln 2 * dt on its value: 0.69 * 1.22 * 1.4427 * 2^-24 |g| =
+    1.22 * 2^-24 |g| on e = exp(-g), which reaches the sigmoid times e / (1 + e) <= 1.  The terms without |g|: v_exp_f32 and v_rcp_f32
+    one ulp each (2^-23; the guides of this project give no other figure for the two), the sum 1 + e (2^-24) and the two products
+    x * s * up (2^-24 each): 7 * 2^-24.  2^-20 = 16 * 2^-24 holds those seven and the 0.22 * 2^-24 |g| left over up to |g| = 40; beyond
+    that silu's own size, which S_gate >= |g| brings into the accumulation term, is orders of magnitude above either.  sig_rel stays
+    four orders of magnitude below u(bf16) = 2^-7: it must never be what makes a comparison pass."""
+    return 2.0 ** -20 + 2.0 ** -24 * gate.double().abs()
+
+
+def gemm_bound(want, S, epi, dtype=torch.bfloat16, ls=None, pre=None):
+    """pre: A . W^T in fp64 [M, N], needed by EPI_SWIGLU alone - the error of the gate's sum passes through silu (slope <= SILU_SLOPE)
+    and is scaled by |up|, that of the up sum by |silu(gate)|, and the fast sigmoid adds sig_rel(gate) |want|"""
+    if epi == EPI_SWIGLU:
+        assert dtype == torch.bfloat16
+        gate, up = pre[:, 0::2].double(), pre[:, 1::2].double()
+        return U[dtype] * want.abs() + C_ACC * (SILU_SLOPE * S[:, 0::2] * up.abs() + F.silu(gate).abs() * S[:, 1::2]) + sig_rel(gate) * want.abs()
     f = ls.double().abs() if epi == EPI_BIAS_LS_RESID else (GELU_SLOPE if epi == EPI_BIAS_GELU else 1.0)
     return U[dtype] * want.abs() + U_ABS[dtype] + C_ACC * f * S + (GELU7_ABS if epi == EPI_BIAS_GELU else 0.0)
+
+
+def one_ulp(got, want):
+    """elements of the bf16 tensor `got` that are neither within one bf16 ulp of the bf16 tensor `want` (a distance of at most one
+    between the bit patterns, so the same sign) nor zero where `want` is zero -> their number"""
+    assert got.shape == want.shape and got.dtype == want.dtype == torch.bfloat16, (got.shape, want.shape, got.dtype, want.dtype)
+    gi, wi = got.contiguous().view(torch.int16).int(), want.contiguous().view(torch.int16).int()
+    return int((~(((gi - wi).abs() <= 1) | ((got == 0) & (want == 0)))).sum())
 
 
 def acc32(A, W, slab=32, fault=None):
@@ -194,10 +235,33 @@ def acc32(A, W, slab=32, fault=None):
     return acc
 
 
+def sigmoid_fast32(x):
+    """sigmoidf_fast of csrc/fvhd_common.h in fp32: 1 / (1 + exp2(x * -log2(e)))"""
+    x = x.float()
+    return 1.0 / (1.0 + torch.exp2(x * x.new_tensor(-1.4426950408889634)))
+
+
 def gemm_model(A, W, bias=None, ls=None, resid=None, epi=EPI_NONE, dtype=torch.bfloat16, fault=None, group=0, erf=False):
-    """the arithmetic a GEMM kernel is allowed: acc32, the epilogue in fp32 with the degree-7 GELU (erf: the exact one), one rounding.
-    fault: acc32's, or "bias16" (no bias on the 16-column group `group`), "ls_neighbour" (column n scaled by ls[n + 1])"""
+    """the arithmetic a GEMM kernel is allowed: acc32, the epilogue in fp32 with the degree-7 GELU (erf: the exact one) or the fast
+    sigmoid, one rounding.  fault: acc32's, or "bias16" (no bias on the 16-column group `group`), "ls_neighbour" (column n scaled by
+    ls[n + 1]); EPI_SWIGLU: "swap_gate_up" (silu of the up column times the gate column), "pair_shift" (gate j with up j + 1 inside every
+    group of 16 columns = 8 outputs, cyclically); EPI_RESID: "resid_neighbour8" (the residual of the other 8-column group of the same 16
+    columns), "resid_dropped" (no residual on the 16-column group `group`)"""
     t = acc32(A, W, fault=fault)
+    if epi == EPI_SWIGLU:
+        gate, up = t[:, 0::2], t[:, 1::2]
+        if fault == "swap_gate_up":
+            gate, up = up, gate
+        if fault == "pair_shift":
+            up = up.reshape(up.shape[0], -1, 8).roll(-1, 2).reshape(up.shape)
+        return (gate * sigmoid_fast32(gate) * up).to(dtype)
+    if epi == EPI_RESID:
+        r = resid.float().clone()
+        if fault == "resid_neighbour8":
+            r = r.reshape(r.shape[0], -1, 2, 8).flip(2).reshape(r.shape)
+        if fault == "resid_dropped":
+            r[:, 16 * group:16 * group + 16] = 0.0
+        return (r + t).to(dtype)
     if epi != EPI_NONE:
         b = bias.float().clone()
         if fault == "bias16":
@@ -211,29 +275,46 @@ def gemm_model(A, W, bias=None, ls=None, resid=None, epi=EPI_NONE, dtype=torch.b
     return t.to(dtype)
 
 
+GATE_NNZ, GATE_MAX = 4, 36      # the pairing family of EPI_SWIGLU: non-zeros of a gate row of W, and the |gate sum| they allow (4 * 3 * 3)
+
+
 def gemm_family(name, M, N, K, epi, seed, device="cpu"):
     """-> (A [M, K] bf16, W [N, K] bf16, bias fp32 [N] | None, ls fp32 [N] | None, resid bf16 [M, N] | None).
     "exact": integers |a|, |w|, |b| <= 3, ls a power of two, an integer residual - every partial sum stays below 2^24 up to K = 6144, so
-      fp32 accumulation is exact in ANY order and the output must be the bits of bf16(fp64 result).
+      fp32 accumulation is exact in ANY order and the output must be the bits of bf16(fp64 result).  EPI_SWIGLU has no bit-exact form
+      (the fast sigmoid): its "exact" is the integer PAIRING family - A and the up rows of W as above, every gate row of W with exactly
+      GATE_NNZ non-zeros in +-3, so that |gate sum| <= GATE_MAX = 36 by construction (below the +-60 beyond which the fast sigmoid's
+      exp nears the end of its fp32 range: test_dec_gemm_one_hot_exact) and both sums are exact in fp32; the output must then be
+      bf16(silu(g) u) to ONE bf16 ulp or zero with it (tower_reference.one_ulp), element by element: the gate / up pairing and the
+      [M, N / 2] column map, not an average over them.
     "rc" (rowscale x colscale): the rows of A carry row_scales 0.05 .. 20, the rows of W (= output columns) and ls each span 1e-5 .. 1
-      (shuffled independently); bias and residual carry the scale of the term they are added to, so that no term hides another."""
+      (shuffled independently); bias and residual carry the scale of the term they are added to, so that no term hides another.
+      EPI_SWIGLU: the gate rows and the up rows of W draw their column scales independently."""
     g = torch.Generator(device=device).manual_seed(seed)
-    has_b, has_ls = epi != EPI_NONE, epi == EPI_BIAS_LS_RESID
+    has_b, has_ls = epi in (EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_LS_RESID), epi == EPI_BIAS_LS_RESID
+    has_r = has_ls or epi == EPI_RESID
     if name == "exact":
         ri = lambda lo, hi, *s: torch.randint(lo, hi + 1, s, device=device, generator=g).float()
         A, W = ri(-3, 3, M, K), ri(-3, 3, N, K)
         bias = ri(-3, 3, N) if has_b else None
         ls = 2.0 ** ri(-3, 1, N) if has_ls else None
-        resid = ri(-8, 8, M, N) if has_ls else None
+        resid = ri(-8, 8, M, N) if has_r else None
+        if epi == EPI_SWIGLU:
+            keep = torch.rand(N // 2, K, device=device, generator=g).argsort(1)[:, :GATE_NNZ]          # GATE_NNZ distinct positions per gate row
+            vals = ri(1, 3, N // 2, GATE_NNZ) * torch.where(torch.rand(N // 2, GATE_NNZ, device=device, generator=g) < 0.5, -1.0, 1.0)
+            W[0::2] = torch.zeros(N // 2, K, device=device).scatter_(1, keep, vals)
+            assert int((W[0::2] != 0).sum(1).min()) == int((W[0::2] != 0).sum(1).max()) == GATE_NNZ
+            assert float((A.abs() @ W[0::2].abs().t()).max()) <= GATE_MAX
     else:
         assert name == "rc", name
         rn = lambda *s: torch.randn(*s, device=device, generator=g)
         span = lambda n: torch.logspace(-5.0, 0.0, n, device=device)[torch.randperm(n, device=device, generator=g)] if n > 1 else torch.ones(1, device=device)
-        rows, cols = row_scales(M, g, device), span(N)
+        rows = row_scales(M, g, device)
+        cols = torch.stack([span(N // 2), span(N // 2)], 1).reshape(N) if epi == EPI_SWIGLU else span(N)
         A, W = rn(M, K) * rows[:, None], rn(N, K) * K ** -0.5 * cols[:, None]
         bias = 0.3 * rn(N) * cols if has_b else None
         ls = span(N) if has_ls else None
-        resid = rn(M, N) * rows[:, None] * (ls * cols)[None] if has_ls else None
+        resid = rn(M, N) * rows[:, None] * ((ls * cols) if has_ls else cols)[None] if has_r else None
     b16 = lambda t: t.to(torch.bfloat16) if t is not None else None
     return b16(A), b16(W), bias, ls, b16(resid)
 
