@@ -73,7 +73,9 @@ typedef void* fvhd_stream_t; /* hipStream_t */
  * call enqueues what it did and fvhd_llm_reserve allocates what it did.  Also added under 510 (new symbols only, the number stays): 4-bit
  * LLM weights - FVHD_W_MXFP4 for fvhd_llm_set_weight_format, fvhd_llm_debug_packed_mxfp4, fvhd_op_quantize_mxfp4, fvhd_op_dec_gemm_w4 /
  * _qkv_w4 / _lm_argmax_w4, fvhd_op_w4_unpack; bf16 and e4m3 contexts enqueue what they did, bit for bit (a caller detects the symbols, as
- * ml_fastvlm_amd/_lib.py w4_lib() does). */
+ * ml_fastvlm_amd/_lib.py w4_lib() does).  Also added under 510 (new symbols only, the number stays): log-probabilities of the chosen tokens -
+ * fvhd_dec_logprobs_scratch_bytes, fvhd_op_dec_logprobs, fvhd_llm_set_logprobs, fvhd_llm_logprobs; with the setting off (the default) every
+ * existing call enqueues what it did and fvhd_llm_cache_reserve allocates what it did (_lib.py logprobs_lib() detects the symbols). */
 #define FVHD_VERSION 510
 int fvhd_version(void);
 const char* fvhd_last_error(void);
@@ -853,6 +855,45 @@ int fvhd_op_lm_score(fvhd_stream_t stream, const void* xn, const void* Wt, const
  * call yet on the current workspace (a stack call that failed part-way leaves none), capture without a sufficient reserve, NULL targets or output. */
 int fvhd_llm_score_reserve(fvhd_llm* ctx, int rows);
 int fvhd_llm_score(fvhd_llm* ctx, const int64_t* target_ids, float* logprob_out, float* lse_out, fvhd_stream_t stream);
+
+/* ---- LLM log-probabilities: the chosen token's log-probability and the n most likely tokens, per step (added under 510) ----------------------
+ * fvhd_llm_start / _decode / _extend return ids; this says how likely they were.  Per row of fp32 logits x [V] and a chosen id:
+ *     M = max x     Z = sum_v exp(x[v] - M)     token_logprob = (x[id] - M) - log Z
+ *     top_ids[0 .. top_n) = the top_n largest x in descending order, top_logprobs[k] = (x[top_ids[k]] - M) - log Z
+ * in ONE launch (llm_logprobs.hip): grid = slices x rows, a slice is ceil(V / S) consecutive ids with S = min(64, ceil(V / 2048)); the
+ * slices' (max, sum relative to that max, top_n candidates) meet in the row's last-arriving workgroup.  No floating-point atomics and a fixed
+ * order of additions: the same inputs give the same bits, eager or replayed from a graph.
+ * Order of top_ids: descending value; equal values by ascending id; -0 and +0 are equal; -inf entries rank last (among them ascending id).
+ * The ids depend on comparisons of the input values only: they are exact.  Only the log-probabilities carry rounding.
+ * A -inf logit (a suppressed token) contributes 0 to Z and has log-probability -inf - never NaN.  A row without a finite logit, or with
+ * +inf or NaN, is undefined (the sampler's rule, "LLM sampling").  id outside [0, V): token_logprob = NaN, nothing is read.
+ * top_n in [0, 16]; top_n > V is refused on the host.  V >= 1 (rows need not be 16-byte aligned), row stride V, 1 <= B <= 64.
+ * Scratch: fvhd_dec_logprobs_scratch_bytes(B, V, top_n) = 16384 + 2 * pad256(4 B S) + pad256(8 B S top_n) bytes (0: the shape is refused),
+ * aligned to 256 bytes.  Its first 16 384 bytes are the rows' arrival counters (one per 256 bytes: 4096 workgroups adding to one cache line
+ * wait for each other): zero before the FIRST launch on it, and every launch leaves them zero, so launches of any (B, V, top_n) that fit
+ * may follow one another on one scratch; the rest needs no initialisation. */
+size_t fvhd_dec_logprobs_scratch_bytes(int B, int V, int top_n);
+/* logits fp32 [B][V], ids int64 [B] -> token_logprob_out fp32 [B], top_ids_out int64 [B][top_n], top_logprobs_out fp32 [B][top_n] (both may be
+ * NULL when top_n = 0).  All pointers on the device. */
+int fvhd_op_dec_logprobs(fvhd_stream_t stream, const float* logits, const int64_t* ids, int B, int V, int top_n, float* token_logprob_out,
+                         int64_t* top_ids_out, float* top_logprobs_out, void* scratch, size_t scratch_bytes);
+/* On a context.  fvhd_llm_set_logprobs(ctx, 1) reserves the scratch for the batch of fvhd_llm_cache_reserve (an allocation of its own, freed
+ * by the next fvhd_llm_cache_reserve, which also switches the setting off) and makes the steps KEEP their logits: a greedy fvhd_llm_decode
+ * with logits_out = NULL then stores them into the context's buffer, as it already does under sampling or logits processors (fvhd_llm_start /
+ * _extend always do).  The (max, index) pairs still come from the lm_head's fused epilogue: the chosen ids keep their bits.  It synchronises
+ * the device and is refused while a stream is being captured; a captured step keeps the setting it was captured with.  With the setting off
+ * every call enqueues the launches it did before.
+ * fvhd_llm_logprobs enqueues the launch on the logits of the LAST fvhd_llm_start / _decode / _extend and the ids that call chose: logits =
+ * NULL reads the context's buffer (the setting must be on and that call must have been given logits_out = NULL), otherwise pass that call's
+ * logits_out.  With logits processors on these are the processed scores; they are always the values BEFORE temperature / top-k / top-p (the
+ * sampler reads them const, so the launch goes after the choice).  Outputs for the rows of the started batch.  No host synchronisation and host
+ * arguments constant per step: capture-safe.  Refused, each with a message: nothing started; logits NULL with the setting off or with no kept
+ * logits; no scratch (the setting was never on for this cache); the chosen ids stale (behind fvhd_llm_cache_rewind / _cache_gather, the rule of
+ * fvhd_llm_decode(token_ids = NULL)); the error word set; top_n outside [0, 16] or above the vocabulary.  A launch that finds the error word
+ * set on the device writes nothing, like the steps. */
+int fvhd_llm_set_logprobs(fvhd_llm* ctx, int on);
+int fvhd_llm_logprobs(fvhd_llm* ctx, const float* logits, int top_n, float* token_logprob_out, int64_t* top_ids_out, float* top_logprobs_out,
+                      fvhd_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -25,6 +25,7 @@ EXTEND_VERSION = 509          # the first with fvhd_llm_extend / fvhd_llm_cache_
 MAX_DECODE_BATCH = 64
 MAX_VERIFY_ROWS = 16           # rows of one verify step (include/fvhd.h)
 MAX_EOS_IDS, MAX_SUPPRESS_IDS = 16, 256      # list limits of fvhd_llm_set_logits_processors (include/fvhd.h)
+MAX_LOGPROBS = 16              # top_n of fvhd_llm_logprobs / fvhd_op_dec_logprobs (include/fvhd.h)
 W_BF16, W_E4M3 = 0, 1           # fvhd_llm_set_weight_format (include/fvhd.h)
 WEIGHT_FORMATS = {"bf16": W_BF16, "fp8_e4m3": W_E4M3}
 W_MXFP4 = 2                     # added under 510 (w4_lib()): OCP MXFP4, e2m1 codes + one e8m0 scale per 32 elements of a row
@@ -189,6 +190,13 @@ def _declare(lib) -> None:
             "fvhd_op_dec_lm_argmax_w4": (ci, [vp, vp, ci, vp, cf, vp, vp, ci, ci, vp, vp, vp, vp]),
             "fvhd_op_w4_unpack": (ci, [vp, vp, vp, vp, ci, ci, ci]),
         })
+    if hasattr(lib, "fvhd_op_dec_logprobs"):       # added under 510: a 510 library built before them loads without; logprobs_lib() then names the rebuild
+        sig.update({
+            "fvhd_dec_logprobs_scratch_bytes": (C.c_size_t, [ci, ci, ci]),
+            "fvhd_op_dec_logprobs": (ci, [vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, C.c_size_t]),
+            "fvhd_llm_set_logprobs": (ci, [vp, ci]),
+            "fvhd_llm_logprobs": (ci, [vp, vp, ci, vp, vp, vp, vp]),
+        })
     del fp, cl
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)     # AttributeError here = the .so does not export what fvhd.h declares
@@ -311,6 +319,17 @@ def w4_lib():
     if not hasattr(lib, "fvhd_op_dec_gemm_w4"):
         raise FvhdError(f"{LIB_PATH} (ABI version {lib.fvhd_version()}) was built before 4-bit weights (FVHD_W_MXFP4, fvhd_op_quantize_mxfp4, "
                         "fvhd_op_dec_gemm_w4, ...) - rebuild the library (`python -m ml_fastvlm_amd.build`)")
+    return lib
+
+
+def logprobs_lib():
+    """load(), for the log-probabilities of generated tokens (fvhd_llm_set_logprobs, fvhd_llm_logprobs, fvhd_op_dec_logprobs, ...): the entry
+    points were added under FVHD_VERSION 510, so a library built before them reports the same number and loads; this says so instead of an
+    AttributeError."""
+    lib = load()
+    if not hasattr(lib, "fvhd_op_dec_logprobs"):
+        raise FvhdError(f"{LIB_PATH} (ABI version {lib.fvhd_version()}) was built before the log-probabilities of generated tokens "
+                        "(fvhd_llm_set_logprobs, fvhd_llm_logprobs, fvhd_op_dec_logprobs, ...) - rebuild the library (`python -m ml_fastvlm_amd.build`)")
     return lib
 
 

@@ -280,13 +280,20 @@ def generator_context(model, batch: int, capacity: int, weights=None):
 @torch.no_grad()
 def generate(model, input_ids, images=None, image_sizes=None, attention_mask=None, max_new_tokens: int = 256, eos_token_id=None,
              pad_token_id=None, do_sample: bool = False, num_beams: int = 1, prompt_lookup_num_tokens=None,
-             max_matching_ngram_size: int = 2, **kwargs):
+             max_matching_ngram_size: int = 2, logprobs=None, **kwargs):
     """`LlavaQwen2ForCausalLM.generate` (`llava_qwen.py:106-143`) with greedy decoding on the library: the multimodal splice
     (`model.prepare_inputs_labels_for_multimodal`) or the token embedding, then the prefill and every decode step on the hand-written
     Qwen2 kernels (`Qwen2Generator.greedy`).  Returns the new tokens [B, n] as transformers' generate(inputs_embeds=...) does.  Greedy only:
     sampling, beam search and other decoding strategies raise NotImplementedError.  The model must be bf16 on a HIP device.
     prompt_lookup_num_tokens=K (1 .. 15, one prompt per call): prompt-lookup decoding (`Qwen2Generator.lookup_greedy`) - the same tokens, K
-    drafts from n-gram matches (n <= max_matching_ngram_size) in `input_ids` and the generated tokens verified per step."""
+    drafts from n-gram matches (n <= max_matching_ngram_size) in `input_ids` and the generated tokens verified per step.
+    logprobs=n (0 .. 16): -> (tokens, `GenerationLogprobs`): every generated token's log-probability and the n most likely tokens of its step
+    (`Qwen2Generator.greedy`); not with prompt_lookup_num_tokens."""
+    from .qwen2_decode import normalize_logprobs
+    logprobs = normalize_logprobs(logprobs)
+    if logprobs is not None and prompt_lookup_num_tokens is not None:
+        raise ValueError("ml_fastvlm_amd.generate: logprobs is not implemented under prompt-lookup decoding (prompt_lookup_num_tokens) - a verify step "
+                         "chooses several tokens per launch")
     if do_sample:
         raise NotImplementedError("ml_fastvlm_amd.generate: do_sample=True (sampling) is not implemented - greedy decoding only; "
                                   "Qwen2Generator.step exposes the logits for sampling in torch")
@@ -313,7 +320,8 @@ def generate(model, input_ids, images=None, image_sizes=None, attention_mask=Non
         eos_token_id = getattr(gc, "eos_token_id", None)
     if pad_token_id is None:
         pad_token_id = getattr(gc, "pad_token_id", None)
-    return _generate_on_library(model, input_ids, images, image_sizes, attention_mask, None, max_new_tokens, eos_token_id, pad_token_id, lookup=lookup)
+    return _generate_on_library(model, input_ids, images, image_sizes, attention_mask, None, max_new_tokens, eos_token_id, pad_token_id, lookup=lookup,
+                                logprobs=logprobs)
 
 
 @torch.no_grad()
@@ -339,10 +347,13 @@ def beam_generate(model, input_ids, images=None, image_sizes=None, attention_mas
 
 
 def _generate_on_library(model, input_ids, images, image_sizes, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id,
-                         sampling=None, beam=None, processors=None, lookup=None):
+                         sampling=None, beam=None, processors=None, lookup=None, logprobs=None):
     """the body shared by `generate`, `beam_generate` and `_make_library_generate`: the multimodal splice (or the token embedding), then the
     prefill and every decode step on the library - `Qwen2Generator.greedy`, `.sample(**sampling)` or `.beam_search(**beam)`; processors:
-    None or the logits-processor keywords of greedy / sample (repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens)"""
+    None or the logits-processor keywords of greedy / sample (repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens);
+    logprobs: None or greedy's / sample's keyword (they then return (tokens, GenerationLogprobs)) - not for beam search or lookup decoding"""
+    if logprobs is not None and (beam is not None or lookup is not None):
+        raise ValueError("logprobs is implemented for greedy decoding and sampling only (beam search has return_scores)")
     if images is not None:
         (input_ids, position_ids, attention_mask, _, inputs_embeds, _) = model.prepare_inputs_labels_for_multimodal(
             input_ids, position_ids, attention_mask, None, None, images, image_sizes=image_sizes)
@@ -361,9 +372,9 @@ def _generate_on_library(model, input_ids, images, image_sizes, attention_mask, 
     processors = processors or {}
     if sampling is None:
         return gen.greedy(inputs_embeds, attention_mask, position_ids, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id,
-                          pad_token_id=pad_token_id, **processors)
+                          pad_token_id=pad_token_id, logprobs=logprobs, **processors)
     return gen.sample(inputs_embeds, attention_mask, position_ids, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id,
-                      pad_token_id=pad_token_id, **sampling, **processors)
+                      pad_token_id=pad_token_id, logprobs=logprobs, **sampling, **processors)
 
 
 # ---- multi-turn generation on one KV cache ------------------------------------------------------------------------------------------------
@@ -531,8 +542,10 @@ class GenerationSession:
 
     @torch.no_grad()
     def generate(self, input_ids, images=None, image_sizes=None, attention_mask=None, max_new_tokens: int = 256, eos_token_id=None,
-                 pad_token_id=None, do_sample: bool = False, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0):
-        """-> the new tokens of this turn [B, n] (`Qwen2Generator.greedy` / `.sample`'s return contract).  First call: `input_ids` is the
+                 pad_token_id=None, do_sample: bool = False, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
+                 logprobs=None):
+        """-> the new tokens of this turn [B, n] (`Qwen2Generator.greedy` / `.sample`'s return contract); with logprobs=n (0 .. 16)
+        (tokens, `GenerationLogprobs`) of this turn.  First call: `input_ids` is the
         whole prompt (with image placeholders when `images` is given).  Later calls: the turn's NEW ids [B, n] only, B = the session's
         rows; attention_mask marks the real tokens of rows of different lengths.  Images in a later turn need B = 1 or rows whose
         spliced lengths are equal (the splice pads to the right, the cache extends to the left)."""
@@ -566,15 +579,16 @@ class GenerationSession:
         gen = self._generator()
         T = embeds.shape[1]
         before = 0 if first else gen.length()
-        kw = dict(max_new_tokens=max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id, continue_cache=not first)
+        kw = dict(max_new_tokens=max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id, continue_cache=not first, logprobs=logprobs)
         if do_sample:
-            tokens = gen.sample(embeds, mask, position_ids, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, **kw)
+            res = gen.sample(embeds, mask, position_ids, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, **kw)
         else:
-            tokens = gen.greedy(embeds, mask, position_ids, **kw)
+            res = gen.greedy(embeds, mask, position_ids, **kw)
+        tokens = res if logprobs is None else res[0]
         keep, self._pending = session_keep(before + T, tokens, eos_token_id)
         gen.rewind(keep)
         gen._session = self                                      # start() clears it: whoever starts the cache again ends this dialogue
-        return tokens
+        return res
 
     @torch.no_grad()
     def score(self, input_ids, continuation_ids, continuation_mask=None):

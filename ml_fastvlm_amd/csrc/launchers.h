@@ -116,4 +116,7 @@ int fvhd_launch_lm_score(hipStream_t st, const void* xn, const void* Wt, const i
 // llm_logits.hip
 int fvhd_launch_dec_logits_process(hipStream_t st, const DecLogitsArgs* a);
 int fvhd_launch_dec_logits_history(hipStream_t st, const int* tokens, int* hist, unsigned* seen, int B, int V, int cap, int g);
+// llm_logprobs.hip (scratch: fvhd_dec_logprobs_scratch_bytes, its first 16 384 bytes zero before the first launch; status: NULL or the error word)
+int fvhd_launch_dec_logprobs(hipStream_t st, const float* logits, const int64_t* ids, int B, int V, int top_n, float* token_logprob, int64_t* top_ids,
+                             float* top_logprobs, void* scratch, const int* status);
 }

@@ -118,6 +118,12 @@ struct __attribute__((visibility("default"))) fvhd_llm {     // (its inline cons
     char* score_ws = nullptr;
     size_t score_bytes = 0;
     bool score_captured = false;
+    // fvhd_llm_set_logprobs (llm_logprobs.hip): with it on, a greedy step without a logits_out keeps its logits in `dlogits`.  lp_ws: the
+    // launch's scratch for (dc_batch, V, 16), an allocation of its own that fvhd_llm_cache_reserve frees with the cache it was sized for;
+    // lp_logits: where the last fvhd_llm_start / _decode / _extend left its logits (NULL: nowhere yet)
+    int lp_on = 0;
+    char* lp_ws = nullptr;
+    const float* lp_logits = nullptr;
 };
 
 inline bool processors_on(const fvhd_llm* c)

@@ -347,6 +347,21 @@ int fvhd_op_dec_sample(fvhd_stream_t st, const float* logits, int B, int V, floa
     return lret("fvhd_op_dec_sample", fvhd_launch_dec_sample((hipStream_t)st, &a, ws[dev]));
 }
 
+int fvhd_op_dec_logprobs(fvhd_stream_t st, const float* logits, const int64_t* ids, int B, int V, int top_n, float* token_logprob_out,
+                         int64_t* top_ids_out, float* top_logprobs_out, void* scratch, size_t scratch_bytes)
+{
+    if (!logits || !ids || !token_logprob_out || !scratch) return lfail("fvhd_op_dec_logprobs: NULL pointer");
+    if (B < 1 || B > 64 || V < 1) return lfail("fvhd_op_dec_logprobs: needs 1 <= B <= 64 and V >= 1");
+    if (top_n < 0 || top_n > 16) return lfail("fvhd_op_dec_logprobs: top_n must be in [0, 16] (got " + std::to_string(top_n) + ")");
+    if (top_n > V) return lfail("fvhd_op_dec_logprobs: top_n = " + std::to_string(top_n) + " exceeds V = " + std::to_string(V));
+    if (top_n && (!top_ids_out || !top_logprobs_out)) return lfail("fvhd_op_dec_logprobs: top_n > 0 needs top_ids_out and top_logprobs_out");
+    if (scratch_bytes < fvhd_dec_logprobs_scratch_bytes(B, V, top_n))
+        return lfail("fvhd_op_dec_logprobs: scratch_bytes = " + std::to_string(scratch_bytes) + " is below fvhd_dec_logprobs_scratch_bytes(B, V, top_n) = " +
+                     std::to_string(fvhd_dec_logprobs_scratch_bytes(B, V, top_n)));
+    return lret("fvhd_op_dec_logprobs", fvhd_launch_dec_logprobs((hipStream_t)st, logits, ids, B, V, top_n, token_logprob_out, top_ids_out, top_logprobs_out,
+                                                                 scratch, nullptr));
+}
+
 // process-wide scratch of a single op, allocated / grown on demand - eager calls only
 static int op_scratch(const char* who, char* (&buf)[64], size_t (&cap)[64], size_t need, char** out)
 {

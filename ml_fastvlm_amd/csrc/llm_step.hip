@@ -153,7 +153,10 @@ int fvhd_llm_cache_reserve(fvhd_llm* c, int batch, int capacity)
     if (c->dc) (void)hipFree(c->dc);
     if (c->beam) (void)hipFree(c->beam);                         // sized for the cache it was reserved for: fvhd_llm_beam_reserve again
     if (c->spec) (void)hipFree(c->spec);                         // likewise: fvhd_llm_spec_reserve again
-    c->dc = c->beam = c->beam_topk = c->spec = nullptr;
+    if (c->lp_ws) (void)hipFree(c->lp_ws);                       // likewise: fvhd_llm_set_logprobs again
+    c->dc = c->beam = c->beam_topk = c->spec = c->lp_ws = nullptr;
+    c->lp_on = 0;
+    c->lp_logits = nullptr;
     c->spec_rows = 0;
     c->sp_begun = false;
     c->dc_batch = c->dc_cap = c->run_batch = 0;
@@ -202,6 +205,7 @@ int fvhd_llm_start(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* ke
     }
     *(volatile int*)c->status_host = 0;
     float* logits = logits_out ? logits_out : c->dlogits;
+    c->lp_logits = nullptr;
     char* pk = c->pre_kv;
     char* pv = c->pre_kv + (size_t)L * layer_src;
     int e = fvhd_llm_prefill(c, embeds, dtype, key_valid, position_ids, B, T, logits, pk, pv, stream);
@@ -245,6 +249,7 @@ int fvhd_llm_start(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* ke
     c->run_batch = B;
     c->sp_begun = false;                                         // a lookup generation belongs to the sequence it was begun on
     c->ids_stale = false;                                        // the ids chosen here are these rows'
+    c->lp_logits = logits;
     return 0;
 }
 
@@ -306,7 +311,8 @@ int fvhd_llm_decode(fvhd_llm* c, const int64_t* token_ids, float* logits_out, in
     }
     DecGemmArgs a = gemm(DEC_EPI_ARGMAX, c->dh, (const float*)(w + c->norm_off), -1, FVHD_MAT_LM_HEAD);
     a.logits = logits_out; a.amax_v = c->amax_v; a.amax_i = c->amax_i;
-    if (proc && !a.logits) a.logits = c->dlogits;
+    if ((proc || c->lp_on) && !a.logits) a.logits = c->dlogits;      // fvhd_llm_set_logprobs: the greedy step keeps its logits too
+    c->lp_logits = nullptr;
     DecLogitsArgs pa;
     if (proc) {
         pa = dec_logits_args(c, a.logits, B, st);
@@ -324,6 +330,7 @@ int fvhd_llm_decode(fvhd_llm* c, const int64_t* token_ids, float* logits_out, in
         LCHECK(fvhd_launch_dec_sample(st, &sa, c->sws), "decode sampling");
         c->sp_begun = false;
         if (token_ids) c->ids_stale = false;
+        c->lp_logits = a.logits;
         return 0;
     }
     LCHECK(fvhd_launch_dec_gemm(st, &a), "decode final norm + lm_head + argmax");
@@ -336,6 +343,7 @@ int fvhd_llm_decode(fvhd_llm* c, const int64_t* token_ids, float* logits_out, in
            "decode argmax reduce");
     c->sp_begun = false;                                         // a plain step: the token buffer of a lookup generation no longer describes the sequence
     if (token_ids) c->ids_stale = false;                         // the ids chosen on fed ids are these rows'
+    c->lp_logits = a.logits;                                     // (NULL: this step kept none)
     return 0;
 }
 
@@ -359,6 +367,7 @@ int fvhd_llm_extend(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* k
     hipStream_t st = (hipStream_t)stream;
     const int B = c->run_batch;
     float* logits = logits_out ? logits_out : c->dlogits;
+    c->lp_logits = nullptr;
     // the prefill's decoder stack on the chunk rows; per layer the append + the attention over slots [0, length + T) (llm_prefill.hip)
     if (int e = decoder_stack(c, embeds, dtype, key_valid, position_ids, B, T, logits, nullptr, nullptr, st, true)) return e;
     LLM_ON_DEVICE(c);
@@ -376,6 +385,7 @@ int fvhd_llm_extend(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* k
     LCHECK(fvhd_launch_llm_extend_state(st, c->posv, c->epos_used, B, T, c->len, c->status), "extend state");
     c->sp_begun = false;                                         // a lookup generation belongs to the sequence it was begun on
     c->ids_stale = false;
+    c->lp_logits = logits;
     return 0;
 }
 
@@ -557,6 +567,7 @@ int fvhd_llm_verify(fvhd_llm* c, const int64_t* draft_ids, int rows, float* logi
     if (int e = dec_embedding_error(c, "fvhd_llm_verify")) return e;
     LLM_ON_DEVICE(c);
     hipStream_t st = (hipStream_t)stream;
+    c->lp_logits = nullptr;                                      // a verify step's rows are not "the logits of the last step"
     int64_t* ids = ids_out ? ids_out : c->sp_ids;                // the argmax reduce writes them, the accept reads them
     if (int e = spec_enqueue(c, draft_ids, rows, logits_out, ids, c->status, st)) return e;
     SpecAcceptArgs a;
@@ -599,6 +610,7 @@ int fvhd_llm_lookup_step(fvhd_llm* c, int rows, int max_ngram, fvhd_stream_t str
     if (int e = dec_embedding_error(c, "fvhd_llm_lookup_step")) return e;
     LLM_ON_DEVICE(c);
     hipStream_t st = (hipStream_t)stream;
+    c->lp_logits = nullptr;
     LCHECK(fvhd_launch_spec_draft(st, c->sp_seq, c->sp_words + SPEC_W_SEQ_LEN, max_ngram, rows - 1, c->sp_draft, c->status, c->sp_words, c->sp_gate),
            "lookup draft");
     if (int e = spec_enqueue(c, c->sp_draft, rows, nullptr, c->sp_ids, c->sp_gate, st)) return e;
@@ -668,6 +680,49 @@ int fvhd_llm_set_logits_processors(fvhd_llm* c, float repetition_penalty, int no
     c->proc_min_new = min_new_tokens;
     c->proc_n_eos = n_eos;
     c->proc_n_sup = n_suppress;
+    return 0;
+}
+
+// ---- log-probabilities of the chosen tokens (include/fvhd.h "LLM log-probabilities"; kernel: llm_logprobs.hip) ----
+int fvhd_llm_set_logprobs(fvhd_llm* c, int on)
+{
+    if (!c) return lfail("fvhd_llm_set_logprobs: ctx is NULL");
+    if (!c->dc) return lfail("fvhd_llm_set_logprobs: no KV cache - call fvhd_llm_cache_reserve first (the scratch is sized for its batch)");
+    LLM_ON_DEVICE(c);
+    hipError_t he = hipDeviceSynchronize();                      // refused while a stream is being captured (like fvhd_llm_cache_reserve)
+    if (he != hipSuccess) return lhip("fvhd_llm_set_logprobs: hipDeviceSynchronize", he);
+    if (on && !c->lp_ws) {
+        const size_t bytes = fvhd_dec_logprobs_scratch_bytes(c->dc_batch, c->V, 16);
+        if ((he = hipMalloc((void**)&c->lp_ws, bytes)) != hipSuccess) { c->lp_ws = nullptr; return lhip("hipMalloc(logprobs scratch)", he); }
+        if ((he = hipMemset(c->lp_ws, 0, bytes)) != hipSuccess) return lhip("hipMemset(logprobs scratch)", he);      // counters start at zero
+    }
+    c->lp_on = on != 0;
+    return 0;
+}
+
+int fvhd_llm_logprobs(fvhd_llm* c, const float* logits, int top_n, float* token_logprob_out, int64_t* top_ids_out, float* top_logprobs_out,
+                      fvhd_stream_t stream)
+{
+    if (!c || !token_logprob_out) return lfail("fvhd_llm_logprobs: NULL argument");
+    if (top_n < 0 || top_n > 16) return lfail("fvhd_llm_logprobs: top_n must be in [0, 16] (got " + std::to_string(top_n) + ")");
+    if (top_n > c->V) return lfail("fvhd_llm_logprobs: top_n = " + std::to_string(top_n) + " exceeds the vocabulary (" + std::to_string(c->V) + ")");
+    if (top_n && (!top_ids_out || !top_logprobs_out)) return lfail("fvhd_llm_logprobs: top_n > 0 needs top_ids_out and top_logprobs_out");
+    if (!c->dc || !c->run_batch) return lfail("fvhd_llm_logprobs: no started sequence - call fvhd_llm_cache_reserve and fvhd_llm_start first");
+    if (int e = dec_status_error(c, "fvhd_llm_logprobs")) return e;
+    if (int e = stale_ids_error(c, "fvhd_llm_logprobs")) return e;
+    if (!logits) {
+        if (!c->lp_on)
+            return lfail("fvhd_llm_logprobs: logits is NULL and keeping the logits is off - switch it on before the step (fvhd_llm_set_logprobs), or pass "
+                         "the logits_out buffer of the step");
+        if (c->lp_logits != c->dlogits)
+            return lfail("fvhd_llm_logprobs: logits is NULL but the last fvhd_llm_start / _decode / _extend did not leave its logits in the context's "
+                         "buffer (none ran since the setting was switched on, or it wrote a logits_out) - pass that buffer");
+        logits = c->dlogits;
+    }
+    if (!c->lp_ws) return lfail("fvhd_llm_logprobs: no scratch - fvhd_llm_set_logprobs(ctx, 1) reserves it (it may be switched off again)");
+    LLM_ON_DEVICE(c);
+    LCHECK(fvhd_launch_dec_logprobs((hipStream_t)stream, logits, c->last_ids, c->run_batch, c->V, top_n, token_logprob_out, top_ids_out, top_logprobs_out,
+                                    c->lp_ws, c->status), "logprobs");
     return 0;
 }
 

@@ -240,6 +240,7 @@ void fvhd_llm_destroy(fvhd_llm* c)
     if (c->beam) (void)hipFree(c->beam);
     if (c->spec) (void)hipFree(c->spec);
     if (c->score_ws) (void)hipFree(c->score_ws);
+    if (c->lp_ws) (void)hipFree(c->lp_ws);
     if (c->pre_kv) (void)hipFree(c->pre_kv);
     if (c->status_host) (void)hipHostFree(c->status_host);
     delete c;

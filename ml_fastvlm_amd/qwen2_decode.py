@@ -27,12 +27,15 @@ what the model's own argmax confirms - the same tokens in fewer steps.
 attention over the cached keys) and `rewind` drops the tail of every row; `greedy` / `sample` with `continue_cache=True` begin with
 `extend` where they otherwise begin with `start` - the next turn of a dialogue costs its own tokens, not the whole history again
 (`ml_fastvlm_amd.GenerationSession` keeps the turns' bookkeeping).
+`greedy` / `sample` with `logprobs=n` (0 .. 16) also return `GenerationLogprobs`: per generated token its log-probability and the n most
+likely tokens with theirs (include/fvhd.h "LLM log-probabilities") - one more launch inside the captured step, on the logits the choice
+was made from.
 """
 from __future__ import annotations
 
 import contextlib
 import ctypes as C
-from typing import Optional, Sequence, Union
+from typing import NamedTuple, Optional, Sequence, Union
 
 import torch
 
@@ -60,6 +63,29 @@ def philox_uniform(seed: int, row: int, n: int) -> float:
     and key (seed low word, seed high word) - exact in fp32"""
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     return (philox4x32_10((row, n, 0, 0), (seed, seed >> 32))[0] >> 8) * 2.0 ** -24
+
+
+class GenerationLogprobs(NamedTuple):
+    """what `greedy` / `sample` return beside the tokens [B, n_tok] under `logprobs=n`: log-softmax values of the logits each token was
+    chosen from (the processed scores when logits processors are on; before temperature / top-k / top-p).  Behind a row's end (the token
+    is the pad): token_logprobs 0, top_ids -1, top_logprobs -inf, so that token_logprobs.sum(1) is the sequence log-likelihood."""
+    token_logprobs: torch.Tensor                                 # fp32 [B, n_tok]
+    top_ids: torch.Tensor                                        # int64 [B, n_tok, n]: descending logit, equal logits by ascending id
+    top_logprobs: torch.Tensor                                   # fp32 [B, n_tok, n]
+
+
+def normalize_logprobs(n, vocab: Optional[int] = None) -> Optional[int]:
+    """the `logprobs` keyword of greedy / sample / generate: None (off) or an int in [0, 16] and <= vocab -> None or the int; anything
+    else is a ValueError.  Touches no device."""
+    if n is None:
+        return None
+    if isinstance(n, bool) or not isinstance(n, int):
+        raise ValueError(f"logprobs must be None or an int in [0, {_lib.MAX_LOGPROBS}] (the number of most likely tokens to return per step), got {n!r}")
+    if not 0 <= n <= _lib.MAX_LOGPROBS:
+        raise ValueError(f"logprobs must be in [0, {_lib.MAX_LOGPROBS}], got {n}")
+    if vocab is not None and n > int(vocab):
+        raise ValueError(f"logprobs = {n} exceeds the vocabulary ({int(vocab)} ids)")
+    return n
 
 
 def generation_position_ids(attention_mask: Optional[torch.Tensor], batch: int, seq_len: int, device=None) -> torch.Tensor:
@@ -258,6 +284,47 @@ class Qwen2Generator:
         if ids is not None:
             self._ids_stale = False
         return lg, self._ids[:B]
+
+    # ---- log-probabilities of the chosen tokens ------------------------------------------------------------------------------------------
+    def set_logprobs(self, on: bool) -> None:
+        """steps keep their logits in the library's buffer from now on (`fvhd_llm_set_logprobs`; also reserves the launch's scratch).
+        Synchronises; a captured step keeps the setting it was captured with."""
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.logprobs_lib().fvhd_llm_set_logprobs(self.pre._h, int(bool(on))), "fvhd_llm_set_logprobs")
+
+    @torch.no_grad()
+    def logprobs(self, top_n: int, token_logprobs: torch.Tensor, top_ids: Optional[torch.Tensor] = None, top_logprobs: Optional[torch.Tensor] = None,
+                 logits: Optional[torch.Tensor] = None) -> None:
+        """of the ids the last start() / step() / extend() chose, on that call's logits (`fvhd_llm_logprobs`): token_logprobs fp32 [B],
+        top_ids int64 [B, top_n], top_logprobs fp32 [B, top_n] (contiguous, on the device; the last two may be None for top_n = 0).  logits
+        None: the library's buffer - `set_logprobs(True)` before that call, and the call made with logits=False; else the logits that call
+        returned.  Host arguments are the same every step: capture-safe."""
+        B, n = self._run_batch, int(top_n)
+        outs = [(token_logprobs, torch.float32, (B,))]
+        if n or top_ids is not None or top_logprobs is not None:
+            outs += [(top_ids, torch.long, (B, n)), (top_logprobs, torch.float32, (B, n))]
+        for t, dt, shape in outs:
+            if t is None or t.dtype != dt or t.device != self.device or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"logprobs: expected a contiguous {dt} tensor {shape} on {self.device}, got "
+                                 f"{None if t is None else (t.dtype, tuple(t.shape), t.device)}")
+        if logits is not None and (logits.dtype != torch.float32 or logits.device != self.device or tuple(logits.shape) != (B, self.pre.vocab)
+                                   or not logits.is_contiguous()):
+            raise ValueError(f"logprobs: logits must be a contiguous fp32 tensor [{B}, {self.pre.vocab}] on {self.device}")
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.logprobs_lib().fvhd_llm_logprobs(self.pre._h, _lib.ptr(logits), n, _lib.ptr(token_logprobs), _lib.ptr(top_ids),
+                                                             _lib.ptr(top_logprobs), _lib.stream_ptr(self.device)), "fvhd_llm_logprobs")
+
+    @contextlib.contextmanager
+    def _logprobs_for_run(self, n):
+        """the `logprobs` keyword of greedy() / sample(): the kept-logits setting on for the run, off in a finally; None touches nothing"""
+        if n is None:
+            yield
+            return
+        self.set_logprobs(True)
+        try:
+            yield
+        finally:
+            self.set_logprobs(False)
 
     # ---- beam search: the two device operations -----------------------------------------------------------------------------------------
     def beam_reserve(self) -> None:
@@ -475,35 +542,45 @@ class Qwen2Generator:
     def greedy(self, inputs_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None,
                max_new_tokens: int = 256, eos_token_id: Union[None, int, Sequence[int]] = None, pad_token_id: Optional[int] = None,
                graph: bool = True, poll_every: int = 16, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0,
-               suppress_tokens: Optional[Sequence[int]] = None, continue_cache: bool = False) -> torch.Tensor:
+               suppress_tokens: Optional[Sequence[int]] = None, continue_cache: bool = False, logprobs: Optional[int] = None):
         """transformers' greedy search (`GenerationMixin._sample` with do_sample=False) on the library's steps -> new tokens [B, n].
         graph=True captures one step (decode + the finished-sequence bookkeeping) into a CUDA graph and replays it; "all finished" is
         polled every `poll_every` steps (no host synchronisation per token) and the output trimmed to the step where it happened.
         repetition_penalty / no_repeat_ngram_size / min_new_tokens (with eos_token_id) / suppress_tokens: transformers' logits processors
         (`set_logits_processors`), set for this run and cleared after it.
         continue_cache=True: `inputs_embeds` is a chunk for the STARTED cache - the run begins with `extend` where it otherwise begins with
-        `start` (not with logits processors); everything after the first token is the same code."""
+        `start` (not with logits processors); everything after the first token is the same code.
+        logprobs=n (0 .. 16): -> (tokens, `GenerationLogprobs`) - every token's log-probability and the n most likely tokens of its step,
+        the first token included, from one more launch inside the captured step; None (the default): the tokens alone, launch for launch
+        what it was."""
+        logprobs = normalize_logprobs(logprobs, self.pre.vocab)
         self._set_greedy()
-        with self._processors_for_run(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, suppress_tokens):
-            return self._run(inputs_embeds, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id, graph, poll_every, continue_cache)
+        with self._processors_for_run(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, suppress_tokens), \
+                self._logprobs_for_run(logprobs):
+            return self._run(inputs_embeds, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id, graph, poll_every, continue_cache,
+                             logprobs)
 
     @torch.no_grad()
     def sample(self, inputs_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None,
                max_new_tokens: int = 256, temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, seed: Optional[int] = None,
                eos_token_id: Union[None, int, Sequence[int]] = None, pad_token_id: Optional[int] = None, graph: bool = True,
                poll_every: int = 16, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0,
-               suppress_tokens: Optional[Sequence[int]] = None, continue_cache: bool = False) -> torch.Tensor:
+               suppress_tokens: Optional[Sequence[int]] = None, continue_cache: bool = False, logprobs: Optional[int] = None):
         """transformers' multinomial sampling (`GenerationMixin._sample` with do_sample=True, num_beams=1: temperature, then top-k, then
         top-p) on the library's steps -> new tokens [B, n], with greedy's return contract, EOS / pad bookkeeping and graph replay.
         seed None: 63 bits from torch's default CPU generator, so `torch.manual_seed` makes a run repeat.  The same seed gives the same
         tokens, eager or graph; the draws are not torch.multinomial's (only the distribution is the same).  The logits processors of
-        `greedy` apply before the temperature, as in transformers.  continue_cache: as in `greedy`."""
+        `greedy` apply before the temperature, as in transformers.  continue_cache: as in `greedy`.  logprobs: as in `greedy` - the
+        log-softmax of the (processed) logits BEFORE temperature / top-k / top-p, not of the distribution the draw was made from."""
+        logprobs = normalize_logprobs(logprobs, self.pre.vocab)
         if seed is None:
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.long).item())
         self.set_sampling(True, temperature, top_k, top_p, seed)
         try:
-            with self._processors_for_run(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, suppress_tokens):
-                return self._run(inputs_embeds, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id, graph, poll_every, continue_cache)
+            with self._processors_for_run(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, suppress_tokens), \
+                    self._logprobs_for_run(logprobs):
+                return self._run(inputs_embeds, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id, graph, poll_every,
+                                 continue_cache, logprobs)
         finally:
             self.set_sampling(False)
 
@@ -522,7 +599,7 @@ class Qwen2Generator:
             self.set_logits_processors()
 
     def _run(self, inputs_embeds, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id, graph, poll_every,
-             continue_cache=False) -> torch.Tensor:
+             continue_cache=False, logprobs=None):
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be >= 1")
         B, T = inputs_embeds.shape[:2]
@@ -545,10 +622,27 @@ class Qwen2Generator:
         unfinished = torch.ones((B,), device=dev, dtype=torch.bool)
         fed = torch.empty((B,), device=dev, dtype=torch.long)
         col = torch.zeros((1,), device=dev, dtype=torch.long)
+        n_lp = logprobs
+        if n_lp is not None:
+            # the step's outputs, and the run's: a finished row (its token is the pad) keeps 0 / -1 / -inf
+            lp_tok = torch.zeros((B,), device=dev, dtype=torch.float32)
+            lp_ids = torch.zeros((B, n_lp), device=dev, dtype=torch.long)
+            lp_top = torch.zeros((B, n_lp), device=dev, dtype=torch.float32)
+            out_tok = torch.zeros((B, max_new_tokens), device=dev, dtype=torch.float32)
+            out_ids = torch.full((B, max_new_tokens, n_lp), -1, device=dev, dtype=torch.long)
+            out_top = torch.full((B, max_new_tokens, n_lp), float("-inf"), device=dev, dtype=torch.float32)
 
         def post(raw):
             # next_tokens * unfinished + pad * (1 - unfinished); then unfinished &= next_tokens not in eos  (transformers' order)
             fed.copy_(torch.where(unfinished, raw, torch.full_like(raw, pad)))
+            if n_lp is not None:
+                # of the logits `raw` was chosen from (the library's buffer), behind the choice; `unfinished` still says whose token is real
+                self.logprobs(n_lp, lp_tok, lp_ids if n_lp else None, lp_top if n_lp else None)
+                out_tok.index_copy_(1, col, torch.where(unfinished, lp_tok, torch.zeros_like(lp_tok))[:, None])
+                if n_lp:
+                    live = unfinished[:, None]
+                    out_ids.index_copy_(1, col, torch.where(live, lp_ids, torch.full_like(lp_ids, -1))[:, None])
+                    out_top.index_copy_(1, col, torch.where(live, lp_top, torch.full_like(lp_top, float("-inf")))[:, None])
             if eos:
                 unfinished.logical_and_(~torch.isin(fed, eos_t))
             out.index_copy_(1, col, fed[:, None])
@@ -586,6 +680,8 @@ class Qwen2Generator:
             dead = (~alive[:done + 1]).nonzero()
             if dead.numel():
                 n = int(dead[0, 0]) + 1
+        if n_lp is not None:
+            return out[:, :n].clone(), GenerationLogprobs(out_tok[:, :n].clone(), out_ids[:, :n].clone(), out_top[:, :n].clone())
         return out[:, :n].clone()
 
     @torch.no_grad()

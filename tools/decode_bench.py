@@ -10,6 +10,7 @@ captured graph and called eagerly, against the stock `transformers` decode loop 
     python tools/decode_bench.py --processors --hidden 896 --batch 1 64         (logits processors on against off, greedy and sampled)
     python tools/decode_bench.py --lookup --hidden 896 3584 --rows 4 8 16       (prompt-lookup decoding: the verify step at one sequence)
     python tools/decode_bench.py --lookup --trace-steps 16 --hidden 896 --rows 8    (eager verify steps only: the program of a kernel trace)
+    python tools/decode_bench.py --logprobs 0 5 16 --hidden 896 3584 --batch 1 64   (log-probabilities of the chosen tokens inside the step)
 
 --batch takes up to 64 sequences per step (more than 16 need a library of version 503).  --repeats times the graph replay that many
 times (`graph_ms_per_token` is their median, `graph_ms_per_token_runs` all of them); --no-stock leaves the stock transformers loop (and
@@ -39,6 +40,12 @@ verify + accept) with the recorded run as lookup ids (drafts right wherever the 
 many were), and the draft and accept launches replayed alone.  Derived: tokens per second at full acceptance and the break-even
 acceptance per draft (t_verify / t_plain(1) - 1) / (rows - 1), t_verify = the slower of the two verify runs.  Random weights
 emit noise-like tokens: no acceptance rate on real text is claimed here.
+
+--logprobs N ... times the captured greedy step with the log-probabilities of the chosen tokens (`Qwen2Generator.set_logprobs` / `.logprobs`,
+csrc/llm_logprobs.hip) for every top-n named, against the same build's step without them and against the composition the library allowed
+before inside the same graph: `step(logits=True)` + torch.log_softmax + gather + topk(n) (n = 0: no topk).  Every case by graph replay over
+--new tokens at vocab 151936, measured twice (the second time in reverse order) and averaged; `off` twice more at the ends, so that its
+four runs show the run-to-run spread the additions are read against.
 
 Full layer counts, random bf16 weights (`tools/ttft.py: build_llm`).  Prints ONE JSON line: per (width, batch) the ms per token of each
 path, the bytes a step must read (packed weights + the KV cache at the mean length) and their fraction of 8 TB/s."""
@@ -236,6 +243,68 @@ def measure_processors(llm, pre, batch: int, prompt: int, new: int, dev) -> dict
     res["logits_store_us"] = us("greedy_off_logits_out", "greedy_off")
     res["process_launch_us"] = res["sample_added_us_per_token"]
     res["argmax_from_logits_us"] = round(us("greedy_on", "greedy_off_logits_out") - res["process_launch_us"], 1)
+    del gen
+    return res
+
+
+@torch.no_grad()
+def measure_logprobs(llm, pre, batch: int, prompt: int, new: int, dev, ns) -> dict:
+    from ml_fastvlm_amd.qwen2_decode import Qwen2Generator
+    cfg = llm.config
+    hidden = cfg.hidden_size
+    gen = Qwen2Generator.from_hf(llm, batch, prompt + new + 4, prefill=pre)
+    g = torch.Generator(device=dev).manual_seed(0)
+    emb = (0.5 * torch.randn(batch, prompt, hidden, device=dev, generator=g)).to(torch.bfloat16)
+    mask = torch.ones(batch, prompt, device=dev, dtype=torch.long)
+    res = {"hidden": hidden, "layers": cfg.num_hidden_layers, "batch": batch, "vocab": cfg.vocab_size, "prompt": prompt, "new_tokens": new,
+           "top_n": list(ns)}
+    gen._set_greedy()
+    tok = torch.zeros((batch,), device=dev)
+    top_i = {n: torch.zeros((batch, n), device=dev, dtype=torch.long) for n in ns}
+    top_v = {n: torch.zeros((batch, n), device=dev) for n in ns}
+
+    def lib_step(n):
+        gen.step(logits=False)
+        gen.logprobs(n, tok, top_i[n] if n else None, top_v[n] if n else None)
+
+    def torch_step(n):                                      # what the library allowed before: the logits out, three torch ops
+        lg, ids = gen.step(logits=True)
+        ls = torch.log_softmax(lg, dim=-1)
+        tok.copy_(ls.gather(1, ids[:, None])[:, 0])
+        if n:
+            v, i = torch.topk(ls, n, dim=-1)
+            top_v[n].copy_(v)
+            top_i[n].copy_(i)
+
+    def graph_ms(kind, n):
+        gen.set_logprobs(kind == "lib")
+        gen.start(emb, mask, logits=False)
+        fn = {"off": lambda: gen.step(logits=False), "lib": lambda: lib_step(n), "torch": lambda: torch_step(n)}[kind]
+        graph = _graph_of(fn, dev)
+        graph.replay()
+        gen.start(emb, mask, logits=False)
+        ms = _ms_per(graph.replay, new, dev)
+        assert gen.cache_state() == (prompt + new, 0)
+        return ms
+
+    cases = {"off": ("off", 0)}
+    for n in ns:
+        cases[f"logprobs_{n}"] = ("lib", n)
+        cases[f"torch_{n}"] = ("torch", n)
+    runs = {k: [] for k in cases}
+    runs["off"].append(graph_ms("off", 0))
+    for order in (list(cases), list(cases)[::-1]):              # twice, the second time in reverse order
+        for k in order:
+            runs[k].append(graph_ms(*cases[k]))
+    runs["off"].append(graph_ms("off", 0))
+    gen.set_logprobs(False)
+    for k, v in runs.items():
+        res[f"{k}_ms_per_token"] = round(sum(v) / len(v), 4)
+        res[f"{k}_ms_per_token_runs"] = [round(x, 4) for x in v]
+    res["off_spread_us"] = round(1000 * (max(runs["off"]) - min(runs["off"])), 1)
+    for n in ns:
+        for kind in ("logprobs", "torch"):
+            res[f"{kind}_{n}_added_us_per_token"] = round(1000 * (res[f"{kind}_{n}_ms_per_token"] - res["off_ms_per_token"]), 1)
     del gen
     return res
 
@@ -510,8 +579,26 @@ def main():
     ap.add_argument("--num-beams", type=int, default=0, help="time beam search with this many beams per prompt (--batch = prompts; needs a library of version 505)")
     ap.add_argument("--lookup", action="store_true", help="the verify step of prompt-lookup decoding at one sequence (needs a library of version 507)")
     ap.add_argument("--rows", type=int, nargs="+", default=[4, 8, 16], help="--lookup: rows per verify step")
+    ap.add_argument("--logprobs", type=int, nargs="+", default=None, metavar="N",
+                    help="the step with the chosen tokens' log-probabilities and top-N alternatives, for every N named, against off and against torch ops")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
+    if a.logprobs is not None:
+        from tools.ttft import build_llm
+        from ml_fastvlm_amd import _lib
+        from ml_fastvlm_amd.qwen2_prefill import Qwen2Prefill
+        rows = []
+        for h in (a.hidden if "--hidden" in sys.argv else [896, 3584]):
+            llm = build_llm(h, dev)
+            pre = Qwen2Prefill.from_hf(llm)
+            for b in a.batch:
+                rows.append(measure_logprobs(llm, pre, b, a.prompt, a.new, dev, a.logprobs))
+                torch.cuda.empty_cache()
+            del pre, llm
+            torch.cuda.empty_cache()
+        print(json.dumps({"tool": "decode_bench", "mode": "logprobs", "device": torch.cuda.get_device_name(dev),
+                          "library_version": _lib.logprobs_lib().fvhd_version(), "results": rows}))
+        return
     if a.lookup:
         from tools.ttft import build_llm
         from ml_fastvlm_amd import _lib
