@@ -59,7 +59,7 @@ typedef void* fvhd_stream_t; /* hipStream_t */
  * greedy and sampled steps compute what 504 did, bit for bit, and fvhd_llm_cache_reserve allocates what it did; nothing earlier changed.
  * 506 adds logits processors in the decode step (fvhd_llm_set_logits_processors, fvhd_op_dec_logits_process): off by default, and then
  * every launch of fvhd_llm_start / fvhd_llm_decode is what 505 enqueued, bit for bit; fvhd_llm_cache_reserve also allocates the token
- * history (4 * batch * capacity + batch * vocab / 8 bytes); nothing earlier changed.  508 adds fvhd_gemm_kernel_plan, a read-only query of
+ * history (4 * batch * capacity + batch * vocab / 8 + 4 * batch bytes); nothing earlier changed.  508 adds fvhd_gemm_kernel_plan, a read-only query of
  * fvhd_op_gemm's kernel choice (the FVHD_GEMM_PLAN_* codes): the launcher switches on the same function's value, every launch and its
  * bits are what 507 ran; nothing earlier changed.  509 adds the extension of a started KV cache by a chunk of tokens and its rewind
  * (fvhd_llm_extend, fvhd_llm_cache_rewind, fvhd_op_attention_extend / _cache_append / _extend_positions / _cache_rewind; error word 4):
@@ -651,7 +651,8 @@ int fvhd_op_w4_unpack(fvhd_stream_t stream, const void* src, const void* scales,
 int fvhd_llm_beam_reserve(fvhd_llm* ctx);
 /* The reorder on the context's cache; the later steps run on rows_out sequences (<= the reserved batch; rows_in <= it too).  src_rows =
  * r / num_beams turns G prefilled rows into G * num_beams.  The host arguments are the same every step: capture-safe after
- * fvhd_llm_beam_reserve and fvhd_llm_start.  n_layers + 1 launches. */
+ * fvhd_llm_beam_reserve and fvhd_llm_start.  n_layers + 1 launches.  Refused with logits processors on (their token history is not
+ * reordered: the rows would go on with the history of whatever sequence held the row before). */
 int fvhd_llm_cache_gather(fvhd_llm* ctx, const int64_t* src_rows, int rows_in, int rows_out, fvhd_stream_t stream);
 /* The top continuations of logits fp32 [groups * num_beams, vocab] (16-byte aligned) and beam_scores fp32 [groups, num_beams] ->
  * cand_scores fp32 [groups, keep], cand_index int64 [groups, keep].  Capture-safe after fvhd_llm_beam_reserve.  3 launches. */
@@ -686,14 +687,16 @@ int fvhd_op_dec_cache_gather(fvhd_stream_t stream, void* k_cache, void* v_cache,
  * Synchronises (refused while a stream is being captured).  Like the sampling settings, these are read when fvhd_llm_start /
  * fvhd_llm_decode enqueue: a captured graph keeps the ones it was captured with (when other lists are set later, the 1 KiB block
  * its launches read is kept alive until fvhd_llm_destroy; setting the same lists again changes nothing).  Set them BEFORE fvhd_llm_start: a decode step with processors on after a start without them is an error (it has no
- * history), and a step enqueued with processors off appends nothing to the history.
+ * history), and a step enqueued with processors off appends nothing to the history: g counts the tokens APPENDED (a device word per
+ * sequence), not the steps since fvhd_llm_start, so the later steps see a history without that token and without a gap in its place.
  * With any processor on, the call writes its fp32 logits to logits_out or the context's own buffer, edits them in place with one launch of
  * one workgroup per sequence (it appends the step's fed token to the history and touches at most g + 272 logits per sequence, never the
  * whole row; every logit is edited by exactly one lane, so the bits are the same eager or replayed), then chooses: greedy = the argmax of
  * the processed logits (lowest index on ties, two launches as for the first token), sampling = the sampler on them.  logits_out then
  * holds the PROCESSED scores (transformers' `scores`, not its raw `logits`).  A step that hits the sticky error word appends nothing.
  * Beam search is not covered: transformers applies the processors to log-softmaxed scores there, and fvhd_llm_cache_gather does not
- * reorder the history - keep the processors off around fvhd_llm_beam_topk / fvhd_llm_cache_gather.
+ * reorder the history - keep the processors off around fvhd_llm_beam_topk; fvhd_llm_cache_gather is REFUSED while a processor is on
+ * ("their token history is not reordered"), as fvhd_llm_cache_rewind, fvhd_llm_extend and fvhd_llm_verify are.
  * With every processor off (the default) nothing changes: no launch, no buffer traffic and no kernel branch is added. */
 int fvhd_llm_set_logits_processors(fvhd_llm* ctx, float repetition_penalty, int no_repeat_ngram_size, int min_new_tokens, const int32_t* host_eos_ids,
                                    int n_eos, const int32_t* host_suppress_ids, int n_suppress);

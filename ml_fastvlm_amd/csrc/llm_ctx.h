@@ -92,8 +92,8 @@ struct __attribute__((visibility("default"))) fvhd_llm {     // (its inline cons
     bool proc_lists_captured = false;      // has recorded is retired (kept until fvhd_llm_destroy) when OTHER lists are set, not overwritten
     std::vector<int32_t> proc_lists_host;  // what proc_lists holds (setting the same lists again uploads and retires nothing)
     int* hist = nullptr;                   // inside `dc`: per-row token history [dc_batch][dc_cap], the bitmap of its tokens
-    unsigned* hist_seen = nullptr;         // [dc_batch][ceil(V / 32)] and the prompt length recorded by the last fvhd_llm_start that ran
-    int* hist_base = nullptr;              // with processors on (history length = cache length - it)
+    unsigned* hist_seen = nullptr;         // [dc_batch][ceil(V / 32)] and per row the number of tokens in its history [dc_batch]: zeroed by a
+    int* hist_count = nullptr;             // fvhd_llm_start with processors on (its rows), advanced by every step enqueued with them on
     bool hist_started = false;             // that start has happened: a decode step with processors on has a history to append to
     // fvhd_llm_spec_reserve (llm_spec.hip): one allocation of its own, sized for the reserved cache - the T-row activations, the k / v
     // staging rows [T][nkv][hd], the per-row positions, the attention partials [T][nh][att_S][hd + 2] and counters [nh], the drafts and

@@ -90,9 +90,9 @@ struct DecLogitsArgs {
     unsigned* seen = nullptr;      // [B][ceil(V / 32)] bits: token occurs in the row's history (tested and set by the append)
     const int64_t* tok = nullptr;  // the step's fed ids: tok, else last; both NULL = nothing to append (the first token, the single op)
     const int64_t* last = nullptr;
-    const int* len = nullptr;      // device words: history length before the append = *len - *base
-    int* base = nullptr;
-    int start_T = 0;               // > 0: fvhd_llm_start's launch - the history is empty and *base = start_T is recorded
+    int* count = nullptr;          // device words [B]: the tokens in each row's history - read before the append, written back behind it
+                                   // (NOT the cache length less the prompt: a step enqueued with processors off appends and counts nothing)
+    int start_T = 0;               // > 0: fvhd_llm_start's launch - the history is empty: count[b] = 0
     int g_fixed = -1;              // >= 0: the history length itself (the single op)
     float penalty = 1.f;           // repetition_penalty (1 = off)
     int ngram = 0, min_new = 0;    // no_repeat_ngram_size, min_new_tokens (0 = off)

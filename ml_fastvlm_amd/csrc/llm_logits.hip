@@ -9,8 +9,10 @@
 //   MinNewTokensLengthLogitsProcessor(0, m)  g < m: every EOS id banned
 //   SuppressTokensLogitsProcessor            the ids banned, always
 // One workgroup per row, one launch:
-//   append   thread 0 adds the step's fed token to the row's history.  A bitmap of V bits per row ("token is in the history") is tested and
-//            set there, and the entry records whether it is the token's first occurrence (sign bit clear) or a repeat (sign bit set)
+//   append   thread 0 adds the step's fed token to the row's history, at the row's own count (a device word per row that only these
+//            launches advance: a step enqueued with processors off appends nothing, counts nothing and leaves no gap).  A bitmap of V
+//            bits per row ("token is in the history") is tested and set there, and the entry records whether it is the token's first
+//            occurrence (sign bit clear) or a repeat (sign bit set)
 //   penalty  lanes walk the history in strides of 256; only a first occurrence edits its logit, so each distinct token is read, scaled
 //            and written by exactly one lane: no atomics, the same bits eager or replayed, however often a token repeats
 //   barrier  the bans come after every penalty (a token both penalised and banned ends up banned)
@@ -43,13 +45,13 @@ __global__ __launch_bounds__(256) void dec_logits_process_kernel(const DecLogits
     int* h = a.hist + (size_t)b * a.cap;
     float* x = a.logits + (size_t)b * V;
     if (tid == 0) {
-        int g = a.g_fixed >= 0 ? a.g_fixed : a.start_T > 0 ? 0 : *a.len - *a.base;
+        int g = a.g_fixed >= 0 ? a.g_fixed : a.start_T > 0 ? 0 : a.count[b];
         g = max(0, min(g, a.cap));
-        if (a.start_T > 0 && b == 0) *a.base = a.start_T;        // (no workgroup of this launch reads it)
         if ((a.tok || a.last) && g < a.cap) {
             history_append(h, a.seen + (size_t)b * ((V + 31) / 32), g, a.tok ? a.tok[b] : a.last[b], V);
             ++g;
         }
+        if (a.g_fixed < 0) a.count[b] = g;                       // the row's own word: only this workgroup reads or writes it
         g_s = g;
     }
     __syncthreads();
@@ -98,8 +100,7 @@ extern "C" int fvhd_launch_dec_logits_process(hipStream_t st, const DecLogitsArg
         a->min_new < 0 || a->n_eos < 0 || a->n_sup < 0 || (a->n_eos && !a->eos) || (a->n_sup && !a->sup))
         return (int)hipErrorInvalidValue;
     if ((a->tok || a->last) && !a->seen) return (int)hipErrorInvalidValue;
-    if (a->g_fixed < 0 && !a->base) return (int)hipErrorInvalidValue;
-    if (a->g_fixed < 0 && a->start_T <= 0 && !a->len) return (int)hipErrorInvalidValue;
+    if (a->g_fixed < 0 && !a->count) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(dec_logits_process_kernel, dim3(a->B), dim3(256), 0, st, *a);
     return (int)hipGetLastError();
 }

@@ -70,7 +70,7 @@ int dec_embedding_error(const fvhd_llm* c, const char* who)
 DecLogitsArgs dec_logits_args(fvhd_llm* c, float* logits, int B, hipStream_t st)
 {
     DecLogitsArgs a;
-    a.logits = logits; a.B = B; a.V = c->V; a.hist = c->hist; a.cap = c->dc_cap; a.seen = c->hist_seen; a.len = c->len; a.base = c->hist_base;
+    a.logits = logits; a.B = B; a.V = c->V; a.hist = c->hist; a.cap = c->dc_cap; a.seen = c->hist_seen; a.count = c->hist_count;
     a.penalty = c->proc_penalty; a.ngram = c->proc_ngram; a.min_new = c->proc_n_eos ? c->proc_min_new : 0;
     a.eos = c->proc_lists; a.n_eos = c->proc_n_eos; a.sup = c->proc_lists ? c->proc_lists + kMaxEos : nullptr; a.n_sup = c->proc_n_sup;
     if (c->proc_lists && is_capturing(st)) c->proc_lists_captured = true;     // the caller's graph now reads the lists: retired, never overwritten
@@ -147,7 +147,7 @@ int fvhd_llm_cache_reserve(fvhd_llm* c, int batch, int capacity)
                  o_apart = a.take((size_t)batch * nh * c->att_S * (hd + 2) * 4), o_cnt = a.take((size_t)(ncol + batch * nh) * 4),
                  o_av = a.take((size_t)lm_ncol * 16 * NB * 4), o_ai = a.take((size_t)lm_ncol * 16 * NB * 4), o_logits = a.take((size_t)batch * V * 4),
                  o_rope = a.take((size_t)c->ws_pos * hd * 4), o_sws = a.take(fvhd_dec_sample_ws_bytes()), o_rstd = a.take(4 * 64),
-                 o_hist = a.take((size_t)batch * capacity * 4), o_seen = a.take((size_t)batch * ((V + 31) / 32) * 4), o_hbase = a.take(4);
+                 o_hist = a.take((size_t)batch * capacity * 4), o_seen = a.take((size_t)batch * ((V + 31) / 32) * 4), o_hcount = a.take((size_t)batch * 4);
     hipError_t he = hipDeviceSynchronize();                      // refused while a stream is being captured (like fvhd_llm_reserve)
     if (he != hipSuccess) return lhip("fvhd_llm_cache_reserve: hipDeviceSynchronize", he);
     if (c->dc) (void)hipFree(c->dc);
@@ -174,7 +174,7 @@ int fvhd_llm_cache_reserve(fvhd_llm* c, int batch, int capacity)
     c->len = (int*)(d + o_len); c->status = (int*)(d + o_status); c->dh = d + o_h; c->dq = d + o_q; c->datt = d + o_att; c->dact = d + o_act;
     c->dpart = (float*)(d + o_part); c->apart = (float*)(d + o_apart); c->cnt = (int*)(d + o_cnt); c->amax_v = (float*)(d + o_av);
     c->amax_i = (int*)(d + o_ai); c->dlogits = (float*)(d + o_logits); c->drope = (float*)(d + o_rope); c->sws = d + o_sws; c->drstd = (float*)(d + o_rstd);
-    c->hist = (int*)(d + o_hist); c->hist_seen = (unsigned*)(d + o_seen); c->hist_base = (int*)(d + o_hbase);
+    c->hist = (int*)(d + o_hist); c->hist_seen = (unsigned*)(d + o_seen); c->hist_count = (int*)(d + o_hcount);
     c->dc_bytes = a.off; c->dc_batch = batch; c->dc_cap = capacity; c->dc_pos = c->ws_pos;
     // the decode's own copy of the rotary table: a later, larger prefill may replace the prefill workspace under a captured decode graph
     if ((he = hipMemcpy(c->drope, c->rope, (size_t)c->ws_pos * hd * 4, hipMemcpyDeviceToDevice)) != hipSuccess) return lhip("hipMemcpy(rope table)", he);
@@ -226,8 +226,8 @@ int fvhd_llm_start(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* ke
     const bool proc = processors_on(c);
     c->hist_started = proc;
     if (proc) {
-        // an empty history: no token is in the bitmap, and the launch records the prompt length the later steps count from; then the
-        // processors on the prefill's logits, before either choice reads them
+        // an empty history: no token is in the bitmap, and the launch zeroes the rows' history counts; then the processors on the
+        // prefill's logits, before either choice reads them
         if ((he = hipMemsetAsync(c->hist_seen, 0, (size_t)B * ((c->V + 31) / 32) * 4, st)) != hipSuccess) return lhip("history bitmap reset", he);
         DecLogitsArgs pa = dec_logits_args(c, logits, B, st);
         pa.start_T = T;
@@ -428,6 +428,9 @@ int fvhd_llm_cache_gather(fvhd_llm* c, const int64_t* src_rows, int rows_in, int
     if (rows_in < 1 || rows_in > c->dc_batch || rows_out < 1 || rows_out > c->dc_batch)
         return lfail("fvhd_llm_cache_gather: rows_in and rows_out must be in [1, the batch of fvhd_llm_cache_reserve]");
     if (int e = dec_status_error(c, "fvhd_llm_cache_gather")) return e;
+    if (processors_on(c))
+        return lfail("fvhd_llm_cache_gather: logits processors are on (fvhd_llm_set_logits_processors) - their token history is not reordered; "
+                     "switch them off around fvhd_llm_cache_gather");
     LLM_ON_DEVICE(c);
     DecCacheGatherArgs a;
     a.kc = c->kcache; a.vc = c->vcache; a.layers = c->L; a.batch = c->dc_batch; a.mask = c->mask; a.posv = c->posv; a.src = src_rows;

@@ -338,7 +338,11 @@ class Qwen2Generator:
     def cache_gather(self, src_rows: torch.Tensor, rows_in: int) -> None:
         """cache row r (K / V of every layer, mask, next position) = old row src_rows[r] (`fvhd_llm_cache_gather`); the following steps run
         on len(src_rows) rows.  src_rows: int64 on the device, entries in [0, rows_in).  Capture-safe after `beam_reserve`.  The chosen ids are
-        not reordered: continue with extend(), or step() with explicit ids - step(None) and verify() are refused."""
+        not reordered: continue with extend(), or step() with explicit ids - step(None) and verify() are refused.  Not with logits
+        processors: their token history is not reordered."""
+        if self._processors is not None:
+            raise ValueError("cache_gather: logits processors are set (set_logits_processors) - their token history is not reordered; "
+                             "clear them with set_logits_processors()")
         if src_rows.dtype != torch.long or src_rows.device != self.device or src_rows.dim() != 1 or not src_rows.is_contiguous():
             raise ValueError(f"src_rows must be a contiguous 1-D int64 tensor on {self.device}")
         rows_out = src_rows.shape[0]
@@ -401,7 +405,8 @@ class Qwen2Generator:
             raise ValueError(f"drafts must be a contiguous 1-D int64 tensor on {self.device}")
         T = drafts.shape[0] + 1
         self._verify_refusal("verify", T)
-        self._stale_ids_refusal("verify")
+        if not getattr(self, "_do_sample", False):               # under sampling the library refuses, and names that reason first, as it
+            self._stale_ids_refusal("verify")                    # does when called directly ("sampling is on ... greedy only")
         if self._spec_rows < T:
             raise ValueError(f"verify: {T} rows exceed the rows this generator reserved with spec_reserve ({self._spec_rows or 'none'})")
         if logits and self._spec_logits is None:
@@ -509,6 +514,7 @@ class Qwen2Generator:
         lib = _lib.sampling_lib()
         _lib.check(lib.fvhd_llm_set_sampling(self.pre._h, int(bool(do_sample)), float(temperature), int(top_k), float(top_p),
                                              int(seed) & 0xFFFFFFFFFFFFFFFF), "fvhd_llm_set_sampling")
+        self._do_sample = bool(do_sample)
 
     # ---- logits processors ---------------------------------------------------------------------------------------------------------------
     def set_logits_processors(self, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0,

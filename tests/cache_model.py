@@ -12,6 +12,13 @@ buffer, tokens written, finished, steps, tokens).
 Every method mirrors one call.  It raises `Refused` where the HOST refuses (the message names the reason as the library's does), returns
 False where the device word is already set or gets set (nothing changes: everything is frozen until `start`), True where the op ran.
 
+THE SETTINGS (include/fvhd.h "LLM sampling", "LLM logits processors", "LLM log-probabilities") add state beside the cache, held here too:
+the processors' configuration (`proc`), "history started" and per row the ids appended since `start` (`hist`: appended only by a step
+enqueued with processors on; emptied by `start` for its B rows); whose logits are in the context's own buffer (`lp_where`: None / "start" /
+"decode" / "extend" - cleared by verify, a lookup step, and a start / step / extend that was given a logits_out); sampling on / off with
+its seed, and per row the (row, n) of the draw (`draw_key`: n = the cache length when the token is chosen).  Every method refuses what the
+header refuses under these settings, with the library's reason, and then changes nothing.
+
 PINNING: tests/test_cache_model.py checks `flat()` against transformers' own incremental forward with past_key_values, op by op, and the
 accept / draft / error-word bookkeeping against hand-made cases."""
 from __future__ import annotations
@@ -23,6 +30,16 @@ from ml_fastvlm_amd.prompt_lookup import propose
 
 MAX_VERIFY_ROWS = 16
 STALE = "the ids the previous step chose belong to the rows as they were before the cache reorder / rewind"
+# the reasons of the settings' refusals: each a phrase that both the library's message and the generator's carry
+NO_CHUNK_IDS = "their token history has no ids for an embedded chunk"
+NOT_REWOUND = "their token history is not rewound"
+NOT_REORDERED = "their token history is not reordered"
+NOT_MAINTAINED = "does not maintain their token history"
+GREEDY_ONLY = "sampling is on"
+NO_HISTORY = "the sequence was started without them"
+LP_OFF = "keeping the logits is off"
+LP_NOT_LAST = "did not leave its logits in the context's buffer"
+LP_NO_SCRATCH = "no scratch"
 
 
 class Refused(Exception):
@@ -42,6 +59,15 @@ class CacheModel:
         self.run_batch = self.length = self.error = 0
         self.ids_stale = False
         self.lookup = None                     # dict(buffer, out, written, finished, steps, tokens, limit, eos) while a generation is open
+        # ---- the settings (a context begins with all of them off)
+        self.proc = None                       # dict(p, n, m, eos, suppress) - tests/logits_testlib.hf_chain's keywords - or None: all off
+        self.hist_started = False              # the last start ran with processors on: a step with them on has a history to append to
+        self.hist = [[] for _ in range(self.batch)]      # per row: the ids appended since that row's last start with processors on
+        self.lp_on = self.lp_scratch = False   # fvhd_llm_set_logprobs; its scratch exists once it was ever on
+        self.lp_where = None                   # whose logits the context's own buffer holds: None / "start" / "decode" / "extend"
+        self.sampling, self.seed = False, 0
+        self.drawn = None                      # the (row, n) of the draws of the op that just ran (None: it chose greedily, or chose nothing)
+        self.last_chunk = None                 # (B, T) of the last start / extend: the rows score_last scores
 
     # ---- helpers -----------------------------------------------------------------------------------------------------------------------
     def state(self):
@@ -60,15 +86,64 @@ class CacheModel:
         if self.ids_stale:
             raise Refused(f"{who}: {STALE} - continue with extend, or with a step on explicit ids")
 
+    # ---- the settings ------------------------------------------------------------------------------------------------------------------
+    def set_processors(self, p=1.0, n=0, m=0, eos=None, suppress=None):
+        """fvhd_llm_set_logits_processors: the configuration alone - the history and "history started" belong to start / step"""
+        on = p != 1.0 or n > 0 or (m > 0 and eos) or suppress
+        self.proc = dict(p=float(p), n=int(n), m=int(m), eos=list(eos or []), suppress=list(suppress or [])) if on else None
+
+    def set_sampling(self, on, seed=0):
+        self.sampling, self.seed = bool(on), int(seed)
+
+    def set_logprobs(self, on):
+        """fvhd_llm_set_logprobs: the setting (and the scratch, once); what the buffer holds is the calls' business"""
+        self.lp_on = bool(on)
+        self.lp_scratch = self.lp_scratch or self.lp_on
+
+    def draw_key(self, row, add=1):
+        """(seed, row, n) of the draw for `row` by a call that adds `add` slots now: n is the length when the token is chosen"""
+        return self.seed, row, self.length + add
+
+    def _chose(self, B, where, logits_given):
+        """behind a start / step / extend that ran: the draws' keys and where its logits are"""
+        self.drawn = [(r, self.length) for r in range(B)] if self.sampling else None
+        kept = where != "decode" or self.proc is not None or self.lp_on or self.sampling      # a plain greedy step keeps no logits
+        self.lp_where = where if kept and not logits_given else None
+
+    def may_step_none(self):
+        """would step(ids = None) be accepted now (nothing is changed)"""
+        return bool(self.run_batch) and not self.ids_stale and not (self.proc is not None and not self.hist_started)
+
+    def logprobs(self, logits_given=False):
+        """fvhd_llm_logprobs(ctx, logits or NULL, ...): of the ids the last start / step / extend chose.  Changes nothing."""
+        self._started("logprobs")
+        if self._pending("logprobs"):
+            return False
+        self._stale("logprobs")
+        if not logits_given:
+            if not self.lp_on:
+                raise Refused(f"logprobs: logits is NULL and {LP_OFF}")
+            if self.lp_where is None:
+                raise Refused(f"logprobs: logits is NULL but the last start / step / extend {LP_NOT_LAST}")
+        if not self.lp_scratch:
+            raise Refused(f"logprobs: {LP_NO_SCRATCH} - set_logprobs(1) reserves it")
+        return True
+
+    def score_last(self):
+        """Qwen2Generator.score_last -> the (B, T) of the rows it scores: those of the last start / extend.  Changes nothing."""
+        self._started("score_last")
+        return self.last_chunk
+
     def _ids(self, ids, n):
         ids = [int(i) for i in (ids.tolist() if isinstance(ids, torch.Tensor) else ids)]
         assert len(ids) == n, (len(ids), n)
         return ids
 
     # ---- start / step / extend ---------------------------------------------------------------------------------------------------------
-    def start(self, embeds, mask, ids_returned):
+    def start(self, embeds, mask, ids_returned, logits_given=False):
         """fvhd_llm_start with generate's own position ids (cumsum(mask) - 1, 0 on padding): slots [0, T), length = T, next position =
-        the last column's position + 1, the error word cleared, every host flag reset"""
+        the last column's position + 1, the error word cleared, every host flag reset; with processors on the history of ITS B rows
+        emptied (the other rows keep what they held)"""
         B, T = embeds.shape[:2]
         if not (1 <= B <= self.batch and 1 <= T <= self.capacity):
             raise Refused("start: batch / length exceed the reserved cache")
@@ -81,13 +156,21 @@ class CacheModel:
         self.last[:B] = self._ids(ids_returned, B)
         self.run_batch, self.length, self.error = B, T, 0
         self.ids_stale, self.lookup = False, None
+        self.hist_started = self.proc is not None
+        if self.hist_started:
+            for r in range(B):
+                self.hist[r] = []
+        self.last_chunk = (B, T)
+        self._chose(B, "start", logits_given)
         return True
 
-    def step(self, ids, ids_returned):
-        """fvhd_llm_decode: ids None = the last chosen ids (refused while they are stale)"""
+    def step(self, ids, ids_returned, logits_given=False):
+        """fvhd_llm_decode: ids None = the last chosen ids (refused while they are stale); with processors on the fed ids join the history"""
         self._started("step")
         if ids is None:
             self._stale("step(ids = None)")
+        if self.proc is not None and not self.hist_started:
+            raise Refused(f"step: logits processors are on but {NO_HISTORY} (no token history)")
         if self._pending("step"):
             return False
         B = self.run_batch
@@ -107,9 +190,13 @@ class CacheModel:
         self.pos[:B] += 1
         self.length = L + 1
         self.last[:B] = self._ids(ids_returned, B)
+        if self.proc is not None:                                # a step enqueued with them off appends nothing
+            for r in range(B):
+                self.hist[r].append(fed[r])
+        self._chose(B, "decode", logits_given)
         return True
 
-    def extend(self, chunk, chunk_mask, ids_returned):
+    def extend(self, chunk, chunk_mask, ids_returned, logits_given=False):
         """fvhd_llm_extend without position ids: every row continues from its next position over its valid chunk tokens"""
         self._started("extend")
         B, T = self.run_batch, chunk.shape[1]
@@ -117,6 +204,8 @@ class CacheModel:
             raise Refused(f"extend: the chunk has {chunk.shape[0]} rows, the started batch is {B}")
         if T < 1 or T > self.capacity:
             raise Refused(f"extend: the chunk length {T} must be in [1, capacity]")
+        if self.proc is not None:
+            raise Refused(f"extend: logits processors are on - {NO_CHUNK_IDS}")
         if self._pending("extend"):
             return False
         self.lookup, self.ids_stale = None, False
@@ -130,6 +219,8 @@ class CacheModel:
         self.pos[:B] += m[:, :T - 1].long().sum(-1) + 1           # the position of the chunk's last token + 1
         self.length = L + T
         self.last[:B] = self._ids(ids_returned, B)
+        self.last_chunk = (B, T)
+        self._chose(B, "extend", logits_given)
         return True
 
     # ---- rewind / gather ---------------------------------------------------------------------------------------------------------------
@@ -138,6 +229,8 @@ class CacheModel:
         self._started("rewind")
         B = self.run_batch
         keep = self._ids(keep, B)
+        if self.proc is not None:
+            raise Refused(f"rewind: logits processors are on - {NOT_REWOUND}")
         if self._pending("rewind"):
             return False
         self.lookup, self.ids_stale = None, True
@@ -155,6 +248,8 @@ class CacheModel:
         rows_out = len(src)
         if not (1 <= rows_in <= self.batch and 1 <= rows_out <= self.batch):
             raise Refused("gather: rows_in and rows_out must be in [1, the reserved batch]")
+        if self.proc is not None:
+            raise Refused(f"gather: logits processors are on - {NOT_REORDERED}")
         if self._pending("gather"):
             return False
         self.run_batch = rows_out
@@ -175,6 +270,10 @@ class CacheModel:
             raise Refused(f"{who}: the verify step takes ONE sequence")
         if not 2 <= rows <= MAX_VERIFY_ROWS:
             raise Refused(f"{who}: rows must be in [2, {MAX_VERIFY_ROWS}]")
+        if self.sampling:
+            raise Refused(f"{who}: {GREEDY_ONLY} - the verify step is greedy only")
+        if self.proc is not None:
+            raise Refused(f"{who}: logits processors are on - the verify step {NOT_MAINTAINED}")
         self._stale(who)
 
     def _accept(self, drafts, ids, cut=None):
@@ -209,6 +308,7 @@ class CacheModel:
         if self._pending("verify"):
             return 0
         self.lookup = None
+        self.lp_where = self.drawn = None                        # a verify step's rows are not "the logits of the last step"
         return self._accept(drafts, self._ids(ids_returned, len(ids_returned)))
 
     def lookup_begin(self, lookup_ids, eos_ids, max_new_tokens):
@@ -232,7 +332,10 @@ class CacheModel:
         if self.lookup is None:
             raise Refused("lookup_step: no token buffer - lookup_begin after start")
         g = self.lookup
-        if self._pending("lookup_step") or g["finished"]:
+        if self._pending("lookup_step"):
+            return 0
+        self.lp_where = self.drawn = None                        # (a finished generation's step still enqueues: it clears the record too)
+        if g["finished"]:
             return 0
         drafts = self.lookup_drafts(rows, max_ngram)
 

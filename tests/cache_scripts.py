@@ -10,10 +10,15 @@ ours).  Two sides run the same scripts:
               compare enough steps) and, where a script calls `sens()`, how far the state error the script exists for moves the oracle's
               logits.  `python tests/cache_scripts.py` writes that table (profiles/cache_sequences_sensitivity.md).
 
+Scripts g - m cross the SETTINGS (logits processors, sampling, log-probabilities) with those calls: the model also holds what the settings
+add beside the cache, and a second side - the `twin`, on its own context with the same weights - is the route the first is compared
+with: the raw logits that transformers' processors turn into the scores the first must return, or the run that never tried a refused call.
+
 Importing this needs no GPU."""
 from __future__ import annotations
 
 import copy
+import functools
 import os
 import sys
 import types
@@ -23,10 +28,23 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 if __name__ == "__main__":                                       # run as a script: the package and `oracle` live one directory up
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from cache_model import CacheModel  # noqa: E402
+from cache_model import CacheModel, Refused  # noqa: E402
 from llm_testlib import DELTA, agree, metrics, prompt, same_bits, wide_prompt  # noqa: E402
+from logits_testlib import hf_chain  # noqa: E402
 
 REL, COS = 2e-2, 0.9995        # the budget of test_gpu_extend.py / compare_prefill for last-position logits
+
+
+def lowest_argmax(x):
+    """argmax with the library's tie rule (the lowest index)"""
+    return (x == x.max(-1, keepdim=True).values).float().argmax(-1)
+
+
+def processed(model, raw):
+    """transformers' processors, configured as the model's, on raw logits [B, V] with the MODEL's history of the run's rows -> scores (CPU)"""
+    B = raw.shape[0]
+    hist = torch.tensor([model.hist[r] for r in range(B)], dtype=torch.long).reshape(B, -1)
+    return hf_chain(hist, raw.detach().float().cpu(), **model.proc)
 
 
 def oracle_rows(ref, flats, last=1):
@@ -62,7 +80,11 @@ class Side:
     def _record(self, lg, ids, want, what):
         top = want.topk(2, -1).values
         self.margins.append(float((top[:, 0] - top[:, 1]).min()))
-        if self.gpu:
+        if self.gpu and self.model.proc is not None:
+            # processed scores hold -inf: no norm.  They are compared with transformers' processors on the twin's raw logits bit for bit
+            # (`check_processed`), and the twin's raw logits with the oracle under the budget
+            print(f"{self.name} {what}: {want.shape[0]} rows of processed scores, oracle margin {self.margins[-1]:.3f}")
+        elif self.gpu:
             worst_rel, worst_cos = 0.0, 1.0
             for r in range(want.shape[0]):                       # every row on its own: one bad row must not hide among good ones
                 rel, cos, _ = metrics(lg[r], want[r])
@@ -72,6 +94,8 @@ class Side:
 
     def _steps(self, lg, ids, want, what, per_position=False):
         self._record(lg, ids, want, what)
+        if self.model.sampling:                                  # the ids are draws: nothing for `agree`
+            return
         if per_position:                                         # a verify step: its rows are consecutive steps of the one sequence
             for t in range(want.shape[0]):
                 self.rec.append((ids[t:t + 1].cpu(), want[t:t + 1].argmax(-1).cpu(), want[t:t + 1].cpu()))
@@ -100,35 +124,72 @@ class Side:
     def sens(self, *a, **k):
         pass
 
+    def hist_sens(self, *a, **k):
+        pass
+
+    # ---- the settings -----------------------------------------------------------------------------------------------------------------
+    def set_processors(self, **kw):
+        """p, n, m, eos, suppress (hf_chain's keywords); none = all off"""
+        self.model.set_processors(**kw)
+        self._set_processors(kw)
+
+    def set_sampling(self, on, seed=0, temperature=1.0, top_k=0, top_p=1.0):
+        self.model.set_sampling(on, seed)
+        self.warp = (temperature, top_k, top_p)
+        self._set_sampling(on, seed, temperature, top_k, top_p)
+
+    def set_logprobs(self, on):
+        self.model.set_logprobs(on)
+        self._set_logprobs(on)
+
+    def refused(self, reason, on_model, on_impl=None):
+        """the model refuses the call with `reason`; so does the implementation (on_impl(gen), GPU side) - and nothing has changed"""
+        before = copy.deepcopy({k: v for k, v in vars(self.model).items() if k != "table"})
+        try:
+            on_model(self.model)
+        except Refused as err:
+            assert reason in str(err), (self.name, reason, str(err))
+        else:
+            raise AssertionError(f"{self.name}: the model does not refuse ({reason})")
+        after = {k: v for k, v in vars(self.model).items() if k != "table"}
+        assert all(torch.equal(before[k], after[k]) if isinstance(after[k], torch.Tensor) else before[k] == after[k] for k in after), (self.name, reason)
+        if on_impl is not None:
+            self._refused(reason, on_impl)
+
     # ---- the ops ----------------------------------------------------------------------------------------------------------------------
-    def _batch_op(self, got, what, length=True):
+    def _batch_op(self, got, what, length=True, raw=None):
         m, B = self.model, self.model.run_batch
         self._check_state(length)
         want = self.want()
+        if m.proc is not None:
+            want = processed(m, want).to(want.device)            # the oracle's processed scores: their margins and ids are `agree`'s
         if got is None:
             lg, ids = want, want.argmax(-1)
             m.last[:B] = ids.tolist()
         else:
             lg, ids = got
+            if lg is None:                                       # the op kept its logits in the context's buffer: the twin's stand in
+                lg = raw
         self._steps(lg, ids, want, what)
         return lg.clone(), ids.clone()
 
-    def start(self, e, mask, what="start"):
-        got = self._start(e, mask)
-        assert self.model.start(e, mask, got[1] if got else [0] * e.shape[0])
-        return self._batch_op(got, what)
+    def start(self, e, mask, what="start", given=True, raw=None):
+        """given: the call is given a logits_out (False: the logits stay in the context's own buffer, and `raw` is what the record gets)"""
+        got = self._start(e, mask, given)
+        assert self.model.start(e, mask, got[1] if got else [0] * e.shape[0], logits_given=given)
+        return self._batch_op(got, what, raw=raw)
 
-    def step(self, ids=None, what="step", length=True, got=None):
+    def step(self, ids=None, what="step", length=True, got=None, given=True, raw=None):
         """got: (logits, ids) of a step that already ran (a replayed graph)"""
         if got is None:
-            got = self._step(ids)
-        assert self.model.step(ids, got[1] if got else [0] * self.model.run_batch)
-        return self._batch_op(got, what, length)
+            got = self._step(ids, given)
+        assert self.model.step(ids, got[1] if got else [0] * self.model.run_batch, logits_given=given)
+        return self._batch_op(got, what, length, raw=raw)
 
-    def extend(self, e, mask, what="extend"):
-        got = self._extend(e, mask)
-        assert self.model.extend(e, mask, got[1] if got else [0] * self.model.run_batch)
-        return self._batch_op(got, what)
+    def extend(self, e, mask, what="extend", given=True, raw=None):
+        got = self._extend(e, mask, given)
+        assert self.model.extend(e, mask, got[1] if got else [0] * self.model.run_batch, logits_given=given)
+        return self._batch_op(got, what, raw=raw)
 
     def rewind(self, keep, length=True, ran=False):
         if not ran:
@@ -164,6 +225,7 @@ class Side:
 
     _start = _step = _extend = _verify = lambda self, *a: None
     _rewind = _gather = lambda self, *a: None
+    _set_processors = _set_sampling = _set_logprobs = _refused = lambda self, *a: None
 
 
 class GpuSide(Side):
@@ -179,18 +241,40 @@ class GpuSide(Side):
         if length:                                               # first: where the host's count is None this is the re-read
             assert self.gen.length() == self.model.length, (self.name, self.gen.length(), self.model.length)
         assert self.gen.cache_state() == self.model.state(), (self.name, self.gen.cache_state(), self.model.state())
+        assert self.gen._run_batch == self.model.run_batch, (self.name, self.gen._run_batch, self.model.run_batch)
 
     def same(self, a, b, what):
         assert same_bits(a, b), (self.name, what, (a - b).abs().max().item())
 
-    def _start(self, e, mask):
-        return self.gen.start(e.to(self.dev, torch.bfloat16), mask.to(self.dev))
+    def _start(self, e, mask, given=True):
+        return self.gen.start(e.to(self.dev, torch.bfloat16), mask.to(self.dev), logits=given)
 
-    def _step(self, ids):
-        return self.gen.step(None if ids is None else torch.as_tensor(ids, dtype=torch.long).to(self.dev).contiguous())
+    def _step(self, ids, given=True):
+        return self.gen.step(None if ids is None else torch.as_tensor(ids, dtype=torch.long).to(self.dev).contiguous(), logits=given)
 
-    def _extend(self, e, mask):
-        return self.gen.extend(e.to(self.dev, torch.bfloat16), mask.to(self.dev))
+    def _extend(self, e, mask, given=True):
+        return self.gen.extend(e.to(self.dev, torch.bfloat16), mask.to(self.dev), logits=given)
+
+    def _set_processors(self, kw):
+        self.gen.set_logits_processors(repetition_penalty=kw.get("p", 1.0), no_repeat_ngram_size=kw.get("n", 0), min_new_tokens=kw.get("m", 0),
+                                       eos_token_id=kw.get("eos") or None, suppress_tokens=kw.get("suppress") or None)
+
+    def _set_sampling(self, on, seed, temperature, top_k, top_p):
+        self.gen.set_sampling(on, temperature, top_k, top_p, seed)
+
+    def _set_logprobs(self, on):
+        self.gen.set_logprobs(on)
+
+    def _refused(self, reason, on_impl):
+        from ml_fastvlm_amd._lib import FvhdError
+        try:
+            on_impl(self.gen)
+        except (ValueError, RuntimeError, FvhdError) as err:
+            assert reason in str(err), (self.name, reason, str(err))
+        else:
+            raise AssertionError(f"{self.name}: the library does not refuse ({reason})")
+        self._check_state()
+        assert self.gen._run_batch == self.model.run_batch
 
     def _rewind(self, keep):
         self.gen.rewind(keep)
@@ -209,6 +293,21 @@ class OracleSide(Side):
     def __init__(self, ref, batch, cap, name=""):
         super().__init__(ref, batch, cap, name)
         self.table = []                        # (script, mutation, the op it is measured at, rel-L2 of mutated against unmutated logits)
+        self.hist_table = []                   # (script, mutation, the op, logits of the run's rows whose processed score moves, largest finite move)
+
+    def hist_sens(self, kind, at, wrong):
+        """how far the oracle's PROCESSED scores of the op that just ran move under a wrong history `wrong` (one id list per row of the
+        run) -> the number of logits whose bits differ.  Scores that become or stop being -inf count; the largest move is over the finite"""
+        m = self.model
+        raw = self.want()
+        good = processed(m, raw)
+        raw = raw.float().cpu()                                  # (row by row: the wrong histories need not be of one length)
+        bad = torch.cat([hf_chain(torch.tensor([w], dtype=torch.long).reshape(1, -1), raw[r:r + 1], **m.proc) for r, w in enumerate(wrong)])
+        moved = good.view(torch.int32) != bad.view(torch.int32)
+        fin = moved & torch.isfinite(good) & torch.isfinite(bad)
+        big = float((good - bad)[fin].abs().max()) if bool(fin.any()) else 0.0
+        self.hist_table.append((self.name, kind, at, int(moved.sum()), big))
+        return int(moved.sum())
 
     def sens(self, kind, at, row=0, slot=None, slots=None, stale=0, other=None):
         """the rel-L2 between the oracle's logits of `row` on its flat sequence and on the sequence with one state error:
@@ -443,6 +542,363 @@ def script_f(side, seed=14):
     return fed, eager
 
 
+# ---- g - m: the settings crossed with the cache calls ----------------------------------------------------------------------------------------
+PROC_X = dict(p=1.3, n=2, m=4)                                   # + eos and suppress made from the raw first choice (`proc_cfg`)
+PROC_J = dict(p=1.3, n=2, suppress=[3, 9])
+PROC_Y = dict(p=1.7, m=3, eos=[5], suppress=[11])
+G_B, G_P, G_STEPS = 3, 21, 8
+SAMPLING = dict(temperature=1.3, top_k=0, top_p=1.0)             # a broad distribution: rows on equal logits draw different ids
+
+
+def proc_cfg(first_raw):
+    """script g's configuration: the raw first choice of every row is suppressed (the first token has to change), min_new_tokens bans two
+    EOS ids for four tokens"""
+    return dict(PROC_X, eos=[7, first_raw[-1] ^ 1], suppress=sorted(set(first_raw)))
+
+
+def check_processed(side, lg, ids, raw, what):
+    """the scores `side` returned are transformers' processors on the twin's raw logits under the MODEL's history, bit for bit, and the
+    chosen ids their argmax (lowest index on ties) -> those scores"""
+    want = processed(side.model, raw)
+    side.same(lg.float().cpu(), want, f"{what}: processed scores against transformers' processors on the raw logits")
+    if side.gpu:
+        assert ids.cpu().tolist() == lowest_argmax(want).tolist(), (side.name, what, ids.tolist())
+    return want
+
+
+def _fed(i, ids, feds):
+    """the explicit ids of step i: the previous choice, every third step an id fed two steps before (repeated bigrams: the n-gram ban acts)"""
+    return ids.tolist() if i % 3 != 2 else list(feds[i - 2])
+
+
+def _proc_run(side, twin, e, mask, n, tag, feds=None):
+    """start + n steps on explicit ids on both sides, every op checked by `check_processed` -> (the fed ids, [(scores, ids) per op])"""
+    raw, _ = twin.start(e, mask, what=f"{tag} start (raw)")
+    lg, ids = side.start(e, mask, what=f"{tag} start")
+    check_processed(side, lg, ids, raw, f"{tag} start")
+    out, rec = [], [(lg, ids)]
+    for i in range(n):
+        fed = feds[i] if feds else _fed(i, ids, out)
+        out.append(fed)
+        raw, _ = twin.step(fed, what=f"{tag} step {i + 1} (raw)")
+        lg, ids = side.step(fed, what=f"{tag} step {i + 1}")
+        check_processed(side, lg, ids, raw, f"{tag} step {i + 1}")
+        rec.append((lg, ids))
+    return out, rec
+
+
+def script_g(side, twin, seed=1):
+    """processors on the straight path, through the model: start(B = 3) + 8 steps on explicit ids; the twin (processors off) returns the raw
+    logits, and the processed scores are transformers' processors on them with the model's history"""
+    e, mask = rows(side.ref, G_B, G_P, seed)
+    raw, first = twin.start(e, mask, what="raw start")
+    twin.agree(at_least=0)
+    side.set_processors(**proc_cfg(first.tolist()))
+    feds, rec = _proc_run(side, twin, e, mask, G_STEPS, "g")
+    if side.gpu:
+        assert all(int(a) != int(b) for a, b in zip(rec[0][1], first))       # fvhd_llm_start applies them: the first token changed
+    side.agree()
+    twin.agree()
+    side.set_processors()
+    return feds, rec
+
+
+H_P1 = 17
+
+
+def script_h(side, twin, seed=1):
+    """stale rows: start(B = 3) with processors + 4 steps, start(B = 1) + 2 steps, start(B = 3) again on the same prompt and fed ids: rows 1
+    and 2 - whose history and bitmap the B = 1 start did not reset - behave as rows with an empty history: the model's, and the bits of the
+    first run"""
+    e, mask = rows(side.ref, 3, G_P, seed)
+    e1, mask1 = one_row(side.ref, H_P1, seed + 1)
+    raw, first = twin.start(e, mask, what="raw start")
+    twin.agree(at_least=0)
+    side.set_processors(**proc_cfg(first.tolist()))
+    feds, rec = _proc_run(side, twin, e, mask, 4, "h B=3")
+    side.agree()
+    twin.agree()
+    old = [list(h) for h in side.model.hist]
+    _proc_run(side, twin, e1, mask1, 2, "h B=1")
+    side.agree(at_least=3)
+    twin.agree(at_least=3)
+    assert side.model.hist[1:] == old[1:]                          # (the model: rows 1, 2 still hold the first run's history here)
+    raw, _ = twin.start(e, mask, what="h again start (raw)")
+    lg, ids = side.start(e, mask, what="h again start")
+    check_processed(side, lg, ids, raw, "h again start")
+    side.same(lg, rec[0][0], "the second B = 3 start equals the first")
+    for i in range(4):
+        raw, _ = twin.step(feds[i], what=f"h again step {i + 1} (raw)")
+        lg, ids = side.step(feds[i], what=f"h again step {i + 1}")
+        check_processed(side, lg, ids, raw, f"h again step {i + 1}")
+        side.same(lg, rec[i + 1][0], f"step {i + 1} of the second B = 3 run equals the first run's")
+        # rows 1, 2 on the first run's history + this run's (the reset covering 1 row instead of B)
+        # rows 1, 2 with the first run's ids still in the bitmap (the reset covering 1 row instead of B): every id of this run is then
+        # recorded as a repeat and never penalised - the scores of a history that holds none of the repeated ids
+        h = side.model.hist
+        side.hist_sens("rows 1, 2: the first run's bitmap not reset", f"B=3 again, step {i + 1}",
+                       [h[0]] + [[t for t in h[r] if t not in old[r]] for r in (1, 2)])
+    side.agree()
+    twin.agree()
+    side.set_processors()
+
+
+I_B, I_P, I_SKIP = 2, 19, [1001, 2002]
+
+
+def script_i(side, twin, seed=1):
+    """on, off for one step, on: start(B = 2) with processors, 2 steps, one step with them off (raw logits: the twin's bits; nothing joins
+    the history), 4 steps with them on again: the scores are the processors on a history WITHOUT the skipped ids"""
+    e, mask = rows(side.ref, I_B, I_P, seed)
+    raw, first = twin.start(e, mask, what="raw start")
+    twin.agree(at_least=0)
+    cfg = proc_cfg(first.tolist())
+    side.set_processors(**cfg)
+    feds, rec = _proc_run(side, twin, e, mask, 2, "i")
+    side.set_processors()
+    raw, _ = twin.step(I_SKIP, what="i skipped step (raw)")
+    lg, ids = side.step(I_SKIP, what="i step with processors off")
+    side.same(lg, raw, "a step with processors off returns the raw logits")
+    assert all(s not in h for s, h in zip(I_SKIP, side.model.hist)) and [len(h) for h in side.model.hist[:I_B]] == [2, 2]
+    side.set_processors(**cfg)
+    for i in range(4):
+        fed = ids.tolist()
+        assert all(s != f for s, f in zip(I_SKIP, fed))           # (the skipped ids never come back by themselves)
+        raw, _ = twin.step(fed, what=f"i step {i + 4} (raw)")
+        lg, ids = side.step(fed, what=f"i step {i + 4}")
+        check_processed(side, lg, ids, raw, f"i step {i + 4}")
+        h = side.model.hist
+        side.hist_sens("the skipped ids present", f"step {i + 4}", [h[r][:2] + [I_SKIP[r]] + h[r][2:] for r in range(I_B)])
+    side.agree()
+    twin.agree()
+    side.set_processors()
+
+
+J_P, J_T = 23, 5
+J_SEED = 77
+
+
+def script_j(side, twin, seed=1, abi=None):
+    """refusals change nothing.  Both sides carry the same settings and run the same calls; `side` also tries what the settings refuse -
+    with processors: extend, rewind, verify, lookup_begin, cache_gather; with sampling: verify and the lookup calls - and its next steps
+    have the twin's bits, ids and draws.  abi(side, phase): the same tries through the C ABI (GPU test)"""
+    import cache_model as CM
+    e, mask = one_row(side.ref, J_P, seed)
+    c, cmask = one_row(side.ref, J_T, seed + 1, pads=1)
+    for phase in ("processors", "sampling"):
+        for s in (side, twin):
+            if phase == "processors":
+                s.set_processors(**PROC_J)
+            else:
+                s.set_processors()
+                s.set_sampling(True, seed=J_SEED, **SAMPLING)
+        lg, ids = side.start(e, mask, what=f"j {phase} start")
+        tlg, tids = twin.start(e, mask, what=f"j {phase} start (twin)")
+        fed = ids.tolist()
+        side.step(fed, what=f"j {phase} step 1")
+        twin.step(fed, what=f"j {phase} step 1 (twin)")
+        drafts = [1, 2, 3, 4]
+        if phase == "processors":
+            side.refused(CM.NO_CHUNK_IDS, lambda m: m.extend(c, cmask, [0]), lambda g: g.extend(c.to(g.device, torch.bfloat16), cmask.to(g.device)))
+            side.refused(CM.NOT_REWOUND, lambda m: m.rewind([J_P]), lambda g: g.rewind([J_P]))
+            side.refused(CM.NOT_MAINTAINED, lambda m: m.verify(drafts, drafts + [0]), lambda g: g.verify(torch.tensor(drafts, device=g.device)))
+            side.refused(CM.NOT_MAINTAINED, lambda m: m.lookup_begin(None, [], 4))
+            side.refused(CM.NOT_REORDERED, lambda m: m.gather([0, 0], 1), lambda g: g.cache_gather(torch.zeros(2, device=g.device, dtype=torch.long), 1))
+        else:
+            side.refused(CM.GREEDY_ONLY, lambda m: m.verify(drafts, drafts + [0]), lambda g: g.verify(torch.tensor(drafts, device=g.device)))
+            side.refused(CM.GREEDY_ONLY, lambda m: m.lookup_begin(None, [], 4))
+            side.refused(CM.GREEDY_ONLY, lambda m: m.lookup_step(5, 2, [0] * 5))
+        if abi:
+            abi(side, phase)
+        for i in range(3):                                       # the stored ids, then explicit ones: neither was touched
+            fed = None if i == 0 else ids.tolist()
+            lg, ids = side.step(fed, what=f"j {phase} step {i + 2}")
+            tlg, tids = twin.step(fed, what=f"j {phase} step {i + 2} (twin)")
+            side.same(lg, tlg, f"{phase}: step {i + 2} behind the refusals equals the twin that never tried")
+            if side.gpu:
+                assert ids.tolist() == tids.tolist(), (phase, i, ids.tolist(), tids.tolist())
+        if phase == "processors":
+            side.agree(at_least=4)
+            twin.agree(at_least=4)
+    for s in (side, twin):
+        s.set_sampling(False)
+
+
+K_B, K_P, K_SEED = 2, 21, 4242
+
+
+def script_k(side, seed=1, draw_check=None):
+    """the draw under moved state.  (1) sampling, start(B = 2) + 5 steps on explicit ids; rewind to the prompt + 1; the same steps with
+    the same seed give the same ids and bits.  (2) start(B = 1), fork 1 -> 3, one step on explicit ids: draw_check(side, logits, ids)
+    holds the sampler op against row r's id with the model's (seed, r, n).  The ids are draws: no `agree`; every op's logits are compared"""
+    e, mask = rows(side.ref, K_B, K_P, seed)
+    side.set_sampling(True, seed=K_SEED, **SAMPLING)
+    lg, ids = side.start(e, mask, what="k start")
+    assert side.model.drawn == [(r, K_P) for r in range(K_B)]
+    feds, rec = [], []
+    for i in range(5):
+        feds.append(ids.tolist())
+        lg, ids = side.step(feds[-1], what=f"k step {i + 1}")
+        rec.append((lg, ids))
+    side.rewind([K_P + 1] * K_B)
+    for i in range(1, 5):
+        lg, ids = side.step(feds[i], what=f"k step {i + 1} behind the rewind")
+        assert side.model.drawn == [(r, K_P + i + 1) for r in range(K_B)]
+        side.same(lg, rec[i][0], f"step {i + 1} behind the rewind")
+        if side.gpu:
+            assert ids.tolist() == rec[i][1].tolist(), ("the same seed and length draw the same ids", i, ids.tolist(), rec[i][1].tolist())
+    e1, mask1 = one_row(side.ref, K_P, seed + 1)
+    side.start(e1, mask1, what="k start B=1")
+    side.step(None, what="k step B=1")
+    side.gather([0, 0, 0], 1)
+    lg, ids = side.step([17, 17, 17], what="k step behind the fork 1 -> 3")
+    n = K_P + 2
+    assert side.model.drawn == [(r, n) for r in range(3)] and side.model.draw_key(1, add=0) == (K_SEED, 1, n)
+    side.same(lg[1], lg[0], "forked rows on one id: equal logits")
+    side.same(lg[2], lg[0], "forked rows on one id: equal logits")
+    if draw_check:
+        draw_check(side, lg, ids)
+    side.set_sampling(False)
+
+
+L_B, L_P, L_T = 2, 19, 5
+
+
+def script_l(side, twin, seed=1, lp=None, proc=False):
+    """log-probability provenance.  `side` keeps its logits in the context's buffer (set_logprobs(1), calls without a logits_out); the twin
+    returns them.  lp(side, logits, ids, passed) (GPU test): fvhd_llm_logprobs for n in {0, 5, 16} against the fp64 reference on `logits`.
+    Accepted after start, decode, extend; refused after a call that wrote a logits_out (passing that buffer is accepted, same numbers),
+    after verify, a lookup step, and behind rewind / gather until a step on explicit ids.  proc: the same with processors on (no extend,
+    verify, rewind, gather: they are refused themselves) - the numbers are those of the processed scores"""
+    import cache_model as CM
+    lp = lp or (lambda *a: None)
+    e, mask = rows(side.ref, L_B, L_P, seed)
+    c, cmask = rows(side.ref, L_B, L_T, seed + 1)
+    side.set_logprobs(True)
+    if proc:
+        for s in (side, twin):
+            s.set_processors(**PROC_J)
+
+    def kept(op, *a, what):
+        """the op on both sides, `side` without a logits_out -> accepted, checked on the twin's logits"""
+        tlg, tids = getattr(twin, op)(*a, what=what + " (twin)")
+        _, ids = getattr(side, op)(*a, what=what, given=False, raw=tlg)
+        if side.gpu:
+            assert ids.tolist() == tids.tolist()
+        assert side.model.logprobs()
+        lp(side, tlg, ids, None)
+        return ids
+
+    def given(op, *a, what):
+        """... with a logits_out: logprobs(NULL) refused, that buffer accepted"""
+        getattr(twin, op)(*a, what=what + " (twin)")
+        lg, ids = getattr(side, op)(*a, what=what)
+        side.refused(CM.LP_NOT_LAST, lambda m: m.logprobs(), lambda g: g.logprobs(0, torch.zeros(g._run_batch, device=g.device)))
+        assert side.model.logprobs(logits_given=True)
+        lp(side, lg, ids, lg)
+        return ids
+
+    ids = kept("start", e, mask, what="l start")
+    ids = kept("step", ids.tolist(), what="l step 1")
+    ids = kept("step", None, what="l step 2")
+    if not proc:
+        ids = kept("extend", c, cmask, what="l extend")
+    ids = given("step", ids.tolist(), what="l step with a logits_out")
+    ids = kept("step", ids.tolist(), what="l step 4")
+    if not proc:
+        ids = given("extend", c, cmask, what="l extend with a logits_out")
+    given("start", e, mask, what="l start with a logits_out")
+    side.agree()
+    twin.agree()
+    if not proc:
+        stale = "before the cache reorder / rewind"
+        tok = lambda g: g.logprobs(0, torch.zeros(g._run_batch, device=g.device))      # noqa: E731
+        e1, mask1 = one_row(side.ref, L_P, seed + 2)
+        ids = kept("start", e1, mask1, what="l start B=1")
+        ids = kept("step", None, what="l B=1 step 1")
+        side.verify([int(ids), 1, 2], what="l verify")
+        side.refused(CM.LP_NOT_LAST, lambda m: m.logprobs(), tok)
+        twin.verify([int(ids), 1, 2], what="l verify (twin)")
+        ids = kept("step", None, what="l step behind the verify")
+        side.rewind([L_P + 1])
+        twin.rewind([L_P + 1])
+        side.refused(stale, lambda m: m.logprobs(), tok)
+        ids = kept("step", [int(ids)], what="l step on explicit ids behind the rewind")
+        side.agree(at_least=0)                                   # (the rows change: the fork's steps are compared on their own)
+        twin.agree(at_least=0)
+        side.gather([0, 0], 1)
+        twin.gather([0, 0], 1)
+        side.refused(stale, lambda m: m.logprobs(), tok)
+        ids = kept("step", [5, 6], what="l step on explicit ids behind the fork")
+        side.agree(at_least=0)
+        twin.agree(at_least=0)
+    side.set_logprobs(False)
+    for s in (side, twin):
+        s.set_processors()
+
+
+M_B, M_P, M_S, M_T = 2, 21, 31337, 271828
+
+
+def script_m(twin, seed=1):
+    """the eager pass of test m: start and one step under (processors X, seed s), one more under (Y, t) -> (prompt, mask, fed ids of the two
+    steps, their (scores, ids))"""
+    e, mask = rows(twin.ref, M_B, M_P, seed)
+    twin.set_processors(**PROC_J)
+    twin.set_sampling(True, seed=M_S, **SAMPLING)
+    _, ids = twin.start(e, mask, what="m start (twin)")
+    fed1 = ids.tolist()
+    r1 = twin.step(fed1, what="m eager step under (X, s)")
+    twin.set_processors(**PROC_Y)
+    twin.set_sampling(True, seed=M_T, **SAMPLING)
+    fed2 = r1[1].tolist()
+    r2 = twin.step(fed2, what="m eager step under (Y, t)")
+    twin.set_processors()
+    twin.set_sampling(False)
+    return e, mask, fed1, r1, fed2, r2
+
+
+@functools.lru_cache(maxsize=None)
+def stand_in(name, fmt="bf16", device="cpu", layers=2):
+    """(the fp32 oracle of) `llm_testlib.models(name)` whose matrices hold bf16 / dequantised e4m3 / dequantised MXFP4 values -> ref, or
+    (m16, ref) on a GPU device"""
+    from llm_testlib import models
+    m16, ref = models(name, seed=1, quantised=fmt == "e4m3", layers=layers, device=device)
+    if fmt == "mxfp4":
+        from ml_fastvlm_amd import dequantize_blocks_mxfp4, quantize_blocks_mxfp4
+        emb = m16.get_input_embeddings().weight
+        with torch.no_grad():
+            for p in m16.parameters():
+                if p.dim() == 2 and (p is not emb or m16.config.tie_word_embeddings):
+                    p.copy_(dequantize_blocks_mxfp4(*quantize_blocks_mxfp4(p)))
+        ref.load_state_dict({k: v.float() for k, v in m16.state_dict().items()})
+    return ref if device == "cpu" else (m16, ref)
+
+
+# the settings scripts: key -> (script, batch, capacity); "lp" = script l with processors on.  Every one runs as
+# run_settings_script(key, side, twin, seed, **hooks)
+SETTINGS_SCRIPTS = {"g": (script_g, 3, 48), "h": (script_h, 3, 48), "i": (script_i, 2, 48), "j": (script_j, 2, 48), "k": (script_k, 3, 48),
+                    "l": (script_l, 2, 48), "lp": (script_l, 2, 48), "m": (script_m, 2, 48)}
+
+
+# seeds per (script, weight format): the first of 1, 2, ... at which, on the fp32 oracle alone (`study`), every `agree` of the script compares
+# what it asks for (at least 4 steps of every row with an oracle top-2 margin above DELTA).  k and m compare no greedy ids (their ids are
+# draws): seed 1.  The margins and the history sensitivities of h and i are in profiles/cache_sequences_sensitivity.md
+SETTINGS_SEEDS = {("g", "bf16"): 9, ("g", "e4m3"): 2, ("g", "mxfp4"): 8, ("h", "bf16"): 9, ("i", "bf16"): 1, ("j", "bf16"): 2, ("k", "bf16"): 1,
+                  ("k", "e4m3"): 1, ("k", "mxfp4"): 1, ("l", "bf16"): 1, ("lp", "bf16"): 2, ("m", "bf16"): 1}
+
+
+def run_settings_script(key, side, twin, seed, **hooks):
+    fn = SETTINGS_SCRIPTS[key][0]
+    if key == "k":
+        return fn(side, seed=seed, **hooks)
+    if key == "m":
+        return fn(twin, seed=seed)
+    if key == "lp":
+        return fn(side, twin, seed=seed, proc=True, **hooks)
+    return fn(side, twin, seed=seed, **hooks)
+
+
 # prompt seeds per (script, model, e4m3): chosen on the CPU with the fp32 oracle alone (`study` below, seeds 1, 2, ... in turn) - the first
 # at which `agree` compares at least 4 steps of every row in every segment, every mutation moves the oracle's logits by >= 3 budgets and,
 # where one exists among the first candidates, the oracle's smallest margin over the whole script exceeds DELTA (our run then follows the
@@ -454,6 +910,34 @@ SEEDS = {("a", "0.5B", False): 3, ("a", "7B", False): 3, ("a", "0.5B", True): 3,
 # script, batch, capacity
 SCRIPTS = {"a": (script_a, 1, 96), "b": (script_b, 1, 96), "c": (script_c, 3, 64), "d": (script_d, 1, 64), "e": (script_e, E_B, 72),
            "f": (script_f, F_B, 48)}
+
+
+def settings_study():
+    """scripts g - m on the oracle alone: the margins of their seeds and, for h and i, how many processed scores a wrong history moves"""
+    out = ["", "## Scripts g - m: the settings crossed with the cache calls (tests/test_gpu_cache_settings.py)", "",
+           "The same study for the settings scripts: both sides are the fp32 oracle.  The compared scores of g, h, i, j and l-with-processors are",
+           "the PROCESSED ones (transformers' processors on the oracle's logits under the model's history): `agree` compares the ids up to the first",
+           "processed top-2 margin <= DELTA.  k and m choose by sampling - their ids are draws, compared with the sampler op and a twin run, not by",
+           "`agree` - so only their logits margins are listed.", "",
+           "| script | weights | seed | compared ops | smallest margin over all ops and rows | steps agree compares per row (min over rows, per call) |", "|---|---|---|---|---|---|"]
+    sens = ["", "### What a wrong history moves (h, i)", "",
+            "The check of g - i is bit equality of whole rows, so ONE moved logit fails it; the table counts, per compared op, the logits (over the",
+            "run's rows) whose processed score has other bits under the wrong history, and the largest finite move.  h: rows 1 and 2 whose bitmap",
+            "still holds the first run's ids (every id of the second run that the first also fed is taken for a repeat and never penalised).",
+            "i: the ids of the step that ran with processors off present in the history.  Both scripts are kept only with seeds where the count is",
+            "non-zero at every compared op.", "", "| script | wrong history | measured at | logits moved | largest finite move |", "|---|---|---|---|---|"]
+    for (key, fmt), seed in SETTINGS_SEEDS.items():
+        ref = stand_in("0.5B", fmt)
+        _, batch, cap = SETTINGS_SCRIPTS[key]
+        side, twin = OracleSide(ref, batch, cap, name=key), OracleSide(ref, batch, cap, name=key + " twin")
+        run_settings_script(key, side, twin, seed)
+        who = twin if key == "m" else side
+        out.append(f"| {key} | {fmt} | {seed} | {len(who.margins)} | {min(who.margins):.3f} | {[min(n) for n in who.compared] or 'draws'} |")
+        for name, kind, at, moved, big in side.hist_table:
+            sens.append(f"| {name} | {kind} | {at} | {moved} | {big:.3f} |")
+            assert moved > 0, (key, at)
+        print(out[-1], flush=True)
+    return out + sens
 
 
 # ---- the CPU study: margins and sensitivity -------------------------------------------------------------------------------------------------
@@ -490,7 +974,7 @@ def study(out_path=None):
                 lines.append(f"| {key} | {label} | {kind} | {at} | {rel:.3e} | {rel / REL:.1f} |")
             margin_lines.append(f"| {key} | {label} | {SEEDS[(key, name, quantised)]} | {len(side.margins)} | {min(side.margins):.3f} | {[min(n) for n in side.compared]} |")
             print(lines[-1], margin_lines[-1], flush=True)
-    text = "\n".join(lines + margin_lines) + "\n"
+    text = "\n".join(lines + margin_lines + settings_study()) + "\n"
     if out_path:
         with open(out_path, "w") as f:
             f.write(text)

@@ -297,3 +297,212 @@ def test_rewind_and_gather_by_hand():
     assert m.pos[:2].tolist() == [4, 1]                          # transformers: the LAST column's position + 1
     with pytest.raises(AssertionError, match="valid slots"):
         m.flat(1)
+
+
+# ---- the settings: history, provenance of the kept logits, the draw's key, the refusals -----------------------------------------------------
+ALL_ON = dict(p=1.3, n=2, m=3, eos=[5, 9], suppress=[1, 40])
+
+
+def _orders():
+    """the orders of scripts g, h and i as (op, argument) lists: ("set", on) / ("start", B) / ("step", None)"""
+    g = [("set", True), ("start", 2)] + [("step", None)] * 6
+    h = [("set", True), ("start", 3)] + [("step", None)] * 4 + [("start", 1)] + [("step", None)] * 2 + [("start", 3)] + [("step", None)] * 4
+    i = [("set", True), ("start", 2)] + [("step", None)] * 2 + [("set", False), ("step", None), ("set", True)] + [("step", None)] * 4
+    return {"g": g, "h": h, "i": i}
+
+
+@pytest.mark.parametrize("order", ["g", "h", "i"])
+def test_history_equals_the_input_ids_of_a_plain_processor_loop(tiny, order):
+    """a plain incremental past_key_values loop on the tiny model that keeps its own `input_ids` the way generate(inputs_embeds=...) does
+    for its processors - empty at the first token, one fed token per step in which the processors ran - beside the model: transformers'
+    four processors on the loop's raw logits give the same scores from the model's history as from the loop's input_ids, at every op"""
+    from logits_testlib import hf_chain
+    table = tiny.get_input_embeddings().weight.detach()
+    m = CacheModel(3, 40, table)
+    inc, input_ids, on, skipped, compared = None, None, False, [], 0
+    gen = torch.Generator().manual_seed(11)
+    for op, arg in _orders()[order]:
+        if op == "set":
+            on = arg
+            m.set_processors(**ALL_ON) if on else m.set_processors()
+            continue
+        if op == "start":
+            B = arg
+            e, mask = _inputs(B, 6, 64, [0, 1, 2][:B], 20 + B)
+            inc = Incremental(tiny)
+            raw = inc.forward(e, mask, (mask.cumsum(-1) - 1).masked_fill(mask == 0, 0))[:, -1]
+            input_ids = torch.zeros(B, 0, dtype=torch.long)       # generate's input_ids under inputs_embeds: empty at the first token
+            stale = [list(h) for h in m.hist[B:]]
+            fed = None
+        else:
+            B = m.run_batch
+            fed = torch.randint(0, 8, (B,), generator=gen)         # few distinct ids: repeats and repeated bigrams happen
+            if not on:
+                fed = fed + 12                                    # the skipped step's ids occur nowhere else: their presence would show
+            raw = inc.forward(table[fed][:, None], torch.ones(B, 1, dtype=torch.long), m.pos[:B, None].clone())[:, -1]
+            if on:
+                input_ids = torch.cat([input_ids, fed[:, None]], 1)
+            else:
+                skipped.append(fed.tolist())
+        ids = raw.argmax(-1)
+        assert m.start(e, mask, ids) if op == "start" else m.step(fed, ids)
+        if op == "start":
+            assert m.hist[B:] == stale                            # a start empties the history of ITS rows only
+        hist = torch.tensor([m.hist[r] for r in range(B)], dtype=torch.long).reshape(B, -1)
+        assert torch.equal(hist, input_ids), (op, hist, input_ids)
+        if on:
+            want = hf_chain(input_ids, raw, **ALL_ON)
+            got = hf_chain(hist, raw, **ALL_ON)
+            assert torch.equal(got, want)
+            compared += not torch.equal(want, raw)
+    assert compared >= 6                                         # the processors did something at (nearly) every compared op
+    if order == "i":
+        assert len(skipped) == 1 and input_ids.shape[1] == 6     # 7 steps, one of them skipped: the skipped token is ABSENT
+        with_it = torch.tensor([m.hist[r][:2] + [skipped[0][r]] + m.hist[r][2:] for r in range(2)])
+        assert not torch.equal(hf_chain(with_it, raw, **ALL_ON), want)      # ... and its presence would have shown
+    if order == "h":
+        assert [len(h) for h in m.hist] == [4, 4, 4]
+
+
+def _snap(m):
+    return copy.deepcopy({k: v for k, v in vars(m).items() if k != "table"})
+
+
+def _same(a, b):
+    return all(torch.equal(a[k], b[k]) if isinstance(a[k], torch.Tensor) else a[k] == b[k] for k in a) and a.keys() == b.keys()
+
+
+def _refused(m, reason, call):
+    """the call raises Refused with the reason and changes nothing"""
+    before = _snap(m)
+    with pytest.raises(Refused, match=reason):
+        call()
+    assert _same(before, _snap(m)), reason
+
+
+def test_settings_refusals_by_hand():
+    import cache_model as CM
+    table = torch.zeros(16, 4)
+    x = torch.zeros(1, 4, 4)
+
+    def fresh(proc=False, sampling=False, lp=False):
+        m = CacheModel(3, 24, table)
+        if proc:
+            m.set_processors(p=1.3)
+        m.set_sampling(sampling, seed=7)
+        m.set_logprobs(lp)
+        m.start(x, None, [1])
+        return m
+
+    # processors on: extend / rewind / gather / verify / the lookup calls
+    m = fresh(proc=True)
+    m.step(None, [2])
+    assert m.hist[0] == [1] and m.hist_started
+    _refused(m, CM.NO_CHUNK_IDS, lambda: m.extend(x, None, [3]))
+    _refused(m, CM.NOT_REWOUND, lambda: m.rewind([3]))
+    _refused(m, CM.NOT_REORDERED, lambda: m.gather([0, 0], 1))
+    _refused(m, CM.NOT_MAINTAINED, lambda: m.verify([1, 2], [1, 2, 3]))
+    _refused(m, CM.NOT_MAINTAINED, lambda: m.lookup_begin(None, [], 4))
+    _refused(m, CM.NOT_MAINTAINED, lambda: m.lookup_step(3, 2, [1, 2, 3]))
+    assert m.step(None, [4]) and m.hist[0] == [1, 2]             # and the next step goes on as if nothing had been tried
+    # any ONE processor is "on"; all-off values are off; min_new_tokens without EOS ids is off
+    for kw in (dict(n=2), dict(m=2, eos=[3]), dict(suppress=[4])):
+        m = fresh()
+        m.set_processors(**kw)
+        _refused(m, CM.NOT_REWOUND, lambda: m.rewind([3]))
+    m = fresh()
+    m.set_processors(m=2)
+    assert m.proc is None and m.rewind([3])
+    # sampling on: verify and the lookup calls; the cache calls run
+    m = fresh(sampling=True)
+    _refused(m, CM.GREEDY_ONLY, lambda: m.verify([1, 2], [1, 2, 3]))
+    _refused(m, CM.GREEDY_ONLY, lambda: m.lookup_begin(None, [], 4))
+    _refused(m, CM.GREEDY_ONLY, lambda: m.lookup_step(3, 2, [1, 2, 3]))
+    assert m.extend(x, None, [3]) and m.rewind([5]) and m.gather([0, 0], 1)
+    # sampling AND processors: the verify step names sampling first, as the library does
+    m = fresh(proc=True, sampling=True)
+    _refused(m, CM.GREEDY_ONLY, lambda: m.verify([1, 2], [1, 2, 3]))
+    # a step with processors on after a start without them
+    m = fresh()
+    m.set_processors(p=1.3)
+    _refused(m, CM.NO_HISTORY, lambda: m.step(None, [2]))
+    _refused(m, CM.NO_HISTORY, lambda: m.step([5], [2]))
+    assert not m.may_step_none()
+    m.set_processors()
+    assert m.may_step_none() and m.step(None, [2]) and m.hist[0] == []
+    # started WITH them, switched off for a step, on again: accepted, and the step in between appended nothing
+    m = fresh(proc=True)
+    m.step(None, [2])
+    m.set_processors()
+    m.step(None, [3])
+    m.set_processors(p=1.3)
+    m.step(None, [4])
+    assert m.hist[0] == [1, 3] and m.length == 7
+    # logprobs(NULL): the setting off; the buffer not the last call's; the ids stale; the scratch
+    m = fresh()
+    _refused(m, CM.LP_OFF, lambda: m.logprobs())
+    _refused(m, CM.LP_NO_SCRATCH, lambda: m.logprobs(logits_given=True))        # the setting was never on for this cache
+    m.set_logprobs(True)
+    assert m.lp_where == "start" and m.logprobs()                # a start always leaves its logits, whatever the setting was
+    m.set_logprobs(False)
+    m.step(None, [2])                                            # a plain greedy step keeps none
+    m.set_logprobs(True)
+    _refused(m, CM.LP_NOT_LAST, lambda: m.logprobs())
+    assert m.logprobs(logits_given=True)
+    m = fresh(lp=True)
+    for where, call in (("start", None), ("decode", lambda g: m.step(None, [2], logits_given=g)), ("extend", lambda g: m.extend(x, None, [3], logits_given=g))):
+        if call:
+            call(False)
+        assert m.lp_where == where and m.logprobs() and m.logprobs(logits_given=True)
+        if call:
+            call(True)                                           # the same call writing a caller's logits_out
+            _refused(m, CM.LP_NOT_LAST, lambda: m.logprobs())
+            assert m.logprobs(logits_given=True)
+    m.start(x, None, [1], logits_given=True)
+    _refused(m, CM.LP_NOT_LAST, lambda: m.logprobs())
+    m.step(None, [2])
+    assert m.verify([1, 2], [1, 2, 3]) == 3
+    _refused(m, CM.LP_NOT_LAST, lambda: m.logprobs())
+    m.step(None, [2])
+    m.lookup_begin(None, [], 6)
+    assert m.logprobs()                                          # lookup_begin enqueues no step
+    assert m.lookup_step(3, 2, [1, 2, 3]) >= 1
+    _refused(m, CM.LP_NOT_LAST, lambda: m.logprobs())
+    m.step(None, [2])
+    m.rewind([4])
+    _refused(m, "before the cache reorder / rewind", lambda: m.logprobs())
+    _refused(m, "before the cache reorder / rewind", lambda: m.logprobs(logits_given=True))
+    m.step([5], [2])
+    assert m.logprobs()
+    m.gather([0, 0], 1)
+    _refused(m, "before the cache reorder / rewind", lambda: m.logprobs())
+    m.step([5, 6], [2, 2])
+    assert m.logprobs() and m.run_batch == 2
+    # a step under sampling or processors keeps its logits without the log-probability setting; reading them still needs it
+    m = fresh(sampling=True)
+    m.step(None, [2])
+    assert m.lp_where == "decode"
+    _refused(m, CM.LP_OFF, lambda: m.logprobs())
+
+
+def test_the_draw_is_keyed_on_the_row_and_the_moved_length():
+    table = torch.zeros(16, 4)
+    m = CacheModel(3, 24, table)
+    m.set_sampling(True, seed=99)
+    m.start(torch.zeros(1, 5, 4), None, [1])
+    assert m.drawn == [(0, 5)]                                   # the prompt length
+    m.step(None, [2])
+    m.step(None, [2])
+    assert m.drawn == [(0, 7)] and m.draw_key(0) == (99, 0, 8)
+    m.rewind([5])
+    assert m.draw_key(0) == (99, 0, 6)                           # the same step again draws the same number
+    m.step([1], [2])
+    assert m.drawn == [(0, 6)]
+    m.gather([0, 0, 0], 1)
+    m.step([1, 1, 1], [2, 2, 2])
+    assert m.drawn == [(0, 7), (1, 7), (2, 7)]                   # every forked row its own stream, n the moved length
+    m.extend(torch.zeros(3, 4, 4), None, [2, 2, 2])
+    assert m.drawn == [(r, 11) for r in range(3)]                # an extend: the new length
+    m.set_sampling(False)
+    m.step(None, [2, 2, 2])
+    assert m.drawn is None

@@ -57,6 +57,21 @@ def test_explicit_ids_pass_the_rule():
     assert gen._ids_stale                                        # a refused call clears nothing
 
 
+def test_with_processors_set_the_generator_refuses_every_call_that_moves_the_cache():
+    """rewind, extend, verify and - the history is not reordered either - cache_gather, each before any device is looked at"""
+    gen = _bare_generator(stale=False)
+    gen._processors = dict(repetition_penalty=1.3)
+    with pytest.raises(ValueError, match="their token history is not reordered"):
+        gen.cache_gather(torch.zeros(3, dtype=torch.long), 1)
+    with pytest.raises(ValueError, match="their token history is not rewound"):
+        gen.rewind([5])
+    with pytest.raises(ValueError, match="their token history has no ids for an embedded chunk"):
+        gen.extend(torch.zeros(1, 2, 8))
+    with pytest.raises(ValueError, match="does not maintain their token history"):
+        gen.verify(torch.zeros(4, dtype=torch.long))
+    assert gen._run_batch == 1 and not gen._ids_stale            # a refused call changes nothing
+
+
 def test_a_generator_without_the_flag_is_not_stale():
     gen = _bare_generator(stale=False)
     del gen._ids_stale                                           # an object made before the flag existed
