@@ -75,7 +75,10 @@ typedef void* fvhd_stream_t; /* hipStream_t */
  * _qkv_w4 / _lm_argmax_w4, fvhd_op_w4_unpack; bf16 and e4m3 contexts enqueue what they did, bit for bit (a caller detects the symbols, as
  * ml_fastvlm_amd/_lib.py w4_lib() does).  Also added under 510 (new symbols only, the number stays): log-probabilities of the chosen tokens -
  * fvhd_dec_logprobs_scratch_bytes, fvhd_op_dec_logprobs, fvhd_llm_set_logprobs, fvhd_llm_logprobs; with the setting off (the default) every
- * existing call enqueues what it did and fvhd_llm_cache_reserve allocates what it did (_lib.py logprobs_lib() detects the symbols). */
+ * existing call enqueues what it did and fvhd_llm_cache_reserve allocates what it did (_lib.py logprobs_lib() detects the symbols).  Also added
+ * under 510 (new symbols only, the number stays): constrained decoding - fvhd_llm_set_constraint, fvhd_llm_constraint_state,
+ * fvhd_op_dec_constrain, fvhd_dec_constrain_slice; with no constraint set (the default) every call enqueues what it did and allocates what it
+ * did (_lib.py constraint_lib() detects the symbols). */
 #define FVHD_VERSION 510
 int fvhd_version(void);
 const char* fvhd_last_error(void);
@@ -897,6 +900,59 @@ int fvhd_op_dec_logprobs(fvhd_stream_t stream, const float* logits, const int64_
 int fvhd_llm_set_logprobs(fvhd_llm* ctx, int on);
 int fvhd_llm_logprobs(fvhd_llm* ctx, const float* logits, int top_n, float* token_logprob_out, int64_t* top_ids_out, float* top_logprobs_out,
                       fvhd_stream_t stream);
+
+/* ---- LLM constrained decoding: a token-level automaton masks the logits inside the step (added under 510) -----------------------------------
+ * The caller hands over an automaton over token ids as CSR data: state s owns the edges offsets[s] .. offsets[s + 1]; tokens[e] (int32,
+ * strictly ascending inside a state) is an id the state allows and targets[e] the state it leads to, or -1 = FREE: a FREE row is
+ * unconstrained from then on and never leaves FREE.  Every state has at least one edge.  Limits: 16 777 216 states, 268 435 456 edges.
+ * The step keeps one int32 state and one int32 flag word per row on the device.  Per step (llm_constrain.hip):
+ *   advance  (decode steps only, not the first choice behind fvhd_llm_start / _extend) the token FED to the step - token_ids[b], or the id the
+ *            previous call chose when token_ids is NULL: the ids the step embeds and the processors append - is looked up in the sorted edges
+ *            of the row's state.  Found: the row takes the edge's target.  Not found: the row goes to FREE and flag bit 0 ("violated") is
+ *            set; only ids the caller fed itself can do that.  A FREE row stays FREE.
+ *   mask     every id of a non-FREE row that is no edge of its (new) state becomes -inf.  Allowed entries are neither read nor written: they
+ *            keep the lm_head's (or the processors') bits, -0.0 included.  A FREE row is not touched.
+ * The advance is a small launch of its own in front of the mask launch (grid = slices of fvhd_dec_constrain_slice() ids x rows), so no
+ * workgroup can read a state another has replaced; every banned logit is written by one lane with a constant, the new state depends on the
+ * old state and the fed id only: the same bits eager or replayed.  A launch that finds the error word set writes nothing, like the steps.
+ * This is transformers' PrefixConstrainedLogitsProcessor with the host callback replaced by the tables.  Its place in
+ * `_get_logits_processor` is behind repetition penalty, n-gram and min-new-tokens and in front of suppress; bans commute and -inf survives
+ * the penalty, so the launches go behind the processors' launch and give the same values.
+ *
+ * fvhd_llm_set_constraint: n_states = 0 switches the feature off (the other arguments are ignored).  Otherwise host_offsets int32
+ * [n_states + 1], host_tokens / host_targets int32 [n_edges], host_start_states int32 [n_start] with n_start = 1 (every row) or the batch of
+ * fvhd_llm_cache_reserve; a start state of -1 leaves the row unconstrained.  Validated, each failure with a message naming the state or
+ * edge: offsets start at 0, are monotone and end at n_edges; every token in [0, vocab); every target in [-1, n_states); tokens strictly
+ * ascending inside a state; no state without an edge; the limits above.  The tables are copied into device memory the context owns.  It
+ * synchronises the device and is refused while a stream is being captured.  A captured step keeps the tables it was captured with: tables
+ * that a capturing stream has recorded are retired (kept until fvhd_llm_destroy) when OTHER tables are set, never overwritten; switching
+ * off keeps the tables, and setting the same tables again uploads nothing.
+ * With a constraint on:
+ *   fvhd_llm_start / fvhd_llm_extend reset the rows' states to their start states, clear the flags and mask the logits their choice is made
+ *     from - behind the processors' launch where those are on, before the argmax or the sampler.  (The start states travel by value in the
+ *     launch: a captured start keeps them.)
+ *   fvhd_llm_decode advances and masks between the lm_head and the choice.  Greedy: the fused (max, index) pairs saw raw logits, so the pairs
+ *     come again from the masked logits, as under the processors - once when both are on.  Sampling: the launches go before the sampler.
+ *   The steps keep their logits (the context's buffer when logits_out is NULL); logits_out holds the processed scores, so
+ *     fvhd_llm_logprobs renormalises over the allowed set: banned ids have log-probability -inf and rank last.
+ *   Refused, each with a message: fvhd_llm_cache_rewind, fvhd_llm_cache_gather, fvhd_llm_beam_topk, fvhd_llm_verify, fvhd_llm_lookup_begin /
+ *     _step (none of them carries the rows' states); fvhd_llm_decode behind a start / extend that ran without the constraint (the rows have
+ *     no states).  fvhd_llm_score is unaffected.
+ *   A row whose processors and constraint together ban every id is undefined (the sampler's rule, "LLM sampling").
+ * Off (the default): no launch, no buffer traffic, no allocation: every call enqueues what it did.
+ * fvhd_llm_constraint_state synchronises and copies, for the first `rows` rows of the started batch, the state after the last FED token - not
+ * advanced by the last chosen one - and the flag words (either output may be NULL); refused while no constraint is on or no sequence was
+ * started under it.
+ * fvhd_op_dec_constrain is the launches on their own, every pointer on the device: logits fp32 [B][V] with row stride V (aligned to 4 bytes;
+ * rows need not be 16-byte aligned), V >= 1, 1 <= B <= 64, tables as above (trusted: validate on the host), states / flags int32 [B], fed_ids
+ * int64 [B] or NULL = no advance.  It writes at most 4 V bytes per constrained row, reads only the edges of the rows' current states and
+ * never reads the logits. */
+int fvhd_dec_constrain_slice(void);
+int fvhd_op_dec_constrain(fvhd_stream_t stream, float* logits, int B, int V, const int32_t* offsets, const int32_t* tokens, const int32_t* targets,
+                          int n_states, int32_t* states, int32_t* flags, const int64_t* fed_ids);
+int fvhd_llm_set_constraint(fvhd_llm* ctx, const int32_t* host_offsets, int n_states, const int32_t* host_tokens, const int32_t* host_targets,
+                            int n_edges, const int32_t* host_start_states, int n_start);
+int fvhd_llm_constraint_state(fvhd_llm* ctx, int32_t* host_states_out, int32_t* host_flags_out, int rows);
 
 #ifdef __cplusplus
 }

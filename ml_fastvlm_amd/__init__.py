@@ -8,11 +8,13 @@ Public surface (mirrors `llava.model.multimodal_encoder` / `multimodal_projector
     KV cache by each turn's tokens instead of prefilling the dialogue again), `process_reference` (the decode step's logits
     processors restated in plain torch), `score` (the log-likelihood of given tokens, `forward(labels=...)` per sequence, with lm_head and the
     log-softmax fused in one kernel; `GenerationSession.score` ranks candidate answers behind one prefilled image), `GenerationLogprobs` (what `generate(..., logprobs=n)`
-    returns beside the tokens: the log-probability of every generated token and the n most likely tokens of its step), and
+    returns beside the tokens: the log-probability of every generated token and the n most likely tokens of its step), `TokenAutomaton` (constrained decoding: `generate(..., constraint=...)` answers in a given
+    form - the allowed token sequences as an automaton the decode step follows on the device), and
     `distributed` for the one-process-per-GPU data-parallel path.
 """
 from .beam import BeamSearchState  # noqa: F401
 from .builder import GenerationSession, beam_generate, build_vision_projector, build_vision_tower, encode_images, generate, install_into_llava, library_projector, project, score  # noqa: F401
+from .constraints import TokenAutomaton  # noqa: F401
 from .logits_processors import process_reference  # noqa: F401
 from .mobileclip_encoder import MobileCLIPVisionTower, load_model_config  # noqa: F401
 from .qwen2_decode import GenerationLogprobs  # noqa: F401
@@ -21,4 +23,4 @@ from .qwen2_prefill import dequantize_blocks_mxfp4, quantize_blocks_mxfp4  # noq
 
 __all__ = ["MobileCLIPVisionTower", "build_vision_tower", "build_vision_projector", "encode_images", "project",
            "library_projector", "install_into_llava", "load_model_config", "generate", "quantize_rows_e4m3", "quantize_blocks_mxfp4", "dequantize_blocks_mxfp4", "beam_generate", "BeamSearchState",
-           "process_reference", "GenerationSession", "score", "GenerationLogprobs"]
+           "process_reference", "GenerationSession", "score", "GenerationLogprobs", "TokenAutomaton"]

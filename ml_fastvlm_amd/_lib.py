@@ -197,6 +197,13 @@ def _declare(lib) -> None:
             "fvhd_llm_set_logprobs": (ci, [vp, ci]),
             "fvhd_llm_logprobs": (ci, [vp, vp, ci, vp, vp, vp, vp]),
         })
+    if hasattr(lib, "fvhd_op_dec_constrain"):      # added under 510: a 510 library built before them loads without; constraint_lib() then names the rebuild
+        sig.update({
+            "fvhd_dec_constrain_slice": (ci, []),
+            "fvhd_op_dec_constrain": (ci, [vp, vp, ci, ci, vp, vp, vp, ci, vp, vp, vp]),
+            "fvhd_llm_set_constraint": (ci, [vp, vp, ci, vp, vp, ci, vp, ci]),
+            "fvhd_llm_constraint_state": (ci, [vp, vp, vp, ci]),
+        })
     del fp, cl
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)     # AttributeError here = the .so does not export what fvhd.h declares
@@ -330,6 +337,17 @@ def logprobs_lib():
     if not hasattr(lib, "fvhd_op_dec_logprobs"):
         raise FvhdError(f"{LIB_PATH} (ABI version {lib.fvhd_version()}) was built before the log-probabilities of generated tokens "
                         "(fvhd_llm_set_logprobs, fvhd_llm_logprobs, fvhd_op_dec_logprobs, ...) - rebuild the library (`python -m ml_fastvlm_amd.build`)")
+    return lib
+
+
+def constraint_lib():
+    """load(), for constrained decoding (fvhd_llm_set_constraint, fvhd_llm_constraint_state, fvhd_op_dec_constrain, ...): the entry points
+    were added under FVHD_VERSION 510, so a library built before them reports the same number and loads; this says so instead of an
+    AttributeError."""
+    lib = load()
+    if not hasattr(lib, "fvhd_op_dec_constrain"):
+        raise FvhdError(f"{LIB_PATH} (ABI version {lib.fvhd_version()}) was built before constrained decoding (fvhd_llm_set_constraint, "
+                        "fvhd_llm_constraint_state, fvhd_op_dec_constrain, ...) - rebuild the library (`python -m ml_fastvlm_amd.build`)")
     return lib
 
 

@@ -93,7 +93,7 @@ def encode_images(vision_tower, mm_projector, images):
 
 
 def install_into_llava(splice: bool = False, prefill: bool = False, prefill_any_dtype: bool = False, generate: bool = False,
-                       llm_weights: str = "bf16", beam_search: bool = False, logits_processors: bool = False) -> None:
+                       llm_weights: str = "bf16", beam_search: bool = False, logits_processors: bool = False, constraints: bool = False) -> None:
     """Make an unmodified `llava` package (the reference) build and call the MI355X tower; splice=True also routes
     `prepare_inputs_labels_for_multimodal` through the GPU splice (needs the embeddings on a HIP device); prefill=True also runs the
     PREFILL step of `LlavaQwen2ForCausalLM.forward` (`llava_qwen.py:92-103`: the first forward of `generate`, on `inputs_embeds`
@@ -108,6 +108,10 @@ def install_into_llava(splice: bool = False, prefill: bool = False, prefill_any_
     keeps falling back, as before.
     logits_processors=True (with generate=True) lets it take the library for `repetition_penalty`, `no_repeat_ngram_size`, `min_new_tokens`
     and `suppress_tokens` too (num_beams = 1; `Qwen2Generator.set_logits_processors`); without it those settings keep falling back.
+    constraints=True (with generate=True): the patched generate pops `constraint=` (a `ml_fastvlm_amd.constraints.TokenAutomaton`) and
+    `constraint_start=` and runs them on the library for num_beams = 1 (`Qwen2Generator.set_constraint`); a call that must fall back, or
+    asks for beam search, raises instead of dropping the constraint.  Without the flag nothing about the patched call changes, and
+    transformers' own `prefix_allowed_tokens_fn` keeps falling back either way.
     llm_weights: "bf16" (the default), "fp8_e4m3" or "mxfp4" - the storage of the LLM's packed matrices in the library's prefill / decode contexts
     (`Qwen2Prefill.from_hf(weights=...)`), recorded on `LlavaQwen2ForCausalLM` for `prefill_context` to read."""
     from ._lib import weight_format_code
@@ -143,6 +147,8 @@ def install_into_llava(splice: bool = False, prefill: bool = False, prefill_any_
         import llava.model.language_model.llava_qwen as lq
         cur = lq.LlavaQwen2ForCausalLM.generate
         extra = dict(logits_processors=True) if logits_processors else {}
+        if constraints:
+            extra["constraints"] = True
         lq.LlavaQwen2ForCausalLM.generate = _make_library_generate(getattr(cur, "_fvhd_orig", cur), beam_search=beam_search, **extra)
 
 
@@ -280,7 +286,7 @@ def generator_context(model, batch: int, capacity: int, weights=None):
 @torch.no_grad()
 def generate(model, input_ids, images=None, image_sizes=None, attention_mask=None, max_new_tokens: int = 256, eos_token_id=None,
              pad_token_id=None, do_sample: bool = False, num_beams: int = 1, prompt_lookup_num_tokens=None,
-             max_matching_ngram_size: int = 2, logprobs=None, **kwargs):
+             max_matching_ngram_size: int = 2, logprobs=None, constraint=None, constraint_start=None, **kwargs):
     """`LlavaQwen2ForCausalLM.generate` (`llava_qwen.py:106-143`) with greedy decoding on the library: the multimodal splice
     (`model.prepare_inputs_labels_for_multimodal`) or the token embedding, then the prefill and every decode step on the hand-written
     Qwen2 kernels (`Qwen2Generator.greedy`).  Returns the new tokens [B, n] as transformers' generate(inputs_embeds=...) does.  Greedy only:
@@ -288,9 +294,16 @@ def generate(model, input_ids, images=None, image_sizes=None, attention_mask=Non
     prompt_lookup_num_tokens=K (1 .. 15, one prompt per call): prompt-lookup decoding (`Qwen2Generator.lookup_greedy`) - the same tokens, K
     drafts from n-gram matches (n <= max_matching_ngram_size) in `input_ids` and the generated tokens verified per step.
     logprobs=n (0 .. 16): -> (tokens, `GenerationLogprobs`): every generated token's log-probability and the n most likely tokens of its step
-    (`Qwen2Generator.greedy`); not with prompt_lookup_num_tokens."""
+    (`Qwen2Generator.greedy`); not with prompt_lookup_num_tokens.
+    constraint: a `ml_fastvlm_amd.constraints.TokenAutomaton` the new tokens of every row must follow, from constraint_start (None: state 0;
+    an int; one state per row, -1 = unconstrained) - `Qwen2Generator.greedy(constraint=...)`; not with prompt_lookup_num_tokens."""
     from .qwen2_decode import normalize_logprobs
     logprobs = normalize_logprobs(logprobs)
+    if constraint is not None and prompt_lookup_num_tokens is not None:
+        raise ValueError("ml_fastvlm_amd.generate: a constraint is not implemented under prompt-lookup decoding (prompt_lookup_num_tokens) - a "
+                         "verify step does not advance the rows' automaton states")
+    if constraint is None and constraint_start is not None:
+        raise ValueError("ml_fastvlm_amd.generate: constraint_start is given without a constraint")
     if logprobs is not None and prompt_lookup_num_tokens is not None:
         raise ValueError("ml_fastvlm_amd.generate: logprobs is not implemented under prompt-lookup decoding (prompt_lookup_num_tokens) - a verify step "
                          "chooses several tokens per launch")
@@ -321,7 +334,7 @@ def generate(model, input_ids, images=None, image_sizes=None, attention_mask=Non
     if pad_token_id is None:
         pad_token_id = getattr(gc, "pad_token_id", None)
     return _generate_on_library(model, input_ids, images, image_sizes, attention_mask, None, max_new_tokens, eos_token_id, pad_token_id, lookup=lookup,
-                                logprobs=logprobs)
+                                logprobs=logprobs, constraint=constraint, constraint_start=constraint_start)
 
 
 @torch.no_grad()
@@ -347,13 +360,17 @@ def beam_generate(model, input_ids, images=None, image_sizes=None, attention_mas
 
 
 def _generate_on_library(model, input_ids, images, image_sizes, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id,
-                         sampling=None, beam=None, processors=None, lookup=None, logprobs=None):
+                         sampling=None, beam=None, processors=None, lookup=None, logprobs=None, constraint=None, constraint_start=None):
     """the body shared by `generate`, `beam_generate` and `_make_library_generate`: the multimodal splice (or the token embedding), then the
     prefill and every decode step on the library - `Qwen2Generator.greedy`, `.sample(**sampling)` or `.beam_search(**beam)`; processors:
     None or the logits-processor keywords of greedy / sample (repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens);
     logprobs: None or greedy's / sample's keyword (they then return (tokens, GenerationLogprobs)) - not for beam search or lookup decoding"""
     if logprobs is not None and (beam is not None or lookup is not None):
         raise ValueError("logprobs is implemented for greedy decoding and sampling only (beam search has return_scores)")
+    if constraint is not None and (beam is not None or lookup is not None):
+        raise ValueError("a constraint is implemented for greedy decoding and sampling only (num_beams = 1, no prompt lookup): beam search and "
+                         "the verify step do not carry the rows' automaton states")
+    con = dict(constraint=constraint, constraint_start=constraint_start) if constraint is not None else {}
     if images is not None:
         (input_ids, position_ids, attention_mask, _, inputs_embeds, _) = model.prepare_inputs_labels_for_multimodal(
             input_ids, position_ids, attention_mask, None, None, images, image_sizes=image_sizes)
@@ -372,9 +389,9 @@ def _generate_on_library(model, input_ids, images, image_sizes, attention_mask, 
     processors = processors or {}
     if sampling is None:
         return gen.greedy(inputs_embeds, attention_mask, position_ids, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id,
-                          pad_token_id=pad_token_id, logprobs=logprobs, **processors)
+                          pad_token_id=pad_token_id, logprobs=logprobs, **processors, **con)
     return gen.sample(inputs_embeds, attention_mask, position_ids, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id,
-                      pad_token_id=pad_token_id, logprobs=logprobs, **sampling, **processors)
+                      pad_token_id=pad_token_id, logprobs=logprobs, **sampling, **processors, **con)
 
 
 # ---- multi-turn generation on one KV cache ------------------------------------------------------------------------------------------------
@@ -543,9 +560,11 @@ class GenerationSession:
     @torch.no_grad()
     def generate(self, input_ids, images=None, image_sizes=None, attention_mask=None, max_new_tokens: int = 256, eos_token_id=None,
                  pad_token_id=None, do_sample: bool = False, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
-                 logprobs=None):
+                 logprobs=None, constraint=None, constraint_start=None):
         """-> the new tokens of this turn [B, n] (`Qwen2Generator.greedy` / `.sample`'s return contract); with logprobs=n (0 .. 16)
-        (tokens, `GenerationLogprobs`) of this turn.  First call: `input_ids` is the
+        (tokens, `GenerationLogprobs`) of this turn.  constraint (a `ml_fastvlm_amd.constraints.TokenAutomaton`, with constraint_start)
+        constrains THIS turn's answer only: every turn begins at its own start states, and the constraint is cleared before the cache is
+        rewound.  First call: `input_ids` is the
         whole prompt (with image placeholders when `images` is given).  Later calls: the turn's NEW ids [B, n] only, B = the session's
         rows; attention_mask marks the real tokens of rows of different lengths.  Images in a later turn need B = 1 or rows whose
         spliced lengths are equal (the splice pads to the right, the cache extends to the left)."""
@@ -580,6 +599,10 @@ class GenerationSession:
         T = embeds.shape[1]
         before = 0 if first else gen.length()
         kw = dict(max_new_tokens=max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id, continue_cache=not first, logprobs=logprobs)
+        if constraint is not None:
+            kw.update(constraint=constraint, constraint_start=constraint_start)
+        elif constraint_start is not None:
+            raise ValueError("GenerationSession.generate: constraint_start is given without a constraint")
         if do_sample:
             res = gen.sample(embeds, mask, position_ids, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, **kw)
         else:
@@ -709,7 +732,7 @@ def _batch_reason(batch: int):
     return f"batch {batch} > {MAX_DECODE_BATCH}" if batch > MAX_DECODE_BATCH else None
 
 
-def _make_library_generate(orig_generate, beam_search: bool = False, logits_processors: bool = False):
+def _make_library_generate(orig_generate, beam_search: bool = False, logits_processors: bool = False, constraints: bool = False):
     """`LlavaQwen2ForCausalLM.generate` (`llava_qwen.py:106-143`) on the library: the same argument handling (position_ids / attention_mask
     popped, inputs_embeds refused), the settings resolved as transformers resolves them (`_library_generate_settings`), then the
     multimodal splice and `Qwen2Generator.greedy` / `.sample` on `generator_context(model, ...)`.  It takes the library only for greedy or
@@ -721,10 +744,18 @@ def _make_library_generate(orig_generate, beam_search: bool = False, logits_proc
     beam search and dict output stay on the original generate.  logits_processors=True: repetition_penalty, no_repeat_ngram_size,
     min_new_tokens and suppress_tokens (num_beams = 1, within the library's limits) run on the library as well
     (`Qwen2Generator.set_logits_processors`); min_length, bad_words_ids, begin_suppress_tokens, sequence_bias and every other processor
-    keep falling back."""
+    keep falling back.  constraints=True: the call may carry `constraint=` (a `ml_fastvlm_amd.constraints.TokenAutomaton`) and
+    `constraint_start=`; they are popped and run on the library (`Qwen2Generator.set_constraint`, num_beams = 1).  The reference's generate
+    knows no such argument, so a constrained call that cannot run on the library raises with the reason instead of falling back; without
+    the flag the keywords are not looked at.  `prefix_allowed_tokens_fn` keeps falling back."""
     def generate(self, inputs=None, images=None, image_sizes=None, **kwargs):
         if "inputs_embeds" in kwargs:                            # as the reference (llava_qwen.py:120-121)
             raise NotImplementedError("`inputs_embeds` is not supported")
+        constraint = constraint_start = None
+        if constraints:
+            constraint, constraint_start = kwargs.pop("constraint", None), kwargs.pop("constraint_start", None)
+            if constraint is None and constraint_start is not None:
+                raise ValueError("generate: constraint_start is given without a constraint")
         settings, reason = _library_generate_settings(self, {k: v for k, v in kwargs.items() if k not in ("position_ids", "attention_mask")},
                                                       beam_search=beam_search, **(dict(processors=True) if logits_processors else {}))
         lm_w = self.lm_head.weight
@@ -733,6 +764,10 @@ def _make_library_generate(orig_generate, beam_search: bool = False, logits_proc
             settings, reason = None, _batch_reason(rows)
         if settings is not None and (lm_w.device.type != "cuda" or lm_w.dtype != torch.bfloat16):
             settings, reason = None, f"the model is {lm_w.dtype} on {lm_w.device} (the library decodes a bf16 model on a HIP device)"
+        if constraint is not None and (settings is None or settings["beam"]):
+            raise ValueError("generate(constraint=...): a constraint runs on the library only, with num_beams = 1 - " +
+                             (f"this call would stay on the reference ({reason})" if settings is None else
+                              "beam search does not carry the rows' automaton states"))
         if settings is None:
             warned = getattr(self, "_fvhd_generate_warned", frozenset())
             if reason not in warned:
@@ -743,7 +778,8 @@ def _make_library_generate(orig_generate, beam_search: bool = False, logits_proc
         with torch.no_grad():
             return _generate_on_library(self, inputs, images, image_sizes, kwargs.get("attention_mask"), kwargs.get("position_ids"),
                                         settings["max_new_tokens"], settings["eos_token_id"], settings["pad_token_id"], settings["sampling"],
-                                        settings["beam"], **(dict(processors=settings["processors"]) if settings.get("processors") else {}))
+                                        settings["beam"], **(dict(processors=settings["processors"]) if settings.get("processors") else {}),
+                                        **(dict(constraint=constraint, constraint_start=constraint_start) if constraint is not None else {}))
     generate._fvhd_generate = True
     generate._fvhd_orig = orig_generate
     return generate

@@ -119,4 +119,6 @@ int fvhd_launch_dec_logits_history(hipStream_t st, const int* tokens, int* hist,
 // llm_logprobs.hip (scratch: fvhd_dec_logprobs_scratch_bytes, its first 16 384 bytes zero before the first launch; status: NULL or the error word)
 int fvhd_launch_dec_logprobs(hipStream_t st, const float* logits, const int64_t* ids, int B, int V, int top_n, float* token_logprob, int64_t* top_ids,
                              float* top_logprobs, void* scratch, const int* status);
+// llm_constrain.hip (the advance / reset launch when the arguments ask for one, then the mask launch)
+int fvhd_launch_dec_constrain(hipStream_t st, const DecConstrainArgs* a);
 }

@@ -11,6 +11,7 @@
 
 constexpr int kMaxSplits = 4;
 constexpr int kMaxEos = 16, kMaxSuppress = 256;     // list limits of the logits processors (include/fvhd.h)
+constexpr int kMaxConStates = 1 << 24, kMaxConEdges = 1 << 28;      // table limits of fvhd_llm_set_constraint (include/fvhd.h)
 
 struct LayerOff { size_t ln1, bqkv, ln2, w[4], s[4]; };     // w, s: by FVHD_MAT_QKV .. FVHD_MAT_DOWN; s: the fp32 row scales of an e4m3 matrix,
                                                             // the block scale bytes of an MXFP4 one
@@ -124,7 +125,22 @@ struct __attribute__((visibility("default"))) fvhd_llm {     // (its inline cons
     int lp_on = 0;
     char* lp_ws = nullptr;
     const float* lp_logits = nullptr;
+    // fvhd_llm_set_constraint (llm_constrain.hip): con_n_states > 0 = on.  con_tab: one allocation of its own, offsets [n_states + 1] |
+    // tokens [n_edges] | targets [n_edges]; tables that a captured step has recorded are retired (kept until fvhd_llm_destroy) when OTHER
+    // tables are set, never overwritten (the proc_lists rule); switching off keeps them, and setting the same tables again uploads nothing.
+    // con_state: the rows' states [64] | flags [64], allocated by the first set and kept until destroy.  The start states travel by value
+    // in the launch arguments of fvhd_llm_start / _extend.
+    int con_n_states = 0, con_n_edges = 0, con_n_start = 0;
+    int con_tab_states = 0, con_tab_edges = 0;       // the shape of the tables in con_tab (they stay while the constraint is off)
+    int* con_tab = nullptr;
+    bool con_captured = false;
+    std::vector<int32_t> con_host;         // what con_tab holds
+    int* con_state = nullptr;
+    int con_start[64] = {};
+    bool con_started = false;              // the last fvhd_llm_start / _extend ran with the constraint on: a decode step has states to advance
 };
+
+inline bool constraint_on(const fvhd_llm* c) { return c->con_n_states > 0; }
 
 inline bool processors_on(const fvhd_llm* c)
 {

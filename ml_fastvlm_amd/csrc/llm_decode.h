@@ -133,3 +133,23 @@ struct SpecAcceptArgs {
     int cap = 0;
     const int* gate = nullptr;     // non-NULL: the launch does nothing while *gate != 0
 };
+
+// Constrained decoding (llm_constrain.hip): the automaton's CSR tables, the rows' states and the step's fed ids
+#define DEC_CON_SLICE 4096   // ids per workgroup of the mask launch (fvhd_dec_constrain_slice)
+
+struct DecConstrainArgs {
+    float* logits = nullptr;       // fp32 [B][V], row stride V, any 4-byte alignment
+    int B = 0, V = 0;
+    const int* offsets = nullptr;  // int32 [n_states + 1]
+    const int* tokens = nullptr;   // int32 [n_edges], strictly ascending inside a state
+    const int* targets = nullptr;  // int32 [n_edges]: the next state, or -1 (FREE)
+    int n_states = 0;
+    int* states = nullptr;         // int32 [B]: -1 = FREE
+    int* flags = nullptr;          // int32 [B]: bit 0 = the row was fed a token its state does not list
+    const int64_t* tok = nullptr;  // the step's fed ids: tok, else last; both NULL = no advance
+    const int64_t* last = nullptr;
+    int reset = 0;                 // 1: states[b] = start[n_start == 1 ? 0 : b], flags[b] = 0 (fvhd_llm_start / _extend) instead of an advance
+    int n_start = 0;
+    int start[64] = {};            // by value: a captured launch keeps the start states it was captured with
+    const int* status = nullptr;   // non-NULL: the launches write nothing while *status != 0
+};

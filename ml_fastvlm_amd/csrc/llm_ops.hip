@@ -362,6 +362,20 @@ int fvhd_op_dec_logprobs(fvhd_stream_t st, const float* logits, const int64_t* i
                                                                  scratch, nullptr));
 }
 
+// the constraint's launches on their own: the advance when fed_ids is given, then the mask
+int fvhd_op_dec_constrain(fvhd_stream_t st, float* logits, int B, int V, const int32_t* offsets, const int32_t* tokens, const int32_t* targets, int n_states,
+                          int32_t* states, int32_t* flags, const int64_t* fed_ids)
+{
+    if (!logits || !offsets || !tokens || !targets || !states || !flags) return lfail("fvhd_op_dec_constrain: NULL pointer");
+    if (B < 1 || B > 64 || V < 1) return lfail("fvhd_op_dec_constrain: needs 1 <= B <= 64 and V >= 1");
+    if (n_states < 1) return lfail("fvhd_op_dec_constrain: needs n_states >= 1");
+    if ((uintptr_t)logits & 3) return lfail("fvhd_op_dec_constrain: logits must be aligned to 4 bytes");
+    DecConstrainArgs a;
+    a.logits = logits; a.B = B; a.V = V; a.offsets = offsets; a.tokens = tokens; a.targets = targets; a.n_states = n_states; a.states = states;
+    a.flags = flags; a.tok = fed_ids;
+    return lret("fvhd_op_dec_constrain", fvhd_launch_dec_constrain((hipStream_t)st, &a));
+}
+
 // process-wide scratch of a single op, allocated / grown on demand - eager calls only
 static int op_scratch(const char* who, char* (&buf)[64], size_t (&cap)[64], size_t need, char** out)
 {

@@ -1,5 +1,5 @@
 // C ABI of the Qwen2 decode (include/fvhd.h "LLM decode"): the library's own KV cache, one token per sequence per step.
-// Kernels: llm_decode.hip, llm_w8.hip, llm_sample.hip, llm_beam.hip, llm_logits.hip, llm_spec.hip, llm_extend.hip.
+// Kernels: llm_decode.hip, llm_w8.hip, llm_sample.hip, llm_beam.hip, llm_logits.hip, llm_constrain.hip, llm_spec.hip, llm_extend.hip.
 #include <algorithm>
 #include <cmath>
 
@@ -75,6 +75,31 @@ DecLogitsArgs dec_logits_args(fvhd_llm* c, float* logits, int B, hipStream_t st)
     a.eos = c->proc_lists; a.n_eos = c->proc_n_eos; a.sup = c->proc_lists ? c->proc_lists + kMaxEos : nullptr; a.n_sup = c->proc_n_sup;
     if (c->proc_lists && is_capturing(st)) c->proc_lists_captured = true;     // the caller's graph now reads the lists: retired, never overwritten
     return a;
+}
+
+// the constraint's tables and states of this enqueue; the fed ids (or the reset to the start states) are the caller's to fill
+DecConstrainArgs dec_constrain_args(fvhd_llm* c, float* logits, int B, hipStream_t st)
+{
+    DecConstrainArgs a;
+    a.logits = logits; a.B = B; a.V = c->V; a.offsets = c->con_tab; a.tokens = c->con_tab + c->con_n_states + 1; a.targets = a.tokens + c->con_n_edges;
+    a.n_states = c->con_n_states; a.states = c->con_state; a.flags = c->con_state + 64;
+    if (is_capturing(st)) c->con_captured = true;                // the caller's graph now reads the tables: retired, never overwritten
+    return a;
+}
+
+// fvhd_llm_start / _extend: the rows take their start states (by value: a captured launch keeps them) and clear their flags
+void constrain_reset(DecConstrainArgs& a, const fvhd_llm* c)
+{
+    a.reset = 1;
+    a.n_start = c->con_n_start;
+    std::copy(c->con_start, c->con_start + 64, a.start);
+}
+
+int constraint_start_error(const fvhd_llm* c, const char* who, int B)
+{
+    if (c->con_n_start == 1 || c->con_n_start >= B) return 0;
+    return lfail(std::string(who) + ": the constraint was set with " + std::to_string(c->con_n_start) + " start states, this call has " + std::to_string(B) +
+                 " rows - set it (fvhd_llm_set_constraint) with one start state, or one per row of fvhd_llm_cache_reserve");
 }
 
 }  // namespace
@@ -161,6 +186,7 @@ int fvhd_llm_cache_reserve(fvhd_llm* c, int batch, int capacity)
     c->sp_begun = false;
     c->dc_batch = c->dc_cap = c->run_batch = 0;
     c->hist_started = false;
+    c->con_started = false;
     c->ids_stale = false;
     if ((he = hipMalloc((void**)&c->dc, a.off)) != hipSuccess) return lhip("hipMalloc(llm KV cache)", he);
     if ((he = hipMemset(c->dc, 0, a.off)) != hipSuccess) return lhip("hipMemset(llm KV cache)", he);      // counters start at zero
@@ -189,6 +215,9 @@ int fvhd_llm_start(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* ke
     if (batch < 1 || batch > c->dc_batch) return lfail("fvhd_llm_start: batch must be in [1, the batch of fvhd_llm_cache_reserve]");
     if (seq_len < 1 || seq_len > c->dc_cap) return lfail("fvhd_llm_start: seq_len must be in [1, the capacity of fvhd_llm_cache_reserve]");
     if (int e = dec_embedding_error(c, "fvhd_llm_start")) return e;
+    const bool con = constraint_on(c);
+    if (con)
+        if (int e = constraint_start_error(c, "fvhd_llm_start", batch)) return e;
     LLM_ON_DEVICE(c);
     hipStream_t st = (hipStream_t)stream;
     const int L = c->L, nkv = c->nkv, hd = c->hd, T = seq_len, B = batch, cap = c->dc_cap;
@@ -233,6 +262,13 @@ int fvhd_llm_start(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* ke
         pa.start_T = T;
         LCHECK(fvhd_launch_dec_logits_process(st, &pa), "first-token logits processors");
     }
+    c->con_started = con;
+    if (con) {
+        // the rows' start states, then the bans of those states on the prefill's logits: behind the processors, before either choice
+        DecConstrainArgs ca = dec_constrain_args(c, logits, B, st);
+        constrain_reset(ca, c);
+        LCHECK(fvhd_launch_dec_constrain(st, &ca), "first-token constraint");
+    }
     if (c->do_sample) {
         // sampling: the cache state first, so that the draw reads n = the prompt length from the device
         LCHECK(fvhd_launch_dec_start_state(st, c->posv, position_ids, B, T, c->len, c->status), "decode state");
@@ -265,6 +301,10 @@ int fvhd_llm_decode(fvhd_llm* c, const int64_t* token_ids, float* logits_out, in
     if (proc && !c->hist_started)
         return lfail("fvhd_llm_decode: logits processors are on but the sequence was started without them (no token history) - set them "
                      "before fvhd_llm_start");
+    const bool con = constraint_on(c);
+    if (con && !c->con_started)
+        return lfail("fvhd_llm_decode: a constraint is on (fvhd_llm_set_constraint) but the sequence was started without it (the rows have no "
+                     "states) - set it before fvhd_llm_start / fvhd_llm_extend");
     LLM_ON_DEVICE(c);
     hipStream_t st = (hipStream_t)stream;
     const int B = c->run_batch, H = c->H, I = c->I, nh = c->nh, nkv = c->nkv, hd = c->hd, cap = c->dc_cap;
@@ -311,12 +351,17 @@ int fvhd_llm_decode(fvhd_llm* c, const int64_t* token_ids, float* logits_out, in
     }
     DecGemmArgs a = gemm(DEC_EPI_ARGMAX, c->dh, (const float*)(w + c->norm_off), -1, FVHD_MAT_LM_HEAD);
     a.logits = logits_out; a.amax_v = c->amax_v; a.amax_i = c->amax_i;
-    if ((proc || c->lp_on) && !a.logits) a.logits = c->dlogits;      // fvhd_llm_set_logprobs: the greedy step keeps its logits too
+    if ((proc || c->lp_on || con) && !a.logits) a.logits = c->dlogits;      // fvhd_llm_set_logprobs: the greedy step keeps its logits too
     c->lp_logits = nullptr;
     DecLogitsArgs pa;
     if (proc) {
         pa = dec_logits_args(c, a.logits, B, st);
         pa.tok = token_ids; pa.last = c->last_ids; pa.status = c->status;
+    }
+    DecConstrainArgs ca;
+    if (con) {
+        ca = dec_constrain_args(c, a.logits, B, st);
+        ca.tok = token_ids; ca.last = c->last_ids; ca.status = c->status;
     }
     if (c->do_sample) {
         // sampling replaces the argmax reduce: it reads the logits (the caller's, else the context's buffer), chooses with n = length + 1
@@ -324,6 +369,7 @@ int fvhd_llm_decode(fvhd_llm* c, const int64_t* token_ids, float* logits_out, in
         if (!a.logits) a.logits = c->dlogits;
         LCHECK(fvhd_launch_dec_gemm(st, &a), "decode final norm + lm_head");
         if (proc) LCHECK(fvhd_launch_dec_logits_process(st, &pa), "decode logits processors");      // one launch over all rows, then the sampler's blocks
+        if (con) LCHECK(fvhd_launch_dec_constrain(st, &ca), "decode constraint");                   // behind the processors: advance, then the bans
         DecSampleArgs sa = dec_sample_args(c, a.logits, B);
         sa.len = c->len; sa.n_add = 1; sa.last = c->last_ids; sa.ids_out = next_ids_out; sa.posv = c->posv; sa.len_advance = c->len;
         sa.status = c->status;
@@ -334,9 +380,11 @@ int fvhd_llm_decode(fvhd_llm* c, const int64_t* token_ids, float* logits_out, in
         return 0;
     }
     LCHECK(fvhd_launch_dec_gemm(st, &a), "decode final norm + lm_head + argmax");
-    if (proc) {
-        // the lm_head's fused (max, index) pairs saw the raw logits: the pairs again, from the processed ones (the first token's launch)
-        LCHECK(fvhd_launch_dec_logits_process(st, &pa), "decode logits processors");
+    if (proc || con) {
+        // the lm_head's fused (max, index) pairs saw the raw logits: the pairs again, ONCE, from the processed and constrained ones (the
+        // first token's launch)
+        if (proc) LCHECK(fvhd_launch_dec_logits_process(st, &pa), "decode logits processors");
+        if (con) LCHECK(fvhd_launch_dec_constrain(st, &ca), "decode constraint");
         LCHECK(fvhd_launch_dec_argmax_blocks(st, a.logits, c->V, B, c->amax_v, c->amax_i), "decode argmax (blocks)");
     }
     LCHECK(fvhd_launch_dec_argmax_finish(st, c->amax_v, c->amax_i, (c->V / 16 + 3) / 4, B, c->last_ids, next_ids_out, c->posv, c->len, c->status),
@@ -364,6 +412,9 @@ int fvhd_llm_extend(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* k
         return lfail("fvhd_llm_extend: logits processors are on (fvhd_llm_set_logits_processors) - their token history has no ids for an embedded "
                      "chunk; switch them off around fvhd_llm_extend");
     if (first_missing_tensor(c) >= 0) return lfail("fvhd_llm_extend: weights incomplete (fvhd_llm_finalize reports the missing tensor)");
+    const bool con = constraint_on(c);
+    if (con)
+        if (int e = constraint_start_error(c, "fvhd_llm_extend", c->run_batch)) return e;
     hipStream_t st = (hipStream_t)stream;
     const int B = c->run_batch;
     float* logits = logits_out ? logits_out : c->dlogits;
@@ -373,6 +424,14 @@ int fvhd_llm_extend(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* k
     LLM_ON_DEVICE(c);
     // the token: the launches of fvhd_llm_start (the sampler's n = the new length = length + T), then the state; all of them gated by
     // the error word the first append sets when length + T > capacity
+    c->con_started = con;
+    if (con) {
+        // a new answer: the rows' start states again, and their bans on the chunk's last logits
+        DecConstrainArgs ca = dec_constrain_args(c, logits, B, st);
+        constrain_reset(ca, c);
+        ca.status = c->status;
+        LCHECK(fvhd_launch_dec_constrain(st, &ca), "extend constraint");
+    }
     if (c->do_sample) {
         DecSampleArgs a = dec_sample_args(c, logits, B);
         a.len = c->len; a.n_add = T; a.last = c->last_ids; a.ids_out = next_ids_out; a.status = c->status;
@@ -397,6 +456,9 @@ int fvhd_llm_cache_rewind(fvhd_llm* c, const int32_t* keep_dev, fvhd_stream_t st
     if (processors_on(c))
         return lfail("fvhd_llm_cache_rewind: logits processors are on (fvhd_llm_set_logits_processors) - their token history is not rewound; "
                      "switch them off around fvhd_llm_cache_rewind");
+    if (constraint_on(c))
+        return lfail("fvhd_llm_cache_rewind: a constraint is on (fvhd_llm_set_constraint) - the rows' automaton states are not rewound; "
+                     "switch it off around fvhd_llm_cache_rewind");
     LLM_ON_DEVICE(c);
     LCHECK(fvhd_launch_llm_cache_rewind((hipStream_t)stream, keep_dev, c->run_batch, c->mask, c->posv, c->dc_cap, c->len, c->status, c->status_host_dev),
            "cache rewind");
@@ -431,6 +493,9 @@ int fvhd_llm_cache_gather(fvhd_llm* c, const int64_t* src_rows, int rows_in, int
     if (processors_on(c))
         return lfail("fvhd_llm_cache_gather: logits processors are on (fvhd_llm_set_logits_processors) - their token history is not reordered; "
                      "switch them off around fvhd_llm_cache_gather");
+    if (constraint_on(c))
+        return lfail("fvhd_llm_cache_gather: a constraint is on (fvhd_llm_set_constraint) - the rows' automaton states are not reordered; "
+                     "switch it off around fvhd_llm_cache_gather");
     LLM_ON_DEVICE(c);
     DecCacheGatherArgs a;
     a.kc = c->kcache; a.vc = c->vcache; a.layers = c->L; a.batch = c->dc_batch; a.mask = c->mask; a.posv = c->posv; a.src = src_rows;
@@ -448,6 +513,9 @@ int fvhd_llm_beam_topk(fvhd_llm* c, const float* logits, const float* beam_score
 {
     if (!c || !logits || !beam_scores || !cand_scores || !cand_index) return lfail("fvhd_llm_beam_topk: NULL argument");
     if (!c->beam) return lfail("fvhd_llm_beam_topk: no workspace - call fvhd_llm_beam_reserve first");
+    if (constraint_on(c))
+        return lfail("fvhd_llm_beam_topk: a constraint is on (fvhd_llm_set_constraint) - beam search does not carry the rows' automaton states; "
+                     "switch it off for beam search");
     if (!fvhd_dec_beam_topk_supported(groups, num_beams, keep, c->V) || ((uintptr_t)logits & 15))
         return lfail("fvhd_llm_beam_topk: needs groups >= 1, 2 <= num_beams <= 16, 1 <= keep <= 64, keep <= vocab, groups * num_beams <= 64, "
                      "vocab % 16 == 0, vocab <= 262144 and logits aligned to 16 bytes");
@@ -504,6 +572,8 @@ int spec_refusal(const fvhd_llm* c, const char* who, int rows)
     if (c->do_sample) return lfail(w + ": sampling is on (fvhd_llm_set_sampling) - the verify step is greedy only: it keeps the drafts the argmax confirms");
     if (processors_on(c))
         return lfail(w + ": logits processors are on (fvhd_llm_set_logits_processors) - the verify step does not maintain their token history");
+    if (constraint_on(c))
+        return lfail(w + ": a constraint is on (fvhd_llm_set_constraint) - the verify step does not advance the rows' automaton states");
     return 0;
 }
 
@@ -726,6 +796,107 @@ int fvhd_llm_logprobs(fvhd_llm* c, const float* logits, int top_n, float* token_
     LLM_ON_DEVICE(c);
     LCHECK(fvhd_launch_dec_logprobs((hipStream_t)stream, logits, c->last_ids, c->run_batch, c->V, top_n, token_logprob_out, top_ids_out, top_logprobs_out,
                                     c->lp_ws, c->status), "logprobs");
+    return 0;
+}
+
+// ---- constrained decoding (include/fvhd.h "LLM constrained decoding"; kernels: llm_constrain.hip) ----
+int fvhd_llm_set_constraint(fvhd_llm* c, const int32_t* off, int n_states, const int32_t* tok, const int32_t* tgt, int n_edges, const int32_t* start,
+                            int n_start)
+{
+    const std::string w = "fvhd_llm_set_constraint: ";
+    if (!c) return lfail(w + "ctx is NULL");
+    if (n_states < 0) return lfail(w + "n_states must be >= 0 (0 = off)");
+    if (n_states > 0) {
+        if (!off || !tok || !tgt || !start) return lfail(w + "NULL table");
+        if (n_states > kMaxConStates) return lfail(w + std::to_string(n_states) + " states exceed the limit of " + std::to_string(kMaxConStates) + " states");
+        if (n_edges < 1 || n_edges > kMaxConEdges)
+            return lfail(w + "n_edges = " + std::to_string(n_edges) + " must be in [1, the limit of " + std::to_string(kMaxConEdges) + " edges]");
+        if (n_start != 1 && (n_start != c->dc_batch || !c->dc))
+            return lfail(w + "n_start = " + std::to_string(n_start) + " must be 1 (every row) or the batch of fvhd_llm_cache_reserve (" +
+                         std::to_string(c->dc_batch) + ")");
+        if (off[0] != 0) return lfail(w + "offsets must start at 0 (offsets[0] = " + std::to_string(off[0]) + ")");
+        if (off[n_states] != n_edges)
+            return lfail(w + "offsets[n_states] = " + std::to_string(off[n_states]) + " is not n_edges = " + std::to_string(n_edges));
+        for (int s = 0; s < n_states; ++s) {
+            const int e0 = off[s], e1 = off[s + 1];
+            if (e1 < e0 || e1 > n_edges) return lfail(w + "offsets are not monotone at state " + std::to_string(s));
+            if (e1 == e0) return lfail(w + "state " + std::to_string(s) + " has no edge - an unsatisfiable state");
+            for (int e = e0; e < e1; ++e) {
+                if (tok[e] < 0 || tok[e] >= c->V)
+                    return lfail(w + "token " + std::to_string(tok[e]) + " of edge " + std::to_string(e) + " (state " + std::to_string(s) +
+                                 ") is outside [0, vocab = " + std::to_string(c->V) + ")");
+                if (tgt[e] < -1 || tgt[e] >= n_states)
+                    return lfail(w + "target " + std::to_string(tgt[e]) + " of edge " + std::to_string(e) + " (state " + std::to_string(s) +
+                                 ") is outside [-1, n_states = " + std::to_string(n_states) + ")");
+                if (e > e0 && tok[e] <= tok[e - 1])
+                    return lfail(w + "the tokens of state " + std::to_string(s) + " are not strictly ascending at edge " + std::to_string(e));
+            }
+        }
+        for (int i = 0; i < n_start; ++i)
+            if (start[i] < -1 || start[i] >= n_states)
+                return lfail(w + "start state " + std::to_string(start[i]) + " of row " + std::to_string(i) + " is outside [-1, n_states = " +
+                             std::to_string(n_states) + ")");
+    }
+    LLM_ON_DEVICE(c);
+    hipError_t he = hipDeviceSynchronize();                      // refused while a stream is being captured; no enqueued step still reads the tables
+    if (he != hipSuccess) return lhip("fvhd_llm_set_constraint: hipDeviceSynchronize", he);
+    if (n_states == 0) {                                         // off: the tables stay (a captured step may replay on them; the same ones may return)
+        c->con_n_states = c->con_n_edges = c->con_n_start = 0;
+        return 0;
+    }
+    if (!c->con_state) {
+        if ((he = hipMalloc((void**)&c->con_state, 2 * 64 * 4)) != hipSuccess) { c->con_state = nullptr; return lhip("hipMalloc(constraint states)", he); }
+        if ((he = hipMemset(c->con_state, 0xff, 64 * 4)) == hipSuccess) he = hipMemset(c->con_state + 64, 0, 64 * 4);      // FREE, no flags
+        if (he != hipSuccess) return lhip("hipMemset(constraint states)", he);
+    }
+    const size_t words = (size_t)n_states + 1 + 2 * (size_t)n_edges;
+    const bool same = c->con_tab && c->con_tab_states == n_states && c->con_tab_edges == n_edges && c->con_host.size() == words &&
+                      std::equal(off, off + n_states + 1, c->con_host.begin()) && std::equal(tok, tok + n_edges, c->con_host.begin() + n_states + 1) &&
+                      std::equal(tgt, tgt + n_edges, c->con_host.begin() + n_states + 1 + n_edges);
+    if (!same) {                                                 // (the same tables again: nothing to upload)
+        if (c->con_tab) {
+            if (c->con_captured) c->retired.push_back((char*)c->con_tab);      // a captured step replays on the old tables
+            else (void)hipFree(c->con_tab);
+            c->con_tab = nullptr;
+        }
+        c->con_captured = false;
+        c->con_host.clear();
+        c->con_tab_states = c->con_tab_edges = 0;
+        c->con_n_states = c->con_n_edges = c->con_n_start = 0;
+        if ((he = hipMalloc((void**)&c->con_tab, words * 4)) != hipSuccess) { c->con_tab = nullptr; return lhip("hipMalloc(constraint tables)", he); }
+        he = hipMemcpy(c->con_tab, off, ((size_t)n_states + 1) * 4, hipMemcpyHostToDevice);
+        if (he == hipSuccess) he = hipMemcpy(c->con_tab + n_states + 1, tok, (size_t)n_edges * 4, hipMemcpyHostToDevice);
+        if (he == hipSuccess) he = hipMemcpy(c->con_tab + n_states + 1 + n_edges, tgt, (size_t)n_edges * 4, hipMemcpyHostToDevice);
+        if (he == hipSuccess) he = hipDeviceSynchronize();
+        if (he != hipSuccess) return lhip("hipMemcpy(constraint tables)", he);
+        c->con_host.reserve(words);
+        c->con_host.insert(c->con_host.end(), off, off + n_states + 1);
+        c->con_host.insert(c->con_host.end(), tok, tok + n_edges);
+        c->con_host.insert(c->con_host.end(), tgt, tgt + n_edges);
+        c->con_tab_states = n_states;
+        c->con_tab_edges = n_edges;
+    }
+    c->con_n_states = n_states;
+    c->con_n_edges = n_edges;
+    c->con_n_start = n_start;
+    std::fill(c->con_start, c->con_start + 64, -1);
+    std::copy(start, start + n_start, c->con_start);
+    return 0;
+}
+
+int fvhd_llm_constraint_state(fvhd_llm* c, int32_t* states_out, int32_t* flags_out, int rows)
+{
+    if (!c) return lfail("fvhd_llm_constraint_state: ctx is NULL");
+    if (!constraint_on(c)) return lfail("fvhd_llm_constraint_state: no constraint is on (fvhd_llm_set_constraint)");
+    if (!c->con_started || !c->run_batch)
+        return lfail("fvhd_llm_constraint_state: no sequence was started under the constraint - fvhd_llm_start / fvhd_llm_extend give the rows their states");
+    if (rows < 1 || rows > c->run_batch)
+        return lfail("fvhd_llm_constraint_state: rows must be in [1, the started batch = " + std::to_string(c->run_batch) + "]");
+    LLM_ON_DEVICE(c);
+    hipError_t he = hipDeviceSynchronize();
+    if (he == hipSuccess && states_out) he = hipMemcpy(states_out, c->con_state, (size_t)rows * 4, hipMemcpyDeviceToHost);
+    if (he == hipSuccess && flags_out) he = hipMemcpy(flags_out, c->con_state + 64, (size_t)rows * 4, hipMemcpyDeviceToHost);
+    if (he != hipSuccess) return lhip("fvhd_llm_constraint_state", he);
     return 0;
 }
 

@@ -241,6 +241,8 @@ void fvhd_llm_destroy(fvhd_llm* c)
     if (c->spec) (void)hipFree(c->spec);
     if (c->score_ws) (void)hipFree(c->score_ws);
     if (c->lp_ws) (void)hipFree(c->lp_ws);
+    if (c->con_tab) (void)hipFree(c->con_tab);
+    if (c->con_state) (void)hipFree(c->con_state);
     if (c->pre_kv) (void)hipFree(c->pre_kv);
     if (c->status_host) (void)hipHostFree(c->status_host);
     delete c;

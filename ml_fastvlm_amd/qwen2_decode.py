@@ -30,6 +30,9 @@ attention over the cached keys) and `rewind` drops the tail of every row; `greed
 `greedy` / `sample` with `logprobs=n` (0 .. 16) also return `GenerationLogprobs`: per generated token its log-probability and the n most
 likely tokens with theirs (include/fvhd.h "LLM log-probabilities") - one more launch inside the captured step, on the logits the choice
 was made from.
+`greedy` / `sample` with `constraint=TokenAutomaton` (`ml_fastvlm_amd.constraints`, include/fvhd.h "LLM constrained decoding") answer in a
+given form: the step keeps one automaton state per row on the device and bans every token the state does not allow before the choice -
+no host work per token, so it runs inside the captured step beside sampling, the processors and the log-probabilities.
 """
 from __future__ import annotations
 
@@ -123,6 +126,7 @@ class Qwen2Generator:
         self._run_batch = 0
         self._length = None                                      # the cache length as the host knows it (None: unknown - `length()` asks the device)
         self._processors = None                                  # what set_logits_processors last set (None = all off)
+        self._constraint = None                                  # the TokenAutomaton set_constraint last set (None = off)
         self._ids_stale = False                                  # a rewind / cache_gather since the ids were chosen (`_stale_ids_refusal`)
         self._spec_rows = 0                                      # the largest row count this generator asked of spec_reserve
         self._spec_logits = self._spec_ids = self._spec_emitted = None      # verify()'s output buffers, made on first use
@@ -251,6 +255,7 @@ class Qwen2Generator:
         if self._processors is not None:
             raise ValueError("rewind: logits processors are set (set_logits_processors) - their token history is not rewound; "
                              "clear them with set_logits_processors()")
+        self._constraint_refusal("rewind", "the rows' automaton states are not rewound")
         on_device = isinstance(keep, torch.Tensor) and keep.device.type != "cpu"
         k = keep if isinstance(keep, torch.Tensor) else torch.tensor([int(v) for v in keep], dtype=torch.int32)
         if k.dim() != 1 or k.shape[0] != B or k.dtype not in (torch.int32, torch.int64):
@@ -343,6 +348,7 @@ class Qwen2Generator:
         if self._processors is not None:
             raise ValueError("cache_gather: logits processors are set (set_logits_processors) - their token history is not reordered; "
                              "clear them with set_logits_processors()")
+        self._constraint_refusal("cache_gather", "the rows' automaton states are not reordered")
         if src_rows.dtype != torch.long or src_rows.device != self.device or src_rows.dim() != 1 or not src_rows.is_contiguous():
             raise ValueError(f"src_rows must be a contiguous 1-D int64 tensor on {self.device}")
         rows_out = src_rows.shape[0]
@@ -375,6 +381,7 @@ class Qwen2Generator:
         if self._processors is not None:
             raise ValueError(f"{who}: logits processors are set (set_logits_processors) - the verify step does not maintain their token history; "
                              "clear them with set_logits_processors()")
+        self._constraint_refusal(who, "the verify step does not advance the rows' automaton states")
 
     def spec_reserve(self, T: int, lookup_capacity: int = 0) -> None:
         """the scratch of verify steps of up to T rows and a token buffer for `lookup_capacity` lookup ids (`fvhd_llm_spec_reserve`).  The
@@ -539,6 +546,71 @@ class Qwen2Generator:
                                                           len(c["suppress_tokens"])), "fvhd_llm_set_logits_processors")
         self._processors = cfg
 
+    # ---- constrained decoding ------------------------------------------------------------------------------------------------------------
+    def set_constraint(self, automaton=None, start_states=None) -> None:
+        """a `ml_fastvlm_amd.constraints.TokenAutomaton` on the logits of start() / extend() / step() from now on, behind the processors
+        and before the choice (`fvhd_llm_set_constraint`): every token a row's state does not allow becomes -inf, and the state advances
+        on the ids fed to the steps.  start_states: None (state 0 for every row), an int, or one state per row (-1 = that row is
+        unconstrained; rows beyond the list are unconstrained).  start() / extend() put the rows back at their start states - set it before start().  None
+        switches it off.  With it on, the logits start() / step() return are the masked scores.  Synchronises; a captured step keeps the
+        tables it was captured with.  Not for beam_search, verify / lookup_greedy, rewind or cache_gather."""
+        from .constraints import TokenAutomaton
+        if torch.cuda.is_current_stream_capturing():             # the library's call synchronises the device, which would invalidate the capture
+            raise ValueError("set_constraint: refused while a stream is being captured (it synchronises the device and uploads tables) - set the "
+                             "constraint before capturing; a captured step keeps the tables it was captured with")
+        if automaton is None:
+            if self._constraint is None and not hasattr(_lib.load(), "fvhd_op_dec_constrain"):
+                return                                           # off on a library that has none: nothing to say
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.constraint_lib().fvhd_llm_set_constraint(self.pre._h, None, 0, None, None, 0, None, 0), "fvhd_llm_set_constraint")
+            self._constraint = None
+            return
+        if not isinstance(automaton, TokenAutomaton):
+            raise ValueError(f"set_constraint: expected a ml_fastvlm_amd.constraints.TokenAutomaton or None, got {type(automaton).__name__}")
+        if automaton.vocab != self.pre.vocab:
+            raise ValueError(f"set_constraint: the automaton was built for a vocabulary of {automaton.vocab} ids, the model has {self.pre.vocab}")
+        starts = automaton.start_states(start_states)
+        if len(starts) > self.batch:
+            raise ValueError(f"set_constraint: {len(starts)} start states exceed the reserved batch {self.batch}")
+        if len(starts) > 1:
+            starts = starts + [-1] * (self.batch - len(starts))  # the library takes one for all, or one per row of the reserved cache
+        st = torch.tensor(starts, dtype=torch.int32)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.constraint_lib().fvhd_llm_set_constraint(self.pre._h, _lib.ptr(automaton.offsets), automaton.n_states, _lib.ptr(automaton.tokens),
+                                                                    _lib.ptr(automaton.targets), automaton.n_edges, _lib.ptr(st), len(starts)),
+                       "fvhd_llm_set_constraint")
+        self._constraint = automaton
+
+    def constraint_state(self):
+        """(states int32 [B], flags int32 [B]) of the started rows, on the host, after a device synchronisation
+        (`fvhd_llm_constraint_state`): the state after the last FED token - not advanced by the last chosen one; -1 = unconstrained;
+        flag bit 0: the row was fed a token its state does not list.  Raises while no constraint is on or nothing was started under it."""
+        B = max(1, self._run_batch)
+        st, fl = torch.zeros((B,), dtype=torch.int32), torch.zeros((B,), dtype=torch.int32)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.constraint_lib().fvhd_llm_constraint_state(self.pre._h, _lib.ptr(st), _lib.ptr(fl), B), "fvhd_llm_constraint_state")
+        return st, fl
+
+    def _constraint_refusal(self, who: str, why: str) -> None:
+        """the library's refusals while a constraint is on (include/fvhd.h), raised before calling in"""
+        if getattr(self, "_constraint", None) is not None:
+            raise ValueError(f"{who}: a constraint is set (set_constraint) - {why}; clear it with set_constraint()")
+
+    @contextlib.contextmanager
+    def _constraint_for_run(self, constraint, constraint_start):
+        """the `constraint` keyword of greedy() / sample(): set for the run, cleared in a finally.  With none given, whatever set_constraint
+        set stays as it is."""
+        if constraint is None:
+            if constraint_start is not None:
+                raise ValueError("constraint_start is given without a constraint")
+            yield
+            return
+        self.set_constraint(constraint, constraint_start)
+        try:
+            yield
+        finally:
+            self.set_constraint()
+
     def _set_greedy(self) -> None:
         if _lib.load().fvhd_version() >= _lib.SAMPLING_VERSION:      # a library without sampling is greedy anyway
             self.set_sampling(False)
@@ -548,7 +620,8 @@ class Qwen2Generator:
     def greedy(self, inputs_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None,
                max_new_tokens: int = 256, eos_token_id: Union[None, int, Sequence[int]] = None, pad_token_id: Optional[int] = None,
                graph: bool = True, poll_every: int = 16, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0,
-               suppress_tokens: Optional[Sequence[int]] = None, continue_cache: bool = False, logprobs: Optional[int] = None):
+               suppress_tokens: Optional[Sequence[int]] = None, continue_cache: bool = False, logprobs: Optional[int] = None,
+               constraint=None, constraint_start=None):
         """transformers' greedy search (`GenerationMixin._sample` with do_sample=False) on the library's steps -> new tokens [B, n].
         graph=True captures one step (decode + the finished-sequence bookkeeping) into a CUDA graph and replays it; "all finished" is
         polled every `poll_every` steps (no host synchronisation per token) and the output trimmed to the step where it happened.
@@ -558,11 +631,14 @@ class Qwen2Generator:
         `start` (not with logits processors); everything after the first token is the same code.
         logprobs=n (0 .. 16): -> (tokens, `GenerationLogprobs`) - every token's log-probability and the n most likely tokens of its step,
         the first token included, from one more launch inside the captured step; None (the default): the tokens alone, launch for launch
-        what it was."""
+        what it was.
+        constraint: a `ml_fastvlm_amd.constraints.TokenAutomaton` (`set_constraint`), set for this run and cleared after it; every row's
+        tokens follow it from constraint_start (None: state 0; an int; or one state per row, -1 = unconstrained).  A row that takes an EOS
+        edge is unconstrained behind it, where the run feeds it pads.  With logprobs, the log-probabilities are over the allowed set."""
         logprobs = normalize_logprobs(logprobs, self.pre.vocab)
         self._set_greedy()
         with self._processors_for_run(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, suppress_tokens), \
-                self._logprobs_for_run(logprobs):
+                self._logprobs_for_run(logprobs), self._constraint_for_run(constraint, constraint_start):
             return self._run(inputs_embeds, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id, graph, poll_every, continue_cache,
                              logprobs)
 
@@ -571,20 +647,22 @@ class Qwen2Generator:
                max_new_tokens: int = 256, temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, seed: Optional[int] = None,
                eos_token_id: Union[None, int, Sequence[int]] = None, pad_token_id: Optional[int] = None, graph: bool = True,
                poll_every: int = 16, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0,
-               suppress_tokens: Optional[Sequence[int]] = None, continue_cache: bool = False, logprobs: Optional[int] = None):
+               suppress_tokens: Optional[Sequence[int]] = None, continue_cache: bool = False, logprobs: Optional[int] = None,
+               constraint=None, constraint_start=None):
         """transformers' multinomial sampling (`GenerationMixin._sample` with do_sample=True, num_beams=1: temperature, then top-k, then
         top-p) on the library's steps -> new tokens [B, n], with greedy's return contract, EOS / pad bookkeeping and graph replay.
         seed None: 63 bits from torch's default CPU generator, so `torch.manual_seed` makes a run repeat.  The same seed gives the same
         tokens, eager or graph; the draws are not torch.multinomial's (only the distribution is the same).  The logits processors of
         `greedy` apply before the temperature, as in transformers.  continue_cache: as in `greedy`.  logprobs: as in `greedy` - the
-        log-softmax of the (processed) logits BEFORE temperature / top-k / top-p, not of the distribution the draw was made from."""
+        log-softmax of the (processed) logits BEFORE temperature / top-k / top-p, not of the distribution the draw was made from.
+        constraint / constraint_start: as in `greedy` - the draw is made among the tokens the row's state allows."""
         logprobs = normalize_logprobs(logprobs, self.pre.vocab)
         if seed is None:
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.long).item())
         self.set_sampling(True, temperature, top_k, top_p, seed)
         try:
             with self._processors_for_run(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, suppress_tokens), \
-                    self._logprobs_for_run(logprobs):
+                    self._logprobs_for_run(logprobs), self._constraint_for_run(constraint, constraint_start):
                 return self._run(inputs_embeds, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id, graph, poll_every,
                                  continue_cache, logprobs)
         finally:
@@ -709,6 +787,7 @@ class Qwen2Generator:
         if self._processors is not None:
             raise ValueError("beam_search: logits processors are set (set_logits_processors) - they are not implemented under beam search; "
                              "clear them with set_logits_processors()")
+        self._constraint_refusal("beam_search", "beam search does not carry the rows' automaton states")
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be >= 1")
         G, T = inputs_embeds.shape[:2]

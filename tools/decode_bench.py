@@ -11,6 +11,7 @@ captured graph and called eagerly, against the stock `transformers` decode loop 
     python tools/decode_bench.py --lookup --hidden 896 3584 --rows 4 8 16       (prompt-lookup decoding: the verify step at one sequence)
     python tools/decode_bench.py --lookup --trace-steps 16 --hidden 896 --rows 8    (eager verify steps only: the program of a kernel trace)
     python tools/decode_bench.py --logprobs 0 5 16 --hidden 896 3584 --batch 1 64   (log-probabilities of the chosen tokens inside the step)
+    python tools/decode_bench.py --constraint --hidden 896 3584 --batch 1 64        (constrained decoding: a token automaton masks the logits)
 
 --batch takes up to 64 sequences per step (more than 16 need a library of version 503).  --repeats times the graph replay that many
 times (`graph_ms_per_token` is their median, `graph_ms_per_token_runs` all of them); --no-stock leaves the stock transformers loop (and
@@ -46,6 +47,13 @@ csrc/llm_logprobs.hip) for every top-n named, against the same build's step with
 before inside the same graph: `step(logits=True)` + torch.log_softmax + gather + topk(n) (n = 0: no topk).  Every case by graph replay over
 --new tokens at vocab 151936, measured twice (the second time in reverse order) and averaged; `off` twice more at the ends, so that its
 four runs show the run-to-run spread the additions are read against.
+
+--constraint times the captured greedy step with a token automaton on (`Qwen2Generator.set_constraint`, csrc/llm_constrain.hip) for two
+kinds of state - sparse (4 edges) and dense (every other id: vocab / 2 edges), each one state that leads back to itself - against the same
+build's step without it and against torch doing the same job inside the same captured step from dense [states, vocab] tables:
+`state = nxt[state, fed]; logits.masked_fill_(~allowed[state], -inf); fed = logits.argmax(-1)` behind `step(fed, logits=True)` (a baseline
+written for the measurement).  Every case by graph replay over --new tokens, measured twice (the second time in reverse order) and averaged;
+`off` twice more at the ends, so that its four runs show the run-to-run spread the additions are read against.
 
 Full layer counts, random bf16 weights (`tools/ttft.py: build_llm`).  Prints ONE JSON line: per (width, batch) the ms per token of each
 path, the bytes a step must read (packed weights + the KV cache at the mean length) and their fraction of 8 TB/s."""
@@ -305,6 +313,78 @@ def measure_logprobs(llm, pre, batch: int, prompt: int, new: int, dev, ns) -> di
     for n in ns:
         for kind in ("logprobs", "torch"):
             res[f"{kind}_{n}_added_us_per_token"] = round(1000 * (res[f"{kind}_{n}_ms_per_token"] - res["off_ms_per_token"]), 1)
+    del gen
+    return res
+
+
+@torch.no_grad()
+def measure_constraint(llm, pre, batch: int, prompt: int, new: int, dev) -> dict:
+    from ml_fastvlm_amd.constraints import TokenAutomaton
+    from ml_fastvlm_amd.qwen2_decode import Qwen2Generator
+    cfg = llm.config
+    hidden, V = cfg.hidden_size, cfg.vocab_size
+    gen = Qwen2Generator.from_hf(llm, batch, prompt + new + 4, prefill=pre)
+    g = torch.Generator(device=dev).manual_seed(0)
+    emb = (0.5 * torch.randn(batch, prompt, hidden, device=dev, generator=g)).to(torch.bfloat16)
+    mask = torch.ones(batch, prompt, device=dev, dtype=torch.long)
+    res = {"hidden": hidden, "layers": cfg.num_hidden_layers, "batch": batch, "vocab": V, "prompt": prompt, "new_tokens": new}
+    gen._set_greedy()
+    ids = {"sparse": [5, V // 3, V // 2 + 1, V - 2], "dense": list(range(0, V, 2))}
+    res["edges"] = {k: len(v) for k, v in ids.items()}
+    allowed_ids = {k: set(v) for k, v in ids.items()}
+    autos = {k: TokenAutomaton([0, len(v)], v, [0] * len(v), V) for k, v in ids.items()}      # one state that leads back to itself
+    state = torch.zeros((batch,), device=dev, dtype=torch.long)
+    fed = torch.zeros((batch,), device=dev, dtype=torch.long)
+    dense = {}
+    for k, a in autos.items():                              # the torch baseline's tables: allowed bool [S, V], nxt int64 [S, V] (-1 = FREE is not reached)
+        dense[k] = (a.mask([0]).to(dev), torch.zeros((1, V), device=dev, dtype=torch.long))
+
+    def torch_step(kind):
+        allowed, nxt = dense[kind]
+        lg, _ = gen.step(fed, logits=True)
+        state.copy_(nxt[state, fed])
+        lg.masked_fill_(~allowed[state], float("-inf"))
+        fed.copy_(lg.argmax(-1))
+
+    def graph_ms(how, kind):
+        gen.set_constraint(autos[kind] if how == "lib" else None)
+        _, first = gen.start(emb, mask, logits=False)
+        state.zero_()
+        fed.copy_(torch.full_like(first, ids[kind][0]) if how == "torch" else first)
+        fn = {"off": lambda: gen.step(logits=False), "lib": lambda: gen.step(logits=False), "torch": lambda: torch_step(kind)}[how]
+        graph = _graph_of(fn, dev)
+        graph.replay()
+        _, first = gen.start(emb, mask, logits=False)
+        state.zero_()
+        fed.copy_(torch.full_like(first, ids[kind][0]) if how == "torch" else first)
+        ms = _ms_per(graph.replay, new, dev)
+        assert gen.cache_state() == (prompt + new, 0)
+        if how == "lib":
+            st, fl = gen.constraint_state()
+            assert st.tolist() == [0] * batch and fl.tolist() == [0] * batch
+        if how != "off":
+            chosen = (fed if how == "torch" else gen._ids[:batch]).tolist()
+            assert all(t in allowed_ids[kind] for t in chosen)
+        return ms
+
+    cases = {"off": ("off", "sparse")}
+    for kind in ids:
+        cases[f"constraint_{kind}"] = ("lib", kind)
+        cases[f"torch_{kind}"] = ("torch", kind)
+    runs = {k: [] for k in cases}
+    runs["off"].append(graph_ms("off", "sparse"))
+    for order in (list(cases), list(cases)[::-1]):              # twice, the second time in reverse order
+        for k in order:
+            runs[k].append(graph_ms(*cases[k]))
+    runs["off"].append(graph_ms("off", "sparse"))
+    gen.set_constraint()
+    for k, v in runs.items():
+        res[f"{k}_ms_per_token"] = round(sum(v) / len(v), 4)
+        res[f"{k}_ms_per_token_runs"] = [round(x, 4) for x in v]
+    res["off_spread_us"] = round(1000 * (max(runs["off"]) - min(runs["off"])), 1)
+    for kind in ids:
+        for how in ("constraint", "torch"):
+            res[f"{how}_{kind}_added_us_per_token"] = round(1000 * (res[f"{how}_{kind}_ms_per_token"] - res["off_ms_per_token"]), 1)
     del gen
     return res
 
@@ -581,8 +661,26 @@ def main():
     ap.add_argument("--rows", type=int, nargs="+", default=[4, 8, 16], help="--lookup: rows per verify step")
     ap.add_argument("--logprobs", type=int, nargs="+", default=None, metavar="N",
                     help="the step with the chosen tokens' log-probabilities and top-N alternatives, for every N named, against off and against torch ops")
+    ap.add_argument("--constraint", action="store_true",
+                    help="the step with a token automaton on (a sparse and a dense state) against off and against torch doing the same from dense tables")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
+    if a.constraint:
+        from tools.ttft import build_llm
+        from ml_fastvlm_amd import _lib
+        from ml_fastvlm_amd.qwen2_prefill import Qwen2Prefill
+        rows = []
+        for h in (a.hidden if "--hidden" in sys.argv else [896, 3584]):
+            llm = build_llm(h, dev)
+            pre = Qwen2Prefill.from_hf(llm)
+            for b in a.batch:
+                rows.append(measure_constraint(llm, pre, b, a.prompt, a.new, dev))
+                torch.cuda.empty_cache()
+            del pre, llm
+            torch.cuda.empty_cache()
+        print(json.dumps({"tool": "decode_bench", "mode": "constraint", "device": torch.cuda.get_device_name(dev),
+                          "library_version": _lib.constraint_lib().fvhd_version(), "results": rows}))
+        return
     if a.logprobs is not None:
         from tools.ttft import build_llm
         from ml_fastvlm_amd import _lib
