@@ -78,7 +78,10 @@ typedef void* fvhd_stream_t; /* hipStream_t */
  * existing call enqueues what it did and fvhd_llm_cache_reserve allocates what it did (_lib.py logprobs_lib() detects the symbols).  Also added
  * under 510 (new symbols only, the number stays): constrained decoding - fvhd_llm_set_constraint, fvhd_llm_constraint_state,
  * fvhd_op_dec_constrain, fvhd_dec_constrain_slice; with no constraint set (the default) every call enqueues what it did and allocates what it
- * did (_lib.py constraint_lib() detects the symbols). */
+ * did (_lib.py constraint_lib() detects the symbols).  Also added under 510 (new symbols only, the number stays): prompt-lookup decoding
+ * under sampling and with log-probabilities - fvhd_llm_set_verify_sampling, fvhd_llm_lookup_logprobs, fvhd_op_dec_sample_rows; with the
+ * setting off (the default) and no arrays registered every call enqueues, refuses and allocates what it did (_lib.py lookup_sample_lib()
+ * detects the symbols). */
 #define FVHD_VERSION 510
 int fvhd_version(void);
 const char* fvhd_last_error(void);
@@ -519,6 +522,14 @@ int fvhd_llm_set_sampling(fvhd_llm* ctx, int do_sample, float temperature, int t
  * first use: eager calls only, not during stream capture. */
 int fvhd_op_dec_sample(fvhd_stream_t stream, const float* logits, int B, int V, float temperature, int top_k, float top_p, unsigned long long seed,
                        int n, const float* u_override, int64_t* ids, float* info);
+/* the sampler on the T rows of ONE sequence (tests; added under 510): the mode a verify step under sampling uses.  logits fp32 [T, V]
+ * (1 <= T <= 16) -> ids int64 [T]; row r draws with the Philox counter (seq_row, n0 + r, 0, 0), so it equals fvhd_op_dec_sample on that row
+ * alone (B = 1) at n = n0 + r when seq_row = 0.  u_override / info: as above, indexed by r.  state_last (int64 [T]), state_position (int64
+ * [T]) and state_length (int): each NULL or device memory that goes into the launch where a decode step passes its last ids, positions and
+ * the length to advance - this mode writes none of them.  Eager calls only. */
+int fvhd_op_dec_sample_rows(fvhd_stream_t stream, const float* logits, int T, int V, float temperature, int top_k, float top_p,
+                            unsigned long long seed, int seq_row, int n0, const float* u_override, int64_t* ids, float* info,
+                            int64_t* state_last, int64_t* state_position, int* state_length);
 
 /* single ops of the decode step (unit-test entry points); B in [1, 64]; K % 128 == 0; `splits` = workgroups per output tile along K
  * (partial: fp32 scratch [splits][N * 16 * ceil(B / 16)], counters: int [ceil(N / 64)] ZEROED before the first call - each launch leaves them zero)
@@ -726,7 +737,7 @@ int fvhd_op_dec_logits_process(fvhd_stream_t stream, float* logits, int B, int V
  * workgroup per kv head move them into cache slots [length, length + T), loads every key block once per wave for the wave's queries, and keeps,
  * per query, the key slices, the 64-key blocks per wave, the online-softmax updates, the j order of P.V and the wave and slice combines of
  * the single-query kernel.
- * Scope: the batch of fvhd_llm_start is 1; greedy only.  Refused with an error that names the reason: sampling on, logits processors on (the
+ * Scope: the batch of fvhd_llm_start is 1; greedy only unless fvhd_llm_set_verify_sampling (below) is on.  Refused with an error that names the reason: sampling on, logits processors on (the
  * verify step does not maintain their token history), a started batch above 1, rows outside [2, max_rows].  bf16 and e4m3 weights.
  * Prompt lookup (what transformers offers as prompt_lookup_num_tokens; no draft model): the token buffer holds the optional lookup ids
  * (e.g. the prompt's input_ids; negative placeholders such as an image token are allowed, they never match and never become a draft) and
@@ -758,6 +769,26 @@ int fvhd_llm_lookup_begin(fvhd_llm* ctx, const int64_t* lookup_ids, int n_lookup
 int fvhd_llm_lookup_step(fvhd_llm* ctx, int rows, int max_ngram, fvhd_stream_t stream);
 /* synchronises the device, then (each optional): tokens written to tokens_out, the finished flag, verify steps run and tokens they emitted */
 int fvhd_llm_lookup_state(fvhd_llm* ctx, int* written, int* finished, int* steps, int* tokens);
+/* Verify and lookup steps under sampling (added under 510; off by default, and then every call above is refused under sampling with the
+ * words it always was, and a greedy step enqueues what it did, launch for launch).  With it on and fvhd_llm_set_sampling on, a step keeps
+ * its T fp32 logits rows (logits_out, else scratch that fvhd_llm_spec_reserve makes only when this setting or fvhd_llm_set_logprobs is on)
+ * and replaces the argmax reduce by the sampler on the T rows of the one sequence: row t draws with the Philox counter (0, length + 1 + t,
+ * 0, 0) - the counter of the decode step that feeds the same token - on logits that have that step's bits, so ids[t] IS the token that
+ * step would have sampled.  The accept launch is what it was: a draft is kept when it equals the draw at its position, the first draw that
+ * differs is emitted and ends the run.  Against a draft that puts probability 1 on one token that is speculative sampling, exactly: the
+ * emitted tokens are those of the sequential sampled run with the same seed, in fewer steps.  Temperature / top-k / top-p / seed are read
+ * when the step enqueues.  Logits processors and constraints stay refused.  Switching it on when a scratch exists may allocate and
+ * synchronise. */
+int fvhd_llm_set_verify_sampling(fvhd_llm* ctx, int on);
+/* Log-probabilities of a lookup generation (added under 510), greedy or sampled: call behind fvhd_llm_lookup_begin with fvhd_llm_set_logprobs
+ * on since before fvhd_llm_start (started without a logits_out).  token_logprobs_out fp32 [max_new_tokens], top_ids_out int64
+ * [max_new_tokens, top_n], top_logprobs_out fp32 [max_new_tokens, top_n] on the device (the last two NULL for top_n = 0), aligned with
+ * tokens_out.  The call writes entry 0 - the launch of fvhd_llm_logprobs on the logits fvhd_llm_start left.  Every later fvhd_llm_lookup_step
+ * enqueued while the setting is on keeps its T fp32 logits rows, runs the logprobs launch at B = T on them with the step's ids (the values
+ * are taken before temperature / top-k / top-p; the slice count depends on the vocabulary alone and each row is merged by its own last
+ * workgroup, so row t has the values of the plain step's launch, bit for bit) and, behind the accept, one small launch copies the rows the
+ * step emitted to the arrays at the offset of its first token.  No host work: the step still captures into one graph. */
+int fvhd_llm_lookup_logprobs(fvhd_llm* ctx, int top_n, float* token_logprobs_out, int64_t* top_ids_out, float* top_logprobs_out, fvhd_stream_t stream);
 /* the three new operations on their own (tests), on plain device pointers.
  * fvhd_op_dec_attention_multi: q [T, n_heads * head_dim] bf16, k_cache / v_cache [n_kv_heads][capacity][head_dim] of the one sequence,
  * k_staged / v_staged [T][n_kv_heads][head_dim] = the keys / values of slots *length .. *length + T - 1, key_valid uint8 [capacity] (bytes

@@ -204,6 +204,12 @@ def _declare(lib) -> None:
             "fvhd_llm_set_constraint": (ci, [vp, vp, ci, vp, vp, ci, vp, ci]),
             "fvhd_llm_constraint_state": (ci, [vp, vp, vp, ci]),
         })
+    if hasattr(lib, "fvhd_llm_set_verify_sampling"):   # added under 510: a 510 library built before them loads without; lookup_sample_lib() then names the rebuild
+        sig.update({
+            "fvhd_llm_set_verify_sampling": (ci, [vp, ci]),
+            "fvhd_llm_lookup_logprobs": (ci, [vp, ci, vp, vp, vp, vp]),
+            "fvhd_op_dec_sample_rows": (ci, [vp, vp, ci, ci, cf, ci, cf, C.c_ulonglong, ci, ci, vp, vp, vp, vp, vp, vp]),
+        })
     del fp, cl
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)     # AttributeError here = the .so does not export what fvhd.h declares
@@ -348,6 +354,18 @@ def constraint_lib():
     if not hasattr(lib, "fvhd_op_dec_constrain"):
         raise FvhdError(f"{LIB_PATH} (ABI version {lib.fvhd_version()}) was built before constrained decoding (fvhd_llm_set_constraint, "
                         "fvhd_llm_constraint_state, fvhd_op_dec_constrain, ...) - rebuild the library (`python -m ml_fastvlm_amd.build`)")
+    return lib
+
+
+def lookup_sample_lib():
+    """load(), for prompt-lookup decoding under sampling and with log-probabilities (fvhd_llm_set_verify_sampling, fvhd_llm_lookup_logprobs,
+    fvhd_op_dec_sample_rows): the entry points were added under FVHD_VERSION 510, so a library built before them reports the same number
+    and loads; this says so instead of an AttributeError."""
+    lib = lookup_lib()
+    if not hasattr(lib, "fvhd_llm_set_verify_sampling"):
+        raise FvhdError(f"{LIB_PATH} (ABI version {lib.fvhd_version()}) was built before prompt-lookup decoding under sampling "
+                        "(fvhd_llm_set_verify_sampling, fvhd_llm_lookup_logprobs, fvhd_op_dec_sample_rows) - rebuild the library "
+                        "(`python -m ml_fastvlm_amd.build`)")
     return lib
 
 

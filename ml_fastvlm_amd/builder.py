@@ -93,7 +93,8 @@ def encode_images(vision_tower, mm_projector, images):
 
 
 def install_into_llava(splice: bool = False, prefill: bool = False, prefill_any_dtype: bool = False, generate: bool = False,
-                       llm_weights: str = "bf16", beam_search: bool = False, logits_processors: bool = False, constraints: bool = False) -> None:
+                       llm_weights: str = "bf16", beam_search: bool = False, logits_processors: bool = False, constraints: bool = False,
+                       prompt_lookup: bool = False) -> None:
     """Make an unmodified `llava` package (the reference) build and call the MI355X tower; splice=True also routes
     `prepare_inputs_labels_for_multimodal` through the GPU splice (needs the embeddings on a HIP device); prefill=True also runs the
     PREFILL step of `LlavaQwen2ForCausalLM.forward` (`llava_qwen.py:92-103`: the first forward of `generate`, on `inputs_embeds`
@@ -112,6 +113,9 @@ def install_into_llava(splice: bool = False, prefill: bool = False, prefill_any_
     `constraint_start=` and runs them on the library for num_beams = 1 (`Qwen2Generator.set_constraint`); a call that must fall back, or
     asks for beam search, raises instead of dropping the constraint.  Without the flag nothing about the patched call changes, and
     transformers' own `prefix_allowed_tokens_fn` keeps falling back either way.
+    prompt_lookup=True (with generate=True) lets it take the library for transformers' `prompt_lookup_num_tokens=K` (1 .. 15; one prompt,
+    num_beams = 1, no processor, no constraint): `Qwen2Generator.lookup_greedy`, or `.lookup_sample` under do_sample - the tokens of the call
+    without the keyword, in fewer steps; without the flag the keyword keeps falling back.
     llm_weights: "bf16" (the default), "fp8_e4m3" or "mxfp4" - the storage of the LLM's packed matrices in the library's prefill / decode contexts
     (`Qwen2Prefill.from_hf(weights=...)`), recorded on `LlavaQwen2ForCausalLM` for `prefill_context` to read."""
     from ._lib import weight_format_code
@@ -149,6 +153,8 @@ def install_into_llava(splice: bool = False, prefill: bool = False, prefill_any_
         extra = dict(logits_processors=True) if logits_processors else {}
         if constraints:
             extra["constraints"] = True
+        if prompt_lookup:
+            extra["prompt_lookup"] = True
         lq.LlavaQwen2ForCausalLM.generate = _make_library_generate(getattr(cur, "_fvhd_orig", cur), beam_search=beam_search, **extra)
 
 
@@ -294,7 +300,7 @@ def generate(model, input_ids, images=None, image_sizes=None, attention_mask=Non
     prompt_lookup_num_tokens=K (1 .. 15, one prompt per call): prompt-lookup decoding (`Qwen2Generator.lookup_greedy`) - the same tokens, K
     drafts from n-gram matches (n <= max_matching_ngram_size) in `input_ids` and the generated tokens verified per step.
     logprobs=n (0 .. 16): -> (tokens, `GenerationLogprobs`): every generated token's log-probability and the n most likely tokens of its step
-    (`Qwen2Generator.greedy`); not with prompt_lookup_num_tokens.
+    (`Qwen2Generator.greedy`, or `Qwen2Generator.lookup_greedy` with prompt_lookup_num_tokens: the same values in fewer steps).
     constraint: a `ml_fastvlm_amd.constraints.TokenAutomaton` the new tokens of every row must follow, from constraint_start (None: state 0;
     an int; one state per row, -1 = unconstrained) - `Qwen2Generator.greedy(constraint=...)`; not with prompt_lookup_num_tokens."""
     from .qwen2_decode import normalize_logprobs
@@ -304,9 +310,6 @@ def generate(model, input_ids, images=None, image_sizes=None, attention_mask=Non
                          "verify step does not advance the rows' automaton states")
     if constraint is None and constraint_start is not None:
         raise ValueError("ml_fastvlm_amd.generate: constraint_start is given without a constraint")
-    if logprobs is not None and prompt_lookup_num_tokens is not None:
-        raise ValueError("ml_fastvlm_amd.generate: logprobs is not implemented under prompt-lookup decoding (prompt_lookup_num_tokens) - a verify step "
-                         "chooses several tokens per launch")
     if do_sample:
         raise NotImplementedError("ml_fastvlm_amd.generate: do_sample=True (sampling) is not implemented - greedy decoding only; "
                                   "Qwen2Generator.step exposes the logits for sampling in torch")
@@ -321,6 +324,9 @@ def generate(model, input_ids, images=None, image_sizes=None, attention_mask=Non
         raise NotImplementedError(f"ml_fastvlm_amd.generate: the generation setting {k}={v!r} is not implemented - greedy decoding only")
     lookup = None
     if prompt_lookup_num_tokens is not None:
+        if not isinstance(input_ids, torch.Tensor) or input_ids.dim() != 2:
+            raise ValueError("ml_fastvlm_amd.generate: prompt-lookup decoding (prompt_lookup_num_tokens) looks its drafts up in input_ids - pass them "
+                             f"as an int64 tensor [1, n] (got {type(input_ids).__name__})")
         if input_ids.shape[0] != 1:
             raise ValueError(f"ml_fastvlm_amd.generate: prompt_lookup_num_tokens takes ONE prompt per call (got a batch of {input_ids.shape[0]})")
         lookup = dict(prompt_lookup_num_tokens=int(prompt_lookup_num_tokens), max_matching_ngram_size=int(max_matching_ngram_size), lookup_ids=input_ids)
@@ -364,8 +370,9 @@ def _generate_on_library(model, input_ids, images, image_sizes, attention_mask, 
     """the body shared by `generate`, `beam_generate` and `_make_library_generate`: the multimodal splice (or the token embedding), then the
     prefill and every decode step on the library - `Qwen2Generator.greedy`, `.sample(**sampling)` or `.beam_search(**beam)`; processors:
     None or the logits-processor keywords of greedy / sample (repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens);
-    logprobs: None or greedy's / sample's keyword (they then return (tokens, GenerationLogprobs)) - not for beam search or lookup decoding"""
-    if logprobs is not None and (beam is not None or lookup is not None):
+    logprobs: None or greedy's / sample's keyword (they then return (tokens, GenerationLogprobs)) - not for beam search; lookup: None or the
+    keywords of `.lookup_greedy` (one prompt), with sampling those of `.lookup_sample`"""
+    if logprobs is not None and beam is not None:
         raise ValueError("logprobs is implemented for greedy decoding and sampling only (beam search has return_scores)")
     if constraint is not None and (beam is not None or lookup is not None):
         raise ValueError("a constraint is implemented for greedy decoding and sampling only (num_beams = 1, no prompt lookup): beam search and "
@@ -381,10 +388,13 @@ def _generate_on_library(model, input_ids, images, image_sizes, attention_mask, 
         gen = generator_context(model, B * beam["num_beams"], T + max_new_tokens)
         return gen.beam_search(inputs_embeds, attention_mask, position_ids, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id,
                                pad_token_id=pad_token_id, **beam)
-    if lookup is not None:                                    # greedy, one prompt: the cache also holds the drafts of the last step
+    if lookup is not None:                                    # one prompt: the cache also holds the drafts of the last step
         gen = generator_context(model, B, T + max_new_tokens + lookup["prompt_lookup_num_tokens"])
+        if sampling is not None:
+            return gen.lookup_sample(inputs_embeds, attention_mask, position_ids, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id,
+                                     pad_token_id=pad_token_id, logprobs=logprobs, **sampling, **lookup)
         return gen.lookup_greedy(inputs_embeds, attention_mask, position_ids, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id,
-                                 pad_token_id=pad_token_id, **lookup)
+                                 pad_token_id=pad_token_id, logprobs=logprobs, **lookup)
     gen = generator_context(model, B, T + max_new_tokens)
     processors = processors or {}
     if sampling is None:
@@ -661,7 +671,7 @@ _GENERATE_ARGS = ("generation_config", "logits_processor", "stopping_criteria", 
 _PROCESSORS = ("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens", "suppress_tokens")
 
 
-def _library_generate_settings(model, kwargs, beam_search: bool = False, processors: bool = False):
+def _library_generate_settings(model, kwargs, beam_search: bool = False, processors: bool = False, prompt_lookup: bool = False, batch=None):
     """transformers' own resolution of a generate(**kwargs) call (`_prepare_generation_config`, which generate itself calls: its global
     defaults such as top_k = 50, the model's generation_config, then the call's arguments) -> (settings, None) when the library can run
     it, (None, reason) when it cannot.  settings: max_new_tokens, eos_token_id, pad_token_id, `sampling` (None = greedy, else the
@@ -669,7 +679,10 @@ def _library_generate_settings(model, kwargs, beam_search: bool = False, process
     Qwen2Generator.beam_search: num_beams, length_penalty, early_stopping, num_return_sequences).  processors=True: with num_beams = 1,
     repetition_penalty, no_repeat_ngram_size, min_new_tokens and suppress_tokens within the library's limits (16 EOS ids, 256 suppressed
     ids, ids inside the vocabulary) no longer disqualify the call, and settings gains `processors`: None when all are off, else those four
-    keywords of Qwen2Generator.greedy / .sample."""
+    keywords of Qwen2Generator.greedy / .sample.  prompt_lookup=True: transformers' own `prompt_lookup_num_tokens=K` no longer disqualifies
+    the call when 1 <= K <= 15, num_beams = 1, no processor is on and `batch` (the number of prompts; None = unknown, not checked) is 1;
+    settings then gains `lookup`: None without the keyword, else prompt_lookup_num_tokens and max_matching_ngram_size (the config's, 2 when it
+    has none) for Qwen2Generator.lookup_greedy / .lookup_sample."""
     for k in _GENERATE_ARGS:
         if kwargs.get(k) is not None:
             return None, f"{k} is given"
@@ -687,6 +700,8 @@ def _library_generate_settings(model, kwargs, beam_search: bool = False, process
         if beams is not None and k in ("num_beams", "num_return_sequences"):
             continue
         if processors and single and k in _PROCESSORS:
+            continue
+        if prompt_lookup and k == "prompt_lookup_num_tokens":
             continue
         if v is not None and v not in off:
             return None, f"{k}={v!r}"
@@ -723,6 +738,24 @@ def _library_generate_settings(model, kwargs, beam_search: bool = False, process
     settings = dict(max_new_tokens=int(gc.max_new_tokens), eos_token_id=gc.eos_token_id, pad_token_id=gc.pad_token_id, sampling=sampling, beam=beam)
     if processors:
         settings["processors"] = proc
+    if prompt_lookup:
+        K = getattr(gc, "prompt_lookup_num_tokens", None)
+        settings["lookup"] = None
+        if K is not None:
+            what = f"prompt_lookup_num_tokens={K!r}"
+            if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= 15:
+                return None, f"{what} (the library verifies 1 .. 15 drafts per step)"
+            if beam is not None:
+                return None, f"{what} with num_beams={beams} (prompt-lookup decoding runs with num_beams = 1)"
+            if proc is not None:
+                return None, f"{what} with logits processors {sorted(proc)} (the verify step does not maintain their token history)"
+            if batch is not None and batch != 1:
+                return None, f"{what} with a batch of {batch} (prompt-lookup decoding takes one prompt per call)"
+            ngram = getattr(gc, "max_matching_ngram_size", None)
+            ngram = 2 if ngram is None else ngram                    # transformers' own default
+            if isinstance(ngram, bool) or not isinstance(ngram, int) or not 1 <= ngram <= 16:
+                return None, f"{what} with max_matching_ngram_size={ngram!r} (the library matches n-grams of 1 .. 16 tokens)"
+            settings["lookup"] = dict(prompt_lookup_num_tokens=K, max_matching_ngram_size=ngram)
     return settings, None
 
 
@@ -732,7 +765,8 @@ def _batch_reason(batch: int):
     return f"batch {batch} > {MAX_DECODE_BATCH}" if batch > MAX_DECODE_BATCH else None
 
 
-def _make_library_generate(orig_generate, beam_search: bool = False, logits_processors: bool = False, constraints: bool = False):
+def _make_library_generate(orig_generate, beam_search: bool = False, logits_processors: bool = False, constraints: bool = False,
+                           prompt_lookup: bool = False):
     """`LlavaQwen2ForCausalLM.generate` (`llava_qwen.py:106-143`) on the library: the same argument handling (position_ids / attention_mask
     popped, inputs_embeds refused), the settings resolved as transformers resolves them (`_library_generate_settings`), then the
     multimodal splice and `Qwen2Generator.greedy` / `.sample` on `generator_context(model, ...)`.  It takes the library only for greedy or
@@ -747,7 +781,10 @@ def _make_library_generate(orig_generate, beam_search: bool = False, logits_proc
     keep falling back.  constraints=True: the call may carry `constraint=` (a `ml_fastvlm_amd.constraints.TokenAutomaton`) and
     `constraint_start=`; they are popped and run on the library (`Qwen2Generator.set_constraint`, num_beams = 1).  The reference's generate
     knows no such argument, so a constrained call that cannot run on the library raises with the reason instead of falling back; without
-    the flag the keywords are not looked at.  `prefix_allowed_tokens_fn` keeps falling back."""
+    the flag the keywords are not looked at.  `prefix_allowed_tokens_fn` keeps falling back.  prompt_lookup=True: transformers' own
+    `prompt_lookup_num_tokens=K` (1 .. 15, with `max_matching_ngram_size` when set) runs `Qwen2Generator.lookup_greedy` / `.lookup_sample` for
+    one prompt with num_beams = 1, no processor and no constraint - the same tokens as without the keyword, in fewer steps; `inputs` are the
+    lookup ids (the image placeholder is negative and never matches).  Anything else, or the flag off, falls back as before."""
     def generate(self, inputs=None, images=None, image_sizes=None, **kwargs):
         if "inputs_embeds" in kwargs:                            # as the reference (llava_qwen.py:120-121)
             raise NotImplementedError("`inputs_embeds` is not supported")
@@ -756,8 +793,15 @@ def _make_library_generate(orig_generate, beam_search: bool = False, logits_proc
             constraint, constraint_start = kwargs.pop("constraint", None), kwargs.pop("constraint_start", None)
             if constraint is None and constraint_start is not None:
                 raise ValueError("generate: constraint_start is given without a constraint")
+        extra = dict(processors=True) if logits_processors else {}
+        if prompt_lookup:
+            extra.update(prompt_lookup=True, batch=None if inputs is None else inputs.shape[0])
         settings, reason = _library_generate_settings(self, {k: v for k, v in kwargs.items() if k not in ("position_ids", "attention_mask")},
-                                                      beam_search=beam_search, **(dict(processors=True) if logits_processors else {}))
+                                                      beam_search=beam_search, **extra)
+        lookup = settings.get("lookup") if settings is not None else None
+        if lookup is not None and (inputs is None or constraint is not None):
+            settings, reason = None, (f"prompt_lookup_num_tokens={lookup['prompt_lookup_num_tokens']} " +
+                                      ("without input_ids" if inputs is None else "with a constraint (the verify step does not advance its states)"))
         lm_w = self.lm_head.weight
         rows = 0 if inputs is None else inputs.shape[0] * (settings["beam"]["num_beams"] if settings is not None and settings["beam"] else 1)
         if settings is not None and inputs is not None and _batch_reason(rows) is not None:
@@ -779,7 +823,8 @@ def _make_library_generate(orig_generate, beam_search: bool = False, logits_proc
             return _generate_on_library(self, inputs, images, image_sizes, kwargs.get("attention_mask"), kwargs.get("position_ids"),
                                         settings["max_new_tokens"], settings["eos_token_id"], settings["pad_token_id"], settings["sampling"],
                                         settings["beam"], **(dict(processors=settings["processors"]) if settings.get("processors") else {}),
-                                        **(dict(constraint=constraint, constraint_start=constraint_start) if constraint is not None else {}))
+                                        **(dict(constraint=constraint, constraint_start=constraint_start) if constraint is not None else {}),
+                                        **(dict(lookup=dict(lookup, lookup_ids=inputs)) if lookup is not None else {}))
     generate._fvhd_generate = True
     generate._fvhd_orig = orig_generate
     return generate

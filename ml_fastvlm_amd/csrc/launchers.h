@@ -109,6 +109,7 @@ int fvhd_launch_spec_embed(hipStream_t st, const int64_t* draft, const int64_t* 
 int fvhd_launch_spec_attention(hipStream_t st, const void* q, void* kc, void* vc, const void* ks, const void* vs, const unsigned char* key_valid, void* out,
                                int T, int nh, int nkv, int hd, int cap, const int* len, int S, int chunk, float* part, int* cnt, const int* status);
 int fvhd_launch_spec_accept(hipStream_t st, const SpecAcceptArgs* a);
+int fvhd_launch_spec_logprobs_copy(hipStream_t st, const SpecLogprobsArgs* a);
 int fvhd_launch_spec_begin(hipStream_t st, const int64_t* lookup, int n, const int64_t* last, int* seq, int64_t* out, int* words, int limit,
                            const SpecEosList* eos);
 // llm_score.hip (the shape is valid when fvhd_lm_score_plan(M, V, K) != 0; scratch: fvhd_lm_score_scratch_bytes, 16-byte aligned)

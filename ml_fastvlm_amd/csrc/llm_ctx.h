@@ -108,6 +108,23 @@ struct __attribute__((visibility("default"))) fvhd_llm {     // (its inline cons
     int64_t* sp_out = nullptr;             // fvhd_llm_lookup_begin: the caller's output tokens [sp_out_cap]
     int sp_out_cap = 0;
     bool sp_begun = false;
+    // fvhd_llm_set_verify_sampling: with it on, verify and lookup steps follow the sampling settings (row t draws with the counter of the
+    // plain step at its position) instead of being refused under them.  `spx`: what such a step, or one that keeps log-probabilities,
+    // needs beyond `spec` - the fp32 logits [spec_rows][V], the logprobs launch's scratch and outputs for spec_rows rows, the accept's
+    // emitted count - in an allocation of its own, made only when either is asked for (a greedy user's footprint is what it was); one
+    // that a capturing stream used is retired when it must grow, like the workspace
+    int verify_sampling = 0;
+    char* spx = nullptr;
+    int spx_rows = 0;
+    bool spx_captured = false;
+    float *spx_logits = nullptr, *spx_tok = nullptr, *spx_top = nullptr;
+    int64_t* spx_ids = nullptr;
+    char* spx_lp_ws = nullptr;
+    int* spx_emitted = nullptr;
+    // fvhd_llm_lookup_logprobs: the output arrays of the lookup generation (sp_lp_n < 0: none registered; fvhd_llm_lookup_begin resets it)
+    int sp_lp_n = -1;
+    float *sp_lp_tok = nullptr, *sp_lp_top = nullptr;
+    int64_t* sp_lp_ids = nullptr;
     // fvhd_llm_cache_rewind / fvhd_llm_cache_gather set it: last_ids (the ids "the previous step chose") then belong to the rows as they were
     // before the call.  Cleared by fvhd_llm_start, fvhd_llm_extend and fvhd_llm_decode with explicit token_ids; while it is set every call
     // that would feed last_ids is refused when it enqueues (a captured step replays as captured)

@@ -62,6 +62,9 @@ struct DecSampleArgs {
     int64_t* posv = nullptr;       // non-NULL: positions += 1
     int* len_advance = nullptr;    // non-NULL: *len_advance += 1 once every row (of the last block) has read n
     const int* status = nullptr;
+    int seq_rows = 0;              // 1: the B <= 16 rows are consecutive positions of ONE sequence (a verify step, llm_spec.hip): logits, ids_out,
+    int seq_row = 0;               // info and u_override are indexed by the row r, the Philox counter is (seq_row, n + r, 0, 0) - the counter of
+                                   // the plain step at that position; the launch writes ids_out / info only, never last, posv or the length
 };
 
 // Arguments of the KV-cache reorder (llm_beam.hip): row r of every layer's K / V (slots [0, *len)), of the mask and of the positions = row src[r].
@@ -132,6 +135,22 @@ struct SpecAcceptArgs {
     unsigned char* key_valid = nullptr;
     int cap = 0;
     const int* gate = nullptr;     // non-NULL: the launch does nothing while *gate != 0
+};
+
+// Arguments of the log-probability copy behind the accept of a lookup step: the rows the step emitted go from the step's scratch to the
+// generation's arrays at the offset of its first emitted token (read from the accept's words on the device)
+struct SpecLogprobsArgs {
+    const float* tok = nullptr;    // the step's scratch: [T], [T][n], [T][n]
+    const int64_t* ids = nullptr;
+    const float* top = nullptr;
+    int n = 0;                     // top_n, 0 .. 16
+    const int* emitted = nullptr;  // the accept's count of this step (1 .. T)
+    const int* words = nullptr;    // SPEC_W_WRITTEN behind the accept = the offset of the first emitted token + emitted
+    float* out_tok = nullptr;      // the generation's arrays: [out_cap], [out_cap][n], [out_cap][n]
+    int64_t* out_ids = nullptr;
+    float* out_top = nullptr;
+    int out_cap = 0;
+    const int* gate = nullptr;     // the step's gate word
 };
 
 // Constrained decoding (llm_constrain.hip): the automaton's CSR tables, the rows' states and the step's fed ids

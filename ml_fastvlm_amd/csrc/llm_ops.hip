@@ -325,26 +325,46 @@ int fvhd_op_quantize_e4m3(fvhd_stream_t st, const void* W, int N, int K, void* c
 }
 
 // the sampler on its own: a process-wide workspace, allocated (and its counters zeroed) on first use - eager calls only
-int fvhd_op_dec_sample(fvhd_stream_t st, const float* logits, int B, int V, float temperature, int top_k, float top_p, unsigned long long seed, int n,
-                       const float* u_override, int64_t* ids, float* info)
+static int op_sample(const char* who, fvhd_stream_t st, DecSampleArgs& a)
 {
-    if (!logits || !ids) return lfail("fvhd_op_dec_sample: NULL pointer");
-    if (B < 1 || B > 16 || V < 1) return lfail("fvhd_op_dec_sample: needs 1 <= B <= 16 and V >= 1");
-    if (const char* e = sampling_error(temperature, top_k, top_p)) return lfail(std::string("fvhd_op_dec_sample: ") + e);
+    const std::string w(who);
+    if (!a.logits || !a.ids_out) return lfail(w + ": NULL pointer");
+    if (a.B < 1 || a.B > 16 || a.V < 1) return lfail(w + ": needs 1 <= B <= 16 and V >= 1");
+    if (const char* e = sampling_error(a.temperature, a.top_k, a.top_p)) return lfail(w + ": " + e);
     static char* ws[64] = {};
     int dev = 0;
     hipError_t he = hipGetDevice(&dev);
     if (he != hipSuccess) return lhip("hipGetDevice", he);
-    if (dev < 0 || dev >= 64) return lfail("fvhd_op_dec_sample: device index out of range");
+    if (dev < 0 || dev >= 64) return lfail(w + ": device index out of range");
     if (!ws[dev]) {
         const size_t bytes = fvhd_dec_sample_ws_bytes();
         if ((he = hipMalloc((void**)&ws[dev], bytes)) != hipSuccess) { ws[dev] = nullptr; return lhip("hipMalloc(sampler workspace)", he); }
         if ((he = hipMemset(ws[dev], 0, bytes)) != hipSuccess) return lhip("hipMemset(sampler workspace)", he);
     }
+    return lret(who, fvhd_launch_dec_sample((hipStream_t)st, &a, ws[dev]));
+}
+
+int fvhd_op_dec_sample(fvhd_stream_t st, const float* logits, int B, int V, float temperature, int top_k, float top_p, unsigned long long seed, int n,
+                       const float* u_override, int64_t* ids, float* info)
+{
     DecSampleArgs a;
     a.logits = logits; a.B = B; a.V = V; a.temperature = temperature; a.top_k = top_k; a.top_p = top_p; a.seed = seed; a.n_add = n;
     a.u_override = u_override; a.ids_out = ids; a.info = info;
-    return lret("fvhd_op_dec_sample", fvhd_launch_dec_sample((hipStream_t)st, &a, ws[dev]));
+    return op_sample("fvhd_op_dec_sample", st, a);
+}
+
+// the T rows of ONE sequence (the verify step's mode): row r draws with the counter (seq_row, n0 + r).  state_last / state_position /
+// state_length go into the launch where a decode step passes last ids, positions and the length to advance: the mode must leave them alone
+int fvhd_op_dec_sample_rows(fvhd_stream_t st, const float* logits, int T, int V, float temperature, int top_k, float top_p, unsigned long long seed,
+                            int seq_row, int n0, const float* u_override, int64_t* ids, float* info, int64_t* state_last, int64_t* state_position,
+                            int* state_length)
+{
+    if (seq_row < 0 || n0 < 0) return lfail("fvhd_op_dec_sample_rows: seq_row and n0 must be >= 0");
+    DecSampleArgs a;
+    a.logits = logits; a.B = T; a.V = V; a.temperature = temperature; a.top_k = top_k; a.top_p = top_p; a.seed = seed; a.n_add = n0;
+    a.u_override = u_override; a.ids_out = ids; a.info = info; a.seq_rows = 1; a.seq_row = seq_row;
+    a.last = state_last; a.posv = state_position; a.len_advance = state_length;
+    return op_sample("fvhd_op_dec_sample_rows", st, a);
 }
 
 int fvhd_op_dec_logprobs(fvhd_stream_t st, const float* logits, const int64_t* ids, int B, int V, int top_n, float* token_logprob_out,

@@ -20,6 +20,8 @@
 //                       fixed order), u from Philox4x32-10, and the inverse CDF in TOKEN-INDEX order: the smallest kept index whose
 //                       prefix mass is > u * Z (the last kept token if rounding finds none).  Same distribution as a draw in sorted
 //                       order, no sort.  Then the ids, the optional info row, and - behind every row - the advance of positions / length.
+// DecSampleArgs.seq_rows: the rows are T <= 16 consecutive positions of ONE sequence (the verify step of llm_spec.hip).  Row r draws with the
+// Philox counter (seq_row, n + r, 0, 0), the counter of the plain step at that position, and the launch writes the ids (and info) only.
 // Everything is deterministic: the same logits, settings, seed and n give the same id, eager or replayed.
 #include "fvhd_common.h"
 #include "launchers.h"      // (with llm_decode.h: the argument structs)
@@ -353,8 +355,9 @@ __global__ __launch_bounds__(256) void dec_sample_draw_kernel(const DecSampleArg
         if (a.u_override) {
             u = a.u_override[row];
         } else {
-            const int n = (a.len ? *a.len : 0) + a.n_add;
-            u = (float)(philox_x0((unsigned)row, (unsigned)n, 0u, 0u, (unsigned)a.seed, (unsigned)(a.seed >> 32)) >> 8) * 0x1p-24f;
+            // the rows of one sequence: row r draws with the counter of the plain step at its position
+            const int n = (a.len ? *a.len : 0) + a.n_add + (a.seq_rows ? row : 0);
+            u = (float)(philox_x0((unsigned)(a.seq_rows ? a.seq_row : row), (unsigned)n, 0u, 0u, (unsigned)a.seed, (unsigned)(a.seed >> 32)) >> 8) * 0x1p-24f;
         }
         const float target = u * Z;
         float cum = 0.f;
@@ -401,9 +404,9 @@ __global__ __launch_bounds__(256) void dec_sample_draw_kernel(const DecSampleArg
     __syncthreads();
     if (tid == 0) {
         const int64_t id = pick_id < 0 ? 0 : pick_id;
-        if (a.last) a.last[row] = id;
+        if (a.last && !a.seq_rows) a.last[row] = id;
         if (a.ids_out) a.ids_out[row] = id;
-        if (a.posv) a.posv[row] += 1;
+        if (a.posv && !a.seq_rows) a.posv[row] += 1;
         if (a.info) {
             a.info[row * 4 + 0] = theta == 0u ? -INFINITY : key_value(theta);
             a.info[row * 4 + 1] = (float)kept_s;
@@ -412,7 +415,7 @@ __global__ __launch_bounds__(256) void dec_sample_draw_kernel(const DecSampleArg
         }
     }
     // every row has read n (the earlier blocks of a wide batch ran before this launch): the last row to get here advances the length
-    if (a.len_advance && arrive_last(w.cnt + BMAX, gridDim.y, &flag) && tid == 0) *a.len_advance += 1;
+    if (a.len_advance && !a.seq_rows && arrive_last(w.cnt + BMAX, gridDim.y, &flag) && tid == 0) *a.len_advance += 1;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -422,6 +425,7 @@ extern "C" int fvhd_launch_dec_sample(hipStream_t st, const DecSampleArgs* a, vo
 {
     if (!a->logits || !ws || a->B < 1 || a->B > 4 * BMAX || a->V < 1 || !(a->temperature > 0.f) || a->top_k < 0 || !(a->top_p >= 0.f && a->top_p <= 1.f))
         return (int)hipErrorInvalidValue;
+    if (a->seq_rows && (a->B > BMAX || !a->ids_out)) return (int)hipErrorInvalidValue;      // one block of the workspace; the ids are its output
     const SampleWs w = carve(ws);
     const int S = a->V >= SMAX * 2048 ? SMAX : (a->V + 2047) / 2048;
     const int levels = 4 * ((a->top_k > 0 && a->top_k < a->V) + (a->top_p < 1.f));

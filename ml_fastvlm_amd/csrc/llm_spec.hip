@@ -360,6 +360,21 @@ __global__ __launch_bounds__(64) void spec_accept_kernel(const SpecAcceptArgs a)
     for (int k = sL + se + threadIdx.x; k < min(sL + T, a.cap); k += 64) a.key_valid[k] = 0;
 }
 
+// One workgroup behind the accept of a lookup step: thread (i, k) = (tid / 16, tid % 16) moves entry k of emitted row i.  The accept has
+// advanced SPEC_W_WRITTEN by the count it left in *emitted, so the step's first token sits at written - emitted.
+__global__ __launch_bounds__(256) void spec_logprobs_copy_kernel(const SpecLogprobsArgs a)
+{
+    if (a.gate && *a.gate) return;
+    const int e = min(max(*a.emitted, 0), 16), first = a.words[SPEC_W_WRITTEN] - e;
+    const int i = threadIdx.x >> 4, k = threadIdx.x & 15, o = first + i;
+    if (i >= e || o < 0 || o >= a.out_cap) return;
+    if (k == 0) a.out_tok[o] = a.tok[i];
+    if (k < a.n) {
+        a.out_ids[(size_t)o * a.n + k] = a.ids[i * a.n + k];
+        a.out_top[(size_t)o * a.n + k] = a.top[i * a.n + k];
+    }
+}
+
 // the token buffer of a lookup generation: the lookup ids (int64 -> int32, negative placeholders kept), then the first token
 __global__ __launch_bounds__(256) void spec_begin_kernel(const int64_t* __restrict__ lookup, int n, const int64_t* last, int* __restrict__ seq, int64_t* out,
                                                          int* words, int limit, const SpecEosList eos)
@@ -419,6 +434,15 @@ extern "C" int fvhd_launch_spec_accept(hipStream_t st, const SpecAcceptArgs* a)
 {
     if (a->T < 2 || a->T > 16 || !a->draft || !a->ids || !a->last || !a->posv || !a->len || !a->key_valid) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(spec_accept_kernel, dim3(1), dim3(64), 0, st, *a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int fvhd_launch_spec_logprobs_copy(hipStream_t st, const SpecLogprobsArgs* a)
+{
+    if (!a->tok || !a->emitted || !a->words || !a->out_tok || a->n < 0 || a->n > 16 || a->out_cap < 1 ||
+        (a->n && (!a->ids || !a->top || !a->out_ids || !a->out_top)))
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(spec_logprobs_copy_kernel, dim3(1), dim3(256), 0, st, *a);
     return (int)hipGetLastError();
 }
 

@@ -95,6 +95,36 @@ void constrain_reset(DecConstrainArgs& a, const fvhd_llm* c)
     std::copy(c->con_start, c->con_start + 64, a.start);
 }
 
+// what a verify step under sampling, or one that keeps log-probabilities, needs beyond fvhd_llm_spec_reserve's scratch (llm_ctx.h `spx`),
+// for the rows that scratch covers.  Kept while it covers them; growing synchronises, so it is refused on a capturing stream.
+int spec_extra_ensure(fvhd_llm* c, const char* who, hipStream_t st)
+{
+    if (c->spx && c->spx_rows >= c->spec_rows) return 0;
+    if (st && is_capturing(st))
+        return lfail(std::string(who) + ": the scratch for the step's logits must grow but the stream is being captured - call fvhd_llm_spec_reserve "
+                     "after fvhd_llm_set_verify_sampling / fvhd_llm_set_logprobs, or run one step before capturing");
+    hipError_t he = hipDeviceSynchronize();
+    if (he != hipSuccess) return lhip("hipDeviceSynchronize", he);
+    if (c->spx) {
+        if (c->spx_captured) c->retired.push_back(c->spx);       // a captured step replays on the old one
+        else (void)hipFree(c->spx);
+    }
+    c->spx = nullptr;
+    c->spx_rows = 0;
+    c->spx_captured = false;
+    const int T = c->spec_rows;
+    Arena a;
+    const size_t o_ws = a.take(fvhd_dec_logprobs_scratch_bytes(T, c->V, 16)), o_logits = a.take((size_t)T * c->V * 4), o_tok = a.take(4 * 16),
+                 o_ids = a.take(8 * 16 * 16), o_top = a.take(4 * 16 * 16), o_emitted = a.take(4);
+    if ((he = hipMalloc((void**)&c->spx, a.off)) != hipSuccess) { c->spx = nullptr; return lhip("hipMalloc(verify step logits scratch)", he); }
+    if ((he = hipMemset(c->spx, 0, a.off)) != hipSuccess) return lhip("hipMemset(verify step logits scratch)", he);      // counters start at zero
+    char* d = c->spx;
+    c->spx_lp_ws = d + o_ws; c->spx_logits = (float*)(d + o_logits); c->spx_tok = (float*)(d + o_tok); c->spx_ids = (int64_t*)(d + o_ids);
+    c->spx_top = (float*)(d + o_top); c->spx_emitted = (int*)(d + o_emitted);
+    c->spx_rows = T;
+    return 0;
+}
+
 int constraint_start_error(const fvhd_llm* c, const char* who, int B)
 {
     if (c->con_n_start == 1 || c->con_n_start >= B) return 0;
@@ -532,8 +562,9 @@ int fvhd_llm_spec_reserve(fvhd_llm* c, int max_rows, int lookup_capacity)
     if (max_rows < 2 || max_rows > 16 || lookup_capacity < 0)
         return lfail("fvhd_llm_spec_reserve: needs 2 <= max_rows <= 16 (the rows of one verify step) and lookup_capacity >= 0");
     if (c->hd != 64 && c->hd != 128) return lfail("fvhd_llm_spec_reserve: the verify step's attention needs head_dim 64 or 128");
-    if (c->spec && c->spec_rows >= max_rows && c->spec_seq_cap >= lookup_capacity + c->dc_cap + 16) return 0;      // covered: kept as it is
     LLM_ON_DEVICE(c);
+    if (c->spec && c->spec_rows >= max_rows && c->spec_seq_cap >= lookup_capacity + c->dc_cap + 16)                  // covered: kept as it is
+        return c->verify_sampling || c->lp_on ? spec_extra_ensure(c, "fvhd_llm_spec_reserve", nullptr) : 0;
     hipError_t he = hipDeviceSynchronize();                      // refused while a stream is being captured (like fvhd_llm_cache_reserve)
     if (he != hipSuccess) return lhip("fvhd_llm_spec_reserve: hipDeviceSynchronize", he);
     const int T = std::max(max_rows, c->spec ? c->spec_rows : 0), H = c->H, I = c->I, nh = c->nh, nkv = c->nkv, hd = c->hd;
@@ -556,6 +587,7 @@ int fvhd_llm_spec_reserve(fvhd_llm* c, int max_rows, int lookup_capacity)
     c->sp_cnt = (int*)(d + o_cnt); c->sp_zero = (int*)(d + o_zero); c->sp_gate = (int*)(d + o_gate); c->sp_words = (int*)(d + o_words);
     c->sp_seq = (int*)(d + o_seq);
     c->spec_rows = T; c->spec_seq_cap = seq_cap;
+    if (c->verify_sampling || c->lp_on) return spec_extra_ensure(c, "fvhd_llm_spec_reserve", nullptr);      // only then: a greedy user's footprint stays
     return 0;
 }
 
@@ -569,7 +601,7 @@ int spec_refusal(const fvhd_llm* c, const char* who, int rows)
     if (c->run_batch != 1) return lfail(w + ": the verify step takes ONE sequence (the batch of fvhd_llm_start is " + std::to_string(c->run_batch) + ")");
     if (rows < 2 || rows > c->spec_rows)
         return lfail(w + ": rows must be in [2, the max_rows of fvhd_llm_spec_reserve = " + std::to_string(c->spec_rows) + "]");
-    if (c->do_sample) return lfail(w + ": sampling is on (fvhd_llm_set_sampling) - the verify step is greedy only: it keeps the drafts the argmax confirms");
+    if (c->do_sample && !c->verify_sampling) return lfail(w + ": sampling is on (fvhd_llm_set_sampling) - the verify step is greedy only: it keeps the drafts the argmax confirms");
     if (processors_on(c))
         return lfail(w + ": logits processors are on (fvhd_llm_set_logits_processors) - the verify step does not maintain their token history");
     if (constraint_on(c))
@@ -577,9 +609,16 @@ int spec_refusal(const fvhd_llm* c, const char* who, int rows)
     return 0;
 }
 
-// one verify step on the drafts at `draft` (device int64 [T - 1]): embed, the decode's launches at B = T, the ids of the T rows
-int spec_enqueue(fvhd_llm* c, const int64_t* draft, int T, float* logits_out, int64_t* ids, int* gate, hipStream_t st)
+// one verify step on the drafts at `draft` (device int64 [T - 1]): embed, the decode's launches at B = T, the ids of the T rows.
+// Under sampling (the opt-in of fvhd_llm_set_verify_sampling; spec_refusal has passed) the rows' ids are the sampler's draws with the
+// counters of the plain steps at their positions; lp_n >= 0: the log-probabilities of the T ids go to the step's scratch (spx_tok ..).
+int spec_enqueue(fvhd_llm* c, const int64_t* draft, int T, float* logits_out, int64_t* ids, int* gate, hipStream_t st, int lp_n = -1)
 {
+    const bool samp = c->do_sample != 0;
+    if ((samp && !logits_out) || lp_n >= 0) {
+        if (int e = spec_extra_ensure(c, "the verify step", st)) return e;
+        if (is_capturing(st)) c->spx_captured = true;
+    }
     const int H = c->H, I = c->I, nh = c->nh, nkv = c->nkv, hd = c->hd, cap = c->dc_cap;
     const char* w = c->wdev;
     const bool q8 = c->wfmt == FVHD_W_E4M3, q4 = c->wfmt == FVHD_W_MXFP4;
@@ -618,8 +657,18 @@ int spec_enqueue(fvhd_llm* c, const int64_t* draft, int T, float* logits_out, in
     }
     DecGemmArgs a = gemm(DEC_EPI_ARGMAX, c->sp_h, (const float*)(w + c->norm_off), -1, FVHD_MAT_LM_HEAD);
     a.logits = logits_out; a.amax_v = c->amax_v; a.amax_i = c->amax_i;
+    if ((samp || lp_n >= 0) && !a.logits) a.logits = c->spx_logits;      // the T fp32 rows the sampler / the logprobs launch read
     LCHECK(fvhd_launch_dec_gemm(st, &a), "verify final norm + lm_head + argmax");
-    LCHECK(fvhd_launch_dec_argmax_finish(st, c->amax_v, c->amax_i, (c->V / 16 + 3) / 4, T, nullptr, ids, nullptr, nullptr, gate), "verify argmax reduce");
+    if (samp) {
+        // row t draws with the counter (0, length + 1 + t): the draw of the decode step that feeds the same token (sa.n_add = 1 there)
+        DecSampleArgs sa = dec_sample_args(c, a.logits, T);
+        sa.seq_rows = 1; sa.seq_row = 0; sa.len = c->len; sa.n_add = 1; sa.ids_out = ids; sa.status = gate;
+        LCHECK(fvhd_launch_dec_sample(st, &sa, c->sws), "verify sampling");
+    } else {
+        LCHECK(fvhd_launch_dec_argmax_finish(st, c->amax_v, c->amax_i, (c->V / 16 + 3) / 4, T, nullptr, ids, nullptr, nullptr, gate), "verify argmax reduce");
+    }
+    if (lp_n >= 0)      // of the logits the choice was made from, before temperature / top-k / top-p, as in fvhd_llm_logprobs
+        LCHECK(fvhd_launch_dec_logprobs(st, a.logits, ids, T, c->V, lp_n, c->spx_tok, c->spx_ids, c->spx_top, c->spx_lp_ws, gate), "verify logprobs");
     return 0;
 }
 
@@ -669,6 +718,37 @@ int fvhd_llm_lookup_begin(fvhd_llm* c, const int64_t* lookup_ids, int n_lookup, 
     LCHECK(fvhd_launch_spec_begin((hipStream_t)stream, lookup_ids, n_lookup, c->last_ids, c->sp_seq, tokens_out, c->sp_words, max_new_tokens, &eos),
            "lookup begin");
     c->sp_out = tokens_out; c->sp_out_cap = max_new_tokens; c->sp_begun = true;
+    c->sp_lp_n = -1;                                             // no log-probability arrays yet: fvhd_llm_lookup_logprobs registers them
+    return 0;
+}
+
+int fvhd_llm_set_verify_sampling(fvhd_llm* c, int on)
+{
+    if (!c) return lfail("fvhd_llm_set_verify_sampling: ctx is NULL");
+    c->verify_sampling = on != 0;
+    if (!on || !c->spec) return 0;                               // (without a scratch yet: fvhd_llm_spec_reserve makes the logits rows)
+    LLM_ON_DEVICE(c);
+    return spec_extra_ensure(c, "fvhd_llm_set_verify_sampling", nullptr);
+}
+
+int fvhd_llm_lookup_logprobs(fvhd_llm* c, int top_n, float* token_logprobs_out, int64_t* top_ids_out, float* top_logprobs_out, fvhd_stream_t stream)
+{
+    if (!c || !token_logprobs_out) return lfail("fvhd_llm_lookup_logprobs: NULL argument");
+    if (top_n < 0 || top_n > 16) return lfail("fvhd_llm_lookup_logprobs: top_n must be in [0, 16] (got " + std::to_string(top_n) + ")");
+    if (top_n > c->V) return lfail("fvhd_llm_lookup_logprobs: top_n = " + std::to_string(top_n) + " exceeds the vocabulary (" + std::to_string(c->V) + ")");
+    if (top_n && (!top_ids_out || !top_logprobs_out)) return lfail("fvhd_llm_lookup_logprobs: top_n > 0 needs top_ids_out and top_logprobs_out");
+    if (!c->spec || !c->sp_begun) return lfail("fvhd_llm_lookup_logprobs: no lookup generation - call fvhd_llm_lookup_begin after fvhd_llm_start");
+    if (!c->lp_on || !c->lp_ws || c->lp_logits != c->dlogits)
+        return lfail("fvhd_llm_lookup_logprobs: the first token's logits are not in the context's buffer - switch fvhd_llm_set_logprobs on before "
+                     "fvhd_llm_start and start without a logits_out");
+    if (int e = dec_status_error(c, "fvhd_llm_lookup_logprobs")) return e;
+    LLM_ON_DEVICE(c);
+    hipStream_t st = (hipStream_t)stream;
+    if (int e = spec_extra_ensure(c, "fvhd_llm_lookup_logprobs", st)) return e;
+    // the first token's entry: the launch of fvhd_llm_logprobs on the logits fvhd_llm_start left, into entry 0 of the arrays
+    LCHECK(fvhd_launch_dec_logprobs(st, c->dlogits, c->last_ids, 1, c->V, top_n, token_logprobs_out, top_ids_out, top_logprobs_out, c->lp_ws, c->status),
+           "lookup first-token logprobs");
+    c->sp_lp_n = top_n; c->sp_lp_tok = token_logprobs_out; c->sp_lp_ids = top_ids_out; c->sp_lp_top = top_logprobs_out;
     return 0;
 }
 
@@ -686,11 +766,20 @@ int fvhd_llm_lookup_step(fvhd_llm* c, int rows, int max_ngram, fvhd_stream_t str
     c->lp_logits = nullptr;
     LCHECK(fvhd_launch_spec_draft(st, c->sp_seq, c->sp_words + SPEC_W_SEQ_LEN, max_ngram, rows - 1, c->sp_draft, c->status, c->sp_words, c->sp_gate),
            "lookup draft");
-    if (int e = spec_enqueue(c, c->sp_draft, rows, nullptr, c->sp_ids, c->sp_gate, st)) return e;
+    const int lp_n = c->lp_on ? c->sp_lp_n : -1;                 // >= 0: the generation keeps log-probabilities (fvhd_llm_lookup_logprobs)
+    if (int e = spec_enqueue(c, c->sp_draft, rows, nullptr, c->sp_ids, c->sp_gate, st, lp_n)) return e;
     SpecAcceptArgs a;
     spec_accept_args(c, c->sp_draft, rows, c->sp_gate, a);
     a.words = c->sp_words; a.seq = c->sp_seq; a.seq_cap = c->spec_seq_cap; a.out = c->sp_out; a.out_cap = c->sp_out_cap;
+    if (lp_n >= 0) a.emitted = c->spx_emitted;
     LCHECK(fvhd_launch_spec_accept(st, &a), "lookup accept");
+    if (lp_n >= 0) {
+        // the rows the accept emitted, to the generation's arrays at the offset of the step's first token: no host work, one graph
+        SpecLogprobsArgs la;
+        la.tok = c->spx_tok; la.ids = c->spx_ids; la.top = c->spx_top; la.n = lp_n; la.emitted = c->spx_emitted; la.words = c->sp_words;
+        la.out_tok = c->sp_lp_tok; la.out_ids = c->sp_lp_ids; la.out_top = c->sp_lp_top; la.out_cap = c->sp_out_cap; la.gate = c->sp_gate;
+        LCHECK(fvhd_launch_spec_logprobs_copy(st, &la), "lookup logprobs copy");
+    }
     return 0;
 }
 

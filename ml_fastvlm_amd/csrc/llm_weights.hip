@@ -239,6 +239,7 @@ void fvhd_llm_destroy(fvhd_llm* c)
     if (c->dc) (void)hipFree(c->dc);
     if (c->beam) (void)hipFree(c->beam);
     if (c->spec) (void)hipFree(c->spec);
+    if (c->spx) (void)hipFree(c->spx);
     if (c->score_ws) (void)hipFree(c->score_ws);
     if (c->lp_ws) (void)hipFree(c->lp_ws);
     if (c->con_tab) (void)hipFree(c->con_tab);

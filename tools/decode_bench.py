@@ -12,6 +12,7 @@ captured graph and called eagerly, against the stock `transformers` decode loop 
     python tools/decode_bench.py --lookup --trace-steps 16 --hidden 896 --rows 8    (eager verify steps only: the program of a kernel trace)
     python tools/decode_bench.py --logprobs 0 5 16 --hidden 896 3584 --batch 1 64   (log-probabilities of the chosen tokens inside the step)
     python tools/decode_bench.py --constraint --hidden 896 3584 --batch 1 64        (constrained decoding: a token automaton masks the logits)
+    python tools/decode_bench.py --lookup-sample 7 --hidden 896 3584 --repeats 3    (the lookup step under sampling and with log-probabilities)
 
 --batch takes up to 64 sequences per step (more than 16 need a library of version 503).  --repeats times the graph replay that many
 times (`graph_ms_per_token` is their median, `graph_ms_per_token_runs` all of them); --no-stock leaves the stock transformers loop (and
@@ -54,6 +55,13 @@ build's step without it and against torch doing the same job inside the same cap
 `state = nxt[state, fed]; logits.masked_fill_(~allowed[state], -inf); fed = logits.argmax(-1)` behind `step(fed, logits=True)` (a baseline
 written for the measurement).  Every case by graph replay over --new tokens, measured twice (the second time in reverse order) and averaged;
 `off` twice more at the ends, so that its four runs show the run-to-run spread the additions are read against.
+
+--lookup-sample K times the whole lookup step (draft + verify of K + 1 rows + accept; `Qwen2Generator.lookup_greedy / lookup_sample`) by
+graph replay under greedy selection and under sampling (predict.py's settings: the T-row sampler in place of the argmax reduce), each
+without and with log-probabilities (--logprobs N, default 5: the logits rows kept, the logprobs launch at B = K + 1, the copy behind the
+accept), next to the plain step the same four ways; every case once per round (--repeats), the rounds in alternating order, medians
+reported.  No lookup ids are given, so on random weights a step emits one token but for chance matches (`accepted_per_step`).  Derived: the
+accepted drafts per step at which the lookup step breaks even with the plain one, t_lookup / t_plain - 1.
 
 Full layer counts, random bf16 weights (`tools/ttft.py: build_llm`).  Prints ONE JSON line: per (width, batch) the ms per token of each
 path, the bytes a step must read (packed weights + the KV cache at the mean length) and their fraction of 8 TB/s."""
@@ -522,6 +530,96 @@ def measure_lookup(llm, pre, rows_list, prompt: int, new: int, dev, repeats: int
     return res
 
 
+@torch.no_grad()
+def measure_lookup_sample(llm, pre, K: int, prompt: int, new: int, dev, repeats: int = 3, lp_n: int = 5) -> dict:
+    """the lookup step (draft + verify + accept, K drafts) by graph replay under greedy and under sampling (predict.py's settings), each
+    without and with log-probabilities, next to the plain step the same ways; no lookup ids, so on random weights nearly every step emits
+    one token (`accepted_per_step` says how many more) - the step's COST, not a speed-up"""
+    from ml_fastvlm_amd import _lib
+    from ml_fastvlm_amd.qwen2_decode import Qwen2Generator
+    cfg = llm.config
+    hidden, V, T = cfg.hidden_size, cfg.vocab_size, K + 1
+    res = {"hidden": hidden, "layers": cfg.num_hidden_layers, "vocab": V, "prompt": prompt, "new_tokens": new, "drafts": K,
+           "sampling": SAMPLE_SETTINGS["predict_py"], "logprobs": lp_n}
+    g0 = torch.Generator(device=dev).manual_seed(0)
+    emb = (0.5 * torch.randn(1, prompt, hidden, device=dev, generator=g0)).to(torch.bfloat16)
+    mask = torch.ones(1, prompt, device=dev, dtype=torch.long)
+    gen = Qwen2Generator.from_hf(llm, 1, prompt + new + T + 4, prefill=pre)
+    lib = _lib.lookup_sample_lib()
+    tok, top_i, top_v = torch.zeros((1,), device=dev), torch.zeros((1, lp_n), device=dev, dtype=torch.long), torch.zeros((1, lp_n), device=dev)
+    out = torch.zeros((new,), device=dev, dtype=torch.long)
+    o_tok, o_ids, o_top = torch.zeros((new,), device=dev), torch.zeros((new, lp_n), device=dev, dtype=torch.long), torch.zeros((new, lp_n), device=dev)
+    eos = (C.c_int32 * 1)()
+
+    def settings(sample, lp):
+        gen.set_sampling(bool(sample), seed=1, **(SAMPLE_SETTINGS["predict_py"] if sample else {}))
+        gen.set_verify_sampling(bool(sample))
+        gen.set_logprobs(bool(lp))
+
+    def plain_ms(sample, lp):
+        settings(sample, lp)
+
+        def step():
+            gen.step(logits=False)
+            if lp:
+                gen.logprobs(lp_n, tok, top_i, top_v)
+
+        gen.start(emb, mask, logits=False)
+        graph = _graph_of(step, dev)
+        graph.replay()
+        gen.start(emb, mask, logits=False)
+        ms = _ms_per(graph.replay, new, dev)
+        assert gen.cache_state() == (prompt + new, 0)
+        return ms, 0
+
+    def lookup_ms(sample, lp):
+        settings(sample, lp)
+        gen.spec_reserve(T, 0)
+
+        def begin():
+            gen.start(emb, mask, logits=False)
+            _lib.check(lib.fvhd_llm_lookup_begin(gen.pre._h, None, 0, C.cast(eos, C.c_void_p), 0, new, _lib.ptr(out), _lib.stream_ptr(dev)), "begin")
+            if lp:
+                _lib.check(lib.fvhd_llm_lookup_logprobs(gen.pre._h, lp_n, _lib.ptr(o_tok), _lib.ptr(o_ids), _lib.ptr(o_top), _lib.stream_ptr(dev)), "logprobs")
+
+        begin()
+        graph = _graph_of(lambda: _lib.check(lib.fvhd_llm_lookup_step(gen.pre._h, T, 2, _lib.stream_ptr(dev)), "step"), dev)
+        while True:                                         # an untimed run counts the steps; the timed run replays exactly that many
+            graph.replay()
+            written, finished, steps, _tok = gen.lookup_state()
+            if finished or written >= new:
+                break
+        begin()
+        ms = _ms_per(graph.replay, steps, dev)
+        assert gen.lookup_state()[:3] == (new, True, steps) and gen.cache_state()[1] == 0
+        return ms, steps
+
+    cases = {"plain_greedy": (plain_ms, False, False), "plain_sample": (plain_ms, True, False), "plain_greedy_logprobs": (plain_ms, False, True),
+             "plain_sample_logprobs": (plain_ms, True, True), "lookup_greedy": (lookup_ms, False, False), "lookup_sample": (lookup_ms, True, False),
+             "lookup_greedy_logprobs": (lookup_ms, False, True), "lookup_sample_logprobs": (lookup_ms, True, True)}
+    runs, steps = {k: [] for k in cases}, {}
+    for rep in range(max(1, repeats)):                      # every case once per round, the rounds in alternating order
+        for k in (list(cases) if rep % 2 == 0 else list(cases)[::-1]):
+            fn, sample, lp = cases[k]
+            ms, st = fn(sample, lp)
+            runs[k].append(round(ms, 4))
+            steps[k] = st
+    settings(False, False)
+    med = lambda v: sorted(v)[len(v) // 2]      # noqa: E731
+    for k, v in runs.items():
+        res[f"{k}_step_ms"], res[f"{k}_step_ms_runs"] = med(v), v
+        if k.startswith("lookup"):
+            res[f"{k}_steps"], res[f"{k}_accepted_per_step"] = steps[k], round((new - 1) / max(steps[k], 1) - 1, 3)
+    res["rows_sampler_over_argmax_finish_us"] = round(1000 * (res["lookup_sample_step_ms"] - res["lookup_greedy_step_ms"]), 1)
+    res["lookup_logprobs_added_us"] = {k: round(1000 * (res[f"lookup_{k}_logprobs_step_ms"] - res[f"lookup_{k}_step_ms"]), 1) for k in ("greedy", "sample")}
+    # a lookup step that accepts a drafts emits 1 + a tokens: it breaks even with the plain step at a = t_lookup / t_plain - 1
+    for k in ("greedy", "sample"):
+        res[f"break_even_accepted_per_step_{k}"] = round(res[f"lookup_{k}_step_ms"] / res[f"plain_{k}_step_ms"] - 1, 3)
+        res[f"break_even_accepted_per_step_{k}_logprobs"] = round(res[f"lookup_{k}_logprobs_step_ms"] / res[f"plain_{k}_logprobs_step_ms"] - 1, 3)
+    del gen
+    return res
+
+
 def _graph_of(fn, dev):
     graph = torch.cuda.CUDAGraph()
     side = torch.cuda.Stream(dev)
@@ -663,8 +761,24 @@ def main():
                     help="the step with the chosen tokens' log-probabilities and top-N alternatives, for every N named, against off and against torch ops")
     ap.add_argument("--constraint", action="store_true",
                     help="the step with a token automaton on (a sparse and a dense state) against off and against torch doing the same from dense tables")
+    ap.add_argument("--lookup-sample", type=int, default=0, metavar="K",
+                    help="the lookup step with K drafts under greedy and under sampling, without and with --logprobs N (default 5), beside the plain step")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
+    if a.lookup_sample:
+        from tools.ttft import build_llm
+        from ml_fastvlm_amd import _lib
+        from ml_fastvlm_amd.qwen2_prefill import Qwen2Prefill
+        rows = []
+        for h in (a.hidden if "--hidden" in sys.argv else [896, 3584]):
+            llm = build_llm(h, dev)
+            pre = Qwen2Prefill.from_hf(llm)
+            rows.append(measure_lookup_sample(llm, pre, a.lookup_sample, a.prompt, a.new, dev, repeats=a.repeats, lp_n=(a.logprobs or [5])[0]))
+            del pre, llm
+            torch.cuda.empty_cache()
+        print(json.dumps({"tool": "decode_bench", "mode": "lookup_sample", "device": torch.cuda.get_device_name(dev),
+                          "library_version": _lib.lookup_sample_lib().fvhd_version(), "results": rows}))
+        return
     if a.constraint:
         from tools.ttft import build_llm
         from ml_fastvlm_amd import _lib
