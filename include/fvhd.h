@@ -81,7 +81,9 @@ typedef void* fvhd_stream_t; /* hipStream_t */
  * did (_lib.py constraint_lib() detects the symbols).  Also added under 510 (new symbols only, the number stays): prompt-lookup decoding
  * under sampling and with log-probabilities - fvhd_llm_set_verify_sampling, fvhd_llm_lookup_logprobs, fvhd_op_dec_sample_rows; with the
  * setting off (the default) and no arrays registered every call enqueues, refuses and allocates what it did (_lib.py lookup_sample_lib()
- * detects the symbols). */
+ * detects the symbols).  Also added under 510 (new symbols only, the number stays): classifier-free guidance - fvhd_dec_guidance_scratch_bytes,
+ * fvhd_op_dec_guidance, fvhd_llm_set_guidance; with the scale at 1 (the default) every call enqueues, refuses and allocates what it did
+ * (_lib.py guidance_lib() detects the symbols). */
 #define FVHD_VERSION 510
 int fvhd_version(void);
 const char* fvhd_last_error(void);
@@ -984,6 +986,50 @@ int fvhd_op_dec_constrain(fvhd_stream_t stream, float* logits, int B, int V, con
 int fvhd_llm_set_constraint(fvhd_llm* ctx, const int32_t* host_offsets, int n_states, const int32_t* host_tokens, const int32_t* host_targets,
                             int n_edges, const int32_t* host_start_states, int n_start);
 int fvhd_llm_constraint_state(fvhd_llm* ctx, int32_t* host_states_out, int32_t* host_flags_out, int rows);
+
+/* ---- LLM classifier-free guidance: the conditional and the unconditional sequence as two rows of one step (added under 510) ------------------
+ * transformers' UnbatchedClassifierFreeGuidanceLogitsProcessor (generate(guidance_scale = s, negative_prompt_ids = ...)) runs a second model
+ * forward per token.  Here the unconditional sequence rides in the same step: for G prompts the step runs B = 2 G rows (G <= 32), row g the
+ * conditional sequence and row G + g the unconditional one (the prompt without the image, say), both fed the same token every step.  Per pair,
+ * with lc = log_softmax(x[g]) and lu = log_softmax(x[G + g]) of the step's fp32 logits:
+ *     guided[v] = s * (lc[v] - lu[v]) + lu[v]
+ * written over row g in front of every other edit: logits processors, the constraint, fvhd_llm_logprobs, temperature / top-k / top-p and the
+ * argmax all act on `guided`, and on the G conditional rows only.  The guided scores are not normalised: fvhd_llm_logprobs reports their
+ * log-softmax, as it renormalises under a constraint.  The logits must be FINITE: guidance runs before any launch that writes -inf.
+ * Kernels (llm_guidance.hip), two launches - the second needs every slice of the first:
+ *   statistics  grid = S slices x 2 G rows, S = min(64, ceil(V / 2048)): per slice the maximum m and sum exp(x - m) (a thread adds its elements
+ *               in index order, a butterfly over the 256 threads); the row's last-arriving workgroup merges the slices into M = max m_s and
+ *               log Z, Z = sum_s sum_s exp(m_s - M) (a butterfly over the slices).  The scheme of the log-probabilities launch: no
+ *               floating-point atomics, a fixed order of additions, the same bits eager or replayed.
+ *   apply       grid = ceil(V / 2048) slices x G pairs.  In this order, every operation rounded once to fp32, no fused multiply-add:
+ *                   lc = (xc - Mc) - log Zc     lu = (xu - Mu) - log Zu     d = lc - lu     p = s * d     guided = p + lu
+ *               Identical rows give d = 0 and guided = lc bit for bit, whatever s.  16-byte loads and stores where both rows of a pair are
+ *               16-byte aligned (always when V % 4 == 0) with a scalar tail of V % 4 elements; a pair with a misaligned row goes element
+ *               by element.  Rows G .. 2 G - 1 are read only: they keep the lm_head's bits.
+ * Behind the choice one small launch copies the id row g chose to row G + g (the ids of the last step and next_ids_out) and, in a decode
+ * step, advances the positions of rows G .. 2 G - 1; the choice's own launches run on G rows.  Under sampling row g draws with the Philox
+ * counter of row g, as without guidance.
+ * fvhd_dec_guidance_scratch_bytes(G, V) = 16384 + 2 * pad256(8 G S) + pad256(16 G) bytes (0: the shape is refused), aligned to 256 bytes; its
+ * first 16 384 bytes are the rows' arrival counters: zero before the FIRST launch, and every launch leaves them zero.
+ * fvhd_op_dec_guidance is the two launches on plain device pointers: logits fp32 [2 G][V], row stride V, aligned to 4 bytes, V >= 1,
+ * 1 <= G <= 32, scale finite.
+ * fvhd_llm_set_guidance(ctx, scale): scale == 1 is off (the default), any other finite scale is on.  It is read when fvhd_llm_start / _decode /
+ * _extend enqueue, like the sampling settings; a captured graph keeps what it was captured with.  The first call that switches guidance on
+ * allocates the launches' scratch (an allocation of its own, for 32 pairs of the context's vocabulary, kept until fvhd_llm_destroy); that
+ * call synchronises the device and is refused while a stream is being captured.  A context that never switches it on keeps its footprint.
+ * With guidance on:
+ *   fvhd_llm_start / _decode / _extend run the two launches on the logits their choice is made from (the greedy decode step keeps its logits
+ *     and takes its (max, index) pairs from them again, as under the processors), then processors and constraint on the G conditional
+ *     rows, the choice on G rows, the mirror launch.  Inside the decode step they obey the error word like the other launches.  logits_out
+ *     holds the guided scores in rows [0, G) and the raw logits in rows [G, 2 G); next_ids_out holds 2 G ids (row G + g = row g).
+ *     Per-row settings (the constraint's start states, fvhd_llm_constraint_state, fvhd_llm_logprobs' outputs) count G rows.
+ *   Refused, each with a message: an odd batch; fvhd_llm_verify, fvhd_llm_lookup_begin / _step; fvhd_llm_beam_topk; fvhd_llm_cache_gather (it
+ *     would break the pairing); fvhd_llm_cache_rewind - rows g and G + g would have to keep equal lengths, and the keeps are on the
+ *     device, where they cannot be checked without a synchronisation, so the call is refused outright.
+ * Off: no launch, no allocation; every call enqueues launch for launch what it did. */
+size_t fvhd_dec_guidance_scratch_bytes(int G, int V);
+int fvhd_op_dec_guidance(fvhd_stream_t stream, float* logits, int G, int V, float scale, void* scratch, size_t scratch_bytes);
+int fvhd_llm_set_guidance(fvhd_llm* ctx, float scale);
 
 #ifdef __cplusplus
 }

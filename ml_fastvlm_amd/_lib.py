@@ -25,6 +25,7 @@ EXTEND_VERSION = 509          # the first with fvhd_llm_extend / fvhd_llm_cache_
 MAX_DECODE_BATCH = 64
 MAX_VERIFY_ROWS = 16           # rows of one verify step (include/fvhd.h)
 MAX_EOS_IDS, MAX_SUPPRESS_IDS = 16, 256      # list limits of fvhd_llm_set_logits_processors (include/fvhd.h)
+MAX_GUIDANCE_PROMPTS = 32      # G of fvhd_llm_set_guidance: the step runs 2 G rows (include/fvhd.h "LLM classifier-free guidance")
 MAX_LOGPROBS = 16              # top_n of fvhd_llm_logprobs / fvhd_op_dec_logprobs (include/fvhd.h)
 W_BF16, W_E4M3 = 0, 1           # fvhd_llm_set_weight_format (include/fvhd.h)
 WEIGHT_FORMATS = {"bf16": W_BF16, "fp8_e4m3": W_E4M3}
@@ -210,6 +211,12 @@ def _declare(lib) -> None:
             "fvhd_llm_lookup_logprobs": (ci, [vp, ci, vp, vp, vp, vp]),
             "fvhd_op_dec_sample_rows": (ci, [vp, vp, ci, ci, cf, ci, cf, C.c_ulonglong, ci, ci, vp, vp, vp, vp, vp, vp]),
         })
+    if hasattr(lib, "fvhd_op_dec_guidance"):       # added under 510: a 510 library built before them loads without; guidance_lib() then names the rebuild
+        sig.update({
+            "fvhd_dec_guidance_scratch_bytes": (C.c_size_t, [ci, ci]),
+            "fvhd_op_dec_guidance": (ci, [vp, vp, ci, ci, cf, vp, C.c_size_t]),
+            "fvhd_llm_set_guidance": (ci, [vp, cf]),
+        })
     del fp, cl
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)     # AttributeError here = the .so does not export what fvhd.h declares
@@ -366,6 +373,17 @@ def lookup_sample_lib():
         raise FvhdError(f"{LIB_PATH} (ABI version {lib.fvhd_version()}) was built before prompt-lookup decoding under sampling "
                         "(fvhd_llm_set_verify_sampling, fvhd_llm_lookup_logprobs, fvhd_op_dec_sample_rows) - rebuild the library "
                         "(`python -m ml_fastvlm_amd.build`)")
+    return lib
+
+
+def guidance_lib():
+    """load(), for classifier-free guidance (fvhd_llm_set_guidance, fvhd_op_dec_guidance, fvhd_dec_guidance_scratch_bytes): the entry points
+    were added under FVHD_VERSION 510, so a library built before them reports the same number and loads; this says so instead of an
+    AttributeError."""
+    lib = load()
+    if not hasattr(lib, "fvhd_op_dec_guidance"):
+        raise FvhdError(f"{LIB_PATH} (ABI version {lib.fvhd_version()}) was built before classifier-free guidance (fvhd_llm_set_guidance, "
+                        "fvhd_op_dec_guidance, fvhd_dec_guidance_scratch_bytes) - rebuild the library (`python -m ml_fastvlm_amd.build`)")
     return lib
 
 

@@ -16,7 +16,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 BUILD = os.path.join(CSRC, "build")
 LIB = os.path.join(PKG, "libfvhd.so")
-SOURCES = ["dwconv.hip", "dwconv_mfma.hip", "dwconv_fused.hip", "dwconv_down.hip", "gemm.hip", "attention.hip", "stem_head.hip", "ffn_fused.hip", "splice.hip", "preprocess.hip", "llm.hip", "llm_extend.hip", "llm_decode.hip", "llm_w8.hip", "llm_w4.hip", "llm_sample.hip", "llm_beam.hip", "llm_logits.hip", "llm_logprobs.hip", "llm_constrain.hip", "llm_spec.hip", "llm_score.hip", "llm_weights.hip", "llm_prefill.hip", "llm_step.hip", "llm_ops.hip", "fvhd_api.hip"]
+SOURCES = ["dwconv.hip", "dwconv_mfma.hip", "dwconv_fused.hip", "dwconv_down.hip", "gemm.hip", "attention.hip", "stem_head.hip", "ffn_fused.hip", "splice.hip", "preprocess.hip", "llm.hip", "llm_extend.hip", "llm_decode.hip", "llm_w8.hip", "llm_w4.hip", "llm_sample.hip", "llm_beam.hip", "llm_logits.hip", "llm_logprobs.hip", "llm_constrain.hip", "llm_guidance.hip", "llm_spec.hip", "llm_score.hip", "llm_weights.hip", "llm_prefill.hip", "llm_step.hip", "llm_ops.hip", "fvhd_api.hip"]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
          "-ffp-contract=fast", "-fno-gpu-rdc"]

@@ -94,7 +94,7 @@ def encode_images(vision_tower, mm_projector, images):
 
 def install_into_llava(splice: bool = False, prefill: bool = False, prefill_any_dtype: bool = False, generate: bool = False,
                        llm_weights: str = "bf16", beam_search: bool = False, logits_processors: bool = False, constraints: bool = False,
-                       prompt_lookup: bool = False) -> None:
+                       prompt_lookup: bool = False, guidance: bool = False) -> None:
     """Make an unmodified `llava` package (the reference) build and call the MI355X tower; splice=True also routes
     `prepare_inputs_labels_for_multimodal` through the GPU splice (needs the embeddings on a HIP device); prefill=True also runs the
     PREFILL step of `LlavaQwen2ForCausalLM.forward` (`llava_qwen.py:92-103`: the first forward of `generate`, on `inputs_embeds`
@@ -116,6 +116,10 @@ def install_into_llava(splice: bool = False, prefill: bool = False, prefill_any_
     prompt_lookup=True (with generate=True) lets it take the library for transformers' `prompt_lookup_num_tokens=K` (1 .. 15; one prompt,
     num_beams = 1, no processor, no constraint): `Qwen2Generator.lookup_greedy`, or `.lookup_sample` under do_sample - the tokens of the call
     without the keyword, in fewer steps; without the flag the keyword keeps falling back.
+    guidance=True (with generate=True) lets it take the library for transformers' `guidance_scale` != 1 with a text-only
+    `negative_prompt_ids` (every id >= 0; `negative_prompt_attention_mask` optional), num_beams = 1 and at most 32 prompts
+    (`Qwen2Generator.greedy` / `.sample(guidance_scale=...)`: the negative prompts are rows of the same step); anything else about such a
+    call, or the flag off, falls back as before.
     llm_weights: "bf16" (the default), "fp8_e4m3" or "mxfp4" - the storage of the LLM's packed matrices in the library's prefill / decode contexts
     (`Qwen2Prefill.from_hf(weights=...)`), recorded on `LlavaQwen2ForCausalLM` for `prefill_context` to read."""
     from ._lib import weight_format_code
@@ -155,6 +159,8 @@ def install_into_llava(splice: bool = False, prefill: bool = False, prefill_any_
             extra["constraints"] = True
         if prompt_lookup:
             extra["prompt_lookup"] = True
+        if guidance:
+            extra["guidance"] = True
         lq.LlavaQwen2ForCausalLM.generate = _make_library_generate(getattr(cur, "_fvhd_orig", cur), beam_search=beam_search, **extra)
 
 
@@ -292,7 +298,8 @@ def generator_context(model, batch: int, capacity: int, weights=None):
 @torch.no_grad()
 def generate(model, input_ids, images=None, image_sizes=None, attention_mask=None, max_new_tokens: int = 256, eos_token_id=None,
              pad_token_id=None, do_sample: bool = False, num_beams: int = 1, prompt_lookup_num_tokens=None,
-             max_matching_ngram_size: int = 2, logprobs=None, constraint=None, constraint_start=None, **kwargs):
+             max_matching_ngram_size: int = 2, logprobs=None, constraint=None, constraint_start=None, guidance_scale=None,
+             negative_prompt_ids=None, negative_prompt_attention_mask=None, **kwargs):
     """`LlavaQwen2ForCausalLM.generate` (`llava_qwen.py:106-143`) with greedy decoding on the library: the multimodal splice
     (`model.prepare_inputs_labels_for_multimodal`) or the token embedding, then the prefill and every decode step on the hand-written
     Qwen2 kernels (`Qwen2Generator.greedy`).  Returns the new tokens [B, n] as transformers' generate(inputs_embeds=...) does.  Greedy only:
@@ -302,9 +309,19 @@ def generate(model, input_ids, images=None, image_sizes=None, attention_mask=Non
     logprobs=n (0 .. 16): -> (tokens, `GenerationLogprobs`): every generated token's log-probability and the n most likely tokens of its step
     (`Qwen2Generator.greedy`, or `Qwen2Generator.lookup_greedy` with prompt_lookup_num_tokens: the same values in fewer steps).
     constraint: a `ml_fastvlm_amd.constraints.TokenAutomaton` the new tokens of every row must follow, from constraint_start (None: state 0;
-    an int; one state per row, -1 = unconstrained) - `Qwen2Generator.greedy(constraint=...)`; not with prompt_lookup_num_tokens."""
-    from .qwen2_decode import normalize_logprobs
+    an int; one state per row, -1 = unconstrained) - `Qwen2Generator.greedy(constraint=...)`; not with prompt_lookup_num_tokens.
+    guidance_scale=s (finite, != 1) with negative_prompt_ids [B, n] (and negative_prompt_attention_mask): classifier-free guidance
+    (`Qwen2Generator.greedy(guidance_scale=...)`, at most 32 prompts).  The negative prompt goes through the same multimodal splice: with
+    the image placeholder it sees the same images, without it it is text only - the visual-contrast case.  Without negative ids the call is
+    refused: the prompt is generated from `inputs_embeds`, so transformers' "last prompt token" default has nothing to take.  Not with
+    prompt_lookup_num_tokens."""
+    from .qwen2_decode import normalize_guidance, normalize_logprobs
     logprobs = normalize_logprobs(logprobs)
+    guidance = _guidance_settings("ml_fastvlm_amd.generate", normalize_guidance(guidance_scale), negative_prompt_ids, negative_prompt_attention_mask,
+                                  None if not isinstance(input_ids, torch.Tensor) else input_ids.shape[0])
+    if guidance is not None and prompt_lookup_num_tokens is not None:
+        raise ValueError("ml_fastvlm_amd.generate: guidance_scale is not implemented under prompt-lookup decoding (prompt_lookup_num_tokens) - a "
+                         "verify step takes one sequence and does not take guidance")
     if constraint is not None and prompt_lookup_num_tokens is not None:
         raise ValueError("ml_fastvlm_amd.generate: a constraint is not implemented under prompt-lookup decoding (prompt_lookup_num_tokens) - a "
                          "verify step does not advance the rows' automaton states")
@@ -340,17 +357,43 @@ def generate(model, input_ids, images=None, image_sizes=None, attention_mask=Non
     if pad_token_id is None:
         pad_token_id = getattr(gc, "pad_token_id", None)
     return _generate_on_library(model, input_ids, images, image_sizes, attention_mask, None, max_new_tokens, eos_token_id, pad_token_id, lookup=lookup,
-                                logprobs=logprobs, constraint=constraint, constraint_start=constraint_start)
+                                logprobs=logprobs, constraint=constraint, constraint_start=constraint_start, guidance=guidance)
+
+
+def _guidance_settings(who, scale, negative_prompt_ids, negative_prompt_attention_mask, batch=None, text_only: bool = False):
+    """the guidance keywords of a generate call -> None (off: scale None / 1) or the `guidance` argument of `_generate_on_library`; each
+    refusal is a ValueError that names its reason.  text_only: an image placeholder (a negative id) in the negative prompt is refused."""
+    from ._lib import MAX_GUIDANCE_PROMPTS
+    if scale is None:
+        return None
+    if negative_prompt_ids is None:
+        raise ValueError(f"{who}: guidance_scale={scale} without negative_prompt_ids - the prompt is generated from inputs_embeds, so transformers' "
+                         "\"last prompt token\" default has nothing to take; pass the unconditional prompt (e.g. the prompt without its image placeholder)")
+    if not isinstance(negative_prompt_ids, torch.Tensor) or negative_prompt_ids.dim() != 2 or negative_prompt_ids.dtype != torch.long:
+        raise ValueError(f"{who}: negative_prompt_ids must be an int64 tensor [B, n]")
+    if batch is not None and negative_prompt_ids.shape[0] != batch:
+        raise ValueError(f"{who}: negative_prompt_ids has {negative_prompt_ids.shape[0]} rows for {batch} prompts (one negative prompt per prompt)")
+    if negative_prompt_ids.shape[0] > MAX_GUIDANCE_PROMPTS:
+        raise ValueError(f"{who}: guidance_scale={scale} with {negative_prompt_ids.shape[0]} prompts - at most {MAX_GUIDANCE_PROMPTS} per call "
+                         "(each takes two rows of the step)")
+    if text_only and bool((negative_prompt_ids < 0).any()):
+        raise ValueError(f"{who}: negative_prompt_ids holds a negative id (an image placeholder) - only a text-only negative prompt runs here")
+    return dict(guidance_scale=scale, negative_prompt_ids=negative_prompt_ids, negative_prompt_attention_mask=negative_prompt_attention_mask)
 
 
 @torch.no_grad()
 def beam_generate(model, input_ids, images=None, image_sizes=None, attention_mask=None, max_new_tokens: int = 256, num_beams: int = 4,
                   length_penalty: float = 1.0, early_stopping=False, num_return_sequences: int = 1, eos_token_id=None, pad_token_id=None,
-                  return_scores: bool = False):
+                  return_scores: bool = False, guidance_scale=None):
     """`generate`'s counterpart for `num_beams` > 1: `LlavaQwen2ForCausalLM.generate(..., num_beams=K)` (predict.py's --num_beams) with the
     splice, the prefill, every decode step, the top continuations and the cache reorder on the library (`Qwen2Generator.beam_search`).
     Returns the new tokens [B * num_return_sequences, n] as transformers' generate(inputs_embeds=..., num_beams=K) does, with return_scores
-    also its `sequences_scores`.  The model must be bf16 on a HIP device and B * num_beams <= 64."""
+    also its `sequences_scores`.  The model must be bf16 on a HIP device and B * num_beams <= 64.  guidance_scale: refused (beam search does
+    not take guidance)."""
+    from .qwen2_decode import normalize_guidance
+    if normalize_guidance(guidance_scale) is not None:
+        raise ValueError("ml_fastvlm_amd.beam_generate: guidance_scale is not implemented under beam search - guidance runs with num_beams = 1 "
+                         "(ml_fastvlm_amd.generate)")
     lm_w = model.lm_head.weight
     if lm_w.device.type != "cuda" or lm_w.dtype != torch.bfloat16:
         raise ValueError(f"ml_fastvlm_amd.beam_generate: needs a bf16 model on a HIP device (got {lm_w.dtype} on {lm_w.device}); "
@@ -366,12 +409,18 @@ def beam_generate(model, input_ids, images=None, image_sizes=None, attention_mas
 
 
 def _generate_on_library(model, input_ids, images, image_sizes, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id,
-                         sampling=None, beam=None, processors=None, lookup=None, logprobs=None, constraint=None, constraint_start=None):
+                         sampling=None, beam=None, processors=None, lookup=None, logprobs=None, constraint=None, constraint_start=None,
+                         guidance=None):
     """the body shared by `generate`, `beam_generate` and `_make_library_generate`: the multimodal splice (or the token embedding), then the
     prefill and every decode step on the library - `Qwen2Generator.greedy`, `.sample(**sampling)` or `.beam_search(**beam)`; processors:
     None or the logits-processor keywords of greedy / sample (repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens);
     logprobs: None or greedy's / sample's keyword (they then return (tokens, GenerationLogprobs)) - not for beam search; lookup: None or the
-    keywords of `.lookup_greedy` (one prompt), with sampling those of `.lookup_sample`"""
+    keywords of `.lookup_greedy` (one prompt), with sampling those of `.lookup_sample`; guidance: None or guidance_scale, negative_prompt_ids
+    and negative_prompt_attention_mask (`_guidance_settings`) - the negative prompt takes the same splice (with the image placeholder it sees
+    the same images, without it it is text only) and rides as rows G .. 2 G - 1 of greedy / sample"""
+    if guidance is not None and (beam is not None or lookup is not None):
+        raise ValueError("guidance_scale is implemented for greedy decoding and sampling only (num_beams = 1, no prompt lookup): beam search and "
+                         "the verify step do not take guidance")
     if logprobs is not None and beam is not None:
         raise ValueError("logprobs is implemented for greedy decoding and sampling only (beam search has return_scores)")
     if constraint is not None and (beam is not None or lookup is not None):
@@ -395,6 +444,18 @@ def _generate_on_library(model, input_ids, images, image_sizes, attention_mask, 
                                      pad_token_id=pad_token_id, logprobs=logprobs, **sampling, **lookup)
         return gen.lookup_greedy(inputs_embeds, attention_mask, position_ids, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id,
                                  pad_token_id=pad_token_id, logprobs=logprobs, **lookup)
+    if guidance is not None:
+        neg_ids, neg_mask = guidance["negative_prompt_ids"], guidance["negative_prompt_attention_mask"]
+        neg_pos = None
+        if images is not None and bool((neg_ids < 0).any()):
+            (_, neg_pos, neg_mask, _, neg_embeds, _) = model.prepare_inputs_labels_for_multimodal(neg_ids, None, neg_mask, None, None, images,
+                                                                                                 image_sizes=image_sizes)
+        else:
+            neg_embeds = model.get_input_embeddings()(neg_ids.to(inputs_embeds.device))
+        con = dict(con, guidance_scale=guidance["guidance_scale"], negative_inputs_embeds=neg_embeds, negative_attention_mask=neg_mask,
+                   negative_position_ids=neg_pos)
+        T = max(T, neg_embeds.shape[1])
+        B = 2 * B
     gen = generator_context(model, B, T + max_new_tokens)
     processors = processors or {}
     if sampling is None:
@@ -570,14 +631,19 @@ class GenerationSession:
     @torch.no_grad()
     def generate(self, input_ids, images=None, image_sizes=None, attention_mask=None, max_new_tokens: int = 256, eos_token_id=None,
                  pad_token_id=None, do_sample: bool = False, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
-                 logprobs=None, constraint=None, constraint_start=None):
+                 logprobs=None, constraint=None, constraint_start=None, guidance_scale=None):
         """-> the new tokens of this turn [B, n] (`Qwen2Generator.greedy` / `.sample`'s return contract); with logprobs=n (0 .. 16)
         (tokens, `GenerationLogprobs`) of this turn.  constraint (a `ml_fastvlm_amd.constraints.TokenAutomaton`, with constraint_start)
         constrains THIS turn's answer only: every turn begins at its own start states, and the constraint is cleared before the cache is
         rewound.  First call: `input_ids` is the
         whole prompt (with image placeholders when `images` is given).  Later calls: the turn's NEW ids [B, n] only, B = the session's
         rows; attention_mask marks the real tokens of rows of different lengths.  Images in a later turn need B = 1 or rows whose
-        spliced lengths are equal (the splice pads to the right, the cache extends to the left)."""
+        spliced lengths are equal (the splice pads to the right, the cache extends to the left).  guidance_scale: refused - a session rewinds
+        its cache between turns, which guidance does not allow."""
+        from .qwen2_decode import normalize_guidance
+        if normalize_guidance(guidance_scale) is not None:
+            raise ValueError("GenerationSession.generate: guidance_scale is not implemented for sessions - a session rewinds its cache between "
+                             "turns, which the library refuses under guidance; use ml_fastvlm_amd.generate")
         model = self.model
         lm_w = model.lm_head.weight
         if lm_w.device.type != "cuda" or lm_w.dtype != torch.bfloat16:
@@ -667,11 +733,14 @@ _OFF = {
 # generate()'s own arguments beside **kwargs: any of them given asks for something the library does not do
 _GENERATE_ARGS = ("generation_config", "logits_processor", "stopping_criteria", "prefix_allowed_tokens_fn", "synced_gpus", "assistant_model",
                   "streamer", "negative_prompt_ids", "negative_prompt_attention_mask", "custom_generate", "assistant_tokenizer", "tokenizer")
+# those of _GENERATE_ARGS that stop disqualifying a call under `guidance=True` (they belong to `guidance_scale`)
+_GUIDANCE_ARGS = ("negative_prompt_ids", "negative_prompt_attention_mask")
 # the settings of _OFF that `Qwen2Generator.set_logits_processors` implements (num_beams = 1)
 _PROCESSORS = ("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens", "suppress_tokens")
 
 
-def _library_generate_settings(model, kwargs, beam_search: bool = False, processors: bool = False, prompt_lookup: bool = False, batch=None):
+def _library_generate_settings(model, kwargs, beam_search: bool = False, processors: bool = False, prompt_lookup: bool = False, batch=None,
+                               guidance: bool = False):
     """transformers' own resolution of a generate(**kwargs) call (`_prepare_generation_config`, which generate itself calls: its global
     defaults such as top_k = 50, the model's generation_config, then the call's arguments) -> (settings, None) when the library can run
     it, (None, reason) when it cannot.  settings: max_new_tokens, eos_token_id, pad_token_id, `sampling` (None = greedy, else the
@@ -682,7 +751,14 @@ def _library_generate_settings(model, kwargs, beam_search: bool = False, process
     keywords of Qwen2Generator.greedy / .sample.  prompt_lookup=True: transformers' own `prompt_lookup_num_tokens=K` no longer disqualifies
     the call when 1 <= K <= 15, num_beams = 1, no processor is on and `batch` (the number of prompts; None = unknown, not checked) is 1;
     settings then gains `lookup`: None without the keyword, else prompt_lookup_num_tokens and max_matching_ngram_size (the config's, 2 when it
-    has none) for Qwen2Generator.lookup_greedy / .lookup_sample."""
+    has none) for Qwen2Generator.lookup_greedy / .lookup_sample.  guidance=True: `guidance_scale` != 1 no longer disqualifies the call when
+    `negative_prompt_ids` is given and text only (every id >= 0), num_beams = 1, no prompt lookup and `batch` (None = not checked) is at
+    most 32; `negative_prompt_ids` / `negative_prompt_attention_mask` stop disqualifying it; settings then gains `guidance`: None while the
+    scale is 1 / unset, else guidance_scale, negative_prompt_ids and negative_prompt_attention_mask for `_generate_on_library`."""
+    negative = {}
+    if guidance:
+        negative = {k: kwargs[k] for k in _GUIDANCE_ARGS if kwargs.get(k) is not None}
+        kwargs = {k: v for k, v in kwargs.items() if k not in _GUIDANCE_ARGS}
     for k in _GENERATE_ARGS:
         if kwargs.get(k) is not None:
             return None, f"{k} is given"
@@ -702,6 +778,8 @@ def _library_generate_settings(model, kwargs, beam_search: bool = False, process
         if processors and single and k in _PROCESSORS:
             continue
         if prompt_lookup and k == "prompt_lookup_num_tokens":
+            continue
+        if guidance and single and k == "guidance_scale":
             continue
         if v is not None and v not in off:
             return None, f"{k}={v!r}"
@@ -756,6 +834,17 @@ def _library_generate_settings(model, kwargs, beam_search: bool = False, process
             if isinstance(ngram, bool) or not isinstance(ngram, int) or not 1 <= ngram <= 16:
                 return None, f"{what} with max_matching_ngram_size={ngram!r} (the library matches n-grams of 1 .. 16 tokens)"
             settings["lookup"] = dict(prompt_lookup_num_tokens=K, max_matching_ngram_size=ngram)
+    if guidance:
+        from .qwen2_decode import normalize_guidance
+        settings["guidance"] = None
+        try:
+            scale = normalize_guidance(gc.guidance_scale) if single else None
+            if scale is not None and getattr(gc, "prompt_lookup_num_tokens", None) is not None:
+                return None, f"guidance_scale={scale} with prompt_lookup_num_tokens (the verify step does not take guidance)"
+            settings["guidance"] = _guidance_settings("generate", scale, negative.get("negative_prompt_ids"),
+                                                      negative.get("negative_prompt_attention_mask"), batch, text_only=True)
+        except ValueError as e:
+            return None, str(e).split(": ", 1)[-1]
     return settings, None
 
 
@@ -766,7 +855,7 @@ def _batch_reason(batch: int):
 
 
 def _make_library_generate(orig_generate, beam_search: bool = False, logits_processors: bool = False, constraints: bool = False,
-                           prompt_lookup: bool = False):
+                           prompt_lookup: bool = False, guidance: bool = False):
     """`LlavaQwen2ForCausalLM.generate` (`llava_qwen.py:106-143`) on the library: the same argument handling (position_ids / attention_mask
     popped, inputs_embeds refused), the settings resolved as transformers resolves them (`_library_generate_settings`), then the
     multimodal splice and `Qwen2Generator.greedy` / `.sample` on `generator_context(model, ...)`.  It takes the library only for greedy or
@@ -784,7 +873,10 @@ def _make_library_generate(orig_generate, beam_search: bool = False, logits_proc
     the flag the keywords are not looked at.  `prefix_allowed_tokens_fn` keeps falling back.  prompt_lookup=True: transformers' own
     `prompt_lookup_num_tokens=K` (1 .. 15, with `max_matching_ngram_size` when set) runs `Qwen2Generator.lookup_greedy` / `.lookup_sample` for
     one prompt with num_beams = 1, no processor and no constraint - the same tokens as without the keyword, in fewer steps; `inputs` are the
-    lookup ids (the image placeholder is negative and never matches).  Anything else, or the flag off, falls back as before."""
+    lookup ids (the image placeholder is negative and never matches).  Anything else, or the flag off, falls back as before.
+    guidance=True: transformers' own `guidance_scale` != 1 with a text-only `negative_prompt_ids` (every id >= 0), num_beams = 1 and at most
+    32 prompts runs `Qwen2Generator.greedy` / `.sample(guidance_scale=...)`; `negative_prompt_ids` / `negative_prompt_attention_mask` stop
+    disqualifying the call only under this flag.  Anything else falls back with the usual one-time warning; with the flag off nothing changes."""
     def generate(self, inputs=None, images=None, image_sizes=None, **kwargs):
         if "inputs_embeds" in kwargs:                            # as the reference (llava_qwen.py:120-121)
             raise NotImplementedError("`inputs_embeds` is not supported")
@@ -796,14 +888,21 @@ def _make_library_generate(orig_generate, beam_search: bool = False, logits_proc
         extra = dict(processors=True) if logits_processors else {}
         if prompt_lookup:
             extra.update(prompt_lookup=True, batch=None if inputs is None else inputs.shape[0])
+        if guidance:
+            extra.update(guidance=True, batch=None if inputs is None else inputs.shape[0])
         settings, reason = _library_generate_settings(self, {k: v for k, v in kwargs.items() if k not in ("position_ids", "attention_mask")},
                                                       beam_search=beam_search, **extra)
         lookup = settings.get("lookup") if settings is not None else None
         if lookup is not None and (inputs is None or constraint is not None):
             settings, reason = None, (f"prompt_lookup_num_tokens={lookup['prompt_lookup_num_tokens']} " +
                                       ("without input_ids" if inputs is None else "with a constraint (the verify step does not advance its states)"))
+        guided = settings.get("guidance") if settings is not None else None
+        if guided is not None and (inputs is None or lookup is not None):
+            settings, reason = None, f"guidance_scale={guided['guidance_scale']} " + ("without input_ids" if inputs is None else "with prompt lookup")
         lm_w = self.lm_head.weight
         rows = 0 if inputs is None else inputs.shape[0] * (settings["beam"]["num_beams"] if settings is not None and settings["beam"] else 1)
+        if settings is not None and guided is not None:
+            rows *= 2                                            # every prompt rides with its negative prompt
         if settings is not None and inputs is not None and _batch_reason(rows) is not None:
             settings, reason = None, _batch_reason(rows)
         if settings is not None and (lm_w.device.type != "cuda" or lm_w.dtype != torch.bfloat16):
@@ -824,7 +923,8 @@ def _make_library_generate(orig_generate, beam_search: bool = False, logits_proc
                                         settings["max_new_tokens"], settings["eos_token_id"], settings["pad_token_id"], settings["sampling"],
                                         settings["beam"], **(dict(processors=settings["processors"]) if settings.get("processors") else {}),
                                         **(dict(constraint=constraint, constraint_start=constraint_start) if constraint is not None else {}),
-                                        **(dict(lookup=dict(lookup, lookup_ids=inputs)) if lookup is not None else {}))
+                                        **(dict(lookup=dict(lookup, lookup_ids=inputs)) if lookup is not None else {}),
+                                        **(dict(guidance=guided) if guided is not None else {}))
     generate._fvhd_generate = True
     generate._fvhd_orig = orig_generate
     return generate

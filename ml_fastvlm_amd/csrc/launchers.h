@@ -122,4 +122,9 @@ int fvhd_launch_dec_logprobs(hipStream_t st, const float* logits, const int64_t*
                              float* top_logprobs, void* scratch, const int* status);
 // llm_constrain.hip (the advance / reset launch when the arguments ask for one, then the mask launch)
 int fvhd_launch_dec_constrain(hipStream_t st, const DecConstrainArgs* a);
+// llm_guidance.hip (logits fp32 [2 G][V], finite; scratch: fvhd_dec_guidance_scratch_bytes, its first 16 384 bytes zero before the first launch;
+// status: NULL or the error word).  The statistics launch and the apply launch; the mirror: ids of rows [0, G) -> rows [G, 2 G), posv (optional) + 1 there
+size_t fvhd_dec_guidance_scratch_bytes(int G, int V);
+int fvhd_launch_dec_guidance(hipStream_t st, float* logits, int G, int V, float scale, void* scratch, const int* status);
+int fvhd_launch_dec_guidance_mirror(hipStream_t st, int G, int64_t* last, int64_t* ids_out, int64_t* posv, const int* status);
 }

@@ -155,9 +155,17 @@ struct __attribute__((visibility("default"))) fvhd_llm {     // (its inline cons
     int* con_state = nullptr;
     int con_start[64] = {};
     bool con_started = false;              // the last fvhd_llm_start / _extend ran with the constraint on: a decode step has states to advance
+    // fvhd_llm_set_guidance (llm_guidance.hip): guid_scale != 1 = on, read when fvhd_llm_start / _decode / _extend enqueue, like the sampling
+    // settings.  guid_ws: the launches' scratch for 32 pairs of this vocabulary, an allocation of its own made by the first call that
+    // switches guidance on and kept until fvhd_llm_destroy.  guid_rows: the conditional rows G of the last start / decode / extend when it
+    // ran under guidance (fvhd_llm_logprobs then takes the G conditional rows), else 0
+    float guid_scale = 1.f;
+    char* guid_ws = nullptr;
+    int guid_rows = 0;
 };
 
 inline bool constraint_on(const fvhd_llm* c) { return c->con_n_states > 0; }
+inline bool guidance_on(const fvhd_llm* c) { return c->guid_scale != 1.f; }
 
 inline bool processors_on(const fvhd_llm* c)
 {

@@ -1,4 +1,6 @@
 // C ABI of the Qwen2 kernels one at a time (include/fvhd.h fvhd_op_*): the unit tests' entry points.  None of them takes a context.
+#include <cmath>
+
 #include "llm_ctx.h"
 
 extern "C" {
@@ -394,6 +396,19 @@ int fvhd_op_dec_constrain(fvhd_stream_t st, float* logits, int B, int V, const i
     a.logits = logits; a.B = B; a.V = V; a.offsets = offsets; a.tokens = tokens; a.targets = targets; a.n_states = n_states; a.states = states;
     a.flags = flags; a.tok = fed_ids;
     return lret("fvhd_op_dec_constrain", fvhd_launch_dec_constrain((hipStream_t)st, &a));
+}
+
+// classifier-free guidance on its own: the statistics launch and the apply launch (llm_guidance.hip)
+int fvhd_op_dec_guidance(fvhd_stream_t st, float* logits, int G, int V, float scale, void* scratch, size_t scratch_bytes)
+{
+    if (!logits || !scratch) return lfail("fvhd_op_dec_guidance: NULL pointer");
+    if (G < 1 || G > 32 || V < 1) return lfail("fvhd_op_dec_guidance: needs 1 <= G <= 32 pairs and V >= 1");
+    if (!std::isfinite(scale)) return lfail("fvhd_op_dec_guidance: scale must be finite");
+    if ((uintptr_t)logits & 3) return lfail("fvhd_op_dec_guidance: logits must be aligned to 4 bytes");
+    if (scratch_bytes < fvhd_dec_guidance_scratch_bytes(G, V))
+        return lfail("fvhd_op_dec_guidance: scratch_bytes = " + std::to_string(scratch_bytes) + " is below fvhd_dec_guidance_scratch_bytes(G, V) = " +
+                     std::to_string(fvhd_dec_guidance_scratch_bytes(G, V)));
+    return lret("fvhd_op_dec_guidance", fvhd_launch_dec_guidance((hipStream_t)st, logits, G, V, scale, scratch, nullptr));
 }
 
 // process-wide scratch of a single op, allocated / grown on demand - eager calls only

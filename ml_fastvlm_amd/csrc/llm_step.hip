@@ -1,5 +1,5 @@
 // C ABI of the Qwen2 decode (include/fvhd.h "LLM decode"): the library's own KV cache, one token per sequence per step.
-// Kernels: llm_decode.hip, llm_w8.hip, llm_sample.hip, llm_beam.hip, llm_logits.hip, llm_constrain.hip, llm_spec.hip, llm_extend.hip.
+// Kernels: llm_decode.hip, llm_w8.hip, llm_sample.hip, llm_beam.hip, llm_logits.hip, llm_constrain.hip, llm_guidance.hip, llm_spec.hip, llm_extend.hip.
 #include <algorithm>
 #include <cmath>
 
@@ -132,6 +132,21 @@ int constraint_start_error(const fvhd_llm* c, const char* who, int B)
                  " rows - set it (fvhd_llm_set_constraint) with one start state, or one per row of fvhd_llm_cache_reserve");
 }
 
+// classifier-free guidance pairs row g with row B / 2 + g
+int guidance_rows_error(const char* who, int B)
+{
+    if (B % 2 == 0) return 0;
+    return lfail(std::string(who) + ": guidance is on (fvhd_llm_set_guidance) and the batch is odd (" + std::to_string(B) + " rows) - row g is the "
+                 "conditional sequence and row B / 2 + g its unconditional one, so the batch must be 2 G");
+}
+
+// the refusal of a call that would break, or does not carry, the pairing of the rows
+int guidance_refusal(const fvhd_llm* c, const char* who, const char* why)
+{
+    if (!guidance_on(c)) return 0;
+    return lfail(std::string(who) + ": guidance is on (fvhd_llm_set_guidance) - " + why + "; switch it off (scale 1) around the call");
+}
+
 }  // namespace
 
 std::string processors_error(float repetition_penalty, int no_repeat_ngram_size, int min_new_tokens, const int32_t* eos_ids, int n_eos,
@@ -245,9 +260,13 @@ int fvhd_llm_start(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* ke
     if (batch < 1 || batch > c->dc_batch) return lfail("fvhd_llm_start: batch must be in [1, the batch of fvhd_llm_cache_reserve]");
     if (seq_len < 1 || seq_len > c->dc_cap) return lfail("fvhd_llm_start: seq_len must be in [1, the capacity of fvhd_llm_cache_reserve]");
     if (int e = dec_embedding_error(c, "fvhd_llm_start")) return e;
+    const bool gd = guidance_on(c);
+    if (gd)
+        if (int e = guidance_rows_error("fvhd_llm_start", batch)) return e;
+    const int R = gd ? batch / 2 : batch;                        // the rows the choice is made on: under guidance the G conditional ones
     const bool con = constraint_on(c);
     if (con)
-        if (int e = constraint_start_error(c, "fvhd_llm_start", batch)) return e;
+        if (int e = constraint_start_error(c, "fvhd_llm_start", R)) return e;
     LLM_ON_DEVICE(c);
     hipStream_t st = (hipStream_t)stream;
     const int L = c->L, nkv = c->nkv, hd = c->hd, T = seq_len, B = batch, cap = c->dc_cap;
@@ -282,36 +301,40 @@ int fvhd_llm_start(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* ke
     if (he == hipSuccess)
         he = key_valid ? hipMemcpy2DAsync(c->mask, cap, key_valid, T, T, B, hipMemcpyDeviceToDevice, st) : hipMemset2DAsync(c->mask, cap, 1, T, B, st);
     if (he != hipSuccess) return lhip("key mask copy", he);
+    // guidance first, where transformers puts it: the guided scores replace the conditional rows before anything else reads them
+    if (gd) LCHECK(fvhd_launch_dec_guidance(st, logits, R, c->V, c->guid_scale, c->guid_ws, nullptr), "first-token guidance");
     const bool proc = processors_on(c);
     c->hist_started = proc;
     if (proc) {
         // an empty history: no token is in the bitmap, and the launch zeroes the rows' history counts; then the processors on the
         // prefill's logits, before either choice reads them
-        if ((he = hipMemsetAsync(c->hist_seen, 0, (size_t)B * ((c->V + 31) / 32) * 4, st)) != hipSuccess) return lhip("history bitmap reset", he);
-        DecLogitsArgs pa = dec_logits_args(c, logits, B, st);
+        if ((he = hipMemsetAsync(c->hist_seen, 0, (size_t)R * ((c->V + 31) / 32) * 4, st)) != hipSuccess) return lhip("history bitmap reset", he);
+        DecLogitsArgs pa = dec_logits_args(c, logits, R, st);
         pa.start_T = T;
         LCHECK(fvhd_launch_dec_logits_process(st, &pa), "first-token logits processors");
     }
     c->con_started = con;
     if (con) {
         // the rows' start states, then the bans of those states on the prefill's logits: behind the processors, before either choice
-        DecConstrainArgs ca = dec_constrain_args(c, logits, B, st);
+        DecConstrainArgs ca = dec_constrain_args(c, logits, R, st);
         constrain_reset(ca, c);
         LCHECK(fvhd_launch_dec_constrain(st, &ca), "first-token constraint");
     }
     if (c->do_sample) {
         // sampling: the cache state first, so that the draw reads n = the prompt length from the device
         LCHECK(fvhd_launch_dec_start_state(st, c->posv, position_ids, B, T, c->len, c->status), "decode state");
-        DecSampleArgs a = dec_sample_args(c, logits, B);
+        DecSampleArgs a = dec_sample_args(c, logits, R);
         a.len = c->len; a.last = c->last_ids; a.ids_out = next_ids_out;
         LCHECK(fvhd_launch_dec_sample(st, &a, c->sws), "first-token sampling");
     } else {
         // the first token: the same (max, index) pairs + reduce as the decode's lm_head (lowest index on ties), then the cache state
-        LCHECK(fvhd_launch_dec_argmax_blocks(st, logits, c->V, B, c->amax_v, c->amax_i), "first-token argmax (blocks)");
-        LCHECK(fvhd_launch_dec_argmax_finish(st, c->amax_v, c->amax_i, (c->V + 63) / 64, B, c->last_ids, next_ids_out, nullptr, nullptr, nullptr),
+        LCHECK(fvhd_launch_dec_argmax_blocks(st, logits, c->V, R, c->amax_v, c->amax_i), "first-token argmax (blocks)");
+        LCHECK(fvhd_launch_dec_argmax_finish(st, c->amax_v, c->amax_i, (c->V + 63) / 64, R, c->last_ids, next_ids_out, nullptr, nullptr, nullptr),
                "first-token argmax (reduce)");
         LCHECK(fvhd_launch_dec_start_state(st, c->posv, position_ids, B, T, c->len, c->status), "decode state");
     }
+    if (gd) LCHECK(fvhd_launch_dec_guidance_mirror(st, R, c->last_ids, next_ids_out, nullptr, nullptr), "first-token guidance mirror");
+    c->guid_rows = gd ? R : 0;
     c->run_batch = B;
     c->sp_begun = false;                                         // a lookup generation belongs to the sequence it was begun on
     c->ids_stale = false;                                        // the ids chosen here are these rows'
@@ -331,6 +354,9 @@ int fvhd_llm_decode(fvhd_llm* c, const int64_t* token_ids, float* logits_out, in
     if (proc && !c->hist_started)
         return lfail("fvhd_llm_decode: logits processors are on but the sequence was started without them (no token history) - set them "
                      "before fvhd_llm_start");
+    const bool gd = guidance_on(c);
+    if (gd)
+        if (int e = guidance_rows_error("fvhd_llm_decode", c->run_batch)) return e;
     const bool con = constraint_on(c);
     if (con && !c->con_started)
         return lfail("fvhd_llm_decode: a constraint is on (fvhd_llm_set_constraint) but the sequence was started without it (the rows have no "
@@ -338,6 +364,7 @@ int fvhd_llm_decode(fvhd_llm* c, const int64_t* token_ids, float* logits_out, in
     LLM_ON_DEVICE(c);
     hipStream_t st = (hipStream_t)stream;
     const int B = c->run_batch, H = c->H, I = c->I, nh = c->nh, nkv = c->nkv, hd = c->hd, cap = c->dc_cap;
+    const int R = gd ? B / 2 : B;                                // the rows the choice is made on: under guidance the G conditional ones
     const char* w = c->wdev;
     const bool q8 = c->wfmt == FVHD_W_E4M3, q4 = c->wfmt == FVHD_W_MXFP4;
     if (q4 && !c->emb) {
@@ -381,16 +408,17 @@ int fvhd_llm_decode(fvhd_llm* c, const int64_t* token_ids, float* logits_out, in
     }
     DecGemmArgs a = gemm(DEC_EPI_ARGMAX, c->dh, (const float*)(w + c->norm_off), -1, FVHD_MAT_LM_HEAD);
     a.logits = logits_out; a.amax_v = c->amax_v; a.amax_i = c->amax_i;
-    if ((proc || c->lp_on || con) && !a.logits) a.logits = c->dlogits;      // fvhd_llm_set_logprobs: the greedy step keeps its logits too
+    if ((proc || c->lp_on || con || gd) && !a.logits) a.logits = c->dlogits;      // fvhd_llm_set_logprobs: the greedy step keeps its logits too
     c->lp_logits = nullptr;
+    c->guid_rows = gd ? R : 0;
     DecLogitsArgs pa;
     if (proc) {
-        pa = dec_logits_args(c, a.logits, B, st);
+        pa = dec_logits_args(c, a.logits, R, st);
         pa.tok = token_ids; pa.last = c->last_ids; pa.status = c->status;
     }
     DecConstrainArgs ca;
     if (con) {
-        ca = dec_constrain_args(c, a.logits, B, st);
+        ca = dec_constrain_args(c, a.logits, R, st);
         ca.tok = token_ids; ca.last = c->last_ids; ca.status = c->status;
     }
     if (c->do_sample) {
@@ -398,27 +426,31 @@ int fvhd_llm_decode(fvhd_llm* c, const int64_t* token_ids, float* logits_out, in
         // (the cache holds this step's token), and advances positions and length
         if (!a.logits) a.logits = c->dlogits;
         LCHECK(fvhd_launch_dec_gemm(st, &a), "decode final norm + lm_head");
+        if (gd) LCHECK(fvhd_launch_dec_guidance(st, a.logits, R, c->V, c->guid_scale, c->guid_ws, c->status), "decode guidance");      // first, as in transformers
         if (proc) LCHECK(fvhd_launch_dec_logits_process(st, &pa), "decode logits processors");      // one launch over all rows, then the sampler's blocks
         if (con) LCHECK(fvhd_launch_dec_constrain(st, &ca), "decode constraint");                   // behind the processors: advance, then the bans
-        DecSampleArgs sa = dec_sample_args(c, a.logits, B);
+        DecSampleArgs sa = dec_sample_args(c, a.logits, R);
         sa.len = c->len; sa.n_add = 1; sa.last = c->last_ids; sa.ids_out = next_ids_out; sa.posv = c->posv; sa.len_advance = c->len;
         sa.status = c->status;
         LCHECK(fvhd_launch_dec_sample(st, &sa, c->sws), "decode sampling");
+        if (gd) LCHECK(fvhd_launch_dec_guidance_mirror(st, R, c->last_ids, next_ids_out, c->posv, c->status), "decode guidance mirror");
         c->sp_begun = false;
         if (token_ids) c->ids_stale = false;
         c->lp_logits = a.logits;
         return 0;
     }
     LCHECK(fvhd_launch_dec_gemm(st, &a), "decode final norm + lm_head + argmax");
-    if (proc || con) {
-        // the lm_head's fused (max, index) pairs saw the raw logits: the pairs again, ONCE, from the processed and constrained ones (the
-        // first token's launch)
+    if (proc || con || gd) {
+        // the lm_head's fused (max, index) pairs saw the raw logits: the pairs again, ONCE, from the guided, processed and constrained ones
+        // (the first token's launch), for the rows the choice is made on
+        if (gd) LCHECK(fvhd_launch_dec_guidance(st, a.logits, R, c->V, c->guid_scale, c->guid_ws, c->status), "decode guidance");
         if (proc) LCHECK(fvhd_launch_dec_logits_process(st, &pa), "decode logits processors");
         if (con) LCHECK(fvhd_launch_dec_constrain(st, &ca), "decode constraint");
-        LCHECK(fvhd_launch_dec_argmax_blocks(st, a.logits, c->V, B, c->amax_v, c->amax_i), "decode argmax (blocks)");
+        LCHECK(fvhd_launch_dec_argmax_blocks(st, a.logits, c->V, R, c->amax_v, c->amax_i), "decode argmax (blocks)");
     }
-    LCHECK(fvhd_launch_dec_argmax_finish(st, c->amax_v, c->amax_i, (c->V / 16 + 3) / 4, B, c->last_ids, next_ids_out, c->posv, c->len, c->status),
+    LCHECK(fvhd_launch_dec_argmax_finish(st, c->amax_v, c->amax_i, (c->V / 16 + 3) / 4, R, c->last_ids, next_ids_out, c->posv, c->len, c->status),
            "decode argmax reduce");
+    if (gd) LCHECK(fvhd_launch_dec_guidance_mirror(st, R, c->last_ids, next_ids_out, c->posv, c->status), "decode guidance mirror");
     c->sp_begun = false;                                         // a plain step: the token buffer of a lookup generation no longer describes the sequence
     if (token_ids) c->ids_stale = false;                         // the ids chosen on fed ids are these rows'
     c->lp_logits = a.logits;                                     // (NULL: this step kept none)
@@ -442,11 +474,14 @@ int fvhd_llm_extend(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* k
         return lfail("fvhd_llm_extend: logits processors are on (fvhd_llm_set_logits_processors) - their token history has no ids for an embedded "
                      "chunk; switch them off around fvhd_llm_extend");
     if (first_missing_tensor(c) >= 0) return lfail("fvhd_llm_extend: weights incomplete (fvhd_llm_finalize reports the missing tensor)");
+    const bool gd = guidance_on(c);
+    if (gd)
+        if (int e = guidance_rows_error("fvhd_llm_extend", c->run_batch)) return e;
+    const int B = c->run_batch, R = gd ? B / 2 : B;              // R: the rows the choice is made on (under guidance the G conditional ones)
     const bool con = constraint_on(c);
     if (con)
-        if (int e = constraint_start_error(c, "fvhd_llm_extend", c->run_batch)) return e;
+        if (int e = constraint_start_error(c, "fvhd_llm_extend", R)) return e;
     hipStream_t st = (hipStream_t)stream;
-    const int B = c->run_batch;
     float* logits = logits_out ? logits_out : c->dlogits;
     c->lp_logits = nullptr;
     // the prefill's decoder stack on the chunk rows; per layer the append + the attention over slots [0, length + T) (llm_prefill.hip)
@@ -454,23 +489,26 @@ int fvhd_llm_extend(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* k
     LLM_ON_DEVICE(c);
     // the token: the launches of fvhd_llm_start (the sampler's n = the new length = length + T), then the state; all of them gated by
     // the error word the first append sets when length + T > capacity
+    if (gd) LCHECK(fvhd_launch_dec_guidance(st, logits, R, c->V, c->guid_scale, c->guid_ws, c->status), "extend guidance");
     c->con_started = con;
     if (con) {
         // a new answer: the rows' start states again, and their bans on the chunk's last logits
-        DecConstrainArgs ca = dec_constrain_args(c, logits, B, st);
+        DecConstrainArgs ca = dec_constrain_args(c, logits, R, st);
         constrain_reset(ca, c);
         ca.status = c->status;
         LCHECK(fvhd_launch_dec_constrain(st, &ca), "extend constraint");
     }
     if (c->do_sample) {
-        DecSampleArgs a = dec_sample_args(c, logits, B);
+        DecSampleArgs a = dec_sample_args(c, logits, R);
         a.len = c->len; a.n_add = T; a.last = c->last_ids; a.ids_out = next_ids_out; a.status = c->status;
         LCHECK(fvhd_launch_dec_sample(st, &a, c->sws), "extend sampling");
     } else {
-        LCHECK(fvhd_launch_dec_argmax_blocks(st, logits, c->V, B, c->amax_v, c->amax_i), "extend argmax (blocks)");
-        LCHECK(fvhd_launch_dec_argmax_finish(st, c->amax_v, c->amax_i, (c->V + 63) / 64, B, c->last_ids, next_ids_out, nullptr, nullptr, c->status),
+        LCHECK(fvhd_launch_dec_argmax_blocks(st, logits, c->V, R, c->amax_v, c->amax_i), "extend argmax (blocks)");
+        LCHECK(fvhd_launch_dec_argmax_finish(st, c->amax_v, c->amax_i, (c->V + 63) / 64, R, c->last_ids, next_ids_out, nullptr, nullptr, c->status),
                "extend argmax (reduce)");
     }
+    if (gd) LCHECK(fvhd_launch_dec_guidance_mirror(st, R, c->last_ids, next_ids_out, nullptr, c->status), "extend guidance mirror");
+    c->guid_rows = gd ? R : 0;
     LCHECK(fvhd_launch_llm_extend_state(st, c->posv, c->epos_used, B, T, c->len, c->status), "extend state");
     c->sp_begun = false;                                         // a lookup generation belongs to the sequence it was begun on
     c->ids_stale = false;
@@ -489,6 +527,9 @@ int fvhd_llm_cache_rewind(fvhd_llm* c, const int32_t* keep_dev, fvhd_stream_t st
     if (constraint_on(c))
         return lfail("fvhd_llm_cache_rewind: a constraint is on (fvhd_llm_set_constraint) - the rows' automaton states are not rewound; "
                      "switch it off around fvhd_llm_cache_rewind");
+    // rows g and G + g would need equal keeps; the keeps are on the device, and checking them there needs a synchronisation: refused
+    if (int e = guidance_refusal(c, "fvhd_llm_cache_rewind", "rows g and G + g must keep equal lengths, which cannot be checked without a synchronisation"))
+        return e;
     LLM_ON_DEVICE(c);
     LCHECK(fvhd_launch_llm_cache_rewind((hipStream_t)stream, keep_dev, c->run_batch, c->mask, c->posv, c->dc_cap, c->len, c->status, c->status_host_dev),
            "cache rewind");
@@ -516,6 +557,7 @@ int fvhd_llm_cache_gather(fvhd_llm* c, const int64_t* src_rows, int rows_in, int
 {
     if (!c || !src_rows) return lfail("fvhd_llm_cache_gather: NULL argument");
     if (!c->dc || !c->run_batch) return lfail("fvhd_llm_cache_gather: no started sequence - call fvhd_llm_cache_reserve and fvhd_llm_start first");
+    if (int e = guidance_refusal(c, "fvhd_llm_cache_gather", "a cache reorder would break the pairing of rows g and G + g")) return e;
     if (!c->beam) return lfail("fvhd_llm_cache_gather: no scratch - call fvhd_llm_beam_reserve first");
     if (rows_in < 1 || rows_in > c->dc_batch || rows_out < 1 || rows_out > c->dc_batch)
         return lfail("fvhd_llm_cache_gather: rows_in and rows_out must be in [1, the batch of fvhd_llm_cache_reserve]");
@@ -542,6 +584,7 @@ int fvhd_llm_beam_topk(fvhd_llm* c, const float* logits, const float* beam_score
                        int64_t* cand_index, fvhd_stream_t stream)
 {
     if (!c || !logits || !beam_scores || !cand_scores || !cand_index) return lfail("fvhd_llm_beam_topk: NULL argument");
+    if (int e = guidance_refusal(c, "fvhd_llm_beam_topk", "beam search does not carry the pairing of conditional and unconditional rows")) return e;
     if (!c->beam) return lfail("fvhd_llm_beam_topk: no workspace - call fvhd_llm_beam_reserve first");
     if (constraint_on(c))
         return lfail("fvhd_llm_beam_topk: a constraint is on (fvhd_llm_set_constraint) - beam search does not carry the rows' automaton states; "
@@ -597,6 +640,7 @@ int spec_refusal(const fvhd_llm* c, const char* who, int rows)
 {
     const std::string w(who);
     if (!c->dc || !c->run_batch) return lfail(w + ": no started sequence - call fvhd_llm_cache_reserve and fvhd_llm_start first");
+    if (int e = guidance_refusal(c, who, "the verify step takes one sequence and does not combine a conditional row with an unconditional one")) return e;
     if (!c->spec) return lfail(w + ": no scratch - call fvhd_llm_spec_reserve first");
     if (c->run_batch != 1) return lfail(w + ": the verify step takes ONE sequence (the batch of fvhd_llm_start is " + std::to_string(c->run_batch) + ")");
     if (rows < 2 || rows > c->spec_rows)
@@ -883,8 +927,27 @@ int fvhd_llm_logprobs(fvhd_llm* c, const float* logits, int top_n, float* token_
     }
     if (!c->lp_ws) return lfail("fvhd_llm_logprobs: no scratch - fvhd_llm_set_logprobs(ctx, 1) reserves it (it may be switched off again)");
     LLM_ON_DEVICE(c);
-    LCHECK(fvhd_launch_dec_logprobs((hipStream_t)stream, logits, c->last_ids, c->run_batch, c->V, top_n, token_logprob_out, top_ids_out, top_logprobs_out,
-                                    c->lp_ws, c->status), "logprobs");
+    // (behind a step under guidance: the G conditional rows, whose logits are the guided scores)
+    LCHECK(fvhd_launch_dec_logprobs((hipStream_t)stream, logits, c->last_ids, c->guid_rows ? c->guid_rows : c->run_batch, c->V, top_n, token_logprob_out,
+                                    top_ids_out, top_logprobs_out, c->lp_ws, c->status), "logprobs");
+    return 0;
+}
+
+// ---- classifier-free guidance (include/fvhd.h "LLM classifier-free guidance"; kernels: llm_guidance.hip) ----
+int fvhd_llm_set_guidance(fvhd_llm* c, float scale)
+{
+    if (!c) return lfail("fvhd_llm_set_guidance: ctx is NULL");
+    if (!std::isfinite(scale)) return lfail("fvhd_llm_set_guidance: scale must be finite (1 = off)");
+    if (scale != 1.f && !c->guid_ws) {
+        if (c->V < 1) return lfail("fvhd_llm_set_guidance: the context has no vocabulary yet");
+        LLM_ON_DEVICE(c);
+        hipError_t he = hipDeviceSynchronize();                  // refused while a stream is being captured (like fvhd_llm_set_logprobs)
+        if (he != hipSuccess) return lhip("fvhd_llm_set_guidance: hipDeviceSynchronize", he);
+        const size_t bytes = fvhd_dec_guidance_scratch_bytes(32, c->V);
+        if ((he = hipMalloc((void**)&c->guid_ws, bytes)) != hipSuccess) { c->guid_ws = nullptr; return lhip("hipMalloc(guidance scratch)", he); }
+        if ((he = hipMemset(c->guid_ws, 0, bytes)) != hipSuccess) return lhip("hipMemset(guidance scratch)", he);      // counters start at zero
+    }
+    c->guid_scale = scale;
     return 0;
 }
 

@@ -244,6 +244,7 @@ void fvhd_llm_destroy(fvhd_llm* c)
     if (c->lp_ws) (void)hipFree(c->lp_ws);
     if (c->con_tab) (void)hipFree(c->con_tab);
     if (c->con_state) (void)hipFree(c->con_state);
+    if (c->guid_ws) (void)hipFree(c->guid_ws);
     if (c->pre_kv) (void)hipFree(c->pre_kv);
     if (c->status_host) (void)hipHostFree(c->status_host);
     delete c;

@@ -35,6 +35,10 @@ was made from.
 `greedy` / `sample` with `constraint=TokenAutomaton` (`ml_fastvlm_amd.constraints`, include/fvhd.h "LLM constrained decoding") answer in a
 given form: the step keeps one automaton state per row on the device and bans every token the state does not allow before the choice -
 no host work per token, so it runs inside the captured step beside sampling, the processors and the log-probabilities.
+`greedy` / `sample` with `guidance_scale=s` and `negative_inputs_embeds=` run classifier-free guidance (include/fvhd.h "LLM classifier-free
+guidance", transformers' `UnbatchedClassifierFreeGuidanceLogitsProcessor`): the negative prompts ride as rows G .. 2 G - 1 of the same
+step, two launches combine each pair's log-softmax rows in front of every other edit of the logits, and the choice is made on the G
+conditional rows - no second model forward per token.
 """
 from __future__ import annotations
 
@@ -115,6 +119,57 @@ def generation_position_ids(attention_mask: Optional[torch.Tensor], batch: int, 
     return pos.masked_fill(attention_mask == 0, 0)
 
 
+def normalize_guidance(scale, who: str = "guidance_scale"):
+    """the `guidance_scale` keyword: None or 1 (off) -> None, another finite number -> float; anything else is a ValueError.  Touches no device."""
+    import math
+    if scale is None:
+        return None
+    if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not math.isfinite(scale):
+        raise ValueError(f"{who} must be a finite number (1 = off), got {scale!r}")
+    return None if float(scale) == 1.0 else float(scale)
+
+
+def guidance_batch(inputs_embeds, attention_mask, position_ids, negative_inputs_embeds, negative_attention_mask=None, negative_position_ids=None,
+                   positions: bool = True):
+    """The 2 G-row batch of a run under classifier-free guidance: rows [0, G) the prompts, rows [G, 2 G) the negative prompts, both halves
+    left-padded to the longer length -> (inputs_embeds [2 G, T, hidden], attention_mask [2 G, T], position_ids [2 G, T] or None).
+    A half without a mask is all valid.  positions: a half without position ids gets generate's own from its mask
+    (`generation_position_ids`: cumsum(mask) - 1, 0 on padding) - its real tokens keep the positions they have on their own; False (a chunk
+    for a started cache): None unless both halves bring theirs - `extend` continues every row from its next position."""
+    e, n = inputs_embeds, negative_inputs_embeds
+    if not isinstance(e, torch.Tensor) or e.dim() != 3:
+        raise ValueError(f"guidance: expected inputs_embeds of shape [G, T, hidden], got {tuple(e.shape) if isinstance(e, torch.Tensor) else type(e)}")
+    if not isinstance(n, torch.Tensor) or n.dim() != 3 or n.shape[0] != e.shape[0] or n.shape[2] != e.shape[2]:
+        raise ValueError(f"guidance: negative_inputs_embeds must be [G, T', hidden] = [{e.shape[0]}, T', {e.shape[2]}] (one negative prompt per prompt), "
+                         f"got {tuple(n.shape) if isinstance(n, torch.Tensor) else type(n)}")
+    G = e.shape[0]
+    if G > _lib.MAX_GUIDANCE_PROMPTS:
+        raise ValueError(f"guidance: at most {_lib.MAX_GUIDANCE_PROMPTS} prompts per call (each takes two rows of the step), got {G}")
+    dev = e.device
+    halves = []
+    for x, m, p, name in ((e, attention_mask, position_ids, ""), (n.to(device=dev, dtype=e.dtype), negative_attention_mask, negative_position_ids, "negative_")):
+        Tx = x.shape[1]
+        for t, what in ((m, "attention_mask"), (p, "position_ids")):
+            if t is not None and tuple(t.shape) != (G, Tx):
+                raise ValueError(f"guidance: {name}{what} must be [{G}, {Tx}], got {tuple(t.shape)}")
+        m = torch.ones((G, Tx), device=dev, dtype=torch.long) if m is None else m.to(dev)
+        if p is None and positions:
+            p = generation_position_ids(m, G, Tx, dev)
+        halves.append((x, m, None if p is None else p.to(dev)))
+    T = max(h[0].shape[1] for h in halves)
+    x2 = e.new_zeros((2 * G, T, e.shape[2]))
+    m2 = halves[0][1].new_zeros((2 * G, T))
+    both_pos = all(h[2] is not None for h in halves)
+    p2 = torch.zeros((2 * G, T), device=dev, dtype=torch.long) if both_pos else None
+    for k, (x, m, p) in enumerate(halves):
+        Tx = x.shape[1]
+        x2[k * G:(k + 1) * G, T - Tx:] = x
+        m2[k * G:(k + 1) * G, T - Tx:] = m.to(m2.dtype)
+        if both_pos:
+            p2[k * G:(k + 1) * G, T - Tx:] = p
+    return x2, m2, p2
+
+
 class Qwen2Generator:
     def __init__(self, prefill: Qwen2Prefill, batch: int, capacity: int, embed_tokens: Optional[torch.Tensor] = None,
                  tie_word_embeddings: Optional[bool] = None):
@@ -140,6 +195,7 @@ class Qwen2Generator:
         self._length = None                                      # the cache length as the host knows it (None: unknown - `length()` asks the device)
         self._processors = None                                  # what set_logits_processors last set (None = all off)
         self._constraint = None                                  # the TokenAutomaton set_constraint last set (None = off)
+        self._guidance = None                                    # the scale set_guidance last set (None = off)
         self._ids_stale = False                                  # a rewind / cache_gather since the ids were chosen (`_stale_ids_refusal`)
         self._spec_rows = 0                                      # the largest row count this generator asked of spec_reserve
         self._spec_logits = self._spec_ids = self._spec_emitted = None      # verify()'s output buffers, made on first use
@@ -170,6 +226,7 @@ class Qwen2Generator:
             raise ValueError(f"batch {B} / length {T} exceed the reserved cache (batch {self.batch}, capacity {self.capacity})")
         if pos is None:
             pos = generation_position_ids(am, B, T, self.device).contiguous()
+        self._note_choice(B)
         lg = self._logits[:B] if logits else None
         ids = self._ids[:B]
         with torch.cuda.device(self.device):
@@ -226,6 +283,7 @@ class Qwen2Generator:
         if T < 1 or T > self.capacity:
             raise ValueError(f"extend: the chunk length {T} must be in [1, the reserved capacity {self.capacity}]")
         x, am, pos = self.pre._check(inputs_embeds, attention_mask, position_ids)
+        self._note_choice(B)
         lg = self._logits[:B] if logits else None
         ids = self._ids[:B]
         with torch.cuda.device(self.device):
@@ -269,6 +327,7 @@ class Qwen2Generator:
             raise ValueError("rewind: logits processors are set (set_logits_processors) - their token history is not rewound; "
                              "clear them with set_logits_processors()")
         self._constraint_refusal("rewind", "the rows' automaton states are not rewound")
+        self._guidance_refusal("rewind", "rows g and G + g must keep equal lengths, which the library cannot check without a synchronisation")
         on_device = isinstance(keep, torch.Tensor) and keep.device.type != "cpu"
         k = keep if isinstance(keep, torch.Tensor) else torch.tensor([int(v) for v in keep], dtype=torch.int32)
         if k.dim() != 1 or k.shape[0] != B or k.dtype not in (torch.int32, torch.int64):
@@ -294,6 +353,7 @@ class Qwen2Generator:
             self._stale_ids_refusal("step(ids=None)")
         if ids is not None and (ids.dtype != torch.long or ids.device != self.device or tuple(ids.shape) != (B,) or not ids.is_contiguous()):
             raise ValueError(f"ids must be a contiguous int64 tensor [{B}] on {self.device}")
+        self._note_choice(B)
         lg = self._logits[:B] if logits else None
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().fvhd_llm_decode(self.pre._h, _lib.ptr(ids), _lib.ptr(lg), _lib.ptr(self._ids[:B]), _lib.stream_ptr(self.device)),
@@ -317,7 +377,7 @@ class Qwen2Generator:
         top_ids int64 [B, top_n], top_logprobs fp32 [B, top_n] (contiguous, on the device; the last two may be None for top_n = 0).  logits
         None: the library's buffer - `set_logprobs(True)` before that call, and the call made with logits=False; else the logits that call
         returned.  Host arguments are the same every step: capture-safe."""
-        B, n = self._run_batch, int(top_n)
+        B, n = self._choice_rows(), int(top_n)                   # under guidance: the G conditional rows
         outs = [(token_logprobs, torch.float32, (B,))]
         if n or top_ids is not None or top_logprobs is not None:
             outs += [(top_ids, torch.long, (B, n)), (top_logprobs, torch.float32, (B, n))]
@@ -325,8 +385,8 @@ class Qwen2Generator:
             if t is None or t.dtype != dt or t.device != self.device or tuple(t.shape) != shape or not t.is_contiguous():
                 raise ValueError(f"logprobs: expected a contiguous {dt} tensor {shape} on {self.device}, got "
                                  f"{None if t is None else (t.dtype, tuple(t.shape), t.device)}")
-        if logits is not None and (logits.dtype != torch.float32 or logits.device != self.device or tuple(logits.shape) != (B, self.pre.vocab)
-                                   or not logits.is_contiguous()):
+        if logits is not None and (logits.dtype != torch.float32 or logits.device != self.device or
+                                   tuple(logits.shape) not in ((B, self.pre.vocab), (self._run_batch, self.pre.vocab)) or not logits.is_contiguous()):
             raise ValueError(f"logprobs: logits must be a contiguous fp32 tensor [{B}, {self.pre.vocab}] on {self.device}")
         with torch.cuda.device(self.device):
             _lib.check(_lib.logprobs_lib().fvhd_llm_logprobs(self.pre._h, _lib.ptr(logits), n, _lib.ptr(token_logprobs), _lib.ptr(top_ids),
@@ -362,6 +422,7 @@ class Qwen2Generator:
             raise ValueError("cache_gather: logits processors are set (set_logits_processors) - their token history is not reordered; "
                              "clear them with set_logits_processors()")
         self._constraint_refusal("cache_gather", "the rows' automaton states are not reordered")
+        self._guidance_refusal("cache_gather", "a cache reorder would break the pairing of rows g and G + g")
         if src_rows.dtype != torch.long or src_rows.device != self.device or src_rows.dim() != 1 or not src_rows.is_contiguous():
             raise ValueError(f"src_rows must be a contiguous 1-D int64 tensor on {self.device}")
         rows_out = src_rows.shape[0]
@@ -395,6 +456,7 @@ class Qwen2Generator:
             raise ValueError(f"{who}: logits processors are set (set_logits_processors) - the verify step does not maintain their token history; "
                              "clear them with set_logits_processors()")
         self._constraint_refusal(who, "the verify step does not advance the rows' automaton states")
+        self._guidance_refusal(who, "prompt lookup and the verify step take one sequence and do not take guidance")
 
     def spec_reserve(self, T: int, lookup_capacity: int = 0) -> None:
         """the scratch of verify steps of up to T rows and a token buffer for `lookup_capacity` lookup ids (`fvhd_llm_spec_reserve`).  The
@@ -698,6 +760,70 @@ class Qwen2Generator:
         finally:
             self.set_constraint()
 
+    # ---- classifier-free guidance --------------------------------------------------------------------------------------------------------
+    def set_guidance(self, scale=1.0) -> None:
+        """classifier-free guidance on the logits of start() / extend() / step() from now on (`fvhd_llm_set_guidance`): the started batch is
+        2 G rows, row g a prompt and row G + g its negative prompt, both fed the same token; the guided scores
+        s * (log_softmax(row g) - log_softmax(row G + g)) + log_softmax(row G + g) replace row g in front of the processors, the constraint,
+        the log-probabilities and the choice, which all act on the G conditional rows.  The ids returned have 2 G entries (row G + g = row
+        g); the logits returned hold the guided scores in rows [0, G).  1 (the default) switches it off.  The first call that switches it
+        on allocates the launches' scratch and synchronises; a captured step keeps the scale it was captured with.  Not for beam_search,
+        verify / lookup_greedy / lookup_sample, rewind or cache_gather."""
+        s = normalize_guidance(scale, "set_guidance: scale")
+        if s is None and getattr(self, "_guidance", None) is None and not hasattr(_lib.load(), "fvhd_op_dec_guidance"):
+            return                                               # off on a library that has none: nothing to say
+        if s is not None and torch.cuda.is_current_stream_capturing():
+            raise ValueError("set_guidance: refused while a stream is being captured (the first call that switches guidance on allocates and "
+                             "synchronises) - set it before capturing; a captured step keeps the scale it was captured with")
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.guidance_lib().fvhd_llm_set_guidance(self.pre._h, 1.0 if s is None else s), "fvhd_llm_set_guidance")
+        self._guidance = s
+
+    def _choice_rows(self) -> int:
+        """the rows the last start() / step() / extend() chose ids for: the started batch, under guidance its G conditional rows"""
+        return getattr(self, "_guided_rows", 0) or self._run_batch
+
+    def _note_choice(self, B: int) -> None:
+        on = getattr(self, "_guidance", None) is not None
+        if on and B % 2:
+            raise ValueError(f"guidance is set (set_guidance) and the batch is odd ({B} rows): row g is a prompt and row B / 2 + g its negative prompt")
+        self._guided_rows = B // 2 if on else 0                  # (0: the started batch, which cache_gather may change)
+
+    def _guidance_refusal(self, who: str, why: str) -> None:
+        """the library's refusals while guidance is on (include/fvhd.h), raised before calling in"""
+        if getattr(self, "_guidance", None) is not None:
+            raise ValueError(f"{who}: guidance is set (set_guidance) - {why}; clear it with set_guidance()")
+
+    @contextlib.contextmanager
+    def _guidance_for_run(self, scale):
+        """the `guidance_scale` keyword of greedy() / sample(): set for the run, cleared in a finally.  With none given (None or 1), whatever
+        set_guidance set stays as it is."""
+        if scale is None:
+            yield
+            return
+        self.set_guidance(scale)
+        try:
+            yield
+        finally:
+            self.set_guidance()
+
+    def _guided_inputs(self, who, scale, inputs_embeds, attention_mask, position_ids, negative_inputs_embeds, negative_attention_mask,
+                       negative_position_ids, continue_cache):
+        """the arguments of greedy() / sample() under the `guidance_scale` keyword -> (scale or None, inputs_embeds, attention_mask,
+        position_ids): with guidance the 2 G-row batch of `guidance_batch`.  Touches no device beyond building that batch."""
+        s = normalize_guidance(scale, f"{who}: guidance_scale")
+        if s is None:
+            if negative_inputs_embeds is not None or negative_attention_mask is not None or negative_position_ids is not None:
+                raise ValueError(f"{who}: negative_inputs_embeds / negative_attention_mask / negative_position_ids are given without a guidance_scale != 1")
+            return None, inputs_embeds, attention_mask, position_ids
+        if negative_inputs_embeds is None:
+            raise ValueError(f"{who}: guidance_scale = {s} needs negative_inputs_embeds - the unconditional prompt of every row (e.g. the prompt without its image)")
+        x, m, p = guidance_batch(inputs_embeds, attention_mask, position_ids, negative_inputs_embeds, negative_attention_mask, negative_position_ids,
+                                 positions=not continue_cache)
+        if x.shape[0] > self.batch:
+            raise ValueError(f"{who}: {x.shape[0] // 2} prompts under guidance take {x.shape[0]} rows, the reserved batch is {self.batch}")
+        return s, x, m, p
+
     def _set_greedy(self) -> None:
         if _lib.load().fvhd_version() >= _lib.SAMPLING_VERSION:      # a library without sampling is greedy anyway
             self.set_sampling(False)
@@ -708,7 +834,8 @@ class Qwen2Generator:
                max_new_tokens: int = 256, eos_token_id: Union[None, int, Sequence[int]] = None, pad_token_id: Optional[int] = None,
                graph: bool = True, poll_every: int = 16, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0,
                suppress_tokens: Optional[Sequence[int]] = None, continue_cache: bool = False, logprobs: Optional[int] = None,
-               constraint=None, constraint_start=None):
+               constraint=None, constraint_start=None, guidance_scale=None, negative_inputs_embeds: Optional[torch.Tensor] = None,
+               negative_attention_mask: Optional[torch.Tensor] = None, negative_position_ids: Optional[torch.Tensor] = None):
         """transformers' greedy search (`GenerationMixin._sample` with do_sample=False) on the library's steps -> new tokens [B, n].
         graph=True captures one step (decode + the finished-sequence bookkeeping) into a CUDA graph and replays it; "all finished" is
         polled every `poll_every` steps (no host synchronisation per token) and the output trimmed to the step where it happened.
@@ -721,11 +848,20 @@ class Qwen2Generator:
         what it was.
         constraint: a `ml_fastvlm_amd.constraints.TokenAutomaton` (`set_constraint`), set for this run and cleared after it; every row's
         tokens follow it from constraint_start (None: state 0; an int; or one state per row, -1 = unconstrained).  A row that takes an EOS
-        edge is unconstrained behind it, where the run feeds it pads.  With logprobs, the log-probabilities are over the allowed set."""
+        edge is unconstrained behind it, where the run feeds it pads.  With logprobs, the log-probabilities are over the allowed set.
+        guidance_scale=s (finite, != 1) with negative_inputs_embeds [G, T', hidden] (and its mask / position ids): classifier-free
+        guidance (`set_guidance`, set for this run and cleared after it) - transformers' generate(guidance_scale=s, negative_prompt_ids=...).
+        The run builds the 2 G-row batch (`guidance_batch`: both halves left-padded to the longer length, positions from the masks), the
+        step combines each pair's logits before the processors, the constraint, the log-probabilities and the choice, and every step feeds
+        row G + g the token of row g.  The return shapes are those of G prompts; logprobs are the log-softmax of the guided scores.  With
+        continue_cache=True the chunk carries both halves, for a cache that was started under guidance.  At most 32 prompts."""
         logprobs = normalize_logprobs(logprobs, self.pre.vocab)
+        gs, inputs_embeds, attention_mask, position_ids = self._guided_inputs("greedy", guidance_scale, inputs_embeds, attention_mask, position_ids,
+                                                                              negative_inputs_embeds, negative_attention_mask, negative_position_ids,
+                                                                              continue_cache)
         self._set_greedy()
         with self._processors_for_run(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, suppress_tokens), \
-                self._logprobs_for_run(logprobs), self._constraint_for_run(constraint, constraint_start):
+                self._logprobs_for_run(logprobs), self._constraint_for_run(constraint, constraint_start), self._guidance_for_run(gs):
             return self._run(inputs_embeds, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id, graph, poll_every, continue_cache,
                              logprobs)
 
@@ -735,21 +871,27 @@ class Qwen2Generator:
                eos_token_id: Union[None, int, Sequence[int]] = None, pad_token_id: Optional[int] = None, graph: bool = True,
                poll_every: int = 16, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0,
                suppress_tokens: Optional[Sequence[int]] = None, continue_cache: bool = False, logprobs: Optional[int] = None,
-               constraint=None, constraint_start=None):
+               constraint=None, constraint_start=None, guidance_scale=None, negative_inputs_embeds: Optional[torch.Tensor] = None,
+               negative_attention_mask: Optional[torch.Tensor] = None, negative_position_ids: Optional[torch.Tensor] = None):
         """transformers' multinomial sampling (`GenerationMixin._sample` with do_sample=True, num_beams=1: temperature, then top-k, then
         top-p) on the library's steps -> new tokens [B, n], with greedy's return contract, EOS / pad bookkeeping and graph replay.
         seed None: 63 bits from torch's default CPU generator, so `torch.manual_seed` makes a run repeat.  The same seed gives the same
         tokens, eager or graph; the draws are not torch.multinomial's (only the distribution is the same).  The logits processors of
         `greedy` apply before the temperature, as in transformers.  continue_cache: as in `greedy`.  logprobs: as in `greedy` - the
         log-softmax of the (processed) logits BEFORE temperature / top-k / top-p, not of the distribution the draw was made from.
-        constraint / constraint_start: as in `greedy` - the draw is made among the tokens the row's state allows."""
+        constraint / constraint_start: as in `greedy` - the draw is made among the tokens the row's state allows.
+        guidance_scale / negative_*: as in `greedy` - the draw is made from the guided scores (temperature, top-k and top-p act on them);
+        row g draws with the Philox counter of row g, as without guidance."""
         logprobs = normalize_logprobs(logprobs, self.pre.vocab)
+        gs, inputs_embeds, attention_mask, position_ids = self._guided_inputs("sample", guidance_scale, inputs_embeds, attention_mask, position_ids,
+                                                                              negative_inputs_embeds, negative_attention_mask, negative_position_ids,
+                                                                              continue_cache)
         if seed is None:
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.long).item())
         self.set_sampling(True, temperature, top_k, top_p, seed)
         try:
             with self._processors_for_run(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, suppress_tokens), \
-                    self._logprobs_for_run(logprobs), self._constraint_for_run(constraint, constraint_start):
+                    self._logprobs_for_run(logprobs), self._constraint_for_run(constraint, constraint_start), self._guidance_for_run(gs):
                 return self._run(inputs_embeds, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id, graph, poll_every,
                                  continue_cache, logprobs)
         finally:
@@ -773,7 +915,11 @@ class Qwen2Generator:
              continue_cache=False, logprobs=None):
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be >= 1")
-        B, T = inputs_embeds.shape[:2]
+        rows, T = inputs_embeds.shape[:2]
+        guided = getattr(self, "_guidance", None) is not None
+        if guided and rows % 2:
+            raise ValueError(f"guidance is set (set_guidance) and the batch is odd ({rows} rows): row g is a prompt and row B / 2 + g its negative prompt")
+        B = rows // 2 if guided else rows                        # the sequences of the result: under guidance the G conditional rows
         past = 0
         if continue_cache:
             if self._run_batch == 0:
@@ -792,6 +938,7 @@ class Qwen2Generator:
         alive = torch.ones((max_new_tokens,), device=dev, dtype=torch.bool)      # alive[i]: some sequence unfinished after token i
         unfinished = torch.ones((B,), device=dev, dtype=torch.bool)
         fed = torch.empty((B,), device=dev, dtype=torch.long)
+        fed_rows = torch.empty((rows,), device=dev, dtype=torch.long) if guided else fed      # what the step is fed: under guidance cat(fed, fed)
         col = torch.zeros((1,), device=dev, dtype=torch.long)
         n_lp = logprobs
         if n_lp is not None:
@@ -805,7 +952,11 @@ class Qwen2Generator:
 
         def post(raw):
             # next_tokens * unfinished + pad * (1 - unfinished); then unfinished &= next_tokens not in eos  (transformers' order)
+            raw = raw[:B]                                        # (under guidance rows [B, 2 B) repeat them)
             fed.copy_(torch.where(unfinished, raw, torch.full_like(raw, pad)))
+            if guided:
+                fed_rows[:B].copy_(fed)
+                fed_rows[B:].copy_(fed)
             if n_lp is not None:
                 # of the logits `raw` was chosen from (the library's buffer), behind the choice; `unfinished` still says whose token is real
                 self.logprobs(n_lp, lp_tok, lp_ids if n_lp else None, lp_top if n_lp else None)
@@ -830,7 +981,7 @@ class Qwen2Generator:
             s.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(s):
                 with torch.cuda.graph(g, stream=s):
-                    _, raw = self.step(fed, logits=False)
+                    _, raw = self.step(fed_rows, logits=False)
                     post(raw)
             torch.cuda.current_stream(dev).wait_stream(s)
         done = 0
@@ -843,7 +994,7 @@ class Qwen2Generator:
                 if g is not None:
                     g.replay()
                 else:
-                    _, raw = self.step(fed, logits=False)
+                    _, raw = self.step(fed_rows, logits=False)
                     post(raw)
             done += k
         self._length = past + T + done                           # replayed steps included: the host counted them
@@ -875,6 +1026,7 @@ class Qwen2Generator:
             raise ValueError("beam_search: logits processors are set (set_logits_processors) - they are not implemented under beam search; "
                              "clear them with set_logits_processors()")
         self._constraint_refusal("beam_search", "beam search does not carry the rows' automaton states")
+        self._guidance_refusal("beam_search", "beam search does not take guidance")
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be >= 1")
         G, T = inputs_embeds.shape[:2]

@@ -63,6 +63,10 @@ accept), next to the plain step the same four ways; every case once per round (-
 reported.  No lookup ids are given, so on random weights a step emits one token but for chance matches (`accepted_per_step`).  Derived: the
 accepted drafts per step at which the lookup step breaks even with the plain one, t_lookup / t_plain - 1.
 
+--guidance: the step under classifier-free guidance (`Qwen2Generator.set_guidance`, csrc/llm_guidance.hip) for G prompts (--batch) = 2 G rows
+against the same build's plain step at B = 2 G and against the stock loop's two eager forwards per token (`measure_guidance`); --out FILE
+also writes the result line to a file.
+
 Full layer counts, random bf16 weights (`tools/ttft.py: build_llm`).  Prints ONE JSON line: per (width, batch) the ms per token of each
 path, the bytes a step must read (packed weights + the KV cache at the mean length) and their fraction of 8 TB/s."""
 from __future__ import annotations
@@ -620,6 +624,60 @@ def measure_lookup_sample(llm, pre, K: int, prompt: int, new: int, dev, repeats:
     return res
 
 
+@torch.no_grad()
+def measure_guidance(llm, pre, G: int, prompt: int, new: int, dev, repeats: int = 3, scale: float = 1.5) -> dict:
+    """--guidance: the step under classifier-free guidance for G prompts (2 G rows: the two guidance launches, the choice on G rows, the mirror
+    launch) against the same build's plain step at B = 2 G (guidance off: launch for launch the step without the feature), graph replay, the
+    two in alternating rounds, medians; and the stock transformers loop doing what generate(guidance_scale=...) does per token - one eager
+    forward of the G conditional rows, a second one of the G unconditional rows on its own cache, and the processor's combination."""
+    from ml_fastvlm_amd.qwen2_decode import Qwen2Generator
+    from ml_fastvlm_amd.qwen2_prefill import kv_to_dynamic_cache
+    cfg = llm.config
+    hidden, B = cfg.hidden_size, 2 * G
+    gen = Qwen2Generator.from_hf(llm, B, prompt + new + 4, prefill=pre)
+    g = torch.Generator(device=dev).manual_seed(0)
+    emb = (0.5 * torch.randn(B, prompt, hidden, device=dev, generator=g)).to(torch.bfloat16)
+    mask = torch.ones(B, prompt, device=dev, dtype=torch.long)
+    res = {"hidden": hidden, "layers": cfg.num_hidden_layers, "prompts": G, "rows": B, "prompt": prompt, "new_tokens": new, "guidance_scale": scale}
+    graphs = {}
+    for name, s in (("plain", 1.0), ("guided", scale)):
+        gen.set_guidance(s)
+        gen.start(emb, mask, logits=False)
+        graphs[name] = _graph_of(lambda: gen.step(logits=False), dev)
+    runs = {"plain": [], "guided": []}
+    for r in range(max(1, repeats)):
+        for name in (("plain", "guided") if r % 2 == 0 else ("guided", "plain")):
+            gen.set_guidance(scale if name == "guided" else 1.0)
+            gen.start(emb, mask, logits=False)
+            runs[name].append(round(_ms_per(graphs[name].replay, new, dev), 4))
+            assert gen.cache_state() == (prompt + new, 0)
+    gen.set_guidance()
+    for name in runs:
+        res[f"{name}_2G_rows_graph_ms_per_token"] = sorted(runs[name])[len(runs[name]) // 2]
+        res[f"{name}_2G_rows_graph_ms_per_token_runs"] = runs[name]
+    res["guidance_adds_ms_per_token"] = round(res["guided_2G_rows_graph_ms_per_token"] - res["plain_2G_rows_graph_ms_per_token"], 4)
+    # the stock loop: two eager forwards per token on two caches, then the processor's arithmetic
+    state = []
+    for half in (slice(0, G), slice(G, B)):
+        logits, k, v = pre(emb[half], mask[half], None, return_kv=True)
+        state.append({"cache": kv_to_dynamic_cache(k, v), "logits": logits})
+    st = {"tok": state[0]["logits"].argmax(-1), "mask": mask[:G], "pos": torch.full((G, 1), prompt - 1, device=dev, dtype=torch.long)}
+
+    def hf_step():
+        st["mask"] = torch.cat([st["mask"], torch.ones(G, 1, device=dev, dtype=torch.long)], 1)
+        st["pos"] = st["pos"] + 1
+        lc, lu = (torch.nn.functional.log_softmax(
+            llm(input_ids=st["tok"][:, None], attention_mask=st["mask"], position_ids=st["pos"], past_key_values=h["cache"], use_cache=True).logits[:, -1].float(),
+            dim=-1) for h in state)
+        st["tok"] = (scale * (lc - lu) + lu).argmax(-1)
+
+    for _ in range(3):
+        hf_step()
+    res["stock_transformers_guidance_ms_per_token"] = round(_ms_per(hf_step, new, dev), 4)
+    res["speedup_guided_graph_vs_stock"] = round(res["stock_transformers_guidance_ms_per_token"] / res["guided_2G_rows_graph_ms_per_token"], 2)
+    return res
+
+
 def _graph_of(fn, dev):
     graph = torch.cuda.CUDAGraph()
     side = torch.cuda.Stream(dev)
@@ -763,8 +821,31 @@ def main():
                     help="the step with a token automaton on (a sparse and a dense state) against off and against torch doing the same from dense tables")
     ap.add_argument("--lookup-sample", type=int, default=0, metavar="K",
                     help="the lookup step with K drafts under greedy and under sampling, without and with --logprobs N (default 5), beside the plain step")
+    ap.add_argument("--guidance", action="store_true",
+                    help="the step under classifier-free guidance (--batch = prompts G, 2 G rows) against the plain step at B = 2 G and the stock loop's two forwards")
+    ap.add_argument("--out", default=None, help="--guidance: also write the JSON result to this file")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
+    if a.guidance:
+        from tools.ttft import build_llm
+        from ml_fastvlm_amd import _lib
+        from ml_fastvlm_amd.qwen2_prefill import Qwen2Prefill
+        rows = []
+        for h in (a.hidden if "--hidden" in sys.argv else [896, 3584]):
+            llm = build_llm(h, dev)
+            pre = Qwen2Prefill.from_hf(llm)
+            for b in a.batch:
+                rows.append(measure_guidance(llm, pre, b, a.prompt, a.new, dev, repeats=max(a.repeats, 3)))
+                torch.cuda.empty_cache()
+            del pre, llm
+            torch.cuda.empty_cache()
+        line = json.dumps({"tool": "decode_bench", "mode": "guidance", "device": torch.cuda.get_device_name(dev),
+                           "library_version": _lib.guidance_lib().fvhd_version(), "results": rows})
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        print(line)
+        return
     if a.lookup_sample:
         from tools.ttft import build_llm
         from ml_fastvlm_amd import _lib
