@@ -66,35 +66,6 @@ int dec_embedding_error(const fvhd_llm* c, const char* who)
                  "fvhd_llm_set_tied_embeddings(ctx, 1) for a model whose lm_head IS its embedding table (tie_word_embeddings)");
 }
 
-// the processors' settings of this enqueue; the history fields of the step (fed ids, length, start) are the caller's to fill
-DecLogitsArgs dec_logits_args(fvhd_llm* c, float* logits, int B, hipStream_t st)
-{
-    DecLogitsArgs a;
-    a.logits = logits; a.B = B; a.V = c->V; a.hist = c->hist; a.cap = c->dc_cap; a.seen = c->hist_seen; a.count = c->hist_count;
-    a.penalty = c->proc_penalty; a.ngram = c->proc_ngram; a.min_new = c->proc_n_eos ? c->proc_min_new : 0;
-    a.eos = c->proc_lists; a.n_eos = c->proc_n_eos; a.sup = c->proc_lists ? c->proc_lists + kMaxEos : nullptr; a.n_sup = c->proc_n_sup;
-    if (c->proc_lists && is_capturing(st)) c->proc_lists_captured = true;     // the caller's graph now reads the lists: retired, never overwritten
-    return a;
-}
-
-// the constraint's tables and states of this enqueue; the fed ids (or the reset to the start states) are the caller's to fill
-DecConstrainArgs dec_constrain_args(fvhd_llm* c, float* logits, int B, hipStream_t st)
-{
-    DecConstrainArgs a;
-    a.logits = logits; a.B = B; a.V = c->V; a.offsets = c->con_tab; a.tokens = c->con_tab + c->con_n_states + 1; a.targets = a.tokens + c->con_n_edges;
-    a.n_states = c->con_n_states; a.states = c->con_state; a.flags = c->con_state + 64;
-    if (is_capturing(st)) c->con_captured = true;                // the caller's graph now reads the tables: retired, never overwritten
-    return a;
-}
-
-// fvhd_llm_start / _extend: the rows take their start states (by value: a captured launch keeps them) and clear their flags
-void constrain_reset(DecConstrainArgs& a, const fvhd_llm* c)
-{
-    a.reset = 1;
-    a.n_start = c->con_n_start;
-    std::copy(c->con_start, c->con_start + 64, a.start);
-}
-
 // what a verify step under sampling, or one that keeps log-probabilities, needs beyond fvhd_llm_spec_reserve's scratch (llm_ctx.h `spx`),
 // for the rows that scratch covers.  Kept while it covers them; growing synchronises, so it is refused on a capturing stream.
 int spec_extra_ensure(fvhd_llm* c, const char* who, hipStream_t st)
@@ -145,6 +116,167 @@ int guidance_refusal(const fvhd_llm* c, const char* who, const char* why)
 {
     if (!guidance_on(c)) return 0;
     return lfail(std::string(who) + ": guidance is on (fvhd_llm_set_guidance) - " + why + "; switch it off (scale 1) around the call");
+}
+
+// a cache rewind / reorder moves K, V, mask and positions only: `done` = "rewound" / "reordered"
+int row_state_refusal(const fvhd_llm* c, const char* who, const char* done)
+{
+    const std::string w(who);
+    if (processors_on(c))
+        return lfail(w + ": logits processors are on (fvhd_llm_set_logits_processors) - their token history is not " + done + "; switch them off around " + w);
+    if (constraint_on(c))
+        return lfail(w + ": a constraint is on (fvhd_llm_set_constraint) - the rows' automaton states are not " + done + "; switch it off around " + w);
+    return 0;
+}
+
+int logprobs_args_error(const fvhd_llm* c, const char* who, int top_n, const float* token_out, const int64_t* top_ids_out, const float* top_out)
+{
+    const std::string w(who);
+    if (!c || !token_out) return lfail(w + ": NULL argument");
+    if (top_n < 0 || top_n > 16) return lfail(w + ": top_n must be in [0, 16] (got " + std::to_string(top_n) + ")");
+    if (top_n > c->V) return lfail(w + ": top_n = " + std::to_string(top_n) + " exceeds the vocabulary (" + std::to_string(c->V) + ")");
+    if (top_n && (!top_ids_out || !top_out)) return lfail(w + ": top_n > 0 needs top_ids_out and top_logprobs_out");
+    return 0;
+}
+
+// ---- from logits to a chosen token: the ONE place that orders the logits edits ----
+struct ChoiceArgs {
+    const char* who = nullptr;     // "first-token" / "decode" / "extend": the launches' LCHECK labels begin with it
+    const char* reduce_what = nullptr;   // the argmax reduce's whole label (the decode's is spelled without parentheses)
+    float* logits = nullptr;       // fp32 [R][V]; under guidance the unconditional rows lie behind them
+    int R = 0;                     // the rows the choice is made on: under guidance the G conditional ones
+    const int* gate = nullptr;     // non-NULL: the launches do nothing while *gate != 0
+    bool step = false;             // a decode step: histories and automaton states advance on `tok` (NULL: on the ids the previous step chose), the
+    const int64_t* tok = nullptr;  // choice advances positions and length, and the lm_head left its fused (max, index) pairs of `logits`;
+                                   // false (fvhd_llm_start / _extend): the rows take their start states
+    int start_T = 0;               // > 0: fvhd_llm_start on a prompt of start_T tokens - the token history begins empty
+    int n_add = 0;                 // the sampler's counter is n = length + n_add
+    int64_t* ids_out = nullptr;
+};
+
+// guidance, processors, constraint, then the sampler or the argmax, then the guidance mirror - with the host's marks of what the sequence
+// was started with.  `state` is fvhd_llm_start's cache-state launch: before the draw, which reads n = the prompt length from the device,
+// and behind the argmax reduce.
+template <class StateLaunch = int (*)()>
+int choose_tokens(fvhd_llm* c, hipStream_t st, const ChoiceArgs& a, StateLaunch state = [] { return 0; })
+{
+    const std::string w(a.who);
+    const bool gd = guidance_on(c), proc = processors_on(c), con = constraint_on(c);
+    int64_t* const posv = a.step ? c->posv : nullptr;
+    c->guid_rows = gd ? a.R : 0;
+    if (a.start_T) c->hist_started = proc;
+    if (!a.step) c->con_started = con;
+    // guidance first, where transformers puts it: the guided scores replace the conditional rows before anything else reads them
+    if (gd) LCHECK(fvhd_launch_dec_guidance(st, a.logits, a.R, c->V, c->guid_scale, c->guid_ws, a.gate), (w + " guidance").c_str());
+    if (proc) {
+        // an empty history: no token is in the bitmap, and the launch zeroes the rows' history counts
+        if (a.start_T)
+            if (hipError_t he = hipMemsetAsync(c->hist_seen, 0, (size_t)a.R * ((c->V + 31) / 32) * 4, st)) return lhip("history bitmap reset", he);
+        DecLogitsArgs pa;
+        pa.logits = a.logits; pa.B = a.R; pa.V = c->V; pa.hist = c->hist; pa.cap = c->dc_cap; pa.seen = c->hist_seen; pa.count = c->hist_count;
+        pa.penalty = c->proc_penalty; pa.ngram = c->proc_ngram; pa.min_new = c->proc_n_eos ? c->proc_min_new : 0;
+        pa.eos = c->proc_lists; pa.n_eos = c->proc_n_eos; pa.sup = c->proc_lists ? c->proc_lists + kMaxEos : nullptr; pa.n_sup = c->proc_n_sup;
+        pa.start_T = a.start_T; pa.status = a.gate;
+        if (a.step) { pa.tok = a.tok; pa.last = c->last_ids; }
+        if (c->proc_lists && is_capturing(st)) c->proc_lists_captured = true;     // the caller's graph now reads the lists: retired, never overwritten
+        LCHECK(fvhd_launch_dec_logits_process(st, &pa), (w + " logits processors").c_str());      // one launch over all rows
+    }
+    if (con) {
+        // behind the processors: the advance on the fed ids, then the bans of the rows' states
+        DecConstrainArgs ca;
+        ca.logits = a.logits; ca.B = a.R; ca.V = c->V; ca.offsets = c->con_tab; ca.tokens = c->con_tab + c->con_n_states + 1;
+        ca.targets = ca.tokens + c->con_n_edges; ca.n_states = c->con_n_states; ca.states = c->con_state; ca.flags = c->con_state + 64; ca.status = a.gate;
+        if (a.step) { ca.tok = a.tok; ca.last = c->last_ids; }
+        else {                                                   // the rows take their start states (by value: a captured launch keeps them), no flags
+            ca.reset = 1; ca.n_start = c->con_n_start;
+            std::copy(c->con_start, c->con_start + 64, ca.start);
+        }
+        if (is_capturing(st)) c->con_captured = true;            // the caller's graph now reads the tables: retired, never overwritten
+        LCHECK(fvhd_launch_dec_constrain(st, &ca), (w + " constraint").c_str());
+    }
+    if (c->do_sample) {
+        if (int e = state()) return e;
+        DecSampleArgs sa = dec_sample_args(c, a.logits, a.R);
+        sa.len = c->len; sa.n_add = a.n_add; sa.last = c->last_ids; sa.ids_out = a.ids_out; sa.posv = posv; sa.len_advance = a.step ? c->len : nullptr;
+        sa.status = a.gate;
+        LCHECK(fvhd_launch_dec_sample(st, &sa, c->sws), (w + " sampling").c_str());
+    } else {
+        // the (max, index) pairs + reduce of the decode's lm_head (lowest index on ties).  Fused pairs saw the raw logits: the pairs
+        // again, ONCE, from the guided, processed and constrained ones.  (vocab % 16 == 0: either way there are (V + 63) / 64 of them)
+        if (!a.step || gd || proc || con)
+            LCHECK(fvhd_launch_dec_argmax_blocks(st, a.logits, c->V, a.R, c->amax_v, c->amax_i), (w + " argmax (blocks)").c_str());
+        LCHECK(fvhd_launch_dec_argmax_finish(st, c->amax_v, c->amax_i, (c->V + 63) / 64, a.R, c->last_ids, a.ids_out, posv, a.step ? c->len : nullptr,
+                                             a.gate), a.reduce_what);
+        if (int e = state()) return e;
+    }
+    if (gd) LCHECK(fvhd_launch_dec_guidance_mirror(st, a.R, c->last_ids, a.ids_out, posv, a.gate), (w + " guidance mirror").c_str());
+    return 0;
+}
+
+// ---- the decoder layers and the lm_head on the decode GEMM, for the rows of a decode step or of a verify step ----
+struct DecRows {
+    const char* who = nullptr;     // "decode" / "verify": the launches' LCHECK labels begin with it
+    const char* lm_head_what = nullptr;  // the lm_head launch's whole label
+    void *h = nullptr, *q = nullptr, *att = nullptr, *act = nullptr;      // bf16 rows: hidden (the embedded tokens), q, attention output, MLP activation
+    const int64_t* pos = nullptr;  // the rows' positions
+    int rows = 0;
+    const int* gate = nullptr;     // the launches do nothing while *gate != 0
+    float* rstd = nullptr;         // DecGemmArgs::rstd
+    void *ks = nullptr, *vs = nullptr;   // a verify step's staging rows: k / v go there (a "cache" of capacity 1 whose length word is 0) and the
+                                   // attention appends them; NULL: k / v go to the cache's slot *len
+    float* apart = nullptr;        // the attention's partials and counters
+    int* acnt = nullptr;
+    float* logits = nullptr;       // fp32 [rows][V] or NULL; the (max, index) pairs go to the context's
+};
+
+int decode_layers(fvhd_llm* c, hipStream_t st, const DecRows& r)
+{
+    const int H = c->H, I = c->I, nh = c->nh, nkv = c->nkv, hd = c->hd, cap = c->dc_cap;
+    const char* w = c->wdev;
+    const bool q8 = c->wfmt == FVHD_W_E4M3, q4 = c->wfmt == FVHD_W_MXFP4;
+    const std::string who(r.who);
+    const size_t layer_kv = (size_t)c->dc_batch * nkv * cap * hd * 2;
+    auto gemm = [&](int epi, const void* x, const float* norm_w, int layer, int matrix) {
+        const Mat m = mat_of(c, layer, matrix);
+        const fvhd_llm::Plan& p = c->plan[matrix];
+        DecGemmArgs a;
+        a.wscale = q8 ? (const float*)(w + m.soff) : nullptr;
+        a.wblk = q4 ? (const unsigned char*)(w + m.soff) : nullptr;
+        a.x = x; a.ldx = m.K; a.norm_w = norm_w; a.eps = c->eps; a.W = w + m.off; a.N = (int)m.N; a.K = m.K; a.B = r.rows; a.S = p.S; a.cpw = p.cpw;
+        a.part = c->dpart; a.cnt = c->cnt; a.epi = epi; a.status = r.gate; a.rstd = r.rstd;
+        return a;
+    };
+    for (int l = 0; l < c->L; ++l) {
+        const LayerOff& o = c->lo[l];
+        char *kl = c->kcache + l * layer_kv, *vl = c->vcache + l * layer_kv;
+        DecGemmArgs a = gemm(DEC_EPI_QKV, r.h, (const float*)(w + o.ln1), l, FVHD_MAT_QKV);
+        a.bias = (const float*)(w + o.bqkv); a.out = r.q; a.ldo = nh * hd; a.pos = r.pos; a.rope = c->drope; a.P = c->dc_pos; a.theta = c->theta;
+        a.nh = nh; a.nkv = nkv; a.hd = hd;
+        if (r.ks) {
+            a.kc = r.ks; a.vc = r.vs; a.cap = 1; a.len = c->sp_zero;
+            LCHECK(fvhd_launch_dec_gemm(st, &a), "verify q|k|v + rope + staging");
+            LCHECK(fvhd_launch_spec_attention(st, r.q, kl, vl, r.ks, r.vs, c->mask, r.att, r.rows, nh, nkv, hd, cap, c->len, c->att_S, c->att_chunk, r.apart,
+                                              r.acnt, r.gate), "verify attention + cache append");
+        } else {
+            a.kc = kl; a.vc = vl; a.cap = cap; a.len = c->len;
+            LCHECK(fvhd_launch_dec_gemm(st, &a), "decode q|k|v + rope + cache append");
+            LCHECK(fvhd_launch_dec_attention(st, r.q, kl, vl, c->mask, r.att, r.rows, nh, nkv, hd, cap, c->len, 1, c->att_S, c->att_chunk, r.apart, r.acnt,
+                                             r.gate), "decode attention");
+        }
+        a = gemm(DEC_EPI_RESID, r.att, nullptr, l, FVHD_MAT_O);
+        a.resid = r.h; a.out = r.h; a.ldo = H;
+        LCHECK(fvhd_launch_dec_gemm(st, &a), (who + " o_proj + residual").c_str());
+        a = gemm(DEC_EPI_SWIGLU, r.h, (const float*)(w + o.ln2), l, FVHD_MAT_GATE_UP);
+        a.out = r.act; a.ldo = I;
+        LCHECK(fvhd_launch_dec_gemm(st, &a), (who + " rmsnorm + gate|up + silu").c_str());
+        a = gemm(DEC_EPI_RESID, r.act, nullptr, l, FVHD_MAT_DOWN);
+        a.resid = r.h; a.out = r.h; a.ldo = H;
+        LCHECK(fvhd_launch_dec_gemm(st, &a), (who + " down_proj + residual").c_str());
+    }
+    DecGemmArgs a = gemm(DEC_EPI_ARGMAX, r.h, (const float*)(w + c->norm_off), -1, FVHD_MAT_LM_HEAD);
+    a.logits = r.logits; a.amax_v = c->amax_v; a.amax_i = c->amax_i;
+    LCHECK(fvhd_launch_dec_gemm(st, &a), r.lm_head_what);
+    return 0;
 }
 
 }  // namespace
@@ -301,40 +433,14 @@ int fvhd_llm_start(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* ke
     if (he == hipSuccess)
         he = key_valid ? hipMemcpy2DAsync(c->mask, cap, key_valid, T, T, B, hipMemcpyDeviceToDevice, st) : hipMemset2DAsync(c->mask, cap, 1, T, B, st);
     if (he != hipSuccess) return lhip("key mask copy", he);
-    // guidance first, where transformers puts it: the guided scores replace the conditional rows before anything else reads them
-    if (gd) LCHECK(fvhd_launch_dec_guidance(st, logits, R, c->V, c->guid_scale, c->guid_ws, nullptr), "first-token guidance");
-    const bool proc = processors_on(c);
-    c->hist_started = proc;
-    if (proc) {
-        // an empty history: no token is in the bitmap, and the launch zeroes the rows' history counts; then the processors on the
-        // prefill's logits, before either choice reads them
-        if ((he = hipMemsetAsync(c->hist_seen, 0, (size_t)R * ((c->V + 31) / 32) * 4, st)) != hipSuccess) return lhip("history bitmap reset", he);
-        DecLogitsArgs pa = dec_logits_args(c, logits, R, st);
-        pa.start_T = T;
-        LCHECK(fvhd_launch_dec_logits_process(st, &pa), "first-token logits processors");
-    }
-    c->con_started = con;
-    if (con) {
-        // the rows' start states, then the bans of those states on the prefill's logits: behind the processors, before either choice
-        DecConstrainArgs ca = dec_constrain_args(c, logits, R, st);
-        constrain_reset(ca, c);
-        LCHECK(fvhd_launch_dec_constrain(st, &ca), "first-token constraint");
-    }
-    if (c->do_sample) {
-        // sampling: the cache state first, so that the draw reads n = the prompt length from the device
+    // the first token, ungated, of the prefill's logits; the histories and the rows' automaton states begin here
+    ChoiceArgs ch;
+    ch.who = "first-token"; ch.reduce_what = "first-token argmax (reduce)"; ch.logits = logits; ch.R = R; ch.start_T = T; ch.ids_out = next_ids_out;
+    e = choose_tokens(c, st, ch, [&] {
         LCHECK(fvhd_launch_dec_start_state(st, c->posv, position_ids, B, T, c->len, c->status), "decode state");
-        DecSampleArgs a = dec_sample_args(c, logits, R);
-        a.len = c->len; a.last = c->last_ids; a.ids_out = next_ids_out;
-        LCHECK(fvhd_launch_dec_sample(st, &a, c->sws), "first-token sampling");
-    } else {
-        // the first token: the same (max, index) pairs + reduce as the decode's lm_head (lowest index on ties), then the cache state
-        LCHECK(fvhd_launch_dec_argmax_blocks(st, logits, c->V, R, c->amax_v, c->amax_i), "first-token argmax (blocks)");
-        LCHECK(fvhd_launch_dec_argmax_finish(st, c->amax_v, c->amax_i, (c->V + 63) / 64, R, c->last_ids, next_ids_out, nullptr, nullptr, nullptr),
-               "first-token argmax (reduce)");
-        LCHECK(fvhd_launch_dec_start_state(st, c->posv, position_ids, B, T, c->len, c->status), "decode state");
-    }
-    if (gd) LCHECK(fvhd_launch_dec_guidance_mirror(st, R, c->last_ids, next_ids_out, nullptr, nullptr), "first-token guidance mirror");
-    c->guid_rows = gd ? R : 0;
+        return 0;
+    });
+    if (e) return e;
     c->run_batch = B;
     c->sp_begun = false;                                         // a lookup generation belongs to the sequence it was begun on
     c->ids_stale = false;                                        // the ids chosen here are these rows'
@@ -363,8 +469,7 @@ int fvhd_llm_decode(fvhd_llm* c, const int64_t* token_ids, float* logits_out, in
                      "states) - set it before fvhd_llm_start / fvhd_llm_extend");
     LLM_ON_DEVICE(c);
     hipStream_t st = (hipStream_t)stream;
-    const int B = c->run_batch, H = c->H, I = c->I, nh = c->nh, nkv = c->nkv, hd = c->hd, cap = c->dc_cap;
-    const int R = gd ? B / 2 : B;                                // the rows the choice is made on: under guidance the G conditional ones
+    const int B = c->run_batch, H = c->H, cap = c->dc_cap;
     const char* w = c->wdev;
     const bool q8 = c->wfmt == FVHD_W_E4M3, q4 = c->wfmt == FVHD_W_MXFP4;
     if (q4 && !c->emb) {
@@ -377,83 +482,23 @@ int fvhd_llm_decode(fvhd_llm* c, const int64_t* token_ids, float* logits_out, in
         LCHECK(fvhd_launch_dec_embed(st, token_ids, c->last_ids, c->emb ? c->emb : w + c->lm_off, c->V, H, c->dh, c->mask, B, cap, c->len, c->status,
                                      c->status_host_dev), "decode embed");
     }
-    const size_t layer_kv = (size_t)c->dc_batch * nkv * cap * hd * 2;
-    auto gemm = [&](int epi, const void* x, const float* norm_w, int layer, int matrix) {
-        const Mat m = mat_of(c, layer, matrix);
-        const fvhd_llm::Plan& p = c->plan[matrix];
-        DecGemmArgs a;
-        a.wscale = q8 ? (const float*)(w + m.soff) : nullptr;
-        a.wblk = q4 ? (const unsigned char*)(w + m.soff) : nullptr;
-        a.x = x; a.ldx = m.K; a.norm_w = norm_w; a.eps = c->eps; a.W = w + m.off; a.N = (int)m.N; a.K = m.K; a.B = B; a.S = p.S; a.cpw = p.cpw;
-        a.part = c->dpart; a.cnt = c->cnt; a.epi = epi; a.status = c->status; a.rstd = c->dec_rstd_once ? c->drstd : nullptr;
-        return a;
-    };
-    for (int l = 0; l < c->L; ++l) {
-        const LayerOff& o = c->lo[l];
-        DecGemmArgs a = gemm(DEC_EPI_QKV, c->dh, (const float*)(w + o.ln1), l, FVHD_MAT_QKV);
-        a.bias = (const float*)(w + o.bqkv); a.out = c->dq; a.ldo = nh * hd; a.pos = c->posv; a.rope = c->drope; a.P = c->dc_pos; a.theta = c->theta;
-        a.nh = nh; a.nkv = nkv; a.hd = hd; a.kc = c->kcache + l * layer_kv; a.vc = c->vcache + l * layer_kv; a.cap = cap; a.len = c->len;
-        LCHECK(fvhd_launch_dec_gemm(st, &a), "decode q|k|v + rope + cache append");
-        LCHECK(fvhd_launch_dec_attention(st, c->dq, c->kcache + l * layer_kv, c->vcache + l * layer_kv, c->mask, c->datt, B, nh, nkv, hd, cap, c->len, 1,
-                                         c->att_S, c->att_chunk, c->apart, c->cnt + c->cnt_att, c->status), "decode attention");
-        a = gemm(DEC_EPI_RESID, c->datt, nullptr, l, FVHD_MAT_O);
-        a.resid = c->dh; a.out = c->dh; a.ldo = H;
-        LCHECK(fvhd_launch_dec_gemm(st, &a), "decode o_proj + residual");
-        a = gemm(DEC_EPI_SWIGLU, c->dh, (const float*)(w + o.ln2), l, FVHD_MAT_GATE_UP);
-        a.out = c->dact; a.ldo = I;
-        LCHECK(fvhd_launch_dec_gemm(st, &a), "decode rmsnorm + gate|up + silu");
-        a = gemm(DEC_EPI_RESID, c->dact, nullptr, l, FVHD_MAT_DOWN);
-        a.resid = c->dh; a.out = c->dh; a.ldo = H;
-        LCHECK(fvhd_launch_dec_gemm(st, &a), "decode down_proj + residual");
-    }
-    DecGemmArgs a = gemm(DEC_EPI_ARGMAX, c->dh, (const float*)(w + c->norm_off), -1, FVHD_MAT_LM_HEAD);
-    a.logits = logits_out; a.amax_v = c->amax_v; a.amax_i = c->amax_i;
-    if ((proc || c->lp_on || con || gd) && !a.logits) a.logits = c->dlogits;      // fvhd_llm_set_logprobs: the greedy step keeps its logits too
+    DecRows r;
+    r.who = "decode"; r.lm_head_what = c->do_sample ? "decode final norm + lm_head" : "decode final norm + lm_head + argmax";
+    r.h = c->dh; r.q = c->dq; r.att = c->datt; r.act = c->dact; r.pos = c->posv; r.rows = B; r.gate = c->status;
+    r.rstd = c->dec_rstd_once ? c->drstd : nullptr; r.apart = c->apart; r.acnt = c->cnt + c->cnt_att;
+    // the logits are kept where something reads them behind the lm_head: an edit, the sampler, fvhd_llm_set_logprobs
+    r.logits = logits_out ? logits_out : proc || con || gd || c->do_sample || c->lp_on ? c->dlogits : nullptr;
     c->lp_logits = nullptr;
-    c->guid_rows = gd ? R : 0;
-    DecLogitsArgs pa;
-    if (proc) {
-        pa = dec_logits_args(c, a.logits, R, st);
-        pa.tok = token_ids; pa.last = c->last_ids; pa.status = c->status;
-    }
-    DecConstrainArgs ca;
-    if (con) {
-        ca = dec_constrain_args(c, a.logits, R, st);
-        ca.tok = token_ids; ca.last = c->last_ids; ca.status = c->status;
-    }
-    if (c->do_sample) {
-        // sampling replaces the argmax reduce: it reads the logits (the caller's, else the context's buffer), chooses with n = length + 1
-        // (the cache holds this step's token), and advances positions and length
-        if (!a.logits) a.logits = c->dlogits;
-        LCHECK(fvhd_launch_dec_gemm(st, &a), "decode final norm + lm_head");
-        if (gd) LCHECK(fvhd_launch_dec_guidance(st, a.logits, R, c->V, c->guid_scale, c->guid_ws, c->status), "decode guidance");      // first, as in transformers
-        if (proc) LCHECK(fvhd_launch_dec_logits_process(st, &pa), "decode logits processors");      // one launch over all rows, then the sampler's blocks
-        if (con) LCHECK(fvhd_launch_dec_constrain(st, &ca), "decode constraint");                   // behind the processors: advance, then the bans
-        DecSampleArgs sa = dec_sample_args(c, a.logits, R);
-        sa.len = c->len; sa.n_add = 1; sa.last = c->last_ids; sa.ids_out = next_ids_out; sa.posv = c->posv; sa.len_advance = c->len;
-        sa.status = c->status;
-        LCHECK(fvhd_launch_dec_sample(st, &sa, c->sws), "decode sampling");
-        if (gd) LCHECK(fvhd_launch_dec_guidance_mirror(st, R, c->last_ids, next_ids_out, c->posv, c->status), "decode guidance mirror");
-        c->sp_begun = false;
-        if (token_ids) c->ids_stale = false;
-        c->lp_logits = a.logits;
-        return 0;
-    }
-    LCHECK(fvhd_launch_dec_gemm(st, &a), "decode final norm + lm_head + argmax");
-    if (proc || con || gd) {
-        // the lm_head's fused (max, index) pairs saw the raw logits: the pairs again, ONCE, from the guided, processed and constrained ones
-        // (the first token's launch), for the rows the choice is made on
-        if (gd) LCHECK(fvhd_launch_dec_guidance(st, a.logits, R, c->V, c->guid_scale, c->guid_ws, c->status), "decode guidance");
-        if (proc) LCHECK(fvhd_launch_dec_logits_process(st, &pa), "decode logits processors");
-        if (con) LCHECK(fvhd_launch_dec_constrain(st, &ca), "decode constraint");
-        LCHECK(fvhd_launch_dec_argmax_blocks(st, a.logits, c->V, R, c->amax_v, c->amax_i), "decode argmax (blocks)");
-    }
-    LCHECK(fvhd_launch_dec_argmax_finish(st, c->amax_v, c->amax_i, (c->V / 16 + 3) / 4, R, c->last_ids, next_ids_out, c->posv, c->len, c->status),
-           "decode argmax reduce");
-    if (gd) LCHECK(fvhd_launch_dec_guidance_mirror(st, R, c->last_ids, next_ids_out, c->posv, c->status), "decode guidance mirror");
+    if (int e = decode_layers(c, st, r)) return e;
+    // the choice advances positions and length; under sampling it replaces the argmax reduce and draws with n = length + 1 (the cache
+    // holds this step's token)
+    ChoiceArgs ch;
+    ch.who = "decode"; ch.reduce_what = "decode argmax reduce"; ch.logits = r.logits; ch.R = gd ? B / 2 : B; ch.gate = c->status;
+    ch.step = true; ch.tok = token_ids; ch.n_add = 1; ch.ids_out = next_ids_out;
+    if (int e = choose_tokens(c, st, ch)) return e;
     c->sp_begun = false;                                         // a plain step: the token buffer of a lookup generation no longer describes the sequence
     if (token_ids) c->ids_stale = false;                         // the ids chosen on fed ids are these rows'
-    c->lp_logits = a.logits;                                     // (NULL: this step kept none)
+    c->lp_logits = r.logits;                                     // (NULL: this step kept none)
     return 0;
 }
 
@@ -489,26 +534,10 @@ int fvhd_llm_extend(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* k
     LLM_ON_DEVICE(c);
     // the token: the launches of fvhd_llm_start (the sampler's n = the new length = length + T), then the state; all of them gated by
     // the error word the first append sets when length + T > capacity
-    if (gd) LCHECK(fvhd_launch_dec_guidance(st, logits, R, c->V, c->guid_scale, c->guid_ws, c->status), "extend guidance");
-    c->con_started = con;
-    if (con) {
-        // a new answer: the rows' start states again, and their bans on the chunk's last logits
-        DecConstrainArgs ca = dec_constrain_args(c, logits, R, st);
-        constrain_reset(ca, c);
-        ca.status = c->status;
-        LCHECK(fvhd_launch_dec_constrain(st, &ca), "extend constraint");
-    }
-    if (c->do_sample) {
-        DecSampleArgs a = dec_sample_args(c, logits, R);
-        a.len = c->len; a.n_add = T; a.last = c->last_ids; a.ids_out = next_ids_out; a.status = c->status;
-        LCHECK(fvhd_launch_dec_sample(st, &a, c->sws), "extend sampling");
-    } else {
-        LCHECK(fvhd_launch_dec_argmax_blocks(st, logits, c->V, R, c->amax_v, c->amax_i), "extend argmax (blocks)");
-        LCHECK(fvhd_launch_dec_argmax_finish(st, c->amax_v, c->amax_i, (c->V + 63) / 64, R, c->last_ids, next_ids_out, nullptr, nullptr, c->status),
-               "extend argmax (reduce)");
-    }
-    if (gd) LCHECK(fvhd_launch_dec_guidance_mirror(st, R, c->last_ids, next_ids_out, nullptr, c->status), "extend guidance mirror");
-    c->guid_rows = gd ? R : 0;
+    // (a new answer: the rows' start states again, and their bans on the chunk's last logits)
+    ChoiceArgs ch;
+    ch.who = "extend"; ch.reduce_what = "extend argmax (reduce)"; ch.logits = logits; ch.R = R; ch.gate = c->status; ch.n_add = T; ch.ids_out = next_ids_out;
+    if (int e = choose_tokens(c, st, ch)) return e;
     LCHECK(fvhd_launch_llm_extend_state(st, c->posv, c->epos_used, B, T, c->len, c->status), "extend state");
     c->sp_begun = false;                                         // a lookup generation belongs to the sequence it was begun on
     c->ids_stale = false;
@@ -521,12 +550,7 @@ int fvhd_llm_cache_rewind(fvhd_llm* c, const int32_t* keep_dev, fvhd_stream_t st
     if (!c || !keep_dev) return lfail("fvhd_llm_cache_rewind: NULL argument");
     if (!c->dc || !c->run_batch) return lfail("fvhd_llm_cache_rewind: no started sequence - call fvhd_llm_cache_reserve and fvhd_llm_start first");
     if (int e = dec_status_error(c, "fvhd_llm_cache_rewind")) return e;
-    if (processors_on(c))
-        return lfail("fvhd_llm_cache_rewind: logits processors are on (fvhd_llm_set_logits_processors) - their token history is not rewound; "
-                     "switch them off around fvhd_llm_cache_rewind");
-    if (constraint_on(c))
-        return lfail("fvhd_llm_cache_rewind: a constraint is on (fvhd_llm_set_constraint) - the rows' automaton states are not rewound; "
-                     "switch it off around fvhd_llm_cache_rewind");
+    if (int e = row_state_refusal(c, "fvhd_llm_cache_rewind", "rewound")) return e;
     // rows g and G + g would need equal keeps; the keeps are on the device, and checking them there needs a synchronisation: refused
     if (int e = guidance_refusal(c, "fvhd_llm_cache_rewind", "rows g and G + g must keep equal lengths, which cannot be checked without a synchronisation"))
         return e;
@@ -562,12 +586,7 @@ int fvhd_llm_cache_gather(fvhd_llm* c, const int64_t* src_rows, int rows_in, int
     if (rows_in < 1 || rows_in > c->dc_batch || rows_out < 1 || rows_out > c->dc_batch)
         return lfail("fvhd_llm_cache_gather: rows_in and rows_out must be in [1, the batch of fvhd_llm_cache_reserve]");
     if (int e = dec_status_error(c, "fvhd_llm_cache_gather")) return e;
-    if (processors_on(c))
-        return lfail("fvhd_llm_cache_gather: logits processors are on (fvhd_llm_set_logits_processors) - their token history is not reordered; "
-                     "switch them off around fvhd_llm_cache_gather");
-    if (constraint_on(c))
-        return lfail("fvhd_llm_cache_gather: a constraint is on (fvhd_llm_set_constraint) - the rows' automaton states are not reordered; "
-                     "switch it off around fvhd_llm_cache_gather");
+    if (int e = row_state_refusal(c, "fvhd_llm_cache_gather", "reordered")) return e;
     LLM_ON_DEVICE(c);
     DecCacheGatherArgs a;
     a.kc = c->kcache; a.vc = c->vcache; a.layers = c->L; a.batch = c->dc_batch; a.mask = c->mask; a.posv = c->posv; a.src = src_rows;
@@ -663,56 +682,28 @@ int spec_enqueue(fvhd_llm* c, const int64_t* draft, int T, float* logits_out, in
         if (int e = spec_extra_ensure(c, "the verify step", st)) return e;
         if (is_capturing(st)) c->spx_captured = true;
     }
-    const int H = c->H, I = c->I, nh = c->nh, nkv = c->nkv, hd = c->hd, cap = c->dc_cap;
     const char* w = c->wdev;
     const bool q8 = c->wfmt == FVHD_W_E4M3, q4 = c->wfmt == FVHD_W_MXFP4;
     const bool packed = !c->emb;                                 // a tied model: the token rows dequantised from the lm_head codes
     LCHECK(fvhd_launch_spec_embed(st, draft, c->last_ids, c->emb ? c->emb : w + c->lm_off, packed && q8 ? (const float*)(w + c->lm_soff) : nullptr,
-                                  packed && q4 ? w + c->lm_soff : nullptr, c->V, H, c->sp_h, c->mask, T, cap, c->len, c->posv, c->sp_pos, c->status, c->status_host_dev, gate), "verify embed");
-    const size_t layer_kv = (size_t)c->dc_batch * nkv * cap * hd * 2;
-    auto gemm = [&](int epi, const void* x, const float* norm_w, int layer, int matrix) {
-        const Mat m = mat_of(c, layer, matrix);
-        const fvhd_llm::Plan& p = c->plan[matrix];
-        DecGemmArgs a;
-        a.wscale = q8 ? (const float*)(w + m.soff) : nullptr;
-        a.wblk = q4 ? (const unsigned char*)(w + m.soff) : nullptr;
-        a.x = x; a.ldx = m.K; a.norm_w = norm_w; a.eps = c->eps; a.W = w + m.off; a.N = (int)m.N; a.K = m.K; a.B = T; a.S = p.S; a.cpw = p.cpw;
-        a.part = c->dpart; a.cnt = c->cnt; a.epi = epi; a.status = gate;
-        return a;
-    };
-    for (int l = 0; l < c->L; ++l) {
-        const LayerOff& o = c->lo[l];
-        // q|k|v on the decode's launch: per-row positions, k / v into staging row t (a "cache" of capacity 1 whose length word is 0)
-        DecGemmArgs a = gemm(DEC_EPI_QKV, c->sp_h, (const float*)(w + o.ln1), l, FVHD_MAT_QKV);
-        a.bias = (const float*)(w + o.bqkv); a.out = c->sp_q; a.ldo = nh * hd; a.pos = c->sp_pos; a.rope = c->drope; a.P = c->dc_pos; a.theta = c->theta;
-        a.nh = nh; a.nkv = nkv; a.hd = hd; a.kc = c->sp_ks; a.vc = c->sp_vs; a.cap = 1; a.len = c->sp_zero;
-        LCHECK(fvhd_launch_dec_gemm(st, &a), "verify q|k|v + rope + staging");
-        LCHECK(fvhd_launch_spec_attention(st, c->sp_q, c->kcache + l * layer_kv, c->vcache + l * layer_kv, c->sp_ks, c->sp_vs, c->mask, c->sp_att, T, nh, nkv,
-                                          hd, cap, c->len, c->att_S, c->att_chunk, c->sp_apart, c->sp_cnt, gate), "verify attention + cache append");
-        a = gemm(DEC_EPI_RESID, c->sp_att, nullptr, l, FVHD_MAT_O);
-        a.resid = c->sp_h; a.out = c->sp_h; a.ldo = H;
-        LCHECK(fvhd_launch_dec_gemm(st, &a), "verify o_proj + residual");
-        a = gemm(DEC_EPI_SWIGLU, c->sp_h, (const float*)(w + o.ln2), l, FVHD_MAT_GATE_UP);
-        a.out = c->sp_act; a.ldo = I;
-        LCHECK(fvhd_launch_dec_gemm(st, &a), "verify rmsnorm + gate|up + silu");
-        a = gemm(DEC_EPI_RESID, c->sp_act, nullptr, l, FVHD_MAT_DOWN);
-        a.resid = c->sp_h; a.out = c->sp_h; a.ldo = H;
-        LCHECK(fvhd_launch_dec_gemm(st, &a), "verify down_proj + residual");
-    }
-    DecGemmArgs a = gemm(DEC_EPI_ARGMAX, c->sp_h, (const float*)(w + c->norm_off), -1, FVHD_MAT_LM_HEAD);
-    a.logits = logits_out; a.amax_v = c->amax_v; a.amax_i = c->amax_i;
-    if ((samp || lp_n >= 0) && !a.logits) a.logits = c->spx_logits;      // the T fp32 rows the sampler / the logprobs launch read
-    LCHECK(fvhd_launch_dec_gemm(st, &a), "verify final norm + lm_head + argmax");
+                                  packed && q4 ? w + c->lm_soff : nullptr, c->V, c->H, c->sp_h, c->mask, T, c->dc_cap, c->len, c->posv, c->sp_pos, c->status, c->status_host_dev, gate), "verify embed");
+    // the decode's launches at B = T: per-row positions, k / v into staging row t
+    DecRows r;
+    r.who = "verify"; r.lm_head_what = "verify final norm + lm_head + argmax";
+    r.h = c->sp_h; r.q = c->sp_q; r.att = c->sp_att; r.act = c->sp_act; r.pos = c->sp_pos; r.rows = T; r.gate = gate; r.ks = c->sp_ks; r.vs = c->sp_vs;
+    r.apart = c->sp_apart; r.acnt = c->sp_cnt;
+    r.logits = logits_out ? logits_out : samp || lp_n >= 0 ? c->spx_logits : nullptr;      // the T fp32 rows the sampler / the logprobs launch read
+    if (int e = decode_layers(c, st, r)) return e;
     if (samp) {
         // row t draws with the counter (0, length + 1 + t): the draw of the decode step that feeds the same token (sa.n_add = 1 there)
-        DecSampleArgs sa = dec_sample_args(c, a.logits, T);
+        DecSampleArgs sa = dec_sample_args(c, r.logits, T);
         sa.seq_rows = 1; sa.seq_row = 0; sa.len = c->len; sa.n_add = 1; sa.ids_out = ids; sa.status = gate;
         LCHECK(fvhd_launch_dec_sample(st, &sa, c->sws), "verify sampling");
     } else {
         LCHECK(fvhd_launch_dec_argmax_finish(st, c->amax_v, c->amax_i, (c->V / 16 + 3) / 4, T, nullptr, ids, nullptr, nullptr, gate), "verify argmax reduce");
     }
     if (lp_n >= 0)      // of the logits the choice was made from, before temperature / top-k / top-p, as in fvhd_llm_logprobs
-        LCHECK(fvhd_launch_dec_logprobs(st, a.logits, ids, T, c->V, lp_n, c->spx_tok, c->spx_ids, c->spx_top, c->spx_lp_ws, gate), "verify logprobs");
+        LCHECK(fvhd_launch_dec_logprobs(st, r.logits, ids, T, c->V, lp_n, c->spx_tok, c->spx_ids, c->spx_top, c->spx_lp_ws, gate), "verify logprobs");
     return 0;
 }
 
@@ -777,10 +768,7 @@ int fvhd_llm_set_verify_sampling(fvhd_llm* c, int on)
 
 int fvhd_llm_lookup_logprobs(fvhd_llm* c, int top_n, float* token_logprobs_out, int64_t* top_ids_out, float* top_logprobs_out, fvhd_stream_t stream)
 {
-    if (!c || !token_logprobs_out) return lfail("fvhd_llm_lookup_logprobs: NULL argument");
-    if (top_n < 0 || top_n > 16) return lfail("fvhd_llm_lookup_logprobs: top_n must be in [0, 16] (got " + std::to_string(top_n) + ")");
-    if (top_n > c->V) return lfail("fvhd_llm_lookup_logprobs: top_n = " + std::to_string(top_n) + " exceeds the vocabulary (" + std::to_string(c->V) + ")");
-    if (top_n && (!top_ids_out || !top_logprobs_out)) return lfail("fvhd_llm_lookup_logprobs: top_n > 0 needs top_ids_out and top_logprobs_out");
+    if (int e = logprobs_args_error(c, "fvhd_llm_lookup_logprobs", top_n, token_logprobs_out, top_ids_out, top_logprobs_out)) return e;
     if (!c->spec || !c->sp_begun) return lfail("fvhd_llm_lookup_logprobs: no lookup generation - call fvhd_llm_lookup_begin after fvhd_llm_start");
     if (!c->lp_on || !c->lp_ws || c->lp_logits != c->dlogits)
         return lfail("fvhd_llm_lookup_logprobs: the first token's logits are not in the context's buffer - switch fvhd_llm_set_logprobs on before "
@@ -909,10 +897,7 @@ int fvhd_llm_set_logprobs(fvhd_llm* c, int on)
 int fvhd_llm_logprobs(fvhd_llm* c, const float* logits, int top_n, float* token_logprob_out, int64_t* top_ids_out, float* top_logprobs_out,
                       fvhd_stream_t stream)
 {
-    if (!c || !token_logprob_out) return lfail("fvhd_llm_logprobs: NULL argument");
-    if (top_n < 0 || top_n > 16) return lfail("fvhd_llm_logprobs: top_n must be in [0, 16] (got " + std::to_string(top_n) + ")");
-    if (top_n > c->V) return lfail("fvhd_llm_logprobs: top_n = " + std::to_string(top_n) + " exceeds the vocabulary (" + std::to_string(c->V) + ")");
-    if (top_n && (!top_ids_out || !top_logprobs_out)) return lfail("fvhd_llm_logprobs: top_n > 0 needs top_ids_out and top_logprobs_out");
+    if (int e = logprobs_args_error(c, "fvhd_llm_logprobs", top_n, token_logprob_out, top_ids_out, top_logprobs_out)) return e;
     if (!c->dc || !c->run_batch) return lfail("fvhd_llm_logprobs: no started sequence - call fvhd_llm_cache_reserve and fvhd_llm_start first");
     if (int e = dec_status_error(c, "fvhd_llm_logprobs")) return e;
     if (int e = stale_ids_error(c, "fvhd_llm_logprobs")) return e;
