@@ -1,5 +1,6 @@
 """TEST INFRASTRUCTURE ONLY - the helpers the Qwen2 test files share, each defined once: C-ABI plumbing, the comparison contracts,
-sentinel guards, the inputs and launch wrappers of the decode ops, and the small models with their fp32 oracles.  Imported as
+sentinel guards, the inputs and launch wrappers of the decode ops, the automaton, prompts and op wrappers of the step's logits edits, and
+the small models with their fp32 oracles.  Imported as
 decode_reference / prefill_reference are (after the tests directory is put on sys.path; a file that had its own copy of a helper binds
 the shared one to the name it used, `from llm_testlib import ptr as _p`).  Importing it needs
 no GPU: nothing here touches torch.cuda before a function is called, and `transformers` is imported by the functions that use it.
@@ -258,8 +259,82 @@ def oracle_scores(logits, T, k, p):
     return s
 
 
+# ---- the step's logits edits: what the constraint, guidance and step-chain tests share -------------------------------------------------
+def bits(t):
+    """fp32 -> its int32 bit patterns (a bit-for-bit comparison tells -0 from +0 and one NaN from another)"""
+    return t.contiguous().view(torch.int32)
+
+
+AUTOMATON_SIZES = (3, 5, 40, 2000, 7, 1)
+AUTOMATON_WIDE = (300, 500, 400, 2000, 70, 100)      # under the processors: no state whose every edge an n-gram ban could take (such a row is undefined)
+
+
+def make_automaton(seed=0, vocab=4096, sizes=AUTOMATON_SIZES):
+    """6 states; state 0: three tokens that all lead back to it; state 4 has an edge to FREE; the others wander among 1 .. 5"""
+    from ml_fastvlm_amd.constraints import FREE, TokenAutomaton
+    g = torch.Generator().manual_seed(seed)
+    offsets, tokens, targets = [0], [], []
+    for s, k in enumerate(sizes):
+        ids = torch.randperm(vocab, generator=g)[:k].sort().values.tolist()
+        tokens += ids
+        tgt = [0] * k if s == 0 else (1 + torch.randint(0, 5, (k,), generator=g)).tolist()
+        if s == 4:
+            tgt[0] = FREE
+        targets += tgt
+        offsets.append(len(tokens))
+    return TokenAutomaton(offsets, tokens, targets, vocab)
+
+
+def automaton_starts(B, n_states):
+    """rows in different start states, row 1 unconstrained"""
+    from ml_fastvlm_amd.constraints import FREE
+    return [FREE if b == 1 else (b * 5 + 1) % n_states for b in range(B)]
+
+
+def op_logprobs(lib, x, ids, n):
+    """one fvhd_op_dec_logprobs launch on x fp32 [B, W] and ids int64 [B] -> (token log-probabilities [B], top ids [B, n], theirs [B, n])"""
+    B, W = x.shape
+    nbytes = lib.fvhd_dec_logprobs_scratch_bytes(B, W, n)
+    scratch = torch.zeros(nbytes, device="cuda", dtype=torch.uint8)
+    tok = torch.zeros(B, device="cuda")
+    top = torch.zeros(B, n, device="cuda", dtype=torch.long)
+    top_lp = torch.zeros(B, n, device="cuda")
+    check(lib.fvhd_op_dec_logprobs(stream(), ptr(x), ptr(ids), B, W, n, ptr(tok), ptr(top), ptr(top_lp), ptr(scratch), nbytes), "fvhd_op_dec_logprobs")
+    torch.cuda.synchronize()
+    return tok, top, top_lp
+
+
+def op_guidance(lib, raw, s):
+    """fvhd_op_dec_guidance on a copy of raw [2 G, V] -> the guided rows [G, V]"""
+    x = raw.clone()
+    G = x.shape[0] // 2
+    nbytes = lib.fvhd_dec_guidance_scratch_bytes(G, x.shape[1])
+    scratch = torch.zeros(nbytes, device="cuda", dtype=torch.uint8)
+    check(lib.fvhd_op_dec_guidance(stream(), ptr(x), G, x.shape[1], float(s), ptr(scratch), nbytes), "fvhd_op_dec_guidance")
+    torch.cuda.synchronize()
+    return x[:G].contiguous()
+
+
+GUIDANCE_TC, GUIDANCE_TU = 9, 6      # prompt and negative-prompt lengths of `guidance_inputs`: the negative half is left-padded by 3 more
+
+
+def guidance_inputs(m16, G, seed=0, same=False, vocab=4096):
+    """prompts as ids, embeddings from the model's table; row g of either half has g % 3 padded positions on the left -> (prompt embeddings,
+    mask, negative-prompt embeddings, mask)"""
+    g = torch.Generator().manual_seed(seed)
+    ids = torch.randint(10, vocab, (G, GUIDANCE_TC), generator=g).cuda()
+    nids = ids.clone() if same else torch.randint(10, vocab, (G, GUIDANCE_TU), generator=g).cuda()
+    mask, nmask = torch.ones_like(ids), torch.ones_like(nids)
+    for b in range(G):
+        mask[b, :b % 3] = 0
+        nmask[b, :b % 3] = 0
+    emb = m16.get_input_embeddings()
+    with torch.no_grad():
+        return emb(ids), mask, emb(nids), nmask
+
+
 # ---- models: the decode tests' ---------------------------------------------------------------------------------------------------------
-DELTA = 0.02          # fp32 logit margin above which our bf16 step must pick the oracle's token (the steps' logit error is ~10x smaller)
+DELTA = 0.02         # fp32 logit margin above which our bf16 step must pick the oracle's token (the steps' logit error is ~10x smaller)
 
 CONFIGS = {
     "0.5B": dict(hidden_size=896, num_hidden_layers=2, num_attention_heads=14, num_key_value_heads=2, intermediate_size=4864, tie_word_embeddings=True),

@@ -21,28 +21,12 @@ pytestmark = pytest.mark.gpu
 V = 4096
 T = 12
 
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-SIZES = (3, 5, 40, 2000, 7, 1)
-WIDE = (300, 500, 400, 2000, 70, 100)      # under the processors: no state whose every edge an n-gram ban could take (such a row is undefined)
-
-
-def make_automaton(seed=0, vocab=V, sizes=SIZES):
-    """6 states; state 0: three tokens that all lead back to it; state 4 has an edge to FREE; the others wander among 1 .. 5"""
-    g = torch.Generator().manual_seed(seed)
-    offsets, tokens, targets = [0], [], []
-    for s, k in enumerate(sizes):
-        ids = torch.randperm(vocab, generator=g)[:k].sort().values.tolist()
-        tokens += ids
-        tgt = [0] * k if s == 0 else (1 + torch.randint(0, 5, (k,), generator=g)).tolist()
-        if s == 4:
-            tgt[0] = FREE
-        targets += tgt
-        offsets.append(len(tokens))
-    return TokenAutomaton(offsets, tokens, targets, vocab)
+# shared with the step-chain tests and tools/decode_bits.py: defined once in llm_testlib
+_bits = L.bits
+SIZES, WIDE = L.AUTOMATON_SIZES, L.AUTOMATON_WIDE
+make_automaton = L.make_automaton
+_starts = L.automaton_starts
+_op_logprobs = L.op_logprobs
 
 
 @pytest.fixture(scope="module")
@@ -197,19 +181,6 @@ def test_sampling_draws_from_the_masked_logits(lib, small, auto, seed):
     finally:
         A.set_constraint()
         A.set_sampling(False)
-
-
-def _op_logprobs(lib, x, ids, n):
-    B, W = x.shape
-    nbytes = lib.fvhd_dec_logprobs_scratch_bytes(B, W, n)
-    scratch = torch.zeros(nbytes, device="cuda", dtype=torch.uint8)
-    tok = torch.zeros(B, device="cuda")
-    top = torch.zeros(B, n, device="cuda", dtype=torch.long)
-    top_lp = torch.zeros(B, n, device="cuda")
-    L.check(lib.fvhd_op_dec_logprobs(L.stream(), L.ptr(x), L.ptr(ids), B, W, n, L.ptr(tok), L.ptr(top), L.ptr(top_lp), L.ptr(scratch), nbytes),
-            "fvhd_op_dec_logprobs")
-    torch.cuda.synchronize()
-    return tok, top, top_lp
 
 
 def test_logprobs_renormalise_over_the_allowed_set(lib, small, auto):

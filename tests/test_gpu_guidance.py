@@ -15,7 +15,7 @@ import guidance_reference as GR  # noqa: E402
 import llm_testlib as L  # noqa: E402
 import logprobs_reference as LR  # noqa: E402
 from llm_testlib import lib  # noqa: E402,F401
-from logits_testlib import hf_chain  # noqa: E402
+from logits_testlib import hf_chain, hf_guidance  # noqa: E402
 from ml_fastvlm_amd import _lib  # noqa: E402
 from ml_fastvlm_amd.constraints import TokenAutomaton  # noqa: E402
 from ml_fastvlm_amd.qwen2_decode import Qwen2Generator, guidance_batch  # noqa: E402
@@ -24,30 +24,15 @@ pytestmark = pytest.mark.gpu
 
 V = 4096
 NEW = 12
-TC, TU = 9, 6                  # prompt and negative-prompt lengths: the negative half is left-padded by 3 more
+TC, TU = L.GUIDANCE_TC, L.GUIDANCE_TU      # prompt and negative-prompt lengths: the negative half is left-padded by 3 more
 
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
+# shared with the step-chain tests: defined once in llm_testlib
+_bits, _inputs, _op = L.bits, L.guidance_inputs, L.op_guidance
 
 
 @pytest.fixture(scope="module")
 def small():
     return L.models("0.5B", seed=1)
-
-
-def _inputs(m16, G, seed=0, same=False):
-    """prompts as ids, embeddings from the model's table; row g of either half has g % 3 padded positions on the left"""
-    g = torch.Generator().manual_seed(seed)
-    ids = torch.randint(10, V, (G, TC), generator=g).cuda()
-    nids = ids.clone() if same else torch.randint(10, V, (G, TU), generator=g).cuda()
-    mask, nmask = torch.ones_like(ids), torch.ones_like(nids)
-    for b in range(G):
-        mask[b, :b % 3] = 0
-        nmask[b, :b % 3] = 0
-    emb = m16.get_input_embeddings()
-    with torch.no_grad():
-        return emb(ids), mask, emb(nids), nmask
 
 
 def _gen(m16, rows, weights="bf16"):
@@ -63,17 +48,6 @@ def _teacher(U, batch, tokens):
             fed = tokens[:, i - 1].contiguous()
             lg, _ = U.step(torch.cat([fed, fed]))
             yield lg.clone()
-
-
-def _op(lib, raw, s):
-    """fvhd_op_dec_guidance on a copy of raw [2 G, V] -> the guided rows [G, V]"""
-    x = raw.clone()
-    G = x.shape[0] // 2
-    nbytes = lib.fvhd_dec_guidance_scratch_bytes(G, x.shape[1])
-    scratch = torch.zeros(nbytes, device="cuda", dtype=torch.uint8)
-    L.check(lib.fvhd_op_dec_guidance(L.stream(), L.ptr(x), G, x.shape[1], float(s), L.ptr(scratch), nbytes), "fvhd_op_dec_guidance")
-    torch.cuda.synchronize()
-    return x[:G].contiguous()
 
 
 # ---- twin ----------------------------------------------------------------------------------------------------------------------------------
@@ -195,7 +169,7 @@ def _automaton():
 def test_transformers_own_processors_on_the_guided_scores_choose_the_same_tokens(lib, small, what):
     """UnbatchedCFG fed the twin's unconditional logits through a stub, then RepetitionPenalty and NoRepeatNGram, or PrefixConstrained, in
     transformers' order; the guided scores are the op's on the twin's logits, checked against fp64 under the bound"""
-    from transformers.generation.logits_process import PrefixConstrainedLogitsProcessor, UnbatchedClassifierFreeGuidanceLogitsProcessor
+    from transformers.generation.logits_process import PrefixConstrainedLogitsProcessor
     m16, _ = small
     G, s = 3, 1.5
     e, m, ne, nm = _inputs(m16, G, seed=8)
@@ -204,13 +178,7 @@ def test_transformers_own_processors_on_the_guided_scores_choose_the_same_tokens
     kw = dict(repetition_penalty=1.3, no_repeat_ngram_size=2) if what == "processors" else dict(constraint=auto, constraint_start=starts)
     tokens = A.greedy(e, m, None, max_new_tokens=NEW, pad_token_id=0, guidance_scale=s, negative_inputs_embeds=ne, negative_attention_mask=nm, **kw)
 
-    class Stub:
-        def __call__(self, input_ids, **_):
-            return type("Out", (dict,), {"logits": property(lambda o: o["logits"])})(logits=self.uncond[:, None, :], past_key_values=None)
-
-    stub = Stub()
-    cfg = UnbatchedClassifierFreeGuidanceLogitsProcessor(s, stub, unconditional_ids=torch.zeros((G, 1), dtype=torch.long),
-                                                         unconditional_attention_mask=torch.ones((G, 1), dtype=torch.long))
+    cfg, stub = hf_guidance(s, G)
     changed = 0
     for i, raw in enumerate(_teacher(U, guidance_batch(e, m, None, ne, nm, None), tokens)):
         guided = _op(lib, raw, s)

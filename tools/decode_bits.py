@@ -92,7 +92,7 @@ def dump_features(path, new=NEW, names=tuple(CONFIGS)):
     from ml_fastvlm_amd.qwen2_decode import Qwen2Generator
     from ml_fastvlm_amd.qwen2_prefill import Qwen2Prefill
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
-    from test_gpu_decode_constraint import WIDE, make_automaton
+    from llm_testlib import AUTOMATON_WIDE as WIDE, make_automaton
     auto = make_automaton()
     wide = make_automaton(sizes=WIDE)      # under the processors and for top-n log-probabilities: no state an n-gram ban could empty
     out = {"version": _lib.load().fvhd_version(), "device": torch.cuda.get_device_name(0)}
