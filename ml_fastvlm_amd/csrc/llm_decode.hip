@@ -7,7 +7,9 @@
 //                       does not fill the chip; the slices meet in the last-arriving workgroup (fp32 slabs, agent-scope release / acquire,
 //                       summed in slice order: deterministic, no float atomics).  RMSNorm is folded into the operand load (every workgroup
 //                       recomputes the B row statistics), the epilogue is one of: residual add, silu(gate) * up, bias + rotary embedding +
-//                       KV-cache append, or fp32 logits + per-workgroup argmax.
+//                       KV-cache append, or fp32 logits + per-workgroup argmax.  Everything around the main loop - statistics, weight-row
+//                       mapping, slabs, epilogues - is dec_gemm_parts.h, shared with the e4m3 and MXFP4 kernels (llm_w8.hip, llm_w4.hip);
+//                       the hand-off is split_handoff.h.
 //   dec_gemm_wide_kernel   the same for B in [17, 64]: ceil(B / 16) batch tiles of 16 rows per weight fragment, the arithmetic of
 //                       dec_gemm_kernel per tile; the row statistics come from dec_rstd_kernel, once per launch.
 //   dec_attention       single-query grouped-query attention over the cache, split over the key axis (flash-decoding) with the same
@@ -18,36 +20,11 @@
 // captured graph replays the step for a whole generation.
 #include "fvhd_common.h"
 #include "launchers.h"      // (with llm_decode.h: the argument structs)
-#include "rope.h"
+#include "dec_gemm_parts.h"  // better, the row statistics, the split-K meeting, the epilogues (with rope.h, split_handoff.h)
 
 namespace {
 
 FVHD_DEV bf16x8 ld_nt(const bf16* p) { return __builtin_bit_cast(bf16x8, __builtin_nontemporal_load((const u32x4*)p)); }
-
-// the in-launch hand-off of a split reduction (cdna_hip_programming.md §5, "In-launch split-K reduction"): every wave has stored its
-// slab; returns (in every thread) whether this workgroup arrived last for counter `c`, which it then resets for the next launch
-__device__ bool arrive_last(int* c, int n, int* flag)
-{
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const int t = __hip_atomic_fetch_add(c, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int last = t == n - 1;
-        if (last) {
-            __hip_atomic_store(c, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        *flag = last;
-    }
-    __syncthreads();
-    return *flag != 0;
-}
-
-// (value, index) order of torch.argmax: larger value first, the lower index on a tie
-FVHD_DEV bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
 
 }  // namespace
 
@@ -70,25 +47,8 @@ __global__ __launch_bounds__(256) void dec_gemm_kernel(const DecGemmArgs a)
     const bool active = tile < ntiles;                           // wave-uniform
     const int B = a.B, K = a.K;
     const bf16* x = (const bf16*)a.x;
-    if (a.norm_w) {                                              // rmsnorm_kernel's statistics, in its order (identical bits)
-        for (int b = wave; b < B; b += 4) {
-            const bf16* xr = x + (size_t)b * a.ldx;
-            float ss = 0.f;
-            for (int c = lane * 8; c < K; c += 512) {
-                const f32x8 v = bf8_to_f32(*(const bf16x8*)(xr + c));
-#pragma unroll
-                for (int k = 0; k < 8; ++k) ss = __builtin_fmaf(v[k], v[k], ss);
-            }
-            ss = wave_sum(ss);
-            if (lane == 0) rstd[b] = 1.0f / sqrtf(ss / (float)K + a.eps);
-        }
-        __syncthreads();
-    }
-    int wrow = tile * 16 + lr;
-    if constexpr (EPI == DEC_EPI_QKV) {
-        const int tph = a.hd / 16, head = tile / tph, pb = tile % tph;
-        wrow = head * a.hd + (lr < 8 ? pb * 8 + lr : a.hd / 2 + pb * 8 + lr - 8);
-    }
+    dec_row_stats<false>(a, rstd, tid, lane, wave, B, K, x);
+    const int wrow = dec_weight_row<EPI>(a, tile, lr);
     const int xb = min(lr, B - 1);
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     if (active) {
@@ -119,90 +79,21 @@ __global__ __launch_bounds__(256) void dec_gemm_kernel(const DecGemmArgs a)
         }
     }
     if (S > 1) {
-        if (active) *(f32x4*)(a.part + (((size_t)s * ntiles + tile) * 64 + lane) * 4) = acc;
+        dec_slab_store<1>(a.part, &acc, s, ntiles, tile, active, lane);
         if (!arrive_last(a.cnt + column, S, flag)) return;
-        if (active) {
-            acc = f32x4{0.f, 0.f, 0.f, 0.f};
-            for (int t = 0; t < S; ++t) acc += *(const f32x4*)(a.part + (((size_t)t * ntiles + tile) * 64 + lane) * 4);
-        }
+        dec_slab_sum<1>(a.part, &acc, S, ntiles, tile, active, lane);
     }
-    const int b = lr, n0 = tile * 16 + g * 4;                    // this lane's 4 outputs: rows n0 .. n0 + 3 of batch row b
-    if constexpr (EPI == DEC_EPI_RESID) {
-        if (active && b < B) {
-            const f32x4 r = bf4_to_f32(*(const bf16x4*)((const bf16*)a.resid + (size_t)b * a.ldo + n0));
-            *(bf16x4*)((bf16*)a.out + (size_t)b * a.ldo + n0) = f32_to_bf4(r + acc);
-        }
-    } else if constexpr (EPI == DEC_EPI_SWIGLU) {
-        if (active && b < B) {
-            bf16x2 o;
-            o[0] = (bf16)(acc[0] * sigmoidf_fast(acc[0]) * acc[1]);
-            o[1] = (bf16)(acc[2] * sigmoidf_fast(acc[2]) * acc[3]);
-            *(bf16x2*)((bf16*)a.out + (size_t)b * a.ldo + n0 / 2) = o;
-        }
-    } else if constexpr (EPI == DEC_EPI_QKV) {
-        if (active) {
-            const int hd = a.hd, tph = hd / 16, head = tile / tph, pb = tile % tph;
-            const bool first = g < 2;
-            const int i4 = pb * 8 + (g & 1) * 4, d = first ? i4 : hd / 2 + i4;
-            const f32x4 bias = *(const f32x4*)(a.bias + head * hd + d);
-            const f32x4 v = bf4_to_f32(f32_to_bf4(acc + bias));     // the projection's output as the reference holds it (bf16)
-            f32x4 other;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) other[r] = __shfl_xor(v[r], 32, 64);
-            bf16x4 res = f32_to_bf4(v);
-            if (b < B) {
-                if (head < a.nh + a.nkv) {
-                    bf16x4 ra, rb;
-                    rope_rotate(first ? v : other, first ? other : v, (long)a.pos[b], i4, a.rope, hd, a.P, a.theta, ra, rb);
-                    res = first ? ra : rb;
-                }
-                if (head < a.nh) {
-                    *(bf16x4*)((bf16*)a.out + (size_t)b * a.ldo + head * hd + d) = res;
-                } else {
-                    const int kvh = head < a.nh + a.nkv ? head - a.nh : head - a.nh - a.nkv;
-                    bf16* cache = (bf16*)(head < a.nh + a.nkv ? a.kc : a.vc);
-                    const int slot = *a.len;
-                    if (slot >= 0 && slot < a.cap)
-                        *(bf16x4*)(cache + (((size_t)b * a.nkv + kvh) * a.cap + slot) * hd + d) = res;
-                }
-            }
-        }
-    } else if constexpr (EPI == DEC_EPI_ARGMAX) {
-        float bv = -INFINITY;
-        int bi = 0x7fffffff;
-        if (active && b < B) {
-            if (a.logits) *(f32x4*)(a.logits + (size_t)b * a.N + n0) = acc;
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (better(acc[r], n0 + r, bv, bi)) { bv = acc[r]; bi = n0 + r; }
-        }
-#pragma unroll
-        for (int o = 16; o <= 32; o <<= 1) {
-            const float ov = __shfl_xor(bv, o, 64);
-            const int oi = __shfl_xor(bi, o, 64);
-            if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-        }
-        float* rv = sh + 20;
-        int* ri = (int*)(sh + 20 + 64);
-        if (lane < 16) { rv[wave * 16 + lane] = bv; ri[wave * 16 + lane] = bi; }
-        __syncthreads();
-        if (tid < 16 && tid < B) {
-            float v = rv[tid];
-            int i = ri[tid];
-            for (int w = 1; w < 4; ++w)
-                if (better(rv[w * 16 + tid], ri[w * 16 + tid], v, i)) { v = rv[w * 16 + tid]; i = ri[w * 16 + tid]; }
-            a.amax_v[(size_t)blockIdx.x * 16 + tid] = v;
-            a.amax_i[(size_t)blockIdx.x * 16 + tid] = i;
-        }
-    }
+    const int n0 = tile * 16 + g * 4;                            // this lane's 4 outputs: rows n0 .. n0 + 3 of batch row lr
+    dec_gemm_epilogue<EPI, 1>(a, &acc, sh, tid, lane, wave, lr, g, B, tile, active, n0);
 }
 
 // The same GEMM for 17 .. 64 rows: NB = ceil(B / 16) batch tiles of 16 rows in 2 .. 4.  A weight fragment is still read once (ld_nt) and
 // multiplies the NB activation fragments into NB accumulators; lane (lr, g) loads activation row min(t * 16 + lr, B - 1) for tile t and
 // accumulator t holds out[row = g * 4 + r][batch = t * 16 + lr].  Batch tile t does the arithmetic of dec_gemm_kernel on rows
 // [16 t, 16 t + 16) in its order, so a row's bits do not depend on the batch it is decoded in; the split-K slab is [S][N / 16][NB][64][4],
-// the (max, index) pairs [gridDim][16 * NB].  dec_gemm_kernel stays what it was, instruction for instruction: written as the NB = 1 case of
-// this template the compiler scheduled its prologue differently, which cost 0.2-0.5 % of the 0.5B step at B = 1 / 8.
+// the (max, index) pairs [gridDim][16 * NB].  dec_gemm_kernel stays a kernel and a loop of its own: written as the NB = 1 case of this
+// template the compiler scheduled its prologue differently, which cost 0.2-0.5 % of the 0.5B step at B = 1 / 8.  The parts
+// around the loops are shared (dec_gemm_parts.h): they leave both kernels' prologues and loops as they were.
 template <int EPI, int NB>
 __global__ __launch_bounds__(256) void dec_gemm_wide_kernel(const DecGemmArgs a)
 {
@@ -218,29 +109,8 @@ __global__ __launch_bounds__(256) void dec_gemm_wide_kernel(const DecGemmArgs a)
     const bool active = tile < ntiles;                           // wave-uniform
     const int B = a.B, K = a.K;
     const bf16* x = (const bf16*)a.x;
-    if (a.norm_w) {
-        if (a.rstd) {                                            // dec_rstd_kernel wrote them once for the launch
-            if (tid < B) rstd[tid] = a.rstd[tid];
-        } else {                                                 // rmsnorm_kernel's statistics, in its order (identical bits)
-            for (int b = wave; b < B; b += 4) {
-                const bf16* xr = x + (size_t)b * a.ldx;
-                float ss = 0.f;
-                for (int c = lane * 8; c < K; c += 512) {
-                    const f32x8 v = bf8_to_f32(*(const bf16x8*)(xr + c));
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) ss = __builtin_fmaf(v[k], v[k], ss);
-                }
-                ss = wave_sum(ss);
-                if (lane == 0) rstd[b] = 1.0f / sqrtf(ss / (float)K + a.eps);
-            }
-        }
-        __syncthreads();
-    }
-    int wrow = tile * 16 + lr;
-    if constexpr (EPI == DEC_EPI_QKV) {
-        const int tph = a.hd / 16, head = tile / tph, pb = tile % tph;
-        wrow = head * a.hd + (lr < 8 ? pb * 8 + lr : a.hd / 2 + pb * 8 + lr - 8);
-    }
+    dec_row_stats<true>(a, rstd, tid, lane, wave, B, K, x);
+    const int wrow = dec_weight_row<EPI>(a, tile, lr);
     int xb[NB];
     f32x4 acc[NB];
 #pragma unroll
@@ -285,105 +155,12 @@ __global__ __launch_bounds__(256) void dec_gemm_wide_kernel(const DecGemmArgs a)
         }
     }
     if (S > 1) {
-        if (active) {
-#pragma unroll
-            for (int t = 0; t < NB; ++t) *(f32x4*)(a.part + ((((size_t)s * ntiles + tile) * NB + t) * 64 + lane) * 4) = acc[t];
-        }
+        dec_slab_store<NB>(a.part, acc, s, ntiles, tile, active, lane);
         if (!arrive_last(a.cnt + column, S, flag)) return;
-        if (active) {
-#pragma unroll
-            for (int t = 0; t < NB; ++t) {
-                acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-                for (int u = 0; u < S; ++u) acc[t] += *(const f32x4*)(a.part + ((((size_t)u * ntiles + tile) * NB + t) * 64 + lane) * 4);
-            }
-        }
+        dec_slab_sum<NB>(a.part, acc, S, ntiles, tile, active, lane);
     }
     const int n0 = tile * 16 + g * 4;                            // this lane's 4 outputs of batch tile t: rows n0 .. n0 + 3 of batch row t * 16 + lr
-    if constexpr (EPI == DEC_EPI_RESID) {
-#pragma unroll
-        for (int t = 0; t < NB; ++t) {
-            const int b = t * 16 + lr;
-            if (active && b < B) {
-                const f32x4 r = bf4_to_f32(*(const bf16x4*)((const bf16*)a.resid + (size_t)b * a.ldo + n0));
-                *(bf16x4*)((bf16*)a.out + (size_t)b * a.ldo + n0) = f32_to_bf4(r + acc[t]);
-            }
-        }
-    } else if constexpr (EPI == DEC_EPI_SWIGLU) {
-#pragma unroll
-        for (int t = 0; t < NB; ++t) {
-            const int b = t * 16 + lr;
-            if (active && b < B) {
-                bf16x2 o;
-                o[0] = (bf16)(acc[t][0] * sigmoidf_fast(acc[t][0]) * acc[t][1]);
-                o[1] = (bf16)(acc[t][2] * sigmoidf_fast(acc[t][2]) * acc[t][3]);
-                *(bf16x2*)((bf16*)a.out + (size_t)b * a.ldo + n0 / 2) = o;
-            }
-        }
-    } else if constexpr (EPI == DEC_EPI_QKV) {
-        if (active) {
-            const int hd = a.hd, tph = hd / 16, head = tile / tph, pb = tile % tph;
-            const bool first = g < 2;
-            const int i4 = pb * 8 + (g & 1) * 4, d = first ? i4 : hd / 2 + i4;
-            const f32x4 bias = *(const f32x4*)(a.bias + head * hd + d);
-#pragma unroll
-            for (int t = 0; t < NB; ++t) {
-                const int b = t * 16 + lr;
-                const f32x4 v = bf4_to_f32(f32_to_bf4(acc[t] + bias));  // the projection's output as the reference holds it (bf16)
-                f32x4 other;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) other[r] = __shfl_xor(v[r], 32, 64);
-                bf16x4 res = f32_to_bf4(v);
-                if (b < B) {
-                    if (head < a.nh + a.nkv) {
-                        bf16x4 ra, rb;
-                        rope_rotate(first ? v : other, first ? other : v, (long)a.pos[b], i4, a.rope, hd, a.P, a.theta, ra, rb);
-                        res = first ? ra : rb;
-                    }
-                    if (head < a.nh) {
-                        *(bf16x4*)((bf16*)a.out + (size_t)b * a.ldo + head * hd + d) = res;
-                    } else {
-                        const int kvh = head < a.nh + a.nkv ? head - a.nh : head - a.nh - a.nkv;
-                        bf16* cache = (bf16*)(head < a.nh + a.nkv ? a.kc : a.vc);
-                        const int slot = *a.len;
-                        if (slot >= 0 && slot < a.cap)
-                            *(bf16x4*)(cache + (((size_t)b * a.nkv + kvh) * a.cap + slot) * hd + d) = res;
-                    }
-                }
-            }
-        }
-    } else if constexpr (EPI == DEC_EPI_ARGMAX) {
-        float* rv = sh + 16 * NB + 4;                            // [wave][batch tile][16] best value / index of the wave's 16 weight rows
-        int* ri = (int*)(rv + 64 * NB);
-#pragma unroll
-        for (int t = 0; t < NB; ++t) {
-            const int b = t * 16 + lr;
-            float bv = -INFINITY;
-            int bi = 0x7fffffff;
-            if (active && b < B) {
-                if (a.logits) *(f32x4*)(a.logits + (size_t)b * a.N + n0) = acc[t];
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    if (better(acc[t][r], n0 + r, bv, bi)) { bv = acc[t][r]; bi = n0 + r; }
-            }
-#pragma unroll
-            for (int o = 16; o <= 32; o <<= 1) {
-                const float ov = __shfl_xor(bv, o, 64);
-                const int oi = __shfl_xor(bi, o, 64);
-                if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-            }
-            if (lane < 16) { rv[(wave * NB + t) * 16 + lane] = bv; ri[(wave * NB + t) * 16 + lane] = bi; }
-        }
-        __syncthreads();
-        if (tid < 16 * NB && tid < B) {
-            const int t = tid >> 4, r = tid & 15;
-            float v = rv[t * 16 + r];
-            int i = ri[t * 16 + r];
-            for (int w = 1; w < 4; ++w)
-                if (better(rv[(w * NB + t) * 16 + r], ri[(w * NB + t) * 16 + r], v, i)) { v = rv[(w * NB + t) * 16 + r]; i = ri[(w * NB + t) * 16 + r]; }
-            a.amax_v[(size_t)blockIdx.x * (16 * NB) + tid] = v;
-            a.amax_i[(size_t)blockIdx.x * (16 * NB) + tid] = i;
-        }
-    }
+    dec_gemm_epilogue<EPI, NB>(a, acc, sh, tid, lane, wave, lr, g, B, tile, active, n0);
 }
 
 // The RMSNorm row statistics of a wide launch (B > 16), once per launch site instead of once per workgroup of dec_gemm_kernel: wave = row,
@@ -500,7 +277,7 @@ __global__ __launch_bounds__(256) void dec_attention_kernel(const bf16* __restri
 #pragma unroll
             for (int i = 0; i < DPL; ++i) slab[2 + lane * DPL + i] = O[i];
         }
-        if (!arrive_last(cnt + bh, S, flag)) return;             // every wave joins the hand-off's barriers
+        if (!arrive_last(cnt + bh, S, flag)) return;             // every wave joins the hand-off's barriers (split_handoff.h)
         if (wave != 0) return;
         M = -INFINITY;
         for (int t = 0; t < S; ++t) M = fmaxf(M, part[((size_t)bh * S + t) * (HD + 2)]);

@@ -23,6 +23,7 @@
 // same token - and, in a decode step, advances the positions of rows G .. 2 G - 1, which the choice's launch (run on G rows) left alone.
 #include "fvhd_common.h"
 #include "launchers.h"
+#include "split_handoff.h"  // publish, arrive_last_published
 
 namespace {
 
@@ -54,28 +55,6 @@ GdWs carve(void* base, int rows, int S)
     p += al256g((size_t)4 * rows * S);
     w.stat = (float*)p;
     return w;
-}
-
-// the hand-off of llm_logprobs.hip: thread 0 has stored the slice's two words write-through (agent-scope relaxed atomic stores), waits
-// until they have left, and adds to the row's counter; true (in every thread) in the workgroup that arrived last, behind an agent-scope
-// acquire.  The last arriver puts the counter back to zero.
-__device__ void publish(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ bool arrive_last(int* c, int n, int* flag)
-{
-    if (threadIdx.x == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const int t = __hip_atomic_fetch_add(c, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int last = t == n - 1;
-        if (last) {
-            __hip_atomic_store(c, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        *flag = last;
-    }
-    __syncthreads();
-    return *flag != 0;
 }
 
 // the apply's arithmetic: five subtractions / one product / one addition, each rounded once (no fused multiply-add)
@@ -116,7 +95,7 @@ __global__ __launch_bounds__(256) void dec_guidance_stats_kernel(const float* __
         publish(w.pm + b * S + s, m);
         publish(w.ps + b * S + s, (reds[0] + reds[1]) + (reds[2] + reds[3]));
     }
-    if (!arrive_last(w.cnt + b * GD_CNT_STRIDE, S, &flag)) return;
+    if (!arrive_last_published(w.cnt + b * GD_CNT_STRIDE, S, &flag)) return;
     // ---- the row's last workgroup: merge the slices in one wave ----
     if (wave == 0) {
         const float ms = lane < S ? w.pm[b * S + lane] : -INFINITY;

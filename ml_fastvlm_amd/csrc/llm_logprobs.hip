@@ -15,11 +15,12 @@
 //   C  top_n rounds of "block maximum of the threads' bests": the thread that owned the winner looks through its elements again for its best
 //      below it, every other thread's best is still valid
 // Slice partials (m, sum, the top_n candidate words) go to the scratch; the last-arriving workgroup of a row (the in-launch hand-off of
-// llm_decode.hip / llm_sample.hip, which leaves the counter at zero; `arrive_last` below has a lighter producer side) merges them: M, Z = sum_s sum_s exp(m_s - M) in a butterfly over the
+// split_handoff.h, which leaves the counter at zero: `arrive_last_published`, the protocol with the lighter producer side) merges them: M, Z = sum_s sum_s exp(m_s - M) in a butterfly over the
 // slices, and top_n rounds of block maximum over the S * top_n candidates, which sit in registers (4 per thread).  The ids depend on
 // comparisons of the input values only: they are exact.  The same inputs give the same bits, eager or replayed.
 #include "fvhd_common.h"
 #include "launchers.h"
+#include "split_handoff.h"  // publish, arrive_last_published
 
 namespace {
 
@@ -93,31 +94,6 @@ FVHD_DEV u64 block_max(u64 v, u64* buf)
     return umax64(umax64(buf[0], buf[1]), umax64(buf[2], buf[3]));
 }
 
-// The in-launch hand-off of llm_decode.hip / llm_sample.hip - a counter per row, the last arriver merges and resets it - with a lighter
-// producer side: ONE thread stores the slice's few partial words write-through (agent-scope relaxed atomic stores), waits until they have
-// left, and adds to the counter.  The release fence of the other files is an L2 write-back per workgroup; those serialise within an XCD,
-// and at 64 rows x 64 slices they were most of the launch (87 us against 25).  Thread 0 only; true (in every thread) in the
-// workgroup that arrived last, behind an agent-scope acquire.
-template <typename T>
-FVHD_DEV void publish(T* p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ bool arrive_last(int* c, int n, int* flag)
-{
-    if (threadIdx.x == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const int t = __hip_atomic_fetch_add(c, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int last = t == n - 1;
-        if (last) {
-            __hip_atomic_store(c, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        *flag = last;
-    }
-    __syncthreads();
-    return *flag != 0;
-}
-
 }  // namespace
 
 __global__ __launch_bounds__(256) void dec_logprobs_kernel(const LpArgs a, const LpWs w)
@@ -163,7 +139,7 @@ __global__ __launch_bounds__(256) void dec_logprobs_kernel(const LpArgs a, const
             best = nb;
         }
     }
-    if (!arrive_last(w.cnt + b * LP_CNT_STRIDE, S, &flag)) return;
+    if (!arrive_last_published(w.cnt + b * LP_CNT_STRIDE, S, &flag)) return;
     // ---- the row's last workgroup: merge the slices ----
     if (wave == 0) {
         const float ms = lane < S ? w.pm[b * S + lane] : -INFINITY;

@@ -25,6 +25,7 @@
 // Everything is deterministic: the same logits, settings, seed and n give the same id, eager or replayed.
 #include "fvhd_common.h"
 #include "launchers.h"      // (with llm_decode.h: the argument structs)
+#include "split_handoff.h"  // arrive_last
 
 namespace {
 
@@ -83,28 +84,6 @@ size_t ws_bytes()
 {
     return al256s(sizeof(SampleRow) * BMAX) + 2 * al256s(4 * BMAX * SMAX) + al256s(4 * BMAX * SMAX * 256) + al256s(8 * BMAX * SMAX * 256) +
            2 * al256s(4 * BMAX * SMAX * 256) + 2 * al256s(4 * BMAX * SMAX) + al256s(4 * (BMAX + 1));
-}
-
-// the in-launch hand-off of llm_decode.hip: every thread's stores are done; true (in every thread) in the workgroup that arrived last for
-// counter `c`, which it resets for the next launch
-__device__ bool arrive_last(int* c, int n, int* flag)
-{
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const int t = __hip_atomic_fetch_add(c, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int last = t == n - 1;
-        if (last) {
-            __hip_atomic_store(c, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        *flag = last;
-    }
-    __syncthreads();
-    return *flag != 0;
 }
 
 // order-preserving key of an fp32 value: a > b <=> key(a) > key(b); -0 and +0 share one key

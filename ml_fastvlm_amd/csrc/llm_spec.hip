@@ -12,35 +12,13 @@
 // bits of the plain step at length *len + t + 1.
 #include "fvhd_common.h"
 #include "launchers.h"
+#include "split_handoff.h"  // arrive_last
 #include "w4_layout.h"  // w4_pos, w4_scale, fp4x8_to_bf8
 #include "w8_layout.h"  // w8_pos, e4m3x8_to_f32
 
 namespace {
 
 typedef unsigned char u8;
-
-
-// the hand-off of a split reduction, as in llm_decode.hip
-__device__ bool arrive_last(int* c, int n, int* flag)
-{
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const int t = __hip_atomic_fetch_add(c, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int last = t == n - 1;
-        if (last) {
-            __hip_atomic_store(c, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        *flag = last;
-    }
-    __syncthreads();
-    return *flag != 0;
-}
-
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------

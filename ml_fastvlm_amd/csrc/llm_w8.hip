@@ -2,11 +2,12 @@
 // one fp32 scale per output row, row n standing for code * scale[n].
 //   quantize_e4m3_kernel   bf16 [N][K] -> codes + scales: scale = 2^ceil(log2(amax_row / 448)) (an all-zero row: 1), codes = w / scale
 //                          rounded to nearest even by v_cvt_pk_fp8_f32; nothing saturates (amax / scale <= 448)
-//   dec_gemm_w8_kernel     dec_gemm_kernel / dec_gemm_wide_kernel (llm_decode.hip) on such a matrix: the same tiles, split-K hand-off,
-//                          slabs and epilogues; the weight fragment is loaded as bytes, converted e4m3 -> fp32 -> bf16 (exact) in
-//                          registers and multiplies the same activation fragments on the same 16 x 16 x 32 bf16 MFMA; the row scale
-//                          multiplies the finished accumulator (after the split-K sum, before the epilogue).  Siblings of the bf16
-//                          kernels, not instantiations of them: those stay what they were, instruction for instruction.
+//   dec_gemm_w8_kernel     dec_gemm_kernel / dec_gemm_wide_kernel (llm_decode.hip) on such a matrix.  What the decode GEMMs share - row
+//                          statistics, weight-row mapping, split-K slabs, epilogues - is dec_gemm_parts.h; this kernel's own is its main
+//                          loop: the weight fragment is loaded as bytes, converted e4m3 -> fp32 -> bf16 (exact) in registers and
+//                          multiplies the same activation fragments on the same 16 x 16 x 32 bf16 MFMA; the row scale multiplies the
+//                          finished accumulator (after the split-K sum, before the epilogue; q|k|v: fused with the bias add).  A kernel
+//                          of its own, not an instantiation of the bf16 kernels: kernels and loops stay separate.
 //   w8_unpack_kernel       codes -> bf16 [N][K] (code * scale, exact for power-of-two scales): the prefill's GEMMs stay bf16 and read
 //                          each matrix from a scratch it is dequantised into right before; also the plain-order read-back / repack
 //   dec_embed_w8_kernel    dec_embed_kernel on the lm_head codes of a tied model
@@ -16,7 +17,7 @@
 // wave's load covers 64 contiguous bytes of 16 rows - the access shape of the bf16 kernel at half the bytes.
 #include "fvhd_common.h"
 #include "launchers.h"      // (with llm_decode.h: the argument structs)
-#include "rope.h"
+#include "dec_gemm_parts.h"  // better, the row statistics, the split-K meeting, the epilogues (with rope.h, split_handoff.h)
 #include "w8_layout.h"  // w8_pos, e4m3x8_to_f32
 
 namespace {
@@ -27,29 +28,6 @@ typedef unsigned char u8;
 FVHD_DEV bf16x8 e4m3x8_to_bf8(uint32_t lo, uint32_t hi) { return f32_to_bf8(e4m3x8_to_f32(lo, hi)); }
 
 FVHD_DEV u32x4 ld_nt16(const u8* p) { return __builtin_nontemporal_load((const u32x4*)p); }
-
-// the hand-off of a split reduction, as in llm_decode.hip
-__device__ bool arrive_last(int* c, int n, int* flag)
-{
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const int t = __hip_atomic_fetch_add(c, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int last = t == n - 1;
-        if (last) {
-            __hip_atomic_store(c, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        *flag = last;
-    }
-    __syncthreads();
-    return *flag != 0;
-}
-
-FVHD_DEV bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
 
 }  // namespace
 
@@ -145,7 +123,7 @@ __global__ __launch_bounds__(256) void dec_embed_w8_kernel(const int64_t* __rest
 // The decode GEMM on e4m3 weights, NB = ceil(B / 16) batch tiles in 1 .. 4.  Lane (lr, g) of a wave owns weight row lr of its tile and
 // loads, per 128-deep chunk, the 16 bytes at 16 g of both 64-byte halves: MFMA steps (0, 1) and (2, 3).  Everything else - the activation
 // fragments, the folded RMSNorm, the order of the MFMAs, the slabs [S][N / 16][NB][64][4] and their sum in slice order, the epilogues - is
-// dec_gemm_kernel's (NB = 1) / dec_gemm_wide_kernel's, so that with every scale = 1 the output has the bits of the bf16 kernel on
+// dec_gemm_kernel's (NB = 1) / dec_gemm_wide_kernel's (the loop by its text, the rest by dec_gemm_parts.h), so that with every scale = 1 the output has the bits of the bf16 kernel on
 // bf16(codes).  The scales of a lane's four output rows multiply its accumulator once, after the split-K sum.
 template <int EPI, int NB>
 __global__ __launch_bounds__(256) void dec_gemm_w8_kernel(const DecGemmArgs a)
@@ -162,29 +140,8 @@ __global__ __launch_bounds__(256) void dec_gemm_w8_kernel(const DecGemmArgs a)
     const bool active = tile < ntiles;                           // wave-uniform
     const int B = a.B, K = a.K;
     const bf16* x = (const bf16*)a.x;
-    if (a.norm_w) {
-        if (NB > 1 && a.rstd) {                                  // dec_rstd_kernel wrote them once for the launch
-            if (tid < B) rstd[tid] = a.rstd[tid];
-        } else {                                                 // rmsnorm_kernel's statistics, in its order (identical bits)
-            for (int b = wave; b < B; b += 4) {
-                const bf16* xr = x + (size_t)b * a.ldx;
-                float ss = 0.f;
-                for (int c = lane * 8; c < K; c += 512) {
-                    const f32x8 v = bf8_to_f32(*(const bf16x8*)(xr + c));
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) ss = __builtin_fmaf(v[k], v[k], ss);
-                }
-                ss = wave_sum(ss);
-                if (lane == 0) rstd[b] = 1.0f / sqrtf(ss / (float)K + a.eps);
-            }
-        }
-        __syncthreads();
-    }
-    int wrow = tile * 16 + lr;
-    if constexpr (EPI == DEC_EPI_QKV) {
-        const int tph = a.hd / 16, head = tile / tph, pb = tile % tph;
-        wrow = head * a.hd + (lr < 8 ? pb * 8 + lr : a.hd / 2 + pb * 8 + lr - 8);
-    }
+    dec_row_stats<(NB > 1)>(a, rstd, tid, lane, wave, B, K, x);
+    const int wrow = dec_weight_row<EPI>(a, tile, lr);
     int xb[NB];
     f32x4 acc[NB];
 #pragma unroll
@@ -233,115 +190,26 @@ __global__ __launch_bounds__(256) void dec_gemm_w8_kernel(const DecGemmArgs a)
         }
     }
     if (S > 1) {
-        if (active) {
-#pragma unroll
-            for (int t = 0; t < NB; ++t) *(f32x4*)(a.part + ((((size_t)s * ntiles + tile) * NB + t) * 64 + lane) * 4) = acc[t];
-        }
+        dec_slab_store<NB>(a.part, acc, s, ntiles, tile, active, lane);
         if (!arrive_last(a.cnt + column, S, flag)) return;
-        if (active) {
-#pragma unroll
-            for (int t = 0; t < NB; ++t) {
-                acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-                for (int u = 0; u < S; ++u) acc[t] += *(const f32x4*)(a.part + ((((size_t)u * ntiles + tile) * NB + t) * 64 + lane) * 4);
-            }
-        }
+        dec_slab_sum<NB>(a.part, acc, S, ntiles, tile, active, lane);
     }
     const int n0 = tile * 16 + g * 4;                            // this lane's 4 outputs of batch tile t: rows n0 .. n0 + 3 of batch row t * 16 + lr
+    f32x4 sc = {1.f, 1.f, 1.f, 1.f};
     if (active) {                                                // their scales: the weight rows the lane's accumulator rows came from
         int srow = n0;
         if constexpr (EPI == DEC_EPI_QKV) {
             const int hd = a.hd, tph = hd / 16, head = tile / tph, pb = tile % tph;
             srow = head * hd + (g < 2 ? 0 : hd / 2) + pb * 8 + (g & 1) * 4;
         }
-        const f32x4 sc = *(const f32x4*)(a.wscale + srow);
+        sc = *(const f32x4*)(a.wscale + srow);
+        if constexpr (EPI != DEC_EPI_QKV) {
 #pragma unroll
-        for (int t = 0; t < NB; ++t) acc[t] *= sc;
-    }
-    if constexpr (EPI == DEC_EPI_RESID) {
-#pragma unroll
-        for (int t = 0; t < NB; ++t) {
-            const int b = t * 16 + lr;
-            if (active && b < B) {
-                const f32x4 r = bf4_to_f32(*(const bf16x4*)((const bf16*)a.resid + (size_t)b * a.ldo + n0));
-                *(bf16x4*)((bf16*)a.out + (size_t)b * a.ldo + n0) = f32_to_bf4(r + acc[t]);
-            }
-        }
-    } else if constexpr (EPI == DEC_EPI_SWIGLU) {
-#pragma unroll
-        for (int t = 0; t < NB; ++t) {
-            const int b = t * 16 + lr;
-            if (active && b < B) {
-                bf16x2 o;
-                o[0] = (bf16)(acc[t][0] * sigmoidf_fast(acc[t][0]) * acc[t][1]);
-                o[1] = (bf16)(acc[t][2] * sigmoidf_fast(acc[t][2]) * acc[t][3]);
-                *(bf16x2*)((bf16*)a.out + (size_t)b * a.ldo + n0 / 2) = o;
-            }
-        }
-    } else if constexpr (EPI == DEC_EPI_QKV) {
-        if (active) {
-            const int hd = a.hd, tph = hd / 16, head = tile / tph, pb = tile % tph;
-            const bool first = g < 2;
-            const int i4 = pb * 8 + (g & 1) * 4, d = first ? i4 : hd / 2 + i4;
-            const f32x4 bias = *(const f32x4*)(a.bias + head * hd + d);
-#pragma unroll
-            for (int t = 0; t < NB; ++t) {
-                const int b = t * 16 + lr;
-                const f32x4 v = bf4_to_f32(f32_to_bf4(acc[t] + bias));  // the projection's output as the reference holds it (bf16)
-                f32x4 other;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) other[r] = __shfl_xor(v[r], 32, 64);
-                bf16x4 res = f32_to_bf4(v);
-                if (b < B) {
-                    if (head < a.nh + a.nkv) {
-                        bf16x4 ra, rb;
-                        rope_rotate(first ? v : other, first ? other : v, (long)a.pos[b], i4, a.rope, hd, a.P, a.theta, ra, rb);
-                        res = first ? ra : rb;
-                    }
-                    if (head < a.nh) {
-                        *(bf16x4*)((bf16*)a.out + (size_t)b * a.ldo + head * hd + d) = res;
-                    } else {
-                        const int kvh = head < a.nh + a.nkv ? head - a.nh : head - a.nh - a.nkv;
-                        bf16* cache = (bf16*)(head < a.nh + a.nkv ? a.kc : a.vc);
-                        const int slot = *a.len;
-                        if (slot >= 0 && slot < a.cap)
-                            *(bf16x4*)(cache + (((size_t)b * a.nkv + kvh) * a.cap + slot) * hd + d) = res;
-                    }
-                }
-            }
-        }
-    } else if constexpr (EPI == DEC_EPI_ARGMAX) {
-        float* rv = sh + 16 * NB + 4;                            // [wave][batch tile][16] best value / index of the wave's 16 weight rows
-        int* ri = (int*)(rv + 64 * NB);
-#pragma unroll
-        for (int t = 0; t < NB; ++t) {
-            const int b = t * 16 + lr;
-            float bv = -INFINITY;
-            int bi = 0x7fffffff;
-            if (active && b < B) {
-                if (a.logits) *(f32x4*)(a.logits + (size_t)b * a.N + n0) = acc[t];
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    if (better(acc[t][r], n0 + r, bv, bi)) { bv = acc[t][r]; bi = n0 + r; }
-            }
-#pragma unroll
-            for (int o = 16; o <= 32; o <<= 1) {
-                const float ov = __shfl_xor(bv, o, 64);
-                const int oi = __shfl_xor(bi, o, 64);
-                if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-            }
-            if (lane < 16) { rv[(wave * NB + t) * 16 + lane] = bv; ri[(wave * NB + t) * 16 + lane] = bi; }
-        }
-        __syncthreads();
-        if (tid < 16 * NB && tid < B) {
-            const int t = tid >> 4, r = tid & 15;
-            float v = rv[t * 16 + r];
-            int i = ri[t * 16 + r];
-            for (int w = 1; w < 4; ++w)
-                if (better(rv[(w * NB + t) * 16 + r], ri[(w * NB + t) * 16 + r], v, i)) { v = rv[(w * NB + t) * 16 + r]; i = ri[(w * NB + t) * 16 + r]; }
-            a.amax_v[(size_t)blockIdx.x * (16 * NB) + tid] = v;
-            a.amax_i[(size_t)blockIdx.x * (16 * NB) + tid] = i;
+            for (int t = 0; t < NB; ++t) acc[t] *= sc;
         }
     }
+    // q|k|v: the scale is left to the epilogue, which rounds acc * scale + bias once (a fused multiply-add)
+    dec_gemm_epilogue<EPI, NB>(a, acc, sh, tid, lane, wave, lr, g, B, tile, active, n0, EPI == DEC_EPI_QKV ? &sc : nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -8,7 +8,9 @@ stand-ins, then compares two dumps with torch.equal.
 Per width (the 0.5B and 7B shapes, 2 / 1 layers, vocab 4096) and batch (1, 8, 16 - what every library version decodes - unless batches
 are named: `dump x.pt 1 8 16 64` for two libraries of version 503 or later): the fp32 logits
 of the prefill and of 16 steps fed fixed token ids, the greedy ids of every step, and the ids of a sampled generation (temperature 0.7,
-top_k 50, top_p 0.9, seed 3).  Everything is seeded; the two dumps must come from the same GPU model.
+top_k 50, top_p 0.9, seed 3).  Everything is seeded; the two dumps must come from the same GPU model.  One word among the batches that is
+no number is the weight format, `dump x.pt 1 16 64 fp8_e4m3` (or mxfp4; bf16 when absent): it goes to `from_hf(weights=...)`, so that the
+e4m3 and MXFP4 decode kernels are compared too; the dump records it and `compare` refuses two dumps of different formats.
 
     python tools/decode_bits.py dump x.pt features      (two libraries of version 510 or later)
 
@@ -29,6 +31,7 @@ CONFIGS = {
     "7B": dict(hidden_size=3584, num_hidden_layers=1, num_attention_heads=28, num_key_value_heads=4, intermediate_size=18944, tie_word_embeddings=False),
 }
 BATCHES = (1, 8, 16)
+META = ("version", "device", "weights")          # what a dump holds beside its tensors
 T, STEPS, VOCAB = 24, 16, 4096
 
 
@@ -45,14 +48,14 @@ def _model(name):
 
 
 @torch.no_grad()
-def dump(path, batches=BATCHES):
+def dump(path, batches=BATCHES, weights="bf16"):
     from ml_fastvlm_amd import _lib
     from ml_fastvlm_amd.qwen2_decode import Qwen2Generator
     from ml_fastvlm_amd.qwen2_prefill import Qwen2Prefill
-    out = {"version": _lib.load().fvhd_version(), "device": torch.cuda.get_device_name(0)}
+    out = {"version": _lib.load().fvhd_version(), "device": torch.cuda.get_device_name(0), "weights": weights}
     for name in CONFIGS:
         m = _model(name)
-        pre = Qwen2Prefill.from_hf(m)
+        pre = Qwen2Prefill.from_hf(m, weights=weights)
         for B in batches:
             g = torch.Generator().manual_seed(100 + B)
             e = (0.5 * torch.randn(B, T, m.config.hidden_size, generator=g)).to("cuda", torch.bfloat16)
@@ -61,7 +64,7 @@ def dump(path, batches=BATCHES):
                 mask[b, :(5 * b) % 13] = 0
             mask = mask.cuda()
             fed = torch.randint(0, VOCAB, (STEPS, B), generator=g).cuda()
-            gen = Qwen2Generator.from_hf(m, B, T + STEPS + 4, prefill=pre)
+            gen = Qwen2Generator.from_hf(m, B, T + STEPS + 4, prefill=pre, weights=weights)
             lg, ids = gen.start(e, mask)
             logits, chosen = [lg.clone().cpu()], [ids.clone().cpu()]
             for i in range(STEPS):
@@ -75,7 +78,7 @@ def dump(path, batches=BATCHES):
             out[key + " greedy generation"] = gen.greedy(e, mask, None, max_new_tokens=STEPS, pad_token_id=0).cpu()
             del gen
     torch.save(out, path)
-    print(f"decode_bits: library version {out['version']} on {out['device']}: {len(out) - 2} tensors -> {path}")
+    print(f"decode_bits: library version {out['version']} on {out['device']}, {weights} weights: {len(out) - len(META)} tensors -> {path}")
 
 
 PROCESSORS = dict(repetition_penalty=1.3, no_repeat_ngram_size=2, min_new_tokens=4, eos_token_id=5, suppress_tokens=[7, 9])
@@ -140,9 +143,12 @@ def dump_features(path, new=NEW, names=tuple(CONFIGS)):
 
 def compare(pa, pb):
     a, b = torch.load(pa), torch.load(pb)
-    print(f"decode_bits compare: library version {a['version']} ({a['device']}) against {b['version']} ({b['device']})")
-    keys = [k for k in a if k not in ("version", "device")]
-    assert keys == [k for k in b if k not in ("version", "device")]
+    wa, wb = a.get("weights", "bf16"), b.get("weights", "bf16")
+    print(f"decode_bits compare: library version {a['version']} ({a['device']}) against {b['version']} ({b['device']}), {wa} weights")
+    if wa != wb:
+        sys.exit(f"decode_bits compare: the dumps hold different weight formats ({wa} and {wb})")
+    keys = [k for k in a if k not in META]
+    assert keys == [k for k in b if k not in META]
     bad = 0
     for k in keys:
         same = a[k].shape == b[k].shape and torch.equal(a[k], b[k])
@@ -157,7 +163,10 @@ if __name__ == "__main__":
     if len(sys.argv) == 4 and sys.argv[1] == "dump" and sys.argv[3] == "features":
         dump_features(sys.argv[2])
     elif len(sys.argv) >= 3 and sys.argv[1] == "dump":
-        dump(sys.argv[2], tuple(int(b) for b in sys.argv[3:]) or BATCHES)
+        words = [w for w in sys.argv[3:] if not w.isdigit()]
+        if len(words) > 1:
+            sys.exit(__doc__)
+        dump(sys.argv[2], tuple(int(b) for b in sys.argv[3:] if b.isdigit()) or BATCHES, *words)
     elif len(sys.argv) == 4 and sys.argv[1] == "compare":
         sys.exit(compare(sys.argv[2], sys.argv[3]))
     else:
