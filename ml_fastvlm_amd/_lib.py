@@ -4,8 +4,9 @@ the import fails loudly, and creating a context without a HIP device is an error
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
-from typing import Dict, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # FVHD_LIB: another build of the same ABI (the ablation library of `python -m ml_fastvlm_amd.build` with FVHD_FFN_ABLATE=1)
@@ -27,9 +28,11 @@ MAX_VERIFY_ROWS = 16           # rows of one verify step (include/fvhd.h)
 MAX_EOS_IDS, MAX_SUPPRESS_IDS = 16, 256      # list limits of fvhd_llm_set_logits_processors (include/fvhd.h)
 MAX_GUIDANCE_PROMPTS = 32      # G of fvhd_llm_set_guidance: the step runs 2 G rows (include/fvhd.h "LLM classifier-free guidance")
 MAX_LOGPROBS = 16              # top_n of fvhd_llm_logprobs / fvhd_op_dec_logprobs (include/fvhd.h)
+CACHE_ERRORS = {1: "past the cache's capacity", 2: "a token id out of range", 3: "a cache reorder's row index out of range",
+                4: "a cache rewind's keep length out of range"}      # the error word of fvhd_llm_cache_state (include/fvhd.h)
 W_BF16, W_E4M3 = 0, 1           # fvhd_llm_set_weight_format (include/fvhd.h)
 WEIGHT_FORMATS = {"bf16": W_BF16, "fp8_e4m3": W_E4M3}
-W_MXFP4 = 2                     # added under 510 (w4_lib()): OCP MXFP4, e2m1 codes + one e8m0 scale per 32 elements of a row
+W_MXFP4 = 2                     # added under 510 (FEATURES["w4"]): OCP MXFP4, e2m1 codes + one e8m0 scale per 32 elements of a row
 MX_WEIGHT_FORMATS = {"mxfp4": W_MXFP4}
 MAT_QKV, MAT_O, MAT_GATE_UP, MAT_DOWN, MAT_LM_HEAD = 0, 1, 2, 3, 4     # fvhd_llm_debug_packed_e4m3
 F32, F16, BF16 = 0, 1, 2
@@ -43,181 +46,196 @@ class FvhdError(RuntimeError):
     pass
 
 
+vp, ci, cf = C.c_void_p, C.c_int, C.c_float
+
+# name -> (restype, argtypes) of everything a library of ABI_VERSION has
+BASE_SIGNATURES = {
+    "fvhd_version": (ci, []),
+    "fvhd_last_error": (C.c_char_p, []),
+    "fvhd_create": (ci, [C.POINTER(vp), ci, ci, ci]),
+    "fvhd_destroy": (None, [vp]),
+    "fvhd_reserve": (ci, [vp, ci]),
+    "fvhd_set_tensor": (ci, [vp, C.c_char_p, vp, C.POINTER(C.c_int64), ci]),
+    "fvhd_finalize_weights": (ci, [vp]),
+    "fvhd_set_projector": (ci, [vp, vp, vp, vp, vp, ci, ci]),
+    "fvhd_encode": (ci, [vp, vp, ci, ci, vp, ci, vp]),
+    "fvhd_project": (ci, [vp, vp, ci, ci, vp, ci, vp]),
+    "fvhd_encode_images": (ci, [vp, vp, ci, ci, vp, ci, vp]),
+    "fvhd_num_steps": (ci, [vp]),
+    "fvhd_step_info": (ci, [vp, ci] + [C.POINTER(ci)] * 7),
+    "fvhd_run_steps": (ci, [vp, ci, ci, vp, ci, vp, vp]),
+    "fvhd_num_tokens": (ci, [vp]),
+    "fvhd_hidden_size": (ci, [vp]),
+    "fvhd_profile_enable": (ci, [vp, ci]),
+    "fvhd_profile_reset": (ci, [vp]),
+    "fvhd_profile_read": (ci, [vp, ci, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(ci)]),
+    "fvhd_op_dwconv": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci]),
+    "fvhd_op_dw7_mfma": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci]),
+    "fvhd_op_dw3_dw7": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
+    "fvhd_dw3_dw7_supported": (ci, [ci, ci, ci, ci, ci]),
+    "fvhd_dw7s2_mfma_supported": (ci, [ci, ci, ci, ci, ci]),
+    "fvhd_op_dw7s2_mfma": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci]),
+    "fvhd_op_gemm": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci]),
+    "fvhd_op_gemm_splitk_ls": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci]),
+    "fvhd_gemm_splitk_plan": (ci, [ci, ci, ci]),
+    "fvhd_op_layernorm": (ci, [vp, vp, vp, vp, vp, ci, ci, cf]),
+    "fvhd_op_attention": (ci, [vp, vp, vp, ci, ci, ci]),
+    "fvhd_op_attention_fp8": (ci, [vp, vp, vp, ci, ci, ci]),
+    "fvhd_set_attention_fp8": (ci, [vp, ci]),
+    "fvhd_set_graph": (ci, [vp, ci]),
+    "fvhd_set_batch_invariant": (ci, [vp, ci]),
+    "fvhd_op_stem_conv": (ci, [vp, vp, ci, vp, vp, vp, ci, ci]),
+    "fvhd_op_stem_fused": (ci, [vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci]),
+    "fvhd_op_se_head": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci]),
+    "fvhd_op_ffn_fused": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci]),
+    "fvhd_ffn_fused_supported": (ci, [ci]),
+    "fvhd_ffn_pack": (ci, [ci, vp, vp, vp, vp, ci]),
+    "fvhd_set_ffn_precision": (ci, [vp, ci, ci]),
+    "fvhd_get_ffn_precision": (ci, [vp, ci]),
+    "fvhd_audit_ranges": (ci, [vp, vp, ci, ci, cf, C.POINTER(C.c_float), C.POINTER(ci), vp]),
+    "fvhd_set_range_guard": (ci, [vp, ci]),
+    "fvhd_range_guard_limit": (ci, [vp, ci, C.POINTER(C.c_float)]),
+    "fvhd_range_guard_poll": (ci, [vp, ci, C.POINTER(ci), C.POINTER(C.c_float), ci, C.POINTER(ci)]),
+    "fvhd_op_dw7_amax": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
+    "fvhd_op_preprocess": (ci, [vp, vp, ci, ci, C.c_int64, ci, ci, C.c_uint32, vp, vp, ci, vp, vp, ci, ci, ci, vp, vp, ci, vp, ci]),
+    "fvhd_op_splice": (ci, [vp] * 12 + [ci, ci, ci, ci, C.c_int64, C.c_int64, ci, ci]),
+    "fvhd_llm_create": (ci, [C.POINTER(vp), ci, ci, ci, ci, ci, ci, ci, ci, cf, cf]),
+    "fvhd_llm_destroy": (None, [vp]),
+    "fvhd_llm_set_tensor": (ci, [vp, C.c_char_p, vp, ci, C.POINTER(C.c_int64), ci]),
+    "fvhd_llm_finalize": (ci, [vp]),
+    "fvhd_llm_reserve": (ci, [vp, ci, ci]),
+    "fvhd_llm_prefill": (ci, [vp, vp, ci, vp, vp, ci, ci, vp, vp, vp, vp]),
+    "fvhd_llm_debug_hidden": (ci, [vp, vp, ci, vp]),
+    "fvhd_op_rmsnorm": (ci, [vp, vp, vp, vp, ci, ci, cf]),
+    "fvhd_op_rope": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, cf]),
+    "fvhd_gemm_qkv_rope_supported": (ci, [ci, ci, ci, ci, ci, ci]),
+    "fvhd_op_gemm_qkv_rope": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, cf]),
+    "fvhd_llm_set_tensor_device": (ci, [vp, C.c_char_p, vp, ci, C.POINTER(C.c_int64), ci, vp]),
+    "fvhd_llm_set_max_positions": (ci, [vp, ci]),
+    "fvhd_llm_workspace_generation": (ci, [vp]),
+    "fvhd_op_attention_causal": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci]),
+    "fvhd_op_gemm_splitk": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci]),
+    "fvhd_op_qkv_splitk_rope": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, ci]),
+    "fvhd_op_gemm_splitk_norm": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, C.c_float]),
+    "fvhd_llm_set_tied_embeddings": (ci, [vp, ci]),
+    "fvhd_llm_cache_reserve": (ci, [vp, ci, ci]),
+    "fvhd_llm_start": (ci, [vp, vp, ci, vp, vp, ci, ci, vp, vp, vp]),
+    "fvhd_llm_decode": (ci, [vp, vp, vp, vp, vp]),
+    "fvhd_llm_cache_state": (ci, [vp, C.POINTER(ci), C.POINTER(ci)]),
+    "fvhd_op_dec_gemm": (ci, [vp, ci, vp, ci, vp, cf, vp, ci, ci, vp, vp, vp, vp, ci]),
+    "fvhd_op_dec_qkv": (ci, [vp, vp, ci, ci, vp, cf, vp, vp, vp, vp, vp, ci, cf, vp, vp, ci, vp, ci, ci, ci, vp, vp, ci]),
+    "fvhd_op_dec_attention": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, ci]),
+    "fvhd_op_dec_lm_argmax": (ci, [vp, vp, ci, vp, cf, vp, ci, ci, vp, vp, vp, vp]),
+}
+
+
+class Feature(NamedTuple):
+    """one optional part of the library: a library without it loads, declares none of its symbols, and `require` names the rebuild"""
+    phrase: str                     # what the error message calls it ...
+    names: str                      # ... and the symbols it gives as examples
+    sig: dict                       # name -> (restype, argtypes), as in BASE_SIGNATURES
+    since: Optional[int] = None     # present from this FVHD_VERSION on, or ...
+    probe: Optional[str] = None     # ... added under 510 (a 510 library built before it reports the same number): present when this symbol is exported
+    needs: Optional[str] = None     # another feature it is built on
+
+
+FEATURES = {
+    "sampling": Feature("sampling", "fvhd_llm_set_sampling, fvhd_op_dec_sample", since=SAMPLING_VERSION, sig={
+        "fvhd_llm_set_sampling": (ci, [vp, ci, cf, ci, cf, C.c_ulonglong]),
+        "fvhd_op_dec_sample": (ci, [vp, vp, ci, ci, cf, ci, cf, C.c_ulonglong, ci, vp, vp, vp]),
+    }),
+    "w8": Feature("8-bit weights", "fvhd_llm_set_weight_format, fvhd_op_dec_gemm_w8, ...", since=W8_VERSION, sig={
+        "fvhd_llm_set_weight_format": (ci, [vp, ci]),
+        "fvhd_llm_weight_bytes": (ci, [vp, C.POINTER(C.c_size_t)]),
+        "fvhd_llm_debug_packed_e4m3": (ci, [vp, ci, ci, vp, vp, vp]),
+        "fvhd_op_quantize_e4m3": (ci, [vp, vp, ci, ci, vp, vp]),
+        "fvhd_op_dec_gemm_w8": (ci, [vp, ci, vp, ci, vp, cf, vp, vp, ci, ci, vp, vp, vp, vp, ci]),
+        "fvhd_op_dec_qkv_w8": (ci, [vp, vp, ci, ci, vp, cf, vp, vp, vp, vp, vp, vp, ci, cf, vp, vp, ci, vp, ci, ci, ci, vp, vp, ci]),
+        "fvhd_op_dec_lm_argmax_w8": (ci, [vp, vp, ci, vp, cf, vp, vp, ci, ci, vp, vp, vp, vp]),
+    }),
+    "beam": Feature("beam search", "fvhd_llm_beam_reserve, fvhd_llm_cache_gather, fvhd_llm_beam_topk, ...", since=BEAM_VERSION, sig={
+        "fvhd_llm_beam_reserve": (ci, [vp]),
+        "fvhd_llm_cache_gather": (ci, [vp, vp, ci, ci, vp]),
+        "fvhd_llm_beam_topk": (ci, [vp, vp, vp, ci, ci, ci, vp, vp, vp]),
+        "fvhd_op_dec_beam_topk": (ci, [vp, vp, vp, ci, ci, ci, ci, vp, vp]),
+        "fvhd_op_dec_cache_gather": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp]),
+    }),
+    "processors": Feature("logits processors", "fvhd_llm_set_logits_processors, fvhd_op_dec_logits_process", since=PROCESSORS_VERSION, sig={
+        "fvhd_llm_set_logits_processors": (ci, [vp, cf, ci, ci, vp, ci, vp, ci]),
+        "fvhd_op_dec_logits_process": (ci, [vp, vp, ci, ci, vp, ci, ci, cf, ci, ci, vp, ci, vp, ci]),
+    }),
+    "lookup": Feature("prompt-lookup decoding", "fvhd_llm_spec_reserve, fvhd_llm_verify, fvhd_llm_lookup_step, ...", since=LOOKUP_VERSION, sig={
+        "fvhd_llm_spec_reserve": (ci, [vp, ci, ci]),
+        "fvhd_llm_verify": (ci, [vp, vp, ci, vp, vp, vp, vp]),
+        "fvhd_llm_lookup_begin": (ci, [vp, vp, ci, vp, ci, ci, vp, vp]),
+        "fvhd_llm_lookup_step": (ci, [vp, ci, ci, vp]),
+        "fvhd_llm_lookup_state": (ci, [vp] + [C.POINTER(ci)] * 4),
+        "fvhd_op_dec_attention_multi": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, ci]),
+        "fvhd_op_dec_lookup_draft": (ci, [vp, vp, vp, ci, ci, vp]),
+        "fvhd_op_dec_lookup_accept": (ci, [vp, vp, vp, ci, vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, ci]),
+    }),
+    "gemm_plan": Feature("the GEMM dispatch query", "fvhd_gemm_kernel_plan", since=GEMM_PLAN_VERSION, sig={
+        "fvhd_gemm_kernel_plan": (ci, [ci, ci, ci, ci, ci]),
+    }),
+    "extend": Feature("extending a started cache", "fvhd_llm_extend, fvhd_llm_cache_rewind, fvhd_op_attention_extend, ...", since=EXTEND_VERSION, sig={
+        "fvhd_llm_extend": (ci, [vp, vp, ci, vp, vp, ci, vp, vp, vp]),
+        "fvhd_llm_cache_rewind": (ci, [vp, vp, vp]),
+        "fvhd_op_attention_extend": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]),
+        "fvhd_op_cache_append": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]),
+        "fvhd_op_extend_positions": (ci, [vp, vp, vp, vp, ci, ci]),
+        "fvhd_op_cache_rewind": (ci, [vp, vp, ci, vp, vp, ci, vp, vp]),
+    }),
+    "score": Feature("scoring", "fvhd_llm_score, fvhd_llm_score_reserve, fvhd_op_lm_score, ...", probe="fvhd_op_lm_score", sig={
+        "fvhd_lm_score_scratch_bytes": (C.c_size_t, [ci, ci, ci]),
+        "fvhd_lm_score_plan": (ci, [ci, ci, ci]),
+        "fvhd_op_lm_score": (ci, [vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, C.c_size_t]),
+        "fvhd_llm_score_reserve": (ci, [vp, ci]),
+        "fvhd_llm_score": (ci, [vp, vp, vp, vp, vp]),
+    }),
+    "w4": Feature("4-bit weights", "FVHD_W_MXFP4, fvhd_op_quantize_mxfp4, fvhd_op_dec_gemm_w4, ...", probe="fvhd_op_dec_gemm_w4", sig={
+        "fvhd_llm_debug_packed_mxfp4": (ci, [vp, ci, ci, vp, vp, vp]),
+        "fvhd_op_quantize_mxfp4": (ci, [vp, vp, ci, ci, vp, vp]),
+        "fvhd_op_dec_gemm_w4": (ci, [vp, ci, vp, ci, vp, cf, vp, vp, ci, ci, vp, vp, vp, vp, ci]),
+        "fvhd_op_dec_qkv_w4": (ci, [vp, vp, ci, ci, vp, cf, vp, vp, vp, vp, vp, vp, ci, cf, vp, vp, ci, vp, ci, ci, ci, vp, vp, ci]),
+        "fvhd_op_dec_lm_argmax_w4": (ci, [vp, vp, ci, vp, cf, vp, vp, ci, ci, vp, vp, vp, vp]),
+        "fvhd_op_w4_unpack": (ci, [vp, vp, vp, vp, ci, ci, ci]),
+    }),
+    "logprobs": Feature("the log-probabilities of generated tokens", "fvhd_llm_set_logprobs, fvhd_llm_logprobs, fvhd_op_dec_logprobs, ...", probe="fvhd_op_dec_logprobs", sig={
+        "fvhd_dec_logprobs_scratch_bytes": (C.c_size_t, [ci, ci, ci]),
+        "fvhd_op_dec_logprobs": (ci, [vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, C.c_size_t]),
+        "fvhd_llm_set_logprobs": (ci, [vp, ci]),
+        "fvhd_llm_logprobs": (ci, [vp, vp, ci, vp, vp, vp, vp]),
+    }),
+    "constraint": Feature("constrained decoding", "fvhd_llm_set_constraint, fvhd_llm_constraint_state, fvhd_op_dec_constrain, ...", probe="fvhd_op_dec_constrain", sig={
+        "fvhd_dec_constrain_slice": (ci, []),
+        "fvhd_op_dec_constrain": (ci, [vp, vp, ci, ci, vp, vp, vp, ci, vp, vp, vp]),
+        "fvhd_llm_set_constraint": (ci, [vp, vp, ci, vp, vp, ci, vp, ci]),
+        "fvhd_llm_constraint_state": (ci, [vp, vp, vp, ci]),
+    }),
+    "lookup_sample": Feature("prompt-lookup decoding under sampling", "fvhd_llm_set_verify_sampling, fvhd_llm_lookup_logprobs, fvhd_op_dec_sample_rows", probe="fvhd_llm_set_verify_sampling", needs="lookup", sig={
+        "fvhd_llm_set_verify_sampling": (ci, [vp, ci]),
+        "fvhd_llm_lookup_logprobs": (ci, [vp, ci, vp, vp, vp, vp]),
+        "fvhd_op_dec_sample_rows": (ci, [vp, vp, ci, ci, cf, ci, cf, C.c_ulonglong, ci, ci, vp, vp, vp, vp, vp, vp]),
+    }),
+    "guidance": Feature("classifier-free guidance", "fvhd_llm_set_guidance, fvhd_op_dec_guidance, fvhd_dec_guidance_scratch_bytes", probe="fvhd_op_dec_guidance", sig={
+        "fvhd_dec_guidance_scratch_bytes": (C.c_size_t, [ci, ci]),
+        "fvhd_op_dec_guidance": (ci, [vp, vp, ci, ci, cf, vp, C.c_size_t]),
+        "fvhd_llm_set_guidance": (ci, [vp, cf]),
+    }),
+}
+del vp, ci, cf
+
+
+def _has(lib, name: str) -> bool:
+    f = FEATURES[name]
+    return (f.needs is None or _has(lib, f.needs)) and (lib.fvhd_version() >= f.since if f.probe is None else hasattr(lib, f.probe))
+
+
 def _declare(lib) -> None:
-    vp, ci, cf, cl = C.c_void_p, C.c_int, C.c_float, C.c_long
-    fp = C.POINTER(C.c_float)
-    sig = {
-        "fvhd_version": (ci, []),
-        "fvhd_last_error": (C.c_char_p, []),
-        "fvhd_create": (ci, [C.POINTER(vp), ci, ci, ci]),
-        "fvhd_destroy": (None, [vp]),
-        "fvhd_reserve": (ci, [vp, ci]),
-        "fvhd_set_tensor": (ci, [vp, C.c_char_p, vp, C.POINTER(C.c_int64), ci]),
-        "fvhd_finalize_weights": (ci, [vp]),
-        "fvhd_set_projector": (ci, [vp, vp, vp, vp, vp, ci, ci]),
-        "fvhd_encode": (ci, [vp, vp, ci, ci, vp, ci, vp]),
-        "fvhd_project": (ci, [vp, vp, ci, ci, vp, ci, vp]),
-        "fvhd_encode_images": (ci, [vp, vp, ci, ci, vp, ci, vp]),
-        "fvhd_num_steps": (ci, [vp]),
-        "fvhd_step_info": (ci, [vp, ci] + [C.POINTER(ci)] * 7),
-        "fvhd_run_steps": (ci, [vp, ci, ci, vp, ci, vp, vp]),
-        "fvhd_num_tokens": (ci, [vp]),
-        "fvhd_hidden_size": (ci, [vp]),
-        "fvhd_profile_enable": (ci, [vp, ci]),
-        "fvhd_profile_reset": (ci, [vp]),
-        "fvhd_profile_read": (ci, [vp, ci, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(ci)]),
-        "fvhd_op_dwconv": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci]),
-        "fvhd_op_dw7_mfma": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci]),
-        "fvhd_op_dw3_dw7": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
-        "fvhd_dw3_dw7_supported": (ci, [ci, ci, ci, ci, ci]),
-        "fvhd_dw7s2_mfma_supported": (ci, [ci, ci, ci, ci, ci]),
-        "fvhd_op_dw7s2_mfma": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci]),
-        "fvhd_op_gemm": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci]),
-        "fvhd_op_gemm_splitk_ls": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci]),
-        "fvhd_gemm_splitk_plan": (ci, [ci, ci, ci]),
-        "fvhd_op_layernorm": (ci, [vp, vp, vp, vp, vp, ci, ci, cf]),
-        "fvhd_op_attention": (ci, [vp, vp, vp, ci, ci, ci]),
-        "fvhd_op_attention_fp8": (ci, [vp, vp, vp, ci, ci, ci]),
-        "fvhd_set_attention_fp8": (ci, [vp, ci]),
-        "fvhd_set_graph": (ci, [vp, ci]),
-        "fvhd_set_batch_invariant": (ci, [vp, ci]),
-        "fvhd_op_stem_conv": (ci, [vp, vp, ci, vp, vp, vp, ci, ci]),
-        "fvhd_op_stem_fused": (ci, [vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci]),
-        "fvhd_op_se_head": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci]),
-        "fvhd_op_ffn_fused": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci]),
-        "fvhd_ffn_fused_supported": (ci, [ci]),
-        "fvhd_ffn_pack": (ci, [ci, vp, vp, vp, vp, ci]),
-        "fvhd_set_ffn_precision": (ci, [vp, ci, ci]),
-        "fvhd_get_ffn_precision": (ci, [vp, ci]),
-        "fvhd_audit_ranges": (ci, [vp, vp, ci, ci, cf, C.POINTER(C.c_float), C.POINTER(ci), vp]),
-        "fvhd_set_range_guard": (ci, [vp, ci]),
-        "fvhd_range_guard_limit": (ci, [vp, ci, C.POINTER(C.c_float)]),
-        "fvhd_range_guard_poll": (ci, [vp, ci, C.POINTER(ci), C.POINTER(C.c_float), ci, C.POINTER(ci)]),
-        "fvhd_op_dw7_amax": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
-        "fvhd_op_preprocess": (ci, [vp, vp, ci, ci, C.c_int64, ci, ci, C.c_uint32, vp, vp, ci, vp, vp, ci, ci, ci, vp, vp, ci, vp, ci]),
-        "fvhd_op_splice": (ci, [vp] * 12 + [ci, ci, ci, ci, C.c_int64, C.c_int64, ci, ci]),
-        "fvhd_llm_create": (ci, [C.POINTER(vp), ci, ci, ci, ci, ci, ci, ci, ci, cf, cf]),
-        "fvhd_llm_destroy": (None, [vp]),
-        "fvhd_llm_set_tensor": (ci, [vp, C.c_char_p, vp, ci, C.POINTER(C.c_int64), ci]),
-        "fvhd_llm_finalize": (ci, [vp]),
-        "fvhd_llm_reserve": (ci, [vp, ci, ci]),
-        "fvhd_llm_prefill": (ci, [vp, vp, ci, vp, vp, ci, ci, vp, vp, vp, vp]),
-        "fvhd_llm_debug_hidden": (ci, [vp, vp, ci, vp]),
-        "fvhd_op_rmsnorm": (ci, [vp, vp, vp, vp, ci, ci, cf]),
-        "fvhd_op_rope": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, cf]),
-        "fvhd_gemm_qkv_rope_supported": (ci, [ci, ci, ci, ci, ci, ci]),
-        "fvhd_op_gemm_qkv_rope": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, cf]),
-        "fvhd_llm_set_tensor_device": (ci, [vp, C.c_char_p, vp, ci, C.POINTER(C.c_int64), ci, vp]),
-        "fvhd_llm_set_max_positions": (ci, [vp, ci]),
-        "fvhd_llm_workspace_generation": (ci, [vp]),
-        "fvhd_op_attention_causal": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci]),
-        "fvhd_op_gemm_splitk": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci]),
-        "fvhd_op_qkv_splitk_rope": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, ci]),
-        "fvhd_op_gemm_splitk_norm": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, C.c_float]),
-        "fvhd_llm_set_tied_embeddings": (ci, [vp, ci]),
-        "fvhd_llm_cache_reserve": (ci, [vp, ci, ci]),
-        "fvhd_llm_start": (ci, [vp, vp, ci, vp, vp, ci, ci, vp, vp, vp]),
-        "fvhd_llm_decode": (ci, [vp, vp, vp, vp, vp]),
-        "fvhd_llm_cache_state": (ci, [vp, C.POINTER(ci), C.POINTER(ci)]),
-        "fvhd_op_dec_gemm": (ci, [vp, ci, vp, ci, vp, cf, vp, ci, ci, vp, vp, vp, vp, ci]),
-        "fvhd_op_dec_qkv": (ci, [vp, vp, ci, ci, vp, cf, vp, vp, vp, vp, vp, ci, cf, vp, vp, ci, vp, ci, ci, ci, vp, vp, ci]),
-        "fvhd_op_dec_attention": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, ci]),
-        "fvhd_op_dec_lm_argmax": (ci, [vp, vp, ci, vp, cf, vp, ci, ci, vp, vp, vp, vp]),
-    }
-    if lib.fvhd_version() >= SAMPLING_VERSION:     # an older library loads without them; sampling_lib() then names the rebuild
-        sig.update({
-            "fvhd_llm_set_sampling": (ci, [vp, ci, cf, ci, cf, C.c_ulonglong]),
-            "fvhd_op_dec_sample": (ci, [vp, vp, ci, ci, cf, ci, cf, C.c_ulonglong, ci, vp, vp, vp]),
-        })
-    if lib.fvhd_version() >= W8_VERSION:           # an older library loads without them; w8_lib() then names the rebuild
-        sig.update({
-            "fvhd_llm_set_weight_format": (ci, [vp, ci]),
-            "fvhd_llm_weight_bytes": (ci, [vp, C.POINTER(C.c_size_t)]),
-            "fvhd_llm_debug_packed_e4m3": (ci, [vp, ci, ci, vp, vp, vp]),
-            "fvhd_op_quantize_e4m3": (ci, [vp, vp, ci, ci, vp, vp]),
-            "fvhd_op_dec_gemm_w8": (ci, [vp, ci, vp, ci, vp, cf, vp, vp, ci, ci, vp, vp, vp, vp, ci]),
-            "fvhd_op_dec_qkv_w8": (ci, [vp, vp, ci, ci, vp, cf, vp, vp, vp, vp, vp, vp, ci, cf, vp, vp, ci, vp, ci, ci, ci, vp, vp, ci]),
-            "fvhd_op_dec_lm_argmax_w8": (ci, [vp, vp, ci, vp, cf, vp, vp, ci, ci, vp, vp, vp, vp]),
-        })
-    if lib.fvhd_version() >= BEAM_VERSION:         # an older library loads without them; beam_lib() then names the rebuild
-        sig.update({
-            "fvhd_llm_beam_reserve": (ci, [vp]),
-            "fvhd_llm_cache_gather": (ci, [vp, vp, ci, ci, vp]),
-            "fvhd_llm_beam_topk": (ci, [vp, vp, vp, ci, ci, ci, vp, vp, vp]),
-            "fvhd_op_dec_beam_topk": (ci, [vp, vp, vp, ci, ci, ci, ci, vp, vp]),
-            "fvhd_op_dec_cache_gather": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp]),
-        })
-    if lib.fvhd_version() >= PROCESSORS_VERSION:   # an older library loads without them; processors_lib() then names the rebuild
-        sig.update({
-            "fvhd_llm_set_logits_processors": (ci, [vp, cf, ci, ci, vp, ci, vp, ci]),
-            "fvhd_op_dec_logits_process": (ci, [vp, vp, ci, ci, vp, ci, ci, cf, ci, ci, vp, ci, vp, ci]),
-        })
-    if lib.fvhd_version() >= LOOKUP_VERSION:       # an older library loads without them; lookup_lib() then names the rebuild
-        sig.update({
-            "fvhd_llm_spec_reserve": (ci, [vp, ci, ci]),
-            "fvhd_llm_verify": (ci, [vp, vp, ci, vp, vp, vp, vp]),
-            "fvhd_llm_lookup_begin": (ci, [vp, vp, ci, vp, ci, ci, vp, vp]),
-            "fvhd_llm_lookup_step": (ci, [vp, ci, ci, vp]),
-            "fvhd_llm_lookup_state": (ci, [vp] + [C.POINTER(ci)] * 4),
-            "fvhd_op_dec_attention_multi": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, ci]),
-            "fvhd_op_dec_lookup_draft": (ci, [vp, vp, vp, ci, ci, vp]),
-            "fvhd_op_dec_lookup_accept": (ci, [vp, vp, vp, ci, vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, ci]),
-        })
-    if lib.fvhd_version() >= GEMM_PLAN_VERSION:    # an older library loads without it; gemm_plan_lib() then names the rebuild
-        sig.update({"fvhd_gemm_kernel_plan": (ci, [ci, ci, ci, ci, ci])})
-    if lib.fvhd_version() >= EXTEND_VERSION:       # an older library loads without them; extend_lib() then names the rebuild
-        sig.update({
-            "fvhd_llm_extend": (ci, [vp, vp, ci, vp, vp, ci, vp, vp, vp]),
-            "fvhd_llm_cache_rewind": (ci, [vp, vp, vp]),
-            "fvhd_op_attention_extend": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]),
-            "fvhd_op_cache_append": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]),
-            "fvhd_op_extend_positions": (ci, [vp, vp, vp, vp, ci, ci]),
-            "fvhd_op_cache_rewind": (ci, [vp, vp, ci, vp, vp, ci, vp, vp]),
-        })
-    if hasattr(lib, "fvhd_op_lm_score"):           # added under 510: a 510 library built before them loads without; score_lib() then names the rebuild
-        sig.update({
-            "fvhd_lm_score_scratch_bytes": (C.c_size_t, [ci, ci, ci]),
-            "fvhd_lm_score_plan": (ci, [ci, ci, ci]),
-            "fvhd_op_lm_score": (ci, [vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, C.c_size_t]),
-            "fvhd_llm_score_reserve": (ci, [vp, ci]),
-            "fvhd_llm_score": (ci, [vp, vp, vp, vp, vp]),
-        })
-    if hasattr(lib, "fvhd_op_dec_gemm_w4"):        # added under 510: a 510 library built before them loads without; w4_lib() then names the rebuild
-        sig.update({
-            "fvhd_llm_debug_packed_mxfp4": (ci, [vp, ci, ci, vp, vp, vp]),
-            "fvhd_op_quantize_mxfp4": (ci, [vp, vp, ci, ci, vp, vp]),
-            "fvhd_op_dec_gemm_w4": (ci, [vp, ci, vp, ci, vp, cf, vp, vp, ci, ci, vp, vp, vp, vp, ci]),
-            "fvhd_op_dec_qkv_w4": (ci, [vp, vp, ci, ci, vp, cf, vp, vp, vp, vp, vp, vp, ci, cf, vp, vp, ci, vp, ci, ci, ci, vp, vp, ci]),
-            "fvhd_op_dec_lm_argmax_w4": (ci, [vp, vp, ci, vp, cf, vp, vp, ci, ci, vp, vp, vp, vp]),
-            "fvhd_op_w4_unpack": (ci, [vp, vp, vp, vp, ci, ci, ci]),
-        })
-    if hasattr(lib, "fvhd_op_dec_logprobs"):       # added under 510: a 510 library built before them loads without; logprobs_lib() then names the rebuild
-        sig.update({
-            "fvhd_dec_logprobs_scratch_bytes": (C.c_size_t, [ci, ci, ci]),
-            "fvhd_op_dec_logprobs": (ci, [vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, C.c_size_t]),
-            "fvhd_llm_set_logprobs": (ci, [vp, ci]),
-            "fvhd_llm_logprobs": (ci, [vp, vp, ci, vp, vp, vp, vp]),
-        })
-    if hasattr(lib, "fvhd_op_dec_constrain"):      # added under 510: a 510 library built before them loads without; constraint_lib() then names the rebuild
-        sig.update({
-            "fvhd_dec_constrain_slice": (ci, []),
-            "fvhd_op_dec_constrain": (ci, [vp, vp, ci, ci, vp, vp, vp, ci, vp, vp, vp]),
-            "fvhd_llm_set_constraint": (ci, [vp, vp, ci, vp, vp, ci, vp, ci]),
-            "fvhd_llm_constraint_state": (ci, [vp, vp, vp, ci]),
-        })
-    if hasattr(lib, "fvhd_llm_set_verify_sampling"):   # added under 510: a 510 library built before them loads without; lookup_sample_lib() then names the rebuild
-        sig.update({
-            "fvhd_llm_set_verify_sampling": (ci, [vp, ci]),
-            "fvhd_llm_lookup_logprobs": (ci, [vp, ci, vp, vp, vp, vp]),
-            "fvhd_op_dec_sample_rows": (ci, [vp, vp, ci, ci, cf, ci, cf, C.c_ulonglong, ci, ci, vp, vp, vp, vp, vp, vp]),
-        })
-    if hasattr(lib, "fvhd_op_dec_guidance"):       # added under 510: a 510 library built before them loads without; guidance_lib() then names the rebuild
-        sig.update({
-            "fvhd_dec_guidance_scratch_bytes": (C.c_size_t, [ci, ci]),
-            "fvhd_op_dec_guidance": (ci, [vp, vp, ci, ci, cf, vp, C.c_size_t]),
-            "fvhd_llm_set_guidance": (ci, [vp, cf]),
-        })
-    del fp, cl
+    sig = dict(BASE_SIGNATURES)
+    for name, f in FEATURES.items():
+        if _has(lib, name):
+            sig.update(f.sig)
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)     # AttributeError here = the .so does not export what fvhd.h declares
         fn.restype = res
@@ -245,146 +263,38 @@ def load():
     return _lib
 
 
-def sampling_lib():
-    """load(), for the sampling entry points: a library older than SAMPLING_VERSION loads (greedy decoding works on it) but has none of
-    them, and this says so instead of an AttributeError."""
-    lib = load()
-    got = lib.fvhd_version()
-    if got < SAMPLING_VERSION:
-        raise FvhdError(f"{LIB_PATH} reports ABI version {got}: sampling (fvhd_llm_set_sampling, fvhd_op_dec_sample) needs {SAMPLING_VERSION} - "
+def has(feature: str) -> bool:
+    """whether the loaded library has FEATURES[feature]"""
+    return _has(load(), feature)
+
+
+def require(feature: str):
+    """load(), for the entry points of FEATURES[feature]: a library without them loads (everything else works on it), and this names the
+    rebuild instead of an AttributeError"""
+    f = FEATURES[feature]
+    lib = require(f.needs) if f.needs else load()
+    if not _has(lib, feature):
+        if f.probe is None:
+            raise FvhdError(f"{LIB_PATH} reports ABI version {lib.fvhd_version()}: {f.phrase} ({f.names}) needs {f.since} - "
+                            "rebuild the library (`python -m ml_fastvlm_amd.build`)")
+        raise FvhdError(f"{LIB_PATH} (ABI version {lib.fvhd_version()}) was built before {f.phrase} ({f.names}) - "
                         "rebuild the library (`python -m ml_fastvlm_amd.build`)")
     return lib
 
 
-def w8_lib():
-    """load(), for the 8-bit weight entry points: a library older than W8_VERSION loads (bf16 weights work on it) but has none of them, and
-    this says so instead of an AttributeError."""
-    lib = load()
-    got = lib.fvhd_version()
-    if got < W8_VERSION:
-        raise FvhdError(f"{LIB_PATH} reports ABI version {got}: 8-bit weights (fvhd_llm_set_weight_format, fvhd_op_dec_gemm_w8, ...) need "
-                        f"{W8_VERSION} - rebuild the library (`python -m ml_fastvlm_amd.build`)")
-    return lib
-
-
-def beam_lib():
-    """load(), for the beam-search entry points: a library older than BEAM_VERSION loads (greedy and sampled decoding work on it) but has
-    none of them, and this says so instead of an AttributeError."""
-    lib = load()
-    got = lib.fvhd_version()
-    if got < BEAM_VERSION:
-        raise FvhdError(f"{LIB_PATH} reports ABI version {got}: beam search (fvhd_llm_beam_reserve, fvhd_llm_cache_gather, fvhd_llm_beam_topk, ...) "
-                        f"needs {BEAM_VERSION} - rebuild the library (`python -m ml_fastvlm_amd.build`)")
-    return lib
-
-
-def processors_lib():
-    """load(), for the logits-processor entry points: a library older than PROCESSORS_VERSION loads (greedy, sampled and beam decoding work
-    on it) but has none of them, and this says so instead of an AttributeError."""
-    lib = load()
-    got = lib.fvhd_version()
-    if got < PROCESSORS_VERSION:
-        raise FvhdError(f"{LIB_PATH} reports ABI version {got}: logits processors (fvhd_llm_set_logits_processors, "
-                        f"fvhd_op_dec_logits_process) need {PROCESSORS_VERSION} - rebuild the library (`python -m ml_fastvlm_amd.build`)")
-    return lib
-
-
-def lookup_lib():
-    """load(), for speculative verification and prompt-lookup decoding: a library older than LOOKUP_VERSION loads (every other way of
-    decoding works on it) but has none of the entry points, and this says so instead of an AttributeError."""
-    lib = load()
-    got = lib.fvhd_version()
-    if got < LOOKUP_VERSION:
-        raise FvhdError(f"{LIB_PATH} reports ABI version {got}: prompt-lookup decoding (fvhd_llm_spec_reserve, fvhd_llm_verify, "
-                        f"fvhd_llm_lookup_step, ...) needs {LOOKUP_VERSION} - rebuild the library (`python -m ml_fastvlm_amd.build`)")
-    return lib
-
-
-def gemm_plan_lib():
-    """load(), for fvhd_gemm_kernel_plan: a library older than GEMM_PLAN_VERSION loads (everything else works on it) but has no such query,
-    and this says so instead of an AttributeError."""
-    lib = load()
-    got = lib.fvhd_version()
-    if got < GEMM_PLAN_VERSION:
-        raise FvhdError(f"{LIB_PATH} reports ABI version {got}: the GEMM dispatch query (fvhd_gemm_kernel_plan) needs {GEMM_PLAN_VERSION} - "
-                        "rebuild the library (`python -m ml_fastvlm_amd.build`)")
-    return lib
-
-
-def extend_lib():
-    """load(), for extending / rewinding a started KV cache: a library older than EXTEND_VERSION loads (every generation that begins at an
-    empty cache works on it) but has none of the entry points, and this says so instead of an AttributeError."""
-    lib = load()
-    got = lib.fvhd_version()
-    if got < EXTEND_VERSION:
-        raise FvhdError(f"{LIB_PATH} reports ABI version {got}: extending a started cache (fvhd_llm_extend, fvhd_llm_cache_rewind, "
-                        f"fvhd_op_attention_extend, ...) needs {EXTEND_VERSION} - rebuild the library (`python -m ml_fastvlm_amd.build`)")
-    return lib
-
-
-def score_lib():
-    """load(), for scoring given tokens (fvhd_llm_score, fvhd_op_lm_score, ...): the entry points were added under FVHD_VERSION 510, so a
-    library built before them reports the same number and loads; this says so instead of an AttributeError."""
-    lib = load()
-    if not hasattr(lib, "fvhd_op_lm_score"):
-        raise FvhdError(f"{LIB_PATH} (ABI version {lib.fvhd_version()}) was built before scoring (fvhd_llm_score, fvhd_llm_score_reserve, "
-                        "fvhd_op_lm_score, ...) - rebuild the library (`python -m ml_fastvlm_amd.build`)")
-    return lib
-
-
-def w4_lib():
-    """load(), for the 4-bit (MXFP4) weight entry points: they were added under FVHD_VERSION 510, so a library built before them reports
-    the same number and loads; this says so instead of an AttributeError."""
-    lib = load()
-    if not hasattr(lib, "fvhd_op_dec_gemm_w4"):
-        raise FvhdError(f"{LIB_PATH} (ABI version {lib.fvhd_version()}) was built before 4-bit weights (FVHD_W_MXFP4, fvhd_op_quantize_mxfp4, "
-                        "fvhd_op_dec_gemm_w4, ...) - rebuild the library (`python -m ml_fastvlm_amd.build`)")
-    return lib
-
-
-def logprobs_lib():
-    """load(), for the log-probabilities of generated tokens (fvhd_llm_set_logprobs, fvhd_llm_logprobs, fvhd_op_dec_logprobs, ...): the entry
-    points were added under FVHD_VERSION 510, so a library built before them reports the same number and loads; this says so instead of an
-    AttributeError."""
-    lib = load()
-    if not hasattr(lib, "fvhd_op_dec_logprobs"):
-        raise FvhdError(f"{LIB_PATH} (ABI version {lib.fvhd_version()}) was built before the log-probabilities of generated tokens "
-                        "(fvhd_llm_set_logprobs, fvhd_llm_logprobs, fvhd_op_dec_logprobs, ...) - rebuild the library (`python -m ml_fastvlm_amd.build`)")
-    return lib
-
-
-def constraint_lib():
-    """load(), for constrained decoding (fvhd_llm_set_constraint, fvhd_llm_constraint_state, fvhd_op_dec_constrain, ...): the entry points
-    were added under FVHD_VERSION 510, so a library built before them reports the same number and loads; this says so instead of an
-    AttributeError."""
-    lib = load()
-    if not hasattr(lib, "fvhd_op_dec_constrain"):
-        raise FvhdError(f"{LIB_PATH} (ABI version {lib.fvhd_version()}) was built before constrained decoding (fvhd_llm_set_constraint, "
-                        "fvhd_llm_constraint_state, fvhd_op_dec_constrain, ...) - rebuild the library (`python -m ml_fastvlm_amd.build`)")
-    return lib
-
-
-def lookup_sample_lib():
-    """load(), for prompt-lookup decoding under sampling and with log-probabilities (fvhd_llm_set_verify_sampling, fvhd_llm_lookup_logprobs,
-    fvhd_op_dec_sample_rows): the entry points were added under FVHD_VERSION 510, so a library built before them reports the same number
-    and loads; this says so instead of an AttributeError."""
-    lib = lookup_lib()
-    if not hasattr(lib, "fvhd_llm_set_verify_sampling"):
-        raise FvhdError(f"{LIB_PATH} (ABI version {lib.fvhd_version()}) was built before prompt-lookup decoding under sampling "
-                        "(fvhd_llm_set_verify_sampling, fvhd_llm_lookup_logprobs, fvhd_op_dec_sample_rows) - rebuild the library "
-                        "(`python -m ml_fastvlm_amd.build`)")
-    return lib
-
-
-def guidance_lib():
-    """load(), for classifier-free guidance (fvhd_llm_set_guidance, fvhd_op_dec_guidance, fvhd_dec_guidance_scratch_bytes): the entry points
-    were added under FVHD_VERSION 510, so a library built before them reports the same number and loads; this says so instead of an
-    AttributeError."""
-    lib = load()
-    if not hasattr(lib, "fvhd_op_dec_guidance"):
-        raise FvhdError(f"{LIB_PATH} (ABI version {lib.fvhd_version()}) was built before classifier-free guidance (fvhd_llm_set_guidance, "
-                        "fvhd_op_dec_guidance, fvhd_dec_guidance_scratch_bytes) - rebuild the library (`python -m ml_fastvlm_amd.build`)")
-    return lib
+sampling_lib = functools.partial(require, "sampling")
+w8_lib = functools.partial(require, "w8")
+beam_lib = functools.partial(require, "beam")
+processors_lib = functools.partial(require, "processors")
+lookup_lib = functools.partial(require, "lookup")
+gemm_plan_lib = functools.partial(require, "gemm_plan")
+extend_lib = functools.partial(require, "extend")
+score_lib = functools.partial(require, "score")
+w4_lib = functools.partial(require, "w4")
+logprobs_lib = functools.partial(require, "logprobs")
+constraint_lib = functools.partial(require, "constraint")
+lookup_sample_lib = functools.partial(require, "lookup_sample")
+guidance_lib = functools.partial(require, "guidance")
 
 
 def weight_format_code(weights: str) -> int:

@@ -17,6 +17,7 @@ import re
 import torch
 import torch.nn as nn
 
+from .beam import eos_list
 from .mobileclip_encoder import MobileCLIPVisionTower
 
 
@@ -493,7 +494,7 @@ def session_keep(length_before_decode: int, tokens, eos_token_id=None):
     first n_b - 1 were fed to decode steps and belong in the cache; the last one is PENDING - chosen, never fed.  -> (keep: the cache slots
     every row keeps, length_before_decode + n_b - 1, as a list; pending int64 [B]).  Rewinding to `keep` drops the pad tokens that the
     run fed to finished rows and the steps that ran past the end between two polls."""
-    eos = [] if eos_token_id is None else ([int(eos_token_id)] if isinstance(eos_token_id, int) else [int(e) for e in eos_token_id])
+    eos = eos_list(eos_token_id)
     tokens = tokens.cpu()
     B, n = tokens.shape
     keep, pending = [], []

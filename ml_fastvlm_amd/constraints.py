@@ -16,6 +16,8 @@ from typing import List, Optional, Sequence, Tuple, Union
 
 import torch
 
+from .beam import eos_list
+
 FREE = -1                      # the state of an unconstrained row: every id allowed, never left
 MAX_STATES = 1 << 24           # limits of fvhd_llm_set_constraint (include/fvhd.h)
 MAX_EDGES = 1 << 28
@@ -164,7 +166,7 @@ class TokenAutomaton:
         """the trie of the allowed id sequences; state 0 is its root.  With EOS ids a node where a sequence ends gets one edge per EOS id
         to FREE beside its children (a sequence may be a proper prefix of another); without, the last token's edge goes to FREE and a
         sequence that is a proper prefix of another is refused.  Duplicates merge; an empty sequence is refused."""
-        eos = [] if eos_token_id is None else ([int(eos_token_id)] if isinstance(eos_token_id, int) else sorted({int(e) for e in eos_token_id}))
+        eos = sorted(set(eos_list(eos_token_id)))
         seqs = [[int(t) for t in (s.tolist() if isinstance(s, torch.Tensor) else s)] for s in sequences]
         if not seqs:
             raise ValueError("TokenAutomaton.from_sequences: no sequence given")

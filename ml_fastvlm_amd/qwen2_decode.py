@@ -49,6 +49,7 @@ from typing import NamedTuple, Optional, Sequence, Union
 import torch
 
 from . import _lib
+from .beam import eos_list
 from .qwen2_prefill import Qwen2Prefill
 
 
@@ -106,6 +107,11 @@ def _sampling_refusal(who: str, temperature, top_k, top_p) -> None:
         raise ValueError(f"{who}: top_k must be an int >= 0 (0 = off), got {top_k!r}")
     if not isinstance(top_p, (int, float)) or not 0.0 <= top_p <= 1.0:
         raise ValueError(f"{who}: top_p must be in [0, 1] (1 = off), got {top_p!r}")
+
+
+def _random_seed() -> int:
+    """63 bits from torch's default CPU generator, so `torch.manual_seed` makes a run repeat"""
+    return int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.long).item())
 
 
 def generation_position_ids(attention_mask: Optional[torch.Tensor], batch: int, seq_len: int, device=None) -> torch.Tensor:
@@ -171,6 +177,21 @@ def guidance_batch(inputs_embeds, attention_mask, position_ids, negative_inputs_
 
 
 class Qwen2Generator:
+    # the state of a generator that has started nothing (an object made without __init__ reads the same)
+    _run_batch = 0                                               # the started rows
+    _length = None                                               # the cache length as the host knows it (None: unknown - `length()` asks the device)
+    _ids_stale = False                                           # a rewind / cache_gather since the ids were chosen (`_stale_ids_refusal`)
+    _processors = None                                           # what set_logits_processors last set (None = all off)
+    _constraint = None                                           # the TokenAutomaton set_constraint last set (None = off)
+    _guidance = None                                             # the scale set_guidance last set (None = off)
+    _guided_rows = 0                                             # under guidance the G conditional rows of the last choice (0: the started batch)
+    _do_sample = _verify_sampling = False                        # what set_sampling / set_verify_sampling last set
+    _beam_reserved = False                                       # beam_reserve ran
+    _spec_rows = 0                                               # the largest row count this generator asked of spec_reserve
+    _spec_logits = _spec_ids = _spec_emitted = None              # verify()'s output buffers, made on first use
+    _last_chunk = _last_mask = _last_call = None                 # the rows, mask and call token of the last start() / extend() (`score_last`)
+    _session = None                                              # the GenerationSession whose dialogue the cache holds
+
     def __init__(self, prefill: Qwen2Prefill, batch: int, capacity: int, embed_tokens: Optional[torch.Tensor] = None,
                  tie_word_embeddings: Optional[bool] = None):
         """prefill: the context whose packed weights the steps use; batch <= 64 sequences (`_lib.MAX_DECODE_BATCH`; more than 16 need a
@@ -191,14 +212,6 @@ class Qwen2Generator:
             _lib.check(lib.fvhd_llm_cache_reserve(prefill._h, self.batch, self.capacity), "fvhd_llm_cache_reserve")
         self._logits = torch.empty((self.batch, prefill.vocab), device=self.device, dtype=torch.float32)
         self._ids = torch.zeros((self.batch,), device=self.device, dtype=torch.long)
-        self._run_batch = 0
-        self._length = None                                      # the cache length as the host knows it (None: unknown - `length()` asks the device)
-        self._processors = None                                  # what set_logits_processors last set (None = all off)
-        self._constraint = None                                  # the TokenAutomaton set_constraint last set (None = off)
-        self._guidance = None                                    # the scale set_guidance last set (None = off)
-        self._ids_stale = False                                  # a rewind / cache_gather since the ids were chosen (`_stale_ids_refusal`)
-        self._spec_rows = 0                                      # the largest row count this generator asked of spec_reserve
-        self._spec_logits = self._spec_ids = self._spec_emitted = None      # verify()'s output buffers, made on first use
 
     @classmethod
     def from_hf(cls, model, batch: int, capacity: int, prefill: Optional[Qwen2Prefill] = None, weights: str = "bf16") -> "Qwen2Generator":
@@ -234,29 +247,33 @@ class Qwen2Generator:
                                                   _lib.ptr(ids), _lib.stream_ptr(self.device)), "fvhd_llm_start")
         self._run_batch = B
         self._length = T
+        self._session = None                                     # a GenerationSession's dialogue ends where the cache is started again
+        self._note_rows(B, T, am)
+        return lg, ids
+
+    def _note_rows(self, B: int, T: int, am) -> None:
+        """behind start() / extend(): the chosen ids are fresh, and the call's rows are what score_last may score"""
         self._ids_stale = False
         self._last_chunk = self.pre._last_rows = (B, T)          # what score_last may score ...
         self._last_mask = am                                     # ... under this mask ...
         self._last_call = self.pre._last_call = object()         # ... while this call is still the context's last stack call
-        self._session = None                                     # a GenerationSession's dialogue ends where the cache is started again
-        return lg, ids
 
     # ---- extend / rewind ---------------------------------------------------------------------------------------------------------------
     def length(self) -> int:
         """the cache length: what the host tracked through start / extend / step / rewind / greedy / sample, else (after a verify or lookup
         step, whose emitted count lives on the device) one `cache_state` synchronisation"""
-        if getattr(self, "_length", None) is None:
+        if self._length is None:
             self._length = self.cache_state()[0]
         return self._length
 
     def _stale_ids_refusal(self, who: str) -> None:
         """the library's enqueue-time rule (include/fvhd.h, fvhd_llm_cache_rewind / fvhd_llm_cache_gather), raised before calling in"""
-        if getattr(self, "_ids_stale", False):
+        if self._ids_stale:
             raise ValueError(f"{who}: the ids the previous step chose belong to the rows as they were before the cache reorder / rewind "
                              "(cache_gather / rewind) - continue with extend(), or with step() on explicit ids")
 
     def _length_add(self, n: int) -> None:
-        if getattr(self, "_length", None) is not None:
+        if self._length is not None:
             self._length += int(n)
 
     @torch.no_grad()
@@ -290,10 +307,7 @@ class Qwen2Generator:
             _lib.check(_lib.extend_lib().fvhd_llm_extend(self.pre._h, _lib.ptr(x), _lib.dtype_code(x.dtype), _lib.ptr(am), _lib.ptr(pos), T, _lib.ptr(lg),
                                                          _lib.ptr(ids), _lib.stream_ptr(self.device)), "fvhd_llm_extend")
         self._length_add(T)
-        self._ids_stale = False
-        self._last_chunk = self.pre._last_rows = (B, T)
-        self._last_mask = am
-        self._last_call = self.pre._last_call = object()
+        self._note_rows(B, T, am)
         return lg, ids
 
     @torch.no_grad()
@@ -303,7 +317,7 @@ class Qwen2Generator:
         [B, T], lse fp32 [B, T]); entry [b][t] = log p(labels[b][t] | the cache before the chunk, chunk tokens < t), 0 at [b][0]: the
         first token of a chunk is predicted by the call BEFORE it (its logits were that call's return value)."""
         from .qwen2_prefill import label_aligned, score_targets
-        chunk = getattr(self, "_last_chunk", None)
+        chunk = self._last_chunk
         if chunk is None or getattr(self.pre, "_last_call", None) is not self._last_call:
             raise RuntimeError("Qwen2Generator.score_last: no start() / extend() of this generator is the context's last stack call "
                                "(a prefill or another generator's call on the same context ran since): its rows and mask are gone")
@@ -332,7 +346,7 @@ class Qwen2Generator:
         k = keep if isinstance(keep, torch.Tensor) else torch.tensor([int(v) for v in keep], dtype=torch.int32)
         if k.dim() != 1 or k.shape[0] != B or k.dtype not in (torch.int32, torch.int64):
             raise ValueError(f"rewind: keep must hold one int32 / int64 entry per started row ({B}), got {k.dtype} {tuple(k.shape)}")
-        if not on_device and (int(k.min()) < 0 or (getattr(self, "_length", None) is not None and int(k.max()) > self._length)):
+        if not on_device and (int(k.min()) < 0 or (self._length is not None and int(k.max()) > self._length)):
             raise ValueError(f"rewind: keep {k.tolist()} must lie in [0, the cache length{'' if self._length is None else ' ' + str(self._length)}]")
         new_len = None if on_device else int(k.max())
         k = k.to(device=self.device, dtype=torch.int32).contiguous()
@@ -392,22 +406,10 @@ class Qwen2Generator:
             _lib.check(_lib.logprobs_lib().fvhd_llm_logprobs(self.pre._h, _lib.ptr(logits), n, _lib.ptr(token_logprobs), _lib.ptr(top_ids),
                                                              _lib.ptr(top_logprobs), _lib.stream_ptr(self.device)), "fvhd_llm_logprobs")
 
-    @contextlib.contextmanager
-    def _logprobs_for_run(self, n):
-        """the `logprobs` keyword of greedy() / sample(): the kept-logits setting on for the run, off in a finally; None touches nothing"""
-        if n is None:
-            yield
-            return
-        self.set_logprobs(True)
-        try:
-            yield
-        finally:
-            self.set_logprobs(False)
-
     # ---- beam search: the two device operations -----------------------------------------------------------------------------------------
     def beam_reserve(self) -> None:
         """the reorder's scratch and the top-K workspace for this cache (`fvhd_llm_beam_reserve`; once per generator, synchronises)"""
-        if not getattr(self, "_beam_reserved", False):
+        if not self._beam_reserved:
             with torch.cuda.device(self.device):
                 _lib.check(_lib.beam_lib().fvhd_llm_beam_reserve(self.pre._h), "fvhd_llm_beam_reserve")
             self._beam_reserved = True
@@ -489,7 +491,7 @@ class Qwen2Generator:
             raise ValueError(f"drafts must be a contiguous 1-D int64 tensor on {self.device}")
         T = drafts.shape[0] + 1
         self._verify_refusal("verify", T)
-        if not getattr(self, "_do_sample", False) or getattr(self, "_verify_sampling", False):
+        if not self._do_sample or self._verify_sampling:
             self._stale_ids_refusal("verify")                    # (under sampling without the opt-in the library refuses, and names that
                                                                  # reason first, as it does when called directly: "sampling is on ...")
         if self._spec_rows < T:
@@ -526,10 +528,8 @@ class Qwen2Generator:
         logprobs=n (0 .. 16): -> (tokens, `GenerationLogprobs`) [, stats] as `greedy(..., logprobs=n)` returns them: a step keeps its
         logits rows, one more launch takes the values of all of them, and a small launch behind the accept keeps those of the emitted
         rows (`fvhd_llm_lookup_logprobs`) - still one graph."""
-        args = self._lookup_check("lookup_greedy", inputs_embeds, max_new_tokens, prompt_lookup_num_tokens, max_matching_ngram_size, eos_token_id,
-                                  logprobs)
-        self._set_greedy()
-        return self._lookup_run("lookup_greedy", args, inputs_embeds, attention_mask, position_ids, lookup_ids, graph, poll_every, return_stats)
+        return self._lookup("lookup_greedy", None, inputs_embeds, attention_mask, position_ids, max_new_tokens, prompt_lookup_num_tokens,
+                            max_matching_ngram_size, lookup_ids, eos_token_id, graph, poll_every, return_stats, logprobs)
 
     @torch.no_grad()
     def lookup_sample(self, inputs_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None,
@@ -544,21 +544,8 @@ class Qwen2Generator:
         - speculative sampling against a draft that puts probability 1 on one token, which is exact.  The first token is `start`'s under
         the sampling settings.  The other arguments, the return value, `return_stats` and `logprobs` are `lookup_greedy`'s; seed None:
         as in `sample`.  The opt-in and the sampling settings are restored when the run ends."""
-        args = self._lookup_check("lookup_sample", inputs_embeds, max_new_tokens, prompt_lookup_num_tokens, max_matching_ngram_size, eos_token_id,
-                                  logprobs)
-        _sampling_refusal("lookup_sample", temperature, top_k, top_p)
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.long).item())
-        _lib.lookup_sample_lib()
-        self.set_sampling(True, temperature, top_k, top_p, seed)
-        try:
-            self.set_verify_sampling(True)
-            return self._lookup_run("lookup_sample", args, inputs_embeds, attention_mask, position_ids, lookup_ids, graph, poll_every, return_stats)
-        finally:
-            try:
-                self.set_verify_sampling(False)
-            finally:
-                self.set_sampling(False)
+        return self._lookup("lookup_sample", (temperature, top_k, top_p, seed), inputs_embeds, attention_mask, position_ids, max_new_tokens,
+                            prompt_lookup_num_tokens, max_matching_ngram_size, lookup_ids, eos_token_id, graph, poll_every, return_stats, logprobs)
 
     def set_verify_sampling(self, on: bool) -> None:
         """verify() and the lookup steps follow the sampling settings from now on instead of being refused under them
@@ -568,8 +555,10 @@ class Qwen2Generator:
             _lib.check(_lib.lookup_sample_lib().fvhd_llm_set_verify_sampling(self.pre._h, int(bool(on))), "fvhd_llm_set_verify_sampling")
         self._verify_sampling = bool(on)
 
-    def _lookup_check(self, who, inputs_embeds, max_new_tokens, prompt_lookup_num_tokens, max_matching_ngram_size, eos_token_id, logprobs):
-        """the arguments of a lookup generation, checked before any device is touched -> (T, max_new_tokens, max_ngram, eos list, logprobs)"""
+    def _lookup(self, who, sampling, inputs_embeds, attention_mask, position_ids, max_new_tokens, prompt_lookup_num_tokens, max_matching_ngram_size,
+                lookup_ids, eos_token_id, graph, poll_every, return_stats, logprobs):
+        """lookup_greedy() (sampling None) and lookup_sample() (sampling = temperature, top_k, top_p, seed): the arguments, checked before any
+        device is touched, then the generation under that selection"""
         T = int(prompt_lookup_num_tokens) + 1
         self._verify_refusal(who, T)
         if max_new_tokens < 1:
@@ -582,27 +571,49 @@ class Qwen2Generator:
         if P + max_new_tokens + T - 1 > self.capacity:
             raise ValueError(f"prompt {P} + {max_new_tokens} new tokens + {T - 1} drafts need a cache of {P + max_new_tokens + T - 1} positions, "
                              f"reserved {self.capacity}")
-        eos = [] if eos_token_id is None else ([int(eos_token_id)] if isinstance(eos_token_id, int) else [int(e) for e in eos_token_id])
+        eos = eos_list(eos_token_id)
         if len(eos) > _lib.MAX_EOS_IDS:
             raise ValueError(f"{who}: at most {_lib.MAX_EOS_IDS} EOS ids (got {len(eos)})")
-        return T, int(max_new_tokens), int(max_matching_ngram_size), eos, normalize_logprobs(logprobs, self.pre.vocab)
+        n_lp = normalize_logprobs(logprobs, self.pre.vocab)
+        sampled = sampling is not None
+        if not sampled:
+            self._set_greedy()
+        else:
+            _sampling_refusal(who, *sampling[:3])
+            if sampling[3] is None:
+                sampling = sampling[:3] + (_random_seed(),)
+            _lib.lookup_sample_lib()
+        with self._for_run(sampled, self.set_sampling, (True,) + (sampling or ())):
+            try:                                                 # the opt-in inside it: the library notes it before an allocation that may fail
+                if sampled:
+                    self.set_verify_sampling(True)
+                return self._lookup_run(who, T, int(max_new_tokens), int(max_matching_ngram_size), eos, n_lp, inputs_embeds, attention_mask, position_ids,
+                                        lookup_ids, graph, poll_every, return_stats)
+            finally:
+                if sampled:
+                    self.set_verify_sampling(False)
 
-    def _lookup_run(self, who, args, inputs_embeds, attention_mask, position_ids, lookup_ids, graph, poll_every, return_stats):
+    def _lookup_run(self, who, T, max_new_tokens, max_matching_ngram_size, eos, n_lp, inputs_embeds, attention_mask, position_ids, lookup_ids, graph,
+                    poll_every, return_stats):
         """the generation of lookup_greedy / lookup_sample under the selection the caller has set"""
-        T, max_new_tokens, max_matching_ngram_size, eos, n_lp = args
         look = None
         if lookup_ids is not None:
             look = lookup_ids.reshape(-1).to(device=self.device, dtype=torch.long).contiguous()
         n_look = 0 if look is None else look.shape[0]
         lib = _lib.lookup_lib() if n_lp is None else _lib.lookup_sample_lib()
         dev = self.device
-        with self._logprobs_for_run(n_lp):
+
+        def one_step():
+            with torch.cuda.device(dev):
+                _lib.check(lib.fvhd_llm_lookup_step(self.pre._h, T, max_matching_ngram_size, _lib.stream_ptr(dev)), "fvhd_llm_lookup_step")
+
+        with self._for_run(n_lp is not None, self.set_logprobs, (True,), (False,)):
             self.spec_reserve(T, n_look)
             out = torch.zeros((max_new_tokens,), device=dev, dtype=torch.long)
             self.start(inputs_embeds, attention_mask, position_ids, logits=False)
             eos_c = (C.c_int32 * max(1, len(eos)))(*eos)
             with torch.cuda.device(dev):
-                _lib.check(lib.fvhd_llm_lookup_begin(self.pre._h, _lib.ptr(look), n_look, C.cast(eos_c, C.c_void_p), len(eos), int(max_new_tokens),
+                _lib.check(lib.fvhd_llm_lookup_begin(self.pre._h, _lib.ptr(look), n_look, C.cast(eos_c, C.c_void_p), len(eos), max_new_tokens,
                                                      _lib.ptr(out), _lib.stream_ptr(dev)), "fvhd_llm_lookup_begin")
             if n_lp is not None:
                 # aligned with `out`; the call writes the first token's entry from the logits start() left in the library's buffer
@@ -612,49 +623,26 @@ class Qwen2Generator:
                 with torch.cuda.device(dev):
                     _lib.check(lib.fvhd_llm_lookup_logprobs(self.pre._h, n_lp, _lib.ptr(out_tok), _lib.ptr(out_ids) if n_lp else None,
                                                             _lib.ptr(out_top) if n_lp else None, _lib.stream_ptr(dev)), "fvhd_llm_lookup_logprobs")
-            res, stats = self._lookup_steps(who, lib, T, max_new_tokens, max_matching_ngram_size, out, graph, poll_every)
-        ret = (res,)
+            run_step = self._captured(one_step, graph and max_new_tokens > 1)
+            written, finished, steps, tokens = self.lookup_state()
+            while not finished and written < max_new_tokens:
+                for _ in range(max(1, int(poll_every))):         # at least one token per step: at most max_new_tokens - 1 steps in all
+                    run_step()
+                before = written
+                written, finished, steps, tokens = self.lookup_state()      # host sync once per poll_every steps
+                if written == before:                            # a live step emits at least one token: the error word stopped them
+                    break
+            n, st = self.cache_state()
+            self._length = n
+            if st:
+                raise _lib.FvhdError(f"{who}: the steps left error word {st} ({', '.join(f'{k} = {v}' for k, v in _lib.CACHE_ERRORS.items())})")
+            ret = (out[:written].clone()[None],)
+        n = written
         if n_lp is not None:
-            n = res.shape[1]
             ret += (GenerationLogprobs(out_tok[:n].clone()[None], out_ids[:n].clone()[None], out_top[:n].clone()[None]),)
         if return_stats:
-            ret += (stats,)
-        return ret if len(ret) > 1 else res
-
-    def _lookup_steps(self, who, lib, T, max_new_tokens, max_matching_ngram_size, out, graph, poll_every):
-        dev = self.device
-
-        def one_step():
-            with torch.cuda.device(dev):
-                _lib.check(lib.fvhd_llm_lookup_step(self.pre._h, T, int(max_matching_ngram_size), _lib.stream_ptr(dev)), "fvhd_llm_lookup_step")
-
-        g = None
-        if graph and max_new_tokens > 1:
-            g = torch.cuda.CUDAGraph()
-            s = torch.cuda.Stream(dev)
-            s.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(s):
-                with torch.cuda.graph(g, stream=s):
-                    one_step()
-            torch.cuda.current_stream(dev).wait_stream(s)
-            # (capturing enqueues nothing: the generation's state is what lookup_begin left)
-        written, finished, steps, tokens = self.lookup_state()
-        while not finished and written < max_new_tokens:
-            for _ in range(max(1, int(poll_every))):             # at least one token per step: at most max_new_tokens - 1 steps in all
-                if g is not None:
-                    g.replay()
-                else:
-                    one_step()
-            before = written
-            written, finished, steps, tokens = self.lookup_state()      # host sync once per poll_every steps
-            if written == before:                                # a live step emits at least one token: the error word stopped them
-                break
-        n, st = self.cache_state()
-        self._length = n
-        if st:
-            raise _lib.FvhdError(f"{who}: the steps left error word {st} (1 = past the cache's capacity, 2 = a token id out of range, "
-                                 "3 = a cache reorder's row index out of range, 4 = a cache rewind's keep length out of range)")
-        return out[:written].clone()[None], {"steps": steps, "tokens": written}
+            ret += ({"steps": steps, "tokens": written},)
+        return ret if len(ret) > 1 else ret[0]
 
     def cache_state(self):
         """(length, error word) after a device synchronisation; error 1 = a step ran past the capacity, 2 = a token id out of range, 3 = a
@@ -682,7 +670,7 @@ class Qwen2Generator:
         scores.  Synchronises; a captured step keeps the settings it was captured with.  Not for beam_search."""
         from .logits_processors import normalize
         cfg = normalize(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, suppress_tokens, vocab=self.pre.vocab)
-        if cfg is None and self._processors is None and _lib.load().fvhd_version() < _lib.PROCESSORS_VERSION:
+        if cfg is None and self._processors is None and not _lib.has("processors"):
             return                                               # off on a library that has none: nothing to say
         lib = _lib.processors_lib()
         off = dict(repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, eos_token_id=[], suppress_tokens=[])
@@ -708,7 +696,7 @@ class Qwen2Generator:
             raise ValueError("set_constraint: refused while a stream is being captured (it synchronises the device and uploads tables) - set the "
                              "constraint before capturing; a captured step keeps the tables it was captured with")
         if automaton is None:
-            if self._constraint is None and not hasattr(_lib.load(), "fvhd_op_dec_constrain"):
+            if self._constraint is None and not _lib.has("constraint"):
                 return                                           # off on a library that has none: nothing to say
             with torch.cuda.device(self.device):
                 _lib.check(_lib.constraint_lib().fvhd_llm_set_constraint(self.pre._h, None, 0, None, None, 0, None, 0), "fvhd_llm_set_constraint")
@@ -742,23 +730,8 @@ class Qwen2Generator:
 
     def _constraint_refusal(self, who: str, why: str) -> None:
         """the library's refusals while a constraint is on (include/fvhd.h), raised before calling in"""
-        if getattr(self, "_constraint", None) is not None:
+        if self._constraint is not None:
             raise ValueError(f"{who}: a constraint is set (set_constraint) - {why}; clear it with set_constraint()")
-
-    @contextlib.contextmanager
-    def _constraint_for_run(self, constraint, constraint_start):
-        """the `constraint` keyword of greedy() / sample(): set for the run, cleared in a finally.  With none given, whatever set_constraint
-        set stays as it is."""
-        if constraint is None:
-            if constraint_start is not None:
-                raise ValueError("constraint_start is given without a constraint")
-            yield
-            return
-        self.set_constraint(constraint, constraint_start)
-        try:
-            yield
-        finally:
-            self.set_constraint()
 
     # ---- classifier-free guidance --------------------------------------------------------------------------------------------------------
     def set_guidance(self, scale=1.0) -> None:
@@ -770,7 +743,7 @@ class Qwen2Generator:
         on allocates the launches' scratch and synchronises; a captured step keeps the scale it was captured with.  Not for beam_search,
         verify / lookup_greedy / lookup_sample, rewind or cache_gather."""
         s = normalize_guidance(scale, "set_guidance: scale")
-        if s is None and getattr(self, "_guidance", None) is None and not hasattr(_lib.load(), "fvhd_op_dec_guidance"):
+        if s is None and self._guidance is None and not _lib.has("guidance"):
             return                                               # off on a library that has none: nothing to say
         if s is not None and torch.cuda.is_current_stream_capturing():
             raise ValueError("set_guidance: refused while a stream is being captured (the first call that switches guidance on allocates and "
@@ -781,31 +754,22 @@ class Qwen2Generator:
 
     def _choice_rows(self) -> int:
         """the rows the last start() / step() / extend() chose ids for: the started batch, under guidance its G conditional rows"""
-        return getattr(self, "_guided_rows", 0) or self._run_batch
+        return self._guided_rows or self._run_batch
 
-    def _note_choice(self, B: int) -> None:
-        on = getattr(self, "_guidance", None) is not None
+    def _guided_count(self, B: int) -> int:
+        """of B rows, the G conditional ones under guidance; 0 without it"""
+        on = self._guidance is not None
         if on and B % 2:
             raise ValueError(f"guidance is set (set_guidance) and the batch is odd ({B} rows): row g is a prompt and row B / 2 + g its negative prompt")
-        self._guided_rows = B // 2 if on else 0                  # (0: the started batch, which cache_gather may change)
+        return B // 2 if on else 0
+
+    def _note_choice(self, B: int) -> None:
+        self._guided_rows = self._guided_count(B)                # (0: the started batch, which cache_gather may change)
 
     def _guidance_refusal(self, who: str, why: str) -> None:
         """the library's refusals while guidance is on (include/fvhd.h), raised before calling in"""
-        if getattr(self, "_guidance", None) is not None:
+        if self._guidance is not None:
             raise ValueError(f"{who}: guidance is set (set_guidance) - {why}; clear it with set_guidance()")
-
-    @contextlib.contextmanager
-    def _guidance_for_run(self, scale):
-        """the `guidance_scale` keyword of greedy() / sample(): set for the run, cleared in a finally.  With none given (None or 1), whatever
-        set_guidance set stays as it is."""
-        if scale is None:
-            yield
-            return
-        self.set_guidance(scale)
-        try:
-            yield
-        finally:
-            self.set_guidance()
 
     def _guided_inputs(self, who, scale, inputs_embeds, attention_mask, position_ids, negative_inputs_embeds, negative_attention_mask,
                        negative_position_ids, continue_cache):
@@ -825,7 +789,7 @@ class Qwen2Generator:
         return s, x, m, p
 
     def _set_greedy(self) -> None:
-        if _lib.load().fvhd_version() >= _lib.SAMPLING_VERSION:      # a library without sampling is greedy anyway
+        if _lib.has("sampling"):                                 # a library without sampling is greedy anyway
             self.set_sampling(False)
 
     # ---- generation --------------------------------------------------------------------------------------------------------------------
@@ -855,15 +819,9 @@ class Qwen2Generator:
         step combines each pair's logits before the processors, the constraint, the log-probabilities and the choice, and every step feeds
         row G + g the token of row g.  The return shapes are those of G prompts; logprobs are the log-softmax of the guided scores.  With
         continue_cache=True the chunk carries both halves, for a cache that was started under guidance.  At most 32 prompts."""
-        logprobs = normalize_logprobs(logprobs, self.pre.vocab)
-        gs, inputs_embeds, attention_mask, position_ids = self._guided_inputs("greedy", guidance_scale, inputs_embeds, attention_mask, position_ids,
-                                                                              negative_inputs_embeds, negative_attention_mask, negative_position_ids,
-                                                                              continue_cache)
-        self._set_greedy()
-        with self._processors_for_run(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, suppress_tokens), \
-                self._logprobs_for_run(logprobs), self._constraint_for_run(constraint, constraint_start), self._guidance_for_run(gs):
-            return self._run(inputs_embeds, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id, graph, poll_every, continue_cache,
-                             logprobs)
+        return self._generate("greedy", None, inputs_embeds, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id, graph, poll_every,
+                              (repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, suppress_tokens), continue_cache, logprobs,
+                              constraint, constraint_start, guidance_scale, negative_inputs_embeds, negative_attention_mask, negative_position_ids)
 
     @torch.no_grad()
     def sample(self, inputs_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None,
@@ -882,44 +840,71 @@ class Qwen2Generator:
         constraint / constraint_start: as in `greedy` - the draw is made among the tokens the row's state allows.
         guidance_scale / negative_*: as in `greedy` - the draw is made from the guided scores (temperature, top-k and top-p act on them);
         row g draws with the Philox counter of row g, as without guidance."""
+        return self._generate("sample", (temperature, top_k, top_p, seed), inputs_embeds, attention_mask, position_ids, max_new_tokens, eos_token_id,
+                              pad_token_id, graph, poll_every, (repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, suppress_tokens),
+                              continue_cache, logprobs, constraint, constraint_start, guidance_scale, negative_inputs_embeds, negative_attention_mask,
+                              negative_position_ids)
+
+    def _generate(self, who, sampling, inputs_embeds, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id, graph, poll_every,
+                  processors, continue_cache, logprobs, constraint, constraint_start, guidance_scale, negative_inputs_embeds, negative_attention_mask,
+                  negative_position_ids):
+        """greedy() (sampling None) and sample() (sampling = temperature, top_k, top_p, seed): the run under its keyword settings, each set
+        for the run and cleared after it in the reverse order - sampling outermost, then the processors, the log-probabilities, the
+        constraint and the guidance"""
+        from .logits_processors import normalize
         logprobs = normalize_logprobs(logprobs, self.pre.vocab)
-        gs, inputs_embeds, attention_mask, position_ids = self._guided_inputs("sample", guidance_scale, inputs_embeds, attention_mask, position_ids,
+        gs, inputs_embeds, attention_mask, position_ids = self._guided_inputs(who, guidance_scale, inputs_embeds, attention_mask, position_ids,
                                                                               negative_inputs_embeds, negative_attention_mask, negative_position_ids,
                                                                               continue_cache)
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.long).item())
-        self.set_sampling(True, temperature, top_k, top_p, seed)
-        try:
-            with self._processors_for_run(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, suppress_tokens), \
-                    self._logprobs_for_run(logprobs), self._constraint_for_run(constraint, constraint_start), self._guidance_for_run(gs):
+        if sampling is None:
+            self._set_greedy()
+        elif sampling[3] is None:
+            sampling = sampling[:3] + (_random_seed(),)
+        with self._for_run(sampling is not None, self.set_sampling, (True,) + (sampling or ())), \
+                self._for_run(normalize(*processors, vocab=self.pre.vocab) is not None, self.set_logits_processors, processors), \
+                self._for_run(logprobs is not None, self.set_logprobs, (True,), (False,)):
+            if constraint is None and constraint_start is not None:
+                raise ValueError("constraint_start is given without a constraint")
+            with self._for_run(constraint is not None, self.set_constraint, (constraint, constraint_start)), \
+                    self._for_run(gs is not None, self.set_guidance, (gs,)):
                 return self._run(inputs_embeds, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id, graph, poll_every,
                                  continue_cache, logprobs)
-        finally:
-            self.set_sampling(False)
 
     @contextlib.contextmanager
-    def _processors_for_run(self, repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, suppress_tokens):
-        """the keyword processors of greedy() / sample(): set for the run, cleared in a finally.  With none given, whatever
-        set_logits_processors set stays as it is."""
-        from .logits_processors import normalize
-        if normalize(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, suppress_tokens, vocab=self.pre.vocab) is None:
+    def _for_run(self, asked: bool, setter, on: tuple, off: tuple = ()):
+        """a keyword of greedy() / sample() / lookup_*(): with `asked`, setter(*on) for the run and setter(*off) in a finally; without,
+        whatever the setter last set stays as it is"""
+        if not asked:
             yield
             return
-        self.set_logits_processors(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, suppress_tokens)
+        setter(*on)
         try:
             yield
         finally:
-            self.set_logits_processors()
+            setter(*off)
+
+    def _captured(self, one_step, capture: bool):
+        """what a generation loop calls per step: `one_step` itself, or with `capture` the replay of ONE graph of it, captured on a side stream
+        (capturing enqueues nothing: the state is what the calls before left)"""
+        if not capture:
+            return one_step
+        dev = self.device
+        g = torch.cuda.CUDAGraph()
+        s = torch.cuda.Stream(dev)
+        s.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(s):
+            with torch.cuda.graph(g, stream=s):
+                one_step()
+        torch.cuda.current_stream(dev).wait_stream(s)
+        return g.replay
 
     def _run(self, inputs_embeds, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id, graph, poll_every,
              continue_cache=False, logprobs=None):
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be >= 1")
         rows, T = inputs_embeds.shape[:2]
-        guided = getattr(self, "_guidance", None) is not None
-        if guided and rows % 2:
-            raise ValueError(f"guidance is set (set_guidance) and the batch is odd ({rows} rows): row g is a prompt and row B / 2 + g its negative prompt")
-        B = rows // 2 if guided else rows                        # the sequences of the result: under guidance the G conditional rows
+        guided = self._guidance is not None
+        B = self._guided_count(rows) or rows                     # the sequences of the result: under guidance the G conditional rows
         past = 0
         if continue_cache:
             if self._run_batch == 0:
@@ -928,7 +913,7 @@ class Qwen2Generator:
         if past + T + max_new_tokens - 1 > self.capacity:
             raise ValueError(f"{'the cached ' + str(past) + ' + chunk' if continue_cache else 'prompt'} {T} + {max_new_tokens} new tokens need a cache of "
                              f"{past + T + max_new_tokens - 1} positions, reserved {self.capacity}")
-        eos = [] if eos_token_id is None else ([int(eos_token_id)] if isinstance(eos_token_id, int) else [int(e) for e in eos_token_id])
+        eos = eos_list(eos_token_id)
         if eos and pad_token_id is None:
             pad_token_id = eos[0]                                # what transformers does (with a warning) when no pad token is set
         dev = self.device
@@ -971,19 +956,12 @@ class Qwen2Generator:
             alive.index_copy_(0, col, unfinished.any()[None])
             col.add_(1)
 
-        _, ids = (self.extend if continue_cache else self.start)(inputs_embeds, attention_mask, position_ids, logits=False)
-        post(ids)
+        def one_step():
+            post(self.step(fed_rows, logits=False)[1])
+
+        post((self.extend if continue_cache else self.start)(inputs_embeds, attention_mask, position_ids, logits=False)[1])
         steps = max_new_tokens - 1
-        g = None
-        if graph and steps > 0:
-            g = torch.cuda.CUDAGraph()
-            s = torch.cuda.Stream(dev)
-            s.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(s):
-                with torch.cuda.graph(g, stream=s):
-                    _, raw = self.step(fed_rows, logits=False)
-                    post(raw)
-            torch.cuda.current_stream(dev).wait_stream(s)
+        run_step = self._captured(one_step, graph and steps > 0)
         done = 0
         n = max_new_tokens
         while done < steps:
@@ -991,11 +969,7 @@ class Qwen2Generator:
             if eos and not bool(alive[done]):                    # host sync once per poll_every steps
                 break
             for _ in range(k):
-                if g is not None:
-                    g.replay()
-                else:
-                    _, raw = self.step(fed_rows, logits=False)
-                    post(raw)
+                run_step()
             done += k
         self._length = past + T + done                           # replayed steps included: the host counted them
         if eos:
@@ -1060,24 +1034,13 @@ class Qwen2Generator:
             state.update(cand_scores, cand_index)
 
         steps = max_new_tokens - 1
-        g = None
-        if graph and steps > 0:
-            g = torch.cuda.CUDAGraph()
-            s = torch.cuda.Stream(dev)
-            s.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(s):
-                with torch.cuda.graph(g, stream=s):
-                    one_step()
-            torch.cuda.current_stream(dev).wait_stream(s)
+        run_step = self._captured(one_step, graph and steps > 0)
         done = 0
         while done < steps:
             if state.finished():                                 # host sync once per poll_every steps
                 break
             for _ in range(min(poll_every, steps - done)):
-                if g is not None:
-                    g.replay()
-                else:
-                    one_step()
+                run_step()
             done += min(poll_every, steps - done)
         self._length = T + done
         tokens, scores = state.result()

@@ -124,57 +124,6 @@ def test_settings_are_checked():
         BeamSearchState(1, 2, 64, 4, early_stopping="always")
 
 
-# ---- binding ---------------------------------------------------------------------------------------------------------------------------
-BEAM_SYMBOLS = ("fvhd_llm_beam_reserve", "fvhd_llm_cache_gather", "fvhd_llm_beam_topk", "fvhd_op_dec_beam_topk", "fvhd_op_dec_cache_gather")
-
-
-def test_the_library_has_the_beam_entry_points():
-    from ml_fastvlm_amd import _lib
-    lib = _lib.load()
-    assert _lib.BEAM_VERSION == 505 <= lib.fvhd_version() and _lib.beam_lib() is lib
-    for name in BEAM_SYMBOLS:
-        assert getattr(lib, name).argtypes is not None, name
-
-
-def _stub_library(monkeypatch, version, calls):
-    """a stand-in for CDLL that reports `version` and records the symbols asked for (tests/test_w8.py's pattern)"""
-    from ml_fastvlm_amd import _lib
-
-    class _Fn:
-        def __init__(self, f):
-            self.f, self.restype, self.argtypes = f, None, None
-
-        def __call__(self, *a):
-            return self.f(*a)
-
-    class Lib:
-        fvhd_version = _Fn(lambda: version)
-
-        def __getattr__(self, name):
-            calls.append(name)
-            fn = _Fn(lambda *a: 0)
-            object.__setattr__(self, name, fn)
-            return fn
-
-    monkeypatch.setattr(_lib, "_lib", None)
-    monkeypatch.setattr(_lib.os.path, "exists", lambda p: True)
-    monkeypatch.setattr(_lib.C, "CDLL", lambda path: Lib())
-    return _lib.load()
-
-
-def test_a_504_library_loads_and_beam_search_names_the_rebuild(monkeypatch):
-    from ml_fastvlm_amd import _lib
-    asked = []
-    lib = _stub_library(monkeypatch, 504, asked)
-    assert lib.fvhd_version() == 504 and _lib.w8_lib() is lib and _lib.sampling_lib() is lib
-    assert not set(BEAM_SYMBOLS) & set(asked)                     # declared only when the library has them
-    with pytest.raises(_lib.FvhdError, match="505"):
-        _lib.beam_lib()
-    asked.clear()
-    lib = _stub_library(monkeypatch, 505, asked)
-    assert _lib.beam_lib() is lib and set(BEAM_SYMBOLS) <= set(asked)
-
-
 # ---- builder ---------------------------------------------------------------------------------------------------------------------------
 BEAMS = dict(do_sample=False, num_beams=4, max_new_tokens=8, use_cache=True)
 

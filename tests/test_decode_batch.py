@@ -10,6 +10,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import llm_testlib as L  # noqa: E402
+from binding_stub import stub  # noqa: E402
 
 
 def test_constants_and_versions():
@@ -57,26 +58,7 @@ def test_a_502_library_loads_and_a_wide_batch_names_the_rebuild(monkeypatch):
     from ml_fastvlm_amd.qwen2_decode import Qwen2Generator
     reserved = []
 
-    class Fn:
-        def __init__(self, f):
-            self.f = f
-
-        def __call__(self, *a):
-            return self.f(*a)
-
-    class Lib502:
-        fvhd_version = Fn(lambda: 502)
-        fvhd_llm_cache_reserve = Fn(lambda h, batch, cap: reserved.append((batch, cap)) or 0)
-
-        def __getattr__(self, name):
-            fn = Fn(lambda *a: 0)
-            object.__setattr__(self, name, fn)
-            return fn
-
-    monkeypatch.setattr(_lib, "_lib", None)
-    monkeypatch.setattr(_lib.os.path, "exists", lambda p: True)
-    monkeypatch.setattr(_lib.C, "CDLL", lambda path: Lib502())
-    lib = _lib.load()
+    lib = stub(monkeypatch, 502, [], fvhd_llm_cache_reserve=lambda h, batch, cap: reserved.append((batch, cap)) or 0)
     assert lib.fvhd_version() == 502
     assert _lib.sampling_lib() is lib and _lib.decode_lib(1) is lib and _lib.decode_lib(16) is lib
     with pytest.raises(_lib.FvhdError, match="503"):

@@ -1,4 +1,4 @@
-"""Extending a started KV cache, without a GPU: the version pins, the refusals of the C entry points and of the Python methods (all raised
+"""Extending a started KV cache, without a GPU: the refusals of the C entry points and of the Python methods (all raised
 before any device is looked at) and GenerationSession's chunk building and keep-length bookkeeping on plain tensors."""
 import ctypes as C
 import os
@@ -12,39 +12,6 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from ml_fastvlm_amd import GenerationSession, _lib  # noqa: E402
 from ml_fastvlm_amd.builder import session_chunk, session_keep  # noqa: E402
 from ml_fastvlm_amd.qwen2_decode import Qwen2Generator  # noqa: E402
-
-EXTEND_SYMBOLS = ["fvhd_llm_extend", "fvhd_llm_cache_rewind", "fvhd_op_attention_extend", "fvhd_op_cache_append", "fvhd_op_extend_positions",
-                  "fvhd_op_cache_rewind"]
-
-
-def test_the_library_has_the_extend_entry_points():
-    lib = _lib.load()
-    assert _lib.EXTEND_VERSION == 509 <= lib.fvhd_version() and _lib.extend_lib() is lib
-    for name in EXTEND_SYMBOLS:
-        assert getattr(lib, name).argtypes is not None, name
-
-
-def test_a_508_library_loads_and_extend_names_the_rebuild(monkeypatch):
-    class _Fn:
-        restype = argtypes = None
-
-    asked = []
-
-    class _Old:
-        def __getattr__(self, name):
-            asked.append(name)
-            fn = _Fn()
-            if name == "fvhd_version":
-                return lambda: 508
-            return fn
-
-    old = _Old()
-    _lib._declare(old)
-    assert not set(EXTEND_SYMBOLS) & set(asked)                 # declared only when the library has them
-    monkeypatch.setattr(_lib, "_lib", old)
-    assert _lib.gemm_plan_lib() is old
-    with pytest.raises(_lib.FvhdError, match="509"):
-        _lib.extend_lib()
 
 
 def test_the_entry_points_reject_bad_arguments():

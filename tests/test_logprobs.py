@@ -33,23 +33,6 @@ def test_normalize_logprobs_accepts_and_refuses():
     assert _lib.MAX_LOGPROBS == 16
 
 
-def test_a_library_built_before_them_names_the_rebuild(monkeypatch):
-    class Old:
-        def fvhd_version(self):
-            return 510
-
-    monkeypatch.setattr(_lib, "load", lambda: Old())
-    with pytest.raises(_lib.FvhdError, match="rebuild"):
-        _lib.logprobs_lib()
-
-
-def test_the_built_library_has_them_under_510():
-    lib = _lib.logprobs_lib()
-    assert lib is _lib.load() and lib.fvhd_version() == 510
-    for name in ("fvhd_dec_logprobs_scratch_bytes", "fvhd_op_dec_logprobs", "fvhd_llm_set_logprobs", "fvhd_llm_logprobs"):
-        assert getattr(lib, name).argtypes is not None, name
-
-
 def test_the_header_declares_the_four_functions_and_the_launcher_once():
     hdr = open(os.path.join(ROOT, "include", "fvhd.h")).read()
     assert "#define FVHD_VERSION 510" in hdr

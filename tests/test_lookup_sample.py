@@ -12,14 +12,6 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import llm_testlib as L  # noqa: E402
 
 
-def test_binding_declares_the_exports_under_510():
-    from ml_fastvlm_amd import _lib
-    lib = _lib.lookup_sample_lib()
-    assert lib.fvhd_version() == 510
-    for n in ("fvhd_llm_set_verify_sampling", "fvhd_llm_lookup_logprobs", "fvhd_op_dec_sample_rows"):
-        assert getattr(lib, n).argtypes is not None, n
-
-
 def test_the_entry_points_reject_bad_arguments():
     from ml_fastvlm_amd import _lib
     lib = _lib.lookup_sample_lib()
@@ -35,24 +27,6 @@ def test_the_entry_points_reject_bad_arguments():
     for (T, k, p), what in [((0.0, 50, 0.9), b"temperature"), ((0.7, -1, 0.9), b"top_k"), ((0.7, 50, 1.5), b"top_p")]:
         assert lib.fvhd_op_dec_sample_rows(None, one, 4, 64, T, k, p, 0, 0, 0, None, one, None, None, None, None) != 0
         assert what in lib.fvhd_last_error(), (T, k, p)
-
-
-def test_a_library_built_before_them_loads_and_names_the_rebuild(monkeypatch):
-    from ml_fastvlm_amd import _lib
-    real = _lib.load()
-
-    class Before:                                                # the current version number, none of the three symbols
-        def __getattr__(self, name):
-            if name in ("fvhd_llm_set_verify_sampling", "fvhd_llm_lookup_logprobs", "fvhd_op_dec_sample_rows"):
-                raise AttributeError(name)
-            return getattr(real, name)
-
-    monkeypatch.setattr(_lib, "_lib", None)
-    monkeypatch.setattr(_lib.C, "CDLL", lambda path: Before())
-    assert _lib.load().fvhd_version() == real.fvhd_version()     # loads: every other way of decoding works on it
-    _lib.lookup_lib()
-    with pytest.raises(_lib.FvhdError, match="rebuild the library"):
-        _lib.lookup_sample_lib()
 
 
 def _bare_generator(batch=1, capacity=64, run_batch=1):

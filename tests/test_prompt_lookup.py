@@ -1,9 +1,15 @@
 """Prompt-lookup decoding without a GPU: the drafting rule (`ml_fastvlm_amd.prompt_lookup.propose`, the specification of the device's
 drafter), the binding's version gate, and the refusals that `Qwen2Generator` raises before any device is touched."""
+import os
+import sys
+
 import pytest
 import torch
 
-from ml_fastvlm_amd.prompt_lookup import propose
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from binding_stub import stub  # noqa: E402
+
+from ml_fastvlm_amd.prompt_lookup import propose  # noqa: E402
 
 
 # ---- the drafting rule -----------------------------------------------------------------------------------------------------------------
@@ -86,55 +92,15 @@ def test_propose_against_a_brute_force_restatement():
 
 
 # ---- binding ---------------------------------------------------------------------------------------------------------------------------
-LOOKUP_SYMBOLS = ("fvhd_llm_spec_reserve", "fvhd_llm_verify", "fvhd_llm_lookup_begin", "fvhd_llm_lookup_step", "fvhd_llm_lookup_state",
-                  "fvhd_op_dec_attention_multi", "fvhd_op_dec_lookup_draft", "fvhd_op_dec_lookup_accept")
-
-
-def test_the_library_has_the_lookup_entry_points():
-    from ml_fastvlm_amd import _lib
-    lib = _lib.load()
-    assert _lib.LOOKUP_VERSION == 507 <= lib.fvhd_version() and _lib.lookup_lib() is lib
-    for name in LOOKUP_SYMBOLS:
-        assert getattr(lib, name).argtypes is not None, name
-
-
 def test_a_506_library_loads_and_lookup_names_the_rebuild(monkeypatch):
     from ml_fastvlm_amd import _lib
-
-    class _Fn:
-        def __init__(self, f):
-            self.f, self.restype, self.argtypes = f, None, None
-
-        def __call__(self, *a):
-            return self.f(*a)
-
-    def stub(version, calls):
-        class Lib:
-            fvhd_version = _Fn(lambda: version)
-
-            def __getattr__(self, name):
-                calls.append(name)
-                fn = _Fn(lambda *a: 0)
-                object.__setattr__(self, name, fn)
-                return fn
-
-        monkeypatch.setattr(_lib, "_lib", None)
-        monkeypatch.setattr(_lib.os.path, "exists", lambda p: True)
-        monkeypatch.setattr(_lib.C, "CDLL", lambda path: Lib())
-        return _lib.load()
-
-    asked = []
-    lib = stub(506, asked)
-    assert lib.fvhd_version() == 506 and _lib.processors_lib() is lib and _lib.beam_lib() is lib
-    assert not set(LOOKUP_SYMBOLS) & set(asked)                   # declared only when the library has them
-    with pytest.raises(_lib.FvhdError, match="507"):
-        _lib.lookup_lib()
+    calls = []
+    lib = stub(monkeypatch, 506, calls)
+    assert lib.fvhd_version() == 506
     gen = _bare_generator()
     with pytest.raises(_lib.FvhdError, match="507"):
         gen.spec_reserve(4)
-    asked.clear()
-    lib = stub(507, asked)
-    assert _lib.lookup_lib() is lib and set(LOOKUP_SYMBOLS) <= set(asked)
+    assert calls == []
 
 
 def test_the_entry_points_reject_bad_arguments():

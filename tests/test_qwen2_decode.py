@@ -8,6 +8,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import llm_testlib as L  # noqa: E402
+from binding_stub import Everything, stub  # noqa: E402
 
 
 def test_stale_library_fails_with_the_abi_message(monkeypatch):
@@ -15,24 +16,8 @@ def test_stale_library_fails_with_the_abi_message(monkeypatch):
     mismatch, not an AttributeError for the first symbol it lacks"""
     from ml_fastvlm_amd import _lib
 
-    class Fn:
-        def __init__(self, f):
-            self.f = f
-
-        def __call__(self, *a):
-            return self.f(*a)
-
-    class Stale:                                    # what an older libfvhd.so looks like: version 500 and none of the decode exports
-        fvhd_version = Fn(lambda: 500)
-
-        def __getattr__(self, name):
-            raise AttributeError(name)
-
-    monkeypatch.setattr(_lib, "_lib", None)
-    monkeypatch.setattr(_lib.os.path, "exists", lambda p: True)
-    monkeypatch.setattr(_lib.C, "CDLL", lambda path: Stale())
-    with pytest.raises(_lib.FvhdError, match="ABI version 500"):
-        _lib.load()
+    with pytest.raises(_lib.FvhdError, match="ABI version 500"):    # a library of version 500 that exports nothing else
+        stub(monkeypatch, 500, [], without=Everything())
 
 
 def test_binding_declares_the_decode_exports():

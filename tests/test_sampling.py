@@ -9,6 +9,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import llm_testlib as L  # noqa: E402
+from binding_stub import stub  # noqa: E402
 
 
 @pytest.mark.parametrize("counter,key,want", [
@@ -28,14 +29,6 @@ def test_philox_uniform_is_an_fp32_value_in_unit_interval():
     x0 = philox4x32_10((3, 285, 0, 0), (0x89ABCDEF, 0x01234567))[0]
     assert u == (x0 >> 8) / 2 ** 24 and 0.0 <= u < 1.0
     assert torch.tensor(u, dtype=torch.float32).item() == u
-
-
-def test_binding_declares_the_sampling_exports():
-    from ml_fastvlm_amd import _lib
-    lib = _lib.load()
-    assert lib.fvhd_version() >= 502 and _lib.ABI_VERSION == 501
-    for n in ("fvhd_llm_set_sampling", "fvhd_op_dec_sample"):
-        assert getattr(lib, n).argtypes is not None, n
 
 
 def test_sampling_entry_points_reject_bad_arguments():
@@ -60,27 +53,7 @@ def test_a_501_library_loads_and_sampling_names_the_rebuild(monkeypatch):
     from ml_fastvlm_amd import _lib
     from ml_fastvlm_amd.qwen2_decode import Qwen2Generator
 
-    class Fn:
-        def __init__(self, f):
-            self.f = f
-
-        def __call__(self, *a):
-            return self.f(*a)
-
-    class Lib501:
-        fvhd_version = Fn(lambda: 501)
-
-        def __getattr__(self, name):
-            if name in ("fvhd_llm_set_sampling", "fvhd_op_dec_sample"):
-                raise AttributeError(name)
-            fn = Fn(lambda *a: 0)
-            object.__setattr__(self, name, fn)
-            return fn
-
-    monkeypatch.setattr(_lib, "_lib", None)
-    monkeypatch.setattr(_lib.os.path, "exists", lambda p: True)
-    monkeypatch.setattr(_lib.C, "CDLL", lambda path: Lib501())
-    lib = _lib.load()
+    lib = stub(monkeypatch, 501, [], without=("fvhd_llm_set_sampling", "fvhd_op_dec_sample"))
     assert lib.fvhd_version() == 501
     with pytest.raises(_lib.FvhdError, match="502"):
         _lib.sampling_lib()

@@ -125,18 +125,6 @@ def test_format_tables():
     assert "quantize_blocks_mxfp4" in ml_fastvlm_amd.__all__ and "dequantize_blocks_mxfp4" in ml_fastvlm_amd.__all__
 
 
-def test_a_library_built_before_them_names_the_rebuild(monkeypatch):
-    from ml_fastvlm_amd import _lib
-
-    class Old:
-        def fvhd_version(self):
-            return 510
-
-    monkeypatch.setattr(_lib, "load", lambda: Old())
-    with pytest.raises(_lib.FvhdError, match="rebuild"):
-        _lib.w4_lib()
-
-
 def test_new_entry_points_refuse_null_and_bad_arguments_with_a_message():
     """host pointers and a NULL stream: a launch would fault, the refusal comes first"""
     from ml_fastvlm_amd import _lib

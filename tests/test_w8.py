@@ -9,6 +9,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import llm_testlib as L  # noqa: E402
+from binding_stub import stub  # noqa: E402
 
 
 def _matrices():
@@ -134,37 +135,11 @@ def test_a_prefill_context_in_another_format_is_an_error_not_a_repack():
             Qwen2Generator.from_hf(m, 1, 8, prefill=pre, weights=want)
 
 
-class _Fn:
-    def __init__(self, f):
-        self.f = f
-
-    def __call__(self, *a):
-        return self.f(*a)
-
-
-def _stub_library(monkeypatch, version, calls):
-    """the pattern of tests/test_decode_batch.py: a stand-in library that reports `version` and records the calls named in `calls`"""
-    from ml_fastvlm_amd import _lib
-
-    class Lib:
-        fvhd_version = _Fn(lambda: version)
-
-        def __getattr__(self, name):
-            fn = _Fn(lambda *a: calls.append(name) or 0)
-            object.__setattr__(self, name, fn)
-            return fn
-
-    monkeypatch.setattr(_lib, "_lib", None)
-    monkeypatch.setattr(_lib.os.path, "exists", lambda p: True)
-    monkeypatch.setattr(_lib.C, "CDLL", lambda path: Lib())
-    return _lib.load()
-
-
 def test_a_503_library_loads_and_8bit_weights_name_the_rebuild(monkeypatch):
     from ml_fastvlm_amd import _lib
     from ml_fastvlm_amd.qwen2_prefill import Qwen2Prefill
     calls = []
-    lib = _stub_library(monkeypatch, 503, calls)
+    lib = stub(monkeypatch, 503, calls)
     assert lib.fvhd_version() == 503 and _lib.decode_lib(64) is lib and _lib.sampling_lib() is lib
     with pytest.raises(_lib.FvhdError, match="504"):
         _lib.w8_lib()
@@ -182,7 +157,7 @@ def test_the_weight_format_is_refused_once_a_tensor_was_set(monkeypatch):
     from ml_fastvlm_amd import _lib
     from ml_fastvlm_amd.qwen2_prefill import Qwen2Prefill
     calls = []
-    _stub_library(monkeypatch, 504, calls)
+    stub(monkeypatch, 504, calls)
     pre = Qwen2Prefill(0, 128, 1, 2, 1, 64, 128, 64)
     pre.set_weight_format("fp8_e4m3")
     assert calls.count("fvhd_llm_set_weight_format") == 1 and pre.weight_format == "fp8_e4m3"
