@@ -21,8 +21,13 @@
 //   * W1 / W2 chunk images (64*C bytes each) are pre-swizzled on the host into the exact byte order the
 //     LDS wants (16-B slot XOR swizzles that make the fragment ds_read_b128 conflict-free for the lane
 //     groups of MI355X_MICROARCH "LDS"), so staging is a linear LDS-DMA copy
-//     (global_load_lds_dwordx4: no VGPRs, no ds_write pass), double buffered per matrix, issued one
-//     iteration ahead; one barrier per chunk.  The chunk stream is CYCLIC: chunk NCH-1 is followed by chunk 0.
+//     (global_load_lds_dwordx4: no VGPRs, no ds_write pass) into a ring of THREE slots per matrix, issued two
+//     iterations ahead; one barrier per chunk, behind a COUNTED s_waitcnt vmcnt(pieces of the iteration just ended): the
+//     images an iteration reads were issued a whole iteration before the youngest ones still in flight, so the wait is
+//     normally free, and the pieces may be issued anywhere in the iteration (FVHD_FFN_RING / FVHD_FFN_PLACE*; measured in
+//     profiles/ffn_ring3_ab.md: 309.6 / 324.2 / 400.2 -> 305.3 / 311.5 / 387.7 us per launch at C = 384 / 192 / 96).
+//     LDS: 6 x 64 C bytes of rings + b1 = 150.3 / 75.3 / 37.8 KB per workgroup, 1 / 2 / 3 workgroups per CU as before.
+//     The chunk stream is CYCLIC: chunk NCH-1 is followed by chunk 0.
 //   * HBM traffic per row: A in (2C B), X in/out (4C B) - the algorithmic minimum; weights come from L2.
 //
 // Round 2 built PERSISTENT variants of this kernel (one workgroup per CU keeping the chunk pipeline going across row tiles, tile
@@ -153,20 +158,65 @@ template <int K = 0> FVHD_DEV void gelu16_dispatch(int k, GeluSt16& g, f32x2 x, 
 // Issued from inline asm, not __builtin_amdgcn_global_load_lds: with the builtin in the loop hipcc's waitcnt pass
 // degrades every counted lgkmcnt(N) of the fragment ds_reads to lgkmcnt(0) (measured: 96 counted waits without the
 // builtin, 0 with it), which exposes the full LDS latency before every MFMA.  hipcc does not count an asm load, so the
-// consumer side waits explicitly: s_waitcnt vmcnt(0) before the barrier that publishes the images (ffn_wait_dma).
+// consumer side waits explicitly: s_waitcnt vmcnt(N) before the barrier that publishes the images (ffn_wait_dma, FFN_STEP).
 // M0 is compiler-reserved: saved and restored inside the statement (cdna_hip_programming.md 5.7).
+// ffn_wait_dma<N>: at most N of this wave's VMEM operations may still be in flight - they retire in issue order, so everything but the
+// N issued last has landed (N = 0 drains the wave; the counter has 6 bits).
 #ifdef FVHD_FFN_ABL_NOWAIT      // ablation (wrong results, timing only): the chunk loop never waits for its weight DMA
-FVHD_DEV void ffn_wait_dma() {}
+template <int N = 0> FVHD_DEV void ffn_wait_dma() {}
 #else
-FVHD_DEV void ffn_wait_dma() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+template <int N = 0> FVHD_DEV void ffn_wait_dma()
+{
+    static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit counter");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
 #endif
+// Depth of the W1 / W2 chunk rings of ffn_fused_kernel (ffn_pair384_kernel keeps its two slots).  3: the images of iteration t + 2 are
+// issued during iteration t and have a whole iteration to land; the wait in front of a barrier is COUNTED (see FFN_STEP).
+// 2: the round 1-4 form - images one iteration ahead, vmcnt(0) in front of every barrier (A/B builds: -DFVHD_FFN_RING=2; per width:
+// -DFVHD_FFN_RING384=2 ...).
+#ifndef FVHD_FFN_RING
+#define FVHD_FFN_RING 3
+#endif
+#ifndef FVHD_FFN_RING384
+#define FVHD_FFN_RING384 FVHD_FFN_RING
+#endif
+#ifndef FVHD_FFN_RING192
+#define FVHD_FFN_RING192 FVHD_FFN_RING
+#endif
+#ifndef FVHD_FFN_RING96
+#define FVHD_FFN_RING96 FVHD_FFN_RING
+#endif
+template <int C> __host__ __device__ constexpr int ffn_ring() { return C == 384 ? FVHD_FFN_RING384 : C == 192 ? FVHD_FFN_RING192 : FVHD_FFN_RING96; }
+// Where in the iteration a wave issues its DMA pieces (VAR bits 128 / 256 of ffn_iter): 0 first half (the only choice with two slots:
+// the pieces must land before the next barrier), 1 spread over the whole iteration, 2 second half only.  -DFVHD_FFN_PLACE=n sets all
+// three widths (the sweep builds).  Measured per launch inside the flagship step (profiles/ffn_ring3_ab.md), placement 0 / 1 / 2:
+// C = 384: 305.8 / 305.3 / 306.5 us,  C = 192: 312.7 / 311.5 / 313.8,  C = 96: 387.7 / (= 0: one run of three pieces) / 388.9.
+#ifdef FVHD_FFN_PLACE
+#define FVHD_FFN_PLACE384 FVHD_FFN_PLACE
+#define FVHD_FFN_PLACE192 FVHD_FFN_PLACE
+#define FVHD_FFN_PLACE96 FVHD_FFN_PLACE
+#endif
+#ifndef FVHD_FFN_PLACE384
+#define FVHD_FFN_PLACE384 1
+#endif
+#ifndef FVHD_FFN_PLACE192
+#define FVHD_FFN_PLACE192 1
+#endif
+#ifndef FVHD_FFN_PLACE96
+#define FVHD_FFN_PLACE96 0
+#endif
+template <int C> __host__ __device__ constexpr int ffn_place_var()
+{
+    return ffn_ring<C>() == 2 ? 0 : 128 * (C == 384 ? FVHD_FFN_PLACE384 : C == 192 ? FVHD_FFN_PLACE192 : FVHD_FFN_PLACE96);
+}
 
 // One pipeline iteration t, for the NB 32-row blocks a wave owns:
 //     s_out <- b1(t) + GEMM1(chunk t);   p_out <- GELU(s_in = S(t-1));   O += GEMM2(chunk t-2, p_in = P(t-2)).
 // The iteration is cut into NM = 2*KS*NB slots of one MFMA each.  Fragment f (f even: W1 k-step f/2, f odd: W2 fragment
 // f/2) is read from LDS once and feeds NB consecutive slots (one per row block), so consecutive MFMAs never share an
 // accumulator, and the instruction order is pinned slot by slot with sched_barrier:
-//     slot m = { MFMA m | LDS fragment read (PF fragments ahead) | one 1-KiB LDS-DMA piece of next iteration's weights
+//     slot m = { MFMA m | LDS fragment read (PF fragments ahead) | one 1-KiB LDS-DMA piece of a later iteration's weights
 //                (some slots) | 96*NB/NM GELU half-stages (2-3 VALU each, from independent dependency chains) }
 // i.e. every 32-cycle MFMA carries a handful of independent single-issue fillers - what one wave can issue in its shadow
 // (MI355X_MICROARCH "one wave per SIMD") - instead of 200+ VALU in a lump between two MFMA bursts.
@@ -182,9 +232,13 @@ FVHD_DEV void ffn_iter(const bf16x8 (&afr)[NB][C / 16], f32x16 (&o)[NB][C / 32],
     constexpr int DW = WAVES, TP = 2 * NG, NPW = (TP + DW - 1) / DW;   // 1-KiB DMA pieces per iteration (W1 then W2), per wave
     static_assert(TP % DW == 0, "every wave issues the same number of pieces");
     // VAR (ablation / tuning bits; 0 in production): 1 no weight DMA, 2 no GELU math, 4 no GEMM2 MFMAs, 8 no GEMM1 MFMAs,
-    // 16 instruction order not pinned (hipcc schedules), 32 all DMA pieces issued in the first slots, 64 scalar (unpacked) GELU
+    // 16 instruction order not pinned (hipcc schedules), 32 all DMA pieces issued in the first slots, 64 scalar (unpacked) GELU,
+    // 128 / 256 DMA pieces spread over the whole iteration / over its second half only (three-slot ring: ffn_place_var)
     constexpr bool PIN = !(VAR & 16);
-    constexpr int DSTRIDE = (VAR & 32) ? 1 : ((NM / 2) / NPW > 0 ? (NM / 2) / NPW : 1);   // DMA issue spread over the first half
+    constexpr int PLACE = (VAR >> 7) & 3;
+    static_assert(PLACE <= 2, "placement: first half, whole iteration or second half");
+    constexpr int DBASE = PLACE == 2 ? NM / 2 : 0, DSPAN = PLACE == 1 ? NM : NM / 2;     // slots [DBASE, DBASE + DSPAN) carry the pieces
+    constexpr int DSTRIDE = (VAR & 32) ? 1 : (DSPAN / NPW > 0 ? DSPAN / NPW : 1);
     // fragment addresses = per-lane pointer (swizzle resolved once per kernel) + compile-time immediate:
     //   W1 k-step ks: w1p[ks % NA] + (ks / NA) * NA * 32;   W2 n-fragment nf, k-step kk: w2p[kk] + nf * 2048
 #define FFN_LD_W1(ks) (*(const bf16x8*)(w1p[(ks) % NA] + ring * CHB + ((ks) / NA) * NA * 32))
@@ -252,7 +306,7 @@ FVHD_DEV void ffn_iter(const bf16x8 (&afr)[NB][C / 16], f32x16 (&o)[NB][C / 32],
                 if (f + 5 < NF) wf[f + 5] = FFN_LD(f + 5);
             }
         } else if (nb == 0 && f + PF < NF && FFN_LD_ON(f + PF)) wf[f + PF] = FFN_LD(f + PF);
-        if constexpr (DO_DMA) {             // next iteration's weight images
+        if constexpr (DO_DMA) {             // the weight images of iteration t + RING - 1
 #if FVHD_FFN_DMARUN
             // RUNS of 3-4 consecutive 1-KiB pieces per statement (glds16_run: one M0 setting, scalar base + the constant lane offset,
             // the instruction offset advances the global and the LDS side together): 2-3 issue slots per piece instead of 7 (M0 save /
@@ -260,18 +314,20 @@ FVHD_DEV void ffn_iter(const bf16x8 (&afr)[NB][C / 16], f32x16 (&o)[NB][C / 32],
             // against the ~5 one wave per SIMD hides), and the per-piece form spent 84 of its ~300 instructions at C = 384 on this.
             // Waves 0-1 stream W1, waves 2-3 W2; a wave's PPW pieces are consecutive in the (linear) chunk image.
             // (DW waves: the first DW / 2 stream W1, the others W2)
-            constexpr int PPW = TP / DW, RUN = PPW % 4 == 0 ? 4 : PPW % 3 == 0 ? 3 : PPW, NRUN = PPW / RUN, RSTRIDE = (NM / 2) / NRUN > 0 ? (NM / 2) / NRUN : 1;
+            constexpr int PPW = TP / DW, RUN = PPW % 4 == 0 ? 4 : PPW % 3 == 0 ? 3 : PPW, NRUN = PPW / RUN, RSTRIDE = DSPAN / NRUN > 0 ? DSPAN / NRUN : 1;
             static_assert(TP % DW == 0 && PPW % RUN == 0 && RUN <= 4 && DW % 2 == 0 && NG % PPW == 0, "a wave's pieces lie in one matrix");
-            if (m % RSTRIDE == 0 && m / RSTRIDE < NRUN) {
+            static_assert(DBASE + (NRUN - 1) * RSTRIDE < NM, "every run has a slot");
+            if (m >= DBASE && (m - DBASE) % RSTRIDE == 0 && (m - DBASE) / RSTRIDE < NRUN) {
                 const int second = uwave >= DW / 2;                                       // wave-uniform (SGPR)
-                const unsigned pc0 = (unsigned)((uwave % (DW / 2)) * PPW + (m / RSTRIDE) * RUN) * 1024u;
+                const unsigned pc0 = (unsigned)((uwave % (DW / 2)) * PPW + ((m - DBASE) / RSTRIDE) * RUN) * 1024u;
                 const char* sb = (second ? dma_src2 : dma_src1) + pc0;
                 const unsigned dst = (second ? dma_dst2 : dma_dst1) + pc0;
                 if (second ? dma2 : dma1) glds16_run<RUN>(sb, (threadIdx.x & 63) * 16u, dst);
             }
 #else
-            if (m % DSTRIDE == 0 && m / DSTRIDE < NPW) {    // one 1-KiB piece per DSTRIDE slots
-                const int flat = (m / DSTRIDE) * DW + uwave;
+            static_assert(DBASE + (NPW - 1) * DSTRIDE < NM, "every piece has a slot");
+            if (m >= DBASE && (m - DBASE) % DSTRIDE == 0 && (m - DBASE) / DSTRIDE < NPW) {    // one 1-KiB piece per DSTRIDE slots
+                const int flat = ((m - DBASE) / DSTRIDE) * DW + uwave;
                 const int lane16 = (threadIdx.x & 63) * 16;
                 const bool second = flat >= NG;
                 const int pc = second ? flat - NG : flat;
@@ -378,18 +434,25 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(OCC,
     constexpr int HID = 4 * C, KS = C / 16, NFR = C / 32, NCH = HID / 32;
     constexpr int CHB = 64 * C;             // bytes of one W1 (or W2) chunk image
     constexpr int NG = CHB / 1024;          // 1-KiB DMA pieces per chunk image
-    static_assert(NCH % 2 == 0, "pipeline is unrolled by two");
+    // RING slots per matrix, images issued D iterations ahead; the S / P ping-pong has period 2, so the steady state is unrolled by
+    // U = lcm(2, RING) and every ring slot and parity is a compile-time constant
+    constexpr int RING = ffn_ring<C>(), D = RING - 1, U = RING == 2 ? 2 : 6;
+    constexpr int VARP = VAR | ffn_place_var<C>();
+    static_assert(RING == 2 || RING == 3, "two or three ring slots");
+    static_assert(NCH % U == 0 && NCH >= U + 2, "NCH = C / 8 = 12 / 24 / 48: a multiple of the unroll");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    // [W1 ring: 2 x CHB][W2 ring: 2 x CHB][b1 fp32 HID]   - one array: see cdna_hip_programming.md 5 item 4(a)
+    // [W1 ring: RING x CHB][W2 ring: RING x CHB][b1 fp32 HID]   - one array: see cdna_hip_programming.md 5 item 4(a)
     char* w1ring = smem;
-    char* w2ring = smem + 2 * CHB;
-    // C = 384 with the coalesced tile I/O (FVHD_FFN_CIO384): the transposing stage of the tile prologue must not sit in the W1 ring
-    // (W1[0] is streamed in while the A tile is staged), so it starts at the W2 ring and runs 4 * 24 KB = 96 KB from there, past the
-    // 4 * CHB of the rings; b1 moves behind it.  C <= 192: the stage is the (still empty) ring area itself.
+    char* w2ring = smem + RING * CHB;
+    // C = 384 with the coalesced tile I/O (FVHD_FFN_CIO384): the transposing stage of the tile prologue must not sit in the W1 slots
+    // that are streamed into while the A tile is staged (W1[0] .. W1[D - 1] -> slots 0 .. D - 1), so it starts at 2 * CHB - the W2
+    // ring with two slots, W1 slot 2 with three - and runs 4 * 24 KB = 96 KB from there: past the 4 * CHB of two-slot rings (b1 moves
+    // behind it), exactly to the end of the 6 * CHB of three-slot ones.  C <= 192: the stage is the (still empty) ring area itself.
     constexpr bool CIO = C <= 192 || FVHD_FFN_CIO384;
     constexpr int STAGE0 = (C == 384 && CIO) ? 2 * CHB : 0;
     constexpr int STAGE_END = CIO ? STAGE0 + WAVES * (32 * C * 2) : 0;     // (more than 4 waves at C <= 192: the stage outgrows the rings)
-    float* lb1 = (float*)(smem + (STAGE_END > 4 * CHB ? STAGE_END : 4 * CHB));
+    static_assert(STAGE0 == 0 || STAGE0 >= D * CHB, "the stage stays clear of the W1 slots that fill while it is in use");
+    float* lb1 = (float*)(smem + (STAGE_END > 2 * RING * CHB ? STAGE_END : 2 * RING * CHB));
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 31, half = lane >> 5;
@@ -410,12 +473,12 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(OCC,
     for (int k = 0; k < 2; ++k) w2p[k] = w2ring + w2_off(li, 2 * k + half);
 
 #define FFN_W1_FIRST()                                                                                                  \
-    _Pragma("unroll") for (int g = 0; g < (NG + WAVES - 1) / WAVES; ++g) {             /* W1[0] */                      \
-        const int piece = g * WAVES + uwave;                                                                           \
-        if (NG % WAVES == 0 || piece < NG) glds16(w1img + piece * 1024 + lane * 16, lds_w1 + piece * 1024);            \
+    _Pragma("unroll") for (int g = 0; g < (D * NG + WAVES - 1) / WAVES; ++g) {         /* W1[0 .. D - 1] -> slots 0 .. D - 1 */ \
+        const int piece = g * WAVES + uwave;              /* (chunk images and ring slots are both consecutive) */       \
+        if ((D * NG) % WAVES == 0 || piece < D * NG) glds16(w1img + piece * 1024 + lane * 16, lds_w1 + piece * 1024);  \
     }
-    // (STAGE0 != 0: the stage does not overlap the W1 ring - W1[0] streams in while the A tile is staged; the W2 ring, which the stage
-    // does overlap, is first written during iteration 1, two barriers after the last fragment read)
+    // (STAGE0 != 0: the stage does not overlap W1 slots 0 .. D - 1, which fill while the A tile is staged; the slots it does overlap are
+    // first written during iteration 0 (three slots) or 1 (two), behind the barrier that follows the last fragment read of the stage)
     if constexpr (CIO && STAGE0 != 0) { FFN_W1_FIRST() }
     bf16x8 afr[NB][KS];
     f32x16 o[NB][NFR];
@@ -473,32 +536,65 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(OCC,
         for (int r = 0; r < 8; ++r) { p0[nb][0][r] = 0; p0[nb][1][r] = 0; p1[nb][0][r] = 0; p1[nb][1][r] = 0; }
     }
 
-    // Iteration t reads W1[t] (ring slot t&1) and W2[t-2] (ring slot t&1); it issues the DMA of W1[t+1] and W2[t-1] into the
-    // other slots, which every wave finished reading before this iteration's barrier.  FFN_SYNC = vmcnt(0) (the DMA is
-    // invisible to hipcc's own counting) + barrier: the images issued during the previous iteration have landed and are
-    // visible to every wave.  (w1img carries one zero chunk past the end, so W1[t+1] is always a valid source.)
-#define FFN_DMA_ARGS(t) w1img + (size_t)((t) < NCH ? (t) + 1 : 0) * CHB, lds_w1 + (((t) + 1) & 1) * CHB, (t) < NCH, \
-                        w2img + (size_t)((t) >= 1 ? (t) - 1 : 0) * CHB, lds_w2 + (((t) + 1) & 1) * CHB, (t) >= 1, uwave
-#define FFN_SYNC() ffn_wait_dma(); __syncthreads()
+    // Iteration t reads W1[t] and W2[t-2], both from ring slot t % RING; it issues the DMA of W1[t+D] and W2[t+D-2] into slot
+    // (t+D) % RING - the slot iteration t-1 read, which every wave left before this iteration's barrier.  (w1img carries one zero
+    // chunk past the end: the source of the surplus W1 prefetches of the last D iterations, so that every iteration t < NCH issues
+    // the same PPW pieces from every wave.)
+    // FFN_STEP = ffn_wait_dma<N>() + barrier + ffn_iter.  The DMA is invisible to hipcc's own counting, so the wave waits itself, and
+    // the barrier then publishes every wave's images.  What a wave has outstanding at the wait in front of iteration t:
+    //   two slots:   the pieces of iteration t-1, which this iteration reads: N = 0 (in the tail also the X tile).
+    //   three slots: t = 0: the A tile (C = 384 without the stage) and W1[0], W1[1]: N = 0, once per tile;
+    //                1 <= t <= NCH: the PPW pieces of iteration t-2 (read now; none at t = 1) and, issued after them, the PPW pieces
+    //                of iteration t-1 (read one iteration later): N = PPW - already satisfied unless L2 is a whole iteration late;
+    //                t = NCH+1: the PPW pieces of iteration NCH-1 and, issued after them, the XN loads of the X tile (iteration
+    //                NCH issues no DMA): N = XN, so the X tile stays in flight until the epilogue asks for it.
+    // Anything else a wave might have in flight (a spill) is younger than the pieces waited for and only makes the count stricter.
+    constexpr int PPW = 2 * NG / WAVES;                 // pieces per wave and iteration (ffn_iter asserts that every wave issues as many)
+    constexpr bool XPRE = !(C == 96 && NB == 2);        // the X tile is fetched before the last two iterations (see FFN_LOAD_X)
+    constexpr int XLD = CIO ? NB * NL : NB * NFR * 4;   // VMEM loads of FFN_LOAD_X per lane
+    constexpr int XN = !XPRE ? 0 : XLD < 63 ? XLD : 63;
+    constexpr int NW = RING == 3 ? PPW : 0, NWX = RING == 3 ? XN : 0;
+#define FFN_DMA_ARGS(tt, SLOT, F1, F2) w1img + (size_t)((F1) ? ((tt) + D < NCH ? (tt) + D : NCH) : 0) * CHB, lds_w1 + (((SLOT) + D) % RING) * CHB, F1, \
+                                       w2img + (size_t)((F2) ? (tt) + D - 2 : 0) * CHB, lds_w2 + (((SLOT) + D) % RING) * CHB, F2, uwave
 #define FFN_B1PREV(cur) ((cur) == lb1 ? lb1 + (NCH - 1) * 32 : (cur) - 32)     // b1 of the chunk before `cur` (cyclic)
-    FFN_SYNC();
-    ffn_iter<C, NB, WAVES, true, false, false, !(VAR & 1), VAR, PF, F16>(afr, o, s0, s1, p1, p0, w1p, w2p, 0, lb1, FFN_B1PREV(lb1), half, FFN_DMA_ARGS(0));
-    FFN_SYNC();
-    ffn_iter<C, NB, WAVES, true, true, false, !(VAR & 1), VAR, PF, F16>(afr, o, s1, s0, p0, p1, w1p, w2p, 1, lb1 + 32, FFN_B1PREV(lb1 + 32), half, FFN_DMA_ARGS(1));
+    // PAR = t & 1: even t: S(t) -> s0, GELU(s1) -> p1, GEMM2 reads p0;  odd t: S(t) -> s1, GELU(s0) -> p0, GEMM2 reads p1
+#define FFN_STEP(DA, DB, DC, PAR, SLOT, NWAIT, F1, F2, tt, b1c)                                                                      \
+    ffn_wait_dma<NWAIT>();                                                                                                           \
+    __syncthreads();                                                                                                                 \
+    if constexpr ((PAR) == 0)                                                                                                        \
+        ffn_iter<C, NB, WAVES, DA, DB, DC, !(VAR & 1) && ((F1) || (F2)), VARP, PF, F16>(afr, o, s0, s1, p1, p0, w1p, w2p, SLOT, b1c, FFN_B1PREV(b1c), half, FFN_DMA_ARGS(tt, SLOT, F1, F2)); \
+    else                                                                                                                             \
+        ffn_iter<C, NB, WAVES, DA, DB, DC, !(VAR & 1) && ((F1) || (F2)), VARP, PF, F16>(afr, o, s1, s0, p0, p1, w1p, w2p, SLOT, b1c, FFN_B1PREV(b1c), half, FFN_DMA_ARGS(tt, SLOT, F1, F2));
+#define FFN_STEADY(i, tt) FFN_STEP(true, true, true, (i) & 1, (2 + (i)) % RING, NW, true, true, tt, lb1 + (tt) * 32)
+    FFN_STEP(true, false, false, 0, 0, 0, true, RING == 3, 0, lb1)                   // t = 0: GEMM1 only
+    FFN_STEP(true, true, false, 1, 1, NW, true, true, 1, lb1 + 32)                   // t = 1: no GEMM2 yet
+    // steady state t = 2 .. NCH-1: NCH - 2 = U k + RTAIL iterations - a loop of U, then RTAIL (0 or 4) more written out
+    constexpr int RTAIL = (NCH - 2) % U;
+    static_assert((NCH - RTAIL) % U == 2 % U && RTAIL % 2 == 0, "slot and parity of step i are those of t = 2 + i");
 #pragma unroll 1
-    for (int t = 2; t < NCH; t += 2) {
-        FFN_SYNC();                  // even t: S(t) -> s0, GELU(s1) -> p1, GEMM2 reads p0
-        ffn_iter<C, NB, WAVES, true, true, true, !(VAR & 1), VAR, PF, F16>(afr, o, s0, s1, p1, p0, w1p, w2p, 0, lb1 + t * 32, FFN_B1PREV(lb1 + t * 32), half, FFN_DMA_ARGS(t));
-        FFN_SYNC();                  // odd t:  S(t) -> s1, GELU(s0) -> p0, GEMM2 reads p1
-        ffn_iter<C, NB, WAVES, true, true, true, !(VAR & 1), VAR, PF, F16>(afr, o, s1, s0, p0, p1, w1p, w2p, 1, lb1 + (t + 1) * 32, FFN_B1PREV(lb1 + (t + 1) * 32), half, FFN_DMA_ARGS(t + 1));
+    for (int t = 2; t < NCH - RTAIL; t += U) {
+        FFN_STEADY(0, t)
+        FFN_STEADY(1, t + 1)
+        if constexpr (U == 6) {
+            FFN_STEADY(2, t + 2)
+            FFN_STEADY(3, t + 3)
+            FFN_STEADY(4, t + 4)
+            FFN_STEADY(5, t + 5)
+        }
     }
-    // the residual tile of X is fetched now, coalesced like A^T above (the A^T registers are dead from here on), so that
-    // its HBM latency hides behind the last two pipeline iterations instead of stalling the epilogue
+    if constexpr (RTAIL == 4) {
+        FFN_STEADY(0, NCH - 4)
+        FFN_STEADY(1, NCH - 3)
+        FFN_STEADY(2, NCH - 2)
+        FFN_STEADY(3, NCH - 1)
+    }
+    // the residual tile of X is fetched behind the barrier of iteration NCH, coalesced like A^T above (the A^T registers are dead from
+    // here on), so that its HBM latency hides behind the last two pipeline iterations instead of stalling the epilogue (in front of
+    // that barrier, where rounds 1-4 had it, the wait of the barrier drained it at once)
     u32x4 xq[CIO ? NB : 1][CIO ? NL : 1];
     bf16x4 xres[NB][NFR][4];
     // (C = 96 with two blocks per wave: the 48 registers of the prefetched X tile would not fit beside the pipeline's live state under
     // the 256-register limit of two waves per SIMD - there the tile is fetched after the last iteration instead)
-    constexpr bool XPRE = !(C == 96 && NB == 2);
 #define FFN_LOAD_X()                                                                                                   \
     if constexpr (CIO) {                                                                                               \
         int xln = lane;                                                                                                \
@@ -515,14 +611,18 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(OCC,
                 _Pragma("unroll") for (int q = 0; q < 4; ++q) xres[nb][nf][q] = *(const bf16x4*)(xrd + nf * 32 + 8 * q); \
         }                                                                                                              \
     }
+    // t = NCH (even): GELU(S(NCH-1) in s1) -> p1, GEMM2(chunk NCH-2) reads p0; two slots: DMA W2[NCH-1].  Written out (not FFN_STEP): the X
+    // loads go between the barrier and the iteration.
+    ffn_wait_dma<NW>();
+    __syncthreads();
     if constexpr (XPRE) { FFN_LOAD_X() }
-    FFN_SYNC();                      // t = NCH (even): GELU(S(NCH-1) in s1) -> p1, GEMM2(chunk NCH-2) reads p0; DMA W2[NCH-1]
-    ffn_iter<C, NB, WAVES, false, true, true, !(VAR & 1), VAR, PF, F16>(afr, o, s0, s1, p1, p0, w1p, w2p, 0, lb1, FFN_B1PREV(lb1), half, FFN_DMA_ARGS(NCH));
-    FFN_SYNC();                      // t = NCH + 1: GEMM2(chunk NCH-1) reads p1
-    ffn_iter<C, NB, WAVES, false, false, true, false, VAR, PF, F16>(afr, o, s1, s0, p0, p1, w1p, w2p, 1, lb1, FFN_B1PREV(lb1), half, FFN_DMA_ARGS(NCH));
+    ffn_iter<C, NB, WAVES, false, true, true, !(VAR & 1) && RING == 2, VARP, PF, F16>(afr, o, s0, s1, p1, p0, w1p, w2p, 0, lb1, FFN_B1PREV(lb1), half, FFN_DMA_ARGS(NCH, 0, false, RING == 2));
+    FFN_STEP(false, false, true, 1, 1, NWX, false, false, NCH + 1, lb1)              // t = NCH + 1: GEMM2(chunk NCH-1) reads p1
     if constexpr (!XPRE) { FFN_LOAD_X() }
 #undef FFN_LOAD_X
 #undef FFN_DMA_ARGS
+#undef FFN_STEP
+#undef FFN_STEADY
 
     // ---- epilogue.  The accumulators are in MFMA layout (lane = row li, 4 consecutive channels n0 = nf*32 + 8q + 4*half per
     // register quad); X and the output want the coalesced layout.  Two trips through the (now idle) ring area of this wave:
@@ -583,8 +683,6 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(OCC,
     }
     }
 }
-
-#undef FFN_SYNC
 
 // =====================================================================================================================
 // C = 384, half-precision form: WAVE PAIRS (round 4).  With 32 rows per wave every weight fragment read from LDS
@@ -897,7 +995,7 @@ static hipError_t launch_ffn(hipStream_t st, const bf16* A, const char* w1img, c
 {
     constexpr int ROWS = 32 * NB * WAVES;
     const int nwg = (M + ROWS - 1) / ROWS;
-    const size_t rings = (size_t)4 * 64 * C, stage_end = (C == 384 ? (FVHD_FFN_CIO384 ? (size_t)2 * 64 * C : 0) : 0) + ((C <= 192 || FVHD_FFN_CIO384) ? (size_t)WAVES * 32 * C * 2 : 0);
+    const size_t rings = (size_t)2 * ffn_ring<C>() * 64 * C, stage_end = (C == 384 ? (FVHD_FFN_CIO384 ? (size_t)2 * 64 * C : 0) : 0) + ((C <= 192 || FVHD_FFN_CIO384) ? (size_t)WAVES * 32 * C * 2 : 0);
     const size_t shmem = (stage_end > rings ? stage_end : rings) + (size_t)4 * C * 4 + 256;
     static bool attr_set[64];                // the attribute is per device
     hipError_t e = ffn_set_lds(ffn_fused_kernel<C, NB, WAVES, VAR, PF, OCC, F16>, shmem, attr_set);
