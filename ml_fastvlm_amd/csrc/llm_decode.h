@@ -52,6 +52,11 @@ struct DecSampleArgs {
     float temperature = 1.f;       // > 0
     int top_k = 0;                 // 0 = off
     float top_p = 1.f;             // 1 = off
+    float min_p = 0.f;             // the warpers behind top-p, in transformers' order (fvhd_llm_set_sampling_warpers): 0 = off
+    float typical_p = 1.f;         // 1 = off
+    float epsilon_cutoff = 0.f;    // 0 = off
+    float eta_cutoff = 0.f;        // 0 = off
+    float* info8 = nullptr;        // [B][8]: lowest kept s, kept count, Z, u, highest kept s, kept counts behind min_p / typical_p / epsilon_cutoff
     unsigned long long seed = 0;   // Philox key: low word, high word
     const int* len = nullptr;      // Philox counter (row, n = (len ? *len : 0) + n_add, 0, 0)
     int n_add = 0;

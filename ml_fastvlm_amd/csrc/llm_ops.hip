@@ -331,8 +331,11 @@ static int op_sample(const char* who, fvhd_stream_t st, DecSampleArgs& a)
 {
     const std::string w(who);
     if (!a.logits || !a.ids_out) return lfail(w + ": NULL pointer");
-    if (a.B < 1 || a.B > 16 || a.V < 1) return lfail(w + ": needs 1 <= B <= 16 and V >= 1");
+    const int bmax = a.info8 && !a.seq_rows ? 64 : 16;                         // fvhd_op_dec_sample_warpers takes the wide batch too
+    if (a.B < 1 || a.B > bmax || a.V < 1) return lfail(w + ": needs 1 <= B <= " + std::to_string(bmax) + " and V >= 1");
     if (const char* e = sampling_error(a.temperature, a.top_k, a.top_p)) return lfail(w + ": " + e);
+    const std::string we = warpers_error(a.min_p, a.typical_p, a.epsilon_cutoff, a.eta_cutoff);
+    if (!we.empty()) return lfail(w + ": " + we);
     static char* ws[64] = {};
     int dev = 0;
     hipError_t he = hipGetDevice(&dev);
@@ -367,6 +370,19 @@ int fvhd_op_dec_sample_rows(fvhd_stream_t st, const float* logits, int T, int V,
     a.u_override = u_override; a.ids_out = ids; a.info = info; a.seq_rows = 1; a.seq_row = seq_row;
     a.last = state_last; a.posv = state_position; a.len_advance = state_length;
     return op_sample("fvhd_op_dec_sample_rows", st, a);
+}
+
+int fvhd_op_dec_sample_warpers(fvhd_stream_t st, const float* logits, int B, int V, float temperature, int top_k, float top_p, float min_p,
+                               float typical_p, float epsilon_cutoff, float eta_cutoff, unsigned long long seed, int seq_rows, int seq_row, int n,
+                               const float* u_override, int64_t* ids, float* info)
+{
+    if (!info) return lfail("fvhd_op_dec_sample_warpers: NULL pointer");
+    if (seq_row < 0 || n < 0) return lfail("fvhd_op_dec_sample_warpers: seq_row and n must be >= 0");
+    DecSampleArgs a;
+    a.logits = logits; a.B = B; a.V = V; a.temperature = temperature; a.top_k = top_k; a.top_p = top_p; a.seed = seed; a.n_add = n;
+    a.min_p = min_p; a.typical_p = typical_p; a.epsilon_cutoff = epsilon_cutoff; a.eta_cutoff = eta_cutoff;
+    a.u_override = u_override; a.ids_out = ids; a.info8 = info; a.seq_rows = seq_rows != 0; a.seq_row = seq_rows ? seq_row : 0;
+    return op_sample("fvhd_op_dec_sample_warpers", st, a);
 }
 
 int fvhd_op_dec_logprobs(fvhd_stream_t st, const float* logits, const int64_t* ids, int B, int V, int top_n, float* token_logprob_out,

@@ -53,6 +53,7 @@ DecSampleArgs dec_sample_args(const fvhd_llm* c, const float* logits, int B)
 {
     DecSampleArgs a;
     a.logits = logits; a.B = B; a.V = c->V; a.temperature = c->temperature; a.top_k = c->top_k; a.top_p = c->top_p; a.seed = c->seed;
+    a.min_p = c->min_p; a.typical_p = c->typical_p; a.epsilon_cutoff = c->epsilon_cutoff; a.eta_cutoff = c->eta_cutoff;
     return a;
 }
 
@@ -306,6 +307,16 @@ const char* sampling_error(float temperature, int top_k, float top_p)
     if (top_k < 0) return "top_k must be >= 0 (0 = off)";
     if (!(top_p >= 0.f && top_p <= 1.f)) return "top_p must be in [0, 1] (1 = off)";
     return nullptr;
+}
+
+// fvhd_llm_set_sampling_warpers' rule: "" when the four are valid, else the refusal, which names the value
+std::string warpers_error(float min_p, float typical_p, float epsilon_cutoff, float eta_cutoff)
+{
+    if (!(min_p >= 0.f && min_p <= 1.f)) return "min_p must be in [0, 1] (0 = off), got " + std::to_string(min_p);
+    if (!(typical_p > 0.f && typical_p <= 1.f)) return "typical_p must be in (0, 1] (1 = off), got " + std::to_string(typical_p);
+    if (!(epsilon_cutoff >= 0.f && epsilon_cutoff < 1.f)) return "epsilon_cutoff must be in [0, 1) (0 = off), got " + std::to_string(epsilon_cutoff);
+    if (!(eta_cutoff >= 0.f && eta_cutoff < 1.f)) return "eta_cutoff must be in [0, 1) (0 = off), got " + std::to_string(eta_cutoff);
+    return "";
 }
 
 extern "C" {
@@ -839,6 +850,18 @@ int fvhd_llm_set_sampling(fvhd_llm* c, int do_sample, float temperature, int top
     c->top_k = top_k;
     c->top_p = top_p;
     c->seed = seed;
+    return 0;
+}
+
+int fvhd_llm_set_sampling_warpers(fvhd_llm* c, float min_p, float typical_p, float epsilon_cutoff, float eta_cutoff)
+{
+    if (!c) return lfail("fvhd_llm_set_sampling_warpers: ctx is NULL");
+    const std::string err = warpers_error(min_p, typical_p, epsilon_cutoff, eta_cutoff);
+    if (!err.empty()) return lfail("fvhd_llm_set_sampling_warpers: " + err);
+    c->min_p = min_p;
+    c->typical_p = typical_p;
+    c->epsilon_cutoff = epsilon_cutoff;
+    c->eta_cutoff = eta_cutoff;
     return 0;
 }
 

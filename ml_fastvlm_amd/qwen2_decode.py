@@ -109,6 +109,31 @@ def _sampling_refusal(who: str, temperature, top_k, top_p) -> None:
         raise ValueError(f"{who}: top_p must be in [0, 1] (1 = off), got {top_p!r}")
 
 
+WARPERS_OFF = dict(min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0)     # fvhd_llm_set_sampling_warpers' off values
+
+
+def normalize_warpers(who: str, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None) -> Optional[dict]:
+    """the four warpers behind top-p as `fvhd_llm_set_sampling_warpers` takes them, or None when all are off (None and the off value mean
+    off); the library's rule, raised before anything is called: touches no device"""
+    import math
+    got = dict(min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
+    out = {}
+    for k, v in got.items():
+        if v is None:
+            v = WARPERS_OFF[k]
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or math.isnan(v):
+            raise ValueError(f"{who}: {k} must be a number, got {v!r}")
+        out[k] = float(v)
+    if not 0.0 <= out["min_p"] <= 1.0:
+        raise ValueError(f"{who}: min_p must be in [0, 1] (0 = off), got {min_p!r}")
+    if not 0.0 < out["typical_p"] <= 1.0:
+        raise ValueError(f"{who}: typical_p must be in (0, 1] (1 = off), got {typical_p!r}")
+    for k in ("epsilon_cutoff", "eta_cutoff"):
+        if not 0.0 <= out[k] < 1.0:
+            raise ValueError(f"{who}: {k} must be in [0, 1) (0 = off), got {got[k]!r}")
+    return None if out == WARPERS_OFF else out
+
+
 def _random_seed() -> int:
     """63 bits from torch's default CPU generator, so `torch.manual_seed` makes a run repeat"""
     return int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.long).item())
@@ -536,15 +561,18 @@ class Qwen2Generator:
                       max_new_tokens: int = 256, temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, seed: Optional[int] = None,
                       prompt_lookup_num_tokens: int = 7, max_matching_ngram_size: int = 2, lookup_ids: Optional[torch.Tensor] = None,
                       eos_token_id: Union[None, int, Sequence[int]] = None, pad_token_id: Optional[int] = None, graph: bool = True,
-                      poll_every: int = 16, return_stats: bool = False, logprobs: Optional[int] = None):
+                      poll_every: int = 16, return_stats: bool = False, logprobs: Optional[int] = None, *, min_p: Optional[float] = None,
+                      typical_p: Optional[float] = None, epsilon_cutoff: Optional[float] = None, eta_cutoff: Optional[float] = None):
         """`sample` for ONE sequence with prompt-lookup decoding: the tokens are those of `sample(seed=s)` with the same settings and
         seed, token for token, in fewer steps wherever a draft is accepted.  Row t of a verify step draws with the Philox counter of the
         sequential step at its position (`set_verify_sampling`) on logits that have that step's bits, so the draw IS the token `sample`
         would have produced there; a draft is kept when it equals the draw, and the first draw that differs is emitted and ends the step
         - speculative sampling against a draft that puts probability 1 on one token, which is exact.  The first token is `start`'s under
         the sampling settings.  The other arguments, the return value, `return_stats` and `logprobs` are `lookup_greedy`'s; seed None:
-        as in `sample`.  The opt-in and the sampling settings are restored when the run ends."""
-        return self._lookup("lookup_sample", (temperature, top_k, top_p, seed), inputs_embeds, attention_mask, position_ids, max_new_tokens,
+        as in `sample`; min_p / typical_p / epsilon_cutoff / eta_cutoff: as in `sample` - the rows of a verify step take the warpers too.  The
+        opt-in and the sampling settings are restored when the run ends."""
+        return self._lookup("lookup_sample", (temperature, top_k, top_p, seed, normalize_warpers("lookup_sample", min_p, typical_p, epsilon_cutoff, eta_cutoff)),
+                            inputs_embeds, attention_mask, position_ids, max_new_tokens,
                             prompt_lookup_num_tokens, max_matching_ngram_size, lookup_ids, eos_token_id, graph, poll_every, return_stats, logprobs)
 
     def set_verify_sampling(self, on: bool) -> None:
@@ -557,7 +585,7 @@ class Qwen2Generator:
 
     def _lookup(self, who, sampling, inputs_embeds, attention_mask, position_ids, max_new_tokens, prompt_lookup_num_tokens, max_matching_ngram_size,
                 lookup_ids, eos_token_id, graph, poll_every, return_stats, logprobs):
-        """lookup_greedy() (sampling None) and lookup_sample() (sampling = temperature, top_k, top_p, seed): the arguments, checked before any
+        """lookup_greedy() (sampling None) and lookup_sample() (sampling = temperature, top_k, top_p, seed, warpers): the arguments, checked before any
         device is touched, then the generation under that selection"""
         T = int(prompt_lookup_num_tokens) + 1
         self._verify_refusal(who, T)
@@ -581,9 +609,11 @@ class Qwen2Generator:
         else:
             _sampling_refusal(who, *sampling[:3])
             if sampling[3] is None:
-                sampling = sampling[:3] + (_random_seed(),)
+                sampling = sampling[:3] + (_random_seed(),) + sampling[4:]
             _lib.lookup_sample_lib()
-        with self._for_run(sampled, self.set_sampling, (True,) + (sampling or ())):
+            if sampling[4] is not None:
+                _lib.sampling_warpers_lib()
+        with self._for_run(sampled, self._set_sampling_for_run, (True,) + (sampling or ())):
             try:                                                 # the opt-in inside it: the library notes it before an allocation that may fail
                 if sampled:
                     self.set_verify_sampling(True)
@@ -652,13 +682,29 @@ class Qwen2Generator:
         return n.value, st.value
 
     # ---- sampling settings ---------------------------------------------------------------------------------------------------------------
-    def set_sampling(self, do_sample: bool = False, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0) -> None:
+    def set_sampling(self, do_sample: bool = False, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0, *,
+                     min_p: Optional[float] = None, typical_p: Optional[float] = None, epsilon_cutoff: Optional[float] = None,
+                     eta_cutoff: Optional[float] = None) -> None:
         """the selection of start() / step() from now on (`fvhd_llm_set_sampling`): greedy (the default) or sampling; a captured step keeps the
-        settings it was captured with.  top_k 0 and top_p 1 are off; the seed is the Philox key (64 bits)."""
+        settings it was captured with.  top_k 0 and top_p 1 are off; the seed is the Philox key (64 bits).
+        min_p / typical_p / epsilon_cutoff / eta_cutoff: transformers' warpers behind top-p, in that order (`fvhd_llm_set_sampling_warpers`);
+        None and the off value (0, 1, 0, 0) mean off, and every call sets all four.  A library built before them takes the call as long as
+        they are off."""
+        warpers = normalize_warpers("set_sampling", min_p, typical_p, epsilon_cutoff, eta_cutoff)
         lib = _lib.sampling_lib()
+        if warpers is not None:
+            lib = _lib.sampling_warpers_lib()
         _lib.check(lib.fvhd_llm_set_sampling(self.pre._h, int(bool(do_sample)), float(temperature), int(top_k), float(top_p),
                                              int(seed) & 0xFFFFFFFFFFFFFFFF), "fvhd_llm_set_sampling")
+        if warpers is not None or _lib.has("sampling_warpers"):
+            w = warpers or WARPERS_OFF
+            _lib.check(lib.fvhd_llm_set_sampling_warpers(self.pre._h, w["min_p"], w["typical_p"], w["epsilon_cutoff"], w["eta_cutoff"]),
+                       "fvhd_llm_set_sampling_warpers")
         self._do_sample = bool(do_sample)
+
+    def _set_sampling_for_run(self, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, warpers=None) -> None:
+        """set_sampling as `_for_run` calls it: the warpers as one dict (None: off)"""
+        self.set_sampling(do_sample, temperature, top_k, top_p, seed, **(warpers or {}))
 
     # ---- logits processors ---------------------------------------------------------------------------------------------------------------
     def set_logits_processors(self, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0,
@@ -830,7 +876,9 @@ class Qwen2Generator:
                poll_every: int = 16, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0,
                suppress_tokens: Optional[Sequence[int]] = None, continue_cache: bool = False, logprobs: Optional[int] = None,
                constraint=None, constraint_start=None, guidance_scale=None, negative_inputs_embeds: Optional[torch.Tensor] = None,
-               negative_attention_mask: Optional[torch.Tensor] = None, negative_position_ids: Optional[torch.Tensor] = None):
+               negative_attention_mask: Optional[torch.Tensor] = None, negative_position_ids: Optional[torch.Tensor] = None, *,
+               min_p: Optional[float] = None, typical_p: Optional[float] = None, epsilon_cutoff: Optional[float] = None,
+               eta_cutoff: Optional[float] = None):
         """transformers' multinomial sampling (`GenerationMixin._sample` with do_sample=True, num_beams=1: temperature, then top-k, then
         top-p) on the library's steps -> new tokens [B, n], with greedy's return contract, EOS / pad bookkeeping and graph replay.
         seed None: 63 bits from torch's default CPU generator, so `torch.manual_seed` makes a run repeat.  The same seed gives the same
@@ -839,8 +887,11 @@ class Qwen2Generator:
         log-softmax of the (processed) logits BEFORE temperature / top-k / top-p, not of the distribution the draw was made from.
         constraint / constraint_start: as in `greedy` - the draw is made among the tokens the row's state allows.
         guidance_scale / negative_*: as in `greedy` - the draw is made from the guided scores (temperature, top-k and top-p act on them);
-        row g draws with the Philox counter of row g, as without guidance."""
-        return self._generate("sample", (temperature, top_k, top_p, seed), inputs_embeds, attention_mask, position_ids, max_new_tokens, eos_token_id,
+        row g draws with the Philox counter of row g, as without guidance.
+        min_p / typical_p / epsilon_cutoff / eta_cutoff: transformers' warpers between top-p and the draw, in that order (`set_sampling`),
+        set for this run and cleared after it; None and the off value mean off, and then the run enqueues what it did without them.  They
+        act behind the processors, the constraint and the guidance; logprobs are taken before them, as before top-k / top-p."""
+        return self._generate("sample", (temperature, top_k, top_p, seed, normalize_warpers("sample", min_p, typical_p, epsilon_cutoff, eta_cutoff)), inputs_embeds, attention_mask, position_ids, max_new_tokens, eos_token_id,
                               pad_token_id, graph, poll_every, (repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, suppress_tokens),
                               continue_cache, logprobs, constraint, constraint_start, guidance_scale, negative_inputs_embeds, negative_attention_mask,
                               negative_position_ids)
@@ -848,7 +899,7 @@ class Qwen2Generator:
     def _generate(self, who, sampling, inputs_embeds, attention_mask, position_ids, max_new_tokens, eos_token_id, pad_token_id, graph, poll_every,
                   processors, continue_cache, logprobs, constraint, constraint_start, guidance_scale, negative_inputs_embeds, negative_attention_mask,
                   negative_position_ids):
-        """greedy() (sampling None) and sample() (sampling = temperature, top_k, top_p, seed): the run under its keyword settings, each set
+        """greedy() (sampling None) and sample() (sampling = temperature, top_k, top_p, seed, warpers): the run under its keyword settings, each set
         for the run and cleared after it in the reverse order - sampling outermost, then the processors, the log-probabilities, the
         constraint and the guidance"""
         from .logits_processors import normalize
@@ -859,8 +910,10 @@ class Qwen2Generator:
         if sampling is None:
             self._set_greedy()
         elif sampling[3] is None:
-            sampling = sampling[:3] + (_random_seed(),)
-        with self._for_run(sampling is not None, self.set_sampling, (True,) + (sampling or ())), \
+            sampling = sampling[:3] + (_random_seed(),) + sampling[4:]
+        if sampling is not None and sampling[4] is not None:
+            _lib.sampling_warpers_lib()
+        with self._for_run(sampling is not None, self._set_sampling_for_run, (True,) + (sampling or ())), \
                 self._for_run(normalize(*processors, vocab=self.pre.vocab) is not None, self.set_logits_processors, processors), \
                 self._for_run(logprobs is not None, self.set_logprobs, (True,), (False,)):
             if constraint is None and constraint_start is not None:

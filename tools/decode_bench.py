@@ -13,6 +13,7 @@ captured graph and called eagerly, against the stock `transformers` decode loop 
     python tools/decode_bench.py --logprobs 0 5 16 --hidden 896 3584 --batch 1 64   (log-probabilities of the chosen tokens inside the step)
     python tools/decode_bench.py --constraint --hidden 896 3584 --batch 1 64        (constrained decoding: a token automaton masks the logits)
     python tools/decode_bench.py --lookup-sample 7 --hidden 896 3584 --repeats 3    (the lookup step under sampling and with log-probabilities)
+    python tools/decode_bench.py --warpers --hidden 896 3584 --batch 1 64           (min_p / typical_p / epsilon_cutoff / eta_cutoff in the sampled step)
 
 --batch takes up to 64 sequences per step (more than 16 need a library of version 503).  --repeats times the graph replay that many
 times (`graph_ms_per_token` is their median, `graph_ms_per_token_runs` all of them); --no-stock leaves the stock transformers loop (and
@@ -74,6 +75,7 @@ from __future__ import annotations
 import argparse
 import ctypes as C
 import json
+import math
 import os
 import sys
 
@@ -169,6 +171,106 @@ def measure_width(hidden: int, batches, prompt: int, new: int, dev, weights: str
     del pre, llm
     torch.cuda.empty_cache()
     return rows
+
+
+WARPER_SETTINGS = {"min_p": dict(min_p=0.05), "typical_p": dict(typical_p=0.9), "epsilon_cutoff": dict(epsilon_cutoff=3e-4),
+                   "eta_cutoff": dict(eta_cutoff=2e-3), "all_four": dict(min_p=0.05, typical_p=0.9, epsilon_cutoff=3e-4, eta_cutoff=2e-3)}
+
+
+@torch.no_grad()
+def measure_warpers(llm, pre, batch: int, prompt: int, new: int, dev, repeats: int = 3) -> dict:
+    """the sampled step (predict.py's settings) plain - `repeats` runs, whose spread the additions are read against; on a library built
+    before the warpers that is all - then with each warper alone and all four, and torch doing all four from step(logits=True) inside the
+    same captured graph (transformers' warpers restated in plain torch, and torch.multinomial: a baseline written for the measurement)"""
+    from ml_fastvlm_amd import _lib
+    from ml_fastvlm_amd.qwen2_decode import Qwen2Generator
+    hidden = llm.config.hidden_size
+    gen = Qwen2Generator(pre, batch, prompt + new + 4, embed_tokens=None if llm.config.tie_word_embeddings else llm.get_input_embeddings().weight,
+                         tie_word_embeddings=bool(llm.config.tie_word_embeddings))
+    g = torch.Generator(device=dev).manual_seed(0)
+    emb = (0.5 * torch.randn(batch, prompt, hidden, device=dev, generator=g)).to(torch.bfloat16)
+    mask = torch.ones(batch, prompt, device=dev, dtype=torch.long)
+    st = SAMPLE_SETTINGS["predict_py"]
+    res = {"hidden": hidden, "layers": llm.config.num_hidden_layers, "batch": batch, "vocab": llm.config.vocab_size, "prompt": prompt,
+           "new_tokens": new, "settings": st, "warpers": WARPER_SETTINGS}
+
+    def graph_ms(warpers, torch_job=False):
+        gen.set_sampling(True, seed=1, **st, **(warpers or {}))
+        gen.start(emb, mask, logits=False)
+        fed = torch.zeros(batch, device=dev, dtype=torch.long)
+
+        a4, NEG = WARPER_SETTINGS["all_four"], float("-inf")
+
+        def entropy_of(s):                                  # -(p log p) summed over the kept tokens (0 * -inf counts as 0: transformers' nansum)
+            logp = torch.log_softmax(s, -1)
+            return logp, -torch.nan_to_num(logp.exp() * logp, nan=0.0).sum(-1, keepdim=True)
+
+        def torch_step():
+            # transformers' warpers restated in plain torch without a host synchronisation (its EtaLogitsWarper builds a validated
+            # torch.distributions.Categorical per call, which reads a flag back and cannot be captured)
+            lg, _ = gen.step(fed, logits=True)
+            s = lg / st["temperature"]
+            s = s.masked_fill(s < s.topk(st["top_k"], -1).values[..., -1:], NEG)
+            p = torch.softmax(s, -1)
+            s = s.masked_fill(p < a4["min_p"] * p.amax(-1, keepdim=True), NEG)
+            logp, ent = entropy_of(s)
+            key, idx = torch.sort((-logp - ent).abs(), -1)
+            cum = s.gather(-1, idx).softmax(-1).cumsum(-1)
+            last = (cum < a4["typical_p"]).sum(-1, keepdim=True).clamp(max=s.shape[-1] - 1)
+            drop = key > key.gather(-1, last)
+            drop[..., :1] = False
+            s = s.masked_fill(drop.scatter(-1, idx, drop), NEG)
+            p = torch.softmax(s, -1)
+            s = s.masked_fill((p < a4["epsilon_cutoff"]) & (s < s.amax(-1, keepdim=True)), NEG)
+            logp, ent = entropy_of(s)
+            eta = (math.sqrt(a4["eta_cutoff"]) * torch.exp(-ent)).clamp(max=a4["eta_cutoff"])
+            s = s.masked_fill((logp.exp() < eta) & (s < s.amax(-1, keepdim=True)), NEG)
+            p = torch.softmax(s, -1)
+            if torch_job == "multinomial":
+                fed.copy_(torch.multinomial(p, 1)[:, 0])
+            else:                                           # the same draw as torch.multinomial makes it: argmax of p / Exp(1)
+                fed.copy_((p / torch.empty_like(p).exponential_()).argmax(-1))
+
+        one = torch_step if torch_job else (lambda: gen.step(logits=False))
+        if torch_job:
+            one()                                           # lazy initialisation stays out of the capture
+            gen.start(emb, mask, logits=False)
+        graph = torch.cuda.CUDAGraph()
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            with torch.cuda.graph(graph, stream=side):
+                one()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        graph.replay()
+        gen.start(emb, mask, logits=False)
+        ms = _ms_per(graph.replay, new, dev)
+        assert gen.cache_state() == (prompt + new, 0)
+        return ms
+
+    plain = [graph_ms(None) for _ in range(max(repeats, 3))]
+    res["plain_sample_graph_ms_per_token_runs"] = [round(x, 4) for x in plain]
+    res["plain_sample_graph_ms_per_token"] = round(sorted(plain)[len(plain) // 2], 4)
+    res["plain_spread_us"] = round(1000 * (max(plain) - min(plain)), 1)
+    if _lib.has("sampling_warpers"):
+        for name, w in WARPER_SETTINGS.items():
+            ms = graph_ms(w)
+            res[f"{name}_graph_ms_per_token"] = round(ms, 4)
+            res[f"{name}_added_us_per_token"] = round(1000 * (ms - res["plain_sample_graph_ms_per_token"]), 1)
+        for draw in ("multinomial", "exponential_argmax"):  # the second only if a capture refuses the first
+            try:
+                ms = graph_ms(None, torch_job=draw)
+            except Exception as e:
+                res[f"torch_all_four_{draw}_error"] = f"{type(e).__name__}: {str(e)[:200]}"
+                continue
+            res["torch_all_four_draw"] = draw
+            res["torch_all_four_graph_ms_per_token"] = round(ms, 4)
+            res["torch_all_four_added_us_per_token"] = round(1000 * (ms - res["plain_sample_graph_ms_per_token"]), 1)
+            break
+    gen.set_sampling(False)
+    del gen
+    torch.cuda.empty_cache()
+    return res
 
 
 SAMPLE_SETTINGS = {"predict_py": dict(temperature=0.2, top_k=50, top_p=1.0), "flat": dict(temperature=1.0, top_k=0, top_p=0.95)}
@@ -823,9 +925,31 @@ def main():
                     help="the lookup step with K drafts under greedy and under sampling, without and with --logprobs N (default 5), beside the plain step")
     ap.add_argument("--guidance", action="store_true",
                     help="the step under classifier-free guidance (--batch = prompts G, 2 G rows) against the plain step at B = 2 G and the stock loop's two forwards")
-    ap.add_argument("--out", default=None, help="--guidance: also write the JSON result to this file")
+    ap.add_argument("--warpers", action="store_true",
+                    help="the sampled step with min_p / typical_p / epsilon_cutoff / eta_cutoff, each and all, against the plain sampled step and torch")
+    ap.add_argument("--out", default=None, help="--guidance / --warpers: also write the JSON result to this file")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
+    if a.warpers:
+        from tools.ttft import build_llm
+        from ml_fastvlm_amd import _lib
+        from ml_fastvlm_amd.qwen2_prefill import Qwen2Prefill
+        rows = []
+        for h in (a.hidden if "--hidden" in sys.argv else [896, 3584]):
+            llm = build_llm(h, dev)
+            pre = Qwen2Prefill.from_hf(llm)
+            for b in a.batch:
+                rows.append(measure_warpers(llm, pre, b, a.prompt, a.new, dev, repeats=max(a.repeats, 3)))
+                torch.cuda.empty_cache()
+            del pre, llm
+            torch.cuda.empty_cache()
+        line = json.dumps({"tool": "decode_bench", "mode": "warpers", "device": torch.cuda.get_device_name(dev),
+                           "library_version": _lib.sampling_lib().fvhd_version(), "has_warpers": _lib.has("sampling_warpers"), "results": rows})
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        print(line)
+        return
     if a.guidance:
         from tools.ttft import build_llm
         from ml_fastvlm_amd import _lib
