@@ -85,7 +85,9 @@ typedef void* fvhd_stream_t; /* hipStream_t */
  * fvhd_op_dec_guidance, fvhd_llm_set_guidance; with the scale at 1 (the default) every call enqueues, refuses and allocates what it did
  * (_lib.py guidance_lib() detects the symbols).  Also added under 510 (new symbols only, the number stays): the sampling warpers behind
  * top-p - fvhd_llm_set_sampling_warpers, fvhd_op_dec_sample_warpers; with the four at their off values (the default) every call enqueues,
- * refuses and allocates what it did (_lib.py sampling_warpers_lib() detects the symbols). */
+ * refuses and allocates what it did (_lib.py sampling_warpers_lib() detects the symbols).  Also added under 510 (new symbols only, the number
+ * stays): beam-search sampling - fvhd_llm_beam_sample_reserve, fvhd_llm_beam_sample_topk, fvhd_op_dec_beam_sample; every existing call
+ * enqueues, refuses and allocates what it did (_lib.py beam_sample_lib() detects the symbols). */
 #define FVHD_VERSION 510
 int fvhd_version(void);
 const char* fvhd_last_error(void);
@@ -707,6 +709,43 @@ int fvhd_op_dec_beam_topk(fvhd_stream_t stream, const float* logits, const float
 int fvhd_op_dec_cache_gather(fvhd_stream_t stream, void* k_cache, void* v_cache, uint8_t* key_valid, int64_t* positions, const int64_t* src_rows,
                              int n_layers, int batch, int rows_in, int rows_out, int n_kv_heads, int head_dim, int capacity, const int* length,
                              int* status);
+
+/* ---- LLM beam-search sampling: the top continuations DRAWN, not ranked (added under 510) -----------------------------------------------------
+ * transformers' `_beam_search(do_sample=True)` (generate(do_sample=True, num_beams=K)): per step and prompt, log_softmax, then
+ * TemperatureLogitsWarper / TopKLogitsWarper / TopPLogitsWarper with min_tokens_to_keep = min_keep (n_eos + 1; 2 without an EOS id), +
+ * running_beam_scores, and `keep` draws without replacement from softmax over the prompt's K * V values - which is the top `keep` of the values
+ * plus independent Gumbel noise - returned in draw order with their UNPERTURBED values.  Per row r = g K + k and token v, x = logits[r][v],
+ * M = the row maximum, L = log sum exp(x - M) (the orders of fvhd_llm_beam_topk):
+ *   a[k V + v] = (((x - M) - L) / T) + score[g][k], IEEE fp32 in that order (T = 1: fvhd_llm_beam_topk's value, bit for bit);
+ *   kept: s = x / T >= max(theta_k', min(theta_p, v_m)) and x > -inf - theta_k' the max(top_k, min_keep)-th largest s (off at top_k = 0),
+ *         theta_p the sampler's top-p threshold among the top-k survivors (off at top_p = 1), v_m the min_keep-th largest s; tokens tied at a
+ *         threshold are kept as a group; a row with fewer than min_keep finite logits keeps the finite ones;
+ *   g = -log(-log u), u = (2 (w >> 9) + 1) 2^-24 with w = word v & 3 of Philox4x32-10 on the counter (r, n, v >> 2, 1), key = the seed's two
+ *         words, n = the cache length when the choice is made (fvhd_llm_set_sampling's n; its counter is (row, n, 0, 0));
+ *   the `keep` kept candidates of a prompt with the largest a + g, in descending a + g (equal keys: the lower flat index first) ->
+ *         cand_scores = their a, cand_index = k V + v; a slot that cannot be filled (fewer than `keep` kept candidates) holds (-inf, 0).
+ * A row's candidates are pre-selected by (x / T) + g, which differs from a + g by a row constant and fp32 rounding (DESIGN 4.3 has the bound).
+ * The limits are fvhd_llm_beam_topk's, and 1 <= min_keep <= keep.  A score of -1e9 (a dead beam) is an ordinary input.  Deterministic: the same
+ * logits, scores, settings, seed and n give the same bits, eager or replayed; no floating-point atomics.  min_p / typical_p / the cutoffs,
+ * logits processors, a constraint and guidance are not implemented under beams: the calls below are refused with them on where
+ * fvhd_llm_beam_topk is. */
+/* Allocates (and zeroes) the workspace of fvhd_llm_beam_sample_topk, about 7 MiB, an allocation of its own: fvhd_llm_beam_reserve and
+ * fvhd_llm_cache_reserve allocate what they did.  It does not depend on the cache: once per context.  Synchronises (refused while a stream is
+ * being captured). */
+int fvhd_llm_beam_sample_reserve(fvhd_llm* ctx);
+/* logits fp32 [groups * num_beams, vocab] (16-byte aligned), beam_scores fp32 [groups, num_beams] -> cand_scores fp32 [groups, keep],
+ * cand_index int64 [groups, keep].  n is read from the context's cache length on the device when the launch runs, so the host arguments are
+ * the same every step: capture-safe after fvhd_llm_beam_sample_reserve and fvhd_llm_cache_reserve.  2 launches, 1 + 4 per filter that is on and
+ * 1 more per block of 16 rows, then 3. */
+int fvhd_llm_beam_sample_topk(fvhd_llm* ctx, const float* logits, const float* beam_scores, int groups, int num_beams, int keep, float temperature,
+                              int top_k, float top_p, int min_keep, unsigned long long seed, float* cand_scores, int64_t* cand_index,
+                              fvhd_stream_t stream);
+/* the operation on its own (tests), on plain device pointers with n given; a process-wide workspace, allocated on first use: eager calls only.
+ * noise_override: NULL, or fp32 [rows, V] (16-byte aligned) used as g in place of Philox.  noise_out: NULL, or fp32 [rows, V] (16-byte aligned):
+ * every token's g, kept or not.  info: NULL, or fp32 [rows, 4] = (the row's threshold as s, -inf when no filter binds; kept count; M; L). */
+int fvhd_op_dec_beam_sample(fvhd_stream_t stream, const float* logits, const float* beam_scores, int groups, int num_beams, int keep, int V,
+                            float temperature, int top_k, float top_p, int min_keep, unsigned long long seed, int n, const float* noise_override,
+                            float* noise_out, float* info, float* cand_scores, int64_t* cand_index);
 
 /* ---- LLM logits processors: repetition penalty, no-repeat n-grams, min_new_tokens and token bans inside the step (version 506) ----------
  * transformers' processors for num_beams = 1 (generation/logits_process.py), applied in its order and before temperature / top-k / top-p, to

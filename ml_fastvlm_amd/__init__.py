@@ -6,7 +6,8 @@ Public surface (mirrors `llava.model.multimodal_encoder` / `multimodal_projector
     install_into_llava, `generate` (greedy generation with the Qwen2 prefill and decode steps on the library's kernels; with
     `prompt_lookup_num_tokens=K` prompt-lookup decoding, also under `logprobs=n`; `install_into_llava(generate=True, prompt_lookup=True)` runs
     transformers' own keyword on the library, sampled calls included: `Qwen2Generator.lookup_sample` returns `sample`'s tokens in fewer steps),
-    `beam_generate` (the same with beam search; `BeamSearchState` is its bookkeeping), `GenerationSession` (multi-turn generation that extends the
+    `beam_generate` (the same with beam search, with `do_sample=True` beam-search sampling: the continuations are drawn inside the step;
+    `BeamSearchState` is its bookkeeping), `GenerationSession` (multi-turn generation that extends the
     KV cache by each turn's tokens instead of prefilling the dialogue again), `process_reference` (the decode step's logits
     processors restated in plain torch), `score` (the log-likelihood of given tokens, `forward(labels=...)` per sequence, with lm_head and the
     log-softmax fused in one kernel; `GenerationSession.score` ranks candidate answers behind one prefilled image), `GenerationLogprobs` (what `generate(..., logprobs=n)`

@@ -231,11 +231,23 @@ FEATURES_LATER = {
         "fvhd_op_dec_sample_warpers": (ci, [vp, vp, ci, ci, cf, ci, cf, cf, cf, cf, cf, C.c_ulonglong, ci, ci, ci, vp, vp, vp]),
     }),
 }
+# ... and those added after tests/test_sampling_warpers.py pinned the names of FEATURES_LATER, in the same way.  tests/test_beam_sample_settings.py
+# covers them.
+FEATURES_LATEST = {
+    "beam_sample": Feature("beam-search sampling", "fvhd_llm_beam_sample_reserve, fvhd_llm_beam_sample_topk, fvhd_op_dec_beam_sample", probe="fvhd_llm_beam_sample_topk", needs="beam", sig={
+        "fvhd_llm_beam_sample_reserve": (ci, [vp]),
+        "fvhd_llm_beam_sample_topk": (ci, [vp, vp, vp, ci, ci, ci, cf, ci, cf, ci, C.c_ulonglong, vp, vp, vp]),
+        "fvhd_op_dec_beam_sample": (ci, [vp, vp, vp, ci, ci, ci, ci, cf, ci, cf, ci, C.c_ulonglong, ci, vp, vp, vp, vp, vp]),
+    }),
+}
 del vp, ci, cf
 
 
 def _feature(name: str) -> Feature:
-    return FEATURES[name] if name in FEATURES else FEATURES_LATER[name]
+    for table in (FEATURES, FEATURES_LATER):
+        if name in table:
+            return table[name]
+    return FEATURES_LATEST[name]
 
 
 def _has(lib, name: str) -> bool:
@@ -245,7 +257,7 @@ def _has(lib, name: str) -> bool:
 
 def _declare(lib) -> None:
     sig = dict(BASE_SIGNATURES)
-    for name, f in {**FEATURES, **FEATURES_LATER}.items():
+    for name, f in {**FEATURES, **FEATURES_LATER, **FEATURES_LATEST}.items():
         if _has(lib, name):
             sig.update(f.sig)
     for name, (res, args) in sig.items():
@@ -276,7 +288,7 @@ def load():
 
 
 def has(feature: str) -> bool:
-    """whether the loaded library has FEATURES[feature] (or FEATURES_LATER[feature])"""
+    """whether the loaded library has FEATURES[feature] (or FEATURES_LATER / FEATURES_LATEST[feature])"""
     return _has(load(), feature)
 
 
@@ -308,6 +320,7 @@ constraint_lib = functools.partial(require, "constraint")
 lookup_sample_lib = functools.partial(require, "lookup_sample")
 guidance_lib = functools.partial(require, "guidance")
 sampling_warpers_lib = functools.partial(require, "sampling_warpers")
+beam_sample_lib = functools.partial(require, "beam_sample")
 
 
 def weight_format_code(weights: str) -> int:

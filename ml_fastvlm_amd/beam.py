@@ -95,7 +95,9 @@ class BeamSearchState:
     @torch.no_grad()
     def update(self, topk_log_probs: torch.Tensor, topk_indices: torch.Tensor) -> None:
         """steps c (after its topk) to g of one `_beam_search` iteration.  topk_log_probs fp32 [G, keep] in descending order,
-        topk_indices int64 [G, keep] = beam * vocab + token."""
+        topk_indices int64 [G, keep] = beam * vocab + token.  Under beam-search sampling (`Qwen2Generator.beam_sample_topk`) the order
+        it is given is the DRAW order with the unperturbed scores, as transformers' `_get_top_k_continuations(do_sample=True)` returns them:
+        nothing here assumes the scores descend - the first K slots are "the top num_beams" of step e, whatever their values."""
         G, K, N, lp = self.G, self.K, self.N, self.length_penalty
         cur = self.cur
         col = cur.clamp(max=N - 1).view(1, 1, 1)                 # (a finished search may stand at N: such an update is discarded, but must index inside)

@@ -95,7 +95,7 @@ def encode_images(vision_tower, mm_projector, images):
 
 def install_into_llava(splice: bool = False, prefill: bool = False, prefill_any_dtype: bool = False, generate: bool = False,
                        llm_weights: str = "bf16", beam_search: bool = False, logits_processors: bool = False, constraints: bool = False,
-                       prompt_lookup: bool = False, guidance: bool = False, sampling_warpers: bool = False) -> None:
+                       prompt_lookup: bool = False, guidance: bool = False, sampling_warpers: bool = False, beam_sample: bool = False) -> None:
     """Make an unmodified `llava` package (the reference) build and call the MI355X tower; splice=True also routes
     `prepare_inputs_labels_for_multimodal` through the GPU splice (needs the embeddings on a HIP device); prefill=True also runs the
     PREFILL step of `LlavaQwen2ForCausalLM.forward` (`llava_qwen.py:92-103`: the first forward of `generate`, on `inputs_embeds`
@@ -107,7 +107,11 @@ def install_into_llava(splice: bool = False, prefill: bool = False, prefill_any_
     implement falls back to the reference's generate with a one-time warning.
     beam_search=True (with generate=True) lets that patched generate take the library for `num_beams` > 1 as well
     (`Qwen2Generator.beam_search`): do_sample=False, one beam group, no other processor, batch * num_beams <= 64; without it num_beams > 1
-    keeps falling back, as before.
+    keeps falling back, as before.  On its own it serves predict.py's `--num_beams` only together with `--temperature 0`: at predict.py's
+    default temperature the call is do_sample=True, which is beam-search SAMPLING.
+    beam_sample=True (with generate=True and beam_search=True) lets it take the library for do_sample=True with `num_beams` > 1 as well
+    (`Qwen2Generator.beam_search(do_sample=True)`: temperature / top-k / top-p, the continuations drawn inside the step) - predict.py's
+    `--num_beams 4` as it stands; min_p / typical_p / the cutoffs / top_h under beams keep falling back, and so does the call without the flag.
     logits_processors=True (with generate=True) lets it take the library for `repetition_penalty`, `no_repeat_ngram_size`, `min_new_tokens`
     and `suppress_tokens` too (num_beams = 1; `Qwen2Generator.set_logits_processors`); without it those settings keep falling back.
     constraints=True (with generate=True): the patched generate pops `constraint=` (a `ml_fastvlm_amd.constraints.TokenAutomaton`) and
@@ -167,6 +171,8 @@ def install_into_llava(splice: bool = False, prefill: bool = False, prefill_any_
             extra["guidance"] = True
         if sampling_warpers:
             extra["sampling_warpers"] = True
+        if beam_sample:
+            extra["beam_sample"] = True
         lq.LlavaQwen2ForCausalLM.generate = _make_library_generate(getattr(cur, "_fvhd_orig", cur), beam_search=beam_search, **extra)
 
 
@@ -390,13 +396,17 @@ def _guidance_settings(who, scale, negative_prompt_ids, negative_prompt_attentio
 @torch.no_grad()
 def beam_generate(model, input_ids, images=None, image_sizes=None, attention_mask=None, max_new_tokens: int = 256, num_beams: int = 4,
                   length_penalty: float = 1.0, early_stopping=False, num_return_sequences: int = 1, eos_token_id=None, pad_token_id=None,
-                  return_scores: bool = False, guidance_scale=None):
+                  return_scores: bool = False, guidance_scale=None, do_sample: bool = False, temperature: float = 1.0, top_k: int = 50,
+                  top_p: float = 1.0, seed=None):
     """`generate`'s counterpart for `num_beams` > 1: `LlavaQwen2ForCausalLM.generate(..., num_beams=K)` (predict.py's --num_beams) with the
     splice, the prefill, every decode step, the top continuations and the cache reorder on the library (`Qwen2Generator.beam_search`).
     Returns the new tokens [B * num_return_sequences, n] as transformers' generate(inputs_embeds=..., num_beams=K) does, with return_scores
     also its `sequences_scores`.  The model must be bf16 on a HIP device and B * num_beams <= 64.  guidance_scale: refused (beam search does
-    not take guidance)."""
-    from .qwen2_decode import normalize_guidance
+    not take guidance).  do_sample=True: generate(do_sample=True, num_beams=K) - beam search with multinomial sampling, the keywords of
+    `Qwen2Generator.beam_search` (temperature, top_k, top_p, seed; predict.py's --num_beams at its default temperature)."""
+    from .qwen2_decode import _sampling_refusal, normalize_guidance
+    if do_sample:
+        _sampling_refusal("ml_fastvlm_amd.beam_generate", temperature, top_k, top_p)
     if normalize_guidance(guidance_scale) is not None:
         raise ValueError("ml_fastvlm_amd.beam_generate: guidance_scale is not implemented under beam search - guidance runs with num_beams = 1 "
                          "(ml_fastvlm_amd.generate)")
@@ -411,6 +421,8 @@ def beam_generate(model, input_ids, images=None, image_sizes=None, attention_mas
         pad_token_id = getattr(gc, "pad_token_id", None)
     beam = dict(num_beams=int(num_beams), length_penalty=float(length_penalty), early_stopping=early_stopping,
                 num_return_sequences=int(num_return_sequences), return_scores=return_scores)
+    if do_sample:
+        beam.update(do_sample=True, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
     return _generate_on_library(model, input_ids, images, image_sizes, attention_mask, None, max_new_tokens, eos_token_id, pad_token_id, beam=beam)
 
 
@@ -778,7 +790,7 @@ def _warper_settings(gc):
 
 
 def _library_generate_settings(model, kwargs, beam_search: bool = False, processors: bool = False, prompt_lookup: bool = False, batch=None,
-                               guidance: bool = False, sampling_warpers: bool = False):
+                               guidance: bool = False, sampling_warpers: bool = False, beam_sample: bool = False):
     """transformers' own resolution of a generate(**kwargs) call (`_prepare_generation_config`, which generate itself calls: its global
     defaults such as top_k = 50, the model's generation_config, then the call's arguments) -> (settings, None) when the library can run
     it, (None, reason) when it cannot.  settings: max_new_tokens, eos_token_id, pad_token_id, `sampling` (None = greedy, else the
@@ -794,7 +806,10 @@ def _library_generate_settings(model, kwargs, beam_search: bool = False, process
     most 32; `negative_prompt_ids` / `negative_prompt_attention_mask` stop disqualifying it; settings then gains `guidance`: None while the
     scale is 1 / unset, else guidance_scale, negative_prompt_ids and negative_prompt_attention_mask for `_generate_on_library`.
     sampling_warpers=True: with num_beams = 1, `min_p`, `typical_p`, `epsilon_cutoff` and `eta_cutoff` no longer disqualify the call, and
-    under do_sample `sampling` carries those that are on (`_warper_settings`); `top_h` keeps disqualifying it."""
+    under do_sample `sampling` carries those that are on (`_warper_settings`); `top_h` keeps disqualifying it.
+    beam_sample=True (with beam_search=True): do_sample with num_beams > 1 no longer disqualifies the call; `beam` then gains do_sample,
+    temperature, top_k and top_p (the keywords of Qwen2Generator.beam_search) and `sampling` is None.  The warpers of `_WARPERS` and `top_h`
+    keep disqualifying a call with beams."""
     negative = {}
     if guidance:
         negative = {k: kwargs[k] for k in _GUIDANCE_ARGS if kwargs.get(k) is not None}
@@ -837,7 +852,7 @@ def _library_generate_settings(model, kwargs, beam_search: bool = False, process
             proc.pop("eos_token_id")                                 # greedy / sample take the run's own eos_token_id
     beam = None
     if beams is not None:
-        if gc.do_sample:
+        if gc.do_sample and not beam_sample:
             return None, f"do_sample=True with num_beams={beams} (beam sampling)"
         n_ret = 1 if gc.num_return_sequences is None else int(gc.num_return_sequences)
         early = False if gc.early_stopping is None else gc.early_stopping
@@ -860,6 +875,9 @@ def _library_generate_settings(model, kwargs, beam_search: bool = False, process
             if warp is None:
                 return None, why
             sampling.update(warp)
+        if beam is not None:                                     # beam-search sampling: the draw is beam_search's, not sample's
+            beam.update(do_sample=True, **sampling)
+            sampling = None
     settings = dict(max_new_tokens=int(gc.max_new_tokens), eos_token_id=gc.eos_token_id, pad_token_id=gc.pad_token_id, sampling=sampling, beam=beam)
     if processors:
         settings["processors"] = proc
@@ -902,7 +920,7 @@ def _batch_reason(batch: int):
 
 
 def _make_library_generate(orig_generate, beam_search: bool = False, logits_processors: bool = False, constraints: bool = False,
-                           prompt_lookup: bool = False, guidance: bool = False, sampling_warpers: bool = False):
+                           prompt_lookup: bool = False, guidance: bool = False, sampling_warpers: bool = False, beam_sample: bool = False):
     """`LlavaQwen2ForCausalLM.generate` (`llava_qwen.py:106-143`) on the library: the same argument handling (position_ids / attention_mask
     popped, inputs_embeds refused), the settings resolved as transformers resolves them (`_library_generate_settings`), then the
     multimodal splice and `Qwen2Generator.greedy` / `.sample` on `generator_context(model, ...)`.  It takes the library only for greedy or
@@ -925,7 +943,9 @@ def _make_library_generate(orig_generate, beam_search: bool = False, logits_proc
     32 prompts runs `Qwen2Generator.greedy` / `.sample(guidance_scale=...)`; `negative_prompt_ids` / `negative_prompt_attention_mask` stop
     disqualifying the call only under this flag.  Anything else falls back with the usual one-time warning; with the flag off nothing changes.
     sampling_warpers=True: `min_p`, `typical_p`, `epsilon_cutoff` and `eta_cutoff` (num_beams = 1) run on the library as keywords of
-    `Qwen2Generator.sample` / `.lookup_sample`; `top_h` keeps falling back, and with the flag off all five do."""
+    `Qwen2Generator.sample` / `.lookup_sample`; `top_h` keeps falling back, and with the flag off all five do.
+    beam_sample=True (with beam_search=True): do_sample=True with num_beams > 1 takes `Qwen2Generator.beam_search(do_sample=True)`; with
+    the flag off it keeps falling back as beam sampling."""
     def generate(self, inputs=None, images=None, image_sizes=None, **kwargs):
         if "inputs_embeds" in kwargs:                            # as the reference (llava_qwen.py:120-121)
             raise NotImplementedError("`inputs_embeds` is not supported")
@@ -941,6 +961,8 @@ def _make_library_generate(orig_generate, beam_search: bool = False, logits_proc
             extra.update(guidance=True, batch=None if inputs is None else inputs.shape[0])
         if sampling_warpers:
             extra.update(sampling_warpers=True)
+        if beam_sample:
+            extra.update(beam_sample=True)
         settings, reason = _library_generate_settings(self, {k: v for k, v in kwargs.items() if k not in ("position_ids", "attention_mask")},
                                                       beam_search=beam_search, **extra)
         lookup = settings.get("lookup") if settings is not None else None

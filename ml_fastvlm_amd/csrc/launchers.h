@@ -94,10 +94,13 @@ int fvhd_launch_dec_embed_w4(hipStream_t st, const int64_t* tok, const int64_t* 
 // llm_sample.hip
 size_t fvhd_dec_sample_ws_bytes(void);
 int fvhd_launch_dec_sample(hipStream_t st, const DecSampleArgs* a, void* ws);
+int fvhd_launch_dec_sample_theta(hipStream_t st, const DecSampleArgs* a, void* ws, unsigned* theta_key);
 // llm_beam.hip
 size_t fvhd_dec_beam_topk_ws_bytes(void);
 int fvhd_dec_beam_topk_supported(int G, int K, int C, int V);
 int fvhd_launch_dec_beam_topk(hipStream_t st, const float* logits, const float* scores, int G, int K, int C, int V, float* out_v, int64_t* out_i, void* ws);
+size_t fvhd_dec_beam_sample_ws_bytes(void);      // zeroed once by the owner: it holds the sampler's arrival counters
+int fvhd_launch_dec_beam_sample(hipStream_t st, const DecBeamSampleArgs* a, void* ws);
 size_t fvhd_dec_cache_gather_ws_bytes(int rows, int nkv, int hd, int cap);
 int fvhd_launch_dec_cache_gather(hipStream_t st, const DecCacheGatherArgs* a);
 // llm_spec.hip

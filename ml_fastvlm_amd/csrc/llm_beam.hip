@@ -22,7 +22,8 @@
 #include <algorithm>
 
 #include "fvhd_common.h"
-#include "launchers.h"      // (with llm_decode.h: DecCacheGatherArgs)
+#include "launchers.h"      // (with llm_decode.h: DecCacheGatherArgs, DecBeamSampleArgs)
+#include "sample_rng.h"     // scaled, philox4x32_10, gumbel_of_word
 
 namespace {
 
@@ -185,6 +186,139 @@ __global__ __launch_bounds__(256) void beam_group_kernel(const u64* __restrict__
     }
 }
 
+// ---- beam-search sampling: per prompt the `keep` KEPT candidates with the largest a + g (include/fvhd.h "LLM beam-search sampling") --------------
+// transformers' `_beam_search(do_sample=True)`: a = log_softmax(x) / T + score behind the top-k / top-p warpers with min_tokens_to_keep = m, then
+// torch.multinomial without replacement over the prompt's K * V values = the top `keep` of a + Gumbel noise, returned in that order with the
+// unperturbed a.  The noise is per candidate, so a row's candidates can no longer be pre-selected by their raw logits: the greedy chain runs over
+// PERTURBED keys.  Launches (dec_beam_sample below):
+//   beam_slice, beam_row (C = m)   the kernels above on the raw logits: M, L, and the m largest logits of every row (v_m = the m-th / T)
+//   the sampler's max / level passes in blocks of 16 rows (fvhd_launch_dec_sample_theta; none when no filter is on): theta_s on s = x / T for
+//                                  top_k' = max(top_k, m) and top_p.  The kept set is {s >= min(theta_s, v_m), x > -inf}: theta_s is the top-p
+//                                  threshold when top-p is on (searched among the top-k' survivors, so it is >= theta_k'), else theta_k' <= v_m.
+//   beam_sample_slice              the slice's kept tokens keyed by s + g -> its top C and its kept count
+//   beam_row                       the kernel above over those keys -> the row's top C by s + g
+//   beam_sample_group              the K * C survivors re-keyed by (((x - M) - L) / T + score) + g -> the C best, their unperturbed a, flat indices
+// Within a row a differs from s by one constant, so the row's order under s + g is its order under a + g up to fp32 rounding (the bound is in
+// DESIGN 4.3); with g = 0 and T = 1 the keys are the greedy chain's and so are the results, bit for bit.  g is Philox word v & 3 of the counter
+// (row, n, v >> 2, 1) - one generator call per float4 - or noise_override[row][v].
+struct BeamNoise {
+    const float* over;
+    unsigned n, k0, k1;
+    FVHD_DEV BeamNoise(const DecBeamSampleArgs& a)
+    {
+        over = a.noise_override;
+        n = (unsigned)((a.len ? *a.len : 0) + a.n_add);
+        k0 = (unsigned)a.seed;
+        k1 = (unsigned)(a.seed >> 32);
+    }
+    FVHD_DEV Philox4 words(int row, int v) const { return philox4x32_10((unsigned)row, n, (unsigned)v >> 2, 1u, k0, k1); }
+};
+
+// the kept set's threshold key of a row: min(the sampler's, the key of v_m)
+FVHD_DEV unsigned beam_theta(const DecBeamSampleArgs& a, const u64* __restrict__ rawtop, const unsigned* __restrict__ theta_s, int row)
+{
+    const u64 c = rawtop[(size_t)row * a.min_keep + a.min_keep - 1];
+    const unsigned vm = c ? okey(scaled(cand_value(c), a.temperature)) : 0u;
+    const unsigned ts = theta_s ? theta_s[row] : 0u;
+    return ts < vm ? ts : vm;
+}
+
+FVHD_DEV float beam_acc(float x, float M, float L, float T, float score) { return scaled((x - M) - L, T) + score; }
+
+__global__ __launch_bounds__(256) void beam_sample_slice_kernel(const DecBeamSampleArgs a, int S, const u64* __restrict__ rawtop,
+                                                                const unsigned* __restrict__ theta_s, u64* __restrict__ keys, int* __restrict__ pcnt)
+{
+    __shared__ u64 red[8];
+    __shared__ int cred[4];
+    const int s = blockIdx.x, row = blockIdx.y, t = threadIdx.x, V = a.V;
+    const float* x = a.logits + (size_t)row * V;
+    const unsigned theta = beam_theta(a, rawtop, theta_s, row);
+    const BeamNoise noise(a);
+    const float T = a.temperature;
+    u64 key[16];
+    int cnt = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int e = s * SLICE + (j * 256 + t) * 4;
+        if (e < V) {                                             // V % 16 == 0: a float4 lies inside the row or outside it
+            const f32x4 v = *(const f32x4*)(x + e);
+            f32x4 g;
+            if (noise.over) {
+                g = *(const f32x4*)(noise.over + (size_t)row * V + e);
+            } else {
+                const Philox4 w = noise.words(row, e);
+                g[0] = gumbel_of_word(w.w[0]); g[1] = gumbel_of_word(w.w[1]); g[2] = gumbel_of_word(w.w[2]); g[3] = gumbel_of_word(w.w[3]);
+            }
+            if (a.noise_out) *(f32x4*)(a.noise_out + (size_t)row * V + e) = g;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float sv = scaled(v[i], T);
+                const bool kept = okey(sv) >= theta && v[i] > -INFINITY;      // a -inf logit is never kept
+                key[4 * j + i] = kept ? make_key(sv + g[i], e + i) : 0;
+                cnt += kept;
+            }
+        } else {
+            key[4 * j + 0] = key[4 * j + 1] = key[4 * j + 2] = key[4 * j + 3] = 0;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o; o >>= 1) cnt += __shfl_xor(cnt, o);
+    if ((t & 63) == 0) cred[t >> 6] = cnt;
+    __syncthreads();
+    if (t == 0) pcnt[row * S + s] = (cred[0] + cred[1]) + (cred[2] + cred[3]);
+    block_top<16>(key, a.keep, keys + ((size_t)row * S + s) * a.keep, red);
+}
+
+__global__ __launch_bounds__(256) void beam_sample_group_kernel(const DecBeamSampleArgs a, int S, const u64* __restrict__ rowtop, const float* __restrict__ rowmax,
+                                                                const float* __restrict__ rowlog, const u64* __restrict__ rawtop,
+                                                                const unsigned* __restrict__ theta_s, const int* __restrict__ pcnt)
+{
+    __shared__ u64 red[8];
+    __shared__ u64 top[CMAX];
+    const int g = blockIdx.x, t = threadIdx.x, K = a.K, C = a.keep, V = a.V, n = K * C;      // n <= 1024
+    const BeamNoise noise(a);
+    const float T = a.temperature;
+    u64 key[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int i = j * 256 + t;
+        key[j] = 0;
+        if (i < n) {
+            const int k = i / C, row = g * K + k;
+            const u64 c = rowtop[(size_t)row * C + i % C];
+            if (c) {
+                const int v = (int)cand_index(c);
+                const float acc = beam_acc(a.logits[(size_t)row * V + v], rowmax[row], rowlog[row], T, a.scores[row]);
+                const float gn = noise.over ? noise.over[(size_t)row * V + v] : gumbel_of_word(noise.words(row, v).w[v & 3]);
+                key[j] = make_key(acc + gn, (unsigned)k * (unsigned)V + (unsigned)v);
+            }
+        }
+    }
+    block_top<4>(key, C, top, red);
+    __syncthreads();
+    if (t < C) {
+        const u64 c = top[t];
+        float acc = -INFINITY;
+        if (c) {
+            const int k = (int)(cand_index(c) / (unsigned)V), v = (int)(cand_index(c) % (unsigned)V), row = g * K + k;
+            acc = beam_acc(a.logits[(size_t)row * V + v], rowmax[row], rowlog[row], T, a.scores[row]);       // the unperturbed value
+        }
+        a.out_v[(size_t)g * C + t] = acc;
+        a.out_i[(size_t)g * C + t] = c ? (int64_t)cand_index(c) : 0;
+    }
+    if (a.info && t < K) {
+        const int row = g * K + t;
+        const unsigned theta = beam_theta(a, rawtop, theta_s, row);
+        int kept = 0;
+        for (int s = 0; s < S; ++s) kept += pcnt[row * S + s];
+        float* o = a.info + (size_t)row * 4;
+        o[0] = theta == 0u ? -INFINITY : key_value(theta);
+        o[1] = (float)kept;
+        o[2] = rowmax[row];
+        o[3] = rowlog[row];
+    }
+}
+
 struct TopkWs { u64* keys; float* pmax; float* psum; u64* rowtop; float* rowmax; float* rowlog; };
 
 size_t al256b(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -287,6 +421,42 @@ extern "C" int fvhd_launch_dec_beam_topk(hipStream_t st, const float* logits, co
     hipLaunchKernelGGL(beam_slice_kernel, dim3(S, rows), dim3(256), 0, st, logits, V, S, C, w.keys, w.pmax, w.psum);
     hipLaunchKernelGGL(beam_row_kernel, dim3(rows), dim3(256), 0, st, w.keys, w.pmax, w.psum, S, C, w.rowtop, w.rowmax, w.rowlog);
     hipLaunchKernelGGL(beam_group_kernel, dim3(G), dim3(256), 0, st, w.rowtop, w.rowmax, w.rowlog, scores, K, C, V, out_v, out_i);
+    return (int)hipGetLastError();
+}
+
+// two top-K workspaces (the raw pass, the perturbed pass), the rows' thresholds, the slices' kept counts, the sampler's workspace
+extern "C" size_t fvhd_dec_beam_sample_ws_bytes(void)
+{
+    return 2 * al256b(fvhd_dec_beam_topk_ws_bytes()) + al256b(4 * RMAX) + al256b(4 * RMAX * SMAXB) + al256b(fvhd_dec_sample_ws_bytes());
+}
+
+extern "C" int fvhd_launch_dec_beam_sample(hipStream_t st, const DecBeamSampleArgs* a, void* ws)
+{
+    if (!fvhd_dec_beam_topk_supported(a->G, a->K, a->keep, a->V) || ((uintptr_t)a->logits & 15) || !a->scores || !a->out_v || !a->out_i || !ws ||
+        !(a->temperature > 0.f) || a->top_k < 0 || !(a->top_p >= 0.f && a->top_p <= 1.f) || a->min_keep < 1 || a->min_keep > a->keep ||
+        ((uintptr_t)a->noise_override & 15) || ((uintptr_t)a->noise_out & 15))
+        return (int)hipErrorInvalidValue;
+    char* p = (char*)ws;
+    const TopkWs raw = carve_topk(p), sel = carve_topk(p + al256b(fvhd_dec_beam_topk_ws_bytes()));
+    p += 2 * al256b(fvhd_dec_beam_topk_ws_bytes());
+    unsigned* theta = (unsigned*)p;
+    int* pcnt = (int*)(p + al256b(4 * RMAX));
+    void* sws = p + al256b(4 * RMAX) + al256b(4 * RMAX * SMAXB);
+    const int rows = a->G * a->K, V = a->V, m = a->min_keep, C = a->keep, S = (V + SLICE - 1) / SLICE;
+    hipLaunchKernelGGL(beam_slice_kernel, dim3(S, rows), dim3(256), 0, st, a->logits, V, S, m, raw.keys, raw.pmax, raw.psum);
+    hipLaunchKernelGGL(beam_row_kernel, dim3(rows), dim3(256), 0, st, raw.keys, raw.pmax, raw.psum, S, m, raw.rowtop, raw.rowmax, raw.rowlog);
+    const int top_k = a->top_k > 0 ? std::max(a->top_k, m) : 0;  // TopKLogitsWarper: max(top_k, min_tokens_to_keep)
+    const bool filtered = (top_k > 0 && top_k < V) || a->top_p < 1.f;
+    if (filtered) {
+        DecSampleArgs sa;
+        sa.logits = a->logits; sa.B = rows; sa.V = V; sa.temperature = a->temperature; sa.top_k = top_k; sa.top_p = a->top_p;
+        if (int e = fvhd_launch_dec_sample_theta(st, &sa, sws, theta)) return e;
+    }
+    const unsigned* th = filtered ? theta : nullptr;
+    hipLaunchKernelGGL(beam_sample_slice_kernel, dim3(S, rows), dim3(256), 0, st, *a, S, raw.rowtop, th, sel.keys, pcnt);
+    // (M and L again from the same partials: the same bits)
+    hipLaunchKernelGGL(beam_row_kernel, dim3(rows), dim3(256), 0, st, sel.keys, raw.pmax, raw.psum, S, C, sel.rowtop, sel.rowmax, sel.rowlog);
+    hipLaunchKernelGGL(beam_sample_group_kernel, dim3(a->G), dim3(256), 0, st, *a, S, sel.rowtop, sel.rowmax, sel.rowlog, raw.rowtop, th, pcnt);
     return (int)hipGetLastError();
 }
 

@@ -87,6 +87,7 @@ struct __attribute__((visibility("default"))) fvhd_llm {     // (its inline cons
     // fvhd_llm_beam_reserve: one allocation of its own (fvhd_llm_cache_reserve's footprint is what it was), sized for the reserved cache
     char* beam = nullptr;                  // the reorder's scratch (llm_beam.hip: two layers' K | V, the mask, the positions), then the top-K workspace
     char* beam_topk = nullptr;
+    char* beam_sample = nullptr;           // fvhd_llm_beam_sample_reserve: the workspace of beam-search sampling, an allocation of its own (no cache size in it)
     // fvhd_llm_set_logits_processors (llm_logits.hip): read when fvhd_llm_start / fvhd_llm_decode enqueue, like the sampling settings
     float proc_penalty = 1.f;
     int proc_ngram = 0, proc_min_new = 0, proc_n_eos = 0, proc_n_sup = 0;

@@ -88,6 +88,26 @@ struct DecCacheGatherArgs {
     char* ws = nullptr;            // fvhd_dec_cache_gather_ws_bytes(batch, nkv, hd, cap) bytes
 };
 
+// Arguments of beam-search sampling (llm_beam.hip): per prompt the `keep` kept candidates with the largest a + g (include/fvhd.h "LLM beam-search
+// sampling"), logits fp32 [G * K][V] 16-byte aligned, scores fp32 [G][K].
+struct DecBeamSampleArgs {
+    const float* logits = nullptr;
+    const float* scores = nullptr;
+    int G = 0, K = 0, keep = 0, V = 0;
+    float temperature = 1.f;       // > 0
+    int top_k = 0;                 // 0 = off
+    float top_p = 1.f;             // 1 = off
+    int min_keep = 1;              // transformers' min_tokens_to_keep under beams, in [1, keep]
+    unsigned long long seed = 0;   // Philox key: low word, high word
+    const int* len = nullptr;      // Philox counter (row, n = (len ? *len : 0) + n_add, v >> 2, 1)
+    int n_add = 0;
+    const float* noise_override = nullptr;   // non-NULL: g [G * K][V] instead of Philox
+    float* noise_out = nullptr;    // non-NULL: [G * K][V], every token's g
+    float* info = nullptr;         // non-NULL: [G * K][4]: theta as s (-inf: no filter binds), kept count, row maximum M, L = log sum exp(x - M)
+    float* out_v = nullptr;        // [G][keep]: the unperturbed a of the picks, in descending a + g
+    int64_t* out_i = nullptr;      // [G][keep]: beam * V + token
+};
+
 // Arguments of the logits processors (llm_logits.hip): sparse in-place edits of fp32 logits [B][V] from a per-row token history, one
 // workgroup per row (include/fvhd.h "LLM logits processors").
 struct DecLogitsArgs {

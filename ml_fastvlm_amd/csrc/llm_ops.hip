@@ -459,6 +459,37 @@ int fvhd_op_dec_beam_topk(fvhd_stream_t st, const float* logits, const float* be
     return lret("fvhd_op_dec_beam_topk", fvhd_launch_dec_beam_topk((hipStream_t)st, logits, beam_scores, groups, num_beams, keep, V, cand_scores, cand_index, ws));
 }
 
+// beam-search sampling on its own: a process-wide workspace, allocated and zeroed (the sampler's arrival counters) on first use - eager calls only
+int fvhd_op_dec_beam_sample(fvhd_stream_t st, const float* logits, const float* beam_scores, int groups, int num_beams, int keep, int V, float temperature,
+                            int top_k, float top_p, int min_keep, unsigned long long seed, int n, const float* noise_override, float* noise_out, float* info,
+                            float* cand_scores, int64_t* cand_index)
+{
+    if (!logits || !beam_scores || !cand_scores || !cand_index) return lfail("fvhd_op_dec_beam_sample: NULL pointer");
+    if (!fvhd_dec_beam_topk_supported(groups, num_beams, keep, V) || ((uintptr_t)logits & 15))
+        return lfail("fvhd_op_dec_beam_sample: needs groups >= 1, 2 <= num_beams <= 16, 1 <= keep <= 64, keep <= V, groups * num_beams <= 64, V % 16 == 0, "
+                     "V <= 262144 and logits aligned to 16 bytes");
+    if (const char* e = sampling_error(temperature, top_k, top_p)) return lfail(std::string("fvhd_op_dec_beam_sample: ") + e);
+    if (min_keep < 1 || min_keep > keep)
+        return lfail("fvhd_op_dec_beam_sample: min_keep must be in [1, keep] (got " + std::to_string(min_keep) + " with keep = " + std::to_string(keep) + ")");
+    if (n < 0) return lfail("fvhd_op_dec_beam_sample: n must be >= 0");
+    if (((uintptr_t)noise_override & 15) || ((uintptr_t)noise_out & 15)) return lfail("fvhd_op_dec_beam_sample: noise_override and noise_out must be aligned to 16 bytes");
+    static char* ws[64] = {};
+    int dev = 0;
+    hipError_t he = hipGetDevice(&dev);
+    if (he != hipSuccess) return lhip("hipGetDevice", he);
+    if (dev < 0 || dev >= 64) return lfail("fvhd_op_dec_beam_sample: device index out of range");
+    if (!ws[dev]) {
+        const size_t bytes = fvhd_dec_beam_sample_ws_bytes();
+        if ((he = hipMalloc((void**)&ws[dev], bytes)) != hipSuccess) { ws[dev] = nullptr; return lhip("hipMalloc(beam sampling workspace)", he); }
+        if ((he = hipMemset(ws[dev], 0, bytes)) != hipSuccess) return lhip("hipMemset(beam sampling workspace)", he);
+    }
+    DecBeamSampleArgs a;
+    a.logits = logits; a.scores = beam_scores; a.G = groups; a.K = num_beams; a.keep = keep; a.V = V; a.temperature = temperature; a.top_k = top_k;
+    a.top_p = top_p; a.min_keep = min_keep; a.seed = seed; a.n_add = n; a.noise_override = noise_override; a.noise_out = noise_out; a.info = info;
+    a.out_v = cand_scores; a.out_i = cand_index;
+    return lret("fvhd_op_dec_beam_sample", fvhd_launch_dec_beam_sample((hipStream_t)st, &a, ws[dev]));
+}
+
 int fvhd_op_dec_cache_gather(fvhd_stream_t st, void* k_cache, void* v_cache, uint8_t* key_valid, int64_t* positions, const int64_t* src_rows, int n_layers,
                              int batch, int rows_in, int rows_out, int n_kv_heads, int head_dim, int capacity, const int* length, int* status)
 {

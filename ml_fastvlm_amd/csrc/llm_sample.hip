@@ -35,6 +35,7 @@
 // Everything is deterministic: the same logits, settings, seed and n give the same id, eager or replayed.
 #include "fvhd_common.h"
 #include "launchers.h"      // (with llm_decode.h: the argument structs)
+#include "sample_rng.h"     // scaled, philox_x0
 #include "split_handoff.h"  // arrive_last
 
 namespace {
@@ -118,26 +119,7 @@ FVHD_DEV unsigned okey(float s)
 
 FVHD_DEV float key_value(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
-FVHD_DEV float scaled(float x, float T) { return __fdiv_rn(x, T); }     // TemperatureLogitsWarper: scores / temperature, IEEE
-
 FVHD_DEV unsigned long long fixed_mass(float e) { return (unsigned long long)(e * 0x1p40f); }
-
-// Philox4x32-10 (Salmon et al., SC'11): counter (c0..c3), key (k0, k1) -> the first output word
-FVHD_DEV unsigned philox_x0(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1)
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c0;
-}
 
 // slice s of S over a row of V: [i0, i1)
 FVHD_DEV void slice_of(int V, int S, int s, int& i0, int& i1)
@@ -664,7 +646,17 @@ FVHD_DEV void dec_sample_draw(const DecSampleArgs& a, const SampleWs& w)
 __global__ __launch_bounds__(256) void dec_sample_draw_kernel(const DecSampleArgs a, const SampleWs w) { dec_sample_draw<false>(a, w); }
 __global__ __launch_bounds__(256) void dec_sample_draw_warp_kernel(const DecSampleArgs a, const SampleWs w) { dec_sample_draw<true>(a, w); }
 
+// the search's result of a block of rows, for a caller that does not draw (fvhd_launch_dec_sample_theta)
+__global__ __launch_bounds__(64) void dec_sample_theta_kernel(const SampleWs w, int B, unsigned* __restrict__ theta_key)
+{
+    const int b = threadIdx.x;
+    if (b < B) theta_key[b] = w.rows[b].mode == SM_DRAW ? w.rows[b].theta_key : 0u;
+}
+
 // ---------------------------------------------------------------------------------------------------
+static int slices_of(int V) { return V >= SMAX * 2048 ? SMAX : (V + 2047) / 2048; }
+static int levels_of(const DecSampleArgs& a) { return 4 * ((a.top_k > 0 && a.top_k < a.V) + (a.top_p < 1.f)); }
+
 extern "C" size_t fvhd_dec_sample_ws_bytes(void) { return ws_bytes(); }
 
 extern "C" int fvhd_launch_dec_sample(hipStream_t st, const DecSampleArgs* a, void* ws)
@@ -677,8 +669,8 @@ extern "C" int fvhd_launch_dec_sample(hipStream_t st, const DecSampleArgs* a, vo
         return (int)hipErrorInvalidValue;
     const bool warp = minp_on(*a) || typ_on(*a) || eps_on(*a) || eta_on(*a) || a->info8;    // off: today's launches, today's kernels
     const SampleWs w = carve(ws);
-    const int S = a->V >= SMAX * 2048 ? SMAX : (a->V + 2047) / 2048;
-    const int levels = 4 * ((a->top_k > 0 && a->top_k < a->V) + (a->top_p < 1.f));
+    const int S = slices_of(a->V);
+    const int levels = levels_of(*a);
     // blocks of BMAX rows, one after the other on the stream (they share the workspace): every block reads the same n, the last one
     // advances the length
     for (int row0 = 0; row0 < a->B; row0 += BMAX) {
@@ -697,6 +689,29 @@ extern "C" int fvhd_launch_dec_sample(hipStream_t st, const DecSampleArgs* a, vo
         if (eta_on(*a)) hipLaunchKernelGGL(dec_sample_stats_kernel, grid, block, 0, st, blk, w, (int)ST_ETA);
         if (warp) hipLaunchKernelGGL(dec_sample_draw_warp_kernel, grid, block, 0, st, blk, w);
         else hipLaunchKernelGGL(dec_sample_draw_kernel, grid, block, 0, st, blk, w);
+    }
+    return (int)hipGetLastError();
+}
+
+// The threshold search alone (beam-search sampling, llm_beam.hip): the max and level passes of the launch above on temperature / top_k / top_p,
+// stopping in front of the draw - theta_key[row] = the order-preserving key of the row's threshold on s (0: no filter binds).  Nothing else
+// of the arguments is read or written: no ids, no positions, no length.
+extern "C" int fvhd_launch_dec_sample_theta(hipStream_t st, const DecSampleArgs* a, void* ws, unsigned* theta_key)
+{
+    if (!a->logits || !ws || !theta_key || a->B < 1 || a->B > 4 * BMAX || a->V < 1 || !(a->temperature > 0.f) || a->top_k < 0 ||
+        !(a->top_p >= 0.f && a->top_p <= 1.f))
+        return (int)hipErrorInvalidValue;
+    const SampleWs w = carve(ws);
+    const int S = slices_of(a->V);
+    const int levels = levels_of(*a);
+    for (int row0 = 0; row0 < a->B; row0 += BMAX) {
+        DecSampleArgs blk = *a;
+        blk.row0 = row0;
+        blk.B = a->B - row0 < BMAX ? a->B - row0 : BMAX;
+        const dim3 grid((unsigned)S, (unsigned)blk.B), block(256);
+        hipLaunchKernelGGL(dec_sample_max_kernel, grid, block, 0, st, blk, w);
+        for (int l = 0; l < levels; ++l) hipLaunchKernelGGL(dec_sample_level_kernel, grid, block, 0, st, blk, w);
+        hipLaunchKernelGGL(dec_sample_theta_kernel, dim3(1), dim3(64), 0, st, w, blk.B, theta_key + row0);
     }
     return (int)hipGetLastError();
 }

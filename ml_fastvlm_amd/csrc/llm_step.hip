@@ -628,6 +628,44 @@ int fvhd_llm_beam_topk(fvhd_llm* c, const float* logits, const float* beam_score
     return 0;
 }
 
+// ---- beam-search sampling (include/fvhd.h "LLM beam-search sampling"; kernels: llm_beam.hip on llm_sample.hip's threshold search) ----
+int fvhd_llm_beam_sample_reserve(fvhd_llm* c)
+{
+    if (!c) return lfail("fvhd_llm_beam_sample_reserve: NULL context");
+    LLM_ON_DEVICE(c);
+    hipError_t he = hipDeviceSynchronize();                      // refused while a stream is being captured (like fvhd_llm_beam_reserve)
+    if (he != hipSuccess) return lhip("fvhd_llm_beam_sample_reserve: hipDeviceSynchronize", he);
+    if (c->beam_sample) return 0;
+    const size_t bytes = fvhd_dec_beam_sample_ws_bytes();
+    if ((he = hipMalloc((void**)&c->beam_sample, bytes)) != hipSuccess) { c->beam_sample = nullptr; return lhip("hipMalloc(beam sampling workspace)", he); }
+    if ((he = hipMemset(c->beam_sample, 0, bytes)) != hipSuccess) return lhip("hipMemset(beam sampling workspace)", he);      // counters start at zero
+    return 0;
+}
+
+int fvhd_llm_beam_sample_topk(fvhd_llm* c, const float* logits, const float* beam_scores, int groups, int num_beams, int keep, float temperature,
+                              int top_k, float top_p, int min_keep, unsigned long long seed, float* cand_scores, int64_t* cand_index, fvhd_stream_t stream)
+{
+    if (!c || !logits || !beam_scores || !cand_scores || !cand_index) return lfail("fvhd_llm_beam_sample_topk: NULL argument");
+    if (int e = guidance_refusal(c, "fvhd_llm_beam_sample_topk", "beam search does not carry the pairing of conditional and unconditional rows")) return e;
+    if (!c->dc) return lfail("fvhd_llm_beam_sample_topk: no KV cache - call fvhd_llm_cache_reserve first (the draw's counter is the cache length)");
+    if (!c->beam_sample) return lfail("fvhd_llm_beam_sample_topk: no workspace - call fvhd_llm_beam_sample_reserve first");
+    if (constraint_on(c))
+        return lfail("fvhd_llm_beam_sample_topk: a constraint is on (fvhd_llm_set_constraint) - beam search does not carry the rows' automaton states; "
+                     "switch it off for beam search");
+    if (!fvhd_dec_beam_topk_supported(groups, num_beams, keep, c->V) || ((uintptr_t)logits & 15))
+        return lfail("fvhd_llm_beam_sample_topk: needs groups >= 1, 2 <= num_beams <= 16, 1 <= keep <= 64, keep <= vocab, groups * num_beams <= 64, "
+                     "vocab % 16 == 0, vocab <= 262144 and logits aligned to 16 bytes");
+    if (const char* e = sampling_error(temperature, top_k, top_p)) return lfail(std::string("fvhd_llm_beam_sample_topk: ") + e);
+    if (min_keep < 1 || min_keep > keep)
+        return lfail("fvhd_llm_beam_sample_topk: min_keep must be in [1, keep] (got " + std::to_string(min_keep) + " with keep = " + std::to_string(keep) + ")");
+    LLM_ON_DEVICE(c);
+    DecBeamSampleArgs a;
+    a.logits = logits; a.scores = beam_scores; a.G = groups; a.K = num_beams; a.keep = keep; a.V = c->V; a.temperature = temperature; a.top_k = top_k;
+    a.top_p = top_p; a.min_keep = min_keep; a.seed = seed; a.len = c->len; a.out_v = cand_scores; a.out_i = cand_index;
+    LCHECK(fvhd_launch_dec_beam_sample((hipStream_t)stream, &a, c->beam_sample), "beam sampling");
+    return 0;
+}
+
 // ---- speculative verification (include/fvhd.h "LLM speculative verification"; kernels: llm_spec.hip) ----
 int fvhd_llm_spec_reserve(fvhd_llm* c, int max_rows, int lookup_capacity)
 {

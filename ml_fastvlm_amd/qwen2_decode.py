@@ -75,6 +75,15 @@ def philox_uniform(seed: int, row: int, n: int) -> float:
     return (philox4x32_10((row, n, 0, 0), (seed, seed >> 32))[0] >> 8) * 2.0 ** -24
 
 
+def philox_gumbel_uniform(seed: int, row: int, n: int, v: int) -> float:
+    """beam-search sampling's u for token v of batch row `row` when the cache holds n tokens: (2 (w >> 9) + 1) * 2^-24 with w = word v & 3
+    of Philox4x32-10 on the counter (row, n, v >> 2, 1) and key (seed low word, seed high word) - exact in fp32, inside (0, 1); the
+    candidate's noise is g = -log(-log u)"""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    w = philox4x32_10((row, n, int(v) >> 2, 1), (seed, seed >> 32))[int(v) & 3]
+    return (2 * (w >> 9) + 1) * 2.0 ** -24
+
+
 class GenerationLogprobs(NamedTuple):
     """what `greedy` / `sample` return beside the tokens [B, n_tok] under `logprobs=n`: log-softmax values of the logits each token was
     chosen from (the processed scores when logits processors are on; before temperature / top-k / top-p).  Behind a row's end (the token
@@ -212,6 +221,7 @@ class Qwen2Generator:
     _guided_rows = 0                                             # under guidance the G conditional rows of the last choice (0: the started batch)
     _do_sample = _verify_sampling = False                        # what set_sampling / set_verify_sampling last set
     _beam_reserved = False                                       # beam_reserve ran
+    _beam_sample_reserved = False                                # beam_sample_reserve ran
     _spec_rows = 0                                               # the largest row count this generator asked of spec_reserve
     _spec_logits = _spec_ids = _spec_emitted = None              # verify()'s output buffers, made on first use
     _last_chunk = _last_mask = _last_call = None                 # the rows, mask and call token of the last start() / extend() (`score_last`)
@@ -473,6 +483,35 @@ class Qwen2Generator:
         with torch.cuda.device(self.device):
             _lib.check(_lib.beam_lib().fvhd_llm_beam_topk(self.pre._h, _lib.ptr(logits), _lib.ptr(beam_scores), G, K, int(keep), _lib.ptr(out_scores),
                                                           _lib.ptr(out_index), _lib.stream_ptr(self.device)), "fvhd_llm_beam_topk")
+
+    def beam_sample_reserve(self) -> None:
+        """the workspace of `beam_sample_topk` (`fvhd_llm_beam_sample_reserve`; once per generator, synchronises)"""
+        if not self._beam_sample_reserved:
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.beam_sample_lib().fvhd_llm_beam_sample_reserve(self.pre._h), "fvhd_llm_beam_sample_reserve")
+            self._beam_sample_reserved = True
+
+    @torch.no_grad()
+    def beam_sample_topk(self, logits: torch.Tensor, beam_scores: torch.Tensor, keep: int, out_scores: torch.Tensor, out_index: torch.Tensor,
+                         temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, min_keep: int = 2, seed: int = 0) -> None:
+        """per prompt `keep` draws without replacement from softmax over its K * vocab values a = log_softmax(logits) / temperature +
+        beam_scores, behind top-k / top-p with min_tokens_to_keep = min_keep -> out_scores fp32 [G, keep] = the UNPERTURBED a of the
+        picks in draw order, out_index int64 [G, keep] = beam * vocab + token (`fvhd_llm_beam_sample_topk`: the top `keep` of a + Gumbel
+        noise from Philox, `philox_gumbel_uniform`).  The draw's counter n is the cache length on the device when the launch runs.
+        Capture-safe after `beam_sample_reserve`."""
+        _sampling_refusal("beam_sample_topk", temperature, top_k, top_p)
+        if isinstance(min_keep, bool) or not isinstance(min_keep, int) or not 1 <= min_keep <= keep:
+            raise ValueError(f"beam_sample_topk: min_keep must be an int in [1, keep = {keep}], got {min_keep!r}")
+        G, K = beam_scores.shape
+        for t, dt, shape in ((logits, torch.float32, (G * K, self.pre.vocab)), (beam_scores, torch.float32, (G, K)),
+                             (out_scores, torch.float32, (G, keep)), (out_index, torch.long, (G, keep))):
+            if t.dtype != dt or t.device != self.device or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"beam_sample_topk: expected a contiguous {dt} tensor {shape} on {self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        lib = _lib.beam_sample_lib()                             # a library built before the feature: named here, before any device call
+        with torch.cuda.device(self.device):
+            _lib.check(lib.fvhd_llm_beam_sample_topk(
+                self.pre._h, _lib.ptr(logits), _lib.ptr(beam_scores), G, K, int(keep), float(temperature), int(top_k), float(top_p), int(min_keep),
+                int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(out_scores), _lib.ptr(out_index), _lib.stream_ptr(self.device)), "fvhd_llm_beam_sample_topk")
 
     # ---- speculative verification -------------------------------------------------------------------------------------------------------
     def _verify_refusal(self, who: str, rows: int) -> None:
@@ -1037,15 +1076,22 @@ class Qwen2Generator:
     def beam_search(self, inputs_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None,
                     num_beams: int = 4, max_new_tokens: int = 256, length_penalty: float = 1.0, early_stopping: Union[bool, str] = False,
                     num_return_sequences: int = 1, eos_token_id: Union[None, int, Sequence[int]] = None, pad_token_id: Optional[int] = None,
-                    graph: bool = True, poll_every: int = 16, return_scores: bool = False):
-        """transformers' beam search (`GenerationMixin._beam_search`, do_sample=False) on the library's steps -> new tokens
+                    graph: bool = True, poll_every: int = 16, return_scores: bool = False, do_sample: bool = False, temperature: float = 1.0,
+                    top_k: int = 50, top_p: float = 1.0, seed: Optional[int] = None):
+        """transformers' beam search (`GenerationMixin._beam_search`) on the library's steps -> new tokens
         [G * num_return_sequences, n], with return_scores also the `sequences_scores` [G * num_return_sequences]: what
         generate(inputs_embeds=..., num_beams=K) returns - per prompt its best finished hypotheses in descending score order, finished rows
         padded with `pad_token_id`, cropped to the longest one.
         The prompt is prefilled ONCE per prompt (`start` on G rows); one cache reorder with src = r // K makes the G * K rows.  Then one
         step = reorder by the previous step's parent rows -> `step(fed_ids)` under greedy settings, for its logits -> `beam_topk` ->
         `BeamSearchState.update`, which writes the next fed_ids and parent rows; graph=True captures that step once (one linear stream) and
-        replays it, and "search finished" is polled every `poll_every` steps - a finished search ignores the steps that ran past it."""
+        replays it, and "search finished" is polled every `poll_every` steps - a finished search ignores the steps that ran past it.
+        do_sample=True: transformers' beam search with multinomial sampling (generate(do_sample=True, num_beams=K)) - the same step with
+        `beam_sample_topk` in place of `beam_topk`: the 2 K (or (1 + n_eos) K) continuations are DRAWN without replacement from the
+        softmax of log_softmax(logits) / temperature + beam scores behind top-k / top-p, with min_tokens_to_keep = n_eos + 1 (2 without
+        an EOS id) as transformers sets it under beams; top_k = 50 is transformers' default.  seed None: as in `sample`.  The same seed
+        gives the same tokens and scores, eager or graph; the draws are not torch.multinomial's.  With do_sample=False the four settings
+        are not read and the call enqueues what it did."""
         from .beam import BeamSearchState
         if num_beams < 2:
             raise ValueError(f"beam_search needs num_beams >= 2 (got {num_beams}): one beam is `greedy`")
@@ -1056,6 +1102,10 @@ class Qwen2Generator:
         self._guidance_refusal("beam_search", "beam search does not take guidance")
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be >= 1")
+        if do_sample:
+            _sampling_refusal("beam_search", temperature, top_k, top_p)
+            if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int)):
+                raise ValueError(f"beam_search: seed must be None or an int, got {seed!r}")
         G, T = inputs_embeds.shape[:2]
         K = int(num_beams)
         rows = G * K
@@ -1070,6 +1120,15 @@ class Qwen2Generator:
                                 pad_token_id, device=dev)
         self.beam_reserve()
         self._set_greedy()
+        topk = self.beam_topk
+        if do_sample:
+            self.beam_sample_reserve()
+            # transformers' warpers under beams: min_tokens_to_keep = n_eos + 1, 2 without an EOS id (`_get_logits_processor`)
+            drawn = dict(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), min_keep=max(2, 1 + len(eos_list(eos_token_id))),
+                         seed=_random_seed() if seed is None else int(seed))
+
+            def topk(*a):
+                self.beam_sample_topk(*a, **drawn)
         cand_scores = torch.zeros((G, state.keep), device=dev, dtype=torch.float32)
         cand_index = torch.zeros((G, state.keep), device=dev, dtype=torch.long)
         lg, _ = self.start(inputs_embeds, attention_mask, position_ids, logits=True)
@@ -1077,13 +1136,13 @@ class Qwen2Generator:
         logits = self._logits[:rows]
         logits.copy_(lg.repeat_interleave(K, dim=0))
         self.cache_gather(torch.arange(rows, device=dev, dtype=torch.long) // K, G)
-        self.beam_topk(logits, state.running_beam_scores, state.keep, cand_scores, cand_index)
+        topk(logits, state.running_beam_scores, state.keep, cand_scores, cand_index)
         state.update(cand_scores, cand_index)
 
         def one_step():
             self.cache_gather(state.parent, rows)
             step_logits, _ = self.step(state.fed_ids, logits=True)
-            self.beam_topk(step_logits, state.running_beam_scores, state.keep, cand_scores, cand_index)
+            topk(step_logits, state.running_beam_scores, state.keep, cand_scores, cand_index)
             state.update(cand_scores, cand_index)
 
         steps = max_new_tokens - 1

@@ -792,7 +792,10 @@ def _graph_of(fn, dev):
 
 
 @torch.no_grad()
-def measure_beam(llm, pre, groups: int, K: int, prompt: int, new: int, dev, repeats: int = 1, stock: bool = True, weights: str = "bf16") -> dict:
+def measure_beam(llm, pre, groups: int, K: int, prompt: int, new: int, dev, repeats: int = 1, stock: bool = True, weights: str = "bf16",
+                 do_sample: bool = False) -> dict:
+    """do_sample: beam-search SAMPLING at predict.py's settings (temperature 0.2, top_k 50, top_p off): `beam_sample_topk` in place of
+    `beam_topk` in the step, and the stock loop run with do_sample=True"""
     from ml_fastvlm_amd.beam import BeamSearchState
     from ml_fastvlm_amd.qwen2_decode import Qwen2Generator
     cfg = llm.config
@@ -802,10 +805,17 @@ def measure_beam(llm, pre, groups: int, K: int, prompt: int, new: int, dev, repe
     emb = (0.5 * torch.randn(groups, prompt, hidden, device=dev, generator=g)).to(torch.bfloat16)
     mask = torch.ones(groups, prompt, device=dev, dtype=torch.long)
     res = {"hidden": hidden, "layers": cfg.num_hidden_layers, "prompts": groups, "num_beams": K, "rows": rows, "vocab": V, "prompt": prompt,
-           "new_tokens": new, "weights": weights}
+           "new_tokens": new, "weights": weights, "do_sample": do_sample}
     gen.beam_reserve()
     gen._set_greedy()
     keep = 2 * K
+    topk = gen.beam_topk
+    if do_sample:
+        res.update(temperature=0.2, top_k=50, top_p=1.0, min_keep=2)
+        gen.beam_sample_reserve()
+
+        def topk(*a):
+            gen.beam_sample_topk(*a, temperature=0.2, top_k=50, top_p=1.0, min_keep=2, seed=1)
     cand_s = torch.zeros((groups, keep), device=dev)
     cand_i = torch.zeros((groups, keep), device=dev, dtype=torch.long)
     expand = torch.arange(rows, device=dev) // K
@@ -823,7 +833,7 @@ def measure_beam(llm, pre, groups: int, K: int, prompt: int, new: int, dev, repe
         lg, _ = gen.start(emb, mask, logits=True)
         gen._logits[:rows].copy_(lg.repeat_interleave(K, dim=0))
         gen.cache_gather(expand, groups)
-        gen.beam_topk(gen._logits[:rows], st.running_beam_scores, keep, cand_s, cand_i)
+        topk(gen._logits[:rows], st.running_beam_scores, keep, cand_s, cand_i)
         st.update(cand_s, cand_i)
         return st
 
@@ -832,7 +842,7 @@ def measure_beam(llm, pre, groups: int, K: int, prompt: int, new: int, dev, repe
     def one_step():
         gen.cache_gather(st.parent, rows)
         lg, _ = gen.step(st.fed_ids, logits=True)
-        gen.beam_topk(lg, st.running_beam_scores, keep, cand_s, cand_i)
+        topk(lg, st.running_beam_scores, keep, cand_s, cand_i)
         st.update(cand_s, cand_i)
 
     full = _graph_of(one_step, dev)
@@ -853,7 +863,7 @@ def measure_beam(llm, pre, groups: int, K: int, prompt: int, new: int, dev, repe
     worst = torch.roll(torch.arange(rows, device=dev), 1)
     src = parent.clone()
     parts = {"plain_step_with_logits": lambda: gen.step(st.fed_ids, logits=True), "plain_step": lambda: gen.step(st.fed_ids, logits=False),
-             "topk": lambda: gen.beam_topk(gen._logits[:rows], st.running_beam_scores, keep, cand_s, cand_i),
+             "topk": lambda: topk(gen._logits[:rows], st.running_beam_scores, keep, cand_s, cand_i),
              "bookkeeping": lambda: st.update(cand_s, cand_i), "gather": lambda: gen.cache_gather(src, rows)}
     for name, fn in parts.items():
         graph = _graph_of(fn, dev)
@@ -870,6 +880,8 @@ def measure_beam(llm, pre, groups: int, K: int, prompt: int, new: int, dev, repe
     res["kv_bytes_moved_twice_if_every_row_moves"] = int(2 * 2 * cfg.num_hidden_layers * rows * nkv * (prompt + new / 2) * hd * 2)
     if stock:
         ref_kw = dict(inputs_embeds=emb, attention_mask=mask, num_beams=K, max_new_tokens=new, do_sample=False, eos_token_id=None, pad_token_id=0)
+        if do_sample:
+            ref_kw.update(do_sample=True, temperature=0.2, top_k=50, top_p=1.0)
         llm.generation_config.eos_token_id = None           # (random weights: no early end)
         llm.generate(**dict(ref_kw, max_new_tokens=4))      # lazy initialisation stays out of the timing
         torch.cuda.synchronize(dev)
@@ -914,6 +926,7 @@ def main():
                     help="storage of the packed LLM matrices (fp8_e4m3 needs a library of version 504, mxfp4 one built with the 4-bit entry points)")
     ap.add_argument("--trace-steps", type=int, default=0, help="run only the prefill and this many eager steps (for a kernel trace)")
     ap.add_argument("--processors", action="store_true", help="the step with all four logits processors on against off (needs a library of version 506)")
+    ap.add_argument("--beam-sample", action="store_true", help="with --num-beams: beam-search sampling (do_sample=True, temperature 0.2, top_k 50) instead of the greedy search")
     ap.add_argument("--num-beams", type=int, default=0, help="time beam search with this many beams per prompt (--batch = prompts; needs a library of version 505)")
     ap.add_argument("--lookup", action="store_true", help="the verify step of prompt-lookup decoding at one sequence (needs a library of version 507)")
     ap.add_argument("--rows", type=int, nargs="+", default=[4, 8, 16], help="--lookup: rows per verify step")
@@ -1039,7 +1052,7 @@ def main():
             llm = build_llm(h, dev)
             pre = Qwen2Prefill.from_hf(llm, weights=a.weights)
             for b in a.batch:
-                rows.append(measure_beam(llm, pre, b, a.num_beams, a.prompt, a.new, dev, repeats=a.repeats, stock=not a.no_stock, weights=a.weights))
+                rows.append(measure_beam(llm, pre, b, a.num_beams, a.prompt, a.new, dev, repeats=a.repeats, stock=not a.no_stock, weights=a.weights, do_sample=a.beam_sample))
                 torch.cuda.empty_cache()
             del pre, llm
             torch.cuda.empty_cache()
