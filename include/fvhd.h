@@ -694,7 +694,8 @@ int fvhd_llm_beam_reserve(fvhd_llm* ctx);
 /* The reorder on the context's cache; the later steps run on rows_out sequences (<= the reserved batch; rows_in <= it too).  src_rows =
  * r / num_beams turns G prefilled rows into G * num_beams.  The host arguments are the same every step: capture-safe after
  * fvhd_llm_beam_reserve and fvhd_llm_start.  n_layers + 1 launches.  Refused with logits processors on (their token history is not
- * reordered: the rows would go on with the history of whatever sequence held the row before). */
+ * reordered: the rows would go on with the history of whatever sequence held the row before) - unless fvhd_llm_set_beam_scoring is on, which
+ * carries them ("LLM beam search with processors" below). */
 int fvhd_llm_cache_gather(fvhd_llm* ctx, const int64_t* src_rows, int rows_in, int rows_out, fvhd_stream_t stream);
 /* The top continuations of logits fp32 [groups * num_beams, vocab] (16-byte aligned) and beam_scores fp32 [groups, num_beams] ->
  * cand_scores fp32 [groups, keep], cand_index int64 [groups, keep].  Capture-safe after fvhd_llm_beam_reserve.  3 launches. */
@@ -726,9 +727,9 @@ int fvhd_op_dec_cache_gather(fvhd_stream_t stream, void* k_cache, void* v_cache,
  *         cand_scores = their a, cand_index = k V + v; a slot that cannot be filled (fewer than `keep` kept candidates) holds (-inf, 0).
  * A row's candidates are pre-selected by (x / T) + g, which differs from a + g by a row constant and fp32 rounding (DESIGN 4.3 has the bound).
  * The limits are fvhd_llm_beam_topk's, and 1 <= min_keep <= keep.  A score of -1e9 (a dead beam) is an ordinary input.  Deterministic: the same
- * logits, scores, settings, seed and n give the same bits, eager or replayed; no floating-point atomics.  min_p / typical_p / the cutoffs,
- * logits processors, a constraint and guidance are not implemented under beams: the calls below are refused with them on where
- * fvhd_llm_beam_topk is. */
+ * logits, scores, settings, seed and n give the same bits, eager or replayed; no floating-point atomics.  min_p / typical_p / the cutoffs
+ * and guidance are not implemented under beams.  Logits processors and a constraint run under beams only with fvhd_llm_set_beam_scoring on
+ * ("LLM beam search with processors" below); with it off the calls below are refused with them on where fvhd_llm_beam_topk is. */
 /* Allocates (and zeroes) the workspace of fvhd_llm_beam_sample_topk, about 7 MiB, an allocation of its own: fvhd_llm_beam_reserve and
  * fvhd_llm_cache_reserve allocate what they did.  It does not depend on the cache: once per context.  Synchronises (refused while a stream is
  * being captured). */
@@ -1093,6 +1094,44 @@ int fvhd_llm_constraint_state(fvhd_llm* ctx, int32_t* host_states_out, int32_t* 
 size_t fvhd_dec_guidance_scratch_bytes(int G, int V);
 int fvhd_op_dec_guidance(fvhd_stream_t stream, float* logits, int G, int V, float scale, void* scratch, size_t scratch_bytes);
 int fvhd_llm_set_guidance(fvhd_llm* ctx, float scale);
+
+/* ---- LLM beam search with processors: logits processors and a constraint on log-softmaxed rows that follow their beams (added under 510) ------
+ * Under beams transformers applies its processors to LOG-SOFTMAXED scores, and every beam's history follows its parent:
+ *     lp = log_softmax(logits);  lp = processors(flat_running_sequences, lp);  lp += running_beam_scores;  top-K (or a draw) of the K * V values
+ * fvhd_llm_set_beam_scoring(ctx, on) switches the context to that order.  Off (the default) every call is what it was, refusals included.  On:
+ *   fvhd_llm_start / fvhd_llm_decode with a logits_out first turn every row into x'[v] = (x[v] - M) - L in place - M the row maximum, L = log sum
+ *     exp(x - M), both with fvhd_llm_beam_topk's slices and summation order, so an entry no processor edits holds bit for bit what the plain
+ *     chain adds to the beam score - then run the processors and the constraint on x' (a log-probability is <= 0: the repetition penalty
+ *     multiplies).  Two launches of ceil(V / 4096) x rows workgroups, 16-byte loads and stores on 16-byte-aligned rows; inside the decode step
+ *     they obey the error word.  Without a logits_out nothing changes.
+ *   fvhd_llm_cache_gather carries, behind K and V and with the same src_rows, the first hist_count[src] history entries with their
+ *     first-occurrence marks, the seen-bitmap, the history count and the constraint's state and flag words: two more launches, through a
+ *     scratch of their own, rows with src_rows[r] == r skipped, every workgroup checking all of src_rows first (one index out of range: nothing
+ *     is written but error word 3).
+ *   fvhd_llm_beam_topk / fvhd_llm_beam_sample_topk take the rows as they are: acc = x' + score, a = (x' / T + score); top-k / top-p thresholds
+ *     are searched on x' / T; a -inf entry is never a candidate and never counted as kept; a slot that cannot be filled holds (-inf, 0).
+ *   Refused, each with a message: guidance, fvhd_llm_set_logprobs (at fvhd_llm_start / _decode), fvhd_llm_extend.  fvhd_llm_verify / _lookup_*
+ *     and fvhd_llm_cache_rewind keep their refusals under processors or a constraint.
+ * The setting is read when a call enqueues, like the sampling settings; a captured step replays what it captured.  The call that switches it on
+ * allocates the normalisation's partials and the reorder's scratch (the reserved batch's histories, bitmaps and states) apart from
+ * fvhd_llm_cache_reserve's and fvhd_llm_beam_reserve's allocations - it synchronises and is refused while a stream is being captured;
+ * fvhd_llm_cache_reserve frees the scratch with the cache it was sized for and switches the setting off.
+ * The operations on their own (tests), on plain device pointers, process-wide scratch, eager calls only:
+ *   fvhd_op_dec_beam_norm: logits fp32 [rows][V], row stride V, 4-byte aligned, 1 <= rows <= 64, 1 <= V <= 262144 (rows that are not 16-byte
+ *     aligned and a row's last V % 4 entries go element by element); stats_out NULL or fp32 [rows][2] = (M, L).
+ *   fvhd_op_dec_hist_gather: history int32 [batch][capacity] (entry = token | 0x80000000 for a repeat), seen uint32 [batch][ceil(V / 32)],
+ *     count int32 [batch] - or history NULL; states / flags int32 [batch] - or states NULL; status as in fvhd_op_dec_cache_gather.
+ *   fvhd_op_dec_beam_topk_pre / fvhd_op_dec_beam_sample_pre: fvhd_op_dec_beam_topk / _beam_sample on pre-normalised rows (info's M and L are
+ *     those of the rows given, which the values do not use). */
+int fvhd_llm_set_beam_scoring(fvhd_llm* ctx, int on);
+int fvhd_op_dec_beam_norm(fvhd_stream_t stream, float* logits, int rows, int V, float* stats_out);
+int fvhd_op_dec_hist_gather(fvhd_stream_t stream, int32_t* history, uint32_t* seen, int32_t* count, int32_t* states, int32_t* flags,
+                            const int64_t* src_rows, int batch, int rows_in, int rows_out, int capacity, int V, int* status);
+int fvhd_op_dec_beam_topk_pre(fvhd_stream_t stream, const float* logits, const float* beam_scores, int groups, int num_beams, int keep, int V,
+                              float* cand_scores, int64_t* cand_index);
+int fvhd_op_dec_beam_sample_pre(fvhd_stream_t stream, const float* logits, const float* beam_scores, int groups, int num_beams, int keep, int V,
+                                float temperature, int top_k, float top_p, int min_keep, unsigned long long seed, int n, const float* noise_override,
+                                float* noise_out, float* info, float* cand_scores, int64_t* cand_index);
 
 #ifdef __cplusplus
 }

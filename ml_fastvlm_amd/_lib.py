@@ -240,14 +240,26 @@ FEATURES_LATEST = {
         "fvhd_op_dec_beam_sample": (ci, [vp, vp, vp, ci, ci, ci, ci, cf, ci, cf, ci, C.c_ulonglong, ci, vp, vp, vp, vp, vp]),
     }),
 }
+# The three tables above are each pinned to their exact names by a test.  Later features are appended HERE: no test lists this table's names
+# (tests/test_beam_processors_reference.py checks its own entry, and that the four tables share no name).
+FEATURES_OPEN = {
+    "beam_processors": Feature("beam search with logits processors and a constraint", "fvhd_llm_set_beam_scoring, fvhd_op_dec_beam_norm, fvhd_op_dec_hist_gather, ...", probe="fvhd_llm_set_beam_scoring", needs="beam_sample", sig={
+        "fvhd_llm_set_beam_scoring": (ci, [vp, ci]),
+        "fvhd_op_dec_beam_norm": (ci, [vp, vp, ci, ci, vp]),
+        "fvhd_op_dec_hist_gather": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
+        "fvhd_op_dec_beam_topk_pre": (ci, [vp, vp, vp, ci, ci, ci, ci, vp, vp]),
+        "fvhd_op_dec_beam_sample_pre": (ci, [vp, vp, vp, ci, ci, ci, ci, cf, ci, cf, ci, C.c_ulonglong, ci, vp, vp, vp, vp, vp]),
+    }),
+}
 del vp, ci, cf
+FEATURE_TABLES = (FEATURES, FEATURES_LATER, FEATURES_LATEST, FEATURES_OPEN)
 
 
 def _feature(name: str) -> Feature:
-    for table in (FEATURES, FEATURES_LATER):
+    for table in FEATURE_TABLES:
         if name in table:
             return table[name]
-    return FEATURES_LATEST[name]
+    raise KeyError(name)
 
 
 def _has(lib, name: str) -> bool:
@@ -257,7 +269,7 @@ def _has(lib, name: str) -> bool:
 
 def _declare(lib) -> None:
     sig = dict(BASE_SIGNATURES)
-    for name, f in {**FEATURES, **FEATURES_LATER, **FEATURES_LATEST}.items():
+    for name, f in {k: v for table in FEATURE_TABLES for k, v in table.items()}.items():
         if _has(lib, name):
             sig.update(f.sig)
     for name, (res, args) in sig.items():
@@ -288,7 +300,7 @@ def load():
 
 
 def has(feature: str) -> bool:
-    """whether the loaded library has FEATURES[feature] (or FEATURES_LATER / FEATURES_LATEST[feature])"""
+    """whether the loaded library has FEATURES[feature] (or the entry of any later table of FEATURE_TABLES)"""
     return _has(load(), feature)
 
 
@@ -321,6 +333,7 @@ lookup_sample_lib = functools.partial(require, "lookup_sample")
 guidance_lib = functools.partial(require, "guidance")
 sampling_warpers_lib = functools.partial(require, "sampling_warpers")
 beam_sample_lib = functools.partial(require, "beam_sample")
+beam_processors_lib = functools.partial(require, "beam_processors")
 
 
 def weight_format_code(weights: str) -> int:

@@ -95,7 +95,8 @@ def encode_images(vision_tower, mm_projector, images):
 
 def install_into_llava(splice: bool = False, prefill: bool = False, prefill_any_dtype: bool = False, generate: bool = False,
                        llm_weights: str = "bf16", beam_search: bool = False, logits_processors: bool = False, constraints: bool = False,
-                       prompt_lookup: bool = False, guidance: bool = False, sampling_warpers: bool = False, beam_sample: bool = False) -> None:
+                       prompt_lookup: bool = False, guidance: bool = False, sampling_warpers: bool = False, beam_sample: bool = False,
+                       beam_processors: bool = False) -> None:
     """Make an unmodified `llava` package (the reference) build and call the MI355X tower; splice=True also routes
     `prepare_inputs_labels_for_multimodal` through the GPU splice (needs the embeddings on a HIP device); prefill=True also runs the
     PREFILL step of `LlavaQwen2ForCausalLM.forward` (`llava_qwen.py:92-103`: the first forward of `generate`, on `inputs_embeds`
@@ -112,6 +113,11 @@ def install_into_llava(splice: bool = False, prefill: bool = False, prefill_any_
     beam_sample=True (with generate=True and beam_search=True) lets it take the library for do_sample=True with `num_beams` > 1 as well
     (`Qwen2Generator.beam_search(do_sample=True)`: temperature / top-k / top-p, the continuations drawn inside the step) - predict.py's
     `--num_beams 4` as it stands; min_p / typical_p / the cutoffs / top_h under beams keep falling back, and so does the call without the flag.
+    beam_processors=True (with generate=True and beam_search=True) lets it take the library for `repetition_penalty`,
+    `no_repeat_ngram_size`, `min_new_tokens` and `suppress_tokens` with `num_beams` > 1 as well (`Qwen2Generator.beam_search(...)`: the
+    processors on the log-softmaxed scores, every beam's history following its parent, inside the step), and with constraints=True for
+    `constraint=` under beams; min_length, bad_words_ids, sequence_bias, prefix_allowed_tokens_fn and the warpers under beams keep falling
+    back, and so does the call without the flag.
     logits_processors=True (with generate=True) lets it take the library for `repetition_penalty`, `no_repeat_ngram_size`, `min_new_tokens`
     and `suppress_tokens` too (num_beams = 1; `Qwen2Generator.set_logits_processors`); without it those settings keep falling back.
     constraints=True (with generate=True): the patched generate pops `constraint=` (a `ml_fastvlm_amd.constraints.TokenAutomaton`) and
@@ -173,6 +179,8 @@ def install_into_llava(splice: bool = False, prefill: bool = False, prefill_any_
             extra["sampling_warpers"] = True
         if beam_sample:
             extra["beam_sample"] = True
+        if beam_processors:
+            extra["beam_processors"] = True
         lq.LlavaQwen2ForCausalLM.generate = _make_library_generate(getattr(cur, "_fvhd_orig", cur), beam_search=beam_search, **extra)
 
 
@@ -397,13 +405,16 @@ def _guidance_settings(who, scale, negative_prompt_ids, negative_prompt_attentio
 def beam_generate(model, input_ids, images=None, image_sizes=None, attention_mask=None, max_new_tokens: int = 256, num_beams: int = 4,
                   length_penalty: float = 1.0, early_stopping=False, num_return_sequences: int = 1, eos_token_id=None, pad_token_id=None,
                   return_scores: bool = False, guidance_scale=None, do_sample: bool = False, temperature: float = 1.0, top_k: int = 50,
-                  top_p: float = 1.0, seed=None):
+                  top_p: float = 1.0, seed=None, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0,
+                  suppress_tokens=None, constraint=None, constraint_start=None):
     """`generate`'s counterpart for `num_beams` > 1: `LlavaQwen2ForCausalLM.generate(..., num_beams=K)` (predict.py's --num_beams) with the
     splice, the prefill, every decode step, the top continuations and the cache reorder on the library (`Qwen2Generator.beam_search`).
     Returns the new tokens [B * num_return_sequences, n] as transformers' generate(inputs_embeds=..., num_beams=K) does, with return_scores
     also its `sequences_scores`.  The model must be bf16 on a HIP device and B * num_beams <= 64.  guidance_scale: refused (beam search does
     not take guidance).  do_sample=True: generate(do_sample=True, num_beams=K) - beam search with multinomial sampling, the keywords of
-    `Qwen2Generator.beam_search` (temperature, top_k, top_p, seed; predict.py's --num_beams at its default temperature)."""
+    `Qwen2Generator.beam_search` (temperature, top_k, top_p, seed; predict.py's --num_beams at its default temperature).
+    repetition_penalty / no_repeat_ngram_size / min_new_tokens / suppress_tokens / constraint / constraint_start: transformers' processors
+    under beams, the keywords of `Qwen2Generator.beam_search`; all off, the call is what it was."""
     from .qwen2_decode import _sampling_refusal, normalize_guidance
     if do_sample:
         _sampling_refusal("ml_fastvlm_amd.beam_generate", temperature, top_k, top_p)
@@ -423,6 +434,13 @@ def beam_generate(model, input_ids, images=None, image_sizes=None, attention_mas
                 num_return_sequences=int(num_return_sequences), return_scores=return_scores)
     if do_sample:
         beam.update(do_sample=True, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
+    from .logits_processors import normalize
+    proc = normalize(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, suppress_tokens, vocab=getattr(model.config, "vocab_size", None))
+    if proc is not None:
+        proc.pop("eos_token_id")
+        beam.update(proc)
+    if constraint is not None or constraint_start is not None:
+        beam.update(constraint=constraint, constraint_start=constraint_start)
     return _generate_on_library(model, input_ids, images, image_sizes, attention_mask, None, max_new_tokens, eos_token_id, pad_token_id, beam=beam)
 
 
@@ -790,7 +808,7 @@ def _warper_settings(gc):
 
 
 def _library_generate_settings(model, kwargs, beam_search: bool = False, processors: bool = False, prompt_lookup: bool = False, batch=None,
-                               guidance: bool = False, sampling_warpers: bool = False, beam_sample: bool = False):
+                               guidance: bool = False, sampling_warpers: bool = False, beam_sample: bool = False, beam_processors: bool = False):
     """transformers' own resolution of a generate(**kwargs) call (`_prepare_generation_config`, which generate itself calls: its global
     defaults such as top_k = 50, the model's generation_config, then the call's arguments) -> (settings, None) when the library can run
     it, (None, reason) when it cannot.  settings: max_new_tokens, eos_token_id, pad_token_id, `sampling` (None = greedy, else the
@@ -809,7 +827,11 @@ def _library_generate_settings(model, kwargs, beam_search: bool = False, process
     under do_sample `sampling` carries those that are on (`_warper_settings`); `top_h` keeps disqualifying it.
     beam_sample=True (with beam_search=True): do_sample with num_beams > 1 no longer disqualifies the call; `beam` then gains do_sample,
     temperature, top_k and top_p (the keywords of Qwen2Generator.beam_search) and `sampling` is None.  The warpers of `_WARPERS` and `top_h`
-    keep disqualifying a call with beams."""
+    keep disqualifying a call with beams.
+    beam_processors=True (with beam_search=True): with num_beams > 1, repetition_penalty, no_repeat_ngram_size, min_new_tokens and
+    suppress_tokens within the library's limits no longer disqualify the call; `beam` then carries those that are on, as keywords of
+    Qwen2Generator.beam_search (transformers applies them to the log-softmaxed scores, every beam's history following its parent).
+    min_length, bad_words_ids, sequence_bias, prefix_allowed_tokens_fn, the warpers and `top_h` keep disqualifying a call with beams."""
     negative = {}
     if guidance:
         negative = {k: kwargs[k] for k in _GUIDANCE_ARGS if kwargs.get(k) is not None}
@@ -832,6 +854,8 @@ def _library_generate_settings(model, kwargs, beam_search: bool = False, process
             continue
         if processors and single and k in _PROCESSORS:
             continue
+        if beam_processors and beams is not None and k in _PROCESSORS:
+            continue
         if prompt_lookup and k == "prompt_lookup_num_tokens":
             continue
         if guidance and single and k == "guidance_scale":
@@ -841,7 +865,7 @@ def _library_generate_settings(model, kwargs, beam_search: bool = False, process
         if v is not None and v not in off:
             return None, f"{k}={v!r}"
     proc = None
-    if processors and single:
+    if (processors and single) or (beam_processors and beams is not None):
         from .logits_processors import normalize
         vocab = getattr(getattr(model, "config", None), "vocab_size", None)
         try:
@@ -860,6 +884,9 @@ def _library_generate_settings(model, kwargs, beam_search: bool = False, process
             return None, f"num_beams={beams}, num_return_sequences={gc.num_return_sequences!r}, early_stopping={gc.early_stopping!r}"
         beam = dict(num_beams=beams, length_penalty=1.0 if gc.length_penalty is None else float(gc.length_penalty), early_stopping=early,
                     num_return_sequences=n_ret)
+        if proc is not None:                                     # (only under beam_processors)
+            beam.update(proc)
+            proc = None
     if gc.max_new_tokens is None:
         return None, "max_new_tokens is not given"
     if not gc.use_cache:
@@ -920,7 +947,8 @@ def _batch_reason(batch: int):
 
 
 def _make_library_generate(orig_generate, beam_search: bool = False, logits_processors: bool = False, constraints: bool = False,
-                           prompt_lookup: bool = False, guidance: bool = False, sampling_warpers: bool = False, beam_sample: bool = False):
+                           prompt_lookup: bool = False, guidance: bool = False, sampling_warpers: bool = False, beam_sample: bool = False,
+                           beam_processors: bool = False):
     """`LlavaQwen2ForCausalLM.generate` (`llava_qwen.py:106-143`) on the library: the same argument handling (position_ids / attention_mask
     popped, inputs_embeds refused), the settings resolved as transformers resolves them (`_library_generate_settings`), then the
     multimodal splice and `Qwen2Generator.greedy` / `.sample` on `generator_context(model, ...)`.  It takes the library only for greedy or
@@ -945,7 +973,10 @@ def _make_library_generate(orig_generate, beam_search: bool = False, logits_proc
     sampling_warpers=True: `min_p`, `typical_p`, `epsilon_cutoff` and `eta_cutoff` (num_beams = 1) run on the library as keywords of
     `Qwen2Generator.sample` / `.lookup_sample`; `top_h` keeps falling back, and with the flag off all five do.
     beam_sample=True (with beam_search=True): do_sample=True with num_beams > 1 takes `Qwen2Generator.beam_search(do_sample=True)`; with
-    the flag off it keeps falling back as beam sampling."""
+    the flag off it keeps falling back as beam sampling.
+    beam_processors=True (with beam_search=True): repetition_penalty, no_repeat_ngram_size, min_new_tokens and suppress_tokens with
+    num_beams > 1 run as keywords of `Qwen2Generator.beam_search`, and (with constraints=True) so does `constraint=`; with the flag off such
+    a call keeps falling back, and a constraint under beams keeps raising."""
     def generate(self, inputs=None, images=None, image_sizes=None, **kwargs):
         if "inputs_embeds" in kwargs:                            # as the reference (llava_qwen.py:120-121)
             raise NotImplementedError("`inputs_embeds` is not supported")
@@ -963,6 +994,8 @@ def _make_library_generate(orig_generate, beam_search: bool = False, logits_proc
             extra.update(sampling_warpers=True)
         if beam_sample:
             extra.update(beam_sample=True)
+        if beam_processors:
+            extra.update(beam_processors=True)
         settings, reason = _library_generate_settings(self, {k: v for k, v in kwargs.items() if k not in ("position_ids", "attention_mask")},
                                                       beam_search=beam_search, **extra)
         lookup = settings.get("lookup") if settings is not None else None
@@ -980,6 +1013,9 @@ def _make_library_generate(orig_generate, beam_search: bool = False, logits_proc
             settings, reason = None, _batch_reason(rows)
         if settings is not None and (lm_w.device.type != "cuda" or lm_w.dtype != torch.bfloat16):
             settings, reason = None, f"the model is {lm_w.dtype} on {lm_w.device} (the library decodes a bf16 model on a HIP device)"
+        if constraint is not None and settings is not None and settings["beam"] and beam_processors:
+            settings["beam"].update(constraint=constraint, constraint_start=constraint_start)      # beam_search's own keywords
+            constraint = constraint_start = None
         if constraint is not None and (settings is None or settings["beam"]):
             raise ValueError("generate(constraint=...): a constraint runs on the library only, with num_beams = 1 - " +
                              (f"this call would stay on the reference ({reason})" if settings is None else

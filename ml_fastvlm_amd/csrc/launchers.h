@@ -99,6 +99,14 @@ int fvhd_launch_dec_sample_theta(hipStream_t st, const DecSampleArgs* a, void* w
 size_t fvhd_dec_beam_topk_ws_bytes(void);
 int fvhd_dec_beam_topk_supported(int G, int K, int C, int V);
 int fvhd_launch_dec_beam_topk(hipStream_t st, const float* logits, const float* scores, int G, int K, int C, int V, float* out_v, int64_t* out_i, void* ws);
+int fvhd_launch_dec_beam_topk_mode(hipStream_t st, const float* logits, const float* scores, int G, int K, int C, int V, int prenorm, float* out_v, int64_t* out_i,
+                                   void* ws);
+size_t fvhd_dec_beam_norm_ws_bytes(void);
+int fvhd_dec_beam_norm_supported(int rows, int V);
+// stats: NULL, or fp32 [rows][2] = the (M, L) that were subtracted; status: NULL, or the launches do nothing while *status != 0
+int fvhd_launch_dec_beam_norm(hipStream_t st, float* logits, int rows, int V, void* ws, float* stats, const int* status);
+size_t fvhd_dec_hist_gather_ws_bytes(int batch, int cap, int V);
+int fvhd_launch_dec_hist_gather(hipStream_t st, const DecHistGatherArgs* a);
 size_t fvhd_dec_beam_sample_ws_bytes(void);      // zeroed once by the owner: it holds the sampler's arrival counters
 int fvhd_launch_dec_beam_sample(hipStream_t st, const DecBeamSampleArgs* a, void* ws);
 size_t fvhd_dec_cache_gather_ws_bytes(int rows, int nkv, int hd, int cap);

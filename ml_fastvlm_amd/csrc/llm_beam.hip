@@ -19,6 +19,10 @@
 // NEXT launch, which at the same time gathers the next layer into the scratch's other half - L + 1 launches for L layers, the mask and the
 // positions riding on the first two.  Rows with src[r] == r leave at once, in both directions.  Every workgroup checks all of src first:
 // one index outside [0, rows_in) and no launch writes anything but the error word (3).
+//
+// Beam search with processors (include/fvhd.h "LLM beam search with processors"): beam_norm_* turn the rows into log-probabilities in place
+// with the statistics above, beam_group / beam_sample_group take such rows as they are (`prenorm`), and dec_hist_move carries the rows'
+// processor histories and automaton states behind the cache reorder, by its rules.
 #include <algorithm>
 
 #include "fvhd_common.h"
@@ -131,6 +135,20 @@ __global__ __launch_bounds__(256) void beam_slice_kernel(const float* __restrict
     block_top<16>(key, C, keys + ((size_t)row * S + s) * C, red);
 }
 
+// a row's (max, log sum exp(x - max)) from its slices' partials, in slice order: ONE copy of the order, for beam_row and the normalisation
+FVHD_DEV void row_stats(const float* __restrict__ pmax, const float* __restrict__ psum, int row, int S, float& M_out, float& L_out)
+{
+    float M = -INFINITY;
+    for (int s = 0; s < S; ++s) M = fmaxf(M, pmax[row * S + s]);
+    float sum = 0.f;
+    for (int s = 0; s < S; ++s) {
+        const float ms = pmax[row * S + s];
+        if (ms > -INFINITY) sum += psum[row * S + s] * expf(ms - M);
+    }
+    M_out = M;
+    L_out = logf(sum);
+}
+
 __global__ __launch_bounds__(256) void beam_row_kernel(const u64* __restrict__ keys, const float* __restrict__ pmax, const float* __restrict__ psum,
                                                        int S, int C, u64* __restrict__ rowtop, float* __restrict__ rowmax, float* __restrict__ rowlog)
 {
@@ -142,23 +160,13 @@ __global__ __launch_bounds__(256) void beam_row_kernel(const u64* __restrict__ k
         const int i = j * 256 + t;
         key[j] = i < n ? keys[(size_t)row * n + i] : 0;
     }
-    if (t == 0) {
-        float M = -INFINITY;
-        for (int s = 0; s < S; ++s) M = fmaxf(M, pmax[row * S + s]);
-        float sum = 0.f;
-        for (int s = 0; s < S; ++s) {
-            const float ms = pmax[row * S + s];
-            if (ms > -INFINITY) sum += psum[row * S + s] * expf(ms - M);
-        }
-        rowmax[row] = M;
-        rowlog[row] = logf(sum);
-    }
+    if (t == 0) row_stats(pmax, psum, row, S, rowmax[row], rowlog[row]);
     block_top<16>(key, C, rowtop + (size_t)row * C, red);
 }
 
 __global__ __launch_bounds__(256) void beam_group_kernel(const u64* __restrict__ rowtop, const float* __restrict__ rowmax, const float* __restrict__ rowlog,
-                                                         const float* __restrict__ scores, int K, int C, int V, float* __restrict__ out_v,
-                                                         int64_t* __restrict__ out_i)
+                                                         const float* __restrict__ scores, int K, int C, int V, int prenorm,
+                                                         float* __restrict__ out_v, int64_t* __restrict__ out_i)
 {
     __shared__ u64 red[8];
     __shared__ u64 top[CMAX];
@@ -171,8 +179,8 @@ __global__ __launch_bounds__(256) void beam_group_kernel(const u64* __restrict__
         if (i < n) {
             const int k = i / C, row = g * K + k;
             const u64 c = rowtop[(size_t)row * C + i % C];
-            if (c) {
-                const float acc = ((cand_value(c) - rowmax[row]) - rowlog[row]) + scores[row];
+            if (c && !(prenorm && cand_value(c) == -INFINITY)) {                // a pre-normalised row: its value as it is; a banned entry is no candidate
+                const float acc = prenorm ? cand_value(c) + scores[row] : ((cand_value(c) - rowmax[row]) - rowlog[row]) + scores[row];
                 key[j] = make_key(acc, (unsigned)k * (unsigned)V + cand_index(c));
             }
         }
@@ -183,6 +191,85 @@ __global__ __launch_bounds__(256) void beam_group_kernel(const u64* __restrict__
         const u64 c = top[t];
         out_v[(size_t)g * C + t] = c ? cand_value(c) : -INFINITY;
         out_i[(size_t)g * C + t] = c ? (int64_t)cand_index(c) : 0;
+    }
+}
+
+// ---- row normalisation: x[r][v] <- (x[r][v] - M_r) - L_r in place (include/fvhd.h "LLM beam search with processors") -------------------------
+// Under beams transformers runs its processors on log_softmax(x).  M_r and L_r are beam_slice's / beam_row's: the same slices, the same
+// per-thread element order, the same trees - so an entry that no processor edits holds, bit for bit, what the plain chain adds to the beam
+// score.  Two launches of grid (S, rows): the slices' partials, then the apply (every workgroup merges its row's partials again, in slice
+// order).  Any V: a row that is not 16-byte aligned (V % 4 != 0) and a row's last 1 .. 3 entries go element by element.
+__global__ __launch_bounds__(256) void beam_norm_slice_kernel(const float* __restrict__ logits, int V, int S, float* __restrict__ pmax,
+                                                              float* __restrict__ psum, const int* __restrict__ status)
+{
+    if (status && *status) return;
+    __shared__ float fred[8];
+    const int s = blockIdx.x, row = blockIdx.y, t = threadIdx.x;
+    const float* x = logits + (size_t)row * V;
+    const bool vec = ((uintptr_t)x & 15) == 0;
+    float v[16];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int e = s * SLICE + (j * 256 + t) * 4;
+        if (vec && e + 3 < V) {
+            const f32x4 q = *(const f32x4*)(x + e);
+            v[4 * j + 0] = q[0]; v[4 * j + 1] = q[1]; v[4 * j + 2] = q[2]; v[4 * j + 3] = q[3];
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[4 * j + i] = e + i < V ? x[e + i] : -INFINITY;      // (outside the row: no part of the maximum, skipped by the sum)
+        }
+    }
+    float m = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) m = fmaxf(m, v[j]);
+#pragma unroll
+    for (int o = 32; o; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    if ((t & 63) == 0) fred[4 + (t >> 6)] = m;
+    __syncthreads();
+    m = fmaxf(fmaxf(fred[4], fred[5]), fmaxf(fred[6], fred[7]));
+    m = m == 0.f ? 0.f : m;                                      // (beam_slice's maximum comes out of a key: -0 is +0 there)
+    float acc = 0.f;
+    if (m > -INFINITY) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int e = s * SLICE + ((j >> 2) * 256 + t) * 4 + (j & 3);
+            if (e < V) acc += expf(v[j] - m);
+        }
+    }
+    acc = wave_sum(acc);
+    if ((t & 63) == 0) fred[t >> 6] = acc;
+    __syncthreads();
+    if (t == 0) {
+        pmax[row * S + s] = m;
+        psum[row * S + s] = ((fred[0] + fred[1]) + fred[2]) + fred[3];
+    }
+}
+
+__global__ __launch_bounds__(256) void beam_norm_apply_kernel(float* __restrict__ logits, int V, int S, const float* __restrict__ pmax,
+                                                              const float* __restrict__ psum, float* __restrict__ stats, const int* __restrict__ status)
+{
+    if (status && *status) return;
+    __shared__ float ml[2];
+    const int s = blockIdx.x, row = blockIdx.y, t = threadIdx.x;
+    if (t == 0) {
+        row_stats(pmax, psum, row, S, ml[0], ml[1]);
+        if (stats && s == 0) { stats[2 * row] = ml[0]; stats[2 * row + 1] = ml[1]; }
+    }
+    __syncthreads();
+    const float M = ml[0], L = ml[1];
+    float* x = logits + (size_t)row * V;
+    const bool vec = ((uintptr_t)x & 15) == 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int e = s * SLICE + (j * 256 + t) * 4;
+        if (vec && e + 3 < V) {
+            f32x4 q = *(const f32x4*)(x + e);
+            q[0] = (q[0] - M) - L; q[1] = (q[1] - M) - L; q[2] = (q[2] - M) - L; q[3] = (q[3] - M) - L;
+            *(f32x4*)(x + e) = q;
+        } else {
+            for (int i = 0; i < 4; ++i)
+                if (e + i < V) x[e + i] = (x[e + i] - M) - L;
+        }
     }
 }
 
@@ -224,6 +311,11 @@ FVHD_DEV unsigned beam_theta(const DecBeamSampleArgs& a, const u64* __restrict__
 }
 
 FVHD_DEV float beam_acc(float x, float M, float L, float T, float score) { return scaled((x - M) - L, T) + score; }
+// a.prenorm: the rows hold log-probabilities already - a = x / T + score
+FVHD_DEV float beam_acc(const DecBeamSampleArgs& a, float x, const float* __restrict__ rowmax, const float* __restrict__ rowlog, int row)
+{
+    return a.prenorm ? scaled(x, a.temperature) + a.scores[row] : beam_acc(x, rowmax[row], rowlog[row], a.temperature, a.scores[row]);
+}
 
 __global__ __launch_bounds__(256) void beam_sample_slice_kernel(const DecBeamSampleArgs a, int S, const u64* __restrict__ rawtop,
                                                                 const unsigned* __restrict__ theta_s, u64* __restrict__ keys, int* __restrict__ pcnt)
@@ -277,7 +369,6 @@ __global__ __launch_bounds__(256) void beam_sample_group_kernel(const DecBeamSam
     __shared__ u64 top[CMAX];
     const int g = blockIdx.x, t = threadIdx.x, K = a.K, C = a.keep, V = a.V, n = K * C;      // n <= 1024
     const BeamNoise noise(a);
-    const float T = a.temperature;
     u64 key[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -288,7 +379,7 @@ __global__ __launch_bounds__(256) void beam_sample_group_kernel(const DecBeamSam
             const u64 c = rowtop[(size_t)row * C + i % C];
             if (c) {
                 const int v = (int)cand_index(c);
-                const float acc = beam_acc(a.logits[(size_t)row * V + v], rowmax[row], rowlog[row], T, a.scores[row]);
+                const float acc = beam_acc(a, a.logits[(size_t)row * V + v], rowmax, rowlog, row);
                 const float gn = noise.over ? noise.over[(size_t)row * V + v] : gumbel_of_word(noise.words(row, v).w[v & 3]);
                 key[j] = make_key(acc + gn, (unsigned)k * (unsigned)V + (unsigned)v);
             }
@@ -301,7 +392,7 @@ __global__ __launch_bounds__(256) void beam_sample_group_kernel(const DecBeamSam
         float acc = -INFINITY;
         if (c) {
             const int k = (int)(cand_index(c) / (unsigned)V), v = (int)(cand_index(c) % (unsigned)V), row = g * K + k;
-            acc = beam_acc(a.logits[(size_t)row * V + v], rowmax[row], rowlog[row], T, a.scores[row]);       // the unperturbed value
+            acc = beam_acc(a, a.logits[(size_t)row * V + v], rowmax, rowlog, row);       // the unperturbed value
         }
         a.out_v[(size_t)g * C + t] = acc;
         a.out_i[(size_t)g * C + t] = c ? (int64_t)cand_index(c) : 0;
@@ -400,7 +491,103 @@ __global__ __launch_bounds__(256) void dec_cache_move_kernel(CacheMoveArgs a)
     }
 }
 
+// ---- the rows' processor histories and automaton states behind the KV reorder (DecHistGatherArgs) ---------------------------------------------
+// New row r = old row src[r] of: the first count[src[r]] history entries (sign bits and all), the seen-bitmap's W words, the count, the
+// constraint's state and flag words.  dec_cache_move's rules: through a scratch, never in place (launch 0 gathers into it, launch 1 copies back);
+// rows with src[r] == r leave at once; every workgroup checks all of src first.  grid (x, rows_out): the x workgroups of a row stride over it.
+static_assert(RMAX <= 256, "dec_cache_move / dec_hist_move check all of src with one thread per row of one 256-thread workgroup");
+struct HistScratch { int* hist; unsigned* seen; int* count; int* state; int* flags; size_t bytes; };
+
+HistScratch carve_hist(char* base, int batch, int cap, int W)
+{
+    HistScratch h;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char* q = base + off; off += (bytes + 255) & ~(size_t)255; return q; };
+    h.hist = (int*)take((size_t)batch * cap * 4);
+    h.seen = (unsigned*)take((size_t)batch * W * 4);
+    h.count = (int*)take((size_t)batch * 4);
+    h.state = (int*)take(RMAX * 4);
+    h.flags = (int*)take(RMAX * 4);
+    h.bytes = off;
+    return h;
+}
+
+__global__ __launch_bounds__(256) void dec_hist_move_kernel(DecHistGatherArgs a, HistScratch sc, int back)
+{
+    __shared__ int bad;
+    const int t = threadIdx.x;
+    if (t == 0) bad = 0;
+    __syncthreads();
+    if (t < a.rows_out) {
+        const int64_t s = a.src[t];
+        if (s < 0 || s >= a.rows_in) bad = 1;
+    }
+    __syncthreads();
+    const int st = *(volatile const int*)a.status;
+    if (bad) {                                                   // every workgroup of both launches finds the same: nothing is written
+        if (!st && t == 0 && blockIdx.x == 0 && blockIdx.y == 0) {
+            *a.status = 3;
+            if (a.status_host) *a.status_host = 3;
+        }
+        return;
+    }
+    if (st) return;
+    const int r = blockIdx.y, W = (a.V + 31) / 32;
+    const int64_t s = a.src[r];
+    if (s == r) return;
+    const int64_t from = back ? r : s;
+    const bool one = blockIdx.x == 0 && t == 0;
+    if (a.hist) {
+        const int* fc = back ? sc.count : a.count;
+        const int* fh = back ? sc.hist : a.hist;
+        const unsigned* fs = back ? sc.seen : a.seen;
+        int* th = back ? a.hist : sc.hist;
+        unsigned* ts = back ? a.seen : sc.seen;
+        const int n = max(0, min(fc[from], a.cap));
+        for (int i = blockIdx.x * 256 + t; i < n; i += gridDim.x * 256) th[(size_t)r * a.cap + i] = fh[from * a.cap + i];
+        for (int i = blockIdx.x * 256 + t; i < W; i += gridDim.x * 256) ts[(size_t)r * W + i] = fs[from * W + i];
+        if (one) (back ? a.count : sc.count)[r] = fc[from];
+    }
+    if (a.states && one) {
+        (back ? a.states : sc.state)[r] = (back ? sc.state : a.states)[from];
+        (back ? a.flags : sc.flags)[r] = (back ? sc.flags : a.flags)[from];
+    }
+}
+
 }  // namespace
+
+extern "C" size_t fvhd_dec_hist_gather_ws_bytes(int batch, int cap, int V)
+{
+    return al256b((size_t)batch * cap * 4) + al256b((size_t)batch * ((V + 31) / 32) * 4) + al256b((size_t)batch * 4) + 2 * al256b(RMAX * 4);
+}
+
+extern "C" int fvhd_launch_dec_hist_gather(hipStream_t st, const DecHistGatherArgs* a)
+{
+    if (!a->src || !a->status || !a->ws || a->rows_in < 1 || a->rows_out < 1 || a->rows_in > a->batch || a->rows_out > a->batch || a->batch > RMAX ||
+        a->cap < 1 || a->V < 1 || (a->hist && (!a->seen || !a->count)) || (a->states && !a->flags) || ((uintptr_t)a->ws & 15))
+        return (int)hipErrorInvalidValue;
+    if (!a->hist && !a->states) return 0;
+    const int W = (a->V + 31) / 32, gx = a->hist ? std::min(8, (std::max(a->cap, W) + 255) / 256) : 1;
+    const HistScratch sc = carve_hist(a->ws, a->batch, a->cap, W);
+    for (int back = 0; back < 2; ++back) hipLaunchKernelGGL(dec_hist_move_kernel, dim3(gx, a->rows_out), dim3(256), 0, st, *a, sc, back);
+    return (int)hipGetLastError();
+}
+
+// the normalisation's scratch: the slices' partials of RMAX rows
+extern "C" size_t fvhd_dec_beam_norm_ws_bytes(void) { return 2 * al256b(4 * RMAX * SMAXB); }
+
+extern "C" int fvhd_dec_beam_norm_supported(int rows, int V) { return rows >= 1 && rows <= RMAX && V >= 1 && V <= SLICE * SMAXB; }
+
+extern "C" int fvhd_launch_dec_beam_norm(hipStream_t st, float* logits, int rows, int V, void* ws, float* stats, const int* status)
+{
+    if (!fvhd_dec_beam_norm_supported(rows, V) || !logits || !ws || ((uintptr_t)logits & 3)) return (int)hipErrorInvalidValue;
+    float* pmax = (float*)ws;
+    float* psum = (float*)((char*)ws + al256b(4 * RMAX * SMAXB));
+    const int S = (V + SLICE - 1) / SLICE;
+    hipLaunchKernelGGL(beam_norm_slice_kernel, dim3(S, rows), dim3(256), 0, st, logits, V, S, pmax, psum, status);
+    hipLaunchKernelGGL(beam_norm_apply_kernel, dim3(S, rows), dim3(256), 0, st, logits, V, S, pmax, psum, stats, status);
+    return (int)hipGetLastError();
+}
 
 extern "C" size_t fvhd_dec_beam_topk_ws_bytes(void)
 {
@@ -415,12 +602,19 @@ extern "C" int fvhd_dec_beam_topk_supported(int G, int K, int C, int V)
 extern "C" int fvhd_launch_dec_beam_topk(hipStream_t st, const float* logits, const float* scores, int G, int K, int C, int V, float* out_v, int64_t* out_i,
                                          void* ws)
 {
+    return fvhd_launch_dec_beam_topk_mode(st, logits, scores, G, K, C, V, 0, out_v, out_i, ws);
+}
+
+// prenorm: the rows hold processed log-probabilities - acc = x + score, and a -inf entry is no candidate; the same three launches
+extern "C" int fvhd_launch_dec_beam_topk_mode(hipStream_t st, const float* logits, const float* scores, int G, int K, int C, int V, int prenorm,
+                                              float* out_v, int64_t* out_i, void* ws)
+{
     if (!fvhd_dec_beam_topk_supported(G, K, C, V) || ((uintptr_t)logits & 15)) return (int)hipErrorInvalidValue;
     const TopkWs w = carve_topk(ws);
     const int rows = G * K, S = (V + SLICE - 1) / SLICE;
     hipLaunchKernelGGL(beam_slice_kernel, dim3(S, rows), dim3(256), 0, st, logits, V, S, C, w.keys, w.pmax, w.psum);
     hipLaunchKernelGGL(beam_row_kernel, dim3(rows), dim3(256), 0, st, w.keys, w.pmax, w.psum, S, C, w.rowtop, w.rowmax, w.rowlog);
-    hipLaunchKernelGGL(beam_group_kernel, dim3(G), dim3(256), 0, st, w.rowtop, w.rowmax, w.rowlog, scores, K, C, V, out_v, out_i);
+    hipLaunchKernelGGL(beam_group_kernel, dim3(G), dim3(256), 0, st, w.rowtop, w.rowmax, w.rowlog, scores, K, C, V, prenorm, out_v, out_i);
     return (int)hipGetLastError();
 }
 

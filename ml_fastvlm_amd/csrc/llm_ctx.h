@@ -88,6 +88,15 @@ struct __attribute__((visibility("default"))) fvhd_llm {     // (its inline cons
     char* beam = nullptr;                  // the reorder's scratch (llm_beam.hip: two layers' K | V, the mask, the positions), then the top-K workspace
     char* beam_topk = nullptr;
     char* beam_sample = nullptr;           // fvhd_llm_beam_sample_reserve: the workspace of beam-search sampling, an allocation of its own (no cache size in it)
+    // fvhd_llm_set_beam_scoring: with it on, fvhd_llm_start / _decode with a logits_out turn the rows into log-probabilities in front of the
+    // processors and the constraint, fvhd_llm_cache_gather carries the rows' histories and automaton states, and the two top-K calls take the
+    // rows as they are.  Read when a call enqueues, like the sampling settings.  beam_proc: the normalisation's partials, then the scratch of
+    // the history / state reorder - an allocation of its own, made by the call that switches the mode on and sized for the reserved cache
+    // (fvhd_llm_cache_reserve frees it and switches the mode off)
+    int beam_scoring = 0;
+    char* beam_proc = nullptr;
+    char* beam_proc_norm = nullptr;        // inside beam_proc: the normalisation's partials ...
+    char* beam_proc_hist = nullptr;        // ... and the reorder's scratch
     // fvhd_llm_set_logits_processors (llm_logits.hip): read when fvhd_llm_start / fvhd_llm_decode enqueue, like the sampling settings
     float proc_penalty = 1.f;
     int proc_ngram = 0, proc_min_new = 0, proc_n_eos = 0, proc_n_sup = 0;

@@ -88,6 +88,20 @@ struct DecCacheGatherArgs {
     char* ws = nullptr;            // fvhd_dec_cache_gather_ws_bytes(batch, nkv, hd, cap) bytes
 };
 
+// Arguments of the reorder of the rows' processor histories and automaton states (llm_beam.hip), behind the KV reorder with the same src.
+struct DecHistGatherArgs {
+    int* hist = nullptr;           // [batch][cap] history entries (DecLogitsArgs::hist), or NULL: no histories move
+    unsigned* seen = nullptr;      // [batch][ceil(V / 32)]
+    int* count = nullptr;          // [batch]
+    int* states = nullptr;         // the constraint's states [batch] and flags [batch], or NULL: no states move
+    int* flags = nullptr;
+    const int64_t* src = nullptr;  // int64 [rows_out] on the device, every entry in [0, rows_in)
+    int rows_in = 0, rows_out = 0, batch = 0, cap = 0, V = 0;
+    int* status = nullptr;         // as DecCacheGatherArgs::status
+    int* status_host = nullptr;
+    char* ws = nullptr;            // fvhd_dec_hist_gather_ws_bytes(batch, cap, V) bytes, 16-byte aligned
+};
+
 // Arguments of beam-search sampling (llm_beam.hip): per prompt the `keep` kept candidates with the largest a + g (include/fvhd.h "LLM beam-search
 // sampling"), logits fp32 [G * K][V] 16-byte aligned, scores fp32 [G][K].
 struct DecBeamSampleArgs {
@@ -106,6 +120,7 @@ struct DecBeamSampleArgs {
     float* info = nullptr;         // non-NULL: [G * K][4]: theta as s (-inf: no filter binds), kept count, row maximum M, L = log sum exp(x - M)
     float* out_v = nullptr;        // [G][keep]: the unperturbed a of the picks, in descending a + g
     int64_t* out_i = nullptr;      // [G][keep]: beam * V + token
+    int prenorm = 0;               // 1: the rows hold processed log-probabilities x' - a = x' / T + score, no M or L subtracted
 };
 
 // Arguments of the logits processors (llm_logits.hip): sparse in-place edits of fp32 logits [B][V] from a per-row token history, one

@@ -445,39 +445,53 @@ static int op_scratch(const char* who, char* (&buf)[64], size_t (&cap)[64], size
     return 0;
 }
 
-int fvhd_op_dec_beam_topk(fvhd_stream_t st, const float* logits, const float* beam_scores, int groups, int num_beams, int keep, int V, float* cand_scores,
-                          int64_t* cand_index)
+static int op_beam_topk(const char* who, fvhd_stream_t st, const float* logits, const float* beam_scores, int groups, int num_beams, int keep, int V,
+                        int prenorm, float* cand_scores, int64_t* cand_index)
 {
-    if (!logits || !beam_scores || !cand_scores || !cand_index) return lfail("fvhd_op_dec_beam_topk: NULL pointer");
+    const std::string w(who);
+    if (!logits || !beam_scores || !cand_scores || !cand_index) return lfail(w + ": NULL pointer");
     if (!fvhd_dec_beam_topk_supported(groups, num_beams, keep, V) || ((uintptr_t)logits & 15))
-        return lfail("fvhd_op_dec_beam_topk: needs groups >= 1, 2 <= num_beams <= 16, 1 <= keep <= 64, keep <= V, groups * num_beams <= 64, V % 16 == 0, "
+        return lfail(w + ": needs groups >= 1, 2 <= num_beams <= 16, 1 <= keep <= 64, keep <= V, groups * num_beams <= 64, V % 16 == 0, "
                      "V <= 262144 and logits aligned to 16 bytes");
     static char* buf[64] = {};
     static size_t cap[64] = {};
     char* ws = nullptr;
-    if (int e = op_scratch("fvhd_op_dec_beam_topk", buf, cap, fvhd_dec_beam_topk_ws_bytes(), &ws)) return e;
-    return lret("fvhd_op_dec_beam_topk", fvhd_launch_dec_beam_topk((hipStream_t)st, logits, beam_scores, groups, num_beams, keep, V, cand_scores, cand_index, ws));
+    if (int e = op_scratch(who, buf, cap, fvhd_dec_beam_topk_ws_bytes(), &ws)) return e;
+    return lret(who, fvhd_launch_dec_beam_topk_mode((hipStream_t)st, logits, beam_scores, groups, num_beams, keep, V, prenorm, cand_scores, cand_index, ws));
+}
+
+int fvhd_op_dec_beam_topk(fvhd_stream_t st, const float* logits, const float* beam_scores, int groups, int num_beams, int keep, int V, float* cand_scores,
+                          int64_t* cand_index)
+{
+    return op_beam_topk("fvhd_op_dec_beam_topk", st, logits, beam_scores, groups, num_beams, keep, V, 0, cand_scores, cand_index);
+}
+
+int fvhd_op_dec_beam_topk_pre(fvhd_stream_t st, const float* logits, const float* beam_scores, int groups, int num_beams, int keep, int V, float* cand_scores,
+                              int64_t* cand_index)
+{
+    return op_beam_topk("fvhd_op_dec_beam_topk_pre", st, logits, beam_scores, groups, num_beams, keep, V, 1, cand_scores, cand_index);
 }
 
 // beam-search sampling on its own: a process-wide workspace, allocated and zeroed (the sampler's arrival counters) on first use - eager calls only
-int fvhd_op_dec_beam_sample(fvhd_stream_t st, const float* logits, const float* beam_scores, int groups, int num_beams, int keep, int V, float temperature,
-                            int top_k, float top_p, int min_keep, unsigned long long seed, int n, const float* noise_override, float* noise_out, float* info,
-                            float* cand_scores, int64_t* cand_index)
+static int op_beam_sample(const char* who, fvhd_stream_t st, const float* logits, const float* beam_scores, int groups, int num_beams, int keep, int V,
+                          float temperature, int top_k, float top_p, int min_keep, unsigned long long seed, int n, const float* noise_override, float* noise_out,
+                          float* info, float* cand_scores, int64_t* cand_index, int prenorm)
 {
-    if (!logits || !beam_scores || !cand_scores || !cand_index) return lfail("fvhd_op_dec_beam_sample: NULL pointer");
+    const std::string w(who);
+    if (!logits || !beam_scores || !cand_scores || !cand_index) return lfail(w + ": NULL pointer");
     if (!fvhd_dec_beam_topk_supported(groups, num_beams, keep, V) || ((uintptr_t)logits & 15))
-        return lfail("fvhd_op_dec_beam_sample: needs groups >= 1, 2 <= num_beams <= 16, 1 <= keep <= 64, keep <= V, groups * num_beams <= 64, V % 16 == 0, "
+        return lfail(w + ": needs groups >= 1, 2 <= num_beams <= 16, 1 <= keep <= 64, keep <= V, groups * num_beams <= 64, V % 16 == 0, "
                      "V <= 262144 and logits aligned to 16 bytes");
-    if (const char* e = sampling_error(temperature, top_k, top_p)) return lfail(std::string("fvhd_op_dec_beam_sample: ") + e);
+    if (const char* e = sampling_error(temperature, top_k, top_p)) return lfail(w + ": " + e);
     if (min_keep < 1 || min_keep > keep)
-        return lfail("fvhd_op_dec_beam_sample: min_keep must be in [1, keep] (got " + std::to_string(min_keep) + " with keep = " + std::to_string(keep) + ")");
-    if (n < 0) return lfail("fvhd_op_dec_beam_sample: n must be >= 0");
-    if (((uintptr_t)noise_override & 15) || ((uintptr_t)noise_out & 15)) return lfail("fvhd_op_dec_beam_sample: noise_override and noise_out must be aligned to 16 bytes");
+        return lfail(w + ": min_keep must be in [1, keep] (got " + std::to_string(min_keep) + " with keep = " + std::to_string(keep) + ")");
+    if (n < 0) return lfail(w + ": n must be >= 0");
+    if (((uintptr_t)noise_override & 15) || ((uintptr_t)noise_out & 15)) return lfail(w + ": noise_override and noise_out must be aligned to 16 bytes");
     static char* ws[64] = {};
     int dev = 0;
     hipError_t he = hipGetDevice(&dev);
     if (he != hipSuccess) return lhip("hipGetDevice", he);
-    if (dev < 0 || dev >= 64) return lfail("fvhd_op_dec_beam_sample: device index out of range");
+    if (dev < 0 || dev >= 64) return lfail(w + ": device index out of range");
     if (!ws[dev]) {
         const size_t bytes = fvhd_dec_beam_sample_ws_bytes();
         if ((he = hipMalloc((void**)&ws[dev], bytes)) != hipSuccess) { ws[dev] = nullptr; return lhip("hipMalloc(beam sampling workspace)", he); }
@@ -486,8 +500,57 @@ int fvhd_op_dec_beam_sample(fvhd_stream_t st, const float* logits, const float* 
     DecBeamSampleArgs a;
     a.logits = logits; a.scores = beam_scores; a.G = groups; a.K = num_beams; a.keep = keep; a.V = V; a.temperature = temperature; a.top_k = top_k;
     a.top_p = top_p; a.min_keep = min_keep; a.seed = seed; a.n_add = n; a.noise_override = noise_override; a.noise_out = noise_out; a.info = info;
-    a.out_v = cand_scores; a.out_i = cand_index;
-    return lret("fvhd_op_dec_beam_sample", fvhd_launch_dec_beam_sample((hipStream_t)st, &a, ws[dev]));
+    a.out_v = cand_scores; a.out_i = cand_index; a.prenorm = prenorm;
+    return lret(who, fvhd_launch_dec_beam_sample((hipStream_t)st, &a, ws[dev]));
+}
+
+int fvhd_op_dec_beam_sample(fvhd_stream_t st, const float* logits, const float* beam_scores, int groups, int num_beams, int keep, int V, float temperature,
+                            int top_k, float top_p, int min_keep, unsigned long long seed, int n, const float* noise_override, float* noise_out, float* info,
+                            float* cand_scores, int64_t* cand_index)
+{
+    return op_beam_sample("fvhd_op_dec_beam_sample", st, logits, beam_scores, groups, num_beams, keep, V, temperature, top_k, top_p, min_keep, seed, n,
+                          noise_override, noise_out, info, cand_scores, cand_index, 0);
+}
+
+int fvhd_op_dec_beam_sample_pre(fvhd_stream_t st, const float* logits, const float* beam_scores, int groups, int num_beams, int keep, int V, float temperature,
+                                int top_k, float top_p, int min_keep, unsigned long long seed, int n, const float* noise_override, float* noise_out, float* info,
+                                float* cand_scores, int64_t* cand_index)
+{
+    return op_beam_sample("fvhd_op_dec_beam_sample_pre", st, logits, beam_scores, groups, num_beams, keep, V, temperature, top_k, top_p, min_keep, seed, n,
+                          noise_override, noise_out, info, cand_scores, cand_index, 1);
+}
+
+// the row normalisation on its own: stats_out NULL, or fp32 [rows][2] = the (M, L) subtracted from every row
+int fvhd_op_dec_beam_norm(fvhd_stream_t st, float* logits, int rows, int V, float* stats_out)
+{
+    if (!logits) return lfail("fvhd_op_dec_beam_norm: NULL pointer");
+    if (!fvhd_dec_beam_norm_supported(rows, V) || ((uintptr_t)logits & 3))
+        return lfail("fvhd_op_dec_beam_norm: needs 1 <= rows <= 64, 1 <= V <= 262144 and logits aligned to 4 bytes");
+    static char* buf[64] = {};
+    static size_t cap[64] = {};
+    char* ws = nullptr;
+    if (int e = op_scratch("fvhd_op_dec_beam_norm", buf, cap, fvhd_dec_beam_norm_ws_bytes(), &ws)) return e;
+    return lret("fvhd_op_dec_beam_norm", fvhd_launch_dec_beam_norm((hipStream_t)st, logits, rows, V, ws, stats_out, nullptr));
+}
+
+// the history / state reorder on its own: history NULL (no histories move) or int32 [batch][capacity] entries as the step keeps them, seen
+// uint32 [batch][ceil(V / 32)], count int32 [batch]; states NULL (no states move) or int32 [batch] with flags int32 [batch]
+int fvhd_op_dec_hist_gather(fvhd_stream_t st, int32_t* history, uint32_t* seen, int32_t* count, int32_t* states, int32_t* flags, const int64_t* src_rows,
+                            int batch, int rows_in, int rows_out, int capacity, int V, int* status)
+{
+    if (!src_rows || !status) return lfail("fvhd_op_dec_hist_gather: NULL pointer");
+    if (batch < 1 || batch > 64 || rows_in < 1 || rows_in > batch || rows_out < 1 || rows_out > batch || capacity < 1 || V < 1 ||
+        (history && (!seen || !count)) || (states && !flags))
+        return lfail("fvhd_op_dec_hist_gather: needs 1 <= rows_in, rows_out <= batch <= 64, capacity >= 1, V >= 1, seen and count with a history, flags "
+                     "with states");
+    static char* buf[64] = {};
+    static size_t cap[64] = {};
+    char* ws = nullptr;
+    if (int e = op_scratch("fvhd_op_dec_hist_gather", buf, cap, fvhd_dec_hist_gather_ws_bytes(batch, capacity, V), &ws)) return e;
+    DecHistGatherArgs a;
+    a.hist = history; a.seen = seen; a.count = count; a.states = states; a.flags = flags; a.src = src_rows; a.rows_in = rows_in; a.rows_out = rows_out;
+    a.batch = batch; a.cap = capacity; a.V = V; a.status = status; a.ws = ws;
+    return lret("fvhd_op_dec_hist_gather", fvhd_launch_dec_hist_gather((hipStream_t)st, &a));
 }
 
 int fvhd_op_dec_cache_gather(fvhd_stream_t st, void* k_cache, void* v_cache, uint8_t* key_valid, int64_t* positions, const int64_t* src_rows, int n_layers,

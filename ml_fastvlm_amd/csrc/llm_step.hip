@@ -153,7 +153,22 @@ struct ChoiceArgs {
     int start_T = 0;               // > 0: fvhd_llm_start on a prompt of start_T tokens - the token history begins empty
     int n_add = 0;                 // the sampler's counter is n = length + n_add
     int64_t* ids_out = nullptr;
+    bool beam_rows = false;        // beam scoring is on and the caller takes the logits: they become log-probabilities before any edit
 };
+
+// what fvhd_llm_set_beam_scoring does not cover, refused when a call enqueues under it
+int beam_scoring_refusal(const fvhd_llm* c, const char* who)
+{
+    if (!c->beam_scoring) return 0;
+    const std::string w(who);
+    if (guidance_on(c))
+        return lfail(w + ": beam scoring is on (fvhd_llm_set_beam_scoring) and so is guidance (fvhd_llm_set_guidance) - beam search does not carry "
+                         "the pairing of conditional and unconditional rows; switch one of them off");
+    if (c->lp_on)
+        return lfail(w + ": beam scoring is on (fvhd_llm_set_beam_scoring) and so are log-probabilities (fvhd_llm_set_logprobs) - the rows would be "
+                         "normalised twice; switch one of them off");
+    return 0;
+}
 
 // guidance, processors, constraint, then the sampler or the argmax, then the guidance mirror - with the host's marks of what the sequence
 // was started with.  `state` is fvhd_llm_start's cache-state launch: before the draw, which reads n = the prompt length from the device,
@@ -169,6 +184,8 @@ int choose_tokens(fvhd_llm* c, hipStream_t st, const ChoiceArgs& a, StateLaunch 
     if (!a.step) c->con_started = con;
     // guidance first, where transformers puts it: the guided scores replace the conditional rows before anything else reads them
     if (gd) LCHECK(fvhd_launch_dec_guidance(st, a.logits, a.R, c->V, c->guid_scale, c->guid_ws, a.gate), (w + " guidance").c_str());
+    // under beams transformers' processors see log_softmax(x): the rows are normalised before the first edit (llm_beam.hip)
+    if (a.beam_rows) LCHECK(fvhd_launch_dec_beam_norm(st, a.logits, a.R, c->V, c->beam_proc_norm, nullptr, a.gate), (w + " row normalisation").c_str());
     if (proc) {
         // an empty history: no token is in the bitmap, and the launch zeroes the rows' history counts
         if (a.start_T)
@@ -367,7 +384,9 @@ int fvhd_llm_cache_reserve(fvhd_llm* c, int batch, int capacity)
     if (c->beam) (void)hipFree(c->beam);                         // sized for the cache it was reserved for: fvhd_llm_beam_reserve again
     if (c->spec) (void)hipFree(c->spec);                         // likewise: fvhd_llm_spec_reserve again
     if (c->lp_ws) (void)hipFree(c->lp_ws);                       // likewise: fvhd_llm_set_logprobs again
-    c->dc = c->beam = c->beam_topk = c->spec = c->lp_ws = nullptr;
+    if (c->beam_proc) (void)hipFree(c->beam_proc);               // likewise: fvhd_llm_set_beam_scoring again
+    c->dc = c->beam = c->beam_topk = c->spec = c->lp_ws = c->beam_proc = c->beam_proc_norm = c->beam_proc_hist = nullptr;
+    c->beam_scoring = 0;
     c->lp_on = 0;
     c->lp_logits = nullptr;
     c->spec_rows = 0;
@@ -403,6 +422,7 @@ int fvhd_llm_start(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* ke
     if (batch < 1 || batch > c->dc_batch) return lfail("fvhd_llm_start: batch must be in [1, the batch of fvhd_llm_cache_reserve]");
     if (seq_len < 1 || seq_len > c->dc_cap) return lfail("fvhd_llm_start: seq_len must be in [1, the capacity of fvhd_llm_cache_reserve]");
     if (int e = dec_embedding_error(c, "fvhd_llm_start")) return e;
+    if (int e = beam_scoring_refusal(c, "fvhd_llm_start")) return e;
     const bool gd = guidance_on(c);
     if (gd)
         if (int e = guidance_rows_error("fvhd_llm_start", batch)) return e;
@@ -447,6 +467,7 @@ int fvhd_llm_start(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* ke
     // the first token, ungated, of the prefill's logits; the histories and the rows' automaton states begin here
     ChoiceArgs ch;
     ch.who = "first-token"; ch.reduce_what = "first-token argmax (reduce)"; ch.logits = logits; ch.R = R; ch.start_T = T; ch.ids_out = next_ids_out;
+    ch.beam_rows = c->beam_scoring && logits_out;
     e = choose_tokens(c, st, ch, [&] {
         LCHECK(fvhd_launch_dec_start_state(st, c->posv, position_ids, B, T, c->len, c->status), "decode state");
         return 0;
@@ -465,6 +486,7 @@ int fvhd_llm_decode(fvhd_llm* c, const int64_t* token_ids, float* logits_out, in
     if (!c->dc || !c->run_batch) return lfail("fvhd_llm_decode: no started sequence - call fvhd_llm_cache_reserve and fvhd_llm_start first");
     if (int e = dec_status_error(c, "fvhd_llm_decode")) return e;
     if (int e = dec_embedding_error(c, "fvhd_llm_decode")) return e;
+    if (int e = beam_scoring_refusal(c, "fvhd_llm_decode")) return e;
     if (!token_ids)
         if (int e = stale_ids_error(c, "fvhd_llm_decode(token_ids = NULL)")) return e;
     const bool proc = processors_on(c);
@@ -505,7 +527,7 @@ int fvhd_llm_decode(fvhd_llm* c, const int64_t* token_ids, float* logits_out, in
     // holds this step's token)
     ChoiceArgs ch;
     ch.who = "decode"; ch.reduce_what = "decode argmax reduce"; ch.logits = r.logits; ch.R = gd ? B / 2 : B; ch.gate = c->status;
-    ch.step = true; ch.tok = token_ids; ch.n_add = 1; ch.ids_out = next_ids_out;
+    ch.step = true; ch.tok = token_ids; ch.n_add = 1; ch.ids_out = next_ids_out; ch.beam_rows = c->beam_scoring && logits_out;
     if (int e = choose_tokens(c, st, ch)) return e;
     c->sp_begun = false;                                         // a plain step: the token buffer of a lookup generation no longer describes the sequence
     if (token_ids) c->ids_stale = false;                         // the ids chosen on fed ids are these rows'
@@ -526,6 +548,9 @@ int fvhd_llm_extend(fvhd_llm* c, const void* embeds, int dtype, const uint8_t* k
                      std::to_string(c->dc_cap) + ")");
     if (c->hd != 64 && c->hd != 128) return lfail("fvhd_llm_extend: the attention over the cache needs head_dim 64 or 128");
     if (int e = dec_status_error(c, "fvhd_llm_extend")) return e;
+    if (c->beam_scoring)
+        return lfail("fvhd_llm_extend: beam scoring is on (fvhd_llm_set_beam_scoring) - a chunk's logits are not normalised; switch it off around "
+                     "fvhd_llm_extend");
     if (processors_on(c))
         return lfail("fvhd_llm_extend: logits processors are on (fvhd_llm_set_logits_processors) - their token history has no ids for an embedded "
                      "chunk; switch them off around fvhd_llm_extend");
@@ -597,13 +622,23 @@ int fvhd_llm_cache_gather(fvhd_llm* c, const int64_t* src_rows, int rows_in, int
     if (rows_in < 1 || rows_in > c->dc_batch || rows_out < 1 || rows_out > c->dc_batch)
         return lfail("fvhd_llm_cache_gather: rows_in and rows_out must be in [1, the batch of fvhd_llm_cache_reserve]");
     if (int e = dec_status_error(c, "fvhd_llm_cache_gather")) return e;
-    if (int e = row_state_refusal(c, "fvhd_llm_cache_gather", "reordered")) return e;
+    if (!c->beam_scoring)
+        if (int e = row_state_refusal(c, "fvhd_llm_cache_gather", "reordered")) return e;
     LLM_ON_DEVICE(c);
     DecCacheGatherArgs a;
     a.kc = c->kcache; a.vc = c->vcache; a.layers = c->L; a.batch = c->dc_batch; a.mask = c->mask; a.posv = c->posv; a.src = src_rows;
     a.rows_in = rows_in; a.rows_out = rows_out; a.nkv = c->nkv; a.hd = c->hd; a.cap = c->dc_cap; a.len = c->len; a.status = c->status;
     a.status_host = c->status_host_dev; a.ws = c->beam;
     LCHECK(fvhd_launch_dec_cache_gather((hipStream_t)stream, &a), "cache reorder");
+    if (c->beam_scoring && (processors_on(c) || constraint_on(c))) {
+        // the rows' histories and automaton states follow their K and V (two launches; the same src, the same error word)
+        DecHistGatherArgs h;
+        if (processors_on(c)) { h.hist = c->hist; h.seen = c->hist_seen; h.count = c->hist_count; }
+        if (constraint_on(c)) { h.states = c->con_state; h.flags = c->con_state + 64; }
+        h.src = src_rows; h.rows_in = rows_in; h.rows_out = rows_out; h.batch = c->dc_batch; h.cap = c->dc_cap; h.V = c->V; h.status = c->status;
+        h.status_host = c->status_host_dev; h.ws = c->beam_proc_hist;
+        LCHECK(fvhd_launch_dec_hist_gather((hipStream_t)stream, &h), "history and state reorder");
+    }
     c->run_batch = rows_out;
     c->sp_begun = false;                                         // a lookup generation belongs to the row it was begun on
     c->ids_stale = true;                                         // the reorder moves K, V, mask and positions, not last_ids
@@ -616,15 +651,15 @@ int fvhd_llm_beam_topk(fvhd_llm* c, const float* logits, const float* beam_score
     if (!c || !logits || !beam_scores || !cand_scores || !cand_index) return lfail("fvhd_llm_beam_topk: NULL argument");
     if (int e = guidance_refusal(c, "fvhd_llm_beam_topk", "beam search does not carry the pairing of conditional and unconditional rows")) return e;
     if (!c->beam) return lfail("fvhd_llm_beam_topk: no workspace - call fvhd_llm_beam_reserve first");
-    if (constraint_on(c))
+    if (constraint_on(c) && !c->beam_scoring)
         return lfail("fvhd_llm_beam_topk: a constraint is on (fvhd_llm_set_constraint) - beam search does not carry the rows' automaton states; "
                      "switch it off for beam search");
     if (!fvhd_dec_beam_topk_supported(groups, num_beams, keep, c->V) || ((uintptr_t)logits & 15))
         return lfail("fvhd_llm_beam_topk: needs groups >= 1, 2 <= num_beams <= 16, 1 <= keep <= 64, keep <= vocab, groups * num_beams <= 64, "
                      "vocab % 16 == 0, vocab <= 262144 and logits aligned to 16 bytes");
     LLM_ON_DEVICE(c);
-    LCHECK(fvhd_launch_dec_beam_topk((hipStream_t)stream, logits, beam_scores, groups, num_beams, keep, c->V, cand_scores, cand_index, c->beam_topk),
-           "beam top-K");
+    LCHECK(fvhd_launch_dec_beam_topk_mode((hipStream_t)stream, logits, beam_scores, groups, num_beams, keep, c->V, c->beam_scoring, cand_scores, cand_index,
+                                          c->beam_topk), "beam top-K");
     return 0;
 }
 
@@ -649,7 +684,7 @@ int fvhd_llm_beam_sample_topk(fvhd_llm* c, const float* logits, const float* bea
     if (int e = guidance_refusal(c, "fvhd_llm_beam_sample_topk", "beam search does not carry the pairing of conditional and unconditional rows")) return e;
     if (!c->dc) return lfail("fvhd_llm_beam_sample_topk: no KV cache - call fvhd_llm_cache_reserve first (the draw's counter is the cache length)");
     if (!c->beam_sample) return lfail("fvhd_llm_beam_sample_topk: no workspace - call fvhd_llm_beam_sample_reserve first");
-    if (constraint_on(c))
+    if (constraint_on(c) && !c->beam_scoring)
         return lfail("fvhd_llm_beam_sample_topk: a constraint is on (fvhd_llm_set_constraint) - beam search does not carry the rows' automaton states; "
                      "switch it off for beam search");
     if (!fvhd_dec_beam_topk_supported(groups, num_beams, keep, c->V) || ((uintptr_t)logits & 15))
@@ -662,7 +697,30 @@ int fvhd_llm_beam_sample_topk(fvhd_llm* c, const float* logits, const float* bea
     DecBeamSampleArgs a;
     a.logits = logits; a.scores = beam_scores; a.G = groups; a.K = num_beams; a.keep = keep; a.V = c->V; a.temperature = temperature; a.top_k = top_k;
     a.top_p = top_p; a.min_keep = min_keep; a.seed = seed; a.len = c->len; a.out_v = cand_scores; a.out_i = cand_index;
+    a.prenorm = c->beam_scoring;
     LCHECK(fvhd_launch_dec_beam_sample((hipStream_t)stream, &a, c->beam_sample), "beam sampling");
+    return 0;
+}
+
+// ---- beam search with processors and a constraint (include/fvhd.h "LLM beam search with processors") ----
+int fvhd_llm_set_beam_scoring(fvhd_llm* c, int on)
+{
+    if (!c) return lfail("fvhd_llm_set_beam_scoring: ctx is NULL");
+    if (!on) { c->beam_scoring = 0; return 0; }                  // (the scratch stays until fvhd_llm_cache_reserve or fvhd_llm_destroy)
+    if (!c->dc) return lfail("fvhd_llm_set_beam_scoring: no KV cache - call fvhd_llm_cache_reserve first (the reorder's scratch is sized for it)");
+    if (!fvhd_dec_beam_norm_supported(c->dc_batch, c->V))
+        return lfail("fvhd_llm_set_beam_scoring: the row normalisation needs vocab <= 262144");
+    if (!c->beam_proc) {
+        LLM_ON_DEVICE(c);
+        hipError_t he = hipDeviceSynchronize();                  // refused while a stream is being captured (like fvhd_llm_beam_reserve)
+        if (he != hipSuccess) return lhip("fvhd_llm_set_beam_scoring: hipDeviceSynchronize", he);
+        Arena a;
+        const size_t o_norm = a.take(fvhd_dec_beam_norm_ws_bytes()), o_hist = a.take(fvhd_dec_hist_gather_ws_bytes(c->dc_batch, c->dc_cap, c->V));
+        if ((he = hipMalloc((void**)&c->beam_proc, a.off)) != hipSuccess) { c->beam_proc = nullptr; return lhip("hipMalloc(beam scoring scratch)", he); }
+        c->beam_proc_norm = c->beam_proc + o_norm;
+        c->beam_proc_hist = c->beam_proc + o_hist;
+    }
+    c->beam_scoring = 1;
     return 0;
 }
 

@@ -239,6 +239,7 @@ void fvhd_llm_destroy(fvhd_llm* c)
     if (c->dc) (void)hipFree(c->dc);
     if (c->beam) (void)hipFree(c->beam);
     if (c->beam_sample) (void)hipFree(c->beam_sample);
+    if (c->beam_proc) (void)hipFree(c->beam_proc);
     if (c->spec) (void)hipFree(c->spec);
     if (c->spx) (void)hipFree(c->spx);
     if (c->score_ws) (void)hipFree(c->score_ws);

@@ -222,6 +222,7 @@ class Qwen2Generator:
     _do_sample = _verify_sampling = False                        # what set_sampling / set_verify_sampling last set
     _beam_reserved = False                                       # beam_reserve ran
     _beam_sample_reserved = False                                # beam_sample_reserve ran
+    _beam_scoring = False                                        # what set_beam_scoring last set
     _spec_rows = 0                                               # the largest row count this generator asked of spec_reserve
     _spec_logits = _spec_ids = _spec_emitted = None              # verify()'s output buffers, made on first use
     _last_chunk = _last_mask = _last_call = None                 # the rows, mask and call token of the last start() / extend() (`score_last`)
@@ -454,11 +455,13 @@ class Qwen2Generator:
         """cache row r (K / V of every layer, mask, next position) = old row src_rows[r] (`fvhd_llm_cache_gather`); the following steps run
         on len(src_rows) rows.  src_rows: int64 on the device, entries in [0, rows_in).  Capture-safe after `beam_reserve`.  The chosen ids are
         not reordered: continue with extend(), or step() with explicit ids - step(None) and verify() are refused.  Not with logits
-        processors: their token history is not reordered."""
-        if self._processors is not None:
-            raise ValueError("cache_gather: logits processors are set (set_logits_processors) - their token history is not reordered; "
-                             "clear them with set_logits_processors()")
-        self._constraint_refusal("cache_gather", "the rows' automaton states are not reordered")
+        processors or a constraint (their token history and automaton states are not reordered) - unless `set_beam_scoring(True)`, under
+        which both follow their rows."""
+        if not self._beam_scoring:
+            if self._processors is not None:
+                raise ValueError("cache_gather: logits processors are set (set_logits_processors) - their token history is not reordered; "
+                                 "clear them with set_logits_processors()")
+            self._constraint_refusal("cache_gather", "the rows' automaton states are not reordered")
         self._guidance_refusal("cache_gather", "a cache reorder would break the pairing of rows g and G + g")
         if src_rows.dtype != torch.long or src_rows.device != self.device or src_rows.dim() != 1 or not src_rows.is_contiguous():
             raise ValueError(f"src_rows must be a contiguous 1-D int64 tensor on {self.device}")
@@ -483,6 +486,20 @@ class Qwen2Generator:
         with torch.cuda.device(self.device):
             _lib.check(_lib.beam_lib().fvhd_llm_beam_topk(self.pre._h, _lib.ptr(logits), _lib.ptr(beam_scores), G, K, int(keep), _lib.ptr(out_scores),
                                                           _lib.ptr(out_index), _lib.stream_ptr(self.device)), "fvhd_llm_beam_topk")
+
+    def set_beam_scoring(self, on: bool) -> None:
+        """transformers' order under beams, from now on (`fvhd_llm_set_beam_scoring`): start() / step() with logits=True return
+        log_softmax(logits) with the processors and the constraint applied to THAT, `cache_gather` carries the rows' token histories and
+        automaton states, and `beam_topk` / `beam_sample_topk` add the beam scores to the rows as they are.  Switching it on allocates
+        (once per generator) and synchronises; a captured step keeps what it was captured with.  Not with guidance, logprobs or extend()."""
+        if not on and not self._beam_scoring and not _lib.has("beam_processors"):
+            return                                               # off on a library that has none: nothing to say
+        if on and torch.cuda.is_current_stream_capturing():
+            raise ValueError("set_beam_scoring: refused while a stream is being captured (switching it on allocates and synchronises) - set it "
+                             "before capturing; a captured step keeps the setting it was captured with")
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.beam_processors_lib().fvhd_llm_set_beam_scoring(self.pre._h, int(bool(on))), "fvhd_llm_set_beam_scoring")
+        self._beam_scoring = bool(on)
 
     def beam_sample_reserve(self) -> None:
         """the workspace of `beam_sample_topk` (`fvhd_llm_beam_sample_reserve`; once per generator, synchronises)"""
@@ -752,7 +769,8 @@ class Qwen2Generator:
         `ml_fastvlm_amd.logits_processors`): repetition_penalty != 1, no_repeat_ngram_size >= 1, min_new_tokens >= 1 with eos_token_id (at
         most 16 ids), suppress_tokens (at most 256 ids); the defaults switch them off.  The history they read is the tokens fed to the
         steps since start() - set them before start().  With any of them on, the logits that start() / step() return are the processed
-        scores.  Synchronises; a captured step keeps the settings it was captured with.  Not for beam_search."""
+        scores.  Synchronises; a captured step keeps the settings it was captured with.  Under beams they are
+        keywords of `beam_search`, which sets them for its run; set here they make beam_search raise."""
         from .logits_processors import normalize
         cfg = normalize(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, suppress_tokens, vocab=self.pre.vocab)
         if cfg is None and self._processors is None and not _lib.has("processors"):
@@ -775,7 +793,8 @@ class Qwen2Generator:
         on the ids fed to the steps.  start_states: None (state 0 for every row), an int, or one state per row (-1 = that row is
         unconstrained; rows beyond the list are unconstrained).  start() / extend() put the rows back at their start states - set it before start().  None
         switches it off.  With it on, the logits start() / step() return are the masked scores.  Synchronises; a captured step keeps the
-        tables it was captured with.  Not for beam_search, verify / lookup_greedy, rewind or cache_gather."""
+        tables it was captured with.  Not for verify / lookup_greedy, rewind or cache_gather; under beams it is the `constraint=` keyword of
+        `beam_search`, which sets it for its run - set here it makes beam_search raise."""
         from .constraints import TokenAutomaton
         if torch.cuda.is_current_stream_capturing():             # the library's call synchronises the device, which would invalidate the capture
             raise ValueError("set_constraint: refused while a stream is being captured (it synchronises the device and uploads tables) - set the "
@@ -1077,7 +1096,8 @@ class Qwen2Generator:
                     num_beams: int = 4, max_new_tokens: int = 256, length_penalty: float = 1.0, early_stopping: Union[bool, str] = False,
                     num_return_sequences: int = 1, eos_token_id: Union[None, int, Sequence[int]] = None, pad_token_id: Optional[int] = None,
                     graph: bool = True, poll_every: int = 16, return_scores: bool = False, do_sample: bool = False, temperature: float = 1.0,
-                    top_k: int = 50, top_p: float = 1.0, seed: Optional[int] = None):
+                    top_k: int = 50, top_p: float = 1.0, seed: Optional[int] = None, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
+                    min_new_tokens: int = 0, suppress_tokens: Optional[Sequence[int]] = None, constraint=None, constraint_start=None):
         """transformers' beam search (`GenerationMixin._beam_search`) on the library's steps -> new tokens
         [G * num_return_sequences, n], with return_scores also the `sequences_scores` [G * num_return_sequences]: what
         generate(inputs_embeds=..., num_beams=K) returns - per prompt its best finished hypotheses in descending score order, finished rows
@@ -1091,14 +1111,26 @@ class Qwen2Generator:
         softmax of log_softmax(logits) / temperature + beam scores behind top-k / top-p, with min_tokens_to_keep = n_eos + 1 (2 without
         an EOS id) as transformers sets it under beams; top_k = 50 is transformers' default.  seed None: as in `sample`.  The same seed
         gives the same tokens and scores, eager or graph; the draws are not torch.multinomial's.  With do_sample=False the four settings
-        are not read and the call enqueues what it did."""
+        are not read and the call enqueues what it did.
+        repetition_penalty / no_repeat_ngram_size / min_new_tokens (with eos_token_id) / suppress_tokens / constraint (with
+        constraint_start, one state for all or one per PROMPT): transformers' processors under beams - applied to log_softmax(logits),
+        every beam's history and automaton state following its parent (`set_beam_scoring`, `set_logits_processors`, `set_constraint`: set
+        for this run and restored after it, on exceptions too).  The history is the tokens generated since the prompt, as in `greedy`.
+        With all of them off the call enqueues what it did; processors or a constraint set OUTSIDE the call are still refused."""
         from .beam import BeamSearchState
+        from .logits_processors import normalize
         if num_beams < 2:
             raise ValueError(f"beam_search needs num_beams >= 2 (got {num_beams}): one beam is `greedy`")
+        processors = (repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, suppress_tokens)
+        proc_on = normalize(*processors) is not None              # (the ids against the vocabulary: below, with the other checks of the run)
+        if constraint is None and constraint_start is not None:
+            raise ValueError("constraint_start is given without a constraint")
+        processed = proc_on or constraint is not None
         if self._processors is not None:
             raise ValueError("beam_search: logits processors are set (set_logits_processors) - they are not implemented under beam search; "
-                             "clear them with set_logits_processors()")
-        self._constraint_refusal("beam_search", "beam search does not carry the rows' automaton states")
+                             "clear them with set_logits_processors()" + (" and pass them as keywords of beam_search" if processed else ""))
+        self._constraint_refusal("beam_search", "beam search does not carry the rows' automaton states" +
+                                 (" of a constraint set outside the call (pass it as the `constraint` keyword)" if processed else ""))
         self._guidance_refusal("beam_search", "beam search does not take guidance")
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be >= 1")
@@ -1106,6 +1138,8 @@ class Qwen2Generator:
             _sampling_refusal("beam_search", temperature, top_k, top_p)
             if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int)):
                 raise ValueError(f"beam_search: seed must be None or an int, got {seed!r}")
+        if proc_on:
+            normalize(*processors, vocab=self.pre.vocab)
         G, T = inputs_embeds.shape[:2]
         K = int(num_beams)
         rows = G * K
@@ -1131,29 +1165,33 @@ class Qwen2Generator:
                 self.beam_sample_topk(*a, **drawn)
         cand_scores = torch.zeros((G, state.keep), device=dev, dtype=torch.float32)
         cand_index = torch.zeros((G, state.keep), device=dev, dtype=torch.long)
-        lg, _ = self.start(inputs_embeds, attention_mask, position_ids, logits=True)
-        # the first step: the K rows of a prompt are equal (transformers forwards K copies of the prompt; only beam 0 has score 0)
-        logits = self._logits[:rows]
-        logits.copy_(lg.repeat_interleave(K, dim=0))
-        self.cache_gather(torch.arange(rows, device=dev, dtype=torch.long) // K, G)
-        topk(logits, state.running_beam_scores, state.keep, cand_scores, cand_index)
-        state.update(cand_scores, cand_index)
-
-        def one_step():
-            self.cache_gather(state.parent, rows)
-            step_logits, _ = self.step(state.fed_ids, logits=True)
-            topk(step_logits, state.running_beam_scores, state.keep, cand_scores, cand_index)
+        # the processed run: beam scoring outermost, then the processors and the constraint, each restored behind the run (`_for_run`)
+        with self._for_run(processed, self.set_beam_scoring, (True,), (False,)), \
+                self._for_run(proc_on, self.set_logits_processors, processors), \
+                self._for_run(constraint is not None, self.set_constraint, (constraint, constraint_start)):
+            lg, _ = self.start(inputs_embeds, attention_mask, position_ids, logits=True)
+            # the first step: the K rows of a prompt are equal (transformers forwards K copies of the prompt; only beam 0 has score 0)
+            logits = self._logits[:rows]
+            logits.copy_(lg.repeat_interleave(K, dim=0))
+            self.cache_gather(torch.arange(rows, device=dev, dtype=torch.long) // K, G)
+            topk(logits, state.running_beam_scores, state.keep, cand_scores, cand_index)
             state.update(cand_scores, cand_index)
 
-        steps = max_new_tokens - 1
-        run_step = self._captured(one_step, graph and steps > 0)
-        done = 0
-        while done < steps:
-            if state.finished():                                 # host sync once per poll_every steps
-                break
-            for _ in range(min(poll_every, steps - done)):
-                run_step()
-            done += min(poll_every, steps - done)
-        self._length = T + done
-        tokens, scores = state.result()
-        return (tokens, scores) if return_scores else tokens
+            def one_step():
+                self.cache_gather(state.parent, rows)
+                step_logits, _ = self.step(state.fed_ids, logits=True)
+                topk(step_logits, state.running_beam_scores, state.keep, cand_scores, cand_index)
+                state.update(cand_scores, cand_index)
+
+            steps = max_new_tokens - 1
+            run_step = self._captured(one_step, graph and steps > 0)
+            done = 0
+            while done < steps:
+                if state.finished():                                 # host sync once per poll_every steps
+                    break
+                for _ in range(min(poll_every, steps - done)):
+                    run_step()
+                done += min(poll_every, steps - done)
+            self._length = T + done
+            tokens, scores = state.result()
+            return (tokens, scores) if return_scores else tokens

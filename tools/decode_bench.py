@@ -8,6 +8,8 @@ captured graph and called eagerly, against the stock `transformers` decode loop 
     python tools/decode_bench.py --weights mxfp4 ...                            (as MXFP4: e2m1 codes + one scale byte per 32 elements)
     python tools/decode_bench.py --num-beams 4 --hidden 896 3584 --batch 1 16   (beam search: --batch prompts x K beams per step)
     python tools/decode_bench.py --processors --hidden 896 --batch 1 64         (logits processors on against off, greedy and sampled)
+    python tools/decode_bench.py --num-beams 4 --processors --hidden 896 3584 --batch 1 16   (the beam step under repetition_penalty 1.2, no_repeat_ngram_size 3)
+    python tools/decode_bench.py --num-beams 4 --constraint --hidden 896 3584 --batch 1 16   (the beam step under a token automaton; both flags combine)
     python tools/decode_bench.py --lookup --hidden 896 3584 --rows 4 8 16       (prompt-lookup decoding: the verify step at one sequence)
     python tools/decode_bench.py --lookup --trace-steps 16 --hidden 896 --rows 8    (eager verify steps only: the program of a kernel trace)
     python tools/decode_bench.py --logprobs 0 5 16 --hidden 896 3584 --batch 1 64   (log-probabilities of the chosen tokens inside the step)
@@ -791,11 +793,18 @@ def _graph_of(fn, dev):
     return graph
 
 
+BEAM_PROCESSORS = dict(repetition_penalty=1.2, no_repeat_ngram_size=3)      # --num-beams with --processors: the usual caption settings
+
+
 @torch.no_grad()
 def measure_beam(llm, pre, groups: int, K: int, prompt: int, new: int, dev, repeats: int = 1, stock: bool = True, weights: str = "bf16",
-                 do_sample: bool = False) -> dict:
+                 do_sample: bool = False, processors: bool = False, constraint: bool = False) -> dict:
     """do_sample: beam-search SAMPLING at predict.py's settings (temperature 0.2, top_k 50, top_p off): `beam_sample_topk` in place of
-    `beam_topk` in the step, and the stock loop run with do_sample=True"""
+    `beam_topk` in the step, and the stock loop run with do_sample=True.  processors: the step under BEAM_PROCESSORS
+    (`Qwen2Generator.set_beam_scoring` + `set_logits_processors`: the rows normalised, the processors' launch, the histories carried by the
+    reorder, the top-K on the rows as they are), and the stock loop with the same settings.  constraint: the step under a one-state automaton that
+    allows every other id (`set_beam_scoring` + `set_constraint`: the states carried by the reorder); the stock loop is then left out (its
+    `prefix_allowed_tokens_fn` is a host callback per row per step)"""
     from ml_fastvlm_amd.beam import BeamSearchState
     from ml_fastvlm_amd.qwen2_decode import Qwen2Generator
     cfg = llm.config
@@ -808,6 +817,18 @@ def measure_beam(llm, pre, groups: int, K: int, prompt: int, new: int, dev, repe
            "new_tokens": new, "weights": weights, "do_sample": do_sample}
     gen.beam_reserve()
     gen._set_greedy()
+    if processors:
+        res["processors"] = BEAM_PROCESSORS
+        gen.set_beam_scoring(True)
+        gen.set_logits_processors(**BEAM_PROCESSORS)
+    if constraint:
+        from ml_fastvlm_amd.constraints import TokenAutomaton
+        ids = list(range(0, V, 2))
+        res["constraint_edges"] = len(ids)
+        gen.set_beam_scoring(True)
+        gen.set_constraint(TokenAutomaton([0, len(ids)], ids, [0] * len(ids), V))
+        stock = False
+    processors = processors or constraint                   # (from here on: "the step is the processed one")
     keep = 2 * K
     topk = gen.beam_topk
     if do_sample:
@@ -862,7 +883,10 @@ def measure_beam(llm, pre, groups: int, K: int, prompt: int, new: int, dev, repe
     res["rows_moved_at_mid_search"] = int((parent != torch.arange(rows, device=dev)).sum())
     worst = torch.roll(torch.arange(rows, device=dev), 1)
     src = parent.clone()
-    parts = {"plain_step_with_logits": lambda: gen.step(st.fed_ids, logits=True), "plain_step": lambda: gen.step(st.fed_ids, logits=False),
+    # under `processors` the step is not the plain one: with logits it holds the normalisation and the processors' launch, without them the
+    # processors' launch alone - named for what they are, and no "added over the plain step" is derived (the plain run of the same build has it)
+    step = "processed_step" if processors else "plain_step"
+    parts = {f"{step}_with_logits": lambda: gen.step(st.fed_ids, logits=True), step: lambda: gen.step(st.fed_ids, logits=False),
              "topk": lambda: topk(gen._logits[:rows], st.running_beam_scores, keep, cand_s, cand_i),
              "bookkeeping": lambda: st.update(cand_s, cand_i), "gather": lambda: gen.cache_gather(src, rows)}
     for name, fn in parts.items():
@@ -873,8 +897,9 @@ def measure_beam(llm, pre, groups: int, K: int, prompt: int, new: int, dev, repe
                 for _ in range(new // 2):                   # the cache at its mean length
                     full.replay()
                 src.copy_(m)
-            res[f"{name}{tag}_ms"] = round(_ms_per(graph.replay, new - 1 if name.startswith("plain") else new // 2, dev), 4)
-    res["added_ms_over_plain_step"] = round(res["beam_step_ms"] - res["plain_step_ms"], 4)
+            res[f"{name}{tag}_ms"] = round(_ms_per(graph.replay, new - 1 if name.startswith(step) else new // 2, dev), 4)
+    if not processors:
+        res["added_ms_over_plain_step"] = round(res["beam_step_ms"] - res["plain_step_ms"], 4)
     nkv, hd = cfg.num_key_value_heads, hidden // cfg.num_attention_heads
     res["logits_bytes"] = rows * V * 4
     res["kv_bytes_moved_twice_if_every_row_moves"] = int(2 * 2 * cfg.num_hidden_layers * rows * nkv * (prompt + new / 2) * hd * 2)
@@ -882,6 +907,8 @@ def measure_beam(llm, pre, groups: int, K: int, prompt: int, new: int, dev, repe
         ref_kw = dict(inputs_embeds=emb, attention_mask=mask, num_beams=K, max_new_tokens=new, do_sample=False, eos_token_id=None, pad_token_id=0)
         if do_sample:
             ref_kw.update(do_sample=True, temperature=0.2, top_k=50, top_p=1.0)
+        if "processors" in res:
+            ref_kw.update(BEAM_PROCESSORS)
         llm.generation_config.eos_token_id = None           # (random weights: no early end)
         llm.generate(**dict(ref_kw, max_new_tokens=4))      # lazy initialisation stays out of the timing
         torch.cuda.synchronize(dev)
@@ -897,6 +924,10 @@ def measure_beam(llm, pre, groups: int, K: int, prompt: int, new: int, dev, repe
         torch.cuda.synchronize(dev)
         res["stock_transformers_beam_ms_per_step"] = round((a.elapsed_time(b) - first) / (new - 1), 4)
         res["speedup_beam_step_vs_stock"] = round(res["stock_transformers_beam_ms_per_step"] / res["beam_step_ms"], 2)
+    if processors:
+        gen.set_logits_processors()
+        gen.set_constraint()
+        gen.set_beam_scoring(False)
     del gen
     return res
 
@@ -997,7 +1028,7 @@ def main():
         print(json.dumps({"tool": "decode_bench", "mode": "lookup_sample", "device": torch.cuda.get_device_name(dev),
                           "library_version": _lib.lookup_sample_lib().fvhd_version(), "results": rows}))
         return
-    if a.constraint:
+    if a.constraint and not a.num_beams:
         from tools.ttft import build_llm
         from ml_fastvlm_amd import _lib
         from ml_fastvlm_amd.qwen2_prefill import Qwen2Prefill
@@ -1052,7 +1083,8 @@ def main():
             llm = build_llm(h, dev)
             pre = Qwen2Prefill.from_hf(llm, weights=a.weights)
             for b in a.batch:
-                rows.append(measure_beam(llm, pre, b, a.num_beams, a.prompt, a.new, dev, repeats=a.repeats, stock=not a.no_stock, weights=a.weights, do_sample=a.beam_sample))
+                rows.append(measure_beam(llm, pre, b, a.num_beams, a.prompt, a.new, dev, repeats=a.repeats, stock=not a.no_stock, weights=a.weights, do_sample=a.beam_sample,
+                                         processors=a.processors, constraint=a.constraint))
                 torch.cuda.empty_cache()
             del pre, llm
             torch.cuda.empty_cache()
